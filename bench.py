@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """The bench line of BASELINE.json's metric, "queries/sec + p50 retrieve+rerank latency, 1536-d top-k=20, 1/2/4/8 GPU".
 
-Top level (`value`, `ms_per_step`, `p50_single_query_latency_ms`, `roofline`, `cpu_baseline`) = BASELINE.json configs[3], the
-configuration the metric is quoted on: hybrid top-100 (dense + BM25 + RRF) -> ms-marco-MiniLM-L-6 cross-encoder -> top-20,
-256-query batches over a 1M x 1536-d corpus, inputs resident in HBM. A "step" = one 256-query batch answered end to end.
-The same line carries the lighter configurations as blocks with their own `roofline` / `cpu_baseline`: `dense` (configs[1]:
-dense cosine top-20, 1024-query batches), on one GPU `hybrid` (configs[2]) and `agent_latency` (the calls the reference agent
-makes), and `shard_12p5M` (configs[4] at its real per-GPU size: 12.5M rows + postings + token store + cross-encoder on EVERY
-rank, N = 1 included; weak scaling).
+Top level (`value`, `ms_per_step`) = BASELINE.json configs[3], the configuration the metric is quoted on: hybrid top-100
+(dense + BM25 + RRF) -> ms-marco-MiniLM-L-6 cross-encoder -> top-20, 256-query batches over a 1M x 1536-d corpus, inputs
+resident in HBM. A "step" = one 256-query batch answered end to end.
 
-  python bench.py --gpus N --steps K --warmup W
+A plain run does only that: set-up, `--warmup` untimed and `--steps` timed batches, the line. `--full` adds everything else
+the line has carried: the headline's p50 latencies, `roofline` and `cpu_baseline`, and the lighter configurations as blocks
+with their own `roofline` / `cpu_baseline`: `dense` (configs[1]: dense cosine top-20, 1024-query batches), on one GPU `hybrid`
+(configs[2]) and `agent_latency` (the calls the reference agent makes), and `shard_12p5M` (configs[4] at its real per-GPU
+size: 12.5M rows + postings + token store + cross-encoder on EVERY rank, N = 1 included; weak scaling).
+`--dump-outputs DIR` writes what the last timed batch returned (ids, scores, logits, candidates) as DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
        or just `python bench.py --gpus N`: with WORLD_SIZE unset the script starts that launcher itself as a child process
        (before anything touches a GPU) and relays rank 0's JSON line.
@@ -211,6 +215,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed 256-query retrieve + rerank batches (the headline); the dense block times 20 of its own")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole line: the headline's latencies, roofline and CPU baseline, and the dense / hybrid / agent_latency / "
+                         "shard_12p5M blocks (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed headline batch to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dense-steps", type=int, default=20, help="timed 1024-query batches of the `dense` block (configs[1])")
     ap.add_argument("--rows", type=int, default=1_000_000, help="total corpus rows (sharded over the ranks)")
@@ -243,6 +252,10 @@ def main():
     ap.add_argument("--vocab", type=int, default=100_000, help="--mode hybrid: BM25 vocabulary size (> 100000 selects the "
                     "truncated-Zipf generator bench_modes.zipf_postings_gpu)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mode != "line" or args.dense_only or args.corpus != "iid"):
+        ap.error("--dump-outputs writes the headline's outputs: it needs --mode line, no --dense-only and --corpus iid")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -271,6 +284,8 @@ def main():
             dist.init_process_group("nccl", device_id=device)
         else:
             dist.init_process_group(backend)
+    if not (args.full or args.dense_only or args.corpus != "iid"):
+        return headline_line(args, rank, world, local_rank, device, backend)
 
     from optimized_rag_amd import RagEngine
     Q, k = args.queries, args.k
@@ -379,7 +394,7 @@ def main():
     def phase(p):
         state["phase"] = p
 
-    deadline = float(os.environ.get("RAG_BENCH_DEADLINE", os.environ.get("RAG_BENCH_SHARD_DEADLINE", "900")))
+    deadline = bench_deadline()
 
     def give_up():
         if rank == 0:
@@ -415,6 +430,9 @@ def main():
         try:
             blocks["headline"] = BS.headline_rerank(eng, device, args.rows, rank=rank, world=world, steps=args.steps, warmup=args.warmup,
                                                     cpu_baseline=not args.no_cpu_baseline and world == 1, phase=phase)
+            outputs = blocks["headline"].pop("outputs")
+            if rank == 0 and args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
         except Exception as e:
             blocks["headline"] = {"error": f"{type(e).__name__}: {e}"}
         # ---- configs[4] at its real per-GPU size (12.5M rows on every rank; weak scaling), N = 1 included
@@ -436,6 +454,55 @@ def main():
         emit_line(args, line, blocks)
     if world > 1:
         dist.destroy_process_group()
+
+
+def bench_deadline():
+    return float(os.environ.get("RAG_BENCH_DEADLINE", os.environ.get("RAG_BENCH_SHARD_DEADLINE", "900")))
+
+
+def headline_line(args, rank, world, local_rank, device, backend):
+    """A plain run: only what the headline figure needs - the configs[3] set-up, `--warmup` untimed and `--steps` timed
+    retrieve + rerank batches, the outputs of the last timed batch (--dump-outputs), the line. As in the full line, a part that
+    stalls (a rank failing inside a collective) ends every rank with a NON-ZERO exit code and a line that names the phase."""
+    import threading
+    import bench_shard as BS
+    from optimized_rag_amd import RagEngine
+    assert args.rows % (CHUNK_ROWS * world) == 0, "rows must be a multiple of 125000 * n_gpus"
+    state = {"phase": "start"}
+    deadline = bench_deadline()
+
+    def give_up():
+        if rank == 0:
+            print(json.dumps({**headline_fields(args, world, None, None), "value": None, "ms_per_step": None,
+                              "error": f"no result within {deadline:.0f} s (RAG_BENCH_DEADLINE); stalled in phase '{state['phase']}'"}),
+                  flush=True)
+        sys.stdout.flush()
+        os._exit(3)
+
+    watchdog = threading.Timer(deadline, give_up)
+    watchdog.daemon = True
+    watchdog.start()
+    eng = RagEngine(dim=DIM, device=local_rank)
+    state["phase"] = "choose_exchange"
+    comm = choose_exchange(eng, rank, world, device, backend, args.torch_comm)
+    head = BS.headline_rerank(eng, device, args.rows, rank=rank, world=world, steps=args.steps, warmup=args.warmup, cpu_baseline=False,
+                              phase=lambda p: state.update(phase=p), full=False)
+    watchdog.cancel()
+    if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, head["outputs"])
+        print(json.dumps({**headline_fields(args, world, comm, None), "value": head["value"], "ms_per_step": head["ms_per_step"]}),
+              flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, outputs):
+    """`outputs`: name -> host array of the last timed batch. float32 stays float32, everything else (int64 ids, float64 scores)
+    is written as float64, which holds every id below 2**53 exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def dense_block_dict(args, world, n_local, tenant, gemm_ms, gemm_launches, dt, p50, lat1, stats, planted_hit, comm, host_corpus, queries,
@@ -540,19 +607,7 @@ def emit_line(args, line, blocks):
         if head is not None:
             out["headline_error"] = head["error"]
     else:
-        out = {"metric": "queries/sec + p50 retrieve+rerank latency, 1536-d top-k=20", "value": head["value"], "unit": "queries/sec",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
-               "scaling": "strong", "vs_baseline": None,
-               "dtype": "f16 MFMA + block-scaled bf8 MFMA corrections (fp32 acc) in the cross-encoder; f16 MFMA pass + f64 rescore in the "
-                        "dense leg; f64 BM25 / RRF",
-               "data": "synthetic",
-               "config": {"workload": f"{args.rows} docs x {DIM}-d + BM25 postings (2M-term Zipf vocabulary) + 224-token passage store; batch=256 "
-                                      f"queries: dense top-100 + BM25 top-100 + RRF -> top-100 -> ms-marco-MiniLM-L-6 cross-encoder (L=256, "
-                                      f"25,600 pairs, mean {head['mean_pair_tokens']:.0f} tokens, seeded weights) -> top-20 (BASELINE.json configs[3])",
-                          "corpus_rows": args.rows, "rows_per_gpu": args.rows // world, "batch_queries": 256, "pool": 100, "k": 20,
-                          "parallelism": "one rag_retrieve_rerank_dev call per batch" if world == 1 else
-                                         f"row-sharded x{world}: per-shard lists, one all-gather, device fusion, pairs split over the ranks, one gather of the logits",
-                          "exchange": line["exchange"]},
+        out = {**headline_fields(args, world, line["exchange"], head["mean_pair_tokens"]), "value": head["value"], "ms_per_step": head["ms_per_step"],
                "p50_batch_latency_ms": head["p50_batch_latency_ms"], "p50_single_query_latency_ms": head["p50_single_query_latency_ms"],
                "pairs_per_sec": head["pairs_per_sec"], "sanity": head["sanity"], "hbm_used_gb": head["hbm_used_gb"],
                "roofline": head["roofline"], "cpu_baseline": head.get("cpu_baseline")}
@@ -564,6 +619,25 @@ def emit_line(args, line, blocks):
         if name in blocks:
             out[name] = blocks[name]
     print(json.dumps(out), flush=True)
+
+
+def headline_fields(args, world, exchange, mean_pair_tokens):
+    """The fields of the line that describe the headline measurement, the same in a plain and a --full run (the figures
+    `value` / `ms_per_step` are the caller's). `mean_pair_tokens` is measured by --full runs only."""
+    mean = "" if mean_pair_tokens is None else f"mean {mean_pair_tokens:.0f} tokens, "
+    return {"metric": "queries/sec + p50 retrieve+rerank latency, 1536-d top-k=20", "value": None, "unit": "queries/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None,
+            "dtype": "f16 MFMA + block-scaled bf8 MFMA corrections (fp32 acc) in the cross-encoder; f16 MFMA pass + f64 rescore in the "
+                     "dense leg; f64 BM25 / RRF",
+            "data": "synthetic",
+            "config": {"workload": f"{args.rows} docs x {DIM}-d + BM25 postings (2M-term Zipf vocabulary) + 224-token passage store; batch=256 "
+                                   f"queries: dense top-100 + BM25 top-100 + RRF -> top-100 -> ms-marco-MiniLM-L-6 cross-encoder (L=256, "
+                                   f"25,600 pairs, {mean}seeded weights) -> top-20 (BASELINE.json configs[3])",
+                       "corpus_rows": args.rows, "rows_per_gpu": args.rows // world, "batch_queries": 256, "pool": 100, "k": 20,
+                       "parallelism": "one rag_retrieve_rerank_dev call per batch" if world == 1 else
+                                      f"row-sharded x{world}: per-shard lists, one all-gather, device fusion, pairs split over the ranks, one gather of the logits",
+                       "exchange": exchange}}
 
 
 def launcher_selftest(args):

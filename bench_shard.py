@@ -229,13 +229,15 @@ def token_lengths(rows, total_rows, device, vocab_size, with_tokens=False):
     return lens, toks
 
 
-def headline_rerank(eng, device, rows_total, rank=0, world=1, steps=20, warmup=3, cpu_baseline=True, pool=100, k=20, L_pair=256, phase=None):
+def headline_rerank(eng, device, rows_total, rank=0, world=1, steps=20, warmup=3, cpu_baseline=True, pool=100, k=20, L_pair=256, phase=None,
+                    full=True):
     """BASELINE.json configs[3], the configuration its metric is quoted on: hybrid top-100 -> MiniLM-L-6 cross-encoder -> top-20,
     256-query batches over a `rows_total` x 1536-d corpus, row-sharded over `world` ranks (strong scaling: the same corpus and
     batch at every N; one rank: the one-call entry rag_retrieve_rerank_dev, several: ShardedPipeline - per-shard candidate lists,
     one all-gather, fusion, the 25,600 pairs split over the ranks, one gather of the logits). bench.py's timing contract:
     `warmup` untimed batches, exactly `steps` timed ones between barrier + synchronize, MAX over ranks. Returns the fields of the
-    bench line (value, ms_per_step, latencies, roofline, cpu_baseline)."""
+    bench line (value, ms_per_step, the last timed batch's `outputs` as host arrays; with `full` also latencies, roofline,
+    cpu_baseline). Without `full` nothing runs after the timed batches and the profiling spans stay off."""
     import torch.distributed as dist
     from optimized_rag_amd.sharded import ShardedPipeline
     say = phase or (lambda s: None)
@@ -251,13 +253,23 @@ def headline_rerank(eng, device, rows_total, rank=0, world=1, steps=20, warmup=3
         return pipe.retrieve_rerank(q[:nq].contiguous(), st["ptr_d"][:nq + 1].contiguous(), st["terms_d"], st["q_tok_d"][:nq].contiguous(),
                                     st["q_len_d"][:nq].contiguous(), pool, k, L_pair=L_pair)
 
+    last = [None]
+
+    def timed_step():
+        last[0] = run()
+
     say("headline: warmup")
     for _ in range(max(1, warmup)):
         run()
     torch.cuda.synchronize()
-    eng.set_profiling(True)
+    if full:
+        eng.set_profiling(True)
     say("headline: timed steps")
-    t = BM.timed_all_ranks(run, steps, 0, world)
+    t = BM.timed_all_ranks(timed_step, steps, 0, world)
+    # what a caller of the timed path receives from the last timed batch, copied before anything else reuses the buffers
+    outputs = dict(zip(("ids", "scores", "logits", "candidates"), (x.cpu().numpy() for x in last[0])))
+    if not full:
+        return {"value": round(Q / t, 2), "ms_per_step": round(t * 1e3, 3), "outputs": outputs}
     ce_ms, ce_spans = eng.stage_kernel_ms(2)
     eng.set_profiling(False)
     say("headline: latencies")
@@ -289,7 +301,7 @@ def headline_rerank(eng, device, rows_total, rank=0, world=1, steps=20, warmup=3
     fwd_ms = ce_ms / max(1, ce_spans)
     ce_tf = flops / world / (fwd_ms * 1e-3) / 1e12            # this rank's forward scores 1 / world of the pairs
     out = {
-        "value": round(Q / t, 2), "ms_per_step": round(t * 1e3, 3),
+        "value": round(Q / t, 2), "ms_per_step": round(t * 1e3, 3), "outputs": outputs,
         "p50_batch_latency_ms": round(float(np.median(lat_b)), 3), "p50_single_query_latency_ms": round(float(np.median(lat_1)), 3),
         "pairs_per_sec": round(Q * pool / t, 1), "mean_pair_tokens": round(float(plen.mean()), 1),
         "roofline": {"bound": "mfma", "kernel": "cross-encoder forward of one batch on rank 0 (mx_gemm_kernel<qkv | ln | gelu> + ce_attention_kernel + "

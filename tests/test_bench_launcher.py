@@ -82,7 +82,9 @@ for name, fail, mode in (("one_rank_fails", 1, "raise"), ("one_rank_hangs", 1, "
     out[name] = dict(label=label, inited=e.inited, destroyed=e.destroyed, probe_inited=probes[0].inited, probe_destroyed=probes[0].destroyed,
                      seconds=time.time() - t0)
 out["torch_comm"] = bench.choose_exchange(FakeEngine(rank, -1), rank, world, torch.device("cpu"), "nccl", torch_comm=True)
-print("RANK%d %s" % (rank, json.dumps(out)), flush=True)
+# one file per rank: the ranks share the launcher's stdout, where their lines (and gloo's own messages) can interleave
+with open(os.path.join(sys.argv[2], "rank%d.json" % rank), "w") as f:
+    json.dump(out, f)
 dist.destroy_process_group()
 os._exit(0)                                      # a probe thread may still sleep inside its fake rendezvous
 """
@@ -103,13 +105,14 @@ def test_one_rank_failing_or_hanging_comm_init_sends_every_rank_to_the_torch_pat
     s.close()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), str(script), ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=300)
+                        "--master-port", str(port), str(script), ROOT, str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     res = {}
-    for ln in p.stdout.splitlines():
-        if ln.startswith("RANK"):
-            res[int(ln[4])] = json.loads(ln[6:])
+    for r in (0, 1):
+        path = tmp_path / ("rank%d.json" % r)
+        if path.exists():
+            res[r] = json.loads(path.read_text())
     assert set(res) == {0, 1}
     for r in (0, 1):
         for case in ("one_rank_fails", "one_rank_hangs"):

@@ -1,6 +1,6 @@
 """GPU: `python bench.py --gpus 2` end to end on ONE GPU (both ranks open cuda:0, collectives through gloo: RAG_BENCH_BACKEND=gloo),
 started exactly as the driver starts the 1-GPU line (WORLD_SIZE unset: bench.py launches its ranks itself). Guards the N > 1
-line the driver's scaling run depends on: ONE JSON line whose top level is BASELINE.json's metric on configs[3] (retrieve + rerank
+line of --full runs: ONE JSON line whose top level is BASELINE.json's metric on configs[3] (retrieve + rerank
 through ShardedPipeline, whole-job value), the exchange that was used, the `dense` block (configs[1]), the configs[4] block through
 the sharded classes (here with small shards), and the watchdog: when a later part stalls, what was measured still comes out, the
 phase that stalled is named and the exit code is NOT zero (a stalled collective must not read as success)."""
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(extra_env, timeout=600, expect_rc0=True):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RAG_BENCH_BACKEND="gloo", **extra_env)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "250000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--rows", "250000",
                         "--shard-rows", "125000", "--latency-batches", "3"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=timeout)
     assert (p.returncode == 0) == expect_rc0, (p.returncode, p.stderr[-3000:])

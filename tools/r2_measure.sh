@@ -5,7 +5,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-echo "== default bench"; timeout -k 10 500 python bench.py > $O/r2m_bench.json 2> $O/r2m_bench.err || echo "bench failed"
+echo "== default bench"; timeout -k 10 500 python bench.py --full > $O/r2m_bench.json 2> $O/r2m_bench.err || echo "bench failed"
 for c in clustered sorted tenant-contiguous; do
   echo "== corpus $c"; timeout -k 10 300 python bench.py --dense-only --corpus $c --latency-batches 30 > $O/r2m_bench_$c.json 2> $O/r2m_bench_$c.err || echo "$c failed"
 done
@@ -16,7 +16,7 @@ timeout -k 10 300 python bench.py --dense-only --no-cpu-baseline --latency-batch
 S=/tmp/r2m_scratch; mkdir -p $S      # raw rocprof output stays out of gpurun_out (64 MiB cap): only summaries are copied
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprof dense"; timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $S/r2m_prof_dense -o d -- python3 $R/bench.py --dense-only --no-cpu-baseline --latency-batches 10 > $O/r2m_prof_dense.log 2>&1
-echo "== rocprof full line"; timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $S/r2m_prof_full -o f -- python3 $R/bench.py --no-cpu-baseline --latency-batches 10 > $O/r2m_prof_full.log 2>&1
+echo "== rocprof full line"; timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $S/r2m_prof_full -o f -- python3 $R/bench.py --full --no-cpu-baseline --latency-batches 10 > $O/r2m_prof_full.log 2>&1
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES"; do
   tag=$(echo $pmc | tr ' ' '_' | cut -c1-24)
   echo "== pmc $pmc"; timeout -k 10 300 rocprofv3 --pmc $pmc --kernel-trace -d $S/r2m_pmc_$tag -o p -- python3 $R/bench.py --dense-only --no-cpu-baseline --steps 5 --warmup 1 --latency-batches 1 > $O/r2m_pmc_$tag.log 2>&1

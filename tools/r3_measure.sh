@@ -32,6 +32,6 @@ cepmc)
     python3 $R/tools/rocpd_pmc.py $S/ce_$pmc/p_results.db ce_ > $O/r3m_ce_pmc_$pmc.json
   done ;;
 bench)
-  cd $R; echo "== default bench"; timeout -k 10 600 python bench.py > $O/r3m_bench.json 2> $O/r3m_bench.err || echo FAILED; tail -c 1500 $O/r3m_bench.json; cd /tmp ;;
+  cd $R; echo "== default bench"; timeout -k 10 600 python bench.py --full > $O/r3m_bench.json 2> $O/r3m_bench.err || echo FAILED; tail -c 1500 $O/r3m_bench.json; cd /tmp ;;
 esac
 done
