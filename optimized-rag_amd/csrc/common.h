@@ -46,10 +46,8 @@ struct rag_options {
     int bm25_packed = 0;          // (read when postings are LOADED) 4-byte packed postings + shared impact table instead of (doc, impact)
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
-    int ce_no_fused_ln = 0;       // unfused residual + LayerNorm path of the cross-encoder
-    int ce_no_fused_ffn = 0;      // FFN as two GEMM launches (up-projection, then the fused-LN down-projection)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
-    int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h): 0 = from MX_MIN_ROWS padded rows on, 1 = always, -1 = never
+    int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 and 1 = yes, -1 = never
 };
 
 struct rag_ctx {
@@ -136,7 +134,7 @@ struct rag_ctx {
     void* pipe_ws = nullptr;
     size_t pipe_ws_bytes = 0;
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process
-    bool attr_dense = false, attr_bm25 = false, attr_ce_gemm = false, attr_ce_gemm_ln = false, attr_ce_ffn = false;
+    bool attr_dense = false, attr_bm25 = false, attr_ce_gemm = false;
     int attr_ce_attn_lds[3] = {0, 0, 0};
     int attr_ce_attn_mx_lds[3] = {0, 0, 0};
     bool attr_ce_mx = false;

@@ -16,9 +16,6 @@
 //   ce_pack_scan/rows  lens -> pair_off / row_pair / m_packed (the packed row layout of the chunk)
 //   ce_embed_ln        word+pos+type gather -> LayerNorm -> x16: the residual stream IS the split-fp16 GEMM operand (hi + lo
 //                      = 22 significant bits); there is no separate fp32 copy
-//   ce_gemm_ln         out-proj / FFN-down with bias + residual + LayerNorm fused into the epilogue (hidden = 384): a
-//                      workgroup owns ALL features of its 128 tokens, so a row's statistics never leave the CU and the
-//                      pre-LayerNorm tensor never touches HBM
 //   ce_gemm<EPI>       persistent, XCD-aware; 128 (out features) x 256 (tokens) tiles, BK = 32, three LDS stages by
 //                      LDS-DMA with a continuous stream across tiles, 8 staggered waves (2 x 4 of 64 x 64), source-swizzled
 //                      conflict-free ds_read_b128. Output features sit on the MFMA ROW (bias = 4 registers per lane).
@@ -28,6 +25,9 @@
 //                      registers as the next MFMA's operand, online softmax over 32-key blocks, keys past len skipped.
 //   ce_layernorm       one wave per token (384 = 6/lane), fp32 statistics, eps from config
 //   ce_pool_classify   tanh(Wp.x_cls + bp) -> wc.pooled + bc, fp32
+// One layer, in launch order: QKV GEMM, attention, out-projection GEMM (bias + residual -> fp32) + LayerNorm, FFN-up GEMM
+// (bias + GELU) + FFN-down GEMM (bias + residual -> fp32) + LayerNorm. These split-fp16 kernels run every model whose shape
+// the MX forward (ce_mx.h: hi16 + lo8 operands, hidden 384) does not take, and option ce_mx = -1.
 #include "common.h"
 #include "ce_mx.h"
 #include <type_traits>
@@ -35,6 +35,17 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+
+// one chunk's token arrays, packed row layout and host staging (sized for `pairs` pairs of L tokens, Mp padded rows). Each
+// forward has an instance of its own, so switching between them (option ce_mx) never resizes the other forward's buffers.
+struct ce_chunk_bufs {
+    int32_t *ids = nullptr, *tt = nullptr, *lens = nullptr;            // [Mp] token / type ids padded to L, [pairs] lengths
+    // packed (variable-length) row layout of the current chunk: pair p owns rows [pair_off[p], pair_off[p+1]) where
+    // pair_off[p+1] - pair_off[p] = len rounded up to 16; row_pair[m] = owning pair (-1 past the end); m_packed[0] = rows
+    int32_t *pair_off = nullptr, *row_pair = nullptr, *m_packed = nullptr;
+    int32_t *sid = nullptr, *stt = nullptr;                            // staging of one chunk's [pairs][L_in] token / type ids
+    float* logits = nullptr;                                           // staging of one chunk's outputs, [pairs][out_width]
+};
 
 struct rag_ce_model {
     rag_ce_config cfg;
@@ -53,21 +64,14 @@ struct rag_ce_model {
     float *wp = nullptr, *bp = nullptr, *wc = nullptr, *bc = nullptr;            // pooler / classifier fp32
     float* wpT = nullptr;                                                         // pooler matrix transposed (mx_pool_classify_kernel)
     std::vector<void*> allocs;
-    // activation workspace (sized for ws_tokens)
+    // activation workspace of the split-fp16 forward (sized for ws_tokens)
     int64_t ws_tokens = 0;
     int ws_pairs = 0, ws_L = 0;
-    float* y32 = nullptr;                              // pre-LayerNorm sums of the unfused residual + LayerNorm path, grown on demand
-    int64_t y32_rows = 0;
-    int64_t h16_rows = 0;                              // rows of h16 (the FFN intermediate of the two-launch form), grown on demand
+    float* y32 = nullptr;                              // pre-LayerNorm sums of the residual GEMMs (fp32 [tokens][hidden])
     half_t *x16 = nullptr, *q16 = nullptr, *kf16 = nullptr, *vf16 = nullptr, *ctx16 = nullptr, *h16 = nullptr;
-    int32_t *ids = nullptr, *tt = nullptr, *lens = nullptr;
-    // packed (variable-length) row layout of the current chunk: pair p owns rows [pair_off[p], pair_off[p+1]) where
-    // pair_off[p+1] - pair_off[p] = len rounded up to 16; row_pair[m] = owning pair (-1 past the end); m_packed[0] = rows
-    int32_t *pair_off = nullptr, *row_pair = nullptr, *m_packed = nullptr;
-    int32_t *sid = nullptr, *stt = nullptr;          // staging of one chunk's [pairs][L_in] token / type ids
-    float* logits = nullptr;
-    // the MX forward (ce_mx.h: hi16 + lo8 operands) has a workspace of its own: it runs the large batches, the split-fp16 kernels
-    // above the small ones (their tiles are finer), and neither path must size or evict the other's buffers
+    ce_chunk_bufs io;
+    // the MX forward (ce_mx.h: hi16 + lo8 operands) has a workspace of its own: it runs every model whose shape allows it, the
+    // split-fp16 kernels the others (and option ce_mx = -1), and neither path must size or evict the other's buffers
     bool mx_ok = false;                                // the shape allows the MX path (hidden 384, ffn a multiple of 384 up to 1536) and its weights are loaded
     struct MxWs {
         int pairs = 0, L = 0;
@@ -76,9 +80,7 @@ struct rag_ce_model {
         char *xc8 = nullptr, *cc8 = nullptr, *hc8 = nullptr;             // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
         int32_t* m_cls = nullptr;                                        // device scalar: rows of the compact tensors (= pairs of the chunk)
         half_t *qf16 = nullptr, *kf16 = nullptr, *vf16 = nullptr;       // Q, K, V in the attention kernel's fragment order (hi | lo planes)
-        int32_t *ids = nullptr, *tt = nullptr, *lens = nullptr, *pair_off = nullptr, *row_pair = nullptr, *m_packed = nullptr;
-        int32_t *sid = nullptr, *stt = nullptr;
-        float* logits = nullptr;
+        ce_chunk_bufs io;
     } mx;
 };
 
@@ -121,11 +123,6 @@ __device__ __forceinline__ void store_split4(half_t* __restrict__ p, size_t plan
 // LDS rows are 128 B (8 chunks of 16 B: hi chunks 0-3, lo chunks 4-7 of one 32-element K group). Chunk c of row r is
 // stored at position c ^ ((r>>1) & 7) - dense.hip's swizzle, conflict-free for ds_read_b128 fragment reads - applied on the
 // DMA SOURCE address; the LDS destination stays lane-linear.
-__device__ __forceinline__ void ce_dma(const half_t* __restrict__ g, char* lds, int wid) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)(lds + wid * 64 * 16), 16, 0, 0);
-}
-
 // LDS-DMA piece through a buffer descriptor: per-lane byte offset in ONE VGPR, piece / K-step offset in a scalar register
 // (no 64-bit address arithmetic per piece; reads past the descriptor's end return zeros)
 __device__ __forceinline__ void ce_bdma(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, char* lds, int wid) {
@@ -147,10 +144,7 @@ __device__ __forceinline__ void ce_bdma(__amdgpu_buffer_rsrc_t rs, unsigned voff
 // starts with both stages resident. The packed row count lives on the device (no host sync): the loop stops at the
 // first token tile past it.
 #define CE_EPI_WAVE_BYTES (CE_STAGE_BYTES / 8)            // 6 KiB of the free stage per wave
-// TERMS: which correction products run beside hi*hi. bit 0 = W_lo * x_hi (undoes the fp16 rounding of the WEIGHTS), bit 1 =
-// W_hi * x_lo (undoes the rounding of the ACTIVATIONS). 3 = both (default everywhere); the other instances exist for the
-// per-site ablation of DESIGN.md section 4.5 (RAG_CE_TERMS) and for sites where a term is provably not needed.
-template <int EPI, int TERMS>
+template <int EPI>
 __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__ W, const half_t* __restrict__ X,
                                                        int N, int K, const float* __restrict__ bias,
                                                        const half_t* __restrict__ resid, float* __restrict__ out32,
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
     const int a_base = wm * 64 * 128, b_base = CE_W_TILE + wn * 64 * 128;
     const int nt = K / CE_BK;
     const int last = nt - 1;
-    // Buffer addressing (as ce_gemm_ln_kernel): W through one descriptor + a scalar tile offset, the 256 token rows of a tile
+    // Buffer addressing: W through one descriptor + a scalar tile offset, the 256 token rows of a tile
     // through a per-tile descriptor, ONE per-lane byte offset for all six pieces of a stage. The pointer form spent ~14 VALU
     // instructions per K-step on 64-bit source addresses inside the part of the step that is on the critical path.
     const unsigned voff = (unsigned)(((size_t)sr * ldk + schunk * 8) * sizeof(half_t));
@@ -252,12 +246,12 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 ah[i] = *reinterpret_cast<const half8*>(st + a_base + i * 16 * 128 + off);
-                if (TERMS & 1) al[i] = *reinterpret_cast<const half8*>(st + a_base + i * 16 * 128 + off_lo);
+                al[i] = *reinterpret_cast<const half8*>(st + a_base + i * 16 * 128 + off_lo);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 bh[j] = *reinterpret_cast<const half8*>(st + b_base + j * 16 * 128 + off);
-                if (TERMS & 2) bl[j] = *reinterpret_cast<const half8*>(st + b_base + j * 16 * 128 + off_lo);
+                bl[j] = *reinterpret_cast<const half8*>(st + b_base + j * 16 * 128 + off_lo);
             }
             CE_ISSUE(t + 2)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -271,8 +265,10 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (TERMS & 1) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    if (TERMS & 2) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    // both correction products at every site: dropping either spends the whole logit-error budget
+                    // (profiles/r02_b_ce_term_ablation.md)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);       // W_lo * x_hi
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);       // W_hi * x_lo
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
                 }
             __builtin_amdgcn_s_setprio(0);
@@ -400,547 +396,6 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
         sbase = (sbase + nt) % 3;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // clamped tail re-loads of the last tile: retire them before exit
-}
-
-// ---- out-proj / FFN-down with bias + residual + LayerNorm in the epilogue (hidden = 384) -------------------------------
-// The cross-encoder forward is bound by activation traffic, not by the matrix pipe (tools/ce_probe_build.sh: without MFMAs
-// the forward is 9 % faster, without epilogue stores 35 %). The unfused form moves, per token and LayerNorm site,
-// y32 out (1.5 KB), y32 + residual in (3 KB), x out (1.5 KB); fused, the residual comes in and the new stream goes out
-// (1.5 KB each), and two kernel launches per layer disappear.
-// Geometry: a persistent workgroup owns 128 tokens x ALL 384 features (so the row statistics stay on the CU): 8 waves =
-// 2 feature halves (192 = 12 MFMA row blocks) x 4 token groups (32 = 2 column blocks), 96 accumulator registers per lane.
-// Per 32-deep K-step the W slice (384 rows x [hi|lo] 128 B = 48 KiB, double-buffered: its source is L2-resident) and the
-// token slice (128 rows x 128 B = 16 KiB, triple-buffered: its source is an HBM stream, two steps of lead) arrive by
-// LDS-DMA as ONE continuous stream across tiles; one barrier per K-step (RAW: counted vmcnt(2); WAR: a slot is refilled
-// only after the barrier that follows its last read). The W stage that is free after the last K-step is the epilogue's
-// transpose scratch (6 KiB per wave). K must be a multiple of 192 (stages are then functions of the K-step alone).
-#define lng_dma ce_bdma
-#define LNG_W_STAGE (384 * 128)                    // 48 KiB
-#define LNG_X_STAGE (128 * 128)                    // 16 KiB
-#define LNG_LDS (2 * LNG_W_STAGE + 3 * LNG_X_STAGE)    // 144 KiB
-#define LN_UNFUSED_MAX_ROWS (128 * 256)            // P x L up to which the residual + LayerNorm sites run unfused (finer tiles)
-template <int TERMS>
-__global__ __launch_bounds__(512) void ce_gemm_ln_kernel(const half_t* __restrict__ W, const half_t* __restrict__ X, int K,
-                                                          const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float eps, half_t* __restrict__ stream16,
-                                                          const int32_t* __restrict__ m_packed) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int H = 384;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wid >> 2, wn = wid & 3;
-    const int m_end = m_packed[0];
-    int tile = blockIdx.x;
-    if (tile * 128 >= m_end) return;
-    const int nt = K / CE_BK;
-    const size_t ldk = (size_t)2 * K;
-    // DMA source per thread: piece pc = p * 8 + wid covers rows pc * 8 .. + 8; lane -> row pc * 8 + (lane >> 3), 16-B position
-    // lane & 7, source chunk = position ^ ((row >> 1) & 7) = position ^ ((wid & 1) * 4 + (lane >> 4))  (p * 8 is even)
-    // Every DMA is a BUFFER load: descriptor (scalar registers: W, or the 128 token rows of one tile) + ONE per-lane byte
-    // offset shared by all pieces + a scalar offset (piece, K-step). No address VGPRs besides that one (the first version
-    // carried 6 + 4 pointer pairs through the main loop and spilled them), no address arithmetic in the loop, and reads
-    // past a descriptor's end return zeros instead of faulting.
-    const int schunk = (lane & 7) ^ ((wid & 1) * 4 + (lane >> 4));
-    const unsigned voff = (unsigned)(((size_t)(wid * 8 + (lane >> 3)) * ldk + schunk * 8) * sizeof(half_t));
-    const unsigned piece_b = (unsigned)(64 * ldk * sizeof(half_t));                           // 64 rows further, in bytes
-    const unsigned tile_b = 2 * piece_b;                                                      // 128 token rows
-    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(W), 0, (int)(6 * piece_b), 0x00020000);
-    __amdgpu_buffer_rsrc_t x_cur = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(X + (size_t)tile * 128 * ldk), 0, (int)tile_b, 0x00020000);
-    __amdgpu_buffer_rsrc_t x_nxt = x_cur;
-    bool has_next = false;
-    char* const wring = smem;
-    char* const xring = smem + 2 * LNG_W_STAGE;
-    const int fr = lane & 15, fq = lane >> 4, sw = (fr >> 1) & 7;
-    const int off_hi = fr * 128 + ((fq ^ sw) << 4), off_lo = fr * 128 + (((4 + fq) ^ sw) << 4);
-    const int a_base = wm * 192 * 128, b_base = wn * 32 * 128;
-#define LNG_ISSUE_W(u)   /* W slice of K-step (u mod nt) into W stage u & 1 */                                       \
-    {                                                                                                                \
-        const int ks_ = (u) < nt ? (u) : (u) - nt;                                                                  \
-        char* st_ = wring + ((u) & 1) * LNG_W_STAGE;                                                                \
-        _Pragma("unroll") for (int p_ = 0; p_ < 6; ++p_)                                                            \
-            lng_dma(w_rs, voff, p_ * piece_b + ks_ * 128, st_ + p_ * 8192, wid);                                    \
-    }
-#define LNG_ISSUE_X(u)   /* token slice of step u: this tile, or steps 0.. of the next one (clamped at the very end) */ \
-    {                                                                                                                \
-        const bool nx_ = (u) >= nt && has_next;                                                                     \
-        const int ks_ = (u) < nt ? (u) : (has_next ? (u) - nt : nt - 1);                                            \
-        char* st_ = xring + ((u) % 3) * LNG_X_STAGE;                                                                \
-        if (nx_) {                                                                                                  \
-            lng_dma(x_nxt, voff, ks_ * 128, st_, wid);                                                              \
-            lng_dma(x_nxt, voff, piece_b + ks_ * 128, st_ + 8192, wid);                                             \
-        } else {                                                                                                    \
-            lng_dma(x_cur, voff, ks_ * 128, st_, wid);                                                              \
-            lng_dma(x_cur, voff, piece_b + ks_ * 128, st_ + 8192, wid);                                             \
-        }                                                                                                           \
-    }
-    LNG_ISSUE_W(0)
-    LNG_ISSUE_X(0)
-    LNG_ISSUE_X(1)
-    for (bool first = true;; first = false) {
-        const int m0 = tile * 128;
-        {
-            const int nx = tile + gridDim.x;
-            has_next = nx * 128 < m_end;
-            if (has_next) x_nxt = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(X + (size_t)nx * 128 * ldk), 0, (int)tile_b, 0x00020000);
-        }
-        f32x4 acc[12][2];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) { acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        for (int t = 0; t < nt; ++t) {
-            // W(t) and X(t) have landed once at most the 2 pieces of X(t+1) are outstanding; the barrier makes that hold for
-            // every wave's pieces and closes every wave's reads of the slots refilled below
-            // (step 0 of a continued tile: both slices were waited for before the previous epilogue's stores; a counted wait
-            // here would only wait for those stores)
-            if (first || t > 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            CE_BAR
-            // the 8 DMA pieces of this step are issued one or two at a time BEHIND the MFMA groups below: a piece costs its wave
-            // 60-180 issue cycles, and with all eight up front both waves of a SIMD sat in them at the same time, the matrix pipe
-            // idle (W(t+1) first: it is needed one step from now; the two X(t+2) pieces last)
-            const int wu_ = t + 1, xu_ = t + 2;
-            const unsigned wks_ = (unsigned)(wu_ < nt ? wu_ : wu_ - nt) * 128u;
-            char* const wst_ = wring + (wu_ & 1) * LNG_W_STAGE;
-            const bool xnx_ = xu_ >= nt && has_next;
-            const unsigned xks_ = (unsigned)(xu_ < nt ? xu_ : (has_next ? xu_ - nt : nt - 1)) * 128u;
-            char* const xst_ = xring + (xu_ % 3) * LNG_X_STAGE;
-            const __amdgpu_buffer_rsrc_t xrs_ = xnx_ ? x_nxt : x_cur;
-            const char* ws = wring + (t & 1) * LNG_W_STAGE + a_base;
-            const char* xs = xring + (t % 3) * LNG_X_STAGE + b_base;
-            half8 bh[2], bl[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                bh[j] = *reinterpret_cast<const half8*>(xs + j * 16 * 128 + off_hi);
-                if (TERMS & 2) bl[j] = *reinterpret_cast<const half8*>(xs + j * 16 * 128 + off_lo);
-            }
-            // The wave's 12 feature blocks go through TWO fragment slots of two blocks each (32 VGPRs, as one third of them did
-            // before), refilled right behind the MFMAs that consumed them: the reads of pair p+2 fly under the 12 MFMAs of pair
-            // p+1, so a K-step exposes one LDS round trip instead of three (the waits are the compiler's counted lgkmcnt).
-            half8 ah[2][2], al[2][2];
-#define LNG_READ_PAIR(p, s)                                                                                           \
-            _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                        \
-                ah[s][ii] = *reinterpret_cast<const half8*>(ws + ((p) * 2 + ii) * 16 * 128 + off_hi);                 \
-                if (TERMS & 1) al[s][ii] = *reinterpret_cast<const half8*>(ws + ((p) * 2 + ii) * 16 * 128 + off_lo);  \
-            }
-            LNG_READ_PAIR(0, 0)
-            LNG_READ_PAIR(1, 1)
-#pragma unroll
-            for (int p = 0; p < 6; ++p) {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        f32x4& a = acc[p * 2 + ii][j];
-                        if (TERMS & 1) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[p & 1][ii], bh[j], a, 0, 0, 0);
-                        if (TERMS & 2) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p & 1][ii], bl[j], a, 0, 0, 0);
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p & 1][ii], bh[j], a, 0, 0, 0);
-                    }
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (p + 2 < 6) LNG_READ_PAIR(p + 2, p & 1)
-                if (p < 3) {
-                    lng_dma(w_rs, voff, (2 * p) * piece_b + wks_, wst_ + (2 * p) * 8192, wid);
-                    lng_dma(w_rs, voff, (2 * p + 1) * piece_b + wks_, wst_ + (2 * p + 1) * 8192, wid);
-                } else if (p < 5) {
-                    lng_dma(xrs_, voff, (p - 3) * piece_b + xks_, xst_ + (p - 3) * 8192, wid);
-                }
-            }
-#undef LNG_READ_PAIR
-        }
-        // ---- epilogue. acc[i][j][r] = sum for feature wm*192 + i*16 + fq*4 + r, token m0 + wn*32 + j*16 + fr.
-        // Every wave is past its reads of W stage (nt-1)&1 = 1 after this barrier; its refill (step 1 of the next tile) comes
-        // after the next tile's first barrier, so the stage is this epilogue's scratch: 6 KiB per wave. Steps 0 and 1 of the next
-        // tile are in flight: retire them here, where no store is outstanding yet.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        CE_BAR
-        char* wl = wring + LNG_W_STAGE + wid * 6144;                 // [16 tokens][64 features] fp32, rows 272 B
-        float* st_sum = reinterpret_cast<float*>(wl + 4352);         // [32] per-token partial sums of this wave's 192 features
-        float* st_sq = st_sum + 32;
-        const float* pr_sum = reinterpret_cast<const float*>(wring + LNG_W_STAGE + (wid ^ 4) * 6144 + 4352);   // the other feature half
-        const float* pr_sq = pr_sum + 32;
-        const int rr = lane >> 4, cc = lane & 15;
-        // epilogue addresses = uniform base + ONE per-lane byte offset + compile-time constants. The offsets are made opaque
-        // here, inside the tile loop, so that the compiler derives each address where it is used instead of hoisting ~70
-        // address registers out of the loop and carrying them through the main loop (which spilled its DMA pointers).
-        unsigned so = (unsigned)((rr * 2 * H + (wm * 6 + (cc >> 3)) * 64 + (cc & 7) * 4) * sizeof(half_t));   // stream row, split index
-        unsigned fo = (unsigned)((wm * 192 + cc * 4) * sizeof(float));                                          // bias / gamma / beta
-        asm volatile("" : "+v"(so), "+v"(fo));
-        char* const srow = reinterpret_cast<char*>(stream16 + (size_t)(m0 + wn * 32) * 2 * H);
-        f32x4 vv[2][3][4];                                           // [token block][64-feature group][4 rows per lane]
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-#pragma unroll
-                for (int ii = 0; ii < 4; ++ii)
-                    *reinterpret_cast<f32x4*>(wl + fr * 272 + (ii * 16 + fq * 4) * 4) = acc[g * 4 + ii][j];
-                __builtin_amdgcn_wave_barrier();
-                const float4 bv = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(bias) + fo + g * 256);
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int row = it * 4 + rr;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(wl + row * 272 + cc * 16);
-                    // token m0 + wn*32 + j*16 + row, features wm*192 + g*64 + cc*4 .. +4: K group wm*6 + g*2 + (cc>>3)
-                    const half_t* rp = reinterpret_cast<const half_t*>(srow + so + ((j * 16 + it * 4) * 2 * H + g * 128) * sizeof(half_t));
-                    const half4 rh = *reinterpret_cast<const half4*>(rp), rl = *reinterpret_cast<const half4*>(rp + 32);
-                    vv[j][g][it] = (f32x4){v[0] + bv.x + ((float)rh[0] + (float)rl[0]), v[1] + bv.y + ((float)rh[1] + (float)rl[1]),
-                                           v[2] + bv.z + ((float)rh[2] + (float)rl[2]), v[3] + bv.w + ((float)rh[3] + (float)rl[3])};
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_sched_barrier(0);        // one pass at a time: hoisting all 24 residual loads costs ~100 VGPRs
-            }
-        // row statistics: two passes (mean, then centred squares) as the stand-alone LayerNorm; a token's 384 features are
-        // spread over 16 lanes x 3 groups in this wave and as many in the wave that owns the other feature half
-        float mean[2][4], rstd[2][4];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                float sm = 0.f;
-#pragma unroll
-                for (int g = 0; g < 3; ++g) sm += (vv[j][g][it][0] + vv[j][g][it][1]) + (vv[j][g][it][2] + vv[j][g][it][3]);
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) sm += __shfl_xor(sm, o);
-                mean[j][it] = sm;
-                if (cc == 0) st_sum[j * 16 + it * 4 + rr] = sm;
-            }
-        CE_BAR
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const float mu = (mean[j][it] + pr_sum[j * 16 + it * 4 + rr]) * (1.0f / (float)H);
-                mean[j][it] = mu;
-                float q = 0.f;
-#pragma unroll
-                for (int g = 0; g < 3; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float d = vv[j][g][it][e] - mu; q += d * d; }
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) q += __shfl_xor(q, o);
-                rstd[j][it] = q;
-                if (cc == 0) st_sq[j * 16 + it * 4 + rr] = q;
-            }
-        CE_BAR
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-                rstd[j][it] = 1.0f / sqrtf((rstd[j][it] + pr_sq[j * 16 + it * 4 + rr]) * (1.0f / (float)H) + eps);
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            const float4 gv = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(gamma) + fo + g * 256);
-            const float4 be = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(beta) + fo + g * 256);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const f32x4 v = vv[j][g][it];
-                    const float mu = mean[j][it], rs = rstd[j][it];
-                    half_t* o = reinterpret_cast<half_t*>(srow + so + ((j * 16 + it * 4) * 2 * H + g * 128) * sizeof(half_t));
-                    store_split4(o, 32, (v[0] - mu) * rs * gv.x + be.x, (v[1] - mu) * rs * gv.y + be.y, (v[2] - mu) * rs * gv.z + be.z,
-                                 (v[3] - mu) * rs * gv.w + be.w);
-                }
-        }
-        if (!has_next) break;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // scratch reads retired before the stage is refilled
-        tile += gridDim.x;
-        x_cur = x_nxt;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // clamped tail re-loads: retire them before exit
-#undef LNG_ISSUE_W
-#undef LNG_ISSUE_X
-}
-
-// ---- the whole FFN in ONE kernel (hidden = 384): up-projection + bias + erf-GELU + down-projection + bias + residual + LayerNorm
-// The 1536-wide intermediate activation never reaches HBM: it was the largest tensor of the forward (6 of the ~15 KB stored and
-// 12 of the 33.8 KB moved per token and layer; profiles/r02_i: 1.02 TB of HBM traffic per 25,600-pair forward) and its round
-// trip cost one launch and one store-bound epilogue per layer.
-// A persistent workgroup owns 128 tokens. The intermediate is produced and consumed 128 features (one CHUNK) at a time:
-//   phase A  H_c^T[128 feat x 128 tok] = W1[chunk c] . X^T, K = 384: 12 K-steps of 32 (W1 slice 16 KiB + token slice 16 KiB per
-//            step, three 32-KiB ring slots, two steps of lead); 8 waves = 2 feature halves x 4 token groups, 32 accumulators;
-//   E        bias + GELU, split fp16, written to LDS in the operand layout phase B reads ([K group][token][hi 32 | lo 32]):
-//            64 KiB, never in HBM;
-//   phase B  Y^T[384 x 128 tok] += W2[:, chunk c] . H_c^T, K = 128: 4 K-steps (W2 slice 48 KiB per step, two 48-KiB ring slots
-//            laid over the SAME 96 KiB as phase A's three); 8 waves = 2 feature halves x 4 token groups, 96 accumulators that live
-//            across all 12 chunks;
-// then the bias + residual + LayerNorm epilogue of ce_gemm_ln_kernel. LDS = 96 KiB ring + 64 KiB H = 160 KiB.
-// One barrier per step; every DMA piece is issued right after the barrier that closes the last read of the bytes it overwrites:
-//   A_t (t <= 9) issues A_{t+2};  A_11 issues B_0;  E issues B_1;  B_1 issues B_2;  B_2 issues B_3;  B_3 issues the next A_0
-//   (next chunk or next tile);  A_0 issues A_1 and A_2.
-// Counted waits (pieces per wave: 4 per A step, 6 per B step): A_1..A_10 vmcnt(4), B_0 vmcnt(6), every other step vmcnt(0).
-// The first-projection bias of chunk c + 1 is loaded during B_1 of chunk c (ahead of B_2's pieces: B_2's own wait covers it).
-#define FFN_RING (96 * 1024)
-#define FFN_HBUF (64 * 1024)
-#define FFN_LDS (FFN_RING + FFN_HBUF)
-#define FFN_CH 128                                // intermediate features per chunk
-#define FFN_FUSED_MIN_ROWS (5120 * 256)            // P x L from which the fused kernel is used (below: the two-launch form)
-#define MX_MIN_ROWS 0                              // P x L from which the MX forward (ce_mx.h) runs instead of the split-fp16 kernels: every size. tools/ce_mx_sweep.py: 13 pairs tie (0.82 | 0.80 ms), 25 pairs and up MX is 10-19 % faster - and a pair's logit must not depend on how a batch was split over ranks or chunks, so the rule is by SHAPE only
-template <int TERMS>
-__global__ __launch_bounds__(512) void ce_ffn_ln_kernel(const half_t* __restrict__ W1, const float* __restrict__ b1,
-                                                         const half_t* __restrict__ W2, const float* __restrict__ b2, int F,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                         half_t* __restrict__ stream16, const int32_t* __restrict__ m_packed) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int H = 384, NTA = H / CE_BK, NTB = FFN_CH / CE_BK;     // 12 K-steps up, 4 K-steps down per chunk
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wid >> 2, wn = wid & 3;
-    const int m_end = m_packed[0];
-    int tile = blockIdx.x;
-    if (tile * 128 >= m_end) return;
-    const int n_chunks = F / FFN_CH;
-    // DMA sources (see ce_gemm_ln_kernel): a piece = 64 rows x 128 B, one 1-KiB instruction per wave; per-lane byte offset for rows
-    // of 2*H halfs (W1, X) and of 2*F halfs (W2); descriptors in scalar registers
-    const int schunk = (lane & 7) ^ ((wid & 1) * 4 + (lane >> 4));
-    const unsigned row_a = (unsigned)(2 * H * sizeof(half_t)), row_b = (unsigned)(2 * F * sizeof(half_t));
-    const unsigned voff_a = (unsigned)((wid * 8 + (lane >> 3)) * row_a + schunk * 16);
-    const unsigned voff_b = (unsigned)((wid * 8 + (lane >> 3)) * row_b + schunk * 16);
-    const __amdgpu_buffer_rsrc_t w1_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(W1), 0, (int)((size_t)F * row_a), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w2_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(W2), 0, (int)((size_t)H * row_b), 0x00020000);
-    __amdgpu_buffer_rsrc_t x_cur = __builtin_amdgcn_make_buffer_rsrc(stream16 + (size_t)tile * 128 * 2 * H, 0, (int)(128 * row_a), 0x00020000);
-    char* const hbuf = smem + FFN_RING;
-    const int fr = lane & 15, fq = lane >> 4, sw = (fr >> 1) & 7;
-    const int off_hi = fr * 128 + ((fq ^ sw) << 4), off_lo = fr * 128 + (((4 + fq) ^ sw) << 4);
-    // phase A: this wave's 64 intermediate features (rows of the W1 slice) x 32 tokens; phase B: 192 output features x 32 tokens
-    const int a_base_A = wm * 64 * 128, b_base_A = 16384 + wn * 32 * 128;
-    const int a_base_B = wm * 192 * 128, b_base_B = wn * 32 * 128;
-#define FFN_XSRC(x) x
-    // one 8-KiB piece (64 rows x 128 B) at a time, so that the issue cost of a transfer (60-180 cycles per piece per wave) is
-    // spread behind the MFMA groups of a step instead of standing in front of them
-#define FFN_PIECE_A(c, t, xrs, k)  /* piece k of step t of chunk c: 0, 1 = W1 slice halves, 2, 3 = token slice halves -> A slot t % 3 */ \
-    {                                                                                                                      \
-        char* st_ = smem + ((t) % 3) * 32768 + (k) * 8192;                                                                \
-        if ((k) < 2) ce_bdma(w1_rs, voff_a, (unsigned)(c) * (FFN_CH * row_a) + (unsigned)(t) * 128u + (unsigned)(k) * (64 * row_a), st_, wid); \
-        else ce_bdma(FFN_XSRC(xrs), voff_a, (unsigned)((k) - 2) * (64 * row_a) + (unsigned)(t) * 128u, st_, wid);          \
-    }
-#define FFN_ISSUE_A(c, t, xrs) { FFN_PIECE_A(c, t, xrs, 0) FFN_PIECE_A(c, t, xrs, 1) FFN_PIECE_A(c, t, xrs, 2) FFN_PIECE_A(c, t, xrs, 3) }
-#define FFN_PIECE_B(c, u, k)       /* piece k (0..5: 64 output rows each) of the W2 slice of chunk c, K-step u -> B slot u & 1 */ \
-    ce_bdma(w2_rs, voff_b, (unsigned)(k) * 64u * row_b + ((unsigned)(c) * NTB + (unsigned)(u)) * 128u, smem + ((u) & 1) * 49152 + (k) * 8192, wid);
-    f32x4 acc[12][2];                                  // phase B accumulators: live across the 12 chunks of a tile
-    float4 bv[4];                                      // first-projection bias of the current chunk: features wm*64 + i*16 + fq*4 ..+4
-#define FFN_LOAD_BIAS(c) \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) bv[i_] = *reinterpret_cast<const float4*>(b1 + (c) * FFN_CH + wm * 64 + i_ * 16 + fq * 4);
-    FFN_LOAD_BIAS(0)
-    FFN_ISSUE_A(0, 0, x_cur)
-    for (bool first = true;; first = false) {
-        const int m0 = tile * 128;
-        const int nx = tile + gridDim.x;
-        const bool has_next = nx * 128 < m_end;
-        __amdgpu_buffer_rsrc_t x_nxt = x_cur;
-        if (has_next) x_nxt = __builtin_amdgcn_make_buffer_rsrc(stream16 + (size_t)nx * 128 * 2 * H, 0, (int)(128 * row_a), 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) { acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        for (int c = 0; c < n_chunks; ++c) {
-            // ================= phase A: 12 K-steps =================
-            f32x4 ha[4][2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { ha[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; ha[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int t = 0; t < NTA; ++t) {
-                // own pieces of step t landed (step 0 of a continued tile was waited for inside the previous epilogue)
-                if (t == 0 || t == NTA - 1) { if (!(t == 0 && c == 0 && !first)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-                else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                CE_BAR
-                const char* st = smem + (t % 3) * 32768;
-                half8 bh[2], bl[2], ah[4], al[4];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    bh[j] = *reinterpret_cast<const half8*>(st + b_base_A + j * 2048 + off_hi);
-                    if (TERMS & 2) bl[j] = *reinterpret_cast<const half8*>(st + b_base_A + j * 2048 + off_lo);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    ah[i] = *reinterpret_cast<const half8*>(st + a_base_A + i * 2048 + off_hi);
-                    if (TERMS & 1) al[i] = *reinterpret_cast<const half8*>(st + a_base_A + i * 2048 + off_lo);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        if (TERMS & 1) ha[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], ha[i][j], 0, 0, 0);
-                        if (TERMS & 2) ha[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], ha[i][j], 0, 0, 0);
-                        ha[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], ha[i][j], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    // the pieces this step owes, one or two behind each MFMA group (W1 halves first: the X halves are L2-hot)
-                    if (t == 0) { FFN_PIECE_A(c, 1 + (i >> 1), x_cur, (i & 1) * 2) FFN_PIECE_A(c, 1 + (i >> 1), x_cur, (i & 1) * 2 + 1) }
-                    else if (t + 2 < NTA) FFN_PIECE_A(c, t + 2, x_cur, i)
-                    else if (t == NTA - 1) { FFN_PIECE_B(c, 0, i) if (i >= 2) FFN_PIECE_B(c, 0, i + 2) }
-                }
-            }
-            // ================= E: bias + GELU -> split fp16 in LDS, phase B's operand layout =================
-            CE_BAR                                          // every wave is past its reads of the last A step: B slot 1 is free
-            // ha[i][j][r] = H^T[feature wm*64 + i*16 + fq*4 + r][token wn*32 + j*16 + fr]; K group = feature / 32 = wm*2 + (i>>1),
-            // inside it the 4 features sit at half index (i&1)*16 + fq*4 .. +4: 16-B piece (i&1)*2 + (fq>>1), second half if fq odd
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int tk = wn * 32 + j * 16 + fr;
-                    const int swt = (tk >> 1) & 7, pc = (i & 1) * 2 + (fq >> 1);
-                    char* row = hbuf + (wm * 2 + (i >> 1)) * 16384 + tk * 128 + (fq & 1) * 8;
-                    const float v0 = ce_gelu(ha[i][j][0] + bv[i].x), v1 = ce_gelu(ha[i][j][1] + bv[i].y);
-                    const float v2 = ce_gelu(ha[i][j][2] + bv[i].z), v3 = ce_gelu(ha[i][j][3] + bv[i].w);
-                    const half4 hi = {(half_t)v0, (half_t)v1, (half_t)v2, (half_t)v3};
-                    const half4 lo = {(half_t)(v0 - (float)hi[0]), (half_t)(v1 - (float)hi[1]), (half_t)(v2 - (float)hi[2]), (half_t)(v3 - (float)hi[3])};
-                    *reinterpret_cast<half4*>(row + ((pc ^ swt) << 4)) = hi;
-                    *reinterpret_cast<half4*>(row + (((4 + pc) ^ swt) << 4)) = lo;
-                    if (i * 2 + j < 6) FFN_PIECE_B(c, 1, i * 2 + j)          // B_1's six pieces, one behind each block's GELU
-                }
-            // ================= phase B: 4 K-steps =================
-#pragma unroll
-            for (int u = 0; u < NTB; ++u) {
-                if (u == 0) asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");       // B_0 landed; the H writes are done
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                CE_BAR
-                if (u == 1) { if (c + 1 < n_chunks) { FFN_LOAD_BIAS(c + 1) } else { FFN_LOAD_BIAS(0) } }
-                const char* ws = smem + (u & 1) * 49152 + a_base_B;
-                const char* xs = hbuf + u * 16384 + b_base_B;
-                half8 bh[2], bl[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    bh[j] = *reinterpret_cast<const half8*>(xs + j * 2048 + off_hi);
-                    if (TERMS & 2) bl[j] = *reinterpret_cast<const half8*>(xs + j * 2048 + off_lo);
-                }
-                half8 ah[2][2], al[2][2];
-#define FFN_READ_PAIR(p, s)                                                                                           \
-                _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                    \
-                    ah[s][ii] = *reinterpret_cast<const half8*>(ws + ((p) * 2 + ii) * 2048 + off_hi);                 \
-                    if (TERMS & 1) al[s][ii] = *reinterpret_cast<const half8*>(ws + ((p) * 2 + ii) * 2048 + off_lo);  \
-                }
-                FFN_READ_PAIR(0, 0)
-                FFN_READ_PAIR(1, 1)
-#pragma unroll
-                for (int p = 0; p < 6; ++p) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            f32x4& a = acc[p * 2 + ii][j];
-                            if (TERMS & 1) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[p & 1][ii], bh[j], a, 0, 0, 0);
-                            if (TERMS & 2) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p & 1][ii], bl[j], a, 0, 0, 0);
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p & 1][ii], bh[j], a, 0, 0, 0);
-                        }
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (p + 2 < 6) FFN_READ_PAIR(p + 2, p & 1)
-                    // what this step owes, one piece behind each MFMA group: B_1 -> B_2, B_2 -> B_3, B_3 -> the next A_0
-                    if (u == 1) FFN_PIECE_B(c, 2, p)
-                    else if (u == 2) FFN_PIECE_B(c, 3, p)
-                    else if (u == 3 && p < 4) {
-                        if (c + 1 < n_chunks) FFN_PIECE_A(c + 1, 0, x_cur, p)
-                        else if (has_next) FFN_PIECE_A(0, 0, x_nxt, p)
-                    }
-                }
-#undef FFN_READ_PAIR
-            }
-        }
-        // ---- epilogue: bias + residual + LayerNorm, as ce_gemm_ln_kernel. acc[i][j][r] = sum for feature wm*192 + i*16 + fq*4 + r,
-        // token m0 + wn*32 + j*16 + fr. The last B step read B slot 1 = ring bytes [48K, 96K): after this barrier it is the
-        // transpose scratch (6 KiB per wave); the next tile's A_0 pieces are in flight into [0, 32K).
-        CE_BAR
-        char* wl = smem + 49152 + wid * 6144;                        // [16 tokens][64 features] fp32, rows 272 B
-        float* st_sum = reinterpret_cast<float*>(wl + 4352);         // [32] per-token partial sums of this wave's 192 features
-        float* st_sq = st_sum + 32;
-        const float* pr_sum = reinterpret_cast<const float*>(smem + 49152 + (wid ^ 4) * 6144 + 4352);   // the other feature half
-        const float* pr_sq = pr_sum + 32;
-        const int rr = lane >> 4, cc = lane & 15;
-        unsigned so = (unsigned)((rr * 2 * H + (wm * 6 + (cc >> 3)) * 64 + (cc & 7) * 4) * sizeof(half_t));   // stream row, split index
-        unsigned fo = (unsigned)((wm * 192 + cc * 4) * sizeof(float));                                          // bias / gamma / beta
-        asm volatile("" : "+v"(so), "+v"(fo));
-        char* const srow = reinterpret_cast<char*>(stream16 + (size_t)(m0 + wn * 32) * 2 * H);
-        f32x4 vv[2][3][4];                                           // [token block][64-feature group][4 rows per lane]
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-#pragma unroll
-                for (int ii = 0; ii < 4; ++ii)
-                    *reinterpret_cast<f32x4*>(wl + fr * 272 + (ii * 16 + fq * 4) * 4) = acc[g * 4 + ii][j];
-                __builtin_amdgcn_wave_barrier();
-                const float4 b2v = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(b2) + fo + g * 256);
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int row = it * 4 + rr;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(wl + row * 272 + cc * 16);
-                    const half_t* rp = reinterpret_cast<const half_t*>(srow + so + ((j * 16 + it * 4) * 2 * H + g * 128) * sizeof(half_t));
-                    const half4 rh = *reinterpret_cast<const half4*>(rp), rl = *reinterpret_cast<const half4*>(rp + 32);
-                    vv[j][g][it] = (f32x4){v[0] + b2v.x + ((float)rh[0] + (float)rl[0]), v[1] + b2v.y + ((float)rh[1] + (float)rl[1]),
-                                           v[2] + b2v.z + ((float)rh[2] + (float)rl[2]), v[3] + b2v.w + ((float)rh[3] + (float)rl[3])};
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        float mean[2][4], rstd[2][4];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                float sm = 0.f;
-#pragma unroll
-                for (int g = 0; g < 3; ++g) sm += (vv[j][g][it][0] + vv[j][g][it][1]) + (vv[j][g][it][2] + vv[j][g][it][3]);
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) sm += __shfl_xor(sm, o);
-                mean[j][it] = sm;
-                if (cc == 0) st_sum[j * 16 + it * 4 + rr] = sm;
-            }
-        CE_BAR
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const float mu = (mean[j][it] + pr_sum[j * 16 + it * 4 + rr]) * (1.0f / (float)H);
-                mean[j][it] = mu;
-                float q = 0.f;
-#pragma unroll
-                for (int g = 0; g < 3; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float d = vv[j][g][it][e] - mu; q += d * d; }
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) q += __shfl_xor(q, o);
-                rstd[j][it] = q;
-                if (cc == 0) st_sq[j * 16 + it * 4 + rr] = q;
-            }
-        CE_BAR
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-                rstd[j][it] = 1.0f / sqrtf((rstd[j][it] + pr_sq[j * 16 + it * 4 + rr]) * (1.0f / (float)H) + eps);
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            const float4 gv = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(gamma) + fo + g * 256);
-            const float4 be = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(beta) + fo + g * 256);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const f32x4 v = vv[j][g][it];
-                    const float mu = mean[j][it], rs = rstd[j][it];
-                    half_t* o = reinterpret_cast<half_t*>(srow + so + ((j * 16 + it * 4) * 2 * H + g * 128) * sizeof(half_t));
-                    store_split4(o, 32, (v[0] - mu) * rs * gv.x + be.x, (v[1] - mu) * rs * gv.y + be.y, (v[2] - mu) * rs * gv.z + be.z,
-                                 (v[3] - mu) * rs * gv.w + be.w);
-                }
-        }
-        if (!has_next) break;
-        // the next tile's A_0 pieces (issued before this epilogue's loads) have landed: every load above was waited for in order.
-        // The scratch is overwritten by A_1 / A_2 of the next tile only after its first barrier.
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        tile = nx;
-        x_cur = x_nxt;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#undef FFN_ISSUE_A
-#undef FFN_PIECE_A
-#undef FFN_PIECE_B
-#undef FFN_XSRC
-#undef FFN_LOAD_BIAS
 }
 
 // ---- LayerNorm helpers: one wave per token row of `hidden` floats (hidden % 64 == 0, <= 1024) --------------
@@ -1369,15 +824,29 @@ __global__ void ce_f32_split_kernel(const float* __restrict__ in, half_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+static int chunk_bufs_alloc(rag_ctx* h, ce_chunk_bufs& c, int P, int L, int64_t Mp, int out_width) {
+    HIP_TRY(h, hipMalloc(&c.ids, (size_t)Mp * 4));
+    HIP_TRY(h, hipMalloc(&c.tt, (size_t)Mp * 4));
+    HIP_TRY(h, hipMalloc(&c.lens, (size_t)P * 4));
+    HIP_TRY(h, hipMalloc(&c.pair_off, (size_t)(P + 1) * 4));
+    HIP_TRY(h, hipMalloc(&c.row_pair, (size_t)Mp * 4));
+    HIP_TRY(h, hipMalloc(&c.m_packed, 4));
+    HIP_TRY(h, hipMalloc(&c.sid, (size_t)P * L * 4));            // L_in <= L
+    HIP_TRY(h, hipMalloc(&c.stt, (size_t)P * L * 4));
+    HIP_TRY(h, hipMalloc(&c.logits, (size_t)P * out_width * 4));
+    return RAG_OK;
+}
+
+static void chunk_bufs_free(ce_chunk_bufs& c) {
+    hipFree(c.ids); hipFree(c.tt); hipFree(c.lens); hipFree(c.pair_off); hipFree(c.row_pair); hipFree(c.m_packed);
+    hipFree(c.sid); hipFree(c.stt); hipFree(c.logits);
+    c = ce_chunk_bufs();
+}
+
 static void ce_free_ws(rag_ce_model* m) {
-    hipFree(m->y32); hipFree(m->x16); hipFree(m->q16); hipFree(m->kf16); hipFree(m->vf16); hipFree(m->ctx16);
-    hipFree(m->h16); hipFree(m->ids); hipFree(m->tt); hipFree(m->lens); hipFree(m->logits); hipFree(m->pair_off); hipFree(m->row_pair); hipFree(m->m_packed); hipFree(m->sid); hipFree(m->stt);
+    hipFree(m->y32); hipFree(m->x16); hipFree(m->q16); hipFree(m->kf16); hipFree(m->vf16); hipFree(m->ctx16); hipFree(m->h16);
     m->y32 = nullptr; m->x16 = m->q16 = m->kf16 = m->vf16 = m->ctx16 = m->h16 = nullptr;
-    m->h16_rows = 0;
-    m->y32_rows = 0;
-    m->ids = m->tt = m->lens = nullptr; m->logits = nullptr;
-    m->pair_off = m->row_pair = m->m_packed = nullptr;
-    m->sid = m->stt = nullptr;
+    chunk_bufs_free(m->io);
     m->ws_tokens = 0; m->ws_pairs = 0; m->ws_L = 0;
 }
 
@@ -1385,8 +854,7 @@ static void mx_free_ws(rag_ce_model* m) {
     auto& w = m->mx;
     hipFree(w.x8); hipFree(w.ctx8); hipFree(w.h8); hipFree(w.qf16); hipFree(w.kf16); hipFree(w.vf16);
     hipFree(w.xc8); hipFree(w.cc8); hipFree(w.hc8); hipFree(w.m_cls);
-    hipFree(w.ids); hipFree(w.tt); hipFree(w.lens); hipFree(w.pair_off); hipFree(w.row_pair); hipFree(w.m_packed);
-    hipFree(w.sid); hipFree(w.stt); hipFree(w.logits);
+    chunk_bufs_free(w.io);
     w = rag_ce_model::MxWs();
 }
 
@@ -1538,14 +1006,14 @@ static int launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, const ce_
     }
     const int waves = L / (16 * QB);
     hipLaunchKernelGGL((ce_attention_kernel<QB>), dim3(m->cfg.heads, P), dim3(64 * waves), lds, st, m->q16, m->kf16, m->vf16,
-                       pp.kv, lens_dev, m->pair_off, L, m->cfg.hidden, m->cfg.heads,
+                       pp.kv, lens_dev, m->io.pair_off, L, m->cfg.hidden, m->cfg.heads,
                        (int)round_up((int64_t)m->ws_pairs * L, CE_BN), m->ctx16);
     return RAG_OK;
 }
 
 template <int PER>
 static void launch_ln(rag_ce_model* m, const float* y, const float* g, const float* b, int64_t M, hipStream_t st) {
-    hipLaunchKernelGGL(ce_layernorm_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, y, g, b, m->m_packed, m->cfg.hidden,
+    hipLaunchKernelGGL(ce_layernorm_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, y, g, b, m->io.m_packed, m->cfg.hidden,
                        (float)m->cfg.ln_eps, m->x16);
 }
 
@@ -1558,121 +1026,58 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
     const ce_planes pp = planes_for(m, Mp);
     const int per = H / 64;
     const float eps = (float)m->cfg.ln_eps;
+    const ce_chunk_bufs& io = m->io;
     bool& attr = h->attr_ce_gemm;
     const size_t lds = CE_GEMM_LDS;
     if (!attr) {
-#define CE_ATTR(E, T) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_gemm_kernel<E, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#define CE_ATTR4(E) CE_ATTR(E, 3)
-        CE_ATTR4(EPI_QKV) CE_ATTR4(EPI_GELU) CE_ATTR4(EPI_RESID)
+#define CE_ATTR(E) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_gemm_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CE_ATTR(EPI_QKV) CE_ATTR(EPI_GELU) CE_ATTR(EPI_RESID)
         attr = true;
     }
-    // Correction terms per GEMM site (qkv, out-proj, ffn-up, ffn-down): the split-fp16 kernels run the full form (both terms
-    // everywhere: profiles/r02_b_ce_term_ablation.md shows that dropping any one of them spends the whole logit-error budget;
-    // the per-site ablation build that produced that table lives in the round-3 history, commit e52b089, not in the product).
-    int terms[4] = {3, 3, 3, 3};
-#define CE_GEMM(E, T, ...) hipLaunchKernelGGL((ce_gemm_kernel<E, 3>), dim3(n_cu), blk, lds, st, __VA_ARGS__);
-    (void)terms;
- // bias + residual + LayerNorm in the GEMM epilogue when the geometry allows (hidden = 384, K a multiple of 192: the
-    // MiniLM-L-6 shape); RAG_CE_NO_FUSED_LN=1 forces the stand-alone path (parity test of both)
-    // ... except for SMALL batches: the fused kernel's tiles are 128 tokens x all 384 features, so one query's 100 pairs (~140
-    // tiles) leave 45 % of the CUs without a tile, while the plain GEMM (128 features x 256 tokens: three times as many tiles) + a
-    // LayerNorm launch fills them (tools/ln_sweep.py, forward ms fused | unfused: 13 pairs 0.98 | 0.78, 25 1.09 | 0.92, 50 1.33 |
-    // 1.21, 100 1.90 | 1.77, 150 2.40 | 2.64, 400 5.97 | 6.09, 800 11.2 | 11.8). ce_no_fused_ln: 1 = never fused, -1 = always.
-    const bool fused_ln = H == 384 && F % 192 == 0 && h->opt.ce_no_fused_ln <= 0 &&
-                          (h->opt.ce_no_fused_ln < 0 || h->opt.ce_no_fused_ffn < 0 || (int64_t)P * L > LN_UNFUSED_MAX_ROWS);     // (a forced fused FFN contains a fused LayerNorm)
-    const int64_t y_rows = round_up((int64_t)P * L, CE_BN);
-    if (!fused_ln && y_rows > m->y32_rows) {                 // sized by this call (a single query after a 2M-token batch must not take 3 GB)
-        HIP_TRY(h, hipStreamSynchronize(st));
-        hipFree(m->y32);
-        m->y32 = nullptr;
-        m->y32_rows = 0;
-        HIP_TRY(h, hipMalloc(&m->y32, (size_t)y_rows * H * 4));
-        m->y32_rows = y_rows;
-    }
-    if (fused_ln && !h->attr_ce_gemm_ln) {
-#define CE_ATTR_LN(T) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_gemm_ln_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, LNG_LDS));
-        CE_ATTR_LN(3)
-        h->attr_ce_gemm_ln = true;
-    }
-#define CE_GEMM_LN(T, ...) hipLaunchKernelGGL((ce_gemm_ln_kernel<3>), dim3(n_cu), blk, LNG_LDS, st, __VA_ARGS__);
-    // the whole FFN in one kernel (ce_ffn_ln_kernel) when the geometry allows; option ce_no_fused_ffn keeps the two-launch form
-    // ... from FFN_FUSED_MIN_ROWS padded rows on (tools/ffn_sweep.py, forward ms fused | two-launch: 100 pairs 2.03 | 1.92, 400
-    // 6.51 | 5.99, 1600 23.2 | 22.7, 3200 44.8 | 44.6, 6400 88.2 | 88.9): a small batch (one query's 100 pairs = ~140 tiles of 128
-    // tokens for 256 CUs) finishes sooner as two launches whose tiles are finer. ce_no_fused_ffn: 1 = never, -1 = always.
-    const bool fused_ffn = fused_ln && F % FFN_CH == 0 && h->opt.ce_no_fused_ffn <= 0 &&
-                           (h->opt.ce_no_fused_ffn < 0 || (int64_t)P * L >= FFN_FUSED_MIN_ROWS);
-    // the FFN intermediate [tokens][ffn] (the largest activation: 12 GB per 2M-token chunk) exists only for the two-launch form
-    // (sized by what this call needs, not by the workspace: after a large fused batch a single query must not allocate 12 GB)
-    const int64_t h_rows = round_up((int64_t)P * L, CE_BN);
-    if (!fused_ffn && h_rows > m->h16_rows) {
-        HIP_TRY(h, hipStreamSynchronize(st));
-        hipFree(m->h16);
-        m->h16 = nullptr;
-        m->h16_rows = 0;
-        HIP_TRY(h, hipMalloc(&m->h16, (size_t)h_rows * F * 4));
-        HIP_TRY(h, hipMemsetAsync(m->h16, 0, (size_t)h_rows * F * 4, st));   // padded token rows are read by the GEMM tiles: keep them finite
-        m->h16_rows = h_rows;
-    }
-    if (fused_ffn && !h->attr_ce_ffn) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_ffn_ln_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, FFN_LDS));
-        h->attr_ce_ffn = true;
-    }
+#define CE_GEMM(E, ...) hipLaunchKernelGGL((ce_gemm_kernel<E>), dim3(n_cu), blk, lds, st, __VA_ARGS__);
 #define CE_PER_DISPATCH(CALL)                                                                 \
     switch (per) {                                                                            \
         case 2: CALL(2); break; case 4: CALL(4); break; case 6: CALL(6); break;               \
         case 8: CALL(8); break; case 12: CALL(12); break; case 16: CALL(16); break;           \
         default: h->err = "ce: unsupported hidden size"; return RAG_ERR_ARG;                  \
     }
-#define EMB(PER) hipLaunchKernelGGL(ce_embed_ln_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, m->ids, m->tt, m->word, \
-                                    m->pos, m->type, m->emb_ln_g, m->emb_ln_b, m->m_packed, m->row_pair, m->pair_off, L, H,            \
+#define EMB(PER) hipLaunchKernelGGL(ce_embed_ln_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, \
+                                    m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H,            \
                                     m->cfg.vocab_size, eps, m->x16)
     // packed row layout of this chunk (no host round trip: grids cover the padded worst case, kernels stop at m_packed)
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, m->pair_off, m->m_packed);
-    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, m->pair_off, P, L, Mp, m->row_pair);
+    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, io.pair_off, io.m_packed);
+    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, io.pair_off, P, L, Mp, io.row_pair);
     CE_PER_DISPATCH(EMB)
     const dim3 blk(512);
     static const unsigned n_cu = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return (unsigned)(n >= 8 ? n / 8 * 8 : 256); }();
-    const half_t* nullh = nullptr;
     for (int l = 0; l < m->cfg.layers; ++l) {
         auto& ly = m->layers[l];
-        CE_GEMM(EPI_QKV, terms[0], ly.wqkv, m->x16,
+        CE_GEMM(EPI_QKV, ly.wqkv, m->x16,
                 3 * H, H, ly.bqkv, (const half_t*)nullptr, (float*)nullptr, m->q16, m->kf16, m->vf16, pp.kv, H,
-                m->cfg.heads, m->m_packed, (int)Mp)
+                m->cfg.heads, io.m_packed, (int)Mp)
         {
             const int rc = L == 32 ? launch_attention<1>(h, m, P, L, pp, st, lens_dev) : launch_attention<2>(h, m, P, L, pp, st, lens_dev);
             if (rc != RAG_OK) return rc;
         }
+        // out-projection + bias + residual -> y32, then LayerNorm -> x16
 #define LN1(PER) launch_ln<PER>(m, m->y32, ly.ln1_g, ly.ln1_b, M, st)
-        if (fused_ln) {
-            CE_GEMM_LN(terms[1], ly.wo, m->ctx16, H, ly.bo, ly.ln1_g, ly.ln1_b, eps, m->x16, m->m_packed)
-        } else {
-            CE_GEMM(EPI_RESID, terms[1], ly.wo, m->ctx16, H, H,
-                    ly.bo, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, m->m_packed, (int)Mp)
-            CE_PER_DISPATCH(LN1)
-        }
-        if (fused_ffn) {
-            hipLaunchKernelGGL((ce_ffn_ln_kernel<3>), dim3(n_cu), blk, FFN_LDS, st, (const half_t*)ly.w1, (const float*)ly.b1, (const half_t*)ly.w2,
-                               (const float*)ly.b2, F, (const float*)ly.ln2_g, (const float*)ly.ln2_b, eps, m->x16, (const int32_t*)m->m_packed);
-            continue;
-        }
-        CE_GEMM(EPI_GELU, terms[2], ly.w1, m->x16, F, H,
+        CE_GEMM(EPI_RESID, ly.wo, m->ctx16, H, H,
+                ly.bo, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, io.m_packed, (int)Mp)
+        CE_PER_DISPATCH(LN1)
+        // FFN: up-projection + bias + GELU -> h16, down-projection + bias + residual -> y32, then LayerNorm -> x16
+        CE_GEMM(EPI_GELU, ly.w1, m->x16, F, H,
                 ly.b1, (const half_t*)nullptr, (float*)nullptr, m->h16, (half_t*)nullptr, (half_t*)nullptr, (size_t)0,
-                H, m->cfg.heads, m->m_packed, (int)Mp)
+                H, m->cfg.heads, io.m_packed, (int)Mp)
 #define LN2(PER) launch_ln<PER>(m, m->y32, ly.ln2_g, ly.ln2_b, M, st)
-        if (fused_ln) {
-            CE_GEMM_LN(terms[3], ly.w2, m->h16, F, ly.b2, ly.ln2_g, ly.ln2_b, eps, m->x16, m->m_packed)
-        } else {
-            CE_GEMM(EPI_RESID, terms[3], ly.w2, m->h16, H, F,
-                    ly.b2, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, m->m_packed, (int)Mp)
-            CE_PER_DISPATCH(LN2)
-        }
+        CE_GEMM(EPI_RESID, ly.w2, m->h16, H, F,
+                ly.b2, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, io.m_packed, (int)Mp)
+        CE_PER_DISPATCH(LN2)
     }
-    (void)nullh;
     if (m->embed)
-        hipLaunchKernelGGL(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, (const half_t*)m->x16, (const int32_t*)m->pair_off, lens_dev, L, H,
+        hipLaunchKernelGGL(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, (const half_t*)m->x16, (const int32_t*)io.pair_off, lens_dev, L, H,
                            m->normalize, logits_dev);
     else
-        hipLaunchKernelGGL(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, m->x16, m->wp, m->bp, m->wc, m->bc, m->pair_off, H, logits_dev);
+        hipLaunchKernelGGL(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, m->x16, m->wp, m->bp, m->wc, m->bc, io.pair_off, H, logits_dev);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -1691,21 +1096,17 @@ static int ce_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t s
     HIP_TRY(h, hipMalloc(&m->kf16, 2 * pp.kv * 2));
     HIP_TRY(h, hipMalloc(&m->vf16, 2 * pp.kv * 2));
     HIP_TRY(h, hipMalloc(&m->ctx16, 2 * pp.ctx * 2));
-    HIP_TRY(h, hipMalloc(&m->ids, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&m->tt, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&m->lens, (size_t)P * 4));
-    HIP_TRY(h, hipMalloc(&m->pair_off, (size_t)(P + 1) * 4));
-    HIP_TRY(h, hipMalloc(&m->row_pair, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&m->m_packed, 4));
-    HIP_TRY(h, hipMalloc(&m->sid, (size_t)P * L * 4));            // L_in <= L
-    HIP_TRY(h, hipMalloc(&m->stt, (size_t)P * L * 4));
-    HIP_TRY(h, hipMalloc(&m->logits, (size_t)P * m->out_width * 4));
+    HIP_TRY(h, hipMalloc(&m->h16, 2 * pp.h * 2));
+    HIP_TRY(h, hipMalloc(&m->y32, pp.x * 4));
+    if (int rc = chunk_bufs_alloc(h, m->io, P, L, Mp, m->out_width)) return rc;
     // padded token rows are read by the GEMM tiles: keep them finite
     HIP_TRY(h, hipMemsetAsync(m->x16, 0, 2 * pp.x * 2, st));
     HIP_TRY(h, hipMemsetAsync(m->ctx16, 0, 2 * pp.ctx * 2, st));
     HIP_TRY(h, hipMemsetAsync(m->q16, 0, 2 * pp.q * 2, st));
     HIP_TRY(h, hipMemsetAsync(m->kf16, 0, 2 * pp.kv * 2, st));
     HIP_TRY(h, hipMemsetAsync(m->vf16, 0, 2 * pp.kv * 2, st));
+    HIP_TRY(h, hipMemsetAsync(m->h16, 0, 2 * pp.h * 2, st));
+    HIP_TRY(h, hipMemsetAsync(m->y32, 0, pp.x * 4, st));
     m->ws_pairs = P;
     m->ws_L = L;
     m->ws_tokens = Mp;
@@ -1735,15 +1136,7 @@ static int mx_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t s
     HIP_TRY(h, hipMalloc(&w.qf16, 2 * kv * 2));
     HIP_TRY(h, hipMalloc(&w.kf16, 2 * kv * 2));
     HIP_TRY(h, hipMalloc(&w.vf16, 2 * kv * 2));
-    HIP_TRY(h, hipMalloc(&w.ids, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&w.tt, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&w.lens, (size_t)P * 4));
-    HIP_TRY(h, hipMalloc(&w.pair_off, (size_t)(P + 1) * 4));
-    HIP_TRY(h, hipMalloc(&w.row_pair, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&w.m_packed, 4));
-    HIP_TRY(h, hipMalloc(&w.sid, (size_t)P * L * 4));
-    HIP_TRY(h, hipMalloc(&w.stt, (size_t)P * L * 4));
-    HIP_TRY(h, hipMalloc(&w.logits, (size_t)P * m->out_width * 4));
+    if (int rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width)) return rc;
     // rows past a chunk's packed rows are read by the last token tile of every GEMM: keep them finite (zero is a valid image)
     HIP_TRY(h, hipMemsetAsync(w.x8, 0, (size_t)Mp * H * 3, st));
     HIP_TRY(h, hipMemsetAsync(w.ctx8, 0, (size_t)Mp * H * 3, st));
@@ -1769,12 +1162,12 @@ static int mx_launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, size_t
     auto& w = m->mx;
     if (max_qblocks == 1) {                                  // the [CLS]-only last layer: one wave per (head, pair), no LDS
         hipLaunchKernelGGL((ce_attention_kernel<1, true, true>), dim3(m->cfg.heads, P), dim3(64), 0, st, (const half_t*)w.qf16,
-                           (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.pair_off, L, m->cfg.hidden,
+                           (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
                            m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8), 1);
         return RAG_OK;
     }
     hipLaunchKernelGGL((ce_attention_kernel<QB, true>), dim3(m->cfg.heads, P), dim3(64 * (L / (16 * QB))), lds, st, (const half_t*)w.qf16,
-                       (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.pair_off, L, m->cfg.hidden,
+                       (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
                        m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8), max_qblocks);
     return RAG_OK;
 }
@@ -1791,11 +1184,11 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_ln>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
         h->attr_ce_mx = true;
     }
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, w.pair_off, w.m_packed);
-    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, (const int32_t*)w.pair_off, P, L, Mp, w.row_pair);
-    hipLaunchKernelGGL(mx_embed_ln_kernel, dim3((unsigned)((M + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, (const int32_t*)w.ids, (const int32_t*)w.tt,
+    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, w.io.pair_off, w.io.m_packed);
+    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, (const int32_t*)w.io.pair_off, P, L, Mp, w.io.row_pair);
+    hipLaunchKernelGGL(mx_embed_ln_kernel, dim3((unsigned)((M + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, (const int32_t*)w.io.ids, (const int32_t*)w.io.tt,
                        (const float*)m->word, (const float*)m->pos, (const float*)m->type, (const float*)m->emb_ln_g, (const float*)m->emb_ln_b,
-                       (const int32_t*)w.m_packed, (const int32_t*)w.row_pair, (const int32_t*)w.pair_off, L, m->cfg.vocab_size, eps, w.x8);
+                       (const int32_t*)w.io.m_packed, (const int32_t*)w.io.row_pair, (const int32_t*)w.io.pair_off, L, m->cfg.vocab_size, eps, w.x8);
     static const unsigned n_cu = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return (unsigned)(n >= 8 ? n / 8 * 8 : 256); }();
     const dim3 blk(512);
     for (int l = 0; l < m->cfg.layers; ++l) {
@@ -1804,15 +1197,15 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
         if (cls_tail) {
             // last layer of a classifier (see below): K and V for every token, Q for the [CLS] rows alone
             hipLaunchKernelGGL(mx_gather_rows_kernel, dim3((unsigned)(((int64_t)P * 72 + 255) / 256)), dim3(256), 0, st, (const char*)w.x8, (const char*)nullptr,
-                               (const int32_t*)w.pair_off, P, H / 32, w.xc8, (char*)nullptr, w.m_cls);
+                               (const int32_t*)w.io.pair_off, P, H / 32, w.xc8, (char*)nullptr, w.m_cls);
             hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8 + (size_t)(H / 32) * MX_A_STAGE,
-                               (const char*)w.x8, H / 32, 2, (const int32_t*)w.m_packed,
+                               (const char*)w.x8, H / 32, 2, (const int32_t*)w.io.m_packed,
                                mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 1, (const int32_t*)nullptr, 0});
             hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8, (const char*)w.xc8, H / 32, 1,
-                               (const int32_t*)w.m_cls, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)w.pair_off, P});
+                               (const int32_t*)w.m_cls, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)w.io.pair_off, P});
         } else
         hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8, (const char*)w.x8, H / 32, 3,
-                           (const int32_t*)w.m_packed, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)nullptr, 0});
+                           (const int32_t*)w.io.m_packed, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)nullptr, 0});
         // The classifier reads the [CLS] row of the last layer alone (pooler: hidden_states[:, 0]), and nothing after the last layer's
         // attention mixes tokens. So in the LAST layer of a classifier only the first 16-query block of every pair goes through
         // attention, and out-projection, FFN and both LayerNorms run on ONE row per pair (gathered into compact tensors): the same
@@ -1826,7 +1219,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
         }
         if (cls_tail) {
             hipLaunchKernelGGL(mx_gather_rows_kernel, dim3((unsigned)(((int64_t)P * 72 + 255) / 256)), dim3(256), 0, st, (const char*)w.ctx8, (const char*)nullptr,
-                               (const int32_t*)w.pair_off, P, H / 32, w.cc8, (char*)nullptr, w.m_cls);
+                               (const int32_t*)w.io.pair_off, P, H / 32, w.cc8, (char*)nullptr, w.m_cls);
             hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wo8, (const char*)w.cc8, H / 32, 1,
                                (const int32_t*)w.m_cls, mx_epi_ln{w.xc8, ly.bo, ly.ln1_g, ly.ln1_b, eps});
             hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_gelu>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w18, (const char*)w.xc8, H / 32, F / MX_TM,
@@ -1844,18 +1237,18 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
             return RAG_OK;
         }
         hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wo8, (const char*)w.ctx8, H / 32, 1,
-                           (const int32_t*)w.m_packed, mx_epi_ln{w.x8, ly.bo, ly.ln1_g, ly.ln1_b, eps});
+                           (const int32_t*)w.io.m_packed, mx_epi_ln{w.x8, ly.bo, ly.ln1_g, ly.ln1_b, eps});
         hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_gelu>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w18, (const char*)w.x8, H / 32, F / MX_TM,
-                           (const int32_t*)w.m_packed, mx_epi_gelu{w.h8, ly.b1, F / 32});
+                           (const int32_t*)w.io.m_packed, mx_epi_gelu{w.h8, ly.b1, F / 32});
         hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w28, (const char*)w.h8, F / 32, 1,
-                           (const int32_t*)w.m_packed, mx_epi_ln{w.x8, ly.b2, ly.ln2_g, ly.ln2_b, eps});
+                           (const int32_t*)w.io.m_packed, mx_epi_ln{w.x8, ly.b2, ly.ln2_g, ly.ln2_b, eps});
     }
     if (m->embed)
-        hipLaunchKernelGGL(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8), (const int32_t*)w.pair_off, lens_dev,
+        hipLaunchKernelGGL(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8), (const int32_t*)w.io.pair_off, lens_dev,
                            L, H, m->normalize, logits_dev);
     else
         hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8), (const float*)m->wp,
-                           (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)w.pair_off, H, logits_dev);
+                           (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)w.io.pair_off, H, logits_dev);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -1886,15 +1279,13 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
     const int chunk_max = std::max(1, std::min(P, (int)(chunk_tokens / L)));
     const int chunk = (P + (P + chunk_max - 1) / chunk_max - 1) / ((P + chunk_max - 1) / chunk_max);
     // Which forward: the MX kernels (hi16 + lo8 operands, 384 x 128 tiles; ce_mx.h) whenever the SHAPE allows (hidden 384, ffn a multiple
-    // of 384), the split-fp16 kernels for every other model. Option ce_mx: -1 = never (1 = always, the same as the default today).
-    const bool use_mx = m->mx_ok && L >= 32 && h->opt.ce_mx >= 0 && (h->opt.ce_mx > 0 || (int64_t)P * L >= MX_MIN_ROWS);
+    // of 384), the split-fp16 kernels for every other model. By shape alone, never by batch size: a pair's logit must not depend on
+    // how a batch was split over ranks or chunks. Option ce_mx: -1 = never (0 and 1 = by shape).
+    const bool use_mx = m->mx_ok && h->opt.ce_mx >= 0;
     int rc = use_mx ? mx_ensure_ws(h, m, chunk, L, st) : ce_ensure_ws(h, m, chunk, L, st);
     if (rc) return rc;
     const hipMemcpyKind kin = hipMemcpyHostToDevice, kout = hipMemcpyDeviceToHost;
-    int32_t *sid = use_mx ? m->mx.sid : m->sid, *stt = use_mx ? m->mx.stt : m->stt;
-    int32_t* const lens_stage = use_mx ? m->mx.lens : m->lens;
-    float* const logits_stage = use_mx ? m->mx.logits : m->logits;
-    int32_t *const ids_pad = use_mx ? m->mx.ids : m->ids, *const tt_pad = use_mx ? m->mx.tt : m->tt;
+    const ce_chunk_bufs& io = use_mx ? m->mx.io : m->io;
     if ((rc = prof_begin(h, 2, st))) return rc;
     for (int p0 = 0; p0 < P; p0 += chunk) {
         const int pc = std::min(chunk, P - p0);
@@ -1903,16 +1294,16 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
         const int32_t *src_ids = ids + (size_t)p0 * L_in, *src_tt = tt + (size_t)p0 * L_in, *lens_dev = lens + p0;
         float* logits_dev = out + (size_t)p0 * ow;
         if (host_ptrs) {
-            HIP_TRY(h, hipMemcpyAsync(sid, src_ids, (size_t)pc * L_in * 4, kin, st));
-            HIP_TRY(h, hipMemcpyAsync(stt, src_tt, (size_t)pc * L_in * 4, kin, st));
-            HIP_TRY(h, hipMemcpyAsync(lens_stage, lens_dev, (size_t)pc * 4, kin, st));
-            src_ids = sid; src_tt = stt; lens_dev = lens_stage; logits_dev = logits_stage;
+            HIP_TRY(h, hipMemcpyAsync(io.sid, src_ids, (size_t)pc * L_in * 4, kin, st));
+            HIP_TRY(h, hipMemcpyAsync(io.stt, src_tt, (size_t)pc * L_in * 4, kin, st));
+            HIP_TRY(h, hipMemcpyAsync(io.lens, lens_dev, (size_t)pc * 4, kin, st));
+            src_ids = io.sid; src_tt = io.stt; lens_dev = io.lens; logits_dev = io.logits;
         }
         const int64_t n = (int64_t)pc * L;
-        hipLaunchKernelGGL(ce_pad_tokens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_ids, src_tt, pc, L_in, L, ids_pad, tt_pad);
+        hipLaunchKernelGGL(ce_pad_tokens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_ids, src_tt, pc, L_in, L, io.ids, io.tt);
         rc = use_mx ? mx_forward_chunk(h, m, pc, L, st, lens_dev, logits_dev) : ce_forward_chunk(h, m, pc, L, st, lens_dev, logits_dev);
         if (rc) break;
-        if (host_ptrs) HIP_TRY(h, hipMemcpyAsync(out + (size_t)p0 * ow, logits_stage, (size_t)pc * ow * 4, kout, st));
+        if (host_ptrs) HIP_TRY(h, hipMemcpyAsync(out + (size_t)p0 * ow, io.logits, (size_t)pc * ow * 4, kout, st));
     }
     if (!rc) rc = prof_end(h, 2, st);
     // device-pointer calls stay asynchronous on the caller's stream (all buffers belong to the model workspace);

@@ -538,8 +538,8 @@ def test_dense_topk_odd_dims_explicit_ids_absent_tenant(seed, n, q, k, dim, expl
 @given(seed=st.integers(0, 2**31 - 1), hidden=st.sampled_from([128, 256, 512]), ffn_mult=st.sampled_from([1, 2, 4]), n_pairs=st.integers(1, 30),
        l_in=st.integers(2, 120))
 def test_cross_encoder_other_hidden_sizes_take_the_unfused_path(seed, hidden, ffn_mult, n_pairs, l_in):
-    """Hidden sizes other than 384 (head dim 32, multiples of 128) run the residual GEMM + stand-alone LayerNorm path instead
-    of the fused one: logits within 4e-3 of the float64 forward."""
+    """Hidden sizes other than 384 (head dim 32, multiples of 128) run the split-fp16 forward (residual GEMM + stand-alone
+    LayerNorm): logits within 4e-3 of the float64 forward."""
     from oracle import bert_oracle as B
     from optimized_rag_amd.cross_encoder import flatten_state_dict
     cfg = dict(vocab_size=1500, hidden=hidden, layers=2, heads=hidden // 32, ffn=hidden * ffn_mult, max_pos=128, type_vocab=2, eps=1e-12)
@@ -563,10 +563,11 @@ def test_cross_encoder_other_hidden_sizes_take_the_unfused_path(seed, hidden, ff
     assert np.abs(got[sel] - exp).max() < 4e-3, (got[sel], exp)
 
 
-def test_cross_encoder_unfused_layernorm_path_at_hidden_384(monkeypatch):
-    """Option ce_no_fused_ln sends the MiniLM shape through the residual GEMM + stand-alone LayerNorm kernels: same logits as
-    the fused path to rounding, both within 4e-3 of the float64 forward. These are variants of the SPLIT-FP16 forward (ce_mx = -1:
-    since round 4 the MX kernels run this shape by default, tests/test_cross_encoder_gpu.py covers both)."""
+def test_cross_encoder_split16_forward_at_hidden_384():
+    """Option ce_mx = -1 sends the MiniLM shape through the SPLIT-FP16 forward (residual GEMM + stand-alone LayerNorm, the path of
+    every other hidden size; since round 4 the MX kernels run this shape by default, tests/test_cross_encoder_gpu.py covers both):
+    within 4e-3 of the float64 forward like MX, different from it by rounding only, and the same bits for a pair in a small batch
+    as in a larger one."""
     from oracle import bert_oracle as B
     from optimized_rag_amd.cross_encoder import flatten_state_dict
     cfg = dict(vocab_size=3000, hidden=384, layers=2, heads=12, ffn=1536, max_pos=128, type_vocab=2, eps=1e-12)
@@ -581,25 +582,17 @@ def test_cross_encoder_unfused_layernorm_path_at_hidden_384(monkeypatch):
     ids[np.arange(L)[None, :] >= lens[:, None]] = 0
     tt = ((np.arange(L)[None, :] >= 9) & (np.arange(L)[None, :] < lens[:, None])).astype(np.int32)
     eng.set_option("ce_mx", -1)
-    eng.set_option("ce_no_fused_ln", -1)                     # -1: fused whatever the batch size (0 = by size, see LN_UNFUSED_MAX_ROWS)
     try:
-        fused = eng.ce_score(ids, tt, lens)
-        fused_small = eng.ce_score(ids[:40], tt[:40], lens[:40])
-        eng.set_option("ce_no_fused_ln", 1)
         plain = eng.ce_score(ids, tt, lens)
-        eng.set_option("ce_no_fused_ln", 0)
-        auto_small = eng.ce_score(ids[:40], tt[:40], lens[:40])     # 40 x 128 rows: the size rule picks the unfused sites
+        small = eng.ce_score(ids[:40], tt[:40], lens[:40])
     finally:
-        eng.set_option("ce_no_fused_ln", 0)
         eng.set_option("ce_mx", 0)
     mx = eng.ce_score(ids, tt, lens)                                # the default forward of this shape and size
     assert np.abs(mx - plain).max() < 8e-3 and np.abs(mx - plain).max() > 0
-    np.testing.assert_array_equal(auto_small, plain[:40])
-    assert np.abs(fused_small - plain[:40]).max() < 1e-3
-    assert np.abs(fused - plain).max() < 1e-3
+    np.testing.assert_array_equal(small, plain[:40])
     sel = [0, 1, 150, 299]
     exp = B.forward_logits(w, cfg, ids[sel].astype(np.int64), tt[sel].astype(np.int64), lens[sel], fast_erf=True)
-    assert np.abs(plain[sel] - exp).max() < 4e-3 and np.abs(fused[sel] - exp).max() < 4e-3 and np.abs(mx[sel] - exp).max() < 4e-3
+    assert np.abs(plain[sel] - exp).max() < 4e-3 and np.abs(mx[sel] - exp).max() < 4e-3
 
 
 @settings(**{**COMMON, "max_examples": max(8, N_EX // 25)})

@@ -1,5 +1,5 @@
 """Diagnostic (not product): forward time of the MX forward (option ce_mx = 1) against the split-fp16 forward (ce_mx = -1) over batch
-sizes - where MX_MIN_ROWS (cross_encoder.hip) should sit.  python tools/ce_mx_sweep.py"""
+sizes (the measurement behind running MX at every batch size).  python tools/ce_mx_sweep.py"""
 import os
 import sys
 import time
