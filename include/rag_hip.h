@@ -76,6 +76,47 @@ int rag_index_set_tenants_host(rag_handle_t h, const int32_t* tenant_of_row_host
  * n_rows == rows appended so far; NULL restores id = id_base + row. */
 int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids_host, int64_t n_rows);
 int rag_index_rows(rag_handle_t h, int64_t* n_rows_out);
+
+/* ---- live writes: the INSERT / DELETE the reference agent makes while it runs, without reloading the index.
+ *      archival_memory_insert -> DatabaseOperations.insert_archival_memory (database/operations.py:22-57), the chunk inserts of
+ *      DocumentStore.upload_and_index (rag/document_store.py:343-390), delete_document (:524-542), delete_archival_memory
+ *      (database/operations.py:162-172, `WHERE id = %s AND agent_id = %s`).
+ * Writes are synchronous and take the handle lock; each first waits for all work the handle's *_dev calls queued (on any
+ * stream): a *_dev search queued before a write returns the result from before it.
+ *
+ * rag_index_insert_host: rows become searchable when the call returns, at rows [*first_row_out, +n). Per row: the float32
+ * embedding, a doc id (ids may be NULL only on an implicit-id index, whose new rows then get id_base + row; the first insert
+ * with explicit ids stores the id column), a tenant iff a tenant table is set, a temporal score iff temporal scores are set,
+ * passage tokens [n][tok_L] + lens iff a token store is loaded (on an EMPTY index, tenants / temporal start those planes).
+ * A missing plane, an id that is live already or repeated inside the block: RAG_ERR_ARG (the primary key of the SQL table).
+ * Rows first fill the capacity rag_index_reserve left; past it every row-aligned plane grows (RAG_ERR_NOMEM when it cannot).
+ * A failed insert leaves the index as it was. Inserting on a handle with no index creates one. Marks the BM25 postings stale.
+ *
+ * rag_index_delete_host: deletes the live rows whose id is in ids[n_ids] (and, tenant >= 0, whose tenant is `tenant`: the
+ * `AND agent_id = %s`); *n_deleted_out = rows removed. Unknown / already deleted ids are not an error. Every search entry
+ * point skips deleted rows (BM25 keeps the idf / avgdl of the loaded postings, normalises by the best live document;
+ * rag_bm25_scores_host gives 0.0 for them); entry points that take explicit rows (fetch_rows, mmr_select_dev,
+ * ce_build_pairs_dev) do not look. Results equal those of a fresh handle loaded with only the live rows, in row order.
+ *
+ * rag_index_compact: removes the deleted rows from every plane, stably and in place (at most 1 GiB of staging);
+ * row_map_out[rows before] (may be NULL) = new row of each old row or -1, *n_rows_out = rows after. Doc ids never change
+ * (an implicit-id index stores its ids first). Marks the BM25 postings stale.
+ *
+ * Stale postings: BM25 and hybrid entry points return RAG_ERR_STATE until rag_bm25_load_host loads postings aligned with the
+ * current rows (deletes do not make them stale). */
+typedef struct rag_row_block {
+    int64_t n;
+    const float* emb;            /* [n][dim] */
+    const int64_t* ids;          /* [n]; NULL only on an implicit-id index */
+    const int32_t* tenants;      /* [n] (>= 0); required iff a tenant table is set */
+    const double* temporal;      /* [n]; required iff temporal scores are set */
+    const int32_t* tokens;       /* [n][tok_L]; required iff a token store is loaded */
+    const int32_t* token_lens;   /* [n] */
+} rag_row_block;
+int rag_index_insert_host(rag_handle_t h, const rag_row_block* rows, int64_t* first_row_out);
+int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int tenant, int64_t* n_deleted_out);
+int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
+int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out);
 /* copy rows' fp32 embeddings back (kills apply_mmr's per-doc re-embedding, rag/nodes/helpers.py:215-223) */
 int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, float* out_host);
 

@@ -31,6 +31,11 @@ class DenseStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RowBlock(C.Structure):
+    _fields_ = [("n", C.c_int64), ("emb", C.c_void_p), ("ids", C.c_void_p), ("tenants", C.c_void_p), ("temporal", C.c_void_p),
+                ("tokens", C.c_void_p), ("token_lens", C.c_void_p)]
+
+
 class CeConfig(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("ffn", C.c_int32), ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("reserved", C.c_int32),
@@ -58,6 +63,10 @@ _SIGS = {
     "rag_index_set_ids_host": ([_P, _P, C.c_int64], C.c_int),
     "rag_index_rows": ([_P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_fetch_rows_host": ([_P, _P, C.c_int, _P], C.c_int),
+    "rag_index_insert_host": ([_P, C.POINTER(RowBlock), C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_delete_host": ([_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_compact": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_deleted_rows": ([_P, C.POINTER(C.c_int64)], C.c_int),
     "rag_dense_topk_host": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_dense_topk_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_dense_last_stats": ([_P, C.POINTER(DenseStats)], C.c_int),
@@ -276,6 +285,58 @@ class RagEngine:
         self._check(self.lib.rag_index_fetch_rows_host(self.h, _ptr(rows), rows.shape[0], _ptr(out)),
                     "rag_index_fetch_rows_host")
         return out
+
+    # ---- live writes (include/rag_hip.h rag_index_insert_host / _delete_host / _compact) ---------------------------------
+    def index_insert(self, emb, ids=None, tenants=None, temporal=None, tokens=None, token_lens=None):
+        """Insert rows (host arrays); searchable on return. Returns the first new row number."""
+        emb = _np(emb, np.float32)
+        if emb.ndim == 1:
+            emb = emb[None]
+        if emb.ndim != 2 or emb.shape[1] != self.dim:
+            raise RagError(f"index_insert: expected [N,{self.dim}] got {emb.shape}")
+        n = emb.shape[0]
+        planes = {}
+        for name, a, dt in (("ids", ids, np.int64), ("tenants", tenants, np.int32), ("temporal", temporal, np.float64),
+                            ("tokens", tokens, np.int32), ("token_lens", token_lens, np.int32)):
+            if a is not None:
+                a = _np(a, dt)
+                if a.shape[0] != n:
+                    raise RagError(f"index_insert: {name} has {a.shape[0]} rows, emb has {n}")
+            planes[name] = a
+        tok_L = getattr(self, "_tok_L", None)
+        if planes["tokens"] is not None:           # the C side reads n * tok_L ids and n lengths from these pointers
+            if tok_L is None or planes["tokens"].ndim != 2 or planes["tokens"].shape[1] != tok_L:
+                raise RagError(f"index_insert: tokens must be [{n}, {tok_L}] (the loaded token store's passage length)")
+            if planes["token_lens"] is None or planes["token_lens"].shape != (n,):
+                raise RagError(f"index_insert: token_lens must be [{n}]")
+        rb = RowBlock(n, emb.ctypes.data, *[None if planes[k] is None else planes[k].ctypes.data
+                                            for k in ("ids", "tenants", "temporal", "tokens", "token_lens")])
+        first = C.c_int64()
+        self._check(self.lib.rag_index_insert_host(self.h, C.byref(rb), C.byref(first)), "rag_index_insert_host")
+        self.n_rows = int(first.value) + n
+        return int(first.value)
+
+    def index_delete(self, ids, tenant=-1):
+        """Delete the live rows with these doc ids (and tenant, when >= 0). Returns the number of rows removed."""
+        ids = _np(np.atleast_1d(ids), np.int64)
+        out = C.c_int64()
+        self._check(self.lib.rag_index_delete_host(self.h, _ptr(ids), ids.shape[0], int(tenant), C.byref(out)), "rag_index_delete_host")
+        return int(out.value)
+
+    def index_compact(self):
+        """Remove deleted rows from every plane. Returns row_map (int64 [rows before]: new row or -1)."""
+        n = C.c_int64()
+        self._check(self.lib.rag_index_rows(self.h, C.byref(n)), "rag_index_rows")
+        row_map = np.empty(int(n.value), dtype=np.int64)
+        after = C.c_int64()
+        self._check(self.lib.rag_index_compact(self.h, _ptr(row_map), C.byref(after)), "rag_index_compact")
+        self.n_rows = int(after.value)
+        return row_map
+
+    def index_deleted_rows(self):
+        out = C.c_int64()
+        self._check(self.lib.rag_index_deleted_rows(self.h, C.byref(out)), "rag_index_deleted_rows")
+        return int(out.value)
 
     def dense_topk(self, queries, k, tenant=-1):
         """queries [Q, dim] float32 (numpy). Returns (ids int64 [Q,k], rows int32 [Q,k], scores float64 [Q,k])."""
@@ -604,9 +665,11 @@ class RagEngine:
         lens = _np(lens, np.int32)
         self._check(self.lib.rag_tokens_load_host(self.h, _ptr(tokens), _ptr(lens), tokens.shape[0], tokens.shape[1]),
                     "rag_tokens_load_host")
+        self._tok_L = int(tokens.shape[1])
 
     def tokens_reserve(self, n_rows_total, L):
         self._check(self.lib.rag_tokens_reserve(self.h, int(n_rows_total), int(L)), "rag_tokens_reserve")
+        self._tok_L = int(L)
 
     def tokens_append_dev(self, tokens, lens, stream=None):
         """Append a row block of the passage token store from device memory: tokens [n, L] int32, lens [n] int32 CUDA tensors."""

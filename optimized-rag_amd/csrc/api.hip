@@ -211,8 +211,10 @@ static int index_load_common(rag_ctx* h, const float* emb, const int64_t* ids, i
         if (ids) {
             HIP_TRY(h, hipMalloc(&h->ids, (size_t)n_rows * sizeof(int64_t)));
             HIP_TRY(h, hipMemcpyAsync(h->ids, ids, (size_t)n_rows * sizeof(int64_t), kind, st));
+            h->cap_ids = n_rows;
         }
     }
+    h->cap32 = n_rows;
     int rc = dense_index_build(h, h->emb32, n_rows, st);
     if (rc) return rc;
     h->index_loaded = true;
@@ -244,6 +246,7 @@ int rag_index_reserve(rag_handle_t h, int64_t n_rows_total, int64_t id_base) {
     h->n_reserved = n_rows_total;
     h->n_rows_pad = round_up(n_rows_total, (int64_t)RAG_TILE * 8);
     HIP_TRY(h, hipMalloc(&h->emb32, (size_t)n_rows_total * h->dim * sizeof(float)));
+    h->cap32 = n_rows_total;
     HIP_TRY(h, hipMalloc(&h->emb16, (size_t)h->n_rows_pad * h->dim_pad * sizeof(half_t)));
     HIP_TRY(h, hipMalloc(&h->bad_rows, sizeof(int)));
     HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), h->stream));
@@ -264,6 +267,7 @@ static int index_append(rag_ctx* h, const float* emb, int64_t n, hipStream_t st,
                               host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     int rc = dense_index_normalize_range(h, h->n_rows, n, st);
     if (rc) return rc;
+    if (h->vis && (rc = live_vis_extend(h, h->n_rows, n))) return rc;      // appended rows are live
     h->n_rows += n;
     if (host) HIP_TRY(h, hipStreamSynchronize(st));
     return RAG_OK;
@@ -286,12 +290,20 @@ int rag_index_set_tenants_host(rag_handle_t h, const int32_t* t, int64_t n_rows)
     LOCK(h);
     ARG_CHECK(h, t == nullptr || n_rows == h->n_rows, "tenant array length must equal the index row count");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (h->vis) HIP_TRY(h, hipDeviceSynchronize());       // vis is rebuilt below: no queued search may still read it
     hipFree(h->tenants);
     h->tenants = nullptr;
-    if (t == nullptr || n_rows == 0) return dense_build_tenant_tiles(h, nullptr, 0);      // NULL clears the filter table
+    h->cap_ten = 0;
+    int rc;
+    if (t == nullptr || n_rows == 0) {                     // NULL clears the filter table
+        if ((rc = dense_build_tenant_tiles(h, nullptr, 0))) return rc;
+        return live_vis_rebuild(h);                        // deleted rows stay deleted
+    }
     HIP_TRY(h, hipMalloc(&h->tenants, (size_t)n_rows * sizeof(int32_t)));
+    h->cap_ten = n_rows;
     HIP_TRY(h, hipMemcpy(h->tenants, t, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    return dense_build_tenant_tiles(h, t, n_rows);
+    if ((rc = dense_build_tenant_tiles(h, t, n_rows))) return rc;
+    return live_vis_rebuild(h);
 }
 
 int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
@@ -301,8 +313,10 @@ int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
     HIP_TRY(h, hipSetDevice(h->device));
     hipFree(h->ids);
     h->ids = nullptr;
+    h->cap_ids = 0;
     if (ids == nullptr || n_rows == 0) return RAG_OK;
     HIP_TRY(h, hipMalloc(&h->ids, (size_t)n_rows * sizeof(int64_t)));
+    h->cap_ids = n_rows;
     HIP_TRY(h, hipMemcpy(h->ids, ids, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice));
     return RAG_OK;
 }
@@ -514,6 +528,7 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
     LOCK(h);
     ARG_CHECK(h, q_dev && term_ptr_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid: null pointer");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid: 0 < pool <= 256");
+    if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows, "hybrid: the BM25 postings must be row-aligned with the index (same number of documents)");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -531,11 +546,13 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
     HIP_TRY(h, hipSetDevice(h->device));
     hipFree(h->temporal);
     h->temporal = nullptr;
+    h->cap_tmp = 0;
     h->temporal_absmax = 0.0;
     if (temporal == nullptr || n_rows == 0) return RAG_OK;
     for (int64_t i = 0; i < n_rows; ++i) h->temporal_absmax = std::max(h->temporal_absmax, std::fabs(temporal[i]));
     ARG_CHECK(h, std::isfinite(h->temporal_absmax), "temporal scores must be finite");
     HIP_TRY(h, hipMalloc(&h->temporal, (size_t)n_rows * sizeof(double)));
+    h->cap_tmp = n_rows;
     HIP_TRY(h, hipMemcpy(h->temporal, temporal, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice));
     return RAG_OK;
 }
@@ -556,6 +573,7 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
     ARG_CHECK(h, alpha > 0.0, "hybrid_linear: alpha must be positive (the cosine drives the candidate search)");
     ARG_CHECK(h, std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma), "hybrid_linear: weights must be finite");
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_linear: tenant filter requested but no tenants loaded");
+    if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows && h->n_rows > 0, "hybrid_linear: needs BM25 postings row-aligned with a non-empty index");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;

@@ -533,10 +533,11 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     if (mode == 1) {
         double m = -INFINITY;
         for (int i = tid; i < lim; i += BM_THREADS) {
-            const double v = sc[SC_IDX(i)];
+            // a deleted row scores 0.0 (it is not in the corpus the reference would score)
+            const double v = row_visible(tenants, base + i, -1) ? sc[SC_IDX(i)] : 0.0;
             dense_out[(size_t)q * n_docs + base + i] = v;
             if (dx.raw32 != nullptr) dx.raw32[(size_t)q * dx.ld + base + i] = (float)v;
-            if (dx.max_key != nullptr && (tenants == nullptr || tenants[base + i] == tenant)) m = fmax(m, v);
+            if (dx.max_key != nullptr && row_visible(tenants, base + i, tenant)) m = fmax(m, v);
         }
         if (dx.max_key != nullptr) {
 #pragma unroll
@@ -552,7 +553,7 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     // (key 0, below every real score) from here on, so it can neither enter a partial list nor move the threshold.
     if (lim <= k) {
         for (int i = tid; i < k; i += BM_THREADS) {
-            const bool mine = i < lim && (tenants == nullptr || tenants[base + i] == tenant);
+            const bool mine = i < lim && row_visible(tenants, base + i, tenant);
             part_key[po + i] = mine ? f64_orderable(sc[SC_IDX(i)]) : 0ull;
             part_row[po + i] = (uint32_t)(base + i);
         }
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     if (tenants != nullptr) {
 #pragma unroll
         for (int j = 0; j < BM_SEG; ++j)
-            if ((valid >> j & 1u) && tenants[base + seg0 + j] != tenant) valid &= ~(1u << j);
+            if ((valid >> j & 1u) && !row_visible(tenants, base + seg0 + j, tenant)) valid &= ~(1u << j);
     }
     // Thresholded ranges (second stage, see bm25_launch_topk): tau_key[q] is the k-th best key over the first-stage
     // ranges, a lower bound of the global k-th. Only keys >= tau can reach the global top-k; a later range holds
@@ -1249,6 +1250,7 @@ int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const 
     if (rc) return rc;
     bm25_free(h);
     h->bm25 = ix;
+    h->bm25_stale = false;
     return RAG_OK;
 }
 
@@ -1263,12 +1265,29 @@ static int bm25_set_attr(rag_ctx* h) {
     return RAG_OK;
 }
 
+// The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
+// does not tell: i inserts then i compacted rows restore it): refuse until rag_bm25_load_host reloads them.
+static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
+    if (ix != h->bm25 || !h->bm25_stale) return RAG_OK;
+    h->err = "bm25: the postings are stale (rows were inserted or compacted since rag_bm25_load_host): reload postings aligned "
+             "with the current rows";
+    return RAG_ERR_STATE;
+}
+
+// the same check for the hybrid entry points, before their row-alignment checks (an insert changes the row count)
+int bm25_fresh(rag_ctx* h) { return h->bm25 ? bm25_check_fresh(h, h->bm25) : RAG_OK; }
+
+// visibility argument of the scoring kernels (row_visible): the tenant filter and / or the deleted rows of the resident index
 static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, const int32_t** tenants_out) {
     *tenants_out = nullptr;
-    if (tenant < 0) return RAG_OK;
+    if (int rc = bm25_check_fresh(h, ix)) return rc;
+    if (tenant < 0) {
+        if (ix == h->bm25 && h->vis != nullptr && h->n_rows == ix->n_docs) *tenants_out = h->vis;
+        return RAG_OK;
+    }
     ARG_CHECK(h, h->tenants != nullptr && h->n_rows == ix->n_docs,
               "bm25: a tenant filter needs rag_index_set_tenants_host and postings row-aligned with the index");
-    *tenants_out = h->tenants;
+    *tenants_out = search_vis(h, tenant);
     return RAG_OK;
 }
 
@@ -1286,6 +1305,7 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     if (rc) return rc;
     if ((rc = bm25_set_attr(h))) return rc;
     hipStream_t st = h->stream;
+    const int32_t* dense_vis = mode == 1 ? tenants : nullptr;          // bm25_scores_host: 0.0 for deleted rows
     const int nr = ix->n_ranges;
     const size_t n_part = mode == 0 ? (size_t)Q * nr * k : 0, n_out = mode == 0 ? (size_t)Q * k : 0;
     const size_t n_dense = mode == 1 ? (size_t)Q * ix->n_docs : 0;
@@ -1331,7 +1351,7 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     } else {
         bm25_launch_plan(ix, tp, tm, Q, w.plan, st);
         BM_RANGE_LAUNCH(h, ix, nr, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, tp, tm, k, 1, dd, (uint64_t*)nullptr, (uint32_t*)nullptr, 0,
-                        (const uint64_t*)nullptr, (int*)nullptr, (const int32_t*)nullptr, -1, (const int32_t*)w.plan.off,
+                        (const uint64_t*)nullptr, (int*)nullptr, dense_vis, -1, (const int32_t*)w.plan.off,
                         (const bm_plan_meta*)w.plan.meta)
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(dense_out, dd, n_dense * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1372,6 +1392,7 @@ int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st) {
     ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
+    if (int rc = bm25_check_fresh(h, h->bm25)) return rc;
     const size_t per_query = (size_t)h->bm25->n_ranges * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
     const size_t budget = h->opt.bm25_ws_mb > 0 ? (size_t)h->opt.bm25_ws_mb << 20 : BM_WS_BUDGET;
     const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, budget / std::max<size_t>(1, per_query)));
@@ -1449,13 +1470,14 @@ int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* term
     int rc = bm25_set_attr(h);
     if (rc) return rc;
     const int32_t* tenants = nullptr;
+    if ((rc = bm25_check_fresh(h, ix))) return rc;
     if (max_key_dev != nullptr && (rc = bm25_tenant_args(h, ix, tenant, &tenants))) return rc;
     const bm_dense_extra dx = {raw32_dev, ld, max_key_dev};
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
     const bm25_plan_ws pw = {ix->ws_plan_off, ix->ws_plan_meta};
     bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, pw, st);
     BM_RANGE_LAUNCH(h, ix, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, out_dev, (uint64_t*)nullptr,
-                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenants ? tenant : -1,
+                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant,
                     (const int32_t*)pw.off, (const bm_plan_meta*)pw.meta)
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;

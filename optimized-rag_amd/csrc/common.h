@@ -79,7 +79,15 @@ struct rag_ctx {
     size_t lin_ws_bytes = 0;
     int32_t* tenant_tiles = nullptr;                                   // concatenated per-tenant lists of 256-row tiles
     std::unordered_map<int32_t, std::pair<int64_t, int>> tenant_span;  // tenant -> (offset, count) into tenant_tiles
+    std::unordered_map<int32_t, std::vector<int32_t>> tenant_lists;    // host copy of those lists (inserts extend them)
     int64_t tenant_rows = 0;                                           // row count the tenant table was built for
+    // live writes (live.hip). vis[row] = the row's tenant (0 without a tenant table) or RAG_DEAD_ROW once deleted; null while
+    // nothing is deleted, so the search kernels keep their unfiltered path. Row capacities of the planes inserts grow in place
+    // (emb16's is n_rows_pad, the token store's tok_cap).
+    int32_t* vis = nullptr;
+    int64_t n_deleted = 0;
+    int64_t cap32 = 0, cap_ids = 0, cap_ten = 0, cap_tmp = 0, cap_vis = 0;
+    bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
     int* bad_rows = nullptr;     // device counter: rows with zero / non-finite norm
 
     // dense search workspace (sized for ws_q queries)
@@ -160,6 +168,20 @@ struct rag_ctx {
     } while (0)
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// ---- row visibility: the one predicate every search kernel applies to an index row. vis = rag_ctx::vis when rows are
+// deleted (tenant numbers with RAG_DEAD_ROW for deleted rows), else the tenant table under a tenant filter, else null.
+// tenant >= 0: the row belongs to that tenant (a deleted row never does); tenant < 0: the row is not deleted.
+#define RAG_DEAD_ROW ((int32_t)0x80000000)
+__device__ __forceinline__ bool row_visible(const int32_t* __restrict__ vis, int64_t row, int tenant) {
+    if (vis == nullptr) return true;
+    const int32_t v = vis[row];
+    return tenant >= 0 ? v == tenant : v != RAG_DEAD_ROW;
+}
+// the vis argument of a search over the resident index (host side)
+static inline const int32_t* search_vis(const rag_ctx* h, int tenant) {
+    return h->vis != nullptr ? h->vis : (tenant >= 0 ? h->tenants : nullptr);
+}
 
 // ---- profiling spans (no-ops unless rag_set_profiling(h, 1))
 static inline int prof_begin(rag_ctx* h, int stage, hipStream_t st) {
@@ -249,6 +271,10 @@ int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, i
                       double* kw_out, double* tmp_out, hipStream_t st);
 int dense_free(rag_ctx* h);
 int dense_build_tenant_tiles(rag_ctx* h, const int32_t* tenants_host, int64_t n_rows);
+int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t first_row, int64_t n);
+int live_vis_rebuild(rag_ctx* h);
+int bm25_fresh(rag_ctx* h);            // RAG_ERR_STATE while the postings are stale (inserts / compaction since the last load)
+int live_vis_extend(rag_ctx* h, int64_t first_row, int64_t n);
 int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists, int64_t list_stride, int Q, int k,
                int64_t* ids_out, double* scores_out, hipStream_t st, int normalize = 0);
 int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev,

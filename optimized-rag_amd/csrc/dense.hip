@@ -158,11 +158,11 @@ __device__ __forceinline__ void load_fragB(FragB& f, const char* base, const int
 #define EMIT_PARAMS                                                                                                   \
     const half_t *__restrict__ corpus16, const half_t *__restrict__ q16, int Dp, int rtile_begin, int n_rtiles, int n_qtiles,  \
         int n_rows_valid, int q_valid, const float *__restrict__ tau, unsigned *__restrict__ cnt, uint64_t *__restrict__ cand, \
-        const int32_t *__restrict__ tenants, int tenant, const int32_t *__restrict__ tile_list, int tile_mul, int tile_mod,    \
+        const int32_t *__restrict__ vis, int tenant, const int32_t *__restrict__ tile_list, int tile_mul, int tile_mod,    \
         int tile_cnt, const int *__restrict__ active_count, const float *__restrict__ bias, int64_t bias_ld, float alpha,      \
         const int *__restrict__ qmap, const float *__restrict__ qscale, const float *__restrict__ gt
 #define EMIT_PASS                                                                                                     \
-    corpus16, q16, Dp, rtile_begin, n_rtiles, n_qtiles, n_rows_valid, q_valid, tau, cnt, cand, tenants, tenant, tile_list,    \
+    corpus16, q16, Dp, rtile_begin, n_rtiles, n_qtiles, n_rows_valid, q_valid, tau, cnt, cand, vis, tenant, tile_list,    \
         tile_mul, tile_mod, tile_cnt, active_count, bias, bias_ld, alpha, qmap, qscale, gt
 // one 256 x 256 tile; vb = the (virtual) block index that selects it
 template <bool DENSE0, bool SMALLQ, bool FUSED>
@@ -307,7 +307,7 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, EMIT_PARAMS) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = rbase + r;
-                    const bool ok = row < n_rows_valid && (tenants == nullptr || tenants[row] == tenant);
+                    const bool ok = row < n_rows_valid && row_visible(vis, row, tenant);
                     kk[r] = ok ? make_key(acc[i][j][r] * scale, (uint32_t)row) : 0ull;
                 }
                 ulonglong2* dst = reinterpret_cast<ulonglong2*>(cand + (size_t)q * RAG_CAND_CAP + (rbase - row0) + pos * RAG_TILE);
@@ -320,11 +320,12 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, EMIT_PARAMS) {
     // Thresholded emission, aggregated per lane:
     //  (1) per column block: max of the lane's 32 scores against the threshold (cheap reject, ~45 % of blocks have
     //      no hit at all), hit mask only for lanes that have one;
-    //  (2) rare fix-ups (rows past the end of the corpus in the last tile, tenant filter) in a rolled loop over set bits;
+    //  (2) rare fix-ups (rows past the end of the corpus in the last tile, tenant filter, deleted rows) in a rolled loop over
+    //      set bits: the cost is per hit, not per row;
     //  (3) ONE returning atomic per (lane, column block), all four issued before any result is consumed;
     //  (4) key stores. The compare is done on raw accumulators against tau * 2^14 (exact: power-of-two scale).
     unsigned hits[4], slot[4];
-    const bool fixups = (row0 + RAG_TILE > n_rows_valid) || (tenants != nullptr);       // block-uniform
+    const bool fixups = (row0 + RAG_TILE > n_rows_valid) || (vis != nullptr);       // block-uniform
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int q = q0 + wn * 64 + j * 16 + fr;
@@ -346,7 +347,7 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, EMIT_PARAMS) {
                     const int bit = __ffs(rem) - 1;
                     rem &= rem - 1;
                     const int row = row0 + wm * 128 + (bit >> 2) * 16 + fq * 4 + (bit & 3);
-                    if (row >= n_rows_valid || (tenants != nullptr && tenants[row] != tenant)) h &= ~(1u << bit);
+                    if (row >= n_rows_valid || !row_visible(vis, row, tenant)) h &= ~(1u << bit);
                 }
             }
         }
@@ -705,7 +706,7 @@ __device__ __forceinline__ void bitonic_sort_pairs(uint64_t* k1, uint32_t* k2, i
 }
 
 __global__ __launch_bounds__(256) void scan_chunk_kernel(const float* __restrict__ q32, const float* __restrict__ emb32,
-                                                          const int32_t* __restrict__ tenants, int tenant, int64_t n_rows,
+                                                          const int32_t* __restrict__ vis, int tenant, int64_t n_rows,
                                                           int64_t rows_per_block, int dim, int k, const int* __restrict__ list,
                                                           const int* __restrict__ count, int f0, int round_q,
                                                           uint64_t* __restrict__ part_key,
@@ -726,7 +727,7 @@ __global__ __launch_bounds__(256) void scan_chunk_kernel(const float* __restrict
             for (int i = wv; i < window; i += 4) {
                 const int64_t row = w0 + i;
                 uint64_t key = 0ull;          // 0 = empty (below every real score: orderable(-inf) > 0)
-                if (row < base_end && (tenants == nullptr || tenants[row] == tenant)) {
+                if (row < base_end && row_visible(vis, row, tenant)) {
                     double v = exact_cosine_wave(q32 + (size_t)q * dim, emb32 + (size_t)row * dim, dim, lane);
                     if (raw != nullptr)               // linear fusion (rag/retrieval.py:302), same operation order as linear_fuse_kernel
                         v = (fa * v + fb * (raw[(size_t)q * raw_ld + row] / raw_mx[q])) + fg * (temporal ? temporal[row] : 0.0);
@@ -951,34 +952,65 @@ static int tile_multiplier(int T) {
 // Tenant tile lists (built once per rag_index_set_tenants_host): for every tenant the ascending list of 256-row tiles that
 // hold at least one of its rows. A tenant-filtered search walks ONLY those tiles - a tenant stored contiguously (the usual
 // export order) costs its own rows, not a pass over the table - and draws its threshold stages from them.
+typedef std::unordered_map<int32_t, std::vector<int32_t>> tenant_list_map;
+static void tenant_lists_add(tenant_list_map& lists, const int32_t* tenants_host, int64_t first_row, int64_t n) {
+    for (int64_t r = first_row; r < first_row + n; ++r) {
+        auto& v = lists[tenants_host[r - first_row]];
+        const int32_t t = (int32_t)(r / RAG_TILE);
+        if (v.empty() || v.back() != t) v.push_back(t);
+    }
+}
+// flattens host lists into the device table (O(tiles): 49K entries at 12.5M rows); they become the handle's lists on success
+static int tenant_lists_upload(rag_ctx* h, tenant_list_map& lists, int64_t n_rows) {
+    std::vector<int32_t> flat;
+    std::unordered_map<int32_t, std::pair<int64_t, int>> span;
+    for (auto& kv : lists) {
+        span[kv.first] = {(int64_t)flat.size(), (int)kv.second.size()};
+        flat.insert(flat.end(), kv.second.begin(), kv.second.end());
+    }
+    int32_t* dev = nullptr;
+    HIP_TRY(h, hipMalloc(&dev, std::max<size_t>(1, flat.size()) * sizeof(int32_t)));
+    const hipError_t e = hipMemcpy(dev, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(dev);
+        HIP_TRY(h, e);
+    }
+    hipFree(h->tenant_tiles);
+    h->tenant_tiles = dev;
+    h->tenant_span.swap(span);
+    h->tenant_lists.swap(lists);
+    h->tenant_rows = n_rows;
+    return RAG_OK;
+}
+
 int dense_build_tenant_tiles(rag_ctx* h, const int32_t* tenants_host, int64_t n_rows) {
     hipFree(h->tenant_tiles);
     h->tenant_tiles = nullptr;
     h->tenant_span.clear();
+    h->tenant_lists.clear();
     h->tenant_rows = 0;
     if (!tenants_host || n_rows == 0) return RAG_OK;
-    std::unordered_map<int32_t, std::vector<int32_t>> lists;
-    for (int64_t r = 0; r < n_rows; ++r) {
-        auto& v = lists[tenants_host[r]];
-        const int32_t t = (int32_t)(r / RAG_TILE);
-        if (v.empty() || v.back() != t) v.push_back(t);
-    }
-    std::vector<int32_t> flat;
-    for (auto& kv : lists) {
-        h->tenant_span[kv.first] = {(int64_t)flat.size(), (int)kv.second.size()};
-        flat.insert(flat.end(), kv.second.begin(), kv.second.end());
-    }
-    HIP_TRY(h, hipMalloc(&h->tenant_tiles, std::max<size_t>(1, flat.size()) * sizeof(int32_t)));
-    HIP_TRY(h, hipMemcpy(h->tenant_tiles, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->tenant_rows = n_rows;
-    return RAG_OK;
+    tenant_list_map lists;
+    tenant_lists_add(lists, tenants_host, 0, n_rows);
+    return tenant_lists_upload(h, lists, n_rows);
+}
+
+// rows [first_row, first_row + n) were inserted with these tenants (rag_index_insert_host): extend the lists, new tenants
+// included, without a pass over the table. A copy is extended: a failed upload leaves the handle's lists as they were.
+int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t first_row, int64_t n) {
+    tenant_list_map lists = h->tenant_lists;
+    tenant_lists_add(lists, tenants_host, first_row, n);
+    return tenant_lists_upload(h, lists, first_row + n);
 }
 
 int dense_free(rag_ctx* h) {
     hipFree(h->emb32); hipFree(h->emb16); hipFree(h->ids); hipFree(h->tenants); hipFree(h->bad_rows);
     h->emb32 = nullptr; h->emb16 = nullptr; h->ids = nullptr; h->tenants = nullptr; h->bad_rows = nullptr;
     hipFree(h->scan_scores); h->scan_scores = nullptr; h->scan_rows = 0;
-    hipFree(h->tenant_tiles); h->tenant_tiles = nullptr; h->tenant_span.clear(); h->tenant_rows = 0;
+    hipFree(h->tenant_tiles); h->tenant_tiles = nullptr; h->tenant_span.clear(); h->tenant_lists.clear(); h->tenant_rows = 0;
+    hipFree(h->vis); h->vis = nullptr; h->n_deleted = 0;
+    h->cap32 = h->cap_ids = h->cap_ten = h->cap_vis = 0;
+    h->bm25_stale = false;
     h->n_rows = h->n_rows_pad = 0;
     h->n_reserved = 0;
     h->index_loaded = false;
@@ -1037,7 +1069,7 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "tenant filter requested but no tenants loaded");
     int rc = ensure_workspace(h, Q, st);
     if (rc) return rc;
-    const int32_t* tenants = tenant >= 0 ? h->tenants : nullptr;
+    const int32_t* vis = search_vis(h, tenant);            // tenant filter and / or deleted rows (null: every row)
     // fused: |alpha| * (fp16-pass error of the cosine) + the float32 roundings of the emitted score alpha_f * S + bias:
     // bias = float(beta * kw + gamma * t) (2^-24 relative), alpha_f = float(alpha) (2^-24 |alpha| |S|), the fma's own rounding
     // (2^-24 of the result) - together <= 2^-23 * (|alpha| + |beta| * max|kw| + |gamma| * max|t|). The keyword score is
@@ -1130,7 +1162,7 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
             if (prc) return prc;
         }
 #define EMIT_ARGS(QP, NQT, QV, TAU, CNT, CAND, ACT, QMAP)                                                        \
-    h->emb16, QP, h->dim_pad, begin_, n_rt_, NQT, (int)h->n_rows, QV, TAU, CNT, CAND, tenants, tenant, tile_list, tile_mul, tile_mod, \
+    h->emb16, QP, h->dim_pad, begin_, n_rt_, NQT, (int)h->n_rows, QV, TAU, CNT, CAND, vis, tenant, tile_list, tile_mul, tile_mod, \
         n_tiles, (const int*)(ACT), bias, bias_ld, alpha_f, (const int*)(QMAP), qscale, gt
         const int begin_ = begin, n_rt_ = n_rt;
         if (stage == 0 && fz)
@@ -1217,7 +1249,7 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
         uint64_t* pk = reinterpret_cast<uint64_t*>(h->scan_scores);
         uint32_t* pr = reinterpret_cast<uint32_t*>(pk + h->scan_rows);
         for (int f0 = 0; f0 < Q; f0 += round_q) {
-            hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, tenants, tenant, h->n_rows,
+            hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, h->n_rows,
                                rows_per_block, h->dim, k, scan_list, scan_count, f0, round_q, pk, pr, fz ? fz->raw : (const double*)nullptr,
                                fz ? fz->n : (int64_t)0, fz ? fz->mx : (const double*)nullptr, fz ? fz->temporal : (const double*)nullptr,
                                fz ? fz->alpha : 0.0, fz ? fz->beta : 0.0, fz ? fz->gamma : 0.0);

@@ -253,6 +253,9 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     ARG_CHECK(h, L_pair >= 8 && L_pair <= 512 && Lq > 0 && q_emb_dev && q_tok_dev && q_len_dev && ids_out && scores_out && logits_out,
               "retrieve_rerank: bad arguments");
     ARG_CHECK(h, mode == 0 || (mode == 1 && term_ptr_dev && h->bm25 != nullptr), "retrieve_rerank: mode 1 needs BM25 postings and query terms");
+    if (mode != 0) {
+        if (int rc = bm25_fresh(h)) return rc;
+    }
     ARG_CHECK(h, mode == 0 || bm25_n_docs(h) == h->n_rows, "retrieve_rerank: the BM25 postings must be row-aligned with the index");
     const size_t P = (size_t)Q * pool;
     // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][pool] i64 | rrf [Q][pool] f64 | ranks [Q][pool][2] i32

@@ -4,7 +4,10 @@
 `ORDER BY dc.embedding <=> %s::vector LIMIT %s` with `WHERE dc.agent_id = %s` becomes rag_dense_topk_* with a
 per-row tenant filter; the exact-scan result (not the HNSW approximation) is what is reproduced. Row payloads
 (content, filename, metadata) stay on the host; only embeddings live in HBM."""
+import functools
 import logging
+import math
+import threading
 from typing import Any, Dict, List, Optional
 
 import numpy as np
@@ -32,6 +35,34 @@ class _ShardRows:
         return r
 
 
+class _RowView:
+    """Payload rows after live writes: `base` (a list or _ShardRows) seen through `keep` (compaction), then appended rows."""
+
+    def __init__(self, base, keep=None):
+        self.base, self.keep, self.extra = base, keep, []
+
+    def __len__(self):
+        return (len(self.base) if self.keep is None else len(self.keep)) + len(self.extra)
+
+    def __getitem__(self, i):
+        n = len(self) - len(self.extra)
+        i = int(i)
+        if i >= n:
+            return self.extra[i - n]
+        return self.base[i if self.keep is None else int(self.keep[i])]
+
+    def append(self, r):
+        self.extra.append(r)
+
+
+def _locked(fn):
+    @functools.wraps(fn)
+    def f(self, *a, **kw):
+        with self._lock:
+            return fn(self, *a, **kw)
+    return f
+
+
 class GpuDocumentIndex:
     def __init__(self, embedding_service, dim: int = 1536, *, engine=None):
         self.embeddings = embedding_service            # same attribute name the reference's DocumentStore uses
@@ -39,6 +70,12 @@ class GpuDocumentIndex:
         self._engine = engine
         self.rows: List[Dict[str, Any]] = []
         self._tenant_id: Dict[str, int] = {}
+        # live writes: one lock around writes and searches (a search sees a document's old chunk set or its new one, never a
+        # mix); doc id -> row bookkeeping lives in the engine, (agent, document_id) -> chunk ids here
+        self._lock = threading.RLock()
+        self._next_id = 0
+        self._doc_chunks: Dict[tuple, List[int]] = {}
+        self._shard_without_doc_ids = False
 
     @property
     def engine(self):
@@ -51,23 +88,151 @@ class GpuDocumentIndex:
         (the export of document_chunks / archival_memory)."""
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         assert emb.shape == (len(rows), self.dim)
-        self.rows = list(rows)
+        # a row without `id` carries its engine id (the row number) from here on: compaction renumbers rows, never ids
+        self.rows = [r if "id" in r else dict(r, id=i) for i, r in enumerate(rows)]
         tenants = np.empty(len(rows), dtype=np.int32)
         for i, r in enumerate(rows):
             tenants[i] = self._tenant_id.setdefault(str(r.get("agent_id", "")), len(self._tenant_id))
         self.engine.index_load(emb)
         self.engine.set_tenants(tenants)
+        # engine ids stay id_base + row (implicit); live writes address rows by the row's `id` where it has one
+        self._doc_chunks = {}
+        ids = []
+        for i, r in enumerate(self.rows):
+            ids.append(int(r.get("id", i)))
+            if r.get("document_id") is not None:
+                self._doc_chunks.setdefault((str(r.get("agent_id", "")), int(r["document_id"])), []).append(ids[-1])
+        self._next_id = max(ids, default=-1) + 1
+        if any(int(r["id"]) != i for i, r in enumerate(self.rows)):
+            self.engine.set_ids(np.asarray(ids, dtype=np.int64))
 
-    def load_shard(self, shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072) -> None:
+    def load_shard(self, shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072, headroom_rows: int = 0) -> None:
         """Stream an exported shard directory (shard_format.py; path or open Shard) into the index: rows [begin, end),
-        payloads stay on disk and are read lazily per hit, doc ids are the table's primary keys."""
+        payloads stay on disk and are read lazily per hit, doc ids are the table's primary keys. headroom_rows reserves
+        capacity for live inserts (growing a 115-GB share in place would need a second copy)."""
         from . import shard_format as SF
         sh = SF.open_shard(shard) if isinstance(shard, str) else shard
         end = sh.n_rows if end is None else end
         assert sh.dim == self.dim
-        SF.load_shard_into(self.engine, sh, begin, end, chunk_rows)
+        SF.load_shard_into(self.engine, sh, begin, end, chunk_rows, headroom_rows=headroom_rows)
         self._tenant_id = dict(sh.tenant_table)
         self.rows = _ShardRows(sh, begin, end)
+        self._next_id = int(sh.ids[begin:end].max()) + 1 if end > begin else 0
+        self._doc_chunks = {}
+        doc = getattr(sh, "document_ids", None)
+        self._shard_without_doc_ids = doc is None
+        if doc is not None:
+            agent_of = {v: k for k, v in self._tenant_id.items()}
+            for g in range(begin, end):
+                if doc[g] >= 0:
+                    self._doc_chunks.setdefault((agent_of[int(sh.tenants[g])], int(doc[g])), []).append(int(sh.ids[g]))
+
+    # ---- live writes (rag_index_insert_host / rag_index_delete_host / rag_index_compact) --------------------------------
+    @_locked
+    def add_rows(self, rows: List[Dict[str, Any]], embeddings) -> List[int]:
+        """The incremental form of bulk_load: rows[i] {content, agent_id, id?, document_id?, ...} + embeddings [n, dim].
+        A row without `id` gets the next one. Returns the ids; the rows are searchable on return."""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
+        assert emb.shape[0] == len(rows)
+        if not rows:
+            return []
+        ids = np.empty(len(rows), dtype=np.int64)
+        ten = np.empty(len(rows), dtype=np.int32)
+        for i, r in enumerate(rows):
+            ids[i] = int(r["id"]) if r.get("id") is not None else self._next_id
+            self._next_id = max(self._next_id, int(ids[i]) + 1)
+            ten[i] = self._tenant_id.setdefault(str(r.get("agent_id", "")), len(self._tenant_id))
+        self.engine.index_insert(emb, ids=ids, tenants=ten)
+        if not isinstance(self.rows, (list, _RowView)):
+            self.rows = _RowView(self.rows)
+        for i, r in enumerate(rows):
+            r = dict(r, id=int(ids[i]))
+            self.rows.append(r)
+            if r.get("document_id") is not None:
+                self._doc_chunks.setdefault((str(r.get("agent_id", "")), int(r["document_id"])), []).append(int(ids[i]))
+        return [int(v) for v in ids]
+
+    def _delete_ids(self, agent_id, ids) -> int:
+        t = self._tenant_id.get(str(agent_id))
+        if t is None or not len(ids):
+            return 0
+        return self.engine.index_delete(np.asarray(ids, dtype=np.int64), tenant=t)
+
+    @_locked
+    def index_document_chunks(self, agent_id: str, document_id: int, chunks: List[Dict[str, Any]], embeddings, filename=None,
+                              file_type=None, metadata: Optional[Dict[str, Any]] = None) -> Dict[str, int]:
+        """The chunk phase of DocumentStore.upload_and_index (rag/document_store.py:343-390), after its transaction commits.
+        chunks = what upload_and_index got from `self.chunker.chunk(content)`: dicts {content, metadata?}; metadata = its
+        `full_metadata`. Each stored row is what the reference inserts: content with NUL removed (:372), metadata
+        {**metadata, **chunk['metadata']} (:367-370); empty / non-finite embeddings are skipped (:355-364). The new chunks are
+        inserted before the old ones are deleted, under the index lock: a search sees one chunk set or the other, and a failed
+        insert leaves the old set in place."""
+        rows, embs, skipped = [], [], 0
+        for c, e in zip(chunks, embeddings):
+            if not e or len(e) == 0 or any(math.isnan(float(v)) or math.isinf(float(v)) for v in e):
+                skipped += 1
+                continue
+            rows.append({"content": c["content"].replace("\x00", ""), "agent_id": agent_id, "document_id": int(document_id),
+                         "filename": filename, "file_type": file_type,
+                         "metadata": {**(metadata or {}), **(c.get("metadata") or {})}})
+            embs.append(e)
+        key = (str(agent_id), int(document_id))
+        old = self._doc_chunks.pop(key, [])
+        try:
+            if rows:
+                self.add_rows(rows, np.asarray(embs, dtype=np.float32))
+        except Exception:
+            self._doc_chunks[key] = old
+            raise
+        self._delete_ids(agent_id, old)
+        return {"chunks_created": len(rows), "chunks_skipped": skipped}
+
+    @_locked
+    def delete_document(self, agent_id: str, document_id: int) -> bool:
+        """DocumentStore.delete_document (rag/document_store.py:524-542): True once the chunks are gone (whether or not the
+        document existed), False on failure - a shard exported without document_ids.npy cannot name a document's rows."""
+        try:
+            key = (str(agent_id), int(document_id))
+            if key not in self._doc_chunks and self._shard_without_doc_ids:
+                logger.error("Delete failed: the loaded shard has no document ids (document_ids.npy)")
+                return False
+            self._delete_ids(agent_id, self._doc_chunks.pop(key, []))
+            return True
+        except Exception as e:
+            logger.error(f"Delete failed: {e}")
+            return False
+
+    def insert_archival_memory(self, agent_id: str, content: str, embedding: List[float], metadata: Optional[Dict] = None) -> int:
+        """DatabaseOperations.insert_archival_memory (database/operations.py:22-57): returns the new id."""
+        return self.add_rows([{"agent_id": agent_id, "content": content, "metadata": metadata or {}}], [embedding])[0]
+
+    def bulk_insert_archival_memory(self, agent_id: str, contents: List[str], embeddings: List[List[float]],
+                                    metadatas: List[Dict]) -> List[int]:
+        if not (len(contents) == len(embeddings) == len(metadatas)):
+            raise ValueError("Contents, embeddings, and metadatas must have same length")
+        return self.add_rows([{"agent_id": agent_id, "content": c, "metadata": m or {}} for c, m in zip(contents, metadatas)],
+                             np.asarray(embeddings, dtype=np.float32).reshape(-1, self.dim))
+
+    @_locked
+    def delete_archival_memory(self, agent_id: str, memory_id: int) -> bool:
+        """`DELETE FROM archival_memory WHERE id = %s AND agent_id = %s` (database/operations.py:162-172): rowcount > 0."""
+        return self._delete_ids(agent_id, [int(memory_id)]) > 0
+
+    @_locked
+    def compact(self) -> np.ndarray:
+        """Drop deleted rows from HBM (rag_index_compact) and remap the payload rows; returns row_map[old row]."""
+        row_map = self.engine.index_compact()
+        keep = np.nonzero(row_map >= 0)[0]
+        if isinstance(self.rows, list):
+            self.rows = [self.rows[int(i)] for i in keep]
+        else:
+            v = self.rows if isinstance(self.rows, _RowView) else _RowView(self.rows)
+            nb = len(v) - len(v.extra)
+            base_keep = keep[keep < nb]
+            mapped = _RowView(v.base, base_keep if v.keep is None else np.asarray(v.keep)[base_keep])
+            mapped.extra = [v.extra[int(i) - nb] for i in keep[keep >= nb]]
+            self.rows = mapped
+        return row_map
 
     def _search_rows(self, agent_id, query_embeddings, top_k):
         if agent_id is not None and str(agent_id) not in self._tenant_id:
@@ -80,22 +245,26 @@ class GpuDocumentIndex:
 
     def search(self, agent_id: str, query: str, top_k: int = 5, with_embeddings: bool = True) -> List[Dict[str, Any]]:
         try:
-            q = self.embeddings.generate_embedding(query)
-            rows, scores = self._search_rows(agent_id, [q], top_k)
-            hit = [int(r) for r in rows[0] if r >= 0]
-            embs = self.engine.fetch_rows(hit) if (with_embeddings and hit) else None
-            out = []
-            for j, r in enumerate(hit):
-                row = self.rows[r]
-                d = {"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
-                     "score": float(scores[0][j]), "metadata": row.get("metadata") or {}}
-                if embs is not None:
-                    d["embedding"] = embs[j].tolist()                 # Python floats; saves apply_mmr's re-embedding calls
-                out.append(d)
-            return out
+            q = self.embeddings.generate_embedding(query)            # outside the index lock: a network call in the reference
+            with self._lock:
+                return self._search_locked(agent_id, q, top_k, with_embeddings)
         except Exception as e:                                       # reference: log and return [] (:483-485)
             logger.error("Search failed: %s", e)
             return []
+
+    def _search_locked(self, agent_id, q, top_k, with_embeddings):
+        rows, scores = self._search_rows(agent_id, [q], top_k)
+        hit = [int(r) for r in rows[0] if r >= 0]
+        embs = self.engine.fetch_rows(hit) if (with_embeddings and hit) else None
+        out = []
+        for j, r in enumerate(hit):
+            row = self.rows[r]
+            d = {"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                 "score": float(scores[0][j]), "metadata": row.get("metadata") or {}}
+            if embs is not None:
+                d["embedding"] = embs[j].tolist()                     # Python floats; saves apply_mmr's re-embedding calls
+            out.append(d)
+        return out
 
     def search_many(self, agent_id: str, queries: List[str], top_k: int = 5, with_embeddings: bool = True) -> List[List[Dict[str, Any]]]:
         """Batched `search` (the reference agent can only submit one query per call, so nothing in
@@ -110,31 +279,37 @@ class GpuDocumentIndex:
                 embs = self.embeddings.generate_embeddings_batch(list(queries))
             else:
                 embs = [self.embeddings.generate_embedding(q) for q in queries]
-            rows, scores = self._search_rows(agent_id, embs, top_k)
-            hits = [[int(r) for r in rows[i] if r >= 0] for i in range(len(queries))]
-            flat = [r for h in hits for r in h]
-            fetched = self.engine.fetch_rows(flat) if (with_embeddings and flat) else None
-            out, pos = [], 0
-            for i, h in enumerate(hits):
-                res = []
-                for j, r in enumerate(h):
-                    row = self.rows[r]
-                    d = {"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
-                         "score": float(scores[i][j]), "metadata": row.get("metadata") or {}}
-                    if fetched is not None:
-                        d["embedding"] = fetched[pos + j].tolist()
-                    res.append(d)
-                pos += len(h)
-                out.append(res)
-            return out
+            with self._lock:                                         # embeddings first, outside the index lock
+                return self._search_many_locked(agent_id, queries, embs, top_k, with_embeddings)
         except Exception as e:
             logger.error("Batched search failed: %s", e)
             return [[] for _ in queries]
 
+    def _search_many_locked(self, agent_id, queries, embs, top_k, with_embeddings):
+        rows, scores = self._search_rows(agent_id, embs, top_k)
+        hits = [[int(r) for r in rows[i] if r >= 0] for i in range(len(queries))]
+        flat = [r for h in hits for r in h]
+        fetched = self.engine.fetch_rows(flat) if (with_embeddings and flat) else None
+        out, pos = [], 0
+        for i, h in enumerate(hits):
+            res = []
+            for j, r in enumerate(h):
+                row = self.rows[r]
+                d = {"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                     "score": float(scores[i][j]), "metadata": row.get("metadata") or {}}
+                if fetched is not None:
+                    d["embedding"] = fetched[pos + j].tolist()
+                res.append(d)
+            pos += len(h)
+            out.append(res)
+        return out
+
+    @_locked
     def search_batch(self, agent_id: Optional[str], query_embeddings, top_k: int = 20):
         """Batched entry the reference lacks: Q query embeddings at once -> (row indices [Q,k], cosines [Q,k])."""
         return self._search_rows(agent_id, query_embeddings, top_k)
 
+    @_locked
     def search_archival_memory(self, agent_id: str, query_embedding: List[float], limit: int = 5) -> List[Dict[str, Any]]:
         rows, scores = self._search_rows(agent_id, [query_embedding], limit)
         return [{"id": self.rows[int(r)].get("id", int(r)), "content": self.rows[int(r)].get("content", ""),

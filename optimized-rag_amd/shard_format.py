@@ -77,11 +77,12 @@ class ShardWriter:
         self._emb = open(os.path.join(path, "embeddings.raw"), "wb")
         self._rows = open(os.path.join(path, "rows.jsonl"), "wb")
         self._ids, self._tenants, self._created, self._offsets = [], [], [], [0]
+        self._doc_ids = []                 # document_chunks.document_id per row (-1 = none); written only when one is given
         self._tenant_id: Dict[str, int] = {}
         self._contents = []
 
     def add(self, id: int, agent_id: str, content: str, embedding, metadata: Any = None, created_at=None,
-            filename: Optional[str] = None, file_type: Optional[str] = None) -> None:
+            filename: Optional[str] = None, file_type: Optional[str] = None, document_id: Optional[int] = None) -> None:
         v = parse_pgvector_text(embedding, self.dim) if isinstance(embedding, str) else np.asarray(embedding, dtype=np.float32)
         if v.shape != (self.dim,):
             raise ValueError("row %r: embedding has shape %r, expected (%d,)" % (id, v.shape, self.dim))
@@ -100,6 +101,7 @@ class ShardWriter:
         self._rows.write(line)
         self._offsets.append(self._offsets[-1] + len(line))
         self._ids.append(int(id))
+        self._doc_ids.append(-1 if document_id is None else int(document_id))
         self._tenants.append(self._tenant_id.setdefault(str(agent_id), len(self._tenant_id)))
         self._created.append(_epoch(created_at))
         self._contents.append(content)
@@ -123,6 +125,8 @@ class ShardWriter:
         np.save(os.path.join(self.path, "tenants.npy"), np.asarray(self._tenants, dtype=np.int32))
         np.save(os.path.join(self.path, "created_at.npy"), np.asarray(self._created, dtype=np.float64))
         np.save(os.path.join(self.path, "rows.idx.npy"), np.asarray(self._offsets, dtype=np.int64))
+        if any(d >= 0 for d in self._doc_ids):
+            np.save(os.path.join(self.path, "document_ids.npy"), np.asarray(self._doc_ids, dtype=np.int64))
         if build_bm25 and n:
             p = Bm25Postings.from_corpus(self._contents)
             vocab = np.array(sorted(p.vocab, key=p.vocab.get), dtype=object)
@@ -171,6 +175,8 @@ class Shard:
         self.created_at = np.load(os.path.join(path, "created_at.npy"), mmap_mode="r")
         self._idx = np.load(os.path.join(path, "rows.idx.npy"), mmap_mode="r")
         self._rows = open(os.path.join(path, "rows.jsonl"), "rb")
+        dp = os.path.join(path, "document_ids.npy")          # optional (older shards have none)
+        self.document_ids = np.load(dp, mmap_mode="r") if os.path.exists(dp) else None
         self.tokens = self.token_lens = None
         if self.meta.get("token_len"):
             self.tokens = np.load(os.path.join(path, "tokens.npy"), mmap_mode="r")
@@ -205,13 +211,13 @@ def open_shard(path: str) -> Shard:
 
 
 def load_shard_into(engine, shard: Shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072,
-                    with_bm25: bool = True):
+                    with_bm25: bool = True, headroom_rows: int = 0):
     """Stream rows [begin, end) of the shard into `engine` (RagEngine): fp32 master + fp16 unit copy are built on the
     device chunk by chunk; doc ids = the table's primary keys; tenant filter and (optionally) the BM25 slice loaded.
     Returns the Bm25Postings that were loaded (or None)."""
     end = shard.n_rows if end is None else end
     n = end - begin
-    engine.index_reserve(max(n, 1))
+    engine.index_reserve(max(n + int(headroom_rows), 1))             # headroom: capacity for live inserts
     for b in range(begin, end, chunk_rows):
         engine.index_append(np.ascontiguousarray(shard.embeddings[b:min(end, b + chunk_rows)]))
     if n:
