@@ -47,7 +47,7 @@ struct rag_options {
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
-    int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 and 1 = yes, -1 = never
+    int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 = yes if the load-time probe saw it hold (cross_encoder.hip ce_probe_mx), 1 = yes, -1 = never
 };
 
 struct rag_ctx {

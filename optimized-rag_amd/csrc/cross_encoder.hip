@@ -27,7 +27,8 @@
 //   ce_pool_classify   tanh(Wp.x_cls + bp) -> wc.pooled + bc, fp32
 // One layer, in launch order: QKV GEMM, attention, out-projection GEMM (bias + residual -> fp32) + LayerNorm, FFN-up GEMM
 // (bias + GELU) + FFN-down GEMM (bias + residual -> fp32) + LayerNorm. These split-fp16 kernels run every model whose shape
-// the MX forward (ce_mx.h: hi16 + lo8 operands, hidden 384) does not take, and option ce_mx = -1.
+// the MX forward (ce_mx.h: hi16 + lo8 operands, hidden 384) does not take, classifiers whose load-time probe saw MX miss
+// (ce_probe_mx), and option ce_mx = -1.
 #include "common.h"
 #include "ce_mx.h"
 #include <type_traits>
@@ -73,6 +74,7 @@ struct rag_ce_model {
     // the MX forward (ce_mx.h: hi16 + lo8 operands) has a workspace of its own: it runs every model whose shape allows it, the
     // split-fp16 kernels the others (and option ce_mx = -1), and neither path must size or evict the other's buffers
     bool mx_ok = false;                                // the shape allows the MX path (hidden 384, ffn a multiple of 384 up to 1536) and its weights are loaded
+    bool mx_default = true;                            // option ce_mx = 0 takes the MX path: false when the load-time probe (ce_probe_mx) saw it miss
     struct MxWs {
         int pairs = 0, L = 0;
         int64_t tokens = 0;                            // padded rows (a multiple of 256)
@@ -557,8 +559,8 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
             ce_dma_at(vf16 + g0 + kv_plane + (size_t)c * 512, sv_lo + c * 1024);
         }
         // an odd tile count leaves the second half of the last 32-key block outside the pair: P is 0 there (masked keys), V must be
-        // finite - the never-staged tile is zeroed once instead of selecting zeros at every fragment read (DIRECT reads the next
-        // pair's rows or the zeroed slack of the buffer there: finite too)
+        // finite (0 x NaN = NaN) - the never-staged tile is zeroed once instead of selecting zeros at every fragment read. DIRECT
+        // would read the next pair's rows or stale slack there, which may hold anything: it selects zeros for that tile instead.
         if ((nt & 1) && wv == 0) {
             *reinterpret_cast<u32x4*>(sv_hi + nt * 1024 + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
             *reinterpret_cast<u32x4*>(sv_lo + nt * 1024 + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
@@ -612,12 +614,18 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
         const half8 k0h = *reinterpret_cast<const half8*>(k_hi + fo), k1h = *reinterpret_cast<const half8*>(k_hi + fo + 1024);
         const half8 k0l = *reinterpret_cast<const half8*>(k_lo + fo), k1l = *reinterpret_cast<const half8*>(k_lo + fo + 1024);
         // V fragment = the lane's 4 key slots of tile 2kb | of tile 2kb+1 (tile = [d half][lane][4 slots], 512 B per half); tile 2kb+1
-        // of an odd-count pair is zeros (LDS) or another pair's finite rows (DIRECT) under P = 0
+        // of an odd-count pair lies outside the pair under P = 0: zeros in LDS, and DIRECT selects zeros (that memory belongs to the
+        // next pair or is stale slack: a non-finite value there would turn this pair's context into NaN)
         const int vo = kb * 2048 + lane * 8;
-        const half4 a0h = *reinterpret_cast<const half4*>(v_hi + vo), b0h = *reinterpret_cast<const half4*>(v_hi + vo + 1024);
-        const half4 a1h = *reinterpret_cast<const half4*>(v_hi + vo + 512), b1h = *reinterpret_cast<const half4*>(v_hi + vo + 1536);
-        const half4 a0l = *reinterpret_cast<const half4*>(v_lo + vo), b0l = *reinterpret_cast<const half4*>(v_lo + vo + 1024);
-        const half4 a1l = *reinterpret_cast<const half4*>(v_lo + vo + 512), b1l = *reinterpret_cast<const half4*>(v_lo + vo + 1536);
+        const half4 a0h = *reinterpret_cast<const half4*>(v_hi + vo), a1h = *reinterpret_cast<const half4*>(v_hi + vo + 512);
+        const half4 a0l = *reinterpret_cast<const half4*>(v_lo + vo), a1l = *reinterpret_cast<const half4*>(v_lo + vo + 512);
+        half4 b0h = {}, b1h = {}, b0l = {}, b1l = {};
+        if (!(DIRECT && EDGE && (nt & 1))) {
+            b0h = *reinterpret_cast<const half4*>(v_hi + vo + 1024);
+            b1h = *reinterpret_cast<const half4*>(v_hi + vo + 1536);
+            b0l = *reinterpret_cast<const half4*>(v_lo + vo + 1024);
+            b1l = *reinterpret_cast<const half4*>(v_lo + vo + 1536);
+        }
         const half8 v0h = __builtin_shufflevector(a0h, b0h, 0, 1, 2, 3, 4, 5, 6, 7), v1h = __builtin_shufflevector(a1h, b1h, 0, 1, 2, 3, 4, 5, 6, 7);
         const half8 v0l = __builtin_shufflevector(a0l, b0l, 0, 1, 2, 3, 4, 5, 6, 7), v1l = __builtin_shufflevector(a1l, b1l, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
@@ -915,6 +923,7 @@ static int up_mx_concat(rag_ctx* h, rag_ce_model* m, std::vector<const float*> s
 //  per layer (16): q.w q.b k.w k.b v.w v.b attn.out.w attn.out.b attn.LN.w attn.LN.b inter.w inter.b out.w out.b out.LN.w out.LN.b
 //  then pooler.w pooler.b classifier.w classifier.b
 //  (an embedding model - BertModel behind a mean-pooling head - ends after the layers: no pooler / classifier tensors)
+static int ce_probe_mx(rag_ctx* h, rag_ce_model* m);
 static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n, bool embed, int normalize, rag_ce_model** slot) {
     ARG_CHECK(h, cfg && T, "ce_load: null");
     ARG_CHECK(h, cfg->hidden % 128 == 0 && cfg->hidden <= 1024 && cfg->ffn % 128 == 0, "ce_load: hidden/ffn must be multiples of 128");
@@ -976,7 +985,7 @@ static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* cons
         if ((rc = up_f32(h, m, t[3], 1, &m->bc))) return rc;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RAG_OK;
+    return m->mx_ok && !embed ? ce_probe_mx(h, m) : RAG_OK;
 }
 
 int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n) {
@@ -1038,7 +1047,8 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
 #define CE_PER_DISPATCH(CALL)                                                                 \
     switch (per) {                                                                            \
         case 2: CALL(2); break; case 4: CALL(4); break; case 6: CALL(6); break;               \
-        case 8: CALL(8); break; case 12: CALL(12); break; case 16: CALL(16); break;           \
+        case 8: CALL(8); break; case 10: CALL(10); break; case 12: CALL(12); break;           \
+        case 14: CALL(14); break; case 16: CALL(16); break;                                   \
         default: h->err = "ce: unsupported hidden size"; return RAG_ERR_ARG;                  \
     }
 #define EMB(PER) hipLaunchKernelGGL(ce_embed_ln_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, \
@@ -1263,9 +1273,17 @@ __global__ void ce_pad_tokens_kernel(const int32_t* __restrict__ in_ids, const i
     tt[i] = t < L_in ? in_tt[(size_t)p * L_in + t] : 0;
 }
 
+// Which forward: the MX kernels (hi16 + lo8 operands, 384 x 128 tiles; ce_mx.h) whenever the SHAPE allows (hidden 384, ffn a multiple
+// of 384) and the load-time probe saw them within CE_PROBE_TOL of the split-fp16 forward, the split-fp16 kernels for every other
+// model. By model alone, never by batch size: a pair's logit must not depend on how a batch was split over ranks or chunks.
+// Option ce_mx: -1 = never, 1 = by shape (probe ignored), 0 = by shape and probe.
+static bool ce_use_mx(const rag_ctx* h, const rag_ce_model* m) {
+    return m->mx_ok && (h->opt.ce_mx > 0 || (h->opt.ce_mx == 0 && m->mx_default));
+}
+
 // out: [P][m->out_width] floats (logits of a cross-encoder, pooled vectors of an embedding model)
 static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* out,
-                  hipStream_t st, bool host_ptrs) {
+                  hipStream_t st, bool host_ptrs, bool use_mx) {
     ARG_CHECK(h, ids && tt && lens && out && P > 0 && L_in > 0, "ce_score: bad arguments");
     const size_t ow = (size_t)m->out_width;
     ARG_CHECK(h, L_in <= m->cfg.max_pos && L_in <= 512, "ce_score: sequence longer than max_position_embeddings/512");
@@ -1278,10 +1296,6 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
     // GEMM workgroups of its one-feature-tile kernels 12-or-13 tiles each: 6 % of that chunk idle)
     const int chunk_max = std::max(1, std::min(P, (int)(chunk_tokens / L)));
     const int chunk = (P + (P + chunk_max - 1) / chunk_max - 1) / ((P + chunk_max - 1) / chunk_max);
-    // Which forward: the MX kernels (hi16 + lo8 operands, 384 x 128 tiles; ce_mx.h) whenever the SHAPE allows (hidden 384, ffn a multiple
-    // of 384), the split-fp16 kernels for every other model. By shape alone, never by batch size: a pair's logit must not depend on
-    // how a batch was split over ranks or chunks. Option ce_mx: -1 = never (0 and 1 = by shape).
-    const bool use_mx = m->mx_ok && h->opt.ce_mx >= 0;
     int rc = use_mx ? mx_ensure_ws(h, m, chunk, L, st) : ce_ensure_ws(h, m, chunk, L, st);
     if (rc) return rc;
     const hipMemcpyKind kin = hipMemcpyHostToDevice, kout = hipMemcpyDeviceToHost;
@@ -1320,13 +1334,46 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
 int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* out,
              hipStream_t st, bool host_ptrs) {
     ARG_CHECK(h, h->ce != nullptr, "no cross-encoder loaded");
-    return ce_run(h, h->ce, ids, tt, lens, P, L_in, out, st, host_ptrs);
+    return ce_run(h, h->ce, ids, tt, lens, P, L_in, out, st, host_ptrs, ce_use_mx(h, h->ce));
 }
 
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* out, hipStream_t st,
               bool host_ptrs) {
     ARG_CHECK(h, h->emb != nullptr, "no embedding model loaded");
-    return ce_run(h, h->emb, ids, tt, lens, P, L_in, out, st, host_ptrs);
+    return ce_run(h, h->emb, ids, tt, lens, P, L_in, out, st, host_ptrs, ce_use_mx(h, h->emb));
+}
+
+// Load-time accuracy probe of a classifier's MX forward. Its 8-bit correction operands track the split-fp16 forward to ~1e-3 on
+// models like the seeded and random-init ones, but sharp attention heads (large Q / K weights) or LayerNorm outlier dimensions
+// push the MX logits past the 4e-3 bar (stress levels). A fixed batch goes through both forwards; when they
+// differ by more than CE_PROBE_TOL, option ce_mx = 0 takes the split-fp16 forward for this model. The choice depends on the
+// weights alone. Pairs that are not finite on either forward say nothing about precision and are skipped.
+#define CE_PROBE_PAIRS 16
+#define CE_PROBE_TOL 2.5e-3f
+static int ce_probe_mx(rag_ctx* h, rag_ce_model* m) {
+    const int P = CE_PROBE_PAIRS, L = std::min(128, m->cfg.max_pos), V = m->cfg.vocab_size;
+    const int id0 = V > 2000 ? 1000 : 0;               // WordPiece vocabularies keep [unused] and special tokens below 1000
+    std::vector<int32_t> ids((size_t)P * L, 0), tt((size_t)P * L, 0), lens(P);
+    uint32_t s = 0x9E3779B9u;
+    for (int p = 0; p < P; ++p) {
+        lens[p] = std::max(1, L - p * L / P);
+        for (int t = 0; t < lens[p]; ++t) {
+            s = s * 1664525u + 1013904223u;
+            ids[(size_t)p * L + t] = id0 + (int)((s >> 8) % (uint32_t)(V - id0));
+            tt[(size_t)p * L + t] = 3 * t >= lens[p];
+        }
+    }
+    std::vector<float> mx(P), sp(P);
+    int rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, mx.data(), h->stream, true, true);
+    if (!rc) rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, sp.data(), h->stream, true, false);
+    ce_free_ws(m);                                      // the next call sizes its workspace for its own batch
+    mx_free_ws(m);
+    if (rc) return rc;
+    float d = 0.f;
+    for (int p = 0; p < P; ++p)
+        if (std::isfinite(mx[p]) && std::isfinite(sp[p])) d = std::max(d, std::fabs(mx[p] - sp[p]));
+    m->mx_default = d <= CE_PROBE_TOL;
+    return RAG_OK;
 }
 
 int embed_dim(const rag_ctx* h) { return h->emb ? h->emb->cfg.hidden : -1; }

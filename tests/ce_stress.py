@@ -1,0 +1,115 @@
+"""Stress weights for the cross-encoder tests (a helper module, not a conftest): deterministic transforms of
+oracle/bert_oracle.seeded_weights towards what trained BERT-family checkpoints look like.
+
+Seeded weights are i.i.d. Gaussian at one mild scale: layer-0 attention logits have a standard deviation of about 2.5 per row and
+no feature is an outlier. MiniLM is distilled from BERT's attention distributions, so many of its heads are sharp, and its
+LayerNorms have a few outlier dimensions. Every transform returns a new state dict and checks its own target on a fixed batch in
+numpy (`stats`), so that a later edit cannot quietly make the stress mild again; tests/test_ce_stress_targets.py pins the targets
+of the levels tests/test_cross_encoder_stress_gpu.py runs."""
+import math
+
+import numpy as np
+
+from oracle import bert_oracle as B
+
+OUTLIER_DIMS = (7, 100, 222, 333)
+
+
+def probe_batch(cfg, pairs=4, L=64, seed=0):
+    """A fixed batch of full-length pairs: token ids above the special / unused ids when the vocabulary has them, type 1 from
+    position 18."""
+    rng = np.random.default_rng(seed)
+    lo = 1000 if cfg["vocab_size"] > 2000 else 5
+    L = min(L, cfg["max_pos"])
+    ids = rng.integers(lo, cfg["vocab_size"], (pairs, L)).astype(np.int64)
+    tt = np.zeros((pairs, L), dtype=np.int64)
+    tt[:, 18:] = 1
+    return ids, tt, np.full(pairs, L, dtype=np.int64)
+
+
+def stats(w, cfg, dims=OUTLIER_DIMS):
+    """On probe_batch, float64:
+    attn_std  layer-0 attention logits (q.k / sqrt(d_head)): standard deviation over the keys of a row, mean over rows
+    outlier   mean |embedding-LayerNorm output| on `dims` / the same on the other dims
+    gelu_tail fraction of layer-0 FFN-up pre-activations (the GELU inputs) with |x| > 5"""
+    ids, tt, _ = probe_batch(cfg)
+    W = {k: v.astype(np.float64) for k, v in w.items()}
+    P, L = ids.shape
+    H, nh = cfg["hidden"], cfg["heads"]
+    dh = H // nh
+    x = (W["bert.embeddings.word_embeddings.weight"][ids] + W["bert.embeddings.token_type_embeddings.weight"][tt]
+         + W["bert.embeddings.position_embeddings.weight"][np.arange(L)][None])
+    x = B._ln(x, W["bert.embeddings.LayerNorm.weight"], W["bert.embeddings.LayerNorm.bias"], cfg["eps"])
+    mask = np.zeros(H, dtype=bool)
+    mask[list(dims)] = True
+    outlier = np.abs(x[..., mask]).mean() / np.abs(x[..., ~mask]).mean()
+    p = "bert.encoder.layer.0."
+    sp = lambda t: t.reshape(P, L, nh, dh).transpose(0, 2, 1, 3)
+    q = sp(x @ W[p + "attention.self.query.weight"].T + W[p + "attention.self.query.bias"])
+    k = sp(x @ W[p + "attention.self.key.weight"].T + W[p + "attention.self.key.bias"])
+    s = q @ k.transpose(0, 1, 3, 2) / math.sqrt(dh)
+    attn_std = float(s.std(-1).mean())
+    # the GELU inputs of layer 0, after the attention block (the oracle's own layer, without its FFN)
+    a = np.exp(s - s.max(-1, keepdims=True))
+    a /= a.sum(-1, keepdims=True)
+    v = sp(x @ W[p + "attention.self.value.weight"].T + W[p + "attention.self.value.bias"])
+    ctx = (a @ v).transpose(0, 2, 1, 3).reshape(P, L, H)
+    o = ctx @ W[p + "attention.output.dense.weight"].T + W[p + "attention.output.dense.bias"]
+    x = B._ln(o + x, W[p + "attention.output.LayerNorm.weight"], W[p + "attention.output.LayerNorm.bias"], cfg["eps"])
+    hpre = x @ W[p + "intermediate.dense.weight"].T + W[p + "intermediate.dense.bias"]
+    return dict(attn_std=attn_std, outlier=float(outlier), gelu_tail=float((np.abs(hpre) > 5).mean()))
+
+
+def _layers(cfg):
+    return [f"bert.encoder.layer.{l}." for l in range(cfg["layers"])]
+
+
+def sharp(w, cfg, f):
+    """Query and key weights of every layer times f: attention logits times ~f^2 (sharp heads)."""
+    out = dict(w)
+    for p in _layers(cfg):
+        for nm in ("query", "key"):
+            out[p + f"attention.self.{nm}.weight"] = (w[p + f"attention.self.{nm}.weight"] * np.float32(f)).astype(np.float32)
+    before, after = stats(w, cfg)["attn_std"], stats(out, cfg)["attn_std"]
+    assert after >= 0.9 * f * f * before, (before, after)
+    return out
+
+
+def outliers(w, cfg, g, b=0.0, dims=OUTLIER_DIMS):
+    """LayerNorm gamma times g and beta + b on `dims`, in every LayerNorm including the embedding one: a few hidden features
+    ~g times larger than the rest through the whole residual stream."""
+    out = dict(w)
+    names = ["bert.embeddings.LayerNorm."] + [p + s for p in _layers(cfg) for s in ("attention.output.LayerNorm.", "output.LayerNorm.")]
+    idx = list(dims)
+    for n in names:
+        gam, bet = w[n + "weight"].copy(), w[n + "bias"].copy()
+        gam[idx] *= np.float32(g)
+        bet[idx] += np.float32(b)
+        out[n + "weight"], out[n + "bias"] = gam, bet
+    r = stats(out, cfg, dims)["outlier"]
+    assert r >= 0.7 * g, r
+    return out
+
+
+def ffn_tails(w, cfg, f):
+    """FFN-up (intermediate) weights of every layer times f: the GELU sees inputs well past |x| = 5."""
+    out = dict(w)
+    for p in _layers(cfg):
+        out[p + "intermediate.dense.weight"] = (w[p + "intermediate.dense.weight"] * np.float32(f)).astype(np.float32)
+    tail = stats(out, cfg)["gelu_tail"]
+    assert tail >= 0.01, tail
+    return out
+
+
+def centre_logits(w, cfg):
+    """Classifier bias set so that the oracle's logits on probe_batch (at two lengths) have mean 0: the sigmoid is steepest there,
+    so the 1e-3 score bar is tightest."""
+    ids, tt, lens = probe_batch(cfg, pairs=8)
+    lens = lens.copy()
+    lens[::2] = lens[::2] // 2
+    out = dict(w)
+    out["classifier.bias"] = np.zeros(1, dtype=np.float32)
+    z = B.forward_logits(out, cfg, ids, tt, lens, fast_erf=True)
+    out["classifier.bias"] = np.array([-z.mean()], dtype=np.float32)
+    assert abs(B.forward_logits(out, cfg, ids, tt, lens, fast_erf=True).mean()) < 1e-3
+    return out
