@@ -189,7 +189,9 @@ int rag_pairwise_cosine_f64_host(rag_handle_t h, const double* a_host, int m, co
  * lists_host: [Q][n_lists][list_len] int64 keys, -1 = padding (only at the tail of a list).
  * For each query: score[key] += 1.0/(rrf_k+rank) (rank from 1, list order), sort desc, first-seen
  * order on ties, top_k. Outputs -1 padded; ranks_out[Q][top_k][n_lists] = 1-based rank of the key's first
- * occurrence in each list (0 = absent) (may be NULL). */
+ * occurrence in each list (0 = absent) (may be NULL).
+ * n_lists * list_len <= 1024 items per query (more: RAG_ERR_ARG); keys are any int64 >= 0; list_len = 0 is legal (nothing
+ * to fuse, nothing is read: all outputs are padding); top_k may exceed the number of distinct keys. */
 int rag_rrf_fuse_host(rag_handle_t h, const int64_t* lists_host, int n_queries, int n_lists, int list_len,
                       int rrf_k, int top_k, int64_t* keys_out_host, double* scores_out_host,
                       int32_t* ranks_out_host);
@@ -227,7 +229,8 @@ int rag_mmr_select_dev(rag_handle_t h, const float* q_dev, const int32_t* rows_d
  *      (rag/chunking.py:153-199): sentence i joins the running chunk when cos(running pairwise average, e_i) >= threshold
  *      and the chunk stays <= max_chunk characters, else the chunk closes if it has >= min_chunk characters (otherwise
  *      the sentence is absorbed). emb[n][dim] sentence embeddings, sent_len[n] = len(sentence);
- *      group_out[n] = chunk number of each sentence. */
+ *      group_out[n] = chunk number of each sentence. n >= 1, 1 <= dim <= 8192 (the running average lives in LDS as
+ *      float64: 64 KiB at the limit), else RAG_ERR_ARG. */
 int rag_chunk_chain_host(rag_handle_t h, const float* emb_host, const int32_t* sent_len_host, int n, int dim,
                          double threshold, int max_chunk, int min_chunk, int32_t* group_out_host);
 
@@ -280,7 +283,9 @@ int rag_bm25_scores_adhoc_host(rag_handle_t h, const int64_t* indptr_host, const
                                const int32_t* terms_host, int n_queries, double* out_host);
 
 /* ---- weighted linear fusion + top-k: replaces rag/retrieval.py:294-322
- *      hybrid = alpha*semantic + beta*keyword + gamma*temporal, stable sort desc, [:top_k]. */
+ *      hybrid = alpha*semantic + beta*keyword + gamma*temporal, stable sort desc, [:top_k].
+ *      0 < top_k <= min(n, 1024), else RAG_ERR_ARG; hybrid_out[n] holds every fused score, idx_out[top_k] the order. +-inf
+ *      inputs sort as in Python; NaN fused scores are unspecified (as the reference's own sort is). */
 int rag_linear_fuse_topk_host(rag_handle_t h, const double* semantic_host, const double* keyword_host,
                               const double* temporal_host /*NULL = zeros*/, int n, double alpha, double beta,
                               double gamma, int top_k, int32_t* idx_out_host, double* hybrid_out_host);
@@ -340,11 +345,14 @@ int rag_embed_dim(rag_handle_t h, int* dim_out);
  *      pairs are [CLS] query [SEP] passage [SEP] truncated 'longest_first' to max_length L_pair (what CrossEncoder.predict's
  *      tokenizer call does; the reference's max_length is 512, rag/reranker.py:290-294) and padded to it; outputs per query:
  *      ids_out[k] doc ids (-1 padded), scores_out[k] = sigmoid(logit) as float64, logits_out[k] raw logits,
- *      cand_out[pool] (may be NULL) the candidate list that was reranked. */
+ *      cand_out[pool] (may be NULL) the candidate list that was reranked. 0 < k <= pool <= 256.
+ *      Token store: 1 <= L <= 512, ids in [0, 65535] (the resident store is 16 bits wide); anything else is RAG_ERR_ARG. */
 int rag_tokens_load_host(rag_handle_t h, const int32_t* tokens_host, const int32_t* lens_host, int64_t n_rows, int L);
 /* Chunked form for stores that should not exist as one host array (a replicated 100M-passage store, SURVEY.md section 8e, is
  * 45 GB resident as uint16 and would be 90 GB as one int32 host array): reserve once, then append row blocks in order from
- * DEVICE memory (tokens_dev[n][L] int32, lens_dev[n]); each append returns after its rows are resident and checked. */
+ * DEVICE memory (tokens_dev[n][L] int32, lens_dev[n]); each append returns after its rows are resident and checked.
+ * An append before rag_tokens_reserve, past the reservation, or with an id outside [0, 65535] is RAG_ERR_ARG and is rejected
+ * whole: the rows appended before stay, the row count does not move, and the same row range may be appended again. */
 int rag_tokens_reserve(rag_handle_t h, int64_t n_rows_total, int L);
 int rag_tokens_append_dev(rag_handle_t h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, void* stream);
 int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
@@ -354,7 +362,9 @@ int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_
 
 /* The pipeline's two small kernels on their own (row-sharded composition): pair assembly from GLOBAL
  * candidate doc ids against a replicated token store whose first row has id token_id_base; and sigmoid + stable top-k of
- * the logits of a [Q][pool] candidate table (rag/reranker.py:359,372-376). */
+ * the logits of a [Q][pool] candidate table (rag/reranker.py:359,372-376). rag_rerank_topk_dev: 0 < k <= pool <= 256
+ * (else RAG_ERR_ARG); slots with cand < 0 are skipped wherever they sit; equal scores keep candidate order; outputs are
+ * padded with -1 / 0.0 / 0.0. */
 int rag_ce_build_pairs_dev(rag_handle_t h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev,
                            int n_queries, int pool, int64_t token_id_base, int L_pair, int cls_id, int sep_id,
                            int32_t* ids_out_dev, int32_t* tt_out_dev, int32_t* lens_out_dev, void* stream);

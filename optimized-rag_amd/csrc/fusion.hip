@@ -15,6 +15,7 @@ __device__ __forceinline__ unsigned hash64(uint64_t x) {
 }
 
 // One workgroup per query. List l of query q starts at lists + q*query_stride + l*list_stride (len keys, -1 padding).
+// len may be 0 (T = 0: no loop below that divides by len or reads `lists` runs; the outputs are all padding).
 __global__ __launch_bounds__(256) void rrf_fuse_kernel(const int64_t* __restrict__ lists, int L, int len, int64_t list_stride,
                                                         int64_t query_stride, int rrf_k, int top_k, int64_t* __restrict__ keys_out,
                                                         double* __restrict__ scores_out, int32_t* __restrict__ ranks_out) {
@@ -106,7 +107,7 @@ int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, in
     ARG_CHECK(h, Q > 0 && L > 0 && len >= 0 && top_k > 0, "rrf: sizes must be positive");
     ARG_CHECK(h, (int64_t)L * len <= RRF_MAX_ITEMS, "rrf: n_lists*list_len must be <= 1024");
     ARG_CHECK(h, lists_dev && keys_dev && scores_dev, "rrf: null pointer");
-    if (len == 0) len = 1, list_stride = 0;       // nothing to fuse: every item reads as padding below
+    // len == 0: nothing to fuse. The kernel then has T = 0 items, reads nothing from lists_dev and writes only the padding.
     hipLaunchKernelGGL(rrf_fuse_kernel, dim3(Q), dim3(256), 0, st, lists_dev, L, len, list_stride, query_stride, rrf_k, top_k,
                        keys_dev, scores_dev, ranks_dev);
     HIP_TRY(h, hipGetLastError());
@@ -128,8 +129,7 @@ int rrf_fuse_host(rag_ctx* h, const int64_t* lists, int Q, int L, int len, int r
     double* sd = stage_take<double>(p, n_out);
     int32_t* rd = ranks_out ? stage_take<int32_t>(p, n_out * L) : nullptr;
     if (T) HIP_TRY(h, hipMemcpyAsync(ld, lists, (size_t)Q * T * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rrf_fuse_kernel, dim3(Q), dim3(256), 0, st, ld, L, std::max(len, 1), (int64_t)len, (int64_t)T, rrf_k, top_k,
-                       kd, sd, rd);
+    hipLaunchKernelGGL(rrf_fuse_kernel, dim3(Q), dim3(256), 0, st, ld, L, len, (int64_t)len, (int64_t)T, rrf_k, top_k, kd, sd, rd);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(keys_out, kd, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(scores_out, sd, n_out * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -66,8 +66,8 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(const float* __restrict
         // ---- score every live candidate, first-maximum argmax ----------------------------------
         double best = -INFINITY;
         int best_i = 0x7fffffff;
-        for (int j = tid; j < n; j += 256) {
-            if (!alive[j]) continue;
+        for (int j = tid; j < n; j += 256) {            // n <= MMR_MAX_N = the workgroup size: at most one candidate per thread, so
+            if (!alive[j]) continue;                    // ties are decided by the two reductions below, never in this loop
             double s;
             if (variant == 0) {
                 const double div = t == 0 ? 1.0 : 1.0 - maxsim[j];

@@ -137,6 +137,12 @@ int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens
     int n_bad = 0;                                                   // synchronous check: a load path, not a search path
     HIP_TRY(h, hipMemcpyAsync(&n_bad, h->tok_bad, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
+    if (n_bad != 0) {
+        // the block is rejected whole (tok_rows does not move, its slots are overwritten by the next append); the counter starts
+        // again at zero, or every later - valid - append on this handle would be rejected with it
+        HIP_TRY(h, hipMemsetAsync(h->tok_bad, 0, sizeof(int), st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
     ARG_CHECK(h, n_bad == 0, "tokens_append: token ids must be in [0, 65535]");
     h->tok_rows += n;
     return RAG_OK;

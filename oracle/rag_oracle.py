@@ -5,8 +5,8 @@ leg may import this module; the product package never does.
 Every function cites the reference file:line (under /root/reference) whose behaviour it restates.
 
 Pinning status
-  * cosine, hybrid_search (linear fusion, keyword-overlap path, temporal decay), RRF, both MMR variants,
-    consistency checker, context compressor, OpenAI/cross-encoder re-ranker post-processing:
+  * cosine, hybrid_search (linear fusion, keyword-overlap path, temporal decay), RRF, both MMR variants, the semantic
+    chunker's sentence chain, consistency checker, context compressor, OpenAI/cross-encoder re-ranker post-processing:
     PINNED by tests/golden/*.json|npz, produced by tools/make_golden.py running the reference's own
     Python in the build container (tests/test_oracle_golden.py).
   * BM25Okapi: third-party `rank-bm25` (requirements.txt:22, pinned only as >=0.2.2) is absent from the
@@ -283,13 +283,14 @@ def mmr_class(query_emb, embs, top_k, lam):
     return sel, sel_scores
 
 
-def mmr_helper(query_emb, embs, k, lam):
-    """λ·rel − (1-λ)·max_sim; returns all positions unchanged when len <= k (helpers.py:206-207)."""
+def mmr_helper(query_emb, embs, k, lam, with_scores=False):
+    """λ·rel − (1-λ)·max_sim; returns all positions unchanged when len <= k (helpers.py:206-207).
+    with_scores: also return the score each pick won with (the reference computes and discards it)."""
     n = len(embs)
     if n <= k:
-        return list(range(n))
+        return (list(range(n)), None) if with_scores else list(range(n))
     remaining = list(range(n))
-    sel = []
+    sel, sel_scores = [], []
     rel = [cosine(query_emb, e) for e in embs]
     while len(sel) < k and remaining:
         best, best_s = None, None
@@ -299,8 +300,81 @@ def mmr_helper(query_emb, embs, k, lam):
             if best is None or s > best_s:
                 best, best_s = i, s
         sel.append(best)
+        sel_scores.append(best_s)
         remaining.remove(best)
-    return sel
+    return (sel, sel_scores) if with_scores else sel
+
+
+def mmr_greedy(rel, sim, top_k, lam, variant):
+    """The two greedy loops above on PRECOMPUTED cosines (rel[i] = cos(query, e_i), sim[i][j] = cos(e_i, e_j)), carrying
+    each candidate's max over the selected set forward instead of recomputing it every round. max() is exact and does
+    not depend on the order of its arguments, and the score expression is the same, so picks and scores are bit-identical
+    to mmr_class (variant 0) / mmr_helper (variant 1, WITHOUT its len <= k shortcut) fed the same cosines
+    (tests/test_oracle_golden.py::test_mmr_greedy_is_the_two_loops). O(k n) instead of O(k^2 n) cosines: for pools of 256.
+    Returns (positions, scores)."""
+    n = len(rel)
+    remaining = list(range(n))
+    maxsim = [None] * n
+    sel, sel_scores = [], []
+    while len(sel) < top_k and remaining:
+        best, best_s = None, None
+        for i in remaining:
+            if variant == 0:
+                s = lam * rel[i] + (1 - lam) * ((1 - maxsim[i]) if sel else 1.0)
+            else:
+                s = lam * rel[i] - (1 - lam) * (maxsim[i] if sel else 0.0)
+            if best is None or s > best_s:
+                best, best_s = i, s
+        sel.append(best)
+        sel_scores.append(best_s)
+        remaining.remove(best)
+        for i in remaining:
+            c = sim[i][best]
+            if maxsim[i] is None or c > maxsim[i]:
+                maxsim[i] = c
+    return sel, sel_scores
+
+
+# ---------------------------------------------------------------------------------------------
+# a8b semantic chunker chain   (rag/chunking.py:153-199, cosine :205-210, pairwise average :212-221)
+# ---------------------------------------------------------------------------------------------
+
+
+def chunk_chain(embs, sent_len, threshold, max_chunk, min_chunk, order=None, with_sims=False):
+    """Sentence loop of SemanticChunker.chunk on plain Python floats. The running chunk carries `cur`, which starts as the
+    embedding of its first sentence and becomes (cur + e_i) / 2 each time a sentence is taken in (an average of TWO vectors,
+    not the chunk mean), and `size`, the sum of its sentences' lengths. Sentence i is taken in when
+    cos(cur, e_i) >= threshold and size + len_i <= max_chunk; failing that the chunk is closed and sentence i opens the next
+    one - unless size < min_chunk, in which case the sentence is absorbed all the same. The cosine is three left-to-right
+    sums, math.sqrt of the two squared norms, dot / (m1 * m2), and 0.0 when either norm is zero.
+    order: a permutation of range(dim) in which the three sums visit the coordinates (None = 0..dim-1). Tests use it to
+    prove an input's sums exact: the similarities must not depend on it.
+    Returns groups (chunk number per sentence), or (groups, sims) with sims[i - 1] = the cosine seen by sentence i."""
+    rows = [[float(x) for x in e] for e in embs]
+    if not rows:
+        return ([], []) if with_sims else []
+    idx = range(len(rows[0])) if order is None else [int(d) for d in order]
+    cur, size, chunk_id = rows[0], int(sent_len[0]), 0
+    groups, sims = [0], []
+    for i in range(1, len(rows)):
+        e = rows[i]
+        dot = sq_c = sq_e = 0.0
+        for d in idx:
+            dot += cur[d] * e[d]
+            sq_c += cur[d] * cur[d]
+            sq_e += e[d] * e[d]
+        m1, m2 = math.sqrt(sq_c), math.sqrt(sq_e)
+        sim = dot / (m1 * m2) if m1 and m2 else 0.0
+        sims.append(sim)
+        li = int(sent_len[i])
+        if (sim >= threshold and size + li <= max_chunk) or size < min_chunk:
+            cur = [(a + b) / 2 for a, b in zip(cur, e)]
+            size += li
+        else:
+            chunk_id += 1
+            cur, size = e, li
+        groups.append(chunk_id)
+    return (groups, sims) if with_sims else groups
 
 
 # ---------------------------------------------------------------------------------------------
@@ -428,6 +502,18 @@ def longest_first_lengths(n1, n2, max_content):
 
 def sigmoid(x):
     return 1 / (1 + math.exp(-x))                                 # reranker.py:359
+
+
+def rerank_topk(logits, cand, k):
+    """CrossEncoderReranker.rerank's post-processing (reranker.py:359, 372-376) over one query's candidate slots: sigmoid of
+    every slot that holds a candidate (cand[j] >= 0), stable sort by score descending (candidate order on ties), first k.
+    Returns (ids, scores, logits) of length k, padded with -1 / 0.0 / 0.0."""
+    live = [j for j in range(len(cand)) if cand[j] >= 0]
+    sc = {j: sigmoid(float(logits[j])) for j in live}
+    top = sorted(live, key=lambda j: sc[j], reverse=True)[:k]
+    pad = k - len(top)
+    return ([int(cand[j]) for j in top] + [-1] * pad, [sc[j] for j in top] + [0.0] * pad,
+            [float(logits[j]) for j in top] + [0.0] * pad)
 
 
 def openai_rerank_scores(query_emb, content_embs, originals):     # reranker.py:67-77

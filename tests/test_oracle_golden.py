@@ -130,3 +130,86 @@ def test_reranker_postprocessing(golden_dir):
     assert [int(i) for i in order] == [e["pos"] for e in cr["expected"]]
     for i, e in zip(order, cr["expected"]):
         assert abs(sig[i] - e["cross_encoder_score"]) < 1e-15
+
+
+def test_chunk_chain_reproduces_the_reference_chunks(golden_dir):
+    """O.chunk_chain, fed the sentences and embeddings the reference's SemanticChunker saw, groups them into the chunks the
+    reference recorded (tests/golden/cosine_sites.json["chunker"]): contents, chunk ids, sentence counts and sizes."""
+    import re
+    g = load(golden_dir, "cosine_sites.json")
+    table = g["embeddings_noise09"]
+    n_chain = 0
+    for c in g["chunker"]:
+        text, md = c["text"], c["metadata"]
+        sentences = [s.strip() for s in re.split(r'(?<=[.!?])\s+', text) if s.strip()]
+        if not sentences:
+            got = []
+        elif len(text) < c["min_chunk_size"]:                     # the whole text is one chunk before any embedding is made
+            got = [{"content": text, "metadata": {**(md or {}), "chunk_id": 0}}]
+        else:
+            groups = O.chunk_chain([table[s] for s in sentences], [len(s) for s in sentences], c["threshold"],
+                                   c["max_chunk_size"], c["min_chunk_size"])
+            assert groups[0] == 0 and all(b - a in (0, 1) for a, b in zip(groups, groups[1:]))
+            got = []
+            for cid in range(groups[-1] + 1):
+                content = " ".join(s for s, gi in zip(sentences, groups) if gi == cid)
+                got.append({"content": content, "metadata": {"chunk_id": cid, "num_sentences": groups.count(cid),
+                                                             "chunk_size": len(content), **(md or {})}})
+            n_chain += len(got) > 2
+        assert got == c["expected"]
+    assert n_chain >= 4                                           # joins and splits both happen in the fixture
+
+
+def test_mmr_greedy_is_the_two_loops():
+    """O.mmr_greedy (running max over precomputed cosines, used for pools of 256 where the O(k^2 n) loops take minutes) returns
+    bit-identical picks and scores to O.mmr_class / O.mmr_helper, on Gaussian inputs, on integer inputs full of exact ties, with
+    duplicates and a zero row, up to top_k = n."""
+    for seed, n, dim, integer in [(0, 1, 8, False), (1, 7, 3, True), (2, 24, 16, False), (3, 33, 5, True), (4, 64, 2, True),
+                                  (5, 40, 64, False)]:
+        rng = np.random.default_rng(seed)
+        embs = rng.integers(-3, 4, (n, dim)).astype(np.float64) if integer else rng.standard_normal((n, dim)).astype(np.float32).astype(np.float64)
+        if n > 4:
+            embs[3] = embs[1]
+            embs[2] = 0.0
+        q = embs[0] + 1.0 if integer else rng.standard_normal(dim)
+        rel0 = [O.cosine(q, e, empty_is_zero=True) for e in embs]
+        sim = [[O.cosine(a, b) for b in embs] for a in embs]
+        for lam in (0.0, 0.5, 0.7, 1.0):
+            for k in sorted({1, max(1, n // 2), n}):
+                assert O.mmr_greedy(rel0, sim, k, lam, 0) == O.mmr_class(q, embs, k, lam)
+                if n > k:
+                    assert O.mmr_greedy(rel0, sim, k, lam, 1) == O.mmr_helper(q, embs, k, lam, with_scores=True)
+                    assert O.mmr_helper(q, embs, k, lam) == O.mmr_greedy(rel0, sim, k, lam, 1)[0]
+
+
+def test_exact_chain_recipe_is_independent_of_the_summation_order():
+    """The input recipe of tests/small_inputs.py for the chunk chain: at every dimension the GPU test uses, the oracle's
+    similarities are IDENTICAL under the sequential and a randomly permuted summation order (every sum is exact), each chain
+    makes at least three chunks, and a threshold taken from the chain is met exactly on the chain again, where `>=` against `>`
+    decides the grouping."""
+    import small_inputs as SI
+    for dim in SI.CHAIN_DIMS:
+        for seed in range(3 if dim > 2000 else 6):
+            embs, lens = SI.exact_chain(seed, dim)
+            perm = np.random.default_rng(seed).permutation(dim)
+            g0, s0 = O.chunk_chain(embs, lens, 0.5, SI.CHAIN_MAX, SI.CHAIN_MIN, with_sims=True)
+            g1, s1 = O.chunk_chain(embs, lens, 0.5, SI.CHAIN_MAX, SI.CHAIN_MIN, order=perm, with_sims=True)
+            assert s0 == s1 and g0 == g1, (dim, seed)
+            assert g0[-1] >= 2, (dim, seed)
+            assert max(g0.count(c) for c in set(g0)) <= 9
+            t = SI.deciding_threshold(g0, s0, lens, SI.CHAIN_MAX, SI.CHAIN_MIN)
+            assert t is not None and t >= 0.5, (dim, seed)
+            gt, st_ = O.chunk_chain(embs, lens, t, SI.CHAIN_MAX, SI.CHAIN_MIN, with_sims=True)
+            assert gt == g0 and st_ == s0 and t in st_
+            assert O.chunk_chain(embs, lens, SI.next_up(t), SI.CHAIN_MAX, SI.CHAIN_MIN) != gt, (dim, seed)
+
+
+def test_rerank_topk_is_sigmoid_then_the_stable_sort(golden_dir):
+    cr = load(golden_dir, "rerankers.json")["cross"]
+    lg = [float(np.float32(x)) for x in cr["logits"]]
+    ids, sc, out_lg = O.rerank_topk(lg, list(range(100, 100 + len(lg))), cr["top_k"])
+    assert ids == [100 + e["pos"] for e in cr["expected"]]
+    assert all(abs(s - e["cross_encoder_score"]) < 1e-15 for s, e in zip(sc, cr["expected"]))
+    # empty slots are skipped wherever they sit, exact ties keep candidate order, short lists are padded
+    assert O.rerank_topk([40.0, 3.0, 50.0, 3.0, -1.0], [7, -1, 8, 9, 10], 4) == ([7, 8, 9, 10], [1.0, 1.0, O.sigmoid(3.0), O.sigmoid(-1.0)], [40.0, 50.0, 3.0, -1.0])
+    assert O.rerank_topk([1.0, 2.0], [-1, 5], 2) == ([5, -1], [O.sigmoid(2.0), 0.0], [2.0, 0.0])
