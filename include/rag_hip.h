@@ -57,7 +57,10 @@ int rag_set_option(rag_handle_t h, const char* name, int value);
  *      `ORDER BY embedding <=> %s::vector LIMIT %s`     (database/operations.py:126-137)
  * Rows are float32 (pgvector `vector(1536)` is float4). ids may be NULL (id = id_base + row).
  * Builds in HBM: fp32 master rows, fp16 unit-normalised rows (MFMA operand). Rows with a zero or
- * non-finite norm score 0.0 against every query (the reference's `return 0.0`, rag/retrieval.py:368-369). */
+ * non-finite norm score 0.0 against every query (the reference's `return 0.0`, rag/retrieval.py:368-369).
+ * ONLY those: every other float32 row or query - components that are all float32 denormals (norm down to 1e-45) up to
+ * a norm just below float32 overflow - is normalised in float64 and gets the cosine the float64 scan gives it
+ * (tests/test_dense_exactness_gpu.py sweeps 2^-140 ... 2^120; the device does not flush float32 denormals here). */
 int rag_index_load_host(rag_handle_t h, const float* emb_host, const int64_t* ids_host, int64_t id_base,
                         int64_t n_rows);
 int rag_index_load_dev(rag_handle_t h, const float* emb_dev, const int64_t* ids_dev, int64_t id_base,
@@ -125,7 +128,10 @@ int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, f
  * lower row first; ids_out[Q*k] (-1 padded), rows_out[Q*k] local row numbers (may be NULL),
  * scores_out[Q*k] = 1 - distance as float64. Identical id sets to the float64 exact scan hold BY CONSTRUCTION:
  * the fp16 MFMA pass only discards rows whose score is more than 2*eps below the k-th best (eps = proven bound on
- * the fp16 error), survivors are rescored in float64; a float64 scan of every row is the overflow fallback. */
+ * the fp16 error), survivors are rescored in float64; a float64 scan of every row is the overflow fallback.
+ * eps (rag_dense_stats.eps) is pinned by tests on worst-case rows whose fp16 products all err the same way: they reach
+ * max |fp16 score - cosine| = 0.85 eps at dim 64, 0.76 at dim 100, 0.78 at dim 384, 0.68 at dim 1536, and put a row of
+ * the exact top-k 1.29 to 1.49 eps below the k-th best fp16 score (tests/fp16_adversary.py). */
 int rag_dense_topk_host(rag_handle_t h, const float* q_host, int n_queries, int k, int tenant,
                         int64_t* ids_out_host, int32_t* rows_out_host, double* scores_out_host);
 int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int n_queries, int k, int tenant,
@@ -300,7 +306,13 @@ int rag_linear_fuse_topk_host(rag_handle_t h, const double* semantic_host, const
  * ids, hybrid_out the float64 hybrid scores; semantic / keyword / temporal_out (each [Q*k], may be NULL) are the
  * components the reference returns next to them. alpha must be > 0; tenant as in rag_dense_topk_dev. The postings must be
  * row-aligned with the index. Exact by the same construction as the dense search: the fp16 MFMA pass only discards rows
- * whose FUSED score is provably below the k-th best, survivors are rescored in float64. */
+ * whose FUSED score is provably below the k-th best, survivors are rescored in float64. The bound on the fused fp16-pass
+ * score is |alpha| * eps + 2^-21 * (|alpha| + |beta| * max|keyword| + |gamma| * max|temporal|): beta and gamma may have
+ * either sign, temporal scores any finite magnitude (their maximum is tracked), and max|keyword| is 1 unless the query
+ * postings hold negative idf values: then it is the larger of 1 and (k1 + 1) * (largest such |idf|) * (tokens of the
+ * query) / max, a bound on every negative raw score of that query, so keyword scores far below -1 (a long query over terms that most
+ * documents contain) are covered too.
+ * rag_dense_stats.eps after this call is the bound at max|keyword| = 1. */
 int rag_index_set_temporal_host(rag_handle_t h, const double* temporal_host, int64_t n_rows);
 int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                           int n_queries, int k, double alpha, double beta, double gamma, int tenant,

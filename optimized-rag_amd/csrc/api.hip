@@ -24,6 +24,7 @@ int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int
 int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
 int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
                     float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant);
+int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out);
 int bm25_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st);
@@ -581,7 +582,7 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
     // queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
     // shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
     const int QB = (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)8 << 30) / (n * 12)));
-    const size_t need = stage_size((size_t)QB * n, 8) + stage_size((size_t)QB * ld, 4) + 2 * stage_size(QB, 8) + stage_size(QB, 4) + stage_size(ld, 4);
+    const size_t need = stage_size((size_t)QB * n, 8) + stage_size((size_t)QB * ld, 4) + 2 * stage_size(QB, 8) + 2 * stage_size(QB, 4) + stage_size(ld, 4);
     if (need > h->lin_ws_bytes) {
         hipFree(h->lin_ws);
         h->lin_ws = nullptr;
@@ -596,7 +597,10 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
     double* mx = stage_take<double>(p, QB);
     unsigned long long* max_key = stage_take<unsigned long long>(p, QB);
     float* qscale = stage_take<float>(p, QB);
+    float* margin = stage_take<float>(p, QB);
     float* gt = (h->temporal != nullptr && gamma != 0.0) ? stage_take<float>(p, ld) : nullptr;
+    double neg_per_token = 0.0;
+    if (int rc = bm25_negative_bound_args(h, &neg_per_token)) return rc;
     for (int q0 = 0; q0 < Q; q0 += QB) {
         const int qc = std::min(QB, Q - q0);
         // ONE pass of the scoring kernel writes the float64 scores (exact fusion of the survivors), their float32 copy (the emission
@@ -605,8 +609,10 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
         HIP_TRY(h, hipMemsetAsync(max_key, 0, (size_t)qc * sizeof(unsigned long long), st));
         int rc = bm25_scores_dev(h, term_ptr_dev + q0, terms_dev, qc, raw, st, raw32, ld, max_key, tenant);
         if (rc) return rc;
-        if ((rc = linear_prepare(h, max_key, qc, n, h->temporal, beta, gamma, mx, qscale, q0 == 0 ? gt : nullptr, ld, st))) return rc;
-        const dense_fused fz = {raw32, ld, qscale, gt, raw, n, mx, h->temporal, alpha, beta, gamma};
+        const linear_neg_bound nb = {term_ptr_dev + q0, neg_per_token};
+        if ((rc = linear_prepare(h, max_key, nb, qc, n, h->temporal, beta, gamma, mx, qscale, margin, q0 == 0 ? gt : nullptr, ld, st)))
+            return rc;
+        const dense_fused fz = {raw32, ld, qscale, margin, gt, raw, n, mx, h->temporal, alpha, beta, gamma};
         rc = dense_search_fused(h, q_dev + (size_t)q0 * h->dim, qc, k, tenant, ids_out_dev + (size_t)q0 * k, rows_out_dev + (size_t)q0 * k,
                                 hybrid_out_dev + (size_t)q0 * k, st, &fz);
         if (rc) return rc;

@@ -95,6 +95,7 @@ struct rag_bm25_index {
     int ws_plan_q = 0;
     int plan_t = 64;                   // planned token slots per query of the CURRENT call (bm25_pick_plan_t), <= BM_PLAN_T
     double avgdl = 0, k1 = 1.5, b = 0.75;
+    double neg_idf_absmax = 0;         // largest |idf| among the negative idf values (0: none), for bm25_negative_bound_args
     int normalize = 1;                 // 0: top-k scores stay raw (row-sharded search divides by the GLOBAL max after the merge)
 };
 
@@ -1148,6 +1149,7 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
         int64_t e_t = 0;
         const int g = bm_plan_term(df, n_pad, &e_t);
         meta_h[(size_t)t] = {indptr[t], n_tab, idf[t], (int32_t)df, g};
+        if (idf[t] < 0.0) ix->neg_idf_absmax = std::max(ix->neg_idf_absmax, -idf[t]);
         n_tab += e_t;
     }
     ix->tab_entries = n_tab;
@@ -1490,6 +1492,18 @@ int bm25_set_normalize(rag_ctx* h, int on) {
 }
 
 int64_t bm25_n_docs(const rag_ctx* h) { return h->bm25 ? h->bm25->n_docs : -1; }
+
+// What bounds a NEGATIVE raw score from the query alone (linear_scale_kernel, the fused emission margin): a raw score is a sum over
+// the query's tokens of idf[t] * tf (k1+1) / (tf + k1 (1 - b + b dl / avgdl)), and the tf factor is at most k1 + 1 for k1 >= 0 and
+// 0 <= b <= 1 (the denominator is then >= tf), so no score is below -(tokens of the query) * neg_idf_absmax * (k1 + 1).
+// per_token_out = neg_idf_absmax * (k1 + 1): 0 when no idf is negative, +inf for parameters outside that range.
+int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out) {
+    if (!h->bm25) return RAG_ERR_ARG;
+    const rag_bm25_index* ix = h->bm25;
+    const bool std_params = ix->k1 >= 0.0 && ix->b >= 0.0 && ix->b <= 1.0;
+    *per_token_out = ix->neg_idf_absmax > 0.0 ? (std_params ? ix->neg_idf_absmax * (ix->k1 + 1.0) : (double)INFINITY) : 0.0;
+    return RAG_OK;
+}
 
 // HBM bytes of an index built from these postings, from the host CSR offsets alone (no device call): postings (doc + impact,
 // 12 B each), per-term metadata (32 B each) and the bracket tables (4 B per entry, <= nnz bytes by construction).

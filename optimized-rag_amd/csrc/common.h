@@ -255,6 +255,7 @@ int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64
 struct dense_fused {
     const float* bias; int64_t bias_ld;          // float32 raw BM25 scores [Q][bias_ld] (written by the scoring kernel itself)
     const float* qscale;                         // [Q] float(beta / max of the query)
+    const float* margin;                         // [Q] added to 2 * eps for a query whose |keyword score| exceeds 1 (linear_scale_kernel)
     const float* gt;                             // [bias_ld] float(gamma * temporal) or null
     const double* raw; int64_t n;
     const double* mx; const double* temporal;
@@ -265,8 +266,10 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
 void comm_free(rag_ctx* h);
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
                 int64_t* lists_dev, double* scores_ws_dev, hipStream_t st);
-int linear_prepare(rag_ctx* h, const unsigned long long* max_key, int Q, int64_t n, const double* temporal, double beta, double gamma, double* mx,
-                   float* qscale, float* gt, int64_t ld, hipStream_t st);
+// the query terms and what bounds a negative raw BM25 score from them (bm25_negative_bound_args)
+struct linear_neg_bound { const int32_t* term_ptr; double per_token; };
+int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bound nb, int Q, int64_t n, const double* temporal,
+                   double beta, double gamma, double* mx, float* qscale, float* margin, float* gt, int64_t ld, hipStream_t st);
 int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, int Q, int k, const dense_fused* fz, double* sem_out,
                       double* kw_out, double* tmp_out, hipStream_t st);
 int dense_free(rag_ctx* h);

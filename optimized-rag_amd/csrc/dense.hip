@@ -25,7 +25,8 @@
 #define WAVE 64
 
 // ------------------------------------------------------------------------------------------------
-// K0: one wave per row: out16[row] = fp16(2^7 * x/|x|), zero row when |x| is 0 or not finite.
+// K0: one wave per row: out16[row] = fp16(2^7 * x/|x|), zero row when |x| is 0 or not finite. Every other float32 row,
+// from all-denormal components up to a norm just below overflow, is scaled in double and gets its ordinary cosine.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __restrict__ in, half_t* __restrict__ out,
                                                               int64_t n_rows, int dim, int dim_pad, int* bad_rows) {
@@ -42,7 +43,11 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
         const bool ok = (acc > 0.0) && (acc < 1e300);          // false for 0, inf and NaN
-        const float inv = ok ? (float)((double)(1 << RAG_SCALE_LOG2) / sqrt(acc)) : 0.0f;
+        // The scale stays in double and so does the product: as a float it overflows to +inf for a norm below 128 / FLT_MAX
+        // ~ 3.8e-37 (a row of float32 denormals), the fp16 row is then inf / NaN and no threshold stage ever emits it. In
+        // double every finite non-zero float32 row lands on norm 128 (|x| * inv <= 128: the one rounding to float is exact
+        // enough, the cast to fp16 rounds to nearest even).
+        const double inv = ok ? (double)(1 << RAG_SCALE_LOG2) / sqrt(acc) : 0.0;
         if (!ok && lane == 0 && bad_rows) atomicAdd(bad_rows, 1);
         half_t* o = out + row * dim_pad;
         for (int i = lane * 4; i < dim_pad; i += 256) {
@@ -50,10 +55,10 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
             if (i < dim) {
                 float4 v = *reinterpret_cast<const float4*>(x + i);
                 if (ok) {
-                    hv[0] = (half_t)(v.x * inv);
-                    hv[1] = (half_t)(v.y * inv);
-                    hv[2] = (half_t)(v.z * inv);
-                    hv[3] = (half_t)(v.w * inv);
+                    hv[0] = (half_t)(float)((double)v.x * inv);
+                    hv[1] = (half_t)(float)((double)v.y * inv);
+                    hv[2] = (half_t)(float)((double)v.z * inv);
+                    hv[3] = (half_t)(float)((double)v.w * inv);
                 }
             }
             *reinterpret_cast<half4*>(o + i) = hv;
@@ -479,9 +484,11 @@ __device__ __forceinline__ void select_wave(uint64_t* __restrict__ c, uint64_t* 
 //     (count may exceed the RAG_TILE slots of the list: readers clamp);
 //   sc_list (the second-pass select): a re-emission that fitted replaces the query's candidate list - the compacted keys are
 //     written to the query's own buffer straight from registers - and clears its overflow mark.
+//   margin (fused search): per-query addition to two_eps, indexed by the query's number in the batch (linear_scale_kernel).
 struct select_extra {
     int* ovf_list; int* ovf_count;
     const int* sc_list; uint64_t* sc_cand; int* sc_n_sorted; float* sc_bound;
+    const float* margin;
 };
 __global__ __launch_bounds__(256) void select_kernel(uint64_t* __restrict__ cand, unsigned* __restrict__ cnt,
                                                       float* __restrict__ tau, float* __restrict__ bound,
@@ -503,6 +510,7 @@ __global__ __launch_bounds__(256) void select_kernel(uint64_t* __restrict__ cand
     float tau_new;
     int n_top;
     const int dst_q = ex.sc_list != nullptr ? ex.sc_list[q] : 0;
+    if (ex.margin != nullptr) two_eps += ex.margin[ex.sc_list != nullptr ? dst_q : q];
     uint64_t* copy_to = (ex.sc_list != nullptr && !overflow) ? ex.sc_cand + (size_t)dst_q * RAG_CAND_CAP : nullptr;
     if (n_in <= SEL_REG_SMALL * 64) select_wave<SEL_REG_SMALL>(c, spill, n_in, k, two_eps, tau_in, lane, tau_new, n_top, copy_to);
     else if (n_in <= SEL_REG_MID * 64) select_wave<SEL_REG_MID>(c, spill, n_in, k, two_eps, tau_in, lane, tau_new, n_top, copy_to);
@@ -826,8 +834,16 @@ __global__ __launch_bounds__(256) void overflow_gather_kernel(int* __restrict__ 
 // one over the tenant's documents (atomicMax in that same kernel; 0 = no document). Under a tenant filter the corpus hybrid_search
 // was handed is the tenant's own documents (`WHERE agent_id = %s`, rag/document_store.py:457), as rag_bm25_topk_* do.
 // -> mx[q] = `max_score if max_score > 0 else 1.0` (rag/retrieval.py:343-344), qscale[q] = float(beta / mx[q]) for the emission.
-__global__ void linear_scale_kernel(const unsigned long long* __restrict__ max_key, int Q, double beta, double* __restrict__ mx,
-                                    float* __restrict__ qscale) {
+// margin[q]: the emission margin of dense_search_fused assumes |keyword score| <= 1, which holds whenever every raw score is
+// >= 0. Negative raw scores (negative idf values) are divided by the same mx and can be of any size - all of them, divided by
+// 1.0, when no score is positive. No raw score of query q is below -(number of its tokens) * per_token, per_token =
+// (largest |idf| among the negative idf values) * (k1 + 1) (bm25_negative_bound_args; 0 when no idf is negative): that over mx
+// bounds the keyword scores below zero (kw_neg), and what it exceeds 1 by is added to the margin:
+// margin[q] = 2 * |beta| * max(0, kw_neg - 1) * 2^-21 (the float32 roundings of raw32 * qscale, as in dense_search_fused).
+// per_token = +inf (negative idf values with BM25 parameters outside k1 >= 0, 0 <= b <= 1) makes the margin infinite: nothing
+// is dropped, the buffer overflows, and the float64 scan answers - slow, and still exact.
+__global__ void linear_scale_kernel(const unsigned long long* __restrict__ max_key, linear_neg_bound nb, int Q, double beta,
+                                    double* __restrict__ mx, float* __restrict__ qscale, float* __restrict__ margin) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= Q) return;
     const unsigned long long kq = max_key[q];
@@ -839,6 +855,9 @@ __global__ void linear_scale_kernel(const unsigned long long* __restrict__ max_k
     const double d = m > 0.0 ? m : 1.0;
     mx[q] = d;
     qscale[q] = (float)(beta / d);
+    const int n_tok = nb.term_ptr[q + 1] - nb.term_ptr[q];
+    const double kw_neg = (nb.per_token > 0.0 && n_tok > 0) ? nb.per_token * n_tok / d : 0.0;
+    margin[q] = beta == 0.0 ? 0.f : (float)(2.0 * fabs(beta) * fmax(0.0, kw_neg - 1.0) / 2097152.0 * 1.0001);    // (0 * inf is NaN)
 }
 
 // float32 recency term of every row for the emission: gamma * temporal (zero past the last row)
@@ -1051,6 +1070,11 @@ static double fp16_pass_eps(int dim_pad) {
     // fp32 accumulation of dim_pad terms (any order, rel <= dim_pad * 2^-24 of sum |a_i b_i| <= 1),
     // fp32 normalisation of both rows (rel ~3 * 2^-24 each), small absolute slack for the 2^7 scaling's
     // residual subnormals.  Cauchy-Schwarz: sum |q_i c_i| <= 1.
+    // PINNED by tests/test_dense_exactness_gpu.py on the worst-case rows of tests/fp16_adversary.py (components at fp16 rounding
+    // midpoints, every product's error pointing the same way). max |S~ - S| / eps reached there (numpy emulation of the pass):
+    // 0.85 at dim 64, 0.76 at dim 100, 0.78 at dim 384, 0.68 at dim 1536; a row of the exact top-k then sits 1.29 to 1.49 eps
+    // below s~(k). So half this margin, a tenth of this eps, or a threshold of s~(k) - eps each lose a row and fail those tests.
+    // (Gaussian data reaches 0.01 eps and cannot tell.)
     const double u16 = 1.0 / 2048.0, u32 = 1.0 / 16777216.0;
     return (2 * u16 + u16 * u16) * 1.01 + 2.0 * dim_pad * u32 + 8 * u32 + 2e-6;
 }
@@ -1072,10 +1096,15 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
     const int32_t* vis = search_vis(h, tenant);            // tenant filter and / or deleted rows (null: every row)
     // fused: |alpha| * (fp16-pass error of the cosine) + the float32 roundings of the emitted score alpha_f * S + bias:
     // bias = float(beta * kw + gamma * t) (2^-24 relative), alpha_f = float(alpha) (2^-24 |alpha| |S|), the fma's own rounding
-    // (2^-24 of the result) - together <= 2^-23 * (|alpha| + |beta| * max|kw| + |gamma| * max|t|). The keyword score is
-    // raw / max (in [0, 1] whenever the max is positive; the raw scores themselves, all <= 0, in the `else 1.0` case of
-    // rag/retrieval.py:344, where 8 covers any realistic BM25 magnitude); max|t| is tracked by rag_index_set_temporal_host.
-    const double f32_mag = fz ? fabs(fz->alpha) + 8.0 * fabs(fz->beta) + fabs(fz->gamma) * h->temporal_absmax : 0.0;
+    // (2^-24 of the result) - together <= 2^-23 * (|alpha| + |beta| * max|kw| + |gamma| * max|t|). RULE for max|kw|: the
+    // keyword score is raw / max, in [0, 1] when no raw score is negative - the host-side eps below counts max|kw| = 1. Raw
+    // scores below zero (negative idf values) have no such limit, least of all in the `else 1.0` case of
+    // rag/retrieval.py:344 where they are not divided at all. linear_scale_kernel bounds them per query from the query's
+    // length - none is below -(k1 + 1) * (largest |negative idf|) * (tokens of the query) - and adds
+    // 2 * |beta| * max(0, that bound / max - 1) * 2^-21 to the query's two_eps on the device (select_extra.margin). A constant stood here before (8); a long query over common terms scores far below -8, and with
+    // alpha small beside beta the float32 rounding of the bias then exceeded the whole margin
+    // (tests/test_dense_exactness_gpu.py, negative-idf corpus). max|t| is tracked by rag_index_set_temporal_host / insert.
+    const double f32_mag = fz ? fabs(fz->alpha) + fabs(fz->beta) + fabs(fz->gamma) * h->temporal_absmax : 0.0;
     // (round 4: the emitted keyword + recency term is formed in float32 from raw32 * qscale + gt: raw32, qscale and gt each carry one
     // 2^-24 rounding, the two fmas one each - 2^-21 of the magnitude covers them with a factor of two to spare)
     const double eps = fz ? fabs(fz->alpha) * fp16_pass_eps(h->dim_pad) + f32_mag / 2097152.0 + 1e-7 : fp16_pass_eps(h->dim_pad);
@@ -1099,9 +1128,10 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
                        h->dim_pad, (int*)nullptr);
     int* const ovf_count = h->ovf_list + RAG_TILE;
     hipLaunchKernelGGL(search_init_kernel, dim3((qpad + 255) / 256), dim3(256), 0, st, tau, h->bound, h->cnt, h->stats, ovf_count, qpad);
-    const select_extra no_extra = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const float* margin = fz ? fz->margin : nullptr;
+    const select_extra no_extra = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, margin};
     const bool second_pass = !h->opt.no_second_pass;
-    const select_extra list_extra = {second_pass ? h->ovf_list : (int*)nullptr, ovf_count, nullptr, nullptr, nullptr, nullptr};
+    const select_extra list_extra = {second_pass ? h->ovf_list : (int*)nullptr, ovf_count, nullptr, nullptr, nullptr, nullptr, margin};
 
     bool& attr_set = h->attr_dense;
     if (!attr_set) {
@@ -1215,7 +1245,7 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
                 hipLaunchKernelGGL((dense_emit_persist_kernel<false>), dim3(std::min(n_cu, total_tiles)), dim3(512), DENSE_LDS_BYTES, st, total_tiles,
                                    EMIT_ARGS(h->q16b, 1, RAG_TILE, h->taub, h->cntb, h->candb, ovf_count, nullptr));
         }
-        const select_extra scatter_extra = {nullptr, nullptr, h->ovf_list, h->cand, h->n_sorted, h->bound};
+        const select_extra scatter_extra = {nullptr, nullptr, h->ovf_list, h->cand, h->n_sorted, h->bound, margin};
         hipLaunchKernelGGL(select_kernel, dim3(RAG_TILE / 4), dim3(256), SELECT_LDS_BYTES, st, h->candb, h->cntb, h->taub, h->boundb,
                            h->n_sortedb, h->stats, RAG_TILE, 0, k, two_eps, 1, (const int*)ovf_count, scatter_extra);
         HIP_TRY(h, hipGetLastError());
@@ -1268,9 +1298,9 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
 }
 
 // bias / max / components of the linear fusion (called by rag_hybrid_linear_dev around dense_search_fused)
-int linear_prepare(rag_ctx* h, const unsigned long long* max_key, int Q, int64_t n, const double* temporal, double beta, double gamma, double* mx,
-                   float* qscale, float* gt, int64_t ld, hipStream_t st) {
-    hipLaunchKernelGGL(linear_scale_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, max_key, Q, beta, mx, qscale);
+int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bound nb, int Q, int64_t n, const double* temporal,
+                   double beta, double gamma, double* mx, float* qscale, float* margin, float* gt, int64_t ld, hipStream_t st) {
+    hipLaunchKernelGGL(linear_scale_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, max_key, nb, Q, beta, mx, qscale, margin);
     if (gt != nullptr) hipLaunchKernelGGL(linear_gt_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, temporal, n, ld, gamma, gt);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
