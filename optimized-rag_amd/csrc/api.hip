@@ -45,7 +45,6 @@ void ce_free(rag_ctx* h);
 int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize);
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st, bool host_ptrs);
 int embed_dim(const rag_ctx* h);
-void pipeline_free(rag_ctx* h);
 int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev, int Q, int pool,
                        int64_t token_id_base, int L_pair, int cls_id, int sep_id, int32_t* ids_out, int32_t* tt_out, int32_t* lens_out,
                        hipStream_t st);
@@ -93,7 +92,7 @@ static int pairwise_cosine_host_t(rag_handle_t h, const T* a, int m, const T* b,
     hipStream_t st = h->stream;
     int rc = stage_reserve(h, stage_size((size_t)m * dim, sizeof(T)) + stage_size(same ? 0 : (size_t)n * dim, sizeof(T)) + stage_size((size_t)m * n, 8));
     if (rc) return rc;
-    char* p = (char*)h->stage;
+    char* p = h->stage;
     T* ad = stage_take<T>(p, (size_t)m * dim);
     T* bd = same ? ad : stage_take<T>(p, (size_t)n * dim);
     double* od = stage_take<double>(p, (size_t)m * n);
@@ -132,6 +131,7 @@ int rag_create(int device_id, int dim, rag_handle_t* out) {
     h->dim = dim;
     h->dim_pad = (int)round_up(dim, RAG_BK);
     options_from_env(&h->opt);
+    if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
         return RAG_ERR_HIP;
@@ -149,18 +149,13 @@ int rag_destroy(rag_handle_t h) {
     dense_free(h);
     bm25_free(h);
     ce_free(h);
-    pipeline_free(h);
-    hipFree(h->q32); hipFree(h->q16); hipFree(h->cand); hipFree(h->cnt); hipFree(h->tau); hipFree(h->bound);
-    hipFree(h->n_sorted); hipFree(h->exact); hipFree(h->flag); hipFree(h->scan_list); hipFree(h->stats); hipFree(h->stage);
-    hipFree(h->temporal); hipFree(h->lin_ws);
-    hipFree(h->q16b); hipFree(h->candb); hipFree(h->cntb); hipFree(h->taub); hipFree(h->boundb); hipFree(h->n_sortedb); hipFree(h->ovf_list);
+    static_cast<rag_device_mem&>(*h) = rag_device_mem();      // every device buffer the handle itself owns
     for (auto& p : h->prof)
         for (auto& e : p.ev) {
             hipEventDestroy(e.first);
             hipEventDestroy(e.second);
         }
     if (h->side_stream) { hipStreamSynchronize(h->side_stream); hipStreamDestroy(h->side_stream); hipEventDestroy(h->ev_fork); hipEventDestroy(h->ev_join); }
-    hipFree(h->side_scores);
     hipStreamDestroy(h->stream);
     delete h;
     return RAG_OK;
@@ -207,10 +202,10 @@ static int index_load_common(rag_ctx* h, const float* emb, const int64_t* ids, i
     h->id_base = id_base;
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (n_rows > 0) {
-        HIP_TRY(h, hipMalloc(&h->emb32, (size_t)n_rows * h->dim * sizeof(float)));
+        if (int rc = h->emb32.alloc(h, (size_t)n_rows * h->dim)) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->emb32, emb, (size_t)n_rows * h->dim * sizeof(float), kind, st));
         if (ids) {
-            HIP_TRY(h, hipMalloc(&h->ids, (size_t)n_rows * sizeof(int64_t)));
+            if (int rc = h->ids.alloc(h, (size_t)n_rows)) return rc;
             HIP_TRY(h, hipMemcpyAsync(h->ids, ids, (size_t)n_rows * sizeof(int64_t), kind, st));
             h->cap_ids = n_rows;
         }
@@ -246,10 +241,11 @@ int rag_index_reserve(rag_handle_t h, int64_t n_rows_total, int64_t id_base) {
     h->id_base = id_base;
     h->n_reserved = n_rows_total;
     h->n_rows_pad = round_up(n_rows_total, (int64_t)RAG_TILE * 8);
-    HIP_TRY(h, hipMalloc(&h->emb32, (size_t)n_rows_total * h->dim * sizeof(float)));
+    int rc;
+    if ((rc = h->emb32.alloc(h, (size_t)n_rows_total * h->dim))) return rc;
     h->cap32 = n_rows_total;
-    HIP_TRY(h, hipMalloc(&h->emb16, (size_t)h->n_rows_pad * h->dim_pad * sizeof(half_t)));
-    HIP_TRY(h, hipMalloc(&h->bad_rows, sizeof(int)));
+    if ((rc = h->emb16.alloc(h, (size_t)h->n_rows_pad * h->dim_pad))) return rc;
+    if ((rc = h->bad_rows.alloc(h, 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), h->stream));
     // rows not appended yet (and the tile padding) must read as zero vectors
     HIP_TRY(h, hipMemsetAsync(h->emb16, 0, (size_t)h->n_rows_pad * h->dim_pad * sizeof(half_t), h->stream));
@@ -292,15 +288,14 @@ int rag_index_set_tenants_host(rag_handle_t h, const int32_t* t, int64_t n_rows)
     ARG_CHECK(h, t == nullptr || n_rows == h->n_rows, "tenant array length must equal the index row count");
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->vis) HIP_TRY(h, hipDeviceSynchronize());       // vis is rebuilt below: no queued search may still read it
-    hipFree(h->tenants);
-    h->tenants = nullptr;
+    h->tenants.reset();
     h->cap_ten = 0;
     int rc;
     if (t == nullptr || n_rows == 0) {                     // NULL clears the filter table
         if ((rc = dense_build_tenant_tiles(h, nullptr, 0))) return rc;
         return live_vis_rebuild(h);                        // deleted rows stay deleted
     }
-    HIP_TRY(h, hipMalloc(&h->tenants, (size_t)n_rows * sizeof(int32_t)));
+    if ((rc = h->tenants.alloc(h, (size_t)n_rows))) return rc;
     h->cap_ten = n_rows;
     HIP_TRY(h, hipMemcpy(h->tenants, t, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     if ((rc = dense_build_tenant_tiles(h, t, n_rows))) return rc;
@@ -312,11 +307,10 @@ int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
     LOCK(h);
     ARG_CHECK(h, n_rows == h->n_rows, "id array length must equal the index row count");
     HIP_TRY(h, hipSetDevice(h->device));
-    hipFree(h->ids);
-    h->ids = nullptr;
+    h->ids.reset();
     h->cap_ids = 0;
     if (ids == nullptr || n_rows == 0) return RAG_OK;
-    HIP_TRY(h, hipMalloc(&h->ids, (size_t)n_rows * sizeof(int64_t)));
+    if (int rc = h->ids.alloc(h, (size_t)n_rows)) return rc;
     h->cap_ids = n_rows;
     HIP_TRY(h, hipMemcpy(h->ids, ids, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice));
     return RAG_OK;
@@ -366,7 +360,7 @@ int rag_dense_topk_host(rag_handle_t h, const float* q_host, int Q, int k, int t
     const size_t n_out = (size_t)Q * k;
     int rc = stage_reserve(h, stage_size((size_t)Q * h->dim, 4) + 2 * stage_size(n_out, 8) + stage_size(n_out, 4));
     if (rc) return rc;
-    char* p = (char*)h->stage;
+    char* p = h->stage;
     float* qd = stage_take<float>(p, (size_t)Q * h->dim);
     int64_t* ids_d = stage_take<int64_t>(p, n_out);
     double* sc_d = stage_take<double>(p, n_out);
@@ -545,14 +539,13 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
     LOCK(h);
     ARG_CHECK(h, temporal == nullptr || n_rows == h->n_rows, "temporal array length must equal the index row count");
     HIP_TRY(h, hipSetDevice(h->device));
-    hipFree(h->temporal);
-    h->temporal = nullptr;
+    h->temporal.reset();
     h->cap_tmp = 0;
     h->temporal_absmax = 0.0;
     if (temporal == nullptr || n_rows == 0) return RAG_OK;
     for (int64_t i = 0; i < n_rows; ++i) h->temporal_absmax = std::max(h->temporal_absmax, std::fabs(temporal[i]));
     ARG_CHECK(h, std::isfinite(h->temporal_absmax), "temporal scores must be finite");
-    HIP_TRY(h, hipMalloc(&h->temporal, (size_t)n_rows * sizeof(double)));
+    if (int rc = h->temporal.alloc(h, (size_t)n_rows)) return rc;
     h->cap_tmp = n_rows;
     HIP_TRY(h, hipMemcpy(h->temporal, temporal, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice));
     return RAG_OK;
@@ -583,15 +576,11 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
     // shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
     const int QB = (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)8 << 30) / (n * 12)));
     const size_t need = stage_size((size_t)QB * n, 8) + stage_size((size_t)QB * ld, 4) + 2 * stage_size(QB, 8) + 2 * stage_size(QB, 4) + stage_size(ld, 4);
-    if (need > h->lin_ws_bytes) {
-        hipFree(h->lin_ws);
-        h->lin_ws = nullptr;
-        h->lin_ws_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->lin_ws, need));
-        h->lin_ws_bytes = need;
+    if (need > h->lin_ws.size()) {
+        if (int rc = h->lin_ws.alloc(h, need)) return rc;
         HIP_TRY(h, hipMemsetAsync(h->lin_ws, 0, need, st));      // the pad rows [n, ld) of raw32 are read by the last tile: keep them 0
     }
-    char* p = (char*)h->lin_ws;
+    char* p = h->lin_ws;
     double* raw = stage_take<double>(p, (size_t)QB * n);
     float* raw32 = stage_take<float>(p, (size_t)QB * ld);
     double* mx = stage_take<double>(p, QB);

@@ -27,6 +27,8 @@
 //            as the fallback when more than k survive). Then a per-query merge of the partial lists.
 #include "common.h"
 
+#include <memory>
+
 typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));          // posting segments start at any posting
 typedef double double2u __attribute__((ext_vector_type(2), aligned(8)));
 #ifndef BM_RANGE            // -DBM_RANGE / -DBM_THREADS: variant builds by tools/bm25_variant_build.sh
@@ -62,37 +64,30 @@ static_assert((BM_RANGE & (BM_RANGE - 1)) == 0, "BM_RANGE must be a power of two
 struct bm_plan_meta;
 struct rag_bm25_index {
     int64_t n_docs = 0, n_terms = 0, nnz = 0;
-    int64_t* indptr = nullptr;
-    int32_t* doc = nullptr;
-    double* w = nullptr;
-    double* idf = nullptr;
+    dev_buf<int32_t> doc;
+    dev_buf<double> w;
     // OPTIONAL compact form (option bm25_packed at load time): 4-byte postings (doc & (BM_RANGE - 1)) | code << BM_RANGE_LOG2, code =
     // tf rank * n_dl + length rank, and the table g[code] = tf (k1+1) / (tf + k1 (1 - b + b dl / avgdl)) shared by all terms
     // (impact = idf * g, the same float64 product): 8 B per posting resident instead of 12 (`doc` stays for the plan kernel's
     // searches, `w` is not built) and a third of the streamed bytes - but the scoring loop gets SLOWER (1M documents, 1024 queries:
     // 4.22 against 3.36 ms): four 8-byte table gathers per chunk cost the texture path more than the two coalesced impact loads
     // they replace. The default therefore streams (doc i32, impact f64).
-    uint32_t* packed = nullptr;
-    double* gtab = nullptr;
+    dev_buf<uint32_t> packed;
+    dev_buf<double> gtab;
     int64_t n_codes = 0;
-    bm_term_meta* meta = nullptr;      // [n_terms]
-    int32_t* range_tab = nullptr;      // concatenated per-term tables: entry c = first posting (rel. to meta.post) with doc >= c << shift
+    dev_buf<bm_term_meta> meta;        // [n_terms]
+    dev_buf<int32_t> range_tab;        // concatenated per-term tables: entry c = first posting (rel. to meta.post) with doc >= c << shift
     int64_t tab_entries = 0;
     int n_ranges = 0;
-    uint64_t* ws_key = nullptr;        // per-range partial top-k workspace for the device entry point
-    uint32_t* ws_row = nullptr;
-    size_t ws_entries = 0;
-    uint64_t* ws_tau = nullptr;        // [ws_tau_q] first-stage threshold per query
-    int ws_tau_q = 0;
-    int* ws_cnt = nullptr;             // [ws_cnt_n] valid entries per (query, range) partial list
-    size_t ws_cnt_n = 0;
-    uint64_t* ws_run_key = nullptr;    // [ws_run_n] running top-k of every query across the threshold stages
-    uint32_t* ws_run_row = nullptr;
-    size_t ws_run_n = 0;
-    int32_t* ws_plan_off = nullptr;    // per-call plan of the device entry points (bm25_plan_kernel), grown on demand
-    bm_plan_meta* ws_plan_meta = nullptr;
-    size_t ws_plan_entries = 0;
-    int ws_plan_q = 0;
+    // grow-only workspaces of the device entry points
+    dev_buf<uint64_t> ws_key;          // per-range partial top-k lists
+    dev_buf<uint32_t> ws_row;
+    dev_buf<uint64_t> ws_tau;          // first-stage threshold per query
+    dev_buf<int> ws_cnt;               // valid entries per (query, range) partial list
+    dev_buf<uint64_t> ws_run_key;      // running top-k of every query across the threshold stages
+    dev_buf<uint32_t> ws_run_row;
+    dev_buf<int32_t> ws_plan_off;      // per-call plan (bm25_plan_kernel)
+    dev_buf<bm_plan_meta> ws_plan_meta;
     int plan_t = 64;                   // planned token slots per query of the CURRENT call (bm25_pick_plan_t), <= BM_PLAN_T
     double avgdl = 0, k1 = 1.5, b = 0.75;
     double neg_idf_absmax = 0;         // largest |idf| among the negative idf values (0: none), for bm25_negative_bound_args
@@ -1108,32 +1103,22 @@ static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const i
 }
 
 // ------------------------------------------------------------------------------------------------
-static void bm25_index_free(rag_bm25_index* ix) {
-    if (!ix) return;
-    hipFree(ix->indptr); hipFree(ix->doc); hipFree(ix->w); hipFree(ix->idf); hipFree(ix->meta); hipFree(ix->range_tab);
-    hipFree(ix->packed); hipFree(ix->gtab);
-    hipFree(ix->ws_key); hipFree(ix->ws_row); hipFree(ix->ws_tau); hipFree(ix->ws_cnt); hipFree(ix->ws_run_key); hipFree(ix->ws_run_row);
-    hipFree(ix->ws_plan_off); hipFree(ix->ws_plan_meta);
-    delete ix;
-}
-
 void bm25_free(rag_ctx* h) {
-    bm25_index_free(h->bm25);
+    delete h->bm25;
     h->bm25 = nullptr;
 }
 
-// host CSR -> device index (impacts + range table). Synchronous. On failure *out is freed and left null.
+// host CSR -> device index (impacts + range table). Synchronous. *out receives the index on success only.
 static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
-                      const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b, rag_bm25_index** out) {
-    *out = nullptr;
+                      const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
+                      std::unique_ptr<rag_bm25_index>* out) {
     ARG_CHECK(h, n_docs > 0 && n_terms >= 0 && n_docs < 0x7fffffff, "bm25_load: bad sizes");
     ARG_CHECK(h, indptr && doc_len && (n_terms == 0 || idf), "bm25_load: null pointer");
     const int64_t nnz = n_terms ? indptr[n_terms] : 0;
     ARG_CHECK(h, nnz == 0 || (doc && tf), "bm25_load: null postings");
-    rag_bm25_index* ix = new rag_bm25_index();
+    std::unique_ptr<rag_bm25_index> ix(new rag_bm25_index());
     ix->n_docs = n_docs; ix->n_terms = n_terms; ix->nnz = nnz; ix->avgdl = avgdl; ix->k1 = k1; ix->b = b;
     hipStream_t st = h->stream;
-    int32_t *tfd = nullptr, *dld = nullptr;
     ix->n_ranges = (int)((n_docs + BM_RANGE - 1) / BM_RANGE);
     // per-term metadata + the plan of the bracket tables (host: one pass over indptr)
     const int64_t n_pad = (int64_t)ix->n_ranges * BM_RANGE;
@@ -1142,7 +1127,6 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
     for (int64_t t = 0; t < n_terms; ++t) {
         const int64_t df = indptr[t + 1] - indptr[t];
         if (df < 0 || df > n_docs) {
-            delete ix;
             h->err = "bad argument: bm25_load: indptr must be non-decreasing with at most n_docs postings per term";
             return RAG_ERR_ARG;
         }
@@ -1183,75 +1167,81 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
     if (!packed_ok) ix->n_codes = 0;
     // + 8 postings of padding: the scoring kernel reads 4 consecutive postings per thread, the bracket search 8 doc ids, without
     // a bounds branch
-    uint32_t *tfr_d = nullptr, *dlr_d = nullptr;
-    double *tfv_d = nullptr, *dlv_d = nullptr;
-    hipError_t e = hipMalloc(&ix->indptr, (size_t)(n_terms + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&ix->doc, (size_t)(nnz + 8) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(ix->doc + nnz, 0, 8 * sizeof(int32_t), st);
-    if (packed_ok) {
-        if (e == hipSuccess) e = hipMalloc(&ix->packed, (size_t)(nnz + 8) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(ix->packed + nnz, 0, 8 * sizeof(uint32_t), st);
-        if (e == hipSuccess) e = hipMalloc(&ix->gtab, (size_t)ix->n_codes * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&tfr_d, tf_rank_h.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&dlr_d, dl_rank_of_doc_h.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&tfv_d, tf_values_h.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&dlv_d, dl_values_h.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(tfr_d, tf_rank_h.data(), tf_rank_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dlr_d, dl_rank_of_doc_h.data(), dl_rank_of_doc_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(tfv_d, tf_values_h.data(), tf_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dlv_d, dl_values_h.data(), dl_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st);
-    } else {
-        if (e == hipSuccess) e = hipMalloc(&ix->w, (size_t)(nnz + 8) * sizeof(double));
-        if (e == hipSuccess) e = hipMemsetAsync(ix->w + nnz, 0, 8 * sizeof(double), st);
-    }
-    if (e == hipSuccess) e = hipMalloc(&ix->idf, std::max<size_t>(1, n_terms) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&ix->meta, meta_h.size() * sizeof(bm_term_meta));
-    if (e == hipSuccess) e = hipMalloc(&tfd, std::max<size_t>(1, nnz) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&dld, (size_t)n_docs * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&ix->range_tab, std::max<size_t>(1, (size_t)n_tab) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(ix->indptr, indptr, (size_t)(n_terms + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(tfd, tf, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_terms) e = hipMemcpyAsync(ix->idf, idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_terms) e = hipMemcpyAsync(ix->meta, meta_h.data(), (size_t)n_terms * sizeof(bm_term_meta), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dld, doc_len, (size_t)n_docs * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz && !packed_ok) {
-        hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, ix->indptr, ix->doc, tfd,
-                           dld, nnz, avgdl, k1, b, ix->idf, n_terms, ix->w);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && packed_ok) {
-        hipLaunchKernelGGL(bm25_pack_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, ix->doc, tfd, tfr_d, dlr_d, nnz,
-                           (uint32_t)dl_values_h.size(), ix->packed);
-        hipLaunchKernelGGL(bm25_gtab_kernel, dim3((unsigned)((ix->n_codes + 255) / 256)), dim3(256), 0, st, tfv_d, dlv_d, ix->n_codes,
-                           (uint32_t)dl_values_h.size(), avgdl, k1, b, ix->gtab);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && n_tab) {
-        hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((n_tab + 255) / 256)), dim3(256), 0, st, ix->meta, ix->doc,
-                           n_terms, n_tab, ix->range_tab);
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);               // (also keeps meta_h alive until its copy has been read)
-    hipFree(tfd); hipFree(dld); hipFree(tfr_d); hipFree(dlr_d); hipFree(tfv_d); hipFree(dlv_d);
-    hipFree(ix->indptr); hipFree(ix->idf);                         // only the builders above read them: the metadata carries both
-    ix->indptr = nullptr; ix->idf = nullptr;
-    if (e != hipSuccess || e2 != hipSuccess) {
-        bm25_index_free(ix);
-        h->err = std::string("bm25_load: ") + hipGetErrorString(e != hipSuccess ? e : e2);
+    // the builders' inputs: the index keeps none of them (its metadata carries the offsets and the idf)
+    dev_buf<int64_t> indptr_d;
+    dev_buf<double> idf_d, tfv_d, dlv_d;
+    dev_buf<int32_t> tfd, dld;
+    dev_buf<uint32_t> tfr_d, dlr_d;
+    auto enqueue = [&]() -> int {
+        int rc;
+        if ((rc = indptr_d.alloc(h, (size_t)n_terms + 1))) return rc;
+        if ((rc = ix->doc.alloc(h, (size_t)nnz + 8))) return rc;
+        HIP_TRY(h, hipMemsetAsync(ix->doc + nnz, 0, 8 * sizeof(int32_t), st));
+        if (packed_ok) {
+            if ((rc = ix->packed.alloc(h, (size_t)nnz + 8))) return rc;
+            HIP_TRY(h, hipMemsetAsync(ix->packed + nnz, 0, 8 * sizeof(uint32_t), st));
+            if ((rc = ix->gtab.alloc(h, (size_t)ix->n_codes))) return rc;
+            if ((rc = tfr_d.alloc(h, tf_rank_h.size()))) return rc;
+            if ((rc = dlr_d.alloc(h, dl_rank_of_doc_h.size()))) return rc;
+            if ((rc = tfv_d.alloc(h, tf_values_h.size()))) return rc;
+            if ((rc = dlv_d.alloc(h, dl_values_h.size()))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(tfr_d, tf_rank_h.data(), tf_rank_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(dlr_d, dl_rank_of_doc_h.data(), dl_rank_of_doc_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(tfv_d, tf_values_h.data(), tf_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(dlv_d, dl_values_h.data(), dl_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        } else {
+            if ((rc = ix->w.alloc(h, (size_t)nnz + 8))) return rc;
+            HIP_TRY(h, hipMemsetAsync(ix->w + nnz, 0, 8 * sizeof(double), st));
+        }
+        if ((rc = idf_d.alloc(h, std::max<size_t>(1, n_terms)))) return rc;
+        if ((rc = ix->meta.alloc(h, meta_h.size()))) return rc;
+        if ((rc = tfd.alloc(h, std::max<size_t>(1, nnz)))) return rc;
+        if ((rc = dld.alloc(h, (size_t)n_docs))) return rc;
+        if ((rc = ix->range_tab.alloc(h, std::max<size_t>(1, (size_t)n_tab)))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(indptr_d, indptr, (size_t)(n_terms + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(tfd, tf, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (n_terms) HIP_TRY(h, hipMemcpyAsync(idf_d, idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st));
+        if (n_terms) HIP_TRY(h, hipMemcpyAsync(ix->meta, meta_h.data(), (size_t)n_terms * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(dld, doc_len, (size_t)n_docs * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (nnz && !packed_ok) {
+            hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, indptr_d.get(), ix->doc.get(), tfd.get(),
+                               dld.get(), nnz, avgdl, k1, b, idf_d.get(), n_terms, ix->w.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (packed_ok) {
+            hipLaunchKernelGGL(bm25_pack_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, ix->doc.get(), tfd.get(), tfr_d.get(), dlr_d.get(), nnz,
+                               (uint32_t)dl_values_h.size(), ix->packed.get());
+            hipLaunchKernelGGL(bm25_gtab_kernel, dim3((unsigned)((ix->n_codes + 255) / 256)), dim3(256), 0, st, tfv_d.get(), dlv_d.get(), ix->n_codes,
+                               (uint32_t)dl_values_h.size(), avgdl, k1, b, ix->gtab.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (n_tab) {
+            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((n_tab + 255) / 256)), dim3(256), 0, st, ix->meta.get(), ix->doc.get(),
+                               n_terms, n_tab, ix->range_tab.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        return RAG_OK;
+    };
+    const int rc = enqueue();
+    // also after a failure: the host vectors above stay alive until their copies have been read
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (e2 != hipSuccess) {
+        h->err = std::string("bm25_load: ") + hipGetErrorString(e2);
         return RAG_ERR_HIP;
     }
-    *out = ix;
+    *out = std::move(ix);
     return RAG_OK;
 }
 
 int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                    const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b) {
-    rag_bm25_index* ix = nullptr;
+    std::unique_ptr<rag_bm25_index> ix;
     const int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix);
     if (rc) return rc;
     bm25_free(h);
-    h->bm25 = ix;
+    h->bm25 = ix.release();
     h->bm25_stale = false;
     return RAG_OK;
 }
@@ -1294,7 +1284,7 @@ static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, co
 }
 
 // host-pointer search against `ix` (the resident index or an ad-hoc one). Device staging comes from the handle's
-// grow-only arena: no hipMalloc / hipFree per call.
+// grow-only arena: no device allocation per call.
 static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int mode, int tenant,
                     int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out, double* dense_out) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
@@ -1321,7 +1311,7 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
                    stage_size(n_out, 8) + stage_size(n_dense, 8) + stage_size(bm25_plan_off_entries(ix, Q), 4) +
                    stage_size((size_t)Q * BM_PLAN_T, sizeof(bm_plan_meta));
     if ((rc = stage_reserve(h, total))) return rc;
-    char* p = (char*)h->stage;
+    char* p = h->stage;
     int32_t* tp = stage_take<int32_t>(p, Q + 1);
     int32_t* tm = stage_take<int32_t>(p, std::max(1, n_terms_q));
     bm25_topk_ws w;
@@ -1364,22 +1354,8 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
 
 static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
     ix->plan_t = bm25_pick_plan_t(h, ix, Q);
-    const size_t need = bm25_plan_off_entries(ix, Q);
-    if (need > ix->ws_plan_entries) {
-        hipFree(ix->ws_plan_off);
-        ix->ws_plan_off = nullptr;
-        ix->ws_plan_entries = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_plan_off, need * sizeof(int32_t)));
-        ix->ws_plan_entries = need;
-    }
-    if (Q > ix->ws_plan_q) {
-        hipFree(ix->ws_plan_meta);
-        ix->ws_plan_meta = nullptr;
-        ix->ws_plan_q = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_plan_meta, (size_t)Q * BM_PLAN_T * sizeof(bm_plan_meta)));
-        ix->ws_plan_q = Q;
-    }
-    return RAG_OK;
+    if (int rc = ix->ws_plan_off.reserve(h, bm25_plan_off_entries(ix, Q))) return rc;
+    return ix->ws_plan_meta.reserve(h, (size_t)Q * BM_PLAN_T);
 }
 
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
@@ -1418,37 +1394,13 @@ static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const in
     int rc = bm25_tenant_args(h, ix, tenant, &tenants);
     if (rc) return rc;
     if ((rc = bm25_set_attr(h))) return rc;
-    const size_t need = (size_t)Q * ix->n_ranges * k;
-    if (need > ix->ws_entries) {
-        hipFree(ix->ws_key); hipFree(ix->ws_row);
-        ix->ws_key = nullptr; ix->ws_row = nullptr; ix->ws_entries = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_key, need * sizeof(uint64_t)));
-        HIP_TRY(h, hipMalloc(&ix->ws_row, need * sizeof(uint32_t)));
-        ix->ws_entries = need;
-    }
-    if (Q > ix->ws_tau_q) {
-        hipFree(ix->ws_tau);
-        ix->ws_tau = nullptr;
-        ix->ws_tau_q = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_tau, (size_t)Q * sizeof(uint64_t)));
-        ix->ws_tau_q = Q;
-    }
-    const size_t need_cnt = (size_t)Q * ix->n_ranges;
-    if (need_cnt > ix->ws_cnt_n) {
-        hipFree(ix->ws_cnt);
-        ix->ws_cnt = nullptr;
-        ix->ws_cnt_n = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_cnt, need_cnt * sizeof(int)));
-        ix->ws_cnt_n = need_cnt;
-    }
-    const size_t need_run = (size_t)Q * k;
-    if (need_run > ix->ws_run_n) {
-        hipFree(ix->ws_run_key); hipFree(ix->ws_run_row);
-        ix->ws_run_key = nullptr; ix->ws_run_row = nullptr; ix->ws_run_n = 0;
-        HIP_TRY(h, hipMalloc(&ix->ws_run_key, need_run * sizeof(uint64_t)));
-        HIP_TRY(h, hipMalloc(&ix->ws_run_row, need_run * sizeof(uint32_t)));
-        ix->ws_run_n = need_run;
-    }
+    const size_t need = (size_t)Q * ix->n_ranges * k, need_run = (size_t)Q * k;
+    if ((rc = ix->ws_key.reserve(h, need))) return rc;
+    if ((rc = ix->ws_row.reserve(h, need))) return rc;
+    if ((rc = ix->ws_tau.reserve(h, (size_t)Q))) return rc;
+    if ((rc = ix->ws_cnt.reserve(h, (size_t)Q * ix->n_ranges))) return rc;
+    if ((rc = ix->ws_run_key.reserve(h, need_run))) return rc;
+    if ((rc = ix->ws_run_row.reserve(h, need_run))) return rc;
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
     // doc ids follow the dense index's mapping when both indexes cover the same rows (hybrid fusion needs one id space)
     const bool aligned = h->n_rows == ix->n_docs;
@@ -1551,10 +1503,7 @@ int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc
                            const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
                            const int32_t* term_ptr, const int32_t* terms, int Q, double* out) {
     ARG_CHECK(h, out, "bm25_scores_adhoc: null output");
-    rag_bm25_index* ix = nullptr;
-    int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix);
-    if (rc) return rc;
-    rc = bm25_run(h, ix, term_ptr, terms, Q, 1, 1, -1, nullptr, nullptr, nullptr, nullptr, out);
-    bm25_index_free(ix);
-    return rc;
+    std::unique_ptr<rag_bm25_index> ix;         // dropped when the call returns
+    if (int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix)) return rc;
+    return bm25_run(h, ix.get(), term_ptr, terms, Q, 1, 1, -1, nullptr, nullptr, nullptr, nullptr, out);
 }

@@ -26,6 +26,35 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define RAG_PROF_STAGES 3
 struct rag_ce_model;             // cross_encoder.hip
 struct rag_bm25_index;           // bm25.hip
+struct rag_ctx;
+
+// ---- device memory: the ONE owner of a hipMalloc allocation (and the only place that calls hipMalloc / hipFree). Move-only;
+// the destructor, reset() and every re-allocation hipFree at once (callers rely on hipFree waiting for the device). Reads as
+// a T* in kernel launches, copies and pointer arithmetic; structs passed to kernels by value keep raw pointers.
+template <class T>
+struct dev_buf {
+    dev_buf() = default;
+    dev_buf(dev_buf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    dev_buf& operator=(dev_buf&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~dev_buf() { reset(); }
+    void reset() {
+        if (p_) hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    int alloc(rag_ctx* h, size_t n);                     // frees what it holds; RAG_ERR_HIP (h->err set, left empty) on failure
+    int reserve(rag_ctx* h, size_t n) { return n <= n_ ? RAG_OK : alloc(h, n); }     // grow-only: contents are NOT kept
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }                   // elements
+
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
 
 // Diagnostic / tuning switches of one handle. The defaults come from the environment (RAG_<NAME>) ONCE, in rag_create;
 // rag_set_option(h, "<name>", value) changes them afterwards (tests flip them between calls on one handle). Nothing on a
@@ -50,15 +79,61 @@ struct rag_options {
     int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 = yes if the load-time probe saw it hold (cross_encoder.hip ce_probe_mx), 1 = yes, -1 = never
 };
 
-struct rag_ctx {
+// Every device allocation of a handle, in two groups so that each can be released as a whole by assigning an empty value:
+// the planes of the dense index (dropped by every index load, dense_free) ...
+struct rag_index_mem {
+    dev_buf<float> emb32;            // [n_rows][dim]        fp32 master rows
+    dev_buf<half_t> emb16;           // [n_rows_pad][dim_pad] fp16 (2^7 * unit rows), zero padded
+    dev_buf<int64_t> ids;            // [n_rows] or null
+    dev_buf<int32_t> tenants;        // [n_rows] or null
+    dev_buf<int> bad_rows;           // device counter: rows with zero / non-finite norm
+    dev_buf<char> scan_scores;       // exact-scan fallback: partial lists, 12 B per entry (allocated on first use)
+    dev_buf<int32_t> tenant_tiles;   // concatenated per-tenant lists of 256-row tiles
+    // live writes (live.hip). vis[row] = the row's tenant (0 without a tenant table) or RAG_DEAD_ROW once deleted; null while
+    // nothing is deleted, so the search kernels keep their unfiltered path.
+    dev_buf<int32_t> vis;
+};
+// ... and everything else (dropped by rag_destroy, with the index planes)
+struct rag_device_mem : rag_index_mem {
+    dev_buf<double> side_scores;     // hybrid_legs: score scratch of the BM25 leg on the side stream
+    dev_buf<double> temporal;        // [n_rows] per-row temporal score (linear fusion) or null
+    dev_buf<char> lin_ws;            // rag_hybrid_linear_dev: raw BM25 + bias + max of one sub-batch
+    // dense search workspace (sized for ws_q queries)
+    dev_buf<float> q32;              // [ws_q][dim]     staging for host queries
+    dev_buf<half_t> q16;             // [ws_qpad][dim_pad]
+    dev_buf<uint64_t> cand;          // [ws_qpad][RAG_CAND_CAP]
+    dev_buf<unsigned> cnt;           // [ws_qpad]   emitted candidates (may exceed cap = overflow)
+    dev_buf<float> tau;              // [ws_qpad]   emission threshold = k-th best fp16-pass score so far - 2 eps
+    dev_buf<float> bound;            // [ws_qpad]   -inf, or +inf once the candidate buffer overflowed (sticky)
+    dev_buf<int> n_sorted;           // [ws_qpad]   survivors left in cand[] after the final select
+    dev_buf<double> exact;           // [ws_qpad][RAG_CAND_CAP] float64 rescored cosines
+    dev_buf<int> flag;               // [ws_qpad]   0 done, 2 needs exact scan, 3 scanned
+    dev_buf<int> scan_list;          // [ws_qpad]   queries flagged 2 (appended by finalize_kernel; count = stats[7])
+    dev_buf<int> stats;              // [8] device counters
+    // second pass for overflowed queries: one 256-query tile of its own (dense.hip)
+    dev_buf<half_t> q16b;
+    dev_buf<uint64_t> candb;
+    dev_buf<unsigned> cntb;
+    dev_buf<float> taub, boundb;
+    dev_buf<int> n_sortedb, ovf_list;
+    // grow-only device arena of the synchronous *_host entry points: their per-call staging (queries in, results out, partial
+    // lists) is carved from it, so an agent-facing call pays no allocation
+    dev_buf<char> stage;
+    // passage token store (pipeline.hip): [tok_rows][tok_L] uint16 WordPiece ids + lengths, row-aligned with the index
+    dev_buf<uint16_t> tok;
+    dev_buf<int32_t> tok_len;
+    dev_buf<int> tok_bad;            // device counter of out-of-range token ids seen by the appends
+    dev_buf<char> pipe_ws;           // retrieve_rerank_dev: candidate lists, pair tokens, logits of one call
+};
+
+struct rag_ctx : rag_device_mem {
     int device = 0;
+    int n_cu = 0;                // compute units of `device` (rag_create): sizes the persistent grids
     int dim = 0;
     int dim_pad = 0;             // multiple of RAG_BK
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;       // hybrid_legs: the BM25 leg of a small batch runs beside the dense leg
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    double* side_scores = nullptr;           // [side_scores_n] score scratch of that leg
-    size_t side_scores_n = 0;
     std::string err;
     rag_options opt;
     bool profiling = false;
@@ -69,54 +144,19 @@ struct rag_ctx {
     int64_t n_rows = 0, n_rows_pad = 0, id_base = 0;
     bool index_loaded = false;   // rag_index_load_* / rag_index_reserve ran (an EMPTY index is a valid, searchable state)
     int64_t n_reserved = 0;      // rows allocated by rag_index_reserve (chunked bulk load), 0 otherwise
-    float* emb32 = nullptr;      // [n_rows][dim]        fp32 master rows
-    half_t* emb16 = nullptr;     // [n_rows_pad][dim_pad] fp16 (2^7 * unit rows), zero padded
-    int64_t* ids = nullptr;      // [n_rows] or null
-    int32_t* tenants = nullptr;  // [n_rows] or null
-    double* temporal = nullptr;                                        // [n_rows] per-row temporal score (linear fusion) or null
     double temporal_absmax = 0.0;                                      // max |temporal[i]| (sizes the fused emission margin)
-    void* lin_ws = nullptr;                                            // rag_hybrid_linear_dev: raw BM25 + bias + max of one sub-batch
-    size_t lin_ws_bytes = 0;
-    int32_t* tenant_tiles = nullptr;                                   // concatenated per-tenant lists of 256-row tiles
     std::unordered_map<int32_t, std::pair<int64_t, int>> tenant_span;  // tenant -> (offset, count) into tenant_tiles
     std::unordered_map<int32_t, std::vector<int32_t>> tenant_lists;    // host copy of those lists (inserts extend them)
     int64_t tenant_rows = 0;                                           // row count the tenant table was built for
-    // live writes (live.hip). vis[row] = the row's tenant (0 without a tenant table) or RAG_DEAD_ROW once deleted; null while
-    // nothing is deleted, so the search kernels keep their unfiltered path. Row capacities of the planes inserts grow in place
-    // (emb16's is n_rows_pad, the token store's tok_cap).
-    int32_t* vis = nullptr;
+    // live writes (live.hip). Row capacities of the planes inserts grow in place (emb16's is n_rows_pad, the token store's
+    // tok_cap): kept as rows beside the buffers' element counts because a plane may be absent (capacity 0) and live.hip
+    // compares and grows them in rows.
     int64_t n_deleted = 0;
     int64_t cap32 = 0, cap_ids = 0, cap_ten = 0, cap_tmp = 0, cap_vis = 0;
     bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
-    int* bad_rows = nullptr;     // device counter: rows with zero / non-finite norm
 
-    // dense search workspace (sized for ws_q queries)
-    int ws_q = 0;
-    float* q32 = nullptr;            // [ws_q][dim]     staging for host queries
-    half_t* q16 = nullptr;           // [ws_qpad][dim_pad]
+    int ws_q = 0;                    // queries the dense search workspace is sized for
     int q16_dirty = 0;               // rows [q16_dirty, ws_qpad) of q16 are known to be zero (pad rows of a query tile must be)
-    uint64_t* cand = nullptr;        // [ws_qpad][RAG_CAND_CAP]
-    unsigned* cnt = nullptr;         // [ws_qpad]   emitted candidates (may exceed cap = overflow)
-    float* tau = nullptr;            // [ws_qpad]   emission threshold = k-th best fp16-pass score so far - 2 eps
-    float* bound = nullptr;          // [ws_qpad]   -inf, or +inf once the candidate buffer overflowed (sticky)
-    int* n_sorted = nullptr;         // [ws_qpad]   survivors left in cand[] after the final select
-    double* exact = nullptr;         // [ws_qpad][RAG_CAND_CAP] float64 rescored cosines
-    int* flag = nullptr;             // [ws_qpad]   0 done, 2 needs exact scan, 3 scanned
-    int* scan_list = nullptr;        // [ws_qpad]   queries flagged 2 (appended by finalize_kernel; count = stats[7])
-    int* stats = nullptr;            // [8] device counters
-    // second pass for overflowed queries: one 256-query tile of its own (dense.hip)
-    half_t* q16b = nullptr;
-    uint64_t* candb = nullptr;
-    unsigned* cntb = nullptr;
-    float *taub = nullptr, *boundb = nullptr;
-    int *n_sortedb = nullptr, *ovf_list = nullptr;
-    // exact-scan fallback workspace
-    double* scan_scores = nullptr;   // [n_rows] (allocated on first use)
-    int64_t scan_rows = 0;
-    // grow-only device arena of the synchronous *_host entry points: their per-call staging (queries in, results out, partial
-    // lists) is carved from it, so an agent-facing call pays no hipMalloc / hipFree
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
     // one lock per handle, taken by every entry point: the reference's DocumentStore.search may be called from up to 10
     // threads (database/connection.py:38-42). *_host calls are then fully thread-safe (they are synchronous inside the
     // lock); *_dev calls are serialised while they enqueue and share the handle's workspaces, so they must target ONE stream.
@@ -133,14 +173,8 @@ struct rag_ctx {
     double last_eps = 0;
 
     rag_bm25_index* bm25 = nullptr;
-    // passage token store (pipeline.hip): [tok_rows][tok_L] uint16 WordPiece ids + lengths, row-aligned with the index
-    uint16_t* tok = nullptr;
-    int32_t* tok_len = nullptr;
-    int64_t tok_rows = 0, tok_cap = 0;       // rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
-    int* tok_bad = nullptr;                  // device counter of out-of-range token ids seen by the appends
+    int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
-    void* pipe_ws = nullptr;
-    size_t pipe_ws_bytes = 0;
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process
     bool attr_dense = false, attr_bm25 = false, attr_ce_gemm = false;
     int attr_ce_attn_lds[3] = {0, 0, 0};
@@ -158,6 +192,14 @@ struct rag_ctx {
             return RAG_ERR_HIP;                                                               \
         }                                                                                     \
     } while (0)
+
+template <class T>
+int dev_buf<T>::alloc(rag_ctx* h, size_t n) {
+    reset();
+    HIP_TRY(h, hipMalloc(&p_, n * sizeof(T)));
+    n_ = n;
+    return RAG_OK;
+}
 
 #define ARG_CHECK(h, cond, msg)                                                               \
     do {                                                                                      \
@@ -180,7 +222,7 @@ __device__ __forceinline__ bool row_visible(const int32_t* __restrict__ vis, int
 }
 // the vis argument of a search over the resident index (host side)
 static inline const int32_t* search_vis(const rag_ctx* h, int tenant) {
-    return h->vis != nullptr ? h->vis : (tenant >= 0 ? h->tenants : nullptr);
+    return h->vis ? h->vis.get() : (tenant >= 0 ? h->tenants.get() : nullptr);
 }
 
 // ---- profiling spans (no-ops unless rag_set_profiling(h, 1))
@@ -207,17 +249,9 @@ static inline int prof_end(rag_ctx* h, int stage, hipStream_t st) {
 // ---- staging arena (see rag_ctx::stage): sum stage_size() of every piece, stage_reserve() once, stage_take() in the same order
 static inline size_t stage_size(size_t n, size_t elt) { return (size_t)round_up((int64_t)(n * elt), 256); }
 static inline int stage_reserve(rag_ctx* h, size_t bytes) {
-    if (bytes <= h->stage_bytes) return RAG_OK;
-    if (h->stage) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        hipFree(h->stage);
-        h->stage = nullptr;
-        h->stage_bytes = 0;
-    }
-    bytes = (size_t)round_up((int64_t)(bytes + bytes / 4), 1 << 20);          // headroom: slightly larger batches do not reallocate
-    HIP_TRY(h, hipMalloc(&h->stage, bytes));
-    h->stage_bytes = bytes;
-    return RAG_OK;
+    if (bytes <= h->stage.size()) return RAG_OK;
+    if (h->stage) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return h->stage.alloc(h, (size_t)round_up((int64_t)(bytes + bytes / 4), 1 << 20));      // headroom: slightly larger batches do not reallocate
 }
 template <class T>
 static inline T* stage_take(char*& p, size_t n) {

@@ -40,37 +40,39 @@
 // one chunk's token arrays, packed row layout and host staging (sized for `pairs` pairs of L tokens, Mp padded rows). Each
 // forward has an instance of its own, so switching between them (option ce_mx) never resizes the other forward's buffers.
 struct ce_chunk_bufs {
-    int32_t *ids = nullptr, *tt = nullptr, *lens = nullptr;            // [Mp] token / type ids padded to L, [pairs] lengths
+    dev_buf<int32_t> ids, tt, lens;                                    // [Mp] token / type ids padded to L, [pairs] lengths
     // packed (variable-length) row layout of the current chunk: pair p owns rows [pair_off[p], pair_off[p+1]) where
     // pair_off[p+1] - pair_off[p] = len rounded up to 16; row_pair[m] = owning pair (-1 past the end); m_packed[0] = rows
-    int32_t *pair_off = nullptr, *row_pair = nullptr, *m_packed = nullptr;
-    int32_t *sid = nullptr, *stt = nullptr;                            // staging of one chunk's [pairs][L_in] token / type ids
-    float* logits = nullptr;                                           // staging of one chunk's outputs, [pairs][out_width]
+    dev_buf<int32_t> pair_off, row_pair, m_packed;
+    dev_buf<int32_t> sid, stt;                                         // staging of one chunk's [pairs][L_in] token / type ids
+    dev_buf<float> logits;                                             // staging of one chunk's outputs, [pairs][out_width]
 };
 
-struct rag_ce_model {
+// activation workspace of the split-fp16 forward (sized for ws_tokens); dropped by assigning an empty one
+struct ce_split_ws {
+    int64_t ws_tokens = 0;
+    int ws_pairs = 0, ws_L = 0;
+    dev_buf<float> y32;                                // pre-LayerNorm sums of the residual GEMMs (fp32 [tokens][hidden])
+    dev_buf<half_t> x16, q16, kf16, vf16, ctx16, h16;
+    ce_chunk_bufs io;
+};
+
+struct rag_ce_model : ce_split_ws {
     rag_ce_config cfg;
     bool embed = false;          // true: sentence-embedding encoder (mean pooling over the tokens, no pooler / classifier head)
     int normalize = 1;           // embed: L2-normalise the pooled vectors
     int out_width = 1;           // floats per pair the forward produces: 1 logit, or `hidden` for an embedding model
     // embeddings fp32
-    float *word = nullptr, *pos = nullptr, *type = nullptr, *emb_ln_g = nullptr, *emb_ln_b = nullptr;
+    dev_buf<float> word, pos, type, emb_ln_g, emb_ln_b;
     struct Layer {
-        half_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;      // fp16 [out][in]
-        char *wqkv8 = nullptr, *wo8 = nullptr, *w18 = nullptr, *w28 = nullptr;     // the same matrices as hi16 + lo8 images (ce_mx.h), when the shape allows
-        float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
-        float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
+        dev_buf<half_t> wqkv, wo, w1, w2;              // fp16 [out][in]
+        dev_buf<char> wqkv8, wo8, w18, w28;            // the same matrices as hi16 + lo8 images (ce_mx.h), when the shape allows
+        dev_buf<float> bqkv, bo, b1, b2;
+        dev_buf<float> ln1_g, ln1_b, ln2_g, ln2_b;
     };
     std::vector<Layer> layers;
-    float *wp = nullptr, *bp = nullptr, *wc = nullptr, *bc = nullptr;            // pooler / classifier fp32
-    float* wpT = nullptr;                                                         // pooler matrix transposed (mx_pool_classify_kernel)
-    std::vector<void*> allocs;
-    // activation workspace of the split-fp16 forward (sized for ws_tokens)
-    int64_t ws_tokens = 0;
-    int ws_pairs = 0, ws_L = 0;
-    float* y32 = nullptr;                              // pre-LayerNorm sums of the residual GEMMs (fp32 [tokens][hidden])
-    half_t *x16 = nullptr, *q16 = nullptr, *kf16 = nullptr, *vf16 = nullptr, *ctx16 = nullptr, *h16 = nullptr;
-    ce_chunk_bufs io;
+    dev_buf<float> wp, bp, wc, bc;                     // pooler / classifier fp32
+    dev_buf<float> wpT;                                // pooler matrix transposed (mx_pool_classify_kernel)
     // the MX forward (ce_mx.h: hi16 + lo8 operands) has a workspace of its own: it runs every model whose shape allows it, the
     // split-fp16 kernels the others (and option ce_mx = -1), and neither path must size or evict the other's buffers
     bool mx_ok = false;                                // the shape allows the MX path (hidden 384, ffn a multiple of 384 up to 1536) and its weights are loaded
@@ -78,10 +80,10 @@ struct rag_ce_model {
     struct MxWs {
         int pairs = 0, L = 0;
         int64_t tokens = 0;                            // padded rows (a multiple of 256)
-        char *x8 = nullptr, *ctx8 = nullptr, *h8 = nullptr;              // residual stream, attention output, FFN intermediate (image layout)
-        char *xc8 = nullptr, *cc8 = nullptr, *hc8 = nullptr;             // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
-        int32_t* m_cls = nullptr;                                        // device scalar: rows of the compact tensors (= pairs of the chunk)
-        half_t *qf16 = nullptr, *kf16 = nullptr, *vf16 = nullptr;       // Q, K, V in the attention kernel's fragment order (hi | lo planes)
+        dev_buf<char> x8, ctx8, h8;                    // residual stream, attention output, FFN intermediate (image layout)
+        dev_buf<char> xc8, cc8, hc8;                   // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
+        dev_buf<int32_t> m_cls;                        // device scalar: rows of the compact tensors (= pairs of the chunk)
+        dev_buf<half_t> qf16, kf16, vf16;              // Q, K, V in the attention kernel's fragment order (hi | lo planes)
         ce_chunk_bufs io;
     } mx;
 };
@@ -833,88 +835,48 @@ __global__ void ce_f32_split_kernel(const float* __restrict__ in, half_t* __rest
 
 // ------------------------------------------------------------------------------------------------
 static int chunk_bufs_alloc(rag_ctx* h, ce_chunk_bufs& c, int P, int L, int64_t Mp, int out_width) {
-    HIP_TRY(h, hipMalloc(&c.ids, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&c.tt, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&c.lens, (size_t)P * 4));
-    HIP_TRY(h, hipMalloc(&c.pair_off, (size_t)(P + 1) * 4));
-    HIP_TRY(h, hipMalloc(&c.row_pair, (size_t)Mp * 4));
-    HIP_TRY(h, hipMalloc(&c.m_packed, 4));
-    HIP_TRY(h, hipMalloc(&c.sid, (size_t)P * L * 4));            // L_in <= L
-    HIP_TRY(h, hipMalloc(&c.stt, (size_t)P * L * 4));
-    HIP_TRY(h, hipMalloc(&c.logits, (size_t)P * out_width * 4));
-    return RAG_OK;
-}
-
-static void chunk_bufs_free(ce_chunk_bufs& c) {
-    hipFree(c.ids); hipFree(c.tt); hipFree(c.lens); hipFree(c.pair_off); hipFree(c.row_pair); hipFree(c.m_packed);
-    hipFree(c.sid); hipFree(c.stt); hipFree(c.logits);
-    c = ce_chunk_bufs();
-}
-
-static void ce_free_ws(rag_ce_model* m) {
-    hipFree(m->y32); hipFree(m->x16); hipFree(m->q16); hipFree(m->kf16); hipFree(m->vf16); hipFree(m->ctx16); hipFree(m->h16);
-    m->y32 = nullptr; m->x16 = m->q16 = m->kf16 = m->vf16 = m->ctx16 = m->h16 = nullptr;
-    chunk_bufs_free(m->io);
-    m->ws_tokens = 0; m->ws_pairs = 0; m->ws_L = 0;
-}
-
-static void mx_free_ws(rag_ce_model* m) {
-    auto& w = m->mx;
-    hipFree(w.x8); hipFree(w.ctx8); hipFree(w.h8); hipFree(w.qf16); hipFree(w.kf16); hipFree(w.vf16);
-    hipFree(w.xc8); hipFree(w.cc8); hipFree(w.hc8); hipFree(w.m_cls);
-    chunk_bufs_free(w.io);
-    w = rag_ce_model::MxWs();
-}
-
-static void ce_free_model(rag_ce_model** slot) {
-    if (!*slot) return;
-    for (void* p : (*slot)->allocs) hipFree(p);
-    ce_free_ws(*slot);
-    mx_free_ws(*slot);
-    delete *slot;
-    *slot = nullptr;
+    int rc;
+    if ((rc = c.ids.alloc(h, (size_t)Mp))) return rc;
+    if ((rc = c.tt.alloc(h, (size_t)Mp))) return rc;
+    if ((rc = c.lens.alloc(h, (size_t)P))) return rc;
+    if ((rc = c.pair_off.alloc(h, (size_t)P + 1))) return rc;
+    if ((rc = c.row_pair.alloc(h, (size_t)Mp))) return rc;
+    if ((rc = c.m_packed.alloc(h, 1))) return rc;
+    if ((rc = c.sid.alloc(h, (size_t)P * L))) return rc;              // L_in <= L
+    if ((rc = c.stt.alloc(h, (size_t)P * L))) return rc;
+    return c.logits.alloc(h, (size_t)P * out_width);
 }
 
 void ce_free(rag_ctx* h) {
-    ce_free_model(&h->ce);
-    ce_free_model(&h->emb);
+    delete h->ce;
+    delete h->emb;
+    h->ce = h->emb = nullptr;
 }
 
-static int up_f32(rag_ctx* h, rag_ce_model* m, const float* src, size_t n, float** dst) {
-    HIP_TRY(h, hipMalloc(dst, n * sizeof(float)));
-    m->allocs.push_back(*dst);
-    HIP_TRY(h, hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+static int up_f32(rag_ctx* h, const float* src, size_t n, dev_buf<float>& dst) {
+    if (int rc = dst.alloc(h, n)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     return RAG_OK;
 }
 
-// rows of several fp32 host matrices (same `cols`) concatenated -> one fp16 device matrix
-static int up_f16_concat(rag_ctx* h, rag_ce_model* m, std::vector<const float*> srcs, size_t rows_each, size_t cols, half_t** dst) {
+// rows of several fp32 host matrices (same `cols`) concatenated -> one device matrix: split fp16 (hi plane | lo plane) for a
+// half_t destination, the hi16 + lo8 image tensor (ce_mx.h) for a char one
+template <class T>
+static int up_concat(rag_ctx* h, std::vector<const float*> srcs, size_t rows_each, size_t cols, dev_buf<T>& dst) {
+    constexpr bool mx = std::is_same<T, char>::value;
     const size_t n_each = rows_each * cols, total = n_each * srcs.size();
-    float* tmp = nullptr;
-    HIP_TRY(h, hipMalloc(&tmp, total * sizeof(float)));
-    HIP_TRY(h, hipMalloc(dst, 2 * total * sizeof(half_t)));      // hi plane | lo plane
-    m->allocs.push_back(*dst);
+    dev_buf<float> tmp;
+    int rc;
+    if ((rc = tmp.alloc(h, total))) return rc;
+    if ((rc = dst.alloc(h, (mx ? 3 : 2) * total))) return rc;
     for (size_t i = 0; i < srcs.size(); ++i)
         HIP_TRY(h, hipMemcpyAsync(tmp + i * n_each, srcs[i], n_each * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(ce_f32_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp, *dst, (int64_t)total, (int)cols);
+    if constexpr (mx)
+        hipLaunchKernelGGL(mx_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp.get(),
+                           (int)(rows_each * srcs.size()), (int)cols, dst.get());
+    else
+        hipLaunchKernelGGL(ce_f32_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp.get(), dst.get(), (int64_t)total, (int)cols);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(tmp);
-    return RAG_OK;
-}
-
-// rows of several fp32 host matrices (same `cols`) concatenated -> one hi16 + lo8 image tensor (ce_mx.h)
-static int up_mx_concat(rag_ctx* h, rag_ce_model* m, std::vector<const float*> srcs, size_t rows_each, size_t cols, char** dst) {
-    const size_t n_each = rows_each * cols, total = n_each * srcs.size();
-    float* tmp = nullptr;
-    HIP_TRY(h, hipMalloc(&tmp, total * sizeof(float)));
-    HIP_TRY(h, hipMalloc(dst, 3 * total));
-    m->allocs.push_back(*dst);
-    for (size_t i = 0; i < srcs.size(); ++i)
-        HIP_TRY(h, hipMemcpyAsync(tmp + i * n_each, srcs[i], n_each * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(mx_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp, (int)(rows_each * srcs.size()),
-                       (int)cols, *dst);
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(tmp);
     return RAG_OK;
 }
 
@@ -929,60 +891,59 @@ static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* cons
     ARG_CHECK(h, cfg->hidden % 128 == 0 && cfg->hidden <= 1024 && cfg->ffn % 128 == 0, "ce_load: hidden/ffn must be multiples of 128");
     ARG_CHECK(h, cfg->heads > 0 && cfg->hidden / cfg->heads == 32, "ce_load: head dim must be 32");
     ARG_CHECK(h, n == 5 + 16 * cfg->layers + (embed ? 0 : 4), "ce_load: wrong tensor count");
-    ce_free_model(slot);
-    rag_ce_model* m = new rag_ce_model();
-    *slot = m;
+    delete *slot;
+    rag_ce_model* m = *slot = new rag_ce_model();
     m->cfg = *cfg;
     m->embed = embed;
     m->normalize = normalize;
     m->out_width = embed ? cfg->hidden : 1;
     const size_t H = cfg->hidden, F = cfg->ffn;
     int rc;
-    if ((rc = up_f32(h, m, T[0], (size_t)cfg->vocab_size * H, &m->word))) return rc;
-    if ((rc = up_f32(h, m, T[1], (size_t)cfg->max_pos * H, &m->pos))) return rc;
-    if ((rc = up_f32(h, m, T[2], (size_t)cfg->type_vocab * H, &m->type))) return rc;
-    if ((rc = up_f32(h, m, T[3], H, &m->emb_ln_g))) return rc;
-    if ((rc = up_f32(h, m, T[4], H, &m->emb_ln_b))) return rc;
+    if ((rc = up_f32(h, T[0], (size_t)cfg->vocab_size * H, m->word))) return rc;
+    if ((rc = up_f32(h, T[1], (size_t)cfg->max_pos * H, m->pos))) return rc;
+    if ((rc = up_f32(h, T[2], (size_t)cfg->type_vocab * H, m->type))) return rc;
+    if ((rc = up_f32(h, T[3], H, m->emb_ln_g))) return rc;
+    if ((rc = up_f32(h, T[4], H, m->emb_ln_b))) return rc;
     m->layers.resize(cfg->layers);
     m->mx_ok = H == MX_TM && F % MX_TM == 0 && F <= 1536;    // one feature tile = the hidden state (LayerNorm in the epilogue); the FFN bias is staged in 6 KiB of LDS
     for (int l = 0; l < cfg->layers; ++l) {
         const float* const* t = T + 5 + 16 * l;
         auto& ly = m->layers[l];
         if (m->mx_ok) {
-            if ((rc = up_mx_concat(h, m, {t[0], t[2], t[4]}, H, H, &ly.wqkv8))) return rc;
-            if ((rc = up_mx_concat(h, m, {t[6]}, H, H, &ly.wo8))) return rc;
-            if ((rc = up_mx_concat(h, m, {t[10]}, F, H, &ly.w18))) return rc;
-            if ((rc = up_mx_concat(h, m, {t[12]}, H, F, &ly.w28))) return rc;
+            if ((rc = up_concat(h, {t[0], t[2], t[4]}, H, H, ly.wqkv8))) return rc;
+            if ((rc = up_concat(h, {t[6]}, H, H, ly.wo8))) return rc;
+            if ((rc = up_concat(h, {t[10]}, F, H, ly.w18))) return rc;
+            if ((rc = up_concat(h, {t[12]}, H, F, ly.w28))) return rc;
         }
-        if ((rc = up_f16_concat(h, m, {t[0], t[2], t[4]}, H, H, &ly.wqkv))) return rc;
+        if ((rc = up_concat(h, {t[0], t[2], t[4]}, H, H, ly.wqkv))) return rc;
         std::vector<float> bq(3 * H);
         std::memcpy(bq.data(), t[1], H * 4); std::memcpy(bq.data() + H, t[3], H * 4); std::memcpy(bq.data() + 2 * H, t[5], H * 4);
-        if ((rc = up_f32(h, m, bq.data(), 3 * H, &ly.bqkv))) return rc;
+        if ((rc = up_f32(h, bq.data(), 3 * H, ly.bqkv))) return rc;
         HIP_TRY(h, hipStreamSynchronize(h->stream));          // bq is a stack-lifetime buffer
-        if ((rc = up_f16_concat(h, m, {t[6]}, H, H, &ly.wo))) return rc;
-        if ((rc = up_f32(h, m, t[7], H, &ly.bo))) return rc;
-        if ((rc = up_f32(h, m, t[8], H, &ly.ln1_g))) return rc;
-        if ((rc = up_f32(h, m, t[9], H, &ly.ln1_b))) return rc;
-        if ((rc = up_f16_concat(h, m, {t[10]}, F, H, &ly.w1))) return rc;
-        if ((rc = up_f32(h, m, t[11], F, &ly.b1))) return rc;
-        if ((rc = up_f16_concat(h, m, {t[12]}, H, F, &ly.w2))) return rc;
-        if ((rc = up_f32(h, m, t[13], H, &ly.b2))) return rc;
-        if ((rc = up_f32(h, m, t[14], H, &ly.ln2_g))) return rc;
-        if ((rc = up_f32(h, m, t[15], H, &ly.ln2_b))) return rc;
+        if ((rc = up_concat(h, {t[6]}, H, H, ly.wo))) return rc;
+        if ((rc = up_f32(h, t[7], H, ly.bo))) return rc;
+        if ((rc = up_f32(h, t[8], H, ly.ln1_g))) return rc;
+        if ((rc = up_f32(h, t[9], H, ly.ln1_b))) return rc;
+        if ((rc = up_concat(h, {t[10]}, F, H, ly.w1))) return rc;
+        if ((rc = up_f32(h, t[11], F, ly.b1))) return rc;
+        if ((rc = up_concat(h, {t[12]}, H, F, ly.w2))) return rc;
+        if ((rc = up_f32(h, t[13], H, ly.b2))) return rc;
+        if ((rc = up_f32(h, t[14], H, ly.ln2_g))) return rc;
+        if ((rc = up_f32(h, t[15], H, ly.ln2_b))) return rc;
     }
     if (!embed) {
         const float* const* t = T + 5 + 16 * cfg->layers;
-        if ((rc = up_f32(h, m, t[0], H * H, &m->wp))) return rc;
+        if ((rc = up_f32(h, t[0], H * H, m->wp))) return rc;
         {
             std::vector<float> tr(H * H);
             for (size_t n = 0; n < H; ++n)
                 for (size_t k = 0; k < H; ++k) tr[k * H + n] = t[0][n * H + k];
-            if ((rc = up_f32(h, m, tr.data(), H * H, &m->wpT))) return rc;
+            if ((rc = up_f32(h, tr.data(), H * H, m->wpT))) return rc;
             HIP_TRY(h, hipStreamSynchronize(h->stream));          // tr is a stack-lifetime buffer
         }
-        if ((rc = up_f32(h, m, t[1], H, &m->bp))) return rc;
-        if ((rc = up_f32(h, m, t[2], H, &m->wc))) return rc;
-        if ((rc = up_f32(h, m, t[3], 1, &m->bc))) return rc;
+        if ((rc = up_f32(h, t[1], H, m->bp))) return rc;
+        if ((rc = up_f32(h, t[2], H, m->wc))) return rc;
+        if ((rc = up_f32(h, t[3], 1, m->bc))) return rc;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return m->mx_ok && !embed ? ce_probe_mx(h, m) : RAG_OK;
@@ -998,10 +959,15 @@ int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T,
 
 static const int kAttnL[] = {32, 64, 96, 128, 192, 256, 384, 512};
 
+// halfs per K / V fragment plane of Mp padded rows (both forwards)
+static size_t kv_plane_halfs(int64_t Mp, size_t H) { return (size_t)Mp * H + 2048; }
+// persistent GEMM grid: one workgroup per compute unit, a multiple of 8 (the XCD-aware tile map)
+static unsigned ce_gemm_grid(const rag_ctx* h) { return (unsigned)(h->n_cu >= 8 ? h->n_cu / 8 * 8 : 256); }
+
 struct ce_planes { size_t x, q, kv, ctx, h; };
 static ce_planes planes_for(const rag_ce_model* m, int64_t Mp) {
     const size_t H = m->cfg.hidden, F = m->cfg.ffn;
-    return {(size_t)Mp * H, (size_t)Mp * H, (size_t)Mp * H + 2048, (size_t)Mp * H, (size_t)Mp * F};
+    return {(size_t)Mp * H, (size_t)Mp * H, kv_plane_halfs(Mp, H), (size_t)Mp * H, (size_t)Mp * F};
 }
 
 template <int QB>
@@ -1059,7 +1025,7 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
     hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, io.pair_off, P, L, Mp, io.row_pair);
     CE_PER_DISPATCH(EMB)
     const dim3 blk(512);
-    static const unsigned n_cu = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return (unsigned)(n >= 8 ? n / 8 * 8 : 256); }();
+    const unsigned n_cu = ce_gemm_grid(h);
     for (int l = 0; l < m->cfg.layers; ++l) {
         auto& ly = m->layers[l];
         CE_GEMM(EPI_QKV, ly.wqkv, m->x16,
@@ -1097,18 +1063,20 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
 // reallocation could otherwise start before its buffers were cleared)
 static int ce_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
     if (P <= m->ws_pairs && L == m->ws_L) return RAG_OK;
-    ce_free_ws(m);
+    ce_split_ws& w = *m;
+    w = ce_split_ws();
     const int64_t Mp = round_up((int64_t)P * L, CE_BN);
-    m->ws_pairs = P;                                     // planes_for() uses the allocated pair count
+    w.ws_pairs = P;                                      // planes_for() uses the allocated pair count
     const ce_planes pp = planes_for(m, Mp);
-    HIP_TRY(h, hipMalloc(&m->x16, 2 * pp.x * 2));
-    HIP_TRY(h, hipMalloc(&m->q16, 2 * pp.q * 2));
-    HIP_TRY(h, hipMalloc(&m->kf16, 2 * pp.kv * 2));
-    HIP_TRY(h, hipMalloc(&m->vf16, 2 * pp.kv * 2));
-    HIP_TRY(h, hipMalloc(&m->ctx16, 2 * pp.ctx * 2));
-    HIP_TRY(h, hipMalloc(&m->h16, 2 * pp.h * 2));
-    HIP_TRY(h, hipMalloc(&m->y32, pp.x * 4));
-    if (int rc = chunk_bufs_alloc(h, m->io, P, L, Mp, m->out_width)) return rc;
+    int rc;
+    if ((rc = w.x16.alloc(h, 2 * pp.x))) return rc;
+    if ((rc = w.q16.alloc(h, 2 * pp.q))) return rc;
+    if ((rc = w.kf16.alloc(h, 2 * pp.kv))) return rc;
+    if ((rc = w.vf16.alloc(h, 2 * pp.kv))) return rc;
+    if ((rc = w.ctx16.alloc(h, 2 * pp.ctx))) return rc;
+    if ((rc = w.h16.alloc(h, 2 * pp.h))) return rc;
+    if ((rc = w.y32.alloc(h, pp.x))) return rc;
+    if ((rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width))) return rc;
     // padded token rows are read by the GEMM tiles: keep them finite
     HIP_TRY(h, hipMemsetAsync(m->x16, 0, 2 * pp.x * 2, st));
     HIP_TRY(h, hipMemsetAsync(m->ctx16, 0, 2 * pp.ctx * 2, st));
@@ -1128,25 +1096,26 @@ static int mx_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t s
     auto& w = m->mx;
     if (P <= w.pairs && L == w.L) return RAG_OK;
     HIP_TRY(h, hipStreamSynchronize(st));
-    mx_free_ws(m);
+    w = rag_ce_model::MxWs();
     const size_t H = m->cfg.hidden, F = m->cfg.ffn;
     const int64_t Mp = round_up((int64_t)P * L, 256);
-    const size_t kv = (size_t)Mp * H + 2048;                       // halfs per plane of qf16 / kf16 / vf16
-    HIP_TRY(h, hipMalloc(&w.x8, (size_t)Mp * H * 3));
-    HIP_TRY(h, hipMalloc(&w.ctx8, (size_t)Mp * H * 3));
-    HIP_TRY(h, hipMalloc(&w.h8, (size_t)Mp * F * 3));
+    const size_t kv = kv_plane_halfs(Mp, H);
+    int rc;
+    if ((rc = w.x8.alloc(h, (size_t)Mp * H * 3))) return rc;
+    if ((rc = w.ctx8.alloc(h, (size_t)Mp * H * 3))) return rc;
+    if ((rc = w.h8.alloc(h, (size_t)Mp * F * 3))) return rc;
     const int64_t Pp = round_up((int64_t)P, MX_TN);
-    HIP_TRY(h, hipMalloc(&w.xc8, (size_t)Pp * H * 3));
-    HIP_TRY(h, hipMalloc(&w.cc8, (size_t)Pp * H * 3));
-    HIP_TRY(h, hipMalloc(&w.hc8, (size_t)Pp * F * 3));
-    HIP_TRY(h, hipMalloc(&w.m_cls, 4));
+    if ((rc = w.xc8.alloc(h, (size_t)Pp * H * 3))) return rc;
+    if ((rc = w.cc8.alloc(h, (size_t)Pp * H * 3))) return rc;
+    if ((rc = w.hc8.alloc(h, (size_t)Pp * F * 3))) return rc;
+    if ((rc = w.m_cls.alloc(h, 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(w.xc8, 0, (size_t)Pp * H * 3, st));
     HIP_TRY(h, hipMemsetAsync(w.cc8, 0, (size_t)Pp * H * 3, st));
     HIP_TRY(h, hipMemsetAsync(w.hc8, 0, (size_t)Pp * F * 3, st));
-    HIP_TRY(h, hipMalloc(&w.qf16, 2 * kv * 2));
-    HIP_TRY(h, hipMalloc(&w.kf16, 2 * kv * 2));
-    HIP_TRY(h, hipMalloc(&w.vf16, 2 * kv * 2));
-    if (int rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width)) return rc;
+    if ((rc = w.qf16.alloc(h, 2 * kv))) return rc;
+    if ((rc = w.kf16.alloc(h, 2 * kv))) return rc;
+    if ((rc = w.vf16.alloc(h, 2 * kv))) return rc;
+    if ((rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width))) return rc;
     // rows past a chunk's packed rows are read by the last token tile of every GEMM: keep them finite (zero is a valid image)
     HIP_TRY(h, hipMemsetAsync(w.x8, 0, (size_t)Mp * H * 3, st));
     HIP_TRY(h, hipMemsetAsync(w.ctx8, 0, (size_t)Mp * H * 3, st));
@@ -1173,12 +1142,12 @@ static int mx_launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, size_t
     if (max_qblocks == 1) {                                  // the [CLS]-only last layer: one wave per (head, pair), no LDS
         hipLaunchKernelGGL((ce_attention_kernel<1, true, true>), dim3(m->cfg.heads, P), dim3(64), 0, st, (const half_t*)w.qf16,
                            (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
-                           m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8), 1);
+                           m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8.get()), 1);
         return RAG_OK;
     }
     hipLaunchKernelGGL((ce_attention_kernel<QB, true>), dim3(m->cfg.heads, P), dim3(64 * (L / (16 * QB))), lds, st, (const half_t*)w.qf16,
                        (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
-                       m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8), max_qblocks);
+                       m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8.get()), max_qblocks);
     return RAG_OK;
 }
 
@@ -1187,7 +1156,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
     const int H = m->cfg.hidden, F = m->cfg.ffn;
     const int64_t M = (int64_t)P * L, Mp = w.tokens;
     const float eps = (float)m->cfg.ln_eps;
-    const size_t kv_plane = (size_t)Mp * H + 2048;
+    const size_t kv_plane = kv_plane_halfs(Mp, H);
     if (!h->attr_ce_mx) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_qkv>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_gelu>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
@@ -1199,7 +1168,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
     hipLaunchKernelGGL(mx_embed_ln_kernel, dim3((unsigned)((M + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, (const int32_t*)w.io.ids, (const int32_t*)w.io.tt,
                        (const float*)m->word, (const float*)m->pos, (const float*)m->type, (const float*)m->emb_ln_g, (const float*)m->emb_ln_b,
                        (const int32_t*)w.io.m_packed, (const int32_t*)w.io.row_pair, (const int32_t*)w.io.pair_off, L, m->cfg.vocab_size, eps, w.x8);
-    static const unsigned n_cu = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return (unsigned)(n >= 8 ? n / 8 * 8 : 256); }();
+    const unsigned n_cu = ce_gemm_grid(h);
     const dim3 blk(512);
     for (int l = 0; l < m->cfg.layers; ++l) {
         auto& ly = m->layers[l];
@@ -1241,7 +1210,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
                 hipLaunchKernelGGL(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, (const char*)w.xc8,
                                    (const float*)m->wpT, (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, P, H, logits_dev);
             else
-                hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.xc8), (const float*)m->wp,
+                hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.xc8.get()), (const float*)m->wp,
                                    (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)nullptr, H, logits_dev);
             HIP_TRY(h, hipGetLastError());
             return RAG_OK;
@@ -1254,10 +1223,10 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
                            (const int32_t*)w.io.m_packed, mx_epi_ln{w.x8, ly.b2, ly.ln2_g, ly.ln2_b, eps});
     }
     if (m->embed)
-        hipLaunchKernelGGL(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8), (const int32_t*)w.io.pair_off, lens_dev,
+        hipLaunchKernelGGL(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), (const int32_t*)w.io.pair_off, lens_dev,
                            L, H, m->normalize, logits_dev);
     else
-        hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8), (const float*)m->wp,
+        hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), (const float*)m->wp,
                            (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)w.io.pair_off, H, logits_dev);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
@@ -1366,8 +1335,8 @@ static int ce_probe_mx(rag_ctx* h, rag_ce_model* m) {
     std::vector<float> mx(P), sp(P);
     int rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, mx.data(), h->stream, true, true);
     if (!rc) rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, sp.data(), h->stream, true, false);
-    ce_free_ws(m);                                      // the next call sizes its workspace for its own batch
-    mx_free_ws(m);
+    static_cast<ce_split_ws&>(*m) = ce_split_ws();      // the next call sizes its workspace for its own batch
+    m->mx = rag_ce_model::MxWs();
     if (rc) return rc;
     float d = 0.f;
     for (int p = 0; p < P; ++p)

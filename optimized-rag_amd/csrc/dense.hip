@@ -924,32 +924,31 @@ __global__ void search_init_kernel(float* __restrict__ tau, float* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 static int ensure_workspace(rag_ctx* h, int Q, hipStream_t st) {
     if (Q <= h->ws_q) return RAG_OK;
-    hipFree(h->q32); hipFree(h->q16); hipFree(h->cand); hipFree(h->cnt); hipFree(h->tau); hipFree(h->bound);
-    hipFree(h->n_sorted); hipFree(h->exact); hipFree(h->flag); hipFree(h->scan_list);
     h->ws_q = 0;
-    const int64_t qpad = round_up(Q, RAG_TILE);
-    HIP_TRY(h, hipMalloc(&h->q32, (size_t)Q * h->dim * sizeof(float)));
-    HIP_TRY(h, hipMalloc(&h->q16, (size_t)qpad * h->dim_pad * sizeof(half_t)));
-    HIP_TRY(h, hipMalloc(&h->cand, (size_t)qpad * RAG_CAND_CAP * sizeof(uint64_t)));
-    HIP_TRY(h, hipMalloc(&h->cnt, (size_t)qpad * sizeof(unsigned)));
-    HIP_TRY(h, hipMalloc(&h->tau, (size_t)qpad * sizeof(float)));
-    HIP_TRY(h, hipMalloc(&h->bound, (size_t)qpad * sizeof(float)));
-    HIP_TRY(h, hipMalloc(&h->n_sorted, (size_t)qpad * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->exact, (size_t)qpad * RAG_CAND_CAP * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->flag, (size_t)qpad * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->scan_list, (size_t)qpad * sizeof(int)));
-    if (!h->stats) HIP_TRY(h, hipMalloc(&h->stats, 8 * sizeof(int)));
+    const size_t qpad = (size_t)round_up(Q, RAG_TILE);
+    int rc;
+    if ((rc = h->q32.alloc(h, (size_t)Q * h->dim))) return rc;
+    if ((rc = h->q16.alloc(h, qpad * h->dim_pad))) return rc;
+    if ((rc = h->cand.alloc(h, qpad * RAG_CAND_CAP))) return rc;
+    if ((rc = h->cnt.alloc(h, qpad))) return rc;
+    if ((rc = h->tau.alloc(h, qpad))) return rc;
+    if ((rc = h->bound.alloc(h, qpad))) return rc;
+    if ((rc = h->n_sorted.alloc(h, qpad))) return rc;
+    if ((rc = h->exact.alloc(h, qpad * RAG_CAND_CAP))) return rc;
+    if ((rc = h->flag.alloc(h, qpad))) return rc;
+    if ((rc = h->scan_list.alloc(h, qpad))) return rc;
+    if ((rc = h->stats.reserve(h, 8))) return rc;
     // zero fills go on the search's own stream: a null-stream hipMemset is not ordered against a non-blocking stream
-    HIP_TRY(h, hipMemsetAsync(h->q16, 0, (size_t)qpad * h->dim_pad * sizeof(half_t), st));
+    HIP_TRY(h, hipMemsetAsync(h->q16, 0, qpad * h->dim_pad * sizeof(half_t), st));
     h->q16_dirty = 0;
     if (!h->q16b) {      // second pass (overflowed queries): one 256-query tile, allocated once per handle
-        HIP_TRY(h, hipMalloc(&h->q16b, (size_t)RAG_TILE * h->dim_pad * sizeof(half_t)));
-        HIP_TRY(h, hipMalloc(&h->candb, (size_t)RAG_TILE * RAG_CAND_CAP * sizeof(uint64_t)));
-        HIP_TRY(h, hipMalloc(&h->cntb, RAG_TILE * sizeof(unsigned)));
-        HIP_TRY(h, hipMalloc(&h->taub, RAG_TILE * sizeof(float)));
-        HIP_TRY(h, hipMalloc(&h->boundb, RAG_TILE * sizeof(float)));
-        HIP_TRY(h, hipMalloc(&h->n_sortedb, RAG_TILE * sizeof(int)));
-        HIP_TRY(h, hipMalloc(&h->ovf_list, (RAG_TILE + 1) * sizeof(int)));
+        if ((rc = h->q16b.alloc(h, (size_t)RAG_TILE * h->dim_pad))) return rc;
+        if ((rc = h->candb.alloc(h, (size_t)RAG_TILE * RAG_CAND_CAP))) return rc;
+        if ((rc = h->cntb.alloc(h, RAG_TILE))) return rc;
+        if ((rc = h->taub.alloc(h, RAG_TILE))) return rc;
+        if ((rc = h->boundb.alloc(h, RAG_TILE))) return rc;
+        if ((rc = h->n_sortedb.alloc(h, RAG_TILE))) return rc;
+        if ((rc = h->ovf_list.alloc(h, RAG_TILE + 1))) return rc;
         HIP_TRY(h, hipMemsetAsync(h->ovf_list, 0, (RAG_TILE + 1) * sizeof(int), st));
         HIP_TRY(h, hipMemsetAsync(h->q16b, 0, (size_t)RAG_TILE * h->dim_pad * sizeof(half_t), st));
     }
@@ -987,15 +986,10 @@ static int tenant_lists_upload(rag_ctx* h, tenant_list_map& lists, int64_t n_row
         span[kv.first] = {(int64_t)flat.size(), (int)kv.second.size()};
         flat.insert(flat.end(), kv.second.begin(), kv.second.end());
     }
-    int32_t* dev = nullptr;
-    HIP_TRY(h, hipMalloc(&dev, std::max<size_t>(1, flat.size()) * sizeof(int32_t)));
-    const hipError_t e = hipMemcpy(dev, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(dev);
-        HIP_TRY(h, e);
-    }
-    hipFree(h->tenant_tiles);
-    h->tenant_tiles = dev;
+    dev_buf<int32_t> dev;
+    if (int rc = dev.alloc(h, std::max<size_t>(1, flat.size()))) return rc;
+    HIP_TRY(h, hipMemcpy(dev, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->tenant_tiles = std::move(dev);
     h->tenant_span.swap(span);
     h->tenant_lists.swap(lists);
     h->tenant_rows = n_rows;
@@ -1003,8 +997,7 @@ static int tenant_lists_upload(rag_ctx* h, tenant_list_map& lists, int64_t n_row
 }
 
 int dense_build_tenant_tiles(rag_ctx* h, const int32_t* tenants_host, int64_t n_rows) {
-    hipFree(h->tenant_tiles);
-    h->tenant_tiles = nullptr;
+    h->tenant_tiles.reset();
     h->tenant_span.clear();
     h->tenant_lists.clear();
     h->tenant_rows = 0;
@@ -1023,11 +1016,9 @@ int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t f
 }
 
 int dense_free(rag_ctx* h) {
-    hipFree(h->emb32); hipFree(h->emb16); hipFree(h->ids); hipFree(h->tenants); hipFree(h->bad_rows);
-    h->emb32 = nullptr; h->emb16 = nullptr; h->ids = nullptr; h->tenants = nullptr; h->bad_rows = nullptr;
-    hipFree(h->scan_scores); h->scan_scores = nullptr; h->scan_rows = 0;
-    hipFree(h->tenant_tiles); h->tenant_tiles = nullptr; h->tenant_span.clear(); h->tenant_lists.clear(); h->tenant_rows = 0;
-    hipFree(h->vis); h->vis = nullptr; h->n_deleted = 0;
+    static_cast<rag_index_mem&>(*h) = rag_index_mem();        // every plane of the index
+    h->tenant_span.clear(); h->tenant_lists.clear(); h->tenant_rows = 0;
+    h->n_deleted = 0;
     h->cap32 = h->cap_ids = h->cap_ten = h->cap_vis = 0;
     h->bm25_stale = false;
     h->n_rows = h->n_rows_pad = 0;
@@ -1040,8 +1031,9 @@ int dense_free(rag_ctx* h) {
 int dense_index_build(rag_ctx* h, const float* emb_dev, int64_t n_rows, hipStream_t st) {
     // pad to a multiple of 8 tiles so the XCD-aware block map needs no bounds logic on loads
     h->n_rows_pad = round_up(n_rows, (int64_t)RAG_TILE * 8);
-    HIP_TRY(h, hipMalloc(&h->emb16, (size_t)h->n_rows_pad * h->dim_pad * sizeof(half_t)));
-    HIP_TRY(h, hipMalloc(&h->bad_rows, sizeof(int)));
+    int rc;
+    if ((rc = h->emb16.alloc(h, (size_t)h->n_rows_pad * h->dim_pad))) return rc;
+    if ((rc = h->bad_rows.alloc(h, 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), st));
     if (h->n_rows_pad > n_rows)
         HIP_TRY(h, hipMemsetAsync(h->emb16 + (size_t)n_rows * h->dim_pad, 0,
@@ -1237,7 +1229,7 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
                            h->q16b, h->taub, h->boundb, h->cntb);
         {
             const int begin_ = 0, n_rt_ = total_tiles;
-            static const int n_cu = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
+            const int n_cu = h->n_cu;
             if (fz)
                 hipLaunchKernelGGL((dense_emit_persist_kernel<true>), dim3(std::min(n_cu, total_tiles)), dim3(512), DENSE_LDS_BYTES, st, total_tiles,
                                    EMIT_ARGS(h->q16b, 1, RAG_TILE, h->taub, h->cntb, h->candb, ovf_count, h->ovf_list));
@@ -1269,15 +1261,9 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
         // 1024-batch in ONE round = two idle launches per search), at least SCAN_ROUND
         const int round_q = std::min(Q, std::max(SCAN_ROUND, (int)std::min<size_t>(65535, ((size_t)512 << 20) / ((size_t)n_blocks * k * 12))));
         const size_t need = (size_t)round_q * n_blocks * k;
-        if ((int64_t)need > h->scan_rows) {
-            hipFree(h->scan_scores);
-            h->scan_scores = nullptr;
-            h->scan_rows = 0;
-            HIP_TRY(h, hipMalloc(&h->scan_scores, need * 12));
-            h->scan_rows = (int64_t)need;
-        }
-        uint64_t* pk = reinterpret_cast<uint64_t*>(h->scan_scores);
-        uint32_t* pr = reinterpret_cast<uint32_t*>(pk + h->scan_rows);
+        if (int rc = h->scan_scores.reserve(h, need * 12)) return rc;         // [entries] u64 keys | [entries] u32 rows
+        uint64_t* pk = reinterpret_cast<uint64_t*>(h->scan_scores.get());
+        uint32_t* pr = reinterpret_cast<uint32_t*>(pk + h->scan_scores.size() / 12);
         for (int f0 = 0; f0 < Q; f0 += round_q) {
             hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, h->n_rows,
                                rows_per_block, h->dim, k, scan_list, scan_count, f0, round_q, pk, pr, fz ? fz->raw : (const double*)nullptr,

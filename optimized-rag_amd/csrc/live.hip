@@ -110,11 +110,10 @@ static int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64
 int live_vis_extend(rag_ctx* h, int64_t first, int64_t n) {
     if (first + n > h->cap_vis) {
         const int64_t cap = std::max(first + n, std::max(h->cap32, h->n_rows));
-        int32_t* nv = nullptr;
-        HIP_TRY(h, hipMalloc(&nv, (size_t)cap * sizeof(int32_t)));
+        dev_buf<int32_t> nv;
+        if (int rc = nv.alloc(h, (size_t)cap)) return rc;
         if (h->vis && first > 0) HIP_TRY(h, hipMemcpy(nv, h->vis, (size_t)first * sizeof(int32_t), hipMemcpyDeviceToDevice));
-        hipFree(h->vis);
-        h->vis = nv;
+        h->vis = std::move(nv);
         h->cap_vis = cap;
     }
     if (n <= 0) return RAG_OK;
@@ -145,17 +144,13 @@ static int live_begin(rag_ctx* h) {
 
 // row-count-sized workspaces follow the row count: the linear-fusion workspace (its pad rows must read as zero) is
 // reallocated by the next rag_hybrid_linear_dev; the float64-scan scratch is sized per call
-static void live_rows_changed(rag_ctx* h) {
-    hipFree(h->lin_ws);
-    h->lin_ws = nullptr;
-    h->lin_ws_bytes = 0;
-}
+static void live_rows_changed(rag_ctx* h) { h->lin_ws.reset(); }
 
 // sorted, unique copy of an id array staged in the handle's arena; count slot behind it
 static int stage_id_set(rag_ctx* h, const std::vector<int64_t>& set, int64_t** set_dev, unsigned long long** count_dev) {
     int rc = stage_reserve(h, stage_size(set.size(), 8) + stage_size(1, 8));
     if (rc) return rc;
-    char* p = (char*)h->stage;
+    char* p = h->stage;
     *set_dev = stage_take<int64_t>(p, set.size());
     *count_dev = stage_take<unsigned long long>(p, 1);
     HIP_TRY(h, hipMemcpyAsync(*set_dev, set.data(), set.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
@@ -184,15 +179,6 @@ static int id_set_apply(rag_ctx* h, const std::vector<int64_t>& set, int tenant,
     *n_out = (int64_t)c;
     return RAG_OK;
 }
-
-// a grown plane: allocated before anything is changed (a failed allocation leaves the index as it was), swapped in after
-struct grown_plane {
-    void** slot;
-    int64_t* cap;       // null for emb16 (n_rows_pad)
-    int64_t new_cap;
-    size_t row_bytes;
-    void* p = nullptr;
-};
 
 static int64_t grow_cap(int64_t cap, int64_t need) { return need <= cap ? cap : std::max(need, cap + cap / 8 + 256); }
 
@@ -257,54 +243,61 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     // ---- capacity: first what rag_index_reserve left, then growth of every row-aligned plane (all allocated before any change)
     const int64_t need = n0 + n;
     const int64_t cap32 = grow_cap(std::max(h->cap32, n0), need);
-    std::vector<grown_plane> g;
-    if (cap32 != h->cap32 || !h->emb32) g.push_back({(void**)&h->emb32, &h->cap32, cap32, (size_t)h->dim * 4});
     const int64_t pad = round_up(std::max(need, cap32), (int64_t)RAG_TILE * 8);
-    if (need > h->n_rows_pad || !h->emb16) g.push_back({(void**)&h->emb16, nullptr, pad, (size_t)h->dim_pad * 2});
-    if (rb->ids && (!h->ids || need > h->cap_ids)) g.push_back({(void**)&h->ids, &h->cap_ids, h->ids ? grow_cap(h->cap_ids, need) : cap32, 8});
-    if (rb->tenants && (!h->tenants || need > h->cap_ten))
-        g.push_back({(void**)&h->tenants, &h->cap_ten, h->tenants ? grow_cap(h->cap_ten, need) : cap32, 4});
-    if (rb->temporal && (!h->temporal || need > h->cap_tmp))
-        g.push_back({(void**)&h->temporal, &h->cap_tmp, h->temporal ? grow_cap(h->cap_tmp, need) : cap32, 8});
-    if (h->vis && need > h->cap_vis) g.push_back({(void**)&h->vis, &h->cap_vis, grow_cap(h->cap_vis, need), 4});
-    if (has_tok && need > h->tok_cap) {
-        const int64_t tc = grow_cap(h->tok_cap, need);
-        g.push_back({(void**)&h->tok, &h->tok_cap, tc, (size_t)h->tok_L * 2});
-        g.push_back({(void**)&h->tok_len, nullptr, tc, 4});
-    }
-    for (auto& e : g) {
-        if (hipMalloc(&e.p, (size_t)e.new_cap * e.row_bytes) != hipSuccess) {
-            for (auto& f : g) hipFree(f.p);
-            (void)hipGetLastError();
-            h->err = "insert: out of device memory while growing the index (reserve headroom with rag_index_reserve)";
-            return RAG_ERR_NOMEM;
-        }
+    const int64_t cap_ids = h->ids ? grow_cap(h->cap_ids, need) : cap32, cap_ten = h->tenants ? grow_cap(h->cap_ten, need) : cap32;
+    const int64_t cap_tmp = h->temporal ? grow_cap(h->cap_tmp, need) : cap32, cap_vis = grow_cap(h->cap_vis, need);
+    const int64_t cap_tok = grow_cap(h->tok_cap, need);
+    rag_device_mem g;                    // the grown planes under the handle's field names: dropped whole unless committed below
+    bool ok = true;
+    auto grow = [&](auto& plane, bool wanted, int64_t rows, size_t row_elems) {
+        ok = ok && (!wanted || plane.alloc(h, (size_t)rows * row_elems) == RAG_OK);
+    };
+    grow(g.emb32, cap32 != h->cap32 || !h->emb32, cap32, h->dim);
+    grow(g.emb16, need > h->n_rows_pad || !h->emb16, pad, h->dim_pad);
+    grow(g.ids, rb->ids && (!h->ids || need > h->cap_ids), cap_ids, 1);
+    grow(g.tenants, rb->tenants && (!h->tenants || need > h->cap_ten), cap_ten, 1);
+    grow(g.temporal, rb->temporal && (!h->temporal || need > h->cap_tmp), cap_tmp, 1);
+    grow(g.vis, h->vis && need > h->cap_vis, cap_vis, 1);
+    grow(g.tok, has_tok && need > h->tok_cap, cap_tok, h->tok_L);
+    grow(g.tok_len, has_tok && need > h->tok_cap, cap_tok, 1);
+    if (!ok) {
+        (void)hipGetLastError();
+        h->err = "insert: out of device memory while growing the index (reserve headroom with rag_index_reserve)";
+        return RAG_ERR_NOMEM;
     }
     hipStream_t st = h->stream;
     if (!h->index_loaded) {              // inserting on a handle with no index creates one
         if (!h->bad_rows) {
-            HIP_TRY(h, hipMalloc(&h->bad_rows, sizeof(int)));
+            if ((rc = h->bad_rows.alloc(h, 1))) return rc;
             HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), st));
         }
         h->n_rows = 0;
         h->id_base = 0;
         h->index_loaded = true;
     }
-    // ---- commit: move the used rows of each grown plane over (device to device), then free the old allocation
-    for (auto& e : g) {
-        void* old = *e.slot;
-        const bool is16 = e.slot == (void**)&h->emb16;
-        if (old && n0 > 0) HIP_TRY(h, hipMemcpyAsync(e.p, old, (size_t)n0 * e.row_bytes, hipMemcpyDeviceToDevice, st));
-        if (is16)            // tile padding and not-yet-written rows must read as zero vectors
-            HIP_TRY(h, hipMemsetAsync((char*)e.p + (size_t)n0 * e.row_bytes, 0, (size_t)(e.new_cap - n0) * e.row_bytes, st));
-        if (e.slot == (void**)&h->ids && !old && n0 > 0)      // implicit ids become a stored column (same values)
-            hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, (int64_t*)e.p, h->id_base, n0);
+    // ---- commit, per grown plane: copy the used rows over (device to device), then move the new allocation into the handle,
+    // which frees the old one
+    auto commit = [&](auto& plane, auto& grown, size_t row_elems, int64_t* cap, int64_t new_cap) -> int {
+        if (!grown) return RAG_OK;
+        if (plane && n0 > 0)
+            HIP_TRY(h, hipMemcpyAsync(grown, plane, (size_t)n0 * row_elems * sizeof(*grown.get()), hipMemcpyDeviceToDevice, st));
         HIP_TRY(h, hipStreamSynchronize(st));
-        hipFree(old);
-        *e.slot = e.p;
-        if (e.cap) *e.cap = e.new_cap;
-        if (is16) h->n_rows_pad = e.new_cap;
-    }
+        plane = std::move(grown);
+        if (cap) *cap = new_cap;
+        return RAG_OK;
+    };
+    if ((rc = commit(h->emb32, g.emb32, h->dim, &h->cap32, cap32))) return rc;
+    if (g.emb16)                         // tile padding and not-yet-written rows must read as zero vectors
+        HIP_TRY(h, hipMemsetAsync(g.emb16 + (size_t)n0 * h->dim_pad, 0, (size_t)(pad - n0) * h->dim_pad * sizeof(half_t), st));
+    if ((rc = commit(h->emb16, g.emb16, h->dim_pad, &h->n_rows_pad, pad))) return rc;
+    if (g.ids && !h->ids && n0 > 0)      // implicit ids become a stored column (same values)
+        hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, g.ids.get(), h->id_base, n0);
+    if ((rc = commit(h->ids, g.ids, 1, &h->cap_ids, cap_ids))) return rc;
+    if ((rc = commit(h->tenants, g.tenants, 1, &h->cap_ten, cap_ten))) return rc;
+    if ((rc = commit(h->temporal, g.temporal, 1, &h->cap_tmp, cap_tmp))) return rc;
+    if ((rc = commit(h->vis, g.vis, 1, &h->cap_vis, cap_vis))) return rc;
+    if ((rc = commit(h->tok, g.tok, h->tok_L, &h->tok_cap, cap_tok))) return rc;
+    if ((rc = commit(h->tok_len, g.tok_len, 1, nullptr, 0))) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->emb32 + (size_t)n0 * h->dim, rb->emb, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
     if ((rc = dense_index_normalize_range(h, n0, n, st))) return rc;
     if (rb->ids) HIP_TRY(h, hipMemcpyAsync(h->ids + n0, rb->ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
@@ -352,8 +345,7 @@ int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int
     int64_t n_del = 0;
     if ((rc = id_set_apply(h, set, tenant, 1, &n_del))) return rc;
     if (created && n_del == 0) {             // nothing deleted: keep the searches on their unfiltered path
-        hipFree(h->vis);
-        h->vis = nullptr;
+        h->vis.reset();
         h->cap_vis = 0;
     }
     h->n_deleted += n_del;
@@ -390,7 +382,7 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     // doc ids never change: an implicit-id index stores its ids before any row moves
     if (!h->ids) {
         const int64_t cap = std::max(h->cap32, n0);
-        HIP_TRY(h, hipMalloc(&h->ids, (size_t)cap * sizeof(int64_t)));
+        if ((rc = h->ids.alloc(h, (size_t)cap))) return rc;
         h->cap_ids = cap;
         hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, h->ids, h->id_base, n0);
         HIP_TRY(h, hipGetLastError());
@@ -399,20 +391,19 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     const size_t map_bytes = stage_size(tiles, 4) + stage_size(tiles, 8) + stage_size(n0, 8) + stage_size(n0, 4);
     ARG_CHECK(h, map_bytes + ((size_t)64 << 20) <= LIVE_STAGING_BYTES, "compact: the row map of this index exceeds the 1 GiB staging bound");
     const size_t data_bytes = std::min<size_t>((size_t)512 << 20, LIVE_STAGING_BYTES - map_bytes);
-    void* ws = nullptr;
-    if (hipMalloc(&ws, map_bytes + data_bytes) != hipSuccess) {
+    dev_buf<char> ws;
+    if (ws.alloc(h, map_bytes + data_bytes)) {
         (void)hipGetLastError();
         h->err = "compact: out of device memory for the staging buffer";
         return RAG_ERR_NOMEM;
     }
-    char* p = (char*)ws;
+    char* p = ws;
     int* tile_cnt = stage_take<int>(p, tiles);
     int64_t* tile_off = stage_take<int64_t>(p, tiles);
     int64_t* row_map = stage_take<int64_t>(p, n0);
     int32_t* src_rows = stage_take<int32_t>(p, n0);
     char* data = p;
     auto fail = [&](hipError_t e, const char* what) {
-        hipFree(ws);
         h->err = std::string("compact: ") + what + ": " + hipGetErrorString(e);
         return RAG_ERR_HIP;
     };
@@ -470,11 +461,10 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(e, "finish");
-    hipFree(ws);
+    ws.reset();
     h->n_rows = n_live;
     if (tok) h->tok_rows = n_live;
-    hipFree(h->vis);
-    h->vis = nullptr;
+    h->vis.reset();
     h->cap_vis = 0;
     h->n_deleted = 0;
     h->bm25_stale = true;

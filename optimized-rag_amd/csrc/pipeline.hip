@@ -42,14 +42,7 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
         HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
     const size_t need = (size_t)Q * pool;
-    if (need > h->side_scores_n) {
-        hipFree(h->side_scores);
-        h->side_scores = nullptr;
-        h->side_scores_n = 0;
-        const size_t want = std::max(need, (size_t)RAG_FORK_MAX_Q * RAG_MAX_K);
-        HIP_TRY(h, hipMalloc(&h->side_scores, want * sizeof(double)));
-        h->side_scores_n = want;
-    }
+    if (int rc = h->side_scores.reserve(h, std::max(need, (size_t)RAG_FORK_MAX_Q * RAG_MAX_K))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_fork, st));                    // inputs are ready wherever the caller's stream is now
     HIP_TRY(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     int rc = bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, h->side_scores, nullptr, h->side_stream);
@@ -62,12 +55,6 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
 
 int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
              bool host_ptrs);
-
-void pipeline_free(rag_ctx* h) {
-    hipFree(h->tok); hipFree(h->tok_len); hipFree(h->pipe_ws); hipFree(h->tok_bad);
-    h->tok = nullptr; h->tok_len = nullptr; h->pipe_ws = nullptr; h->tok_bad = nullptr;
-    h->tok_rows = 0; h->tok_cap = 0; h->tok_L = 0; h->pipe_ws_bytes = 0;
-}
 
 // int32 token ids -> the 16-bit resident store (WordPiece vocabularies have < 65536 entries: 30522 for the MiniLM
 // checkpoints); ids outside [0, 65535] are flagged
@@ -84,15 +71,16 @@ __global__ void tokens_narrow_kernel(const int32_t* __restrict__ in, uint16_t* _
 // device while streaming in (64 Mi tokens per piece through the staging arena).
 int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L) {
     ARG_CHECK(h, tokens && lens && n_rows > 0 && L > 0 && L <= 512, "tokens_load: bad arguments (passage length <= 512)");
-    hipFree(h->tok); hipFree(h->tok_len);
-    h->tok = nullptr; h->tok_len = nullptr; h->tok_rows = 0; h->tok_cap = 0;
+    h->tok.reset();
+    h->tok_len.reset();
+    h->tok_rows = 0; h->tok_cap = 0;
     const int64_t total = n_rows * (int64_t)L, piece = (int64_t)64 << 20;
-    HIP_TRY(h, hipMalloc(&h->tok, (size_t)total * sizeof(uint16_t)));
-    HIP_TRY(h, hipMalloc(&h->tok_len, (size_t)n_rows * sizeof(int32_t)));
-    int rc = stage_reserve(h, stage_size((size_t)std::min(total, piece), 4) + 256);
-    if (rc) return rc;
-    int32_t* buf = reinterpret_cast<int32_t*>(h->stage);
-    int* bad = reinterpret_cast<int*>(reinterpret_cast<char*>(h->stage) + stage_size((size_t)std::min(total, piece), 4));
+    int rc;
+    if ((rc = h->tok.alloc(h, (size_t)total))) return rc;
+    if ((rc = h->tok_len.alloc(h, (size_t)n_rows))) return rc;
+    if ((rc = stage_reserve(h, stage_size((size_t)std::min(total, piece), 4) + 256))) return rc;
+    int32_t* buf = reinterpret_cast<int32_t*>(h->stage.get());
+    int* bad = reinterpret_cast<int*>(h->stage + stage_size((size_t)std::min(total, piece), 4));
     HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(int), h->stream));
     for (int64_t o = 0; o < total; o += piece) {
         const int64_t nn = std::min(piece, total - o);
@@ -114,11 +102,13 @@ int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int
 // array): reserve once, append row blocks in order. tok_rows counts the rows appended so far; tok_cap the reservation.
 int tokens_reserve(rag_ctx* h, int64_t n_rows, int L) {
     ARG_CHECK(h, n_rows > 0 && L > 0 && L <= 512, "tokens_reserve: bad arguments (passage length <= 512)");
-    hipFree(h->tok); hipFree(h->tok_len);
-    h->tok = nullptr; h->tok_len = nullptr; h->tok_rows = 0; h->tok_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->tok, (size_t)n_rows * L * sizeof(uint16_t)));
-    HIP_TRY(h, hipMalloc(&h->tok_len, (size_t)n_rows * sizeof(int32_t)));
-    if (!h->tok_bad) HIP_TRY(h, hipMalloc(&h->tok_bad, sizeof(int)));
+    h->tok.reset();
+    h->tok_len.reset();
+    h->tok_rows = 0; h->tok_cap = 0;
+    int rc;
+    if ((rc = h->tok.alloc(h, (size_t)n_rows * L))) return rc;
+    if ((rc = h->tok_len.alloc(h, (size_t)n_rows))) return rc;
+    if ((rc = h->tok_bad.reserve(h, 1))) return rc;
     HIP_TRY(h, hipMemset(h->tok_bad, 0, sizeof(int)));
     h->tok_cap = n_rows;
     h->tok_L = L;
@@ -267,14 +257,8 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][pool] i64 | rrf [Q][pool] f64 | ranks [Q][pool][2] i32
     //            | pair ids [P][L] | pair tt [P][L] | lens [P] | logits [P]
     const size_t need = P * (16 + 8 + 8 + 8 + 8) + P * L_pair * 8 + P * 8 + 256;
-    if (need > h->pipe_ws_bytes) {
-        hipFree(h->pipe_ws);
-        h->pipe_ws = nullptr;
-        h->pipe_ws_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->pipe_ws, need));
-        h->pipe_ws_bytes = need;
-    }
-    char* w = (char*)h->pipe_ws;
+    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
+    char* w = h->pipe_ws;
     int64_t* lists = (int64_t*)w;              w += P * 16;
     double* sc = (double*)w;                   w += P * 8;
     int64_t* cand = (int64_t*)w;               w += P * 8;
@@ -287,9 +271,8 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     // The candidate stage runs in ROW space (the token store is row-aligned and RRF only needs a consistent key space):
     // the id mapping is switched off for these launches (pointers are kernel arguments, captured at launch) and applied to
     // the outputs at the end, so explicit doc ids (e.g. primary keys of a loaded shard) work as well as id_base + row.
-    int64_t* const ids_saved = h->ids;
+    dev_buf<int64_t> ids_saved = std::move(h->ids);
     const int64_t id_base_saved = h->id_base;
-    h->ids = nullptr;
     h->id_base = 0;
     int rc;
     if (mode == 0) {
@@ -298,7 +281,7 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
         rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st);
         if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, pool, cand, rrf, ranks, st);
     }
-    h->ids = ids_saved;
+    h->ids = std::move(ids_saved);
     h->id_base = id_base_saved;
     if (rc) return rc;
     hipLaunchKernelGGL(ce_build_pairs_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, q_tok_dev, q_len_dev, Lq, cand, (int64_t)0,
@@ -309,11 +292,11 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     hipLaunchKernelGGL(rerank_topk_kernel, dim3(Q), dim3(256), 0, st, logit, cand, pool, k, ids_out, scores_out, logits_out);
     HIP_TRY(h, hipGetLastError());
     if (cand_out) HIP_TRY(h, hipMemcpyAsync(cand_out, cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    if (ids_saved != nullptr || id_base_saved != 0) {
+    if (h->ids != nullptr || id_base_saved != 0) {
         hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)(((size_t)Q * k + 255) / 256)), dim3(256), 0, st, ids_out, (int64_t)Q * k,
-                           ids_saved, id_base_saved);
+                           h->ids, id_base_saved);
         if (cand_out)
-            hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, ids_saved,
+            hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, h->ids,
                                id_base_saved);
         HIP_TRY(h, hipGetLastError());
     }
