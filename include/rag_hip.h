@@ -18,6 +18,20 @@
  *     *_host calls may be issued from several threads at once (the reference graph is single-threaded,
  *     agent/rag_graph.py:506, but its DB pool allows 10 concurrent searches, database/connection.py:38-42); they
  *     run one after another. *_dev calls share the handle's device workspaces: issue them on ONE stream.
+ *   - Ordering (pinned by tests/test_stream_order_gpu.py). A *_dev call returns once its work is queued on `stream`; all it
+ *     reads and writes is ordered on that stream as if it had run there alone: inputs produced earlier on the stream are
+ *     seen, outputs may be consumed by later work on it, no other stream and no device-wide wait is needed. The calls that
+ *     do wait for `stream` say so below (rag_tokens_append_dev; any call that has to grow a workspace it used before frees
+ *     the old one first, which waits for the device - the first call of a larger shape, not the steady state).
+ *     A *_host call may be made while *_dev work of the handle is pending, from any thread, and behaves as if it ran after
+ *     that work: it first waits for the device when a *_dev call was made on the handle since the last such wait (a
+ *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
+ *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
+ *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_bm25_load_host,
+ *     rag_index_load_host, rag_index_reserve, rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
+ *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize and rag_set_option do not
+ *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
+ *     *_dev calls of one handle on SEVERAL streams stay unordered among themselves: that is the caller's to order.
  *   - doc ids are int64 (SQL BIGSERIAL ids, database/migrations/001_initial_schema.sql); scores are
  *     float64 because the reference computes every score as a Python float.
  */

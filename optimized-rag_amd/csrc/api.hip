@@ -79,6 +79,17 @@ static void options_from_env(rag_options* o) {
     }
 }
 #define LOCK(h) std::lock_guard<std::mutex> lock_((h)->mu)
+// first statement after the lock and the argument checks of an entry that touches the device (common.h host_after_dev)
+#define DEV_ENTRY(h)                                                                           \
+    do {                                                                                      \
+        HIP_TRY(h, hipSetDevice((h)->device));                                                \
+        (h)->dev_pending = true;                                                              \
+    } while (0)
+#define HOST_ENTRY(h)                                                                          \
+    do {                                                                                      \
+        HIP_TRY(h, hipSetDevice((h)->device));                                                \
+        if (int rc_ = host_after_dev(h)) return rc_;                                          \
+    } while (0)
 
 template <class T>
 static int pairwise_cosine_host_t(rag_handle_t h, const T* a, int m, const T* b, int n, int dim, double* out) {
@@ -87,7 +98,7 @@ static int pairwise_cosine_host_t(rag_handle_t h, const T* a, int m, const T* b,
     ARG_CHECK(h, m >= 0 && n >= 0 && dim > 0, "bad sizes");
     if (m == 0 || n == 0) return RAG_OK;
     ARG_CHECK(h, a && b && out, "null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     const bool same = (a == b && m == n);
     hipStream_t st = h->stream;
     int rc = stage_reserve(h, stage_size((size_t)m * dim, sizeof(T)) + stage_size(same ? 0 : (size_t)n * dim, sizeof(T)) + stage_size((size_t)m * n, 8));
@@ -196,7 +207,8 @@ static int index_load_common(rag_ctx* h, const float* emb, const int64_t* ids, i
                              hipStream_t st, bool host) {
     ARG_CHECK(h, n_rows >= 0 && n_rows < (int64_t)0x7fffff00, "n_rows must fit int32 per GPU");
     ARG_CHECK(h, n_rows == 0 || emb != nullptr, "emb is null");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (host) HOST_ENTRY(h);
+    else DEV_ENTRY(h);
     dense_free(h);
     h->n_rows = n_rows;
     h->id_base = id_base;
@@ -236,7 +248,7 @@ int rag_index_reserve(rag_handle_t h, int64_t n_rows_total, int64_t id_base) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, n_rows_total > 0 && n_rows_total < (int64_t)0x7fffff00, "n_rows must fit int32 per GPU");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     dense_free(h);
     h->id_base = id_base;
     h->n_reserved = n_rows_total;
@@ -258,7 +270,8 @@ static int index_append(rag_ctx* h, const float* emb, int64_t n, hipStream_t st,
     ARG_CHECK(h, h->n_reserved > 0, "rag_index_reserve first");
     ARG_CHECK(h, n >= 0 && h->n_rows + n <= h->n_reserved, "append exceeds the reserved row count");
     ARG_CHECK(h, n == 0 || emb != nullptr, "emb is null");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (host) HOST_ENTRY(h);
+    else DEV_ENTRY(h);
     if (n == 0) return RAG_OK;
     HIP_TRY(h, hipMemcpyAsync(h->emb32 + (size_t)h->n_rows * h->dim, emb, (size_t)n * h->dim * sizeof(float),
                               host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
@@ -286,8 +299,7 @@ int rag_index_set_tenants_host(rag_handle_t h, const int32_t* t, int64_t n_rows)
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, t == nullptr || n_rows == h->n_rows, "tenant array length must equal the index row count");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->vis) HIP_TRY(h, hipDeviceSynchronize());       // vis is rebuilt below: no queued search may still read it
+    HOST_ENTRY(h);
     h->tenants.reset();
     h->cap_ten = 0;
     int rc;
@@ -306,7 +318,7 @@ int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, n_rows == h->n_rows, "id array length must equal the index row count");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     h->ids.reset();
     h->cap_ids = 0;
     if (ids == nullptr || n_rows == 0) return RAG_OK;
@@ -327,7 +339,7 @@ int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows, int n, float*
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, n >= 0 && (n == 0 || (rows && out)), "null rows/out");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     for (int i = 0; i < n; ++i) {
         ARG_CHECK(h, rows[i] >= 0 && rows[i] < h->n_rows, "row out of range");
         HIP_TRY(h, hipMemcpyAsync(out + (size_t)i * h->dim, h->emb32 + (size_t)rows[i] * h->dim, h->dim * sizeof(float),
@@ -344,7 +356,7 @@ int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int Q, int k, int ten
     LOCK(h);
     ARG_CHECK(h, q_dev && ids_dev && scores_dev, "null pointer");
     ARG_CHECK(h, Q > 0 && Q <= 65535, "1 <= n_queries <= 65535");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return dense_search(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream);
 }
 
@@ -355,7 +367,7 @@ int rag_dense_topk_host(rag_handle_t h, const float* q_host, int Q, int k, int t
     ARG_CHECK(h, q_host && ids_out && scores_out, "null pointer");
     ARG_CHECK(h, Q > 0 && Q <= 65535, "1 <= n_queries <= 65535");
     ARG_CHECK(h, k > 0 && k <= RAG_MAX_K, "0 < k <= 256");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     hipStream_t st = h->stream;
     const size_t n_out = (size_t)Q * k;
     int rc = stage_reserve(h, stage_size((size_t)Q * h->dim, 4) + 2 * stage_size(n_out, 8) + stage_size(n_out, 4));
@@ -423,7 +435,7 @@ int rag_merge_topk_dev(rag_handle_t h, const int64_t* ids_dev, const double* sco
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, ids_dev && scores_dev && ids_out_dev && scores_out_dev, "null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return merge_topk(h, ids_dev, scores_dev, n_lists, list_stride, Q, k, ids_out_dev, scores_out_dev,
                       (hipStream_t)stream);
 }
@@ -436,7 +448,7 @@ int rag_hybrid_fuse_gathered_dev(rag_handle_t h, const int64_t* gathered_dev, in
     LOCK(h);
     ARG_CHECK(h, gathered_dev && lists_out_dev && scores_out_dev && keys_out_dev && rrf_out_dev, "hybrid_fuse_gathered: null pointer");
     ARG_CHECK(h, world > 0 && Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid_fuse_gathered: bad sizes (0 < pool <= 256)");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = (int64_t)Q * pool, stride = 4 * P;
     const double* gs = reinterpret_cast<const double*>(gathered_dev);
@@ -458,7 +470,7 @@ int rag_rrf_fuse_host(rag_handle_t h, const int64_t* lists, int Q, int L, int le
                       double* scores_out, int32_t* ranks_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return rrf_fuse_host(h, lists, Q, L, len, rrf_k, top_k, keys_out, scores_out, ranks_out);
 }
 
@@ -466,7 +478,7 @@ int rag_linear_fuse_topk_host(rag_handle_t h, const double* sem, const double* k
                               double b, double g, int top_k, int32_t* idx_out, double* hyb_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return linear_fuse_topk_host(h, sem, kw, tmp, n, a, b, g, top_k, idx_out, hyb_out);
 }
 
@@ -474,7 +486,7 @@ int rag_bm25_load_host(rag_handle_t h, const int64_t* indptr, const int32_t* doc
                        const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return bm25_load_host(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b);
 }
 
@@ -491,7 +503,7 @@ int rag_bm25_topk_host(rag_handle_t h, const int32_t* term_ptr, const int32_t* t
                        int32_t* rows_out, double* scores_out, double* raw_max_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return bm25_topk_host(h, term_ptr, terms, Q, k, tenant, ids_out, rows_out, scores_out, raw_max_out);
 }
 
@@ -499,7 +511,7 @@ int rag_bm25_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t
                       int32_t* rows_dev, double* scores_dev, double* raw_max_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev,
                          (hipStream_t)stream);
 }
@@ -508,7 +520,7 @@ int rag_rrf_fuse_dev(rag_handle_t h, const int64_t* lists_dev, int Q, int L, int
                      double* scores_dev, int32_t* ranks_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return rrf_fuse_dev(h, lists_dev, Q, L, len, len, (int64_t)L * len, rrf_k, top_k, keys_dev, scores_dev, ranks_dev,
                         (hipStream_t)stream);
 }
@@ -525,7 +537,7 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid: 0 < pool <= 256");
     if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows, "hybrid: the BM25 postings must be row-aligned with the index (same number of documents)");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
     int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st);
     if (rc) return rc;
@@ -538,7 +550,7 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, temporal == nullptr || n_rows == h->n_rows, "temporal array length must equal the index row count");
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     h->temporal.reset();
     h->cap_tmp = 0;
     h->temporal_absmax = 0.0;
@@ -569,7 +581,7 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_linear: tenant filter requested but no tenants loaded");
     if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows && h->n_rows > 0, "hybrid_linear: needs BM25 postings row-aligned with a non-empty index");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = h->n_rows, ld = h->n_rows_pad;
     // queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
@@ -619,13 +631,14 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
 int rag_bm25_set_normalize(rag_handle_t h, int on) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
+    // no wait: the switch is host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value
     return bm25_set_normalize(h, on);
 }
 
 int rag_bm25_scores_host(rag_handle_t h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return bm25_scores_host(h, term_ptr, terms, Q, out);
 }
 
@@ -634,21 +647,21 @@ int rag_bm25_scores_adhoc_host(rag_handle_t h, const int64_t* indptr, const int3
                                const int32_t* term_ptr, const int32_t* terms, int Q, double* out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return bm25_scores_adhoc_host(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, term_ptr, terms, Q, out);
 }
 
 int rag_ce_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors, int n) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return ce_load_host(h, cfg, tensors, n);
 }
 
 int rag_ce_score_host(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return ce_score(h, ids, tt, lens, P, L, out, h->stream, true);
 }
 
@@ -656,28 +669,28 @@ int rag_ce_score_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, cons
                      void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return ce_score(h, ids, tt, lens, P, L, out, (hipStream_t)stream, false);
 }
 
 int rag_embed_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return embed_load_host(h, cfg, tensors, n, normalize);
 }
 
 int rag_embed_host(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int n_texts, int L, float* out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return embed_run(h, ids, tt, lens, n_texts, L, out, h->stream, true);
 }
 
 int rag_embed_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int n_texts, int L, float* out, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return embed_run(h, ids, tt, lens, n_texts, L, out, (hipStream_t)stream, false);
 }
 
@@ -693,7 +706,7 @@ int rag_mmr_select_host(rag_handle_t h, const float* query, const float* emb, in
                         int variant, int32_t* sel_out, double* score_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return mmr_select_host(h, query, emb, n, dim, top_k, lambda, variant, sel_out, score_out);
 }
 
@@ -703,7 +716,7 @@ int rag_mmr_select_dev(rag_handle_t h, const float* q_dev, const int32_t* rows_d
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, h->emb32 != nullptr && rows_dev, "mmr_select_dev: no index loaded / null rows");
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return mmr_select_dev(h, q_dev, h->emb32, rows_dev, Q, pool, h->dim, top_k, lambda, variant, sel_dev, score_dev,
                           (hipStream_t)stream);
 }
@@ -712,28 +725,28 @@ int rag_chunk_chain_host(rag_handle_t h, const float* emb, const int32_t* sent_l
                          int max_chunk, int min_chunk, int32_t* group_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return chunk_chain_host(h, emb, sent_len, n, dim, threshold, max_chunk, min_chunk, group_out);
 }
 
 int rag_tokens_load_host(rag_handle_t h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return tokens_load_host(h, tokens, lens, n_rows, L);
 }
 
 int rag_tokens_reserve(rag_handle_t h, int64_t n_rows_total, int L) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    HOST_ENTRY(h);
     return tokens_reserve(h, n_rows_total, L);
 }
 
 int rag_tokens_append_dev(rag_handle_t h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return tokens_append_dev(h, tokens_dev, lens_dev, n_rows, (hipStream_t)stream);
 }
 
@@ -743,7 +756,7 @@ int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_
                             double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return retrieve_rerank_dev(h, q_emb_dev, term_ptr_dev, terms_dev, q_tok_dev, q_len_dev, Lq, Q, pool, k, rrf_k, tenant, mode,
                                cls_id, sep_id, L_pair, ids_out_dev, scores_out_dev, logits_out_dev, cand_out_dev,
                                (hipStream_t)stream);
@@ -754,7 +767,7 @@ int rag_ce_build_pairs_dev(rag_handle_t h, const int32_t* q_tok_dev, const int32
                            int32_t* tt_out_dev, int32_t* lens_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return ce_build_pairs_dev(h, q_tok_dev, q_len_dev, Lq, cand_dev, Q, pool, token_id_base, L_pair, cls_id, sep_id, ids_out_dev,
                               tt_out_dev, lens_out_dev, (hipStream_t)stream);
 }
@@ -763,7 +776,7 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
                         double* scores_out_dev, float* logits_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    HIP_TRY(h, hipSetDevice(h->device));
+    DEV_ENTRY(h);
     return rerank_topk_dev(h, logits_dev, cand_dev, Q, pool, k, ids_out_dev, scores_out_dev, logits_out_dev, (hipStream_t)stream);
 }
 

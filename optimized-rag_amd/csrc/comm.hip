@@ -90,6 +90,7 @@ int rag_comm_allgather_dev(rag_handle_t h, const void* send_dev, void* recv_dev,
     ARG_CHECK(h, h->comm != nullptr, "comm_allgather: rag_comm_init has not run");
     ARG_CHECK(h, send_dev && recv_dev && bytes > 0, "comm_allgather: bad arguments");
     HIP_TRY(h, hipSetDevice(h->device));
+    h->dev_pending = true;                   // as every *_dev entry (common.h host_after_dev)
     const int rc = rccl().all_gather(send_dev, recv_dev, bytes, 0 /* ncclInt8 */, h->comm, (hipStream_t)stream);
     if (rc != 0) return rccl_fail(h, "ncclAllGather", rc);
     return RAG_OK;

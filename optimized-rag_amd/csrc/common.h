@@ -155,6 +155,9 @@ struct rag_ctx : rag_device_mem {
     int64_t cap32 = 0, cap_ids = 0, cap_ten = 0, cap_tmp = 0, cap_vis = 0;
     bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
 
+    // set by every *_dev entry, cleared by the device-wide wait a *_host entry then starts with (host_after_dev): a *_host
+    // call behaves as if it ran after all *_dev work of the handle, on whatever stream that was queued
+    bool dev_pending = false;
     int ws_q = 0;                    // queries the dense search workspace is sized for
     int q16_dirty = 0;               // rows [q16_dirty, ws_qpad) of q16 are known to be zero (pad rows of a query tile must be)
     // one lock per handle, taken by every entry point: the reference's DocumentStore.search may be called from up to 10
@@ -243,6 +246,18 @@ static inline int prof_end(rag_ctx* h, int stage, hipStream_t st) {
     auto& p = h->prof[stage];
     HIP_TRY(h, hipEventRecord(p.ev[p.used].second, st));
     p.used++;
+    return RAG_OK;
+}
+
+// ---- ordering of *_host calls behind *_dev calls. A *_dev call leaves its work queued on the caller's stream; the *_host
+// entries run on the handle's private non-blocking stream over the SAME workspaces (dense search state, the models' activation
+// planes) and replace planes a queued call reads, and their host-side bookkeeping (ws_q, q16_dirty, ws_pairs) assumes that
+// enqueue order is device order. So a *_host entry first waits for the device when *_dev work was queued since the last wait.
+// Nothing is added to either path while a caller stays with one kind of call: no HIP call, one flag.
+static inline int host_after_dev(rag_ctx* h) {
+    if (!h->dev_pending) return RAG_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->dev_pending = false;
     return RAG_OK;
 }
 

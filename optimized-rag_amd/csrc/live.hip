@@ -138,8 +138,7 @@ int live_vis_rebuild(rag_ctx* h) {
 // write returns the result from before it
 static int live_begin(rag_ctx* h) {
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return RAG_OK;
+    return host_after_dev(h);
 }
 
 // row-count-sized workspaces follow the row count: the linear-fusion workspace (its pad rows must read as zero) is

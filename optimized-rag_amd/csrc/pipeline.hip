@@ -109,7 +109,10 @@ int tokens_reserve(rag_ctx* h, int64_t n_rows, int L) {
     if ((rc = h->tok.alloc(h, (size_t)n_rows * L))) return rc;
     if ((rc = h->tok_len.alloc(h, (size_t)n_rows))) return rc;
     if ((rc = h->tok_bad.reserve(h, 1))) return rc;
-    HIP_TRY(h, hipMemset(h->tok_bad, 0, sizeof(int)));
+    // cleared on the handle's stream and waited for: a null-stream hipMemset is not ordered against the non-blocking stream the
+    // first rag_tokens_append_dev counts into it on
+    HIP_TRY(h, hipMemsetAsync(h->tok_bad, 0, sizeof(int), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->tok_cap = n_rows;
     h->tok_L = L;
     return RAG_OK;
