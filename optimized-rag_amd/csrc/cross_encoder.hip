@@ -41,6 +41,7 @@
 // forward has an instance of its own, so switching between them (option ce_mx) never resizes the other forward's buffers.
 struct ce_chunk_bufs {
     dev_buf<int32_t> ids, tt, lens;                                    // [Mp] token / type ids padded to L, [pairs] lengths
+    dev_buf<int32_t> clen;                                             // [pairs] lengths clamped to [1, L_in]: what every kernel after the scan reads
     // packed (variable-length) row layout of the current chunk: pair p owns rows [pair_off[p], pair_off[p+1]) where
     // pair_off[p+1] - pair_off[p] = len rounded up to 16; row_pair[m] = owning pair (-1 past the end); m_packed[0] = rows
     dev_buf<int32_t> pair_off, row_pair, m_packed;
@@ -428,15 +429,17 @@ __device__ __forceinline__ void wave_layernorm(float (&v)[PER], const float* __r
     }
 }
 
-// ---- packing: pair p owns len_p rounded up to 16 rows; offsets by one block-wide scan, then the row -> pair map
-__global__ __launch_bounds__(1024) void ce_pack_scan_kernel(const int32_t* __restrict__ lens, int P, int L, int32_t* __restrict__ pair_off,
-                                                             int32_t* __restrict__ m_packed) {
+// ---- packing: pair p owns len_p rounded up to 16 rows; offsets by one block-wide scan, then the row -> pair map.
+// The ONE place that reads the caller's lens: a length is clamped to [1, L_in] (L_in = the caller's padded length, not the attention
+// length class it was rounded up to: tokens past L_in do not exist) and written to clen, which attention and the pooling heads read.
+__global__ __launch_bounds__(1024) void ce_pack_scan_kernel(const int32_t* __restrict__ lens, int P, int L_in, int32_t* __restrict__ clen,
+                                                             int32_t* __restrict__ pair_off, int32_t* __restrict__ m_packed) {
     __shared__ int part[1024];
     const int tid = threadIdx.x;
     const int per = (P + 1023) / 1024;
     const int b = tid * per, e = min(P, b + per);
     int s = 0;
-    for (int p = b; p < e; ++p) s += (max(1, min(lens[p], L)) + 15) & ~15;
+    for (int p = b; p < e; ++p) s += (max(1, min(lens[p], L_in)) + 15) & ~15;
     part[tid] = s;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {
@@ -447,8 +450,10 @@ __global__ __launch_bounds__(1024) void ce_pack_scan_kernel(const int32_t* __res
     }
     int off = part[tid] - s;
     for (int p = b; p < e; ++p) {
+        const int len = max(1, min(lens[p], L_in));
+        clen[p] = len;
         pair_off[p] = off;
-        off += (max(1, min(lens[p], L)) + 15) & ~15;
+        off += (len + 15) & ~15;
     }
     if (tid == 1023) { pair_off[P] = part[1023]; m_packed[0] = part[1023]; }
 }
@@ -839,6 +844,7 @@ static int chunk_bufs_alloc(rag_ctx* h, ce_chunk_bufs& c, int P, int L, int64_t 
     if ((rc = c.ids.alloc(h, (size_t)Mp))) return rc;
     if ((rc = c.tt.alloc(h, (size_t)Mp))) return rc;
     if ((rc = c.lens.alloc(h, (size_t)P))) return rc;
+    if ((rc = c.clen.alloc(h, (size_t)P))) return rc;
     if ((rc = c.pair_off.alloc(h, (size_t)P + 1))) return rc;
     if ((rc = c.row_pair.alloc(h, (size_t)Mp))) return rc;
     if ((rc = c.m_packed.alloc(h, 1))) return rc;
@@ -992,9 +998,9 @@ static void launch_ln(rag_ce_model* m, const float* y, const float* g, const flo
                        (float)m->cfg.ln_eps, m->x16);
 }
 
-// lens_dev / logits_dev: this chunk's lengths and logit slots (the model's staging buffers for host-pointer calls, the caller's
-// own device arrays otherwise)
-static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st, const int32_t* lens_dev, float* logits_dev) {
+// lens_in / logits_dev: this chunk's lengths as the caller gave them and its logit slots (the model's staging buffers for
+// host-pointer calls, the caller's own device arrays otherwise); the kernels read the clamped copy the scan writes (io.clen)
+static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, int L_in, hipStream_t st, const int32_t* lens_in, float* logits_dev) {
     const int H = m->cfg.hidden, F = m->cfg.ffn;
     const int64_t M = (int64_t)P * L;
     const int64_t Mp = round_up((int64_t)m->ws_pairs * L, CE_BN);      // plane strides follow the ALLOCATED size
@@ -1021,7 +1027,8 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
                                     m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H,            \
                                     m->cfg.vocab_size, eps, m->x16)
     // packed row layout of this chunk (no host round trip: grids cover the padded worst case, kernels stop at m_packed)
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, io.pair_off, io.m_packed);
+    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_in, P, L_in, io.clen, io.pair_off, io.m_packed);
+    const int32_t* lens_dev = io.clen;
     hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, io.pair_off, P, L, Mp, io.row_pair);
     CE_PER_DISPATCH(EMB)
     const dim3 blk(512);
@@ -1151,7 +1158,7 @@ static int mx_launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, size_t
     return RAG_OK;
 }
 
-static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st, const int32_t* lens_dev, float* logits_dev) {
+static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, int L_in, hipStream_t st, const int32_t* lens_in, float* logits_dev) {
     auto& w = m->mx;
     const int H = m->cfg.hidden, F = m->cfg.ffn;
     const int64_t M = (int64_t)P * L, Mp = w.tokens;
@@ -1163,7 +1170,8 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_ln>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
         h->attr_ce_mx = true;
     }
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_dev, P, L, w.io.pair_off, w.io.m_packed);
+    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_in, P, L_in, w.io.clen, w.io.pair_off, w.io.m_packed);
+    const int32_t* lens_dev = w.io.clen;
     hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, (const int32_t*)w.io.pair_off, P, L, Mp, w.io.row_pair);
     hipLaunchKernelGGL(mx_embed_ln_kernel, dim3((unsigned)((M + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, (const int32_t*)w.io.ids, (const int32_t*)w.io.tt,
                        (const float*)m->word, (const float*)m->pos, (const float*)m->type, (const float*)m->emb_ln_g, (const float*)m->emb_ln_b,
@@ -1284,7 +1292,7 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
         }
         const int64_t n = (int64_t)pc * L;
         hipLaunchKernelGGL(ce_pad_tokens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_ids, src_tt, pc, L_in, L, io.ids, io.tt);
-        rc = use_mx ? mx_forward_chunk(h, m, pc, L, st, lens_dev, logits_dev) : ce_forward_chunk(h, m, pc, L, st, lens_dev, logits_dev);
+        rc = use_mx ? mx_forward_chunk(h, m, pc, L, L_in, st, lens_dev, logits_dev) : ce_forward_chunk(h, m, pc, L, L_in, st, lens_dev, logits_dev);
         if (rc) break;
         if (host_ptrs) HIP_TRY(h, hipMemcpyAsync(out + (size_t)p0 * ow, io.logits, (size_t)pc * ow * 4, kout, st));
     }

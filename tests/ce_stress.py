@@ -113,3 +113,28 @@ def centre_logits(w, cfg):
     out["classifier.bias"] = np.array([-z.mean()], dtype=np.float32)
     assert abs(B.forward_logits(out, cfg, ids, tt, lens, fast_erf=True).mean()) < 1e-3
     return out
+
+
+# ---- the stress levels of the MiniLM shape and their batch, shared by tests/test_cross_encoder_stress_gpu.py (classifier),
+# tests/test_embeddings_stress_gpu.py (embedding head) and tests/test_ce_stress_targets.py (CPU preconditions)
+CFG = B.minilm_config()
+LEVELS = {
+    "seeded": lambda w: w,
+    "moderate": lambda w: outliers(sharp(w, CFG, 1.5), CFG, 8),
+    "sharp": lambda w: sharp(w, CFG, 2),
+    "outlier": lambda w: outliers(w, CFG, 12, 3),
+    "combined": lambda w: ffn_tails(outliers(sharp(w, CFG, 1.5), CFG, 8), CFG, 3),
+}
+L = 128
+LENS = np.array([128, 1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 80, 95, 96, 97, 111, 112, 113, 127, 128], dtype=np.int32)
+
+
+def batch(lens=LENS, L=L, seed=2468, pair_types=True):
+    """Token ids above the special / unused ids, pad id 0 past each length; type 1 from position 18 (a pair) or type 0 throughout
+    (a single text, what an embedding model sees)."""
+    rng = np.random.default_rng(seed)
+    lens = np.asarray(lens, dtype=np.int32)
+    ids = rng.integers(1000, CFG["vocab_size"], (len(lens), L)).astype(np.int32)
+    ids[np.arange(L)[None, :] >= lens[:, None]] = 0
+    tt = ((np.arange(L)[None, :] >= 18) & (np.arange(L)[None, :] < lens[:, None])).astype(np.int32)
+    return ids, tt if pair_types else np.zeros_like(tt)

@@ -1,6 +1,9 @@
 """CPU: the stress transforms of tests/ce_stress.py reach their targets on the MiniLM shape (seed 99, the model of
-tests/test_cross_encoder_stress_gpu.py), so that an edit of a transform cannot quietly make the GPU stress levels mild."""
+tests/test_cross_encoder_stress_gpu.py), so that an edit of a transform cannot quietly make the GPU stress levels mild; and the
+preconditions of tests/test_embeddings_stress_gpu.py: the oracle's pooled vectors are long enough for the unit-vector bars to mean
+something, and the split-fp16 operand scheme stays far inside them on the CPU simulator."""
 import numpy as np
+import pytest
 
 import ce_stress as S
 from oracle import bert_oracle as B
@@ -47,3 +50,37 @@ def test_centre_logits_puts_the_oracle_logits_around_0():
     ids, tt, lens = S.probe_batch(CFG, pairs=8)
     z = B.forward_logits(w, CFG, ids, tt, lens, fast_erf=True)
     assert abs(float(np.median(z))) < 3.0 and w["classifier.bias"][0] != W["classifier.bias"][0]
+
+
+# ---- preconditions of the embedding-head stress test (tests/test_embeddings_stress_gpu.py): its batch, token types 0 ------------
+_POOLED = {}
+
+
+def _pooled(name):
+    """(stress weights, the oracle's un-normalised pooled vectors of the 24 texts)"""
+    if name not in _POOLED:
+        w = S.LEVELS[name](W)
+        ids, tt = S.batch(pair_types=False)
+        _POOLED[name] = (w, B.sentence_embeddings(w, CFG, ids.astype(np.int64), tt.astype(np.int64), S.LENS, normalize=False, fast_erf=True))
+    return _POOLED[name]
+
+
+@pytest.mark.parametrize("name", list(S.LEVELS))
+def test_pooled_vectors_are_long_enough_to_normalise(name):
+    """||pooled|| >= 10 at every level (15 to 116 seen): dividing by it is well conditioned, so an error of the unit vector is an
+    error of the encoder and not of a near-zero mean."""
+    _, raw = _pooled(name)
+    assert np.isfinite(raw).all()
+    assert np.linalg.norm(raw, axis=1).min() >= 10.0
+
+
+@pytest.mark.parametrize("name", list(S.LEVELS))
+def test_split_fp16_operands_stay_far_inside_the_embedding_bar_on_the_simulator(name):
+    """tools/ce_numerics_sim.py, scheme split16 (what the split-fp16 kernels store): under 1e-5 per component of the unit vector at
+    every level, a hundredth of the 1e-3 bar. A GPU miss of the MX forward at a level is then MX operand precision, not the test."""
+    from tools import ce_numerics_sim as sim
+    w, raw = _pooled(name)
+    ids, tt = S.batch(pair_types=False)
+    got = sim.sentence_embeddings(w, CFG, ids.astype(np.int64), tt.astype(np.int64), S.LENS, sim.Scheme("split16"))
+    exp = raw / np.linalg.norm(raw, axis=1, keepdims=True)
+    assert np.abs(got - exp).max() < 1e-5

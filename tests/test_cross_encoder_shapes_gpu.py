@@ -167,6 +167,72 @@ def test_stale_nan_rows_of_a_larger_call_do_not_reach_a_later_call(eng, mode):
     np.testing.assert_array_equal(got, ref)
 
 
+@pytest.mark.parametrize("mode", [0, 1, -1], ids=["default", "mx", "split16"])
+def test_a_nan_text_does_not_reach_the_text_before_it(eng, mode):
+    """The embedding twin of test_a_nan_pair_does_not_reach_the_pair_before_it. The mean pool reads every token row of its text, so it
+    is the head that would show a neighbour's rows: texts A with an odd count of 16-row tiles, each followed by a poisoned text B,
+    the last A at the packed end of a workspace that a fully poisoned 40-text call has just filled with NaN. Every A vector is
+    finite, bit-identical to A embedded alone, and within the bar of the oracle; every component of the B vectors is NaN."""
+    cfg = _NAN_CFG
+    w = _nan_model()
+    eng.embed_load(cfg, _tensors(w, cfg, head=False), normalize=True)
+    rng = np.random.default_rng(4242)
+    L = 64
+    big_lens = np.full(40, 64, dtype=np.int32)
+    big_ids, big_tt = _pairs(rng, cfg, big_lens, L)
+    big_ids[:, 5] = POISON
+    a_lens = [1, 7, 16, 33, 41, 48]
+    lens = np.array([x for a in a_lens for x in (a, 40)] + [33], dtype=np.int32)
+    ids, tt = _pairs(rng, cfg, lens, L)
+    tt[:] = 0
+    ids[1::2, 3] = POISON
+    big = _with_mode(eng, mode, lambda: eng.embed(big_ids, big_tt, big_lens))
+    assert np.isnan(big).all()
+    got = _with_mode(eng, mode, lambda: eng.embed(ids, tt, lens))
+    a = np.arange(0, len(lens), 2)
+    assert np.isnan(got[1::2]).all()
+    assert np.isfinite(got[a]).all(), got[a]
+    for i in a:
+        alone = _with_mode(eng, mode, lambda: eng.embed(ids[i:i + 1], tt[i:i + 1], lens[i:i + 1]))
+        np.testing.assert_array_equal(alone, got[i:i + 1])
+    exp = B.sentence_embeddings(w, cfg, ids[a].astype(np.int64), tt[a].astype(np.int64), lens[a], fast_erf=True)
+    assert np.abs(got[a] - exp).max() < EMB_TOL
+    assert ((got[a] * exp).sum(1) > 1 - 1e-6).all()
+
+
+# ---- lengths outside [1, seq_len] ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("l_in", [20, 32, 100])
+@pytest.mark.parametrize("mode", [1, -1], ids=["mx", "split16"])
+def test_out_of_range_lens_are_clamped_to_the_padded_length(eng, mode, l_in):
+    """include/rag_hip.h: a length is clamped to [1, seq_len], seq_len being the caller's padded length and not the attention
+    length class it is rounded up to (20 -> 32, 100 -> 128: tokens past seq_len do not exist, and a length of seq_len + 5 must not
+    make the forward attend to, or pool over, padding). lens = 0, a negative one and seq_len + 5 give what the oracle gives at 1, 1
+    and seq_len, on both heads; the row packing, the attention kernels and the mean pool read the one clamped value."""
+    cfg = dict(vocab_size=2000, hidden=384, layers=2, heads=12, ffn=1536, max_pos=128, type_vocab=2, eps=1e-12)
+    w = B.seeded_weights(cfg, 2718)
+    rng = np.random.default_rng(l_in)
+    given = np.array([0, l_in + 5, 12, -3, l_in + 5, l_in], dtype=np.int32)
+    clamped = np.clip(given, 1, l_in)
+    ids, tt = _pairs(rng, cfg, np.full(len(given), l_in, dtype=np.int32), l_in)         # real tokens in every position
+    i64 = lambda x: x.astype(np.int64)
+    eng.ce_load(cfg, _tensors(w, cfg))
+    got = _with_mode(eng, mode, lambda: eng.ce_score(ids, tt, given))
+    same = _with_mode(eng, mode, lambda: eng.ce_score(ids, tt, clamped))
+    exp = B.forward_logits(w, cfg, i64(ids), i64(tt), clamped, fast_erf=True)
+    assert np.isfinite(got).all()
+    assert np.abs(got - exp).max() < LOGIT_TOL, (got, exp)
+    assert np.abs(_sigmoid(got) - _sigmoid(exp)).max() < SCORE_TOL
+    np.testing.assert_array_equal(got, same)
+    eng.embed_load(cfg, _tensors(w, cfg, head=False), normalize=True)
+    vec = _with_mode(eng, mode, lambda: eng.embed(ids, tt, given))
+    vsame = _with_mode(eng, mode, lambda: eng.embed(ids, tt, clamped))
+    ref = B.sentence_embeddings(w, cfg, i64(ids), i64(tt), clamped, fast_erf=True)
+    assert np.isfinite(vec).all()
+    assert np.abs(vec - ref).max() < EMB_TOL
+    assert ((vec * ref).sum(1) > 1 - 1e-6).all()
+    np.testing.assert_array_equal(vec, vsame)
+
+
 # ---- the embedding model's multi-chunk loop (out_width = hidden floats per pair) -----------------------------------------------
 @pytest.mark.parametrize("l_in", [100, 300])
 @pytest.mark.parametrize("hidden", [384, 128], ids=["h384-mx", "h128-split16"])

@@ -28,18 +28,9 @@ pytestmark = pytest.mark.gpu
 
 LOGIT_TOL = 4e-3
 SCORE_TOL = 1e-3
-CFG = B.minilm_config()
-L = 128
-LENS = np.array([128, 1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 80, 95, 96, 97, 111, 112, 113, 127, 128], dtype=np.int32)
+CFG, L, LENS, LEVELS = S.CFG, S.L, S.LENS, S.LEVELS          # shared with the embedding-head stress test
 SEL = [0, 2, 7, 12, 18, 23]
 
-LEVELS = {
-    "seeded": lambda w: w,
-    "moderate": lambda w: S.outliers(S.sharp(w, CFG, 1.5), CFG, 8),
-    "sharp": lambda w: S.sharp(w, CFG, 2),
-    "outlier": lambda w: S.outliers(w, CFG, 12, 3),
-    "combined": lambda w: S.ffn_tails(S.outliers(S.sharp(w, CFG, 1.5), CFG, 8), CFG, 3),
-}
 # forced MX at the levels where the checked pairs miss the bar: max |logit - oracle| measured on the MI355X
 MX_MISSES = {"moderate": "MX forward: max |logit - oracle| 9.8e-3, |score - oracle| 1.0e-3 on the MI355X (bar 4e-3 / 1e-3)",
              "sharp": "MX forward: max |logit - oracle| 2.2e-2, |score - oracle| 2.3e-3 on the MI355X (bar 4e-3 / 1e-3)"}
@@ -47,12 +38,7 @@ MX_MISSES = {"moderate": "MX forward: max |logit - oracle| 9.8e-3, |score - orac
 DEFAULT_IS_MX = {"seeded": True, "moderate": False, "sharp": False, "outlier": False, "combined": False}
 
 
-def batch():
-    rng = np.random.default_rng(2468)
-    ids = rng.integers(1000, CFG["vocab_size"], (len(LENS), L)).astype(np.int32)
-    ids[np.arange(L)[None, :] >= LENS[:, None]] = 0
-    tt = ((np.arange(L)[None, :] >= 18) & (np.arange(L)[None, :] < LENS[:, None])).astype(np.int32)
-    return ids, tt
+batch = S.batch
 
 
 _LEVEL_CACHE = {}

@@ -134,7 +134,8 @@ def wscale_for(w):
     return 2.0 ** math.floor(math.log2(448.0 / np.abs(w).max()))
 
 
-def forward(w, cfg, ids, tt, lens, sch, sites=None):
+def hidden(w, cfg, ids, tt, lens, sch):
+    """(weights as float64, last hidden state [P, L, H]) of the encoder under scheme `sch`"""
     from scipy.special import erf
     W = {k: v.astype(np.float64) for k, v in w.items()}
     P, L = ids.shape
@@ -169,8 +170,22 @@ def forward(w, cfg, ids, tt, lens, sch, sites=None):
         h = sch.store(0.5 * h * (1.0 + erf(h / math.sqrt(2.0))))
         o = lin(h, p + "output.dense")
         x = sch.store(B._ln(o + x, W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"], cfg["eps"]))
+    return W, x
+
+
+def forward(w, cfg, ids, tt, lens, sch, sites=None):
+    """classifier logits [P]"""
+    W, x = hidden(w, cfg, ids, tt, lens, sch)
     pooled = np.tanh(x[:, 0] @ W["bert.pooler.dense.weight"].T + W["bert.pooler.dense.bias"])
     return (pooled @ W["classifier.weight"].T + W["classifier.bias"])[:, 0]
+
+
+def sentence_embeddings(w, cfg, ids, tt, lens, sch, normalize=True):
+    """the embedding head (mean over the real tokens, optionally L2-normalised) on the simulated encoder, [P, H]"""
+    _, x = hidden(w, cfg, ids, tt, lens, sch)
+    keep = (np.arange(x.shape[1])[None, :] < np.asarray(lens)[:, None])[..., None]
+    pooled = (x * keep).sum(1) / np.asarray(lens, dtype=np.float64)[:, None]
+    return pooled / np.maximum(np.linalg.norm(pooled, axis=1, keepdims=True), 1e-12) if normalize else pooled
 
 
 def main():
