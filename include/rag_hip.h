@@ -28,7 +28,8 @@
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_bm25_load_host,
- *     rag_index_load_host, rag_index_reserve, rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
+ *     rag_bm25_append_host, rag_bm25_fold, rag_index_load_host, rag_index_reserve, rag_ce_load_host, rag_embed_load_host, the
+ *     live writes) returns the result
  *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize and rag_set_option do not
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
  *     *_dev calls of one handle on SEVERAL streams stay unordered among themselves: that is the caller's to order.
@@ -63,7 +64,7 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, ce_chunk_tokens, ce_mx. Unknown name: RAG_ERR_ARG. */
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, ce_chunk_tokens, ce_mx. Unknown name: RAG_ERR_ARG. */
 int rag_set_option(rag_handle_t h, const char* name, int value);
 
 /* ---- dense index: replaces the pgvector tables behind
@@ -119,8 +120,10 @@ int rag_index_rows(rag_handle_t h, int64_t* n_rows_out);
  * row_map_out[rows before] (may be NULL) = new row of each old row or -1, *n_rows_out = rows after. Doc ids never change
  * (an implicit-id index stores its ids first). Marks the BM25 postings stale.
  *
- * Stale postings: BM25 and hybrid entry points return RAG_ERR_STATE until rag_bm25_load_host loads postings aligned with the
- * current rows (deletes do not make them stale). */
+ * Stale postings: BM25 and hybrid entry points return RAG_ERR_STATE while the postings do not describe the current rows
+ * (deletes do not make them stale). After inserts, rag_bm25_append_host of the new rows' postings makes them current again -
+ * once EVERY inserted row is covered; after a compaction only rag_bm25_load_host of postings aligned with the new row numbers
+ * does. */
 typedef struct rag_row_block {
     int64_t n;
     const float* emb;            /* [n][dim] */
@@ -261,6 +264,36 @@ int rag_bm25_load_host(rag_handle_t h, const int64_t* indptr_host /*V+1*/, const
                        const int32_t* tf_host /*nnz*/, const int32_t* doc_len_host /*N*/,
                        const double* idf_host /*V*/, int64_t n_docs, int64_t n_terms, double avgdl,
                        double k1, double b);
+/* ---- appendable postings: BM25 and hybrid search stay live through rag_index_insert_host without re-uploading the CSR.
+ * rag_bm25_append_host takes the postings of the NEXT n_docs_new rows after the rows the resident postings cover: a term-major
+ * CSR over the handle's vocabulary (indptr[n_terms_total + 1], docs ascending per term and RELATIVE to the block's first row,
+ * doc_len[n_docs_new]). Term numbers at or above the number of terms known so far are new terms; idf_new[n_terms_total - known]
+ * are their idf values; n_terms_total may not shrink. STATISTICS ARE FROZEN at the last rag_bm25_load_host: avgdl, k1, b and the
+ * idf of every known term keep their loaded values (the rule deletes follow), a new term keeps the idf it arrived with; a caller
+ * who wants fresh statistics reloads. After any sequence of appends every BM25 and hybrid result is BIT-IDENTICAL to a fresh
+ * handle that holds the same rows and was loaded with the merged CSR (all rows; each term's list = its old list followed by the
+ * new postings), the concatenated idf table and the same avgdl, k1, b.
+ * Synchronous, takes the handle lock, waits for queued *_dev work like every host write. RAG_ERR_STATE without loaded postings;
+ * RAG_ERR_ARG for n_docs_new < 1, a malformed CSR, or a block that would cover more rows than a loaded dense index has (without
+ * a dense index appends are always allowed); RAG_ERR_NOMEM when it cannot allocate. A failed append leaves postings, coverage
+ * and staleness exactly as they were. The postings stop being stale exactly when, after the call, the covered rows equal the
+ * index rows and nothing but inserts happened since they were last aligned (5 rows inserted, 3 appended: still stale).
+ * Representation: the loaded postings (the base) are never touched; ONE tail segment holds every appended row and is rebuilt on
+ * the device by each append - cost O(tail), never O(base) - always in the (doc, impact) form, also behind a bm25_packed base
+ * (the two forms give the same float64 product). Every search scores base and tail as one index.
+ * rag_bm25_fold merges the tail into the base on the device (per-term concatenation, tables rebuilt); results before and after
+ * are bit-identical. It needs transient memory for the merged arrays: RAG_ERR_NOMEM changes nothing. RAG_ERR_STATE on a
+ * bm25_packed base (the packed code table cannot absorb new (tf, length) pairs). Option bm25_tail_fold: > 0 = an append folds
+ * by itself once the tail holds more than that many documents, -1 = never, 0 = the default policy. */
+typedef struct rag_bm25_segments {
+    int64_t base_docs, tail_docs, base_nnz, tail_nnz, n_terms, tail_bytes, appends, folds;
+} rag_bm25_segments;
+int rag_bm25_append_host(rag_handle_t h, const int64_t* indptr_host /*n_terms_total+1*/, const int32_t* doc_host,
+                         const int32_t* tf_host, const int32_t* doc_len_host /*n_docs_new*/,
+                         const double* idf_new_host /*n_terms_total - terms known so far*/, int64_t n_docs_new,
+                         int64_t n_terms_total);
+int rag_bm25_fold(rag_handle_t h);
+int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out);
 /* HBM bytes rag_bm25_load_host will take for a CSR with these offsets, computed on the host from indptr alone (no GPU call):
  * postings (doc id + float64 impact, 12 B each; 8 B with option bm25_packed: the impact is then idf * g[code of the posting's
  * (term frequency, document length) pair] - bit-identical, less HBM, a slower scoring loop), per-term metadata (32 B each) and

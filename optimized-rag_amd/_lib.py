@@ -36,6 +36,10 @@ class RowBlock(C.Structure):
                 ("tokens", C.c_void_p), ("token_lens", C.c_void_p)]
 
 
+class Bm25Segments(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("base_docs", "tail_docs", "base_nnz", "tail_nnz", "n_terms", "tail_bytes", "appends", "folds")]
+
+
 class CeConfig(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("ffn", C.c_int32), ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("reserved", C.c_int32),
@@ -82,6 +86,9 @@ _SIGS = {
     "rag_pairwise_cosine_f64_host": ([_P, _P, C.c_int, _P, C.c_int, C.c_int, _P], C.c_int),
     "rag_rrf_fuse_host": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_bm25_load_host": ([_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double], C.c_int),
+    "rag_bm25_append_host": ([_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
+    "rag_bm25_fold": ([_P], C.c_int),
+    "rag_bm25_segment_stats": ([_P, C.POINTER(Bm25Segments)], C.c_int),
     "rag_bm25_topk_host": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_bm25_scores_host": ([_P, _P, _P, C.c_int, _P], C.c_int),
     "rag_bm25_scores_adhoc_host": ([_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P,
@@ -517,6 +524,31 @@ class RagEngine:
                                                 doc_len.shape[0], idf.shape[0], float(avgdl), float(k1), float(b)),
                     "rag_bm25_load_host")
         self.bm25_docs = int(doc_len.shape[0])
+
+    # ---- appendable postings (include/rag_hip.h rag_bm25_append_host / rag_bm25_fold / rag_bm25_segment_stats) -------------
+    def bm25_append(self, indptr, doc, tf, doc_len, idf_new, n_terms_total=None):
+        """Postings of the next len(doc_len) rows after the rows the resident postings cover: CSR over the handle's vocabulary
+        (doc relative to the block's first row), idf_new for the terms numbered past the known ones. Statistics stay frozen."""
+        indptr = _np(indptr, np.int64)
+        doc = _np(doc, np.int32)
+        tf = _np(tf, np.int32)
+        doc_len = _np(doc_len, np.int32)
+        idf_new = _np(idf_new, np.float64)
+        V = int(indptr.shape[0] - 1 if n_terms_total is None else n_terms_total)
+        if indptr.shape[0] != V + 1 or doc.shape[0] != tf.shape[0] or (V >= 0 and doc.shape[0] != int(indptr[-1])):
+            raise RagError("bm25_append: indptr must have n_terms_total + 1 entries and end at len(doc) == len(tf)")
+        self._check(self.lib.rag_bm25_append_host(self.h, _ptr(indptr), _ptr(doc), _ptr(tf), _ptr(doc_len), _ptr(idf_new),
+                                                  doc_len.shape[0], V), "rag_bm25_append_host")
+        self.bm25_docs = getattr(self, "bm25_docs", 0) + int(doc_len.shape[0])
+
+    def bm25_fold(self):
+        """Merge the appended tail into the base postings on the device (results do not change)."""
+        self._check(self.lib.rag_bm25_fold(self.h), "rag_bm25_fold")
+
+    def bm25_segment_stats(self):
+        out = Bm25Segments()
+        self._check(self.lib.rag_bm25_segment_stats(self.h, C.byref(out)), "rag_bm25_segment_stats")
+        return {k: int(getattr(out, k)) for k, _ in out._fields_}
 
     def bm25_topk(self, term_ptr, terms, k, tenant=-1):
         term_ptr = _np(term_ptr, np.int32)

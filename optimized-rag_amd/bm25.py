@@ -19,9 +19,12 @@ class Bm25Postings:
     """CSR postings (term-major, docs ascending) + idf. Terms are numbered in first-appearance order, which is
     the dict order rank-bm25 sums idf in (the float64 mean depends on that order)."""
 
-    def __init__(self, indptr, doc, tf, doc_len, idf, avgdl, vocab=None, k1=K1, b=B):
+    def __init__(self, indptr, doc, tf, doc_len, idf, avgdl, vocab=None, k1=K1, b=B, epsilon=EPSILON):
         self.indptr, self.doc, self.tf, self.doc_len, self.idf = indptr, doc, tf, doc_len, idf
-        self.avgdl, self.vocab, self.k1, self.b = avgdl, vocab, k1, b
+        self.avgdl, self.vocab, self.k1, self.b, self.epsilon = avgdl, vocab, k1, b, epsilon
+        # mean of the idf table as built (sequential float64 sum): what a negative idf of a term that arrives LATER is replaced
+        # with (extend), so that it does not depend on how the later documents were split into blocks
+        self._frozen_mean = float(np.cumsum(idf)[-1]) / idf.shape[0] if idf.shape[0] else 0.0
 
     @property
     def n_docs(self):
@@ -71,7 +74,80 @@ class Bm25Postings:
         doc = (key % max(n, 1)).astype(np.int32)
         avgdl = int(doc_len.sum()) / n if n else 0.0
         idf = cls.idf_table(np.diff(indptr), n, epsilon) if V else np.zeros(0)
-        return cls(indptr, doc, tf.astype(np.int32), doc_len, idf, avgdl, vocab, k1, b)
+        return cls(indptr, doc, tf.astype(np.int32), doc_len, idf, avgdl, vocab, k1, b, epsilon)
+
+    # ---- appendable postings: the host mirror of rag_bm25_append_host -----------------------------------------------------
+    def extend(self, texts):
+        """Add documents after the existing ones. The mirror (indptr / doc / tf / doc_len / vocab) becomes exactly what
+        `from_corpus(old + texts)` builds; the STATISTICS stay frozen, as they do on the device: `idf[:V_old]` and `avgdl` keep
+        their values, a term first seen here gets ln(N - df + 0.5) - ln(df + 0.5) with N and df as they stand after this block
+        (a negative value: epsilon * the mean of the table as built) and keeps it from then on. `refreshed()` gives the
+        statistics a rebuild would. Returns the block `append_to` / `RagEngine.bm25_append` takes: the CSR of the new documents
+        alone over the grown vocabulary, doc numbers relative to the block."""
+        if self.vocab is None:
+            raise ValueError("extend needs the vocabulary (postings built by from_corpus)")
+        n_old, nb, V_old = self.n_docs, len(texts), len(self.vocab)
+        vocab, ids = self.vocab, []
+        bl = np.zeros(nb, dtype=np.int32)
+        for di, text in enumerate(texts):
+            toks = tokenize(text)
+            bl[di] = len(toks)
+            for w in toks:
+                if w not in vocab:
+                    vocab[w] = len(vocab)
+            ids.extend(map(vocab.__getitem__, toks))
+        V = len(vocab)
+        term_of_tok = np.asarray(ids, dtype=np.int64)
+        doc_of_tok = np.repeat(np.arange(nb, dtype=np.int64), bl)
+        key, btf = np.unique(term_of_tok * max(nb, 1) + doc_of_tok, return_counts=True)
+        bterm = key // max(nb, 1)
+        bptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(bterm, minlength=V), out=bptr[1:])
+        bdoc = (key % max(nb, 1)).astype(np.int32)
+        btf = btf.astype(np.int32)
+        # merged mirror: every term's old list, then its new postings (the new documents have the larger numbers)
+        odf = np.zeros(V, dtype=np.int64)
+        odf[:V_old] = np.diff(self.indptr)
+        bdf = np.diff(bptr)
+        indptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(odf + bdf, out=indptr[1:])
+        nnz_o, nnz_b = int(self.indptr[-1]), int(bptr[-1])
+        oterm = np.repeat(np.arange(V_old, dtype=np.int64), odf[:V_old])
+        opos = indptr[oterm] + (np.arange(nnz_o, dtype=np.int64) - self.indptr[oterm])
+        bpos = indptr[bterm] + odf[bterm] + (np.arange(nnz_b, dtype=np.int64) - bptr[bterm])
+        doc = np.empty(nnz_o + nnz_b, dtype=np.int32)
+        tf = np.empty(nnz_o + nnz_b, dtype=np.int32)
+        doc[opos], tf[opos] = self.doc, self.tf
+        doc[bpos], tf[bpos] = bdoc + np.int32(n_old), btf
+        n = n_old + nb
+        df_new = (odf + bdf)[V_old:]
+        idf_new = np.array([math.log(n - int(d) + 0.5) - math.log(int(d) + 0.5) for d in df_new], dtype=np.float64)
+        idf_new = np.where(idf_new < 0, self.epsilon * self._frozen_mean, idf_new)
+        self.indptr, self.doc, self.tf = indptr, doc, tf
+        self.doc_len = np.concatenate([self.doc_len, bl])
+        self.idf = np.concatenate([self.idf, idf_new])
+        return {"indptr": bptr, "doc": bdoc, "tf": btf, "doc_len": bl, "idf_new": idf_new, "n_terms_total": V}
+
+    def append_to(self, engine, block):
+        """Hand a block `extend` returned to the engine (after the rows themselves were inserted, or on a standalone BM25 handle)."""
+        engine.bm25_append(block["indptr"], block["doc"], block["tf"], block["doc_len"], block["idf_new"], block["n_terms_total"])
+        return self
+
+    def refreshed(self, epsilon=None):
+        """A new object over the same (merged) CSR with idf / avgdl recomputed: what `from_corpus` over all texts gives."""
+        eps = self.epsilon if epsilon is None else epsilon
+        n = self.n_docs
+        avgdl = int(self.doc_len.sum()) / n if n else 0.0
+        idf = self.idf_table(np.diff(self.indptr), n, eps) if self.indptr.shape[0] > 1 else np.zeros(0)
+        return Bm25Postings(self.indptr.copy(), self.doc.copy(), self.tf.copy(), self.doc_len.copy(), idf, avgdl, dict(self.vocab) if self.vocab is not None else None,
+                            self.k1, self.b, eps)
+
+    def drift(self):
+        """How far the frozen statistics are from what a rebuild would compute: lets a caller decide when to reload."""
+        fresh = self.refreshed()
+        d = np.abs(fresh.idf - self.idf)
+        return {"avgdl_frozen": float(self.avgdl), "avgdl_true": float(fresh.avgdl),
+                "idf_max_abs_change": float(d.max()) if d.size else 0.0}
 
     def shard(self, begin, end):
         """Doc-partitioned slice [begin, end) for row-sharded search: postings of the shard's docs

@@ -20,6 +20,10 @@ int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc
                            const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
                            const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
 int64_t bm25_n_docs(const rag_ctx* h);
+int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
+                     const double* idf_new, int64_t n_new, int64_t n_terms_total);
+int bm25_fold(rag_ctx* h);
+int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
 int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
 int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
@@ -67,6 +71,7 @@ static const struct { const char* name; int rag_options::*field; } g_options[] =
     {"dense_linear_order", &rag_options::dense_linear_order}, {"dense_persist", &rag_options::dense_persist},
     {"bm25_first_ranges", &rag_options::bm25_first_ranges}, {"bm25_no_staging", &rag_options::bm25_no_staging},
     {"bm25_packed", &rag_options::bm25_packed},         {"bm25_plan_slots", &rag_options::bm25_plan_slots},       {"bm25_ws_mb", &rag_options::bm25_ws_mb},
+    {"bm25_tail_fold", &rag_options::bm25_tail_fold},
     {"bm25_linear_grid", &rag_options::bm25_linear_grid},            {"bm25_sort_merge", &rag_options::bm25_sort_merge},
     {"no_fork", &rag_options::no_fork},                 {"fork_max_q", &rag_options::fork_max_q},
     {"ce_chunk_tokens", &rag_options::ce_chunk_tokens}, {"ce_mx", &rag_options::ce_mx},
@@ -488,6 +493,27 @@ int rag_bm25_load_host(rag_handle_t h, const int64_t* indptr, const int32_t* doc
     LOCK(h);
     HOST_ENTRY(h);
     return bm25_load_host(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b);
+}
+
+int rag_bm25_append_host(rag_handle_t h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
+                         const double* idf_new, int64_t n_docs_new, int64_t n_terms_total) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return bm25_append_host(h, indptr, doc, tf, doc_len, idf_new, n_docs_new, n_terms_total);
+}
+
+int rag_bm25_fold(rag_handle_t h) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return bm25_fold(h);
+}
+
+int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return bm25_segment_stats(h, out);
 }
 
 int rag_bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5) {

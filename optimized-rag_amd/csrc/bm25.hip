@@ -92,7 +92,22 @@ struct rag_bm25_index {
     double avgdl = 0, k1 = 1.5, b = 0.75;
     double neg_idf_absmax = 0;         // largest |idf| among the negative idf values (0: none), for bm25_negative_bound_args
     int normalize = 1;                 // 0: top-k scores stay raw (row-sharded search divides by the GLOBAL max after the merge)
+    // ---- appendable postings (rag_bm25_append_host / rag_bm25_fold). The BASE is the index as loaded; ONE TAIL - an index of
+    // the same layout, always in the (doc, impact) form - holds the postings of the rows [n_docs, n_docs + tail_docs) appended
+    // since. The tail numbers its documents from the start of the base's last 2048-document range (row0 = n_docs rounded down to a
+    // range), so its ranges are the index's own ranges and a row's accumulator sits where a merged index would put it; the
+    // boundary range exists in both segments and `first` = n_docs - row0 keeps the tail from emitting the base's rows.
+    std::unique_ptr<rag_bm25_index> tail;
+    int64_t tail_docs = 0;             // base: documents the tail covers
+    int64_t appends = 0, folds = 0;    // base: since the load
+    std::vector<int64_t> indptr_h;     // host copy of the posting offsets [n_terms + 1] (per-term concatenation is planned on the host)
+    std::vector<double> idf_h;         // base: frozen idf of every known term, loaded and appended (size = terms known so far)
+    dev_buf<int64_t> indptr_d;         // tail: the offsets on the device (source of the next append / the fold)
+    int64_t row0 = 0;                  // tail: index row of its local document 0
+    int first = 0;                     // tail: local documents below this are the base's
 };
+static inline int64_t bm_total_docs(const rag_bm25_index* ix) { return ix->n_docs + ix->tail_docs; }
+static inline int bm_total_ranges(const rag_bm25_index* ix) { return ix->n_ranges + (ix->tail ? ix->tail->n_ranges : 0); }
 
 __global__ void bm25_weights_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc,
                                     const int32_t* __restrict__ tf, const int32_t* __restrict__ doc_len, int64_t nnz,
@@ -257,6 +272,10 @@ struct bm_grid { unsigned blocks; int nr_l, n_queries, n_groups, qgroup_len, pla
 // a float32 copy of the raw scores [q][ld] (the emission operand of the fused dense search) and the per-query maximum over the
 // tenant's documents as an orderable key (atomicMax: order-independent, so the result is the bits a sequential max gives).
 struct bm_dense_extra { float* raw32; int64_t ld; unsigned long long* max_key; };
+// where a segment's documents sit in the index: local document d of the launch is index row row0 + d, local documents below
+// `first` (range 0 only) belong to the other segment and are neither emitted nor written, out_ld = row length of the
+// all-document score array (documents of BOTH segments). The base is {0, all documents, 0}.
+struct bm_seg { int64_t row0; int64_t out_ld; int first; };
 static bm_grid bm_make_grid(int nr_l, int Q, int linear) {
     bm_grid g{(unsigned)((int64_t)nr_l * Q), nr_l, Q, 1, 0, BM_PLAN_T};
     if (linear || Q < 128) return g;
@@ -288,7 +307,7 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
                                                                  const uint64_t* __restrict__ tau_key, int* __restrict__ part_cnt,
                                                                  const int32_t* __restrict__ tenants, int tenant,
                                                                  const int32_t* __restrict__ plan_off, const bm_plan_meta* __restrict__ plan_meta,
-                                                                 const bm_grid gm, const bm_dense_extra dx) {
+                                                                 const bm_grid gm, const bm_dense_extra dx, const bm_seg sg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup -> (range, query), see bm_make_grid: XCD x (= workgroup id % 8) walks its columns (range, query group) one after the
     // other, every query of the group on the SAME range side by side, so a range's postings are fetched into that XCD's L2 once
@@ -315,6 +334,8 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     const int lane = tid & 63, wv = tid >> 6;
     const int64_t base = (int64_t)r * BM_RANGE;
     const int lim = (int)min((int64_t)BM_RANGE, n_docs - base);
+    const int first = r == 0 ? sg.first : 0;                           // (scalar) first document of the range this segment owns
+    const int64_t row_base = sg.row0 + base;                           // index row of the range's document 0
     // per-token metadata (idf, posting sub-range of this doc range) is fetched for up to 64 tokens IN PARALLEL into
     // LDS first: fetched inside the token loop it was ~4 dependent global round trips per token per block. The first batch's
     // loads (the planned tokens: two adjacent plan entries each) are issued BEFORE the accumulators are cleared, so that the
@@ -528,12 +549,12 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     }
     if (mode == 1) {
         double m = -INFINITY;
-        for (int i = tid; i < lim; i += BM_THREADS) {
+        for (int i = first + tid; i < lim; i += BM_THREADS) {
             // a deleted row scores 0.0 (it is not in the corpus the reference would score)
-            const double v = row_visible(tenants, base + i, -1) ? sc[SC_IDX(i)] : 0.0;
-            dense_out[(size_t)q * n_docs + base + i] = v;
-            if (dx.raw32 != nullptr) dx.raw32[(size_t)q * dx.ld + base + i] = (float)v;
-            if (dx.max_key != nullptr && row_visible(tenants, base + i, tenant)) m = fmax(m, v);
+            const double v = row_visible(tenants, row_base + i, -1) ? sc[SC_IDX(i)] : 0.0;
+            dense_out[(size_t)q * sg.out_ld + row_base + i] = v;
+            if (dx.raw32 != nullptr) dx.raw32[(size_t)q * dx.ld + row_base + i] = (float)v;
+            if (dx.max_key != nullptr && row_visible(tenants, row_base + i, tenant)) m = fmax(m, v);
         }
         if (dx.max_key != nullptr) {
 #pragma unroll
@@ -549,9 +570,9 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     // (key 0, below every real score) from here on, so it can neither enter a partial list nor move the threshold.
     if (lim <= k) {
         for (int i = tid; i < k; i += BM_THREADS) {
-            const bool mine = i < lim && row_visible(tenants, base + i, tenant);
+            const bool mine = i < lim && i >= first && row_visible(tenants, row_base + i, tenant);
             part_key[po + i] = mine ? f64_orderable(sc[SC_IDX(i)]) : 0ull;
-            part_row[po + i] = (uint32_t)(base + i);
+            part_row[po + i] = (uint32_t)(row_base + i);
         }
         if (tid == 0) part_cnt[(size_t)q * n_ranges + r] = lim;
         return;
@@ -564,10 +585,11 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     for (int j = 0; j < BM_SEG; ++j) sv[j] = sc[SC_IDX(seg0 + j)];
     const int n_here = lim - seg0;
     unsigned valid = n_here >= BM_SEG ? (1u << BM_SEG) - 1u : (n_here <= 0 ? 0u : (1u << n_here) - 1u);
+    if (first > seg0) valid &= first - seg0 >= BM_SEG ? 0u : ~((1u << (first - seg0)) - 1u);     // the other segment's documents: empty slots
     if (tenants != nullptr) {
 #pragma unroll
         for (int j = 0; j < BM_SEG; ++j)
-            if ((valid >> j & 1u) && !row_visible(tenants, base + seg0 + j, tenant)) valid &= ~(1u << j);
+            if ((valid >> j & 1u) && !row_visible(tenants, row_base + seg0 + j, tenant)) valid &= ~(1u << j);
     }
     // Thresholded ranges (second stage, see bm25_launch_topk): tau_key[q] is the k-th best key over the first-stage
     // ranges, a lower bound of the global k-th. Only keys >= tau can reach the global top-k; a later range holds
@@ -608,7 +630,7 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
                 for (int j = 0; j < BM_SEG; ++j)
                     if (pass >> j & 1u) {
                         part_key[po + off] = f64_orderable(sv[j]);
-                        part_row[po + off] = (uint32_t)(base + seg0 + j);
+                        part_row[po + off] = (uint32_t)(row_base + seg0 + j);
                         ++off;
                     }
             }
@@ -698,12 +720,12 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
         const uint64_t key = keys[j];
         if (key > pivot) {
             part_key[po + off_gt] = key;
-            part_row[po + off_gt] = (uint32_t)(base + i);
+            part_row[po + off_gt] = (uint32_t)(row_base + i);
             ++off_gt;
         } else if (key == pivot) {
             if (off_eq < need_ties) {
                 part_key[po + total_gt + off_eq] = key;
-                part_row[po + total_gt + off_eq] = (uint32_t)(base + i);
+                part_row[po + total_gt + off_eq] = (uint32_t)(row_base + i);
             }
             ++off_eq;
         }
@@ -1052,54 +1074,104 @@ struct bm25_topk_out {
 // compacts keys >= tau. Expected survivors per stage ~ k * growth per query however large the shard is (a single
 // threshold from 32768 docs left ~k/2 per range: 38 k entries per query to merge on a 12.5M-doc shard).
 // the scoring launch: packed 4-byte postings when the index has them, the 12-byte form otherwise
-#define BM_RANGE_LAUNCH(H, IX, NR_L, NQ, ST, DX, NR, TP, TM, K, MODE, ...)                                                             \
+// OUT_LD: documents of the whole index (both segments), the row length of the all-document score array
+#define BM_RANGE_LAUNCH(H, IX, OUT_LD, NR_L, NQ, ST, DX, NR, TP, TM, K, MODE, ...)                                                     \
     {                                                                                                                              \
         bm_grid gm_ = bm_make_grid(NR_L, NQ, (H)->opt.bm25_linear_grid);                                                           \
         gm_.plan_t = (IX)->plan_t;                                                                                                 \
+        const bm_seg sg_ = {(IX)->row0, OUT_LD, (IX)->first};                                                                      \
         if ((IX)->packed != nullptr)                                                                                               \
             hipLaunchKernelGGL(bm25_range_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX); \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_); \
         else                                                                                                                       \
             hipLaunchKernelGGL(bm25_range_kernel<false>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX); \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_); \
     }
 static int bm25_pick_plan_t(const rag_ctx* h, const rag_bm25_index* ix, int Q) {
     if (h->opt.bm25_plan_slots > 0) return std::min(BM_PLAN_T, h->opt.bm25_plan_slots);
-    const size_t per_slot = (size_t)Q * (ix->n_ranges + 1) * sizeof(int32_t);
+    const size_t per_slot = (size_t)Q * (ix->n_ranges + 1 + (ix->tail ? ix->tail->n_ranges + 1 : 0)) * sizeof(int32_t);
     return (int)std::min<size_t>(BM_PLAN_T, std::max<size_t>(8, BM_PLAN_BUDGET / std::max<size_t>(1, per_slot)));
 }
 static size_t bm25_plan_off_entries(const rag_bm25_index* ix, int Q) { return (size_t)Q * ix->plan_t * (ix->n_ranges + 1); }
+// the plan of the tail sits behind the base's in the same two buffers (offsets: all of the base's entries; metadata: Q x BM_PLAN_T)
+static size_t bm25_plan_off_total(const rag_bm25_index* ix, int Q) {
+    return bm25_plan_off_entries(ix, Q) + (ix->tail ? (size_t)Q * ix->plan_t * (ix->tail->n_ranges + 1) : 0);
+}
+static size_t bm25_plan_meta_total(const rag_bm25_index* ix, int Q) { return (size_t)Q * BM_PLAN_T * (ix->tail ? 2 : 1); }
+static bm25_plan_ws bm25_tail_plan(const rag_bm25_index* ix, int Q, const bm25_plan_ws& p) {
+    return {p.off + bm25_plan_off_entries(ix, Q), p.meta + (size_t)Q * BM_PLAN_T};
+}
 static void bm25_launch_plan(const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, const bm25_plan_ws& p,
                              hipStream_t st) {
     hipLaunchKernelGGL(bm25_plan_kernel, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab,
                        ix->n_ranges, ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t);
 }
 
+// mode 1 over every segment: out[Q][documents of the index] (+ the linear fusion's extras); each segment writes its own columns
+static void bm25_launch_scores(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q,
+                               double* out, const bm_dense_extra& dx, const int32_t* tenants, int tenant, const bm25_plan_ws& pw, hipStream_t st) {
+    const int64_t n_all = bm_total_docs(ix);
+    bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, pw, st);
+    BM_RANGE_LAUNCH(h, ix, n_all, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, out, (uint64_t*)nullptr,
+                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)pw.off,
+                    (const bm_plan_meta*)pw.meta)
+    rag_bm25_index* tl = ix->tail.get();
+    if (tl == nullptr) return;
+    tl->plan_t = ix->plan_t;
+    const bm25_plan_ws tp = bm25_tail_plan(ix, Q, pw);
+    bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
+    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, dx, tl->n_ranges, term_ptr_dev, terms_dev, 1, 1, out, (uint64_t*)nullptr,
+                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)tp.off,
+                    (const bm_plan_meta*)tp.meta)
+}
+
+// folds the partial lists of the ranges [begin, end) of one segment into the running top-k (selection, or the bitonic sort)
+static void bm25_launch_merge(const rag_ctx* h, const bm25_topk_ws& w, const uint64_t* part_key, const uint32_t* part_row, const int* part_cnt,
+                              int nr, int begin, int end, int Q, int k, int first, int last, const bm25_topk_out& o, hipStream_t st) {
+    if (k <= BMS_KMAX && !h->opt.bm25_sort_merge)
+        hipLaunchKernelGGL(bm25_merge_select_kernel, dim3((Q + BMS_WAVES - 1) / BMS_WAVES), dim3(64 * BMS_WAVES), BMS_LDS_BYTES, st,
+                           part_key, part_row, part_cnt, nr, begin, end, k, w.run_key, w.run_row, first, w.tau, last,
+                           o.idmap, o.id_base, o.ids, o.rows, o.scores, o.raw_max, o.normalize, Q);
+    else
+        hipLaunchKernelGGL(bm25_merge_stage_kernel, dim3(Q), dim3(256), 0, st, part_key, part_row, part_cnt, nr, begin, end, k,
+                           w.run_key, w.run_row, first, w.tau, last, o.idmap, o.id_base, o.ids, o.rows, o.scores,
+                           o.raw_max, o.normalize);
+}
+
 static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
                              const bm25_topk_ws& w, const bm25_topk_out& o, const int32_t* tenants, int tenant, hipStream_t st) {
     const int nr = ix->n_ranges;
+    rag_bm25_index* tl = ix->tail.get();
     bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, w.plan, st);
+    const int64_t n_all = bm_total_docs(ix);
     const int first_cfg = h->opt.bm25_first_ranges >= 1 && h->opt.bm25_first_ranges <= 16 ? h->opt.bm25_first_ranges : BM_FIRST_RANGES;
     const bool staged = nr > 2 * first_cfg && !h->opt.bm25_no_staging;
     int begin = 0, stage = 0;
     while (begin < nr) {
         int end = !staged ? nr : (stage == 0 ? first_cfg : (int)std::min<int64_t>(nr, (int64_t)begin * BM_STAGE_GROWTH));
         if (staged && nr - end < end / 4) end = nr;                   // no tiny trailing stage
-        BM_RANGE_LAUNCH(h, ix, end - begin, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, term_ptr_dev, terms_dev, k, 0, (double*)nullptr,
+        BM_RANGE_LAUNCH(h, ix, n_all, end - begin, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, term_ptr_dev, terms_dev, k, 0, (double*)nullptr,
                         w.part_key, w.part_row, begin, stage == 0 ? (const uint64_t*)nullptr : (const uint64_t*)w.tau, w.part_cnt,
                         tenants, tenant, (const int32_t*)w.plan.off, (const bm_plan_meta*)w.plan.meta)
-        const int last = end == nr;
-        if (k <= BMS_KMAX && !h->opt.bm25_sort_merge)
-            hipLaunchKernelGGL(bm25_merge_select_kernel, dim3((Q + BMS_WAVES - 1) / BMS_WAVES), dim3(64 * BMS_WAVES), BMS_LDS_BYTES, st,
-                               w.part_key, w.part_row, w.part_cnt, nr, begin, end, k, w.run_key, w.run_row, stage == 0 ? 1 : 0, w.tau, last,
-                               o.idmap, o.id_base, o.ids, o.rows, o.scores, o.raw_max, o.normalize, Q);
-        else
-            hipLaunchKernelGGL(bm25_merge_stage_kernel, dim3(Q), dim3(256), 0, st, w.part_key, w.part_row, w.part_cnt, nr, begin, end, k,
-                               w.run_key, w.run_row, stage == 0 ? 1 : 0, w.tau, last, o.idmap, o.id_base, o.ids, o.rows, o.scores,
-                               o.raw_max, o.normalize);
+        const int last = end == nr && tl == nullptr;
+        bm25_launch_merge(h, w, w.part_key, w.part_row, w.part_cnt, nr, begin, end, Q, k, stage == 0 ? 1 : 0, last, o, st);
         begin = end;
         ++stage;
     }
+    if (tl == nullptr) return;
+    // The tail: ONE more thresholded stage. Its rows come after every base row, so the running list's k-th key is the same
+    // lower bound for it as for a later base range (0 - everything passes - while the base held fewer than k documents). Its
+    // partial lists sit behind the base's, [Q][tail ranges][k], and fold into the same running list: the last fold.
+    tl->plan_t = ix->plan_t;
+    const bm25_plan_ws tp = bm25_tail_plan(ix, Q, w.plan);
+    bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
+    uint64_t* t_key = w.part_key + (size_t)Q * nr * k;
+    uint32_t* t_row = w.part_row + (size_t)Q * nr * k;
+    int* t_cnt = w.part_cnt + (size_t)Q * nr;
+    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), tl->n_ranges, term_ptr_dev, terms_dev, k, 0,
+                    (double*)nullptr, t_key, t_row, 0, (const uint64_t*)w.tau, t_cnt, tenants, tenant, (const int32_t*)tp.off,
+                    (const bm_plan_meta*)tp.meta)
+    bm25_launch_merge(h, w, t_key, t_row, t_cnt, tl->n_ranges, 0, tl->n_ranges, Q, k, 0, 1, o, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1137,6 +1209,8 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
         n_tab += e_t;
     }
     ix->tab_entries = n_tab;
+    ix->indptr_h.assign(indptr, indptr + n_terms + 1);
+    if (n_terms) ix->idf_h.assign(idf, idf + n_terms);
     // code space of the packed postings: distinct term frequencies x distinct document lengths (host scans of tf[] and doc_len[])
     const int64_t code_cap = (int64_t)1 << (32 - BM_RANGE_LOG2);
     std::vector<uint32_t> tf_rank_h, dl_rank_of_doc_h;
@@ -1243,6 +1317,273 @@ int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const 
     bm25_free(h);
     h->bm25 = ix.release();
     h->bm25_stale = false;
+    h->bm25_compacted = false;
+    return RAG_OK;
+}
+
+// ---- appendable postings --------------------------------------------------------------------------------------------------
+// Per-term concatenation A ++ B into a new posting array, one thread per DESTINATION posting: its term is the last t with
+// out_indptr[t] <= p (the search of bm25_weights_kernel), its place j inside the term's list picks the source - the first
+// a_df postings come from A (an index: per-term metadata), the rest from B (a CSR: offsets). Document numbers are shifted
+// into the destination's numbering. The append runs it as old tail ++ block, the fold as base ++ tail.
+__global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64_t n_terms, int64_t nnz,
+                                   const bm_term_meta* __restrict__ a_meta, int64_t a_terms, const int32_t* __restrict__ a_doc,
+                                   const double* __restrict__ a_w, const int64_t* __restrict__ b_indptr,
+                                   const int32_t* __restrict__ b_doc, const double* __restrict__ b_w, int32_t b_shift,
+                                   int32_t* __restrict__ doc_out, double* __restrict__ w_out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    int64_t lo = 0, hi = n_terms;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (out_indptr[mid] <= p) lo = mid; else hi = mid;
+    }
+    const int64_t j = p - out_indptr[lo];
+    int64_t a_df = 0, a_post = 0;
+    if (lo < a_terms) {
+        a_df = a_meta[lo].df;
+        a_post = a_meta[lo].post;
+    }
+    if (j < a_df) {
+        doc_out[p] = a_doc[a_post + j];
+        w_out[p] = a_w[a_post + j];
+    } else {
+        const int64_t s = b_indptr[lo] + (j - a_df);
+        doc_out[p] = b_doc[s] + b_shift;
+        w_out[p] = b_w[s];
+    }
+}
+
+// device allocation of the append / fold: RAG_ERR_NOMEM (not RAG_ERR_HIP) when it cannot be had, nothing else changed
+template <class T>
+static int bm_alloc(rag_ctx* h, dev_buf<T>& buf, size_t n, const char* what) {
+    if (buf.alloc(h, std::max<size_t>(1, n)) == RAG_OK) return RAG_OK;
+    (void)hipGetLastError();
+    h->err = std::string(what) + ": out of device memory";
+    return RAG_ERR_NOMEM;
+}
+
+// Term metadata + bracket-table plan of a segment whose offsets are ix->indptr_h (the host loop of bm25_build) -> ix->meta,
+// ix->range_tab (allocated, metadata uploaded; the table itself is filled by bm25_range_table_kernel once ix->doc is there)
+static int bm_plan_segment(rag_ctx* h, rag_bm25_index* ix, const std::vector<double>& idf, std::vector<bm_term_meta>& meta_h, const char* what) {
+    const int64_t n_pad = (int64_t)ix->n_ranges * BM_RANGE;
+    meta_h.resize((size_t)std::max<int64_t>(1, ix->n_terms));
+    int64_t n_tab = 0;
+    for (int64_t t = 0; t < ix->n_terms; ++t) {
+        const int64_t df = ix->indptr_h[(size_t)t + 1] - ix->indptr_h[(size_t)t];
+        int64_t e_t = 0;
+        const int g = bm_plan_term(df, n_pad, &e_t);
+        meta_h[(size_t)t] = {ix->indptr_h[(size_t)t], n_tab, idf[(size_t)t], (int32_t)df, g};
+        n_tab += e_t;
+    }
+    ix->tab_entries = n_tab;
+    int rc;
+    if ((rc = bm_alloc(h, ix->meta, meta_h.size(), what))) return rc;
+    if ((rc = bm_alloc(h, ix->range_tab, (size_t)n_tab, what))) return rc;
+    if ((rc = bm_alloc(h, ix->doc, (size_t)ix->nnz + 8, what))) return rc;
+    if ((rc = bm_alloc(h, ix->w, (size_t)ix->nnz + 8, what))) return rc;
+    return RAG_OK;
+}
+
+// Default of option bm25_tail_fold (0): the tail size, in documents, past which an append folds by itself. NOT MEASURED YET - a
+// guess until the numbers of profiles/live_bm25_1M.json say otherwise: the tail costs every search one more plan +
+// scoring + fold launch and every append a rebuild of the whole tail, the fold one pass over all postings.
+static int64_t bm_default_fold_docs(int64_t base_docs) { return std::max<int64_t>(32 * BM_RANGE, base_docs / 16); }
+
+int bm25_fold(rag_ctx* h);
+
+int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
+                     const double* idf_new, int64_t n_new, int64_t n_terms_total) {
+    if (!h->bm25) {
+        h->err = "bm25_append: no postings loaded (rag_bm25_load_host first)";
+        return RAG_ERR_STATE;
+    }
+    rag_bm25_index* ix = h->bm25;
+    const rag_bm25_index* ot = ix->tail.get();
+    const int64_t known = (int64_t)ix->idf_h.size(), V = n_terms_total, covered = bm_total_docs(ix);
+    ARG_CHECK(h, n_new >= 1 && covered + n_new < 0x7fffffff, "bm25_append: n_docs_new must be >= 1 (and the index stay under 2^31 documents)");
+    ARG_CHECK(h, V >= known && V < 0x7fffffff, "bm25_append: n_terms_total may not shrink");
+    ARG_CHECK(h, indptr && doc_len && (V == known || idf_new), "bm25_append: null pointer");
+    ARG_CHECK(h, !h->index_loaded || covered + n_new <= h->n_rows, "bm25_append: the block would cover more rows than the index has");
+    ARG_CHECK(h, indptr[0] == 0, "bm25_append: indptr must start at 0");
+    for (int64_t t = 0; t < V; ++t) {
+        const int64_t df = indptr[t + 1] - indptr[t];
+        ARG_CHECK(h, df >= 0 && df <= n_new, "bm25_append: indptr must be non-decreasing with at most n_docs_new postings per term");
+    }
+    const int64_t nnz_b = indptr[V];
+    ARG_CHECK(h, nnz_b == 0 || (doc && tf), "bm25_append: null postings");
+    for (int64_t t = 0; t < V; ++t)            // the block's documents become device addresses: in range, ascending inside a term
+        for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p)
+            ARG_CHECK(h, doc[p] >= 0 && doc[p] < n_new && (p == indptr[t] || doc[p] > doc[p - 1]),
+                      "bm25_append: doc must be ascending inside a term and below n_docs_new");
+    std::vector<double> idf_all(ix->idf_h);
+    idf_all.insert(idf_all.end(), idf_new, idf_new + (V - known));
+    double neg = ix->neg_idf_absmax;
+    for (int64_t t = known; t < V; ++t) if (idf_all[(size_t)t] < 0.0) neg = std::max(neg, -idf_all[(size_t)t]);
+    // the new tail = old tail ++ block, built beside the old one and swapped in at the end
+    std::unique_ptr<rag_bm25_index> nt(new rag_bm25_index());
+    const int64_t Vo = ot ? ot->n_terms : 0;
+    nt->first = (int)(ix->n_docs % BM_RANGE);
+    nt->row0 = ix->n_docs - nt->first;
+    nt->n_docs = nt->first + ix->tail_docs + n_new;
+    nt->n_terms = V;
+    nt->n_ranges = (int)((nt->n_docs + BM_RANGE - 1) / BM_RANGE);
+    nt->avgdl = ix->avgdl; nt->k1 = ix->k1; nt->b = ix->b;
+    nt->indptr_h.resize((size_t)V + 1);
+    nt->indptr_h[0] = 0;
+    for (int64_t t = 0; t < V; ++t)
+        nt->indptr_h[(size_t)t + 1] = nt->indptr_h[(size_t)t] + (t < Vo ? ot->indptr_h[(size_t)t + 1] - ot->indptr_h[(size_t)t] : 0) +
+                                      (indptr[t + 1] - indptr[t]);
+    nt->nnz = nt->indptr_h[(size_t)V];
+    hipStream_t st = h->stream;
+    std::vector<bm_term_meta> meta_h;
+    dev_buf<int64_t> b_indptr;
+    dev_buf<int32_t> b_doc, b_tf, b_dl;
+    dev_buf<double> b_w, idf_d;
+    auto enqueue = [&]() -> int {
+        int rc;
+        const char* what = "bm25_append";
+        if ((rc = bm_plan_segment(h, nt.get(), idf_all, meta_h, what))) return rc;
+        if ((rc = bm_alloc(h, nt->indptr_d, (size_t)V + 1, what))) return rc;
+        if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, what))) return rc;
+        if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, what))) return rc;
+        if ((rc = bm_alloc(h, b_tf, (size_t)nnz_b, what))) return rc;
+        if ((rc = bm_alloc(h, b_w, (size_t)nnz_b, what))) return rc;
+        if ((rc = bm_alloc(h, b_dl, (size_t)n_new, what))) return rc;
+        if ((rc = bm_alloc(h, idf_d, (size_t)V, what))) return rc;
+        HIP_TRY(h, hipMemsetAsync(nt->doc + nt->nnz, 0, 8 * sizeof(int32_t), st));
+        HIP_TRY(h, hipMemsetAsync(nt->w + nt->nnz, 0, 8 * sizeof(double), st));
+        HIP_TRY(h, hipMemcpyAsync(nt->indptr_d, nt->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+        if (V) HIP_TRY(h, hipMemcpyAsync(nt->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
+        if (V) HIP_TRY(h, hipMemcpyAsync(idf_d, idf_all.data(), (size_t)V * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(b_dl, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+        if (nnz_b) {
+            HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(b_tf, tf, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
+            // the block's impacts: the arithmetic of the load, with the FROZEN avgdl and the concatenated idf table
+            hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz_b + 255) / 256)), dim3(256), 0, st, b_indptr.get(), b_doc.get(), b_tf.get(),
+                               b_dl.get(), nnz_b, ix->avgdl, ix->k1, ix->b, idf_d.get(), V, b_w.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (nt->nnz) {
+            hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nt->nnz + 255) / 256)), dim3(256), 0, st, nt->indptr_d.get(), V, nt->nnz,
+                               ot ? ot->meta.get() : (const bm_term_meta*)nullptr, Vo, ot ? ot->doc.get() : (const int32_t*)nullptr,
+                               ot ? ot->w.get() : (const double*)nullptr, b_indptr.get(), b_doc.get(), b_w.get(),
+                               (int32_t)(nt->first + ix->tail_docs), nt->doc.get(), nt->w.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (nt->tab_entries) {
+            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((nt->tab_entries + 255) / 256)), dim3(256), 0, st, nt->meta.get(),
+                               nt->doc.get(), V, nt->tab_entries, nt->range_tab.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        return RAG_OK;
+    };
+    const int rc = enqueue();
+    const hipError_t e2 = hipStreamSynchronize(st);          // also after a failure: the host arrays stay alive until read
+    if (rc) return rc;
+    if (e2 != hipSuccess) {
+        h->err = std::string("bm25_append: ") + hipGetErrorString(e2);
+        return RAG_ERR_HIP;
+    }
+    // commit
+    ix->tail = std::move(nt);
+    ix->tail_docs += n_new;
+    ix->idf_h = std::move(idf_all);
+    ix->neg_idf_absmax = neg;
+    ix->appends++;
+    // aligned again: every row is covered and only inserts came between (a compaction renumbers rows: reload)
+    if (h->bm25_stale && !h->bm25_compacted && h->index_loaded && bm_total_docs(ix) == h->n_rows) h->bm25_stale = false;
+    const int64_t fold_at = h->opt.bm25_tail_fold > 0 ? h->opt.bm25_tail_fold : (h->opt.bm25_tail_fold == 0 ? bm_default_fold_docs(ix->n_docs) : -1);
+    if (fold_at > 0 && ix->tail_docs > fold_at && ix->packed == nullptr) {
+        if (bm25_fold(h) != RAG_OK) h->err.clear();          // the append itself is done; the tail simply stays (e.g. no memory for the merged arrays)
+    }
+    return RAG_OK;
+}
+
+// base ++ tail -> one base, on the device; results are bit-identical before and after (the same impacts, per-term lists in the
+// same order, tables from the same builders)
+int bm25_fold(rag_ctx* h) {
+    if (!h->bm25) {
+        h->err = "bm25_fold: no postings loaded";
+        return RAG_ERR_STATE;
+    }
+    rag_bm25_index* ix = h->bm25;
+    rag_bm25_index* tl = ix->tail.get();
+    if (tl == nullptr) return RAG_OK;
+    if (ix->packed != nullptr) {
+        h->err = "bm25_fold: the base postings are packed (option bm25_packed): their code table cannot absorb new (tf, length) pairs; "
+                 "reload to merge";
+        return RAG_ERR_STATE;
+    }
+    const int64_t V = tl->n_terms, Vb = ix->n_terms;
+    std::unique_ptr<rag_bm25_index> nb(new rag_bm25_index());
+    nb->n_docs = bm_total_docs(ix);
+    nb->n_terms = V;
+    nb->n_ranges = (int)((nb->n_docs + BM_RANGE - 1) / BM_RANGE);
+    nb->avgdl = ix->avgdl; nb->k1 = ix->k1; nb->b = ix->b;
+    nb->normalize = ix->normalize;
+    nb->neg_idf_absmax = ix->neg_idf_absmax;
+    nb->indptr_h.resize((size_t)V + 1);
+    nb->indptr_h[0] = 0;
+    for (int64_t t = 0; t < V; ++t)
+        nb->indptr_h[(size_t)t + 1] = nb->indptr_h[(size_t)t] + (t < Vb ? ix->indptr_h[(size_t)t + 1] - ix->indptr_h[(size_t)t] : 0) +
+                                      (tl->indptr_h[(size_t)t + 1] - tl->indptr_h[(size_t)t]);
+    nb->nnz = nb->indptr_h[(size_t)V];
+    hipStream_t st = h->stream;
+    std::vector<bm_term_meta> meta_h;
+    dev_buf<int64_t> out_indptr;
+    auto enqueue = [&]() -> int {
+        int rc;
+        const char* what = "bm25_fold";
+        if ((rc = bm_plan_segment(h, nb.get(), ix->idf_h, meta_h, what))) return rc;
+        if ((rc = bm_alloc(h, out_indptr, (size_t)V + 1, what))) return rc;
+        HIP_TRY(h, hipMemsetAsync(nb->doc + nb->nnz, 0, 8 * sizeof(int32_t), st));
+        HIP_TRY(h, hipMemsetAsync(nb->w + nb->nnz, 0, 8 * sizeof(double), st));
+        HIP_TRY(h, hipMemcpyAsync(out_indptr, nb->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+        if (V) HIP_TRY(h, hipMemcpyAsync(nb->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
+        if (nb->nnz) {
+            hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nb->nnz + 255) / 256)), dim3(256), 0, st, out_indptr.get(), V, nb->nnz,
+                               ix->meta.get(), Vb, ix->doc.get(), ix->w.get(), tl->indptr_d.get(), tl->doc.get(), tl->w.get(),
+                               (int32_t)tl->row0, nb->doc.get(), nb->w.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (nb->tab_entries) {
+            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((nb->tab_entries + 255) / 256)), dim3(256), 0, st, nb->meta.get(),
+                               nb->doc.get(), V, nb->tab_entries, nb->range_tab.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        return RAG_OK;
+    };
+    const int rc = enqueue();
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (e2 != hipSuccess) {
+        h->err = std::string("bm25_fold: ") + hipGetErrorString(e2);
+        return RAG_ERR_HIP;
+    }
+    nb->idf_h = std::move(ix->idf_h);
+    nb->appends = ix->appends;
+    nb->folds = ix->folds + 1;
+    delete ix;                               // the old base, its tail and their workspaces
+    h->bm25 = nb.release();
+    return RAG_OK;
+}
+
+int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
+    ARG_CHECK(h, out != nullptr, "bm25_segment_stats: null output");
+    if (!h->bm25) {
+        h->err = "bm25_segment_stats: no postings loaded";
+        return RAG_ERR_STATE;
+    }
+    const rag_bm25_index* ix = h->bm25;
+    const rag_bm25_index* tl = ix->tail.get();
+    *out = {ix->n_docs, ix->tail_docs, ix->nnz, tl ? tl->nnz : 0, (int64_t)ix->idf_h.size(),
+            tl ? (int64_t)((tl->doc.size() * 4 + tl->w.size() * 8 + tl->meta.size() * sizeof(bm_term_meta) + tl->range_tab.size() * 4 +
+                            tl->indptr_d.size() * 8))
+               : 0,
+            ix->appends, ix->folds};
     return RAG_OK;
 }
 
@@ -1274,10 +1615,10 @@ static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, co
     *tenants_out = nullptr;
     if (int rc = bm25_check_fresh(h, ix)) return rc;
     if (tenant < 0) {
-        if (ix == h->bm25 && h->vis != nullptr && h->n_rows == ix->n_docs) *tenants_out = h->vis;
+        if (ix == h->bm25 && h->vis != nullptr && h->n_rows == bm_total_docs(ix)) *tenants_out = h->vis;
         return RAG_OK;
     }
-    ARG_CHECK(h, h->tenants != nullptr && h->n_rows == ix->n_docs,
+    ARG_CHECK(h, h->tenants != nullptr && h->n_rows == bm_total_docs(ix),
               "bm25: a tenant filter needs rag_index_set_tenants_host and postings row-aligned with the index");
     *tenants_out = search_vis(h, tenant);
     return RAG_OK;
@@ -1298,9 +1639,9 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     if ((rc = bm25_set_attr(h))) return rc;
     hipStream_t st = h->stream;
     const int32_t* dense_vis = mode == 1 ? tenants : nullptr;          // bm25_scores_host: 0.0 for deleted rows
-    const int nr = ix->n_ranges;
+    const int nr = bm_total_ranges(ix);                               // partial lists: the base's ranges, then the tail's
     const size_t n_part = mode == 0 ? (size_t)Q * nr * k : 0, n_out = mode == 0 ? (size_t)Q * k : 0;
-    const size_t n_dense = mode == 1 ? (size_t)Q * ix->n_docs : 0;
+    const size_t n_dense = mode == 1 ? (size_t)Q * bm_total_docs(ix) : 0;
     {   // plan slots: the batch's longest query (term_ptr is on the host here), within the per-call budget
         int max_nt = 1;
         for (int q = 0; q < Q; ++q) max_nt = std::max(max_nt, term_ptr[q + 1] - term_ptr[q]);
@@ -1308,8 +1649,8 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     }
     size_t total = stage_size(Q + 1, 4) + stage_size(std::max(1, n_terms_q), 4) + stage_size(n_part, 8) + stage_size(n_part, 4) +
                    stage_size((size_t)Q * nr, 4) + 2 * stage_size(n_out, 8) + 2 * stage_size(n_out, 4) + 2 * stage_size(Q, 8) +
-                   stage_size(n_out, 8) + stage_size(n_dense, 8) + stage_size(bm25_plan_off_entries(ix, Q), 4) +
-                   stage_size((size_t)Q * BM_PLAN_T, sizeof(bm_plan_meta));
+                   stage_size(n_out, 8) + stage_size(n_dense, 8) + stage_size(bm25_plan_off_total(ix, Q), 4) +
+                   stage_size(bm25_plan_meta_total(ix, Q), sizeof(bm_plan_meta));
     if ((rc = stage_reserve(h, total))) return rc;
     char* p = h->stage;
     int32_t* tp = stage_take<int32_t>(p, Q + 1);
@@ -1326,12 +1667,12 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     double* mxd = stage_take<double>(p, Q);
     double* scd = stage_take<double>(p, n_out);
     double* dd = stage_take<double>(p, n_dense);
-    w.plan.off = stage_take<int32_t>(p, bm25_plan_off_entries(ix, Q));
-    w.plan.meta = stage_take<bm_plan_meta>(p, (size_t)Q * BM_PLAN_T);       // (sized for the largest plan_t)
+    w.plan.off = stage_take<int32_t>(p, bm25_plan_off_total(ix, Q));
+    w.plan.meta = stage_take<bm_plan_meta>(p, bm25_plan_meta_total(ix, Q));  // (sized for the largest plan_t)
     HIP_TRY(h, hipMemcpyAsync(tp, term_ptr, (size_t)(Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(tm, terms, (size_t)n_terms_q * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (mode == 0) {
-        const bool aligned = ix == h->bm25 && h->n_rows == ix->n_docs;
+        const bool aligned = ix == h->bm25 && h->n_rows == bm_total_docs(ix);
         const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, idd, rwd, scd, mxd,
                                  ix->normalize};
         bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, st);
@@ -1341,10 +1682,7 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
         HIP_TRY(h, hipMemcpyAsync(scores_out, scd, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
         if (raw_max_out) HIP_TRY(h, hipMemcpyAsync(raw_max_out, mxd, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
     } else {
-        bm25_launch_plan(ix, tp, tm, Q, w.plan, st);
-        BM_RANGE_LAUNCH(h, ix, nr, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, tp, tm, k, 1, dd, (uint64_t*)nullptr, (uint32_t*)nullptr, 0,
-                        (const uint64_t*)nullptr, (int*)nullptr, dense_vis, -1, (const int32_t*)w.plan.off,
-                        (const bm_plan_meta*)w.plan.meta)
+        bm25_launch_scores(h, ix, tp, tm, Q, dd, bm_dense_extra{nullptr, 0, nullptr}, dense_vis, -1, w.plan, st);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(dense_out, dd, n_dense * sizeof(double), hipMemcpyDeviceToHost, st));
     }
@@ -1354,8 +1692,8 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
 
 static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
     ix->plan_t = bm25_pick_plan_t(h, ix, Q);
-    if (int rc = ix->ws_plan_off.reserve(h, bm25_plan_off_entries(ix, Q))) return rc;
-    return ix->ws_plan_meta.reserve(h, (size_t)Q * BM_PLAN_T);
+    if (int rc = ix->ws_plan_off.reserve(h, bm25_plan_off_total(ix, Q))) return rc;
+    return ix->ws_plan_meta.reserve(h, bm25_plan_meta_total(ix, Q));
 }
 
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
@@ -1371,7 +1709,7 @@ int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_
     ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
     if (int rc = bm25_check_fresh(h, h->bm25)) return rc;
-    const size_t per_query = (size_t)h->bm25->n_ranges * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
+    const size_t per_query = (size_t)bm_total_ranges(h->bm25) * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
     const size_t budget = h->opt.bm25_ws_mb > 0 ? (size_t)h->opt.bm25_ws_mb << 20 : BM_WS_BUDGET;
     const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, budget / std::max<size_t>(1, per_query)));
     for (int q0 = 0; q0 < Q; q0 += qb) {
@@ -1394,16 +1732,17 @@ static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const in
     int rc = bm25_tenant_args(h, ix, tenant, &tenants);
     if (rc) return rc;
     if ((rc = bm25_set_attr(h))) return rc;
-    const size_t need = (size_t)Q * ix->n_ranges * k, need_run = (size_t)Q * k;
+    const int nr_all = bm_total_ranges(ix);
+    const size_t need = (size_t)Q * nr_all * k, need_run = (size_t)Q * k;
     if ((rc = ix->ws_key.reserve(h, need))) return rc;
     if ((rc = ix->ws_row.reserve(h, need))) return rc;
     if ((rc = ix->ws_tau.reserve(h, (size_t)Q))) return rc;
-    if ((rc = ix->ws_cnt.reserve(h, (size_t)Q * ix->n_ranges))) return rc;
+    if ((rc = ix->ws_cnt.reserve(h, (size_t)Q * nr_all))) return rc;
     if ((rc = ix->ws_run_key.reserve(h, need_run))) return rc;
     if ((rc = ix->ws_run_row.reserve(h, need_run))) return rc;
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
     // doc ids follow the dense index's mapping when both indexes cover the same rows (hybrid fusion needs one id space)
-    const bool aligned = h->n_rows == ix->n_docs;
+    const bool aligned = h->n_rows == bm_total_docs(ix);
     const bm25_topk_ws w = {ix->ws_key, ix->ws_row, ix->ws_cnt, ix->ws_run_key, ix->ws_run_row, ix->ws_tau, {ix->ws_plan_off, ix->ws_plan_meta}};
     const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, ids_dev, rows_dev, scores_dev,
                              raw_max_dev, ix->normalize};
@@ -1429,10 +1768,7 @@ int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* term
     const bm_dense_extra dx = {raw32_dev, ld, max_key_dev};
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
     const bm25_plan_ws pw = {ix->ws_plan_off, ix->ws_plan_meta};
-    bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, pw, st);
-    BM_RANGE_LAUNCH(h, ix, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, out_dev, (uint64_t*)nullptr,
-                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant,
-                    (const int32_t*)pw.off, (const bm_plan_meta*)pw.meta)
+    bm25_launch_scores(h, ix, term_ptr_dev, terms_dev, Q, out_dev, dx, tenants, tenant, pw, st);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -1443,7 +1779,7 @@ int bm25_set_normalize(rag_ctx* h, int on) {
     return RAG_OK;
 }
 
-int64_t bm25_n_docs(const rag_ctx* h) { return h->bm25 ? h->bm25->n_docs : -1; }
+int64_t bm25_n_docs(const rag_ctx* h) { return h->bm25 ? bm_total_docs(h->bm25) : -1; }
 
 // What bounds a NEGATIVE raw score from the query alone (linear_scale_kernel, the fused emission margin): a raw score is a sum over
 // the query's tokens of idf[t] * tf (k1+1) / (tf + k1 (1 - b + b dl / avgdl)), and the tf factor is at most k1 + 1 for k1 >= 0 and

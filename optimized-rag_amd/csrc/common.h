@@ -73,6 +73,7 @@ struct rag_options {
     int bm25_plan_slots = 0;      // planned token slots per query of a BM25 call (0 = sized by the per-call budget, bm25_pick_plan_t); tests force 8
     int bm25_ws_mb = 0;           // workspace budget of a device-pointer BM25 call in MiB (0 = 6 GiB): batches beyond it run in sub-batches
     int bm25_packed = 0;          // (read when postings are LOADED) 4-byte packed postings + shared impact table instead of (doc, impact)
+    int bm25_tail_fold = 0;       // appended postings: an append folds the tail into the base once it holds more than this many documents (-1 = never, 0 = the default policy, bm25.hip bm_default_fold_docs)
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
@@ -154,6 +155,7 @@ struct rag_ctx : rag_device_mem {
     int64_t n_deleted = 0;
     int64_t cap32 = 0, cap_ids = 0, cap_ten = 0, cap_tmp = 0, cap_vis = 0;
     bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
+    bool bm25_compacted = false; // ... and a compaction was among them: appended postings cannot align the rows again, only a reload
 
     // set by every *_dev entry, cleared by the device-wide wait a *_host entry then starts with (host_after_dev): a *_host
     // call behaves as if it ran after all *_dev work of the handle, on whatever stream that was queued

@@ -467,6 +467,7 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     h->cap_vis = 0;
     h->n_deleted = 0;
     h->bm25_stale = true;
+    h->bm25_compacted = true;
     live_rows_changed(h);
     if (ten) {                               // tenant tile lists of the new row numbers
         std::vector<int32_t> t((size_t)n_live);

@@ -2,7 +2,12 @@
 """Live-write costs on a 1M x 1536 index with tenants (rag_index_insert_host / _delete_host / _compact):
 single-row insert and single-id delete latency, dense top-k (Q = 256, k = 100) before and after deleting 10 % of the rows at
 random, and compaction at 10 % and 50 % deleted rows (bytes moved = rows after the first moved row x the bytes of every
-plane). Writes profiles/live_index_1M.json.  python tools/live_index_probe.py [--rows N] [--out PATH]"""
+plane). Writes profiles/live_index_1M.json.  python tools/live_index_probe.py [--rows N] [--out PATH]
+
+--bm25: appendable postings instead (rag_bm25_append_host / rag_bm25_fold) on the same index with the bench's synthetic text
+(bench_modes.synthetic_csr: Poisson(120) tokens per document, Zipf(1.1) over 100,000 terms): append time for blocks of 1 and
+1,000 rows, rag_bm25_topk_dev (Q = 256, k = 100) and rag_hybrid_rrf_dev (pool 100, k 20) with a tail of 0, 1 % and 5 % of the
+base, then the fold. Device-synchronised wall times, shapes warmed up. Writes profiles/live_bm25_1M.json."""
 import argparse
 import json
 import os
@@ -23,12 +28,93 @@ def med_ms(f, n):
     return float(np.median(t))
 
 
+def bm25_probe(a):
+    import torch
+    import bench_modes as BM
+    from optimized_rag_amd import RagEngine
+    from optimized_rag_amd.bm25 import Bm25Postings
+    N, D, V = a.rows, a.dim, 100_000
+    extra = N // 20 + 8192                                # the 5 % tail and the timed blocks behind it
+    rng = np.random.default_rng(0)
+    eng = RagEngine(dim=D, device=0)
+    eng.index_reserve(N + extra + 4096)
+    for b in range(0, N, 125_000):
+        eng.index_append(rng.standard_normal((min(125_000, N - b), D), dtype=np.float32))
+    indptr, doc, tf, dl, tok, doc_ptr = BM.synthetic_csr(N + extra, V, 120)
+    term_of = np.repeat(np.arange(V, dtype=np.int32), np.diff(indptr))
+    is_base = doc < N
+
+    def csr(mask, first):
+        ip = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(term_of[mask], minlength=V), out=ip[1:])
+        return ip, (doc[mask] - first).astype(np.int32), tf[mask]
+    ip0, d0, tf0 = csr(is_base, 0)
+    idf = Bm25Postings.idf_table(np.diff(ip0), N)
+    idf[np.diff(ip0) == 0] = 0.0
+    avgdl = float(dl[:N].sum()) / N
+    eng.set_option("bm25_tail_fold", -1)                  # the probe folds when it says so
+    eng.bm25_load(ip0, d0, tf0, dl[:N], idf, avgdl)
+    e_term, e_doc, e_tf = term_of[~is_base], doc[~is_base], tf[~is_base]
+    del term_of, is_base, ip0, d0, tf0
+    none = np.zeros(0, dtype=np.float64)
+
+    def grow(n):                                          # insert + append the next n documents; returns the append's seconds
+        first = eng.n_rows
+        m = (e_doc >= first) & (e_doc < first + n)
+        ip = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(e_term[m], minlength=V), out=ip[1:])
+        bd, bt, bl = (e_doc[m] - first).astype(np.int32), e_tf[m], dl[first:first + n]
+        eng.index_insert(rng.standard_normal((n, D), dtype=np.float32))
+        t0 = time.perf_counter()
+        eng.bm25_append(ip, bd, bt, bl, none, V)
+        return (time.perf_counter() - t0) * 1e3
+    Q = 256
+    ptr, terms = BM._term_queries(tok, doc_ptr, N, Q)
+    pd, td = torch.from_numpy(ptr).cuda(), torch.from_numpy(terms).cuda()
+    q = torch.from_numpy(rng.standard_normal((Q, D), dtype=np.float32)).cuda()
+    ids = torch.empty((Q, 100), dtype=torch.int64, device="cuda")
+    sc = torch.empty((Q, 100), dtype=torch.float64, device="cuda")
+
+    def searches():
+        return {"bm25_topk_dev_q256_k100_ms": BM._p50_ms(lambda: eng.bm25_topk_dev(pd, td, 100, ids, None, sc), 20, 5),
+                "hybrid_rrf_dev_q256_ms": BM._p50_ms(lambda: eng.hybrid_rrf_dev(q, pd, td, 100, 20), 20, 5)}
+    out = {"rows": N, "dim": D, "vocab": V, "mean_doc_len": 120, "base_nnz": int(eng.bm25_segment_stats()["base_nnz"]), "tails": {}}
+    for name, target in (("0", 0), ("1pct", N // 100), ("5pct", N // 20)):
+        have = eng.bm25_segment_stats()["tail_docs"]
+        if target > have:
+            grow(target - have)
+        st = eng.bm25_segment_stats()
+        rec = {"tail_docs": st["tail_docs"], "tail_nnz": st["tail_nnz"], "tail_bytes": st["tail_bytes"]}
+        rec.update(searches())
+        rec["append_1row_ms"] = float(np.median([grow(1) for _ in range(7)]))
+        rec["append_1000rows_ms"] = float(np.median([grow(1000) for _ in range(3)]))
+        out["tails"][name] = rec
+    st = eng.bm25_segment_stats()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.bm25_fold()
+    fold_ms = (time.perf_counter() - t0) * 1e3
+    nnz = st["base_nnz"] + st["tail_nnz"]
+    out["fold"] = {"tail_docs": st["tail_docs"], "tail_nnz": st["tail_nnz"], "ms": fold_ms,
+                   "bytes_moved": int(nnz * 12 * 2), "note": "every posting (doc int32 + impact float64) read once and written once; tables rebuilt"}
+    out["fold"]["tb_per_s"] = out["fold"]["bytes_moved"] / (fold_ms * 1e-3) / 1e12
+    out["after_fold"] = searches()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=1536)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "live_index_1M.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--bm25", action="store_true", help="probe the appendable postings instead (profiles/live_bm25_1M.json)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "live_bm25_1M.json" if a.bm25 else "live_index_1M.json")
+    if a.bm25:
+        return bm25_probe(a)
     from optimized_rag_amd import RagEngine
     N, D = a.rows, a.dim
     rng = np.random.default_rng(0)
