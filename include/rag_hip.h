@@ -28,8 +28,8 @@
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_bm25_load_host,
- *     rag_bm25_append_host, rag_bm25_fold, rag_index_load_host, rag_index_reserve, rag_ce_load_host, rag_embed_load_host, the
- *     live writes) returns the result
+ *     rag_bm25_append_host, rag_bm25_fold, rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
+ *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
  *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize and rag_set_option do not
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
  *     *_dev calls of one handle on SEVERAL streams stay unordered among themselves: that is the caller's to order.
@@ -122,8 +122,32 @@ int rag_index_rows(rag_handle_t h, int64_t* n_rows_out);
  *
  * Stale postings: BM25 and hybrid entry points return RAG_ERR_STATE while the postings do not describe the current rows
  * (deletes do not make them stale). After inserts, rag_bm25_append_host of the new rows' postings makes them current again -
- * once EVERY inserted row is covered; after a compaction only rag_bm25_load_host of postings aligned with the new row numbers
- * does. */
+ * once EVERY inserted row is covered; after a rag_index_compact only rag_bm25_load_host of postings aligned with the new row
+ * numbers does.
+ *
+ * rag_index_compact_bm25: rag_index_compact - the same arguments, the same effect on every row plane - that KEEPS the postings.
+ * When postings are loaded and were describing the rows (no rag_index_compact since their load), they are renumbered through
+ * the compaction's device row map and the postings of the deleted rows are dropped, base and tail both, before any row moves.
+ * Afterwards every BM25 and hybrid result is BIT-IDENTICAL to a fresh handle that holds the live rows in row order and was
+ * loaded with the compacted CSR (each term's surviving postings in order, renumbered), the same idf table (all terms known so
+ * far), avgdl, k1 and b - and to what this handle returned immediately before the call, rows mapped through row_map_out
+ * (deletes already hid the rows and froze the statistics). Term numbers never change; a term that loses every posting stays
+ * in the vocabulary with an empty list and its idf.
+ * Staleness is left as it was: postings that covered every row are current afterwards; if rows had been inserted but not yet
+ * appended, the covered rows are remapped and the postings stay stale until rag_bm25_append_host of the remaining rows, in
+ * their new order, covers them. After an earlier rag_index_compact (postings stale and compacted) the call behaves as
+ * rag_index_compact: only a reload helps. Without postings, or with nothing deleted, it IS rag_index_compact (identity map;
+ * postings, staleness and rag_bm25_segment_stats untouched).
+ * Representation: base and tail are remapped SEPARATELY by a stable stream compaction of each posting array (no fold is
+ * counted; `appends` survives): a bm25_packed base keeps its code bits and its table and gets new low document bits, the tail
+ * stays a tail behind the new base size. base_docs + tail_docs = live covered rows, base_nnz + tail_nnz = surviving postings.
+ * A tail without surviving rows is dropped; a base without surviving rows is replaced by the remapped tail (the (doc, impact)
+ * form); when NO covered row survives there is nothing to keep and the postings end as after rag_index_compact.
+ * Atomic: the new posting arrays, metadata and tables are allocated and built beside the old ones (the transient memory of
+ * rag_bm25_fold) before the first row moves, and swapped in at the end: RAG_ERR_NOMEM leaves rows and postings as they were
+ * (as in rag_index_compact, an index with implicit ids has had its ids plane written out by then: id = row, the same ids).
+ * Synchronous, takes the handle lock, waits for queued *_dev work like every live write. Cost: the postings streamed twice on
+ * the device; never a host rebuild or an upload of postings. */
 typedef struct rag_row_block {
     int64_t n;
     const float* emb;            /* [n][dim] */
@@ -136,6 +160,7 @@ typedef struct rag_row_block {
 int rag_index_insert_host(rag_handle_t h, const rag_row_block* rows, int64_t* first_row_out);
 int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int tenant, int64_t* n_deleted_out);
 int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
+int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
 int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out);
 /* copy rows' fp32 embeddings back (kills apply_mmr's per-doc re-embedding, rag/nodes/helpers.py:215-223) */
 int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, float* out_host);

@@ -70,6 +70,7 @@ _SIGS = {
     "rag_index_insert_host": ([_P, C.POINTER(RowBlock), C.POINTER(C.c_int64)], C.c_int),
     "rag_index_delete_host": ([_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_compact": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_compact_bm25": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_deleted_rows": ([_P, C.POINTER(C.c_int64)], C.c_int),
     "rag_dense_topk_host": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_dense_topk_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
@@ -330,14 +331,19 @@ class RagEngine:
         self._check(self.lib.rag_index_delete_host(self.h, _ptr(ids), ids.shape[0], int(tenant), C.byref(out)), "rag_index_delete_host")
         return int(out.value)
 
-    def index_compact(self):
-        """Remove deleted rows from every plane. Returns row_map (int64 [rows before]: new row or -1)."""
+    def index_compact(self, keep_postings=False):
+        """Remove deleted rows from every plane. Returns row_map (int64 [rows before]: new row or -1). keep_postings
+        (rag_index_compact_bm25): loaded BM25 postings are renumbered on the device and stay live; by default they end stale."""
         n = C.c_int64()
         self._check(self.lib.rag_index_rows(self.h, C.byref(n)), "rag_index_rows")
         row_map = np.empty(int(n.value), dtype=np.int64)
         after = C.c_int64()
-        self._check(self.lib.rag_index_compact(self.h, _ptr(row_map), C.byref(after)), "rag_index_compact")
+        name = "rag_index_compact_bm25" if keep_postings else "rag_index_compact"
+        self._check(getattr(self.lib, name)(self.h, _ptr(row_map), C.byref(after)), name)
         self.n_rows = int(after.value)
+        if keep_postings and hasattr(self, "bm25_docs"):             # the remap dropped documents: bm25_scores' width follows
+            s = self.bm25_segment_stats()
+            self.bm25_docs = s["base_docs"] + s["tail_docs"]
         return row_map
 
     def index_deleted_rows(self):

@@ -133,6 +133,29 @@ class Bm25Postings:
         engine.bm25_append(block["indptr"], block["doc"], block["tf"], block["doc_len"], block["idf_new"], block["n_terms_total"])
         return self
 
+    def compacted(self, row_map):
+        """The host mirror of `RagEngine.index_compact(keep_postings=True)` (rag_index_compact_bm25), in place: row_map[old
+        document] = its new number, or < 0 for a document that was deleted. Drops the postings and `doc_len` entries of the
+        deleted documents and renumbers the rest; term numbers, `vocab`, `idf` and `avgdl` stay (frozen statistics: a term that
+        loses every posting keeps its number and its idf, with an empty list). A compaction keeps the live rows in order, so the
+        live entries of the map must be exactly 0 .. n_live-1 ascending; anything else, or a map of another length than
+        `n_docs`, raises ValueError. Returns self."""
+        row_map = np.asarray(row_map, dtype=np.int64)
+        if row_map.shape != (self.n_docs,):
+            raise ValueError(f"compacted: row_map must have one entry per document ({self.n_docs}), got shape {row_map.shape}")
+        live = row_map >= 0
+        n_live = int(live.sum())
+        if not np.array_equal(row_map[live], np.arange(n_live, dtype=np.int64)):
+            raise ValueError("compacted: the live entries of row_map must be 0 .. n_live-1 in ascending order")
+        keep = live[self.doc]
+        before = np.zeros(keep.shape[0] + 1, dtype=np.int64)      # survivors before each posting: the new offsets, read at the old
+        np.cumsum(keep, out=before[1:])
+        self.indptr = before[self.indptr]
+        self.doc = row_map[self.doc[keep]].astype(np.int32)
+        self.tf = self.tf[keep]
+        self.doc_len = self.doc_len[live]
+        return self
+
     def refreshed(self, epsilon=None):
         """A new object over the same (merged) CSR with idf / avgdl recomputed: what `from_corpus` over all texts gives."""
         eps = self.epsilon if epsilon is None else epsilon

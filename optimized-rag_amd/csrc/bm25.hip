@@ -1365,7 +1365,8 @@ static int bm_alloc(rag_ctx* h, dev_buf<T>& buf, size_t n, const char* what) {
 
 // Term metadata + bracket-table plan of a segment whose offsets are ix->indptr_h (the host loop of bm25_build) -> ix->meta,
 // ix->range_tab (allocated, metadata uploaded; the table itself is filled by bm25_range_table_kernel once ix->doc is there)
-static int bm_plan_segment(rag_ctx* h, rag_bm25_index* ix, const std::vector<double>& idf, std::vector<bm_term_meta>& meta_h, const char* what) {
+static int bm_plan_segment(rag_ctx* h, rag_bm25_index* ix, const std::vector<double>& idf, std::vector<bm_term_meta>& meta_h, const char* what,
+                           bool with_w = true) {
     const int64_t n_pad = (int64_t)ix->n_ranges * BM_RANGE;
     meta_h.resize((size_t)std::max<int64_t>(1, ix->n_terms));
     int64_t n_tab = 0;
@@ -1381,13 +1382,14 @@ static int bm_plan_segment(rag_ctx* h, rag_bm25_index* ix, const std::vector<dou
     if ((rc = bm_alloc(h, ix->meta, meta_h.size(), what))) return rc;
     if ((rc = bm_alloc(h, ix->range_tab, (size_t)n_tab, what))) return rc;
     if ((rc = bm_alloc(h, ix->doc, (size_t)ix->nnz + 8, what))) return rc;
-    if ((rc = bm_alloc(h, ix->w, (size_t)ix->nnz + 8, what))) return rc;
+    if (with_w && (rc = bm_alloc(h, ix->w, (size_t)ix->nnz + 8, what))) return rc;
     return RAG_OK;
 }
 
-// Default of option bm25_tail_fold (0): the tail size, in documents, past which an append folds by itself. NOT MEASURED YET - a
-// guess until the numbers of profiles/live_bm25_1M.json say otherwise: the tail costs every search one more plan +
-// scoring + fold launch and every append a rebuild of the whole tail, the fold one pass over all postings.
+// Default of option bm25_tail_fold (0): the tail size, in documents, past which an append folds by itself. The tail costs every
+// search one more plan + scoring + fold launch and every append a rebuild of the whole tail, the fold one pass over all postings.
+// Measured at 1M documents (profiles/live_bm25_1M.json): a 5 % tail adds 0.1 ms to a 0.94 ms Q = 256 search and 1 ms
+// to an append, the fold takes 5 ms - all small, so the default stays where it was.
 static int64_t bm_default_fold_docs(int64_t base_docs) { return std::max<int64_t>(32 * BM_RANGE, base_docs / 16); }
 
 int bm25_fold(rag_ctx* h);
@@ -1571,6 +1573,240 @@ int bm25_fold(rag_ctx* h) {
     return RAG_OK;
 }
 
+// ---- postings through a compaction (rag_index_compact_bm25) ---------------------------------------------------------------
+// The compaction's row map is monotone on the live rows, so a STABLE stream compaction of a segment's whole posting array keeps
+// it term-major with ascending documents per term: postings of deleted rows drop out, the others get their new document number
+// and keep their impact (or the code bits of a packed posting). Three kernels over tiles of BM_CP_TILE consecutive postings; the
+// exclusive scan of the tile counts is a host round trip (4 B per 2048 postings), like the one of the rows' own tile counts.
+#define BM_CP_TILE 2048
+#define BM_CP_WORDS (BM_CP_TILE / 64)
+
+// keep pass: bit p of `mask` = posting p survives (its row has a new number); tile_cnt[tile] = survivors of the tile. `mask`
+// holds BM_CP_WORDS words for every tile, also the last, partial one.
+__global__ __launch_bounds__(256) void bm25_compact_keep_kernel(const int32_t* __restrict__ doc, int64_t nnz, const int64_t* __restrict__ row_map,
+                                                                 int64_t n_map, int64_t row0, unsigned long long* __restrict__ mask,
+                                                                 int* __restrict__ tile_cnt) {
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * BM_CP_TILE;
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < BM_CP_TILE / 256; ++j) {
+        const int64_t p = p0 + j * 256 + tid;
+        bool keep = false;
+        if (p < nnz) {
+            const int64_t r = row0 + doc[p];
+            keep = (uint64_t)r < (uint64_t)n_map && row_map[r] >= 0;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) {
+            mask[(p0 >> 6) + j * 4 + w] = m;
+            c += __popcll(m);
+        }
+    }
+    if (lane == 0) wsum[w] = c;
+    __syncthreads();
+    if (tid == 0) tile_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// new posting offsets, one thread per entry of indptr: survivors before posting indptr[t] = the tile's offset + the set bits of
+// the tile's mask words before it (at most BM_CP_WORDS words, not a walk over postings)
+__global__ void bm25_compact_indptr_kernel(const int64_t* __restrict__ indptr, int64_t n_entries, int64_t nnz, int64_t nnz_new,
+                                           const unsigned long long* __restrict__ mask, const int64_t* __restrict__ tile_off,
+                                           int64_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_entries) return;
+    const int64_t p = indptr[t];
+    if (p >= nnz) {
+        out[t] = nnz_new;
+        return;
+    }
+    const int64_t tile = p / BM_CP_TILE, word = p >> 6;
+    int64_t c = tile_off[tile];
+    for (int64_t i = tile * BM_CP_WORDS; i < word; ++i) c += __popcll(mask[i]);
+    out[t] = c + __popcll(mask[word] & ((1ull << (p & 63)) - 1ull));
+}
+
+// scatter pass: survivor p goes to tile_off[tile] + its rank inside the tile (set bits of the mask before it), renumbered into
+// the new segment (new local document = new row - new_row0). A tile's destinations are contiguous. PACKED: the 4-byte posting
+// keeps its code bits and gets the low bits of the new document number (a base: new_row0 = 0).
+template <bool PACKED>
+__global__ __launch_bounds__(256) void bm25_compact_scatter_kernel(const int32_t* __restrict__ doc, const double* __restrict__ w,
+                                                                    const uint32_t* __restrict__ packed, const int64_t* __restrict__ row_map,
+                                                                    int64_t row0, int64_t new_row0, const unsigned long long* __restrict__ mask,
+                                                                    const int64_t* __restrict__ tile_off, int32_t* __restrict__ doc_out,
+                                                                    double* __restrict__ w_out, uint32_t* __restrict__ packed_out) {
+    __shared__ int pre[BM_CP_WORDS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const unsigned long long* mw = mask + (int64_t)blockIdx.x * BM_CP_WORDS;
+    if (wv == 0) {                           // exclusive prefix of the words' survivor counts (32 words: half a wave)
+        const int c = lane < BM_CP_WORDS ? __popcll(mw[lane]) : 0;
+        int s = c;
+#pragma unroll
+        for (int d = 1; d < BM_CP_WORDS; d <<= 1) {
+            const int v = __shfl_up(s, d);
+            if (lane >= d) s += v;
+        }
+        if (lane < BM_CP_WORDS) pre[lane] = s - c;
+    }
+    __syncthreads();
+    const int64_t p0 = (int64_t)blockIdx.x * BM_CP_TILE, base = tile_off[blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < BM_CP_TILE / 256; ++j) {
+        const int k = j * 4 + wv;
+        const unsigned long long m = mw[k];
+        if (!((m >> lane) & 1ull)) continue;
+        const int64_t p = p0 + j * 256 + tid;
+        const int64_t dst = base + pre[k] + __popcll(m & ((1ull << lane) - 1ull));
+        const int32_t nd = (int32_t)(row_map[row0 + doc[p]] - new_row0);
+        doc_out[dst] = nd;
+        if (PACKED) packed_out[dst] = (packed[p] & ~(uint32_t)(BM_RANGE - 1)) | ((uint32_t)nd & (BM_RANGE - 1));
+        else w_out[dst] = w[p];
+    }
+}
+
+// One segment `os` -> `ns` (n_docs, n_ranges, row0, first set by the caller; built beside the old one, which is not touched):
+// row_map[os->row0 + local document] is the new row or -1, rows at or past n_map have no entry. Synchronous.
+static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index* ns, const std::vector<double>& idf,
+                            const int64_t* row_map, int64_t n_map, bool keep_indptr_d) {
+    const char* what = "compact_bm25";
+    const int64_t V = os->n_terms, nnz = os->nnz, tiles = (nnz + BM_CP_TILE - 1) / BM_CP_TILE;
+    const bool packed = os->packed != nullptr;
+    hipStream_t st = h->stream;
+    ns->n_terms = V;
+    ns->avgdl = os->avgdl; ns->k1 = os->k1; ns->b = os->b;
+    ns->indptr_h.assign((size_t)V + 1, 0);
+    dev_buf<unsigned long long> mask;
+    dev_buf<int> tile_cnt;
+    dev_buf<int64_t> tile_off, indptr_old, indptr_new;
+    std::vector<int> cnt((size_t)tiles);
+    std::vector<int64_t> off((size_t)tiles);
+    std::vector<bm_term_meta> meta_h;
+    int64_t nnz_new = 0;
+    auto enqueue = [&]() -> int {
+        int rc;
+        if (nnz > 0) {
+            if ((rc = bm_alloc(h, mask, (size_t)tiles * BM_CP_WORDS, what))) return rc;
+            if ((rc = bm_alloc(h, tile_cnt, (size_t)tiles, what))) return rc;
+            if ((rc = bm_alloc(h, tile_off, (size_t)tiles, what))) return rc;
+            if ((rc = bm_alloc(h, indptr_old, (size_t)V + 1, what))) return rc;
+            if ((rc = bm_alloc(h, indptr_new, (size_t)V + 1, what))) return rc;
+            hipLaunchKernelGGL(bm25_compact_keep_kernel, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), nnz, row_map, n_map, os->row0,
+                               mask.get(), tile_cnt.get());
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(cnt.data(), tile_cnt, (size_t)tiles * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            for (int64_t t = 0; t < tiles; ++t) {
+                off[(size_t)t] = nnz_new;
+                nnz_new += cnt[(size_t)t];
+            }
+            HIP_TRY(h, hipMemcpyAsync(tile_off, off.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(indptr_old, os->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(bm25_compact_indptr_kernel, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, st, indptr_old.get(), V + 1, nnz,
+                               nnz_new, mask.get(), tile_off.get(), indptr_new.get());
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(ns->indptr_h.data(), indptr_new, (size_t)(V + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+        }
+        ns->nnz = nnz_new;
+        if ((rc = bm_plan_segment(h, ns, idf, meta_h, what, !packed))) return rc;
+        HIP_TRY(h, hipMemsetAsync(ns->doc + nnz_new, 0, 8 * sizeof(int32_t), st));
+        if (packed) {                        // the code table is shared by every posting that survives: copied as it is
+            if ((rc = bm_alloc(h, ns->packed, (size_t)nnz_new + 8, what))) return rc;
+            if ((rc = bm_alloc(h, ns->gtab, os->gtab.size(), what))) return rc;
+            ns->n_codes = os->n_codes;
+            HIP_TRY(h, hipMemsetAsync(ns->packed + nnz_new, 0, 8 * sizeof(uint32_t), st));
+            HIP_TRY(h, hipMemcpyAsync(ns->gtab, os->gtab, os->gtab.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+        } else {
+            HIP_TRY(h, hipMemsetAsync(ns->w + nnz_new, 0, 8 * sizeof(double), st));
+        }
+        if (keep_indptr_d) {
+            if ((rc = bm_alloc(h, ns->indptr_d, (size_t)V + 1, what))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(ns->indptr_d, ns->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+        }
+        if (V) HIP_TRY(h, hipMemcpyAsync(ns->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
+        if (nnz > 0) {
+            if (packed)
+                hipLaunchKernelGGL(bm25_compact_scatter_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
+                                   os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
+                                   ns->packed.get());
+            else
+                hipLaunchKernelGGL(bm25_compact_scatter_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
+                                   os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
+                                   ns->packed.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (ns->tab_entries) {
+            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((ns->tab_entries + 255) / 256)), dim3(256), 0, st, ns->meta.get(),
+                               ns->doc.get(), V, ns->tab_entries, ns->range_tab.get());
+            HIP_TRY(h, hipGetLastError());
+        }
+        return RAG_OK;
+    };
+    const int rc = enqueue();
+    const hipError_t e2 = hipStreamSynchronize(st);          // also after a failure: the host arrays stay alive until read
+    if (rc) return rc;
+    if (e2 != hipSuccess) {
+        h->err = std::string(what) + ": " + hipGetErrorString(e2);
+        return RAG_ERR_HIP;
+    }
+    return RAG_OK;
+}
+
+int64_t bm25_base_docs(const rag_ctx* h) { return h->bm25 ? h->bm25->n_docs : 0; }
+int64_t bm25_covered_docs(const rag_ctx* h) { return h->bm25 ? bm_total_docs(h->bm25) : 0; }
+
+// The postings as they will be after the compaction whose device row map is `row_map` (entries for the covered rows), built
+// BESIDE the resident ones: *out is handed to bm25_compact_commit once the rows have moved, or to bm25_compact_discard.
+// base_live / covered_live = live rows among the base's rows / among all covered rows. Base and tail are remapped SEPARATELY (no
+// fold: a packed base cannot absorb its tail, and one rule serves both forms); the new tail hangs behind the new base exactly
+// as bm25_append_host would have put it (row0 = the base's last range, first = base documents in that range). A tail without
+// survivors is dropped; a base without survivors is replaced by the remapped tail (always the (doc, impact) form). *out stays
+// null when no covered row survives: there is nothing to keep, the caller falls back to the plain compaction.
+int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t base_live, int64_t covered_live, rag_bm25_index** out) {
+    *out = nullptr;
+    const rag_bm25_index* ix = h->bm25;
+    const rag_bm25_index* tl = ix->tail.get();
+    const int64_t n_map = bm_total_docs(ix), tail_live = covered_live - base_live;
+    if (covered_live <= 0) return RAG_OK;
+    auto shape = [](rag_bm25_index* s, int64_t prev_docs, int64_t docs) {
+        s->first = (int)(prev_docs % BM_RANGE);
+        s->row0 = prev_docs - s->first;
+        s->n_docs = s->first + docs;
+        s->n_ranges = (int)((s->n_docs + BM_RANGE - 1) / BM_RANGE);
+    };
+    std::unique_ptr<rag_bm25_index> nb(new rag_bm25_index());
+    int rc;
+    if (base_live > 0) {
+        shape(nb.get(), 0, base_live);
+        if ((rc = bm_remap_segment(h, ix, nb.get(), ix->idf_h, row_map, n_map, false))) return rc;
+        if (tl != nullptr && tail_live > 0) {
+            std::unique_ptr<rag_bm25_index> nt(new rag_bm25_index());
+            shape(nt.get(), base_live, tail_live);
+            if ((rc = bm_remap_segment(h, tl, nt.get(), ix->idf_h, row_map, n_map, true))) return rc;
+            nb->tail = std::move(nt);
+            nb->tail_docs = tail_live;
+        }
+    } else {
+        shape(nb.get(), 0, tail_live);
+        if ((rc = bm_remap_segment(h, tl, nb.get(), ix->idf_h, row_map, n_map, false))) return rc;
+    }
+    nb->idf_h = ix->idf_h;
+    nb->neg_idf_absmax = ix->neg_idf_absmax;
+    nb->normalize = ix->normalize;
+    nb->appends = ix->appends;
+    nb->folds = ix->folds;
+    *out = nb.release();
+    return RAG_OK;
+}
+
+void bm25_compact_discard(rag_bm25_index* nb) { delete nb; }
+
+void bm25_compact_commit(rag_ctx* h, rag_bm25_index* nb) {
+    delete h->bm25;                          // the old base, its tail and their workspaces
+    h->bm25 = nb;
+}
+
 int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
     ARG_CHECK(h, out != nullptr, "bm25_segment_stats: null output");
     if (!h->bm25) {
@@ -1599,7 +1835,8 @@ static int bm25_set_attr(rag_ctx* h) {
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
-// does not tell: i inserts then i compacted rows restore it): refuse until rag_bm25_load_host reloads them.
+// does not tell: i inserts then i compacted rows restore it): refuse until rag_bm25_append_host covers the inserted rows or
+// rag_bm25_load_host reloads them (rag_index_compact_bm25 renumbers them with the rows and leaves this flag as it was).
 static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
     if (ix != h->bm25 || !h->bm25_stale) return RAG_OK;
     h->err = "bm25: the postings are stale (rows were inserted or compacted since rag_bm25_load_host): reload postings aligned "

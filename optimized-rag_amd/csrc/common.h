@@ -329,6 +329,13 @@ int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t f
 int live_vis_rebuild(rag_ctx* h);
 int bm25_fresh(rag_ctx* h);            // RAG_ERR_STATE while the postings are stale (inserts / compaction since the last load)
 int live_vis_extend(rag_ctx* h, int64_t first_row, int64_t n);
+// postings through a compaction (rag_index_compact_bm25): built beside the resident ones from the device row map before any
+// row moves, swapped in (or dropped) afterwards
+int64_t bm25_base_docs(const rag_ctx* h);
+int64_t bm25_covered_docs(const rag_ctx* h);
+int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map_dev, int64_t base_live, int64_t covered_live, rag_bm25_index** out);
+void bm25_compact_commit(rag_ctx* h, rag_bm25_index* nb);
+void bm25_compact_discard(rag_bm25_index* nb);
 int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists, int64_t list_stride, int Q, int k,
                int64_t* ids_out, double* scores_out, hipStream_t st, int normalize = 0);
 int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev,

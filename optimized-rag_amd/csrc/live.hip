@@ -1,5 +1,5 @@
 // Live writes to the resident index (include/rag_hip.h: rag_index_insert_host, rag_index_delete_host, rag_index_compact,
-// rag_index_deleted_rows): the INSERT / DELETE the reference agent issues on almost every turn (database/operations.py:22-57,
+// rag_index_compact_bm25, rag_index_deleted_rows): the INSERT / DELETE the reference agent issues on almost every turn (database/operations.py:22-57,
 // 162-172; rag/document_store.py:343-390, 524-542) without reloading the index.
 //
 // Representation: a deleted row stays where it is and is marked RAG_DEAD_ROW in rag_ctx::vis (a copy of the tenant table, or
@@ -361,9 +361,10 @@ int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out) {
 
 #define LIVE_STAGING_BYTES ((size_t)1 << 30)       // bound of the compaction's device memory beyond the planes
 
-int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
-    if (!h) return RAG_ERR_ARG;
-    LOCK(h);
+// rag_index_compact (keep_postings = false: the postings end stale and compacted) and rag_index_compact_bm25 (true: loaded
+// postings that describe the rows are renumbered through the row map, beside the old ones, BEFORE the first row moves, and
+// swapped in once the rows have moved; bm25_stale is left as it was - current stays current, uncovered rows stay uncovered)
+static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, bool keep_postings) {
     int rc = live_begin(h);
     if (rc) return rc;
     const int64_t n0 = h->index_loaded ? h->n_rows : 0;
@@ -424,6 +425,30 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     e = hipMemcpyAsync(tile_off, off.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(e, "tile offsets");
     hipLaunchKernelGGL(live_row_map_kernel, dim3((unsigned)tiles), dim3(256), 0, st, h->vis, n0, tile_off, row_map, src_rows);
+    // the postings of the rows that stay, under their new numbers: everything allocated and built here, nothing replaced yet
+    struct new_postings {
+        rag_bm25_index* p = nullptr;
+        ~new_postings() { if (p) bm25_compact_discard(p); }
+    } np;
+    const int64_t covered = bm25_covered_docs(h);
+    if (keep_postings && h->bm25 && !h->bm25_compacted && covered <= n0) {
+        // live rows below row x: the scanned tile offsets + the live rows of x's own tile before it (at most 255 map entries)
+        auto live_below = [&](int64_t x, int64_t* out) -> int {
+            *out = n_live;
+            if (x >= n0) return RAG_OK;
+            const int64_t t0 = x / RAG_TILE * RAG_TILE;
+            int64_t part[RAG_TILE];
+            if (x > t0) HIP_TRY(h, hipMemcpyAsync(part, row_map + t0, (size_t)(x - t0) * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            *out = off[(size_t)(t0 / RAG_TILE)];
+            for (int64_t i = 0; i < x - t0; ++i) *out += part[i] >= 0;
+            return RAG_OK;
+        };
+        int64_t base_live = 0, covered_live = 0;
+        if ((rc = live_below(bm25_base_docs(h), &base_live))) return rc;
+        if ((rc = live_below(covered, &covered_live))) return rc;
+        if ((rc = bm25_compact_prepare(h, row_map, base_live, covered_live, &np.p))) return rc;
+    }
     // every plane, chunk by chunk of destination rows through the staging buffer
     struct plane { void* p; size_t row_bytes; };
     std::vector<plane> planes = {{h->emb32, (size_t)h->dim * 4}, {h->emb16, (size_t)h->dim_pad * 2}, {h->ids, 8}};
@@ -466,8 +491,13 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     h->vis.reset();
     h->cap_vis = 0;
     h->n_deleted = 0;
-    h->bm25_stale = true;
-    h->bm25_compacted = true;
+    if (np.p) {
+        bm25_compact_commit(h, np.p);
+        np.p = nullptr;
+    } else {
+        h->bm25_stale = true;
+        h->bm25_compacted = true;
+    }
     live_rows_changed(h);
     if (ten) {                               // tenant tile lists of the new row numbers
         std::vector<int32_t> t((size_t)n_live);
@@ -477,6 +507,18 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
     }
     if (n_rows_out) *n_rows_out = n_live;
     return RAG_OK;
+}
+
+int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return live_compact(h, row_map_out, n_rows_out, false);
+}
+
+int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return live_compact(h, row_map_out, n_rows_out, true);
 }
 
 }  // extern "C"

@@ -7,7 +7,12 @@ plane). Writes profiles/live_index_1M.json.  python tools/live_index_probe.py [-
 --bm25: appendable postings instead (rag_bm25_append_host / rag_bm25_fold) on the same index with the bench's synthetic text
 (bench_modes.synthetic_csr: Poisson(120) tokens per document, Zipf(1.1) over 100,000 terms): append time for blocks of 1 and
 1,000 rows, rag_bm25_topk_dev (Q = 256, k = 100) and rag_hybrid_rrf_dev (pool 100, k 20) with a tail of 0, 1 % and 5 % of the
-base, then the fold. Device-synchronised wall times, shapes warmed up. Writes profiles/live_bm25_1M.json."""
+base, then the fold. Device-synchronised wall times, shapes warmed up. Writes profiles/live_bm25_1M.json.
+Then compaction that keeps the postings (rag_index_compact_bm25), with and without a 5 % tail, at 10 % and at 50 % of the rows
+deleted, each run on a fresh PAIR of identical handles: one takes rag_index_compact, the other rag_index_compact_bm25 (the difference is the
+cost of the posting remap); the first then takes the path the new call replaces - Bm25Postings.compacted on the host +
+rag_bm25_load_host - and both are searched (the same CSR, remapped on the device against freshly loaded). --part append /
+compact runs one half and merges it into the file."""
 import argparse
 import json
 import os
@@ -28,6 +33,117 @@ def med_ms(f, n):
     return float(np.median(t))
 
 
+def compact_probe(a, data):
+    """Compaction with the postings kept, against the plain compaction + host rebuild + reload it replaces."""
+    import torch
+    import bench_modes as BM
+    from optimized_rag_amd import RagEngine
+    from optimized_rag_amd.bm25 import Bm25Postings
+    N, D, V = a.rows, a.dim, 100_000
+    indptr, doc, tf, dl, tok, doc_ptr = data
+    rng = np.random.default_rng(1)
+    block = rng.standard_normal((min(125_000, N), D), dtype=np.float32)      # the row values do not matter here: one block, repeated
+    term_of = np.repeat(np.arange(V, dtype=np.int32), np.diff(indptr))
+    Q = 256
+    ptr, terms = BM._term_queries(tok, doc_ptr, N, Q)
+    pd, td = torch.from_numpy(ptr).cuda(), torch.from_numpy(terms).cuda()
+    q = torch.from_numpy(rng.standard_normal((Q, D), dtype=np.float32)).cuda()
+    ids = torch.empty((Q, 100), dtype=torch.int64, device="cuda")
+    sc = torch.empty((Q, 100), dtype=torch.float64, device="cuda")
+
+    def csr(lo, hi):
+        m = (doc >= lo) & (doc < hi)
+        ip = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(term_of[m], minlength=V), out=ip[1:])
+        return ip, (doc[m] - lo).astype(np.int32), tf[m]
+    ip0, d0, tf0 = csr(0, N)
+    idf = Bm25Postings.idf_table(np.diff(ip0), N)
+    idf[np.diff(ip0) == 0] = 0.0
+    avgdl = float(dl[:N].sum()) / N
+
+    def build(n_tail):
+        eng = RagEngine(dim=D, device=0)
+        eng.index_reserve(N + n_tail + 4096)
+        for b in range(0, N, block.shape[0]):
+            eng.index_append(block[:min(block.shape[0], N - b)])
+        eng.set_option("bm25_tail_fold", -1)
+        eng.bm25_load(ip0, d0, tf0, dl[:N], idf, avgdl)
+        if n_tail:
+            eng.index_insert(block[:n_tail])
+            ipt, dt_, tft = csr(N, N + n_tail)
+            eng.bm25_append(ipt, dt_, tft, dl[N:N + n_tail], np.zeros(0, dtype=np.float64), V)
+        return eng
+
+    def searches(eng):
+        return {"bm25_topk_dev_q256_k100_ms": BM._p50_ms(lambda: eng.bm25_topk_dev(pd, td, 100, ids, None, sc), 20, 5),
+                "hybrid_rrf_dev_q256_ms": BM._p50_ms(lambda: eng.hybrid_rrf_dev(q, pd, td, 100, 20), 20, 5)}
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        return r, (time.perf_counter() - t0) * 1e3
+    out = {}
+    warm = RagEngine(dim=D, device=0)                            # both calls once on a small index: the timed ones start warm
+    warm.index_load(block[:8192])
+    ipw, dw, tfw = csr(0, 8192)
+    warm.bm25_load(ipw, dw, tfw, dl[:8192], idf, avgdl)
+    for keep_postings in (True, False):
+        warm.index_delete(np.arange(int(keep_postings), 4096, 2, dtype=np.int64))
+        warm.index_compact(keep_postings=keep_postings)
+    warm.close()
+    for tail_name, n_tail in (("no_tail", 0), ("tail_5pct", N // 20)):
+        n_all = N + n_tail
+        ipm, dm, tfm = csr(0, n_all)
+        for tag, frac in (("10pct", 0.1), ("50pct", 0.5)):      # a fresh pair per fraction: each run starts from the full index
+            plain, keep = build(n_tail), build(n_tail)
+            mirror = Bm25Postings(ipm.copy(), dm.copy(), tfm.copy(), dl[:n_all].copy(), idf, avgdl)
+            live_ids = np.arange(n_all, dtype=np.int64)          # implicit ids: id = row
+            victims = rng.permutation(live_ids)[: int(len(live_ids) * frac)]
+            for e in (plain, keep):
+                assert e.index_delete(victims) == len(victims)
+            s0 = keep.bm25_segment_stats()
+            row_map, plain_ms = timed(lambda: plain.index_compact())
+            row_map2, keep_ms = timed(lambda: keep.index_compact(keep_postings=True))
+            assert np.array_equal(row_map, row_map2)
+            s1 = keep.bm25_segment_stats()
+            _, host_ms = timed(lambda: mirror.compacted(row_map))
+            _, load_ms = timed(lambda: plain.bm25_load(mirror.indptr, mirror.doc, mirror.tf, mirror.doc_len, idf, avgdl))
+            live_ids = live_ids[row_map >= 0]
+            nnz0, nnz1 = s0["base_nnz"] + s0["tail_nnz"], s1["base_nnz"] + s1["tail_nnz"]
+            assert nnz1 == int(mirror.indptr[-1]) and s1["base_docs"] + s1["tail_docs"] == len(live_ids)
+            # keep pass: doc ids read, 1 bit per posting written; scatter pass: doc ids + impacts read, survivors written
+            nbytes = nnz0 * 4 + nnz0 // 8 + nnz0 // 8 + nnz0 * 12 + nnz1 * 12
+            remap_ms = keep_ms - plain_ms
+            out[f"{tail_name}_{tag}"] = {
+                "rows_before": int(len(row_map)), "rows_after": int(len(live_ids)), "postings_before": int(nnz0), "postings_after": int(nnz1),
+                "segments_after": {k: s1[k] for k in ("base_docs", "tail_docs", "base_nnz", "tail_nnz", "appends", "folds")},
+                "index_compact_ms": plain_ms, "index_compact_bm25_ms": keep_ms, "remap_ms": remap_ms,
+                "remap_bytes": int(nbytes), "remap_gb_per_s": nbytes / (remap_ms * 1e-3) / 1e9 if remap_ms > 0 else None,
+                "host_compacted_ms": host_ms, "bm25_load_host_ms": load_ms, "reload_path_ms": host_ms + load_ms,
+                "reload_over_remap": (host_ms + load_ms) / remap_ms if remap_ms > 0 else None,
+                "search_after_remap": searches(keep), "search_after_reload": searches(plain)}
+            print(tail_name, tag, json.dumps(out[f"{tail_name}_{tag}"]), flush=True)
+            plain.close()
+            keep.close()
+    out["note"] = ("remap_ms = rag_index_compact_bm25 - rag_index_compact on identical handles; remap_bytes = the posting arrays streamed "
+                   "by the keep and scatter passes (row-map gathers, offsets and table rebuild not counted); reload_path = "
+                   "Bm25Postings.compacted on the host + rag_bm25_load_host, which replaces a tail by one base")
+    return out
+
+
+def write_out(a, part):
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out.update(part)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(part))
+
+
 def bm25_probe(a):
     import torch
     import bench_modes as BM
@@ -35,12 +151,16 @@ def bm25_probe(a):
     from optimized_rag_amd.bm25 import Bm25Postings
     N, D, V = a.rows, a.dim, 100_000
     extra = N // 20 + 8192                                # the 5 % tail and the timed blocks behind it
+    indptr, doc, tf, dl, tok, doc_ptr = BM.synthetic_csr(N + extra, V, 120)
+    if a.part in ("all", "compact"):
+        write_out(a, {"compaction": compact_probe(a, (indptr, doc, tf, dl, tok, doc_ptr))})
+    if a.part == "compact":
+        return
     rng = np.random.default_rng(0)
     eng = RagEngine(dim=D, device=0)
     eng.index_reserve(N + extra + 4096)
     for b in range(0, N, 125_000):
         eng.index_append(rng.standard_normal((min(125_000, N - b), D), dtype=np.float32))
-    indptr, doc, tf, dl, tok, doc_ptr = BM.synthetic_csr(N + extra, V, 120)
     term_of = np.repeat(np.arange(V, dtype=np.int32), np.diff(indptr))
     is_base = doc < N
 
@@ -99,10 +219,7 @@ def bm25_probe(a):
                    "bytes_moved": int(nnz * 12 * 2), "note": "every posting (doc int32 + impact float64) read once and written once; tables rebuilt"}
     out["fold"]["tb_per_s"] = out["fold"]["bytes_moved"] / (fold_ms * 1e-3) / 1e12
     out["after_fold"] = searches()
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    write_out(a, out)
 
 
 def main():
@@ -111,6 +228,8 @@ def main():
     ap.add_argument("--dim", type=int, default=1536)
     ap.add_argument("--out", default=None)
     ap.add_argument("--bm25", action="store_true", help="probe the appendable postings instead (profiles/live_bm25_1M.json)")
+    ap.add_argument("--part", choices=("all", "append", "compact"), default="all",
+                    help="with --bm25: the append / fold runs, the compaction runs, or both (merged into the output file)")
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "live_bm25_1M.json" if a.bm25 else "live_index_1M.json")
     if a.bm25:
