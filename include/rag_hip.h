@@ -28,7 +28,8 @@
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_bm25_load_host,
- *     rag_bm25_append_host, rag_bm25_fold, rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
+ *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
+ *     rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
  *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize and rag_set_option do not
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
@@ -64,7 +65,7 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, ce_chunk_tokens, ce_mx. Unknown name: RAG_ERR_ARG. */
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, ce_chunk_tokens, ce_mx. Unknown name: RAG_ERR_ARG. */
 int rag_set_option(rag_handle_t h, const char* name, int value);
 
 /* ---- dense index: replaces the pgvector tables behind
@@ -293,7 +294,7 @@ int rag_bm25_load_host(rag_handle_t h, const int64_t* indptr_host /*V+1*/, const
  * rag_bm25_append_host takes the postings of the NEXT n_docs_new rows after the rows the resident postings cover: a term-major
  * CSR over the handle's vocabulary (indptr[n_terms_total + 1], docs ascending per term and RELATIVE to the block's first row,
  * doc_len[n_docs_new]). Term numbers at or above the number of terms known so far are new terms; idf_new[n_terms_total - known]
- * are their idf values; n_terms_total may not shrink. STATISTICS ARE FROZEN at the last rag_bm25_load_host: avgdl, k1, b and the
+ * are their idf values; n_terms_total may not shrink. STATISTICS ARE FROZEN at the last rag_bm25_load_host (or rag_bm25_refresh, below): avgdl, k1, b and the
  * idf of every known term keep their loaded values (the rule deletes follow), a new term keeps the idf it arrived with; a caller
  * who wants fresh statistics reloads. After any sequence of appends every BM25 and hybrid result is BIT-IDENTICAL to a fresh
  * handle that holds the same rows and was loaded with the merged CSR (all rows; each term's list = its old list followed by the
@@ -319,6 +320,44 @@ int rag_bm25_append_host(rag_handle_t h, const int64_t* indptr_host /*n_terms_to
                          int64_t n_terms_total);
 int rag_bm25_fold(rag_handle_t h);
 int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out);
+/* ---- statistics refresh: fresh idf / avgdl computed from, and written into, the RESIDENT postings. The reference builds a new
+ * BM25Okapi over the corpus it has on every call (rag/retrieval.py:333-341); appends, deletes and compactions keep the
+ * statistics of the last load instead, so an index that has doubled or lost a tenant ranks by numbers no rebuild would give.
+ * Nothing larger than the per-term tables crosses PCIe.
+ * Opt-in: option bm25_keep_tf (read by rag_bm25_load_host; default 0 = nothing below is kept and all three calls return
+ * RAG_ERR_STATE). With it an unpacked base and the tail keep a uint16 term-frequency plane beside their (doc, impact) planes
+ * (+2 B per posting; a term frequency above 65535 is RAG_ERR_ARG at load / append, the call changes nothing), every segment the
+ * int32 length of its documents (+4 B per document), a bm25_packed base its two value tables (a few KB). Append, fold and
+ * rag_index_compact_bm25 move these with the postings, through the same kernels and with the same atomicity. Search results
+ * with the option set are bit-identical to the option off until a refresh runs.
+ * rag_bm25_live_counts_host: counts over the LIVE covered documents (covered by the postings and not deleted - the predicate
+ * every search applies; a standalone BM25 handle has no deleted rows): df_out[n_terms] (int32) = live postings of each term,
+ * base and tail together (n_terms as rag_bm25_segment_stats reports it), the live documents N and the exact sum of their
+ * lengths. Any output may be NULL. No live document is not an error here (all zero).
+ * rag_bm25_set_statistics_host: installs idf[n_terms] and avgdl: every impact of base and tail is recomputed from the kept
+ * tf / doc_len by the arithmetic of the load (a packed base: its impact table), and the per-term idf, avgdl and the
+ * negative-idf bound of the linear fusion follow. Afterwards every BM25 and hybrid result is BIT-IDENTICAL to a fresh handle
+ * that holds the same rows with the same deletes and was loaded with the merged CSR, this idf, this avgdl and the same k1, b.
+ * Offsets, bracket tables and the order of the postings are untouched; postings of deleted rows are rewritten like the rest and
+ * stay hidden. Later appends, folds and compactions keep their contracts with "frozen" meaning "as of the last load or refresh".
+ * rag_bm25_refresh: both, with the idf rule of rank-bm25 0.2.2 in between, on the host in float64 with libm's log (the table is
+ * bit-equal to Python's math.log arithmetic): for every term with df >= 1, ln(N - df + 0.5) - ln(df + 0.5); mean = their
+ * left-to-right sum in term-number order over their count (negative values included); every negative value becomes
+ * epsilon * mean. A term with df = 0 (it lost every posting to deletes) keeps its number, gets ln(N + 0.5) - ln(0.5) and
+ * stays out of the mean (rank-bm25 would not know it). avgdl = sum of the live lengths / N. idf_out[n_terms] and info_out may be
+ * NULL. The two halves exist on their own for row-sharded indexes (each rank counts, the sums are installed on every rank) and
+ * for callers with another idf rule.
+ * All three are synchronous, take the handle lock and wait for queued *_dev work like every host write. RAG_ERR_STATE: no
+ * postings, postings loaded without bm25_keep_tf, stale postings, (refresh) no live covered document. RAG_ERR_ARG: a non-finite
+ * epsilon, avgdl <= 0 or not finite, a non-finite idf. RAG_ERR_NOMEM: the scratch (df + idf, 12 B per term) cannot be had - it is
+ * allocated before the first impact is overwritten. Any error return leaves postings and statistics as they were. */
+typedef struct rag_bm25_refresh_info {
+    int64_t n_docs_live, nnz_live, n_terms, terms_without_postings, negative_idf_terms;
+    double avgdl_before, avgdl_after, idf_max_abs_change;
+} rag_bm25_refresh_info;
+int rag_bm25_live_counts_host(rag_handle_t h, int32_t* df_out_host /*n_terms*/, int64_t* n_docs_live_out, int64_t* sum_doc_len_out);
+int rag_bm25_set_statistics_host(rag_handle_t h, const double* idf_host /*n_terms*/, double avgdl);
+int rag_bm25_refresh(rag_handle_t h, double epsilon, double* idf_out_host /*n_terms*/, rag_bm25_refresh_info* info_out);
 /* HBM bytes rag_bm25_load_host will take for a CSR with these offsets, computed on the host from indptr alone (no GPU call):
  * postings (doc id + float64 impact, 12 B each; 8 B with option bm25_packed: the impact is then idf * g[code of the posting's
  * (term frequency, document length) pair] - bit-identical, less HBM, a slower scoring loop), per-term metadata (32 B each) and
@@ -327,6 +366,7 @@ int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out);
  * frequency, so table bytes <= postings/12 for ANY vocabulary - the reference tokeniser (`doc.lower().split()`,
  * rag/retrieval.py:334-335) produces millions of distinct terms on a large shard. Lets a loader budget a shard before
  * uploading it. Any of the outputs may be NULL. */
+/* (Option bm25_keep_tf is not counted here: it adds 2 B per posting - none for a bm25_packed base - and 4 B per document.) */
 int rag_bm25_index_bytes(const int64_t* indptr_host, int64_t n_docs, int64_t n_terms, int64_t* postings_bytes_out,
                          int64_t* meta_bytes_out, int64_t* table_bytes_out);
 /* Launch geometry of ONE scoring launch over `n_ranges_in_launch` 2048-document ranges and `n_queries` queries (host-only, no GPU

@@ -40,6 +40,11 @@ class Bm25Segments(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("base_docs", "tail_docs", "base_nnz", "tail_nnz", "n_terms", "tail_bytes", "appends", "folds")]
 
 
+class Bm25RefreshInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_docs_live", "nnz_live", "n_terms", "terms_without_postings", "negative_idf_terms")] + \
+               [(k, C.c_double) for k in ("avgdl_before", "avgdl_after", "idf_max_abs_change")]
+
+
 class CeConfig(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("ffn", C.c_int32), ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("reserved", C.c_int32),
@@ -90,6 +95,9 @@ _SIGS = {
     "rag_bm25_append_host": ([_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
     "rag_bm25_fold": ([_P], C.c_int),
     "rag_bm25_segment_stats": ([_P, C.POINTER(Bm25Segments)], C.c_int),
+    "rag_bm25_live_counts_host": ([_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+    "rag_bm25_set_statistics_host": ([_P, _P, C.c_double], C.c_int),
+    "rag_bm25_refresh": ([_P, C.c_double, _P, C.POINTER(Bm25RefreshInfo)], C.c_int),
     "rag_bm25_topk_host": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_bm25_scores_host": ([_P, _P, _P, C.c_int, _P], C.c_int),
     "rag_bm25_scores_adhoc_host": ([_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P,
@@ -555,6 +563,31 @@ class RagEngine:
         out = Bm25Segments()
         self._check(self.lib.rag_bm25_segment_stats(self.h, C.byref(out)), "rag_bm25_segment_stats")
         return {k: int(getattr(out, k)) for k, _ in out._fields_}
+
+    # ---- statistics refresh (include/rag_hip.h rag_bm25_refresh; needs set_option("bm25_keep_tf", 1) before bm25_load) ------
+    def bm25_live_counts(self):
+        """(df int32 [n_terms], live documents, sum of their lengths) over the covered documents that are not deleted."""
+        V = self.bm25_segment_stats()["n_terms"]
+        df = np.zeros(V, dtype=np.int32)
+        n, s = C.c_int64(), C.c_int64()
+        self._check(self.lib.rag_bm25_live_counts_host(self.h, _ptr(df), C.byref(n), C.byref(s)), "rag_bm25_live_counts_host")
+        return df, int(n.value), int(s.value)
+
+    def bm25_set_statistics(self, idf, avgdl):
+        """Install idf [n_terms] / avgdl: every impact of the resident postings is recomputed on the device."""
+        idf = _np(idf, np.float64)
+        V = self.bm25_segment_stats()["n_terms"]
+        if idf.shape != (V,):
+            raise RagError(f"bm25_set_statistics: idf must have one entry per known term ({V}), got shape {idf.shape}")
+        self._check(self.lib.rag_bm25_set_statistics_host(self.h, _ptr(idf), float(avgdl)), "rag_bm25_set_statistics_host")
+
+    def bm25_refresh(self, epsilon=0.25):
+        """Recompute idf / avgdl over the live documents (rank-bm25's rule) and rewrite the impacts in place -> (idf, info)."""
+        V = self.bm25_segment_stats()["n_terms"]
+        idf = np.zeros(V, dtype=np.float64)
+        info = Bm25RefreshInfo()
+        self._check(self.lib.rag_bm25_refresh(self.h, float(epsilon), _ptr(idf), C.byref(info)), "rag_bm25_refresh")
+        return idf, {k: getattr(info, k) for k, _ in info._fields_}
 
     def bm25_topk(self, term_ptr, terms, k, tenant=-1):
         term_ptr = _np(term_ptr, np.int32)

@@ -165,6 +165,41 @@ class Bm25Postings:
         return Bm25Postings(self.indptr.copy(), self.doc.copy(), self.tf.copy(), self.doc_len.copy(), idf, avgdl, dict(self.vocab) if self.vocab is not None else None,
                             self.k1, self.b, eps)
 
+    def refresh(self, live=None):
+        """The host mirror of rag_bm25_refresh, in place: idf / avgdl over the documents where `live` is true (all by default),
+        term numbers unchanged. For every term with df >= 1, ln(N - df + 0.5) - ln(df + 0.5) (`math.log`); mean = their
+        left-to-right float64 sum in term-number order over their count, negative values included; every negative value becomes
+        epsilon * mean. A term that lost every posting keeps its number, gets ln(N + 0.5) - ln(0.5) and stays out of the mean.
+        This is `idf_table` restricted to the terms that still occur. `_frozen_mean` becomes the new mean, so a later `extend`
+        floors the negative idf of a new term by it. Returns self."""
+        n_all = self.n_docs
+        live = np.ones(n_all, dtype=bool) if live is None else np.asarray(live, dtype=bool)
+        if live.shape != (n_all,):
+            raise ValueError(f"refresh: live must have one entry per document ({n_all}), got shape {live.shape}")
+        n = int(live.sum())
+        if n == 0:
+            raise ValueError("refresh: no live document")
+        V = self.indptr.shape[0] - 1
+        term_of = np.repeat(np.arange(V, dtype=np.int64), np.diff(self.indptr))
+        df = np.bincount(term_of[live[self.doc]], minlength=V).astype(np.int64)
+        occ = df > 0
+        udf, inv = np.unique(df, return_inverse=True)
+        idf = np.array([math.log(n - int(d) + 0.5) - math.log(int(d) + 0.5) for d in udf], dtype=np.float64)[inv]
+        mean = float(np.cumsum(idf[occ])[-1]) / int(occ.sum()) if occ.any() else 0.0
+        self.idf = np.where(occ & (idf < 0), self.epsilon * mean, idf)
+        self.avgdl = int(self.doc_len[live].sum()) / n
+        self._frozen_mean = mean
+        return self
+
+    def refresh_on(self, engine, live=None):
+        """`RagEngine.bm25_refresh` on the device and `refresh` on this mirror; the two idf tables must agree bit for bit.
+        `live`: the documents the engine has not deleted (the mirror does not know the engine's deletes). Returns self."""
+        idf, info = engine.bm25_refresh(self.epsilon)
+        self.refresh(live)
+        if not (np.array_equal(idf.view(np.int64), self.idf.view(np.int64)) and info["avgdl_after"] == self.avgdl):
+            raise AssertionError("refresh_on: the engine's statistics differ from the host mirror's")
+        return self
+
     def drift(self):
         """How far the frozen statistics are from what a rebuild would compute: lets a caller decide when to reload."""
         fresh = self.refreshed()

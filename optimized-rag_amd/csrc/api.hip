@@ -23,6 +23,9 @@ int64_t bm25_n_docs(const rag_ctx* h);
 int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                      const double* idf_new, int64_t n_new, int64_t n_terms_total);
 int bm25_fold(rag_ctx* h);
+int bm25_live_counts_host(rag_ctx* h, int32_t* df_out, int64_t* n_docs_live_out, int64_t* sum_doc_len_out);
+int bm25_set_statistics_host(rag_ctx* h, const double* idf, double avgdl);
+int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_info* info_out);
 int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
 int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
@@ -71,7 +74,7 @@ static const struct { const char* name; int rag_options::*field; } g_options[] =
     {"dense_linear_order", &rag_options::dense_linear_order}, {"dense_persist", &rag_options::dense_persist},
     {"bm25_first_ranges", &rag_options::bm25_first_ranges}, {"bm25_no_staging", &rag_options::bm25_no_staging},
     {"bm25_packed", &rag_options::bm25_packed},         {"bm25_plan_slots", &rag_options::bm25_plan_slots},       {"bm25_ws_mb", &rag_options::bm25_ws_mb},
-    {"bm25_tail_fold", &rag_options::bm25_tail_fold},
+    {"bm25_tail_fold", &rag_options::bm25_tail_fold},     {"bm25_keep_tf", &rag_options::bm25_keep_tf},
     {"bm25_linear_grid", &rag_options::bm25_linear_grid},            {"bm25_sort_merge", &rag_options::bm25_sort_merge},
     {"no_fork", &rag_options::no_fork},                 {"fork_max_q", &rag_options::fork_max_q},
     {"ce_chunk_tokens", &rag_options::ce_chunk_tokens}, {"ce_mx", &rag_options::ce_mx},
@@ -508,6 +511,27 @@ int rag_bm25_fold(rag_handle_t h) {
     LOCK(h);
     HOST_ENTRY(h);
     return bm25_fold(h);
+}
+
+int rag_bm25_live_counts_host(rag_handle_t h, int32_t* df_out_host, int64_t* n_docs_live_out, int64_t* sum_doc_len_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return bm25_live_counts_host(h, df_out_host, n_docs_live_out, sum_doc_len_out);
+}
+
+int rag_bm25_set_statistics_host(rag_handle_t h, const double* idf_host, double avgdl) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return bm25_set_statistics_host(h, idf_host, avgdl);
+}
+
+int rag_bm25_refresh(rag_handle_t h, double epsilon, double* idf_out_host, rag_bm25_refresh_info* info_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return bm25_refresh(h, epsilon, idf_out_host, info_out);
 }
 
 int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out) {

@@ -27,6 +27,8 @@
 //            as the fallback when more than k survive). Then a per-query merge of the partial lists.
 #include "common.h"
 
+#include <cmath>
+#include <cstring>
 #include <memory>
 
 typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));          // posting segments start at any posting
@@ -105,9 +107,27 @@ struct rag_bm25_index {
     dev_buf<int64_t> indptr_d;         // tail: the offsets on the device (source of the next append / the fold)
     int64_t row0 = 0;                  // tail: index row of its local document 0
     int first = 0;                     // tail: local documents below this are the base's
+    // ---- what a statistics refresh needs (option bm25_keep_tf at load time; rag_bm25_refresh). Each segment keeps the length
+    // of its documents, an unpacked segment the term frequency of every posting beside `doc` / `w`, a packed base the two value
+    // tables its impact table is built from. Every operation that moves postings (append, fold, compaction) moves these along.
+    bool keep_tf = false;
+    dev_buf<uint16_t> tf16;            // [nnz] parallel to doc / w (unpacked segments)
+    dev_buf<int32_t> dl;               // [n_docs] length of local document d (a tail's entries below `first` are unused, 0)
+    dev_buf<double> tfv, dlv;          // packed base: distinct term frequencies / document lengths (gtab = their product table)
+    uint32_t n_dl = 0;                 // packed base: entries of dlv
 };
 static inline int64_t bm_total_docs(const rag_bm25_index* ix) { return ix->n_docs + ix->tail_docs; }
 static inline int bm_total_ranges(const rag_bm25_index* ix) { return ix->n_ranges + (ix->tail ? ix->tail->n_ranges : 0); }
+
+// q_freq * (k1 + 1) / (q_freq + k1 * (1 - b + b * doc_len / avgdl))   -- same association as rank-bm25. The ONE place this is
+// written: the load, the packed table and the statistics refresh all call it, so their impacts agree bit for bit.
+__device__ __forceinline__ double bm_tf_factor(double f, double dl, double avgdl, double k1, double b) {
+    const double num = f * (k1 + 1.0);
+    const double t1 = (b * dl) / avgdl;
+    const double t2 = (1.0 - b) + t1;
+    const double den = f + k1 * t2;
+    return num / den;
+}
 
 __global__ void bm25_weights_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc,
                                     const int32_t* __restrict__ tf, const int32_t* __restrict__ doc_len, int64_t nnz,
@@ -123,14 +143,9 @@ __global__ void bm25_weights_kernel(const int64_t* __restrict__ indptr, const in
     }
     const double f = (double)tf[p];
     const double dl = (double)doc_len[doc[p]];
-    // q_freq * (k1 + 1) / (q_freq + k1 * (1 - b + b * doc_len / avgdl))   -- same association as rank-bm25
-    const double num = f * (k1 + 1.0);
-    const double t1 = (b * dl) / avgdl;
-    const double t2 = (1.0 - b) + t1;
-    const double den = f + k1 * t2;
     // the impact is stored already multiplied by the term's idf: `idf * (...)` is the product rank-bm25 adds to the score, so
     // the scoring loop is a pure load + add (one float64 multiply and one LDS lookup fewer per posting)
-    w[p] = idf[lo] * (num / den);
+    w[p] = idf[lo] * bm_tf_factor(f, dl, avgdl, k1, b);
 }
 
 // packed postings (see rag_bm25_index): one thread per posting
@@ -148,12 +163,7 @@ __global__ void bm25_gtab_kernel(const double* __restrict__ tf_values, const dou
                                  double avgdl, double k1, double b, double* __restrict__ gtab) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_codes) return;
-    const double f = tf_values[c / n_dl], dl = dl_values[c % n_dl];
-    const double num = f * (k1 + 1.0);
-    const double t1 = (b * dl) / avgdl;
-    const double t2 = (1.0 - b) + t1;
-    const double den = f + k1 * t2;
-    gtab[c] = num / den;
+    gtab[c] = bm_tf_factor(tf_values[c / n_dl], dl_values[c % n_dl], avgdl, k1, b);
 }
 
 __device__ __forceinline__ int64_t lower_bound_doc(const int32_t* __restrict__ doc, int64_t lo, int64_t hi, int target) {
@@ -1174,6 +1184,21 @@ static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const i
     bm25_launch_merge(h, w, t_key, t_row, t_cnt, tl->n_ranges, 0, tl->n_ranges, Q, k, 0, 1, o, st);
 }
 
+// the kept term-frequency plane (option bm25_keep_tf): the int32 frequencies of a load / an appended block as uint16
+__global__ void bm25_tf16_kernel(const int32_t* __restrict__ tf, int64_t nnz, uint16_t* __restrict__ tf16) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < nnz) tf16[p] = (uint16_t)tf[p];
+}
+// a term frequency the uint16 plane cannot hold: RAG_ERR_ARG before anything is built
+static int bm_check_tf16(rag_ctx* h, const int32_t* tf, int64_t nnz, const char* what) {
+    for (int64_t p = 0; p < nnz; ++p)
+        if (tf[p] < 0 || tf[p] > 65535) {
+            h->err = std::string("bad argument: ") + what + ": a term frequency above 65535 does not fit the kept tf plane (option bm25_keep_tf)";
+            return RAG_ERR_ARG;
+        }
+    return RAG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 void bm25_free(rag_ctx* h) {
     delete h->bm25;
@@ -1183,12 +1208,15 @@ void bm25_free(rag_ctx* h) {
 // host CSR -> device index (impacts + range table). Synchronous. *out receives the index on success only.
 static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                       const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
-                      std::unique_ptr<rag_bm25_index>* out) {
+                      std::unique_ptr<rag_bm25_index>* out, bool keep_tf = false) {
     ARG_CHECK(h, n_docs > 0 && n_terms >= 0 && n_docs < 0x7fffffff, "bm25_load: bad sizes");
     ARG_CHECK(h, indptr && doc_len && (n_terms == 0 || idf), "bm25_load: null pointer");
     const int64_t nnz = n_terms ? indptr[n_terms] : 0;
     ARG_CHECK(h, nnz == 0 || (doc && tf), "bm25_load: null postings");
+    if (keep_tf)
+        if (int rc = bm_check_tf16(h, tf, nnz, "bm25_load")) return rc;
     std::unique_ptr<rag_bm25_index> ix(new rag_bm25_index());
+    ix->keep_tf = keep_tf;
     ix->n_docs = n_docs; ix->n_terms = n_terms; ix->nnz = nnz; ix->avgdl = avgdl; ix->k1 = k1; ix->b = b;
     hipStream_t st = h->stream;
     ix->n_ranges = (int)((n_docs + BM_RANGE - 1) / BM_RANGE);
@@ -1295,6 +1323,13 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
                                n_terms, n_tab, ix->range_tab.get());
             HIP_TRY(h, hipGetLastError());
         }
+        if (keep_tf && !packed_ok) {
+            if ((rc = ix->tf16.alloc(h, std::max<size_t>(1, nnz)))) return rc;
+            if (nnz) {
+                hipLaunchKernelGGL(bm25_tf16_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, tfd.get(), nnz, ix->tf16.get());
+                HIP_TRY(h, hipGetLastError());
+            }
+        }
         return RAG_OK;
     };
     const int rc = enqueue();
@@ -1305,6 +1340,14 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
         h->err = std::string("bm25_load: ") + hipGetErrorString(e2);
         return RAG_ERR_HIP;
     }
+    if (keep_tf) {                           // the builders' inputs a refresh needs stay; the rest goes with this scope
+        ix->dl = std::move(dld);
+        if (packed_ok) {
+            ix->tfv = std::move(tfv_d);
+            ix->dlv = std::move(dlv_d);
+            ix->n_dl = (uint32_t)dl_values_h.size();
+        }
+    }
     *out = std::move(ix);
     return RAG_OK;
 }
@@ -1312,7 +1355,7 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
 int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                    const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b) {
     std::unique_ptr<rag_bm25_index> ix;
-    const int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix);
+    const int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix, h->opt.bm25_keep_tf != 0);
     if (rc) return rc;
     bm25_free(h);
     h->bm25 = ix.release();
@@ -1330,7 +1373,8 @@ __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64
                                    const bm_term_meta* __restrict__ a_meta, int64_t a_terms, const int32_t* __restrict__ a_doc,
                                    const double* __restrict__ a_w, const int64_t* __restrict__ b_indptr,
                                    const int32_t* __restrict__ b_doc, const double* __restrict__ b_w, int32_t b_shift,
-                                   int32_t* __restrict__ doc_out, double* __restrict__ w_out) {
+                                   int32_t* __restrict__ doc_out, double* __restrict__ w_out,
+                                   const uint16_t* __restrict__ a_tf, const uint16_t* __restrict__ b_tf, uint16_t* __restrict__ tf_out) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
     int64_t lo = 0, hi = n_terms;
@@ -1347,10 +1391,12 @@ __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64
     if (j < a_df) {
         doc_out[p] = a_doc[a_post + j];
         w_out[p] = a_w[a_post + j];
+        if (tf_out != nullptr) tf_out[p] = a_tf[a_post + j];       // (uniform) the kept term frequencies travel with the impacts
     } else {
         const int64_t s = b_indptr[lo] + (j - a_df);
         doc_out[p] = b_doc[s] + b_shift;
         w_out[p] = b_w[s];
+        if (tf_out != nullptr) tf_out[p] = b_tf[s];
     }
 }
 
@@ -1418,6 +1464,9 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
         for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p)
             ARG_CHECK(h, doc[p] >= 0 && doc[p] < n_new && (p == indptr[t] || doc[p] > doc[p - 1]),
                       "bm25_append: doc must be ascending inside a term and below n_docs_new");
+    const bool keep = ix->keep_tf;
+    if (keep)
+        if (int rc = bm_check_tf16(h, tf, nnz_b, "bm25_append")) return rc;
     std::vector<double> idf_all(ix->idf_h);
     idf_all.insert(idf_all.end(), idf_new, idf_new + (V - known));
     double neg = ix->neg_idf_absmax;
@@ -1431,6 +1480,7 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     nt->n_terms = V;
     nt->n_ranges = (int)((nt->n_docs + BM_RANGE - 1) / BM_RANGE);
     nt->avgdl = ix->avgdl; nt->k1 = ix->k1; nt->b = ix->b;
+    nt->keep_tf = keep;
     nt->indptr_h.resize((size_t)V + 1);
     nt->indptr_h[0] = 0;
     for (int64_t t = 0; t < V; ++t)
@@ -1442,10 +1492,20 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     dev_buf<int64_t> b_indptr;
     dev_buf<int32_t> b_doc, b_tf, b_dl;
     dev_buf<double> b_w, idf_d;
+    dev_buf<uint16_t> b_tf16;
     auto enqueue = [&]() -> int {
         int rc;
         const char* what = "bm25_append";
         if ((rc = bm_plan_segment(h, nt.get(), idf_all, meta_h, what))) return rc;
+        if (keep) {                          // the tail's tf plane and document lengths: old tail ++ block, like its impacts
+            if ((rc = bm_alloc(h, nt->tf16, (size_t)nt->nnz, what))) return rc;
+            if ((rc = bm_alloc(h, nt->dl, (size_t)nt->n_docs, what))) return rc;
+            if ((rc = bm_alloc(h, b_tf16, (size_t)nnz_b, what))) return rc;
+            HIP_TRY(h, hipMemsetAsync(nt->dl, 0, (size_t)nt->n_docs * 4, st));
+            if (ot && ix->tail_docs)
+                HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first, ot->dl + ot->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first + ix->tail_docs, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+        }
         if ((rc = bm_alloc(h, nt->indptr_d, (size_t)V + 1, what))) return rc;
         if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, what))) return rc;
         if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, what))) return rc;
@@ -1466,13 +1526,16 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
             // the block's impacts: the arithmetic of the load, with the FROZEN avgdl and the concatenated idf table
             hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz_b + 255) / 256)), dim3(256), 0, st, b_indptr.get(), b_doc.get(), b_tf.get(),
                                b_dl.get(), nnz_b, ix->avgdl, ix->k1, ix->b, idf_d.get(), V, b_w.get());
+            if (keep)
+                hipLaunchKernelGGL(bm25_tf16_kernel, dim3((unsigned)((nnz_b + 255) / 256)), dim3(256), 0, st, b_tf.get(), nnz_b, b_tf16.get());
             HIP_TRY(h, hipGetLastError());
         }
         if (nt->nnz) {
             hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nt->nnz + 255) / 256)), dim3(256), 0, st, nt->indptr_d.get(), V, nt->nnz,
                                ot ? ot->meta.get() : (const bm_term_meta*)nullptr, Vo, ot ? ot->doc.get() : (const int32_t*)nullptr,
                                ot ? ot->w.get() : (const double*)nullptr, b_indptr.get(), b_doc.get(), b_w.get(),
-                               (int32_t)(nt->first + ix->tail_docs), nt->doc.get(), nt->w.get());
+                               (int32_t)(nt->first + ix->tail_docs), nt->doc.get(), nt->w.get(),
+                               ot ? ot->tf16.get() : (const uint16_t*)nullptr, b_tf16.get(), keep ? nt->tf16.get() : (uint16_t*)nullptr);
             HIP_TRY(h, hipGetLastError());
         }
         if (nt->tab_entries) {
@@ -1527,6 +1590,7 @@ int bm25_fold(rag_ctx* h) {
     nb->avgdl = ix->avgdl; nb->k1 = ix->k1; nb->b = ix->b;
     nb->normalize = ix->normalize;
     nb->neg_idf_absmax = ix->neg_idf_absmax;
+    nb->keep_tf = ix->keep_tf;
     nb->indptr_h.resize((size_t)V + 1);
     nb->indptr_h[0] = 0;
     for (int64_t t = 0; t < V; ++t)
@@ -1541,6 +1605,12 @@ int bm25_fold(rag_ctx* h) {
         const char* what = "bm25_fold";
         if ((rc = bm_plan_segment(h, nb.get(), ix->idf_h, meta_h, what))) return rc;
         if ((rc = bm_alloc(h, out_indptr, (size_t)V + 1, what))) return rc;
+        if (nb->keep_tf) {                   // tf per term like the impacts; the documents' lengths: the base's, then the tail's own
+            if ((rc = bm_alloc(h, nb->tf16, (size_t)nb->nnz, what))) return rc;
+            if ((rc = bm_alloc(h, nb->dl, (size_t)nb->n_docs, what))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(nb->dl, ix->dl, (size_t)ix->n_docs * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(nb->dl + ix->n_docs, tl->dl + tl->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
+        }
         HIP_TRY(h, hipMemsetAsync(nb->doc + nb->nnz, 0, 8 * sizeof(int32_t), st));
         HIP_TRY(h, hipMemsetAsync(nb->w + nb->nnz, 0, 8 * sizeof(double), st));
         HIP_TRY(h, hipMemcpyAsync(out_indptr, nb->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1548,7 +1618,7 @@ int bm25_fold(rag_ctx* h) {
         if (nb->nnz) {
             hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nb->nnz + 255) / 256)), dim3(256), 0, st, out_indptr.get(), V, nb->nnz,
                                ix->meta.get(), Vb, ix->doc.get(), ix->w.get(), tl->indptr_d.get(), tl->doc.get(), tl->w.get(),
-                               (int32_t)tl->row0, nb->doc.get(), nb->w.get());
+                               (int32_t)tl->row0, nb->doc.get(), nb->w.get(), ix->tf16.get(), tl->tf16.get(), nb->tf16.get());
             HIP_TRY(h, hipGetLastError());
         }
         if (nb->tab_entries) {
@@ -1635,7 +1705,8 @@ __global__ __launch_bounds__(256) void bm25_compact_scatter_kernel(const int32_t
                                                                     const uint32_t* __restrict__ packed, const int64_t* __restrict__ row_map,
                                                                     int64_t row0, int64_t new_row0, const unsigned long long* __restrict__ mask,
                                                                     const int64_t* __restrict__ tile_off, int32_t* __restrict__ doc_out,
-                                                                    double* __restrict__ w_out, uint32_t* __restrict__ packed_out) {
+                                                                    double* __restrict__ w_out, uint32_t* __restrict__ packed_out,
+                                                                    const uint16_t* __restrict__ tf, uint16_t* __restrict__ tf_out) {
     __shared__ int pre[BM_CP_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const unsigned long long* mw = mask + (int64_t)blockIdx.x * BM_CP_WORDS;
@@ -1662,7 +1733,18 @@ __global__ __launch_bounds__(256) void bm25_compact_scatter_kernel(const int32_t
         doc_out[dst] = nd;
         if (PACKED) packed_out[dst] = (packed[p] & ~(uint32_t)(BM_RANGE - 1)) | ((uint32_t)nd & (BM_RANGE - 1));
         else w_out[dst] = w[p];
+        if (!PACKED && tf_out != nullptr) tf_out[dst] = tf[p];      // (uniform) the kept term frequency: same mask, same offset
     }
+}
+
+// the kept document lengths through the row map: old local document d of a segment -> its new local number, when it survives
+__global__ void bm25_compact_dl_kernel(const int32_t* __restrict__ dl, int64_t first, int64_t n_docs, int64_t row0,
+                                       const int64_t* __restrict__ row_map, int64_t n_map, int64_t new_row0, int64_t new_docs,
+                                       int32_t* __restrict__ dl_out) {
+    const int64_t d = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_docs || row0 + d >= n_map) return;
+    const int64_t nd = row_map[row0 + d] - new_row0;
+    if (nd >= 0 && nd < new_docs) dl_out[nd] = dl[d];             // (a deleted row maps to -1: nd < 0)
 }
 
 // One segment `os` -> `ns` (n_docs, n_ranges, row0, first set by the caller; built beside the old one, which is not touched):
@@ -1675,6 +1757,7 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
     hipStream_t st = h->stream;
     ns->n_terms = V;
     ns->avgdl = os->avgdl; ns->k1 = os->k1; ns->b = os->b;
+    ns->keep_tf = os->keep_tf;
     ns->indptr_h.assign((size_t)V + 1, 0);
     dev_buf<unsigned long long> mask;
     dev_buf<int> tile_cnt;
@@ -1717,8 +1800,26 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
             ns->n_codes = os->n_codes;
             HIP_TRY(h, hipMemsetAsync(ns->packed + nnz_new, 0, 8 * sizeof(uint32_t), st));
             HIP_TRY(h, hipMemcpyAsync(ns->gtab, os->gtab, os->gtab.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (os->keep_tf) {               // ... and so are the value tables it is rebuilt from
+                if ((rc = bm_alloc(h, ns->tfv, os->tfv.size(), what))) return rc;
+                if ((rc = bm_alloc(h, ns->dlv, os->dlv.size(), what))) return rc;
+                ns->n_dl = os->n_dl;
+                HIP_TRY(h, hipMemcpyAsync(ns->tfv, os->tfv, os->tfv.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIP_TRY(h, hipMemcpyAsync(ns->dlv, os->dlv, os->dlv.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
         } else {
             HIP_TRY(h, hipMemsetAsync(ns->w + nnz_new, 0, 8 * sizeof(double), st));
+            if (os->keep_tf && (rc = bm_alloc(h, ns->tf16, (size_t)nnz_new, what))) return rc;
+        }
+        if (os->keep_tf) {
+            if ((rc = bm_alloc(h, ns->dl, (size_t)ns->n_docs, what))) return rc;
+            HIP_TRY(h, hipMemsetAsync(ns->dl, 0, (size_t)ns->n_docs * 4, st));
+            const int64_t own = os->n_docs - os->first;
+            if (own > 0) {
+                hipLaunchKernelGGL(bm25_compact_dl_kernel, dim3((unsigned)((own + 255) / 256)), dim3(256), 0, st, os->dl.get(), (int64_t)os->first,
+                                   os->n_docs, os->row0, row_map, n_map, ns->row0, ns->n_docs, ns->dl.get());
+                HIP_TRY(h, hipGetLastError());
+            }
         }
         if (keep_indptr_d) {
             if ((rc = bm_alloc(h, ns->indptr_d, (size_t)V + 1, what))) return rc;
@@ -1729,11 +1830,11 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
             if (packed)
                 hipLaunchKernelGGL(bm25_compact_scatter_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
                                    os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
-                                   ns->packed.get());
+                                   ns->packed.get(), os->tf16.get(), ns->tf16.get());
             else
                 hipLaunchKernelGGL(bm25_compact_scatter_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
                                    os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
-                                   ns->packed.get());
+                                   ns->packed.get(), os->tf16.get(), ns->tf16.get());
             HIP_TRY(h, hipGetLastError());
         }
         if (ns->tab_entries) {
@@ -1817,7 +1918,7 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
     const rag_bm25_index* tl = ix->tail.get();
     *out = {ix->n_docs, ix->tail_docs, ix->nnz, tl ? tl->nnz : 0, (int64_t)ix->idf_h.size(),
             tl ? (int64_t)((tl->doc.size() * 4 + tl->w.size() * 8 + tl->meta.size() * sizeof(bm_term_meta) + tl->range_tab.size() * 4 +
-                            tl->indptr_d.size() * 8))
+                            tl->indptr_d.size() * 8 + tl->tf16.size() * 2 + tl->dl.size() * 4))
                : 0,
             ix->appends, ix->folds};
     return RAG_OK;
@@ -1858,6 +1959,281 @@ static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, co
     ARG_CHECK(h, h->tenants != nullptr && h->n_rows == bm_total_docs(ix),
               "bm25: a tenant filter needs rag_index_set_tenants_host and postings row-aligned with the index");
     *tenants_out = search_vis(h, tenant);
+    return RAG_OK;
+}
+
+// ---- statistics refresh (rag_bm25_live_counts_host / rag_bm25_set_statistics_host / rag_bm25_refresh) --------------------------
+// Fresh idf / avgdl computed from, and written into, the resident postings (option bm25_keep_tf at load time). COUNT: document
+// frequencies over the live postings, live documents, the sum of their lengths - all exact integers, so the atomics' order cannot
+// show. RULE: rank-bm25's idf on the host (libm's log in float64: the table must be the bits Python's math.log gives). INSTALL: every
+// impact of base and tail recomputed from (tf, doc_len, idf, avgdl) by the load's own arithmetic (bm_tf_factor), the packed
+// base's table by bm25_gtab_kernel; offsets, bracket tables and the postings' order are not touched.
+
+// term of posting p: the last t with meta[t].post <= p (terms with an empty list share their start with the next one)
+__device__ __forceinline__ int64_t bm_term_of(const bm_term_meta* __restrict__ meta, int64_t n_terms, int64_t p) {
+    int64_t lo = 0, hi = n_terms;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (meta[mid].post <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// live document frequencies of one segment, added into df[]: a workgroup takes a tile of BM_CP_TILE consecutive postings (the
+// compaction's tiling), one ballot per 64 postings gives the tile's live mask in LDS, and every term that has postings in the
+// tile - a tile is term-major, so these are the terms t_first .. t_last - counts the set bits of its own stretch: ONE atomic
+// per (tile, term), none per posting.
+__global__ __launch_bounds__(256) void bm25_live_df_kernel(const bm_term_meta* __restrict__ meta, int64_t n_terms, const int32_t* __restrict__ doc,
+                                                            int64_t nnz, const int32_t* __restrict__ vis, int64_t row0, int32_t* __restrict__ df) {
+    __shared__ unsigned long long mw[BM_CP_WORDS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * BM_CP_TILE, pe = min(p0 + BM_CP_TILE, nnz);
+#pragma unroll
+    for (int j = 0; j < BM_CP_TILE / 256; ++j) {
+        const int64_t p = p0 + j * 256 + tid;
+        const bool live = p < nnz && row_visible(vis, row0 + doc[p], -1);
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) mw[j * 4 + wv] = m;
+    }
+    __syncthreads();
+    const int64_t t_first = bm_term_of(meta, n_terms, p0), t_last = bm_term_of(meta, n_terms, pe - 1);
+    for (int64_t t = t_first + tid; t <= t_last; t += 256) {
+        const bm_term_meta m = meta[t];
+        const int a = (int)(max(m.post, p0) - p0), e = (int)(min(m.post + m.df, pe) - p0);
+        if (e <= a) continue;                                       // a term without postings (in this tile)
+        int c = 0;
+        for (int k = a >> 6; k <= (e - 1) >> 6; ++k) {
+            unsigned long long x = mw[k];
+            if (k == a >> 6) x &= ~0ull << (a & 63);
+            if (k == (e - 1) >> 6 && (e & 63)) x &= (1ull << (e & 63)) - 1ull;
+            c += __popcll(x);
+        }
+        if (c) atomicAdd(&df[t], c);
+    }
+}
+
+// live documents of one segment and the sum of their lengths, added into out2[0] / out2[1] (64-bit integer atomics, one pair
+// per wave)
+__global__ __launch_bounds__(256) void bm25_live_len_kernel(const int32_t* __restrict__ dl, int64_t first, int64_t n_docs, int64_t row0,
+                                                             const int32_t* __restrict__ vis, unsigned long long* __restrict__ out2) {
+    long long c = 0, s = 0;
+    for (int64_t d = first + (int64_t)blockIdx.x * 256 + threadIdx.x; d < n_docs; d += (int64_t)gridDim.x * 256)
+        if (row_visible(vis, row0 + d, -1)) {
+            ++c;
+            s += dl[d];
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        c += __shfl_xor(c, o);
+        s += __shfl_xor(s, o);
+    }
+    if ((threadIdx.x & 63) == 0 && c) {
+        atomicAdd(&out2[0], (unsigned long long)c);
+        atomicAdd(&out2[1], (unsigned long long)s);
+    }
+}
+
+// the impact rewrite of an unpacked segment: bm25_weights_kernel over the KEPT planes (uint16 tf, the segment's own document
+// lengths, the term found in the metadata instead of the CSR offsets) - one streaming pass, the same product bit for bit
+__global__ void bm25_reweigh_kernel(const bm_term_meta* __restrict__ meta, int64_t n_terms, const int32_t* __restrict__ doc,
+                                    const uint16_t* __restrict__ tf, const int32_t* __restrict__ doc_len, int64_t nnz, double avgdl,
+                                    double k1, double b, const double* __restrict__ idf, double* __restrict__ w) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    const int64_t t = bm_term_of(meta, n_terms, p);
+    w[p] = idf[t] * bm_tf_factor((double)tf[p], (double)doc_len[doc[p]], avgdl, k1, b);
+}
+
+__global__ void bm25_set_idf_kernel(bm_term_meta* __restrict__ meta, int64_t n_terms, const double* __restrict__ idf) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_terms) meta[t].idf = idf[t];
+}
+
+static int bm25_refresh_ready(rag_ctx* h, const char* what) {
+    if (!h->bm25) {
+        h->err = std::string(what) + ": no postings loaded";
+        return RAG_ERR_STATE;
+    }
+    if (!h->bm25->keep_tf) {
+        h->err = std::string(what) + ": the postings were loaded without option bm25_keep_tf (term frequencies and document lengths were not kept)";
+        return RAG_ERR_STATE;
+    }
+    return bm25_check_fresh(h, h->bm25);
+}
+
+// a document is live when it is covered and not deleted: the deleted rows of a row-aligned dense index, nobody otherwise
+static const int32_t* bm_live_vis(const rag_ctx* h, const rag_bm25_index* ix) {
+    return h->vis != nullptr && h->index_loaded && h->n_rows == bm_total_docs(ix) ? h->vis.get() : nullptr;
+}
+
+// the scratch of a refresh: 12 B per term + the two counters, all allocated before anything is overwritten
+struct bm_refresh_ws {
+    dev_buf<int32_t> df;
+    dev_buf<double> idf;
+    dev_buf<unsigned long long> cnt;
+};
+
+// COUNT. df_h[V] = live postings per term (base and tail together). Nothing deleted: the offsets' differences, no posting read.
+static int bm25_count_live(rag_ctx* h, bm_refresh_ws& ws, std::vector<int32_t>& df_h, int64_t* n_live, int64_t* sum_dl) {
+    const rag_bm25_index* ix = h->bm25;
+    const rag_bm25_index* tl = ix->tail.get();
+    const int64_t V = (int64_t)ix->idf_h.size();
+    const int32_t* vis = bm_live_vis(h, ix);
+    hipStream_t st = h->stream;
+    df_h.assign((size_t)V, 0);
+    unsigned long long cnt_h[2] = {0, 0};
+    HIP_TRY(h, hipMemsetAsync(ws.cnt, 0, 2 * sizeof(unsigned long long), st));
+    for (const rag_bm25_index* sg : {ix, tl}) {
+        if (sg == nullptr) continue;
+        const int64_t own = sg->n_docs - sg->first;
+        if (own > 0)
+            hipLaunchKernelGGL(bm25_live_len_kernel, dim3((unsigned)std::min<int64_t>(1024, (own + 255) / 256)), dim3(256), 0, st, sg->dl.get(),
+                               (int64_t)sg->first, sg->n_docs, sg->row0, vis, ws.cnt.get());
+    }
+    if (vis != nullptr) {
+        if (V) HIP_TRY(h, hipMemsetAsync(ws.df, 0, (size_t)V * sizeof(int32_t), st));
+        for (const rag_bm25_index* sg : {ix, tl}) {
+            if (sg == nullptr || sg->nnz == 0) continue;
+            hipLaunchKernelGGL(bm25_live_df_kernel, dim3((unsigned)((sg->nnz + BM_CP_TILE - 1) / BM_CP_TILE)), dim3(256), 0, st, sg->meta.get(),
+                               sg->n_terms, sg->doc.get(), sg->nnz, vis, sg->row0, ws.df.get());
+        }
+        if (V) HIP_TRY(h, hipMemcpyAsync(df_h.data(), ws.df, (size_t)V * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    } else {
+        for (const rag_bm25_index* sg : {ix, tl}) {
+            if (sg == nullptr) continue;
+            for (int64_t t = 0; t < sg->n_terms; ++t) df_h[(size_t)t] += (int32_t)(sg->indptr_h[(size_t)t + 1] - sg->indptr_h[(size_t)t]);
+        }
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(cnt_h, ws.cnt, sizeof(cnt_h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    *n_live = (int64_t)cnt_h[0];
+    *sum_dl = (int64_t)cnt_h[1];
+    return RAG_OK;
+}
+
+// INSTALL. idf[V] (host) and avgdl become the statistics of base and tail.
+static int bm25_install(rag_ctx* h, bm_refresh_ws& ws, const double* idf, double avgdl) {
+    rag_bm25_index* ix = h->bm25;
+    rag_bm25_index* tl = ix->tail.get();
+    const int64_t V = (int64_t)ix->idf_h.size();
+    hipStream_t st = h->stream;
+    if (V) HIP_TRY(h, hipMemcpyAsync(ws.idf, idf, (size_t)V * sizeof(double), hipMemcpyHostToDevice, st));
+    for (rag_bm25_index* sg : {ix, tl}) {
+        if (sg == nullptr) continue;
+        if (sg->packed != nullptr)
+            hipLaunchKernelGGL(bm25_gtab_kernel, dim3((unsigned)((sg->n_codes + 255) / 256)), dim3(256), 0, st, sg->tfv.get(), sg->dlv.get(), sg->n_codes,
+                               sg->n_dl, avgdl, sg->k1, sg->b, sg->gtab.get());
+        else if (sg->nnz)
+            hipLaunchKernelGGL(bm25_reweigh_kernel, dim3((unsigned)((sg->nnz + 255) / 256)), dim3(256), 0, st, sg->meta.get(), sg->n_terms,
+                               sg->doc.get(), sg->tf16.get(), sg->dl.get(), sg->nnz, avgdl, sg->k1, sg->b, ws.idf.get(), sg->w.get());
+        if (sg->n_terms)
+            hipLaunchKernelGGL(bm25_set_idf_kernel, dim3((unsigned)((sg->n_terms + 255) / 256)), dim3(256), 0, st, sg->meta.get(), sg->n_terms,
+                               ws.idf.get());
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(st));
+    ix->idf_h.assign(idf, idf + V);
+    ix->avgdl = avgdl;
+    if (tl) tl->avgdl = avgdl;
+    // recomputed, not kept: epsilon * mean can itself be negative on a tiny corpus (bm25_negative_bound_args)
+    ix->neg_idf_absmax = 0.0;
+    for (int64_t t = 0; t < V; ++t)
+        if (idf[t] < 0.0) ix->neg_idf_absmax = std::max(ix->neg_idf_absmax, -idf[t]);
+    return RAG_OK;
+}
+
+static int bm25_refresh_alloc(rag_ctx* h, bm_refresh_ws& ws, bool count, bool install, const char* what) {
+    const size_t V = h->bm25->idf_h.size();
+    int rc;
+    if (count && (rc = bm_alloc(h, ws.df, V, what))) return rc;
+    if (count && (rc = bm_alloc(h, ws.cnt, 2, what))) return rc;
+    if (install && (rc = bm_alloc(h, ws.idf, V, what))) return rc;
+    return RAG_OK;
+}
+
+int bm25_live_counts_host(rag_ctx* h, int32_t* df_out, int64_t* n_docs_live_out, int64_t* sum_doc_len_out) {
+    const char* what = "bm25_live_counts";
+    int rc = bm25_refresh_ready(h, what);
+    if (rc) return rc;
+    bm_refresh_ws ws;
+    if ((rc = bm25_refresh_alloc(h, ws, true, false, what))) return rc;
+    std::vector<int32_t> df_h;
+    int64_t n_live = 0, sum_dl = 0;
+    if ((rc = bm25_count_live(h, ws, df_h, &n_live, &sum_dl))) return rc;
+    if (df_out && !df_h.empty()) memcpy(df_out, df_h.data(), df_h.size() * sizeof(int32_t));
+    if (n_docs_live_out) *n_docs_live_out = n_live;
+    if (sum_doc_len_out) *sum_doc_len_out = sum_dl;
+    return RAG_OK;
+}
+
+static int bm25_check_statistics(rag_ctx* h, const double* idf, int64_t V, double avgdl, const char* what) {
+    ARG_CHECK(h, V == 0 || idf != nullptr, "bm25_set_statistics: null idf table");
+    ARG_CHECK(h, std::isfinite(avgdl) && avgdl > 0.0, "bm25_set_statistics: avgdl must be finite and > 0");
+    for (int64_t t = 0; t < V; ++t) ARG_CHECK(h, std::isfinite(idf[t]), "bm25_set_statistics: every idf must be finite");
+    return RAG_OK;
+}
+
+int bm25_set_statistics_host(rag_ctx* h, const double* idf, double avgdl) {
+    const char* what = "bm25_set_statistics";
+    int rc = bm25_refresh_ready(h, what);
+    if (rc) return rc;
+    if ((rc = bm25_check_statistics(h, idf, (int64_t)h->bm25->idf_h.size(), avgdl, what))) return rc;
+    bm_refresh_ws ws;
+    if ((rc = bm25_refresh_alloc(h, ws, false, true, what))) return rc;
+    return bm25_install(h, ws, idf, avgdl);
+}
+
+int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_info* info_out) {
+    const char* what = "bm25_refresh";
+    int rc = bm25_refresh_ready(h, what);
+    if (rc) return rc;
+    ARG_CHECK(h, std::isfinite(epsilon), "bm25_refresh: epsilon must be finite");
+    rag_bm25_index* ix = h->bm25;
+    const int64_t V = (int64_t)ix->idf_h.size();
+    bm_refresh_ws ws;
+    if ((rc = bm25_refresh_alloc(h, ws, true, true, what))) return rc;
+    std::vector<int32_t> df;
+    int64_t N = 0, sum_dl = 0;
+    if ((rc = bm25_count_live(h, ws, df, &N, &sum_dl))) return rc;
+    if (N <= 0) {
+        h->err = "bm25_refresh: no live covered document remains";
+        return RAG_ERR_STATE;
+    }
+    // rank-bm25's rule over the terms that still occur, in term-number order (= its dict order); float64, libm's log
+    std::vector<double> idf((size_t)V);
+    rag_bm25_refresh_info info = {};
+    double sum = 0.0;
+    int64_t occurring = 0;
+    for (int64_t t = 0; t < V; ++t) {
+        const int64_t d = df[(size_t)t];
+        info.nnz_live += d;
+        if (d == 0) {                        // lost every posting: stays in the vocabulary, out of the mean
+            idf[(size_t)t] = std::log((double)N + 0.5) - std::log(0.5);
+            info.terms_without_postings++;
+            continue;
+        }
+        const double v = std::log((double)(N - d) + 0.5) - std::log((double)d + 0.5);
+        idf[(size_t)t] = v;
+        sum += v;
+        occurring++;
+    }
+    const double mean = occurring ? sum / (double)occurring : 0.0;
+    for (int64_t t = 0; t < V; ++t)
+        if (df[(size_t)t] != 0 && idf[(size_t)t] < 0.0) {
+            idf[(size_t)t] = epsilon * mean;
+            info.negative_idf_terms++;
+        }
+    const double avgdl = (double)sum_dl / (double)N;
+    if ((rc = bm25_check_statistics(h, idf.data(), V, avgdl, what))) return rc;     // (a corpus of empty documents: avgdl 0)
+    info.n_docs_live = N;
+    info.n_terms = V;
+    info.avgdl_before = ix->avgdl;
+    info.avgdl_after = avgdl;
+    for (int64_t t = 0; t < V; ++t) info.idf_max_abs_change = std::max(info.idf_max_abs_change, std::fabs(idf[(size_t)t] - ix->idf_h[(size_t)t]));
+    if ((rc = bm25_install(h, ws, idf.data(), avgdl))) return rc;
+    if (idf_out && V) memcpy(idf_out, idf.data(), (size_t)V * sizeof(double));
+    if (info_out) *info_out = info;
     return RAG_OK;
 }
 

@@ -73,6 +73,7 @@ struct rag_options {
     int bm25_plan_slots = 0;      // planned token slots per query of a BM25 call (0 = sized by the per-call budget, bm25_pick_plan_t); tests force 8
     int bm25_ws_mb = 0;           // workspace budget of a device-pointer BM25 call in MiB (0 = 6 GiB): batches beyond it run in sub-batches
     int bm25_packed = 0;          // (read when postings are LOADED) 4-byte packed postings + shared impact table instead of (doc, impact)
+    int bm25_keep_tf = 0;         // (read when postings are LOADED) keep uint16 term frequencies + document lengths (a packed base: its value tables) so that rag_bm25_refresh can recompute every impact on the device: +2 B per posting, +4 B per document
     int bm25_tail_fold = 0;       // appended postings: an append folds the tail into the base once it holds more than this many documents (-1 = never, 0 = the default policy, bm25.hip bm_default_fold_docs)
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)

@@ -12,7 +12,12 @@ Then compaction that keeps the postings (rag_index_compact_bm25), with and witho
 deleted, each run on a fresh PAIR of identical handles: one takes rag_index_compact, the other rag_index_compact_bm25 (the difference is the
 cost of the posting remap); the first then takes the path the new call replaces - Bm25Postings.compacted on the host +
 rag_bm25_load_host - and both are searched (the same CSR, remapped on the device against freshly loaded). --part append /
-compact runs one half and merges it into the file."""
+compact runs one half and merges it into the file.
+--part refresh: statistics refreshed on the device (option bm25_keep_tf, rag_bm25_refresh) with a tail of 0 / 1 % / 5 % and 10 % of
+the rows deleted, on a PAIR of identical handles, option off and on: the two searches interleaved A/B (and A/A against a second handle without the option) before
+anything is deleted; then rag_bm25_refresh, its two halves on their own (rag_bm25_live_counts_host, rag_bm25_set_statistics_host; the host idf
+rule is the rest) and the rewrite's achieved TB/s; and what the call replaces, timed in the same run - Bm25Postings.refreshed on the
+host + rag_bm25_load_host of the merged CSR. Writes profiles/live_bm25_refresh_1M.json."""
 import argparse
 import json
 import os
@@ -132,6 +137,108 @@ def compact_probe(a, data):
     return out
 
 
+def refresh_probe(a, data):
+    """rag_bm25_refresh against the host rebuild + reload it replaces; search times with option bm25_keep_tf off and on."""
+    import torch
+    import bench_modes as BM
+    from optimized_rag_amd import RagEngine
+    from optimized_rag_amd.bm25 import Bm25Postings
+    N, D, V = a.rows, a.dim, 100_000
+    indptr, doc, tf, dl, tok, doc_ptr = data
+    rng = np.random.default_rng(2)
+    block = rng.standard_normal((min(125_000, N), D), dtype=np.float32)
+    term_of = np.repeat(np.arange(V, dtype=np.int32), np.diff(indptr))
+    Q = 256
+    ptr, terms = BM._term_queries(tok, doc_ptr, N, Q)
+    pd, td = torch.from_numpy(ptr).cuda(), torch.from_numpy(terms).cuda()
+    q = torch.from_numpy(rng.standard_normal((Q, D), dtype=np.float32)).cuda()
+    ids = torch.empty((Q, 100), dtype=torch.int64, device="cuda")
+    sc = torch.empty((Q, 100), dtype=torch.float64, device="cuda")
+
+    def csr(lo, hi):
+        m = (doc >= lo) & (doc < hi)
+        ip = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(term_of[m], minlength=V), out=ip[1:])
+        return ip, (doc[m] - lo).astype(np.int32), tf[m]
+    ip0, d0, tf0 = csr(0, N)
+    idf = Bm25Postings.idf_table(np.diff(ip0), N)
+    idf[np.diff(ip0) == 0] = 0.0
+    avgdl = float(dl[:N].sum()) / N
+
+    def build(n_tail, keep):
+        eng = RagEngine(dim=D, device=0)
+        eng.index_reserve(N + n_tail + 4096)
+        for b in range(0, N, block.shape[0]):
+            eng.index_append(block[:min(block.shape[0], N - b)])
+        eng.set_option("bm25_tail_fold", -1)
+        eng.set_option("bm25_keep_tf", keep)
+        eng.bm25_load(ip0, d0, tf0, dl[:N], idf, avgdl)
+        if n_tail:
+            eng.index_insert(block[:n_tail])
+            ipt, dt_, tft = csr(N, N + n_tail)
+            eng.bm25_append(ipt, dt_, tft, dl[N:N + n_tail], np.zeros(0, dtype=np.float64), V)
+        return eng
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        return r, (time.perf_counter() - t0) * 1e3
+    out = {"rows": N, "dim": D, "vocab": V, "mean_doc_len": 120}
+    for tail_name, n_tail in (("tail_0", 0), ("tail_1pct", N // 100), ("tail_5pct", N // 20)):
+        n_all = N + n_tail
+        off, on, off_b = build(n_tail, 0), build(n_tail, 1), build(n_tail, 0)    # off_b: a second handle without the option (A/A)
+        calls = {"bm25_topk_dev_q256_k100_ms": lambda e: e.bm25_topk_dev(pd, td, 100, ids, None, sc),
+                 "hybrid_rrf_dev_q256_ms": lambda e: e.hybrid_rrf_dev(q, pd, td, 100, 20)}
+        ab = {k: {"off": [], "on": [], "off_b": []} for k in calls}
+        for _ in range(5):                                       # interleaved: off, on, off_b, off, on, off_b, ...
+            for k, f in calls.items():
+                for name, e in (("off", off), ("on", on), ("off_b", off_b)):
+                    ab[k][name].append(BM._p50_ms(lambda: f(e), 20, 5))
+        off_b.close()
+        s_on = on.bm25_segment_stats()
+        nnz = s_on["base_nnz"] + s_on["tail_nnz"]
+        victims = rng.permutation(n_all)[: n_all // 10].astype(np.int64)
+        for e in (off, on):
+            assert e.index_delete(victims) == len(victims)
+        on.bm25_live_counts()                                    # first use of every kernel
+        runs, first_info = [], None
+        for _ in range(3):
+            (idf_new, info), refresh_ms = timed(lambda: on.bm25_refresh())
+            first_info = first_info or info
+            _, counts_ms = timed(lambda: on.bm25_live_counts())
+            _, rewrite_ms = timed(lambda: on.bm25_set_statistics(idf_new, info["avgdl_after"]))
+            runs.append((refresh_ms, counts_ms, rewrite_ms))
+        refresh_ms, counts_ms, rewrite_ms = (float(np.median([r[i] for r in runs])) for i in range(3))
+        rewrite_bytes = nnz * (4 + 2 + 8)                        # doc id + tf read, impact written (doc_len and metadata: gathers, not counted)
+        after = {k: BM._p50_ms(lambda: f(on), 20, 5) for k, f in calls.items()}
+        after_off = {k: BM._p50_ms(lambda: f(off), 20, 5) for k, f in calls.items()}      # the same deletes, frozen statistics
+        ipm, dm, tfm = csr(0, n_all)
+        mirror = Bm25Postings(ipm, dm, tfm, dl[:n_all].copy(), np.concatenate([idf]), avgdl)
+        fresh, host_ms = timed(lambda: mirror.refreshed())
+        _, load_ms = timed(lambda: off.bm25_load(fresh.indptr, fresh.doc, fresh.tf, fresh.doc_len, fresh.idf, fresh.avgdl))
+        out[tail_name] = {
+            "documents": n_all, "postings": int(nnz), "tail_docs": s_on["tail_docs"], "deleted_rows": int(len(victims)),
+            "search_before_deletes_interleaved_ab": ab,
+            "search_on_over_off_median": {k: float(np.median(v["on"]) / np.median(v["off"])) for k, v in ab.items()},
+            "search_off_spread": {k: [float(min(v["off"] + v["off_b"])), float(max(v["off"] + v["off_b"]))] for k, v in ab.items()},
+            "search_on_spread": {k: [float(min(v["on"])), float(max(v["on"]))] for k, v in ab.items()},
+            "refresh_ms": refresh_ms, "live_counts_ms": counts_ms, "set_statistics_ms": rewrite_ms,
+            "host_idf_ms": refresh_ms - counts_ms - rewrite_ms, "refresh_runs_ms": runs,
+            "rewrite_bytes": int(rewrite_bytes), "rewrite_tb_per_s": rewrite_bytes / (rewrite_ms * 1e-3) / 1e12,
+            "info": first_info, "search_after_refresh_10pct_deleted": after, "search_option_off_10pct_deleted": after_off,
+            "host_refreshed_ms": host_ms, "bm25_load_host_ms": load_ms, "reload_path_ms": host_ms + load_ms,
+            "reload_over_refresh": (host_ms + load_ms) / refresh_ms}
+        print(tail_name, json.dumps(out[tail_name]), flush=True)
+        off.close()
+        on.close()
+    out["note"] = ("refresh_ms = one rag_bm25_refresh; live_counts_ms / set_statistics_ms = its two halves called on their own right after "
+                   "(set_statistics includes the 0.8 MB idf upload), host_idf_ms = the rest (the idf rule on the host + the df download); "
+                   "rewrite_bytes = doc id + tf read and impact written per posting; reload_path = Bm25Postings.refreshed on the host + "
+                   "rag_bm25_load_host of the merged CSR (statistics over ALL documents: the host mirror has no live mask there)")
+    return out
+
+
 def write_out(a, part):
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     out = {}
@@ -152,6 +259,9 @@ def bm25_probe(a):
     N, D, V = a.rows, a.dim, 100_000
     extra = N // 20 + 8192                                # the 5 % tail and the timed blocks behind it
     indptr, doc, tf, dl, tok, doc_ptr = BM.synthetic_csr(N + extra, V, 120)
+    if a.part == "refresh":
+        a.out = a.refresh_out
+        return write_out(a, refresh_probe(a, (indptr, doc, tf, dl, tok, doc_ptr)))
     if a.part in ("all", "compact"):
         write_out(a, {"compaction": compact_probe(a, (indptr, doc, tf, dl, tok, doc_ptr))})
     if a.part == "compact":
@@ -228,8 +338,10 @@ def main():
     ap.add_argument("--dim", type=int, default=1536)
     ap.add_argument("--out", default=None)
     ap.add_argument("--bm25", action="store_true", help="probe the appendable postings instead (profiles/live_bm25_1M.json)")
-    ap.add_argument("--part", choices=("all", "append", "compact"), default="all",
-                    help="with --bm25: the append / fold runs, the compaction runs, or both (merged into the output file)")
+    ap.add_argument("--part", choices=("all", "append", "compact", "refresh"), default="all",
+                    help="with --bm25: the append / fold runs, the compaction runs, or both (merged into the output file); "
+                         "refresh: the statistics refresh, into its own file")
+    ap.add_argument("--refresh-out", default=os.path.join(ROOT, "profiles", "live_bm25_refresh_1M.json"))
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "live_bm25_1M.json" if a.bm25 else "live_index_1M.json")
     if a.bm25:
