@@ -129,23 +129,48 @@ __device__ __forceinline__ double bm_tf_factor(double f, double dl, double avgdl
     return num / den;
 }
 
-__global__ void bm25_weights_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ doc,
-                                    const int32_t* __restrict__ tf, const int32_t* __restrict__ doc_len, int64_t nnz,
-                                    double avgdl, double k1, double b, const double* __restrict__ idf, int64_t n_terms,
-                                    double* __restrict__ w) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    // term of posting p: last t with indptr[t] <= p
-    int64_t lo = 0, hi = n_terms;
+// The file's launch idiom for "one thread per element, 256 per workgroup". The arguments are converted to the kernel's parameter
+// types here (a dev_buf to its pointer, nullptr to a typed null).
+template <class... P, class... A>
+static inline void bm_launch_1d(void (*kernel)(P...), int64_t n, hipStream_t st, A&&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<P>(args)...);
+}
+
+// The owner search, written once: the last t in [0, n) with key(t) <= p, for non-decreasing keys with key(0) <= p. The keys are
+// the starts of per-term stretches (postings, or bracket-table entries). THE EMPTY-LIST RULE: a term with an empty stretch shares
+// its start with the next term, so among equal keys the LAST t is the owner of p - every caller relies on it.
+template <class Key>
+__device__ __forceinline__ int64_t bm_last_le(int64_t n, int64_t p, Key key) {
+    int64_t lo = 0, hi = n;
     while (hi - lo > 1) {
         const int64_t mid = (lo + hi) >> 1;
-        if (indptr[mid] <= p) lo = mid; else hi = mid;
+        if (key(mid) <= p) lo = mid; else hi = mid;
     }
+    return lo;
+}
+// term of posting p, from CSR offsets / from the segment's term metadata
+struct bm_term_by_offsets {
+    const int64_t* indptr; int64_t n_terms;
+    __device__ __forceinline__ int64_t operator()(int64_t p) const { return bm_last_le(n_terms, p, [&](int64_t t) { return indptr[t]; }); }
+};
+struct bm_term_by_meta {
+    const bm_term_meta* meta; int64_t n_terms;
+    __device__ __forceinline__ int64_t operator()(int64_t p) const { return bm_last_le(n_terms, p, [&](int64_t t) { return meta[t].post; }); }
+};
+
+// The impact of every posting, one thread each: the load (int32 tf; the term found in the metadata it has just uploaded), an
+// appended block (int32 tf, CSR offsets) and the statistics refresh (the kept uint16 tf, metadata) run this one kernel, so their
+// products agree bit for bit. The impact is stored already multiplied by the term's idf: `idf * (...)` is the product rank-bm25
+// adds to the score, so the scoring loop is a pure load + add (one float64 multiply and one LDS lookup fewer per posting).
+template <class TF, class TermOf>
+__global__ void bm25_impact_kernel(const TermOf term_of, const int32_t* __restrict__ doc, const TF* __restrict__ tf,
+                                   const int32_t* __restrict__ doc_len, int64_t nnz, double avgdl, double k1, double b,
+                                   const double* __restrict__ idf, double* __restrict__ w) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
     const double f = (double)tf[p];
     const double dl = (double)doc_len[doc[p]];
-    // the impact is stored already multiplied by the term's idf: `idf * (...)` is the product rank-bm25 adds to the score, so
-    // the scoring loop is a pure load + add (one float64 multiply and one LDS lookup fewer per posting)
-    w[p] = idf[lo] * bm_tf_factor(f, dl, avgdl, k1, b);
+    w[p] = idf[term_of(p)] * bm_tf_factor(f, dl, avgdl, k1, b);
 }
 
 // packed postings (see rag_bm25_index): one thread per posting
@@ -158,7 +183,7 @@ __global__ void bm25_pack_kernel(const int32_t* __restrict__ doc, const int32_t*
 }
 
 // g[ti * n_dl + di] for the ti-th distinct term frequency and the di-th distinct document length - the second factor of
-// rank-bm25's `idf * (q_freq * (k1 + 1) / (q_freq + k1 * (1 - b + b * doc_len / avgdl)))`, same association as bm25_weights_kernel
+// rank-bm25's `idf * (q_freq * (k1 + 1) / (q_freq + k1 * (1 - b + b * doc_len / avgdl)))`, same association as bm25_impact_kernel
 __global__ void bm25_gtab_kernel(const double* __restrict__ tf_values, const double* __restrict__ dl_values, int64_t n_codes, uint32_t n_dl,
                                  double avgdl, double k1, double b, double* __restrict__ gtab) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,17 +212,12 @@ static inline int bm_plan_term(int64_t df, int64_t n_pad, int64_t* entries_out) 
     return g;
 }
 
-// one thread per table entry: term = last t whose table starts at or before entry i (terms without a table share their
-// start with the next term, so the LAST such t is the owner)
+// one thread per table entry; its term is the owner (bm_last_le) among the tables' starts: a term without a table has an empty stretch
 __global__ void bm25_range_table_kernel(const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc, int64_t n_terms,
                                         int64_t n_entries, int32_t* __restrict__ range_tab) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_entries) return;
-    int64_t lo = 0, hi = n_terms;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (meta[mid].tab <= i) lo = mid; else hi = mid;
-    }
+    const int64_t lo = bm_last_le(n_terms, i, [&](int64_t t) { return meta[t].tab; });
     const bm_term_meta m = meta[lo];
     const int64_t target = (i - m.tab) << m.shift;
     range_tab[i] = target > 0x7fffffff ? m.df : (int32_t)(lower_bound_doc(doc, m.post, m.post + m.df, (int)target) - m.post);
@@ -1205,6 +1225,129 @@ void bm25_free(rag_ctx* h) {
     h->bm25 = nullptr;
 }
 
+// ---- the segment builder --------------------------------------------------------------------------------------------------
+// Every way a segment comes to be - the load, an append (old tail ++ block), the fold (base ++ tail), a compaction's remap -
+// runs the same steps and differs in step 6 alone:
+//   1 bm_new_segment       a fresh rag_bm25_index: its place behind the documents before it, statistics and flags of its parent
+//   2 bm_plan_terms        offsets -> term metadata + the plan of the bracket tables
+//   3-5 bm_prepare_segment allocate, zero the padding, upload the metadata
+//   6                      fill doc / w (or packed) / tf16 / dl: the caller's own kernels
+//   7-8 bm_finish_segment  the bracket tables, the stream synchronise, the return code
+// Everything new is built BESIDE the resident segments; the caller swaps it in once step 8 has succeeded, so a failure changes nothing.
+
+// Who builds (the name in messages) and how a failed device allocation is reported: the load keeps dev_buf::alloc's RAG_ERR_HIP,
+// the live operations (append, fold, compaction, refresh) report RAG_ERR_NOMEM. The two codes are part of the ABI: not unified.
+template <class T>
+static int bm_alloc(rag_ctx* h, dev_buf<T>& buf, size_t n, const char* what) {
+    if (buf.alloc(h, std::max<size_t>(1, n)) == RAG_OK) return RAG_OK;
+    (void)hipGetLastError();
+    h->err = std::string(what) + ": out of device memory";
+    return RAG_ERR_NOMEM;
+}
+struct bm_builder {
+    rag_ctx* h;
+    const char* what;
+    bool nomem;
+    template <class T>
+    int alloc(dev_buf<T>& buf, size_t n) const { return nomem ? bm_alloc(h, buf, n, what) : buf.alloc(h, std::max<size_t>(1, n)); }
+};
+
+// Step 1. A segment of `docs` documents behind `prev_docs` documents of the index (0: a base). A tail numbers its documents from
+// the start of the range the base ends in (see rag_bm25_index). Statistics, flags and counters come from `parent`, the base of
+// the index it will belong to (null: the load sets its own) - the ONE place they are inherited.
+static std::unique_ptr<rag_bm25_index> bm_new_segment(const rag_bm25_index* parent, int64_t prev_docs, int64_t docs, int64_t n_terms) {
+    std::unique_ptr<rag_bm25_index> s(new rag_bm25_index());
+    s->first = (int)(prev_docs % BM_RANGE);
+    s->row0 = prev_docs - s->first;
+    s->n_docs = s->first + docs;
+    s->n_ranges = (int)((s->n_docs + BM_RANGE - 1) / BM_RANGE);
+    s->n_terms = n_terms;
+    if (parent != nullptr) {
+        s->avgdl = parent->avgdl; s->k1 = parent->k1; s->b = parent->b;
+        s->keep_tf = parent->keep_tf;
+        s->normalize = parent->normalize;
+        s->neg_idf_absmax = parent->neg_idf_absmax;
+        s->appends = parent->appends; s->folds = parent->folds;
+    }
+    return s;
+}
+
+// offsets of the per-term concatenation A ++ B over V terms (A knows Va of them, B knows Vb)
+static std::vector<int64_t> bm_merged_offsets(const int64_t* a, int64_t Va, const int64_t* b, int64_t Vb, int64_t V) {
+    std::vector<int64_t> out((size_t)V + 1, 0);
+    for (int64_t t = 0; t < V; ++t) out[(size_t)t + 1] = out[(size_t)t] + (t < Va ? a[t + 1] - a[t] : 0) + (t < Vb ? b[t + 1] - b[t] : 0);
+    return out;
+}
+
+// Step 2. Offsets -> per-term metadata (null: only counted; idf may then be null too) and the number of bracket-table entries;
+// -1 when a document frequency is negative or above max_df.
+static int64_t bm_plan_terms(const int64_t* indptr, int64_t n_terms, int64_t n_docs, const double* idf, int64_t max_df,
+                             std::vector<bm_term_meta>* meta_h) {
+    const int64_t n_pad = (n_docs + BM_RANGE - 1) / BM_RANGE * BM_RANGE;
+    if (meta_h) meta_h->resize((size_t)std::max<int64_t>(1, n_terms));
+    int64_t n_tab = 0;
+    for (int64_t t = 0; t < n_terms; ++t) {
+        const int64_t df = indptr[t + 1] - indptr[t];
+        if (df < 0 || df > max_df) return -1;
+        int64_t e_t = 0;
+        const int g = bm_plan_term(df, n_pad, &e_t);
+        if (meta_h) (*meta_h)[(size_t)t] = {indptr[t], n_tab, idf[t], (int32_t)df, g};
+        n_tab += e_t;
+    }
+    return n_tab;
+}
+// ... of a segment whose offsets are s->indptr_h (made here: cannot fail)
+static void bm_plan_segment(rag_bm25_index* s, const double* idf, std::vector<bm_term_meta>& meta_h) {
+    s->nnz = s->indptr_h[(size_t)s->n_terms];
+    s->tab_entries = bm_plan_terms(s->indptr_h.data(), s->n_terms, s->n_docs, idf, s->n_docs, &meta_h);
+}
+
+// Steps 3-5. Allocates meta, range_tab, doc and the planes this segment carries (bm_planes), zeroes what the fill does not write,
+// uploads the metadata (meta_h must stay alive until bm_finish_segment returns) and, for indptr_d, the offsets.
+// THE PADDING: doc / w / packed carry 8 zeroed postings past nnz - the scoring kernel reads 4 consecutive postings per thread,
+// the bracket search 8 doc ids, without a bounds branch. dl starts zeroed: a tail's entries below `first` are never written.
+struct bm_planes { bool w, packed, tf16, dl, indptr_d; };
+static int bm_prepare_segment(const bm_builder& B, rag_bm25_index* s, const std::vector<bm_term_meta>& meta_h, const bm_planes& pl) {
+    rag_ctx* h = B.h;
+    hipStream_t st = h->stream;
+    const size_t nnz = (size_t)s->nnz, V = (size_t)s->n_terms;
+    int rc;
+    if ((rc = B.alloc(s->meta, meta_h.size()))) return rc;
+    if ((rc = B.alloc(s->range_tab, (size_t)s->tab_entries))) return rc;
+    if ((rc = B.alloc(s->doc, nnz + 8))) return rc;
+    if (pl.w && (rc = B.alloc(s->w, nnz + 8))) return rc;
+    if (pl.packed && (rc = B.alloc(s->packed, nnz + 8))) return rc;
+    if (pl.tf16 && (rc = B.alloc(s->tf16, nnz))) return rc;
+    if (pl.dl && (rc = B.alloc(s->dl, (size_t)s->n_docs))) return rc;
+    if (pl.indptr_d && (rc = B.alloc(s->indptr_d, V + 1))) return rc;
+    HIP_TRY(h, hipMemsetAsync(s->doc + nnz, 0, 8 * sizeof(int32_t), st));
+    if (pl.w) HIP_TRY(h, hipMemsetAsync(s->w + nnz, 0, 8 * sizeof(double), st));
+    if (pl.packed) HIP_TRY(h, hipMemsetAsync(s->packed + nnz, 0, 8 * sizeof(uint32_t), st));
+    if (pl.dl) HIP_TRY(h, hipMemsetAsync(s->dl, 0, (size_t)s->n_docs * sizeof(int32_t), st));
+    if (V) HIP_TRY(h, hipMemcpyAsync(s->meta, meta_h.data(), V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
+    if (pl.indptr_d) HIP_TRY(h, hipMemcpyAsync(s->indptr_d, s->indptr_h.data(), (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    return RAG_OK;
+}
+
+// Steps 7-8, given the result of everything enqueued so far: the bracket tables (s->doc is filled by now), then THE SYNCHRONISE,
+// which runs after a failed enqueue too - the host arrays that queued copies read from stay alive until it returns.
+static int bm_finish_segment(const bm_builder& B, rag_bm25_index* s, int rc) {
+    rag_ctx* h = B.h;
+    auto tables = [&]() -> int {
+        bm_launch_1d(bm25_range_table_kernel, s->tab_entries, h->stream, s->meta, s->doc, s->n_terms, s->tab_entries, s->range_tab);
+        HIP_TRY(h, hipGetLastError());
+        return RAG_OK;
+    };
+    if (rc == RAG_OK && s->tab_entries) rc = tables();
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    if (e2 != hipSuccess) {
+        h->err = std::string(B.what) + ": " + hipGetErrorString(e2);
+        return RAG_ERR_HIP;
+    }
+    return RAG_OK;
+}
+
 // host CSR -> device index (impacts + range table). Synchronous. *out receives the index on success only.
 static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                       const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
@@ -1215,30 +1358,18 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
     ARG_CHECK(h, nnz == 0 || (doc && tf), "bm25_load: null postings");
     if (keep_tf)
         if (int rc = bm_check_tf16(h, tf, nnz, "bm25_load")) return rc;
-    std::unique_ptr<rag_bm25_index> ix(new rag_bm25_index());
+    const bm_builder B = {h, "bm25_load", false};
+    std::unique_ptr<rag_bm25_index> ix = bm_new_segment(nullptr, 0, n_docs, n_terms);
     ix->keep_tf = keep_tf;
-    ix->n_docs = n_docs; ix->n_terms = n_terms; ix->nnz = nnz; ix->avgdl = avgdl; ix->k1 = k1; ix->b = b;
-    hipStream_t st = h->stream;
-    ix->n_ranges = (int)((n_docs + BM_RANGE - 1) / BM_RANGE);
-    // per-term metadata + the plan of the bracket tables (host: one pass over indptr)
-    const int64_t n_pad = (int64_t)ix->n_ranges * BM_RANGE;
-    std::vector<bm_term_meta> meta_h((size_t)std::max<int64_t>(1, n_terms));
-    int64_t n_tab = 0;
-    for (int64_t t = 0; t < n_terms; ++t) {
-        const int64_t df = indptr[t + 1] - indptr[t];
-        if (df < 0 || df > n_docs) {
-            h->err = "bad argument: bm25_load: indptr must be non-decreasing with at most n_docs postings per term";
-            return RAG_ERR_ARG;
-        }
-        int64_t e_t = 0;
-        const int g = bm_plan_term(df, n_pad, &e_t);
-        meta_h[(size_t)t] = {indptr[t], n_tab, idf[t], (int32_t)df, g};
+    ix->nnz = nnz; ix->avgdl = avgdl; ix->k1 = k1; ix->b = b;
+    std::vector<bm_term_meta> meta_h;
+    ix->tab_entries = bm_plan_terms(indptr, n_terms, n_docs, idf, n_docs, &meta_h);
+    ARG_CHECK(h, ix->tab_entries >= 0, "bm25_load: indptr must be non-decreasing with at most n_docs postings per term");
+    for (int64_t t = 0; t < n_terms; ++t)
         if (idf[t] < 0.0) ix->neg_idf_absmax = std::max(ix->neg_idf_absmax, -idf[t]);
-        n_tab += e_t;
-    }
-    ix->tab_entries = n_tab;
     ix->indptr_h.assign(indptr, indptr + n_terms + 1);
     if (n_terms) ix->idf_h.assign(idf, idf + n_terms);
+    hipStream_t st = h->stream;
     // code space of the packed postings: distinct term frequencies x distinct document lengths (host scans of tf[] and doc_len[])
     const int64_t code_cap = (int64_t)1 << (32 - BM_RANGE_LOG2);
     std::vector<uint32_t> tf_rank_h, dl_rank_of_doc_h;
@@ -1267,21 +1398,22 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
         }
     }
     if (!packed_ok) ix->n_codes = 0;
-    // + 8 postings of padding: the scoring kernel reads 4 consecutive postings per thread, the bracket search 8 doc ids, without
-    // a bounds branch
-    // the builders' inputs: the index keeps none of them (its metadata carries the offsets and the idf)
-    dev_buf<int64_t> indptr_d;
+    // the fill's inputs: the index keeps none of them but what a refresh needs (its metadata carries the offsets and the idf)
     dev_buf<double> idf_d, tfv_d, dlv_d;
-    dev_buf<int32_t> tfd, dld;
+    dev_buf<int32_t> tfd;
     dev_buf<uint32_t> tfr_d, dlr_d;
     auto enqueue = [&]() -> int {
         int rc;
-        if ((rc = indptr_d.alloc(h, (size_t)n_terms + 1))) return rc;
-        if ((rc = ix->doc.alloc(h, (size_t)nnz + 8))) return rc;
-        HIP_TRY(h, hipMemsetAsync(ix->doc + nnz, 0, 8 * sizeof(int32_t), st));
+        // dl: the lengths the impacts are computed from; dropped again below unless a refresh will need them
+        if ((rc = bm_prepare_segment(B, ix.get(), meta_h, {!packed_ok, packed_ok, keep_tf && !packed_ok, true, false}))) return rc;
+        if ((rc = tfd.alloc(h, std::max<size_t>(1, nnz)))) return rc;
+        if ((rc = idf_d.alloc(h, std::max<size_t>(1, n_terms)))) return rc;
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(tfd, tf, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (n_terms) HIP_TRY(h, hipMemcpyAsync(idf_d, idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(ix->dl, doc_len, (size_t)n_docs * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (packed_ok) {
-            if ((rc = ix->packed.alloc(h, (size_t)nnz + 8))) return rc;
-            HIP_TRY(h, hipMemsetAsync(ix->packed + nnz, 0, 8 * sizeof(uint32_t), st));
+            const uint32_t n_dl = (uint32_t)dl_values_h.size();
             if ((rc = ix->gtab.alloc(h, (size_t)ix->n_codes))) return rc;
             if ((rc = tfr_d.alloc(h, tf_rank_h.size()))) return rc;
             if ((rc = dlr_d.alloc(h, dl_rank_of_doc_h.size()))) return rc;
@@ -1291,62 +1423,22 @@ static int bm25_build(rag_ctx* h, const int64_t* indptr, const int32_t* doc, con
             HIP_TRY(h, hipMemcpyAsync(dlr_d, dl_rank_of_doc_h.data(), dl_rank_of_doc_h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(tfv_d, tf_values_h.data(), tf_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(dlv_d, dl_values_h.data(), dl_values_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        } else {
-            if ((rc = ix->w.alloc(h, (size_t)nnz + 8))) return rc;
-            HIP_TRY(h, hipMemsetAsync(ix->w + nnz, 0, 8 * sizeof(double), st));
+            bm_launch_1d(bm25_pack_kernel, nnz, st, ix->doc, tfd, tfr_d, dlr_d, nnz, n_dl, ix->packed);
+            bm_launch_1d(bm25_gtab_kernel, ix->n_codes, st, tfv_d, dlv_d, ix->n_codes, n_dl, avgdl, k1, b, ix->gtab);
+        } else if (nnz) {
+            bm_launch_1d(bm25_impact_kernel<int32_t, bm_term_by_meta>, nnz, st, bm_term_by_meta{ix->meta, n_terms}, ix->doc, tfd, ix->dl, nnz,
+                         avgdl, k1, b, idf_d, ix->w);
+            if (keep_tf) bm_launch_1d(bm25_tf16_kernel, nnz, st, tfd, nnz, ix->tf16);
         }
-        if ((rc = idf_d.alloc(h, std::max<size_t>(1, n_terms)))) return rc;
-        if ((rc = ix->meta.alloc(h, meta_h.size()))) return rc;
-        if ((rc = tfd.alloc(h, std::max<size_t>(1, nnz)))) return rc;
-        if ((rc = dld.alloc(h, (size_t)n_docs))) return rc;
-        if ((rc = ix->range_tab.alloc(h, std::max<size_t>(1, (size_t)n_tab)))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(indptr_d, indptr, (size_t)(n_terms + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (nnz) HIP_TRY(h, hipMemcpyAsync(tfd, tf, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (n_terms) HIP_TRY(h, hipMemcpyAsync(idf_d, idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st));
-        if (n_terms) HIP_TRY(h, hipMemcpyAsync(ix->meta, meta_h.data(), (size_t)n_terms * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(dld, doc_len, (size_t)n_docs * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (nnz && !packed_ok) {
-            hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, indptr_d.get(), ix->doc.get(), tfd.get(),
-                               dld.get(), nnz, avgdl, k1, b, idf_d.get(), n_terms, ix->w.get());
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (packed_ok) {
-            hipLaunchKernelGGL(bm25_pack_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, ix->doc.get(), tfd.get(), tfr_d.get(), dlr_d.get(), nnz,
-                               (uint32_t)dl_values_h.size(), ix->packed.get());
-            hipLaunchKernelGGL(bm25_gtab_kernel, dim3((unsigned)((ix->n_codes + 255) / 256)), dim3(256), 0, st, tfv_d.get(), dlv_d.get(), ix->n_codes,
-                               (uint32_t)dl_values_h.size(), avgdl, k1, b, ix->gtab.get());
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (n_tab) {
-            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((n_tab + 255) / 256)), dim3(256), 0, st, ix->meta.get(), ix->doc.get(),
-                               n_terms, n_tab, ix->range_tab.get());
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (keep_tf && !packed_ok) {
-            if ((rc = ix->tf16.alloc(h, std::max<size_t>(1, nnz)))) return rc;
-            if (nnz) {
-                hipLaunchKernelGGL(bm25_tf16_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, tfd.get(), nnz, ix->tf16.get());
-                HIP_TRY(h, hipGetLastError());
-            }
-        }
+        HIP_TRY(h, hipGetLastError());
         return RAG_OK;
     };
-    const int rc = enqueue();
-    // also after a failure: the host vectors above stay alive until their copies have been read
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (rc) return rc;
-    if (e2 != hipSuccess) {
-        h->err = std::string("bm25_load: ") + hipGetErrorString(e2);
-        return RAG_ERR_HIP;
-    }
-    if (keep_tf) {                           // the builders' inputs a refresh needs stay; the rest goes with this scope
-        ix->dl = std::move(dld);
-        if (packed_ok) {
-            ix->tfv = std::move(tfv_d);
-            ix->dlv = std::move(dlv_d);
-            ix->n_dl = (uint32_t)dl_values_h.size();
-        }
+    if (int rc = bm_finish_segment(B, ix.get(), enqueue())) return rc;
+    if (!keep_tf) ix->dl.reset();
+    else if (packed_ok) {                    // a packed base is refreshed from the two value tables of its impact table
+        ix->tfv = std::move(tfv_d);
+        ix->dlv = std::move(dlv_d);
+        ix->n_dl = (uint32_t)dl_values_h.size();
     }
     *out = std::move(ix);
     return RAG_OK;
@@ -1365,8 +1457,8 @@ int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const 
 }
 
 // ---- appendable postings --------------------------------------------------------------------------------------------------
-// Per-term concatenation A ++ B into a new posting array, one thread per DESTINATION posting: its term is the last t with
-// out_indptr[t] <= p (the search of bm25_weights_kernel), its place j inside the term's list picks the source - the first
+// Per-term concatenation A ++ B into a new posting array, one thread per DESTINATION posting: its term comes from the
+// destination's offsets (bm_term_by_offsets), its place j inside the term's list picks the source - the first
 // a_df postings come from A (an index: per-term metadata), the rest from B (a CSR: offsets). Document numbers are shifted
 // into the destination's numbering. The append runs it as old tail ++ block, the fold as base ++ tail.
 __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64_t n_terms, int64_t nnz,
@@ -1377,11 +1469,7 @@ __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64
                                    const uint16_t* __restrict__ a_tf, const uint16_t* __restrict__ b_tf, uint16_t* __restrict__ tf_out) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
-    int64_t lo = 0, hi = n_terms;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (out_indptr[mid] <= p) lo = mid; else hi = mid;
-    }
+    const int64_t lo = bm_term_by_offsets{out_indptr, n_terms}(p);
     const int64_t j = p - out_indptr[lo];
     int64_t a_df = 0, a_post = 0;
     if (lo < a_terms) {
@@ -1398,38 +1486,6 @@ __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64
         w_out[p] = b_w[s];
         if (tf_out != nullptr) tf_out[p] = b_tf[s];
     }
-}
-
-// device allocation of the append / fold: RAG_ERR_NOMEM (not RAG_ERR_HIP) when it cannot be had, nothing else changed
-template <class T>
-static int bm_alloc(rag_ctx* h, dev_buf<T>& buf, size_t n, const char* what) {
-    if (buf.alloc(h, std::max<size_t>(1, n)) == RAG_OK) return RAG_OK;
-    (void)hipGetLastError();
-    h->err = std::string(what) + ": out of device memory";
-    return RAG_ERR_NOMEM;
-}
-
-// Term metadata + bracket-table plan of a segment whose offsets are ix->indptr_h (the host loop of bm25_build) -> ix->meta,
-// ix->range_tab (allocated, metadata uploaded; the table itself is filled by bm25_range_table_kernel once ix->doc is there)
-static int bm_plan_segment(rag_ctx* h, rag_bm25_index* ix, const std::vector<double>& idf, std::vector<bm_term_meta>& meta_h, const char* what,
-                           bool with_w = true) {
-    const int64_t n_pad = (int64_t)ix->n_ranges * BM_RANGE;
-    meta_h.resize((size_t)std::max<int64_t>(1, ix->n_terms));
-    int64_t n_tab = 0;
-    for (int64_t t = 0; t < ix->n_terms; ++t) {
-        const int64_t df = ix->indptr_h[(size_t)t + 1] - ix->indptr_h[(size_t)t];
-        int64_t e_t = 0;
-        const int g = bm_plan_term(df, n_pad, &e_t);
-        meta_h[(size_t)t] = {ix->indptr_h[(size_t)t], n_tab, idf[(size_t)t], (int32_t)df, g};
-        n_tab += e_t;
-    }
-    ix->tab_entries = n_tab;
-    int rc;
-    if ((rc = bm_alloc(h, ix->meta, meta_h.size(), what))) return rc;
-    if ((rc = bm_alloc(h, ix->range_tab, (size_t)n_tab, what))) return rc;
-    if ((rc = bm_alloc(h, ix->doc, (size_t)ix->nnz + 8, what))) return rc;
-    if (with_w && (rc = bm_alloc(h, ix->w, (size_t)ix->nnz + 8, what))) return rc;
-    return RAG_OK;
 }
 
 // Default of option bm25_tail_fold (0): the tail size, in documents, past which an append folds by itself. The tail costs every
@@ -1471,87 +1527,53 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     idf_all.insert(idf_all.end(), idf_new, idf_new + (V - known));
     double neg = ix->neg_idf_absmax;
     for (int64_t t = known; t < V; ++t) if (idf_all[(size_t)t] < 0.0) neg = std::max(neg, -idf_all[(size_t)t]);
-    // the new tail = old tail ++ block, built beside the old one and swapped in at the end
-    std::unique_ptr<rag_bm25_index> nt(new rag_bm25_index());
+    // the new tail = old tail ++ block
+    const bm_builder B = {h, "bm25_append", true};
+    const char* what = B.what;
+    std::unique_ptr<rag_bm25_index> nt = bm_new_segment(ix, ix->n_docs, ix->tail_docs + n_new, V);
     const int64_t Vo = ot ? ot->n_terms : 0;
-    nt->first = (int)(ix->n_docs % BM_RANGE);
-    nt->row0 = ix->n_docs - nt->first;
-    nt->n_docs = nt->first + ix->tail_docs + n_new;
-    nt->n_terms = V;
-    nt->n_ranges = (int)((nt->n_docs + BM_RANGE - 1) / BM_RANGE);
-    nt->avgdl = ix->avgdl; nt->k1 = ix->k1; nt->b = ix->b;
-    nt->keep_tf = keep;
-    nt->indptr_h.resize((size_t)V + 1);
-    nt->indptr_h[0] = 0;
-    for (int64_t t = 0; t < V; ++t)
-        nt->indptr_h[(size_t)t + 1] = nt->indptr_h[(size_t)t] + (t < Vo ? ot->indptr_h[(size_t)t + 1] - ot->indptr_h[(size_t)t] : 0) +
-                                      (indptr[t + 1] - indptr[t]);
-    nt->nnz = nt->indptr_h[(size_t)V];
-    hipStream_t st = h->stream;
+    nt->indptr_h = bm_merged_offsets(ot ? ot->indptr_h.data() : nullptr, Vo, indptr, V, V);
     std::vector<bm_term_meta> meta_h;
+    bm_plan_segment(nt.get(), idf_all.data(), meta_h);
+    hipStream_t st = h->stream;
     dev_buf<int64_t> b_indptr;
     dev_buf<int32_t> b_doc, b_tf, b_dl;
     dev_buf<double> b_w, idf_d;
     dev_buf<uint16_t> b_tf16;
     auto enqueue = [&]() -> int {
         int rc;
-        const char* what = "bm25_append";
-        if ((rc = bm_plan_segment(h, nt.get(), idf_all, meta_h, what))) return rc;
-        if (keep) {                          // the tail's tf plane and document lengths: old tail ++ block, like its impacts
-            if ((rc = bm_alloc(h, nt->tf16, (size_t)nt->nnz, what))) return rc;
-            if ((rc = bm_alloc(h, nt->dl, (size_t)nt->n_docs, what))) return rc;
+        if ((rc = bm_prepare_segment(B, nt.get(), meta_h, {true, false, keep, keep, true}))) return rc;
+        if (keep) {                          // the tail's document lengths: the old tail's, then the block's (its tf plane: concatenated below)
             if ((rc = bm_alloc(h, b_tf16, (size_t)nnz_b, what))) return rc;
-            HIP_TRY(h, hipMemsetAsync(nt->dl, 0, (size_t)nt->n_docs * 4, st));
             if (ot && ix->tail_docs)
                 HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first, ot->dl + ot->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first + ix->tail_docs, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
         }
-        if ((rc = bm_alloc(h, nt->indptr_d, (size_t)V + 1, what))) return rc;
         if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, what))) return rc;
         if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_tf, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_w, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_dl, (size_t)n_new, what))) return rc;
         if ((rc = bm_alloc(h, idf_d, (size_t)V, what))) return rc;
-        HIP_TRY(h, hipMemsetAsync(nt->doc + nt->nnz, 0, 8 * sizeof(int32_t), st));
-        HIP_TRY(h, hipMemsetAsync(nt->w + nt->nnz, 0, 8 * sizeof(double), st));
-        HIP_TRY(h, hipMemcpyAsync(nt->indptr_d, nt->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
-        if (V) HIP_TRY(h, hipMemcpyAsync(nt->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
         if (V) HIP_TRY(h, hipMemcpyAsync(idf_d, idf_all.data(), (size_t)V * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(b_dl, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
         if (nnz_b) {
             HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(b_tf, tf, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
             // the block's impacts: the arithmetic of the load, with the FROZEN avgdl and the concatenated idf table
-            hipLaunchKernelGGL(bm25_weights_kernel, dim3((unsigned)((nnz_b + 255) / 256)), dim3(256), 0, st, b_indptr.get(), b_doc.get(), b_tf.get(),
-                               b_dl.get(), nnz_b, ix->avgdl, ix->k1, ix->b, idf_d.get(), V, b_w.get());
-            if (keep)
-                hipLaunchKernelGGL(bm25_tf16_kernel, dim3((unsigned)((nnz_b + 255) / 256)), dim3(256), 0, st, b_tf.get(), nnz_b, b_tf16.get());
-            HIP_TRY(h, hipGetLastError());
+            bm_launch_1d(bm25_impact_kernel<int32_t, bm_term_by_offsets>, nnz_b, st, bm_term_by_offsets{b_indptr, V}, b_doc, b_tf, b_dl, nnz_b,
+                         ix->avgdl, ix->k1, ix->b, idf_d, b_w);
+            if (keep) bm_launch_1d(bm25_tf16_kernel, nnz_b, st, b_tf, nnz_b, b_tf16);
         }
-        if (nt->nnz) {
-            hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nt->nnz + 255) / 256)), dim3(256), 0, st, nt->indptr_d.get(), V, nt->nnz,
-                               ot ? ot->meta.get() : (const bm_term_meta*)nullptr, Vo, ot ? ot->doc.get() : (const int32_t*)nullptr,
-                               ot ? ot->w.get() : (const double*)nullptr, b_indptr.get(), b_doc.get(), b_w.get(),
-                               (int32_t)(nt->first + ix->tail_docs), nt->doc.get(), nt->w.get(),
-                               ot ? ot->tf16.get() : (const uint16_t*)nullptr, b_tf16.get(), keep ? nt->tf16.get() : (uint16_t*)nullptr);
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (nt->tab_entries) {
-            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((nt->tab_entries + 255) / 256)), dim3(256), 0, st, nt->meta.get(),
-                               nt->doc.get(), V, nt->tab_entries, nt->range_tab.get());
-            HIP_TRY(h, hipGetLastError());
-        }
+        if (nt->nnz)
+            bm_launch_1d(bm25_concat_kernel, nt->nnz, st, nt->indptr_d, V, nt->nnz, ot ? ot->meta.get() : nullptr, Vo,
+                         ot ? ot->doc.get() : nullptr, ot ? ot->w.get() : nullptr, b_indptr, b_doc, b_w,
+                         (int32_t)(nt->first + ix->tail_docs), nt->doc, nt->w, ot ? ot->tf16.get() : nullptr, b_tf16, nt->tf16);
+        HIP_TRY(h, hipGetLastError());
         return RAG_OK;
     };
-    const int rc = enqueue();
-    const hipError_t e2 = hipStreamSynchronize(st);          // also after a failure: the host arrays stay alive until read
-    if (rc) return rc;
-    if (e2 != hipSuccess) {
-        h->err = std::string("bm25_append: ") + hipGetErrorString(e2);
-        return RAG_ERR_HIP;
-    }
+    if (int rc = bm_finish_segment(B, nt.get(), enqueue())) return rc;
     // commit
     ix->tail = std::move(nt);
     ix->tail_docs += n_new;
@@ -1582,61 +1604,31 @@ int bm25_fold(rag_ctx* h) {
                  "reload to merge";
         return RAG_ERR_STATE;
     }
+    const bm_builder B = {h, "bm25_fold", true};
     const int64_t V = tl->n_terms, Vb = ix->n_terms;
-    std::unique_ptr<rag_bm25_index> nb(new rag_bm25_index());
-    nb->n_docs = bm_total_docs(ix);
-    nb->n_terms = V;
-    nb->n_ranges = (int)((nb->n_docs + BM_RANGE - 1) / BM_RANGE);
-    nb->avgdl = ix->avgdl; nb->k1 = ix->k1; nb->b = ix->b;
-    nb->normalize = ix->normalize;
-    nb->neg_idf_absmax = ix->neg_idf_absmax;
-    nb->keep_tf = ix->keep_tf;
-    nb->indptr_h.resize((size_t)V + 1);
-    nb->indptr_h[0] = 0;
-    for (int64_t t = 0; t < V; ++t)
-        nb->indptr_h[(size_t)t + 1] = nb->indptr_h[(size_t)t] + (t < Vb ? ix->indptr_h[(size_t)t + 1] - ix->indptr_h[(size_t)t] : 0) +
-                                      (tl->indptr_h[(size_t)t + 1] - tl->indptr_h[(size_t)t]);
-    nb->nnz = nb->indptr_h[(size_t)V];
-    hipStream_t st = h->stream;
+    const bool keep = ix->keep_tf;
+    std::unique_ptr<rag_bm25_index> nb = bm_new_segment(ix, 0, bm_total_docs(ix), V);
+    nb->indptr_h = bm_merged_offsets(ix->indptr_h.data(), Vb, tl->indptr_h.data(), V, V);
     std::vector<bm_term_meta> meta_h;
-    dev_buf<int64_t> out_indptr;
+    bm_plan_segment(nb.get(), ix->idf_h.data(), meta_h);
+    hipStream_t st = h->stream;
     auto enqueue = [&]() -> int {
-        int rc;
-        const char* what = "bm25_fold";
-        if ((rc = bm_plan_segment(h, nb.get(), ix->idf_h, meta_h, what))) return rc;
-        if ((rc = bm_alloc(h, out_indptr, (size_t)V + 1, what))) return rc;
-        if (nb->keep_tf) {                   // tf per term like the impacts; the documents' lengths: the base's, then the tail's own
-            if ((rc = bm_alloc(h, nb->tf16, (size_t)nb->nnz, what))) return rc;
-            if ((rc = bm_alloc(h, nb->dl, (size_t)nb->n_docs, what))) return rc;
+        // (indptr_d: the concatenation's destination offsets; only a tail keeps them, see the commit)
+        if (int rc = bm_prepare_segment(B, nb.get(), meta_h, {true, false, keep, keep, true})) return rc;
+        if (keep) {                          // the documents' lengths: the base's, then the tail's own
             HIP_TRY(h, hipMemcpyAsync(nb->dl, ix->dl, (size_t)ix->n_docs * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(nb->dl + ix->n_docs, tl->dl + tl->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
         }
-        HIP_TRY(h, hipMemsetAsync(nb->doc + nb->nnz, 0, 8 * sizeof(int32_t), st));
-        HIP_TRY(h, hipMemsetAsync(nb->w + nb->nnz, 0, 8 * sizeof(double), st));
-        HIP_TRY(h, hipMemcpyAsync(out_indptr, nb->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
-        if (V) HIP_TRY(h, hipMemcpyAsync(nb->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
-        if (nb->nnz) {
-            hipLaunchKernelGGL(bm25_concat_kernel, dim3((unsigned)((nb->nnz + 255) / 256)), dim3(256), 0, st, out_indptr.get(), V, nb->nnz,
-                               ix->meta.get(), Vb, ix->doc.get(), ix->w.get(), tl->indptr_d.get(), tl->doc.get(), tl->w.get(),
-                               (int32_t)tl->row0, nb->doc.get(), nb->w.get(), ix->tf16.get(), tl->tf16.get(), nb->tf16.get());
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (nb->tab_entries) {
-            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((nb->tab_entries + 255) / 256)), dim3(256), 0, st, nb->meta.get(),
-                               nb->doc.get(), V, nb->tab_entries, nb->range_tab.get());
-            HIP_TRY(h, hipGetLastError());
-        }
+        if (nb->nnz)
+            bm_launch_1d(bm25_concat_kernel, nb->nnz, st, nb->indptr_d, V, nb->nnz, ix->meta, Vb, ix->doc, ix->w, tl->indptr_d, tl->doc,
+                         tl->w, (int32_t)tl->row0, nb->doc, nb->w, ix->tf16, tl->tf16, nb->tf16);
+        HIP_TRY(h, hipGetLastError());
         return RAG_OK;
     };
-    const int rc = enqueue();
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (rc) return rc;
-    if (e2 != hipSuccess) {
-        h->err = std::string("bm25_fold: ") + hipGetErrorString(e2);
-        return RAG_ERR_HIP;
-    }
+    if (int rc = bm_finish_segment(B, nb.get(), enqueue())) return rc;
+    // commit
+    nb->indptr_d.reset();
     nb->idf_h = std::move(ix->idf_h);
-    nb->appends = ix->appends;
     nb->folds = ix->folds + 1;
     delete ix;                               // the old base, its tail and their workspaces
     h->bm25 = nb.release();
@@ -1747,17 +1739,15 @@ __global__ void bm25_compact_dl_kernel(const int32_t* __restrict__ dl, int64_t f
     if (nd >= 0 && nd < new_docs) dl_out[nd] = dl[d];             // (a deleted row maps to -1: nd < 0)
 }
 
-// One segment `os` -> `ns` (n_docs, n_ranges, row0, first set by the caller; built beside the old one, which is not touched):
+// One segment `os` -> `ns` (a bm_new_segment; the old one is not touched):
 // row_map[os->row0 + local document] is the new row or -1, rows at or past n_map have no entry. Synchronous.
 static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index* ns, const std::vector<double>& idf,
                             const int64_t* row_map, int64_t n_map, bool keep_indptr_d) {
-    const char* what = "compact_bm25";
+    const bm_builder B = {h, "compact_bm25", true};
+    const char* what = B.what;
     const int64_t V = os->n_terms, nnz = os->nnz, tiles = (nnz + BM_CP_TILE - 1) / BM_CP_TILE;
-    const bool packed = os->packed != nullptr;
+    const bool packed = os->packed != nullptr, keep = os->keep_tf;
     hipStream_t st = h->stream;
-    ns->n_terms = V;
-    ns->avgdl = os->avgdl; ns->k1 = os->k1; ns->b = os->b;
-    ns->keep_tf = os->keep_tf;
     ns->indptr_h.assign((size_t)V + 1, 0);
     dev_buf<unsigned long long> mask;
     dev_buf<int> tile_cnt;
@@ -1765,10 +1755,10 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
     std::vector<int> cnt((size_t)tiles);
     std::vector<int64_t> off((size_t)tiles);
     std::vector<bm_term_meta> meta_h;
-    int64_t nnz_new = 0;
     auto enqueue = [&]() -> int {
         int rc;
-        if (nnz > 0) {
+        if (nnz > 0) {                       // keep pass, then the new offsets (two host round trips)
+            int64_t nnz_new = 0;
             if ((rc = bm_alloc(h, mask, (size_t)tiles * BM_CP_WORDS, what))) return rc;
             if ((rc = bm_alloc(h, tile_cnt, (size_t)tiles, what))) return rc;
             if ((rc = bm_alloc(h, tile_off, (size_t)tiles, what))) return rc;
@@ -1785,73 +1775,37 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
             }
             HIP_TRY(h, hipMemcpyAsync(tile_off, off.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(indptr_old, os->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(bm25_compact_indptr_kernel, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, st, indptr_old.get(), V + 1, nnz,
-                               nnz_new, mask.get(), tile_off.get(), indptr_new.get());
+            bm_launch_1d(bm25_compact_indptr_kernel, V + 1, st, indptr_old, V + 1, nnz, nnz_new, mask, tile_off, indptr_new);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, hipMemcpyAsync(ns->indptr_h.data(), indptr_new, (size_t)(V + 1) * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipStreamSynchronize(st));
         }
-        ns->nnz = nnz_new;
-        if ((rc = bm_plan_segment(h, ns, idf, meta_h, what, !packed))) return rc;
-        HIP_TRY(h, hipMemsetAsync(ns->doc + nnz_new, 0, 8 * sizeof(int32_t), st));
+        bm_plan_segment(ns, idf.data(), meta_h);
+        if ((rc = bm_prepare_segment(B, ns, meta_h, {!packed, packed, keep && !packed, keep, keep_indptr_d}))) return rc;
         if (packed) {                        // the code table is shared by every posting that survives: copied as it is
-            if ((rc = bm_alloc(h, ns->packed, (size_t)nnz_new + 8, what))) return rc;
             if ((rc = bm_alloc(h, ns->gtab, os->gtab.size(), what))) return rc;
             ns->n_codes = os->n_codes;
-            HIP_TRY(h, hipMemsetAsync(ns->packed + nnz_new, 0, 8 * sizeof(uint32_t), st));
             HIP_TRY(h, hipMemcpyAsync(ns->gtab, os->gtab, os->gtab.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if (os->keep_tf) {               // ... and so are the value tables it is rebuilt from
+            if (keep) {                      // ... and so are the value tables it is rebuilt from
                 if ((rc = bm_alloc(h, ns->tfv, os->tfv.size(), what))) return rc;
                 if ((rc = bm_alloc(h, ns->dlv, os->dlv.size(), what))) return rc;
                 ns->n_dl = os->n_dl;
                 HIP_TRY(h, hipMemcpyAsync(ns->tfv, os->tfv, os->tfv.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
                 HIP_TRY(h, hipMemcpyAsync(ns->dlv, os->dlv, os->dlv.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
             }
-        } else {
-            HIP_TRY(h, hipMemsetAsync(ns->w + nnz_new, 0, 8 * sizeof(double), st));
-            if (os->keep_tf && (rc = bm_alloc(h, ns->tf16, (size_t)nnz_new, what))) return rc;
         }
-        if (os->keep_tf) {
-            if ((rc = bm_alloc(h, ns->dl, (size_t)ns->n_docs, what))) return rc;
-            HIP_TRY(h, hipMemsetAsync(ns->dl, 0, (size_t)ns->n_docs * 4, st));
-            const int64_t own = os->n_docs - os->first;
-            if (own > 0) {
-                hipLaunchKernelGGL(bm25_compact_dl_kernel, dim3((unsigned)((own + 255) / 256)), dim3(256), 0, st, os->dl.get(), (int64_t)os->first,
-                                   os->n_docs, os->row0, row_map, n_map, ns->row0, ns->n_docs, ns->dl.get());
-                HIP_TRY(h, hipGetLastError());
-            }
-        }
-        if (keep_indptr_d) {
-            if ((rc = bm_alloc(h, ns->indptr_d, (size_t)V + 1, what))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(ns->indptr_d, ns->indptr_h.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
-        }
-        if (V) HIP_TRY(h, hipMemcpyAsync(ns->meta, meta_h.data(), (size_t)V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
-        if (nnz > 0) {
-            if (packed)
-                hipLaunchKernelGGL(bm25_compact_scatter_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
-                                   os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
-                                   ns->packed.get(), os->tf16.get(), ns->tf16.get());
-            else
-                hipLaunchKernelGGL(bm25_compact_scatter_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(),
-                                   os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(),
-                                   ns->packed.get(), os->tf16.get(), ns->tf16.get());
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (ns->tab_entries) {
-            hipLaunchKernelGGL(bm25_range_table_kernel, dim3((unsigned)((ns->tab_entries + 255) / 256)), dim3(256), 0, st, ns->meta.get(),
-                               ns->doc.get(), V, ns->tab_entries, ns->range_tab.get());
-            HIP_TRY(h, hipGetLastError());
-        }
+        const int64_t own = os->n_docs - os->first;
+        if (keep && own > 0)
+            bm_launch_1d(bm25_compact_dl_kernel, own, st, os->dl, (int64_t)os->first, os->n_docs, os->row0, row_map, n_map, ns->row0,
+                         ns->n_docs, ns->dl);
+        if (nnz > 0)
+            hipLaunchKernelGGL(packed ? bm25_compact_scatter_kernel<true> : bm25_compact_scatter_kernel<false>, dim3((unsigned)tiles), dim3(256),
+                               0, st, os->doc.get(), os->w.get(), os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(),
+                               ns->doc.get(), ns->w.get(), ns->packed.get(), os->tf16.get(), ns->tf16.get());
+        HIP_TRY(h, hipGetLastError());
         return RAG_OK;
     };
-    const int rc = enqueue();
-    const hipError_t e2 = hipStreamSynchronize(st);          // also after a failure: the host arrays stay alive until read
-    if (rc) return rc;
-    if (e2 != hipSuccess) {
-        h->err = std::string(what) + ": " + hipGetErrorString(e2);
-        return RAG_ERR_HIP;
-    }
-    return RAG_OK;
+    return bm_finish_segment(B, ns, enqueue());
 }
 
 int64_t bm25_base_docs(const rag_ctx* h) { return h->bm25 ? h->bm25->n_docs : 0; }
@@ -1870,33 +1824,23 @@ int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t base_live, 
     const rag_bm25_index* tl = ix->tail.get();
     const int64_t n_map = bm_total_docs(ix), tail_live = covered_live - base_live;
     if (covered_live <= 0) return RAG_OK;
-    auto shape = [](rag_bm25_index* s, int64_t prev_docs, int64_t docs) {
-        s->first = (int)(prev_docs % BM_RANGE);
-        s->row0 = prev_docs - s->first;
-        s->n_docs = s->first + docs;
-        s->n_ranges = (int)((s->n_docs + BM_RANGE - 1) / BM_RANGE);
-    };
-    std::unique_ptr<rag_bm25_index> nb(new rag_bm25_index());
+    const int64_t V = ix->n_terms, Vt = tl ? tl->n_terms : 0;
+    std::unique_ptr<rag_bm25_index> nb;
     int rc;
     if (base_live > 0) {
-        shape(nb.get(), 0, base_live);
+        nb = bm_new_segment(ix, 0, base_live, V);
         if ((rc = bm_remap_segment(h, ix, nb.get(), ix->idf_h, row_map, n_map, false))) return rc;
         if (tl != nullptr && tail_live > 0) {
-            std::unique_ptr<rag_bm25_index> nt(new rag_bm25_index());
-            shape(nt.get(), base_live, tail_live);
+            std::unique_ptr<rag_bm25_index> nt = bm_new_segment(ix, base_live, tail_live, Vt);
             if ((rc = bm_remap_segment(h, tl, nt.get(), ix->idf_h, row_map, n_map, true))) return rc;
             nb->tail = std::move(nt);
             nb->tail_docs = tail_live;
         }
     } else {
-        shape(nb.get(), 0, tail_live);
+        nb = bm_new_segment(ix, 0, tail_live, Vt);
         if ((rc = bm_remap_segment(h, tl, nb.get(), ix->idf_h, row_map, n_map, false))) return rc;
     }
     nb->idf_h = ix->idf_h;
-    nb->neg_idf_absmax = ix->neg_idf_absmax;
-    nb->normalize = ix->normalize;
-    nb->appends = ix->appends;
-    nb->folds = ix->folds;
     *out = nb.release();
     return RAG_OK;
 }
@@ -1969,16 +1913,6 @@ static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, co
 // impact of base and tail recomputed from (tf, doc_len, idf, avgdl) by the load's own arithmetic (bm_tf_factor), the packed
 // base's table by bm25_gtab_kernel; offsets, bracket tables and the postings' order are not touched.
 
-// term of posting p: the last t with meta[t].post <= p (terms with an empty list share their start with the next one)
-__device__ __forceinline__ int64_t bm_term_of(const bm_term_meta* __restrict__ meta, int64_t n_terms, int64_t p) {
-    int64_t lo = 0, hi = n_terms;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (meta[mid].post <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // live document frequencies of one segment, added into df[]: a workgroup takes a tile of BM_CP_TILE consecutive postings (the
 // compaction's tiling), one ballot per 64 postings gives the tile's live mask in LDS, and every term that has postings in the
 // tile - a tile is term-major, so these are the terms t_first .. t_last - counts the set bits of its own stretch: ONE atomic
@@ -1996,7 +1930,8 @@ __global__ __launch_bounds__(256) void bm25_live_df_kernel(const bm_term_meta* _
         if (lane == 0) mw[j * 4 + wv] = m;
     }
     __syncthreads();
-    const int64_t t_first = bm_term_of(meta, n_terms, p0), t_last = bm_term_of(meta, n_terms, pe - 1);
+    const bm_term_by_meta term_of{meta, n_terms};
+    const int64_t t_first = term_of(p0), t_last = term_of(pe - 1);
     for (int64_t t = t_first + tid; t <= t_last; t += 256) {
         const bm_term_meta m = meta[t];
         const int a = (int)(max(m.post, p0) - p0), e = (int)(min(m.post + m.df, pe) - p0);
@@ -2031,17 +1966,6 @@ __global__ __launch_bounds__(256) void bm25_live_len_kernel(const int32_t* __res
         atomicAdd(&out2[0], (unsigned long long)c);
         atomicAdd(&out2[1], (unsigned long long)s);
     }
-}
-
-// the impact rewrite of an unpacked segment: bm25_weights_kernel over the KEPT planes (uint16 tf, the segment's own document
-// lengths, the term found in the metadata instead of the CSR offsets) - one streaming pass, the same product bit for bit
-__global__ void bm25_reweigh_kernel(const bm_term_meta* __restrict__ meta, int64_t n_terms, const int32_t* __restrict__ doc,
-                                    const uint16_t* __restrict__ tf, const int32_t* __restrict__ doc_len, int64_t nnz, double avgdl,
-                                    double k1, double b, const double* __restrict__ idf, double* __restrict__ w) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const int64_t t = bm_term_of(meta, n_terms, p);
-    w[p] = idf[t] * bm_tf_factor((double)tf[p], (double)doc_len[doc[p]], avgdl, k1, b);
 }
 
 __global__ void bm25_set_idf_kernel(bm_term_meta* __restrict__ meta, int64_t n_terms, const double* __restrict__ idf) {
@@ -2122,14 +2046,11 @@ static int bm25_install(rag_ctx* h, bm_refresh_ws& ws, const double* idf, double
     for (rag_bm25_index* sg : {ix, tl}) {
         if (sg == nullptr) continue;
         if (sg->packed != nullptr)
-            hipLaunchKernelGGL(bm25_gtab_kernel, dim3((unsigned)((sg->n_codes + 255) / 256)), dim3(256), 0, st, sg->tfv.get(), sg->dlv.get(), sg->n_codes,
-                               sg->n_dl, avgdl, sg->k1, sg->b, sg->gtab.get());
-        else if (sg->nnz)
-            hipLaunchKernelGGL(bm25_reweigh_kernel, dim3((unsigned)((sg->nnz + 255) / 256)), dim3(256), 0, st, sg->meta.get(), sg->n_terms,
-                               sg->doc.get(), sg->tf16.get(), sg->dl.get(), sg->nnz, avgdl, sg->k1, sg->b, ws.idf.get(), sg->w.get());
-        if (sg->n_terms)
-            hipLaunchKernelGGL(bm25_set_idf_kernel, dim3((unsigned)((sg->n_terms + 255) / 256)), dim3(256), 0, st, sg->meta.get(), sg->n_terms,
-                               ws.idf.get());
+            bm_launch_1d(bm25_gtab_kernel, sg->n_codes, st, sg->tfv, sg->dlv, sg->n_codes, sg->n_dl, avgdl, sg->k1, sg->b, sg->gtab);
+        else if (sg->nnz)                    // every impact again from the KEPT planes: one streaming pass of the load's own kernel
+            bm_launch_1d(bm25_impact_kernel<uint16_t, bm_term_by_meta>, sg->nnz, st, bm_term_by_meta{sg->meta, sg->n_terms}, sg->doc, sg->tf16,
+                         sg->dl, sg->nnz, avgdl, sg->k1, sg->b, ws.idf, sg->w);
+        if (sg->n_terms) bm_launch_1d(bm25_set_idf_kernel, sg->n_terms, st, sg->meta, sg->n_terms, ws.idf);
     }
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -2419,15 +2340,8 @@ int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* o
 
 int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out) {
     if (!indptr || n_docs <= 0 || n_terms < 0) return RAG_ERR_ARG;
-    const int64_t n_pad = (n_docs + BM_RANGE - 1) / BM_RANGE * BM_RANGE;
-    int64_t n_tab = 0;
-    for (int64_t t = 0; t < n_terms; ++t) {
-        const int64_t df = indptr[t + 1] - indptr[t];
-        if (df < 0) return RAG_ERR_ARG;
-        int64_t e_t = 0;
-        bm_plan_term(df, n_pad, &e_t);
-        n_tab += e_t;
-    }
+    const int64_t n_tab = bm_plan_terms(indptr, n_terms, n_docs, nullptr, INT64_MAX, nullptr);
+    if (n_tab < 0) return RAG_ERR_ARG;
     if (postings_out) *postings_out = ((n_terms ? indptr[n_terms] - indptr[0] : 0) + 8) * 12;     // default form: doc i32 + impact f64
     if (meta_out) *meta_out = n_terms * (int64_t)sizeof(bm_term_meta);
     if (table_out) *table_out = n_tab * 4;

@@ -57,17 +57,24 @@ def _texts(rng, n, new_terms):
 
 class Live:
     """An engine that takes inserts + appends, and everything a fresh handle / the oracle need to replay it."""
+    N0 = N0                                                      # rows of the base (SmallShape: 2048 + 5)
+
+    def make_texts(self, n, new_terms):
+        return _texts(self.rng, n, new_terms)
+
+    def base_postings(self):
+        from optimized_rag_amd.bm25 import Bm25Postings
+        return Bm25Postings.from_corpus(self.texts)
 
     def __init__(self, make, seed, opts=(), dense=True):
-        from optimized_rag_amd.bm25 import Bm25Postings
         self.make, self.rng, self.dense = make, np.random.default_rng(seed), dense
-        rng = self.rng
-        self.texts = _texts(rng, N0, False)
+        rng, N0 = self.rng, self.N0
+        self.texts = self.make_texts(N0, False)
         self.emb = rng.standard_normal((N0, D)).astype(np.float32)
         self.ids = np.arange(N0, dtype=np.int64)[::-1].copy() + 70_000
         self.ten = np.where(np.arange(N0) < 2500, rng.integers(0, 2, N0), rng.integers(0, 3, N0)).astype(np.int32)
         self.dead = np.zeros(N0, dtype=bool)
-        self.post = Bm25Postings.from_corpus(self.texts)
+        self.post = self.base_postings()
         self.V0 = len(self.post.vocab)
         self.eng = make()
         for k_, v in opts:
@@ -80,7 +87,7 @@ class Live:
     def new_rows(self, nb):
         rng = self.rng
         n = len(self.ids)
-        return (_texts(rng, nb, True), rng.standard_normal((nb, D)).astype(np.float32),
+        return (self.make_texts(nb, True), rng.standard_normal((nb, D)).astype(np.float32),
                 np.arange(n, n + nb, dtype=np.int64) + 500_000, rng.integers(0, 3, nb).astype(np.int32))
 
     def insert(self, texts, e, ids, ten):
@@ -94,6 +101,11 @@ class Live:
 
     def grow(self, nb):
         texts, e, ids, ten = self.new_rows(nb)
+        self.insert(texts, e, ids, ten)
+        self.post.append_to(self.eng, self.post.extend(texts))
+
+    def grow_with(self, texts):
+        _, e, ids, ten = self.new_rows(len(texts))
         self.insert(texts, e, ids, ten)
         self.post.append_to(self.eng, self.post.extend(texts))
 
@@ -137,6 +149,48 @@ class Live:
     def raw(self, terms_of_query):
         p = self.post
         return O.bm25_scores_csr(p.indptr, p.doc, p.tf, p.doc_len, p.idf, p.avgdl, terms_of_query, p.k1, p.b)
+
+
+class SmallShape:
+    """Mixin in front of Live (or a subclass): the smallest base whose boundary range exists in both segments - 2048 + 5 rows -
+    over at most 64 terms: `s<i>` (s0 .. s35 Zipf, with a bracket table; s36 .. s39 with a handful of postings and none) anywhere,
+    `g<j>` only in appended ones. At most 8 queries. empty_terms: the loaded CSR also holds two terms without postings in front
+    of every other term and one behind them (equal offsets; each with an idf of its own, so an impact computed with a
+    neighbour's idf shows)."""
+    N0 = 2048 + 5
+    empty_terms = False
+
+    def make_texts(self, n, new_terms):
+        rng, out = self.rng, []
+        for L in rng.poisson(8, n):
+            w = [f"s{min(int(x), 36) - 1}" for x in rng.zipf(1.3, int(L))]
+            if rng.random() < 0.01:
+                w += [f"s{36 + int(rng.integers(0, 4))}"]
+            if new_terms and rng.random() < 0.5:
+                w += [f"g{int(j)}" for j in rng.integers(0, 20, 2)]
+            out.append(" ".join(w))
+        return out
+
+    def base_postings(self):
+        p = super().base_postings()
+        if self.empty_terms:
+            V, nnz = len(p.vocab), int(p.indptr[-1])
+            p.indptr = np.concatenate([[0, 0], p.indptr, [nnz]]).astype(np.int64)
+            p.idf = np.concatenate([[0.75, 1.25], p.idf, [0.625]])
+            p.vocab = {"e0": 0, "e1": 1, **{w: t + 2 for w, t in p.vocab.items()}, "elast": V + 2}
+        assert len(p.vocab) <= 44
+        return p
+
+    def queries(self):
+        rng, n = self.rng, len(self.texts)
+        pick = lambda i, m: " ".join(rng.choice((self.texts[i] or "s1").split(), size=m))
+        w0 = next(w for w, t in self.post.vocab.items() if t == (2 if self.empty_terms else 0))     # the first term with postings
+        return [pick(int(rng.integers(0, n)), 4), pick(int(rng.integers(0, n)), 3), pick(n - 1, 3), "g3 g7 g3", f"{w0} s1 e0 elast",
+                "s39 s38 s37 e1", " ".join(f"s{int(x)}" for x in rng.integers(0, 40, 11)) + " g5", "zzz-unknown"]
+
+
+class Small(SmallShape, Live):
+    pass
 
 
 def _t(a):
@@ -345,6 +399,44 @@ def test_fold_by_itself(make):
     st.grow(2500)
     assert st.eng.bm25_segment_stats()["tail_docs"] == 2500
     full_check(st)
+
+
+def test_first_append_is_an_empty_block(make):
+    """the tail's vocabulary is the base's while it holds no posting at all; then postings arrive, then the fold"""
+    st = Small(make, 151, (("bm25_tail_fold", -1),))
+    st.grow_with([""] * 5)
+    s = st.eng.bm25_segment_stats()
+    assert s["tail_docs"] == 5 and s["tail_nnz"] == 0 and s["n_terms"] == st.V0 > 0
+    full_check(st)
+    full_check(st, tenant=2)
+    st.grow(300)
+    assert st.eng.bm25_segment_stats()["tail_nnz"] > 0
+    full_check(st)
+    st.eng.bm25_fold()
+    s = st.eng.bm25_segment_stats()
+    assert s["tail_docs"] == 0 and s["base_docs"] == st.N0 + 305 and s["folds"] == 1
+    full_check(st)
+    full_check(st, tenant=2)
+
+
+def test_vocabulary_grows_behind_a_smaller_tail(make):
+    """old tail: the base's terms only; the next block brings the `g` terms, so old tail ++ block merges V_old < V lists, and the
+    fold merges the base's V_base < V with the tail's"""
+    st = Small(make, 157, (("bm25_tail_fold", -1),))
+    st.grow_with(st.make_texts(200, False))
+    assert st.eng.bm25_segment_stats()["n_terms"] == st.V0
+    full_check(st)
+    st.grow(300)
+    V = st.eng.bm25_segment_stats()["n_terms"]
+    assert st.V0 < V == len(st.post.vocab) <= 64
+    assert all(int(st.post.doc[st.post.indptr[t]]) >= st.N0 + 200 for t in range(st.V0, V))      # new terms: only in the block
+    full_check(st)
+    full_check(st, tenant=2)
+    st.eng.bm25_fold()
+    assert st.eng.bm25_segment_stats()["tail_docs"] == 0
+    full_check(st)
+    st.grow(7)                                                   # and a tail behind the grown base
+    full_check(st, tenant=2)
 
 
 def test_partial_coverage_stays_stale(make):

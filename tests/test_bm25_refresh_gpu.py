@@ -15,7 +15,7 @@ import pytest
 import stream_tools as T
 from oracle import rag_oracle as O
 from test_bm25_compact_gpu import CLive, NO_FOLD, PACKED, TENANTS, _delete_in_both
-from test_bm25_live_gpu import D, N0, check_oracle, full_check, outputs, same_bits
+from test_bm25_live_gpu import D, N0, SmallShape, check_oracle, full_check, outputs, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -68,11 +68,6 @@ class RLive(CLive):
 
     def live(self):
         return ~self.dead[:self.post.n_docs]
-
-    def grow_with(self, texts):
-        _, e, ids, ten = self.new_rows(len(texts))
-        self.insert(texts, e, ids, ten)
-        self.post.append_to(self.eng, self.post.extend(texts))
 
     def counts(self):
         """numpy on the mirror: live postings per term, live documents, the sum of their lengths"""
@@ -238,6 +233,39 @@ def test_seeded_random_sequences(make, seq):
         check_oracle(st, got, ptr, terms, qd, tenant)
     finally:
         st.eng.close()
+
+
+class SmallR(SmallShape, RLive):
+    pass
+
+
+@BOTH
+def test_small_life_cycle_keeps_tf_and_lengths(make, opts):
+    """append -> compaction that keeps the postings -> append -> fold (a packed base refuses it) -> refresh on the 2048 + 5 row
+    base: every step moves the kept tf plane / value tables and the document lengths along"""
+    from optimized_rag_amd import RagError
+    st = SmallR(make, 521, opts)
+    st.grow(300)
+    st.delete(np.unique(np.concatenate([st.rng.integers(0, len(st.ids), 150), np.arange(2040, 2060)])))
+    st.compact()
+    s = st.check_stats()
+    assert s["tail_docs"] > 0 and s["base_docs"] < st.N0
+    full_check(st, fresh_opts=_fresh_opts(opts))
+    st.grow(200)
+    if opts is PACKED:
+        with pytest.raises(RagError, match=r"\(-3\).*bm25_fold: the base postings are packed \(option bm25_packed\)"):
+            st.eng.bm25_fold()
+    else:
+        st.eng.bm25_fold()
+        assert st.check_stats()["tail_docs"] == 0
+    full_check(st, fresh_opts=_fresh_opts(opts))
+    st.delete(st.rng.choice(len(st.ids), 40, replace=False))
+    _, info = st.refresh()
+    assert info["n_docs_live"] == len(st.ids) - 40 and info["idf_max_abs_change"] > 0
+    for t in TENANTS:
+        full_check(st, tenant=t, fresh_opts=_fresh_opts(opts))
+    if opts is PACKED:
+        full_check(st)                                                # and against an UNPACKED load
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------

@@ -77,6 +77,42 @@ def test_every_table_class_against_the_csr_oracle(eng):
         _check(eng, post, queries, k)
 
 
+def test_equal_offsets_on_empty_terms():
+    """A load whose first two terms and whose last term have no postings (equal offsets: the owner of a posting / a table entry is
+    the LAST term that starts at or before it), kept with its term frequencies, then through every builder that looks a term up:
+    an append, the fold, and the impact rewrite of new statistics - each against a fresh load of the merged CSR."""
+    from optimized_rag_amd import RagEngine
+    from test_bm25_live_gpu import Small, full_check
+
+    class EmptyTerms(Small):
+        empty_terms = True
+
+    made = []
+
+    def make(dim=256):
+        made.append(RagEngine(dim=dim, device=0))
+        return made[-1]
+
+    try:
+        st = EmptyTerms(make, 163, (("bm25_tail_fold", -1), ("bm25_keep_tf", 1)))
+        p = st.post
+        assert p.indptr[0] == p.indptr[1] == p.indptr[2] == 0 and p.indptr[-1] == p.indptr[-2] and p.indptr[3] > 0
+        assert (st.eng.bm25_live_counts()[0] == np.diff(p.indptr)).all()
+        full_check(st)                                           # the load itself (check_oracle: the CSR oracle)
+        st.grow(300)
+        full_check(st)
+        full_check(st, tenant=2)
+        st.eng.bm25_fold()
+        full_check(st)
+        p.idf = 0.5 + np.arange(len(p.idf)) / 16.0               # no two neighbours share an idf
+        p.avgdl = 1.5 * p.avgdl
+        st.eng.bm25_set_statistics(p.idf, p.avgdl)
+        full_check(st)
+    finally:
+        for e in made:
+            e.close()
+
+
 def test_all_document_scores_through_the_tables(eng):
     """mode 1 of the range kernel (rag_bm25_scores_host: BM25Okapi.get_scores for every document, the input of hybrid_search's
     linear fusion) on an ad-hoc sized corpus: 9,000 documents (5 ranges), every table class again, raw float64 bit-exact."""
