@@ -45,13 +45,6 @@ int mmr_select_dev(rag_ctx* h, const float* queries_dev, const float* emb_dev, c
                    int top_k, double lam, int variant, int32_t* sel_dev, double* score_dev, hipStream_t st);
 int mmr_select_host(rag_ctx* h, const float* query, const float* emb, int n, int dim, int top_k, double lam, int variant,
                     int32_t* sel_out, double* score_out);
-int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n);
-int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out,
-             hipStream_t st, bool host_ptrs);
-void ce_free(rag_ctx* h);
-int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize);
-int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st, bool host_ptrs);
-int embed_dim(const rag_ctx* h);
 int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev, int Q, int pool,
                        int64_t token_id_base, int L_pair, int cls_id, int sep_id, int32_t* ids_out, int32_t* tt_out, int32_t* lens_out,
                        hipStream_t st);

@@ -553,7 +553,25 @@ struct mx_epi_qkv {
 };
 
 // ---- FFN up-projection: bias + erf-GELU -> h8 (image layout, K = ffn for the down-projection)
-__device__ __forceinline__ float mx_gelu(float x) {     // erf as ce_gelu (cross_encoder.hip): A&S 7.1.26, |erf error| <= 1.5e-7
+// erf-GELU (transformers' "gelu"): 0.5 x (1 + erf(x / sqrt 2)) with erf from Abramowitz & Stegun 7.1.26
+// (|error| <= 1.5e-7, below the 2^-22 resolution of the split-fp16 activations): one rcp, one exp2 and six FMAs
+// instead of libm's branchy erff, which cost as much as the whole K = 384 main loop of the FFN-up GEMM.
+// Both forwards' GELUs live here, side by side, because they are NOT one function: the same erf, but ce_gelu (the split-fp16
+// epilogue, ce_gemm_kernel) finishes in the literal form and mx_gelu (mx_epi_gelu) with one rounding less. Their results differ
+// in the last bit, each forward's logits are pinned to its own, and sharing even the erf part changes the code the compiler
+// schedules around it in both GEMM kernels. A change to one belongs in the other.
+__device__ __forceinline__ float ce_gelu(float x) {
+    const float z = fabsf(x) * 0.70710678118654752440f;
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
+    float p = fmaf(1.061405429f, t, -1.453152027f);
+    p = fmaf(p, t, 1.421413741f);
+    p = fmaf(p, t, -0.284496736f);
+    p = fmaf(p, t, 0.254829592f);
+    const float e = __builtin_amdgcn_exp2f(-z * z * 1.4426950408889634f);
+    const float erf_abs = fmaf(-p * t, e, 1.0f);
+    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
+}
+__device__ __forceinline__ float mx_gelu(float x) {
     const float z = fabsf(x) * 0.70710678118654752440f;
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
     float p = fmaf(1.061405429f, t, -1.453152027f);

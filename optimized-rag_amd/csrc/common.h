@@ -182,10 +182,11 @@ struct rag_ctx : rag_device_mem {
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process
-    bool attr_dense = false, attr_bm25 = false, attr_ce_gemm = false;
-    int attr_ce_attn_lds[3] = {0, 0, 0};
-    int attr_ce_attn_mx_lds[3] = {0, 0, 0};
-    bool attr_ce_mx = false;
+    bool attr_dense = false, attr_bm25 = false;
+    // cross_encoder.hip raise_lds: the dynamic LDS each group of kernels was last raised to. The two GEMM families, and the
+    // attention instantiations by [MX operands][query blocks per wave]: every instantiation is a kernel of its own.
+    int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0;
+    int attr_ce_attn_lds[2][3] = {};
     rag_ce_model* ce = nullptr;
     rag_ce_model* emb = nullptr;             // sentence-embedding encoder (rag_embed_load_host): the K7 kernels behind a mean-pooling head
 };
@@ -254,7 +255,7 @@ static inline int prof_end(rag_ctx* h, int stage, hipStream_t st) {
 
 // ---- ordering of *_host calls behind *_dev calls. A *_dev call leaves its work queued on the caller's stream; the *_host
 // entries run on the handle's private non-blocking stream over the SAME workspaces (dense search state, the models' activation
-// planes) and replace planes a queued call reads, and their host-side bookkeeping (ws_q, q16_dirty, ws_pairs) assumes that
+// planes) and replace planes a queued call reads, and their host-side bookkeeping (ws_q, q16_dirty, the models' workspace sizes) assumes that
 // enqueue order is device order. So a *_host entry first waits for the device when *_dev work was queued since the last wait.
 // Nothing is added to either path while a caller stays with one kind of call: no HIP call, one flag.
 static inline int host_after_dev(rag_ctx* h) {
@@ -342,3 +343,13 @@ int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists
 int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev,
                     hipStream_t st);
 int pairwise_cosine_f64(rag_ctx* h, const double* a_dev, int m, const double* b_dev, int n, int dim, double* out_dev, hipStream_t st);
+// cross_encoder.hip: the cross-encoder (h->ce) and the sentence-embedding encoder (h->emb). ids / tt / lens / out are host
+// arrays (staged, the call waits) or device arrays (queued on st) as host_ptrs says.
+int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n);
+int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
+             bool host_ptrs);
+void ce_free(rag_ctx* h);
+int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize);
+int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
+              bool host_ptrs);
+int embed_dim(const rag_ctx* h);

@@ -49,16 +49,26 @@ struct ce_chunk_bufs {
     dev_buf<float> logits;                                             // staging of one chunk's outputs, [pairs][out_width]
 };
 
-// activation workspace of the split-fp16 forward (sized for ws_tokens); dropped by assigning an empty one
-struct ce_split_ws {
-    int64_t ws_tokens = 0;
-    int ws_pairs = 0, ws_L = 0;
+// What the activation workspaces of both forwards share. Each forward adds its own planes (ce_ensure_ws / mx_ensure_ws);
+// a workspace is dropped by assigning an empty one.
+struct ce_ws_base {
+    int pairs = 0, L = 0;                              // what the workspace was allocated for (0: nothing fits)
+    int64_t tokens = 0;                                // padded rows (a multiple of 256): every plane stride follows it
+    ce_chunk_bufs io;
+    bool fits(int P, int L_) const { return P <= pairs && L_ == L; }
+};
+struct ce_split_ws : ce_ws_base {
     dev_buf<float> y32;                                // pre-LayerNorm sums of the residual GEMMs (fp32 [tokens][hidden])
     dev_buf<half_t> x16, q16, kf16, vf16, ctx16, h16;
-    ce_chunk_bufs io;
+};
+struct ce_mx_ws : ce_ws_base {
+    dev_buf<char> x8, ctx8, h8;                        // residual stream, attention output, FFN intermediate (image layout)
+    dev_buf<char> xc8, cc8, hc8;                       // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
+    dev_buf<int32_t> m_cls;                            // device scalar: rows of the compact tensors (= pairs of the chunk)
+    dev_buf<half_t> qf16, kf16, vf16;                  // Q, K, V in the attention kernel's fragment order (hi | lo planes)
 };
 
-struct rag_ce_model : ce_split_ws {
+struct rag_ce_model {
     rag_ce_config cfg;
     bool embed = false;          // true: sentence-embedding encoder (mean pooling over the tokens, no pooler / classifier head)
     int normalize = 1;           // embed: L2-normalise the pooled vectors
@@ -74,19 +84,12 @@ struct rag_ce_model : ce_split_ws {
     std::vector<Layer> layers;
     dev_buf<float> wp, bp, wc, bc;                     // pooler / classifier fp32
     dev_buf<float> wpT;                                // pooler matrix transposed (mx_pool_classify_kernel)
-    // the MX forward (ce_mx.h: hi16 + lo8 operands) has a workspace of its own: it runs every model whose shape allows it, the
-    // split-fp16 kernels the others (and option ce_mx = -1), and neither path must size or evict the other's buffers
+    // the MX forward (ce_mx.h: hi16 + lo8 operands) runs every model whose shape allows it, the split-fp16 kernels the others
+    // (and option ce_mx = -1); each has a workspace of its own, and neither path must size or evict the other's buffers
     bool mx_ok = false;                                // the shape allows the MX path (hidden 384, ffn a multiple of 384 up to 1536) and its weights are loaded
     bool mx_default = true;                            // option ce_mx = 0 takes the MX path: false when the load-time probe (ce_probe_mx) saw it miss
-    struct MxWs {
-        int pairs = 0, L = 0;
-        int64_t tokens = 0;                            // padded rows (a multiple of 256)
-        dev_buf<char> x8, ctx8, h8;                    // residual stream, attention output, FFN intermediate (image layout)
-        dev_buf<char> xc8, cc8, hc8;                   // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
-        dev_buf<int32_t> m_cls;                        // device scalar: rows of the compact tensors (= pairs of the chunk)
-        dev_buf<half_t> qf16, kf16, vf16;              // Q, K, V in the attention kernel's fragment order (hi | lo planes)
-        ce_chunk_bufs io;
-    } mx;
+    ce_split_ws split;
+    ce_mx_ws mx;
 };
 
 #define CE_BM 128     // output features per tile (MFMA rows)
@@ -101,21 +104,6 @@ struct rag_ce_model : ce_split_ws {
 #define CE_EPI_PLANE16 (16 * 144)                         // one fp16 plane of a 16-token x 64-feature epilogue pass, rows padded to 144 B
 
 enum { EPI_QKV = 0, EPI_GELU = 1, EPI_RESID = 2 };
-
-// erf-GELU (transformers' "gelu"): 0.5 x (1 + erf(x / sqrt 2)) with erf from Abramowitz & Stegun 7.1.26
-// (|error| <= 1.5e-7, below the 2^-22 resolution of the split-fp16 activations): one rcp, one exp2 and six FMAs
-// instead of libm's branchy erff, which cost as much as the whole K = 384 main loop of the FFN-up GEMM.
-__device__ __forceinline__ float ce_gelu(float x) {
-    const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(-z * z * 1.4426950408889634f);
-    const float erf_abs = fmaf(-p * t, e, 1.0f);
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
 
 __device__ __forceinline__ void store_split4(half_t* __restrict__ p, size_t plane, float v0, float v1, float v2, float v3) {
     const half4 hi = {(half_t)v0, (half_t)v1, (half_t)v2, (half_t)v3};
@@ -839,7 +827,42 @@ __global__ void ce_f32_split_kernel(const float* __restrict__ in, half_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-static int chunk_bufs_alloc(rag_ctx* h, ce_chunk_bufs& c, int P, int L, int64_t Mp, int out_width) {
+// Host side. Launches kernel k with every argument converted to the kernel's own parameter type: a dev_buf<T> reads as its T*
+// or const T*, nullptr as whatever pointer the kernel takes. The call sites keep only the casts that really reinterpret.
+template <class... KArgs, class... Args>
+static void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+    hipLaunchKernelGGL(k, grid, block, lds, st, static_cast<KArgs>(args)...);
+}
+
+// Dynamic LDS above the 64 KiB default: hipFuncSetAttribute is per kernel instantiation and per device. `have` is the handle's
+// field for exactly these kernels (common.h attr_ce_*), raised when a launch needs more than they were given so far.
+template <class... K>
+static int raise_lds(rag_ctx* h, int& have, int need, K... kernels) {
+    if (need <= have) return RAG_OK;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, need));
+    have = need;
+    return RAG_OK;
+}
+
+// allocates n elements and enqueues their zero fill on st, the stream the forward runs on (a synchronous hipMemset on the null
+// stream is NOT ordered against a non-blocking stream: the first forward after a reallocation could otherwise start before its
+// buffers were cleared)
+template <class T>
+static int alloc_zeroed(rag_ctx* h, dev_buf<T>& b, size_t n, hipStream_t st) {
+    if (int rc = b.alloc(h, n)) return rc;
+    HIP_TRY(h, hipMemsetAsync(b, 0, n * sizeof(T), st));
+    return RAG_OK;
+}
+
+// Drops workspace w and starts one for P pairs of L tokens: rows padded to 256, the chunk buffers allocated. pairs / L stay 0
+// (nothing fits) until the caller has added its planes.
+template <class W>
+static int ws_renew(rag_ctx* h, W& w, int P, int L, int out_width, hipStream_t st) {
+    HIP_TRY(h, hipStreamSynchronize(st));
+    w = W();
+    const int64_t Mp = w.tokens = round_up((int64_t)P * L, 256);
+    ce_chunk_bufs& c = w.io;
     int rc;
     if ((rc = c.ids.alloc(h, (size_t)Mp))) return rc;
     if ((rc = c.tt.alloc(h, (size_t)Mp))) return rc;
@@ -865,24 +888,24 @@ static int up_f32(rag_ctx* h, const float* src, size_t n, dev_buf<float>& dst) {
     return RAG_OK;
 }
 
-// rows of several fp32 host matrices (same `cols`) concatenated -> one device matrix: split fp16 (hi plane | lo plane) for a
-// half_t destination, the hi16 + lo8 image tensor (ce_mx.h) for a char one
-template <class T>
-static int up_concat(rag_ctx* h, std::vector<const float*> srcs, size_t rows_each, size_t cols, dev_buf<T>& dst) {
-    constexpr bool mx = std::is_same<T, char>::value;
+// rows of several fp32 host matrices (same `cols`) concatenated -> one device matrix in both operand formats: split fp16 (hi
+// plane | lo plane) in dst16 and, when the MX forward can run the model (mx), the hi16 + lo8 image tensor (ce_mx.h) in dst8
+static int up_weight(rag_ctx* h, std::vector<const float*> srcs, size_t rows_each, size_t cols, dev_buf<half_t>& dst16,
+                     dev_buf<char>& dst8, bool mx) {
     const size_t n_each = rows_each * cols, total = n_each * srcs.size();
+    const dim3 grid((unsigned)((total + 255) / 256));
     dev_buf<float> tmp;
     int rc;
     if ((rc = tmp.alloc(h, total))) return rc;
-    if ((rc = dst.alloc(h, (mx ? 3 : 2) * total))) return rc;
     for (size_t i = 0; i < srcs.size(); ++i)
         HIP_TRY(h, hipMemcpyAsync(tmp + i * n_each, srcs[i], n_each * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if constexpr (mx)
-        hipLaunchKernelGGL(mx_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp.get(),
-                           (int)(rows_each * srcs.size()), (int)cols, dst.get());
-    else
-        hipLaunchKernelGGL(ce_f32_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp.get(), dst.get(), (int64_t)total, (int)cols);
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if ((rc = dst16.alloc(h, 2 * total))) return rc;
+    launch(ce_f32_split_kernel, grid, dim3(256), 0, h->stream, tmp, dst16, (int64_t)total, (int)cols);
+    if (mx) {
+        if ((rc = dst8.alloc(h, 3 * total))) return rc;
+        launch(mx_pack_weight_kernel, grid, dim3(256), 0, h->stream, tmp, (int)(rows_each * srcs.size()), (int)cols, dst8);
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));              // tmp is freed on return
     return RAG_OK;
 }
 
@@ -911,28 +934,22 @@ static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* cons
     if ((rc = up_f32(h, T[3], H, m->emb_ln_g))) return rc;
     if ((rc = up_f32(h, T[4], H, m->emb_ln_b))) return rc;
     m->layers.resize(cfg->layers);
-    m->mx_ok = H == MX_TM && F % MX_TM == 0 && F <= 1536;    // one feature tile = the hidden state (LayerNorm in the epilogue); the FFN bias is staged in 6 KiB of LDS
+    const bool mx = m->mx_ok = H == MX_TM && F % MX_TM == 0 && F <= 1536;    // one feature tile = the hidden state (LayerNorm in the epilogue); the FFN bias is staged in 6 KiB of LDS
     for (int l = 0; l < cfg->layers; ++l) {
         const float* const* t = T + 5 + 16 * l;
         auto& ly = m->layers[l];
-        if (m->mx_ok) {
-            if ((rc = up_concat(h, {t[0], t[2], t[4]}, H, H, ly.wqkv8))) return rc;
-            if ((rc = up_concat(h, {t[6]}, H, H, ly.wo8))) return rc;
-            if ((rc = up_concat(h, {t[10]}, F, H, ly.w18))) return rc;
-            if ((rc = up_concat(h, {t[12]}, H, F, ly.w28))) return rc;
-        }
-        if ((rc = up_concat(h, {t[0], t[2], t[4]}, H, H, ly.wqkv))) return rc;
+        if ((rc = up_weight(h, {t[0], t[2], t[4]}, H, H, ly.wqkv, ly.wqkv8, mx))) return rc;
         std::vector<float> bq(3 * H);
         std::memcpy(bq.data(), t[1], H * 4); std::memcpy(bq.data() + H, t[3], H * 4); std::memcpy(bq.data() + 2 * H, t[5], H * 4);
         if ((rc = up_f32(h, bq.data(), 3 * H, ly.bqkv))) return rc;
         HIP_TRY(h, hipStreamSynchronize(h->stream));          // bq is a stack-lifetime buffer
-        if ((rc = up_concat(h, {t[6]}, H, H, ly.wo))) return rc;
+        if ((rc = up_weight(h, {t[6]}, H, H, ly.wo, ly.wo8, mx))) return rc;
         if ((rc = up_f32(h, t[7], H, ly.bo))) return rc;
         if ((rc = up_f32(h, t[8], H, ly.ln1_g))) return rc;
         if ((rc = up_f32(h, t[9], H, ly.ln1_b))) return rc;
-        if ((rc = up_concat(h, {t[10]}, F, H, ly.w1))) return rc;
+        if ((rc = up_weight(h, {t[10]}, F, H, ly.w1, ly.w18, mx))) return rc;
         if ((rc = up_f32(h, t[11], F, ly.b1))) return rc;
-        if ((rc = up_concat(h, {t[12]}, H, F, ly.w2))) return rc;
+        if ((rc = up_weight(h, {t[12]}, H, F, ly.w2, ly.w28, mx))) return rc;
         if ((rc = up_f32(h, t[13], H, ly.b2))) return rc;
         if ((rc = up_f32(h, t[14], H, ly.ln2_g))) return rc;
         if ((rc = up_f32(h, t[15], H, ly.ln2_b))) return rc;
@@ -970,275 +987,14 @@ static size_t kv_plane_halfs(int64_t Mp, size_t H) { return (size_t)Mp * H + 204
 // persistent GEMM grid: one workgroup per compute unit, a multiple of 8 (the XCD-aware tile map)
 static unsigned ce_gemm_grid(const rag_ctx* h) { return (unsigned)(h->n_cu >= 8 ? h->n_cu / 8 * 8 : 256); }
 
-struct ce_planes { size_t x, q, kv, ctx, h; };
-static ce_planes planes_for(const rag_ce_model* m, int64_t Mp) {
-    const size_t H = m->cfg.hidden, F = m->cfg.ffn;
-    return {(size_t)Mp * H, (size_t)Mp * H, kv_plane_halfs(Mp, H), (size_t)Mp * H, (size_t)Mp * F};
-}
-
-template <int QB>
-static int launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, const ce_planes& pp, hipStream_t st, const int32_t* lens_dev) {
-    const int lds = L * 256;                                           // K hi | K lo | V hi | V lo fragment planes
-    int& attr_lds = h->attr_ce_attn_lds[QB];
-    if (lds > attr_lds) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_attention_kernel<QB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_lds = lds;
-    }
-    const int waves = L / (16 * QB);
-    hipLaunchKernelGGL((ce_attention_kernel<QB>), dim3(m->cfg.heads, P), dim3(64 * waves), lds, st, m->q16, m->kf16, m->vf16,
-                       pp.kv, lens_dev, m->io.pair_off, L, m->cfg.hidden, m->cfg.heads,
-                       (int)round_up((int64_t)m->ws_pairs * L, CE_BN), m->ctx16);
-    return RAG_OK;
-}
-
-template <int PER>
-static void launch_ln(rag_ce_model* m, const float* y, const float* g, const float* b, int64_t M, hipStream_t st) {
-    hipLaunchKernelGGL(ce_layernorm_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, y, g, b, m->io.m_packed, m->cfg.hidden,
-                       (float)m->cfg.ln_eps, m->x16);
-}
-
-// lens_in / logits_dev: this chunk's lengths as the caller gave them and its logit slots (the model's staging buffers for
-// host-pointer calls, the caller's own device arrays otherwise); the kernels read the clamped copy the scan writes (io.clen)
-static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, int L_in, hipStream_t st, const int32_t* lens_in, float* logits_dev) {
-    const int H = m->cfg.hidden, F = m->cfg.ffn;
-    const int64_t M = (int64_t)P * L;
-    const int64_t Mp = round_up((int64_t)m->ws_pairs * L, CE_BN);      // plane strides follow the ALLOCATED size
-    const ce_planes pp = planes_for(m, Mp);
-    const int per = H / 64;
-    const float eps = (float)m->cfg.ln_eps;
-    const ce_chunk_bufs& io = m->io;
-    bool& attr = h->attr_ce_gemm;
-    const size_t lds = CE_GEMM_LDS;
-    if (!attr) {
-#define CE_ATTR(E) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_gemm_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CE_ATTR(EPI_QKV) CE_ATTR(EPI_GELU) CE_ATTR(EPI_RESID)
-        attr = true;
-    }
-#define CE_GEMM(E, ...) hipLaunchKernelGGL((ce_gemm_kernel<E>), dim3(n_cu), blk, lds, st, __VA_ARGS__);
-#define CE_PER_DISPATCH(CALL)                                                                 \
-    switch (per) {                                                                            \
-        case 2: CALL(2); break; case 4: CALL(4); break; case 6: CALL(6); break;               \
-        case 8: CALL(8); break; case 10: CALL(10); break; case 12: CALL(12); break;           \
-        case 14: CALL(14); break; case 16: CALL(16); break;                                   \
-        default: h->err = "ce: unsupported hidden size"; return RAG_ERR_ARG;                  \
-    }
-#define EMB(PER) hipLaunchKernelGGL(ce_embed_ln_kernel<PER>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, \
-                                    m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H,            \
-                                    m->cfg.vocab_size, eps, m->x16)
-    // packed row layout of this chunk (no host round trip: grids cover the padded worst case, kernels stop at m_packed)
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_in, P, L_in, io.clen, io.pair_off, io.m_packed);
-    const int32_t* lens_dev = io.clen;
-    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, io.pair_off, P, L, Mp, io.row_pair);
-    CE_PER_DISPATCH(EMB)
-    const dim3 blk(512);
-    const unsigned n_cu = ce_gemm_grid(h);
-    for (int l = 0; l < m->cfg.layers; ++l) {
-        auto& ly = m->layers[l];
-        CE_GEMM(EPI_QKV, ly.wqkv, m->x16,
-                3 * H, H, ly.bqkv, (const half_t*)nullptr, (float*)nullptr, m->q16, m->kf16, m->vf16, pp.kv, H,
-                m->cfg.heads, io.m_packed, (int)Mp)
-        {
-            const int rc = L == 32 ? launch_attention<1>(h, m, P, L, pp, st, lens_dev) : launch_attention<2>(h, m, P, L, pp, st, lens_dev);
-            if (rc != RAG_OK) return rc;
-        }
-        // out-projection + bias + residual -> y32, then LayerNorm -> x16
-#define LN1(PER) launch_ln<PER>(m, m->y32, ly.ln1_g, ly.ln1_b, M, st)
-        CE_GEMM(EPI_RESID, ly.wo, m->ctx16, H, H,
-                ly.bo, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, io.m_packed, (int)Mp)
-        CE_PER_DISPATCH(LN1)
-        // FFN: up-projection + bias + GELU -> h16, down-projection + bias + residual -> y32, then LayerNorm -> x16
-        CE_GEMM(EPI_GELU, ly.w1, m->x16, F, H,
-                ly.b1, (const half_t*)nullptr, (float*)nullptr, m->h16, (half_t*)nullptr, (half_t*)nullptr, (size_t)0,
-                H, m->cfg.heads, io.m_packed, (int)Mp)
-#define LN2(PER) launch_ln<PER>(m, m->y32, ly.ln2_g, ly.ln2_b, M, st)
-        CE_GEMM(EPI_RESID, ly.w2, m->h16, H, F,
-                ly.b2, (const half_t*)m->x16, m->y32, (half_t*)nullptr, (half_t*)nullptr, (half_t*)nullptr, (size_t)0, H, m->cfg.heads, io.m_packed, (int)Mp)
-        CE_PER_DISPATCH(LN2)
-    }
-    if (m->embed)
-        hipLaunchKernelGGL(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, (const half_t*)m->x16, (const int32_t*)io.pair_off, lens_dev, L, H,
-                           m->normalize, logits_dev);
-    else
-        hipLaunchKernelGGL(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, m->x16, m->wp, m->bp, m->wc, m->bc, io.pair_off, H, logits_dev);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
-}
-
-// (re)allocates the activation workspace; the zero fills are enqueued on `st`, the stream the forward runs on (a
-// synchronous hipMemset on the null stream is NOT ordered against a non-blocking stream: the first forward after a
-// reallocation could otherwise start before its buffers were cleared)
-static int ce_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
-    if (P <= m->ws_pairs && L == m->ws_L) return RAG_OK;
-    ce_split_ws& w = *m;
-    w = ce_split_ws();
-    const int64_t Mp = round_up((int64_t)P * L, CE_BN);
-    w.ws_pairs = P;                                      // planes_for() uses the allocated pair count
-    const ce_planes pp = planes_for(m, Mp);
-    int rc;
-    if ((rc = w.x16.alloc(h, 2 * pp.x))) return rc;
-    if ((rc = w.q16.alloc(h, 2 * pp.q))) return rc;
-    if ((rc = w.kf16.alloc(h, 2 * pp.kv))) return rc;
-    if ((rc = w.vf16.alloc(h, 2 * pp.kv))) return rc;
-    if ((rc = w.ctx16.alloc(h, 2 * pp.ctx))) return rc;
-    if ((rc = w.h16.alloc(h, 2 * pp.h))) return rc;
-    if ((rc = w.y32.alloc(h, pp.x))) return rc;
-    if ((rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width))) return rc;
-    // padded token rows are read by the GEMM tiles: keep them finite
-    HIP_TRY(h, hipMemsetAsync(m->x16, 0, 2 * pp.x * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->ctx16, 0, 2 * pp.ctx * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->q16, 0, 2 * pp.q * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->kf16, 0, 2 * pp.kv * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->vf16, 0, 2 * pp.kv * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->h16, 0, 2 * pp.h * 2, st));
-    HIP_TRY(h, hipMemsetAsync(m->y32, 0, pp.x * 4, st));
-    m->ws_pairs = P;
-    m->ws_L = L;
-    m->ws_tokens = Mp;
-    return RAG_OK;
-}
-
-// ---- the MX forward (ce_mx.h): every GEMM on 384-feature x 128-token tiles with hi16 + lo8 operands ---------------------
-static int mx_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
-    auto& w = m->mx;
-    if (P <= w.pairs && L == w.L) return RAG_OK;
-    HIP_TRY(h, hipStreamSynchronize(st));
-    w = rag_ce_model::MxWs();
-    const size_t H = m->cfg.hidden, F = m->cfg.ffn;
-    const int64_t Mp = round_up((int64_t)P * L, 256);
-    const size_t kv = kv_plane_halfs(Mp, H);
-    int rc;
-    if ((rc = w.x8.alloc(h, (size_t)Mp * H * 3))) return rc;
-    if ((rc = w.ctx8.alloc(h, (size_t)Mp * H * 3))) return rc;
-    if ((rc = w.h8.alloc(h, (size_t)Mp * F * 3))) return rc;
-    const int64_t Pp = round_up((int64_t)P, MX_TN);
-    if ((rc = w.xc8.alloc(h, (size_t)Pp * H * 3))) return rc;
-    if ((rc = w.cc8.alloc(h, (size_t)Pp * H * 3))) return rc;
-    if ((rc = w.hc8.alloc(h, (size_t)Pp * F * 3))) return rc;
-    if ((rc = w.m_cls.alloc(h, 1))) return rc;
-    HIP_TRY(h, hipMemsetAsync(w.xc8, 0, (size_t)Pp * H * 3, st));
-    HIP_TRY(h, hipMemsetAsync(w.cc8, 0, (size_t)Pp * H * 3, st));
-    HIP_TRY(h, hipMemsetAsync(w.hc8, 0, (size_t)Pp * F * 3, st));
-    if ((rc = w.qf16.alloc(h, 2 * kv))) return rc;
-    if ((rc = w.kf16.alloc(h, 2 * kv))) return rc;
-    if ((rc = w.vf16.alloc(h, 2 * kv))) return rc;
-    if ((rc = chunk_bufs_alloc(h, w.io, P, L, Mp, m->out_width))) return rc;
-    // rows past a chunk's packed rows are read by the last token tile of every GEMM: keep them finite (zero is a valid image)
-    HIP_TRY(h, hipMemsetAsync(w.x8, 0, (size_t)Mp * H * 3, st));
-    HIP_TRY(h, hipMemsetAsync(w.ctx8, 0, (size_t)Mp * H * 3, st));
-    HIP_TRY(h, hipMemsetAsync(w.h8, 0, (size_t)Mp * F * 3, st));
-    HIP_TRY(h, hipMemsetAsync(w.qf16, 0, 2 * kv * 2, st));
-    HIP_TRY(h, hipMemsetAsync(w.kf16, 0, 2 * kv * 2, st));
-    HIP_TRY(h, hipMemsetAsync(w.vf16, 0, 2 * kv * 2, st));
-    w.pairs = P;
-    w.L = L;
-    w.tokens = Mp;
-    return RAG_OK;
-}
-
-template <int QB>
-static int mx_launch_attention(rag_ctx* h, rag_ce_model* m, int P, int L, size_t kv_plane, hipStream_t st, const int32_t* lens_dev, int max_qblocks) {
-    const int lds = L * 256;
-    int& attr_lds = h->attr_ce_attn_mx_lds[QB];
-    if (lds > attr_lds) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ce_attention_kernel<QB, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_lds = lds;
-    }
-    auto& w = m->mx;
-    if (max_qblocks == 1) {                                  // the [CLS]-only last layer: one wave per (head, pair), no LDS
-        hipLaunchKernelGGL((ce_attention_kernel<1, true, true>), dim3(m->cfg.heads, P), dim3(64), 0, st, (const half_t*)w.qf16,
-                           (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
-                           m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8.get()), 1);
-        return RAG_OK;
-    }
-    hipLaunchKernelGGL((ce_attention_kernel<QB, true>), dim3(m->cfg.heads, P), dim3(64 * (L / (16 * QB))), lds, st, (const half_t*)w.qf16,
-                       (const half_t*)w.kf16, (const half_t*)w.vf16, kv_plane, lens_dev, (const int32_t*)w.io.pair_off, L, m->cfg.hidden,
-                       m->cfg.heads, (int)w.tokens, reinterpret_cast<half_t*>(w.ctx8.get()), max_qblocks);
-    return RAG_OK;
-}
-
-static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, int P, int L, int L_in, hipStream_t st, const int32_t* lens_in, float* logits_dev) {
-    auto& w = m->mx;
-    const int H = m->cfg.hidden, F = m->cfg.ffn;
-    const int64_t M = (int64_t)P * L, Mp = w.tokens;
-    const float eps = (float)m->cfg.ln_eps;
-    const size_t kv_plane = kv_plane_halfs(Mp, H);
-    if (!h->attr_ce_mx) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_qkv>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_gelu>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(mx_gemm_kernel<mx_epi_ln>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_KERNEL_LDS));
-        h->attr_ce_mx = true;
-    }
-    hipLaunchKernelGGL(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, lens_in, P, L_in, w.io.clen, w.io.pair_off, w.io.m_packed);
-    const int32_t* lens_dev = w.io.clen;
-    hipLaunchKernelGGL(ce_pack_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, (const int32_t*)w.io.pair_off, P, L, Mp, w.io.row_pair);
-    hipLaunchKernelGGL(mx_embed_ln_kernel, dim3((unsigned)((M + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, (const int32_t*)w.io.ids, (const int32_t*)w.io.tt,
-                       (const float*)m->word, (const float*)m->pos, (const float*)m->type, (const float*)m->emb_ln_g, (const float*)m->emb_ln_b,
-                       (const int32_t*)w.io.m_packed, (const int32_t*)w.io.row_pair, (const int32_t*)w.io.pair_off, L, m->cfg.vocab_size, eps, w.x8);
-    const unsigned n_cu = ce_gemm_grid(h);
-    const dim3 blk(512);
-    for (int l = 0; l < m->cfg.layers; ++l) {
-        auto& ly = m->layers[l];
-        const bool cls_tail = !m->embed && l == m->cfg.layers - 1;
-        if (cls_tail) {
-            // last layer of a classifier (see below): K and V for every token, Q for the [CLS] rows alone
-            hipLaunchKernelGGL(mx_gather_rows_kernel, dim3((unsigned)(((int64_t)P * 72 + 255) / 256)), dim3(256), 0, st, (const char*)w.x8, (const char*)nullptr,
-                               (const int32_t*)w.io.pair_off, P, H / 32, w.xc8, (char*)nullptr, w.m_cls);
-            hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8 + (size_t)(H / 32) * MX_A_STAGE,
-                               (const char*)w.x8, H / 32, 2, (const int32_t*)w.io.m_packed,
-                               mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 1, (const int32_t*)nullptr, 0});
-            hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8, (const char*)w.xc8, H / 32, 1,
-                               (const int32_t*)w.m_cls, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)w.io.pair_off, P});
-        } else
-        hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_qkv>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wqkv8, (const char*)w.x8, H / 32, 3,
-                           (const int32_t*)w.io.m_packed, mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane, ly.bqkv, (int)(Mp >> 4), 0, (const int32_t*)nullptr, 0});
-        // The classifier reads the [CLS] row of the last layer alone (pooler: hidden_states[:, 0]), and nothing after the last layer's
-        // attention mixes tokens. So in the LAST layer of a classifier only the first 16-query block of every pair goes through
-        // attention, and out-projection, FFN and both LayerNorms run on ONE row per pair (gathered into compact tensors): the same
-        // arithmetic on the rows that are read, nothing computed for the rows that are not - 4.6M rows become 25,600 for a third of
-        // the layer's kernels. An embedding model (mean pooling over all tokens) takes the full path.
-        {
-            const int lim = cls_tail ? 1 : 1 << 20;
-            // one 16-query block per wave up to L = 256 (16 waves per (head, pair)): same-box A/B against two blocks per wave: -2.6 % (four: +9 %)
-            const int rc = L <= 256 ? mx_launch_attention<1>(h, m, P, L, kv_plane, st, lens_dev, lim) : mx_launch_attention<2>(h, m, P, L, kv_plane, st, lens_dev, lim);
-            if (rc != RAG_OK) return rc;
-        }
-        if (cls_tail) {
-            hipLaunchKernelGGL(mx_gather_rows_kernel, dim3((unsigned)(((int64_t)P * 72 + 255) / 256)), dim3(256), 0, st, (const char*)w.ctx8, (const char*)nullptr,
-                               (const int32_t*)w.io.pair_off, P, H / 32, w.cc8, (char*)nullptr, w.m_cls);
-            hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wo8, (const char*)w.cc8, H / 32, 1,
-                               (const int32_t*)w.m_cls, mx_epi_ln{w.xc8, ly.bo, ly.ln1_g, ly.ln1_b, eps});
-            hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_gelu>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w18, (const char*)w.xc8, H / 32, F / MX_TM,
-                               (const int32_t*)w.m_cls, mx_epi_gelu{w.hc8, ly.b1, F / 32});
-            hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w28, (const char*)w.hc8, F / 32, 1,
-                               (const int32_t*)w.m_cls, mx_epi_ln{w.xc8, ly.b2, ly.ln2_g, ly.ln2_b, eps});
-            // the batched pooler pays from ~512 pairs on; a single query's 100 pairs fill more CUs with one workgroup per pair
-            if (P >= 512)
-                hipLaunchKernelGGL(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, (const char*)w.xc8,
-                                   (const float*)m->wpT, (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, P, H, logits_dev);
-            else
-                hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.xc8.get()), (const float*)m->wp,
-                                   (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)nullptr, H, logits_dev);
-            HIP_TRY(h, hipGetLastError());
-            return RAG_OK;
-        }
-        hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.wo8, (const char*)w.ctx8, H / 32, 1,
-                           (const int32_t*)w.io.m_packed, mx_epi_ln{w.x8, ly.bo, ly.ln1_g, ly.ln1_b, eps});
-        hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_gelu>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w18, (const char*)w.x8, H / 32, F / MX_TM,
-                           (const int32_t*)w.io.m_packed, mx_epi_gelu{w.h8, ly.b1, F / 32});
-        hipLaunchKernelGGL((mx_gemm_kernel<mx_epi_ln>), dim3(n_cu), blk, MX_KERNEL_LDS, st, (const char*)ly.w28, (const char*)w.h8, F / 32, 1,
-                           (const int32_t*)w.io.m_packed, mx_epi_ln{w.x8, ly.b2, ly.ln2_g, ly.ln2_b, eps});
-    }
-    if (m->embed)
-        hipLaunchKernelGGL(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), (const int32_t*)w.io.pair_off, lens_dev,
-                           L, H, m->normalize, logits_dev);
-    else
-        hipLaunchKernelGGL(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), (const float*)m->wp,
-                           (const float*)m->bp, (const float*)m->wc, (const float*)m->bc, (const int32_t*)w.io.pair_off, H, logits_dev);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
-}
+// One chunk of a call, all device pointers: [P][L_in] token / type ids, the P lengths as the caller gave them and the chunk's
+// [P][out_width] result slots (the workspace's staging buffers for host-pointer calls, the caller's own arrays otherwise); L is
+// the attention length class L_in was rounded up to.
+struct ce_chunk {
+    const int32_t *ids, *tt, *lens;
+    float* out;
+    int P, L_in, L;
+};
 
 // pads [P][L_in] token arrays to the supported attention length L (>= L_in), pad id 0 / type 0
 __global__ void ce_pad_tokens_kernel(const int32_t* __restrict__ in_ids, const int32_t* __restrict__ in_tt, int P, int L_in, int L,
@@ -1248,6 +1004,226 @@ __global__ void ce_pad_tokens_kernel(const int32_t* __restrict__ in_ids, const i
     const int p = (int)(i / L), t = (int)(i % L);
     ids[i] = t < L_in ? in_ids[(size_t)p * L_in + t] : 0;
     tt[i] = t < L_in ? in_tt[(size_t)p * L_in + t] : 0;
+}
+
+// Start of every chunk: tokens padded to L, then the packed row layout (no host round trip: grids cover the padded worst case,
+// kernels stop at m_packed). Every later kernel reads the clamped lengths the scan writes (io.clen), never c.lens.
+static void chunk_prologue(const ce_ws_base& w, const ce_chunk& c, hipStream_t st) {
+    const ce_chunk_bufs& io = w.io;
+    launch(ce_pad_tokens_kernel, dim3((unsigned)(((int64_t)c.P * c.L + 255) / 256)), dim3(256), 0, st, c.ids, c.tt, c.P, c.L_in, c.L, io.ids, io.tt);
+    launch(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, c.lens, c.P, c.L_in, io.clen, io.pair_off, io.m_packed);
+    launch(ce_pack_rows_kernel, dim3((unsigned)((w.tokens + 255) / 256)), dim3(256), 0, st, io.pair_off, c.P, c.L, w.tokens, io.row_pair);
+}
+
+// Attention of one layer: one workgroup per (head, pair), QB 16-query blocks per wave, on the forward's Q / K / V planes into
+// ctx (MX: the image tensor, which the kernel writes as bytes). max_qblocks = 1 (MX only) is the [CLS]-only last layer of a
+// classifier: one wave per (head, pair), no LDS.
+template <int QB, bool MX>
+static int launch_attention(rag_ctx* h, const rag_ce_model* m, const ce_ws_base& w, const half_t* q, const half_t* kf, const half_t* vf,
+                            half_t* ctx, const ce_chunk& c, hipStream_t st, int max_qblocks = 1 << 20) {
+    const int H = m->cfg.hidden, heads = m->cfg.heads, L = c.L;
+    const size_t kv_plane = kv_plane_halfs(w.tokens, H);
+    const dim3 grid(heads, c.P);
+    if constexpr (MX)
+        if (max_qblocks == 1) {
+            launch(ce_attention_kernel<1, true, true>, grid, dim3(64), 0, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, L, H, heads,
+                   (int)w.tokens, ctx, 1);
+            return RAG_OK;
+        }
+    const int lds = L * 256;                                           // K hi | K lo | V hi | V lo fragment planes
+    if (int rc = raise_lds(h, h->attr_ce_attn_lds[MX][QB], lds, ce_attention_kernel<QB, MX>)) return rc;
+    launch(ce_attention_kernel<QB, MX>, grid, dim3(64 * (L / (16 * QB))), lds, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, L, H, heads,
+           (int)w.tokens, ctx, max_qblocks);
+    return RAG_OK;
+}
+
+// ---- the split-fp16 forward ------------------------------------------------------------------------------------------
+static int ce_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
+    ce_split_ws& w = m->split;
+    if (w.fits(P, L)) return RAG_OK;
+    int rc;
+    if ((rc = ws_renew(h, w, P, L, m->out_width, st))) return rc;
+    const size_t H = m->cfg.hidden, F = m->cfg.ffn, rows = (size_t)w.tokens, kv = kv_plane_halfs(w.tokens, H);
+    // padded token rows are read by the GEMM tiles: keep them finite
+    if ((rc = alloc_zeroed(h, w.x16, 2 * rows * H, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.q16, 2 * rows * H, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.kf16, 2 * kv, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.vf16, 2 * kv, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.ctx16, 2 * rows * H, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.h16, 2 * rows * F, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.y32, rows * H, st))) return rc;
+    w.pairs = P;
+    w.L = L;
+    return RAG_OK;
+}
+
+// calls f(std::integral_constant<int, hidden / 64>()): the per-lane feature count the embedding and LayerNorm kernels are built for
+template <class F>
+static int per_lane_dispatch(rag_ctx* h, int hidden, F&& f) {
+    switch (hidden / 64) {
+        case 2: f(std::integral_constant<int, 2>()); break; case 4: f(std::integral_constant<int, 4>()); break; case 6: f(std::integral_constant<int, 6>()); break;
+        case 8: f(std::integral_constant<int, 8>()); break; case 10: f(std::integral_constant<int, 10>()); break; case 12: f(std::integral_constant<int, 12>()); break;
+        case 14: f(std::integral_constant<int, 14>()); break; case 16: f(std::integral_constant<int, 16>()); break;
+        default: h->err = "ce: unsupported hidden size"; return RAG_ERR_ARG;
+    }
+    return RAG_OK;
+}
+
+// LayerNorm of the residual sums y32 -> x16, one wave per token
+static int ce_layernorm(rag_ctx* h, const rag_ce_model* m, const float* g, const float* b, int64_t M, hipStream_t st) {
+    const ce_split_ws& w = m->split;
+    return per_lane_dispatch(h, m->cfg.hidden, [&](auto per) {
+        launch(ce_layernorm_kernel<decltype(per)::value>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, w.y32, g, b, w.io.m_packed,
+               m->cfg.hidden, (float)m->cfg.ln_eps, w.x16);
+    });
+}
+
+// one split-fp16 GEMM over all packed rows: N output features over K, epilogue E; the outputs an epilogue does not write are null
+template <int E>
+static void ce_gemm(rag_ctx* h, const rag_ce_model* m, hipStream_t st, const half_t* W, const half_t* X, int N, int K, const float* bias,
+                    const half_t* resid, float* out32, half_t* out16, half_t* kf = nullptr, half_t* vf = nullptr, size_t kv_plane = 0) {
+    const ce_split_ws& w = m->split;
+    launch(ce_gemm_kernel<E>, dim3(ce_gemm_grid(h)), dim3(512), CE_GEMM_LDS, st, W, X, N, K, bias, resid, out32, out16, kf, vf, kv_plane,
+           m->cfg.hidden, m->cfg.heads, w.io.m_packed, (int)w.tokens);
+}
+
+static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipStream_t st) {
+    ce_split_ws& w = m->split;                                         // plane strides follow the ALLOCATED size (w.tokens)
+    const ce_chunk_bufs& io = w.io;
+    const int H = m->cfg.hidden, F = m->cfg.ffn, P = c.P, L = c.L;
+    const int64_t M = (int64_t)P * L;
+    int rc;
+    if ((rc = raise_lds(h, h->attr_ce_gemm_lds, CE_GEMM_LDS, ce_gemm_kernel<EPI_QKV>, ce_gemm_kernel<EPI_GELU>, ce_gemm_kernel<EPI_RESID>)))
+        return rc;
+    chunk_prologue(w, c, st);
+    rc = per_lane_dispatch(h, H, [&](auto per) {
+        launch(ce_embed_ln_kernel<decltype(per)::value>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, m->pos,
+               m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H, m->cfg.vocab_size, (float)m->cfg.ln_eps, w.x16);
+    });
+    if (rc) return rc;
+    for (const auto& ly : m->layers) {
+        ce_gemm<EPI_QKV>(h, m, st, ly.wqkv, w.x16, 3 * H, H, ly.bqkv, nullptr, nullptr, w.q16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, H));
+        rc = L == 32 ? launch_attention<1, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st)
+                     : launch_attention<2, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st);
+        if (rc) return rc;
+        // out-projection + bias + residual -> y32, then LayerNorm -> x16
+        ce_gemm<EPI_RESID>(h, m, st, ly.wo, w.ctx16, H, H, ly.bo, w.x16, w.y32, nullptr);
+        if ((rc = ce_layernorm(h, m, ly.ln1_g, ly.ln1_b, M, st))) return rc;
+        // FFN: up-projection + bias + GELU -> h16, down-projection + bias + residual -> y32, then LayerNorm -> x16
+        ce_gemm<EPI_GELU>(h, m, st, ly.w1, w.x16, F, H, ly.b1, nullptr, nullptr, w.h16);
+        ce_gemm<EPI_RESID>(h, m, st, ly.w2, w.h16, H, F, ly.b2, w.x16, w.y32, nullptr);
+        if ((rc = ce_layernorm(h, m, ly.ln2_g, ly.ln2_b, M, st))) return rc;
+    }
+    if (m->embed)
+        launch(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, io.pair_off, io.clen, L, H, m->normalize, c.out);
+    else
+        launch(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, m->wp, m->bp, m->wc, m->bc, io.pair_off, H, c.out);
+    HIP_TRY(h, hipGetLastError());
+    return RAG_OK;
+}
+
+// ---- the MX forward (ce_mx.h): every GEMM on 384-feature x 128-token tiles with hi16 + lo8 operands ---------------------
+static int mx_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
+    ce_mx_ws& w = m->mx;
+    if (w.fits(P, L)) return RAG_OK;
+    int rc;
+    if ((rc = ws_renew(h, w, P, L, m->out_width, st))) return rc;
+    const size_t H = m->cfg.hidden, F = m->cfg.ffn, rows = (size_t)w.tokens, kv = kv_plane_halfs(w.tokens, H);
+    const size_t cls_rows = (size_t)round_up((int64_t)P, MX_TN);
+    // rows past a chunk's packed rows are read by the last token tile of every GEMM: keep them finite (zero is a valid image)
+    if ((rc = alloc_zeroed(h, w.x8, rows * H * 3, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.ctx8, rows * H * 3, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.h8, rows * F * 3, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.xc8, cls_rows * H * 3, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.cc8, cls_rows * H * 3, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.hc8, cls_rows * F * 3, st))) return rc;
+    if ((rc = w.m_cls.alloc(h, 1))) return rc;                         // written by every gather before it is read
+    if ((rc = alloc_zeroed(h, w.qf16, 2 * kv, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.kf16, 2 * kv, st))) return rc;
+    if ((rc = alloc_zeroed(h, w.vf16, 2 * kv, st))) return rc;
+    w.pairs = P;
+    w.L = L;
+    return RAG_OK;
+}
+
+// one MX GEMM over `rows[0]` token rows of X: nk K-steps, n_ft feature tiles of W, epilogue epi
+template <class EPI>
+static void mx_gemm(rag_ctx* h, hipStream_t st, const char* W, const char* X, int nk, int n_ft, const int32_t* rows, EPI epi) {
+    launch(mx_gemm_kernel<EPI>, dim3(ce_gemm_grid(h)), dim3(512), MX_KERNEL_LDS, st, W, X, nk, n_ft, rows, epi);
+}
+
+// QKV projection of the rows[0] rows of X: n_ft feature tiles of (Q, K, V) from tile ft_base on. row_map / n_map: Q of compact
+// rows is scattered to the token rows row_map names (mx_epi_qkv).
+static void mx_qkv(rag_ctx* h, const rag_ce_model* m, const rag_ce_model::Layer& ly, hipStream_t st, int ft_base, int n_ft, const char* X,
+                   const int32_t* rows, const int32_t* row_map = nullptr, int n_map = 0) {
+    const ce_mx_ws& w = m->mx;
+    const int nk = m->cfg.hidden / 32;
+    mx_gemm(h, st, ly.wqkv8 + (size_t)ft_base * nk * MX_A_STAGE, X, nk, n_ft, rows,
+            mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, m->cfg.hidden), ly.bqkv, (int)(w.tokens >> 4), ft_base, row_map, n_map});
+}
+
+// The layer after its attention, on rows[0] rows: out-projection + bias + residual + LayerNorm (attn -> x, in place), FFN-up +
+// bias + GELU (x -> ffn), FFN-down + bias + residual + LayerNorm (ffn -> x, in place)
+static void mx_layer_tail(rag_ctx* h, const rag_ce_model* m, const rag_ce_model::Layer& ly, hipStream_t st, const char* attn, char* x,
+                          char* ffn, const int32_t* rows) {
+    const int H = m->cfg.hidden, F = m->cfg.ffn;
+    const float eps = (float)m->cfg.ln_eps;
+    mx_gemm(h, st, ly.wo8, attn, H / 32, 1, rows, mx_epi_ln{x, ly.bo, ly.ln1_g, ly.ln1_b, eps});
+    mx_gemm(h, st, ly.w18, x, H / 32, F / MX_TM, rows, mx_epi_gelu{ffn, ly.b1, F / 32});
+    mx_gemm(h, st, ly.w28, ffn, F / 32, 1, rows, mx_epi_ln{x, ly.b2, ly.ln2_g, ly.ln2_b, eps});
+}
+
+static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipStream_t st) {
+    ce_mx_ws& w = m->mx;
+    const ce_chunk_bufs& io = w.io;
+    const int H = m->cfg.hidden, P = c.P, L = c.L;
+    int rc;
+    if ((rc = raise_lds(h, h->attr_ce_mx_lds, MX_KERNEL_LDS, mx_gemm_kernel<mx_epi_qkv>, mx_gemm_kernel<mx_epi_gelu>, mx_gemm_kernel<mx_epi_ln>)))
+        return rc;
+    chunk_prologue(w, c, st);
+    launch(mx_embed_ln_kernel, dim3((unsigned)(((int64_t)P * L + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, io.ids, io.tt, m->word,
+           m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, m->cfg.vocab_size, (float)m->cfg.ln_eps, w.x8);
+    half_t* const ctx = reinterpret_cast<half_t*>(w.ctx8.get());       // the attention kernel writes the image tensor as bytes
+    const dim3 gather_grid((unsigned)(((int64_t)P * 72 + 255) / 256));
+    // The classifier reads the [CLS] row of the last layer alone (pooler: hidden_states[:, 0]), and nothing after the last layer's
+    // attention mixes tokens. So in the LAST layer of a classifier only the first 16-query block of every pair goes through
+    // attention, and out-projection, FFN and both LayerNorms run on ONE row per pair (gathered into compact tensors): the same
+    // arithmetic on the rows that are read, nothing computed for the rows that are not - 4.6M rows become 25,600 for a third of
+    // the layer's kernels. An embedding model (mean pooling over all tokens) takes the full path.
+    bool cls_tail = false;
+    for (int l = 0; l < m->cfg.layers; ++l) {
+        const auto& ly = m->layers[l];
+        cls_tail = !m->embed && l == m->cfg.layers - 1;
+        if (cls_tail) {                                                // K and V for every token, Q for the [CLS] rows alone
+            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.x8, nullptr, io.pair_off, P, H / 32, w.xc8, nullptr, w.m_cls);
+            mx_qkv(h, m, ly, st, 1, 2, w.x8, io.m_packed);
+            mx_qkv(h, m, ly, st, 0, 1, w.xc8, w.m_cls, io.pair_off, P);
+        } else
+            mx_qkv(h, m, ly, st, 0, 3, w.x8, io.m_packed);
+        // one 16-query block per wave up to L = 256 (16 waves per (head, pair)): same-box A/B against two blocks per wave: -2.6 % (four: +9 %)
+        const int qblocks = cls_tail ? 1 : 1 << 20;
+        rc = L <= 256 ? launch_attention<1, true>(h, m, w, w.qf16, w.kf16, w.vf16, ctx, c, st, qblocks)
+                      : launch_attention<2, true>(h, m, w, w.qf16, w.kf16, w.vf16, ctx, c, st, qblocks);
+        if (rc) return rc;
+        if (cls_tail) {
+            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.ctx8, nullptr, io.pair_off, P, H / 32, w.cc8, nullptr, w.m_cls);
+            mx_layer_tail(h, m, ly, st, w.cc8, w.xc8, w.hc8, w.m_cls);
+        } else
+            mx_layer_tail(h, m, ly, st, w.ctx8, w.x8, w.h8, io.m_packed);
+    }
+    // head. After a [CLS] tail the classifier's rows are the compact tensor (row p = pair p), else row pair_off[p] of the stream.
+    const char* const cls = cls_tail ? w.xc8 : w.x8;
+    if (m->embed)
+        launch(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), io.pair_off, io.clen, L, H,
+               m->normalize, c.out);
+    else if (cls_tail && P >= 512)
+        // the batched pooler pays from ~512 pairs on; a single query's 100 pairs fill more CUs with one workgroup per pair
+        launch(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, cls, m->wpT, m->bp, m->wc, m->bc, P, H, c.out);
+    else
+        launch(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(cls), m->wp, m->bp, m->wc, m->bc,
+               cls_tail ? nullptr : io.pair_off.get(), H, c.out);
+    HIP_TRY(h, hipGetLastError());
+    return RAG_OK;
 }
 
 // Which forward: the MX kernels (hi16 + lo8 operands, 384 x 128 tiles; ce_mx.h) whenever the SHAPE allows (hidden 384, ffn a multiple
@@ -1273,26 +1249,26 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
     // GEMM workgroups of its one-feature-tile kernels 12-or-13 tiles each: 6 % of that chunk idle)
     const int chunk_max = std::max(1, std::min(P, (int)(chunk_tokens / L)));
     const int chunk = (P + (P + chunk_max - 1) / chunk_max - 1) / ((P + chunk_max - 1) / chunk_max);
-    int rc = use_mx ? mx_ensure_ws(h, m, chunk, L, st) : ce_ensure_ws(h, m, chunk, L, st);
+    // the forward, chosen once: its workspace and its two functions
+    const ce_chunk_bufs& io = use_mx ? m->mx.io : m->split.io;
+    const auto ensure_ws = use_mx ? mx_ensure_ws : ce_ensure_ws;
+    const auto forward_chunk = use_mx ? mx_forward_chunk : ce_forward_chunk;
+    int rc = ensure_ws(h, m, chunk, L, st);
     if (rc) return rc;
     const hipMemcpyKind kin = hipMemcpyHostToDevice, kout = hipMemcpyDeviceToHost;
-    const ce_chunk_bufs& io = use_mx ? m->mx.io : m->io;
     if ((rc = prof_begin(h, 2, st))) return rc;
     for (int p0 = 0; p0 < P; p0 += chunk) {
         const int pc = std::min(chunk, P - p0);
         // host arrays are staged chunk by chunk; device arrays are read (ids, lens) and written (logits) where they are: four
         // small copies less per chunk, 45 us of a single-query call
-        const int32_t *src_ids = ids + (size_t)p0 * L_in, *src_tt = tt + (size_t)p0 * L_in, *lens_dev = lens + p0;
-        float* logits_dev = out + (size_t)p0 * ow;
+        ce_chunk c = {ids + (size_t)p0 * L_in, tt + (size_t)p0 * L_in, lens + p0, out + (size_t)p0 * ow, pc, L_in, L};
         if (host_ptrs) {
-            HIP_TRY(h, hipMemcpyAsync(io.sid, src_ids, (size_t)pc * L_in * 4, kin, st));
-            HIP_TRY(h, hipMemcpyAsync(io.stt, src_tt, (size_t)pc * L_in * 4, kin, st));
-            HIP_TRY(h, hipMemcpyAsync(io.lens, lens_dev, (size_t)pc * 4, kin, st));
-            src_ids = io.sid; src_tt = io.stt; lens_dev = io.lens; logits_dev = io.logits;
+            HIP_TRY(h, hipMemcpyAsync(io.sid, c.ids, (size_t)pc * L_in * 4, kin, st));
+            HIP_TRY(h, hipMemcpyAsync(io.stt, c.tt, (size_t)pc * L_in * 4, kin, st));
+            HIP_TRY(h, hipMemcpyAsync(io.lens, c.lens, (size_t)pc * 4, kin, st));
+            c.ids = io.sid; c.tt = io.stt; c.lens = io.lens; c.out = io.logits;
         }
-        const int64_t n = (int64_t)pc * L;
-        hipLaunchKernelGGL(ce_pad_tokens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_ids, src_tt, pc, L_in, L, io.ids, io.tt);
-        rc = use_mx ? mx_forward_chunk(h, m, pc, L, L_in, st, lens_dev, logits_dev) : ce_forward_chunk(h, m, pc, L, L_in, st, lens_dev, logits_dev);
+        rc = forward_chunk(h, m, c, st);
         if (rc) break;
         if (host_ptrs) HIP_TRY(h, hipMemcpyAsync(out + (size_t)p0 * ow, io.logits, (size_t)pc * ow * 4, kout, st));
     }
@@ -1343,8 +1319,8 @@ static int ce_probe_mx(rag_ctx* h, rag_ce_model* m) {
     std::vector<float> mx(P), sp(P);
     int rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, mx.data(), h->stream, true, true);
     if (!rc) rc = ce_run(h, m, ids.data(), tt.data(), lens.data(), P, L, sp.data(), h->stream, true, false);
-    static_cast<ce_split_ws&>(*m) = ce_split_ws();      // the next call sizes its workspace for its own batch
-    m->mx = rag_ce_model::MxWs();
+    m->split = ce_split_ws();                           // the next call sizes its workspace for its own batch
+    m->mx = ce_mx_ws();
     if (rc) return rc;
     float d = 0.f;
     for (int p = 0; p < P; ++p)

@@ -53,9 +53,6 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
     return rc ? rc : rc2;
 }
 
-int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
-             bool host_ptrs);
-
 // int32 token ids -> the 16-bit resident store (WordPiece vocabularies have < 65536 entries: 30522 for the MiniLM
 // checkpoints); ids outside [0, 65535] are flagged
 __global__ void tokens_narrow_kernel(const int32_t* __restrict__ in, uint16_t* __restrict__ out, int64_t n, int* __restrict__ bad) {

@@ -265,3 +265,92 @@ def test_embedding_multi_chunk_loop(eng, hidden, l_in):
     sel = [0, 9, 10, 30, 151, P - 1]
     ref = B.sentence_embeddings(w, cfg, ids[sel].astype(np.int64), tt[sel].astype(np.int64), lens[sel], fast_erf=True)
     assert np.abs(one[sel] - ref).max() < EMB_TOL
+
+
+# ---- the two forwards on one handle: their workspaces and their kernels' LDS limits are separate -----------------------------
+_TWO_FWD_CFG = dict(vocab_size=2000, hidden=384, layers=2, heads=12, ffn=1536, max_pos=512, type_vocab=2, eps=1e-12)
+
+
+def _load_head(e, w, cfg, head):
+    if head == "classifier":
+        e.ce_load(cfg, _tensors(w, cfg))
+    else:
+        e.embed_load(cfg, _tensors(w, cfg, head=False), normalize=True)
+
+
+def _run_head(e, head, mode, call):
+    fn = e.ce_score if head == "classifier" else e.embed
+    return _with_mode(e, mode, lambda: fn(*call))
+
+
+def _first_call_of_a_fresh_handle(w, cfg, head, mode, call):
+    from optimized_rag_amd import RagEngine
+    fresh = RagEngine(dim=384, device=0)
+    try:
+        _load_head(fresh, w, cfg, head)
+        return _run_head(fresh, head, mode, call)
+    finally:
+        fresh.close()
+
+
+@pytest.mark.parametrize("head", ["classifier", "embedding"])
+def test_workspaces_of_the_two_forwards_are_independent_across_resizes(eng, head):
+    """One handle, alternating forwards: MX with 40 pairs at padded length 64, split-fp16 with 3 pairs at 32, MX with 8 pairs at 64
+    (reuses the larger MX workspace; its last pair has 3 tiles, so its last 32-key block reaches into stale rows), the same split
+    call again, MX with 5 pairs at 100 (reallocates to length class 128). Every result is bit-identical to the same call made as
+    the first call of a fresh handle on that forward: neither forward resizes, evicts or dirties the other's buffers."""
+    cfg = _TWO_FWD_CFG
+    w = B.seeded_weights(cfg, 5150)
+    rng = np.random.default_rng(5150)
+
+    def call(lens, L):
+        lens = np.asarray(lens, dtype=np.int32)
+        return _pairs(rng, cfg, lens, L) + (lens,)
+
+    mx40 = call(rng.integers(1, 65, 40), 64)
+    sp3 = call([32, 5, 17], 32)
+    mx8 = call([64] * 7 + [40], 64)
+    mx5 = call([100, 1, 33, 64, 97], 100)
+    steps = [(1, mx40), (-1, sp3), (1, mx8), (-1, sp3), (1, mx5)]
+    _load_head(eng, w, cfg, head)
+    got = [_run_head(eng, head, mode, c) for mode, c in steps]
+    ref = {}
+    for i, (mode, c) in enumerate(steps):
+        if id(c) not in ref:
+            ref[id(c)] = _first_call_of_a_fresh_handle(w, cfg, head, mode, c)
+        assert np.isfinite(got[i]).all(), (i, got[i])
+        np.testing.assert_array_equal(got[i], ref[id(c)], err_msg=f"step {i}")
+
+
+def test_every_attention_instantiation_raises_its_own_lds_limit():
+    """One pair of 300 tokens is length class 384: 96 KiB of dynamic LDS, the smallest class above the 64 KiB default, so each
+    attention kernel instantiation must have had its own limit raised. One handle scores it on the split-fp16 and then on the MX
+    forward, a second handle in the opposite order: both calls succeed on both, and the second call of each handle gives the
+    bits of the other handle's first. Then 600 pairs at length 64 on the MX forward (the batched pooler, after the [CLS]-only
+    attention launch was used): the first 3 logits are those of the same 3 pairs scored alone."""
+    from optimized_rag_amd import RagEngine
+    cfg = _TWO_FWD_CFG
+    w = B.seeded_weights(cfg, 6160)
+    rng = np.random.default_rng(6160)
+    lens = np.array([300], dtype=np.int32)
+    long_call = _pairs(rng, cfg, lens, 300) + (lens,)
+    a, b = RagEngine(dim=384, device=0), RagEngine(dim=384, device=0)
+    try:
+        _load_head(a, w, cfg, "classifier")
+        _load_head(b, w, cfg, "classifier")
+        a_split = _run_head(a, "classifier", -1, long_call)
+        a_mx = _run_head(a, "classifier", 1, long_call)
+        b_mx = _run_head(b, "classifier", 1, long_call)
+        b_split = _run_head(b, "classifier", -1, long_call)
+        assert np.isfinite(a_split).all() and np.isfinite(b_mx).all()
+        np.testing.assert_array_equal(a_mx, b_mx)
+        np.testing.assert_array_equal(b_split, a_split)
+        lens600 = rng.integers(1, 65, 600).astype(np.int32)
+        ids600, tt600 = _pairs(rng, cfg, lens600, 64)
+        many = _run_head(a, "classifier", 1, (ids600, tt600, lens600))
+        alone = _run_head(a, "classifier", 1, (ids600[:3], tt600[:3], lens600[:3]))
+        assert np.isfinite(many).all()
+        np.testing.assert_array_equal(many[:3], alone)
+    finally:
+        a.close()
+        b.close()
