@@ -630,8 +630,7 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     // bijection of the non-NaN doubles; an accumulator is never -0.0: it starts at +0.0 and x + y is -0.0 only for two -0.0),
     // one compare per document instead of a key conversion and two 64-bit compares; only survivors are converted.
     if (tau_key != nullptr) {
-        const uint64_t tb_ = (tk & 0x8000000000000000ull) ? (tk & 0x7fffffffffffffffull) : ~tk;
-        const double tau_d = tk == 0ull ? -__builtin_inf() : __builtin_bit_cast(double, tb_);
+        const double tau_d = tk == 0ull ? -__builtin_inf() : f64_from_orderable(tk);
         unsigned pass = 0;
 #pragma unroll
         // STRICTLY above tau: the running list already holds k documents with score >= tau, all of them from earlier ranges =
@@ -875,16 +874,13 @@ __global__ __launch_bounds__(256) void bm25_merge_stage_kernel(const uint64_t* _
     uint64_t u0 = sk[0];
     double mx = 1.0;
     if (u0 != 0ull) {
-        u0 = (u0 & 0x8000000000000000ull) ? (u0 & 0x7fffffffffffffffull) : ~u0;
-        const double top = __builtin_bit_cast(double, u0);
+        const double top = f64_from_orderable(u0);
         if (top > 0.0) mx = top;
     }
     if (tid == 0 && raw_max_out) raw_max_out[q] = mx;
     for (int i = tid; i < k; i += 256) {
         const bool ok = sk[i] != 0ull;
-        uint64_t u = sk[i];
-        u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-        const double s = __builtin_bit_cast(double, u);
+        const double s = f64_from_orderable(sk[i]);
         ids_out[(size_t)q * k + i] = ok ? (idmap ? idmap[sr[i]] : id_base + (int64_t)sr[i]) : -1;
         if (rows_out) rows_out[(size_t)q * k + i] = ok ? (int32_t)sr[i] : -1;
         scores_out[(size_t)q * k + i] = ok ? (normalize ? s / mx : s) : 0.0;
@@ -1072,16 +1068,13 @@ __global__ __launch_bounds__(64 * BMS_WAVES) void bm25_merge_select_kernel(const
     uint64_t u0 = wk[0];
     double mx = 1.0;
     if (u0 != 0ull) {
-        u0 = (u0 & 0x8000000000000000ull) ? (u0 & 0x7fffffffffffffffull) : ~u0;
-        const double top = __builtin_bit_cast(double, u0);
+        const double top = f64_from_orderable(u0);
         if (top > 0.0) mx = top;
     }
     if (lane == 0 && raw_max_out) raw_max_out[q] = mx;
     for (int i = lane; i < k; i += 64) {
         const bool ok = wk[i] != 0ull;
-        uint64_t u = wk[i];
-        u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-        const double sc_ = __builtin_bit_cast(double, u);
+        const double sc_ = f64_from_orderable(wk[i]);
         ids_out[(size_t)q * k + i] = ok ? (idmap ? idmap[wr[i]] : id_base + (int64_t)wr[i]) : -1;
         if (rows_out) rows_out[(size_t)q * k + i] = ok ? (int32_t)wr[i] : -1;
         scores_out[(size_t)q * k + i] = ok ? (normalize ? sc_ / mx : sc_) : 0.0;
@@ -1869,14 +1862,7 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
 }
 
 static int bm25_set_attr(rag_ctx* h) {
-    if (!h->attr_bm25) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(bm25_range_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, BM_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(bm25_range_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, BM_LDS_BYTES));
-        h->attr_bm25 = true;
-    }
-    return RAG_OK;
+    return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>);
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone

@@ -41,7 +41,7 @@ struct dev_buf {
     }
     ~dev_buf() { reset(); }
     void reset() {
-        if (p_) hipFree(p_);
+        if (p_) (void)hipFree(p_);
         p_ = nullptr;
         n_ = 0;
     }
@@ -81,6 +81,18 @@ struct rag_options {
     int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 = yes if the load-time probe saw it hold (cross_encoder.hip ce_probe_mx), 1 = yes, -1 = never
 };
 
+// Candidate state of one emit / select pass over `rows` queries (a multiple of RAG_TILE): dense.hip runs the batch through one
+// instance and the re-emission of overflowed queries through a second, one tile wide.
+struct dense_ws {
+    dev_buf<half_t> q16;             // [rows][dim_pad]  fp16 unit query rows; pad rows of a query tile must be zero
+    dev_buf<uint64_t> cand;          // [rows][RAG_CAND_CAP]
+    dev_buf<unsigned> cnt;           // [rows]   emitted candidates (may exceed cap = overflow)
+    dev_buf<float> tau;              // [rows]   emission threshold = k-th best fp16-pass score so far - 2 eps
+    dev_buf<float> bound;            // [rows]   -inf, or +inf once the candidate buffer overflowed (sticky)
+    dev_buf<int> n_sorted;           // [rows]   survivors left in cand[] after the final select
+    int alloc(rag_ctx* h, size_t rows, hipStream_t st);      // (re)allocates every plane and enqueues the zero fill of q16 on st
+};
+
 // Every device allocation of a handle, in two groups so that each can be released as a whole by assigning an empty value:
 // the planes of the dense index (dropped by every index load, dense_free) ...
 struct rag_index_mem {
@@ -100,24 +112,16 @@ struct rag_device_mem : rag_index_mem {
     dev_buf<double> side_scores;     // hybrid_legs: score scratch of the BM25 leg on the side stream
     dev_buf<double> temporal;        // [n_rows] per-row temporal score (linear fusion) or null
     dev_buf<char> lin_ws;            // rag_hybrid_linear_dev: raw BM25 + bias + max of one sub-batch
-    // dense search workspace (sized for ws_q queries)
+    // dense search workspace (sized for ws_q queries): the batch's candidate state, and what only the whole batch needs
+    dense_ws ws;                     // [ws_qpad] rows
     dev_buf<float> q32;              // [ws_q][dim]     staging for host queries
-    dev_buf<half_t> q16;             // [ws_qpad][dim_pad]
-    dev_buf<uint64_t> cand;          // [ws_qpad][RAG_CAND_CAP]
-    dev_buf<unsigned> cnt;           // [ws_qpad]   emitted candidates (may exceed cap = overflow)
-    dev_buf<float> tau;              // [ws_qpad]   emission threshold = k-th best fp16-pass score so far - 2 eps
-    dev_buf<float> bound;            // [ws_qpad]   -inf, or +inf once the candidate buffer overflowed (sticky)
-    dev_buf<int> n_sorted;           // [ws_qpad]   survivors left in cand[] after the final select
     dev_buf<double> exact;           // [ws_qpad][RAG_CAND_CAP] float64 rescored cosines
     dev_buf<int> flag;               // [ws_qpad]   0 done, 2 needs exact scan, 3 scanned
     dev_buf<int> scan_list;          // [ws_qpad]   queries flagged 2 (appended by finalize_kernel; count = stats[7])
     dev_buf<int> stats;              // [8] device counters
-    // second pass for overflowed queries: one 256-query tile of its own (dense.hip)
-    dev_buf<half_t> q16b;
-    dev_buf<uint64_t> candb;
-    dev_buf<unsigned> cntb;
-    dev_buf<float> taub, boundb;
-    dev_buf<int> n_sortedb, ovf_list;
+    // second pass for overflowed queries: one 256-query tile of its own (dense.hip), and the list of those queries
+    dense_ws ws_ovf;                 // [RAG_TILE] rows
+    dev_buf<int> ovf_list;           // [RAG_TILE + 1] overflowed queries (appended by the final select), then their count
     // grow-only device arena of the synchronous *_host entry points: their per-call staging (queries in, results out, partial
     // lists) is carved from it, so an agent-facing call pays no allocation
     dev_buf<char> stage;
@@ -162,7 +166,7 @@ struct rag_ctx : rag_device_mem {
     // call behaves as if it ran after all *_dev work of the handle, on whatever stream that was queued
     bool dev_pending = false;
     int ws_q = 0;                    // queries the dense search workspace is sized for
-    int q16_dirty = 0;               // rows [q16_dirty, ws_qpad) of q16 are known to be zero (pad rows of a query tile must be)
+    int q16_dirty = 0;               // rows [q16_dirty, ws_qpad) of ws.q16 are known to be zero (pad rows of a query tile must be)
     // one lock per handle, taken by every entry point: the reference's DocumentStore.search may be called from up to 10
     // threads (database/connection.py:38-42). *_host calls are then fully thread-safe (they are synchronous inside the
     // lock); *_dev calls are serialised while they enqueue and share the handle's workspaces, so they must target ONE stream.
@@ -181,10 +185,11 @@ struct rag_ctx : rag_device_mem {
     rag_bm25_index* bm25 = nullptr;
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
-    // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process
-    bool attr_dense = false, attr_bm25 = false;
-    // cross_encoder.hip raise_lds: the dynamic LDS each group of kernels was last raised to. The two GEMM families, and the
-    // attention instantiations by [MX operands][query blocks per wave]: every instantiation is a kernel of its own.
+    // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process. raise_lds: the
+    // dynamic LDS each group of kernels was last raised to. dense.hip: the emit instantiations by [DENSE0][SMALLQ][FUSED], the
+    // persistent ones by [FUSED], the select kernel; bm25.hip: the range kernels. cross_encoder.hip: the two GEMM families, and
+    // the attention instantiations by [MX operands][query blocks per wave]: every instantiation is a kernel of its own.
+    int attr_dense_emit_lds[2][2][2] = {}, attr_dense_persist_lds[2] = {}, attr_dense_select_lds = 0, attr_bm25_lds = 0;
     int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0;
     int attr_ce_attn_lds[2][3] = {};
     rag_ce_model* ce = nullptr;
@@ -205,6 +210,43 @@ int dev_buf<T>::alloc(rag_ctx* h, size_t n) {
     reset();
     HIP_TRY(h, hipMalloc(&p_, n * sizeof(T)));
     n_ = n;
+    return RAG_OK;
+}
+
+inline int dense_ws::alloc(rag_ctx* h, size_t rows, hipStream_t st) {
+    int rc;
+    if ((rc = q16.alloc(h, rows * h->dim_pad))) return rc;
+    if ((rc = cand.alloc(h, rows * RAG_CAND_CAP))) return rc;
+    if ((rc = cnt.alloc(h, rows))) return rc;
+    if ((rc = tau.alloc(h, rows))) return rc;
+    if ((rc = bound.alloc(h, rows))) return rc;
+    if ((rc = n_sorted.alloc(h, rows))) return rc;
+    // zero fills go on the search's own stream: a null-stream hipMemset is not ordered against a non-blocking stream
+    HIP_TRY(h, hipMemsetAsync(q16, 0, rows * h->dim_pad * sizeof(half_t), st));
+    return RAG_OK;
+}
+
+// ---- kernel launches. Launches kernel k with every argument converted to the kernel's own parameter type: a dev_buf<T> reads as
+// its T* or const T*, nullptr as whatever pointer the kernel takes. The call sites keep only the casts that really reinterpret.
+template <class... KArgs, class... Args>
+static void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+    hipLaunchKernelGGL(k, grid, block, lds, st, static_cast<KArgs>(args)...);
+}
+
+// what a function returns after its launches: the first launch error since the last check, as h->err
+static inline int launch_status(rag_ctx* h) {
+    HIP_TRY(h, hipGetLastError());
+    return RAG_OK;
+}
+
+// Dynamic LDS above the 64 KiB default: hipFuncSetAttribute is per kernel instantiation and per device. `have` is the handle's
+// field for exactly these kernels (rag_ctx attr_*), raised when a launch needs more than they were given so far.
+template <class... K>
+static int raise_lds(rag_ctx* h, int& have, int need, K... kernels) {
+    if (need <= have) return RAG_OK;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, need));
+    have = need;
     return RAG_OK;
 }
 
@@ -297,12 +339,14 @@ __host__ __device__ static inline uint64_t f64_orderable(double s) {
     uint64_t u = __builtin_bit_cast(uint64_t, s);
     return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
+__host__ __device__ static inline double f64_from_orderable(uint64_t u) {
+    u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
+    return __builtin_bit_cast(double, u);
+}
 
 // entry points implemented per file
 int dense_index_build(rag_ctx* h, const float* emb_dev, int64_t n_rows, hipStream_t st);
 int dense_index_normalize_range(rag_ctx* h, int64_t first_row, int64_t n_rows, hipStream_t st);
-int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                 double* scores_dev, hipStream_t st);
 // linear fusion inputs of one query sub-batch (rag_hybrid_linear_dev): float32 emission bias [Q][bias_ld], float64 raw BM25
 // scores [Q][n] with their per-query divisor, per-row temporal scores (or null), the three weights
 struct dense_fused {
@@ -314,8 +358,13 @@ struct dense_fused {
     const double* mx; const double* temporal;
     double alpha, beta, gamma;
 };
+// fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev (dense.hip)
 int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
                        double* scores_dev, hipStream_t st, const dense_fused* fz);
+static inline int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
+                               double* scores_dev, hipStream_t st) {
+    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr);
+}
 void comm_free(rag_ctx* h);
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
                 int64_t* lists_dev, double* scores_ws_dev, hipStream_t st);

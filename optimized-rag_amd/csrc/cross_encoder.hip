@@ -827,24 +827,8 @@ __global__ void ce_f32_split_kernel(const float* __restrict__ in, half_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side. Launches kernel k with every argument converted to the kernel's own parameter type: a dev_buf<T> reads as its T*
-// or const T*, nullptr as whatever pointer the kernel takes. The call sites keep only the casts that really reinterpret.
-template <class... KArgs, class... Args>
-static void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
-    hipLaunchKernelGGL(k, grid, block, lds, st, static_cast<KArgs>(args)...);
-}
-
-// Dynamic LDS above the 64 KiB default: hipFuncSetAttribute is per kernel instantiation and per device. `have` is the handle's
-// field for exactly these kernels (common.h attr_ce_*), raised when a launch needs more than they were given so far.
-template <class... K>
-static int raise_lds(rag_ctx* h, int& have, int need, K... kernels) {
-    if (need <= have) return RAG_OK;
-    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
-        HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, need));
-    have = need;
-    return RAG_OK;
-}
-
+// Host side (launch() and raise_lds() are common.h's).
+// ------------------------------------------------------------------------------------------------
 // allocates n elements and enqueues their zero fill on st, the stream the forward runs on (a synchronous hipMemset on the null
 // stream is NOT ordered against a non-blocking stream: the first forward after a reallocation could otherwise start before its
 // buffers were cleared)

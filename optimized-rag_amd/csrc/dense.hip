@@ -20,9 +20,19 @@
 #include "common.h"
 
 #include <algorithm>
-#include <unordered_map>
 
-#define WAVE 64
+// |q|^2 of a row in float64, one wave per row, the way exact_cosine_wave accumulates and reduces it (same lane partition, same
+// butterfly: the same bits): for the normalisation below and for callers that score many rows against one query
+__device__ __forceinline__ double exact_norm2_wave(const float* __restrict__ qv, int dim, int lane) {
+    double nq = 0.0;
+    for (int i = lane * 4; i < dim; i += 256) {
+        const float4 a = *reinterpret_cast<const float4*>(qv + i);
+        nq += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nq += __shfl_xor(nq, o);
+    return nq;
+}
 
 // ------------------------------------------------------------------------------------------------
 // K0: one wave per row: out16[row] = fp16(2^7 * x/|x|), zero row when |x| is 0 or not finite. Every other float32 row,
@@ -35,13 +45,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     for (int64_t row = wave_global; row < n_rows; row += n_waves) {
         const float* x = in + row * dim;
-        double acc = 0.0;
-        for (int i = lane * 4; i < dim; i += 256) {
-            float4 v = *reinterpret_cast<const float4*>(x + i);
-            acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        const double acc = exact_norm2_wave(x, dim, lane);
         const bool ok = (acc > 0.0) && (acc < 1e300);          // false for 0, inf and NaN
         // The scale stays in double and so does the product: as a float it overflows to +inf for a norm below 128 / FLT_MAX
         // ~ 3.8e-37 (a row of float32 denormals), the fp16 row is then inf / NaN and no threshold stage ever emits it. In
@@ -160,18 +164,49 @@ __device__ __forceinline__ void load_fragB(FragB& f, const char* base, const int
 // FUSED (rag_hybrid_linear_dev): the score that is thresholded and keyed is the weighted LINEAR fusion
 // alpha * cosine + bias[q][row], bias = beta * bm25_normalised + gamma * temporal precomputed per (query, row) in float32
 // (rag/retrieval.py:302); everything downstream (select, float64 rescoring, ranking) is unchanged.
-#define EMIT_PARAMS                                                                                                   \
-    const half_t *__restrict__ corpus16, const half_t *__restrict__ q16, int Dp, int rtile_begin, int n_rtiles, int n_qtiles,  \
-        int n_rows_valid, int q_valid, const float *__restrict__ tau, unsigned *__restrict__ cnt, uint64_t *__restrict__ cand, \
-        const int32_t *__restrict__ vis, int tenant, const int32_t *__restrict__ tile_list, int tile_mul, int tile_mod,    \
-        int tile_cnt, const int *__restrict__ active_count, const float *__restrict__ bias, int64_t bias_ld, float alpha,      \
-        const int *__restrict__ qmap, const float *__restrict__ qscale, const float *__restrict__ gt
-#define EMIT_PASS                                                                                                     \
-    corpus16, q16, Dp, rtile_begin, n_rtiles, n_qtiles, n_rows_valid, q_valid, tau, cnt, cand, vis, tenant, tile_list,    \
-        tile_mul, tile_mod, tile_cnt, active_count, bias, bias_ld, alpha, qmap, qscale, gt
+// ---- tile universe: all tiles in permuted order, or the tenant's tile list in permuted order (search_tiles) ------
+struct tile_universe {
+    const int32_t* list;     // the tenant's tiles (device) or null: every tile
+    int count;               // tile positions
+    int mul, mod;            // position p -> entry (p * mul) mod mod of the list, or tile (p * mul) mod mod without one
+};
+// The arguments of one emit launch, by value. The host fills it once per search (emit_args_of), then sets the per-pass fields
+// where a pass begins and the per-stage fields where a stage begins.
+struct emit_args {
+    const half_t* corpus16;      // [n_rows_pad][Dp] fp16 (2^7 * unit rows)
+    const half_t* q16;           // per pass: [n_qtiles * 256][Dp] fp16 query rows, pad rows zero
+    int Dp;                      // padded dimension (halfs), a multiple of 128
+    int rtile_begin, n_rtiles;   // per stage: the tile POSITIONS [rtile_begin, rtile_begin + n_rtiles)
+    int n_qtiles;                // per pass: 256-query tiles
+    int n_rows_valid;            // rows of the index (rows past it in the last tile are never emitted)
+    int q_valid;                 // per pass: queries (columns past it are never emitted)
+    const float* tau;            // per pass: [q] emission threshold
+    unsigned* cnt;               // per pass: [q] emitted keys so far
+    uint64_t* cand;              // per pass: [q][RAG_CAND_CAP] keys
+    const int32_t* vis;          // row visibility table (row_visible) or null
+    int tenant;                  // tenant filter or < 0
+    tile_universe tiles;         // which tiles the positions stand for
+    const int* active_count;     // per pass: device count of re-emitted queries (0: the launch has nothing to do) or null
+    const float* bias; int64_t bias_ld;      // FUSED: float32 raw BM25 scores [query][bias_ld]
+    float alpha;                 // FUSED: weight of the cosine
+    const int* qmap;             // per pass, FUSED: column -> query number in the batch (second pass) or null
+    const float* qscale;         // FUSED: [query] beta / max of the query
+    const float* gt;             // FUSED: [row] gamma * temporal or null
+};
 // one 256 x 256 tile; vb = the (virtual) block index that selects it
 template <bool DENSE0, bool SMALLQ, bool FUSED>
-__device__ __forceinline__ void dense_emit_tile(const int vb, EMIT_PARAMS) {
+__device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a) {
+    const half_t *__restrict__ corpus16 = a.corpus16, *__restrict__ q16 = a.q16;
+    const int Dp = a.Dp, rtile_begin = a.rtile_begin, n_rtiles = a.n_rtiles, n_qtiles = a.n_qtiles;
+    const int n_rows_valid = a.n_rows_valid, q_valid = a.q_valid, tenant = a.tenant;
+    const float* __restrict__ tau = a.tau;
+    unsigned* __restrict__ cnt = a.cnt;
+    uint64_t* __restrict__ cand = a.cand;
+    const int32_t *__restrict__ vis = a.vis, *__restrict__ tile_list = a.tiles.list;
+    const int tile_mul = a.tiles.mul, tile_mod = a.tiles.mod, tile_cnt = a.tiles.count;
+    const int *__restrict__ active_count = a.active_count, *__restrict__ qmap = a.qmap;
+    const float *__restrict__ bias = a.bias, *__restrict__ qscale = a.qscale, *__restrict__ gt = a.gt;
+    const int64_t bias_ld = a.bias_ld;  const float alpha = a.alpha;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -382,18 +417,18 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, EMIT_PARAMS) {
 }
 
 template <bool DENSE0, bool SMALLQ, bool FUSED = false>
-__global__ __launch_bounds__(512) void dense_emit_kernel(EMIT_PARAMS) {
-    dense_emit_tile<DENSE0, SMALLQ, FUSED>(blockIdx.x, EMIT_PASS);
+__global__ __launch_bounds__(512) void dense_emit_kernel(emit_args a) {
+    dense_emit_tile<DENSE0, SMALLQ, FUSED>(blockIdx.x, a);
 }
 
 // Second pass (queries whose buffer overflowed): almost always there is nothing to do, and a corpus-sized grid of 128 KiB-LDS
 // workgroups costs ~40 us just to be dispatched and retired. One workgroup per CU walks the tiles instead; idle, the launch
 // costs one read of the device-side count per workgroup.
 template <bool FUSED>
-__global__ __launch_bounds__(512) void dense_emit_persist_kernel(int n_vblocks, EMIT_PARAMS) {
-    if (active_count != nullptr && *active_count == 0) return;
+__global__ __launch_bounds__(512) void dense_emit_persist_kernel(int n_vblocks, emit_args a) {
+    if (a.active_count != nullptr && *a.active_count == 0) return;
     for (int vb = blockIdx.x; vb < n_vblocks; vb += gridDim.x) {
-        dense_emit_tile<false, false, FUSED>(vb, EMIT_PASS);
+        dense_emit_tile<false, false, FUSED>(vb, a);
         __syncthreads();                                   // the next tile's prologue refills LDS stages this tile still reads
     }
 }
@@ -455,28 +490,18 @@ __device__ __forceinline__ void select_wave(uint64_t* __restrict__ c, uint64_t* 
     const uint64_t cut = (uint64_t)f32_orderable(tau_new) << 32;
     n_top = 0;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
+    auto keep = [&](const uint64_t key) {                    // (wave-wide: every lane calls it, with 0 where it has no key)
+        const bool top = key != 0ull && key >= cut;
+        const uint64_t bt = __ballot(top);
+        if (top) {
+            c[n_top + __popcll(bt & lt_mask)] = key;
+            if (copy_to != nullptr) copy_to[n_top + __popcll(bt & lt_mask)] = key;
+        }
+        n_top += __popcll(bt);
+    };
 #pragma unroll
-    for (int e = 0; e < NREG; ++e) {
-        const uint64_t key = kreg[e];
-        const bool top = key != 0ull && key >= cut;
-        const uint64_t bt = __ballot(top);
-        if (top) {
-            c[n_top + __popcll(bt & lt_mask)] = key;
-            if (copy_to != nullptr) copy_to[n_top + __popcll(bt & lt_mask)] = key;
-        }
-        n_top += __popcll(bt);
-    }
-    for (int i0 = 0; i0 < n_spill; i0 += 64) {
-        const int i = i0 + lane;
-        const uint64_t key = i < n_spill ? spill[i] : 0ull;
-        const bool top = key != 0ull && key >= cut;
-        const uint64_t bt = __ballot(top);
-        if (top) {
-            c[n_top + __popcll(bt & lt_mask)] = key;
-            if (copy_to != nullptr) copy_to[n_top + __popcll(bt & lt_mask)] = key;
-        }
-        n_top += __popcll(bt);
-    }
+    for (int e = 0; e < NREG; ++e) keep(kreg[e]);
+    for (int i0 = 0; i0 < n_spill; i0 += 64) keep(i0 + lane < n_spill ? spill[i0 + lane] : 0ull);
 }
 
 // Two jobs ride on it so that an uneventful search launches nothing extra (each idle launch costs ~3-5 us on a small shard):
@@ -539,18 +564,6 @@ __global__ __launch_bounds__(256) void select_kernel(uint64_t* __restrict__ cand
 // K3: float64 cosine of shortlisted rows. One wave per (query, candidate).
 // cos = dot / (sqrt(|q|^2) * sqrt(|c|^2)), 0.0 when a norm is 0 or not finite (rag/retrieval.py:362-371).
 // ------------------------------------------------------------------------------------------------
-// |q|^2 of a query the way exact_cosine_wave accumulates and reduces it (same lane partition, same butterfly: the same bits), for
-// callers that score many rows against one query
-__device__ __forceinline__ double exact_norm2_wave(const float* __restrict__ qv, int dim, int lane) {
-    double nq = 0.0;
-    for (int i = lane * 4; i < dim; i += 256) {
-        const float4 a = *reinterpret_cast<const float4*>(qv + i);
-        nq += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nq += __shfl_xor(nq, o);
-    return nq;
-}
 // KNOWN_NQ: |q|^2 comes from exact_norm2_wave (a third of the float64 work and of the cross-lane steps per row less)
 template <bool KNOWN_NQ = false>
 __device__ __forceinline__ double exact_cosine_wave(const float* __restrict__ qv, const float* __restrict__ cv, int dim,
@@ -595,6 +608,20 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
 // whose buffer overflowed in the second pass too appends itself to the exact-scan list. (Round 2 used three more launches for
 // this - wide_kernel and a flag-list kernel - that an uneventful search paid for without using them.)
 #define FIN_PER_THREAD (RAG_CAND_CAP / 256)
+// result slot <- (row, score); the id is the row's entry of the id table, or id_base + row without one
+__device__ __forceinline__ void write_result(int64_t* __restrict__ ids_out, int32_t* __restrict__ rows_out, double* __restrict__ scores_out,
+                                             size_t slot, const int64_t* __restrict__ ids, int64_t id_base, uint32_t row, double score) {
+    ids_out[slot] = ids ? ids[row] : id_base + (int64_t)row;
+    if (rows_out) rows_out[slot] = (int32_t)row;
+    scores_out[slot] = score;
+}
+// result slot <- nothing found
+__device__ __forceinline__ void write_no_result(int64_t* __restrict__ ids_out, int32_t* __restrict__ rows_out, double* __restrict__ scores_out,
+                                                size_t slot) {
+    ids_out[slot] = -1;
+    if (rows_out) rows_out[slot] = -1;
+    scores_out[slot] = 0.0;
+}
 __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t* __restrict__ cand, const int* __restrict__ n_sorted,
                                                         const double* __restrict__ exact, const float* __restrict__ bound,
                                                         const int64_t* __restrict__ ids, int64_t id_base, int k,
@@ -606,11 +633,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t* __restric
     __shared__ uint32_t rw[RAG_MAX_K];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int m = n_sorted[q];
-    for (int i = tid; i < k; i += 256) {
-        ids_out[(size_t)q * k + i] = -1;
-        if (rows_out) rows_out[(size_t)q * k + i] = -1;
-        scores_out[(size_t)q * k + i] = 0.0;
-    }
+    for (int i = tid; i < k; i += 256) write_no_result(ids_out, rows_out, scores_out, (size_t)q * k + i);
     const bool overflowed = bound[q] == INFINITY;
     if (overflowed || force_level > 1) {
         if (tid == 0) {
@@ -650,11 +673,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t* __restric
 #pragma unroll
         for (int j = 0; j < FIN_PER_THREAD; ++j) {
             const int i = j * 256 + tid;
-            if (i < m && rank[j] < k) {
-                ids_out[(size_t)q * k + rank[j]] = ids ? ids[r[j]] : id_base + (int64_t)r[j];
-                if (rows_out) rows_out[(size_t)q * k + rank[j]] = (int32_t)r[j];
-                scores_out[(size_t)q * k + rank[j]] = e[j];
-            }
+            if (i < m && rank[j] < k) write_result(ids_out, rows_out, scores_out, (size_t)q * k + rank[j], ids, id_base, r[j], e[j]);
         }
         if (tid == 0) {
             flag[q] = 0;
@@ -672,11 +691,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t* __restric
         const uint32_t r = rw[tid];
         int rank = 0;
         for (int u = 0; u < m; ++u) rank += (sc[u] > e) || (sc[u] == e && rw[u] < r);
-        if (rank < k) {
-            ids_out[(size_t)q * k + rank] = ids ? ids[r] : id_base + (int64_t)r;
-            if (rows_out) rows_out[(size_t)q * k + rank] = (int32_t)r;
-            scores_out[(size_t)q * k + rank] = e;
-        }
+        if (rank < k) write_result(ids_out, rows_out, scores_out, (size_t)q * k + rank, ids, id_base, r, e);
     }
     if (tid == 0) {
         flag[q] = 0;
@@ -787,13 +802,8 @@ __global__ __launch_bounds__(256) void scan_merge_kernel(const uint64_t* __restr
         pos += take;
     }
     for (int i = tid; i < k; i += 256) {
-        const bool ok = sk[i] != 0ull;
-        uint64_t u = sk[i];
-        u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-        const uint32_t r = sr[i];
-        ids_out[(size_t)q * k + i] = ok ? (ids ? ids[r] : id_base + (int64_t)r) : -1;
-        if (rows_out) rows_out[(size_t)q * k + i] = ok ? (int32_t)r : -1;
-        scores_out[(size_t)q * k + i] = ok ? __builtin_bit_cast(double, u) : 0.0;
+        if (sk[i] != 0ull) write_result(ids_out, rows_out, scores_out, (size_t)q * k + i, ids, id_base, sr[i], f64_from_orderable(sk[i]));
+        else write_no_result(ids_out, rows_out, scores_out, (size_t)q * k + i);
     }
     if (tid == 0) {
         flag[q] = 3;
@@ -847,11 +857,7 @@ __global__ void linear_scale_kernel(const unsigned long long* __restrict__ max_k
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= Q) return;
     const unsigned long long kq = max_key[q];
-    double m = -INFINITY;
-    if (kq != 0ull) {
-        const unsigned long long u = (kq & 0x8000000000000000ull) ? (kq & 0x7fffffffffffffffull) : ~kq;
-        m = __builtin_bit_cast(double, u);
-    }
+    const double m = kq != 0ull ? f64_from_orderable(kq) : -INFINITY;
     const double d = m > 0.0 ? m : 1.0;
     mx[q] = d;
     qscale[q] = (float)(beta / d);
@@ -928,32 +934,28 @@ static int ensure_workspace(rag_ctx* h, int Q, hipStream_t st) {
     const size_t qpad = (size_t)round_up(Q, RAG_TILE);
     int rc;
     if ((rc = h->q32.alloc(h, (size_t)Q * h->dim))) return rc;
-    if ((rc = h->q16.alloc(h, qpad * h->dim_pad))) return rc;
-    if ((rc = h->cand.alloc(h, qpad * RAG_CAND_CAP))) return rc;
-    if ((rc = h->cnt.alloc(h, qpad))) return rc;
-    if ((rc = h->tau.alloc(h, qpad))) return rc;
-    if ((rc = h->bound.alloc(h, qpad))) return rc;
-    if ((rc = h->n_sorted.alloc(h, qpad))) return rc;
+    if ((rc = h->ws.alloc(h, qpad, st))) return rc;
+    h->q16_dirty = 0;
     if ((rc = h->exact.alloc(h, qpad * RAG_CAND_CAP))) return rc;
     if ((rc = h->flag.alloc(h, qpad))) return rc;
     if ((rc = h->scan_list.alloc(h, qpad))) return rc;
     if ((rc = h->stats.reserve(h, 8))) return rc;
-    // zero fills go on the search's own stream: a null-stream hipMemset is not ordered against a non-blocking stream
-    HIP_TRY(h, hipMemsetAsync(h->q16, 0, qpad * h->dim_pad * sizeof(half_t), st));
-    h->q16_dirty = 0;
-    if (!h->q16b) {      // second pass (overflowed queries): one 256-query tile, allocated once per handle
-        if ((rc = h->q16b.alloc(h, (size_t)RAG_TILE * h->dim_pad))) return rc;
-        if ((rc = h->candb.alloc(h, (size_t)RAG_TILE * RAG_CAND_CAP))) return rc;
-        if ((rc = h->cntb.alloc(h, RAG_TILE))) return rc;
-        if ((rc = h->taub.alloc(h, RAG_TILE))) return rc;
-        if ((rc = h->boundb.alloc(h, RAG_TILE))) return rc;
-        if ((rc = h->n_sortedb.alloc(h, RAG_TILE))) return rc;
+    if (!h->ws_ovf.q16) {      // second pass (overflowed queries): one 256-query tile, allocated once per handle
+        if ((rc = h->ws_ovf.alloc(h, RAG_TILE, st))) return rc;
         if ((rc = h->ovf_list.alloc(h, RAG_TILE + 1))) return rc;
-        HIP_TRY(h, hipMemsetAsync(h->ovf_list, 0, (RAG_TILE + 1) * sizeof(int), st));
-        HIP_TRY(h, hipMemsetAsync(h->q16b, 0, (size_t)RAG_TILE * h->dim_pad * sizeof(half_t), st));
+        HIP_TRY(h, hipMemsetAsync(h->ovf_list, 0, (RAG_TILE + 1) * sizeof(int), st));      // on st, as dense_ws::alloc's zero fill is
     }
     h->ws_q = Q;
     return RAG_OK;
+}
+
+// K0 launch, four rows per workgroup: one wave per query row, at most NORMALIZE_INDEX_BLOCKS workgroups striding over index rows
+#define NORMALIZE_INDEX_BLOCKS (256 * 16)
+static int launch_normalize(rag_ctx* h, const float* src, half_t* dst, int64_t n_rows, int* bad_rows, int64_t max_blocks, hipStream_t st) {
+    if (n_rows <= 0) return RAG_OK;
+    launch(normalize_rows_kernel, dim3((unsigned)std::min((n_rows + 3) / 4, max_blocks)), dim3(256), 0, st, src, dst, n_rows, h->dim, h->dim_pad,
+           bad_rows);
+    return launch_status(h);
 }
 
 // multiplier of the tile-order permutation p -> (p * a) mod T: close to the golden-ratio conjugate of T (every prefix of
@@ -1039,23 +1041,13 @@ int dense_index_build(rag_ctx* h, const float* emb_dev, int64_t n_rows, hipStrea
     if (h->n_rows_pad > n_rows)
         HIP_TRY(h, hipMemsetAsync(h->emb16 + (size_t)n_rows * h->dim_pad, 0,
                                   (size_t)(h->n_rows_pad - n_rows) * h->dim_pad * sizeof(half_t), st));
-    if (n_rows > 0) {
-        const int grid = (int)std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
-        hipLaunchKernelGGL(normalize_rows_kernel, dim3(grid), dim3(256), 0, st, emb_dev, h->emb16, n_rows, h->dim,
-                           h->dim_pad, h->bad_rows);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return RAG_OK;
+    return launch_normalize(h, emb_dev, h->emb16, n_rows, h->bad_rows, NORMALIZE_INDEX_BLOCKS, st);
 }
 
 // chunked bulk load: fp16 operand rows for master rows [first_row, first_row + n_rows) (already copied into emb32)
 int dense_index_normalize_range(rag_ctx* h, int64_t first_row, int64_t n_rows, hipStream_t st) {
-    if (n_rows <= 0) return RAG_OK;
-    const int grid = (int)std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
-    hipLaunchKernelGGL(normalize_rows_kernel, dim3(grid), dim3(256), 0, st, h->emb32 + (size_t)first_row * h->dim,
-                       h->emb16 + (size_t)first_row * h->dim_pad, n_rows, h->dim, h->dim_pad, h->bad_rows);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    return launch_normalize(h, h->emb32 + (size_t)first_row * h->dim, h->emb16 + (size_t)first_row * h->dim_pad, n_rows, h->bad_rows,
+                            NORMALIZE_INDEX_BLOCKS, st);
 }
 
 static double fp16_pass_eps(int dim_pad) {
@@ -1072,9 +1064,201 @@ static double fp16_pass_eps(int dim_pad) {
     return (2 * u16 + u16 * u16) * 1.01 + 2.0 * dim_pad * u32 + 8 * u32 + 2e-6;
 }
 
-int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                 double* scores_dev, hipStream_t st) {
-    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr);
+// The bound |emitted score - exact score| <= eps of one search. Plain cosine: the fp16 pass's. Fused:
+// |alpha| * (fp16-pass error of the cosine) + the float32 roundings of the emitted score alpha_f * S + bias:
+// bias = float(beta * kw + gamma * t) (2^-24 relative), alpha_f = float(alpha) (2^-24 |alpha| |S|), the fma's own rounding
+// (2^-24 of the result) - together <= 2^-23 * (|alpha| + |beta| * max|kw| + |gamma| * max|t|). RULE for max|kw|: the
+// keyword score is raw / max, in [0, 1] when no raw score is negative - the host-side eps below counts max|kw| = 1. Raw
+// scores below zero (negative idf values) have no such limit, least of all in the `else 1.0` case of
+// rag/retrieval.py:344 where they are not divided at all. linear_scale_kernel bounds them per query from the query's
+// length - none is below -(k1 + 1) * (largest |negative idf|) * (tokens of the query) - and adds
+// 2 * |beta| * max(0, that bound / max - 1) * 2^-21 to the query's two_eps on the device (select_extra.margin). A constant stood here before (8); a long query over common terms scores far below -8, and with
+// alpha small beside beta the float32 rounding of the bias then exceeded the whole margin
+// (tests/test_dense_exactness_gpu.py, negative-idf corpus). max|t| is tracked by rag_index_set_temporal_host / insert.
+static double search_eps(const rag_ctx* h, const dense_fused* fz) {
+    if (!fz) return fp16_pass_eps(h->dim_pad);
+    const double f32_mag = fabs(fz->alpha) + fabs(fz->beta) + fabs(fz->gamma) * h->temporal_absmax;
+    // (round 4: the emitted keyword + recency term is formed in float32 from raw32 * qscale + gt: raw32, qscale and gt each carry one
+    // 2^-24 rounding, the two fmas one each - 2^-21 of the magnitude covers them with a factor of two to spare)
+    return fabs(fz->alpha) * fp16_pass_eps(h->dim_pad) + f32_mag / 2097152.0 + 1e-7;
+}
+
+// the tile universe of one search (tile_universe, beside emit_args): every tile or the tenant's list, and the permutation over it
+static int search_tiles(rag_ctx* h, int tenant, tile_universe* u) {
+    u->list = nullptr;
+    u->count = (int)(round_up(h->n_rows, RAG_TILE) / RAG_TILE);
+    if (tenant >= 0) {
+        ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
+        const auto it = h->tenant_span.find(tenant);
+        u->count = it == h->tenant_span.end() ? 0 : it->second.second;
+        u->list = it == h->tenant_span.end() ? nullptr : h->tenant_tiles + it->second.first;
+    }
+    // RAG_DENSE_LINEAR_ORDER=1 (diagnostic): r1's table order, to price the permutation on one box
+    u->mul = h->opt.dense_linear_order ? 1 : tile_multiplier(u->count);
+    u->mod = std::max(1, u->count);
+    return RAG_OK;
+}
+
+// ---- stage schedule over tile POSITIONS: 8 tiles (2048 rows) scored densely, then ~8x growth each. The expected
+// emission of a stage is ~k x growth keys per query (tau = k-th best of everything seen so far), so the growth is
+// capped by k: it must stay well inside the 4096-entry buffer (r1 used 32x for small batches at any k; at k = 100
+// that sat at the edge of the buffer and a single query could fall into the exact scan).
+// growth_opt: the stage_growth option (>= 2 replaces the built-in growth: diagnostic). Pure host arithmetic.
+struct stage_range { int begin, end; };          // tile positions [begin, end)
+static std::vector<stage_range> stage_plan(int total_tiles, int Q, int k, int growth_opt) {
+    const int stage0_tiles = std::min(total_tiles, RAG_STAGE0_ROWS / RAG_TILE);
+    const int growth = growth_opt >= 2 ? growth_opt
+                                       : std::max(3, std::min(Q <= 64 ? 4 * RAG_STAGE_GROWTH : RAG_STAGE_GROWTH, (Q <= 64 ? 1024 : 1536) / k));
+    std::vector<stage_range> plan;
+    for (int begin = 0; begin < total_tiles; begin = plan.back().end) {
+        int end = plan.empty() ? stage0_tiles : (int)std::min<int64_t>(total_tiles, (int64_t)begin * growth);
+        // avoid a tiny trailing stage (a universe of 9 tiles is ONE dense stage of 9 tiles: the select below must be told so -
+        // it was handed the nominal 2048 slots and lost the ninth tile's rows, found by tests/test_property_gpu.py)
+        if (total_tiles - end < end / 4) end = total_tiles;
+        plan.push_back({begin, end});
+    }
+    return plan;
+}
+
+// ---- the emit dispatch. One launch helper per kernel: an instantiation's LDS size is stated there and nowhere else.
+template <bool DENSE0, bool SMALLQ, bool FUSED>
+static int launch_emit(rag_ctx* h, int n_vblocks, const emit_args& a, hipStream_t st) {          // one workgroup per virtual block
+    constexpr int lds = SMALLQ ? DENSE_LDS_BYTES_SMALLQ : DENSE_LDS_BYTES;
+    if (int rc = raise_lds(h, h->attr_dense_emit_lds[DENSE0][SMALLQ][FUSED], lds, dense_emit_kernel<DENSE0, SMALLQ, FUSED>)) return rc;
+    launch(dense_emit_kernel<DENSE0, SMALLQ, FUSED>, dim3(n_vblocks), dim3(512), lds, st, a);
+    return RAG_OK;
+}
+template <bool FUSED>
+static int launch_emit_persist(rag_ctx* h, int wgs, int n_vblocks, const emit_args& a, hipStream_t st) {     // wgs workgroups walk them
+    if (int rc = raise_lds(h, h->attr_dense_persist_lds[FUSED], DENSE_LDS_BYTES, dense_emit_persist_kernel<FUSED>)) return rc;
+    launch(dense_emit_persist_kernel<FUSED>, dim3(wgs), dim3(512), DENSE_LDS_BYTES, st, n_vblocks, a);
+    return RAG_OK;
+}
+// (stage 0, fused, small batch, persistent workgroups or 0) -> kernel, in this order of precedence: stage 0 is always the dense
+// full-batch kernel, a fused search has no small-batch variant, only the thresholded full-batch kernels have a persistent form.
+static int emit_dispatch(rag_ctx* h, bool stage0, bool fused, bool smallq, int n_vblocks, int persist_wgs, const emit_args& a, hipStream_t st) {
+    int rc;
+    if (stage0) rc = fused ? launch_emit<true, false, true>(h, n_vblocks, a, st) : launch_emit<true, false, false>(h, n_vblocks, a, st);
+    else if (fused) rc = persist_wgs ? launch_emit_persist<true>(h, persist_wgs, n_vblocks, a, st) : launch_emit<false, false, true>(h, n_vblocks, a, st);
+    else if (smallq) rc = launch_emit<false, true, false>(h, n_vblocks, a, st);
+    else rc = persist_wgs ? launch_emit_persist<false>(h, persist_wgs, n_vblocks, a, st) : launch_emit<false, false, false>(h, n_vblocks, a, st);
+    return rc ? rc : launch_status(h);
+}
+
+static int launch_select(rag_ctx* h, const dense_ws& w, int n_queries, int dense0_rows, int k, float two_eps, bool final_stage,
+                         const int* active_count, const select_extra& ex, hipStream_t st) {
+    if (int rc = raise_lds(h, h->attr_dense_select_lds, SELECT_LDS_BYTES, select_kernel)) return rc;
+    launch(select_kernel, dim3((n_queries + 3) / 4), dim3(256), SELECT_LDS_BYTES, st, w.cand, w.cnt, w.tau, w.bound, w.n_sorted, h->stats,
+           n_queries, dense0_rows, k, two_eps, final_stage ? 1 : 0, active_count, ex);
+    return launch_status(h);
+}
+
+// queries -> fp16 unit rows (pad rows of q16 stay zero from allocation time / previous larger batch), and the per-search state
+static int prepare_queries(rag_ctx* h, const float* q_dev, int Q, hipStream_t st) {
+    const dense_ws& w = h->ws;
+    // only rows a previous, larger batch wrote can be non-zero: same-size batches (the agent's one query after another) clear nothing
+    if (h->q16_dirty > Q)
+        HIP_TRY(h, hipMemsetAsync(w.q16 + (size_t)Q * h->dim_pad, 0, (size_t)(h->q16_dirty - Q) * h->dim_pad * sizeof(half_t), st));
+    h->q16_dirty = Q;
+    if (int rc = launch_normalize(h, q_dev, w.q16, Q, nullptr, INT64_MAX, st)) return rc;
+    const int qpad = (int)round_up(Q, RAG_TILE);
+    launch(search_init_kernel, dim3((qpad + 255) / 256), dim3(256), 0, st, w.tau, w.bound, w.cnt, h->stats, h->ovf_list + RAG_TILE, qpad);
+    return launch_status(h);
+}
+
+// ---- first pass: every stage of the plan emits into the batch workspace and is followed by its select; the final select
+// lists the queries whose buffer overflowed (list_overflowed) for the second pass
+static int first_pass(rag_ctx* h, emit_args a, const std::vector<stage_range>& plan, int Q, int k, float two_eps, const dense_fused* fz,
+                      bool list_overflowed, hipStream_t st) {
+    int* const ovf_count = h->ovf_list + RAG_TILE;
+    const float* margin = fz ? fz->margin : nullptr;
+    const select_extra no_extra = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, margin};
+    const select_extra list_extra = {list_overflowed ? h->ovf_list.get() : nullptr, ovf_count, nullptr, nullptr, nullptr, nullptr, margin};
+    const bool smallq = Q <= 128 && !h->opt.no_smallq;
+    const int n_qtiles = (int)round_up(Q, RAG_TILE) / RAG_TILE;
+    const dense_ws& w = h->ws;
+    a.q16 = w.q16; a.tau = w.tau; a.cnt = w.cnt; a.cand = w.cand;         // the pass runs over the batch workspace
+    a.n_qtiles = n_qtiles; a.q_valid = Q;                                  // (active_count and qmap stay null: every query, in place)
+    int rc;
+    for (size_t s = 0; s < plan.size(); ++s) {
+        const bool stage0 = s == 0, last = s + 1 == plan.size();
+        a.rtile_begin = plan[s].begin; a.n_rtiles = plan[s].end - plan[s].begin;
+        const int grid = (int)round_up(a.n_rtiles, 8) * n_qtiles;
+        // experiment (option dense_persist, plain search only): one workgroup per CU walks the stage's tiles
+        const int persist_wgs = h->opt.dense_persist && !fz && grid > 256 ? 256 : 0;
+        // profiled: the thresholded kernel only (stage 0 is 0.2% of the rows)
+        if (!stage0 && (rc = prof_begin(h, 0, st))) return rc;
+        if ((rc = emit_dispatch(h, stage0, fz != nullptr, smallq, grid, persist_wgs, a, st))) return rc;
+        if (!stage0 && (rc = prof_end(h, 0, st))) return rc;
+        if ((rc = launch_select(h, w, Q, stage0 ? a.n_rtiles * RAG_TILE : 0, k, two_eps, last, nullptr, last ? list_extra : no_extra, st)))
+            return rc;
+    }
+    if (plan.empty())         // empty index / unknown tenant: nothing found
+        return launch_select(h, w, Q, 0, k, two_eps, true, nullptr, no_extra, st);
+    return RAG_OK;
+}
+
+// ---- second pass for overflowed queries (device-side early exit when there are none): gathered into the one-tile workspace,
+// re-emitted over all total_tiles positions by one persistent workgroup per CU, selected, and scattered back where they fitted
+static int second_pass(rag_ctx* h, emit_args a, int total_tiles, int k, float two_eps, const dense_fused* fz, hipStream_t st) {
+    const dense_ws &w = h->ws, &o = h->ws_ovf;
+    int* const ovf_count = h->ovf_list + RAG_TILE;
+    launch(overflow_gather_kernel, dim3(RAG_TILE), dim3(256), 0, st, h->ovf_list, ovf_count, w.q16, w.tau, h->dim_pad, o.q16, o.tau, o.bound,
+           o.cnt);
+    a.q16 = o.q16; a.tau = o.tau; a.cnt = o.cnt; a.cand = o.cand;         // the pass runs over the one-tile workspace, every tile position
+    a.n_qtiles = 1; a.q_valid = RAG_TILE; a.rtile_begin = 0; a.n_rtiles = total_tiles;
+    a.active_count = ovf_count; a.qmap = fz ? h->ovf_list.get() : nullptr;
+    if (int rc = emit_dispatch(h, false, fz != nullptr, false, total_tiles, std::min(h->n_cu, total_tiles), a, st)) return rc;
+    const select_extra scatter_extra = {nullptr, nullptr, h->ovf_list, w.cand, w.n_sorted, w.bound, fz ? fz->margin : nullptr};
+    return launch_select(h, o, RAG_TILE, 0, k, two_eps, true, ovf_count, scatter_extra, st);
+}
+
+// ---- float64 scores of the survivors, then the ranking: writes every proven query's top-k and lists the others for the scan
+static int rescore_and_finalize(rag_ctx* h, const float* q_dev, int Q, int k, const dense_fused* fz, int64_t* ids_dev, int32_t* rows_dev,
+                                double* scores_dev, hipStream_t st) {
+    const dense_ws& w = h->ws;
+    launch(rescore_kernel, dim3(4, Q), dim3(256), 0, st, q_dev, h->emb32, w.cand, w.n_sorted, h->exact, h->dim);
+    if (fz) launch(linear_fuse_kernel, dim3(4, Q), dim3(256), 0, st, w.cand, w.n_sorted, h->exact, fz->raw, fz->n, fz->mx, fz->temporal,
+                   fz->alpha, fz->beta, fz->gamma);
+    launch(finalize_kernel, dim3(Q), dim3(256), 0, st, w.cand, w.n_sorted, h->exact, w.bound, h->ids, h->id_base, k, h->opt.force_level, ids_dev,
+           rows_dev, scores_dev, h->flag, h->stats, h->scan_list, h->stats + 7);
+    return launch_status(h);
+}
+
+// ---- exact scan for whatever is still unproven (the queries finalize appended to scan_list, count = stats[7]): rounds of
+// SCAN_ROUND flagged queries, device-side early exit when none
+static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const int32_t* vis, int tenant, const dense_fused* fz,
+                             int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
+    if (h->n_rows == 0) return RAG_OK;
+    const int window = SCAN_CHUNK - k;
+    const int64_t rows_per_block = std::max<int64_t>(1, (h->n_rows + 1023) / 1024 + window - 1) / window * window;
+    const int n_blocks = (int)((h->n_rows + rows_per_block - 1) / rows_per_block);
+    // flagged queries per round: as many as a 512 MB partial-list scratch holds (k = 20 at 1M rows: every query of a
+    // 1024-batch in ONE round = two idle launches per search), at least SCAN_ROUND
+    const int round_q = std::min(Q, std::max(SCAN_ROUND, (int)std::min<size_t>(65535, ((size_t)512 << 20) / ((size_t)n_blocks * k * 12))));
+    if (int rc = h->scan_scores.reserve(h, (size_t)round_q * n_blocks * k * 12)) return rc;         // [entries] u64 keys | [entries] u32 rows
+    uint64_t* pk = reinterpret_cast<uint64_t*>(h->scan_scores.get());
+    uint32_t* pr = reinterpret_cast<uint32_t*>(pk + h->scan_scores.size() / 12);
+    int* const scan_count = h->stats + 7;
+    const dense_fused none = {};
+    const dense_fused& f = fz ? *fz : none;
+    for (int f0 = 0; f0 < Q; f0 += round_q) {
+        launch(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, h->n_rows, rows_per_block, h->dim, k,
+               h->scan_list, scan_count, f0, round_q, pk, pr, f.raw, f.n, f.mx, f.temporal, f.alpha, f.beta, f.gamma);
+        launch(scan_merge_kernel, dim3(std::min(Q - f0, round_q)), dim3(256), 0, st, pk, pr, n_blocks, k, h->ids, h->id_base, h->scan_list,
+               scan_count, f0, h->flag, ids_dev, rows_dev, scores_dev, h->stats);
+    }
+    return launch_status(h);
+}
+
+// what every emit launch of one search has in common; the per-pass and per-stage fields are set where they change
+static emit_args emit_args_of(const rag_ctx* h, const tile_universe& u, const int32_t* vis, int tenant, const dense_fused* fz) {
+    emit_args a = {};
+    a.corpus16 = h->emb16; a.Dp = h->dim_pad; a.n_rows_valid = (int)h->n_rows;
+    a.vis = vis; a.tenant = tenant; a.tiles = u;
+    a.alpha = fz ? (float)fz->alpha : 1.0f;
+    if (fz) { a.bias = fz->bias; a.bias_ld = fz->bias_ld; a.qscale = fz->qscale; a.gt = fz->gt; }
+    return a;
 }
 
 // fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev: the emitted / keyed / ranked score
@@ -1087,197 +1271,21 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
     int rc = ensure_workspace(h, Q, st);
     if (rc) return rc;
     const int32_t* vis = search_vis(h, tenant);            // tenant filter and / or deleted rows (null: every row)
-    // fused: |alpha| * (fp16-pass error of the cosine) + the float32 roundings of the emitted score alpha_f * S + bias:
-    // bias = float(beta * kw + gamma * t) (2^-24 relative), alpha_f = float(alpha) (2^-24 |alpha| |S|), the fma's own rounding
-    // (2^-24 of the result) - together <= 2^-23 * (|alpha| + |beta| * max|kw| + |gamma| * max|t|). RULE for max|kw|: the
-    // keyword score is raw / max, in [0, 1] when no raw score is negative - the host-side eps below counts max|kw| = 1. Raw
-    // scores below zero (negative idf values) have no such limit, least of all in the `else 1.0` case of
-    // rag/retrieval.py:344 where they are not divided at all. linear_scale_kernel bounds them per query from the query's
-    // length - none is below -(k1 + 1) * (largest |negative idf|) * (tokens of the query) - and adds
-    // 2 * |beta| * max(0, that bound / max - 1) * 2^-21 to the query's two_eps on the device (select_extra.margin). A constant stood here before (8); a long query over common terms scores far below -8, and with
-    // alpha small beside beta the float32 rounding of the bias then exceeded the whole margin
-    // (tests/test_dense_exactness_gpu.py, negative-idf corpus). max|t| is tracked by rag_index_set_temporal_host / insert.
-    const double f32_mag = fz ? fabs(fz->alpha) + fabs(fz->beta) + fabs(fz->gamma) * h->temporal_absmax : 0.0;
-    // (round 4: the emitted keyword + recency term is formed in float32 from raw32 * qscale + gt: raw32, qscale and gt each carry one
-    // 2^-24 rounding, the two fmas one each - 2^-21 of the magnitude covers them with a factor of two to spare)
-    const double eps = fz ? fabs(fz->alpha) * fp16_pass_eps(h->dim_pad) + f32_mag / 2097152.0 + 1e-7 : fp16_pass_eps(h->dim_pad);
+    const double eps = search_eps(h, fz);
     const float two_eps = (float)(2.0 * eps * 1.0001 + 1e-7);        // float subtraction in the select kernel: round up
-    const float* bias = fz ? fz->bias : nullptr;
-    const int64_t bias_ld = fz ? fz->bias_ld : 0;
-    const float* qscale = fz ? fz->qscale : nullptr;
-    const float* gt = fz ? fz->gt : nullptr;
-    const float alpha_f = fz ? (float)fz->alpha : 1.0f;
-    const int qpad = (int)round_up(Q, RAG_TILE);
-    const int n_qtiles = qpad / RAG_TILE;
-    float* tau = h->tau;
-    const int force_level = h->opt.force_level;
-
-    // queries -> fp16 unit rows (pad rows of q16 stay zero from allocation time / previous larger batch)
-    // only rows a previous, larger batch wrote can be non-zero: same-size batches (the agent's one query after another) clear nothing
-    if (h->q16_dirty > Q)
-        HIP_TRY(h, hipMemsetAsync(h->q16 + (size_t)Q * h->dim_pad, 0, (size_t)(h->q16_dirty - Q) * h->dim_pad * sizeof(half_t), st));
-    h->q16_dirty = Q;
-    hipLaunchKernelGGL(normalize_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, q_dev, h->q16, (int64_t)Q, h->dim,
-                       h->dim_pad, (int*)nullptr);
-    int* const ovf_count = h->ovf_list + RAG_TILE;
-    hipLaunchKernelGGL(search_init_kernel, dim3((qpad + 255) / 256), dim3(256), 0, st, tau, h->bound, h->cnt, h->stats, ovf_count, qpad);
-    const float* margin = fz ? fz->margin : nullptr;
-    const select_extra no_extra = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, margin};
-    const bool second_pass = !h->opt.no_second_pass;
-    const select_extra list_extra = {second_pass ? h->ovf_list : (int*)nullptr, ovf_count, nullptr, nullptr, nullptr, nullptr, margin};
-
-    bool& attr_set = h->attr_dense;
-    if (!attr_set) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<true, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<false, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES_SMALLQ));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<true, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<false, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_persist_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_persist_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SELECT_LDS_BYTES));
-        attr_set = true;
-    }
-
-    // ---- tile universe: all tiles in permuted order, or the tenant's tile list in permuted order --------------------
-    const int total_tiles_all = (int)(round_up(h->n_rows, RAG_TILE) / RAG_TILE);
-    const int32_t* tile_list = nullptr;
-    int total_tiles = total_tiles_all;
-    if (tenant >= 0) {
-        ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
-        const auto it = h->tenant_span.find(tenant);
-        total_tiles = it == h->tenant_span.end() ? 0 : it->second.second;
-        tile_list = it == h->tenant_span.end() ? nullptr : h->tenant_tiles + it->second.first;
-    }
-    const int n_tiles = total_tiles;
-    // RAG_DENSE_LINEAR_ORDER=1 (diagnostic): r1's table order, to price the permutation on one box
-    const int tile_mul = h->opt.dense_linear_order ? 1 : tile_multiplier(n_tiles), tile_mod = std::max(1, n_tiles);
-    const bool smallq = Q <= 128 && !h->opt.no_smallq;
-
-    // ---- stage schedule over tile POSITIONS: 8 tiles (2048 rows) scored densely, then ~8x growth each. The expected
-    // emission of a stage is ~k x growth keys per query (tau = k-th best of everything seen so far), so the growth is
-    // capped by k: it must stay well inside the 4096-entry buffer (r1 used 32x for small batches at any k; at k = 100
-    // that sat at the edge of the buffer and a single query could fall into the exact scan).
-    const int stage0_tiles = std::min(n_tiles, RAG_STAGE0_ROWS / RAG_TILE);
-    const int growth_env = h->opt.stage_growth >= 2 ? h->opt.stage_growth : 0;       // diagnostic (rag_set_option)
-    const int growth = growth_env ? growth_env
-                                  : std::max(3, std::min(Q <= 64 ? 4 * RAG_STAGE_GROWTH : RAG_STAGE_GROWTH, (Q <= 64 ? 1024 : 1536) / k));
-    int begin = 0, stage = 0;
-    while (begin < total_tiles) {
-        int end;
-        if (stage == 0) end = stage0_tiles;
-        else end = (int)std::min<int64_t>(total_tiles, (int64_t)begin * growth);
-        // avoid a tiny trailing stage (a universe of 9 tiles is ONE dense stage of 9 tiles: the select below must be told so -
-        // it was handed the nominal 2048 slots and lost the ninth tile's rows, found by tests/test_property_gpu.py)
-        if (total_tiles - end < end / 4) end = total_tiles;
-        const int n_rt = end - begin;
-        const int grid = (int)round_up(n_rt, 8) * n_qtiles;
-        if (stage > 0) {                      // the thresholded kernel only (stage 0 is 0.2% of the rows)
-            const int prc = prof_begin(h, 0, st);
-            if (prc) return prc;
-        }
-#define EMIT_ARGS(QP, NQT, QV, TAU, CNT, CAND, ACT, QMAP)                                                        \
-    h->emb16, QP, h->dim_pad, begin_, n_rt_, NQT, (int)h->n_rows, QV, TAU, CNT, CAND, vis, tenant, tile_list, tile_mul, tile_mod, \
-        n_tiles, (const int*)(ACT), bias, bias_ld, alpha_f, (const int*)(QMAP), qscale, gt
-        const int begin_ = begin, n_rt_ = n_rt;
-        if (stage == 0 && fz)
-            hipLaunchKernelGGL((dense_emit_kernel<true, false, true>), dim3(grid), dim3(512), DENSE_LDS_BYTES, st,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        else if (fz)
-            hipLaunchKernelGGL((dense_emit_kernel<false, false, true>), dim3(grid), dim3(512), DENSE_LDS_BYTES, st,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        else if (stage == 0)
-            hipLaunchKernelGGL((dense_emit_kernel<true, false>), dim3(grid), dim3(512), DENSE_LDS_BYTES, st,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        else if (smallq)
-            hipLaunchKernelGGL((dense_emit_kernel<false, true>), dim3(grid), dim3(512), DENSE_LDS_BYTES_SMALLQ, st,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        else if (h->opt.dense_persist && grid > 256)       // experiment: one workgroup per CU walks the stage's tiles
-            hipLaunchKernelGGL((dense_emit_persist_kernel<false>), dim3(256), dim3(512), DENSE_LDS_BYTES, st, grid,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        else
-            hipLaunchKernelGGL((dense_emit_kernel<false, false>), dim3(grid), dim3(512), DENSE_LDS_BYTES, st,
-                               EMIT_ARGS(h->q16, n_qtiles, Q, tau, h->cnt, h->cand, nullptr, nullptr));
-        HIP_TRY(h, hipGetLastError());
-        if (stage > 0) {
-            const int prc = prof_end(h, 0, st);
-            if (prc) return prc;
-        }
-        const bool last = end == total_tiles;
-        hipLaunchKernelGGL(select_kernel, dim3((Q + 3) / 4), dim3(256), SELECT_LDS_BYTES, st, h->cand, h->cnt, tau, h->bound,
-                           h->n_sorted, h->stats, Q, stage == 0 ? n_rt * RAG_TILE : 0, k, two_eps, last ? 1 : 0,
-                           (const int*)nullptr, last ? list_extra : no_extra);
-        HIP_TRY(h, hipGetLastError());
-        begin = end;
-        ++stage;
-    }
-    if (total_tiles == 0) {   // empty index / unknown tenant: nothing found
-        hipLaunchKernelGGL(select_kernel, dim3((Q + 3) / 4), dim3(256), SELECT_LDS_BYTES, st, h->cand, h->cnt, tau, h->bound,
-                           h->n_sorted, h->stats, Q, 0, k, two_eps, 1, (const int*)nullptr, no_extra);
-    }
-
-    // ---- second pass for overflowed queries (device-side early exit when there are none) ---------------------------
-    if (total_tiles > 0 && second_pass) {
-        hipLaunchKernelGGL(overflow_gather_kernel, dim3(RAG_TILE), dim3(256), 0, st, h->ovf_list, ovf_count, h->q16, tau, h->dim_pad,
-                           h->q16b, h->taub, h->boundb, h->cntb);
-        {
-            const int begin_ = 0, n_rt_ = total_tiles;
-            const int n_cu = h->n_cu;
-            if (fz)
-                hipLaunchKernelGGL((dense_emit_persist_kernel<true>), dim3(std::min(n_cu, total_tiles)), dim3(512), DENSE_LDS_BYTES, st, total_tiles,
-                                   EMIT_ARGS(h->q16b, 1, RAG_TILE, h->taub, h->cntb, h->candb, ovf_count, h->ovf_list));
-            else
-                hipLaunchKernelGGL((dense_emit_persist_kernel<false>), dim3(std::min(n_cu, total_tiles)), dim3(512), DENSE_LDS_BYTES, st, total_tiles,
-                                   EMIT_ARGS(h->q16b, 1, RAG_TILE, h->taub, h->cntb, h->candb, ovf_count, nullptr));
-        }
-        const select_extra scatter_extra = {nullptr, nullptr, h->ovf_list, h->cand, h->n_sorted, h->bound, margin};
-        hipLaunchKernelGGL(select_kernel, dim3(RAG_TILE / 4), dim3(256), SELECT_LDS_BYTES, st, h->candb, h->cntb, h->taub, h->boundb,
-                           h->n_sortedb, h->stats, RAG_TILE, 0, k, two_eps, 1, (const int*)ovf_count, scatter_extra);
-        HIP_TRY(h, hipGetLastError());
-    }
-
-    hipLaunchKernelGGL(rescore_kernel, dim3(4, Q), dim3(256), 0, st, q_dev, h->emb32, h->cand, h->n_sorted, h->exact, h->dim);
-    if (fz)
-        hipLaunchKernelGGL(linear_fuse_kernel, dim3(4, Q), dim3(256), 0, st, h->cand, h->n_sorted, h->exact, fz->raw, fz->n, fz->mx,
-                           fz->temporal, fz->alpha, fz->beta, fz->gamma);
-    int* const scan_list = h->scan_list;              // [ws_qpad]: queries that need the float64 scan, appended by finalize
-    int* const scan_count = h->stats + 7;
-    hipLaunchKernelGGL(finalize_kernel, dim3(Q), dim3(256), 0, st, h->cand, h->n_sorted, h->exact, h->bound, h->ids, h->id_base, k,
-                       force_level, ids_dev, rows_dev, scores_dev, h->flag, h->stats, scan_list, scan_count);
-    HIP_TRY(h, hipGetLastError());
-    // exact scan for whatever is still unproven: rounds of SCAN_ROUND flagged queries, device-side early exit when none
-    if (h->n_rows > 0) {
-        const int window = SCAN_CHUNK - k;
-        const int64_t rows_per_block = std::max<int64_t>(1, (h->n_rows + 1023) / 1024 + window - 1) / window * window;
-        const int n_blocks = (int)((h->n_rows + rows_per_block - 1) / rows_per_block);
-        // flagged queries per round: as many as a 512 MB partial-list scratch holds (k = 20 at 1M rows: every query of a
-        // 1024-batch in ONE round = two idle launches per search), at least SCAN_ROUND
-        const int round_q = std::min(Q, std::max(SCAN_ROUND, (int)std::min<size_t>(65535, ((size_t)512 << 20) / ((size_t)n_blocks * k * 12))));
-        const size_t need = (size_t)round_q * n_blocks * k;
-        if (int rc = h->scan_scores.reserve(h, need * 12)) return rc;         // [entries] u64 keys | [entries] u32 rows
-        uint64_t* pk = reinterpret_cast<uint64_t*>(h->scan_scores.get());
-        uint32_t* pr = reinterpret_cast<uint32_t*>(pk + h->scan_scores.size() / 12);
-        for (int f0 = 0; f0 < Q; f0 += round_q) {
-            hipLaunchKernelGGL(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, h->n_rows,
-                               rows_per_block, h->dim, k, scan_list, scan_count, f0, round_q, pk, pr, fz ? fz->raw : (const double*)nullptr,
-                               fz ? fz->n : (int64_t)0, fz ? fz->mx : (const double*)nullptr, fz ? fz->temporal : (const double*)nullptr,
-                               fz ? fz->alpha : 0.0, fz ? fz->beta : 0.0, fz ? fz->gamma : 0.0);
-            hipLaunchKernelGGL(scan_merge_kernel, dim3(std::min(Q - f0, round_q)), dim3(256), 0, st, pk, pr, n_blocks, k, h->ids,
-                               h->id_base, scan_list, scan_count, f0, h->flag, ids_dev, rows_dev, scores_dev, h->stats);
-        }
-        HIP_TRY(h, hipGetLastError());
-    }
+    tile_universe u;
+    if ((rc = search_tiles(h, tenant, &u))) return rc;
+    const std::vector<stage_range> plan = stage_plan(u.count, Q, k, h->opt.stage_growth);
+    const emit_args a = emit_args_of(h, u, vis, tenant, fz);
+    const bool with_second_pass = !h->opt.no_second_pass;
+    if ((rc = prepare_queries(h, q_dev, Q, st))) return rc;
+    if ((rc = first_pass(h, a, plan, Q, k, two_eps, fz, with_second_pass, st))) return rc;
+    if (u.count > 0 && with_second_pass && (rc = second_pass(h, a, u.count, k, two_eps, fz, st))) return rc;
+    if ((rc = rescore_and_finalize(h, q_dev, Q, k, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
+    if ((rc = exact_scan_rounds(h, q_dev, Q, k, vis, tenant, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
     h->last_q = Q;
     h->last_k = k;
-    h->last_stages = stage;
+    h->last_stages = (int)plan.size();
     h->last_shortlist = k;
     h->last_eps = eps;
     h->last_stats_valid = true;
@@ -1287,18 +1295,16 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
 // bias / max / components of the linear fusion (called by rag_hybrid_linear_dev around dense_search_fused)
 int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bound nb, int Q, int64_t n, const double* temporal,
                    double beta, double gamma, double* mx, float* qscale, float* margin, float* gt, int64_t ld, hipStream_t st) {
-    hipLaunchKernelGGL(linear_scale_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, max_key, nb, Q, beta, mx, qscale, margin);
-    if (gt != nullptr) hipLaunchKernelGGL(linear_gt_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, temporal, n, ld, gamma, gt);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    launch(linear_scale_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, max_key, nb, Q, beta, mx, qscale, margin);
+    if (gt != nullptr) launch(linear_gt_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, temporal, n, ld, gamma, gt);
+    return launch_status(h);
 }
 
 int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, int Q, int k, const dense_fused* fz, double* sem_out,
                       double* kw_out, double* tmp_out, hipStream_t st) {
-    hipLaunchKernelGGL(linear_components_kernel, dim3((unsigned)(((int64_t)Q * k + 3) / 4)), dim3(256), 0, st, q_dev, h->emb32, rows_dev, Q, k,
-                       h->dim, fz->raw, fz->n, fz->mx, fz->temporal, sem_out, kw_out, tmp_out);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    launch(linear_components_kernel, dim3((unsigned)(((int64_t)Q * k + 3) / 4)), dim3(256), 0, st, q_dev, h->emb32, rows_dev, Q, k, h->dim,
+           fz->raw, fz->n, fz->mx, fz->temporal, sem_out, kw_out, tmp_out);
+    return launch_status(h);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1355,10 +1361,8 @@ int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists
     // the kernel's static LDS (per-wave maxima of the normalisation, 32 B) comes on top of the dynamic entries: 64 KiB in all
     ARG_CHECK(h, lds + 64 <= 64 * 1024, "merge: n_lists*k too large (max 4092 entries)");
     ARG_CHECK(h, list_stride >= (int64_t)Q * k, "merge: list_stride < Q*k");
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(Q), dim3(256), lds, st, ids, scores, n_lists, list_stride, Q, k, ids_out,
-                       scores_out, normalize);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    launch(merge_topk_kernel, dim3(Q), dim3(256), lds, st, ids, scores, n_lists, list_stride, Q, k, ids_out, scores_out, normalize);
+    return launch_status(h);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1392,21 +1396,16 @@ __global__ __launch_bounds__(256) void pairwise_cosine_kernel(const T* __restric
     }
 }
 
-int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev,
-                    hipStream_t st) {
+template <class T>
+static int pairwise_cosine_t(rag_ctx* h, const T* a_dev, int m, const T* b_dev, int n, int dim, double* out_dev, hipStream_t st) {
     const int64_t pairs = (int64_t)m * n;
     if (pairs == 0) return RAG_OK;
-    hipLaunchKernelGGL(pairwise_cosine_kernel<float>, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a_dev, m, b_dev, n, dim,
-                       out_dev);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    launch(pairwise_cosine_kernel<T>, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a_dev, m, b_dev, n, dim, out_dev);
+    return launch_status(h);
 }
-
+int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev, hipStream_t st) {
+    return pairwise_cosine_t(h, a_dev, m, b_dev, n, dim, out_dev, st);
+}
 int pairwise_cosine_f64(rag_ctx* h, const double* a_dev, int m, const double* b_dev, int n, int dim, double* out_dev, hipStream_t st) {
-    const int64_t pairs = (int64_t)m * n;
-    if (pairs == 0) return RAG_OK;
-    hipLaunchKernelGGL(pairwise_cosine_kernel<double>, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, a_dev, m, b_dev, n, dim,
-                       out_dev);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    return pairwise_cosine_t(h, a_dev, m, b_dev, n, dim, out_dev, st);
 }

@@ -11,8 +11,6 @@
 //   4. rerank_topk_kernel: sigmoid in float64, stable order (score desc, candidate order on ties), top-k
 #include "common.h"
 
-int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev,
-                 hipStream_t st);
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st);
 int64_t bm25_n_docs(const rag_ctx* h);

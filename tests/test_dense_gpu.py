@@ -436,3 +436,51 @@ def test_corpus_sizes_at_tile_and_stage_boundaries(eng_factory, N):
     eng.index_load(corpus)
     st = check(eng, corpus, queries, min(5, N))
     assert st["exact_scan"] == 0
+
+
+# ------------------------------------------------------------------------ every emit variant the dispatcher can choose
+@pytest.fixture(scope="module")
+def variants_case(eng_factory):
+    """70000 rows = 274 tiles: the stages run 8 -> 64 -> 274 tiles. One engine, one corpus and ONE float64 oracle (for the 257
+    queries; smaller batches are its prefixes) shared by every case below."""
+    rng = np.random.default_rng(4242)
+    N, D, k = 70_000, 64, 5
+    corpus = rng.standard_normal((N, D)).astype(np.float32)
+    queries = planted_queries(rng, corpus, 257)
+    eng = eng_factory(D)
+    eng.index_load(corpus)
+    oid, osc = O.dense_topk(corpus, queries, k)
+    oid.setflags(write=False)
+    osc.setflags(write=False)
+    return eng, queries, k, oid, osc
+
+
+@pytest.mark.parametrize("option", [None, "no_smallq", "dense_persist"])
+@pytest.mark.parametrize("Q", [128, 129, 256, 257])
+def test_every_emit_variant_matches_the_oracle(variants_case, Q, option):
+    """The batch sizes at which the dispatcher changes kernel or grid - 128 / 129: the small-batch switch; 256 / 257: one
+    query tile against two - crossed with the options that pick another variant. The persistent stage kernel needs a stage
+    grid above 256 workgroups: at this size only Q = 257 has one (the last stage's 210 tiles -> 216 x 2 workgroups)."""
+    eng, queries, k, oid, osc = variants_case
+    if option:
+        eng.set_option(option, 1)
+    try:
+        got_ids, got_rows, got_sc = eng.dense_topk(queries[:Q], k)
+    finally:
+        if option:
+            eng.set_option(option, 0)
+    np.testing.assert_array_equal(got_rows, oid[:Q].astype(np.int32))
+    np.testing.assert_array_equal(got_ids, oid[:Q])
+    np.testing.assert_allclose(got_sc, osc[:Q], rtol=0, atol=SCORE_TOL)
+
+
+def test_one_handle_across_batch_sizes(eng_factory):
+    """257 queries, then 3, then 200 on one engine: the workspace grows once and is reused by the smaller batches, whose pad
+    rows of the last query tile (written by the larger batch before them) must read as zero again."""
+    rng = np.random.default_rng(4343)
+    N, D, k = 5000, 64, 5
+    corpus = rng.standard_normal((N, D)).astype(np.float32)
+    eng = eng_factory(D)
+    eng.index_load(corpus)
+    for Q in (257, 3, 200):
+        check(eng, corpus, planted_queries(rng, corpus, Q), k)

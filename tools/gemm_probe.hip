@@ -37,7 +37,9 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                            DENSE_LDS_BYTES));
     const int grid = (int)round_up(n_rt, 8) * n_qt;
-#define EXTRA
+    emit_args ea = {};               // table order (tile_mul 1), no filter, no fusion
+    ea.corpus16 = c; ea.q16 = q; ea.Dp = D; ea.n_rtiles = n_rt; ea.n_qtiles = n_qt; ea.n_rows_valid = N; ea.q_valid = Q;
+    ea.tau = tau; ea.cnt = cnt; ea.cand = cand; ea.tenant = -1; ea.tiles = {nullptr, (N + 255) / 256, 1, (N + 255) / 256}; ea.alpha = 1.0f;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -45,8 +47,7 @@ int main(int argc, char** argv) {
     for (int it = 0; it < iters; ++it) {
         CK(hipMemset(cnt, 0, Q * 4));
         CK(hipEventRecord(e0));
-        hipLaunchKernelGGL((dense_emit_kernel<false, false>), dim3(grid), dim3(512), DENSE_LDS_BYTES, 0, c, q, D, 0, n_rt, n_qt, N, Q, tau, cnt,
-                           cand, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, 1, (N + 2047) / 2048, (N + 255) / 256, (const int*)nullptr, (const float*)nullptr, (int64_t)0, 1.0f, (const int*)nullptr EXTRA);
+        hipLaunchKernelGGL((dense_emit_kernel<false, false>), dim3(grid), dim3(512), DENSE_LDS_BYTES, 0, ea);
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -57,8 +58,9 @@ int main(int argc, char** argv) {
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(dense_emit_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                DENSE_LDS_BYTES));
         CK(hipMemset(cand, 0, (size_t)Q * RAG_CAND_CAP * 8));
-        hipLaunchKernelGGL((dense_emit_kernel<true, false>), dim3(8 * n_qt), dim3(512), DENSE_LDS_BYTES, 0, c, q, D, 0, 8, n_qt, 2048, Q, tau, cnt,
-                           cand, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, 1, (N + 2047) / 2048, (N + 255) / 256, (const int*)nullptr, (const float*)nullptr, (int64_t)0, 1.0f, (const int*)nullptr EXTRA);
+        ea.n_rtiles = 8;
+        ea.n_rows_valid = 2048;
+        hipLaunchKernelGGL((dense_emit_kernel<true, false>), dim3(8 * n_qt), dim3(512), DENSE_LDS_BYTES, 0, ea);
         CK(hipDeviceSynchronize());
         std::vector<uint64_t> hk((size_t)Q * RAG_CAND_CAP);
         CK(hipMemcpy(hk.data(), cand, hk.size() * 8, hipMemcpyDeviceToHost));
