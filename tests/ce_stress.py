@@ -138,3 +138,51 @@ def batch(lens=LENS, L=L, seed=2468, pair_types=True):
     ids[np.arange(L)[None, :] >= lens[:, None]] = 0
     tt = ((np.arange(L)[None, :] >= 18) & (np.arange(L)[None, :] < lens[:, None])).astype(np.int32)
     return ids, tt if pair_types else np.zeros_like(tt)
+
+
+# ---- the error-budget tests (tests/test_ce_error_budget.py on the CPU simulator, tests/test_cross_encoder_budget_gpu.py on the GPU):
+# the seeded model with centred logits, pair token types on BOTH heads so that one encoder pass of the oracle serves both
+# what the CPU test asserts of a forward that lost a correction product (rms error / shipped rms error), and the margins the GPU
+# test gives each forward over its measured error: a margin must stay under its ratio
+SPLIT16_MUTANT_RATIO, MX_MUTANT_RATIO = 20.0, 2.0
+SPLIT16_MARGIN, MX_MARGIN = 2.0, 1.5
+# the non-384 shape of the budget tests: split fp16 only, the unfused LayerNorm and the GEMM instantiations MiniLM does not take
+H128 = dict(vocab_size=2000, hidden=128, layers=2, heads=4, ffn=512, max_pos=128, type_vocab=2, eps=1e-12)
+
+
+def budget_weights(cfg=CFG, seed=99):
+    return centre_logits(B.seeded_weights(cfg, seed), cfg)
+
+
+def budget_batch(reps=1, cfg=None):
+    """(ids, tt, lens) of reps x 24 pairs at L = 128: batch(seed=2468 + i) for i < reps, LENS tiled. 24 pairs pack into 1760 rows of
+    16-row-aligned pairs, so reps = 4 gives 7040 rows: exactly 55 token tiles of 128 rows and 27.5 of 256. cfg: a smaller model's
+    shape - the token ids are folded into its vocabulary."""
+    parts = [batch(seed=2468 + i) for i in range(reps)]
+    ids, tt = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    if cfg is not None and cfg["vocab_size"] < CFG["vocab_size"]:
+        ids = np.where(ids > 0, 5 + ids % (cfg["vocab_size"] - 5), 0).astype(np.int32)
+    return ids, tt, np.tile(LENS, reps)
+
+
+def heads(W, x, lens):
+    """(classifier logits [P], raw mean-pooled vectors [P, H]) of one last hidden state, float64: the two small heads of
+    oracle/bert_oracle.py (forward_logits, sentence_embeddings with normalize=False) behind one encoder pass"""
+    pooled = np.tanh(x[:, 0] @ W["bert.pooler.dense.weight"].T + W["bert.pooler.dense.bias"])
+    logits = (pooled @ W["classifier.weight"].T + W["classifier.bias"])[:, 0]
+    ok = (np.arange(x.shape[1])[None, :] < np.asarray(lens)[:, None]).astype(np.float64)[:, :, None]
+    return logits, (x * ok).sum(1) / np.maximum(ok.sum(1), 1e-9)
+
+
+def oracle_heads(w, cfg, ids, tt, lens):
+    W, x = B.forward_hidden(w, cfg, ids.astype(np.int64), tt.astype(np.int64), lens, fast_erf=True)
+    return heads(W, x, lens)
+
+
+def budget_errors(logits, raw, exp_logits, exp_raw):
+    """The four figures a budget holds: max and rms over all pairs of |logit - oracle|, max and rms over all components of
+    |raw pooled - oracle| / ||oracle||."""
+    dl = np.abs(np.asarray(logits, dtype=np.float64) - exp_logits)
+    dr = np.abs(np.asarray(raw, dtype=np.float64) - exp_raw) / np.linalg.norm(exp_raw, axis=1, keepdims=True)
+    return dict(logit_max=float(dl.max()), logit_rms=float(np.sqrt((dl ** 2).mean())),
+                raw_max=float(dr.max()), raw_rms=float(np.sqrt((dr ** 2).mean())))

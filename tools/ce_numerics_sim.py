@@ -15,6 +15,8 @@ Schemes (x = hi + lo, hi = fp16(x)):
   bf8tt_stream  bf8tt, and every stored activation (residual stream, ctx, FFN intermediate) read back as hi16 + lo8
   ship     bf8tt_stream with attention in split fp16 (what the first MX build shipped); ship_noplo: without the P_lo term of P.V
   shiprn   ship with hi8 rounded to NEAREST (top byte of hi + 0x80) and no gain on lo8: what ships now
+  site_scheme / attn_drop (arguments of hidden(), forward(), sentence_embeddings()): ONE linear site under another scheme, or one
+           attention product without one correction term - the mutants tests/test_ce_error_budget.py holds the error budgets against
   shipfp6_<e2m3|e3m2>_<group>  the correction operands as 6-bit floats (twice the MFMA rate of 8-bit ones) under one E8M0 scale per
            <group> consecutive K elements; lo6 = fp6(lo * 2^11 / scale) shares the scale of hi6; stored activations = hi16 + lo6
 usage: python tools/ce_numerics_sim.py [pairs] [L] [scheme,scheme...]"""
@@ -30,7 +32,13 @@ from oracle import bert_oracle as B  # noqa: E402
 
 
 def f16(x):
-    return x.astype(np.float16).astype(np.float64)
+    """float64 -> the nearest fp16 value, as float64: bit for bit x.astype(np.float16). The lo parts of a split are mostly fp16
+    SUBNORMALS (|lo| <= 2^-12 |x|), which the hardware conversion handles through a slow assist (14 x slower measured: most of a
+    simulated forward). Below 2^-14 fp16 is a fixed-point grid of step 2^-24, so round-half-even there is np.rint of the scaled
+    value, exactly (tests/test_ce_error_budget.py compares the two on every fp16 value, every tie and their neighbours)."""
+    x = np.asarray(x, dtype=np.float64)
+    small = np.abs(x) < 2.0 ** -14
+    return np.where(small, np.rint(x * 2.0 ** 24) * 2.0 ** -24, np.where(small, 0.0, x).astype(np.float16).astype(np.float64))
 
 
 def q8(x, dt):
@@ -116,14 +124,16 @@ class Scheme:
         g = 1.0 if self.name == "shiprn" else TRUNC_GAIN
         return hi + q8((x - hi) * 2048.0 * g, torch.float8_e5m2) / (2048.0 * g)
 
-    def mm(self, a, b, a_scale=1.0, b_scale=1.0, drop_a_lo=False):
-        """a @ b^T over the last axis of both, operands rounded per scheme (leading axes broadcast as numpy matmul)"""
+    def mm(self, a, b, a_scale=1.0, b_scale=1.0, drop_a_lo=False, drop_b_lo=False):
+        """a @ b^T over the last axis of both, operands rounded per scheme (leading axes broadcast as numpy matmul);
+        drop_a_lo / drop_b_lo: without the correction product that carries a_lo / b_lo"""
         ah, al, a8 = self.split(a, a_scale)
         bh, bl, b8 = self.split(b, b_scale)
         bt = lambda t: np.swapaxes(t, -1, -2)
         y = ah @ bt(bh)
         if al is not None:
-            y = y + a8 @ bt(bl)
+            if not drop_b_lo:
+                y = y + a8 @ bt(bl)
             if not drop_a_lo:
                 y = y + al @ bt(b8)
         return y
@@ -134,8 +144,22 @@ def wscale_for(w):
     return 2.0 ** math.floor(math.log2(448.0 / np.abs(w).max()))
 
 
-def hidden(w, cfg, ids, tt, lens, sch):
-    """(weights as float64, last hidden state [P, L, H]) of the encoder under scheme `sch`"""
+# the six linear sites of an encoder layer, by the name that follows "bert.encoder.layer.<l>." in the state dict; the FFN-down
+# projection is "output.dense" and nothing else: sites are looked up whole, never by suffix, so it cannot also catch
+# "attention.output.dense"
+SITES = ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense", "intermediate.dense",
+         "output.dense")
+# switches of the two attention products (split fp16 in every shipped forward): each drops ONE correction product
+ATTN_DROPS = ("k_lo", "p_lo")       # Q.K^T without K_lo * Q_hi; P.V without V_hi * P_lo (what ship_noplo drops)
+
+
+def hidden(w, cfg, ids, tt, lens, sch, site_scheme=None, attn_drop=()):
+    """(weights as float64, last hidden state [P, L, H]) of the encoder under scheme `sch`.
+    site_scheme: {site of SITES: Scheme} - the operand scheme of that linear layer, in every encoder layer, instead of `sch`
+    (stored activations stay as `sch` stores them); attn_drop: members of ATTN_DROPS. The defaults change nothing."""
+    site_scheme = dict(site_scheme or {})
+    assert set(site_scheme) <= set(SITES), sorted(set(site_scheme) - set(SITES))
+    assert set(attn_drop) <= set(ATTN_DROPS), attn_drop
     from scipy.special import erf
     W = {k: v.astype(np.float64) for k, v in w.items()}
     P, L = ids.shape
@@ -146,43 +170,40 @@ def hidden(w, cfg, ids, tt, lens, sch):
     x = sch.store(B._ln(x, W["bert.embeddings.LayerNorm.weight"], W["bert.embeddings.LayerNorm.bias"], cfg["eps"]))
     key_ok = np.arange(L)[None, :] < np.asarray(lens)[:, None]
     add_mask = np.where(key_ok, 0.0, -1e30)[:, None, None, :]
-    lin = lambda t, name: sch.mm(t, W[name + ".weight"], 1.0, wscale_for(W[name + ".weight"])) + W[name + ".bias"]
+    lin = lambda t, p, site: (site_scheme.get(site, sch).mm(t, W[p + site + ".weight"], 1.0, wscale_for(W[p + site + ".weight"]))
+                              + W[p + site + ".bias"])
     for l in range(cfg["layers"]):
         p = f"bert.encoder.layer.{l}."
-        q = lin(x, p + "attention.self.query")
-        k = lin(x, p + "attention.self.key")
-        v = lin(x, p + "attention.self.value")
+        q = lin(x, p, "attention.self.query")
+        k = lin(x, p, "attention.self.key")
+        v = lin(x, p, "attention.self.value")
         sp = lambda t: t.reshape(P, L, nh, dh).transpose(0, 2, 1, 3)
-        s = sch.mm(sp(q), sp(k)) * (dh ** -0.5) + add_mask
-        s = s - s.max(-1, keepdims=True)
-        e = np.exp(s)                                   # unnormalised P in (0, 1], as the kernel's online softmax holds it
         # ship*: the shipped forward keeps attention in split fp16 whatever the GEMM scheme; *_noplo: P.V without the P_lo term
         att = Scheme("split16") if sch.name.startswith("ship") else sch
-        if sch.name.startswith("ship"):
-            s = att.mm(sp(q), sp(k)) * (dh ** -0.5) + add_mask
-            s = s - s.max(-1, keepdims=True)
-            e = np.exp(s)
-        ctx = att.mm(e, np.swapaxes(sp(v), -1, -2), drop_a_lo=sch.name.endswith("noplo")) / e.sum(-1, keepdims=True)
+        s = att.mm(sp(q), sp(k), drop_b_lo="k_lo" in attn_drop) * (dh ** -0.5) + add_mask
+        s = s - s.max(-1, keepdims=True)
+        e = np.exp(s)                                   # unnormalised P in (0, 1], as the kernel's online softmax holds it
+        ctx = att.mm(e, np.swapaxes(sp(v), -1, -2), drop_a_lo=sch.name.endswith("noplo") or "p_lo" in attn_drop) / e.sum(-1, keepdims=True)
         ctx = sch.store(ctx.transpose(0, 2, 1, 3).reshape(P, L, H))
-        o = lin(ctx, p + "attention.output.dense")
+        o = lin(ctx, p, "attention.output.dense")
         x = sch.store(B._ln(o + x, W[p + "attention.output.LayerNorm.weight"], W[p + "attention.output.LayerNorm.bias"], cfg["eps"]))
-        h = lin(x, p + "intermediate.dense")
+        h = lin(x, p, "intermediate.dense")
         h = sch.store(0.5 * h * (1.0 + erf(h / math.sqrt(2.0))))
-        o = lin(h, p + "output.dense")
+        o = lin(h, p, "output.dense")
         x = sch.store(B._ln(o + x, W[p + "output.LayerNorm.weight"], W[p + "output.LayerNorm.bias"], cfg["eps"]))
     return W, x
 
 
-def forward(w, cfg, ids, tt, lens, sch, sites=None):
+def forward(w, cfg, ids, tt, lens, sch, site_scheme=None, attn_drop=()):
     """classifier logits [P]"""
-    W, x = hidden(w, cfg, ids, tt, lens, sch)
+    W, x = hidden(w, cfg, ids, tt, lens, sch, site_scheme, attn_drop)
     pooled = np.tanh(x[:, 0] @ W["bert.pooler.dense.weight"].T + W["bert.pooler.dense.bias"])
     return (pooled @ W["classifier.weight"].T + W["classifier.bias"])[:, 0]
 
 
-def sentence_embeddings(w, cfg, ids, tt, lens, sch, normalize=True):
+def sentence_embeddings(w, cfg, ids, tt, lens, sch, normalize=True, site_scheme=None, attn_drop=()):
     """the embedding head (mean over the real tokens, optionally L2-normalised) on the simulated encoder, [P, H]"""
-    _, x = hidden(w, cfg, ids, tt, lens, sch)
+    _, x = hidden(w, cfg, ids, tt, lens, sch, site_scheme, attn_drop)
     keep = (np.arange(x.shape[1])[None, :] < np.asarray(lens)[:, None])[..., None]
     pooled = (x * keep).sum(1) / np.asarray(lens, dtype=np.float64)[:, None]
     return pooled / np.maximum(np.linalg.norm(pooled, axis=1, keepdims=True), 1e-12) if normalize else pooled
