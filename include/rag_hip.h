@@ -507,6 +507,46 @@ int rag_ce_build_pairs_dev(rag_handle_t h, const int32_t* q_tok_dev, const int32
 int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* cand_dev, int n_queries, int pool, int k,
                         int64_t* ids_out_dev, double* scores_out_dev, float* logits_out_dev, void* stream);
 
+/* ---- agents mixed in one batch: a tenant PER QUERY. Each entry takes the arguments of its namesake with
+ *      `const int32_t* tenants_host` [n_queries] where the namesake has `int tenant`: query i is filtered by tenants_host[i],
+ *      a value < 0 leaves that query unfiltered. The result of query i is bit-identical to what the namesake returns for that
+ *      query alone with tenant = tenants_host[i] (ids, rows, float64 score bits, raw maxima, candidate lists, logits): a tenant
+ *      that owns no live row gives an all-padding result (-1 / 0.0), one with fewer than k live rows is padded, deleted rows
+ *      stay hidden, and the linear fusion normalises each query's keyword score by its own tenant's best document.
+ *      tenants_host is HOST memory in the *_dev entries too: the tenant number is what the caller's agent table holds on the
+ *      host, and the library chooses the tiles to search from it there. It is consumed before the call returns (the caller may
+ *      overwrite or free it at once); the device copy is written as ordinary work of `stream`, so the ordering rules of the
+ *      preamble hold unchanged and, in the steady state, the call waits for nothing (the first call of a larger batch or of
+ *      a longer tile union grows a handle-owned buffer, as workspace growth does in the preamble).
+ *      Argument checks are the namesakes': a tenant >= 0 needs rag_index_set_tenants_host over the index's rows (a stale
+ *      table is RAG_ERR_ARG), BM25 / hybrid / pipeline entries need postings that are row-aligned and not stale
+ *      (RAG_ERR_STATE). A batch whose queries all name the same tenant (or none) runs exactly the namesake's path.
+ *      Cost: the dense pass searches the union of the batch's tenants' tiles when every query is filtered and that union is
+ *      shorter than the table, else every tile; each query filters the other tenants' rows out of it. */
+int rag_dense_topk_tenants_host(rag_handle_t h, const float* q_host, int n_queries, int k, const int32_t* tenants_host,
+                                int64_t* ids_out_host, int32_t* rows_out_host, double* scores_out_host);
+int rag_dense_topk_tenants_dev(rag_handle_t h, const float* q_dev, int n_queries, int k, const int32_t* tenants_host,
+                               int64_t* ids_out_dev, int32_t* rows_out_dev, double* scores_out_dev, void* stream);
+int rag_bm25_topk_tenants_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, int n_queries, int k,
+                               const int32_t* tenants_host, int64_t* ids_out_host, int32_t* rows_out_host,
+                               double* scores_out_host, double* raw_max_out_host);
+int rag_bm25_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int n_queries, int k,
+                              const int32_t* tenants_host, int64_t* ids_out_dev, int32_t* rows_out_dev, double* scores_out_dev,
+                              double* raw_max_out_dev, void* stream);
+int rag_hybrid_rrf_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                               int n_queries, int pool, int k, int rrf_k, const int32_t* tenants_host, int64_t* lists_ws_dev,
+                               double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev,
+                               void* stream);
+int rag_hybrid_linear_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                  int n_queries, int k, double alpha, double beta, double gamma, const int32_t* tenants_host,
+                                  int64_t* ids_out_dev, int32_t* rows_out_dev, double* hybrid_out_dev, double* semantic_out_dev,
+                                  double* keyword_out_dev, double* temporal_out_dev, void* stream);
+int rag_retrieve_rerank_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                    const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int n_queries, int pool, int k,
+                                    int rrf_k, const int32_t* tenants_host, int mode, int cls_id, int sep_id, int L_pair,
+                                    int64_t* ids_out_dev, double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev,
+                                    void* stream);
+
 /* ---- the exchange step of the row-sharded search (the reference is single-process) bound to RCCL
  *      directly, for hosts that do not want torch.distributed in the path: ONE all-gather of each rank's partial top-k lists
  *      per stage, over xGMI, followed by rag_merge_topk_dev / rag_rrf_fuse_dev on every rank. librccl is opened at the first

@@ -129,6 +129,13 @@ _SIGS = {
     "rag_embed_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
     "rag_embed_dim": ([_P, C.POINTER(C.c_int)], C.c_int),
 }
+# The per-query-tenant entries: the arguments of their namesakes with `const int32_t* tenants_host` where those have `int tenant`
+# (argument position of the tenant in the namesake's list).
+for _name, _pos in (("rag_dense_topk_host", 4), ("rag_dense_topk_dev", 4), ("rag_bm25_topk_host", 5), ("rag_bm25_topk_dev", 5),
+                    ("rag_hybrid_rrf_dev", 8), ("rag_hybrid_linear_dev", 9), ("rag_retrieve_rerank_dev", 11)):
+    _args, _res = _SIGS[_name]
+    assert _args[_pos] is C.c_int
+    _SIGS[_name.replace("_host", "_tenants_host").replace("_dev", "_tenants_dev")] = (_args[:_pos] + [_P] + _args[_pos + 1:], _res)
 
 
 def exported_symbols():
@@ -198,6 +205,22 @@ def _np(a, dtype):
 
 def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _tenant_arg(tenant, n_queries):
+    """The `tenant` of a search -> (per_query, C argument). An int is the one filter of the whole batch (the scalar entries); a
+    sequence or int32 array of length n_queries gives every query its own tenant (< 0: not filtered) and selects the
+    rag_*_tenants_* entries. The array is host memory and is consumed before the call returns."""
+    if isinstance(tenant, (int, np.integer)):
+        return False, int(tenant)
+    if _is_torch(tenant):
+        tenant = tenant.cpu().numpy()
+    if np.ndim(tenant) == 0:                                  # a 0-d array or tensor is one number, as int(tenant) always took it
+        return False, int(tenant)
+    t = np.ascontiguousarray(tenant, dtype=np.int32)
+    if t.shape != (n_queries,):
+        raise RagError(f"tenant: expected an int or {n_queries} tenant numbers, got shape {t.shape}")
+    return True, t
 
 
 def _is_torch(x):
@@ -370,7 +393,12 @@ class RagEngine:
         ids = np.empty((Q, k), dtype=np.int64)
         rows = np.empty((Q, k), dtype=np.int32)
         sc = np.empty((Q, k), dtype=np.float64)
-        self._check(self.lib.rag_dense_topk_host(self.h, _ptr(q), Q, int(k), int(tenant), _ptr(ids), _ptr(rows), _ptr(sc)),
+        per_query, t = _tenant_arg(tenant, Q)
+        if per_query:
+            self._check(self.lib.rag_dense_topk_tenants_host(self.h, _ptr(q), Q, int(k), _ptr(t), _ptr(ids), _ptr(rows), _ptr(sc)),
+                        "rag_dense_topk_tenants_host")
+            return ids, rows, sc
+        self._check(self.lib.rag_dense_topk_host(self.h, _ptr(q), Q, int(k), t, _ptr(ids), _ptr(rows), _ptr(sc)),
                     "rag_dense_topk_host")
         return ids, rows, sc
 
@@ -381,9 +409,10 @@ class RagEngine:
         assert ids_out.dtype == torch.int64 and scores_out.dtype == torch.float64
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
         rp = None if rows_out is None else C.c_void_p(rows_out.data_ptr())
-        self._check(self.lib.rag_dense_topk_dev(self.h, C.c_void_p(q.data_ptr()), q.shape[0], int(k), int(tenant),
-                                                C.c_void_p(ids_out.data_ptr()), rp, C.c_void_p(scores_out.data_ptr()), st),
-                    "rag_dense_topk_dev")
+        per_query, t = _tenant_arg(tenant, q.shape[0])
+        fn, name = (self.lib.rag_dense_topk_tenants_dev, "rag_dense_topk_tenants_dev") if per_query else (self.lib.rag_dense_topk_dev, "rag_dense_topk_dev")
+        self._check(fn(self.h, C.c_void_p(q.data_ptr()), q.shape[0], int(k), _ptr(t) if per_query else t,
+                       C.c_void_p(ids_out.data_ptr()), rp, C.c_void_p(scores_out.data_ptr()), st), name)
 
     def dense_stats(self):
         s = DenseStats()
@@ -597,8 +626,10 @@ class RagEngine:
         rows = np.empty((Q, k), dtype=np.int32)
         sc = np.empty((Q, k), dtype=np.float64)
         mx = np.empty((Q,), dtype=np.float64)
-        self._check(self.lib.rag_bm25_topk_host(self.h, _ptr(term_ptr), _ptr(terms), Q, int(k), int(tenant), _ptr(ids),
-                                                _ptr(rows), _ptr(sc), _ptr(mx)), "rag_bm25_topk_host")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_bm25_topk_tenants_host, "rag_bm25_topk_tenants_host") if per_query else (self.lib.rag_bm25_topk_host, "rag_bm25_topk_host")
+        self._check(fn(self.h, _ptr(term_ptr), _ptr(terms), Q, int(k), _ptr(t) if per_query else t, _ptr(ids),
+                       _ptr(rows), _ptr(sc), _ptr(mx)), name)
         return ids, rows, sc, mx
 
     def bm25_set_normalize(self, on):
@@ -610,12 +641,13 @@ class RagEngine:
         import torch
         Q = term_ptr.shape[0] - 1
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        self._check(self.lib.rag_bm25_topk_dev(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()), Q, int(k),
-                                               int(tenant), C.c_void_p(ids_out.data_ptr()),
-                                               C.c_void_p(rows_out.data_ptr() if rows_out is not None else 0),
-                                               C.c_void_p(scores_out.data_ptr()),
-                                               C.c_void_p(raw_max_out.data_ptr() if raw_max_out is not None else 0), st),
-                    "rag_bm25_topk_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_bm25_topk_tenants_dev, "rag_bm25_topk_tenants_dev") if per_query else (self.lib.rag_bm25_topk_dev, "rag_bm25_topk_dev")
+        self._check(fn(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()), Q, int(k),
+                       _ptr(t) if per_query else t, C.c_void_p(ids_out.data_ptr()),
+                       C.c_void_p(rows_out.data_ptr() if rows_out is not None else 0),
+                       C.c_void_p(scores_out.data_ptr()),
+                       C.c_void_p(raw_max_out.data_ptr() if raw_max_out is not None else 0), st), name)
 
     def rrf_fuse_dev(self, lists, keys_out, scores_out, ranks_out, rrf_k=60, stream=None):
         """lists: [Q, n_lists, list_len] int64 doc ids (-1 padded) on the device -> keys/scores [Q, top_k], ranks [Q, top_k, n_lists]."""
@@ -643,11 +675,13 @@ class RagEngine:
             self._hyb_key = key
         lists, sc, keys, rrf, ranks = self._hyb
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        self._check(self.lib.rag_hybrid_rrf_dev(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()),
-                                                C.c_void_p(terms.data_ptr()), Q, int(pool), int(k), int(rrf_k), int(tenant),
-                                                C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
-                                                C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
-                                                C.c_void_p(ranks.data_ptr()), st), "rag_hybrid_rrf_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_hybrid_rrf_tenants_dev, "rag_hybrid_rrf_tenants_dev") if per_query else (self.lib.rag_hybrid_rrf_dev, "rag_hybrid_rrf_dev")
+        self._check(fn(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()),
+                       C.c_void_p(terms.data_ptr()), Q, int(pool), int(k), int(rrf_k), _ptr(t) if per_query else t,
+                       C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
+                       C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
+                       C.c_void_p(ranks.data_ptr()), st), name)
         return keys, rrf, ranks
 
     def set_temporal(self, temporal):
@@ -669,11 +703,13 @@ class RagEngine:
             self._lin_key = key
         o = self._lin
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        self._check(self.lib.rag_hybrid_linear_dev(
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_hybrid_linear_tenants_dev, "rag_hybrid_linear_tenants_dev") if per_query else (self.lib.rag_hybrid_linear_dev, "rag_hybrid_linear_dev")
+        self._check(fn(
             self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()), Q, int(k), float(alpha),
-            float(beta), float(gamma), int(tenant), C.c_void_p(o["ids"].data_ptr()), C.c_void_p(o["rows"].data_ptr()),
+            float(beta), float(gamma), _ptr(t) if per_query else t, C.c_void_p(o["ids"].data_ptr()), C.c_void_p(o["rows"].data_ptr()),
             C.c_void_p(o["hybrid"].data_ptr()), C.c_void_p(o["semantic"].data_ptr()), C.c_void_p(o["keyword"].data_ptr()),
-            C.c_void_p(o["temporal"].data_ptr()), st), "rag_hybrid_linear_dev")
+            C.c_void_p(o["temporal"].data_ptr()), st), name)
         return o
 
     def bm25_scores(self, term_ptr, terms):
@@ -775,12 +811,15 @@ class RagEngine:
         ids, sc, lg, cand = self._rr
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
         mode = 0 if term_ptr is None else 1
-        self._check(self.lib.rag_retrieve_rerank_dev(
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_retrieve_rerank_tenants_dev, "rag_retrieve_rerank_tenants_dev") if per_query
+                    else (self.lib.rag_retrieve_rerank_dev, "rag_retrieve_rerank_dev"))
+        self._check(fn(
             self.h, C.c_void_p(q_emb.data_ptr()), C.c_void_p(term_ptr.data_ptr() if mode else 0),
             C.c_void_p(terms.data_ptr() if mode else 0), C.c_void_p(q_tok.data_ptr()), C.c_void_p(q_len.data_ptr()),
-            int(q_tok.shape[1]), Q, int(pool), int(k), int(rrf_k), int(tenant), mode, int(cls_id), int(sep_id), int(L_pair),
+            int(q_tok.shape[1]), Q, int(pool), int(k), int(rrf_k), _ptr(t) if per_query else t, mode, int(cls_id), int(sep_id), int(L_pair),
             C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(lg.data_ptr()), C.c_void_p(cand.data_ptr()), st),
-            "rag_retrieve_rerank_dev")
+            name)
         return ids, sc, lg, cand
 
     def ce_build_pairs_dev(self, q_tok, q_len, cand, ids_out, tt_out, lens_out, token_id_base=0, cls_id=101, sep_id=102, stream=None):

@@ -15,7 +15,7 @@ int linear_fuse_topk_host(rag_ctx* h, const double* sem, const double* kw, const
 int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                    const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b);
 int bm25_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int tenant, int64_t* ids_out,
-                   int32_t* rows_out, double* scores_out, double* raw_max_out);
+                   int32_t* rows_out, double* scores_out, double* raw_max_out, query_tenants qt);
 int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                            const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
                            const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
@@ -30,11 +30,11 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
 int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
 int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
-                    float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant);
+                    float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant, query_tenants qt);
 int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out);
 int bm25_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st);
+                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
 int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
                  int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
 void bm25_free(rag_ctx* h);
@@ -56,7 +56,7 @@ int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens
 int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                         const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
                         int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out, double* scores_out, float* logits_out,
-                        int64_t* cand_out, hipStream_t st);
+                        int64_t* cand_out, hipStream_t st, query_tenants qt);
 
 static thread_local std::string g_null_err = "null handle";
 
@@ -91,6 +91,21 @@ static void options_from_env(rag_options* o) {
         HIP_TRY(h, hipSetDevice((h)->device));                                                \
         if (int rc_ = host_after_dev(h)) return rc_;                                          \
     } while (0)
+
+// ---- per-query tenants (rag_*_tenants_*). The scalar entry and its namesake share one body: tenants_host == nullptr is the
+// scalar call. A UNIFORM array (every query the same tenant, or none filtered) is the scalar call with that tenant too, so the
+// per-query kernels' path only runs where tenants really differ. Otherwise the array is copied to the device on the call's
+// stream first - consumed before the entry returns, ordered like everything else the call queues.
+struct entry_tenants { int tenant; query_tenants qt; };
+static int entry_tenants_of(rag_ctx* h, int tenant, const int32_t* tenants_host, int Q, hipStream_t st, entry_tenants* out) {
+    *out = {tenant, {nullptr, nullptr}};
+    if (tenants_host == nullptr) return RAG_OK;
+    const int32_t t0 = std::max(tenants_host[0], -1);
+    bool uniform = true;
+    for (int q = 1; q < Q && uniform; ++q) uniform = std::max(tenants_host[q], -1) == t0;
+    out->tenant = t0;
+    return uniform ? RAG_OK : stage_query_tenants(h, tenants_host, Q, st, &out->qt);
+}
 
 template <class T>
 static int pairwise_cosine_host_t(rag_handle_t h, const T* a, int m, const T* b, int n, int dim, double* out) {
@@ -351,18 +366,29 @@ int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows, int n, float*
 }
 
 // ---- dense search ----------------------------------------------------------------------------------
-int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                       double* scores_dev, void* stream) {
+static int dense_topk_dev_entry(rag_handle_t h, const float* q_dev, int Q, int k, int tenant, const int32_t* tenants_host, int64_t* ids_dev,
+                                int32_t* rows_dev, double* scores_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_dev && ids_dev && scores_dev, "null pointer");
     ARG_CHECK(h, Q > 0 && Q <= 65535, "1 <= n_queries <= 65535");
     DEV_ENTRY(h);
-    return dense_search(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
+    return dense_search(h, q_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream, t.qt);
+}
+int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
+                       double* scores_dev, void* stream) {
+    return dense_topk_dev_entry(h, q_dev, Q, k, tenant, nullptr, ids_dev, rows_dev, scores_dev, stream);
+}
+int rag_dense_topk_tenants_dev(rag_handle_t h, const float* q_dev, int Q, int k, const int32_t* tenants_host, int64_t* ids_dev,
+                               int32_t* rows_dev, double* scores_dev, void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return dense_topk_dev_entry(h, q_dev, Q, k, -1, tenants_host, ids_dev, rows_dev, scores_dev, stream);
 }
 
-int rag_dense_topk_host(rag_handle_t h, const float* q_host, int Q, int k, int tenant, int64_t* ids_out, int32_t* rows_out,
-                        double* scores_out) {
+static int dense_topk_host_entry(rag_handle_t h, const float* q_host, int Q, int k, int tenant, const int32_t* tenants_host, int64_t* ids_out,
+                                 int32_t* rows_out, double* scores_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_host && ids_out && scores_out, "null pointer");
@@ -378,14 +404,25 @@ int rag_dense_topk_host(rag_handle_t h, const float* q_host, int Q, int k, int t
     int64_t* ids_d = stage_take<int64_t>(p, n_out);
     double* sc_d = stage_take<double>(p, n_out);
     int32_t* rows_d = stage_take<int32_t>(p, n_out);
+    entry_tenants t;
+    if ((rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t))) return rc;
     HIP_TRY(h, hipMemcpyAsync(qd, q_host, (size_t)Q * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-    rc = dense_search(h, qd, Q, k, tenant, ids_d, rows_d, sc_d, st);
+    rc = dense_search(h, qd, Q, k, t.tenant, ids_d, rows_d, sc_d, st, t.qt);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(ids_out, ids_d, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, rows_d, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(scores_out, sc_d, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return RAG_OK;
+}
+int rag_dense_topk_host(rag_handle_t h, const float* q_host, int Q, int k, int tenant, int64_t* ids_out, int32_t* rows_out,
+                        double* scores_out) {
+    return dense_topk_host_entry(h, q_host, Q, k, tenant, nullptr, ids_out, rows_out, scores_out);
+}
+int rag_dense_topk_tenants_host(rag_handle_t h, const float* q_host, int Q, int k, const int32_t* tenants_host, int64_t* ids_out,
+                                int32_t* rows_out, double* scores_out) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return dense_topk_host_entry(h, q_host, Q, k, -1, tenants_host, ids_out, rows_out, scores_out);
 }
 
 int rag_dense_last_stats(rag_handle_t h, rag_dense_stats* out) {
@@ -547,7 +584,17 @@ int rag_bm25_topk_host(rag_handle_t h, const int32_t* term_ptr, const int32_t* t
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return bm25_topk_host(h, term_ptr, terms, Q, k, tenant, ids_out, rows_out, scores_out, raw_max_out);
+    return bm25_topk_host(h, term_ptr, terms, Q, k, tenant, ids_out, rows_out, scores_out, raw_max_out, {nullptr, nullptr});
+}
+int rag_bm25_topk_tenants_host(rag_handle_t h, const int32_t* term_ptr, const int32_t* terms, int Q, int k, const int32_t* tenants_host,
+                               int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "bm25: null tenants array or bad n_queries");
+    HOST_ENTRY(h);
+    entry_tenants t;                  // (staged on the stream bm25_run works on)
+    if (int rc = entry_tenants_of(h, -1, tenants_host, Q, h->stream, &t)) return rc;
+    return bm25_topk_host(h, term_ptr, terms, Q, k, t.tenant, ids_out, rows_out, scores_out, raw_max_out, t.qt);
 }
 
 int rag_bm25_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
@@ -556,7 +603,18 @@ int rag_bm25_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t
     LOCK(h);
     DEV_ENTRY(h);
     return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev,
-                         (hipStream_t)stream);
+                         (hipStream_t)stream, {nullptr, nullptr});
+}
+int rag_bm25_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
+                              const int32_t* tenants_host, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev,
+                              void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "bm25: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
+    return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, (hipStream_t)stream, t.qt);
 }
 
 int rag_rrf_fuse_dev(rag_handle_t h, const int64_t* lists_dev, int Q, int L, int len, int rrf_k, int top_k, int64_t* keys_dev,
@@ -571,20 +629,36 @@ int rag_rrf_fuse_dev(rag_handle_t h, const int64_t* lists_dev, int Q, int L, int
 // dense top-pool + BM25 top-pool + RRF -> top-k, all on the device, one call (BASELINE.json configs[2]).
 // lists_ws_dev: caller scratch [2][Q][pool] int64 (receives the dense, then the BM25 ranked id list);
 // scores_ws_dev: caller scratch [Q][pool] float64.
-int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool,
-                       int k, int rrf_k, int tenant, int64_t* lists_ws_dev, double* scores_ws_dev, int64_t* keys_out_dev,
-                       double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+static int hybrid_rrf_entry(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool,
+                            int k, int rrf_k, int tenant, const int32_t* tenants_host, int64_t* lists_ws_dev, double* scores_ws_dev,
+                            int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
+    ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid: 1 <= n_queries <= 65535");
     ARG_CHECK(h, q_dev && term_ptr_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid: null pointer");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid: 0 < pool <= 256");
     if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows, "hybrid: the BM25 postings must be row-aligned with the index (same number of documents)");
     DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
-    int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st);
+    entry_tenants t;
+    int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t);
     if (rc) return rc;
+    if ((rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, t.tenant, lists_ws_dev, scores_ws_dev, st, t.qt))) return rc;
     return rrf_fuse_dev(h, lists_ws_dev, Q, 2, pool, (int64_t)Q * pool, pool, rrf_k, k, keys_out_dev, rrf_out_dev, ranks_out_dev, st);
+}
+int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool,
+                       int k, int rrf_k, int tenant, int64_t* lists_ws_dev, double* scores_ws_dev, int64_t* keys_out_dev,
+                       double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+    return hybrid_rrf_entry(h, q_dev, term_ptr_dev, terms_dev, Q, pool, k, rrf_k, tenant, nullptr, lists_ws_dev, scores_ws_dev, keys_out_dev,
+                            rrf_out_dev, ranks_out_dev, stream);
+}
+int rag_hybrid_rrf_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool,
+                               int k, int rrf_k, const int32_t* tenants_host, int64_t* lists_ws_dev, double* scores_ws_dev,
+                               int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return hybrid_rrf_entry(h, q_dev, term_ptr_dev, terms_dev, Q, pool, k, rrf_k, -1, tenants_host, lists_ws_dev, scores_ws_dev, keys_out_dev,
+                            rrf_out_dev, ranks_out_dev, stream);
 }
 
 // Per-row temporal score of the linear fusion: RECENCY_WEIGHT * 0.5 ** (days_old / half_life) computed by the host from
@@ -611,21 +685,27 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
 // the corpus, 1.0 when that max is <= 0; temporal from rag_index_set_temporal_host), stable sort descending, first k.
 // The weights are the caller's (intent table or constructor defaults, :232-238). Queries are processed 256 at a time: the
 // all-document BM25 scores of a sub-batch (float64, 2 GB at 1M rows) and their float32 emission bias stay in a workspace.
-int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
-                          double alpha, double beta, double gamma, int tenant, int64_t* ids_out_dev, int32_t* rows_out_dev,
-                          double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev, double* temporal_out_dev,
-                          void* stream) {
+static int hybrid_linear_entry(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
+                               double alpha, double beta, double gamma, int tenant, const int32_t* tenants_host, int64_t* ids_out_dev,
+                               int32_t* rows_out_dev, double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev,
+                               double* temporal_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_dev && term_ptr_dev && ids_out_dev && rows_out_dev && hybrid_out_dev, "hybrid_linear: null pointer");
     ARG_CHECK(h, Q > 0 && k > 0 && k <= RAG_MAX_K, "hybrid_linear: need Q > 0 and 0 < k <= 256");
     ARG_CHECK(h, alpha > 0.0, "hybrid_linear: alpha must be positive (the cosine drives the candidate search)");
     ARG_CHECK(h, std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma), "hybrid_linear: weights must be finite");
+    ARG_CHECK(h, tenants_host == nullptr || Q <= 65535, "hybrid_linear: a tenant array takes n_queries <= 65535");
+    if (tenants_host != nullptr)
+        for (int q = 0; q < Q && tenant < 0; ++q) tenant = std::max(tenants_host[q], -1);      // (for the check below: some filtered query)
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_linear: tenant filter requested but no tenants loaded");
     if (int rc = bm25_fresh(h)) return rc;
     ARG_CHECK(h, bm25_n_docs(h) == h->n_rows && h->n_rows > 0, "hybrid_linear: needs BM25 postings row-aligned with a non-empty index");
     DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
+    tenant = t.tenant;
     const int64_t n = h->n_rows, ld = h->n_rows_pad;
     // queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
     // shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
@@ -651,14 +731,15 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
         // operand) and the per-query maximum; r3 re-read the 2 GB twice more (a one-workgroup-per-query max: 1.8 ms of a 4.5-ms call;
         // a bias pass: 0.6 ms)
         HIP_TRY(h, hipMemsetAsync(max_key, 0, (size_t)qc * sizeof(unsigned long long), st));
-        int rc = bm25_scores_dev(h, term_ptr_dev + q0, terms_dev, qc, raw, st, raw32, ld, max_key, tenant);
+        // (per-query tenants go with their sub-batch: the maximum is each query's own tenant's, the search filters by it)
+        int rc = bm25_scores_dev(h, term_ptr_dev + q0, terms_dev, qc, raw, st, raw32, ld, max_key, tenant, t.qt + q0);
         if (rc) return rc;
         const linear_neg_bound nb = {term_ptr_dev + q0, neg_per_token};
         if ((rc = linear_prepare(h, max_key, nb, qc, n, h->temporal, beta, gamma, mx, qscale, margin, q0 == 0 ? gt : nullptr, ld, st)))
             return rc;
         const dense_fused fz = {raw32, ld, qscale, margin, gt, raw, n, mx, h->temporal, alpha, beta, gamma};
         rc = dense_search_fused(h, q_dev + (size_t)q0 * h->dim, qc, k, tenant, ids_out_dev + (size_t)q0 * k, rows_out_dev + (size_t)q0 * k,
-                                hybrid_out_dev + (size_t)q0 * k, st, &fz);
+                                hybrid_out_dev + (size_t)q0 * k, st, &fz, t.qt + q0);
         if (rc) return rc;
         if (semantic_out_dev || keyword_out_dev || temporal_out_dev) {
             rc = linear_components(h, q_dev + (size_t)q0 * h->dim, rows_out_dev + (size_t)q0 * k, qc, k, &fz,
@@ -669,6 +750,21 @@ int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* ter
         }
     }
     return RAG_OK;
+}
+int rag_hybrid_linear_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
+                          double alpha, double beta, double gamma, int tenant, int64_t* ids_out_dev, int32_t* rows_out_dev,
+                          double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev, double* temporal_out_dev,
+                          void* stream) {
+    return hybrid_linear_entry(h, q_dev, term_ptr_dev, terms_dev, Q, k, alpha, beta, gamma, tenant, nullptr, ids_out_dev, rows_out_dev,
+                               hybrid_out_dev, semantic_out_dev, keyword_out_dev, temporal_out_dev, stream);
+}
+int rag_hybrid_linear_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
+                                  double alpha, double beta, double gamma, const int32_t* tenants_host, int64_t* ids_out_dev,
+                                  int32_t* rows_out_dev, double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev,
+                                  double* temporal_out_dev, void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return hybrid_linear_entry(h, q_dev, term_ptr_dev, terms_dev, Q, k, alpha, beta, gamma, -1, tenants_host, ids_out_dev, rows_out_dev,
+                               hybrid_out_dev, semantic_out_dev, keyword_out_dev, temporal_out_dev, stream);
 }
 
 int rag_bm25_set_normalize(rag_handle_t h, int on) {
@@ -802,7 +898,21 @@ int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_
     DEV_ENTRY(h);
     return retrieve_rerank_dev(h, q_emb_dev, term_ptr_dev, terms_dev, q_tok_dev, q_len_dev, Lq, Q, pool, k, rrf_k, tenant, mode,
                                cls_id, sep_id, L_pair, ids_out_dev, scores_out_dev, logits_out_dev, cand_out_dev,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, {nullptr, nullptr});
+}
+int rag_retrieve_rerank_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                    const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k,
+                                    const int32_t* tenants_host, int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out_dev,
+                                    double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "retrieve_rerank: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
+    return retrieve_rerank_dev(h, q_emb_dev, term_ptr_dev, terms_dev, q_tok_dev, q_len_dev, Lq, Q, pool, k, rrf_k, t.tenant, mode,
+                               cls_id, sep_id, L_pair, ids_out_dev, scores_out_dev, logits_out_dev, cand_out_dev,
+                               (hipStream_t)stream, t.qt);
 }
 
 int rag_ce_build_pairs_dev(rag_handle_t h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev, int Q,

@@ -325,8 +325,10 @@ static bm_grid bm_make_grid(int nr_l, int Q, int linear) {
 // inside its 2048-document range | code of its (tf, doc length) pair) and looks the impact factor g(tf, dl) up in a table shared
 // by all terms. Default: (doc i32, impact f64) = 12 bytes per posting.
 // (SGPRs capped at 96: 256-thread workgroups are admitted 7 per CU up to 96 scalar registers, 6 from 97 on - MI355X_MICROARCH.md)
+// The body of both kernels below. qten: the tenant of every query of the launch (rag_*_tenants_*) or null - a compile-time null in
+// bm25_range_kernel, whose code is therefore what it was before queries had tenants of their own.
 template <bool PACKED>
-__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_kernel(const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc,
+__device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc,
                                                                  const double* __restrict__ w, const uint32_t* __restrict__ packed,
                                                                  const double* __restrict__ gtab,
                                                                  const int32_t* __restrict__ range_tab, int n_ranges,
@@ -335,9 +337,10 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
                                                                  double* __restrict__ dense_out, uint64_t* __restrict__ part_key,
                                                                  uint32_t* __restrict__ part_row, int range_begin,
                                                                  const uint64_t* __restrict__ tau_key, int* __restrict__ part_cnt,
-                                                                 const int32_t* __restrict__ tenants, int tenant,
+                                                                 const int32_t* __restrict__ tenants, int tenant_all,
                                                                  const int32_t* __restrict__ plan_off, const bm_plan_meta* __restrict__ plan_meta,
-                                                                 const bm_grid gm, const bm_dense_extra dx, const bm_seg sg) {
+                                                                 const bm_grid gm, const bm_dense_extra dx, const bm_seg sg,
+                                                                 const int32_t* __restrict__ qten) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup -> (range, query), see bm_make_grid: XCD x (= workgroup id % 8) walks its columns (range, query group) one after the
     // other, every query of the group on the SAME range side by side, so a range's postings are fetched into that XCD's L2 once
@@ -357,6 +360,8 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     // the query's threshold (thresholded stages) is fetched up front: at the compaction step it would be an exposed global
     // round trip for every workgroup
     const uint64_t tk = tau_key != nullptr ? tau_key[q] : 0ull;
+    // ... and so is the query's own tenant (rag_*_tenants_*; qten null: the launch's tenant for every query). Workgroup-uniform.
+    const int tenant = tenant_of_query(qten, q, tenant_all);
     double* sc = reinterpret_cast<double*>(smem);                       // [BM_RANGE]
     int* hist = reinterpret_cast<int*>(smem + BM_SC_DOUBLES * 8);       // [256]
     int* wsum = hist + 256;                                             // [16] scratch
@@ -762,6 +767,28 @@ __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) vo
     if (tid == 0) part_cnt[(size_t)q * n_ranges + r] = k;
 }
 
+#define BM_RANGE_PARAMS                                                                                                                  \
+    const bm_term_meta *__restrict__ meta, const int32_t *__restrict__ doc, const double *__restrict__ w, const uint32_t *__restrict__ packed, \
+        const double *__restrict__ gtab, const int32_t *__restrict__ range_tab, int n_ranges, const int32_t *__restrict__ term_ptr,       \
+        const int32_t *__restrict__ terms, int64_t n_docs, int64_t n_terms, int k, int mode, double *__restrict__ dense_out,              \
+        uint64_t *__restrict__ part_key, uint32_t *__restrict__ part_row, int range_begin, const uint64_t *__restrict__ tau_key,          \
+        int *__restrict__ part_cnt, const int32_t *__restrict__ tenants, int tenant, const int32_t *__restrict__ plan_off,                \
+        const bm_plan_meta *__restrict__ plan_meta, const bm_grid gm, const bm_dense_extra dx, const bm_seg sg
+#define BM_RANGE_ARGS                                                                                                                    \
+    meta, doc, w, packed, gtab, range_tab, n_ranges, term_ptr, terms, n_docs, n_terms, k, mode, dense_out, part_key, part_row, range_begin, \
+        tau_key, part_cnt, tenants, tenant, plan_off, plan_meta, gm, dx, sg
+// one tenant (or none) for the whole launch
+template <bool PACKED>
+__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_kernel(BM_RANGE_PARAMS) {
+    bm25_range_body<PACKED>(BM_RANGE_ARGS, nullptr);
+}
+// a tenant per query: the workgroup reads its query's (`tenant` is not read)
+template <bool PACKED>
+__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_tenants_kernel(BM_RANGE_PARAMS,
+                                                                                                            const int32_t* __restrict__ qten) {
+    bm25_range_body<PACKED>(BM_RANGE_ARGS, qten);
+}
+
 #define BM_MERGE 2048
 __device__ __forceinline__ void bm_sort_pairs(uint64_t* k1, uint32_t* k2, int P, int tid, int nthreads) {
     for (int k = 2; k <= P; k <<= 1) {
@@ -1098,12 +1125,19 @@ struct bm25_topk_out {
 // threshold from 32768 docs left ~k/2 per range: 38 k entries per query to merge on a 12.5M-doc shard).
 // the scoring launch: packed 4-byte postings when the index has them, the 12-byte form otherwise
 // OUT_LD: documents of the whole index (both segments), the row length of the all-document score array
-#define BM_RANGE_LAUNCH(H, IX, OUT_LD, NR_L, NQ, ST, DX, NR, TP, TM, K, MODE, ...)                                                     \
+// QTEN: the per-query tenants of the launch's queries (device) or null
+#define BM_RANGE_LAUNCH(H, IX, OUT_LD, NR_L, NQ, ST, DX, NR, TP, TM, K, MODE, QTEN, ...)                                               \
     {                                                                                                                              \
         bm_grid gm_ = bm_make_grid(NR_L, NQ, (H)->opt.bm25_linear_grid);                                                           \
         gm_.plan_t = (IX)->plan_t;                                                                                                 \
         const bm_seg sg_ = {(IX)->row0, OUT_LD, (IX)->first};                                                                      \
-        if ((IX)->packed != nullptr)                                                                                               \
+        if ((QTEN) != nullptr && (IX)->packed != nullptr)                                                                          \
+            hipLaunchKernelGGL(bm25_range_tenants_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, QTEN); \
+        else if ((QTEN) != nullptr)                                                                                                \
+            hipLaunchKernelGGL(bm25_range_tenants_kernel<false>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, QTEN); \
+        else if ((IX)->packed != nullptr)                                                                                          \
             hipLaunchKernelGGL(bm25_range_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
                                (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_); \
         else                                                                                                                       \
@@ -1132,10 +1166,11 @@ static void bm25_launch_plan(const rag_bm25_index* ix, const int32_t* term_ptr_d
 
 // mode 1 over every segment: out[Q][documents of the index] (+ the linear fusion's extras); each segment writes its own columns
 static void bm25_launch_scores(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q,
-                               double* out, const bm_dense_extra& dx, const int32_t* tenants, int tenant, const bm25_plan_ws& pw, hipStream_t st) {
+                               double* out, const bm_dense_extra& dx, const int32_t* tenants, int tenant, const int32_t* qten,
+                               const bm25_plan_ws& pw, hipStream_t st) {
     const int64_t n_all = bm_total_docs(ix);
     bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, pw, st);
-    BM_RANGE_LAUNCH(h, ix, n_all, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, out, (uint64_t*)nullptr,
+    BM_RANGE_LAUNCH(h, ix, n_all, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, qten, out, (uint64_t*)nullptr,
                     (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)pw.off,
                     (const bm_plan_meta*)pw.meta)
     rag_bm25_index* tl = ix->tail.get();
@@ -1143,7 +1178,7 @@ static void bm25_launch_scores(const rag_ctx* h, const rag_bm25_index* ix, const
     tl->plan_t = ix->plan_t;
     const bm25_plan_ws tp = bm25_tail_plan(ix, Q, pw);
     bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
-    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, dx, tl->n_ranges, term_ptr_dev, terms_dev, 1, 1, out, (uint64_t*)nullptr,
+    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, dx, tl->n_ranges, term_ptr_dev, terms_dev, 1, 1, qten, out, (uint64_t*)nullptr,
                     (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)tp.off,
                     (const bm_plan_meta*)tp.meta)
 }
@@ -1162,7 +1197,8 @@ static void bm25_launch_merge(const rag_ctx* h, const bm25_topk_ws& w, const uin
 }
 
 static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
-                             const bm25_topk_ws& w, const bm25_topk_out& o, const int32_t* tenants, int tenant, hipStream_t st) {
+                             const bm25_topk_ws& w, const bm25_topk_out& o, const int32_t* tenants, int tenant, const int32_t* qten,
+                             hipStream_t st) {
     const int nr = ix->n_ranges;
     rag_bm25_index* tl = ix->tail.get();
     bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, w.plan, st);
@@ -1173,7 +1209,7 @@ static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const i
     while (begin < nr) {
         int end = !staged ? nr : (stage == 0 ? first_cfg : (int)std::min<int64_t>(nr, (int64_t)begin * BM_STAGE_GROWTH));
         if (staged && nr - end < end / 4) end = nr;                   // no tiny trailing stage
-        BM_RANGE_LAUNCH(h, ix, n_all, end - begin, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, term_ptr_dev, terms_dev, k, 0, (double*)nullptr,
+        BM_RANGE_LAUNCH(h, ix, n_all, end - begin, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, term_ptr_dev, terms_dev, k, 0, qten, (double*)nullptr,
                         w.part_key, w.part_row, begin, stage == 0 ? (const uint64_t*)nullptr : (const uint64_t*)w.tau, w.part_cnt,
                         tenants, tenant, (const int32_t*)w.plan.off, (const bm_plan_meta*)w.plan.meta)
         const int last = end == nr && tl == nullptr;
@@ -1191,7 +1227,7 @@ static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const i
     uint64_t* t_key = w.part_key + (size_t)Q * nr * k;
     uint32_t* t_row = w.part_row + (size_t)Q * nr * k;
     int* t_cnt = w.part_cnt + (size_t)Q * nr;
-    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), tl->n_ranges, term_ptr_dev, terms_dev, k, 0,
+    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), tl->n_ranges, term_ptr_dev, terms_dev, k, 0, qten,
                     (double*)nullptr, t_key, t_row, 0, (const uint64_t*)w.tau, t_cnt, tenants, tenant, (const int32_t*)tp.off,
                     (const bm_plan_meta*)tp.meta)
     bm25_launch_merge(h, w, t_key, t_row, t_cnt, tl->n_ranges, 0, tl->n_ranges, Q, k, 0, 1, o, st);
@@ -1862,7 +1898,8 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
 }
 
 static int bm25_set_attr(rag_ctx* h) {
-    return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>);
+    return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>, bm25_range_tenants_kernel<true>,
+                     bm25_range_tenants_kernel<false>);
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
@@ -1879,8 +1916,10 @@ static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
 int bm25_fresh(rag_ctx* h) { return h->bm25 ? bm25_check_fresh(h, h->bm25) : RAG_OK; }
 
 // visibility argument of the scoring kernels (row_visible): the tenant filter and / or the deleted rows of the resident index
-static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, const int32_t** tenants_out) {
+// (per-query tenants: some query is filtered, so the table is needed as under a scalar filter)
+static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, query_tenants qt, const int32_t** tenants_out) {
     *tenants_out = nullptr;
+    if (qt.host != nullptr) tenant = 0;
     if (int rc = bm25_check_fresh(h, ix)) return rc;
     if (tenant < 0) {
         if (ix == h->bm25 && h->vis != nullptr && h->n_rows == bm_total_docs(ix)) *tenants_out = h->vis;
@@ -2147,17 +2186,18 @@ int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_i
 // host-pointer search against `ix` (the resident index or an ad-hoc one). Device staging comes from the handle's
 // grow-only arena: no device allocation per call.
 static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int mode, int tenant,
-                    int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out, double* dense_out) {
+                    int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out, double* dense_out,
+                    query_tenants qt = {nullptr, nullptr}) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr, "bm25: 1 <= n_queries <= 65535");
     const int n_terms_q = term_ptr[Q];
     ARG_CHECK(h, n_terms_q >= 0 && (n_terms_q == 0 || terms), "bm25: bad term arrays");
     if (mode == 0) ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
     const int32_t* tenants = nullptr;
-    int rc = bm25_tenant_args(h, ix, mode == 0 ? tenant : -1, &tenants);
-    if (rc) return rc;
-    if ((rc = bm25_set_attr(h))) return rc;
     hipStream_t st = h->stream;
+    int rc;
+    if ((rc = bm25_tenant_args(h, ix, mode == 0 ? tenant : -1, qt, &tenants))) return rc;
+    if ((rc = bm25_set_attr(h))) return rc;
     const int32_t* dense_vis = mode == 1 ? tenants : nullptr;          // bm25_scores_host: 0.0 for deleted rows
     const int nr = bm_total_ranges(ix);                               // partial lists: the base's ranges, then the tail's
     const size_t n_part = mode == 0 ? (size_t)Q * nr * k : 0, n_out = mode == 0 ? (size_t)Q * k : 0;
@@ -2195,14 +2235,14 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
         const bool aligned = ix == h->bm25 && h->n_rows == bm_total_docs(ix);
         const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, idd, rwd, scd, mxd,
                                  ix->normalize};
-        bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, st);
+        bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, qt.dev, st);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(ids_out, idd, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, rwd, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(scores_out, scd, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
         if (raw_max_out) HIP_TRY(h, hipMemcpyAsync(raw_max_out, mxd, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
     } else {
-        bm25_launch_scores(h, ix, tp, tm, Q, dd, bm_dense_extra{nullptr, 0, nullptr}, dense_vis, -1, w.plan, st);
+        bm25_launch_scores(h, ix, tp, tm, Q, dd, bm_dense_extra{nullptr, 0, nullptr}, dense_vis, -1, nullptr, w.plan, st);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(dense_out, dd, n_dense * sizeof(double), hipMemcpyDeviceToHost, st));
     }
@@ -2218,14 +2258,14 @@ static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
 
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
 static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st);
+                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
 
 // The per-call workspace (partial lists [Q][n_ranges][k] x 12 B + the plan) grows with Q x shard size: on a 12.5M-document shard a
 // query takes ~9 MB at k = 100. Batches are therefore run in sub-batches whose workspace stays under BM_WS_BUDGET (queries are
 // independent: same results; the 1M-document bench index runs 1,024 queries in one piece, the 12.5M-document shard 256).
 #define BM_WS_BUDGET ((size_t)6 << 30)
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st) {
+                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
     if (int rc = bm25_check_fresh(h, h->bm25)) return rc;
@@ -2236,20 +2276,20 @@ int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_
         const int nq = std::min(qb, Q - q0);
         const int rc = bm25_topk_dev_batch(h, term_ptr_dev + q0, terms_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
                                            rows_dev ? rows_dev + (size_t)q0 * k : nullptr, scores_dev + (size_t)q0 * k,
-                                           raw_max_dev ? raw_max_dev + q0 : nullptr, st);
+                                           raw_max_dev ? raw_max_dev + q0 : nullptr, st, qt + q0);      // (the tenants go with their queries)
         if (rc) return rc;
     }
     return RAG_OK;
 }
 
 static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st) {
+                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && ids_dev && scores_dev, "bm25_topk_dev: bad arguments");
     ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
     rag_bm25_index* ix = h->bm25;
     const int32_t* tenants = nullptr;
-    int rc = bm25_tenant_args(h, ix, tenant, &tenants);
+    int rc = bm25_tenant_args(h, ix, tenant, qt, &tenants);
     if (rc) return rc;
     if ((rc = bm25_set_attr(h))) return rc;
     const int nr_all = bm_total_ranges(ix);
@@ -2267,7 +2307,7 @@ static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const in
     const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, ids_dev, rows_dev, scores_dev,
                              raw_max_dev, ix->normalize};
     if ((rc = prof_begin(h, 1, st))) return rc;
-    bm25_launch_topk(h, ix, term_ptr_dev, terms_dev, Q, k, w, o, tenants, tenant, st);
+    bm25_launch_topk(h, ix, term_ptr_dev, terms_dev, Q, k, w, o, tenants, tenant, qt.dev, st);
     HIP_TRY(h, hipGetLastError());
     return prof_end(h, 1, st);
 }
@@ -2276,7 +2316,7 @@ static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const in
 // (the all-document BM25Okapi.get_scores of rag/retrieval.py:340-341, for the index-level linear fusion)
 // raw32_dev / ld / max_key_dev (all optional): see bm_dense_extra; `tenant` restricts the maximum to the tenant's documents
 int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
-                    float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant) {
+                    float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant, query_tenants qt) {
     ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && out_dev, "bm25_scores_dev: bad arguments");
     rag_bm25_index* ix = h->bm25;
@@ -2284,11 +2324,11 @@ int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* term
     if (rc) return rc;
     const int32_t* tenants = nullptr;
     if ((rc = bm25_check_fresh(h, ix))) return rc;
-    if (max_key_dev != nullptr && (rc = bm25_tenant_args(h, ix, tenant, &tenants))) return rc;
+    if (max_key_dev != nullptr && (rc = bm25_tenant_args(h, ix, tenant, qt, &tenants))) return rc;
     const bm_dense_extra dx = {raw32_dev, ld, max_key_dev};
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
     const bm25_plan_ws pw = {ix->ws_plan_off, ix->ws_plan_meta};
-    bm25_launch_scores(h, ix, term_ptr_dev, terms_dev, Q, out_dev, dx, tenants, tenant, pw, st);
+    bm25_launch_scores(h, ix, term_ptr_dev, terms_dev, Q, out_dev, dx, tenants, tenant, qt.dev, pw, st);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -2335,9 +2375,9 @@ int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int
 }
 
 int bm25_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int tenant, int64_t* ids_out,
-                   int32_t* rows_out, double* scores_out, double* raw_max_out) {
+                   int32_t* rows_out, double* scores_out, double* raw_max_out, query_tenants qt) {
     ARG_CHECK(h, ids_out && scores_out, "bm25_topk: null output");
-    return bm25_run(h, h->bm25, term_ptr, terms, Q, k, 0, tenant, ids_out, rows_out, scores_out, raw_max_out, nullptr);
+    return bm25_run(h, h->bm25, term_ptr, terms, Q, k, 0, tenant, ids_out, rows_out, scores_out, raw_max_out, nullptr, qt);
 }
 
 int bm25_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out) {

@@ -87,7 +87,8 @@ struct dense_ws {
     dev_buf<half_t> q16;             // [rows][dim_pad]  fp16 unit query rows; pad rows of a query tile must be zero
     dev_buf<uint64_t> cand;          // [rows][RAG_CAND_CAP]
     dev_buf<unsigned> cnt;           // [rows]   emitted candidates (may exceed cap = overflow)
-    dev_buf<float> tau;              // [rows]   emission threshold = k-th best fp16-pass score so far - 2 eps
+    dev_buf<float> tau;              // [2][rows] emission threshold = k-th best fp16-pass score so far - 2 eps; behind the thresholds of
+                                     //          a pass, the int32 tenants of its query columns (per-query tenants, dense.hip column_tenants)
     dev_buf<float> bound;            // [rows]   -inf, or +inf once the candidate buffer overflowed (sticky)
     dev_buf<int> n_sorted;           // [rows]   survivors left in cand[] after the final select
     int alloc(rag_ctx* h, size_t rows, hipStream_t st);      // (re)allocates every plane and enqueues the zero fill of q16 on st
@@ -130,6 +131,10 @@ struct rag_device_mem : rag_index_mem {
     dev_buf<int32_t> tok_len;
     dev_buf<int> tok_bad;            // device counter of out-of-range token ids seen by the appends
     dev_buf<char> pipe_ws;           // retrieve_rerank_dev: candidate lists, pair tokens, logits of one call
+    // per-query tenants (the *_tenants_* entries, query_tenants below): the batch's tenant numbers and the union of the batch's
+    // tenant tile lists
+    dev_buf<int32_t> qten;           // [>= n_queries]
+    dev_buf<int32_t> union_tiles;    // [<= tiles of the index]
 };
 
 struct rag_ctx : rag_device_mem {
@@ -218,7 +223,7 @@ inline int dense_ws::alloc(rag_ctx* h, size_t rows, hipStream_t st) {
     if ((rc = q16.alloc(h, rows * h->dim_pad))) return rc;
     if ((rc = cand.alloc(h, rows * RAG_CAND_CAP))) return rc;
     if ((rc = cnt.alloc(h, rows))) return rc;
-    if ((rc = tau.alloc(h, rows))) return rc;
+    if ((rc = tau.alloc(h, 2 * rows))) return rc;
     if ((rc = bound.alloc(h, rows))) return rc;
     if ((rc = n_sorted.alloc(h, rows))) return rc;
     // zero fills go on the search's own stream: a null-stream hipMemset is not ordered against a non-blocking stream
@@ -273,6 +278,22 @@ __device__ __forceinline__ bool row_visible(const int32_t* __restrict__ vis, int
 static inline const int32_t* search_vis(const rag_ctx* h, int tenant) {
     return h->vis ? h->vis.get() : (tenant >= 0 ? h->tenants.get() : nullptr);
 }
+
+// ---- per-query tenants (rag_*_tenants_*): query i of the batch is filtered by its own tenant, < 0 = not filtered. Both null: the
+// call's scalar tenant holds for every query. host = the caller's array (read while the call enqueues: the tile universe is chosen
+// from it), dev = its copy in rag_ctx::qten, written on the call's stream by stage_query_tenants. A sub-batch offsets both.
+struct query_tenants { const int32_t* host; const int32_t* dev; };
+static inline query_tenants operator+(query_tenants t, int q0) {
+    return t.host ? query_tenants{t.host + q0, t.dev + q0} : t;
+}
+// the tenant a kernel applies to query q (qten = query_tenants::dev or null)
+__device__ __forceinline__ int tenant_of_query(const int32_t* __restrict__ qten, int q, int tenant) {
+    return qten != nullptr ? qten[q] : tenant;
+}
+// host words -> device memory as ordinary work of `st`: the words travel as kernel arguments, so the host array is consumed when
+// this returns and nothing waits for the stream (a pageable hipMemcpyAsync would). dense.hip
+int upload_i32(rag_ctx* h, int32_t* dst_dev, const int32_t* src_host, size_t n, hipStream_t st);
+int stage_query_tenants(rag_ctx* h, const int32_t* tenants_host, int Q, hipStream_t st, query_tenants* out);
 
 // ---- profiling spans (no-ops unless rag_set_profiling(h, 1))
 static inline int prof_begin(rag_ctx* h, int stage, hipStream_t st) {
@@ -359,15 +380,16 @@ struct dense_fused {
     double alpha, beta, gamma;
 };
 // fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev (dense.hip)
+// qt: per-query tenants (then `tenant` is not read)
 int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                       double* scores_dev, hipStream_t st, const dense_fused* fz);
+                       double* scores_dev, hipStream_t st, const dense_fused* fz, query_tenants qt = {nullptr, nullptr});
 static inline int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                               double* scores_dev, hipStream_t st) {
-    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr);
+                               double* scores_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr}) {
+    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr, qt);
 }
 void comm_free(rag_ctx* h);
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st);
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr});
 // the query terms and what bounds a negative raw BM25 score from them (bm25_negative_bound_args)
 struct linear_neg_bound { const int32_t* term_ptr; double per_token; };
 int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bound nb, int Q, int64_t n, const double* temporal,

@@ -172,6 +172,20 @@ struct tile_universe {
 };
 // The arguments of one emit launch, by value. The host fills it once per search (emit_args_of), then sets the per-pass fields
 // where a pass begins and the per-stage fields where a stage begins.
+// Per-query tenants reach the emit kernels WITHOUT a new argument: the fused persistent instantiation holds 105 of the 106 scalar
+// registers a wave can have, and one more pointer spilled it to scratch. The tenants of a pass's query columns are stored as
+// int32 behind the pass's thresholds, in the same plane (dense_ws::tau is [2][rows]; a pass over n_qtiles query tiles keeps them
+// at tau + n_qtiles * RAG_TILE), and emit_args::tenant == RAG_TENANT_PER_QUERY says that they are there.
+// It never reaches a kernel from a caller's scalar: dense_search_fused turns every scalar tenant < 0 into -1 first.
+// The layout has one definition, column_tenants: dense_ws::alloc sizes the plane for it (2 x rows, checked below), the search
+// writes rows [0, Q) of the second half and the overflow gather rows [0, RAG_TILE) of the one-tile workspace's; search_init_kernel
+// and select_kernel touch thresholds [0, rows) only.
+#define RAG_TENANT_PER_QUERY (-2)
+static_assert(RAG_TENANT_PER_QUERY < -1, "the per-query mark must differ from the normalised scalar tenants (-1 and >= 0)");
+static_assert(sizeof(int32_t) == sizeof(float), "column tenants share the threshold plane word for word");
+__host__ __device__ static inline int32_t* column_tenants(const float* tau, int n_qtiles) {
+    return reinterpret_cast<int32_t*>(const_cast<float*>(tau)) + (size_t)n_qtiles * RAG_TILE;
+}
 struct emit_args {
     const half_t* corpus16;      // [n_rows_pad][Dp] fp16 (2^7 * unit rows)
     const half_t* q16;           // per pass: [n_qtiles * 256][Dp] fp16 query rows, pad rows zero
@@ -184,7 +198,7 @@ struct emit_args {
     unsigned* cnt;               // per pass: [q] emitted keys so far
     uint64_t* cand;              // per pass: [q][RAG_CAND_CAP] keys
     const int32_t* vis;          // row visibility table (row_visible) or null
-    int tenant;                  // tenant filter or < 0
+    int tenant;                  // tenant filter, < 0: none, RAG_TENANT_PER_QUERY: each query COLUMN of the pass has its own (column_tenants)
     tile_universe tiles;         // which tiles the positions stand for
     const int* active_count;     // per pass: device count of re-emitted queries (0: the launch has nothing to do) or null
     const float* bias; int64_t bias_ld;      // FUSED: float32 raw BM25 scores [query][bias_ld]
@@ -194,7 +208,8 @@ struct emit_args {
     const float* gt;             // FUSED: [row] gamma * temporal or null
 };
 // one 256 x 256 tile; vb = the (virtual) block index that selects it
-template <bool DENSE0, bool SMALLQ, bool FUSED>
+// COLTEN: the instantiation honours RAG_TENANT_PER_QUERY. All do but the fused persistent kernel (see there).
+template <bool DENSE0, bool SMALLQ, bool FUSED, bool COLTEN = true>
 __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a) {
     const half_t *__restrict__ corpus16 = a.corpus16, *__restrict__ q16 = a.q16;
     const int Dp = a.Dp, rtile_begin = a.rtile_begin, n_rtiles = a.n_rtiles, n_qtiles = a.n_qtiles;
@@ -205,6 +220,8 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a
     const int32_t *__restrict__ vis = a.vis, *__restrict__ tile_list = a.tiles.list;
     const int tile_mul = a.tiles.mul, tile_mod = a.tiles.mod, tile_cnt = a.tiles.count;
     const int *__restrict__ active_count = a.active_count, *__restrict__ qmap = a.qmap;
+    // the tenant of query column q (resolved where it is used: a pointer held from here on would cost two scalar registers)
+#define COLUMN_TENANT(q) (COLTEN && tenant == RAG_TENANT_PER_QUERY ? column_tenants(tau, n_qtiles)[q] : tenant)
     const float *__restrict__ bias = a.bias, *__restrict__ qscale = a.qscale, *__restrict__ gt = a.gt;
     const int64_t bias_ld = a.bias_ld;  const float alpha = a.alpha;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -338,6 +355,7 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a
         for (int j = 0; j < 4; ++j) {
             const int q = q0 + wn * 64 + j * 16 + fr;
             if (q >= q_valid) continue;
+            const int tn = COLUMN_TENANT(q);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 // every dense slot is written (0 = empty for padded / filtered rows): no memset needed beforehand; the lane's
@@ -347,7 +365,7 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = rbase + r;
-                    const bool ok = row < n_rows_valid && row_visible(vis, row, tenant);
+                    const bool ok = row < n_rows_valid && row_visible(vis, row, tn);
                     kk[r] = ok ? make_key(acc[i][j][r] * scale, (uint32_t)row) : 0ull;
                 }
                 ulonglong2* dst = reinterpret_cast<ulonglong2*>(cand + (size_t)q * RAG_CAND_CAP + (rbase - row0) + pos * RAG_TILE);
@@ -387,7 +405,8 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a
                     const int bit = __ffs(rem) - 1;
                     rem &= rem - 1;
                     const int row = row0 + wm * 128 + (bit >> 2) * 16 + fq * 4 + (bit & 3);
-                    if (row >= n_rows_valid || !row_visible(vis, row, tenant)) h &= ~(1u << bit);
+                    // (the column's own tenant under per-query tenants, fetched per hit: a hit implies q < q_valid - thr is +inf past it)
+                    if (row >= n_rows_valid || !row_visible(vis, row, COLUMN_TENANT(q))) h &= ~(1u << bit);
                 }
             }
         }
@@ -416,6 +435,8 @@ __device__ __forceinline__ void dense_emit_tile(const int vb, const emit_args& a
     }
 }
 
+#undef COLUMN_TENANT
+
 template <bool DENSE0, bool SMALLQ, bool FUSED = false>
 __global__ __launch_bounds__(512) void dense_emit_kernel(emit_args a) {
     dense_emit_tile<DENSE0, SMALLQ, FUSED>(blockIdx.x, a);
@@ -424,11 +445,14 @@ __global__ __launch_bounds__(512) void dense_emit_kernel(emit_args a) {
 // Second pass (queries whose buffer overflowed): almost always there is nothing to do, and a corpus-sized grid of 128 KiB-LDS
 // workgroups costs ~40 us just to be dispatched and retired. One workgroup per CU walks the tiles instead; idle, the launch
 // costs one read of the device-side count per workgroup.
+// (The fused instantiation holds 105 of a wave's 106 scalar registers and all 256 vector registers: resolving a column's own tenant
+// there spilled to scratch, so it is compiled without it and a fused search with per-query tenants re-emits through the
+// one-workgroup-per-tile kernel instead - emit_dispatch.)
 template <bool FUSED>
 __global__ __launch_bounds__(512) void dense_emit_persist_kernel(int n_vblocks, emit_args a) {
     if (a.active_count != nullptr && *a.active_count == 0) return;
     for (int vb = blockIdx.x; vb < n_vblocks; vb += gridDim.x) {
-        dense_emit_tile<false, false, FUSED>(vb, a);
+        dense_emit_tile<false, false, FUSED, !FUSED>(vb, a);
         __syncthreads();                                   // the next tile's prologue refills LDS stages this tile still reads
     }
 }
@@ -729,7 +753,8 @@ __device__ __forceinline__ void bitonic_sort_pairs(uint64_t* k1, uint32_t* k2, i
 }
 
 __global__ __launch_bounds__(256) void scan_chunk_kernel(const float* __restrict__ q32, const float* __restrict__ emb32,
-                                                          const int32_t* __restrict__ vis, int tenant, int64_t n_rows,
+                                                          const int32_t* __restrict__ vis, int tenant,
+                                                          const int32_t* __restrict__ qten, int64_t n_rows,
                                                           int64_t rows_per_block, int dim, int k, const int* __restrict__ list,
                                                           const int* __restrict__ count, int f0, int round_q,
                                                           uint64_t* __restrict__ part_key,
@@ -745,12 +770,13 @@ __global__ __launch_bounds__(256) void scan_chunk_kernel(const float* __restrict
     const int window = SCAN_CHUNK - k;
     for (int f = f0; f < f_end; ++f) {
         const int q = list[f];
+        const int tn = tenant_of_query(qten, q, tenant);
         for (int i = tid; i < k; i += 256) { sk[i] = 0ull; sr[i] = 0xFFFFFFFFu; }      // running top-k of this row block
         for (int64_t w0 = base; w0 < base_end; w0 += window) {
             for (int i = wv; i < window; i += 4) {
                 const int64_t row = w0 + i;
                 uint64_t key = 0ull;          // 0 = empty (below every real score: orderable(-inf) > 0)
-                if (row < base_end && row_visible(vis, row, tenant)) {
+                if (row < base_end && row_visible(vis, row, tn)) {
                     double v = exact_cosine_wave(q32 + (size_t)q * dim, emb32 + (size_t)row * dim, dim, lane);
                     if (raw != nullptr)               // linear fusion (rag/retrieval.py:302), same operation order as linear_fuse_kernel
                         v = (fa * v + fb * (raw[(size_t)q * raw_ld + row] / raw_mx[q])) + fg * (temporal ? temporal[row] : 0.0);
@@ -818,15 +844,18 @@ __global__ __launch_bounds__(256) void scan_merge_kernel(const uint64_t* __restr
 // that tau into a fresh buffer by the same MFMA kernel; only if THAT overflows too does the query go to the float64 scan.
 // gather: workgroup f copies the fp16 query row and tau of the f-th overflowed query; unused slots get tau = +inf.
 // (the list was appended to by the final select; its dead slots are pointed at query 0 here: the fused re-emission reads the
-// bias row of every slot through it, and a stale entry of an earlier, larger batch would index outside the bias buffer)
+// bias row of every slot through it, and a stale entry of an earlier, larger batch would index outside the bias buffer - or, with
+// per-query tenants, outside the batch's tenant array)
 __global__ __launch_bounds__(256) void overflow_gather_kernel(int* __restrict__ list, const int* __restrict__ count,
                                                                const half_t* __restrict__ q16, const float* __restrict__ tau, int Dp,
                                                                half_t* __restrict__ q16b, float* __restrict__ taub,
-                                                               float* __restrict__ boundb, unsigned* __restrict__ cntb) {
+                                                               float* __restrict__ boundb, unsigned* __restrict__ cntb,
+                                                               const int32_t* __restrict__ qten) {
     const int f = blockIdx.x;
     const bool live = f < min(*count, RAG_TILE);
     if (threadIdx.x == 0) {
         if (!live) list[f] = 0;
+        if (qten != nullptr) column_tenants(taub, 1)[f] = qten[list[f]];       // per-query tenants: column f of the second pass stands for query list[f]
         taub[f] = live ? tau[list[f]] : INFINITY;
         boundb[f] = -INFINITY;
         cntb[f] = 0u;
@@ -958,6 +987,33 @@ static int launch_normalize(rag_ctx* h, const float* src, half_t* dst, int64_t n
     return launch_status(h);
 }
 
+// ---- host words -> device memory through kernel arguments (upload_i32, common.h)
+#define FILL_WORDS 960                    // 3840 B of the 4 KiB a launch's arguments may take
+struct fill_block { int32_t v[FILL_WORDS]; };
+__global__ __launch_bounds__(256) void fill_i32_kernel(int32_t* __restrict__ dst, int n, const fill_block b) {
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = b.v[i];
+}
+int upload_i32(rag_ctx* h, int32_t* dst_dev, const int32_t* src_host, size_t n, hipStream_t st) {
+    fill_block b;
+    for (size_t o = 0; o < n; o += FILL_WORDS) {
+        const int m = (int)std::min<size_t>(FILL_WORDS, n - o);
+        std::copy(src_host + o, src_host + o + m, b.v);
+        launch(fill_i32_kernel, dim3(1), dim3(256), 0, st, dst_dev + o, m, b);
+    }
+    return launch_status(h);
+}
+
+// The batch's per-query tenants -> rag_ctx::qten on st. The caller has
+// ruled out the uniform batch (every query the same tenant, or none filtered: the scalar path serves it), so some query is filtered.
+int stage_query_tenants(rag_ctx* h, const int32_t* tenants_host, int Q, hipStream_t st, query_tenants* out) {
+    ARG_CHECK(h, h->tenants != nullptr, "tenant filter requested but no tenants loaded");
+    int rc;
+    if ((rc = h->qten.reserve(h, (size_t)round_up(Q, 1024)))) return rc;
+    if ((rc = upload_i32(h, h->qten, tenants_host, (size_t)Q, st))) return rc;
+    *out = {tenants_host, h->qten.get()};
+    return RAG_OK;
+}
+
 // multiplier of the tile-order permutation p -> (p * a) mod T: close to the golden-ratio conjugate of T (every prefix of
 // positions is then spread evenly over the table) and coprime to T (a bijection)
 static int tile_multiplier(int T) {
@@ -1084,10 +1140,39 @@ static double search_eps(const rag_ctx* h, const dense_fused* fz) {
 }
 
 // the tile universe of one search (tile_universe, beside emit_args): every tile or the tenant's list, and the permutation over it
-static int search_tiles(rag_ctx* h, int tenant, tile_universe* u) {
+// Per-query tenants (qt, Q queries): when every query is filtered and the tile lists of the batch's distinct tenants are together
+// shorter than the table, the universe is their sorted union, merged here and written into rag_ctx::union_tiles on st; otherwise
+// every tile. (A query then walks tiles of the other tenants too and filters their rows out hit by hit: per-query universes are
+// out of scope)
+static int search_tiles(rag_ctx* h, int tenant, query_tenants qt, int Q, hipStream_t st, tile_universe* u) {
     u->list = nullptr;
     u->count = (int)(round_up(h->n_rows, RAG_TILE) / RAG_TILE);
-    if (tenant >= 0) {
+    if (qt.host != nullptr) {
+        ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
+        std::vector<int32_t> distinct(qt.host, qt.host + Q);
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        size_t total = 0;
+        for (const int32_t t : distinct) {
+            const auto it = h->tenant_lists.find(t);
+            total += t < 0 ? (size_t)u->count : (it == h->tenant_lists.end() ? 0 : it->second.size());
+        }
+        if (total < (size_t)u->count) {
+            std::vector<int32_t> tiles;
+            tiles.reserve(total);
+            for (const int32_t t : distinct) {
+                const auto it = h->tenant_lists.find(t);
+                if (it != h->tenant_lists.end()) tiles.insert(tiles.end(), it->second.begin(), it->second.end());
+            }
+            std::sort(tiles.begin(), tiles.end());
+            tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
+            // (sized for every tile of the index at once: a re-allocation frees, and a free waits for the device)
+            if (int rc = h->union_tiles.reserve(h, std::max<size_t>((size_t)u->count, 1024))) return rc;
+            if (int rc = upload_i32(h, h->union_tiles, tiles.data(), tiles.size(), st)) return rc;
+            u->count = (int)tiles.size();
+            u->list = tiles.empty() ? nullptr : h->union_tiles.get();
+        }
+    } else if (tenant >= 0) {
         ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
         const auto it = h->tenant_span.find(tenant);
         u->count = it == h->tenant_span.end() ? 0 : it->second.second;
@@ -1139,7 +1224,7 @@ static int launch_emit_persist(rag_ctx* h, int wgs, int n_vblocks, const emit_ar
 static int emit_dispatch(rag_ctx* h, bool stage0, bool fused, bool smallq, int n_vblocks, int persist_wgs, const emit_args& a, hipStream_t st) {
     int rc;
     if (stage0) rc = fused ? launch_emit<true, false, true>(h, n_vblocks, a, st) : launch_emit<true, false, false>(h, n_vblocks, a, st);
-    else if (fused) rc = persist_wgs ? launch_emit_persist<true>(h, persist_wgs, n_vblocks, a, st) : launch_emit<false, false, true>(h, n_vblocks, a, st);
+    else if (fused) rc = persist_wgs && a.tenant != RAG_TENANT_PER_QUERY ? launch_emit_persist<true>(h, persist_wgs, n_vblocks, a, st) : launch_emit<false, false, true>(h, n_vblocks, a, st);
     else if (smallq) rc = launch_emit<false, true, false>(h, n_vblocks, a, st);
     else rc = persist_wgs ? launch_emit_persist<false>(h, persist_wgs, n_vblocks, a, st) : launch_emit<false, false, false>(h, n_vblocks, a, st);
     return rc ? rc : launch_status(h);
@@ -1200,11 +1285,13 @@ static int first_pass(rag_ctx* h, emit_args a, const std::vector<stage_range>& p
 
 // ---- second pass for overflowed queries (device-side early exit when there are none): gathered into the one-tile workspace,
 // re-emitted over all total_tiles positions by one persistent workgroup per CU, selected, and scattered back where they fitted
-static int second_pass(rag_ctx* h, emit_args a, int total_tiles, int k, float two_eps, const dense_fused* fz, hipStream_t st) {
+// first_tenants: the first pass's column tenants under per-query tenants, or null
+static int second_pass(rag_ctx* h, emit_args a, int total_tiles, int k, float two_eps, const dense_fused* fz, const int32_t* first_tenants,
+                       hipStream_t st) {
     const dense_ws &w = h->ws, &o = h->ws_ovf;
     int* const ovf_count = h->ovf_list + RAG_TILE;
     launch(overflow_gather_kernel, dim3(RAG_TILE), dim3(256), 0, st, h->ovf_list, ovf_count, w.q16, w.tau, h->dim_pad, o.q16, o.tau, o.bound,
-           o.cnt);
+           o.cnt, first_tenants);                                          // (the columns' tenants are gathered like their thresholds)
     a.q16 = o.q16; a.tau = o.tau; a.cnt = o.cnt; a.cand = o.cand;         // the pass runs over the one-tile workspace, every tile position
     a.n_qtiles = 1; a.q_valid = RAG_TILE; a.rtile_begin = 0; a.n_rtiles = total_tiles;
     a.active_count = ovf_count; a.qmap = fz ? h->ovf_list.get() : nullptr;
@@ -1227,7 +1314,7 @@ static int rescore_and_finalize(rag_ctx* h, const float* q_dev, int Q, int k, co
 
 // ---- exact scan for whatever is still unproven (the queries finalize appended to scan_list, count = stats[7]): rounds of
 // SCAN_ROUND flagged queries, device-side early exit when none
-static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const int32_t* vis, int tenant, const dense_fused* fz,
+static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const int32_t* vis, int tenant, const int32_t* qten, const dense_fused* fz,
                              int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
     if (h->n_rows == 0) return RAG_OK;
     const int window = SCAN_CHUNK - k;
@@ -1243,7 +1330,7 @@ static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const
     const dense_fused none = {};
     const dense_fused& f = fz ? *fz : none;
     for (int f0 = 0; f0 < Q; f0 += round_q) {
-        launch(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, h->n_rows, rows_per_block, h->dim, k,
+        launch(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, qten, h->n_rows, rows_per_block, h->dim, k,
                h->scan_list, scan_count, f0, round_q, pk, pr, f.raw, f.n, f.mx, f.temporal, f.alpha, f.beta, f.gamma);
         launch(scan_merge_kernel, dim3(std::min(Q - f0, round_q)), dim3(256), 0, st, pk, pr, n_blocks, k, h->ids, h->id_base, h->scan_list,
                scan_count, f0, h->flag, ids_dev, rows_dev, scores_dev, h->stats);
@@ -1264,9 +1351,13 @@ static emit_args emit_args_of(const rag_ctx* h, const tile_universe& u, const in
 // fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev: the emitted / keyed / ranked score
 // is alpha * cosine + beta * keyword + gamma * temporal (fz carries the per-(query,row) bias and the float64 inputs).
 int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                       double* scores_dev, hipStream_t st, const dense_fused* fz) {
+                       double* scores_dev, hipStream_t st, const dense_fused* fz, query_tenants qt) {
     ARG_CHECK(h, h->index_loaded, "no index loaded");
     ARG_CHECK(h, Q > 0 && k > 0 && k <= RAG_MAX_K, "need Q>0 and 0<k<=256");
+    // any scalar tenant < 0 is "no filter" (include/rag_hip.h) and is -1 from here on: RAG_TENANT_PER_QUERY, which emit_args_of
+    // below forms for a tenant array alone, is a negative value too and must never arrive from a caller
+    if (tenant < 0) tenant = -1;
+    if (qt.host != nullptr) tenant = 0;            // some query is filtered (stage_query_tenants): the checks and tables of a filter
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "tenant filter requested but no tenants loaded");
     int rc = ensure_workspace(h, Q, st);
     if (rc) return rc;
@@ -1274,15 +1365,22 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
     const double eps = search_eps(h, fz);
     const float two_eps = (float)(2.0 * eps * 1.0001 + 1e-7);        // float subtraction in the select kernel: round up
     tile_universe u;
-    if ((rc = search_tiles(h, tenant, &u))) return rc;
+    if ((rc = search_tiles(h, tenant, qt, Q, st, &u))) return rc;
     const std::vector<stage_range> plan = stage_plan(u.count, Q, k, h->opt.stage_growth);
-    const emit_args a = emit_args_of(h, u, vis, tenant, fz);
+    const emit_args a = emit_args_of(h, u, vis, qt.dev != nullptr ? RAG_TENANT_PER_QUERY : tenant, fz);
+    int32_t* col_tenants = nullptr;                // per-query tenants: the first pass's columns are the queries themselves
+    if (qt.dev != nullptr) {
+        col_tenants = column_tenants(h->ws.tau, (int)round_up(Q, RAG_TILE) / RAG_TILE);
+        ARG_CHECK(h, (size_t)round_up(Q, RAG_TILE) + Q <= h->ws.tau.size() && h->ws_ovf.tau.size() >= 2 * RAG_TILE,
+                  "internal: the threshold plane does not hold the column tenants");
+        HIP_TRY(h, hipMemcpyAsync(col_tenants, qt.dev, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
     const bool with_second_pass = !h->opt.no_second_pass;
     if ((rc = prepare_queries(h, q_dev, Q, st))) return rc;
     if ((rc = first_pass(h, a, plan, Q, k, two_eps, fz, with_second_pass, st))) return rc;
-    if (u.count > 0 && with_second_pass && (rc = second_pass(h, a, u.count, k, two_eps, fz, st))) return rc;
+    if (u.count > 0 && with_second_pass && (rc = second_pass(h, a, u.count, k, two_eps, fz, col_tenants, st))) return rc;
     if ((rc = rescore_and_finalize(h, q_dev, Q, k, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
-    if ((rc = exact_scan_rounds(h, q_dev, Q, k, vis, tenant, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
+    if ((rc = exact_scan_rounds(h, q_dev, Q, k, vis, tenant, qt.dev, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
     h->last_q = Q;
     h->last_k = k;
     h->last_stages = (int)plan.size();

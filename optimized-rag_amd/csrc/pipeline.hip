@@ -12,7 +12,7 @@
 #include "common.h"
 
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st);
+                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
 int64_t bm25_n_docs(const rag_ctx* h);
 int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
                  int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
@@ -26,13 +26,13 @@ int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, in
 // Option no_fork keeps the legs in line always; fork_max_q lowers the largest batch that forks.
 #define RAG_FORK_MAX_Q 4096
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st) {
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt) {
     int64_t* const bm_ids = lists_dev + (size_t)Q * pool;
     const int fork_max = h->opt.fork_max_q > 0 ? h->opt.fork_max_q : RAG_FORK_MAX_Q;
     if (Q > fork_max || h->opt.no_fork) {
-        int rc = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st);
+        int rc = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);
         if (rc) return rc;
-        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores_ws_dev, nullptr, st);
+        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores_ws_dev, nullptr, st, qt);
     }
     if (!h->side_stream) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
@@ -41,12 +41,13 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
     }
     const size_t need = (size_t)Q * pool;
     if (int rc = h->side_scores.reserve(h, std::max(need, (size_t)RAG_FORK_MAX_Q * RAG_MAX_K))) return rc;
-    HIP_TRY(h, hipEventRecord(h->ev_fork, st));                    // inputs are ready wherever the caller's stream is now
+    // inputs are ready wherever the caller's stream is now (the device copy of per-query tenants among them: written on st before this)
+    HIP_TRY(h, hipEventRecord(h->ev_fork, st));
     HIP_TRY(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-    int rc = bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, h->side_scores, nullptr, h->side_stream);
+    int rc = bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, h->side_scores, nullptr, h->side_stream, qt);
     // the join is recorded and waited for even if a leg failed to launch: the caller's stream must never run ahead of the side stream
     HIP_TRY(h, hipEventRecord(h->ev_join, h->side_stream));
-    const int rc2 = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st);
+    const int rc2 = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);
     HIP_TRY(h, hipStreamWaitEvent(st, h->ev_join, 0));
     return rc ? rc : rc2;
 }
@@ -240,7 +241,7 @@ __global__ void map_rows_to_ids_kernel(int64_t* __restrict__ v, int64_t n, const
 int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                         const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
                         int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out, double* scores_out, float* logits_out,
-                        int64_t* cand_out, hipStream_t st) {
+                        int64_t* cand_out, hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, h->ce != nullptr, "retrieve_rerank: no cross-encoder loaded");
     ARG_CHECK(h, h->tok != nullptr && h->tok_rows == h->n_rows, "retrieve_rerank: token store missing or not row-aligned with the index");
     ARG_CHECK(h, Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "retrieve_rerank: 0 < k <= pool <= 256");
@@ -274,9 +275,9 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     h->id_base = 0;
     int rc;
     if (mode == 0) {
-        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st);
+        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st, qt);
     } else {
-        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st);
+        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, qt);
         if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, pool, cand, rrf, ranks, st);
     }
     h->ids = std::move(ids_saved);

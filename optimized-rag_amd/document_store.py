@@ -235,12 +235,32 @@ class GpuDocumentIndex:
         return row_map
 
     def _search_rows(self, agent_id, query_embeddings, top_k):
+        if isinstance(agent_id, (list, tuple, np.ndarray)):
+            return self._search_rows_mixed(agent_id, query_embeddings, top_k)
         if agent_id is not None and str(agent_id) not in self._tenant_id:
             Q = np.asarray(query_embeddings).reshape(-1, self.dim).shape[0]
             return np.full((Q, top_k), -1, dtype=np.int32), np.zeros((Q, top_k))
         tenant = -1 if agent_id is None else self._tenant_id[str(agent_id)]
         _, rows, scores = self.engine.dense_topk(np.asarray(query_embeddings, dtype=np.float32).reshape(-1, self.dim),
                                                  top_k, tenant=tenant)
+        return rows, scores
+
+    def _search_rows_mixed(self, agent_ids, query_embeddings, top_k):
+        """One agent PER QUERY (agents mixed in one batch): ONE dense call with a tenant array (rag_dense_topk_tenants_host), row i
+        filtered by agent_ids[i] (None: not filtered). An unknown agent owns no row: its query searches under a tenant number no
+        row carries and comes back all padding, as the single call returns []."""
+        q = np.asarray(query_embeddings, dtype=np.float32).reshape(-1, self.dim)
+        if len(agent_ids) != q.shape[0]:
+            raise ValueError(f"{len(agent_ids)} agent ids for {q.shape[0]} queries")
+        nobody = max(self._tenant_id.values(), default=-1) + 1
+        tenants = np.array([-1 if a is None else self._tenant_id.get(str(a), nobody) for a in agent_ids], dtype=np.int32)
+        if not self._tenant_id and (tenants >= 0).any():             # no agent known at all (no tenant table): a filtered query finds nothing
+            unfiltered = tenants < 0
+            rows, scores = np.full((q.shape[0], top_k), -1, dtype=np.int32), np.zeros((q.shape[0], top_k))
+            if unfiltered.any():
+                _, rows[unfiltered], scores[unfiltered] = self.engine.dense_topk(q[unfiltered], top_k, tenant=-1)
+            return rows, scores
+        _, rows, scores = self.engine.dense_topk(q, top_k, tenant=tenants)
         return rows, scores
 
     def search(self, agent_id: str, query: str, top_k: int = 5, with_embeddings: bool = True) -> List[Dict[str, Any]]:
@@ -271,7 +291,8 @@ class GpuDocumentIndex:
         its surface reaches the batched throughput): ONE embedding call for all queries when the service offers
         `generate_embeddings_batch`, ONE rag_dense_topk_host call with Q = len(queries), one row fetch. Element i equals
         `search(agent_id, queries[i], top_k, with_embeddings)`; on failure every element is [] (the reference's log-and-
-        return-empty, :483-485)."""
+        return-empty, :483-485). agent_id may be a list with one agent per query (a host serving many agents from one index
+        batches their queries together): element i then equals `search(agent_id[i], queries[i], ...)`, [] for an unknown agent."""
         try:
             if not queries:
                 return []
@@ -306,7 +327,8 @@ class GpuDocumentIndex:
 
     @_locked
     def search_batch(self, agent_id: Optional[str], query_embeddings, top_k: int = 20):
-        """Batched entry the reference lacks: Q query embeddings at once -> (row indices [Q,k], cosines [Q,k])."""
+        """Batched entry the reference lacks: Q query embeddings at once -> (row indices [Q,k], cosines [Q,k]). agent_id: one
+        agent for the batch, None (no filter), or a list with one agent (or None) per query."""
         return self._search_rows(agent_id, query_embeddings, top_k)
 
     @_locked
