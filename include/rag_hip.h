@@ -438,6 +438,12 @@ typedef struct rag_ce_config {
     int32_t vocab_size, hidden, layers, heads, ffn, max_pos, type_vocab, reserved;
     double ln_eps;
 } rag_ce_config;
+/* Shapes that load (rag_ce_load_host and rag_embed_load_host alike; anything else is RAG_ERR_ARG with a "ce_load:" message):
+ * hidden a multiple of 128 up to 1024, ffn a multiple of 128, and a head dim (hidden / heads) of
+ *   32 at every hidden size, or
+ *   64 at hidden 128, 256, 512, 640, 768, 896 and 1024 - the BERT-base (768 / 12) and BERT-large (1024 / 16) shapes, the small
+ *      BERTs (128 / 2, 256 / 4, 512 / 8). These run the split-fp16 forward with an attention instance of their own.
+ * Hidden 384 takes head dim 32 only (12 heads): that width is the MX forward's, whose operands are laid out per 32-wide head. */
 int rag_ce_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors_host, int n_tensors);
 /* input_ids/token_type_ids: [P][L] int32 (padded), lens[P]; logits_out[P] raw logits (float32).
  * lens[p] outside [1, seq_len] is clamped to it (0 and negative values count as 1, anything above seq_len as seq_len), once, before
@@ -457,16 +463,22 @@ int rag_ce_score_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t
  *      _generate_batch_uncached (memory/embeddings.py:100-115, 226-246; dimension lookup :312-332). NOT a parity
  *      replacement: a local encoder produces DIFFERENT vectors than text-embedding-3-small, so an index must be built and
  *      queried with the same model (outside the 1e-3 contract of the north star; what is pinned is this forward against
- *      transformers.BertModel). The model is a BERT encoder (the cross-encoder's kernels) behind sentence-transformers'
- *      Pooling(mean) + Normalize head: tensors as rag_ce_load_host WITHOUT the four pooler / classifier tensors
- *      (5 + 16 * layers), normalize = 1 L2-normalises the pooled vector (x / max(|x|, 1e-12)).
+ *      transformers.BertModel). The model is a BERT encoder (the cross-encoder's kernels; the shapes that load are
+ *      rag_ce_load_host's, 64-wide heads included) behind sentence-transformers' Pooling + Normalize head: tensors as
+ *      rag_ce_load_host WITHOUT the four pooler / classifier tensors (5 + 16 * layers). flags is a bit word:
+ *        RAG_EMBED_NORMALIZE (1)  L2-normalise the pooled vector (x / max(|x|, 1e-12));
+ *        RAG_EMBED_POOL_CLS  (2)  pool by the last hidden state of row 0 ([CLS]; sentence-transformers' pooling_mode_cls_token:
+ *                                 no pooler dense, no tanh) instead of the mean over the real tokens;
+ *      any other bit is RAG_ERR_ARG. 0 and 1 are what the former `normalize` argument meant.
  *      rag_embed_*: input_ids / token_type_ids [n_texts][L] int32 (padded), lens[n_texts]; out[n_texts][hidden] float32.
  *      lens clamping, the length classes and what a vector is a function of: as for rag_ce_score_* above. The mean runs over the
  *      clamped length. A 384-wide encoder takes the MX forward (hi16 + lo8 operands) by shape, without the classifier's load-time
  *      probe: on the stress weights of tests/ce_stress.py it stays within 2.4e-4 per component of the unit vector (bar 1e-3) and
  *      1 - cos <= 6.5e-7 (bar 1e-6, reached only with sharp attention heads; 1.2e-8 or less otherwise) of the float64 oracle;
  *      option ce_mx = -1 selects the split-fp16 forward (2.5e-5, 9.1e-9). DESIGN.md section 4.5. */
-int rag_embed_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors_host, int n_tensors, int normalize);
+#define RAG_EMBED_NORMALIZE 1
+#define RAG_EMBED_POOL_CLS 2
+int rag_embed_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors_host, int n_tensors, int flags);
 int rag_embed_host(rag_handle_t h, const int32_t* input_ids_host, const int32_t* token_type_ids_host, const int32_t* lens_host,
                    int n_texts, int seq_len, float* out_host);
 int rag_embed_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev,

@@ -51,6 +51,10 @@ class CeConfig(C.Structure):
                 ("ln_eps", C.c_double)]
 
 
+# flag bits of rag_embed_load_host (include/rag_hip.h)
+EMBED_NORMALIZE = 1
+EMBED_POOL_CLS = 2
+
 _P = C.c_void_p
 _SIGS = {
     "rag_version": ([], C.c_int),
@@ -741,13 +745,17 @@ class RagEngine:
         self._check(self.lib.rag_ce_load_host(self.h, C.byref(c), ptrs, len(arrs)), "rag_ce_load_host")
 
     # ---- local embedding model (BERT encoder + mean pooling) ---------------------------------------
-    def embed_load(self, cfg, tensors, normalize=True):
-        """tensors: rag_ce_load_host's order WITHOUT the pooler / classifier (cross_encoder.flatten_state_dict(..., head=False))."""
+    def embed_load(self, cfg, tensors, normalize=True, pooling="mean"):
+        """tensors: rag_ce_load_host's order WITHOUT the pooler / classifier (cross_encoder.flatten_state_dict(..., head=False)).
+        pooling: "mean" over the real tokens, or "cls" (the last hidden state of row 0; no pooler dense / tanh)."""
+        if pooling not in ("mean", "cls"):
+            raise ValueError(f"embed_load: unsupported pooling mode {pooling!r} (mean or cls)")
+        flags = (EMBED_NORMALIZE if normalize else 0) | (EMBED_POOL_CLS if pooling == "cls" else 0)
         c = CeConfig(cfg["vocab_size"], cfg["hidden"], cfg["layers"], cfg["heads"], cfg["ffn"], cfg["max_pos"],
                      cfg.get("type_vocab", 2), 0, float(cfg.get("eps", 1e-12)))
         arrs = [_np(t, np.float32) for t in tensors]
         ptrs = (_P * len(arrs))(*[a.ctypes.data for a in arrs])
-        self._check(self.lib.rag_embed_load_host(self.h, C.byref(c), ptrs, len(arrs), 1 if normalize else 0), "rag_embed_load_host")
+        self._check(self.lib.rag_embed_load_host(self.h, C.byref(c), ptrs, len(arrs), flags), "rag_embed_load_host")
         self.embed_hidden = int(cfg["hidden"])
 
     def embed(self, input_ids, token_type_ids, lens):

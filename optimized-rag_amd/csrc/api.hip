@@ -812,11 +812,11 @@ int rag_ce_score_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, cons
     return ce_score(h, ids, tt, lens, P, L, out, (hipStream_t)stream, false);
 }
 
-int rag_embed_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize) {
+int rag_embed_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors, int n, int flags) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return embed_load_host(h, cfg, tensors, n, normalize);
+    return embed_load_host(h, cfg, tensors, n, flags);
 }
 
 int rag_embed_host(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int n_texts, int L, float* out) {

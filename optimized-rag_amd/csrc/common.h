@@ -197,6 +197,7 @@ struct rag_ctx : rag_device_mem {
     int attr_dense_emit_lds[2][2][2] = {}, attr_dense_persist_lds[2] = {}, attr_dense_select_lds = 0, attr_bm25_lds = 0;
     int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0;
     int attr_ce_attn_lds[2][3] = {};
+    int attr_ce_attn64_lds = 0;              // the LDS-staged instance of ce_attention64_kernel (64-wide heads)
     rag_ce_model* ce = nullptr;
     rag_ce_model* emb = nullptr;             // sentence-embedding encoder (rag_embed_load_host): the K7 kernels behind a mean-pooling head
 };
@@ -420,7 +421,7 @@ int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tenso
 int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
              bool host_ptrs);
 void ce_free(rag_ctx* h);
-int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int normalize);
+int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int flags);
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
               bool host_ptrs);
 int embed_dim(const rag_ctx* h);

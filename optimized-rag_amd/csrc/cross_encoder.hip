@@ -23,8 +23,12 @@
 //                      FRAGMENT order per (pair, head)), bias + GELU -> split fp16, bias + residual -> fp32.
 //   ce_attention<QB>   one workgroup per (head, pair); K/V fragments by LDS-DMA, S computed transposed so that P stays in
 //                      registers as the next MFMA's operand, online softmax over 32-key blocks, keys past len skipped.
+//   ce_attention64     the same scheme for models with 64-wide heads (BERT-base / BERT-large shapes; EPI_QKV64 writes their K / V
+//                      tiles): S chains two MFMAs over the head's dim halves, P.V fills four 16-dim accumulators; LDS-staged
+//                      up to length class 256, fragments read from global memory at 384 and 512
 //   ce_layernorm       one wave per token (384 = 6/lane), fp32 statistics, eps from config
 //   ce_pool_classify   tanh(Wp.x_cls + bp) -> wc.pooled + bc, fp32
+//   ce_meanpool        embedding head: mean over the real tokens, or the [CLS] row; optional L2 normalisation
 // One layer, in launch order: QKV GEMM, attention, out-projection GEMM (bias + residual -> fp32) + LayerNorm, FFN-up GEMM
 // (bias + GELU) + FFN-down GEMM (bias + residual -> fp32) + LayerNorm. These split-fp16 kernels run every model whose shape
 // the MX forward (ce_mx.h: hi16 + lo8 operands, hidden 384) does not take, classifiers whose load-time probe saw MX miss
@@ -70,8 +74,10 @@ struct ce_mx_ws : ce_ws_base {
 
 struct rag_ce_model {
     rag_ce_config cfg;
-    bool embed = false;          // true: sentence-embedding encoder (mean pooling over the tokens, no pooler / classifier head)
+    bool embed = false;          // true: sentence-embedding encoder (mean or [CLS] pooling over the tokens, no pooler / classifier head)
     int normalize = 1;           // embed: L2-normalise the pooled vectors
+    int pool_cls = 0;            // embed: pool by the [CLS] row (the last hidden state of row 0) instead of the mean
+    int d_head = 32;             // 32, or 64: the split-fp16 forward with the EPI_QKV64 epilogue and ce_attention64_kernel
     int out_width = 1;           // floats per pair the forward produces: 1 logit, or `hidden` for an embedding model
     // embeddings fp32
     dev_buf<float> word, pos, type, emb_ln_g, emb_ln_b;
@@ -103,7 +109,8 @@ struct rag_ce_model {
 #define CE_GEMM_LDS (3 * CE_STAGE_BYTES)                  // three stages = 144 KiB
 #define CE_EPI_PLANE16 (16 * 144)                         // one fp16 plane of a 16-token x 64-feature epilogue pass, rows padded to 144 B
 
-enum { EPI_QKV = 0, EPI_GELU = 1, EPI_RESID = 2 };
+// EPI_QKV64: the QKV epilogue of a model with 64-wide heads (K and V fragment tiles of ce_attention64_kernel)
+enum { EPI_QKV = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_QKV64 = 3 };
 
 __device__ __forceinline__ void store_split4(half_t* __restrict__ p, size_t plane, float v0, float v1, float v2, float v3) {
     const half4 hi = {(half_t)v0, (half_t)v1, (half_t)v2, (half_t)v3};
@@ -324,6 +331,20 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
                         half_t* o = out16 + (size_t)(mb + j * 16 + row) * ldo + (nb >> 5) * 64 + cc * 8;
                         __builtin_nontemporal_store(v, reinterpret_cast<half8*>(o));
                     }
+                } else if (EPI == EPI_QKV64) {
+                    // 64-wide heads: the wave's 64 features are ONE head, two 32-dim halves. K features ->
+                    // kf16[head][16-row tile][dim half][lane = fq*16 + key%16][8 dims half*32 + fq*8..]: the two A fragments the S chain
+                    // of ce_attention64_kernel reads, 2 KiB per (head, tile) and plane. One store = one whole 1 KiB fragment tile.
+                    const int head = (nb - hidden) >> 6;
+                    const int m = mb + j * 16;
+#pragma unroll
+                    for (int dh = 0; dh < 2; ++dh) {
+                        const half8 hi = *reinterpret_cast<const half8*>(wl + fr * 144 + (dh * 4 + fq) * 16);
+                        const half8 lo = *reinterpret_cast<const half8*>(wl + CE_EPI_PLANE16 + fr * 144 + (dh * 4 + fq) * 16);
+                        half_t* o = kf16 + ((((size_t)head * (m_pad >> 4) + (m >> 4)) * 2 + dh) * 64 + lane) * 8;
+                        __builtin_nontemporal_store(hi, reinterpret_cast<half8*>(o));
+                        __builtin_nontemporal_store(lo, reinterpret_cast<half8*>(o + kv_plane));
+                    }
                 } else {
                     // K features -> kf16[head][16-row tile of the PACKED row space][lane = fq*16 + key%16][8 dims fq*8..]: the MFMA
                     // A-fragment order the attention kernel DMAs straight into LDS; a pair's keys are consecutive tiles of one head
@@ -347,7 +368,9 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
             // tile]. The attention kernel reads a lane's 8 B of two adjacent tiles as one MFMA A fragment: 8 key slots in the
             // order in which the S^T accumulators of the two key tiles sit in a lane's registers, so P never leaves registers.
             // Tiles (not 32-row blocks) are the unit so that a pair may start at any multiple of 16 rows.
-            const int head0 = (nb - 2 * hidden) >> 5;
+            // 64-wide heads (EPI_QKV64): the 64 features are one head's four 16-dim quarters, a tile is [d quarter][lane][4 key slots] =
+            // 2 KiB per (head, tile) and plane; the store pattern is the same with the tile stride doubled.
+            const int head0 = EPI == EPI_QKV64 ? (nb - 2 * hidden) >> 6 : (nb - 2 * hidden) >> 5;
 #pragma unroll
             for (int kl = 0; kl < 2; ++kl) {
                 const int m = mb + kl * 32;
@@ -370,9 +393,11 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
                         const int hl = it >> 1, dh = it & 1;            // head, d half
                         const char* rowp = wl + (hl * 32 + dh * 16 + fr) * 80 + fq * 8;
                         const half4 h0 = *reinterpret_cast<const half4*>(rowp), h1 = *reinterpret_cast<const half4*>(rowp + 32);
-                        half_t* o = vf16 + ((((size_t)(head0 + hl) * (m_pad >> 4) + (m >> 4)) * 2 + dh) * 64 + lane) * 4 + (pl ? kv_plane : 0);
+                        half_t* o = EPI == EPI_QKV64
+                                        ? vf16 + ((((size_t)head0 * (m_pad >> 4) + (m >> 4)) * 4 + it) * 64 + lane) * 4 + (pl ? kv_plane : 0)
+                                        : vf16 + ((((size_t)(head0 + hl) * (m_pad >> 4) + (m >> 4)) * 2 + dh) * 64 + lane) * 4 + (pl ? kv_plane : 0);
                         __builtin_nontemporal_store(h0, reinterpret_cast<half4*>(o));
-                        __builtin_nontemporal_store(h1, reinterpret_cast<half4*>(o + 512));   // the next 16-row tile
+                        __builtin_nontemporal_store(h1, reinterpret_cast<half4*>(o + (EPI == EPI_QKV64 ? 1024 : 512)));   // the next 16-row tile
                     }
                     __builtin_amdgcn_wave_barrier();
                 }
@@ -712,6 +737,211 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
     }
 }
 
+// ---- attention for d_head = 64 (split-fp16 forward only). The scheme of ce_attention_kernel: one workgroup per (head, pair), two
+// 16-query blocks per wave, S transposed so that P stays in registers, online softmax over 32-key blocks in the exp2 domain, hi + lo
+// operands with three products per MFMA position, the edge block masked. What differs: S chains two 16x16x32 MFMAs over the head's two
+// 32-dim halves per product, P.V fills four 16-dim accumulators per query block, the scale is 64^-0.5 * log2(e), and a 16-row tile is
+// 2 KiB per plane (K: [dim half][lane][8 dims], V: [d quarter][lane][4 key slots]; written by the EPI_QKV64 epilogue).
+// The four planes cost 512 B per key: the length classes up to 256 are staged whole in LDS (128 KiB), classes 384 and 512 do not
+// fit in 160 KiB and read the same fragment bytes straight from global memory (DIRECT; every tile is read by all waves of the
+// (head, pair), out of L2). DIRECT waves share nothing, so a (head, pair) is split over blockIdx.z into workgroups of 8 waves (256
+// queries each): 16 waves in one workgroup would cap the kernel at 128 VGPRs, which it does not fit without scratch. Both consume the keys in the same 32-key-block order with the same instructions, so a sequence's result does
+// not depend on its length class.
+template <bool DIRECT>
+__global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __restrict__ q16, const half_t* __restrict__ kf16,
+                                                                              const half_t* __restrict__ vf16, size_t kv_plane,
+                                                                              const int32_t* __restrict__ lens, const int32_t* __restrict__ pair_off,
+                                                                              int L, int hidden, int m_pad, half_t* __restrict__ ctx16) {
+    constexpr int QB = 2;                                             // 16-query blocks per wave, in every length class
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+    const int head = blockIdx.x, pair = blockIdx.y;
+    const int len = max(1, min(lens[pair], L));
+    const int fr = lane & 15, fq = lane >> 4;
+    const int po = pair_off[pair], Lp = pair_off[pair + 1] - po;     // this pair's packed rows: len rounded up to 16
+    const int nt = Lp >> 4;                                           // the pair's 16-row tiles; an odd count leaves the second
+    const int nkb = (len + 31) >> 5;                                  // half of the last 32-key block outside the pair (masked)
+    const size_t plane_b = (size_t)L * 128;                           // bytes of one K (or V) plane of this (pair, head)
+    const size_t t0 = ((size_t)head * (m_pad >> 4) + (po >> 4)) * 1024;                     // first tile of this (head, pair), in halfs
+    // fragment reads below address tile c of a plane at byte c * 2048 + (lane's offset): the same bytes in LDS and in global memory
+    const char* const k_hi = DIRECT ? reinterpret_cast<const char*>(kf16 + t0) : smem;
+    const char* const k_lo = DIRECT ? reinterpret_cast<const char*>(kf16 + t0 + kv_plane) : smem + plane_b;
+    const char* const v_hi = DIRECT ? reinterpret_cast<const char*>(vf16 + t0) : smem + 2 * plane_b;
+    const char* const v_lo = DIRECT ? reinterpret_cast<const char*>(vf16 + t0 + kv_plane) : smem + 3 * plane_b;
+    if (!DIRECT) {
+        char* const sk_hi = smem;
+        char* const sk_lo = smem + plane_b;
+        char* const sv_hi = smem + 2 * plane_b;
+        char* const sv_lo = smem + 3 * plane_b;
+        const size_t g0 = t0 + (size_t)lane * 8;                      // a tile is two 1-KiB pieces per plane
+        for (int c = wv; c < nt; c += nwaves)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const size_t g = g0 + (size_t)c * 1024 + j * 512;
+                const int s = c * 2048 + j * 1024;
+                ce_dma_at(kf16 + g, sk_hi + s);
+                ce_dma_at(kf16 + g + kv_plane, sk_lo + s);
+                ce_dma_at(vf16 + g, sv_hi + s);
+                ce_dma_at(vf16 + g + kv_plane, sv_lo + s);
+            }
+        // an odd tile count leaves the second half of the last 32-key block outside the pair: P is 0 there (masked keys), V must be
+        // finite (0 x NaN = NaN). The never-staged tile is zeroed once; DIRECT selects zeros for it at the fragment read, because
+        // that memory belongs to the next pair or is stale slack.
+        if ((nt & 1) && wv == 0) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                *reinterpret_cast<u32x4*>(sv_hi + nt * 2048 + j * 1024 + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(sv_lo + nt * 2048 + j * 1024 + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
+            }
+        }
+    }
+    const size_t row0 = (size_t)po;
+    const int qb0 = ((DIRECT ? (int)blockIdx.z * nwaves : 0) + wv) * QB;
+    const bool has_rows = qb0 * 16 < Lp;                              // waves past the pair's rows only helped with the DMA
+    // B operand = Q rows (query fr of block b, dims half*32 + 8*fq..+8). Split-row layout: a head's 64 dims are two K groups of
+    // [hi 32 | lo 32] halfs
+    half8 qh[QB][2], ql[QB][2];
+#pragma unroll
+    for (int b = 0; b < QB; ++b) {
+        const int qb = (qb0 + b) * 16 < Lp ? qb0 + b : qb0;           // a block past the pair's rows is computed but not stored
+        const half_t* qp = q16 + (row0 + qb * 16 + fr) * (2 * hidden) + head * 128 + fq * 8;
+#pragma unroll
+        for (int dh = 0; dh < 2; ++dh) {
+            qh[b][dh] = *reinterpret_cast<const half8*>(qp + dh * 64);
+            ql[b][dh] = *reinterpret_cast<const half8*>(qp + dh * 64 + 32);
+        }
+    }
+    f32x4 cx[QB][4];
+    float mrun[QB], lsum[QB];
+#pragma unroll
+    for (int b = 0; b < QB; ++b) {
+#pragma unroll
+        for (int dq = 0; dq < 4; ++dq) cx[b][dq] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mrun[b] = -INFINITY;
+        lsum[b] = 0.f;
+    }
+    const float cs = (float)(0.125 * 1.4426950408889634);             // 64^-0.5 * log2(e)
+    if (!DIRECT) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    if (!has_rows) return;
+    float ce_inf;                                                     // see ce_attention_kernel: max by v_med3_f32(a, b, +inf)
+    asm volatile("s_mov_b32 %0, 0x7f800000" : "=s"(ce_inf));
+#define CE_MAX2(a_, b_) __builtin_amdgcn_fmed3f(a_, b_, ce_inf)
+    // one 32-key block = tiles 2kb and 2kb+1; EDGE (the pair's last block only: the loop is peeled) masks the keys past the length
+    auto key_block = [&](const int kb, auto edge_c) {
+        constexpr bool EDGE = decltype(edge_c)::value;
+        const int fo = kb * 4096 + lane * 16;
+        half8 kh[2][2], kl[2][2];                                     // [tile][dim half]
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) {
+                kh[t][dh] = *reinterpret_cast<const half8*>(k_hi + fo + t * 2048 + dh * 1024);
+                kl[t][dh] = *reinterpret_cast<const half8*>(k_lo + fo + t * 2048 + dh * 1024);
+            }
+        // V fragment of d quarter dq = the lane's 4 key slots of tile 2kb | of tile 2kb+1. Tile 2kb+1 of an odd-count pair lies outside
+        // the pair under P = 0: zeros in LDS, and DIRECT selects zeros.
+        const int vo = kb * 4096 + lane * 8;
+        half8 vh[4], vl[4];
+#pragma unroll
+        for (int dq = 0; dq < 4; ++dq) {
+            const half4 ah = *reinterpret_cast<const half4*>(v_hi + vo + dq * 512), al = *reinterpret_cast<const half4*>(v_lo + vo + dq * 512);
+            half4 bh = {}, bl = {};
+            if (!(DIRECT && EDGE && (nt & 1))) {
+                bh = *reinterpret_cast<const half4*>(v_hi + vo + 2048 + dq * 512);
+                bl = *reinterpret_cast<const half4*>(v_lo + vo + 2048 + dq * 512);
+            }
+            vh[dq] = __builtin_shufflevector(ah, bh, 0, 1, 2, 3, 4, 5, 6, 7);
+            vl[dq] = __builtin_shufflevector(al, bl, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+#pragma unroll
+        for (int b = 0; b < QB; ++b) {
+            f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+            // both correction products over both dim halves first, the hi * hi product last
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) {
+                z0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[0][dh], qh[b][dh], z0, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[1][dh], qh[b][dh], z1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) {
+                z0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[0][dh], ql[b][dh], z0, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[1][dh], ql[b][dh], z1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) {
+                z0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[0][dh], qh[b][dh], z0, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[1][dh], qh[b][dh], z1, 0, 0, 0);
+            }
+            // lane (fr, fq): z0[r] = S[query fr][key kb*32 + fq*4 + r], z1[r] = same + 16
+            if (EDGE) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (kb * 32 + fq * 4 + r >= len) z0[r] = -INFINITY;
+                    if (kb * 32 + 16 + fq * 4 + r >= len) z1[r] = -INFINITY;
+                }
+            }
+            float mx = CE_MAX2(CE_MAX2(CE_MAX2(z0[0], z0[1]), CE_MAX2(z0[2], z0[3])), CE_MAX2(CE_MAX2(z1[0], z1[1]), CE_MAX2(z1[2], z1[3])));
+            {                                                         // lane ^ 16, lane ^ 32: issued by hand, see ce_attention_kernel
+                float cp = mx;
+                asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(mx), "+v"(cp));
+                mx = CE_MAX2(mx, cp);
+                cp = mx;
+                asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(mx), "+v"(cp));
+                mx = CE_MAX2(mx, cp);
+            }
+            const float mnew = CE_MAX2(mrun[b], mx);                // finite: key 0 is always real
+            const float alpha = __builtin_amdgcn_exp2f((mrun[b] - mnew) * cs);
+            mrun[b] = mnew;
+            const float off = -mnew * cs;
+            float e[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                e[r] = __builtin_amdgcn_exp2f(fmaf(z0[r], cs, off));
+                e[4 + r] = __builtin_amdgcn_exp2f(fmaf(z1[r], cs, off));
+            }
+            lsum[b] = lsum[b] * alpha + (((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7])));
+#pragma unroll
+            for (int dq = 0; dq < 4; ++dq)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) cx[b][dq][r] *= alpha;
+            float eh[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) eh[r] = ce_trunc10(e[r]);
+            const u32x4 ph_u = {ce_pk(eh[0], eh[1]), ce_pk(eh[2], eh[3]), ce_pk(eh[4], eh[5]), ce_pk(eh[6], eh[7])};
+            const u32x4 pl_u = {ce_pk(e[0] - eh[0], e[1] - eh[1]), ce_pk(e[2] - eh[2], e[3] - eh[3]),
+                                ce_pk(e[4] - eh[4], e[5] - eh[5]), ce_pk(e[6] - eh[6], e[7] - eh[7])};
+            const half8 ph = __builtin_bit_cast(half8, ph_u), pl = __builtin_bit_cast(half8, pl_u);
+            // ctx^T[d][q] += V^T[d][key] P[q][key]: A = V fragment (row d of quarter dq), B = P (col q = fr)
+#pragma unroll
+            for (int dq = 0; dq < 4; ++dq) cx[b][dq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl[dq], ph, cx[b][dq], 0, 0, 0);
+#pragma unroll
+            for (int dq = 0; dq < 4; ++dq) cx[b][dq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[dq], pl, cx[b][dq], 0, 0, 0);
+#pragma unroll
+            for (int dq = 0; dq < 4; ++dq) cx[b][dq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[dq], ph, cx[b][dq], 0, 0, 0);
+        }
+    };
+    for (int kb = 0; kb + 1 < nkb; ++kb) key_block(kb, std::false_type{});
+    key_block(nkb - 1, std::true_type{});
+#undef CE_MAX2
+    // lane (fr, fq): cx[dq][r] = ctx[query fr][d = dq*16 + fq*4 + r]; the row sum is spread over the 4 fq lanes
+#pragma unroll
+    for (int b = 0; b < QB; ++b) {
+        float l = lsum[b];
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        const float inv = 1.0f / l;
+        if ((qb0 + b) * 16 >= Lp) break;
+        half_t* o = ctx16 + (row0 + (qb0 + b) * 16 + fr) * (2 * hidden) + head * 128 + fq * 4;
+#pragma unroll
+        for (int dq = 0; dq < 4; ++dq)                                // d quarter dq sits in K group dq >> 1 of the head, at dims (dq & 1) * 16..
+            store_split4(o + (dq >> 1) * 64 + (dq & 1) * 16, 32, cx[b][dq][0] * inv, cx[b][dq][1] * inv, cx[b][dq][2] * inv, cx[b][dq][3] * inv);
+    }
+}
+
 template <bool MX>
 __global__ __launch_bounds__(256) void ce_pool_classify_kernel(const half_t* __restrict__ x16, const float* __restrict__ wp,
                                                                 const float* __restrict__ bp, const float* __restrict__ wc,
@@ -783,15 +1013,16 @@ __global__ __launch_bounds__(256) void mx_pool_classify_kernel(const char* __res
     if (tid < POOL_PB && p0 + tid < P) logits[p0 + tid] = part[tid][0] + part[tid][1] + part[tid][2] + part[tid][3] + bc[0];
 }
 
-// Sentence embedding head (sentence-transformers' Pooling(mean) + Normalize): mean of the last hidden state over the pair's
-// real tokens, optionally L2-normalised. One workgroup per sequence; float32 sums over the split-fp16 stream (hi + lo).
+// Sentence embedding head (sentence-transformers' Pooling + Normalize): mean of the last hidden state over the pair's real tokens,
+// or (pool_cls: pooling_mode_cls_token) the last hidden state of row 0 alone, with no pooler dense / tanh; optionally L2-normalised.
+// One workgroup per sequence; float32 sums over the split-fp16 stream (hi + lo).
 template <bool MX>
 __global__ __launch_bounds__(256) void ce_meanpool_kernel(const half_t* __restrict__ x16, const int32_t* __restrict__ pair_off,
-                                                           const int32_t* __restrict__ lens, int L, int hidden, int normalize,
+                                                           const int32_t* __restrict__ lens, int L, int hidden, int normalize, int pool_cls,
                                                            float* __restrict__ out) {
     __shared__ float part[4];
     const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int len = max(1, min(lens[pair], L));
+    const int len = pool_cls ? 1 : max(1, min(lens[pair], L));       // [CLS] pooling: the "mean" of the first row (x / 1.0f is exact)
     const half_t* x = x16 + (size_t)pair_off[pair] * 2 * hidden;
     float sq = 0.f;
     float v[4] = {0.f, 0.f, 0.f, 0.f};                               // hidden <= 1024: up to 4 features per thread
@@ -899,16 +1130,24 @@ static int up_weight(rag_ctx* h, std::vector<const float*> srcs, size_t rows_eac
 //  then pooler.w pooler.b classifier.w classifier.b
 //  (an embedding model - BertModel behind a mean-pooling head - ends after the layers: no pooler / classifier tensors)
 static int ce_probe_mx(rag_ctx* h, rag_ce_model* m);
-static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n, bool embed, int normalize, rag_ce_model** slot) {
+// Head dim: 32 at every hidden size, 64 at every hidden size the split-fp16 forward alone serves (128, 256, 512, 640, 768, 896, 1024).
+// Hidden 384 belongs to the MX forward, whose operand images and attention instances are laid out per 32-wide head: it keeps 32 only.
+static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n, bool embed, int flags, rag_ce_model** slot) {
     ARG_CHECK(h, cfg && T, "ce_load: null");
     ARG_CHECK(h, cfg->hidden % 128 == 0 && cfg->hidden <= 1024 && cfg->ffn % 128 == 0, "ce_load: hidden/ffn must be multiples of 128");
-    ARG_CHECK(h, cfg->heads > 0 && cfg->hidden / cfg->heads == 32, "ce_load: head dim must be 32");
+    ARG_CHECK(h, cfg->heads > 0 && cfg->hidden % cfg->heads == 0, "ce_load: hidden must be a multiple of heads");
+    const int d_head = cfg->hidden / cfg->heads;
+    ARG_CHECK(h, d_head == 32 || d_head == 64, "ce_load: head dim must be 32 or 64");
+    ARG_CHECK(h, d_head == 32 || cfg->hidden != MX_TM, "ce_load: hidden 384 (the MX forward's width) takes head dim 32 only");
+    ARG_CHECK(h, (flags & ~(RAG_EMBED_NORMALIZE | RAG_EMBED_POOL_CLS)) == 0, "embed_load: unknown flag bits");
     ARG_CHECK(h, n == 5 + 16 * cfg->layers + (embed ? 0 : 4), "ce_load: wrong tensor count");
     delete *slot;
     rag_ce_model* m = *slot = new rag_ce_model();
     m->cfg = *cfg;
     m->embed = embed;
-    m->normalize = normalize;
+    m->normalize = (flags & RAG_EMBED_NORMALIZE) != 0;
+    m->pool_cls = (flags & RAG_EMBED_POOL_CLS) != 0;
+    m->d_head = d_head;
     m->out_width = embed ? cfg->hidden : 1;
     const size_t H = cfg->hidden, F = cfg->ffn;
     int rc;
@@ -960,8 +1199,8 @@ int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, in
     return ce_load_model(h, cfg, T, n, false, 0, &h->ce);
 }
 
-int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n, int normalize) {
-    return ce_load_model(h, cfg, T, n, true, normalize, &h->emb);
+int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T, int n, int flags) {
+    return ce_load_model(h, cfg, T, n, true, flags, &h->emb);
 }
 
 static const int kAttnL[] = {32, 64, 96, 128, 192, 256, 384, 512};
@@ -1021,6 +1260,25 @@ static int launch_attention(rag_ctx* h, const rag_ce_model* m, const ce_ws_base&
     return RAG_OK;
 }
 
+// Attention of one layer of a model with 64-wide heads (split-fp16 forward): two 16-query blocks per wave in every length class. Up
+// to class 256 the (head, pair)'s four K / V planes are staged in LDS (512 B per key, 128 KiB at 256); classes 384 and 512 would
+// need 192 and 256 KiB, so they read the fragments from global memory, take no LDS, and run as two workgroups of 8 waves per
+// (head, pair).
+static int launch_attention64(rag_ctx* h, const rag_ce_model* m, const ce_split_ws& w, const ce_chunk& c, hipStream_t st) {
+    const int H = m->cfg.hidden, L = c.L;
+    const size_t kv_plane = kv_plane_halfs(w.tokens, H);
+    const dim3 grid(m->cfg.heads, c.P), block(64 * (L / 32));
+    if (L <= 256) {
+        const int lds = L * 512;                                       // K hi | K lo | V hi | V lo fragment planes
+        if (int rc = raise_lds(h, h->attr_ce_attn64_lds, lds, ce_attention64_kernel<false>)) return rc;
+        launch(ce_attention64_kernel<false>, grid, block, lds, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
+               (int)w.tokens, w.ctx16);
+    } else
+        launch(ce_attention64_kernel<true>, dim3(m->cfg.heads, c.P, (L + 255) / 256), dim3(512), 0, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
+               (int)w.tokens, w.ctx16);
+    return RAG_OK;
+}
+
 // ---- the split-fp16 forward ------------------------------------------------------------------------------------------
 static int ce_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
     ce_split_ws& w = m->split;
@@ -1077,7 +1335,8 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     const int H = m->cfg.hidden, F = m->cfg.ffn, P = c.P, L = c.L;
     const int64_t M = (int64_t)P * L;
     int rc;
-    if ((rc = raise_lds(h, h->attr_ce_gemm_lds, CE_GEMM_LDS, ce_gemm_kernel<EPI_QKV>, ce_gemm_kernel<EPI_GELU>, ce_gemm_kernel<EPI_RESID>)))
+    if ((rc = raise_lds(h, h->attr_ce_gemm_lds, CE_GEMM_LDS, ce_gemm_kernel<EPI_QKV>, ce_gemm_kernel<EPI_GELU>, ce_gemm_kernel<EPI_RESID>,
+                        ce_gemm_kernel<EPI_QKV64>)))
         return rc;
     chunk_prologue(w, c, st);
     rc = per_lane_dispatch(h, H, [&](auto per) {
@@ -1086,9 +1345,14 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     });
     if (rc) return rc;
     for (const auto& ly : m->layers) {
-        ce_gemm<EPI_QKV>(h, m, st, ly.wqkv, w.x16, 3 * H, H, ly.bqkv, nullptr, nullptr, w.q16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, H));
-        rc = L == 32 ? launch_attention<1, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st)
-                     : launch_attention<2, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st);
+        if (m->d_head == 64) {
+            ce_gemm<EPI_QKV64>(h, m, st, ly.wqkv, w.x16, 3 * H, H, ly.bqkv, nullptr, nullptr, w.q16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, H));
+            rc = launch_attention64(h, m, w, c, st);
+        } else {
+            ce_gemm<EPI_QKV>(h, m, st, ly.wqkv, w.x16, 3 * H, H, ly.bqkv, nullptr, nullptr, w.q16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, H));
+            rc = L == 32 ? launch_attention<1, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st)
+                         : launch_attention<2, false>(h, m, w, w.q16, w.kf16, w.vf16, w.ctx16, c, st);
+        }
         if (rc) return rc;
         // out-projection + bias + residual -> y32, then LayerNorm -> x16
         ce_gemm<EPI_RESID>(h, m, st, ly.wo, w.ctx16, H, H, ly.bo, w.x16, w.y32, nullptr);
@@ -1099,7 +1363,7 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
         if ((rc = ce_layernorm(h, m, ly.ln2_g, ly.ln2_b, M, st))) return rc;
     }
     if (m->embed)
-        launch(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, io.pair_off, io.clen, L, H, m->normalize, c.out);
+        launch(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, io.pair_off, io.clen, L, H, m->normalize, m->pool_cls, c.out);
     else
         launch(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, m->wp, m->bp, m->wc, m->bc, io.pair_off, H, c.out);
     HIP_TRY(h, hipGetLastError());
@@ -1199,7 +1463,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     const char* const cls = cls_tail ? w.xc8 : w.x8;
     if (m->embed)
         launch(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), io.pair_off, io.clen, L, H,
-               m->normalize, c.out);
+               m->normalize, m->pool_cls, c.out);
     else if (cls_tail && P >= 512)
         // the batched pooler pays from ~512 pairs on; a single query's 100 pairs fill more CUs with one workgroup per pair
         launch(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, cls, m->wpT, m->bp, m->wc, m->bc, P, H, c.out);

@@ -1,11 +1,12 @@
 """Local embedding service on the GPU: the class surface of the reference's `EmbeddingService`
 (/root/reference/memory/embeddings.py: generate_embedding :64-98, generate_embeddings_batch :154-224, get_embedding_dimension
 :312-332, cache statistics :248-310) with the OpenAI HTTP calls (:100-115, :226-246) replaced by a BERT sentence encoder run by
-the HIP engine (rag_embed_load_host / rag_embed_host: the cross-encoder's kernels behind a mean-pooling + L2-normalise head,
-i.e. a sentence-transformers `Transformer -> Pooling(mean) -> Normalize` checkpoint such as all-MiniLM-L6-v2).
+the HIP engine (rag_embed_load_host / rag_embed_host: the cross-encoder's kernels behind a mean- or [CLS]-pooling + L2-normalise
+head, i.e. a sentence-transformers `Transformer -> Pooling(mean | cls) -> Normalize` checkpoint such as all-MiniLM-L6-v2 or a
+BERT-base-shaped encoder).
 
-NOT a parity replacement: a local encoder returns different vectors (and a different dimension: 384 for the MiniLM shape) than
-text-embedding-3-small. An index has to be built and queried with the same service; what the tests pin is this forward against
+NOT a parity replacement: a local encoder returns different vectors (and a different dimension: the encoder's hidden size, 384
+for the MiniLM shape, 768 for BERT-base, 1024 for BERT-large) than text-embedding-3-small. An index has to be built and queried with the same service; what the tests pin is this forward against
 `transformers.BertModel`. There is no CPU fallback.
 """
 import json
@@ -19,9 +20,31 @@ from .cross_encoder import config_from_hf, flatten_state_dict
 from .engine import get_engine
 
 
+# pooling_mode_* keys of sentence-transformers' 1_Pooling/config.json -> what they are called in an error message
+_POOLING_KEYS = {"pooling_mode_cls_token": "cls", "pooling_mode_mean_tokens": "mean", "pooling_mode_max_tokens": "max",
+                 "pooling_mode_mean_sqrt_len_tokens": "mean_sqrt_len", "pooling_mode_weightedmean_tokens": "weightedmean",
+                 "pooling_mode_lasttoken": "lasttoken"}
+
+
+def pooling_mode_of_dir(path):
+    """"mean" or "cls" for a checkpoint directory: what its 1_Pooling/config.json switches on ("mean" when the file is missing).
+    Any other mode, or several at once (their vectors are concatenated), is a ValueError that names it: the engine has no such
+    head, and pooling such a checkpoint by the mean would silently return other vectors than the model was trained to give."""
+    cfg_path = os.path.join(path, "1_Pooling", "config.json")
+    if not os.path.exists(cfg_path):
+        return "mean"
+    with open(cfg_path) as f:
+        pc = json.load(f)
+    on = [name for key, name in _POOLING_KEYS.items() if pc.get(key)]
+    on += [k for k, v in pc.items() if k.startswith("pooling_mode_") and k not in _POOLING_KEYS and v is True]
+    if on == ["mean"] or on == ["cls"]:
+        return on[0]
+    raise ValueError(f"unsupported pooling mode {'+'.join(on) or 'none'} in {cfg_path}: only mean and cls are supported")
+
+
 class LocalEmbeddingService:
     def __init__(self, cfg, tensors, tokenizer, max_length=256, engine=None, batch_size=2048, normalize=True, model="local-bert-mean-pool",
-                 cache_size=1000):
+                 cache_size=1000, pooling="mean"):
         self.cfg = cfg
         self.model = model
         self.dimensions = int(cfg["hidden"])
@@ -29,7 +52,8 @@ class LocalEmbeddingService:
         self.tokenizer = tokenizer
         self.max_length = min(int(max_length), cfg["max_pos"], 512)
         self.batch_size = int(batch_size)
-        self.engine.embed_load(cfg, tensors, normalize=normalize)
+        self.pooling = pooling
+        self.engine.embed_load(cfg, tensors, normalize=normalize, pooling=pooling)
         # LRU cache of `cache_size` texts (the reference: cachetools.LRUCache(maxsize=EMBEDDING_CACHE_SIZE), default 1000 -
         # memory/embeddings.py:50, config.py:77): ingesting a large corpus must not keep every text in host memory
         self._cache, self._cache_lock = OrderedDict(), threading.Lock()
@@ -50,7 +74,9 @@ class LocalEmbeddingService:
 
     @classmethod
     def from_dir(cls, path, max_length=256, engine=None, **kw):
-        """A local sentence-transformers / HF BertModel directory: config.json, model.safetensors, vocab.txt."""
+        """A local sentence-transformers / HF BertModel directory: config.json, model.safetensors, vocab.txt. The pooling mode is
+        the one sentence-transformers recorded in 1_Pooling/config.json (mean or [CLS]; mean without the file); `normalize` stays
+        the caller's argument."""
         from safetensors.numpy import load_file
         from tokenizers import BertWordPieceTokenizer
         with open(os.path.join(path, "config.json")) as f:
@@ -64,7 +90,7 @@ class LocalEmbeddingService:
                 lower = bool(json.load(f).get("do_lower_case", True))
         tok = BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lower)
         return cls(cfg, flatten_state_dict(sd, cfg["layers"], head=False, prefix=prefix), tok, max_length=max_length, engine=engine,
-                   model=os.path.basename(os.path.normpath(path)), **kw)
+                   model=os.path.basename(os.path.normpath(path)), pooling=pooling_mode_of_dir(path), **kw)
 
     # ---- tokenisation: [CLS] text [SEP], truncated to max_length, padded to the longest of the batch -----------------
     def tokenize(self, texts):
