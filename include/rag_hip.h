@@ -27,12 +27,15 @@
  *     that work: it first waits for the device when a *_dev call was made on the handle since the last such wait (a
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
- *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_bm25_load_host,
+ *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_tokens_load_wide_host,
+ *     rag_tokens_reserve_wide, rag_bm25_load_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
  *     rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
- *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize and rag_set_option do not
+ *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize, rag_set_option and
+ *     rag_ce_set_pair_format do not
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
+ *     rag_tokens_info reads host state only and waits for nothing.
  *     *_dev calls of one handle on SEVERAL streams stay unordered among themselves: that is the caller's to order.
  *   - doc ids are int64 (SQL BIGSERIAL ids, database/migrations/001_initial_schema.sql); scores are
  *     float64 because the reference computes every score as a Python float.
@@ -443,7 +446,10 @@ typedef struct rag_ce_config {
  *   32 at every hidden size, or
  *   64 at hidden 128, 256, 512, 640, 768, 896 and 1024 - the BERT-base (768 / 12) and BERT-large (1024 / 16) shapes, the small
  *      BERTs (128 / 2, 256 / 4, 512 / 8). These run the split-fp16 forward with an attention instance of their own.
- * Hidden 384 takes head dim 32 only (12 heads): that width is the MX forward's, whose operands are laid out per 32-wide head. */
+ * Hidden 384 takes head dim 32 only (12 heads): that width is the MX forward's, whose operands are laid out per 32-wide head.
+ * type_vocab = 1 (RoBERTa / XLM-RoBERTa, whose position table the loader hands over without its first pad_token_id + 1 rows):
+ * the one row of the token-type table is uploaded twice, so with such a model every token takes row 0 whatever token_type_ids
+ * holds. */
 int rag_ce_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* const* tensors_host, int n_tensors);
 /* input_ids/token_type_ids: [P][L] int32 (padded), lens[P]; logits_out[P] raw logits (float32).
  * lens[p] outside [1, seq_len] is clamped to it (0 and negative values count as 1, anything above seq_len as seq_len), once, before
@@ -503,10 +509,36 @@ int rag_tokens_load_host(rag_handle_t h, const int32_t* tokens_host, const int32
  * whole: the rows appended before stay, the row count does not move, and the same row range may be appended again. */
 int rag_tokens_reserve(rag_handle_t h, int64_t n_rows_total, int L);
 int rag_tokens_append_dev(rag_handle_t h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, void* stream);
+/* A 24-bit token store, opt-in, for models over a large vocabulary (XLM-RoBERTa's SentencePiece vocabulary has 250,002 entries:
+ * the multilingual rerankers and embedders). id_bits is 16 or 24, anything else RAG_ERR_ARG; 16 is exactly rag_tokens_load_host /
+ * rag_tokens_reserve. 24 keeps the uint16 plane for the low half of an id and adds a uint8 plane [rows][L] for bits 16-23: 3 B per
+ * token where an int32 store would take 4, ids in [0, 16777215]. Every consumer follows the width the store was created with:
+ * rag_tokens_append_dev narrows on the device into both planes and rejects a block whole if an id is outside [0, 16777215] (the
+ * semantics above, the message names that range); rag_index_insert_host narrows the block on the host into both planes, grows
+ * both past the reservation and leaves both untouched when it fails; rag_index_compact / rag_index_compact_bm25 move the byte
+ * plane as one more row plane; rag_ce_build_pairs_dev and rag_retrieve_rerank[_tenants]_dev read lo | hi << 16. With ids below
+ * 65536 a 24-bit store gives bit-identical results to a 16-bit one. rag_tokens_load_host and rag_tokens_reserve stay 16 bits wide
+ * and, like these, replace whatever store the handle had. Stream ordering, locking and the wait for queued *_dev work are those of
+ * rag_tokens_load_host / rag_tokens_reserve.
+ * rag_tokens_info: rows resident, passage length and width (16 or 24) of the handle's store; any output may be NULL; without a
+ * store 0 / 0 / 0. Host state only. */
+int rag_tokens_load_wide_host(rag_handle_t h, const int32_t* tokens_host, const int32_t* lens_host, int64_t n_rows, int L,
+                              int id_bits);
+int rag_tokens_reserve_wide(rag_handle_t h, int64_t n_rows_total, int L, int id_bits);
+int rag_tokens_info(rag_handle_t h, int64_t* rows_out, int* L_out, int* id_bits_out);
 int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                             const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int n_queries, int pool, int k,
                             int rrf_k, int tenant, int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out_dev,
                             double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev, void* stream);
+/* The layout the pair builder writes, per handle (default RAG_PAIR_BERT; rag_ce_load_host does not touch it). It applies to
+ * rag_retrieve_rerank_dev, rag_retrieve_rerank_tenants_dev and rag_ce_build_pairs_dev; cls_id and sep_id stay call arguments
+ * (XLM-R: <s> = 0, </s> = 2). RAG_PAIR_ROBERTA is what a RoBERTa / XLM-RoBERTa tokenizer's pair template produces: two separators
+ * between the sides, every token type 0, the same 'longest_first' truncation over M = L_pair - 4 content tokens,
+ * lens = ql + dl + 4, padding id 0 / type 0. Host state read while a call enqueues, as rag_set_option: no wait, a call queued
+ * earlier keeps the old layout. An unknown format is RAG_ERR_ARG. */
+#define RAG_PAIR_BERT    0   /* [cls] q [sep] d [sep],        token types 0 | 1, L_pair - 3 content tokens */
+#define RAG_PAIR_ROBERTA 1   /* [cls] q [sep] [sep] d [sep],  token types all 0, L_pair - 4 content tokens */
+int rag_ce_set_pair_format(rag_handle_t h, int format);
 
 /* The pipeline's two small kernels on their own (row-sharded composition): pair assembly from GLOBAL
  * candidate doc ids against a replicated token store whose first row has id token_id_base; and sigmoid + stable top-k of

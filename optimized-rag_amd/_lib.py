@@ -54,6 +54,9 @@ class CeConfig(C.Structure):
 # flag bits of rag_embed_load_host (include/rag_hip.h)
 EMBED_NORMALIZE = 1
 EMBED_POOL_CLS = 2
+# pair layouts of rag_ce_set_pair_format
+PAIR_BERT = 0
+PAIR_ROBERTA = 1
 
 _P = C.c_void_p
 _SIGS = {
@@ -122,6 +125,10 @@ _SIGS = {
     "rag_tokens_load_host": ([_P, _P, _P, C.c_int64, C.c_int], C.c_int),
     "rag_tokens_reserve": ([_P, C.c_int64, C.c_int], C.c_int),
     "rag_tokens_append_dev": ([_P, _P, _P, C.c_int64, _P], C.c_int),
+    "rag_tokens_load_wide_host": ([_P, _P, _P, C.c_int64, C.c_int, C.c_int], C.c_int),
+    "rag_tokens_reserve_wide": ([_P, C.c_int64, C.c_int, C.c_int], C.c_int),
+    "rag_tokens_info": ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "rag_ce_set_pair_format": ([_P, C.c_int], C.c_int),
     "rag_hybrid_fuse_gathered_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "rag_retrieve_rerank_dev": ([_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -774,17 +781,36 @@ class RagEngine:
         self._check(self.lib.rag_embed_dev(self.h, C.c_void_p(input_ids.data_ptr()), C.c_void_p(token_type_ids.data_ptr()),
                                            C.c_void_p(lens.data_ptr()), n, L, C.c_void_p(out.data_ptr()), st), "rag_embed_dev")
 
-    def tokens_load(self, tokens, lens):
-        """Passage token store: tokens [N, L] int32 WordPiece ids without [CLS]/[SEP], lens [N]; row-aligned with the index."""
+    def tokens_load(self, tokens, lens, id_bits=16):
+        """Passage token store: tokens [N, L] int32 token ids without [CLS]/[SEP], lens [N]; row-aligned with the index.
+        id_bits=24 (rag_tokens_load_wide_host) holds ids up to 16777215 at 3 B per token: XLM-R's 250k-entry vocabulary."""
         tokens = _np(tokens, np.int32)
         lens = _np(lens, np.int32)
-        self._check(self.lib.rag_tokens_load_host(self.h, _ptr(tokens), _ptr(lens), tokens.shape[0], tokens.shape[1]),
-                    "rag_tokens_load_host")
+        if int(id_bits) == 16:
+            self._check(self.lib.rag_tokens_load_host(self.h, _ptr(tokens), _ptr(lens), tokens.shape[0], tokens.shape[1]),
+                        "rag_tokens_load_host")
+        else:
+            self._check(self.lib.rag_tokens_load_wide_host(self.h, _ptr(tokens), _ptr(lens), tokens.shape[0], tokens.shape[1], int(id_bits)),
+                        "rag_tokens_load_wide_host")
         self._tok_L = int(tokens.shape[1])
 
-    def tokens_reserve(self, n_rows_total, L):
-        self._check(self.lib.rag_tokens_reserve(self.h, int(n_rows_total), int(L)), "rag_tokens_reserve")
+    def tokens_reserve(self, n_rows_total, L, id_bits=16):
+        if int(id_bits) == 16:
+            self._check(self.lib.rag_tokens_reserve(self.h, int(n_rows_total), int(L)), "rag_tokens_reserve")
+        else:
+            self._check(self.lib.rag_tokens_reserve_wide(self.h, int(n_rows_total), int(L), int(id_bits)), "rag_tokens_reserve_wide")
         self._tok_L = int(L)
+
+    def tokens_info(self):
+        """{"rows", "L", "id_bits"} of the resident token store (all 0 without one)."""
+        rows, L, bits = C.c_int64(), C.c_int(), C.c_int()
+        self._check(self.lib.rag_tokens_info(self.h, C.byref(rows), C.byref(L), C.byref(bits)), "rag_tokens_info")
+        return {"rows": int(rows.value), "L": int(L.value), "id_bits": int(bits.value)}
+
+    def ce_set_pair_format(self, fmt):
+        """Layout the pair builder writes from now on: PAIR_BERT (0, [cls] q [sep] d [sep], types 0 | 1) or PAIR_ROBERTA
+        (1, [cls] q [sep] [sep] d [sep], all type 0). Applies to retrieve_rerank_dev and ce_build_pairs_dev."""
+        self._check(self.lib.rag_ce_set_pair_format(self.h, int(fmt)), "rag_ce_set_pair_format")
 
     def tokens_append_dev(self, tokens, lens, stream=None):
         """Append a row block of the passage token store from device memory: tokens [n, L] int32, lens [n] int32 CUDA tensors."""

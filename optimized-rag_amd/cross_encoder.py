@@ -1,5 +1,6 @@
-"""Host side of the cross-encoder (K7): local checkpoint loading, WordPiece tokenisation of (query, doc) pairs
-and batching into rag_ce_score_host. Stands where `sentence_transformers.CrossEncoder` stands in the reference
+"""Host side of the cross-encoder (K7): local checkpoint loading (BERT, and RoBERTa / XLM-RoBERTa relabelled as BERT:
+map_checkpoint), tokenisation of (query, doc) pairs (WordPiece from vocab.txt, or whatever tokenizer.json describes) and
+batching into rag_ce_score_host. Stands where `sentence_transformers.CrossEncoder` stands in the reference
 (/root/reference/rag/reranker.py:312-313,355): `predict(pairs)` returns RAW logits (the ms-marco checkpoints use an
 identity activation, which is why the reference applies its own sigmoid at :359).
 
@@ -45,6 +46,74 @@ def config_from_hf(cfg):
                 type_vocab=cfg.get("type_vocab_size", 2), eps=cfg.get("layer_norm_eps", 1e-12))
 
 
+ROBERTA_TYPES = ("xlm-roberta", "roberta")
+
+
+def map_checkpoint(hf_cfg, sd, head=True):
+    """config.json (a dict) and a state dict -> (engine config, state dict under the names flatten_state_dict(prefix="bert.")
+    reads). Pure: no engine, no file, no cast - the tensors keep their dtype, so a float64 checkpoint stays float64.
+
+    model_type `bert` (or none): the names are taken with the prefix `bert.` or none. head=True wants the pooler and a one-logit
+    classifier; head=False a bare encoder (a pooler, when the file has one, is left out).
+    model_type `xlm-roberta` / `roberta` (prefix `roberta.` or none): the same encoder under other names, with two differences.
+    RoBERTa numbers the real tokens of a right-padded row pad_token_id + 1, pad_token_id + 2, ...: the position table loses its
+    first pad_token_id + 1 rows and max_pos = max_position_embeddings - pad_token_id - 1, after which position = token index as
+    in BERT. RobertaClassificationHead is dense + tanh + out_proj on row 0, which is BERT's pooler + classifier:
+    classifier.dense -> bert.pooler.dense, classifier.out_proj -> classifier. Such a model has ONE token type (the engine then
+    gives every token row 0 of the type table) and its pairs are laid out [cls] q [sep] [sep] d [sep]: the config carries
+    pair_format = 1 and cls_id / sep_id = bos_token_id / eos_token_id for rag_ce_set_pair_format and the pair builder.
+    (The engine takes a row's real tokens to be its first `len` ones; a pad id INSIDE a text would shift transformers' position
+    numbers, which no tokenizer produces.)
+    ValueError: position_embedding_type other than absolute, a GELU that is not the exact erf one, more than one label."""
+    mt = hf_cfg.get("model_type", "bert")
+    if mt != "bert" and mt not in ROBERTA_TYPES:
+        raise ValueError(f"unsupported model_type {mt!r}: bert, roberta and xlm-roberta checkpoints are supported")
+    if hf_cfg.get("position_embedding_type", "absolute") != "absolute":
+        raise ValueError(f"unsupported position_embedding_type {hf_cfg['position_embedding_type']!r}: only absolute positions")
+    cfg = config_from_hf(hf_cfg)                                  # raises on a non-erf GELU
+    roberta = mt in ROBERTA_TYPES
+    src = "roberta." if roberta else "bert."
+    if not any(k.startswith(src) for k in sd):
+        src = ""
+    names = ["embeddings.word_embeddings.weight", "embeddings.position_embeddings.weight", "embeddings.token_type_embeddings.weight",
+             "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"]
+    names += [f"encoder.layer.{l}.{k}" for l in range(cfg["layers"]) for k in LAYER_KEYS]
+    pairs = [(src + n, "bert." + n) for n in names]
+    if head:
+        hd = ("classifier.dense.", "classifier.out_proj.") if roberta else (src + "pooler.dense.", "classifier.")
+        pairs += [(hd[0] + t, "bert.pooler.dense." + t) for t in ("weight", "bias")] + [(hd[1] + t, "classifier." + t) for t in ("weight", "bias")]
+    missing = [a for a, _ in pairs if a not in sd]
+    if missing:
+        raise KeyError(f"checkpoint lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
+    out = {b: sd[a] for a, b in pairs}
+    if head and (int(hf_cfg.get("num_labels", 1)) != 1 or len(hf_cfg.get("id2label", {0: 0})) != 1 or out["classifier.weight"].shape[0] != 1):
+        raise ValueError("only single-logit classifiers are supported (num_labels = 1)")
+    if roberta:
+        pad = int(hf_cfg.get("pad_token_id", 1))
+        cfg["max_pos"] = cfg["max_pos"] - pad - 1
+        out["bert.embeddings.position_embeddings.weight"] = out["bert.embeddings.position_embeddings.weight"][pad + 1:]
+        if cfg["max_pos"] < 1:
+            raise ValueError("max_position_embeddings leaves no position after the pad_token_id + 1 reserved rows")
+        cfg.update(pair_format=1, cls_id=int(hf_cfg.get("bos_token_id", 0)), sep_id=int(hf_cfg.get("eos_token_id", 2)))
+    return cfg, out
+
+
+def load_tokenizer(path):
+    """The tokenizer of a checkpoint directory: tokenizer.json (any model of the `tokenizers` package, with its own special-token
+    template: XLM-R's SentencePiece one writes <s> a </s> </s> b </s>) when it is there, else WordPiece from vocab.txt."""
+    tj = os.path.join(path, "tokenizer.json")
+    if os.path.exists(tj):
+        from tokenizers import Tokenizer
+        return Tokenizer.from_file(tj)
+    from tokenizers import BertWordPieceTokenizer
+    lower = True
+    tk_cfg = os.path.join(path, "tokenizer_config.json")
+    if os.path.exists(tk_cfg):
+        with open(tk_cfg) as f:
+            lower = bool(json.load(f).get("do_lower_case", True))
+    return BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lower)
+
+
 MINILM_L6_CONFIG = dict(vocab_size=30522, hidden=384, layers=6, heads=12, ffn=1536, max_pos=512, type_vocab=2, eps=1e-12)
 """Shape of cross-encoder/ms-marco-MiniLM-L-6-v2 (the checkpoint the reference names at config.py:49), for benchmarks
 that run without the downloaded weights; a real deployment takes the shape from the checkpoint's config.json."""
@@ -78,25 +147,26 @@ class LocalCrossEncoder:
         self.tokenizer = tokenizer
         self.max_length = min(int(max_length), cfg["max_pos"], 512)
         self.batch_pairs = batch_pairs
+        # what the device-side pair builder needs to assemble the pairs this model was trained on (rag_ce_set_pair_format,
+        # the cls_id / sep_id arguments of retrieve_rerank_dev and ce_build_pairs_dev), and the width a token store must have
+        self.pair_format = int(cfg.get("pair_format", 0))
+        self.vocab_size = int(cfg["vocab_size"])
+        tid = getattr(tokenizer, "token_to_id", lambda t: None)
+        self.cls_id = int(cfg["cls_id"]) if "cls_id" in cfg else (101 if tid("[CLS]") is None else tid("[CLS]"))
+        self.sep_id = int(cfg["sep_id"]) if "sep_id" in cfg else (102 if tid("[SEP]") is None else tid("[SEP]"))
         self.engine.ce_load(cfg, tensors)
+        self.engine.ce_set_pair_format(self.pair_format)
 
     @classmethod
     def from_dir(cls, path, max_length=512, engine=None):
         from safetensors.numpy import load_file
-        from tokenizers import BertWordPieceTokenizer
         with open(os.path.join(path, "config.json")) as f:
-            cfg = config_from_hf(json.load(f))
-        sd = load_file(os.path.join(path, "model.safetensors"))
-        lower = True
-        tk_cfg = os.path.join(path, "tokenizer_config.json")
-        if os.path.exists(tk_cfg):
-            with open(tk_cfg) as f:
-                lower = bool(json.load(f).get("do_lower_case", True))
-        tok = BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lower)
-        return cls(cfg, flatten_state_dict(sd, cfg["layers"]), tok, max_length=max_length, engine=engine)
+            cfg, sd = map_checkpoint(json.load(f), load_file(os.path.join(path, "model.safetensors")))
+        return cls(cfg, flatten_state_dict(sd, cfg["layers"]), load_tokenizer(path), max_length=max_length, engine=engine)
 
     def tokenize_pairs(self, pairs):
-        """[CLS] q [SEP] d [SEP], token_type 0/1, truncation 'longest_first' to max_length, padded to the longest."""
+        """[CLS] q [SEP] d [SEP], token_type 0/1 (or the tokenizer.json's own template: <s> q </s> </s> d </s>, all 0), truncation
+        'longest_first' to max_length, padded to the longest."""
         self.tokenizer.enable_truncation(max_length=self.max_length, strategy="longest_first")
         self.tokenizer.no_padding()
         enc = self.tokenizer.encode_batch([(str(q), str(d)) for q, d in pairs])

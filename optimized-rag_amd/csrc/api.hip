@@ -50,8 +50,9 @@ int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_le
                        hipStream_t st);
 int rerank_topk_dev(rag_ctx* h, const float* logits_dev, const int64_t* cand_dev, int Q, int pool, int k, int64_t* ids_out, double* scores_out,
                     float* logits_out, hipStream_t st);
-int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L);
-int tokens_reserve(rag_ctx* h, int64_t n_rows, int L);
+int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L, int id_bits);
+int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits);
+int tokens_info(const rag_ctx* h, int64_t* rows_out, int* L_out, int* id_bits_out);
 int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, hipStream_t st);
 int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                         const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
@@ -872,14 +873,45 @@ int rag_tokens_load_host(rag_handle_t h, const int32_t* tokens, const int32_t* l
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return tokens_load_host(h, tokens, lens, n_rows, L);
+    return tokens_load_host(h, tokens, lens, n_rows, L, 16);
+}
+
+int rag_tokens_load_wide_host(rag_handle_t h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L, int id_bits) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_load: id_bits must be 16 or 24");
+    HOST_ENTRY(h);
+    return tokens_load_host(h, tokens, lens, n_rows, L, id_bits);
 }
 
 int rag_tokens_reserve(rag_handle_t h, int64_t n_rows_total, int L) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return tokens_reserve(h, n_rows_total, L);
+    return tokens_reserve(h, n_rows_total, L, 16);
+}
+
+int rag_tokens_reserve_wide(rag_handle_t h, int64_t n_rows_total, int L, int id_bits) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_reserve: id_bits must be 16 or 24");
+    HOST_ENTRY(h);
+    return tokens_reserve(h, n_rows_total, L, id_bits);
+}
+
+int rag_tokens_info(rag_handle_t h, int64_t* rows_out, int* L_out, int* id_bits_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return tokens_info(h, rows_out, L_out, id_bits_out);
+}
+
+int rag_ce_set_pair_format(rag_handle_t h, int format) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, format == RAG_PAIR_BERT || format == RAG_PAIR_ROBERTA, "ce_set_pair_format: unknown pair format (RAG_PAIR_BERT or RAG_PAIR_ROBERTA)");
+    // no wait: host state that a *_dev call reads while it enqueues (as rag_set_option), so a call queued earlier keeps the old layout
+    h->pair_format = format;
+    return RAG_OK;
 }
 
 int rag_tokens_append_dev(rag_handle_t h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, void* stream) {

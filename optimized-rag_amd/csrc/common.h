@@ -128,6 +128,7 @@ struct rag_device_mem : rag_index_mem {
     dev_buf<char> stage;
     // passage token store (pipeline.hip): [tok_rows][tok_L] uint16 WordPiece ids + lengths, row-aligned with the index
     dev_buf<uint16_t> tok;
+    dev_buf<uint8_t> tok_hi;         // [tok_rows][tok_L] bits 16-23 of the ids: present iff the store is 24 bits wide (rag_tokens_*_wide)
     dev_buf<int32_t> tok_len;
     dev_buf<int> tok_bad;            // device counter of out-of-range token ids seen by the appends
     dev_buf<char> pipe_ws;           // retrieve_rerank_dev: candidate lists, pair tokens, logits of one call
@@ -190,6 +191,7 @@ struct rag_ctx : rag_device_mem {
     rag_bm25_index* bm25 = nullptr;
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
+    int pair_format = RAG_PAIR_BERT;         // rag_ce_set_pair_format: read while a pair-building call enqueues
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process. raise_lds: the
     // dynamic LDS each group of kernels was last raised to. dense.hip: the emit instantiations by [DENSE0][SMALLQ][FUSED], the
     // persistent ones by [FUSED], the select kernel; bm25.hip: the range kernels. cross_encoder.hip: the two GEMM families, and

@@ -1153,7 +1153,13 @@ static int ce_load_model(rag_ctx* h, const rag_ce_config* cfg, const float* cons
     int rc;
     if ((rc = up_f32(h, T[0], (size_t)cfg->vocab_size * H, m->word))) return rc;
     if ((rc = up_f32(h, T[1], (size_t)cfg->max_pos * H, m->pos))) return rc;
-    if ((rc = up_f32(h, T[2], (size_t)cfg->type_vocab * H, m->type))) return rc;
+    if (cfg->type_vocab == 1) {
+        // one token type (RoBERTa / XLM-R): the forward indexes the table with `token_type != 0`, so the row is uploaded twice -
+        // every token takes row 0's values whatever token_type_ids holds
+        if ((rc = m->type.alloc(h, 2 * H))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(m->type, T[2], H * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(m->type + H, T[2], H * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    } else if ((rc = up_f32(h, T[2], (size_t)cfg->type_vocab * H, m->type))) return rc;
     if ((rc = up_f32(h, T[3], H, m->emb_ln_g))) return rc;
     if ((rc = up_f32(h, T[4], H, m->emb_ln_b))) return rc;
     m->layers.resize(cfg->layers);

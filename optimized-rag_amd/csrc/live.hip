@@ -221,12 +221,20 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
         ARG_CHECK(h, std::isfinite(tmax), "insert: temporal scores must be finite");
     }
     std::vector<uint16_t> tok16;
+    std::vector<uint8_t> tok_hi8;        // bits 16-23, for a 24-bit store
+    const bool wide_tok = has_tok && h->tok_hi != nullptr;
     if (has_tok) {
         const int L = h->tok_L;
         tok16.resize((size_t)n * L);
+        if (wide_tok) tok_hi8.resize((size_t)n * L);
         for (int64_t i = 0; i < n * L; ++i) {
             const int32_t v = rb->tokens[i];
-            ARG_CHECK(h, v >= 0 && v <= 65535, "insert: token ids must be in [0, 65535]");
+            if (wide_tok) {
+                ARG_CHECK(h, v >= 0 && v <= 0xFFFFFF, "insert: token ids must be in [0, 16777215]");
+                tok_hi8[(size_t)i] = (uint8_t)(v >> 16);
+            } else {
+                ARG_CHECK(h, v >= 0 && v <= 65535, "insert: token ids must be in [0, 65535]");
+            }
             tok16[(size_t)i] = (uint16_t)v;
         }
     }
@@ -258,6 +266,7 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     grow(g.temporal, rb->temporal && (!h->temporal || need > h->cap_tmp), cap_tmp, 1);
     grow(g.vis, h->vis && need > h->cap_vis, cap_vis, 1);
     grow(g.tok, has_tok && need > h->tok_cap, cap_tok, h->tok_L);
+    grow(g.tok_hi, wide_tok && need > h->tok_cap, cap_tok, h->tok_L);
     grow(g.tok_len, has_tok && need > h->tok_cap, cap_tok, 1);
     if (!ok) {
         (void)hipGetLastError();
@@ -295,6 +304,7 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     if ((rc = commit(h->tenants, g.tenants, 1, &h->cap_ten, cap_ten))) return rc;
     if ((rc = commit(h->temporal, g.temporal, 1, &h->cap_tmp, cap_tmp))) return rc;
     if ((rc = commit(h->vis, g.vis, 1, &h->cap_vis, cap_vis))) return rc;
+    if ((rc = commit(h->tok_hi, g.tok_hi, h->tok_L, nullptr, 0))) return rc;
     if ((rc = commit(h->tok, g.tok, h->tok_L, &h->tok_cap, cap_tok))) return rc;
     if ((rc = commit(h->tok_len, g.tok_len, 1, nullptr, 0))) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->emb32 + (size_t)n0 * h->dim, rb->emb, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
@@ -307,6 +317,7 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     }
     if (has_tok) {
         HIP_TRY(h, hipMemcpyAsync(h->tok + (size_t)n0 * h->tok_L, tok16.data(), tok16.size() * 2, hipMemcpyHostToDevice, st));
+        if (wide_tok) HIP_TRY(h, hipMemcpyAsync(h->tok_hi + (size_t)n0 * h->tok_L, tok_hi8.data(), tok_hi8.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(h->tok_len + n0, rb->token_lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -457,6 +468,7 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     if (tmp) planes.push_back({h->temporal, 8});
     if (tok) {
         planes.push_back({h->tok, (size_t)h->tok_L * 2});
+        if (h->tok_hi) planes.push_back({h->tok_hi, (size_t)h->tok_L});      // a row of L bytes: any alignment
         planes.push_back({h->tok_len, 4});
     }
     for (const plane& pl : planes) {
@@ -473,7 +485,8 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
             if (pl.row_bytes % 16 == 0) LIVE_GATHER(uint4)
             else if (pl.row_bytes % 8 == 0) LIVE_GATHER(uint2)
             else if (pl.row_bytes % 4 == 0) LIVE_GATHER(uint32_t)
-            else LIVE_GATHER(uint16_t)
+            else if (pl.row_bytes % 2 == 0) LIVE_GATHER(uint16_t)
+            else LIVE_GATHER(uint8_t)
 #undef LIVE_GATHER
             e = hipMemcpyAsync((char*)pl.p + (size_t)d0 * pl.row_bytes, data, bytes, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) return fail(e, "row copy");

@@ -7,6 +7,7 @@
 // between the query arriving and the top-k leaving nothing crosses PCIe.
 //   1. candidates: dense top-pool (mode 0) or dense + BM25 + RRF -> top-pool (mode 1)
 //   2. ce_build_pairs_kernel: [CLS] query [SEP] passage [SEP], token_type 0 | 1, truncated 'longest_first' to L_pair
+//      (or the RoBERTa layout [CLS] query [SEP] [SEP] passage [SEP], all type 0: rag_ce_set_pair_format)
 //   3. ce_score (cross_encoder.hip)
 //   4. rerank_topk_kernel: sigmoid in float64, stable order (score desc, candidate order on ties), top-k
 #include "common.h"
@@ -62,17 +63,46 @@ __global__ void tokens_narrow_kernel(const int32_t* __restrict__ in, uint16_t* _
     out[i] = (uint16_t)v;
 }
 
-// The token store is kept as uint16: 2 B per token (51 GB for 100M x 256-token passages replicated per GPU, the budget of
-// SURVEY.md section 8e; the r1 int32 store would have been 102 GB). The ABI takes int32 ids; they are narrowed on the
-// device while streaming in (64 Mi tokens per piece through the staging arena).
-int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L) {
-    ARG_CHECK(h, tokens && lens && n_rows > 0 && L > 0 && L <= 512, "tokens_load: bad arguments (passage length <= 512)");
+// the same into a 24-bit store (rag_tokens_load_wide_host / rag_tokens_reserve_wide, id_bits = 24: XLM-R's vocabulary has
+// 250,002 entries): the low half into the uint16 plane, bits 16-23 into a byte plane; ids outside [0, 16777215] are flagged
+__global__ void tokens_narrow_wide_kernel(const int32_t* __restrict__ in, uint16_t* __restrict__ out, uint8_t* __restrict__ out_hi,
+                                          int64_t n, int* __restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t v = in[i];
+    if (v < 0 || v > 0xFFFFFF) atomicAdd(bad, 1);
+    out[i] = (uint16_t)v;
+    out_hi[i] = (uint8_t)(v >> 16);
+}
+
+// n ids at in -> store slots [at, at + n): both planes of a wide store, the one plane of a narrow one
+static void tokens_narrow(rag_ctx* h, const int32_t* in, int64_t at, int64_t n, int* bad, hipStream_t st) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (h->tok_hi) hipLaunchKernelGGL(tokens_narrow_wide_kernel, grid, dim3(256), 0, st, in, h->tok + at, h->tok_hi + at, n, bad);
+    else hipLaunchKernelGGL(tokens_narrow_kernel, grid, dim3(256), 0, st, in, h->tok + at, n, bad);
+}
+static const char* tokens_range_msg(const rag_ctx* h, bool append) {
+    if (h->tok_hi) return append ? "tokens_append: token ids must be in [0, 16777215]" : "tokens_load: token ids must be in [0, 16777215]";
+    return append ? "tokens_append: token ids must be in [0, 65535]" : "tokens_load: token ids must be in [0, 65535]";
+}
+static void tokens_drop(rag_ctx* h) {
     h->tok.reset();
+    h->tok_hi.reset();
     h->tok_len.reset();
     h->tok_rows = 0; h->tok_cap = 0;
+}
+
+// The token store is kept as uint16: 2 B per token (51 GB for 100M x 256-token passages replicated per GPU, the budget of
+// SURVEY.md section 8e; the r1 int32 store would have been 102 GB). The ABI takes int32 ids; they are narrowed on the
+// device while streaming in (64 Mi tokens per piece through the staging arena). id_bits = 24 adds the byte plane: 3 B per token.
+int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L, int id_bits) {
+    ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_load: id_bits must be 16 or 24");
+    ARG_CHECK(h, tokens && lens && n_rows > 0 && L > 0 && L <= 512, "tokens_load: bad arguments (passage length <= 512)");
+    tokens_drop(h);
     const int64_t total = n_rows * (int64_t)L, piece = (int64_t)64 << 20;
     int rc;
     if ((rc = h->tok.alloc(h, (size_t)total))) return rc;
+    if (id_bits == 24 && (rc = h->tok_hi.alloc(h, (size_t)total))) return rc;
     if ((rc = h->tok_len.alloc(h, (size_t)n_rows))) return rc;
     if ((rc = stage_reserve(h, stage_size((size_t)std::min(total, piece), 4) + 256))) return rc;
     int32_t* buf = reinterpret_cast<int32_t*>(h->stage.get());
@@ -81,12 +111,12 @@ int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int
     for (int64_t o = 0; o < total; o += piece) {
         const int64_t nn = std::min(piece, total - o);
         HIP_TRY(h, hipMemcpyAsync(buf, tokens + o, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(tokens_narrow_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, buf, h->tok + o, nn, bad);
+        tokens_narrow(h, buf, o, nn, bad, h->stream);
         HIP_TRY(h, hipStreamSynchronize(h->stream));                 // buf is reused by the next piece
     }
     int n_bad = 0;
     HIP_TRY(h, hipMemcpy(&n_bad, bad, sizeof(int), hipMemcpyDeviceToHost));
-    ARG_CHECK(h, n_bad == 0, "tokens_load: token ids must be in [0, 65535]");
+    ARG_CHECK(h, n_bad == 0, tokens_range_msg(h, false));
     HIP_TRY(h, hipMemcpy(h->tok_len, lens, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     h->tok_rows = n_rows;
     h->tok_cap = n_rows;
@@ -96,13 +126,13 @@ int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int
 
 // Chunked fill from device memory (a replicated 100M-passage store is 45 GB as uint16 and would be 90 GB as one int32 host
 // array): reserve once, append row blocks in order. tok_rows counts the rows appended so far; tok_cap the reservation.
-int tokens_reserve(rag_ctx* h, int64_t n_rows, int L) {
+int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits) {
+    ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_reserve: id_bits must be 16 or 24");
     ARG_CHECK(h, n_rows > 0 && L > 0 && L <= 512, "tokens_reserve: bad arguments (passage length <= 512)");
-    h->tok.reset();
-    h->tok_len.reset();
-    h->tok_rows = 0; h->tok_cap = 0;
+    tokens_drop(h);
     int rc;
     if ((rc = h->tok.alloc(h, (size_t)n_rows * L))) return rc;
+    if (id_bits == 24 && (rc = h->tok_hi.alloc(h, (size_t)n_rows * L))) return rc;
     if ((rc = h->tok_len.alloc(h, (size_t)n_rows))) return rc;
     if ((rc = h->tok_bad.reserve(h, 1))) return rc;
     // cleared on the handle's stream and waited for: a null-stream hipMemset is not ordered against the non-blocking stream the
@@ -114,13 +144,20 @@ int tokens_reserve(rag_ctx* h, int64_t n_rows, int L) {
     return RAG_OK;
 }
 
+int tokens_info(const rag_ctx* h, int64_t* rows_out, int* L_out, int* id_bits_out) {
+    const bool have = h->tok != nullptr;
+    if (rows_out) *rows_out = have ? h->tok_rows : 0;
+    if (L_out) *L_out = have ? h->tok_L : 0;
+    if (id_bits_out) *id_bits_out = !have ? 0 : h->tok_hi ? 24 : 16;
+    return RAG_OK;
+}
+
 int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n, hipStream_t st) {
     ARG_CHECK(h, h->tok_cap > 0, "tokens_append: rag_tokens_reserve first");
     ARG_CHECK(h, n >= 0 && h->tok_rows + n <= h->tok_cap && (n == 0 || (tokens_dev && lens_dev)), "tokens_append: exceeds the reservation");
     if (n == 0) return RAG_OK;
     const int64_t total = n * (int64_t)h->tok_L;
-    hipLaunchKernelGGL(tokens_narrow_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tokens_dev,
-                       h->tok + (size_t)h->tok_rows * h->tok_L, total, h->tok_bad);
+    tokens_narrow(h, tokens_dev, h->tok_rows * (int64_t)h->tok_L, total, h->tok_bad, st);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->tok_len + h->tok_rows, lens_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     int n_bad = 0;                                                   // synchronous check: a load path, not a search path
@@ -132,29 +169,32 @@ int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens
         HIP_TRY(h, hipMemsetAsync(h->tok_bad, 0, sizeof(int), st));
         HIP_TRY(h, hipStreamSynchronize(st));
     }
-    ARG_CHECK(h, n_bad == 0, "tokens_append: token ids must be in [0, 65535]");
+    ARG_CHECK(h, n_bad == 0, tokens_range_msg(h, true));
     h->tok_rows += n;
     return RAG_OK;
 }
 
-// one wave per pair: cand[q][j] is a doc id (id_base + row) or -1
+// one wave per pair: cand[q][j] is a doc id (id_base + row) or -1. WIDE: the store is 24 bits wide, an id is lo | hi << 16.
+// FMT (rag_ce_set_pair_format): RAG_PAIR_BERT [cls] q [sep] d [sep], types 0 | 1; RAG_PAIR_ROBERTA [cls] q [sep] [sep] d [sep], all 0
+template <bool WIDE, int FMT>
 __global__ __launch_bounds__(256) void ce_build_pairs_kernel(const int32_t* __restrict__ q_tok, const int32_t* __restrict__ q_len,
                                                               int Lq, const int64_t* __restrict__ cand, int64_t id_base,
                                                               const uint16_t* __restrict__ tok, const int32_t* __restrict__ tok_len,
                                                               int Ld, int64_t n_rows, int n_pairs, int pool, int L, int cls_id,
                                                               int sep_id, int32_t* __restrict__ ids, int32_t* __restrict__ tt,
-                                                              int32_t* __restrict__ lens) {
+                                                              int32_t* __restrict__ lens, const uint8_t* __restrict__ tok_hi) {
+    constexpr int X = FMT == RAG_PAIR_ROBERTA ? 1 : 0;       // the second separator between the two sides
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (p >= n_pairs) return;
     const int q = p / pool;
     const int64_t row = cand[p] < 0 ? -1 : cand[p] - id_base;
     // truncation = 'longest_first' to max_length L, as CrossEncoder.predict tokenises its pairs (SURVEY.md section 8c;
     // the fast tokenizer's rule, pinned against the `tokenizers` package by tests/test_pair_truncation.py): with
-    // M = L - 3 content tokens and n1 <= n2 the two lengths, the shorter side is kept whole while it fits
-    // (n2 = max(n1, M - n1)); if both exceed their share, n1 = M / 2 and n2 = n1 + M % 2.
+    // M = L - 3 content tokens (L - 4 in the RoBERTa layout) and n1 <= n2 the two lengths, the shorter side is kept whole
+    // while it fits (n2 = max(n1, M - n1)); if both exceed their share, n1 = M / 2 and n2 = n1 + M % 2.
     int ql = max(0, min(q_len[q], Lq));
     int dl = (row >= 0 && row < n_rows) ? max(0, min(tok_len[row], Ld)) : 0;
-    const int M = L - 3;
+    const int M = L - 3 - X;
     if (ql + dl > M) {
         const bool swap = ql > dl;
         int n1 = swap ? dl : ql, n2 = swap ? ql : dl;
@@ -163,20 +203,35 @@ __global__ __launch_bounds__(256) void ce_build_pairs_kernel(const int32_t* __re
         ql = swap ? n2 : n1;
         dl = swap ? n1 : n2;
     }
-    const int total = ql + dl + 3;
+    const int total = ql + dl + 3 + X;
     const int32_t* qt = q_tok + (size_t)q * Lq;
     const uint16_t* dt = tok + (size_t)(row < 0 ? 0 : row) * Ld;
+    const uint8_t* dh = WIDE ? tok_hi + (size_t)(row < 0 ? 0 : row) * Ld : nullptr;
     for (int t = lane; t < L; t += 64) {
         int v = 0, ty = 0;
         if (t == 0) v = cls_id;
         else if (t <= ql) v = qt[t - 1];
         else if (t == ql + 1) v = sep_id;
-        else if (t < ql + 2 + dl) { v = dt[t - ql - 2]; ty = 1; }
-        else if (t == ql + 2 + dl) { v = sep_id; ty = 1; }
+        else if (X && t == ql + 2) v = sep_id;
+        else if (t < ql + 2 + X + dl) {
+            v = dt[t - ql - 2 - X];
+            if constexpr (WIDE) v |= (int)dh[t - ql - 2 - X] << 16;
+            ty = X ? 0 : 1;
+        } else if (t == ql + 2 + X + dl) { v = sep_id; ty = X ? 0 : 1; }
         ids[(size_t)p * L + t] = v;
         tt[(size_t)p * L + t] = ty;
     }
     if (lane == 0) lens[p] = total;
+}
+
+// the instantiation for the handle's store width and pair layout (both read here, while the call enqueues)
+static int launch_build_pairs(rag_ctx* h, const int32_t* q_tok, const int32_t* q_len, int Lq, const int64_t* cand, int64_t id_base, size_t P,
+                              int pool, int L_pair, int cls_id, int sep_id, int32_t* ids, int32_t* tt, int32_t* lens, hipStream_t st) {
+    auto k = h->tok_hi ? (h->pair_format == RAG_PAIR_ROBERTA ? ce_build_pairs_kernel<true, RAG_PAIR_ROBERTA> : ce_build_pairs_kernel<true, RAG_PAIR_BERT>)
+                       : (h->pair_format == RAG_PAIR_ROBERTA ? ce_build_pairs_kernel<false, RAG_PAIR_ROBERTA> : ce_build_pairs_kernel<false, RAG_PAIR_BERT>);
+    launch(k, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, q_tok, q_len, Lq, cand, id_base, h->tok, h->tok_len, h->tok_L, h->tok_rows,
+           (int)P, pool, L_pair, cls_id, sep_id, ids, tt, lens, h->tok_hi);
+    return launch_status(h);
 }
 
 // one workgroup per query, pool <= 256: stable rank by (sigmoid desc, candidate position asc)
@@ -217,10 +272,7 @@ int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_le
     ARG_CHECK(h, Q > 0 && pool > 0 && Lq > 0 && L_pair >= 8 && L_pair <= 512 && q_tok_dev && q_len_dev && cand_dev && ids_out && tt_out && lens_out,
               "build_pairs: bad arguments");
     const size_t P = (size_t)Q * pool;
-    hipLaunchKernelGGL(ce_build_pairs_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, q_tok_dev, q_len_dev, Lq, cand_dev, token_id_base,
-                       h->tok, h->tok_len, h->tok_L, h->tok_rows, (int)P, pool, L_pair, cls_id, sep_id, ids_out, tt_out, lens_out);
-    HIP_TRY(h, hipGetLastError());
-    return RAG_OK;
+    return launch_build_pairs(h, q_tok_dev, q_len_dev, Lq, cand_dev, token_id_base, P, pool, L_pair, cls_id, sep_id, ids_out, tt_out, lens_out, st);
 }
 
 int rerank_topk_dev(rag_ctx* h, const float* logits_dev, const int64_t* cand_dev, int Q, int pool, int k, int64_t* ids_out, double* scores_out,
@@ -283,9 +335,7 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     h->ids = std::move(ids_saved);
     h->id_base = id_base_saved;
     if (rc) return rc;
-    hipLaunchKernelGGL(ce_build_pairs_kernel, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, q_tok_dev, q_len_dev, Lq, cand, (int64_t)0,
-                       h->tok, h->tok_len, h->tok_L, h->tok_rows, (int)P, pool, L_pair, cls_id, sep_id, pid, ptt, plen);
-    HIP_TRY(h, hipGetLastError());
+    if ((rc = launch_build_pairs(h, q_tok_dev, q_len_dev, Lq, cand, 0, P, pool, L_pair, cls_id, sep_id, pid, ptt, plen, st))) return rc;
     rc = ce_score(h, pid, ptt, plen, (int)P, L_pair, logit, st, false);
     if (rc) return rc;
     hipLaunchKernelGGL(rerank_topk_kernel, dim3(Q), dim3(256), 0, st, logit, cand, pool, k, ids_out, scores_out, logits_out);

@@ -106,15 +106,17 @@ class GpuDocumentIndex:
         if any(int(r["id"]) != i for i, r in enumerate(self.rows)):
             self.engine.set_ids(np.asarray(ids, dtype=np.int64))
 
-    def load_shard(self, shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072, headroom_rows: int = 0) -> None:
+    def load_shard(self, shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072, headroom_rows: int = 0,
+                   with_tokens: bool = False) -> None:
         """Stream an exported shard directory (shard_format.py; path or open Shard) into the index: rows [begin, end),
         payloads stay on disk and are read lazily per hit, doc ids are the table's primary keys. headroom_rows reserves
-        capacity for live inserts (growing a 115-GB share in place would need a second copy)."""
+        capacity for live inserts (growing a 115-GB share in place would need a second copy). with_tokens loads the shard's
+        passage tokens as the resident token store (24 bits wide when its ids exceed 65535: shard_format.load_shard_into)."""
         from . import shard_format as SF
         sh = SF.open_shard(shard) if isinstance(shard, str) else shard
         end = sh.n_rows if end is None else end
         assert sh.dim == self.dim
-        SF.load_shard_into(self.engine, sh, begin, end, chunk_rows, headroom_rows=headroom_rows)
+        SF.load_shard_into(self.engine, sh, begin, end, chunk_rows, headroom_rows=headroom_rows, with_tokens=with_tokens)
         self._tenant_id = dict(sh.tenant_table)
         self.rows = _ShardRows(sh, begin, end)
         self._next_id = int(sh.ids[begin:end].max()) + 1 if end > begin else 0

@@ -16,7 +16,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .cross_encoder import config_from_hf, flatten_state_dict
+from .cross_encoder import flatten_state_dict, load_tokenizer, map_checkpoint
 from .engine import get_engine
 
 
@@ -74,22 +74,14 @@ class LocalEmbeddingService:
 
     @classmethod
     def from_dir(cls, path, max_length=256, engine=None, **kw):
-        """A local sentence-transformers / HF BertModel directory: config.json, model.safetensors, vocab.txt. The pooling mode is
+        """A local sentence-transformers / HF BertModel, RobertaModel or XLMRobertaModel directory: config.json, model.safetensors,
+        tokenizer.json or vocab.txt (cross_encoder.map_checkpoint / load_tokenizer). The pooling mode is
         the one sentence-transformers recorded in 1_Pooling/config.json (mean or [CLS]; mean without the file); `normalize` stays
         the caller's argument."""
         from safetensors.numpy import load_file
-        from tokenizers import BertWordPieceTokenizer
         with open(os.path.join(path, "config.json")) as f:
-            cfg = config_from_hf(json.load(f))
-        sd = load_file(os.path.join(path, "model.safetensors"))
-        prefix = "bert." if any(k.startswith("bert.") for k in sd) else ""
-        lower = True
-        tk_cfg = os.path.join(path, "tokenizer_config.json")
-        if os.path.exists(tk_cfg):
-            with open(tk_cfg) as f:
-                lower = bool(json.load(f).get("do_lower_case", True))
-        tok = BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lower)
-        return cls(cfg, flatten_state_dict(sd, cfg["layers"], head=False, prefix=prefix), tok, max_length=max_length, engine=engine,
+            cfg, sd = map_checkpoint(json.load(f), load_file(os.path.join(path, "model.safetensors")), head=False)
+        return cls(cfg, flatten_state_dict(sd, cfg["layers"], head=False), load_tokenizer(path), max_length=max_length, engine=engine,
                    model=os.path.basename(os.path.normpath(path)), pooling=pooling_mode_of_dir(path), **kw)
 
     # ---- tokenisation: [CLS] text [SEP], truncated to max_length, padded to the longest of the batch -----------------

@@ -10,14 +10,16 @@ A row's `embedding` arrives either as a float sequence (pgvector's psycopg2 adap
 `'[0.1,0.2,...]'` (what `SELECT embedding::text` / a plain cursor returns) — both are accepted.
 
 Shard directory (everything little-endian, memory-mappable, rows in export order):
-  meta.json          {"version", "n_rows", "dim", "tenants": {agent_id: int}, "has_bm25", "token_len"}
+  meta.json          {"version", "n_rows", "dim", "tenants": {agent_id: int}, "has_bm25", "token_len", "token_id_max"?}
   embeddings.npy     [N, D] float32        the `vector(D)` column, bit-for-bit (pgvector stores float4)
   ids.npy            [N]    int64          the table's primary key (doc ids the search returns)
   tenants.npy        [N]    int32          agent_id -> tenant number (the `WHERE agent_id = %s` filter, on device)
   created_at.npy     [N]    float64        POSIX seconds, NaN = NULL (temporal boost, retrieval.py:266-292)
   rows.jsonl + rows.idx.npy                {content, metadata, filename?, file_type?} per row + byte offsets
   bm25.npz           indptr/doc/tf/doc_len/idf/avgdl/vocab   (optional) term-major CSR built by Bm25Postings.from_corpus
-  tokens.npy, token_lens.npy               (optional) [N, L] int32 passage token ids for the cross-encoder
+  tokens.npy, token_lens.npy               (optional) [N, L] int32 passage token ids for the cross-encoder; meta's optional
+                                           "token_id_max" (the largest id) picks the width of the resident store: above 65535
+                                           (XLM-R's 250k-entry vocabulary) the loader reserves the 24-bit one
 
 Loading streams `chunk_rows` rows at a time from the memory map into rag_index_reserve/rag_index_append_host, so a
 12.5M-row (77 GB) shard never sits in host memory twice; for one-process-per-GPU runs every rank loads its
@@ -132,16 +134,20 @@ class ShardWriter:
             vocab = np.array(sorted(p.vocab, key=p.vocab.get), dtype=object)
             np.savez(os.path.join(self.path, "bm25.npz"), indptr=p.indptr, doc=p.doc, tf=p.tf, doc_len=p.doc_len, idf=p.idf,
                      avgdl=np.float64(p.avgdl), k1=np.float64(p.k1), b=np.float64(p.b), vocab=vocab)
-        token_len = 0
+        token_len, token_id_max = 0, None
         if tokens is not None:
             tokens = np.ascontiguousarray(tokens, dtype=np.int32)
             assert tokens.shape[0] == n and token_lens is not None
             np.save(os.path.join(self.path, "tokens.npy"), tokens)
             np.save(os.path.join(self.path, "token_lens.npy"), np.asarray(token_lens, dtype=np.int32))
             token_len = int(tokens.shape[1])
+            token_id_max = int(tokens.max()) if tokens.size else 0
+        meta = {"version": FORMAT_VERSION, "n_rows": n, "dim": self.dim, "tenants": self._tenant_id,
+                "has_bm25": bool(build_bm25 and n), "token_len": token_len}
+        if token_id_max is not None:
+            meta["token_id_max"] = token_id_max               # optional key: older shards have none (their ids fit 16 bits)
         with open(os.path.join(self.path, "meta.json"), "w") as f:
-            json.dump({"version": FORMAT_VERSION, "n_rows": n, "dim": self.dim, "tenants": self._tenant_id,
-                       "has_bm25": bool(build_bm25 and n), "token_len": token_len}, f)
+            json.dump(meta, f)
         return self.path
 
 
@@ -182,6 +188,10 @@ class Shard:
             self.tokens = np.load(os.path.join(path, "tokens.npy"), mmap_mode="r")
             self.token_lens = np.load(os.path.join(path, "token_lens.npy"), mmap_mode="r")
 
+    def token_id_bits(self) -> int:
+        """Width of the resident token store these tokens need: 24 when meta's token_id_max exceeds 65535, else 16."""
+        return 24 if int(self.meta.get("token_id_max", 0)) > 65535 else 16
+
     def row(self, i: int) -> Dict[str, Any]:
         self._rows.seek(int(self._idx[i]))
         return json.loads(self._rows.read(int(self._idx[i + 1] - self._idx[i])).decode("utf-8"))
@@ -211,9 +221,11 @@ def open_shard(path: str) -> Shard:
 
 
 def load_shard_into(engine, shard: Shard, begin: int = 0, end: Optional[int] = None, chunk_rows: int = 131072,
-                    with_bm25: bool = True, headroom_rows: int = 0):
+                    with_bm25: bool = True, headroom_rows: int = 0, with_tokens: bool = False):
     """Stream rows [begin, end) of the shard into `engine` (RagEngine): fp32 master + fp16 unit copy are built on the
     device chunk by chunk; doc ids = the table's primary keys; tenant filter and (optionally) the BM25 slice loaded.
+    with_tokens: the shard's passage tokens become the resident token store, row-aligned with the index (reserved with the
+    headroom, streamed chunk by chunk through rag_tokens_append_dev), 24 bits wide when the shard's token_id_max exceeds 65535.
     Returns the Bm25Postings that were loaded (or None)."""
     end = shard.n_rows if end is None else end
     n = end - begin
@@ -223,6 +235,16 @@ def load_shard_into(engine, shard: Shard, begin: int = 0, end: Optional[int] = N
     if n:
         engine.set_ids(np.asarray(shard.ids[begin:end]))
         engine.set_tenants(np.asarray(shard.tenants[begin:end]))
+    if with_tokens and shard.tokens is not None and n:
+        import torch
+        L = int(shard.tokens.shape[1])
+        engine.tokens_reserve(n + int(headroom_rows), L, id_bits=shard.token_id_bits())
+        step = max(1, min(chunk_rows, (64 << 20) // L))
+        for b in range(begin, end, step):
+            e = min(end, b + step)
+            # (np.array copies: the memory map is read-only, which torch.from_numpy does not take)
+            engine.tokens_append_dev(torch.from_numpy(np.array(shard.tokens[b:e], dtype=np.int32)).cuda(),
+                                     torch.from_numpy(np.array(shard.token_lens[b:e], dtype=np.int32)).cuda())
     post = None
     if with_bm25 and n:
         post = shard.postings()
