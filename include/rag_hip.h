@@ -68,7 +68,10 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, ce_chunk_tokens, ce_mx. Unknown name: RAG_ERR_ARG. */
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, ce_chunk_tokens, ce_mx, ce_attn_stream (DESIGN.md section 6;
+ * ce_attn_stream: 0 = attention of 64-wide heads above length class 512 by the streamed kernel, -1 = by the global-memory form at
+ * every class above 256, 1 = by the streamed kernel at every class above 512 whatever the default there - the same bits in all
+ * three). Unknown name: RAG_ERR_ARG. */
 int rag_set_option(rag_handle_t h, const char* name, int value);
 
 /* ---- dense index: replaces the pgvector tables behind
@@ -454,15 +457,33 @@ int rag_ce_load_host(rag_handle_t h, const rag_ce_config* cfg, const float* cons
 /* input_ids/token_type_ids: [P][L] int32 (padded), lens[P]; logits_out[P] raw logits (float32).
  * lens[p] outside [1, seq_len] is clamped to it (0 and negative values count as 1, anything above seq_len as seq_len), once, before
  * any kernel uses it: row packing, attention and the pooling heads of rag_ce_score_* and rag_embed_* all see the clamped value.
- * seq_len (at most min(max_pos, 512)) is rounded up to an attention length class - 32, 64, 96, 128, 192, 256, 384 or 512 - which
- * picks the attention instance and launch shape. A result of rag_ce_score_* / rag_embed_* is a function of the sequence's own
- * tokens, the model and the forward (option ce_mx, the load-time probe) alone: bit-identical whatever seq_len and length class the
- * call has, whatever the other sequences of the call are and wherever the call is split into chunks
- * (tests/test_length_class_invariance_gpu.py). */
+ * seq_len is rounded up to an attention length class - 32, 64, 96, 128, 192, 256, 384, 512 for every model, and 768, 1024, 1536,
+ * 2048, 3072, 4096, 6144, 8192 behind them for a model with 64-wide heads - which picks the attention instance and launch shape
+ * (rag_ce_length_class below). seq_len may be at most
+ *   min(max_pos, 8192) for a model with 64-wide heads (the long-context XLM-R-large checkpoints: bge-m3, bge-reranker-v2-m3),
+ *   min(max_pos, 512)  for a model with 32-wide heads (its attention keeps a pair's K / V in LDS, and the MX forward is laid out
+ *                      per 32-wide head);
+ * a call past its model's limit is RAG_ERR_ARG - decided when the call is made, never at load - with a message that names the
+ * limit and whether max_pos or the head width set it, and leaves the handle usable. rag_model_seq_limit reports the limit.
+ * A result of rag_ce_score_* / rag_embed_* is a function of the sequence's own tokens, the model and the forward (option ce_mx,
+ * the load-time probe) alone: bit-identical whatever seq_len and length class the call has - across 512 too: a 100-token sequence
+ * scored in a seq_len = 3000 call returns the bits it returns in a seq_len = 128 call -, whatever the other sequences of the call
+ * are, wherever the call is split into chunks and whichever attention form option ce_attn_stream selects
+ * (tests/test_length_class_invariance_gpu.py, tests/test_long_seq_gpu.py).
+ * The limits above are those of rag_ce_score_* and rag_embed_* alone: the resident token store (rag_tokens_*: L <= 512),
+ * rag_ce_build_pairs_dev and rag_retrieve_rerank*_dev (L_pair <= 512) stay at 512 tokens. */
 int rag_ce_score_host(rag_handle_t h, const int32_t* input_ids_host, const int32_t* token_type_ids_host,
                       const int32_t* lens_host, int n_pairs, int seq_len, float* logits_out_host);
 int rag_ce_score_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev,
                      const int32_t* lens_dev, int n_pairs, int seq_len, float* logits_out_dev, void* stream);
+/* The attention length class a call of seq_len runs in on a model whose heads are head_dim wide (host-only, no GPU call; no reference
+ * counterpart). RAG_ERR_ARG for seq_len < 1, a head_dim other than 32 or 64, a seq_len past that width's limit (512 / 8192), or a
+ * NULL class_out. */
+int rag_ce_length_class(int head_dim, int seq_len, int* class_out);
+/* The longest seq_len the loaded model takes: min(max_pos, 512 or 8192 by head width). which: 0 = the cross-encoder
+ * (rag_ce_load_host), 1 = the embedder (rag_embed_load_host); anything else RAG_ERR_ARG. RAG_ERR_STATE when none is loaded. Host
+ * state only. */
+int rag_model_seq_limit(rag_handle_t h, int which /* 0 cross-encoder, 1 embedder */, int* limit_out);
 
 /* ---- local sentence-embedding model on the device: stands where the reference calls the OpenAI
  *      embeddings endpoint over HTTP for every query and every document - EmbeddingService._generate_embedding_uncached /
@@ -500,7 +521,9 @@ int rag_embed_dim(rag_handle_t h, int* dim_out);
  *      tokenizer call does; the reference's max_length is 512, rag/reranker.py:290-294) and padded to it; outputs per query:
  *      ids_out[k] doc ids (-1 padded), scores_out[k] = sigmoid(logit) as float64, logits_out[k] raw logits,
  *      cand_out[pool] (may be NULL) the candidate list that was reranked. 0 < k <= pool <= 256.
- *      Token store: 1 <= L <= 512, ids in [0, 65535] (the resident store is 16 bits wide); anything else is RAG_ERR_ARG. */
+ *      Token store: 1 <= L <= 512, ids in [0, 65535] (the resident store is 16 bits wide); anything else is RAG_ERR_ARG. L_pair
+ *      is at most 512 as well, whatever the loaded model's own limit (rag_model_seq_limit): the resident pipeline stays at 512
+ *      tokens per pair. */
 int rag_tokens_load_host(rag_handle_t h, const int32_t* tokens_host, const int32_t* lens_host, int64_t n_rows, int L);
 /* Chunked form for stores that should not exist as one host array (a replicated 100M-passage store, SURVEY.md section 8e, is
  * 45 GB resident as uint16 and would be 90 GB as one int32 host array): reserve once, then append row blocks in order from

@@ -139,6 +139,8 @@ _SIGS = {
     "rag_embed_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P], C.c_int),
     "rag_embed_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
     "rag_embed_dim": ([_P, C.POINTER(C.c_int)], C.c_int),
+    "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "rag_model_seq_limit": ([_P, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
 # The per-query-tenant entries: the arguments of their namesakes with `const int32_t* tenants_host` where those have `int tenant`
 # (argument position of the tenant in the namesake's list).
@@ -764,6 +766,22 @@ class RagEngine:
         ptrs = (_P * len(arrs))(*[a.ctypes.data for a in arrs])
         self._check(self.lib.rag_embed_load_host(self.h, C.byref(c), ptrs, len(arrs), flags), "rag_embed_load_host")
         self.embed_hidden = int(cfg["hidden"])
+
+    def model_seq_limit(self, which):
+        """The longest seq_len a call on the loaded cross-encoder (which = 0) or embedder (1) may have: min(max_pos, 512 with
+        32-wide heads, 8192 with 64-wide heads). RagError (RAG_ERR_STATE) when none is loaded."""
+        out = C.c_int()
+        self._check(self.lib.rag_model_seq_limit(self.h, int(which), C.byref(out)), "rag_model_seq_limit")
+        return int(out.value)
+
+    def ce_length_class(self, head_dim, seq_len):
+        """The attention length class a call of seq_len runs in on a model of that head width; host-only, no GPU. RagError when the
+        width is not 32 or 64 or seq_len is outside [1, that width's limit]."""
+        out = C.c_int()
+        rc = self.lib.rag_ce_length_class(int(head_dim), int(seq_len), C.byref(out))
+        if rc != 0:
+            raise RagError(f"rag_ce_length_class(head_dim={head_dim}, seq_len={seq_len}) failed ({rc})")
+        return int(out.value)
 
     def embed(self, input_ids, token_type_ids, lens):
         """int32 [n, L], [n, L], [n] (numpy) -> float32 [n, hidden] sentence embeddings."""

@@ -140,12 +140,18 @@ def random_init_tensors(cfg, seed=0):
     return out
 
 
+def seq_limit(cfg):
+    """The longest sequence, in tokens, a call on a model of this config may carry (rag_model_seq_limit): its position table, capped
+    at 8192 for 64-wide heads (the streamed attention kernel) and at 512 for 32-wide heads."""
+    return min(cfg["max_pos"], 8192 if cfg["hidden"] // cfg["heads"] == 64 else 512)
+
+
 class LocalCrossEncoder:
     def __init__(self, cfg, tensors, tokenizer, max_length=512, engine=None, batch_pairs=4096):
         self.cfg = cfg
         self.engine = engine or get_engine()
         self.tokenizer = tokenizer
-        self.max_length = min(int(max_length), cfg["max_pos"], 512)
+        self.max_length = min(int(max_length), seq_limit(cfg))
         self.batch_pairs = batch_pairs
         # what the device-side pair builder needs to assemble the pairs this model was trained on (rag_ce_set_pair_format,
         # the cls_id / sep_id arguments of retrieve_rerank_dev and ce_build_pairs_dev), and the width a token store must have

@@ -29,6 +29,8 @@ int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_i
 int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
 int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
+int ce_length_class(int d_head, int seq_len);
+int ce_model_seq_limit(const rag_ctx* h, int which);
 int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
                     float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant, query_tenants qt);
 int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out);
@@ -72,6 +74,7 @@ static const struct { const char* name; int rag_options::*field; } g_options[] =
     {"bm25_linear_grid", &rag_options::bm25_linear_grid},            {"bm25_sort_merge", &rag_options::bm25_sort_merge},
     {"no_fork", &rag_options::no_fork},                 {"fork_max_q", &rag_options::fork_max_q},
     {"ce_chunk_tokens", &rag_options::ce_chunk_tokens}, {"ce_mx", &rag_options::ce_mx},
+    {"ce_attn_stream", &rag_options::ce_attn_stream},
 };
 static void options_from_env(rag_options* o) {
     for (const auto& e : g_options) {
@@ -832,6 +835,26 @@ int rag_embed_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, const i
     LOCK(h);
     DEV_ENTRY(h);
     return embed_run(h, ids, tt, lens, n_texts, L, out, (hipStream_t)stream, false);
+}
+
+int rag_ce_length_class(int head_dim, int seq_len, int* class_out) {
+    const int c = ce_length_class(head_dim, seq_len);
+    if (!class_out || c == 0) return RAG_ERR_ARG;
+    *class_out = c;
+    return RAG_OK;
+}
+
+int rag_model_seq_limit(rag_handle_t h, int which, int* limit_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, limit_out && (which == 0 || which == 1), "model_seq_limit: which is 0 (cross-encoder) or 1 (embedder)");
+    const int lim = ce_model_seq_limit(h, which);
+    if (lim == 0) {
+        h->err = which == 0 ? "no cross-encoder loaded" : "no embedding model loaded";
+        return RAG_ERR_STATE;
+    }
+    *limit_out = lim;
+    return RAG_OK;
 }
 
 int rag_embed_dim(rag_handle_t h, int* dim_out) {

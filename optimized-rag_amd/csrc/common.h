@@ -79,6 +79,7 @@ struct rag_options {
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
     int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 = yes if the load-time probe saw it hold (cross_encoder.hip ce_probe_mx), 1 = yes, -1 = never
+    int ce_attn_stream = 0;       // 64-wide heads, length classes above 512: 0 = the streamed attention kernel where it is the default (cross_encoder.hip launch_attention64), -1 = DIRECT everywhere above class 256, 1 = streamed at every class above 512
 };
 
 // Candidate state of one emit / select pass over `rows` queries (a multiple of RAG_TILE): dense.hip runs the batch through one
@@ -200,6 +201,7 @@ struct rag_ctx : rag_device_mem {
     int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0;
     int attr_ce_attn_lds[2][3] = {};
     int attr_ce_attn64_lds = 0;              // the LDS-staged instance of ce_attention64_kernel (64-wide heads)
+    int attr_ce_attn64s_lds = 0;             // its streamed instance (the length classes above 512)
     rag_ce_model* ce = nullptr;
     rag_ce_model* emb = nullptr;             // sentence-embedding encoder (rag_embed_load_host): the K7 kernels behind a mean-pooling head
 };

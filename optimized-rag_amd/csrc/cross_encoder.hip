@@ -25,7 +25,8 @@
 //                      registers as the next MFMA's operand, online softmax over 32-key blocks, keys past len skipped.
 //   ce_attention64     the same scheme for models with 64-wide heads (BERT-base / BERT-large shapes; EPI_QKV64 writes their K / V
 //                      tiles): S chains two MFMAs over the head's dim halves, P.V fills four 16-dim accumulators; LDS-staged
-//                      up to length class 256, fragments read from global memory at 384 and 512
+//                      up to length class 256, fragments read from global memory at 384 and 512, streamed through an LDS ring
+//                      shared by a workgroup's waves in the classes 768 ... 8192
 //   ce_layernorm       one wave per token (384 = 6/lane), fp32 statistics, eps from config
 //   ce_pool_classify   tanh(Wp.x_cls + bp) -> wc.pooled + bc, fp32
 //   ce_meanpool        embedding head: mean over the real tokens, or the [CLS] row; optional L2 normalisation
@@ -486,12 +487,15 @@ __global__ __launch_bounds__(256) void ce_embed_ln_kernel(const int32_t* __restr
                                                            const float* __restrict__ type, const float* __restrict__ g,
                                                            const float* __restrict__ b, const int32_t* __restrict__ m_packed,
                                                            const int32_t* __restrict__ row_pair, const int32_t* __restrict__ pair_off,
-                                                           int L, int hidden, int vocab, float eps, half_t* __restrict__ x16) {
+                                                           int L, int hidden, int vocab, int max_pos, float eps, half_t* __restrict__ x16) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= m_packed[0]) return;
     const int pr = row_pair[row];
     const int p = (int)row - pair_off[pr];                    // position inside the pair (< L: the rounded length never exceeds L)
+    // a real token sits below seq_len <= max_pos; the pad rows behind a length that is no multiple of 16 may lie past the position
+    // table when max_pos is no multiple of 16 either: they take its last row (their values are never read, but must be finite)
+    const int pp = min(p, max_pos - 1);
     const size_t src = (size_t)pr * L + p;
     int id = ids[src];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
@@ -500,7 +504,7 @@ __global__ __launch_bounds__(256) void ce_embed_ln_kernel(const int32_t* __restr
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int c = lane + i * 64;
-        v[i] = word[(size_t)id * hidden + c] + type[(size_t)ty * hidden + c] + pos[(size_t)p * hidden + c];
+        v[i] = word[(size_t)id * hidden + c] + type[(size_t)ty * hidden + c] + pos[(size_t)pp * hidden + c];
     }
     wave_layernorm<PER>(v, g, b, hidden, eps, lane, x16 + row * 2 * hidden);
 }
@@ -745,13 +749,37 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
 // The four planes cost 512 B per key: the length classes up to 256 are staged whole in LDS (128 KiB), classes 384 and 512 do not
 // fit in 160 KiB and read the same fragment bytes straight from global memory (DIRECT; every tile is read by all waves of the
 // (head, pair), out of L2). DIRECT waves share nothing, so a (head, pair) is split over blockIdx.z into workgroups of 8 waves (256
-// queries each): 16 waves in one workgroup would cap the kernel at 128 VGPRs, which it does not fit without scratch. Both consume the keys in the same 32-key-block order with the same instructions, so a sequence's result does
+// queries each): 16 waves in one workgroup would cap the kernel at 128 VGPRs, which it does not fit without scratch. All forms consume the keys in the same 32-key-block order with the same instructions, so a sequence's result does
 // not depend on its length class.
-template <bool DIRECT>
+//
+// STREAM (the classes above 512, up to 8192 keys): the DIRECT geometry - grid (heads, P, L / 256), 8 waves = 256 queries of one
+// (head, pair) - but the workgroup's eight waves share every K / V fragment: the pair's 32-key blocks (K hi | K lo | V hi | V lo,
+// 4 KiB each = 16 KiB) pass through a ring of CE_A64_RING = 4 LDS slots, filled by the LDS-DMA of the resident form. One block
+// per stage: wave w copies tile (w & 1) of plane (w >> 1), two 1-KiB DMAs per block. Per block: the wave waits for ITS two DMAs
+// of block kb by a counted vmcnt (the blocks staged after it stay in flight), one workgroup barrier makes every wave's part of
+// block kb visible and frees the slot of block kb - 1 (all its fragment reads were consumed by MFMAs before the barrier), the wave
+// stages block kb + 3 into that slot and then computes block kb. Three blocks (48 KiB) are in flight under a block's 48 MFMAs
+// per wave; a shallower ring leaves two, a deeper one only adds cases to the counted wait. One block per stage keeps a stage at the 32-key
+// step of the online softmax and costs one barrier per 48 MFMAs. Ring = 4 x 16 KiB = 64 KiB of the CU's 160 KiB. The compiler
+// reports 152 VGPRs, no scratch, 3 waves per SIMD for this form (DIRECT: 152, resident: 153), so the registers, not the LDS, hold a
+// CU to ONE 8-wave workgroup in both forms above class 256; the ring could be 2.5 x as deep at no cost in occupancy, the measured
+// gain did not ask for it. L2 reads of K / V per (head, pair) drop from 8 x to 1 x per workgroup.
+// Three things this form alone must get right: (1) a workgroup whose 256 queries all lie past the pair's rows leaves before its
+// first barrier (uniform), but a WAVE past the rows of a live workgroup keeps staging and reaches every barrier - it only skips
+// the arithmetic; (2) tile nt of a pair with an odd tile count (second half of the last block) is never copied: its V slots are
+// zeroed in the ring, as the resident form zeroes them, because P = 0 there and 0 x NaN would poison the context (its K slots are
+// whatever the ring held: those scores are overwritten by -inf); (3) only the pair's own nkb blocks are staged, never L / 32.
+#define CE_A64_RESIDENT 0
+#define CE_A64_DIRECT 1
+#define CE_A64_STREAM 2
+#define CE_A64_RING 4                                                  // LDS slots of the streamed form (a power of two)
+#define CE_A64_SLOT 16384                                              // bytes of one slot: one 32-key block of the four planes
+template <int MODE>
 __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __restrict__ q16, const half_t* __restrict__ kf16,
                                                                               const half_t* __restrict__ vf16, size_t kv_plane,
                                                                               const int32_t* __restrict__ lens, const int32_t* __restrict__ pair_off,
                                                                               int L, int hidden, int m_pad, half_t* __restrict__ ctx16) {
+    constexpr bool DIRECT = MODE == CE_A64_DIRECT, STREAM = MODE == CE_A64_STREAM;
     constexpr int QB = 2;                                             // 16-query blocks per wave, in every length class
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -762,14 +790,37 @@ __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __res
     const int po = pair_off[pair], Lp = pair_off[pair + 1] - po;     // this pair's packed rows: len rounded up to 16
     const int nt = Lp >> 4;                                           // the pair's 16-row tiles; an odd count leaves the second
     const int nkb = (len + 31) >> 5;                                  // half of the last 32-key block outside the pair (masked)
-    const size_t plane_b = (size_t)L * 128;                           // bytes of one K (or V) plane of this (pair, head)
+    if (STREAM && (int)blockIdx.z * 256 >= Lp) return;                // the whole workgroup, before its first barrier
+    // bytes of one K (or V) plane of this (pair, head); STREAM: of one ring slot. L <= 8192: L * 128 <= 2^20, and the block offsets
+    // kb * 4096 below stay under 2^20 as well (kb < 256), so 32-bit byte offsets hold in every form.
+    const size_t plane_b = STREAM ? 4096 : (size_t)L * 128;
     const size_t t0 = ((size_t)head * (m_pad >> 4) + (po >> 4)) * 1024;                     // first tile of this (head, pair), in halfs
     // fragment reads below address tile c of a plane at byte c * 2048 + (lane's offset): the same bytes in LDS and in global memory
+    // (STREAM: tiles 2kb and 2kb + 1 sit at bytes 0 and 2048 of the planes of slot kb % CE_A64_RING)
     const char* const k_hi = DIRECT ? reinterpret_cast<const char*>(kf16 + t0) : smem;
     const char* const k_lo = DIRECT ? reinterpret_cast<const char*>(kf16 + t0 + kv_plane) : smem + plane_b;
     const char* const v_hi = DIRECT ? reinterpret_cast<const char*>(vf16 + t0) : smem + 2 * plane_b;
     const char* const v_lo = DIRECT ? reinterpret_cast<const char*>(vf16 + t0 + kv_plane) : smem + 3 * plane_b;
-    if (!DIRECT) {
+    // STREAM: this wave's share of every block = tile s_tl of plane s_pl (0 K hi, 1 K lo, 2 V hi, 3 V lo)
+    const int s_pl = wv >> 1, s_tl = wv & 1;
+    const half_t* const s_src = ((s_pl & 2) ? vf16 : kf16) + t0 + ((s_pl & 1) ? kv_plane : 0) + (size_t)s_tl * 1024 + (size_t)lane * 8;
+    const int s_dst = s_pl * 4096 + s_tl * 2048;
+    const bool s_skip_last = (nt & 1) && s_tl;                        // this wave's tile of the last block is tile nt: outside the pair
+    auto stream_stage = [&](const int blk) {
+        char* const d = smem + (blk & (CE_A64_RING - 1)) * CE_A64_SLOT + s_dst;
+        if (s_skip_last && blk == nkb - 1) {
+            if (s_pl & 2) {
+                *reinterpret_cast<u32x4*>(d + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(d + 1024 + lane * 16) = (u32x4){0u, 0u, 0u, 0u};
+            }
+            return;
+        }
+        ce_dma_at(s_src + (size_t)blk * 2048, d);
+        ce_dma_at(s_src + (size_t)blk * 2048 + 512, d + 1024);
+    };
+    if (STREAM)
+        for (int blk = 0; blk < CE_A64_RING - 1 && blk < nkb; ++blk) stream_stage(blk);
+    if (MODE == CE_A64_RESIDENT) {
         char* const sk_hi = smem;
         char* const sk_lo = smem + plane_b;
         char* const sv_hi = smem + 2 * plane_b;
@@ -797,14 +848,15 @@ __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __res
         }
     }
     const size_t row0 = (size_t)po;
-    const int qb0 = ((DIRECT ? (int)blockIdx.z * nwaves : 0) + wv) * QB;
+    const int qb0 = ((DIRECT || STREAM ? (int)blockIdx.z * nwaves : 0) + wv) * QB;
     const bool has_rows = qb0 * 16 < Lp;                              // waves past the pair's rows only helped with the DMA
     // B operand = Q rows (query fr of block b, dims half*32 + 8*fq..+8). Split-row layout: a head's 64 dims are two K groups of
     // [hi 32 | lo 32] halfs
     half8 qh[QB][2], ql[QB][2];
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
-        const int qb = (qb0 + b) * 16 < Lp ? qb0 + b : qb0;           // a block past the pair's rows is computed but not stored
+        // a block past the pair's rows is computed but not stored (a STREAM wave without rows computes nothing: it reads block 0)
+        const int qb = (qb0 + b) * 16 < Lp ? qb0 + b : (STREAM && !has_rows ? 0 : qb0);
         const half_t* qp = q16 + (row0 + qb * 16 + fr) * (2 * hidden) + head * 128 + fq * 8;
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
@@ -822,18 +874,27 @@ __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __res
         lsum[b] = 0.f;
     }
     const float cs = (float)(0.125 * 1.4426950408889634);             // 64^-0.5 * log2(e)
-    if (!DIRECT) {
+    if (STREAM) {
+        // Q is the kernel's only ordinary load: it is waited for HERE (the empty statements read the registers), before the loop, so
+        // that no wait for it lands between the counted waits of the ring and drains them
+#pragma unroll
+        for (int b = 0; b < QB; ++b)
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) asm volatile("" ::"v"(qh[b][dh]), "v"(ql[b][dh]));
+    }
+    if (MODE == CE_A64_RESIDENT) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    if (!has_rows) return;
+    if (!STREAM && !has_rows) return;                                 // STREAM: such a wave stays for the staging and the barriers
     float ce_inf;                                                     // see ce_attention_kernel: max by v_med3_f32(a, b, +inf)
     asm volatile("s_mov_b32 %0, 0x7f800000" : "=s"(ce_inf));
 #define CE_MAX2(a_, b_) __builtin_amdgcn_fmed3f(a_, b_, ce_inf)
     // one 32-key block = tiles 2kb and 2kb+1; EDGE (the pair's last block only: the loop is peeled) masks the keys past the length
     auto key_block = [&](const int kb, auto edge_c) {
         constexpr bool EDGE = decltype(edge_c)::value;
-        const int fo = kb * 4096 + lane * 16;
+        const int bo = STREAM ? (kb & (CE_A64_RING - 1)) * CE_A64_SLOT : kb * 4096;     // the block's byte offset in each plane
+        const int fo = bo + lane * 16;
         half8 kh[2][2], kl[2][2];                                     // [tile][dim half]
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -844,7 +905,7 @@ __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __res
             }
         // V fragment of d quarter dq = the lane's 4 key slots of tile 2kb | of tile 2kb+1. Tile 2kb+1 of an odd-count pair lies outside
         // the pair under P = 0: zeros in LDS, and DIRECT selects zeros.
-        const int vo = kb * 4096 + lane * 8;
+        const int vo = bo + lane * 8;
         half8 vh[4], vl[4];
 #pragma unroll
         for (int dq = 0; dq < 4; ++dq) {
@@ -924,9 +985,32 @@ __global__ __launch_bounds__(512) void ce_attention64_kernel(const half_t* __res
             for (int dq = 0; dq < 4; ++dq) cx[b][dq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[dq], ph, cx[b][dq], 0, 0, 0);
         }
     };
-    for (int kb = 0; kb + 1 < nkb; ++kb) key_block(kb, std::false_type{});
-    key_block(nkb - 1, std::true_type{});
+    // STREAM, per block: wait for this wave's own DMAs of block kb (counted: `ahead` = its DMAs of the blocks staged after kb, which
+    // stay in flight - 2 per block, none for a tile it skipped), barrier (block kb is complete; every wave is done with block kb - 1;
+    // lgkmcnt(0) retires this wave's zero stores and fragment reads), stage block kb + CE_A64_RING - 1 into the slot of block kb - 1.
+    auto stream_step = [&](const int kb) {
+        const int last = min(kb + CE_A64_RING - 2, nkb - 1);          // the last block staged so far
+        const int ahead = 2 * (last - kb) - (s_skip_last && last == nkb - 1 && last > kb ? 2 : 0);
+        if (ahead >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if (ahead == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (kb + CE_A64_RING - 1 < nkb) stream_stage(kb + CE_A64_RING - 1);
+    };
+    static_assert(CE_A64_RING == 4, "stream_step's vmcnt cases cover two blocks ahead of the wait");
+    if (STREAM) {
+        for (int kb = 0; kb + 1 < nkb; ++kb) {
+            stream_step(kb);
+            if (has_rows) key_block(kb, std::false_type{});
+        }
+        stream_step(nkb - 1);
+        if (has_rows) key_block(nkb - 1, std::true_type{});
+    } else {
+        for (int kb = 0; kb + 1 < nkb; ++kb) key_block(kb, std::false_type{});
+        key_block(nkb - 1, std::true_type{});
+    }
 #undef CE_MAX2
+    if (STREAM && !has_rows) return;
     // lane (fr, fq): cx[dq][r] = ctx[query fr][d = dq*16 + fq*4 + r]; the row sum is spread over the 4 fq lanes
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
@@ -1209,7 +1293,23 @@ int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* T,
     return ce_load_model(h, cfg, T, n, true, flags, &h->emb);
 }
 
-static const int kAttnL[] = {32, 64, 96, 128, 192, 256, 384, 512};
+// The attention length classes a call's seq_len is rounded up to. Up to 512: both head widths and both forwards. Above: models with
+// 64-wide heads alone (ce_attention_kernel keeps a pair's K / V in LDS, the MX forward is laid out per 32-wide head, and no
+// long-context checkpoint has 32-wide heads).
+static const int kAttnL[] = {32, 64, 96, 128, 192, 256, 384, 512, 768, 1024, 1536, 2048, 3072, 4096, 6144, 8192};
+static int ce_width_limit(int d_head) { return d_head == 64 ? 8192 : 512; }
+// the class of seq_len for a head width, 0 when there is none (host only)
+int ce_length_class(int d_head, int seq_len) {
+    if ((d_head != 32 && d_head != 64) || seq_len < 1 || seq_len > ce_width_limit(d_head)) return 0;
+    for (int c : kAttnL) if (c >= seq_len) return c;
+    return 0;
+}
+// the longest seq_len a call on model m may have: the position table or the head width's limit, whichever is smaller
+static int ce_seq_limit(const rag_ce_model* m) { return std::min(m->cfg.max_pos, ce_width_limit(m->d_head)); }
+int ce_model_seq_limit(const rag_ctx* h, int which) {
+    const rag_ce_model* m = which == 0 ? h->ce : h->emb;
+    return m ? ce_seq_limit(m) : 0;
+}
 
 // halfs per K / V fragment plane of Mp padded rows (both forwards)
 static size_t kv_plane_halfs(int64_t Mp, size_t H) { return (size_t)Mp * H + 2048; }
@@ -1269,18 +1369,30 @@ static int launch_attention(rag_ctx* h, const rag_ce_model* m, const ce_ws_base&
 // Attention of one layer of a model with 64-wide heads (split-fp16 forward): two 16-query blocks per wave in every length class. Up
 // to class 256 the (head, pair)'s four K / V planes are staged in LDS (512 B per key, 128 KiB at 256); classes 384 and 512 would
 // need 192 and 256 KiB, so they read the fragments from global memory, take no LDS, and run as two workgroups of 8 waves per
-// (head, pair).
+// (head, pair). The classes above 512 run L / 256 such workgroups per (head, pair): the streamed form (a 64-KiB LDS ring shared by
+// the workgroup's waves) from CE_A64_STREAM_FROM on, DIRECT below it: measured at 768, 1024, 1536, 2048, 4096 and 8192, the
+// streamed form is the faster one at every class by more than the round-to-round spread (0.9 % of an embedding forward at 768,
+// 6.1 % at 8192; profiles/ce_long_seq.json); 384 and 512 were neither measured nor switched. Option ce_attn_stream (a diagnostic: the two forms return
+// the same bits and can be timed against each other, tools/ce_long_time.py): -1 = DIRECT at every class above 256, 1 = streamed
+// at every class above 512 whatever the default there, 0 = the default.
+#define CE_A64_STREAM_FROM 768
 static int launch_attention64(rag_ctx* h, const rag_ce_model* m, const ce_split_ws& w, const ce_chunk& c, hipStream_t st) {
     const int H = m->cfg.hidden, L = c.L;
     const size_t kv_plane = kv_plane_halfs(w.tokens, H);
     const dim3 grid(m->cfg.heads, c.P), block(64 * (L / 32));
+    const dim3 zgrid(m->cfg.heads, c.P, (L + 255) / 256);             // workgroups of 256 queries
     if (L <= 256) {
         const int lds = L * 512;                                       // K hi | K lo | V hi | V lo fragment planes
-        if (int rc = raise_lds(h, h->attr_ce_attn64_lds, lds, ce_attention64_kernel<false>)) return rc;
-        launch(ce_attention64_kernel<false>, grid, block, lds, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
+        if (int rc = raise_lds(h, h->attr_ce_attn64_lds, lds, ce_attention64_kernel<CE_A64_RESIDENT>)) return rc;
+        launch(ce_attention64_kernel<CE_A64_RESIDENT>, grid, block, lds, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
+               (int)w.tokens, w.ctx16);
+    } else if (L > 512 && h->opt.ce_attn_stream >= 0 && (L >= CE_A64_STREAM_FROM || h->opt.ce_attn_stream > 0)) {
+        const int lds = CE_A64_RING * CE_A64_SLOT;
+        if (int rc = raise_lds(h, h->attr_ce_attn64s_lds, lds, ce_attention64_kernel<CE_A64_STREAM>)) return rc;
+        launch(ce_attention64_kernel<CE_A64_STREAM>, zgrid, dim3(512), lds, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
                (int)w.tokens, w.ctx16);
     } else
-        launch(ce_attention64_kernel<true>, dim3(m->cfg.heads, c.P, (L + 255) / 256), dim3(512), 0, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
+        launch(ce_attention64_kernel<CE_A64_DIRECT>, zgrid, dim3(512), 0, st, w.q16, w.kf16, w.vf16, kv_plane, w.io.clen, w.io.pair_off, L, H,
                (int)w.tokens, w.ctx16);
     return RAG_OK;
 }
@@ -1347,7 +1459,7 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     chunk_prologue(w, c, st);
     rc = per_lane_dispatch(h, H, [&](auto per) {
         launch(ce_embed_ln_kernel<decltype(per)::value>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, m->pos,
-               m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H, m->cfg.vocab_size, (float)m->cfg.ln_eps, w.x16);
+               m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H, m->cfg.vocab_size, m->cfg.max_pos, (float)m->cfg.ln_eps, w.x16);
     });
     if (rc) return rc;
     for (const auto& ly : m->layers) {
@@ -1493,9 +1605,15 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
                   hipStream_t st, bool host_ptrs, bool use_mx) {
     ARG_CHECK(h, ids && tt && lens && out && P > 0 && L_in > 0, "ce_score: bad arguments");
     const size_t ow = (size_t)m->out_width;
-    ARG_CHECK(h, L_in <= m->cfg.max_pos && L_in <= 512, "ce_score: sequence longer than max_position_embeddings/512");
-    int L = 0;
-    for (int c : kAttnL) if (c >= L_in) { L = c; break; }
+    // the cut is made here, per call, never at load: min(max_pos, 512 with 32-wide heads, 8192 with 64-wide heads)
+    if (L_in > ce_seq_limit(m)) {
+        const int wl = ce_width_limit(m->d_head);
+        h->err = "bad argument: ce_score: seq_len " + std::to_string(L_in) + " is past the model's limit of " + std::to_string(ce_seq_limit(m)) +
+                 (m->cfg.max_pos < wl ? " tokens, set by max_position_embeddings (max_pos " + std::to_string(m->cfg.max_pos) + ")"
+                                      : " tokens, set by the head width (" + std::to_string(m->d_head) + "-wide heads: " + std::to_string(wl) + ")");
+        return RAG_ERR_ARG;
+    }
+    const int L = ce_length_class(m->d_head, L_in);
     // ~2M tokens of activations per chunk (~30 GB). Option ce_chunk_tokens (diagnostic) shrinks it so that parity tests can run
     // the multi-chunk loop on small inputs.
     const int64_t chunk_tokens = h->opt.ce_chunk_tokens >= 32 ? h->opt.ce_chunk_tokens : 2'000'000;

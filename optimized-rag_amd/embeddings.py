@@ -16,7 +16,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .cross_encoder import flatten_state_dict, load_tokenizer, map_checkpoint
+from .cross_encoder import flatten_state_dict, load_tokenizer, map_checkpoint, seq_limit
 from .engine import get_engine
 
 
@@ -50,7 +50,7 @@ class LocalEmbeddingService:
         self.dimensions = int(cfg["hidden"])
         self.engine = engine or get_engine(dim=self.dimensions)
         self.tokenizer = tokenizer
-        self.max_length = min(int(max_length), cfg["max_pos"], 512)
+        self.max_length = min(int(max_length), seq_limit(cfg))
         self.batch_size = int(batch_size)
         self.pooling = pooling
         self.engine.embed_load(cfg, tensors, normalize=normalize, pooling=pooling)

@@ -142,7 +142,8 @@ class CrossEncoderReranker(_EngineMixin):
     BertForSequenceClassification cross-encoder (e.g. a downloaded cross-encoder/ms-marco-MiniLM-L-6-v2). The
     reference hands the same argument to sentence_transformers.CrossEncoder (:312-313), which fetches by name;
     there is no network here, so a name that is not a directory leaves the model unavailable — the same
-    outcome as the reference's swallowed load failure (:315-318)."""
+    outcome as the reference's swallowed load failure (:315-318). `max_length` goes to LocalCrossEncoder as it is: up to the
+    model's own limit (cross_encoder.seq_limit: 8192 tokens for a long-context XLM-R-large reranker, 512 for the default model)."""
 
     TENSOR_ORDER_DOC = "see cross_encoder.flatten_state_dict"
 
