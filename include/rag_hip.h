@@ -512,6 +512,67 @@ int rag_embed_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* t
                   int n_texts, int seq_len, float* out_dev, void* stream);
 int rag_embed_dim(rag_handle_t h, int* dim_out);
 
+/* ---- token-vector and lexical heads of the embedder (no reference counterpart: the three heads of bge-m3 - FlagEmbedding's
+ *      BGEM3FlagModel - and the ColBERT checkpoints on shapes that load: colbertv2.0 768 -> 128, answerai-colbert-small 384 -> 96).
+ *      Semantics restated from upstream, parity with upstream unpinned; x = the last hidden state [len][hidden]:
+ *        lexical   w[t] = relu(lex_w . x[t] + lex_b) for every t < len;
+ *        tokens    v[t - 1] = normalize(tok_w . x[t] + tok_b) for t = 1 ... len - 1 (row 0 dropped, the final [SEP] row kept;
+ *                  x / max(|x|, 1e-12)): a text has len - 1 rows of tok_dim floats.
+ *      rag_embed_heads_load_host attaches either head or both (a NULL matrix leaves that head as it was; both NULL: RAG_ERR_ARG) to
+ *      the embedder rag_embed_load_host loaded - RAG_ERR_STATE when there is none; a later rag_embed_load_host drops the heads.
+ *      tok_w [tok_dim][hidden], tok_b [tok_dim] or NULL (= 0), lex_w [hidden]: float32 host arrays (nn.Linear layout). tok_dim is a
+ *      multiple of 32 in [32, 1024], else RAG_ERR_ARG. Every shape that loads takes heads; behind the 384-wide MX forward the last
+ *      hidden state is rewritten into the split-fp16 layout once per call and the same head kernels run.
+ *      rag_embed_multi_*: the inputs of rag_embed_*, one forward, up to three outputs, each of which may be NULL (all NULL: RAG_ERR_ARG):
+ *        dense_out [n_texts][hidden]    exactly the bits rag_embed_* returns for the same input, load flags and options;
+ *        lex_out   [n_texts][seq_len]   float32; positions at or past the clamped length are written as 0;
+ *        tok_out   float32 rows PACKED text after text, text i = rows [row_off_out[i], row_off_out[i + 1]) = clamped len_i - 1 rows of
+ *                  tok_dim floats; tok_rows_cap = the rows tok_out holds. row_off_out [n_texts + 1] int64 is filled by the library
+ *                  (required with tok_out, optional otherwise). The library never writes a row at or past tok_rows_cap: _host returns
+ *                  RAG_ERR_ARG before any launch when the cap is too small; _dev drops the rows past it, and row_off_out[n_texts] still
+ *                  gives the true total.
+ *      An output whose head is not loaded: RAG_ERR_STATE (the handle stays usable). Length limits, length classes, chunking, lens
+ *      clamping and the invariance rule are those of rag_embed_*: every output of a text is a function of its own tokens and the
+ *      model alone, bit-identical whatever seq_len, length class, chunk split and neighbours the call has. _dev: queued on `stream`,
+ *      ordered as the other device-pointer calls; scratch belongs to the model. Against the float64 reference on seeded models (DESIGN.md
+ *      4.5): token vectors within 1e-3 per component and 1 - cos < 1e-6, lexical weights within 2e-3 * |lex_w|_1. */
+int rag_embed_heads_load_host(rag_handle_t h, const float* tok_w_host, const float* tok_b_host, int tok_dim, const float* lex_w_host,
+                              float lex_b);
+int rag_embed_multi_host(rag_handle_t h, const int32_t* input_ids_host, const int32_t* token_type_ids_host, const int32_t* lens_host,
+                         int n_texts, int seq_len, float* dense_out_host, float* lex_out_host, float* tok_out_host, int64_t tok_rows_cap,
+                         int64_t* row_off_out_host);
+int rag_embed_multi_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev,
+                        int n_texts, int seq_len, float* dense_out_dev, float* lex_out_dev, float* tok_out_dev, int64_t tok_rows_cap,
+                        int64_t* row_off_out_dev, void* stream);
+/* Late interaction (MaxSim) over packed token vectors: out[p] = (1 / nq) * sum_i max_j <q row i, d row j> over the rows
+ * [q_off[pair_q[p]], q_off[pair_q[p] + 1]) of q_vecs and [d_off[pair_d[p]], d_off[pair_d[p] + 1]) of d_vecs - the texts' own rows only;
+ * a maximum may be negative. A pair whose index lies outside its side (-1 included) or whose side has no rows gives 0. q_vecs /
+ * d_vecs: float32 [rows][dim], 16-byte aligned, dim a multiple of 32 in [32, 1024] (else RAG_ERR_ARG); q_off [n_q + 1], d_off
+ * [n_d + 1] int64, non-decreasing from >= 0 (checked by _host; _dev trusts them); pair_q / pair_d [n_pairs] int32; out [n_pairs]
+ * float32. One workgroup per pair, split-fp16 MFMA products (hi*hi + hi*lo + lo*hi): within 1e-4 of float64 on unit vectors.
+ * Deterministic: a pair's result is bit-identical from run to run and whatever other pairs the call holds. _host stages its
+ * arrays and waits; _dev is queued on `stream` and keeps nothing. */
+int rag_maxsim_host(rag_handle_t h, const float* q_vecs_host, const int64_t* q_off_host, int n_q, const float* d_vecs_host,
+                    const int64_t* d_off_host, int n_d, const int32_t* pair_q_host, const int32_t* pair_d_host, int n_pairs, int dim,
+                    float* out_host);
+int rag_maxsim_dev(rag_handle_t h, const float* q_vecs_dev, const int64_t* q_off_dev, int n_q, const float* d_vecs_dev,
+                   const int64_t* d_off_dev, int n_d, const int32_t* pair_q_dev, const int32_t* pair_d_dev, int n_pairs, int dim,
+                   float* out_dev, void* stream);
+/* Lexical match: out[p] = sum over the token ids both texts of pair p hold of (largest weight of the id in q) * (largest weight of
+ * the id in d), summed in float64 and returned as float32. ids / weights [n][L] int32 / float32 with lens [n] (clamped to [0, L]) for
+ * each side; weights <= 0 contribute nothing; the ids in skip_ids (a HOST array in both forms, n_skip <= 8 else RAG_ERR_ARG: the
+ * tokenizer's cls / eos / pad / unk) never match. A pair index outside its side gives 0. One workgroup per pair comparing ids:
+ * lq * (lq + ld) compares - a few hundred per thread for a query of 32 tokens against a passage of 255, half a million (milliseconds)
+ * for two texts of 8192 tokens, which is correct but not fast. */
+int rag_lexical_match_host(rag_handle_t h, const int32_t* q_ids_host, const float* q_weights_host, const int32_t* q_lens_host, int n_q,
+                           int q_seq_len, const int32_t* d_ids_host, const float* d_weights_host, const int32_t* d_lens_host, int n_d,
+                           int d_seq_len, const int32_t* pair_q_host, const int32_t* pair_d_host, int n_pairs,
+                           const int32_t* skip_ids_host, int n_skip, float* out_host);
+int rag_lexical_match_dev(rag_handle_t h, const int32_t* q_ids_dev, const float* q_weights_dev, const int32_t* q_lens_dev, int n_q,
+                          int q_seq_len, const int32_t* d_ids_dev, const float* d_weights_dev, const int32_t* d_lens_dev, int n_d,
+                          int d_seq_len, const int32_t* pair_q_dev, const int32_t* pair_d_dev, int n_pairs,
+                          const int32_t* skip_ids_host, int n_skip, float* out_dev, void* stream);
+
 /* ---- retrieve + rerank in one device-resident call (BASELINE.json configs[3]): the composition of
  *      HybridRetriever.retrieve (rag/retrieval.py:122-212) and CrossEncoderReranker.rerank (rag/reranker.py:320-384:
  *      pairs [query, passage], raw logits, sigmoid, sort desc, [:top_k]) with the passages' token ids resident in HBM.

@@ -139,6 +139,13 @@ _SIGS = {
     "rag_embed_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P], C.c_int),
     "rag_embed_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
     "rag_embed_dim": ([_P, C.POINTER(C.c_int)], C.c_int),
+    "rag_embed_heads_load_host": ([_P, _P, _P, C.c_int, _P, C.c_float], C.c_int),
+    "rag_embed_multi_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P], C.c_int),
+    "rag_embed_multi_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P, _P], C.c_int),
+    "rag_maxsim_host": ([_P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P], C.c_int),
+    "rag_maxsim_dev": ([_P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
+    "rag_lexical_match_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P], C.c_int),
+    "rag_lexical_match_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P], C.c_int),
     "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "rag_model_seq_limit": ([_P, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
@@ -766,6 +773,7 @@ class RagEngine:
         ptrs = (_P * len(arrs))(*[a.ctypes.data for a in arrs])
         self._check(self.lib.rag_embed_load_host(self.h, C.byref(c), ptrs, len(arrs), flags), "rag_embed_load_host")
         self.embed_hidden = int(cfg["hidden"])
+        self.embed_tok_dim = 0                                 # a load drops the heads (embed_heads_load)
 
     def model_seq_limit(self, which):
         """The longest seq_len a call on the loaded cross-encoder (which = 0) or embedder (1) may have: min(max_pos, 512 with
@@ -798,6 +806,97 @@ class RagEngine:
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
         self._check(self.lib.rag_embed_dev(self.h, C.c_void_p(input_ids.data_ptr()), C.c_void_p(token_type_ids.data_ptr()),
                                            C.c_void_p(lens.data_ptr()), n, L, C.c_void_p(out.data_ptr()), st), "rag_embed_dev")
+
+    # ---- token-vector and lexical heads of the embedder (bge-m3's three heads, ColBERT checkpoints) ------------
+    def embed_heads_load(self, tok_w=None, tok_b=None, lex_w=None, lex_b=0.0):
+        """Attach the token-vector head (tok_w [tok_dim, hidden], tok_b [tok_dim] or None) and / or the lexical head (lex_w [hidden]
+        or [1, hidden], lex_b) to the loaded embedder. A head that is not given stays as it was; embed_load drops both."""
+        tw = None if tok_w is None else _np(tok_w, np.float32)
+        tb = None if tok_b is None else _np(tok_b, np.float32).reshape(-1)
+        lw = None if lex_w is None else _np(lex_w, np.float32).reshape(-1)
+        hidden = getattr(self, "embed_hidden", None)
+        if tw is not None and (tw.ndim != 2 or (hidden is not None and tw.shape[1] != hidden) or (tb is not None and tb.shape[0] != tw.shape[0])):
+            raise RagError(f"embed_heads_load: token head of shape {tw.shape} does not fit hidden {hidden}")
+        if lw is not None and hidden is not None and lw.shape[0] != hidden:
+            raise RagError(f"embed_heads_load: lexical head of {lw.shape[0]} weights does not fit hidden {hidden}")
+        self._check(self.lib.rag_embed_heads_load_host(self.h, _ptr(tw), _ptr(tb), 0 if tw is None else tw.shape[0], _ptr(lw),
+                                                       float(np.asarray(lex_b, dtype=np.float64).reshape(-1)[0])), "rag_embed_heads_load_host")
+        if tw is not None:
+            self.embed_tok_dim = int(tw.shape[0])
+
+    def embed_multi(self, input_ids, token_type_ids, lens, dense=True, lexical=True, tokens=True, tok_rows_cap=None):
+        """One forward, up to three outputs: (dense [n, hidden] | None, lexical weights [n, L] | None, token vectors
+        [rows, tok_dim] packed text after text | None, row_off [n + 1] int64). Text i owns rows row_off[i]:row_off[i + 1]
+        (clamped len - 1 of them). tok_rows_cap (default: exactly what the call needs) below that is an error."""
+        ids, tt, ln = _np(input_ids, np.int32), _np(token_type_ids, np.int32), _np(lens, np.int32)
+        n, L = ids.shape
+        d = np.empty((n, self.embed_hidden), dtype=np.float32) if dense else None
+        lx = np.empty((n, L), dtype=np.float32) if lexical else None
+        tk = None
+        cap = 0
+        if tokens:
+            cap = int((np.clip(ln, 1, L).astype(np.int64) - 1).sum()) if tok_rows_cap is None else int(tok_rows_cap)
+            tk = np.empty((cap, int(getattr(self, "embed_tok_dim", 0))), dtype=np.float32)
+        off = np.empty((n + 1,), dtype=np.int64)
+        self._check(self.lib.rag_embed_multi_host(self.h, _ptr(ids), _ptr(tt), _ptr(ln), n, L, _ptr(d), _ptr(lx), _ptr(tk), cap, _ptr(off)),
+                    "rag_embed_multi_host")
+        if tk is not None:
+            tk = tk[:int(off[n])]
+        return d, lx, tk, off
+
+    def embed_multi_dev(self, input_ids, token_type_ids, lens, dense=None, lex=None, tok=None, row_off=None, stream=None):
+        """int32 CUDA tensors [n, L], [n, L], [n] -> whichever of dense [n, hidden], lex [n, L], tok [cap, tok_dim] float32 and
+        row_off [n + 1] int64 CUDA tensors are given; asynchronous on `stream`. Token rows past tok's capacity are dropped and
+        row_off[n] still holds the true total."""
+        import torch
+        n, L = input_ids.shape
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_embed_multi_dev(self.h, p(input_ids), p(token_type_ids), p(lens), n, L, p(dense), p(lex), p(tok),
+                                                 0 if tok is None else int(tok.shape[0]), p(row_off), st), "rag_embed_multi_dev")
+
+    def maxsim(self, q_vecs, q_off, d_vecs, d_off, pair_q, pair_d):
+        """Late interaction over packed float32 token vectors: out[p] = mean over the rows of query pair_q[p] of the largest dot
+        with a row of document pair_d[p]; 0 for an index outside its side or an empty side. Returns float32 [n_pairs]."""
+        q, d = _np(q_vecs, np.float32), _np(d_vecs, np.float32)
+        qo, do = _np(q_off, np.int64), _np(d_off, np.int64)
+        pq, pd = _np(pair_q, np.int32), _np(pair_d, np.int32)
+        dim = q.shape[1] if q.ndim == 2 and q.shape[0] else d.shape[1]
+        out = np.zeros((pq.shape[0],), dtype=np.float32)
+        self._check(self.lib.rag_maxsim_host(self.h, _ptr(q), _ptr(qo), qo.shape[0] - 1, _ptr(d), _ptr(do), do.shape[0] - 1, _ptr(pq), _ptr(pd),
+                                             pq.shape[0], int(dim), _ptr(out)), "rag_maxsim_host")
+        return out
+
+    def maxsim_dev(self, q_vecs, q_off, d_vecs, d_off, pair_q, pair_d, out, stream=None):
+        """CUDA tensors: float32 [rows, dim] vectors, int64 offsets, int32 pairs -> float32 out [n_pairs]; asynchronous on `stream`."""
+        import torch
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_maxsim_dev(self.h, p(q_vecs), p(q_off), q_off.shape[0] - 1, p(d_vecs), p(d_off), d_off.shape[0] - 1, p(pair_q),
+                                            p(pair_d), pair_q.shape[0], int(q_vecs.shape[1]), p(out), st), "rag_maxsim_dev")
+
+    def lexical_match(self, q_ids, q_weights, q_lens, d_ids, d_weights, d_lens, pair_q, pair_d, skip_ids=()):
+        """Lexical match of pairs: sum over shared token ids of (largest weight in q) * (largest weight in d); weights <= 0 and the
+        ids in skip_ids (at most 8) contribute nothing. ids / weights [n, L], lens [n] per side. Returns float32 [n_pairs]."""
+        qi, qw, ql = _np(q_ids, np.int32), _np(q_weights, np.float32), _np(q_lens, np.int32)
+        di, dw, dl = _np(d_ids, np.int32), _np(d_weights, np.float32), _np(d_lens, np.int32)
+        pq, pd = _np(pair_q, np.int32), _np(pair_d, np.int32)
+        sk = _np(list(skip_ids), np.int32)
+        out = np.zeros((pq.shape[0],), dtype=np.float32)
+        self._check(self.lib.rag_lexical_match_host(self.h, _ptr(qi), _ptr(qw), _ptr(ql), qi.shape[0], qi.shape[1], _ptr(di), _ptr(dw), _ptr(dl),
+                                                    di.shape[0], di.shape[1], _ptr(pq), _ptr(pd), pq.shape[0], _ptr(sk), sk.shape[0], _ptr(out)),
+                    "rag_lexical_match_host")
+        return out
+
+    def lexical_match_dev(self, q_ids, q_weights, q_lens, d_ids, d_weights, d_lens, pair_q, pair_d, out, skip_ids=(), stream=None):
+        """The same on CUDA tensors (skip_ids stays a host sequence); float32 out [n_pairs], asynchronous on `stream`."""
+        import torch
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        sk = _np(list(skip_ids), np.int32)
+        self._check(self.lib.rag_lexical_match_dev(self.h, p(q_ids), p(q_weights), p(q_lens), q_ids.shape[0], q_ids.shape[1], p(d_ids),
+                                                   p(d_weights), p(d_lens), d_ids.shape[0], d_ids.shape[1], p(pair_q), p(pair_d),
+                                                   pair_q.shape[0], _ptr(sk), sk.shape[0], p(out), st), "rag_lexical_match_dev")
 
     def tokens_load(self, tokens, lens, id_bits=16):
         """Passage token store: tokens [N, L] int32 token ids without [CLS]/[SEP], lens [N]; row-aligned with the index.

@@ -114,6 +114,46 @@ def load_tokenizer(path):
     return BertWordPieceTokenizer(os.path.join(path, "vocab.txt"), lowercase=lower)
 
 
+M3_HEAD_FILES = {"tok": "colbert_linear.pt", "lex": "sparse_linear.pt"}
+
+
+def load_m3_heads(path, hidden=None):
+    """The optional heads beside model.safetensors in a bge-m3-style directory: colbert_linear.pt (token vectors, nn.Linear hidden ->
+    tok_dim) and sparse_linear.pt (lexical weights, nn.Linear hidden -> 1), each a torch state dict holding `weight` and maybe
+    `bias`. Pure: no engine. Returns dict(tok_w [tok_dim, hidden] | None, tok_b [tok_dim] | None, lex_w [hidden] | None, lex_b float)
+    as float32 numpy; a file that is not there leaves its entries None. hidden defaults to config.json's hidden_size.
+    ValueError naming the file: a weight whose shape does not fit hidden, a tok_dim that is no multiple of 32 in [32, 1024]."""
+    if hidden is None:
+        with open(os.path.join(path, "config.json")) as f:
+            hidden = json.load(f)["hidden_size"]
+    hidden = int(hidden)
+    out = dict(tok_w=None, tok_b=None, lex_w=None, lex_b=0.0)
+    for kind, name in M3_HEAD_FILES.items():
+        fp = os.path.join(path, name)
+        if not os.path.exists(fp):
+            continue
+        import torch
+        sd = torch.load(fp, map_location="cpu", weights_only=True)
+        if "weight" not in sd:
+            raise ValueError(f"{fp}: no `weight` in the state dict")
+        w = np.ascontiguousarray(sd["weight"].detach().to(torch.float32).numpy())
+        b = sd.get("bias")
+        b = None if b is None else np.ascontiguousarray(b.detach().to(torch.float32).numpy()).reshape(-1)
+        if w.ndim != 2 or w.shape[1] != hidden:
+            raise ValueError(f"{fp}: weight of shape {tuple(w.shape)} does not fit hidden {hidden}")
+        if b is not None and b.shape[0] != w.shape[0]:
+            raise ValueError(f"{fp}: bias of {b.shape[0]} entries does not fit weight of shape {tuple(w.shape)}")
+        if kind == "tok":
+            if w.shape[0] % 32 or not 32 <= w.shape[0] <= 1024:
+                raise ValueError(f"{fp}: token dimension {w.shape[0]} is not a multiple of 32 in [32, 1024]")
+            out["tok_w"], out["tok_b"] = w, b
+        else:
+            if w.shape[0] != 1:
+                raise ValueError(f"{fp}: weight of shape {tuple(w.shape)} is not one row of {hidden}")
+            out["lex_w"], out["lex_b"] = w[0].copy(), 0.0 if b is None else float(b[0])
+    return out
+
+
 MINILM_L6_CONFIG = dict(vocab_size=30522, hidden=384, layers=6, heads=12, ffn=1536, max_pos=512, type_vocab=2, eps=1e-12)
 """Shape of cross-encoder/ms-marco-MiniLM-L-6-v2 (the checkpoint the reference names at config.py:49), for benchmarks
 that run without the downloaded weights; a real deployment takes the shape from the checkpoint's config.json."""

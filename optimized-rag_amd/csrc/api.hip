@@ -837,6 +837,64 @@ int rag_embed_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, const i
     return embed_run(h, ids, tt, lens, n_texts, L, out, (hipStream_t)stream, false);
 }
 
+int rag_embed_heads_load_host(rag_handle_t h, const float* tok_w, const float* tok_b, int tok_dim, const float* lex_w, float lex_b) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return embed_heads_load_host(h, tok_w, tok_b, tok_dim, lex_w, lex_b);
+}
+
+int rag_embed_multi_host(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int n_texts, int L, float* dense_out,
+                         float* lex_out, float* tok_out, int64_t tok_rows_cap, int64_t* row_off_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return embed_multi_host(h, ids, tt, lens, n_texts, L, dense_out, lex_out, tok_out, tok_rows_cap, row_off_out);
+}
+
+int rag_embed_multi_dev(rag_handle_t h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int n_texts, int L, float* dense_out,
+                        float* lex_out, float* tok_out, int64_t tok_rows_cap, int64_t* row_off_out, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return embed_multi_dev(h, ids, tt, lens, n_texts, L, dense_out, lex_out, tok_out, tok_rows_cap, row_off_out, (hipStream_t)stream);
+}
+
+int rag_maxsim_host(rag_handle_t h, const float* q_vecs, const int64_t* q_off, int n_q, const float* d_vecs, const int64_t* d_off, int n_d,
+                    const int32_t* pair_q, const int32_t* pair_d, int n_pairs, int dim, float* out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return maxsim_host(h, q_vecs, q_off, n_q, d_vecs, d_off, n_d, pair_q, pair_d, n_pairs, dim, out);
+}
+
+int rag_maxsim_dev(rag_handle_t h, const float* q_vecs, const int64_t* q_off, int n_q, const float* d_vecs, const int64_t* d_off, int n_d,
+                   const int32_t* pair_q, const int32_t* pair_d, int n_pairs, int dim, float* out, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return maxsim_dev(h, q_vecs, q_off, n_q, d_vecs, d_off, n_d, pair_q, pair_d, n_pairs, dim, out, (hipStream_t)stream);
+}
+
+int rag_lexical_match_host(rag_handle_t h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq,
+                           const int32_t* d_ids, const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q,
+                           const int32_t* pair_d, int n_pairs, const int32_t* skip_ids, int n_skip, float* out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return lexical_match_host(h, q_ids, q_w, q_lens, n_q, Lq, d_ids, d_w, d_lens, n_d, Ld, pair_q, pair_d, n_pairs, skip_ids, n_skip, out);
+}
+
+int rag_lexical_match_dev(rag_handle_t h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq,
+                          const int32_t* d_ids, const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q,
+                          const int32_t* pair_d, int n_pairs, const int32_t* skip_ids_host, int n_skip, float* out, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return lexical_match_dev(h, q_ids, q_w, q_lens, n_q, Lq, d_ids, d_w, d_lens, n_d, Ld, pair_q, pair_d, n_pairs, skip_ids_host, n_skip, out,
+                             (hipStream_t)stream);
+}
+
 int rag_ce_length_class(int head_dim, int seq_len, int* class_out) {
     const int c = ce_length_class(head_dim, seq_len);
     if (!class_out || c == 0) return RAG_ERR_ARG;

@@ -202,6 +202,7 @@ struct rag_ctx : rag_device_mem {
     int attr_ce_attn_lds[2][3] = {};
     int attr_ce_attn64_lds = 0;              // the LDS-staged instance of ce_attention64_kernel (64-wide heads)
     int attr_ce_attn64s_lds = 0;             // its streamed instance (the length classes above 512)
+    int attr_m3_gemm_lds = 0;                // the split GEMM with the fp32 epilogue (the embedder's token-vector head)
     rag_ce_model* ce = nullptr;
     rag_ce_model* emb = nullptr;             // sentence-embedding encoder (rag_embed_load_host): the K7 kernels behind a mean-pooling head
 };
@@ -429,3 +430,20 @@ int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* te
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
               bool host_ptrs);
 int embed_dim(const rag_ctx* h);
+// the embedder's optional token-vector and lexical heads, and one forward with up to three outputs (cross_encoder.hip)
+int embed_heads_load_host(rag_ctx* h, const float* tok_w, const float* tok_b, int tok_dim, const float* lex_w, float lex_b);
+int embed_multi_host(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* dense, float* lex, float* tok,
+                     int64_t tok_rows_cap, int64_t* row_off);
+int embed_multi_dev(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* dense, float* lex, float* tok,
+                    int64_t tok_rows_cap, int64_t* row_off, hipStream_t st);
+// m3_heads.hip: pair scores over the heads' outputs
+int maxsim_host(rag_ctx* h, const float* q, const int64_t* q_off, int n_q, const float* d, const int64_t* d_off, int n_d, const int32_t* pair_q,
+                const int32_t* pair_d, int n_pairs, int dim, float* out);
+int maxsim_dev(rag_ctx* h, const float* q, const int64_t* q_off, int n_q, const float* d, const int64_t* d_off, int n_d, const int32_t* pair_q,
+               const int32_t* pair_d, int n_pairs, int dim, float* out, hipStream_t st);
+int lexical_match_host(rag_ctx* h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq, const int32_t* d_ids,
+                       const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q, const int32_t* pair_d, int n_pairs,
+                       const int32_t* skip_ids, int n_skip, float* out);
+int lexical_match_dev(rag_ctx* h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq, const int32_t* d_ids,
+                      const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q, const int32_t* pair_d, int n_pairs,
+                      const int32_t* skip_ids_host, int n_skip, float* out, hipStream_t st);

@@ -30,6 +30,8 @@
 //   ce_layernorm       one wave per token (384 = 6/lane), fp32 statistics, eps from config
 //   ce_pool_classify   tanh(Wp.x_cls + bp) -> wc.pooled + bc, fp32
 //   ce_meanpool        embedding head: mean over the real tokens, or the [CLS] row; optional L2 normalisation
+//   m3_*               the embedder's optional token-vector and lexical heads (rag_embed_multi_*): ce_gemm<EPI_F32> over the last
+//                      hidden state, then normalise + scatter to packed rows; one dot per row for the lexical weights
 // One layer, in launch order: QKV GEMM, attention, out-projection GEMM (bias + residual -> fp32) + LayerNorm, FFN-up GEMM
 // (bias + GELU) + FFN-down GEMM (bias + residual -> fp32) + LayerNorm. These split-fp16 kernels run every model whose shape
 // the MX forward (ce_mx.h: hi16 + lo8 operands, hidden 384) does not take, classifiers whose load-time probe saw MX miss
@@ -73,8 +75,30 @@ struct ce_mx_ws : ce_ws_base {
     dev_buf<half_t> qf16, kf16, vf16;                  // Q, K, V in the attention kernel's fragment order (hi | lo planes)
 };
 
+// The optional heads of an embedder (rag_embed_heads_load_host) and what one rag_embed_multi_* call asks of them.
+struct ce_heads {
+    int tok_dim = 0, tok_pad = 0;                      // token head: output width, and that width rounded up to the GEMM's 128-feature tile
+    dev_buf<half_t> tok_w;                             // [tok_pad][hidden] split fp16, rows past tok_dim zero
+    dev_buf<float> tok_b;                              // [tok_pad], zero where the checkpoint has no bias
+    dev_buf<float> lex_w;                              // [hidden] fp32 (empty: no lexical head)
+    float lex_b = 0.f;
+    // scratch of a multi call, sized with the forward's workspace: the MX forward's last hidden state in the split layout, and
+    // the token head's rows before normalisation (fp32 [tokens][tok_pad])
+    dev_buf<half_t> x16;
+    dev_buf<float> raw;
+    int64_t x16_tokens = 0, raw_tokens = 0;
+};
+// lex / tok: the call's outputs (device, or null); row_off [P + 1] = the packed row each text's token vectors start at
+struct ce_multi {
+    float* lex;
+    float* tok;
+    int64_t* row_off;                                  // written by the call itself (m3_row_off_kernel) before its first chunk
+    int64_t tok_cap;
+};
+
 struct rag_ce_model {
     rag_ce_config cfg;
+    ce_heads heads;
     bool embed = false;          // true: sentence-embedding encoder (mean or [CLS] pooling over the tokens, no pooler / classifier head)
     int normalize = 1;           // embed: L2-normalise the pooled vectors
     int pool_cls = 0;            // embed: pool by the [CLS] row (the last hidden state of row 0) instead of the mean
@@ -111,7 +135,8 @@ struct rag_ce_model {
 #define CE_EPI_PLANE16 (16 * 144)                         // one fp16 plane of a 16-token x 64-feature epilogue pass, rows padded to 144 B
 
 // EPI_QKV64: the QKV epilogue of a model with 64-wide heads (K and V fragment tiles of ce_attention64_kernel)
-enum { EPI_QKV = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_QKV64 = 3 };
+// EPI_F32: bias -> fp32 [token][N] with no residual (the token-vector head of the embedder, before its normalisation)
+enum { EPI_QKV = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_QKV64 = 3, EPI_F32 = 4 };
 
 __device__ __forceinline__ void store_split4(half_t* __restrict__ p, size_t plane, float v0, float v1, float v2, float v3) {
     const half4 hi = {(half_t)v0, (half_t)v1, (half_t)v2, (half_t)v3};
@@ -287,7 +312,7 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
         // outputs are streamed with non-temporal stores: they are read again only by a later kernel (GBs later), and as
         // ordinary stores they pushed the shared token tile and the weights out of the XCD's 4 MiB L2
         char* wl = smem + ((sbase + nt + 2) % 3) * CE_STAGE_BYTES + wid * CE_EPI_WAVE_BYTES;
-        if (EPI == EPI_RESID) {
+        if (EPI == EPI_RESID || EPI == EPI_F32) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                       // fp32 [16 tokens][64 features], row stride 272 B
 #pragma unroll
@@ -301,6 +326,10 @@ __global__ __launch_bounds__(512) void ce_gemm_kernel(const half_t* __restrict__
                     const int row = it * 4 + rr;
                     const float4 v = *reinterpret_cast<const float4*>(wl + row * 272 + cc * 16);
                     const size_t g = (size_t)(mb + j * 16 + row) * N + nb + cc * 4;
+                    if (EPI == EPI_F32) {
+                        __builtin_nontemporal_store((f32x4){v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(out32 + g));
+                        continue;
+                    }
                     const half_t* rp = resid + (size_t)(mb + j * 16 + row) * 2 * N + SPLIT_IDX(nb + cc * 4);      // residual = hi + lo
                     const half4 rh = *reinterpret_cast<const half4*>(rp), rl = *reinterpret_cast<const half4*>(rp + 32);
                     __builtin_nontemporal_store((f32x4){v.x + ((float)rh[0] + (float)rl[0]), v.y + ((float)rh[1] + (float)rl[1]),
@@ -1141,6 +1170,99 @@ __global__ void ce_f32_split_kernel(const float* __restrict__ in, half_t* __rest
     }
 }
 
+// ---- token-vector and lexical heads of the embedder (rag_embed_multi_*; the three-headed bge-m3, the ColBERT checkpoints). Both read
+// the last hidden state in the split layout, one wave per row, float32 sums in a fixed order: a row's outputs depend on that row alone.
+// The MX forward's last hidden state is first rewritten from its image into the split layout (hi = fp16(x), lo = fp16(x - hi)).
+__global__ void m3_mx_to_split_kernel(const char* __restrict__ x8, const int32_t* __restrict__ m_packed, int hidden, half_t* __restrict__ x16) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)m_packed[0] * hidden) return;
+    const int64_t row = i / hidden;
+    const int c = (int)(i % hidden);
+    const float v = mx_load_elem(x8, row, c, hidden >> 5);
+    const half_t hi = (half_t)v;
+    half_t* o = x16 + row * 2 * hidden + SPLIT_IDX(c);
+    o[0] = hi;
+    o[32] = (half_t)(v - (float)hi);
+}
+
+// row_off[p] = sum over the texts before p of (clamped length - 1): where text p's token vectors start in the packed output;
+// row_off[P] = the call's true total. The lengths are clamped as ce_pack_scan_kernel clamps them.
+__global__ __launch_bounds__(1024) void m3_row_off_kernel(const int32_t* __restrict__ lens, int P, int L_in, int64_t* __restrict__ row_off) {
+    __shared__ long long part[1024];
+    const int tid = threadIdx.x;
+    const int per = (P + 1023) / 1024;
+    const int b = min(P, tid * per), e = min(P, b + per);
+    long long s = 0;
+    for (int p = b; p < e; ++p) s += max(1, min(lens[p], L_in)) - 1;
+    part[tid] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const long long v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    long long off = part[tid] - s;
+    for (int p = b; p < e; ++p) {
+        row_off[p] = off;
+        off += max(1, min(lens[p], L_in)) - 1;
+    }
+    if (tid == 1023) row_off[P] = part[1023];
+}
+
+// lexical head: out[p][t] = relu(lex_w . x[t] + lex_b) for t < len, 0 for len <= t < L_in. One wave per (text, position).
+__global__ __launch_bounds__(256) void m3_lexical_kernel(const half_t* __restrict__ x16, const int32_t* __restrict__ pair_off,
+                                                          const int32_t* __restrict__ clen, int P, int L_in, int hidden,
+                                                          const float* __restrict__ lex_w, float lex_b, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= (int64_t)P * L_in) return;
+    const int p = (int)(idx / L_in), t = (int)(idx % L_in);
+    if (t >= clen[p]) {
+        if (lane == 0) out[idx] = 0.f;
+        return;
+    }
+    const half_t* r = x16 + ((size_t)pair_off[p] + t) * 2 * hidden;
+    float s = 0.f;
+    for (int c = lane; c < hidden; c += 64) s += ((float)r[SPLIT_IDX(c)] + (float)r[SPLIT_IDX(c) + 32]) * lex_w[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) out[idx] = fmaxf(s + lex_b, 0.f);
+}
+
+// token head, after its GEMM (raw = tok_W . x + tok_b, fp32 [packed row][tok_pad]): row t >= 1 of a text is L2-normalised
+// (x / max(|x|, 1e-12)) and written to packed output row row_off[text] + t - 1; row 0 ([CLS]), the pad rows behind a length that is
+// no multiple of 16 and every row at or past `cap` are skipped. One wave per packed row, tok_dim <= 1024 = 16 values per lane.
+__global__ __launch_bounds__(256) void m3_tok_scatter_kernel(const float* __restrict__ raw, int tok_pad, int tok_dim,
+                                                              const int32_t* __restrict__ m_packed, const int32_t* __restrict__ row_pair,
+                                                              const int32_t* __restrict__ pair_off, const int32_t* __restrict__ clen,
+                                                              const int64_t* __restrict__ row_off, int64_t cap, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= m_packed[0]) return;
+    const int pr = row_pair[row];
+    const int t = (int)row - pair_off[pr];
+    if (t < 1 || t >= clen[pr]) return;
+    const int64_t dst = row_off[pr] + t - 1;
+    if (dst >= cap) return;
+    float v[16];
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int c = lane + i * 64;
+        v[i] = c < tok_dim ? raw[(size_t)row * tok_pad + c] : 0.f;
+        sq += v[i] * v[i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    const float sc = 1.0f / fmaxf(sqrtf(sq), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int c = lane + i * 64;
+        if (c < tok_dim) out[(size_t)dst * tok_dim + c] = v[i] * sc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side (launch() and raise_lds() are common.h's).
 // ------------------------------------------------------------------------------------------------
@@ -1323,6 +1445,12 @@ struct ce_chunk {
     const int32_t *ids, *tt, *lens;
     float* out;
     int P, L_in, L;
+    // rag_embed_multi_* alone (then `out` may be null: no pooled vector asked for): the chunk's [P][L_in] lexical weights, the
+    // call's packed token vectors with the chunk's slice of the row offsets, each null when not asked for
+    float* lex = nullptr;
+    float* tok = nullptr;
+    const int64_t* row_off = nullptr;
+    int64_t tok_cap = 0;
 };
 
 // pads [P][L_in] token arrays to the supported attention length L (>= L_in), pad id 0 / type 0
@@ -1447,6 +1575,25 @@ static void ce_gemm(rag_ctx* h, const rag_ce_model* m, hipStream_t st, const hal
            m->cfg.hidden, m->cfg.heads, w.io.m_packed, (int)w.tokens);
 }
 
+// The heads of one chunk on its last hidden state x16 (split layout; w = the workspace of the forward that ran). Lexical: one dot
+// per (text, position). Token vectors: the split-fp16 GEMM with the fp32 epilogue over all packed rows, then normalise + scatter.
+static int heads_chunk(rag_ctx* h, rag_ce_model* m, const ce_ws_base& w, const half_t* x16, const ce_chunk& c, hipStream_t st) {
+    ce_heads& hd = m->heads;
+    const ce_chunk_bufs& io = w.io;
+    const int H = m->cfg.hidden;
+    if (c.lex)
+        launch(m3_lexical_kernel, dim3((unsigned)(((int64_t)c.P * c.L_in + 3) / 4)), dim3(256), 0, st, x16, io.pair_off, io.clen, c.P, c.L_in, H,
+               hd.lex_w, hd.lex_b, c.lex);
+    if (c.tok) {
+        if (int rc = raise_lds(h, h->attr_m3_gemm_lds, CE_GEMM_LDS, ce_gemm_kernel<EPI_F32>)) return rc;
+        launch(ce_gemm_kernel<EPI_F32>, dim3(ce_gemm_grid(h)), dim3(512), CE_GEMM_LDS, st, hd.tok_w, x16, hd.tok_pad, H, hd.tok_b, nullptr, hd.raw,
+               nullptr, nullptr, nullptr, (size_t)0, H, m->cfg.heads, io.m_packed, (int)w.tokens);
+        launch(m3_tok_scatter_kernel, dim3((unsigned)(((int64_t)c.P * c.L + 3) / 4)), dim3(256), 0, st, hd.raw, hd.tok_pad, hd.tok_dim, io.m_packed,
+               io.row_pair, io.pair_off, io.clen, c.row_off, c.tok_cap, c.tok);
+    }
+    return RAG_OK;
+}
+
 static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipStream_t st) {
     ce_split_ws& w = m->split;                                         // plane strides follow the ALLOCATED size (w.tokens)
     const ce_chunk_bufs& io = w.io;
@@ -1480,9 +1627,11 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
         ce_gemm<EPI_RESID>(h, m, st, ly.w2, w.h16, H, F, ly.b2, w.x16, w.y32, nullptr);
         if ((rc = ce_layernorm(h, m, ly.ln2_g, ly.ln2_b, M, st))) return rc;
     }
-    if (m->embed)
-        launch(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, io.pair_off, io.clen, L, H, m->normalize, m->pool_cls, c.out);
-    else
+    if (m->embed) {
+        if (c.out) launch(ce_meanpool_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, io.pair_off, io.clen, L, H, m->normalize, m->pool_cls, c.out);
+        if (c.lex || c.tok)
+            if ((rc = heads_chunk(h, m, w, w.x16, c, st))) return rc;
+    } else
         launch(ce_pool_classify_kernel<false>, dim3(P), dim3(256), 0, st, w.x16, m->wp, m->bp, m->wc, m->bc, io.pair_off, H, c.out);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
@@ -1579,10 +1728,15 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     }
     // head. After a [CLS] tail the classifier's rows are the compact tensor (row p = pair p), else row pair_off[p] of the stream.
     const char* const cls = cls_tail ? w.xc8 : w.x8;
-    if (m->embed)
-        launch(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), io.pair_off, io.clen, L, H,
-               m->normalize, m->pool_cls, c.out);
-    else if (cls_tail && P >= 512)
+    if (m->embed) {
+        if (c.out)
+            launch(ce_meanpool_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(w.x8.get()), io.pair_off, io.clen, L, H,
+                   m->normalize, m->pool_cls, c.out);
+        if (c.lex || c.tok) {                                          // the heads read the split layout: rewrite the final image once
+            launch(m3_mx_to_split_kernel, dim3((unsigned)(((int64_t)P * L * H + 255) / 256)), dim3(256), 0, st, w.x8, io.m_packed, H, m->heads.x16);
+            if ((rc = heads_chunk(h, m, w, m->heads.x16, c, st))) return rc;
+        }
+    } else if (cls_tail && P >= 512)
         // the batched pooler pays from ~512 pairs on; a single query's 100 pairs fill more CUs with one workgroup per pair
         launch(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, cls, m->wpT, m->bp, m->wc, m->bc, P, H, c.out);
     else
@@ -1600,10 +1754,31 @@ static bool ce_use_mx(const rag_ctx* h, const rag_ce_model* m) {
     return m->mx_ok && (h->opt.ce_mx > 0 || (h->opt.ce_mx == 0 && m->mx_default));
 }
 
+// Scratch of the heads for a workspace of `tokens` padded rows (a reallocation waits for st first, as ws_renew does)
+static int heads_ensure_ws(rag_ctx* h, rag_ce_model* m, int64_t tokens, bool use_mx, bool tok, hipStream_t st) {
+    ce_heads& hd = m->heads;
+    const size_t H = m->cfg.hidden;
+    int rc;
+    if (use_mx && hd.x16_tokens != tokens) {
+        HIP_TRY(h, hipStreamSynchronize(st));
+        hd.x16_tokens = 0;
+        if ((rc = alloc_zeroed(h, hd.x16, 2 * (size_t)tokens * H, st))) return rc;      // rows past the packed rows are GEMM operands: finite
+        hd.x16_tokens = tokens;
+    }
+    if (tok && hd.raw_tokens != tokens) {
+        HIP_TRY(h, hipStreamSynchronize(st));
+        hd.raw_tokens = 0;
+        if ((rc = hd.raw.alloc(h, (size_t)tokens * hd.tok_pad))) return rc;
+        hd.raw_tokens = tokens;
+    }
+    return RAG_OK;
+}
+
 // out: [P][m->out_width] floats (logits of a cross-encoder, pooled vectors of an embedding model)
 static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* out,
-                  hipStream_t st, bool host_ptrs, bool use_mx) {
-    ARG_CHECK(h, ids && tt && lens && out && P > 0 && L_in > 0, "ce_score: bad arguments");
+                  hipStream_t st, bool host_ptrs, bool use_mx, const ce_multi* mo = nullptr) {
+    // mo (rag_embed_multi_*, device pointers only): the heads' outputs beside `out`, which may then be null
+    ARG_CHECK(h, ids && tt && lens && (out || mo) && P > 0 && L_in > 0 && !(mo && host_ptrs), "ce_score: bad arguments");
     const size_t ow = (size_t)m->out_width;
     // the cut is made here, per call, never at load: min(max_pos, 512 with 32-wide heads, 8192 with 64-wide heads)
     if (L_in > ce_seq_limit(m)) {
@@ -1627,13 +1802,23 @@ static int ce_run(rag_ctx* h, rag_ce_model* m, const int32_t* ids, const int32_t
     const auto forward_chunk = use_mx ? mx_forward_chunk : ce_forward_chunk;
     int rc = ensure_ws(h, m, chunk, L, st);
     if (rc) return rc;
+    if (mo) {
+        if ((rc = heads_ensure_ws(h, m, use_mx ? m->mx.tokens : m->split.tokens, use_mx, mo->tok != nullptr, st))) return rc;
+        if (mo->row_off) launch(m3_row_off_kernel, dim3(1), dim3(1024), 0, st, lens, P, L_in, mo->row_off);
+    }
     const hipMemcpyKind kin = hipMemcpyHostToDevice, kout = hipMemcpyDeviceToHost;
     if ((rc = prof_begin(h, 2, st))) return rc;
     for (int p0 = 0; p0 < P; p0 += chunk) {
         const int pc = std::min(chunk, P - p0);
         // host arrays are staged chunk by chunk; device arrays are read (ids, lens) and written (logits) where they are: four
         // small copies less per chunk, 45 us of a single-query call
-        ce_chunk c = {ids + (size_t)p0 * L_in, tt + (size_t)p0 * L_in, lens + p0, out + (size_t)p0 * ow, pc, L_in, L};
+        ce_chunk c = {ids + (size_t)p0 * L_in, tt + (size_t)p0 * L_in, lens + p0, out ? out + (size_t)p0 * ow : nullptr, pc, L_in, L};
+        if (mo) {
+            c.lex = mo->lex ? mo->lex + (size_t)p0 * L_in : nullptr;
+            c.tok = mo->tok;
+            c.row_off = mo->row_off ? mo->row_off + p0 : nullptr;
+            c.tok_cap = mo->tok_cap;
+        }
         if (host_ptrs) {
             HIP_TRY(h, hipMemcpyAsync(io.sid, c.ids, (size_t)pc * L_in * 4, kin, st));
             HIP_TRY(h, hipMemcpyAsync(io.stt, c.tt, (size_t)pc * L_in * 4, kin, st));
@@ -1666,6 +1851,110 @@ int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* 
               bool host_ptrs) {
     ARG_CHECK(h, h->emb != nullptr, "no embedding model loaded");
     return ce_run(h, h->emb, ids, tt, lens, P, L_in, out, st, host_ptrs, ce_use_mx(h, h->emb));
+}
+
+// ---- the embedder's optional heads ---------------------------------------------------------------------------------------
+// tok_w [tok_dim][hidden] (+ tok_b [tok_dim] or null = 0) and / or lex_w [hidden] (+ lex_b): float32 host arrays. The token matrix
+// is stored in the GEMM's split layout with its rows zero-padded to a multiple of 128 (one feature tile). A head that is not
+// given stays as it was.
+int embed_heads_load_host(rag_ctx* h, const float* tok_w, const float* tok_b, int tok_dim, const float* lex_w, float lex_b) {
+    if (!h->emb) {
+        h->err = "embed_heads_load: no embedding model loaded";
+        return RAG_ERR_STATE;
+    }
+    ARG_CHECK(h, tok_w || lex_w, "embed_heads_load: neither head given");
+    ARG_CHECK(h, !tok_w || (tok_dim >= 32 && tok_dim <= 1024 && tok_dim % 32 == 0), "embed_heads_load: tok_dim must be a multiple of 32 in [32, 1024]");
+    rag_ce_model* m = h->emb;
+    ce_heads& hd = m->heads;
+    const size_t H = m->cfg.hidden;
+    int rc;
+    if (tok_w) {
+        const int pad = (int)round_up(tok_dim, CE_BM);
+        std::vector<float> wp((size_t)pad * H, 0.f), bp((size_t)pad, 0.f);
+        std::memcpy(wp.data(), tok_w, (size_t)tok_dim * H * sizeof(float));
+        if (tok_b) std::memcpy(bp.data(), tok_b, (size_t)tok_dim * sizeof(float));
+        hd.tok_dim = hd.tok_pad = 0;
+        hd.raw = dev_buf<float>();
+        hd.raw_tokens = 0;
+        dev_buf<char> none;
+        if ((rc = up_weight(h, {wp.data()}, (size_t)pad, H, hd.tok_w, none, false))) return rc;      // waits: wp may go
+        if ((rc = up_f32(h, bp.data(), (size_t)pad, hd.tok_b))) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        hd.tok_dim = tok_dim;
+        hd.tok_pad = pad;
+    }
+    if (lex_w) {
+        hd.lex_w = dev_buf<float>();
+        dev_buf<float> w;
+        if ((rc = up_f32(h, lex_w, H, w))) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        hd.lex_w = std::move(w);
+        hd.lex_b = lex_b;
+    }
+    return RAG_OK;
+}
+
+// One forward, up to three outputs (each may be null). Device pointers, queued on st. row_off_out [P + 1] is filled whenever it is
+// given; rows at or past tok_rows_cap are dropped.
+static int embed_multi_dev_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* dense, float* lex,
+                               float* tok, int64_t tok_rows_cap, int64_t* row_off, hipStream_t st) {
+    rag_ce_model* m = h->emb;
+    ce_multi mo = {lex, tok, row_off, tok_rows_cap};
+    return ce_run(h, m, ids, tt, lens, P, L_in, dense, st, false, ce_use_mx(h, m), &mo);
+}
+
+static int embed_multi_check(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, const float* dense,
+                             const float* lex, const float* tok, int64_t tok_rows_cap, const int64_t* row_off) {
+    ARG_CHECK(h, ids && tt && lens && P > 0 && L_in > 0, "embed_multi: bad arguments");
+    ARG_CHECK(h, dense || lex || tok, "embed_multi: no output asked for");
+    ARG_CHECK(h, !tok || (row_off && tok_rows_cap >= 0), "embed_multi: token vectors need row_off_out and a capacity >= 0");
+    if (!h->emb) {
+        h->err = "embed_multi: no embedding model loaded";
+        return RAG_ERR_STATE;
+    }
+    if ((tok && h->emb->heads.tok_dim == 0) || (lex && !h->emb->heads.lex_w)) {
+        h->err = std::string("embed_multi: the ") + (tok && h->emb->heads.tok_dim == 0 ? "token-vector" : "lexical") + " head is not loaded (rag_embed_heads_load_host)";
+        return RAG_ERR_STATE;
+    }
+    return RAG_OK;
+}
+
+int embed_multi_dev(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* dense, float* lex, float* tok,
+                    int64_t tok_rows_cap, int64_t* row_off, hipStream_t st) {
+    if (int rc = embed_multi_check(h, ids, tt, lens, P, L_in, dense, lex, tok, tok_rows_cap, row_off)) return rc;
+    return embed_multi_dev_run(h, ids, tt, lens, P, L_in, dense, lex, tok, tok_rows_cap, row_off, st);
+}
+
+// Host arrays: the row total is known before anything is queued, so a capacity that is too small is an error here. Inputs and
+// outputs are staged in buffers of the call's own, which the device-pointer path then runs on; the call waits.
+int embed_multi_host(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L_in, float* dense, float* lex, float* tok,
+                     int64_t tok_rows_cap, int64_t* row_off) {
+    int rc;
+    if ((rc = embed_multi_check(h, ids, tt, lens, P, L_in, dense, lex, tok, tok_rows_cap, row_off))) return rc;
+    const rag_ce_model* m = h->emb;
+    int64_t total = 0;
+    for (int p = 0; p < P; ++p) total += std::max(1, std::min(lens[p], L_in)) - 1;
+    ARG_CHECK(h, !tok || total <= tok_rows_cap, "embed_multi: tok_rows_cap is smaller than the call's token rows");
+    const size_t H = m->cfg.hidden, D = m->heads.tok_dim, n_tok = (size_t)P * L_in;
+    hipStream_t st = h->stream;
+    dev_buf<int32_t> d_ids, d_tt, d_lens;
+    dev_buf<float> d_dense, d_lex, d_tok;
+    dev_buf<int64_t> d_off;
+    if ((rc = d_ids.alloc(h, n_tok)) || (rc = d_tt.alloc(h, n_tok)) || (rc = d_lens.alloc(h, (size_t)P))) return rc;
+    if (dense && (rc = d_dense.alloc(h, (size_t)P * H))) return rc;
+    if (lex && (rc = d_lex.alloc(h, n_tok))) return rc;
+    if (tok && (rc = d_tok.alloc(h, (size_t)std::max<int64_t>(total, 1) * D))) return rc;
+    if (row_off && (rc = d_off.alloc(h, (size_t)P + 1))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(d_ids, ids, n_tok * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(d_tt, tt, n_tok * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(d_lens, lens, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    rc = embed_multi_dev_run(h, d_ids, d_tt, d_lens, P, L_in, d_dense, d_lex, d_tok, total, d_off, st);
+    if (!rc && dense) HIP_TRY(h, hipMemcpyAsync(dense, d_dense, (size_t)P * H * 4, hipMemcpyDeviceToHost, st));
+    if (!rc && lex) HIP_TRY(h, hipMemcpyAsync(lex, d_lex, n_tok * 4, hipMemcpyDeviceToHost, st));
+    if (!rc && tok && total > 0) HIP_TRY(h, hipMemcpyAsync(tok, d_tok, (size_t)total * D * 4, hipMemcpyDeviceToHost, st));
+    if (!rc && row_off) HIP_TRY(h, hipMemcpyAsync(row_off, d_off, ((size_t)P + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));                   // also before the staging buffers go
+    return rc;
 }
 
 // Load-time accuracy probe of a classifier's MX forward. Its 8-bit correction operands track the split-fp16 forward to ~1e-3 on

@@ -16,7 +16,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .cross_encoder import flatten_state_dict, load_tokenizer, map_checkpoint, seq_limit
+from .cross_encoder import flatten_state_dict, load_m3_heads, load_tokenizer, map_checkpoint, seq_limit
 from .engine import get_engine
 
 
@@ -81,8 +81,88 @@ class LocalEmbeddingService:
         from safetensors.numpy import load_file
         with open(os.path.join(path, "config.json")) as f:
             cfg, sd = map_checkpoint(json.load(f), load_file(os.path.join(path, "model.safetensors")), head=False)
-        return cls(cfg, flatten_state_dict(sd, cfg["layers"], head=False), load_tokenizer(path), max_length=max_length, engine=engine,
-                   model=os.path.basename(os.path.normpath(path)), pooling=pooling_mode_of_dir(path), **kw)
+        svc = cls(cfg, flatten_state_dict(sd, cfg["layers"], head=False), load_tokenizer(path), max_length=max_length, engine=engine,
+                  model=os.path.basename(os.path.normpath(path)), pooling=pooling_mode_of_dir(path), **kw)
+        # bge-m3's other two heads (and a ColBERT checkpoint's projection), when their files lie beside the encoder
+        heads = load_m3_heads(path, hidden=cfg["hidden"])
+        if heads["tok_w"] is not None or heads["lex_w"] is not None:
+            svc.load_heads(heads)
+        return svc
+
+    # ---- token-vector and lexical heads: the surface of FlagEmbedding's BGEM3FlagModel (encode / compute_score), restated ----
+    has_token_head = has_lexical_head = False
+
+    def load_heads(self, heads):
+        """heads: what cross_encoder.load_m3_heads returns (tok_w / tok_b / lex_w / lex_b, None where a head is absent)."""
+        self.engine.embed_heads_load(tok_w=heads.get("tok_w"), tok_b=heads.get("tok_b"), lex_w=heads.get("lex_w"), lex_b=heads.get("lex_b", 0.0))
+        self.has_token_head = self.has_token_head or heads.get("tok_w") is not None
+        self.has_lexical_head = self.has_lexical_head or heads.get("lex_w") is not None
+
+    def special_ids(self):
+        """The token ids a lexical-weight map leaves out: the tokenizer's cls / eos / pad / unk, whichever it has (at most 8)."""
+        tid = getattr(self.tokenizer, "token_to_id", lambda t: None)
+        ids = {int(self.cfg[k]) for k in ("cls_id", "sep_id") if k in self.cfg}
+        ids |= {tid(t) for t in ("<s>", "</s>", "<pad>", "<unk>", "[CLS]", "[SEP]", "[PAD]", "[UNK]")} - {None}
+        return sorted(ids)[:8]
+
+    def _need_heads(self, lexical, tokens):
+        if (lexical and not self.has_lexical_head) or (tokens and not self.has_token_head):
+            raise ValueError(f"{self.model}: the {'lexical' if lexical and not self.has_lexical_head else 'token-vector'} head is not loaded "
+                             "(sparse_linear.pt / colbert_linear.pt beside the checkpoint)")
+
+    def encode_multi(self, texts, return_dense=True, return_sparse=True, return_colbert_vecs=True):
+        """One forward per text, upstream's keys: dense_vecs [n, hidden], lexical_weights (a list of {token_id: weight}: the largest
+        weight > 0 of each id, special tokens left out) and colbert_vecs (a list of [len - 1, tok_dim] arrays); a key that was not
+        asked for is None."""
+        self._need_heads(return_sparse, return_colbert_vecs)
+        texts = [str(t) for t in texts]
+        dense, lexw, vecs = [], [], []
+        skip = set(self.special_ids())
+        for b in range(0, len(texts), self.batch_size):
+            ids, tt, lens = self.tokenize(texts[b:b + self.batch_size])
+            d, lx, tk, off = self.engine.embed_multi(ids, tt, lens, dense=return_dense, lexical=return_sparse, tokens=return_colbert_vecs)
+            if return_dense:
+                dense.append(d)
+            for i in range(len(lens)):
+                if return_sparse:
+                    m = {}
+                    for t in range(int(lens[i])):
+                        k, w = int(ids[i, t]), float(lx[i, t])
+                        if k not in skip and w > 0 and w > m.get(k, 0.0):
+                            m[k] = w
+                    lexw.append(m)
+                if return_colbert_vecs:
+                    vecs.append(tk[int(off[i]):int(off[i + 1])].copy())
+        return {"dense_vecs": np.concatenate(dense) if return_dense and dense else None,
+                "lexical_weights": lexw if return_sparse else None, "colbert_vecs": vecs if return_colbert_vecs else None}
+
+    def compute_score(self, pairs, weights=(0.4, 0.2, 0.4)):
+        """[(query, passage), ...] -> upstream's five lists: dense, sparse, colbert, sparse+dense and colbert+sparse+dense, the last
+        two weighted means by weights = (dense, sparse, colbert) over the weights in use. Every distinct text goes through ONE
+        embed_multi call; MaxSim and the lexical match run on the device (rag_maxsim_*, rag_lexical_match_*), the dense score is the
+        existing pairwise cosine."""
+        self._need_heads(True, True)
+        pairs = [(str(q), str(d)) for q, d in pairs]
+        if not pairs:
+            return {k: [] for k in ("colbert", "sparse", "dense", "sparse+dense", "colbert+sparse+dense")}
+        index = {}
+        for q, d in pairs:
+            index.setdefault(q, len(index))
+            index.setdefault(d, len(index))
+        pq = np.asarray([index[q] for q, _ in pairs], dtype=np.int32)
+        pd = np.asarray([index[d] for _, d in pairs], dtype=np.int32)
+        ids, tt, lens = self.tokenize(list(index))
+        dense, lx, tk, off = self.engine.embed_multi(ids, tt, lens)
+        colbert = self.engine.maxsim(tk, off, tk, off, pq, pd).astype(np.float64)
+        sparse = self.engine.lexical_match(ids, lx, lens, ids, lx, lens, pq, pd, skip_ids=self.special_ids()).astype(np.float64)
+        dn = np.empty(len(pairs), dtype=np.float64)
+        for b in range(0, len(pairs), 256):                   # the cosine call gives a matrix: its diagonal, block by block
+            e = min(len(pairs), b + 256)
+            dn[b:e] = np.diagonal(self.engine.pairwise_cosine(dense[pq[b:e]], dense[pd[b:e]]))
+        w0, w1, w2 = (float(w) for w in weights)
+        return {"colbert": colbert.tolist(), "sparse": sparse.tolist(), "dense": dn.tolist(),
+                "sparse+dense": ((w1 * sparse + w0 * dn) / (w0 + w1)).tolist(),
+                "colbert+sparse+dense": ((w2 * colbert + w1 * sparse + w0 * dn) / (w0 + w1 + w2)).tolist()}
 
     # ---- tokenisation: [CLS] text [SEP], truncated to max_length, padded to the longest of the batch -----------------
     def tokenize(self, texts):

@@ -190,3 +190,50 @@ class CrossEncoderReranker(_EngineMixin):
 
     def is_available(self) -> bool:
         return self.model is not None
+
+
+class LateInteractionReranker:
+    """A reranker of CrossEncoderReranker's shape (rerank(query, results, top_k), is_available(); SelectiveReranker takes it
+    wherever it takes a cross-encoder object) over an embedder with token-vector and lexical heads (embeddings.LocalEmbeddingService
+    from a bge-m3-style directory). No reference counterpart: the candidate side is per-passage work - one embedder forward per
+    passage instead of one cross-encoder forward per pair -, the pair work two small device kernels (rag_maxsim_*,
+    rag_lexical_match_*). mode picks which of compute_score's five scores becomes `score`; weights = (dense, sparse, colbert)."""
+
+    MODES = ("dense", "sparse", "colbert", "sparse+dense", "colbert+sparse+dense")
+
+    def __init__(self, embedding_service, mode: str = "colbert+sparse+dense", weights=(0.4, 0.2, 0.4)):
+        if mode not in self.MODES:
+            raise ValueError(f"unknown mode {mode!r}: one of {self.MODES}")
+        self.service = embedding_service
+        self.mode = mode
+        self.weights = tuple(weights)
+
+    def is_available(self) -> bool:
+        s = self.service
+        return bool(s is not None and getattr(s, "has_token_head", False) and getattr(s, "has_lexical_head", False))
+
+    def rerank(self, query: str, results: List[Dict[str, Any]], top_k: int = 5) -> List[Dict[str, Any]]:
+        if not results:
+            return []
+        if not self.is_available():
+            logger.warning("Late-interaction reranker not available, returning original results")
+            return results[:top_k]
+        try:
+            pairs = []
+            for result in results:
+                content = result.get('content', '')
+                if len(content) > 2000:
+                    content = content[:2000]
+                pairs.append([query, content])
+            sc = self.service.compute_score(pairs, weights=self.weights)      # query + candidates: one embed_multi call
+            for i, result in enumerate(results):
+                if 'score' in result and 'embedding_score' not in result:
+                    result['embedding_score'] = result['score']
+                result['score'] = float(sc[self.mode][i])
+                result['m3_dense_score'] = float(sc['dense'][i])
+                result['m3_sparse_score'] = float(sc['sparse'][i])
+                result['m3_colbert_score'] = float(sc['colbert'][i])
+            return sorted(results, key=lambda x: x['score'], reverse=True)[:top_k]
+        except Exception as e:
+            logger.error("Late-interaction reranking failed: %s", e)
+            return results[:top_k]

@@ -3,7 +3,7 @@
 Pure control flow: nothing here touches the GPU. It exists so that the object graph of
 `MemGPTRAGAgent._initialize_rag` can be built entirely from this package: it drives `CrossEncoderReranker.rerank(query,
 results, top_k)` / `.is_available()` and `OpenAIReranker.rerank(query, results, top_k)` (positional, as the reference
-calls them, :205-226). Behaviour is pinned by tests/golden/selective_reranker.json, produced by running the reference
+calls them, :205-226); `reranker.LateInteractionReranker` has the same two methods and goes where a cross-encoder object goes. Behaviour is pinned by tests/golden/selective_reranker.json, produced by running the reference
 class with recording fakes (tools/make_golden_selective.py)."""
 import logging
 from enum import Enum
