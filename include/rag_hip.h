@@ -28,7 +28,7 @@
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_tokens_load_wide_host,
- *     rag_tokens_reserve_wide, rag_bm25_load_host,
+ *     rag_tokens_reserve_wide, rag_bm25_load_host, rag_sparse_load_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
  *     rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
@@ -267,6 +267,64 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
                        int n_queries, int pool, int k, int rrf_k, int tenant, int64_t* lists_ws_dev,
                        double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev,
                        void* stream);
+
+/* ---- learned-sparse inverted index: weighted top-k and dense + sparse RRF. No reference counterpart: the reference has no
+ * learned-sparse retrieval. The semantics are restated from FlagEmbedding's bge-m3 lexical matching / SPLADE practice (a
+ * document is a {token id: weight} map, a query too, the score is the sum of the products over the shared tokens); parity with
+ * those upstream implementations is NOT pinned by a test here.
+ * The index lives in a slot of its own beside the BM25 postings (both may be resident) and runs the BM25 machinery - term-major
+ * postings, one workgroup per (query, 2048-document range) with float64 accumulators in LDS, bracket tables, the per-call plan,
+ * staged thresholds, the merges - on another posting form: (doc int32, weight float32), 8 B per posting resident (an int32
+ * plane and a float32 plane) plus 32 B per term and the bracket tables (<= 4 B per 4 postings).
+ * rag_sparse_load_host: term-major CSR, indptr_host[n_terms + 1] from 0, the documents of a term strictly ascending in
+ *   [0, n_docs), weights finite and > 0; empty lists are legal. A term number is whatever the caller's vocabulary says (bge-m3:
+ *   the token id, n_terms = 250,002). A malformed CSR, a weight that is not finite or <= 0, n_docs < 1 or n_terms < 1:
+ *   RAG_ERR_ARG, and the resident postings stay as they were. A second load replaces the first. Synchronous; takes the
+ *   handle lock and waits for queued *_dev work like every host write.
+ * rag_sparse_info: documents, terms, postings and HBM bytes of the resident sparse index (all 0: none loaded).
+ * Score: s(q, d) = sum_i (double)qweights[i] * (double)weight[terms[i], d] in float64, over the query's tokens in THEIR ORDER
+ *   on the documents that hold the term. A float32 x float32 product is exact in float64, so the only rounding is the sum,
+ *   and its order is fixed: every score bit equals the numpy loop `score[doc[a:e]] += float64(qw) * w[a:e].astype(float64)`
+ *   run token by token. terms[i] < 0 or >= n_terms adds nothing; a token whose weight is not > 0 (NaN included) adds nothing;
+ *   a term that occurs twice adds twice. Queries are CSR as for BM25: term_ptr[Q + 1], terms[], qweights[] parallel to terms[].
+ * rag_sparse_topk_host / _dev: the documents with s > 0 by score descending, ties to the lower row, at most k; the rest of the
+ *   k slots is ids -1 / rows -1 / scores 0.0. A document that matches nothing is NEVER returned (rag_bm25_topk_* returns
+ *   zero-score rows because it mirrors a sort over the whole corpus; here they would pollute a fusion). Scores are raw.
+ *   Limits: 1 <= n_queries <= 65535, 0 < k <= 1024, as rag_bm25_topk_*. rows_out may be NULL.
+ *   When the postings cover exactly the dense index's rows, ids follow the index's id mapping (explicit ids or id_base + row),
+ *   tenant >= 0 keeps that tenant's rows and deleted rows are hidden, as in BM25 (a hidden row is an empty slot). Without
+ *   such an index ids are row numbers and tenant >= 0 is RAG_ERR_ARG.
+ * rag_sparse_scores_host: out_host[Q][n_docs], every document's score, 0.0 for non-matching and hidden documents (small
+ *   corpora, tests).
+ * Live writes: rag_index_insert_host, rag_index_compact and rag_index_compact_bm25 leave the sparse postings STALE: every
+ *   rag_sparse_* search and rag_hybrid_sparse_rrf_dev returns RAG_ERR_STATE until rag_sparse_load_host runs again (the handle
+ *   stays usable; a compaction that finds no deleted row moves nothing and marks nothing). rag_index_delete_host does not:
+ *   deleted rows are filtered. There is no append, compaction or per-query
+ *   tenant array for this index.
+ * rag_hybrid_sparse_rrf_dev: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list - dense top-`pool` and sparse
+ *   top-`pool` (-1 padded at the tail), rag_rrf_fuse_dev semantics with n_lists = 2, dense first, top-k. Workspaces and limits
+ *   as rag_hybrid_rrf_dev (pool <= 256; lists_ws_dev [2][Q][pool] int64, scores_ws_dev [Q][pool] float64); the postings must
+ *   be row-aligned with the index. Bit-identical to rag_dense_topk_dev + rag_sparse_topk_dev + rag_rrf_fuse_dev called one
+ *   after another. The sparse leg forks onto the internal side stream as the BM25 leg of rag_hybrid_rrf_dev does (batches
+ *   of up to 4096 queries; options no_fork / fork_max_q), joined back by events: everything is ordered on `stream`.
+ * The _dev calls follow the ordering rules of the preamble.
+ * Sharding: raw scores need no global statistic, so rag_merge_topk_dev over the per-shard lists (global ids through id_base
+ *   or explicit ids) reproduces the unsharded list exactly. */
+int rag_sparse_load_host(rag_handle_t h, const int64_t* indptr_host /*n_terms+1*/, const int32_t* doc_host /*nnz*/,
+                         const float* weight_host /*nnz*/, int64_t n_docs, int64_t n_terms);
+int rag_sparse_info(rag_handle_t h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
+int rag_sparse_topk_host(rag_handle_t h, const int32_t* term_ptr_host /*Q+1*/, const int32_t* terms_host,
+                         const float* qweights_host, int n_queries, int k, int tenant, int64_t* ids_out,
+                         int32_t* rows_out /*may be NULL*/, double* scores_out);
+int rag_sparse_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                        int n_queries, int k, int tenant, int64_t* ids_out_dev, int32_t* rows_out_dev /*may be NULL*/,
+                        double* scores_out_dev, void* stream);
+int rag_sparse_scores_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host,
+                           const float* qweights_host, int n_queries, double* out_host /*[Q][n_docs]*/);
+int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                              const float* qweights_dev, int n_queries, int pool, int k, int rrf_k, int tenant,
+                              int64_t* lists_ws_dev, double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev,
+                              int32_t* ranks_out_dev, void* stream);
 
 /* ---- greedy MMR selection on the device: replaces the Python loops of
  *      MMRDiversifier.diversify (rag/reranker.py:116-195; variant 0: lambda*rel + (1-lambda)*(1-max_sim), first pick has

@@ -116,6 +116,12 @@ _SIGS = {
     "rag_rrf_fuse_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_bm25_topk_dev": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "rag_hybrid_rrf_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
+    "rag_sparse_load_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
+    "rag_sparse_info": ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+    "rag_sparse_topk_host": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
+    "rag_sparse_topk_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
+    "rag_sparse_scores_host": ([_P, _P, _P, _P, C.c_int, _P], C.c_int),
+    "rag_hybrid_sparse_rrf_dev": ([_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "rag_index_set_temporal_host": ([_P, _P, C.c_int64], C.c_int),
     "rag_hybrid_linear_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P,
                                _P], C.c_int),
@@ -702,6 +708,80 @@ class RagEngine:
                        C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
                        C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
                        C.c_void_p(ranks.data_ptr()), st), name)
+        return keys, rrf, ranks
+
+    # ---- learned-sparse inverted index (include/rag_hip.h rag_sparse_*; sparse.LexicalPostings builds the arrays) ----------
+    def sparse_load(self, indptr, doc, weight, n_docs):
+        """Term-major CSR of (doc int32, weight float32) postings: indptr [n_terms + 1], docs of a term strictly ascending,
+        weights finite and > 0. Replaces the resident sparse index; the BM25 postings are not touched."""
+        indptr = _np(indptr, np.int64)
+        doc = _np(doc, np.int32)
+        weight = _np(weight, np.float32)
+        if indptr.ndim != 1 or indptr.shape[0] < 2 or doc.shape != weight.shape or doc.shape[0] != int(indptr[-1]):
+            raise RagError("sparse_load: indptr must have n_terms + 1 entries and end at len(doc) == len(weight)")
+        self._check(self.lib.rag_sparse_load_host(self.h, _ptr(indptr), _ptr(doc), _ptr(weight), int(n_docs), indptr.shape[0] - 1),
+                    "rag_sparse_load_host")
+
+    def sparse_info(self):
+        v = [C.c_int64() for _ in range(4)]
+        self._check(self.lib.rag_sparse_info(self.h, *[C.byref(x) for x in v]), "rag_sparse_info")
+        return dict(zip(("n_docs", "n_terms", "nnz", "hbm_bytes"), (int(x.value) for x in v)))
+
+    def sparse_topk(self, term_ptr, terms, weights, k, tenant=-1):
+        """Weighted queries (CSR: term_ptr [Q + 1], terms, float32 weights) -> (ids, rows, scores) [Q, k]: the documents with a
+        score > 0 by score descending, lower row first on ties; -1 / -1 / 0.0 behind them."""
+        term_ptr = _np(term_ptr, np.int32)
+        terms = _np(terms, np.int32)
+        weights = _np(weights, np.float32)
+        Q = term_ptr.shape[0] - 1
+        ids = np.empty((Q, k), dtype=np.int64)
+        rows = np.empty((Q, k), dtype=np.int32)
+        sc = np.empty((Q, k), dtype=np.float64)
+        self._check(self.lib.rag_sparse_topk_host(self.h, _ptr(term_ptr), _ptr(terms), _ptr(weights), Q, int(k), int(tenant), _ptr(ids),
+                                                  _ptr(rows), _ptr(sc)), "rag_sparse_topk_host")
+        return ids, rows, sc
+
+    def sparse_scores(self, term_ptr, terms, weights):
+        """Float64 score of EVERY document [Q, n_docs] (0.0: no match, or a hidden row); for small corpora and tests."""
+        term_ptr = _np(term_ptr, np.int32)
+        terms = _np(terms, np.int32)
+        weights = _np(weights, np.float32)
+        Q = term_ptr.shape[0] - 1
+        out = np.empty((Q, self.sparse_info()["n_docs"]), dtype=np.float64)
+        self._check(self.lib.rag_sparse_scores_host(self.h, _ptr(term_ptr), _ptr(terms), _ptr(weights), Q, _ptr(out)), "rag_sparse_scores_host")
+        return out
+
+    def sparse_topk_dev(self, term_ptr, terms, weights, k, ids_out, rows_out, scores_out, stream=None, tenant=-1):
+        """Device tensors in / out (int32 term arrays, float32 weights; int64 ids, float64 scores [Q, k]); asynchronous on `stream`."""
+        import torch
+        Q = term_ptr.shape[0] - 1
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._check(self.lib.rag_sparse_topk_dev(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()),
+                                                 C.c_void_p(weights.data_ptr()), Q, int(k), int(tenant), C.c_void_p(ids_out.data_ptr()),
+                                                 C.c_void_p(rows_out.data_ptr() if rows_out is not None else 0),
+                                                 C.c_void_p(scores_out.data_ptr()), st), "rag_sparse_topk_dev")
+
+    def hybrid_sparse_rrf_dev(self, q, term_ptr, terms, weights, pool, k, rrf_k=60, tenant=-1, stream=None):
+        """hybrid_rrf_dev with the learned-sparse list in place of the BM25 list: dense top-pool + sparse top-pool -> RRF ->
+        (keys [Q,k] int64, rrf scores [Q,k] float64, ranks [Q,k,2] int32); every input a CUDA tensor."""
+        import torch
+        Q = q.shape[0]
+        dev = q.device
+        key = ("hybs", Q, pool, k)
+        if getattr(self, "_hybs_key", None) != key:
+            self._hybs = (torch.empty((2, Q, pool), dtype=torch.int64, device=dev),
+                          torch.empty((Q, pool), dtype=torch.float64, device=dev),
+                          torch.empty((Q, k), dtype=torch.int64, device=dev),
+                          torch.empty((Q, k), dtype=torch.float64, device=dev),
+                          torch.empty((Q, k, 2), dtype=torch.int32, device=dev))
+            self._hybs_key = key
+        lists, sc, keys, rrf, ranks = self._hybs
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._check(self.lib.rag_hybrid_sparse_rrf_dev(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()),
+                                                       C.c_void_p(terms.data_ptr()), C.c_void_p(weights.data_ptr()), Q, int(pool), int(k),
+                                                       int(rrf_k), int(tenant), C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
+                                                       C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
+                                                       C.c_void_p(ranks.data_ptr()), st), "rag_hybrid_sparse_rrf_dev")
         return keys, rrf, ranks
 
     def set_temporal(self, temporal):

@@ -40,6 +40,16 @@ int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_
 int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
                  int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
 void bm25_free(rag_ctx* h);
+void sparse_free(rag_ctx* h);
+int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_docs, int64_t n_terms);
+int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
+int64_t sparse_n_docs(const rag_ctx* h);
+int sparse_fresh(rag_ctx* h);
+int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant,
+                     int64_t* ids_out, int32_t* rows_out, double* scores_out);
+int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out);
+int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st);
 int bm25_set_normalize(rag_ctx* h, int on);
 int chunk_chain_host(rag_ctx* h, const float* emb, const int32_t* sent_len, int n, int dim, double threshold, int max_chunk,
                      int min_chunk, int32_t* group_out);
@@ -179,6 +189,7 @@ int rag_destroy(rag_handle_t h) {
     comm_free(h);
     dense_free(h);
     bm25_free(h);
+    sparse_free(h);
     ce_free(h);
     static_cast<rag_device_mem&>(*h) = rag_device_mem();      // every device buffer the handle itself owns
     for (auto& p : h->prof)
@@ -663,6 +674,66 @@ int rag_hybrid_rrf_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t
     if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
     return hybrid_rrf_entry(h, q_dev, term_ptr_dev, terms_dev, Q, pool, k, rrf_k, -1, tenants_host, lists_ws_dev, scores_ws_dev, keys_out_dev,
                             rrf_out_dev, ranks_out_dev, stream);
+}
+
+// ---- learned-sparse inverted index (bm25.hip, "the learned-sparse inverted index") ------------------------------------------------
+int rag_sparse_load_host(rag_handle_t h, const int64_t* indptr_host, const int32_t* doc_host, const float* weight_host, int64_t n_docs,
+                         int64_t n_terms) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);                      // queued *_dev searches read the postings this call replaces
+    return sparse_load_host(h, indptr_host, doc_host, weight_host, n_docs, n_terms);
+}
+
+int rag_sparse_info(rag_handle_t h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return sparse_info(h, n_docs_out, n_terms_out, nnz_out, hbm_bytes_out);
+}
+
+int rag_sparse_topk_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host, int n_queries,
+                         int k, int tenant, int64_t* ids_out, int32_t* rows_out, double* scores_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_topk_host(h, term_ptr_host, terms_host, qweights_host, n_queries, k, tenant, ids_out, rows_out, scores_out);
+}
+
+int rag_sparse_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int n_queries,
+                        int k, int tenant, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, n_queries, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream);
+}
+
+int rag_sparse_scores_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
+                           int n_queries, double* out_host) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_scores_host(h, term_ptr_host, terms_host, qweights_host, n_queries, out_host);
+}
+
+// dense top-pool + learned-sparse top-pool + RRF -> top-k: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list
+// (hybrid_legs: the sparse leg forks onto the side stream exactly as the BM25 leg does).
+int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                              const float* qweights_dev, int Q, int pool, int k, int rrf_k, int tenant, int64_t* lists_ws_dev,
+                              double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid_sparse: 1 <= n_queries <= 65535");
+    ARG_CHECK(h, q_dev && term_ptr_dev && qweights_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid_sparse: null pointer");
+    ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid_sparse: 0 < pool <= 256");
+    ARG_CHECK(h, sparse_n_docs(h) >= 0, "no sparse index loaded (rag_sparse_load_host)");
+    if (int rc = sparse_fresh(h)) return rc;
+    ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "hybrid_sparse: the sparse postings must be row-aligned with the index (same number of documents)");
+    DEV_ENTRY(h);
+    hipStream_t st = (hipStream_t)stream;
+    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_sparse: tenant filter requested but no tenants loaded");
+    if (int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st, {nullptr, nullptr}, qweights_dev))
+        return rc;
+    return rrf_fuse_dev(h, lists_ws_dev, Q, 2, pool, (int64_t)Q * pool, pool, rrf_k, k, keys_out_dev, rrf_out_dev, ranks_out_dev, st);
 }
 
 // Per-row temporal score of the linear fusion: RECENCY_WEIGHT * 0.5 ** (days_old / half_life) computed by the host from

@@ -25,6 +25,9 @@
 //            preserving keys, ties -> lower doc id, i.e. Python's stable sort); bm25_tau_kernel takes the k-th best key
 //            over them (a lower bound of the global k-th); every other range only compacts its keys >= tau (exact select
 //            as the fallback when more than k survive). Then a per-query merge of the partial lists.
+// The same machinery serves a second resident index, the LEARNED-SPARSE one (rag_sparse_*, end of this file): postings
+// (doc int32, weight float32), a float32 weight per query token, score += (double)qw * (double)w, and a top-k that holds only
+// documents with a score > 0 - posting form 2 of bm25_range_body.
 #include "common.h"
 
 #include <cmath>
@@ -33,6 +36,7 @@
 
 typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));          // posting segments start at any posting
 typedef double double2u __attribute__((ext_vector_type(2), aligned(8)));
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
 #ifndef BM_RANGE            // -DBM_RANGE / -DBM_THREADS: variant builds by tools/bm25_variant_build.sh
 #define BM_RANGE 2048
 #endif
@@ -77,6 +81,11 @@ struct rag_bm25_index {
     dev_buf<uint32_t> packed;
     dev_buf<double> gtab;
     int64_t n_codes = 0;
+    // LEARNED-SPARSE form (rag_sparse_load_host; the index of rag_ctx::sparse): the posting's weight as the caller's float32, 8 B
+    // per posting with `doc`; `w` is not built, every term's idf is 1 and the QUERY carries a float32 weight per token
+    // (call_qw: the device array of the current call, as plan_t is the current call's). No tail, no refresh, raw scores.
+    dev_buf<float> wf;
+    const float* call_qw = nullptr;
     dev_buf<bm_term_meta> meta;        // [n_terms]
     dev_buf<int32_t> range_tab;        // concatenated per-term tables: entry c = first posting (rel. to meta.post) with doc >= c << shift
     int64_t tab_entries = 0;
@@ -270,10 +279,14 @@ __device__ __forceinline__ void bm_bracket(const bm_term_meta& m, const int32_t*
 #define BM_PLAN_BUDGET ((size_t)512 << 20)
 struct __attribute__((aligned(16))) bm_plan_meta { int64_t post; double idf; };
 
+// WEIGHTED (the learned-sparse index): the float64 slot carries the query token's weight instead of the term's idf - 0 for an
+// unknown term and for a weight that is not > 0 (NaN included), which is what "adds nothing" means to the scoring kernel.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void bm25_plan_kernel(const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc,
                                                          const int32_t* __restrict__ range_tab, int n_ranges, int64_t n_terms,
                                                          const int32_t* __restrict__ term_ptr, const int32_t* __restrict__ terms,
-                                                         int32_t* __restrict__ plan_off, bm_plan_meta* __restrict__ plan_meta, int plan_t) {
+                                                         int32_t* __restrict__ plan_off, bm_plan_meta* __restrict__ plan_meta, int plan_t,
+                                                         const float* __restrict__ qweights) {
     const int q = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
     const int t0 = term_ptr[q], nt = min(plan_t, term_ptr[q + 1] - t0);
     const int64_t tg = (int64_t)r * BM_RANGE;
@@ -282,6 +295,12 @@ __global__ __launch_bounds__(256) void bm25_plan_kernel(const bm_term_meta* __re
         const bool ok = t >= 0 && t < n_terms;               // out-of-vocabulary token: idf.get(q) is None -> 0
         bm_term_meta m = {0, 0, 0.0, 0, BM_NO_TAB};
         if (ok) m = meta[t];
+        if constexpr (WEIGHTED) {
+            if (r == 0) {
+                const float qw = qweights[t0 + s];
+                plan_meta[(size_t)q * plan_t + s] = {m.post, ok && qw > 0.0f ? (double)qw : 0.0};
+            }
+        } else
         if (r == 0) plan_meta[(size_t)q * plan_t + s] = {m.post, ok ? m.idf : 0.0};
         if (r <= n_ranges) {
             int lo, hi;
@@ -327,7 +346,10 @@ static bm_grid bm_make_grid(int nr_l, int Q, int linear) {
 // (SGPRs capped at 96: 256-thread workgroups are admitted 7 per CU up to 96 scalar registers, 6 from 97 on - MI355X_MICROARCH.md)
 // The body of both kernels below. qten: the tenant of every query of the launch (rag_*_tenants_*) or null - a compile-time null in
 // bm25_range_kernel, whose code is therefore what it was before queries had tenants of their own.
-template <bool PACKED>
+// FORM 0: (doc i32, impact f64); 1: PACKED; 2: SPARSE, the learned-sparse index - (doc i32, weight f32) postings, a float32 weight per
+// query token (qweights; the planned tokens' weights come in the plan's float64 slot), score += (double)qw * (double)w, and a
+// document whose score is not > 0 - one that matches nothing - is an EMPTY slot for the selection, like a hidden row.
+template <int FORM>
 __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc,
                                                                  const double* __restrict__ w, const uint32_t* __restrict__ packed,
                                                                  const double* __restrict__ gtab,
@@ -340,7 +362,9 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
                                                                  const int32_t* __restrict__ tenants, int tenant_all,
                                                                  const int32_t* __restrict__ plan_off, const bm_plan_meta* __restrict__ plan_meta,
                                                                  const bm_grid gm, const bm_dense_extra dx, const bm_seg sg,
-                                                                 const int32_t* __restrict__ qten) {
+                                                                 const int32_t* __restrict__ qten, const float* __restrict__ wf,
+                                                                 const float* __restrict__ qweights) {
+    constexpr bool PACKED = FORM == 1, SPARSE = FORM == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup -> (range, query), see bm_make_grid: XCD x (= workgroup id % 8) walks its columns (range, query group) one after the
     // other, every query of the group on the SAME range side by side, so a range's postings are fetched into that XCD's L2 once
@@ -412,6 +436,10 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
                     const int s0 = bm_search(doc + m.post, lo0, hi0, base);
                     const int e0 = bm_search(doc + m.post, max(lo1, s0), hi1, base + BM_RANGE);
                     f = m.idf;
+                    if constexpr (SPARSE) {
+                        const float qw = qweights[tb + tid];
+                        f = qw > 0.0f ? (double)qw : 0.0;
+                    }
                     a = m.post + s0;
                     n = e0 - s0;
                 }
@@ -519,6 +547,72 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
 #undef BMP_TURN
 #undef TOK_IDF
         } else
+        if constexpr (SPARSE) {
+            // (doc i32, weight f32): one 16-byte load from each plane per 4 postings, two register sets as in the unpacked loop
+            // below; the weight becomes float64 and is multiplied by the token's float64 query weight (workgroup-uniform, read
+            // with v_readlane). A float32 x float32 product is exact in float64: the only rounding is the add.
+            const double my_f = m_idf[lane];
+            const int my_f_lo = (int)(uint32_t)__builtin_bit_cast(uint64_t, my_f), my_f_hi = (int)(__builtin_bit_cast(uint64_t, my_f) >> 32);
+#define TOK_QW(TI) __builtin_bit_cast(double, ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(my_f_hi, TI) << 32) | (uint32_t)__builtin_amdgcn_readlane(my_f_lo, TI))
+#define SP_LOAD(TI, C, D, W)                                                                       \
+            {                                                                                      \
+                const int64_t o_ = TOK_A(TI) + min((C) * 4 * BM_THREADS + tid * 4, max(TOK_N(TI) - 1, 0)); \
+                D = *reinterpret_cast<const int4u*>(doc + o_);                                     \
+                W = *reinterpret_cast<const float4u*>(wf + o_);                                    \
+            }
+#define SP_ADD(TI, C, D, W)                                                                        \
+            {                                                                                      \
+                const int p_ = (C) * 4 * BM_THREADS + tid * 4, n_ = TOK_N(TI);                     \
+                const double f_ = TOK_QW(TI);                                                      \
+                char* const sb_ = reinterpret_cast<char*>(sc);                                     \
+                if (((C) + 1) * 4 * BM_THREADS <= n_) {      /* a full chunk (uniform): no tail tests */ \
+                    double* a0_ = reinterpret_cast<double*>(sb_ + SC_OFF(D[0] - (int)base));       \
+                    double* a1_ = reinterpret_cast<double*>(sb_ + SC_OFF(D[1] - (int)base));       \
+                    double* a2_ = reinterpret_cast<double*>(sb_ + SC_OFF(D[2] - (int)base));       \
+                    double* a3_ = reinterpret_cast<double*>(sb_ + SC_OFF(D[3] - (int)base));       \
+                    const double v0_ = *a0_, v1_ = *a1_, v2_ = *a2_, v3_ = *a3_;                   \
+                    *a0_ = v0_ + f_ * (double)W[0];                                                \
+                    *a1_ = v1_ + f_ * (double)W[1];                                                \
+                    *a2_ = v2_ + f_ * (double)W[2];                                                \
+                    *a3_ = v3_ + f_ * (double)W[3];                                                \
+                } else if (p_ < n_) {                                                              \
+                    double* a0_ = reinterpret_cast<double*>(sb_ + SC_OFF(D[0] - (int)base));       \
+                    double* a1_ = p_ + 1 < n_ ? reinterpret_cast<double*>(sb_ + SC_OFF(D[1] - (int)base)) : &sc[BM_SC_DOUBLES - 1]; \
+                    double* a2_ = p_ + 2 < n_ ? reinterpret_cast<double*>(sb_ + SC_OFF(D[2] - (int)base)) : &sc[BM_SC_DOUBLES - 2]; \
+                    double* a3_ = p_ + 3 < n_ ? reinterpret_cast<double*>(sb_ + SC_OFF(D[3] - (int)base)) : &sc[BM_SC_DOUBLES - 3]; \
+                    const double v0_ = *a0_, v1_ = *a1_, v2_ = *a2_, v3_ = *a3_;                   \
+                    *a0_ = v0_ + f_ * (double)W[0];                                                \
+                    if (p_ + 1 < n_) *a1_ = v1_ + f_ * (double)W[1];                               \
+                    if (p_ + 2 < n_) *a2_ = v2_ + f_ * (double)W[2];                               \
+                    if (p_ + 3 < n_) *a3_ = v3_ + f_ * (double)W[3];                               \
+                }                                                                                  \
+            }
+            if (ti < nb) {
+                int4u da, db;
+                float4u wa, wb;
+                SP_LOAD(ti, c, da, wa)
+                for (;;) {
+                    int nti, nc;
+                    BM_NEXT(ti, c, nti, nc)
+                    const bool more1 = nti < nb;
+                    { const int lt = more1 ? nti : ti, lc = more1 ? nc : c; SP_LOAD(lt, lc, db, wb) }
+                    SP_ADD(ti, c, da, wa)
+                    if (nti != ti) BM_TOKEN_BARRIER;
+                    if (!more1) break;
+                    ti = nti; c = nc;
+                    BM_NEXT(ti, c, nti, nc)
+                    const bool more2 = nti < nb;
+                    { const int lt = more2 ? nti : ti, lc = more2 ? nc : c; SP_LOAD(lt, lc, da, wa) }
+                    SP_ADD(ti, c, db, wb)
+                    if (nti != ti) BM_TOKEN_BARRIER;
+                    if (!more2) break;
+                    ti = nti; c = nc;
+                }
+            }
+#undef SP_LOAD
+#undef SP_ADD
+#undef TOK_QW
+        } else
         if (ti < nb) {
             int4u da, db;
             double2u wa0, wa1, wb0, wb1;
@@ -605,7 +699,7 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
     // (key 0, below every real score) from here on, so it can neither enter a partial list nor move the threshold.
     if (lim <= k) {
         for (int i = tid; i < k; i += BM_THREADS) {
-            const bool mine = i < lim && i >= first && row_visible(tenants, row_base + i, tenant);
+            const bool mine = i < lim && i >= first && row_visible(tenants, row_base + i, tenant) && (!SPARSE || sc[SC_IDX(i)] > 0.0);
             part_key[po + i] = mine ? f64_orderable(sc[SC_IDX(i)]) : 0ull;
             part_row[po + i] = (uint32_t)(row_base + i);
         }
@@ -625,6 +719,11 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
 #pragma unroll
         for (int j = 0; j < BM_SEG; ++j)
             if ((valid >> j & 1u) && !row_visible(tenants, row_base + seg0 + j, tenant)) valid &= ~(1u << j);
+    }
+    if constexpr (SPARSE) {                              // a document that matches nothing is never returned
+#pragma unroll
+        for (int j = 0; j < BM_SEG; ++j)
+            if (!(sv[j] > 0.0)) valid &= ~(1u << j);
     }
     // Thresholded ranges (second stage, see bm25_launch_topk): tau_key[q] is the k-th best key over the first-stage
     // ranges, a lower bound of the global k-th. Only keys >= tau can reach the global top-k; a later range holds
@@ -780,13 +879,19 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
 // one tenant (or none) for the whole launch
 template <bool PACKED>
 __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_kernel(BM_RANGE_PARAMS) {
-    bm25_range_body<PACKED>(BM_RANGE_ARGS, nullptr);
+    bm25_range_body<PACKED ? 1 : 0>(BM_RANGE_ARGS, nullptr, nullptr, nullptr);
 }
 // a tenant per query: the workgroup reads its query's (`tenant` is not read)
 template <bool PACKED>
 __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_tenants_kernel(BM_RANGE_PARAMS,
                                                                                                             const int32_t* __restrict__ qten) {
-    bm25_range_body<PACKED>(BM_RANGE_ARGS, qten);
+    bm25_range_body<PACKED ? 1 : 0>(BM_RANGE_ARGS, qten, nullptr, nullptr);
+}
+// the learned-sparse index (rag_sparse_*): float32 posting weights wf (`w`, `packed`, `gtab` are null), a float32 weight per query token
+__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void sparse_range_kernel(BM_RANGE_PARAMS,
+                                                                                                      const float* __restrict__ wf,
+                                                                                                      const float* __restrict__ qweights) {
+    bm25_range_body<2>(BM_RANGE_ARGS, nullptr, wf, qweights);
 }
 
 #define BM_MERGE 2048
@@ -1131,7 +1236,11 @@ struct bm25_topk_out {
         bm_grid gm_ = bm_make_grid(NR_L, NQ, (H)->opt.bm25_linear_grid);                                                           \
         gm_.plan_t = (IX)->plan_t;                                                                                                 \
         const bm_seg sg_ = {(IX)->row0, OUT_LD, (IX)->first};                                                                      \
-        if ((QTEN) != nullptr && (IX)->packed != nullptr)                                                                          \
+        if ((IX)->wf != nullptr)                                                                                                   \
+            hipLaunchKernelGGL(sparse_range_kernel, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, \
+                               (const float*)(IX)->wf, (IX)->call_qw);                                                             \
+        else if ((QTEN) != nullptr && (IX)->packed != nullptr)                                                                     \
             hipLaunchKernelGGL(bm25_range_tenants_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
                                (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, QTEN); \
         else if ((QTEN) != nullptr)                                                                                                \
@@ -1160,8 +1269,12 @@ static bm25_plan_ws bm25_tail_plan(const rag_bm25_index* ix, int Q, const bm25_p
 }
 static void bm25_launch_plan(const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, const bm25_plan_ws& p,
                              hipStream_t st) {
-    hipLaunchKernelGGL(bm25_plan_kernel, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab,
-                       ix->n_ranges, ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t);
+    if (ix->wf != nullptr)
+        launch(bm25_plan_kernel<true>, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab, ix->n_ranges,
+               ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t, ix->call_qw);
+    else
+        launch(bm25_plan_kernel<false>, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab, ix->n_ranges,
+               ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t, nullptr);
 }
 
 // mode 1 over every segment: out[Q][documents of the index] (+ the linear fusion's extras); each segment writes its own columns
@@ -1320,7 +1433,7 @@ static int64_t bm_plan_terms(const int64_t* indptr, int64_t n_terms, int64_t n_d
         if (df < 0 || df > max_df) return -1;
         int64_t e_t = 0;
         const int g = bm_plan_term(df, n_pad, &e_t);
-        if (meta_h) (*meta_h)[(size_t)t] = {indptr[t], n_tab, idf[t], (int32_t)df, g};
+        if (meta_h) (*meta_h)[(size_t)t] = {indptr[t], n_tab, idf ? idf[t] : 1.0, (int32_t)df, g};      // (no idf: the learned-sparse index)
         n_tab += e_t;
     }
     return n_tab;
@@ -1899,13 +2012,20 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
 
 static int bm25_set_attr(rag_ctx* h) {
     return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>, bm25_range_tenants_kernel<true>,
-                     bm25_range_tenants_kernel<false>);
+                     bm25_range_tenants_kernel<false>, sparse_range_kernel);
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
 // does not tell: i inserts then i compacted rows restore it): refuse until rag_bm25_append_host covers the inserted rows or
 // rag_bm25_load_host reloads them (rag_index_compact_bm25 renumbers them with the rows and leaves this flag as it was).
+// the two resident indexes of a handle (BM25 postings, learned-sparse postings) follow the dense index's rows when they cover them
+static inline bool bm_resident(const rag_ctx* h, const rag_bm25_index* ix) { return ix == h->bm25 || ix == h->sparse; }
 static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
+    if (ix == h->sparse && h->sparse_stale) {
+        h->err = "sparse: the postings are stale (rows were inserted or compacted since rag_sparse_load_host): reload postings "
+                 "aligned with the current rows";
+        return RAG_ERR_STATE;
+    }
     if (ix != h->bm25 || !h->bm25_stale) return RAG_OK;
     h->err = "bm25: the postings are stale (rows were inserted or compacted since rag_bm25_load_host): reload postings aligned "
              "with the current rows";
@@ -1922,7 +2042,7 @@ static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, qu
     if (qt.host != nullptr) tenant = 0;
     if (int rc = bm25_check_fresh(h, ix)) return rc;
     if (tenant < 0) {
-        if (ix == h->bm25 && h->vis != nullptr && h->n_rows == bm_total_docs(ix)) *tenants_out = h->vis;
+        if (bm_resident(h, ix) && h->vis != nullptr && h->n_rows == bm_total_docs(ix)) *tenants_out = h->vis;
         return RAG_OK;
     }
     ARG_CHECK(h, h->tenants != nullptr && h->n_rows == bm_total_docs(ix),
@@ -2187,7 +2307,7 @@ int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_i
 // grow-only arena: no device allocation per call.
 static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int mode, int tenant,
                     int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out, double* dense_out,
-                    query_tenants qt = {nullptr, nullptr}) {
+                    query_tenants qt = {nullptr, nullptr}, const float* qweights = nullptr) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr, "bm25: 1 <= n_queries <= 65535");
     const int n_terms_q = term_ptr[Q];
@@ -2210,7 +2330,7 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     size_t total = stage_size(Q + 1, 4) + stage_size(std::max(1, n_terms_q), 4) + stage_size(n_part, 8) + stage_size(n_part, 4) +
                    stage_size((size_t)Q * nr, 4) + 2 * stage_size(n_out, 8) + 2 * stage_size(n_out, 4) + 2 * stage_size(Q, 8) +
                    stage_size(n_out, 8) + stage_size(n_dense, 8) + stage_size(bm25_plan_off_total(ix, Q), 4) +
-                   stage_size(bm25_plan_meta_total(ix, Q), sizeof(bm_plan_meta));
+                   stage_size(bm25_plan_meta_total(ix, Q), sizeof(bm_plan_meta)) + (qweights ? stage_size(std::max(1, n_terms_q), 4) : 0);
     if ((rc = stage_reserve(h, total))) return rc;
     char* p = h->stage;
     int32_t* tp = stage_take<int32_t>(p, Q + 1);
@@ -2231,8 +2351,13 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
     w.plan.meta = stage_take<bm_plan_meta>(p, bm25_plan_meta_total(ix, Q));  // (sized for the largest plan_t)
     HIP_TRY(h, hipMemcpyAsync(tp, term_ptr, (size_t)(Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(tm, terms, (size_t)n_terms_q * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (qweights) {                                                    // the learned-sparse index: a weight per query token
+        float* qw = stage_take<float>(p, std::max(1, n_terms_q));
+        if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(qw, qweights, (size_t)n_terms_q * sizeof(float), hipMemcpyHostToDevice, st));
+        ix->call_qw = qw;
+    }
     if (mode == 0) {
-        const bool aligned = ix == h->bm25 && h->n_rows == bm_total_docs(ix);
+        const bool aligned = bm_resident(h, ix) && h->n_rows == bm_total_docs(ix);
         const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, idd, rwd, scd, mxd,
                                  ix->normalize};
         bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, qt.dev, st);
@@ -2257,37 +2382,40 @@ static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
 }
 
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
-static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
+static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
+                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
 
 // The per-call workspace (partial lists [Q][n_ranges][k] x 12 B + the plan) grows with Q x shard size: on a 12.5M-document shard a
 // query takes ~9 MB at k = 100. Batches are therefore run in sub-batches whose workspace stays under BM_WS_BUDGET (queries are
 // independent: same results; the 1M-document bench index runs 1,024 queries in one piece, the 12.5M-document shard 256).
 #define BM_WS_BUDGET ((size_t)6 << 30)
-int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
-    ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
+// ix: the resident BM25 postings (bm25_topk_dev) or the learned-sparse postings (sparse_topk_dev, which sets ix->call_qw first)
+static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
+                       int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
+    ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
-    if (int rc = bm25_check_fresh(h, h->bm25)) return rc;
-    const size_t per_query = (size_t)bm_total_ranges(h->bm25) * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
+    if (int rc = bm25_check_fresh(h, ix)) return rc;
+    const size_t per_query = (size_t)bm_total_ranges(ix) * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
     const size_t budget = h->opt.bm25_ws_mb > 0 ? (size_t)h->opt.bm25_ws_mb << 20 : BM_WS_BUDGET;
     const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, budget / std::max<size_t>(1, per_query)));
     for (int q0 = 0; q0 < Q; q0 += qb) {
         const int nq = std::min(qb, Q - q0);
-        const int rc = bm25_topk_dev_batch(h, term_ptr_dev + q0, terms_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
+        const int rc = bm25_topk_dev_batch(h, ix, term_ptr_dev + q0, terms_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
                                            rows_dev ? rows_dev + (size_t)q0 * k : nullptr, scores_dev + (size_t)q0 * k,
                                            raw_max_dev ? raw_max_dev + q0 : nullptr, st, qt + q0);      // (the tenants go with their queries)
         if (rc) return rc;
     }
     return RAG_OK;
 }
+int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
+                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
+    return bm_topk_dev(h, h->bm25, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, st, qt);
+}
 
-static int bm25_topk_dev_batch(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                               int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
-    ARG_CHECK(h, h->bm25 != nullptr, "no BM25 index loaded");
+static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
+                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && ids_dev && scores_dev, "bm25_topk_dev: bad arguments");
     ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
-    rag_bm25_index* ix = h->bm25;
     const int32_t* tenants = nullptr;
     int rc = bm25_tenant_args(h, ix, tenant, qt, &tenants);
     if (rc) return rc;
@@ -2395,4 +2523,94 @@ int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc
     std::unique_ptr<rag_bm25_index> ix;         // dropped when the call returns
     if (int rc = bm25_build(h, indptr, doc, tf, doc_len, idf, n_docs, n_terms, avgdl, k1, b, &ix)) return rc;
     return bm25_run(h, ix.get(), term_ptr, terms, Q, 1, 1, -1, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+// ---- the learned-sparse inverted index (rag_sparse_*) ---------------------------------------------------------------------------
+// A second resident index beside the BM25 postings, in its own slot (rag_ctx::sparse): term-major (doc i32, weight f32) postings of
+// a learned-sparse model - bge-m3's lexical head, SPLADE, any {token id: weight} map - and queries whose tokens carry a float32
+// weight. score(q, d) = sum over the query's tokens IN ORDER of (double)qw * (double)w[term, d], float64; the top-k holds only
+// documents with score > 0. Everything but the posting form is the BM25 machinery above: metadata and bracket tables (idf = 1),
+// the per-call plan (its float64 slot carries the query weight), staged thresholds, the merges, the visibility rules.
+void sparse_free(rag_ctx* h) {
+    delete h->sparse;
+    h->sparse = nullptr;
+}
+
+int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_docs, int64_t n_terms) {
+    ARG_CHECK(h, n_docs >= 1 && n_terms >= 1 && n_docs < 0x7fffffff, "sparse_load: need n_docs >= 1 and n_terms >= 1");
+    ARG_CHECK(h, indptr != nullptr && indptr[0] == 0, "sparse_load: indptr must start at 0");
+    for (int64_t t = 0; t < n_terms; ++t)
+        ARG_CHECK(h, indptr[t + 1] >= indptr[t] && indptr[t + 1] - indptr[t] <= n_docs,
+                  "sparse_load: indptr must be non-decreasing with at most n_docs postings per term");
+    const int64_t nnz = indptr[n_terms];
+    ARG_CHECK(h, nnz == 0 || (doc && weight), "sparse_load: null postings");
+    for (int64_t t = 0; t < n_terms; ++t)
+        for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p) {
+            ARG_CHECK(h, doc[p] >= 0 && doc[p] < n_docs && (p == indptr[t] || doc[p] > doc[p - 1]),
+                      "sparse_load: document numbers of a term must be strictly ascending and in [0, n_docs)");
+            ARG_CHECK(h, std::isfinite(weight[p]) && weight[p] > 0.0f, "sparse_load: weights must be finite and > 0");
+        }
+    const bm_builder B = {h, "sparse_load", false};
+    std::unique_ptr<rag_bm25_index> ix = bm_new_segment(nullptr, 0, n_docs, n_terms);
+    ix->nnz = nnz;
+    ix->normalize = 0;                                   // scores are raw
+    std::vector<bm_term_meta> meta_h;
+    ix->tab_entries = bm_plan_terms(indptr, n_terms, n_docs, nullptr, n_docs, &meta_h);
+    hipStream_t st = h->stream;
+    auto enqueue = [&]() -> int {
+        int rc;
+        if ((rc = bm_prepare_segment(B, ix.get(), meta_h, {false, false, false, false, false}))) return rc;
+        if ((rc = B.alloc(ix->wf, (size_t)nnz + 8))) return rc;                  // the same 8 postings of padding as doc
+        HIP_TRY(h, hipMemsetAsync(ix->wf + nnz, 0, 8 * sizeof(float), st));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->wf, weight, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
+        return RAG_OK;
+    };
+    if (int rc = bm_finish_segment(B, ix.get(), enqueue())) return rc;
+    sparse_free(h);
+    h->sparse = ix.release();
+    h->sparse_stale = false;
+    return RAG_OK;
+}
+
+int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out) {
+    const rag_bm25_index* ix = h->sparse;
+    if (n_docs_out) *n_docs_out = ix ? ix->n_docs : 0;
+    if (n_terms_out) *n_terms_out = ix ? ix->n_terms : 0;
+    if (nnz_out) *nnz_out = ix ? ix->nnz : 0;
+    if (hbm_bytes_out)
+        *hbm_bytes_out = ix ? (int64_t)(ix->doc.size() * 4 + ix->wf.size() * 4 + ix->meta.size() * sizeof(bm_term_meta) + ix->range_tab.size() * 4) : 0;
+    return RAG_OK;
+}
+int64_t sparse_n_docs(const rag_ctx* h) { return h->sparse ? h->sparse->n_docs : -1; }
+int sparse_fresh(rag_ctx* h) { return h->sparse ? bm25_check_fresh(h, h->sparse) : RAG_OK; }
+
+// without a dense index of the same rows the ids are row numbers and there is nothing a tenant could be looked up in
+static int sparse_args(rag_ctx* h, const void* term_ptr, const void* qweights, int tenant) {
+    ARG_CHECK(h, h->sparse != nullptr, "no sparse index loaded (rag_sparse_load_host)");
+    ARG_CHECK(h, term_ptr != nullptr && qweights != nullptr, "sparse: null query arrays");
+    if (int rc = bm25_check_fresh(h, h->sparse)) return rc;
+    ARG_CHECK(h, tenant < 0 || (h->index_loaded && h->tenants != nullptr && h->n_rows == h->sparse->n_docs),
+              "sparse: a tenant filter needs a dense index of the same rows with rag_index_set_tenants_host");
+    return RAG_OK;
+}
+
+int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant,
+                     int64_t* ids_out, int32_t* rows_out, double* scores_out) {
+    ARG_CHECK(h, ids_out && scores_out, "sparse_topk: null output");
+    if (int rc = sparse_args(h, term_ptr, qweights, tenant)) return rc;
+    return bm25_run(h, h->sparse, term_ptr, terms, Q, k, 0, tenant, ids_out, rows_out, scores_out, nullptr, nullptr, {nullptr, nullptr}, qweights);
+}
+
+int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out) {
+    ARG_CHECK(h, out, "sparse_scores: null output");
+    if (int rc = sparse_args(h, term_ptr, qweights, -1)) return rc;
+    return bm25_run(h, h->sparse, term_ptr, terms, Q, 1, 1, -1, nullptr, nullptr, nullptr, nullptr, out, {nullptr, nullptr}, qweights);
+}
+
+int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
+    if (int rc = sparse_args(h, term_ptr_dev, qweights_dev, tenant)) return rc;
+    h->sparse->call_qw = qweights_dev;
+    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, {nullptr, nullptr});
 }

@@ -190,6 +190,8 @@ struct rag_ctx : rag_device_mem {
     double last_eps = 0;
 
     rag_bm25_index* bm25 = nullptr;
+    rag_bm25_index* sparse = nullptr;        // learned-sparse postings (rag_sparse_load_host): a slot of its own beside the BM25 postings
+    bool sparse_stale = false;               // rows were inserted or compacted since they were loaded: sparse entry points refuse until a reload
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
     int pair_format = RAG_PAIR_BERT;         // rag_ce_set_pair_format: read while a pair-building call enqueues
@@ -395,7 +397,8 @@ static inline int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int
 }
 void comm_free(rag_ctx* h);
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr});
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr},
+                const float* qweights_dev = nullptr);
 // the query terms and what bounds a negative raw BM25 score from them (bm25_negative_bound_args)
 struct linear_neg_bound { const int32_t* term_ptr; double per_token; };
 int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bound nb, int Q, int64_t n, const double* temporal,

@@ -1080,6 +1080,7 @@ int dense_free(rag_ctx* h) {
     h->cap32 = h->cap_ids = h->cap_ten = h->cap_vis = 0;
     h->bm25_stale = false;
     h->bm25_compacted = false;
+    h->sparse_stale = false;
     h->n_rows = h->n_rows_pad = 0;
     h->n_reserved = 0;
     h->index_loaded = false;

@@ -326,6 +326,7 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     h->n_rows = need;
     if (has_tok) h->tok_rows = need;
     h->bm25_stale = true;
+    h->sparse_stale = true;
     live_rows_changed(h);
     return RAG_OK;
 }
@@ -504,6 +505,7 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     h->vis.reset();
     h->cap_vis = 0;
     h->n_deleted = 0;
+    h->sparse_stale = true;                  // learned-sparse postings are not renumbered: a reload makes them current
     if (np.p) {
         bm25_compact_commit(h, np.p);
         np.p = nullptr;

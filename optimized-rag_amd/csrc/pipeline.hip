@@ -14,6 +14,8 @@
 
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
+int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st);
 int64_t bm25_n_docs(const rag_ctx* h);
 int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
                  int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
@@ -25,15 +27,20 @@ int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, in
 // workgroups leave room for ONE 20-KiB BM25 workgroup per CU - but the BM25 stages fill the thin opening stages, selects and
 // the rescoring of the dense leg: 1024-query hybrid batches 6.85 -> 6.58 ms on one box (A/B by option fork_max_q).
 // Option no_fork keeps the legs in line always; fork_max_q lowers the largest batch that forks.
+// qweights_dev != null: the second leg is the learned-sparse index (rag_hybrid_sparse_rrf_dev; no per-query tenants there).
 #define RAG_FORK_MAX_Q 4096
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt) {
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt, const float* qweights_dev) {
     int64_t* const bm_ids = lists_dev + (size_t)Q * pool;
+    auto keyword_leg = [&](double* scores, hipStream_t s) -> int {
+        if (qweights_dev != nullptr) return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, Q, pool, tenant, bm_ids, nullptr, scores, s);
+        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores, nullptr, s, qt);
+    };
     const int fork_max = h->opt.fork_max_q > 0 ? h->opt.fork_max_q : RAG_FORK_MAX_Q;
     if (Q > fork_max || h->opt.no_fork) {
         int rc = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);
         if (rc) return rc;
-        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores_ws_dev, nullptr, st, qt);
+        return keyword_leg(scores_ws_dev, st);
     }
     if (!h->side_stream) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
@@ -45,7 +52,7 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
     // inputs are ready wherever the caller's stream is now (the device copy of per-query tenants among them: written on st before this)
     HIP_TRY(h, hipEventRecord(h->ev_fork, st));
     HIP_TRY(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-    int rc = bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, h->side_scores, nullptr, h->side_stream, qt);
+    int rc = keyword_leg(h->side_scores, h->side_stream);
     // the join is recorded and waited for even if a leg failed to launch: the caller's stream must never run ahead of the side stream
     HIP_TRY(h, hipEventRecord(h->ev_join, h->side_stream));
     const int rc2 = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);

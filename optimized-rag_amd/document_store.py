@@ -288,6 +288,60 @@ class GpuDocumentIndex:
             out.append(d)
         return out
 
+    # ---- learned-sparse retrieval (sparse.LexicalPostings; rag_sparse_*) ---------------------------------------------------
+    @_locked
+    def load_lexical(self, postings) -> None:
+        """Make the lexical weights of the loaded rows searchable: `postings` is a sparse.LexicalPostings over exactly the rows of
+        this index, in row order (e.g. LexicalPostings.from_texts(self.embeddings, contents)). Inserts and compaction leave them
+        stale - search_lexical then answers [] - until this is called again with postings of the current rows."""
+        if postings.n_docs != len(self.rows):
+            raise ValueError(f"load_lexical: postings of {postings.n_docs} documents for an index of {len(self.rows)} rows")
+        postings.load(self.engine)
+
+    def search_lexical(self, agent_id: str, query: str, top_k: int = 5, mode: str = "dense+sparse", pool: int = 100,
+                       rrf_k: int = 60) -> List[Dict[str, Any]]:
+        """First-stage retrieval with the embedder's lexical head. mode "sparse": the rows whose lexical weights share a token
+        with the query's, by sum of weight products (rag_sparse_topk_host). mode "dense+sparse": reciprocal rank fusion of the
+        dense top-`pool` (what `search` ranks by) and the sparse top-`pool`, dense list first. The query goes through ONE
+        `encode_multi` forward for both its dense vector and its lexical map. Result dicts are `search`'s (without embeddings)
+        plus `sparse_score` (0.0 for a fused hit the sparse list does not hold) and, fused, `rrf_score`; `score` is what the
+        list is ranked by. Errors are logged and answered with []."""
+        try:
+            if mode not in ("dense+sparse", "sparse"):
+                raise ValueError(f"unknown mode {mode!r}")
+            fused = mode == "dense+sparse"
+            out = self.embeddings.encode_multi([query], return_dense=fused, return_sparse=True, return_colbert_vecs=False)
+            with self._lock:
+                return self._search_lexical_locked(agent_id, out, top_k, fused, pool, rrf_k)
+        except Exception as e:
+            logger.error("Lexical search failed: %s", e)
+            return []
+
+    def _search_lexical_locked(self, agent_id, enc, top_k, fused, pool, rrf_k):
+        from .sparse import LexicalPostings
+        if agent_id is not None and str(agent_id) not in self._tenant_id:
+            return []
+        tenant = -1 if agent_id is None else self._tenant_id[str(agent_id)]
+        ptr, terms, weights = LexicalPostings.encode_queries(enc["lexical_weights"])
+        n = max(top_k, pool) if fused else top_k
+        _, s_rows, s_scores = self.engine.sparse_topk(ptr, terms, weights, n, tenant=tenant)
+        if not fused:
+            hits = [(int(r), {"score": float(s), "sparse_score": float(s)}) for r, s in zip(s_rows[0], s_scores[0]) if r >= 0]
+        else:
+            q = np.asarray(enc["dense_vecs"], dtype=np.float32).reshape(1, self.dim)
+            _, d_rows, _ = self.engine.dense_topk(q, n, tenant=tenant)
+            lists = np.stack([d_rows[0], s_rows[0]]).astype(np.int64)[None]                 # rows as keys: [1, 2, n], -1 padded
+            keys, rrf, _ = self.engine.rrf_fuse(lists, rrf_k=rrf_k, top_k=top_k)
+            sparse_of = {int(r): float(s) for r, s in zip(s_rows[0], s_scores[0]) if r >= 0}
+            hits = [(int(r), {"score": float(f), "sparse_score": sparse_of.get(int(r), 0.0), "rrf_score": float(f)})
+                    for r, f in zip(keys[0], rrf[0]) if r >= 0]
+        res = []
+        for r, extra in hits:
+            row = self.rows[r]
+            res.append({"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                        "metadata": row.get("metadata") or {}, **extra})
+        return res
+
     def search_many(self, agent_id: str, queries: List[str], top_k: int = 5, with_embeddings: bool = True) -> List[List[Dict[str, Any]]]:
         """Batched `search` (the reference agent can only submit one query per call, so nothing in
         its surface reaches the batched throughput): ONE embedding call for all queries when the service offers

@@ -1,0 +1,103 @@
+"""Host-side builder of the learned-sparse inverted index: {token id: weight} maps -> term-major CSR postings.
+
+A learned-sparse model (bge-m3's lexical head through `LocalEmbeddingService.encode_multi`, SPLADE, anything that gives a
+{token id: weight} map per text) scores a (query, document) pair as the sum over their shared token ids of the product of the two
+weights. The semantics are restated from FlagEmbedding / SPLADE practice; parity with those upstream implementations is not
+pinned by a test. Scoring runs on the GPU (csrc/bm25.hip, the learned-sparse form) through rag_sparse_load_host /
+rag_sparse_topk_* / rag_hybrid_sparse_rrf_dev; this module is the counterpart of bm25.Bm25Postings for that index.
+"""
+import numpy as np
+
+
+def _flatten(maps):
+    """List of {token id: weight} -> (owner int64, token int64, weight float32), entries in map order."""
+    owner, tok, w = [], [], []
+    for i, m in enumerate(maps):
+        owner.extend([i] * len(m))
+        tok.extend(int(k) for k in m.keys())
+        w.extend(float(v) for v in m.values())
+    return np.asarray(owner, dtype=np.int64), np.asarray(tok, dtype=np.int64), np.asarray(w, dtype=np.float64).astype(np.float32)
+
+
+class LexicalPostings:
+    """CSR postings (term-major, docs strictly ascending inside a term) of float32 weights > 0. A term number is the model's
+    token id, so queries need no vocabulary lookup."""
+
+    def __init__(self, indptr, doc, weight, n_docs):
+        self.indptr, self.doc, self.weight, self._n_docs = indptr, doc, weight, int(n_docs)
+
+    @property
+    def n_docs(self):
+        return self._n_docs
+
+    @property
+    def n_terms(self):
+        return int(self.indptr.shape[0] - 1)
+
+    @property
+    def nnz(self):
+        return int(self.doc.shape[0])
+
+    @classmethod
+    def from_weights(cls, maps, n_terms=None):
+        """maps[d] = {token id: weight} of document d. Weights become float32; an entry whose float32 weight is not > 0 is left
+        out (it could add nothing), a weight that is not finite as float32 or a token id outside [0, n_terms) raises ValueError. n_terms defaults
+        to the largest token id + 1."""
+        n = len(maps)
+        if n < 1:
+            raise ValueError("from_weights: at least one document")
+        owner, tok, w = _flatten(maps)
+        if not np.isfinite(w).all():
+            raise ValueError("from_weights: non-finite weight")
+        keep = w > 0
+        owner, tok, w = owner[keep], tok[keep], w[keep]
+        V = int(n_terms) if n_terms is not None else (int(tok.max()) + 1 if tok.size else 1)
+        if V < 1 or (tok.size and (int(tok.min()) < 0 or int(tok.max()) >= V)):
+            raise ValueError(f"from_weights: token ids must lie in [0, {V})")
+        key = tok * n + owner
+        order = np.argsort(key, kind="stable")             # term-major, documents ascending
+        key = key[order]
+        if key.size > 1 and not (np.diff(key) > 0).all():
+            raise ValueError("from_weights: a token id occurs twice in one document's map")
+        indptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount(tok, minlength=V), out=indptr[1:])
+        return cls(indptr, (key % n).astype(np.int32), np.ascontiguousarray(w[order]), n)
+
+    @classmethod
+    def from_texts(cls, service, texts, batch=256, n_terms=None):
+        """Lexical weights of `texts` from the service's lexical head (`encode_multi`, `batch` texts per call), then from_weights.
+        n_terms defaults to the model's vocabulary size."""
+        maps = []
+        for b in range(0, len(texts), batch):
+            out = service.encode_multi(texts[b:b + batch], return_dense=False, return_sparse=True, return_colbert_vecs=False)
+            maps.extend(out["lexical_weights"])
+        if n_terms is None:
+            n_terms = getattr(service, "cfg", {}).get("vocab_size")
+        return cls.from_weights(maps, n_terms)
+
+    @staticmethod
+    def encode_queries(maps):
+        """List of {token id: weight} -> (term_ptr int32 [Q + 1], terms int32, weights float32). Each query's terms come in
+        ASCENDING token id: the score is a float64 sum in query-token order, so this fixes its bits. Nothing is filtered: a
+        token outside the vocabulary or with a weight that is not > 0 adds nothing on the device."""
+        owner, tok, w = _flatten(maps)
+        order = np.lexsort((tok, owner))
+        ptr = np.zeros(len(maps) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(owner, minlength=len(maps)), out=ptr[1:])
+        if tok.size and (int(tok.min()) < -2**31 or int(tok.max()) >= 2**31):
+            raise ValueError("encode_queries: token ids must fit int32")
+        return ptr.astype(np.int32), tok[order].astype(np.int32), np.ascontiguousarray(w[order])
+
+    def shard(self, begin, end):
+        """Doc-partitioned slice [begin, end) with LOCAL document numbers. Raw scores need no corpus-wide statistic: merging the
+        shards' top-k lists (rag_merge_topk_dev over global ids) reproduces the unsharded list."""
+        counts = np.diff(self.indptr)
+        term_of = np.repeat(np.arange(counts.shape[0], dtype=np.int64), counts)
+        keep = (self.doc >= begin) & (self.doc < end)
+        indptr = np.zeros(counts.shape[0] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(term_of[keep], minlength=counts.shape[0]), out=indptr[1:])
+        return LexicalPostings(indptr, (self.doc[keep] - begin).astype(np.int32), self.weight[keep].copy(), end - begin)
+
+    def load(self, engine):
+        engine.sparse_load(self.indptr, self.doc, self.weight, self.n_docs)
+        return self
