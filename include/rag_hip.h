@@ -21,14 +21,15 @@
  *   - Ordering (pinned by tests/test_stream_order_gpu.py). A *_dev call returns once its work is queued on `stream`; all it
  *     reads and writes is ordered on that stream as if it had run there alone: inputs produced earlier on the stream are
  *     seen, outputs may be consumed by later work on it, no other stream and no device-wide wait is needed. The calls that
- *     do wait for `stream` say so below (rag_tokens_append_dev; any call that has to grow a workspace it used before frees
+ *     do wait for `stream` say so below (rag_tokens_append_dev, rag_tokvec_append_dev; any call that has to grow a workspace it used before frees
  *     the old one first, which waits for the device - the first call of a larger shape, not the steady state).
  *     A *_host call may be made while *_dev work of the handle is pending, from any thread, and behaves as if it ran after
  *     that work: it first waits for the device when a *_dev call was made on the handle since the last such wait (a
  *     device-wide wait, so *_dev work on any stream is covered; nothing is added to a *_host call that follows a *_host
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_tokens_load_wide_host,
- *     rag_tokens_reserve_wide, rag_bm25_load_host, rag_sparse_load_host,
+ *     rag_tokens_reserve_wide, rag_bm25_load_host, rag_sparse_load_host, rag_tokvec_reserve, rag_tokvec_load_host,
+ *     rag_tokvec_append_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
  *     rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
@@ -692,6 +693,73 @@ int rag_ce_build_pairs_dev(rag_handle_t h, const int32_t* q_tok_dev, const int32
                            int32_t* ids_out_dev, int32_t* tt_out_dev, int32_t* lens_out_dev, void* stream);
 int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* cand_dev, int n_queries, int pool, int k,
                         int64_t* ids_out_dev, double* scores_out_dev, float* logits_out_dev, void* stream);
+
+/* ---- resident token-vector store and late-interaction rerank on the device (no reference counterpart; the token vectors are the
+ *      tok_out of rag_embed_multi_*). rag_maxsim_* scores pairs whose float32 vectors the caller passes; here the passages' vectors
+ *      are computed once at ingest and kept in HBM as packed fp16 rows [rows][dim] with int64 offsets [n_docs + 1], so that a query
+ *      costs its own forward only and a rerank reads half the bytes. Document i is row i of the dense index; a document with 0
+ *      rows is legal. dim is a multiple of 32 in [32, 1024] (the limits of rag_maxsim_*), else RAG_ERR_ARG.
+ * rag_tokvec_reserve: room for n_docs_total (>= 1) documents and rows_total (>= 0) rows; replaces any earlier store.
+ * rag_tokvec_append_dev: the next n_docs documents from DEVICE memory: vecs_dev float32 [rows][dim], row_off_dev int64 [n_docs + 1] -
+ *   the tok_out / row_off_out of rag_embed_multi_dev as they are. Offsets are taken relative to row_off[0] (rows row_off[0] ...
+ *   row_off[n_docs] - 1 of vecs_dev are read). Like rag_tokens_append_dev it waits for `stream` and returns once the rows are
+ *   resident and checked. A block is rejected whole with RAG_ERR_ARG when it comes before a reserve, goes past either reservation,
+ *   has a negative first or a decreasing offset, or holds a value that rounds to NaN or inf as fp16 (NaN, inf, |x| >= 65520; a
+ *   float32 in (65504, 65520) rounds to 65504 and is accepted): the counts do
+ *   not move and the same block may be appended again. rag_tokvec_append_host: the same arguments from host arrays, staged in
+ *   pieces of at most 64 Mi floats. rag_tokvec_load_host: reserve(n_docs, off[n_docs] - off[0], dim) + append_host.
+ *   Conversion is float32 -> fp16 round to nearest even, on the device: the stored bits are numpy's x.astype(float16). Rows are not
+ *   renormalised afterwards.
+ * rag_tokvec_info: documents and rows appended so far, dim, HBM bytes of the reservation; all 0 without a store; host state only.
+ * rag_tokvec_fetch_host: the stored rows of one document as float32 (exact) [*n_rows_out][dim], for tests; *n_rows_out is written
+ *   first, RAG_ERR_ARG when it exceeds cap_rows or doc is outside the documents appended.
+ * rag_tokvec_rerank_dev: for each of n_queries queries - float32 token vectors q_vecs [rows][dim] (16-byte aligned), int64 q_off
+ *   [n_queries + 1], trusted as in rag_maxsim_dev - and each of its `pool` candidate rows cand_rows [Q][pool] int32:
+ *     score[q][j] = (1 / nq) * sum_i max_r <vq[i], store[cand[q][j]][r]>
+ *   then the top k by score descending, equal scores in candidate order. 0 < k <= pool <= 256, n_queries * pool < 2^24 (one
+ *   workgroup per slot in one launch), else RAG_ERR_ARG. A slot with cand < 0, a row at or
+ *   past the store's documents, a document with 0 rows or a query with 0 rows scores 0.0 and is skipped by the top-k. Outputs:
+ *   ids_out [Q][k] int64 (the index's id mapping - explicit ids or id_base + row; -1 for a scored row the index does not have, e.g. a store filled
+ *   ahead of the inserts: rows_out still names it; without an index the row numbers), rows_out
+ *   [Q][k] int32 (may be NULL), scores_out [Q][k] float64 = the float32 pair score widened, padded with -1 / -1 / 0.0;
+ *   pair_scores_out [Q][pool] float32 (may be NULL) every slot's score. Explicit rows: row visibility (deletes, tenants) is not
+ *   looked at. _host: the same from host arrays (q_off checked), synchronous.
+ *   Numerics: the float32 query is split into hi + lo fp16, the stored fp16 rows are exact MFMA operands, two
+ *   mfma_f32_16x16x32_f16 per product (lo_q * d + hi_q * d) with fp32 accumulation, per-query maxima summed in float64 in query
+ *   order: within 1e-4 of float64 MaxSim over the STORED (fp16-rounded) vectors, within 1e-3 of float64 MaxSim over the original
+ *   float32 unit vectors (fp16 rounding moves a dot of unit vectors by at most 2^-11). A pair's score is a function of its own
+ *   rows only: bit-identical from run to run, whatever pool, neighbours or batch surround it.
+ * rag_retrieve_maxsim_dev: candidates, MaxSim rerank and top-k in one device-resident call, as rag_retrieve_rerank_dev does for the
+ *   cross-encoder. mode 0: the dense top-`pool` of q_emb [Q][dim index]; mode 1: the top-`pool` of dense + learned-sparse RRF
+ *   (term_ptr / terms / qweights as rag_hybrid_sparse_rrf_dev, rrf_k), with tenant and deleted-row filtering as in those searches;
+ *   then rag_tokvec_rerank_dev over those rows. ids_out / scores_out [Q][k], cand_out [Q][pool] int64 (may be NULL) the candidate
+ *   ids. 1 <= n_queries <= 65535, 0 < k <= pool <= 256. Bit-identical to rag_dense_topk_dev (mode 0) or rag_hybrid_sparse_rrf_dev
+ *   with k = pool (mode 1) followed by rag_tokvec_rerank_dev on the rows. Needs store documents == index rows, else RAG_ERR_STATE.
+ *   Workspaces are handle-owned and grown as the preamble says (the first call of a larger shape frees the old one, which waits).
+ * Live writes, as the BM25 postings: rag_index_compact / rag_index_compact_bm25 mark the store STALE when deleted rows are removed;
+ *   every rag_tokvec_rerank_* and rag_retrieve_maxsim_dev then returns RAG_ERR_STATE until rag_tokvec_reserve / rag_tokvec_load_host
+ *   runs again (the handle stays usable; a compaction that finds nothing deleted marks nothing). rag_index_insert_host leaves the
+ *   store alone: rag_retrieve_maxsim_dev returns RAG_ERR_STATE until appends cover the new rows (reserve headroom for them).
+ *   Deletes need nothing: the composite's searches hide deleted rows, and the explicit-row entries do not look.
+ * Ordering: reserve / load / append_host / fetch / rerank_host are host calls (they wait for queued *_dev work); the _dev calls
+ *   follow the preamble, rag_tokvec_append_dev waiting for `stream` as said.
+ * Sharding: raw MaxSim scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev. */
+int rag_tokvec_reserve(rag_handle_t h, int64_t n_docs_total, int64_t rows_total, int dim);
+int rag_tokvec_append_dev(rag_handle_t h, const float* vecs_dev, const int64_t* row_off_dev, int64_t n_docs, void* stream);
+int rag_tokvec_append_host(rag_handle_t h, const float* vecs_host, const int64_t* row_off_host, int64_t n_docs);
+int rag_tokvec_load_host(rag_handle_t h, const float* vecs_host, const int64_t* off_host, int64_t n_docs, int dim);
+int rag_tokvec_info(rag_handle_t h, int64_t* n_docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out);
+int rag_tokvec_fetch_host(rag_handle_t h, int64_t doc, float* out_host, int64_t cap_rows, int64_t* n_rows_out);
+int rag_tokvec_rerank_dev(rag_handle_t h, const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev,
+                          int n_queries, int pool, int k, int64_t* ids_out_dev, int32_t* rows_out_dev /*may be NULL*/,
+                          double* scores_out_dev, float* pair_scores_out_dev /*may be NULL*/, void* stream);
+int rag_tokvec_rerank_host(rag_handle_t h, const float* q_vecs_host, const int64_t* q_off_host, const int32_t* cand_rows_host,
+                           int n_queries, int pool, int k, int64_t* ids_out_host, int32_t* rows_out_host /*may be NULL*/,
+                           double* scores_out_host, float* pair_scores_out_host /*may be NULL*/);
+int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                            const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool,
+                            int k, int rrf_k, int tenant, int mode, int64_t* ids_out_dev, double* scores_out_dev,
+                            int64_t* cand_out_dev /*may be NULL*/, void* stream);
 
 /* ---- agents mixed in one batch: a tenant PER QUERY. Each entry takes the arguments of its namesake with
  *      `const int32_t* tenants_host` [n_queries] where the namesake has `int tenant`: query i is filtered by tenants_host[i],

@@ -152,6 +152,15 @@ _SIGS = {
     "rag_maxsim_dev": ([_P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
     "rag_lexical_match_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P], C.c_int),
     "rag_lexical_match_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P], C.c_int),
+    "rag_tokvec_reserve": ([_P, C.c_int64, C.c_int64, C.c_int], C.c_int),
+    "rag_tokvec_append_dev": ([_P, _P, _P, C.c_int64, _P], C.c_int),
+    "rag_tokvec_append_host": ([_P, _P, _P, C.c_int64], C.c_int),
+    "rag_tokvec_load_host": ([_P, _P, _P, C.c_int64, C.c_int], C.c_int),
+    "rag_tokvec_info": ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64)], C.c_int),
+    "rag_tokvec_fetch_host": ([_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)], C.c_int),
+    "rag_tokvec_rerank_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
+    "rag_tokvec_rerank_host": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
+    "rag_retrieve_maxsim_dev": ([_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "rag_model_seq_limit": ([_P, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
@@ -977,6 +986,117 @@ class RagEngine:
         self._check(self.lib.rag_lexical_match_dev(self.h, p(q_ids), p(q_weights), p(q_lens), q_ids.shape[0], q_ids.shape[1], p(d_ids),
                                                    p(d_weights), p(d_lens), d_ids.shape[0], d_ids.shape[1], p(pair_q), p(pair_d),
                                                    pair_q.shape[0], _ptr(sk), sk.shape[0], p(out), st), "rag_lexical_match_dev")
+
+    # ---- resident token-vector store and late-interaction rerank (rag_tokvec_*, rag_retrieve_maxsim_dev) ---------
+    def tokvec_reserve(self, n_docs_total, rows_total, dim):
+        """Room for n_docs_total documents and rows_total fp16 token-vector rows of `dim`; replaces any earlier store."""
+        self._check(self.lib.rag_tokvec_reserve(self.h, int(n_docs_total), int(rows_total), int(dim)), "rag_tokvec_reserve")
+        self._tv_dim = int(dim)
+
+    def _tokvec_dim_check(self, width, what):
+        if int(width) != getattr(self, "_tv_dim", int(width)):
+            raise RagError(f"{what}: vectors of width {int(width)} for a store of dim {self._tv_dim}")
+
+    def _tokvec_rerank_check(self, q_shape, q_rows_used, what):
+        """query vectors must be as wide as the store (the library reads rows of the STORE's dim) and hold every row the offsets name
+        (q_rows_used; None for device offsets, which are trusted as in maxsim_dev)"""
+        dim = self.tokvec_info()["dim"]
+        if dim and (len(q_shape) != 2 or int(q_shape[1]) != dim):
+            raise RagError(f"{what}: query vectors of shape {tuple(q_shape)} for a store of dim {dim}")
+        if q_rows_used is not None and q_rows_used > int(q_shape[0]):
+            raise RagError(f"{what}: the query offsets end at row {q_rows_used}, past the {int(q_shape[0])} query rows")
+
+    def tokvec_append(self, vecs, row_off):
+        """The next documents from host arrays: float32 [rows, dim], int64 row offsets [n + 1] (taken relative to row_off[0])."""
+        v, off = _np(vecs, np.float32), _np(row_off, np.int64)
+        if v.ndim != 2 or off.ndim != 1 or off.shape[0] < 1:
+            raise RagError("tokvec_append: expected vectors [rows, dim] and offsets [n + 1]")
+        self._tokvec_dim_check(v.shape[1], "tokvec_append")
+        if off.shape[0] > 1 and int(off[-1]) > v.shape[0]:
+            raise RagError("tokvec_append: the offsets end past the vectors")
+        self._check(self.lib.rag_tokvec_append_host(self.h, _ptr(v), _ptr(off), off.shape[0] - 1), "rag_tokvec_append_host")
+
+    def tokvec_append_dev(self, vecs, row_off, n_docs=None, stream=None):
+        """The same from CUDA tensors - the tok / row_off outputs of embed_multi_dev as they are; waits for `stream` and returns once
+        the rows are resident and checked."""
+        import torch
+        assert vecs.is_cuda and vecs.dtype == torch.float32 and vecs.is_contiguous() and row_off.is_cuda and row_off.dtype == torch.int64
+        self._tokvec_dim_check(vecs.shape[1], "tokvec_append_dev")
+        n = row_off.shape[0] - 1 if n_docs is None else int(n_docs)
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._check(self.lib.rag_tokvec_append_dev(self.h, C.c_void_p(vecs.data_ptr()), C.c_void_p(row_off.data_ptr()), n, st),
+                    "rag_tokvec_append_dev")
+
+    def tokvec_load(self, vecs, offsets):
+        """reserve + append of a whole store from host arrays: float32 [rows, dim], int64 offsets [n_docs + 1]."""
+        v, off = _np(vecs, np.float32), _np(offsets, np.int64)
+        if v.ndim != 2 or off.ndim != 1 or off.shape[0] < 2 or int(off[-1]) > v.shape[0]:
+            raise RagError("tokvec_load: expected vectors [rows, dim] and offsets [n_docs + 1] that end inside them")
+        self._check(self.lib.rag_tokvec_load_host(self.h, _ptr(v), _ptr(off), off.shape[0] - 1, int(v.shape[1])), "rag_tokvec_load_host")
+        self._tv_dim = int(v.shape[1])
+
+    def tokvec_info(self):
+        """{"n_docs", "rows", "dim", "hbm_bytes"} of the resident token-vector store (all 0 without one)."""
+        docs, rows, dim, nb = C.c_int64(), C.c_int64(), C.c_int(), C.c_int64()
+        self._check(self.lib.rag_tokvec_info(self.h, C.byref(docs), C.byref(rows), C.byref(dim), C.byref(nb)), "rag_tokvec_info")
+        return {"n_docs": int(docs.value), "rows": int(rows.value), "dim": int(dim.value), "hbm_bytes": int(nb.value)}
+
+    def tokvec_fetch(self, doc):
+        """The stored (fp16-rounded) rows of one document as float32 [n, dim]."""
+        dim = self.tokvec_info()["dim"]
+        n = C.c_int64()
+        rc = self.lib.rag_tokvec_fetch_host(self.h, int(doc), None, 0, C.byref(n))
+        if rc != 0 and n.value <= 0:
+            self._check(rc, "rag_tokvec_fetch_host")
+        out = np.empty((int(n.value), dim), dtype=np.float32)
+        if n.value:
+            self._check(self.lib.rag_tokvec_fetch_host(self.h, int(doc), _ptr(out), int(n.value), C.byref(n)), "rag_tokvec_fetch_host")
+        return out
+
+    def tokvec_rerank(self, q_vecs, q_off, cand_rows, k):
+        """MaxSim of each query's token vectors (float32 [rows, dim], int64 q_off [Q + 1]) against its candidate rows (int32
+        [Q, pool], -1 = empty) over the resident store -> (ids [Q, k] int64, rows [Q, k] int32, scores [Q, k] float64,
+        pair_scores [Q, pool] float32): score descending, equal scores in candidate order, -1 / -1 / 0.0 padded."""
+        q, qo, cand = _np(q_vecs, np.float32), _np(q_off, np.int64), _np(cand_rows, np.int32)
+        if q.ndim != 2 or cand.ndim != 2 or qo.shape != (cand.shape[0] + 1,):
+            raise RagError("tokvec_rerank: expected query vectors [rows, dim], offsets [Q + 1] and candidate rows [Q, pool]")
+        self._tokvec_rerank_check(q.shape, int(qo[-1]), "tokvec_rerank")
+        Q, pool = cand.shape
+        ids, rows = np.empty((Q, k), dtype=np.int64), np.empty((Q, k), dtype=np.int32)
+        sc, ps = np.empty((Q, k), dtype=np.float64), np.empty((Q, pool), dtype=np.float32)
+        self._check(self.lib.rag_tokvec_rerank_host(self.h, _ptr(q), _ptr(qo), _ptr(cand), Q, pool, int(k), _ptr(ids), _ptr(rows), _ptr(sc),
+                                                    _ptr(ps)), "rag_tokvec_rerank_host")
+        return ids, rows, sc, ps
+
+    def tokvec_rerank_dev(self, q_vecs, q_off, cand_rows, k, ids_out, rows_out, scores_out, pair_scores_out=None, stream=None):
+        """The same on CUDA tensors (rows_out / pair_scores_out may be None); asynchronous on `stream`."""
+        import torch
+        Q, pool = cand_rows.shape
+        self._tokvec_rerank_check(tuple(q_vecs.shape), None, "tokvec_rerank_dev")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_tokvec_rerank_dev(self.h, p(q_vecs), p(q_off), p(cand_rows), int(Q), int(pool), int(k), p(ids_out), p(rows_out),
+                                                   p(scores_out), p(pair_scores_out), st), "rag_tokvec_rerank_dev")
+
+    def retrieve_maxsim_dev(self, q_emb, q_vecs, q_off, pool, k, term_ptr=None, terms=None, weights=None, rrf_k=60, tenant=-1, stream=None):
+        """Dense (term_ptr None) or dense + learned-sparse RRF candidates -> MaxSim over the resident token vectors -> top-k, all on
+        the device (CUDA tensors). Returns (ids [Q, k] int64, scores [Q, k] float64, candidates [Q, pool] int64)."""
+        import torch
+        Q, dev = q_emb.shape[0], q_emb.device
+        key = ("rm", Q, pool, k)
+        if getattr(self, "_rm_key", None) != key:
+            self._rm = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float64, device=dev),
+                        torch.empty((Q, pool), dtype=torch.int64, device=dev))
+            self._rm_key = key
+        ids, sc, cand = self._rm
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        mode = 0 if term_ptr is None else 1
+        self._tokvec_rerank_check(tuple(q_vecs.shape), None, "retrieve_maxsim_dev")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_retrieve_maxsim_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
+                                                     int(k), int(rrf_k), int(tenant), mode, p(ids), p(sc), p(cand), st),
+                    "rag_retrieve_maxsim_dev")
+        return ids, sc, cand
 
     def tokens_load(self, tokens, lens, id_bits=16):
         """Passage token store: tokens [N, L] int32 token ids without [CLS]/[SEP], lens [N]; row-aligned with the index.

@@ -70,6 +70,9 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
                         const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
                         int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out, double* scores_out, float* logits_out,
                         int64_t* cand_out, hipStream_t st, query_tenants qt);
+int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                        const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
+                        int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st);
 
 static thread_local std::string g_null_err = "null handle";
 
@@ -1115,6 +1118,76 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
     LOCK(h);
     DEV_ENTRY(h);
     return rerank_topk_dev(h, logits_dev, cand_dev, Q, pool, k, ids_out_dev, scores_out_dev, logits_out_dev, (hipStream_t)stream);
+}
+
+// ---- resident token-vector store and late-interaction rerank (tokvec.hip; the composite in pipeline.hip) ---------------------------
+int rag_tokvec_reserve(rag_handle_t h, int64_t n_docs_total, int64_t rows_total, int dim) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);                      // queued *_dev reranks read the store this call replaces
+    return tokvec_reserve(h, n_docs_total, rows_total, dim);
+}
+
+int rag_tokvec_append_dev(rag_handle_t h, const float* vecs_dev, const int64_t* row_off_dev, int64_t n_docs, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return tokvec_append(h, vecs_dev, row_off_dev, n_docs, (hipStream_t)stream, false);
+}
+
+int rag_tokvec_append_host(rag_handle_t h, const float* vecs_host, const int64_t* row_off_host, int64_t n_docs) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_append(h, vecs_host, row_off_host, n_docs, h->stream, true);
+}
+
+int rag_tokvec_load_host(rag_handle_t h, const float* vecs_host, const int64_t* off_host, int64_t n_docs, int dim) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_load_host(h, vecs_host, off_host, n_docs, dim);
+}
+
+int rag_tokvec_info(rag_handle_t h, int64_t* n_docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return tokvec_info(h, n_docs_out, rows_out, dim_out, hbm_bytes_out);
+}
+
+int rag_tokvec_fetch_host(rag_handle_t h, int64_t doc, float* out_host, int64_t cap_rows, int64_t* n_rows_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_fetch_host(h, doc, out_host, cap_rows, n_rows_out);
+}
+
+int rag_tokvec_rerank_dev(rag_handle_t h, const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev, int Q, int pool,
+                          int k, int64_t* ids_out_dev, int32_t* rows_out_dev, double* scores_out_dev, float* pair_scores_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return tokvec_rerank(h, q_vecs_dev, q_off_dev, cand_rows_dev, Q, pool, k, ids_out_dev, rows_out_dev, scores_out_dev, pair_scores_out_dev,
+                         (hipStream_t)stream);
+}
+
+int rag_tokvec_rerank_host(rag_handle_t h, const float* q_vecs_host, const int64_t* q_off_host, const int32_t* cand_rows_host, int Q, int pool,
+                           int k, int64_t* ids_out_host, int32_t* rows_out_host, double* scores_out_host, float* pair_scores_out_host) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_rerank_host(h, q_vecs_host, q_off_host, cand_rows_host, Q, pool, k, ids_out_host, rows_out_host, scores_out_host,
+                              pair_scores_out_host);
+}
+
+int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                            const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k,
+                            int tenant, int mode, int64_t* ids_out_dev, double* scores_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return retrieve_maxsim_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, tenant, mode,
+                               ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

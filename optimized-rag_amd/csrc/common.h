@@ -137,6 +137,11 @@ struct rag_device_mem : rag_index_mem {
     // tenant tile lists
     dev_buf<int32_t> qten;           // [>= n_queries]
     dev_buf<int32_t> union_tiles;    // [<= tiles of the index]
+    // resident token-vector store (tokvec.hip): packed fp16 rows, document i = rows [tv_off[i], tv_off[i + 1]) = row i of the index
+    dev_buf<half_t> tv;              // [tv_rows_cap][tv_dim]
+    dev_buf<int64_t> tv_off;         // [tv_docs_cap + 1], tv_off[0] = 0
+    dev_buf<int> tv_bad;             // [2] device counters of one append: values that are not finite as fp16, decreasing offsets
+    dev_buf<char> tv_ws;             // rag_tokvec_rerank_*: pair scores float32 [Q][pool] | scored rows int32 [Q][pool] (-1 = empty slot)
 };
 
 struct rag_ctx : rag_device_mem {
@@ -194,6 +199,10 @@ struct rag_ctx : rag_device_mem {
     bool sparse_stale = false;               // rows were inserted or compacted since they were loaded: sparse entry points refuse until a reload
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
+    int64_t tv_docs = 0, tv_rows = 0;        // token-vector store: documents / rows appended so far ...
+    int64_t tv_docs_cap = 0, tv_rows_cap = 0;    // ... and reserved (rag_tokvec_reserve); tv_docs_cap > 0 = a store exists
+    int tv_dim = 0;
+    bool tv_stale = false;                   // a compaction renumbered the rows since the store was filled: its entries refuse until a reload
     int pair_format = RAG_PAIR_BERT;         // rag_ce_set_pair_format: read while a pair-building call enqueues
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process. raise_lds: the
     // dynamic LDS each group of kernels was last raised to. dense.hip: the emit instantiations by [DENSE0][SMALLQ][FUSED], the
@@ -450,3 +459,17 @@ int lexical_match_host(rag_ctx* h, const int32_t* q_ids, const float* q_w, const
 int lexical_match_dev(rag_ctx* h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq, const int32_t* d_ids,
                       const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q, const int32_t* pair_d, int n_pairs,
                       const int32_t* skip_ids_host, int n_skip, float* out, hipStream_t st);
+// tokvec.hip: the resident token-vector store and MaxSim rerank over it. tokvec_rerank checks the store and its arguments, scores
+// [Q][pool] slots and selects through tokvec_topk (pipeline.hip: the kernel behind rag_rerank_topk_dev, without the sigmoid).
+int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim);
+int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t n_docs, hipStream_t st, bool host_ptrs);
+int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim);
+int tokvec_info(const rag_ctx* h, int64_t* docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out);
+int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int64_t* n_rows_out);
+int tokvec_usable(rag_ctx* h, const char* who);          // RAG_ERR_STATE without a store or with a stale one
+int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
+                  int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st);
+int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
+                       int32_t* rows_out, double* scores_out, float* pair_scores_out);
+int tokvec_topk(rag_ctx* h, const float* scores_dev, const int32_t* slot_rows_dev, int Q, int pool, int k, int64_t* ids_out, int32_t* rows_out,
+                double* scores_out, hipStream_t st);

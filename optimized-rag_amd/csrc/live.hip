@@ -506,6 +506,7 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     h->cap_vis = 0;
     h->n_deleted = 0;
     h->sparse_stale = true;                  // learned-sparse postings are not renumbered: a reload makes them current
+    if (h->tv_docs_cap > 0) h->tv_stale = true;      // nor are the resident token vectors (tokvec.hip)
     if (np.p) {
         bm25_compact_commit(h, np.p);
         np.p = nullptr;

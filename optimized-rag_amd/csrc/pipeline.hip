@@ -241,33 +241,74 @@ static int launch_build_pairs(rag_ctx* h, const int32_t* q_tok, const int32_t* q
     return launch_status(h);
 }
 
-// one workgroup per query, pool <= 256: stable rank by (sigmoid desc, candidate position asc)
+// one workgroup per query, pool <= 256: stable rank by (sigmoid desc, candidate position asc).
+// RAW (rag_tokvec_rerank_*, tokvec.hip): the score is the float32 itself, no sigmoid; slot_rows [Q][pool] int32 holds the row each
+// slot was scored for, -1 = an empty slot, skipped; ids_out gets the row's doc id - idmap[row] or id_base + row for a row of the
+// index (row < n_index), -1 for a row the index does not have (its id_base + row could be another row's explicit id); n_index < 0:
+// no index, the row number - rows_out (may be null) the row, padding -1 / -1 / 0.0; cand and logit_out are not read.
+template <bool RAW>
 __global__ __launch_bounds__(256) void rerank_topk_kernel(const float* __restrict__ logits, const int64_t* __restrict__ cand, int pool,
                                                            int k, int64_t* __restrict__ ids_out, double* __restrict__ score_out,
-                                                           float* __restrict__ logit_out) {
+                                                           float* __restrict__ logit_out, const int32_t* __restrict__ slot_rows,
+                                                           const int64_t* __restrict__ idmap, int64_t n_index, int64_t id_base,
+                                                           int32_t* __restrict__ rows_out) {
     __shared__ double s[256];
     __shared__ int ok[256];
     const int q = blockIdx.x, j = threadIdx.x;
     double mine = -1.0;
     int valid = 0;
     if (j < pool) {
-        valid = cand[(size_t)q * pool + j] >= 0;
-        if (valid) mine = 1.0 / (1.0 + exp(-(double)logits[(size_t)q * pool + j]));          // reranker.py:359
+        if constexpr (RAW) {
+            valid = slot_rows[(size_t)q * pool + j] >= 0;
+            if (valid) mine = (double)logits[(size_t)q * pool + j];
+        } else {
+            valid = cand[(size_t)q * pool + j] >= 0;
+            if (valid) mine = 1.0 / (1.0 + exp(-(double)logits[(size_t)q * pool + j]));          // reranker.py:359
+        }
     }
     s[j] = mine;
     ok[j] = valid;
     __syncthreads();
-    for (int i = j; i < k; i += 256) { ids_out[(size_t)q * k + i] = -1; score_out[(size_t)q * k + i] = 0.0; logit_out[(size_t)q * k + i] = 0.f; }
+    for (int i = j; i < k; i += 256) {
+        ids_out[(size_t)q * k + i] = -1;
+        score_out[(size_t)q * k + i] = 0.0;
+        if constexpr (RAW) {
+            if (rows_out) rows_out[(size_t)q * k + i] = -1;
+        } else {
+            logit_out[(size_t)q * k + i] = 0.f;
+        }
+    }
     __syncthreads();
     if (j < pool && valid) {
         int rank = 0;
         for (int i = 0; i < pool; ++i) rank += ok[i] && (s[i] > mine || (s[i] == mine && i < j));
         if (rank < k) {
-            ids_out[(size_t)q * k + rank] = cand[(size_t)q * pool + j];
             score_out[(size_t)q * k + rank] = mine;
-            logit_out[(size_t)q * k + rank] = logits[(size_t)q * pool + j];
+            if constexpr (RAW) {
+                const int64_t row = slot_rows[(size_t)q * pool + j];
+                ids_out[(size_t)q * k + rank] = n_index < 0 ? row : row >= n_index ? (int64_t)-1 : idmap != nullptr ? idmap[row] : id_base + row;
+                if (rows_out) rows_out[(size_t)q * k + rank] = (int32_t)row;
+            } else {
+                ids_out[(size_t)q * k + rank] = cand[(size_t)q * pool + j];
+                logit_out[(size_t)q * k + rank] = logits[(size_t)q * pool + j];
+            }
         }
     }
+}
+// the sigmoid instantiation, as rag_rerank_topk_dev and rag_retrieve_rerank_dev launch it
+static void launch_rerank_topk(const float* logits, const int64_t* cand, int Q, int pool, int k, int64_t* ids_out, double* scores_out,
+                               float* logits_out, hipStream_t st) {
+    launch(rerank_topk_kernel<false>, dim3(Q), dim3(256), 0, st, logits, cand, pool, k, ids_out, scores_out, logits_out, nullptr, nullptr,
+           (int64_t)0, (int64_t)0, nullptr);
+}
+
+// stable top-k of raw MaxSim scores over the slots tokvec_maxsim_kernel filled; ids follow the index's mapping, row numbers without one
+int tokvec_topk(rag_ctx* h, const float* scores_dev, const int32_t* slot_rows_dev, int Q, int pool, int k, int64_t* ids_out, int32_t* rows_out,
+                double* scores_out, hipStream_t st) {
+    const bool idx = h->index_loaded;
+    launch(rerank_topk_kernel<true>, dim3(Q), dim3(256), 0, st, scores_dev, nullptr, pool, k, ids_out, scores_out, nullptr, slot_rows_dev,
+           idx ? h->ids.get() : nullptr, idx ? h->n_rows : (int64_t)-1, idx ? h->id_base : (int64_t)0, rows_out);
+    return launch_status(h);
 }
 
 // The two pipeline kernels on their own, for the row-sharded composition (sharded.py::ShardedPipeline): candidates are
@@ -286,7 +327,7 @@ int rerank_topk_dev(rag_ctx* h, const float* logits_dev, const int64_t* cand_dev
                     float* logits_out, hipStream_t st) {
     ARG_CHECK(h, Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool && logits_dev && cand_dev && ids_out && scores_out && logits_out,
               "rerank_topk: 0 < k <= pool <= 256");
-    hipLaunchKernelGGL(rerank_topk_kernel, dim3(Q), dim3(256), 0, st, logits_dev, cand_dev, pool, k, ids_out, scores_out, logits_out);
+    launch_rerank_topk(logits_dev, cand_dev, Q, pool, k, ids_out, scores_out, logits_out, st);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -345,7 +386,7 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     if ((rc = launch_build_pairs(h, q_tok_dev, q_len_dev, Lq, cand, 0, P, pool, L_pair, cls_id, sep_id, pid, ptt, plen, st))) return rc;
     rc = ce_score(h, pid, ptt, plen, (int)P, L_pair, logit, st, false);
     if (rc) return rc;
-    hipLaunchKernelGGL(rerank_topk_kernel, dim3(Q), dim3(256), 0, st, logit, cand, pool, k, ids_out, scores_out, logits_out);
+    launch_rerank_topk(logit, cand, Q, pool, k, ids_out, scores_out, logits_out, st);
     HIP_TRY(h, hipGetLastError());
     if (cand_out) HIP_TRY(h, hipMemcpyAsync(cand_out, cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     if (h->ids != nullptr || id_base_saved != 0) {
@@ -355,6 +396,76 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
             hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, h->ids,
                                id_base_saved);
         HIP_TRY(h, hipGetLastError());
+    }
+    return RAG_OK;
+}
+
+// ---- retrieve + late-interaction rerank as one device-resident call (rag_retrieve_maxsim_dev): what retrieve_rerank_dev does for
+// the cross-encoder, with the resident token vectors (tokvec.hip) in place of the token store and the forward.
+//   1. candidates: dense top-pool (mode 0) or dense + learned-sparse RRF -> top-pool (mode 1), tenant and deleted rows filtered
+//   2. tokvec_maxsim_kernel over the [Q][pool] candidate rows   3. the raw top-k of rerank_topk_kernel
+// The candidate stage runs in row space as in retrieve_rerank_dev; the ids are mapped at the end.
+int64_t sparse_n_docs(const rag_ctx* h);
+int sparse_fresh(rag_ctx* h);
+
+__global__ void rows_narrow_kernel(const int64_t* __restrict__ in, int32_t* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i] < 0 ? -1 : (int32_t)in[i];
+}
+
+int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                        const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
+                        int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st) {
+    if (int rc = tokvec_usable(h, "retrieve_maxsim")) return rc;
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "retrieve_maxsim: 1 <= n_queries <= 65535, 0 < k <= pool <= 256");
+    ARG_CHECK(h, q_emb_dev && q_vecs_dev && q_off_dev && ids_out && scores_out, "retrieve_maxsim: null argument");
+    ARG_CHECK(h, mode == 0 || mode == 1, "retrieve_maxsim: mode is 0 (dense) or 1 (dense + sparse)");
+    ARG_CHECK(h, h->index_loaded, "retrieve_maxsim: no index loaded");
+    if (h->tv_docs != h->n_rows) {
+        h->err = "retrieve_maxsim: the token-vector store does not hold exactly the index's rows (append the vectors of the inserted rows)";
+        return RAG_ERR_STATE;
+    }
+    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_maxsim: tenant filter requested but no tenants loaded");
+    if (mode == 1) {
+        ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_maxsim: mode 1 needs the query's terms and weights");
+        ARG_CHECK(h, sparse_n_docs(h) >= 0, "no sparse index loaded (rag_sparse_load_host)");
+        if (int rc = sparse_fresh(h)) return rc;
+        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "retrieve_maxsim: the sparse postings must be row-aligned with the index (same number of documents)");
+    }
+    const size_t P = (size_t)Q * pool;
+    // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][pool] i64 | rrf [Q][pool] f64 | ranks [Q][pool][2] i32 | rows [Q][pool] i32
+    const size_t need = P * (16 + 8 + 8 + 8 + 8 + 4) + 256;
+    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
+    char* w = h->pipe_ws;
+    int64_t* lists = (int64_t*)w;              w += P * 16;
+    double* sc = (double*)w;                   w += P * 8;
+    int64_t* cand = (int64_t*)w;               w += P * 8;
+    double* rrf = (double*)w;                  w += P * 8;
+    int32_t* ranks = (int32_t*)w;              w += P * 8;
+    int32_t* rows = (int32_t*)w;
+    dev_buf<int64_t> ids_saved = std::move(h->ids);
+    const int64_t id_base_saved = h->id_base;
+    h->id_base = 0;
+    int rc;
+    if (mode == 0) {
+        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st);
+    } else {
+        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, {nullptr, nullptr}, qweights_dev);
+        if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, pool, cand, rrf, ranks, st);
+    }
+    h->ids = std::move(ids_saved);
+    h->id_base = id_base_saved;
+    if (rc) return rc;
+    launch(rows_narrow_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand, rows, (int64_t)P);
+    if ((rc = launch_status(h))) return rc;
+    if ((rc = tokvec_rerank(h, q_vecs_dev, q_off_dev, rows, Q, pool, k, ids_out, nullptr, scores_out, nullptr, st))) return rc;
+    if (cand_out) {
+        HIP_TRY(h, hipMemcpyAsync(cand_out, cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (h->ids != nullptr || id_base_saved != 0) {
+            hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, h->ids,
+                               id_base_saved);
+            HIP_TRY(h, hipGetLastError());
+        }
     }
     return RAG_OK;
 }

@@ -1,0 +1,368 @@
+// Resident token-vector store and late-interaction rerank over it (rag_tokvec_*; rag_retrieve_maxsim_dev in pipeline.hip).
+// The passages' token vectors ("ColBERT" rows, the tok_out of rag_embed_multi_*) are computed once at ingest and kept in HBM as
+// packed fp16 rows [rows][dim] with int64 offsets [docs + 1]; document i is row i of the dense index. A query then costs one
+// embedder forward (its own), and a rerank reads half the bytes rag_maxsim_* reads for the same pairs.
+//   tokvec_convert_kernel     float32 -> fp16, round to nearest even (v_cvt_f16_f32), counting values that are not finite as fp16
+//   tokvec_offsets_kernel     a block's offsets, relative to its first, behind the store's; counting decreasing ones
+//   tokvec_maxsim_kernel      score[q][j] = (1 / nq) * sum_i max_r <vq[i], store[cand[q][j]][r]>
+//
+// tokvec_maxsim_kernel carries over m3_maxsim_kernel's fragment map and masking (m3_heads.hip): lane (fr = lane & 15, fq = lane >> 4)
+// holds A[row fr][k = 8 fq ..+8] and B[col fr][the same k], acc[r] = C[row 4 fq + r][col fr]; A = 16 document rows, B = 16 query
+// rows. One workgroup (4 waves) per (query, candidate slot); queries in blocks of 32 rows; wave w takes the document tile groups
+// w, w + 4, ... Rows of a tile past the document are loaded from its last row and masked out of the maximum, never zero-filled.
+// What differs: the document fragment is loaded as fp16 (16 B per lane and row, half of the float32 path) straight into the A
+// operand and is exact there; only the float32 query is split, per K-step, into hi = fp16(x), lo = fp16(x - hi), and a product is
+// two mfma_f32_16x16x32_f16: lo_q * d + hi_q * d with fp32 accumulation. hi * fp16 products are exact in fp32, the split costs
+// 2^-22 relative, the accumulation over at most 1024 terms 1024 * 2^-24 = 6.1e-5: within 1e-4 of float64 MaxSim over the STORED
+// vectors, and (fp16 rounding of unit rows moves a dot by at most 2^-11) within 1e-3 of float64 MaxSim over the original ones.
+// A wave holds 4 document tiles against the 2 query tiles when the document has more than 8 tiles (a 255-row passage is 16: every
+// wave reads the query block once), else 2, so that short documents still spread over the waves; which of the two runs is a
+// function of the document's own row count, and either gives every accumulator the same MFMA sequence: the same bits.
+// The loads of K-step k + 1 are requested before the MFMAs of step k. Per-wave maxima meet in LDS and one thread sums them in
+// query order in float64: no atomics; a pair's score is a function of its own rows, bit-identical whatever surrounds it.
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+
+#define TV_QT 2          // 16-row query tiles per block of queries
+
+__global__ __launch_bounds__(256) void tokvec_convert_kernel(const float* __restrict__ in, half_t* __restrict__ out, int64_t n,
+                                                              int* __restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const half_t v = (half_t)in[i];                            // round to nearest even
+    if (!(fabsf((float)v) <= 65504.f)) atomicAdd(bad, 1);      // NaN, or inf once rounded: a float32 inf or |x| >= 65520
+    out[i] = v;
+}
+
+// dst[i] = base + off[i + 1] - off[0] for i < n (dst = the store's offsets behind the documents it holds); off[i + 1] < off[i] counts
+__global__ __launch_bounds__(256) void tokvec_offsets_kernel(const int64_t* __restrict__ off, int64_t n, int64_t base, int64_t* __restrict__ dst,
+                                                              int* __restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (off[i + 1] < off[i]) atomicAdd(bad, 1);
+    dst[i] = base + (off[i + 1] - off[0]);
+}
+
+struct tv_raw8 { float4 a, b; };             // a lane's 8 consecutive floats of one query row
+__device__ __forceinline__ tv_raw8 tv_load8(const float* __restrict__ p) {
+    return {*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4)};
+}
+__device__ __forceinline__ void tv_split8(const tv_raw8& r, half8& hi, half8& lo) {
+    const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        hi[i] = (half_t)v[i];
+        lo[i] = (half_t)(v[i] - (float)hi[i]);
+    }
+}
+
+// one block of TV_QT * 16 query rows against every document tile group of this wave, DT tiles at a time: best[j] = the maximum over
+// the wave's document rows for query row 16 j + fr (in the lanes of every fq, before the cross-lane steps)
+template <int DT>
+__device__ __forceinline__ void tv_query_block(const half_t* __restrict__ doc, int64_t nd, int64_t nd_tiles, const float* const (&qp)[TV_QT],
+                                               int dim, int wv, int fr, int fq, float (&best)[TV_QT]) {
+    for (int64_t dt0 = (int64_t)wv * DT; dt0 < nd_tiles; dt0 += 4 * DT) {
+        const half_t* dp[DT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t) dp[t] = doc + min((dt0 + t) * 16 + fr, nd - 1) * dim + fq * 8;
+        f32x4 acc[DT][TV_QT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        half8 dr[DT];
+        tv_raw8 qr[TV_QT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t) dr[t] = *reinterpret_cast<const half8*>(dp[t]);
+#pragma unroll
+        for (int j = 0; j < TV_QT; ++j) qr[j] = tv_load8(qp[j]);
+        for (int k = 0; k < dim; k += 32) {
+            const int kn = k + 32 < dim ? k + 32 : k;          // the last step re-reads itself: no branch around the loads
+            half8 dn[DT];
+            tv_raw8 qn[TV_QT];
+#pragma unroll
+            for (int t = 0; t < DT; ++t) dn[t] = *reinterpret_cast<const half8*>(dp[t] + kn);
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) qn[j] = tv_load8(qp[j] + kn);
+            half8 bh[TV_QT], bl[TV_QT];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) tv_split8(qr[j], bh[j], bl[j]);
+#pragma unroll
+            for (int t = 0; t < DT; ++t)
+#pragma unroll
+                for (int j = 0; j < TV_QT; ++j) {
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(dr[t], bl[j], acc[t][j], 0, 0, 0);
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(dr[t], bh[j], acc[t][j], 0, 0, 0);
+                }
+#pragma unroll
+            for (int t = 0; t < DT; ++t) dr[t] = dn[t];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) qr[j] = qn[j];
+        }
+        // acc[t][j][r] = <document row (dt0 + t) * 16 + 4 fq + r, query row 16 j + fr>; rows past the document stay out of the maximum
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((dt0 + t) * 16 + fq * 4 + r < nd) {
+#pragma unroll
+                    for (int j = 0; j < TV_QT; ++j) best[j] = fmaxf(best[j], acc[t][j][r]);
+                }
+    }
+}
+
+// grid = Q * pool workgroups. slot[q][j] = the row that was scored, or -1 for an empty slot (score 0.0): cand < 0, a row at or past
+// the store's documents, a document without rows, a query without rows.
+__global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restrict__ q, const int64_t* __restrict__ q_off,
+                                                             const half_t* __restrict__ store, const int64_t* __restrict__ d_off, int64_t n_docs,
+                                                             const int32_t* __restrict__ cand, int pool, int dim, float* __restrict__ out,
+                                                             int32_t* __restrict__ slot) {
+    __shared__ float wmax[4][TV_QT * 16];
+    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int qi = pair / pool, di = cand[pair];
+    const int64_t q0 = q_off[qi], nq = q_off[qi + 1] - q0;
+    int64_t d0 = 0, nd = 0;
+    if (di >= 0 && di < n_docs) {
+        d0 = d_off[di];
+        nd = d_off[di + 1] - d0;
+    }
+    if (nq <= 0 || nd <= 0) {                                  // uniform over the workgroup
+        if (tid == 0) {
+            out[pair] = 0.f;
+            slot[pair] = -1;
+        }
+        return;
+    }
+    const int64_t nd_tiles = (nd + 15) >> 4;
+    const half_t* doc = store + d0 * dim;
+    double total = 0.0;                                        // thread 0 alone
+    for (int64_t qb = 0; qb < nq; qb += TV_QT * 16) {
+        const float* qp[TV_QT];
+        float best[TV_QT];
+#pragma unroll
+        for (int j = 0; j < TV_QT; ++j) {
+            const int64_t row = min(qb + j * 16 + fr, nq - 1);
+            qp[j] = q + (q0 + row) * dim + fq * 8;
+            best[j] = -INFINITY;
+        }
+        if (nd_tiles > 8) tv_query_block<4>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+        else tv_query_block<2>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+#pragma unroll
+        for (int j = 0; j < TV_QT; ++j) {
+            best[j] = fmaxf(best[j], __shfl_xor(best[j], 16));
+            best[j] = fmaxf(best[j], __shfl_xor(best[j], 32));
+            if (lane < 16) wmax[wv][j * 16 + lane] = best[j];
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int i = 0; i < TV_QT * 16 && qb + i < nq; ++i)
+                total += (double)fmaxf(fmaxf(wmax[0][i], wmax[1][i]), fmaxf(wmax[2][i], wmax[3][i]));
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[pair] = (float)(total / (double)nq);
+        slot[pair] = di;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side
+// ------------------------------------------------------------------------------------------------
+static void tokvec_drop(rag_ctx* h) {
+    h->tv.reset();
+    h->tv_off.reset();
+    h->tv_docs = h->tv_rows = h->tv_docs_cap = h->tv_rows_cap = 0;
+    h->tv_dim = 0;
+    h->tv_stale = false;
+}
+
+int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim) {
+    ARG_CHECK(h, n_docs_total > 0 && n_docs_total < (int64_t)0x7fffff00 && rows_total >= 0, "tokvec_reserve: need 0 < documents < 2^31 and rows >= 0");
+    ARG_CHECK(h, dim >= 32 && dim <= 1024 && dim % 32 == 0, "tokvec_reserve: dim must be a multiple of 32 in [32, 1024]");
+    tokvec_drop(h);
+    int rc;
+    if ((rc = h->tv.alloc(h, std::max<size_t>((size_t)rows_total * dim, 8))) || (rc = h->tv_off.alloc(h, (size_t)n_docs_total + 1)) ||
+        (rc = h->tv_bad.reserve(h, 2))) {
+        tokvec_drop(h);
+        return rc;
+    }
+    // cleared on the handle's stream and waited for: a null-stream hipMemset is not ordered against the non-blocking stream an
+    // append may count on
+    HIP_TRY(h, hipMemsetAsync(h->tv_bad, 0, 2 * sizeof(int), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->tv_off, 0, sizeof(int64_t), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->tv_docs_cap = n_docs_total;
+    h->tv_rows_cap = rows_total;
+    h->tv_dim = dim;
+    return RAG_OK;
+}
+
+// One block, from device memory (queued on st, then waited for) or host memory (staged in pieces of at most 64 Mi floats).
+// Nothing the store counts moves before the whole block is resident and checked; a rejected block leaves only slots past the
+// counts written, which the next append overwrites.
+int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t n, hipStream_t st, bool host_ptrs) {
+    ARG_CHECK(h, h->tv_docs_cap > 0, "tokvec_append: rag_tokvec_reserve first");
+    ARG_CHECK(h, n >= 0 && h->tv_docs + n <= h->tv_docs_cap, "tokvec_append: exceeds the reserved documents");
+    if (n == 0) return RAG_OK;
+    ARG_CHECK(h, row_off != nullptr, "tokvec_append: null offsets");
+    const int dim = h->tv_dim;
+    int64_t ends[2] = {0, 0};
+    if (host_ptrs) {
+        ends[0] = row_off[0];
+        ends[1] = row_off[n];
+        for (int64_t i = 0; i < n; ++i) ARG_CHECK(h, row_off[i + 1] >= row_off[i], "tokvec_append: row offsets must never decrease");
+    } else {
+        HIP_TRY(h, hipMemcpyAsync(&ends[0], row_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(&ends[1], row_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    const int64_t rows = ends[1] - ends[0];
+    ARG_CHECK(h, ends[0] >= 0 && rows >= 0, "tokvec_append: row offsets must start at >= 0 and never decrease");
+    ARG_CHECK(h, h->tv_rows + rows <= h->tv_rows_cap, "tokvec_append: exceeds the reserved rows");
+    ARG_CHECK(h, rows == 0 || vecs != nullptr, "tokvec_append: null vectors");
+    half_t* dst = h->tv + (size_t)h->tv_rows * dim;
+    int64_t* dst_off = h->tv_off + h->tv_docs + 1;
+    const int64_t total = rows * dim;
+    const int64_t piece = (int64_t)64 << 20;                     // floats per launch (a grid stays far below 2^32 threads) and per staged copy
+    auto convert = [&](const float* src_dev, int64_t at, int64_t cnt) {
+        for (int64_t o = 0; o < cnt; o += piece) {
+            const int64_t nn = std::min(piece, cnt - o);
+            launch(tokvec_convert_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, src_dev + o, dst + at + o, nn, h->tv_bad.get());
+        }
+    };
+    if (host_ptrs) {
+        std::vector<int64_t> abs_off((size_t)n);
+        for (int64_t i = 0; i < n; ++i) abs_off[(size_t)i] = h->tv_rows + (row_off[i + 1] - ends[0]);
+        HIP_TRY(h, hipMemcpyAsync(dst_off, abs_off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        dev_buf<float> buf;
+        if (total > 0)
+            if (int rc = buf.alloc(h, (size_t)std::min(total, piece))) return rc;
+        const float* src = vecs + (size_t)ends[0] * dim;
+        for (int64_t o = 0; o < total; o += piece) {
+            const int64_t nn = std::min(piece, total - o);
+            HIP_TRY(h, hipMemcpyAsync(buf, src + o, (size_t)nn * sizeof(float), hipMemcpyHostToDevice, st));
+            convert(buf, o, nn);
+            HIP_TRY(h, hipStreamSynchronize(st));              // buf is reused by the next piece; abs_off is consumed
+        }
+        HIP_TRY(h, hipStreamSynchronize(st));
+    } else {
+        launch(tokvec_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, row_off, n, h->tv_rows, dst_off, h->tv_bad + 1);
+        // a block whose inner offsets leave [off[0], off[n]] is a decreasing one and is rejected below; the rows converted are
+        // the contiguous span between its ends either way, inside vecs by the caller's contract and inside the reservation
+        if (total > 0) convert(vecs + (size_t)ends[0] * dim, 0, total);
+    }
+    HIP_TRY(h, hipGetLastError());
+    int bad[2] = {0, 0};                                         // synchronous check: a load path, not a search path
+    HIP_TRY(h, hipMemcpyAsync(bad, h->tv_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (bad[0] != 0 || bad[1] != 0) {
+        // the counters start again at zero, or every later - valid - append on this handle would be rejected with this one
+        HIP_TRY(h, hipMemsetAsync(h->tv_bad, 0, sizeof(bad), st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    ARG_CHECK(h, bad[1] == 0, "tokvec_append: row offsets must never decrease");
+    ARG_CHECK(h, bad[0] == 0, "tokvec_append: the vectors hold a value that is not finite as fp16");
+    h->tv_docs += n;
+    h->tv_rows += rows;
+    return RAG_OK;
+}
+
+int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim) {
+    ARG_CHECK(h, off != nullptr && n_docs > 0, "tokvec_load: need offsets and at least one document");
+    ARG_CHECK(h, off[n_docs] >= off[0], "tokvec_load: row offsets must never decrease");
+    if (int rc = tokvec_reserve(h, n_docs, off[n_docs] - off[0], dim)) return rc;
+    return tokvec_append(h, vecs, off, n_docs, h->stream, true);
+}
+
+int tokvec_info(const rag_ctx* h, int64_t* docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out) {
+    const bool have = h->tv_docs_cap > 0;
+    if (docs_out) *docs_out = have ? h->tv_docs : 0;
+    if (rows_out) *rows_out = have ? h->tv_rows : 0;
+    if (dim_out) *dim_out = have ? h->tv_dim : 0;
+    if (hbm_bytes_out) *hbm_bytes_out = have ? (int64_t)(h->tv.size() * sizeof(half_t) + h->tv_off.size() * sizeof(int64_t)) : 0;
+    return RAG_OK;
+}
+
+int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int64_t* n_rows_out) {
+    ARG_CHECK(h, h->tv_docs_cap > 0, "tokvec_fetch: no token-vector store");
+    ARG_CHECK(h, doc >= 0 && doc < h->tv_docs && n_rows_out != nullptr && cap_rows >= 0, "tokvec_fetch: document out of range or null count");
+    int64_t span[2];
+    HIP_TRY(h, hipMemcpyAsync(span, h->tv_off + doc, sizeof(span), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int64_t n = span[1] - span[0];
+    *n_rows_out = n;
+    ARG_CHECK(h, n <= cap_rows && (n == 0 || out != nullptr), "tokvec_fetch: the document has more rows than the output holds");
+    if (n == 0) return RAG_OK;
+    std::vector<half_t> tmp((size_t)n * h->tv_dim);
+    HIP_TRY(h, hipMemcpyAsync(tmp.data(), h->tv + (size_t)span[0] * h->tv_dim, tmp.size() * sizeof(half_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < tmp.size(); ++i) out[i] = (float)tmp[i];
+    return RAG_OK;
+}
+
+int tokvec_usable(rag_ctx* h, const char* who) {
+    if (h->tv_docs_cap <= 0) {
+        h->err = std::string(who) + ": no token-vector store (rag_tokvec_reserve / rag_tokvec_load_host)";
+        return RAG_ERR_STATE;
+    }
+    if (h->tv_stale) {
+        h->err = std::string(who) + ": the token-vector store is stale (a compaction renumbered the rows since it was filled): reload it";
+        return RAG_ERR_STATE;
+    }
+    return RAG_OK;
+}
+
+int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
+                  int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st) {
+    if (int rc = tokvec_usable(h, "tokvec_rerank")) return rc;
+    ARG_CHECK(h, Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "tokvec_rerank: need n_queries > 0 and 0 < k <= pool <= 256");
+    // one 256-thread workgroup per slot, and a launch holds fewer than 2^32 threads
+    ARG_CHECK(h, (int64_t)Q * pool < ((int64_t)1 << 24), "tokvec_rerank: n_queries * pool must be below 2^24");
+    ARG_CHECK(h, q_vecs && q_off && cand_rows && ids_out && scores_out, "tokvec_rerank: null argument");
+    ARG_CHECK(h, (reinterpret_cast<uintptr_t>(q_vecs) & 15) == 0, "tokvec_rerank: query vectors must be 16-byte aligned");
+    const size_t P = (size_t)Q * pool;
+    if (int rc = h->tv_ws.reserve(h, stage_size(P, 4) * 2)) return rc;
+    float* sc = reinterpret_cast<float*>(h->tv_ws.get());
+    int32_t* slot = reinterpret_cast<int32_t*>(h->tv_ws.get() + stage_size(P, 4));
+    launch(tokvec_maxsim_kernel, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), h->tv_docs, cand_rows, pool,
+           h->tv_dim, sc, slot);
+    if (int rc = launch_status(h)) return rc;
+    if (pair_scores_out) HIP_TRY(h, hipMemcpyAsync(pair_scores_out, sc, P * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return tokvec_topk(h, sc, slot, Q, pool, k, ids_out, rows_out, scores_out, st);
+}
+
+int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
+                       int32_t* rows_out, double* scores_out, float* pair_scores_out) {
+    if (int rc = tokvec_usable(h, "tokvec_rerank")) return rc;
+    ARG_CHECK(h, Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "tokvec_rerank: need n_queries > 0 and 0 < k <= pool <= 256");
+    ARG_CHECK(h, q_off && cand_rows && ids_out && scores_out, "tokvec_rerank: null argument");
+    ARG_CHECK(h, q_off[0] >= 0, "tokvec_rerank: query offsets must start at >= 0 and never decrease");
+    for (int i = 0; i < Q; ++i) ARG_CHECK(h, q_off[i + 1] >= q_off[i], "tokvec_rerank: query offsets must start at >= 0 and never decrease");
+    ARG_CHECK(h, q_vecs || q_off[Q] == 0, "tokvec_rerank: null query vectors");
+    hipStream_t st = h->stream;
+    const size_t P = (size_t)Q * pool, K = (size_t)Q * k, nqv = (size_t)q_off[Q] * h->tv_dim;
+    dev_buf<float> dq, dps;
+    dev_buf<int64_t> dqo, dids;
+    dev_buf<int32_t> dcand, drows;
+    dev_buf<double> dsc;
+    int rc;
+    if ((rc = dq.alloc(h, std::max<size_t>(nqv, 4))) || (rc = dqo.alloc(h, (size_t)Q + 1)) || (rc = dcand.alloc(h, P)) || (rc = dids.alloc(h, K)) ||
+        (rc = drows.alloc(h, K)) || (rc = dsc.alloc(h, K)) || (rc = dps.alloc(h, P)))
+        return rc;
+    if (nqv) HIP_TRY(h, hipMemcpyAsync(dq, q_vecs, nqv * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dqo, q_off, ((size_t)Q + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dcand, cand_rows, P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    rc = tokvec_rerank(h, dq, dqo, dcand, Q, pool, k, dids, drows, dsc, dps, st);
+    if (!rc) {
+        HIP_TRY(h, hipMemcpyAsync(ids_out, dids, K * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, drows, K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(scores_out, dsc, K * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (pair_scores_out) HIP_TRY(h, hipMemcpyAsync(pair_scores_out, dps, P * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return rc;
+}

@@ -342,6 +342,88 @@ class GpuDocumentIndex:
                         "metadata": row.get("metadata") or {}, **extra})
         return res
 
+    # ---- late interaction over resident token vectors (rag_tokvec_*) -------------------------------------------------------
+    @_locked
+    def load_token_vectors(self, vecs, offsets) -> None:
+        """Make the rows' token vectors resident: float32 [rows, tok_dim] packed row after row, int64 offsets [len(self.rows) + 1]
+        (e.g. embed_multi's outputs kept from an earlier ingest). They are stored as fp16; a compaction leaves them stale - and
+        search_late_interaction falling back to `search` - until this or build_token_vectors runs again."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if off.shape[0] - 1 != len(self.rows):
+            raise ValueError(f"load_token_vectors: offsets of {off.shape[0] - 1} documents for an index of {len(self.rows)} rows")
+        self.engine.tokvec_load(vecs, off)
+
+    @_locked
+    def build_token_vectors(self, texts, batch: int = 64) -> None:
+        """Compute the token vectors of the rows' texts (texts[i] belongs to row i) with the embedding service's token-vector head
+        and append them to the resident store on the device, `batch` texts per forward: the vectors go from the forward's output
+        tensor into the store and never exist on the host."""
+        import torch
+        svc = self.embeddings
+        texts = [str(t) for t in texts]
+        if len(texts) != len(self.rows):
+            raise ValueError(f"build_token_vectors: {len(texts)} texts for an index of {len(self.rows)} rows")
+        if not texts:
+            raise ValueError("build_token_vectors: the index holds no rows")
+        svc._need_heads(False, True)
+        tok_dim = int(svc.engine.embed_tok_dim)
+        batch = max(1, int(batch))
+        batches = [svc.tokenize(texts[b:b + batch]) for b in range(0, len(texts), batch)]
+        n_rows = [int((np.clip(lens, 1, ids.shape[1]).astype(np.int64) - 1).sum()) for ids, _, lens in batches]
+        self.engine.tokvec_reserve(len(texts), sum(n_rows), tok_dim)
+        for (ids, tt, lens), rows in zip(batches, n_rows):
+            tok = torch.empty((max(rows, 1), tok_dim), dtype=torch.float32, device="cuda")
+            off = torch.empty((len(lens) + 1,), dtype=torch.int64, device="cuda")
+            svc.engine.embed_multi_dev(torch.from_numpy(ids).cuda(), torch.from_numpy(tt).cuda(), torch.from_numpy(lens).cuda(), tok=tok, row_off=off)
+            self.engine.tokvec_append_dev(tok, off)          # waits for the stream: the block is resident and checked on return
+
+    def search_late_interaction(self, agent_id: str, query: str, top_k: int = 5, pool: int = 100, mode: str = "dense") -> List[Dict[str, Any]]:
+        """Retrieve `pool` candidates - mode "dense": what `search` ranks by; "dense+sparse": reciprocal rank fusion with the
+        learned-sparse list, as search_lexical - and rerank them by MaxSim of the query's token vectors against the rows' resident
+        ones (rag_tokvec_rerank_*). The query goes through ONE encode_multi forward. Result dicts are `search`'s (without
+        embeddings) plus `colbert_score`, which `score` equals. Never raises: an error (no store, a stale one, a missing head) is
+        logged and answered with `search`."""
+        try:
+            if mode not in ("dense", "dense+sparse"):
+                raise ValueError(f"unknown mode {mode!r}")
+            fused = mode == "dense+sparse"
+            enc = self.embeddings.encode_multi([query], return_dense=True, return_sparse=fused, return_colbert_vecs=True)
+            with self._lock:
+                return self._search_late_locked(agent_id, enc, top_k, int(pool), fused)
+        except Exception as e:
+            logger.error("Late-interaction search failed, answering with search: %s", e)
+            return self.search(agent_id, query, top_k, with_embeddings=False)
+
+    def _search_late_locked(self, agent_id, enc, top_k, pool, fused, rrf_k=60):
+        from .sparse import LexicalPostings
+        if agent_id is not None and str(agent_id) not in self._tenant_id:
+            return []
+        info = self.engine.tokvec_info()
+        if info["n_docs"] != len(self.rows):
+            raise RuntimeError(f"token vectors of {info['n_docs']} documents for an index of {len(self.rows)} rows")
+        tenant = -1 if agent_id is None else self._tenant_id[str(agent_id)]
+        pool = max(1, min(256, max(pool, top_k)))
+        k = min(int(top_k), pool)
+        q = np.asarray(enc["dense_vecs"], dtype=np.float32).reshape(1, self.dim)
+        _, d_rows, _ = self.engine.dense_topk(q, pool, tenant=tenant)
+        cand = d_rows
+        if fused:
+            ptr, terms, weights = LexicalPostings.encode_queries(enc["lexical_weights"])
+            _, s_rows, _ = self.engine.sparse_topk(ptr, terms, weights, pool, tenant=tenant)
+            lists = np.stack([d_rows[0], s_rows[0]]).astype(np.int64)[None]                 # rows as keys: [1, 2, pool], -1 padded
+            keys, _, _ = self.engine.rrf_fuse(lists, rrf_k=rrf_k, top_k=pool)
+            cand = keys
+        qv = np.ascontiguousarray(enc["colbert_vecs"][0], dtype=np.float32)
+        _, rows, scores, _ = self.engine.tokvec_rerank(qv, np.array([0, qv.shape[0]], dtype=np.int64), np.asarray(cand, dtype=np.int32), k)
+        res = []
+        for r, s in zip(rows[0], scores[0]):
+            if r < 0:
+                continue
+            row = self.rows[int(r)]
+            res.append({"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                        "score": float(s), "colbert_score": float(s), "metadata": row.get("metadata") or {}})
+        return res
+
     def search_many(self, agent_id: str, queries: List[str], top_k: int = 5, with_embeddings: bool = True) -> List[List[Dict[str, Any]]]:
         """Batched `search` (the reference agent can only submit one query per call, so nothing in
         its surface reaches the batched throughput): ONE embedding call for all queries when the service offers
