@@ -31,7 +31,7 @@
  *     rag_tokens_reserve_wide, rag_bm25_load_host, rag_sparse_load_host, rag_tokvec_reserve, rag_tokvec_load_host,
  *     rag_tokvec_append_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
- *     rag_index_compact_bm25, rag_index_load_host, rag_index_reserve,
+ *     rag_sparse_append_host, rag_sparse_fold, rag_index_compact_bm25, rag_index_compact_live, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
  *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize, rag_set_option and
  *     rag_ce_set_pair_format do not
@@ -69,7 +69,7 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, ce_chunk_tokens, ce_mx, ce_attn_stream (DESIGN.md section 6;
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, sparse_tail_fold, tokvec_compact_rows, ce_chunk_tokens, ce_mx, ce_attn_stream (DESIGN.md section 6;
  * ce_attn_stream: 0 = attention of 64-wide heads above length class 512 by the streamed kernel, -1 = by the global-memory form at
  * every class above 256, 1 = by the streamed kernel at every class above 512 whatever the default there - the same bits in all
  * three). Unknown name: RAG_ERR_ARG. */
@@ -155,7 +155,30 @@ int rag_index_rows(rag_handle_t h, int64_t* n_rows_out);
  * rag_bm25_fold) before the first row moves, and swapped in at the end: RAG_ERR_NOMEM leaves rows and postings as they were
  * (as in rag_index_compact, an index with implicit ids has had its ids plane written out by then: id = row, the same ids).
  * Synchronous, takes the handle lock, waits for queued *_dev work like every live write. Cost: the postings streamed twice on
- * the device; never a host rebuild or an upload of postings. */
+ * the device; never a host rebuild or an upload of postings.
+ *
+ * rag_index_compact_live: rag_index_compact_bm25 - the same arguments, the same effect on every row plane and on the BM25
+ * postings - that ALSO keeps the learned-sparse postings and the resident token-vector store.
+ * Sparse postings: kept when they are loaded and were describing the rows (no rag_index_compact / rag_index_compact_bm25 since
+ * their load). Base and tail are remapped separately through the device row map by the same stable stream compaction (the
+ * float32 weights move as stored bits), postings of deleted rows are dropped, term numbers never change; a tail without
+ * survivors is dropped, a base without survivors is replaced by the remapped tail, and when no covered row survives the
+ * postings end as after rag_index_compact. Staleness is left as it was: rows inserted but not yet appended stay uncovered
+ * until rag_sparse_append_host of the remaining rows, in their new order.
+ * Token-vector store: documents [0, min(store documents, rows before)) move through the row map and a deleted document's rows
+ * are dropped; documents the store holds at or past the index rows (a store filled ahead of the inserts) keep their order behind
+ * the survivors. The offsets are rewritten, the document and row counts shrink - the freed rows are headroom of the same
+ * reservation again - and the store is NOT marked stale. Vectors move as stored fp16 bits, in place, 16 bytes per lane, one
+ * chunk of destination rows at a time through the compaction's staging buffer (option tokvec_compact_rows: token rows per
+ * chunk, 0 = sized from the staging bound); beyond the store, the move needs 16 B per document (new offsets, first source
+ * row), inside the 1 GiB staging bound whatever the store's size. A store that was stale already stays stale.
+ * Atomic as rag_index_compact_bm25: the new posting arrays of both indexes, the store's new offsets and every workspace are
+ * allocated and built beside the old ones before the first row of any plane moves and swapped in at the end; RAG_ERR_NOMEM
+ * leaves rows, both posting sets and the store as they were. With nothing deleted the call moves and marks nothing.
+ * Afterwards rag_sparse_*, rag_hybrid_sparse_rrf_dev, rag_tokvec_rerank_* (on mapped candidate rows) and rag_retrieve_maxsim_dev
+ * are BIT-IDENTICAL to a fresh handle that holds the live rows in row order with the compacted sparse CSR and the surviving
+ * documents' vectors loaded - and to what this handle returned immediately before the call, rows mapped through row_map_out.
+ * rag_tokvec_fetch_host of every surviving document returns the bits it returned before. */
 typedef struct rag_row_block {
     int64_t n;
     const float* emb;            /* [n][dim] */
@@ -169,6 +192,7 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rows, int64_t* fi
 int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int tenant, int64_t* n_deleted_out);
 int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
 int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
+int rag_index_compact_live(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
 int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out);
 /* copy rows' fp32 embeddings back (kills apply_mmr's per-doc re-embedding, rag/nodes/helpers.py:215-223) */
 int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, float* out_host);
@@ -300,8 +324,8 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
  * Live writes: rag_index_insert_host, rag_index_compact and rag_index_compact_bm25 leave the sparse postings STALE: every
  *   rag_sparse_* search and rag_hybrid_sparse_rrf_dev returns RAG_ERR_STATE until rag_sparse_load_host runs again (the handle
  *   stays usable; a compaction that finds no deleted row moves nothing and marks nothing). rag_index_delete_host does not:
- *   deleted rows are filtered. There is no append, compaction or per-query
- *   tenant array for this index.
+ *   deleted rows are filtered. After inserts, rag_sparse_append_host (below, behind rag_bm25_segments) makes the postings
+ *   current again; rag_index_compact_live renumbers them with the rows. There is no per-query tenant array for this index.
  * rag_hybrid_sparse_rrf_dev: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list - dense top-`pool` and sparse
  *   top-`pool` (-1 padded at the tail), rag_rrf_fuse_dev semantics with n_lists = 2, dense first, top-k. Workspaces and limits
  *   as rag_hybrid_rrf_dev (pool <= 256; lists_ws_dev [2][Q][pool] int64, scores_ws_dev [Q][pool] float64); the postings must
@@ -385,6 +409,30 @@ int rag_bm25_append_host(rag_handle_t h, const int64_t* indptr_host /*n_terms_to
                          int64_t n_terms_total);
 int rag_bm25_fold(rag_handle_t h);
 int rag_bm25_segment_stats(rag_handle_t h, rag_bm25_segments* out);
+/* ---- appendable learned-sparse postings: the rag_sparse_* searches, rag_hybrid_sparse_rrf_dev and rag_retrieve_maxsim_dev
+ * mode 1 stay live through rag_index_insert_host. The same machinery as the BM25 append, over the sparse slot.
+ * rag_sparse_append_host takes the postings of the NEXT n_docs_new rows after the rows the resident sparse postings cover: a
+ * term-major CSR over the handle's vocabulary (indptr[n_terms_total + 1] from 0, documents strictly ascending per term and
+ * RELATIVE to the block's first row, weights finite and > 0). n_terms_total may grow - new terms have empty base lists - and may
+ * not shrink. Everything is validated on the host before anything is built: RAG_ERR_STATE without loaded sparse postings;
+ * RAG_ERR_ARG for n_docs_new < 1, a malformed block, a weight that is not finite or <= 0, or a block that would cover more
+ * rows than a loaded dense index has; RAG_ERR_NOMEM when it cannot allocate. A rejected or failed append leaves postings,
+ * coverage and staleness exactly as they were. The postings stop being stale exactly when, after the call, the covered rows
+ * equal the index rows and nothing but inserts happened since they were last aligned (5 rows inserted, 3 appended: still stale).
+ * Representation: the loaded postings (the base) are never touched; ONE tail segment of the same form (int32 document plane,
+ * float32 weight plane, idf 1.0, its own bracket tables) holds every appended row and is rebuilt on the device by each append
+ * in O(tail). The tail is numbered from the base's last 2048-document range, so one search scores base and tail as one index.
+ * After any sequence of appends and folds every result of rag_sparse_topk_* (with and without a tenant), rag_sparse_scores_host,
+ * rag_hybrid_sparse_rrf_dev and rag_retrieve_maxsim_dev mode 1 is BIT-IDENTICAL to a fresh handle that holds the same rows and
+ * was loaded by rag_sparse_load_host with the merged CSR (each term's list = its old list followed by the new postings): a
+ * document lives in one segment only, so its float64 accumulator receives the same products in the same token order.
+ * rag_sparse_fold merges the tail into the base on the device; results before and after are bit-identical; RAG_ERR_NOMEM
+ * changes nothing. Option sparse_tail_fold has the meaning of bm25_tail_fold. rag_sparse_segment_stats reports the segments
+ * (n_terms: terms known so far; tail_bytes: HBM bytes of the tail); rag_sparse_info reports base and tail together. */
+int rag_sparse_append_host(rag_handle_t h, const int64_t* indptr_host /*n_terms_total+1*/, const int32_t* doc_host,
+                           const float* weight_host, int64_t n_docs_new, int64_t n_terms_total);
+int rag_sparse_fold(rag_handle_t h);
+int rag_sparse_segment_stats(rag_handle_t h, rag_bm25_segments* out);
 /* ---- statistics refresh: fresh idf / avgdl computed from, and written into, the RESIDENT postings. The reference builds a new
  * BM25Okapi over the corpus it has on every call (rag/retrieval.py:333-341); appends, deletes and compactions keep the
  * statistics of the last load instead, so an index that has doubled or lost a tenant ranks by numbers no rebuild would give.
@@ -736,7 +784,8 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
  *   ids. 1 <= n_queries <= 65535, 0 < k <= pool <= 256. Bit-identical to rag_dense_topk_dev (mode 0) or rag_hybrid_sparse_rrf_dev
  *   with k = pool (mode 1) followed by rag_tokvec_rerank_dev on the rows. Needs store documents == index rows, else RAG_ERR_STATE.
  *   Workspaces are handle-owned and grown as the preamble says (the first call of a larger shape frees the old one, which waits).
- * Live writes, as the BM25 postings: rag_index_compact / rag_index_compact_bm25 mark the store STALE when deleted rows are removed;
+ * Live writes, as the BM25 postings: rag_index_compact / rag_index_compact_bm25 mark the store STALE when deleted rows are removed
+ * (rag_index_compact_live moves the store's documents with their rows instead and does not);
  *   every rag_tokvec_rerank_* and rag_retrieve_maxsim_dev then returns RAG_ERR_STATE until rag_tokvec_reserve / rag_tokvec_load_host
  *   runs again (the handle stays usable; a compaction that finds nothing deleted marks nothing). rag_index_insert_host leaves the
  *   store alone: rag_retrieve_maxsim_dev returns RAG_ERR_STATE until appends cover the new rows (reserve headroom for them).

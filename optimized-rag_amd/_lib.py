@@ -83,6 +83,7 @@ _SIGS = {
     "rag_index_delete_host": ([_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_compact": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_compact_bm25": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_compact_live": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_deleted_rows": ([_P, C.POINTER(C.c_int64)], C.c_int),
     "rag_dense_topk_host": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_dense_topk_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
@@ -117,6 +118,9 @@ _SIGS = {
     "rag_bm25_topk_dev": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "rag_hybrid_rrf_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "rag_sparse_load_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
+    "rag_sparse_append_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
+    "rag_sparse_fold": ([_P], C.c_int),
+    "rag_sparse_segment_stats": ([_P, C.POINTER(Bm25Segments)], C.c_int),
     "rag_sparse_info": ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "rag_sparse_topk_host": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_sparse_topk_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
@@ -397,14 +401,17 @@ class RagEngine:
         self._check(self.lib.rag_index_delete_host(self.h, _ptr(ids), ids.shape[0], int(tenant), C.byref(out)), "rag_index_delete_host")
         return int(out.value)
 
-    def index_compact(self, keep_postings=False):
+    def index_compact(self, keep_postings=False, keep_resident=False):
         """Remove deleted rows from every plane. Returns row_map (int64 [rows before]: new row or -1). keep_postings
-        (rag_index_compact_bm25): loaded BM25 postings are renumbered on the device and stay live; by default they end stale."""
+        (rag_index_compact_bm25): loaded BM25 postings are renumbered on the device and stay live; by default they end stale.
+        keep_resident (rag_index_compact_live): the same, and the learned-sparse postings are renumbered and the token-vector
+        store's documents move with their rows; neither ends stale."""
         n = C.c_int64()
         self._check(self.lib.rag_index_rows(self.h, C.byref(n)), "rag_index_rows")
         row_map = np.empty(int(n.value), dtype=np.int64)
         after = C.c_int64()
-        name = "rag_index_compact_bm25" if keep_postings else "rag_index_compact"
+        name = "rag_index_compact_live" if keep_resident else ("rag_index_compact_bm25" if keep_postings else "rag_index_compact")
+        keep_postings = keep_postings or keep_resident
         self._check(getattr(self.lib, name)(self.h, _ptr(row_map), C.byref(after)), name)
         self.n_rows = int(after.value)
         if keep_postings and hasattr(self, "bm25_docs"):             # the remap dropped documents: bm25_scores' width follows
@@ -730,6 +737,28 @@ class RagEngine:
             raise RagError("sparse_load: indptr must have n_terms + 1 entries and end at len(doc) == len(weight)")
         self._check(self.lib.rag_sparse_load_host(self.h, _ptr(indptr), _ptr(doc), _ptr(weight), int(n_docs), indptr.shape[0] - 1),
                     "rag_sparse_load_host")
+
+    # ---- appendable sparse postings (include/rag_hip.h rag_sparse_append_host / rag_sparse_fold / rag_sparse_segment_stats) --
+    def sparse_append(self, indptr, doc, weight, n_docs_new, n_terms_total=None):
+        """Postings of the next n_docs_new rows after the rows the resident sparse postings cover: CSR over the handle's
+        vocabulary (doc relative to the block's first row), weights finite and > 0. n_terms_total may grow, never shrink."""
+        indptr = _np(indptr, np.int64)
+        doc = _np(doc, np.int32)
+        weight = _np(weight, np.float32)
+        V = int(indptr.shape[0] - 1 if n_terms_total is None else n_terms_total)
+        if indptr.ndim != 1 or indptr.shape[0] != V + 1 or V < 0 or doc.shape != weight.shape or doc.shape[0] != int(indptr[-1]):
+            raise RagError("sparse_append: indptr must have n_terms_total + 1 entries and end at len(doc) == len(weight)")
+        self._check(self.lib.rag_sparse_append_host(self.h, _ptr(indptr), _ptr(doc), _ptr(weight), int(n_docs_new), V),
+                    "rag_sparse_append_host")
+
+    def sparse_fold(self):
+        """Merge the appended tail into the base sparse postings on the device (results do not change)."""
+        self._check(self.lib.rag_sparse_fold(self.h), "rag_sparse_fold")
+
+    def sparse_segment_stats(self):
+        out = Bm25Segments()
+        self._check(self.lib.rag_sparse_segment_stats(self.h, C.byref(out)), "rag_sparse_segment_stats")
+        return {k: int(getattr(out, k)) for k, _ in out._fields_}
 
     def sparse_info(self):
         v = [C.c_int64() for _ in range(4)]

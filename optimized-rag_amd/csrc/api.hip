@@ -45,6 +45,9 @@ int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
 int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
 int64_t sparse_n_docs(const rag_ctx* h);
 int sparse_fresh(rag_ctx* h);
+int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_new, int64_t n_terms_total);
+int sparse_fold(rag_ctx* h);
+int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant,
                      int64_t* ids_out, int32_t* rows_out, double* scores_out);
 int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out);
@@ -84,6 +87,7 @@ static const struct { const char* name; int rag_options::*field; } g_options[] =
     {"bm25_first_ranges", &rag_options::bm25_first_ranges}, {"bm25_no_staging", &rag_options::bm25_no_staging},
     {"bm25_packed", &rag_options::bm25_packed},         {"bm25_plan_slots", &rag_options::bm25_plan_slots},       {"bm25_ws_mb", &rag_options::bm25_ws_mb},
     {"bm25_tail_fold", &rag_options::bm25_tail_fold},     {"bm25_keep_tf", &rag_options::bm25_keep_tf},
+    {"sparse_tail_fold", &rag_options::sparse_tail_fold}, {"tokvec_compact_rows", &rag_options::tokvec_compact_rows},
     {"bm25_linear_grid", &rag_options::bm25_linear_grid},            {"bm25_sort_merge", &rag_options::bm25_sort_merge},
     {"no_fork", &rag_options::no_fork},                 {"fork_max_q", &rag_options::fork_max_q},
     {"ce_chunk_tokens", &rag_options::ce_chunk_tokens}, {"ce_mx", &rag_options::ce_mx},
@@ -686,6 +690,27 @@ int rag_sparse_load_host(rag_handle_t h, const int64_t* indptr_host, const int32
     LOCK(h);
     HOST_ENTRY(h);                      // queued *_dev searches read the postings this call replaces
     return sparse_load_host(h, indptr_host, doc_host, weight_host, n_docs, n_terms);
+}
+
+int rag_sparse_append_host(rag_handle_t h, const int64_t* indptr_host, const int32_t* doc_host, const float* weight_host, int64_t n_docs_new,
+                           int64_t n_terms_total) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);                      // queued *_dev searches read the tail this call replaces
+    return sparse_append_host(h, indptr_host, doc_host, weight_host, n_docs_new, n_terms_total);
+}
+
+int rag_sparse_fold(rag_handle_t h) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_fold(h);
+}
+
+int rag_sparse_segment_stats(rag_handle_t h, rag_bm25_segments* out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return sparse_segment_stats(h, out);
 }
 
 int rag_sparse_info(rag_handle_t h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out) {

@@ -83,7 +83,7 @@ struct rag_bm25_index {
     int64_t n_codes = 0;
     // LEARNED-SPARSE form (rag_sparse_load_host; the index of rag_ctx::sparse): the posting's weight as the caller's float32, 8 B
     // per posting with `doc`; `w` is not built, every term's idf is 1 and the QUERY carries a float32 weight per token
-    // (call_qw: the device array of the current call, as plan_t is the current call's). No tail, no refresh, raw scores.
+    // (call_qw: the device array of the current call, as plan_t is the current call's). A tail is of the same form; no refresh, raw scores.
     dev_buf<float> wf;
     const float* call_qw = nullptr;
     dev_buf<bm_term_meta> meta;        // [n_terms]
@@ -108,6 +108,8 @@ struct rag_bm25_index {
     // since. The tail numbers its documents from the start of the base's last 2048-document range (row0 = n_docs rounded down to a
     // range), so its ranges are the index's own ranges and a row's accumulator sits where a merged index would put it; the
     // boundary range exists in both segments and `first` = n_docs - row0 keeps the tail from emitting the base's rows.
+    // Both resident indexes of a handle - the BM25 postings and the learned-sparse postings - are appended, folded and compacted
+    // through the same code (bm_slot); a learned-sparse tail carries float32 weights as its base does.
     std::unique_ptr<rag_bm25_index> tail;
     int64_t tail_docs = 0;             // base: documents the tail covers
     int64_t appends = 0, folds = 0;    // base: since the load
@@ -1289,6 +1291,7 @@ static void bm25_launch_scores(const rag_ctx* h, const rag_bm25_index* ix, const
     rag_bm25_index* tl = ix->tail.get();
     if (tl == nullptr) return;
     tl->plan_t = ix->plan_t;
+    tl->call_qw = ix->call_qw;                                       // (learned-sparse: the call's query weights, for the tokens past the plan)
     const bm25_plan_ws tp = bm25_tail_plan(ix, Q, pw);
     bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
     BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, dx, tl->n_ranges, term_ptr_dev, terms_dev, 1, 1, qten, out, (uint64_t*)nullptr,
@@ -1335,6 +1338,7 @@ static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const i
     // lower bound for it as for a later base range (0 - everything passes - while the base held fewer than k documents). Its
     // partial lists sit behind the base's, [Q][tail ranges][k], and fold into the same running list: the last fold.
     tl->plan_t = ix->plan_t;
+    tl->call_qw = ix->call_qw;                                       // (learned-sparse: the call's query weights, for the tokens past the plan)
     const bm25_plan_ws tp = bm25_tail_plan(ix, Q, w.plan);
     bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
     uint64_t* t_key = w.part_key + (size_t)Q * nr * k;
@@ -1446,9 +1450,9 @@ static void bm_plan_segment(rag_bm25_index* s, const double* idf, std::vector<bm
 
 // Steps 3-5. Allocates meta, range_tab, doc and the planes this segment carries (bm_planes), zeroes what the fill does not write,
 // uploads the metadata (meta_h must stay alive until bm_finish_segment returns) and, for indptr_d, the offsets.
-// THE PADDING: doc / w / packed carry 8 zeroed postings past nnz - the scoring kernel reads 4 consecutive postings per thread,
+// THE PADDING: doc / w / packed / wf carry 8 zeroed postings past nnz - the scoring kernel reads 4 consecutive postings per thread,
 // the bracket search 8 doc ids, without a bounds branch. dl starts zeroed: a tail's entries below `first` are never written.
-struct bm_planes { bool w, packed, tf16, dl, indptr_d; };
+struct bm_planes { bool w, packed, tf16, dl, indptr_d, wf; };
 static int bm_prepare_segment(const bm_builder& B, rag_bm25_index* s, const std::vector<bm_term_meta>& meta_h, const bm_planes& pl) {
     rag_ctx* h = B.h;
     hipStream_t st = h->stream;
@@ -1459,12 +1463,14 @@ static int bm_prepare_segment(const bm_builder& B, rag_bm25_index* s, const std:
     if ((rc = B.alloc(s->doc, nnz + 8))) return rc;
     if (pl.w && (rc = B.alloc(s->w, nnz + 8))) return rc;
     if (pl.packed && (rc = B.alloc(s->packed, nnz + 8))) return rc;
+    if (pl.wf && (rc = B.alloc(s->wf, nnz + 8))) return rc;
     if (pl.tf16 && (rc = B.alloc(s->tf16, nnz))) return rc;
     if (pl.dl && (rc = B.alloc(s->dl, (size_t)s->n_docs))) return rc;
     if (pl.indptr_d && (rc = B.alloc(s->indptr_d, V + 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(s->doc + nnz, 0, 8 * sizeof(int32_t), st));
     if (pl.w) HIP_TRY(h, hipMemsetAsync(s->w + nnz, 0, 8 * sizeof(double), st));
     if (pl.packed) HIP_TRY(h, hipMemsetAsync(s->packed + nnz, 0, 8 * sizeof(uint32_t), st));
+    if (pl.wf) HIP_TRY(h, hipMemsetAsync(s->wf + nnz, 0, 8 * sizeof(float), st));
     if (pl.dl) HIP_TRY(h, hipMemsetAsync(s->dl, 0, (size_t)s->n_docs * sizeof(int32_t), st));
     if (V) HIP_TRY(h, hipMemcpyAsync(s->meta, meta_h.data(), V * sizeof(bm_term_meta), hipMemcpyHostToDevice, st));
     if (pl.indptr_d) HIP_TRY(h, hipMemcpyAsync(s->indptr_d, s->indptr_h.data(), (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -1602,12 +1608,14 @@ int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const 
 // Per-term concatenation A ++ B into a new posting array, one thread per DESTINATION posting: its term comes from the
 // destination's offsets (bm_term_by_offsets), its place j inside the term's list picks the source - the first
 // a_df postings come from A (an index: per-term metadata), the rest from B (a CSR: offsets). Document numbers are shifted
-// into the destination's numbering. The append runs it as old tail ++ block, the fold as base ++ tail.
+// into the destination's numbering. The append runs it as old tail ++ block, the fold as base ++ tail. W: the posting's weight
+// plane - float64 impacts (BM25) or the float32 weights of the learned-sparse index - copied as stored bits.
+template <class W>
 __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64_t n_terms, int64_t nnz,
                                    const bm_term_meta* __restrict__ a_meta, int64_t a_terms, const int32_t* __restrict__ a_doc,
-                                   const double* __restrict__ a_w, const int64_t* __restrict__ b_indptr,
-                                   const int32_t* __restrict__ b_doc, const double* __restrict__ b_w, int32_t b_shift,
-                                   int32_t* __restrict__ doc_out, double* __restrict__ w_out,
+                                   const W* __restrict__ a_w, const int64_t* __restrict__ b_indptr,
+                                   const int32_t* __restrict__ b_doc, const W* __restrict__ b_w, int32_t b_shift,
+                                   int32_t* __restrict__ doc_out, W* __restrict__ w_out,
                                    const uint16_t* __restrict__ a_tf, const uint16_t* __restrict__ b_tf, uint16_t* __restrict__ tf_out) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
@@ -1636,7 +1644,118 @@ __global__ void bm25_concat_kernel(const int64_t* __restrict__ out_indptr, int64
 // to an append, the fold takes 5 ms - all small, so the default stays where it was.
 static int64_t bm_default_fold_docs(int64_t base_docs) { return std::max<int64_t>(32 * BM_RANGE, base_docs / 16); }
 
-int bm25_fold(rag_ctx* h);
+// The handle's two resident indexes - the BM25 postings and the learned-sparse postings - as ONE kind of slot: the index, its two
+// staleness flags, its fold option and its names in messages. Append, fold, segment statistics and the compaction's remap are
+// written once over a slot; what differs per slot is how an appended block's weight plane comes to be (impacts computed from
+// term frequencies / float32 weights uploaded as they are) and the plane's type (bm_weights).
+struct bm_slot {
+    rag_bm25_index*& ix;
+    bool& stale;                 // rows were inserted or compacted since the postings were aligned
+    bool& compacted;             // ... and a plain compaction was among them: only a reload helps
+    int fold_opt;                // option bm25_tail_fold / sparse_tail_fold
+    const char* append_name;
+    const char* fold_name;
+    const char* stats_name;
+};
+static bm_slot bm_slot_bm25(rag_ctx* h) {
+    return {h->bm25, h->bm25_stale, h->bm25_compacted, h->opt.bm25_tail_fold, "bm25_append", "bm25_fold", "bm25_segment_stats"};
+}
+static bm_slot bm_slot_sparse(rag_ctx* h) {
+    return {h->sparse, h->sparse_stale, h->sparse_compacted, h->opt.sparse_tail_fold, "sparse_append", "sparse_fold", "sparse_segment_stats"};
+}
+template <class W> static dev_buf<W>& bm_weights(rag_bm25_index* s);
+template <> dev_buf<double>& bm_weights<double>(rag_bm25_index* s) { return s->w; }
+template <> dev_buf<float>& bm_weights<float>(rag_bm25_index* s) { return s->wf; }
+// terms the index knows, loaded and appended (the BM25 postings keep an idf for each)
+static int64_t bm_known_terms(const rag_bm25_index* ix) {
+    return ix->wf != nullptr ? std::max(ix->n_terms, ix->tail ? ix->tail->n_terms : (int64_t)0) : (int64_t)ix->idf_h.size();
+}
+
+static int bm_fold(rag_ctx* h, const bm_slot& S);
+
+// Host checks of an appended block, before anything is built: the next n_new rows behind the covered ones, a term-major CSR over
+// V >= the known terms, documents ascending inside a term and relative to the block. ptrs_ok / planes_ok: the caller's further
+// arrays (document lengths, new idf values / the postings' value plane) are present.
+static int bm_check_block(rag_ctx* h, const char* who, const rag_bm25_index* ix, const int64_t* indptr, const int32_t* doc, int64_t n_new,
+                          int64_t V, bool ptrs_ok, bool planes_ok) {
+    const std::string w = std::string(who) + ": ";
+    const int64_t known = bm_known_terms(ix), covered = bm_total_docs(ix);
+    ARG_CHECK(h, n_new >= 1 && covered + n_new < 0x7fffffff, w + "n_docs_new must be >= 1 (and the index stay under 2^31 documents)");
+    ARG_CHECK(h, V >= known && V < 0x7fffffff, w + "n_terms_total may not shrink");
+    ARG_CHECK(h, indptr && ptrs_ok, w + "null pointer");
+    ARG_CHECK(h, !h->index_loaded || covered + n_new <= h->n_rows, w + "the block would cover more rows than the index has");
+    ARG_CHECK(h, indptr[0] == 0, w + "indptr must start at 0");
+    for (int64_t t = 0; t < V; ++t) {
+        const int64_t df = indptr[t + 1] - indptr[t];
+        ARG_CHECK(h, df >= 0 && df <= n_new, w + "indptr must be non-decreasing with at most n_docs_new postings per term");
+    }
+    ARG_CHECK(h, indptr[V] == 0 || (doc && planes_ok), w + "null postings");
+    for (int64_t t = 0; t < V; ++t)            // the block's documents become device addresses: in range, ascending inside a term
+        for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p)
+            ARG_CHECK(h, doc[p] >= 0 && doc[p] < n_new && (p == indptr[t] || doc[p] > doc[p - 1]),
+                      w + "doc must be ascending inside a term and below n_docs_new");
+    return RAG_OK;
+}
+
+// The new tail = old tail ++ block, built beside the old one: *out receives it on success only. `fill(b_indptr, b_doc, &b_w,
+// &b_tf16)` enqueues the block's weight plane (and, under keep_tf, its uint16 term frequencies) on the device; the buffers it
+// allocates belong to the caller and outlive this call's synchronise. idf: one value per term of V, or null (every idf 1).
+template <class W, class Fill>
+static int bm_build_tail(rag_ctx* h, const bm_builder& B, const rag_bm25_index* ix, const int64_t* indptr, const int32_t* doc,
+                         const int32_t* doc_len, int64_t n_new, int64_t V, const double* idf, Fill&& fill,
+                         std::unique_ptr<rag_bm25_index>* out) {
+    constexpr bool F32 = std::is_same<W, float>::value;
+    rag_bm25_index* ot = ix->tail.get();
+    const bool keep = ix->keep_tf;
+    const int64_t nnz_b = indptr[V], Vo = ot ? ot->n_terms : 0;
+    std::unique_ptr<rag_bm25_index> nt = bm_new_segment(ix, ix->n_docs, ix->tail_docs + n_new, V);
+    nt->indptr_h = bm_merged_offsets(ot ? ot->indptr_h.data() : nullptr, Vo, indptr, V, V);
+    std::vector<bm_term_meta> meta_h;
+    bm_plan_segment(nt.get(), idf, meta_h);
+    hipStream_t st = h->stream;
+    dev_buf<int64_t> b_indptr;
+    dev_buf<int32_t> b_doc;
+    auto enqueue = [&]() -> int {
+        int rc;
+        if ((rc = bm_prepare_segment(B, nt.get(), meta_h, {!F32, false, keep, keep, true, F32}))) return rc;
+        if (keep) {                          // the tail's document lengths: the old tail's, then the block's (its tf plane: concatenated below)
+            if (ot && ix->tail_docs)
+                HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first, ot->dl + ot->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first + ix->tail_docs, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, B.what))) return rc;
+        if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, B.what))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+        if (nnz_b) HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
+        const W* b_w = nullptr;
+        const uint16_t* b_tf16 = nullptr;
+        if ((rc = fill(b_indptr.get(), b_doc.get(), &b_w, &b_tf16))) return rc;
+        if (nt->nnz)
+            bm_launch_1d(bm25_concat_kernel<W>, nt->nnz, st, nt->indptr_d, V, nt->nnz, ot ? ot->meta.get() : nullptr, Vo,
+                         ot ? ot->doc.get() : nullptr, ot ? bm_weights<W>(ot).get() : nullptr, b_indptr, b_doc, b_w,
+                         (int32_t)(nt->first + ix->tail_docs), nt->doc, bm_weights<W>(nt.get()), ot ? ot->tf16.get() : nullptr, b_tf16,
+                         nt->tf16);
+        HIP_TRY(h, hipGetLastError());
+        return RAG_OK;
+    };
+    if (int rc = bm_finish_segment(B, nt.get(), enqueue())) return rc;
+    *out = std::move(nt);
+    return RAG_OK;
+}
+
+// The commit of an append: the new tail replaces the old one; the postings are aligned again when every row is covered and only
+// inserts came between (a plain compaction renumbers rows: reload); then the automatic fold of the slot's option.
+static void bm_append_commit(rag_ctx* h, const bm_slot& S, std::unique_ptr<rag_bm25_index> nt, int64_t n_new) {
+    rag_bm25_index* ix = S.ix;
+    ix->tail = std::move(nt);
+    ix->tail_docs += n_new;
+    ix->appends++;
+    if (S.stale && !S.compacted && h->index_loaded && bm_total_docs(ix) == h->n_rows) S.stale = false;
+    const int64_t fold_at = S.fold_opt > 0 ? S.fold_opt : (S.fold_opt == 0 ? bm_default_fold_docs(ix->n_docs) : -1);
+    if (fold_at > 0 && ix->tail_docs > fold_at && ix->packed == nullptr) {
+        if (bm_fold(h, S) != RAG_OK) h->err.clear();         // the append itself is done; the tail simply stays (e.g. no memory for the merged arrays)
+    }
+}
 
 int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
                      const double* idf_new, int64_t n_new, int64_t n_terms_total) {
@@ -1644,24 +1763,11 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
         h->err = "bm25_append: no postings loaded (rag_bm25_load_host first)";
         return RAG_ERR_STATE;
     }
+    const bm_slot S = bm_slot_bm25(h);
     rag_bm25_index* ix = h->bm25;
-    const rag_bm25_index* ot = ix->tail.get();
-    const int64_t known = (int64_t)ix->idf_h.size(), V = n_terms_total, covered = bm_total_docs(ix);
-    ARG_CHECK(h, n_new >= 1 && covered + n_new < 0x7fffffff, "bm25_append: n_docs_new must be >= 1 (and the index stay under 2^31 documents)");
-    ARG_CHECK(h, V >= known && V < 0x7fffffff, "bm25_append: n_terms_total may not shrink");
-    ARG_CHECK(h, indptr && doc_len && (V == known || idf_new), "bm25_append: null pointer");
-    ARG_CHECK(h, !h->index_loaded || covered + n_new <= h->n_rows, "bm25_append: the block would cover more rows than the index has");
-    ARG_CHECK(h, indptr[0] == 0, "bm25_append: indptr must start at 0");
-    for (int64_t t = 0; t < V; ++t) {
-        const int64_t df = indptr[t + 1] - indptr[t];
-        ARG_CHECK(h, df >= 0 && df <= n_new, "bm25_append: indptr must be non-decreasing with at most n_docs_new postings per term");
-    }
+    const int64_t known = (int64_t)ix->idf_h.size(), V = n_terms_total;
+    if (int rc = bm_check_block(h, S.append_name, ix, indptr, doc, n_new, V, doc_len && (V <= known || idf_new), tf != nullptr)) return rc;
     const int64_t nnz_b = indptr[V];
-    ARG_CHECK(h, nnz_b == 0 || (doc && tf), "bm25_append: null postings");
-    for (int64_t t = 0; t < V; ++t)            // the block's documents become device addresses: in range, ascending inside a term
-        for (int64_t p = indptr[t]; p < indptr[t + 1]; ++p)
-            ARG_CHECK(h, doc[p] >= 0 && doc[p] < n_new && (p == indptr[t] || doc[p] > doc[p - 1]),
-                      "bm25_append: doc must be ascending inside a term and below n_docs_new");
     const bool keep = ix->keep_tf;
     if (keep)
         if (int rc = bm_check_tf16(h, tf, nnz_b, "bm25_append")) return rc;
@@ -1669,76 +1775,48 @@ int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     idf_all.insert(idf_all.end(), idf_new, idf_new + (V - known));
     double neg = ix->neg_idf_absmax;
     for (int64_t t = known; t < V; ++t) if (idf_all[(size_t)t] < 0.0) neg = std::max(neg, -idf_all[(size_t)t]);
-    // the new tail = old tail ++ block
-    const bm_builder B = {h, "bm25_append", true};
+    const bm_builder B = {h, S.append_name, true};
     const char* what = B.what;
-    std::unique_ptr<rag_bm25_index> nt = bm_new_segment(ix, ix->n_docs, ix->tail_docs + n_new, V);
-    const int64_t Vo = ot ? ot->n_terms : 0;
-    nt->indptr_h = bm_merged_offsets(ot ? ot->indptr_h.data() : nullptr, Vo, indptr, V, V);
-    std::vector<bm_term_meta> meta_h;
-    bm_plan_segment(nt.get(), idf_all.data(), meta_h);
     hipStream_t st = h->stream;
-    dev_buf<int64_t> b_indptr;
-    dev_buf<int32_t> b_doc, b_tf, b_dl;
+    dev_buf<int32_t> b_tf, b_dl;
     dev_buf<double> b_w, idf_d;
     dev_buf<uint16_t> b_tf16;
-    auto enqueue = [&]() -> int {
+    // the block's impacts: the arithmetic of the load, with the FROZEN avgdl and the concatenated idf table
+    auto fill = [&](const int64_t* b_indptr, const int32_t* b_doc, const double** w_out, const uint16_t** tf16_out) -> int {
         int rc;
-        if ((rc = bm_prepare_segment(B, nt.get(), meta_h, {true, false, keep, keep, true}))) return rc;
-        if (keep) {                          // the tail's document lengths: the old tail's, then the block's (its tf plane: concatenated below)
-            if ((rc = bm_alloc(h, b_tf16, (size_t)nnz_b, what))) return rc;
-            if (ot && ix->tail_docs)
-                HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first, ot->dl + ot->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first + ix->tail_docs, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
-        }
-        if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, what))) return rc;
-        if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, what))) return rc;
+        if (keep && (rc = bm_alloc(h, b_tf16, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_tf, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_w, (size_t)nnz_b, what))) return rc;
         if ((rc = bm_alloc(h, b_dl, (size_t)n_new, what))) return rc;
         if ((rc = bm_alloc(h, idf_d, (size_t)V, what))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
         if (V) HIP_TRY(h, hipMemcpyAsync(idf_d, idf_all.data(), (size_t)V * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(b_dl, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
         if (nnz_b) {
-            HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(b_tf, tf, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
-            // the block's impacts: the arithmetic of the load, with the FROZEN avgdl and the concatenated idf table
             bm_launch_1d(bm25_impact_kernel<int32_t, bm_term_by_offsets>, nnz_b, st, bm_term_by_offsets{b_indptr, V}, b_doc, b_tf, b_dl, nnz_b,
                          ix->avgdl, ix->k1, ix->b, idf_d, b_w);
             if (keep) bm_launch_1d(bm25_tf16_kernel, nnz_b, st, b_tf, nnz_b, b_tf16);
         }
-        if (nt->nnz)
-            bm_launch_1d(bm25_concat_kernel, nt->nnz, st, nt->indptr_d, V, nt->nnz, ot ? ot->meta.get() : nullptr, Vo,
-                         ot ? ot->doc.get() : nullptr, ot ? ot->w.get() : nullptr, b_indptr, b_doc, b_w,
-                         (int32_t)(nt->first + ix->tail_docs), nt->doc, nt->w, ot ? ot->tf16.get() : nullptr, b_tf16, nt->tf16);
-        HIP_TRY(h, hipGetLastError());
+        *w_out = b_w;
+        *tf16_out = b_tf16;
         return RAG_OK;
     };
-    if (int rc = bm_finish_segment(B, nt.get(), enqueue())) return rc;
-    // commit
-    ix->tail = std::move(nt);
-    ix->tail_docs += n_new;
+    std::unique_ptr<rag_bm25_index> nt;
+    if (int rc = bm_build_tail<double>(h, B, ix, indptr, doc, doc_len, n_new, V, idf_all.data(), fill, &nt)) return rc;
     ix->idf_h = std::move(idf_all);
     ix->neg_idf_absmax = neg;
-    ix->appends++;
-    // aligned again: every row is covered and only inserts came between (a compaction renumbers rows: reload)
-    if (h->bm25_stale && !h->bm25_compacted && h->index_loaded && bm_total_docs(ix) == h->n_rows) h->bm25_stale = false;
-    const int64_t fold_at = h->opt.bm25_tail_fold > 0 ? h->opt.bm25_tail_fold : (h->opt.bm25_tail_fold == 0 ? bm_default_fold_docs(ix->n_docs) : -1);
-    if (fold_at > 0 && ix->tail_docs > fold_at && ix->packed == nullptr) {
-        if (bm25_fold(h) != RAG_OK) h->err.clear();          // the append itself is done; the tail simply stays (e.g. no memory for the merged arrays)
-    }
+    bm_append_commit(h, S, std::move(nt), n_new);
     return RAG_OK;
 }
 
 // base ++ tail -> one base, on the device; results are bit-identical before and after (the same impacts, per-term lists in the
 // same order, tables from the same builders)
-int bm25_fold(rag_ctx* h) {
-    if (!h->bm25) {
-        h->err = "bm25_fold: no postings loaded";
+static int bm_fold(rag_ctx* h, const bm_slot& S) {
+    if (!S.ix) {
+        h->err = std::string(S.fold_name) + ": no postings loaded";
         return RAG_ERR_STATE;
     }
-    rag_bm25_index* ix = h->bm25;
+    rag_bm25_index* ix = S.ix;
     rag_bm25_index* tl = ix->tail.get();
     if (tl == nullptr) return RAG_OK;
     if (ix->packed != nullptr) {
@@ -1746,23 +1824,26 @@ int bm25_fold(rag_ctx* h) {
                  "reload to merge";
         return RAG_ERR_STATE;
     }
-    const bm_builder B = {h, "bm25_fold", true};
-    const int64_t V = tl->n_terms, Vb = ix->n_terms;
-    const bool keep = ix->keep_tf;
+    const bm_builder B = {h, S.fold_name, true};
+    const int64_t V = std::max(tl->n_terms, ix->n_terms), Vb = ix->n_terms, Vt = tl->n_terms;
+    const bool keep = ix->keep_tf, f32 = ix->wf != nullptr;
     std::unique_ptr<rag_bm25_index> nb = bm_new_segment(ix, 0, bm_total_docs(ix), V);
-    nb->indptr_h = bm_merged_offsets(ix->indptr_h.data(), Vb, tl->indptr_h.data(), V, V);
+    nb->indptr_h = bm_merged_offsets(ix->indptr_h.data(), Vb, tl->indptr_h.data(), Vt, V);
     std::vector<bm_term_meta> meta_h;
-    bm_plan_segment(nb.get(), ix->idf_h.data(), meta_h);
+    bm_plan_segment(nb.get(), ix->idf_h.empty() ? nullptr : ix->idf_h.data(), meta_h);
     hipStream_t st = h->stream;
     auto enqueue = [&]() -> int {
         // (indptr_d: the concatenation's destination offsets; only a tail keeps them, see the commit)
-        if (int rc = bm_prepare_segment(B, nb.get(), meta_h, {true, false, keep, keep, true})) return rc;
+        if (int rc = bm_prepare_segment(B, nb.get(), meta_h, {!f32, false, keep, keep, true, f32})) return rc;
         if (keep) {                          // the documents' lengths: the base's, then the tail's own
             HIP_TRY(h, hipMemcpyAsync(nb->dl, ix->dl, (size_t)ix->n_docs * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(nb->dl + ix->n_docs, tl->dl + tl->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
         }
-        if (nb->nnz)
-            bm_launch_1d(bm25_concat_kernel, nb->nnz, st, nb->indptr_d, V, nb->nnz, ix->meta, Vb, ix->doc, ix->w, tl->indptr_d, tl->doc,
+        if (nb->nnz && f32)
+            bm_launch_1d(bm25_concat_kernel<float>, nb->nnz, st, nb->indptr_d, V, nb->nnz, ix->meta, Vb, ix->doc, ix->wf, tl->indptr_d, tl->doc,
+                         tl->wf, (int32_t)tl->row0, nb->doc, nb->wf, ix->tf16, tl->tf16, nb->tf16);
+        else if (nb->nnz)
+            bm_launch_1d(bm25_concat_kernel<double>, nb->nnz, st, nb->indptr_d, V, nb->nnz, ix->meta, Vb, ix->doc, ix->w, tl->indptr_d, tl->doc,
                          tl->w, (int32_t)tl->row0, nb->doc, nb->w, ix->tf16, tl->tf16, nb->tf16);
         HIP_TRY(h, hipGetLastError());
         return RAG_OK;
@@ -1773,9 +1854,11 @@ int bm25_fold(rag_ctx* h) {
     nb->idf_h = std::move(ix->idf_h);
     nb->folds = ix->folds + 1;
     delete ix;                               // the old base, its tail and their workspaces
-    h->bm25 = nb.release();
+    S.ix = nb.release();
     return RAG_OK;
 }
+int bm25_fold(rag_ctx* h) { return bm_fold(h, bm_slot_bm25(h)); }
+int sparse_fold(rag_ctx* h) { return bm_fold(h, bm_slot_sparse(h)); }
 
 // ---- postings through a compaction (rag_index_compact_bm25) ---------------------------------------------------------------
 // The compaction's row map is monotone on the live rows, so a STABLE stream compaction of a segment's whole posting array keeps
@@ -1833,13 +1916,14 @@ __global__ void bm25_compact_indptr_kernel(const int64_t* __restrict__ indptr, i
 
 // scatter pass: survivor p goes to tile_off[tile] + its rank inside the tile (set bits of the mask before it), renumbered into
 // the new segment (new local document = new row - new_row0). A tile's destinations are contiguous. PACKED: the 4-byte posting
-// keeps its code bits and gets the low bits of the new document number (a base: new_row0 = 0).
-template <bool PACKED>
-__global__ __launch_bounds__(256) void bm25_compact_scatter_kernel(const int32_t* __restrict__ doc, const double* __restrict__ w,
+// keeps its code bits and gets the low bits of the new document number (a base: new_row0 = 0). W: the weight plane of an unpacked
+// segment, float64 impacts or the learned-sparse index's float32 weights, moved as stored bits.
+template <bool PACKED, class W>
+__global__ __launch_bounds__(256) void bm25_compact_scatter_kernel(const int32_t* __restrict__ doc, const W* __restrict__ w,
                                                                     const uint32_t* __restrict__ packed, const int64_t* __restrict__ row_map,
                                                                     int64_t row0, int64_t new_row0, const unsigned long long* __restrict__ mask,
                                                                     const int64_t* __restrict__ tile_off, int32_t* __restrict__ doc_out,
-                                                                    double* __restrict__ w_out, uint32_t* __restrict__ packed_out,
+                                                                    W* __restrict__ w_out, uint32_t* __restrict__ packed_out,
                                                                     const uint16_t* __restrict__ tf, uint16_t* __restrict__ tf_out) {
     __shared__ int pre[BM_CP_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1885,7 +1969,8 @@ __global__ void bm25_compact_dl_kernel(const int32_t* __restrict__ dl, int64_t f
 // row_map[os->row0 + local document] is the new row or -1, rows at or past n_map have no entry. Synchronous.
 static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index* ns, const std::vector<double>& idf,
                             const int64_t* row_map, int64_t n_map, bool keep_indptr_d) {
-    const bm_builder B = {h, "compact_bm25", true};
+    const bool f32 = os->wf != nullptr;     // a learned-sparse segment (every idf 1: `idf` is empty)
+    const bm_builder B = {h, f32 ? "compact_live (sparse postings)" : "compact_bm25", true};
     const char* what = B.what;
     const int64_t V = os->n_terms, nnz = os->nnz, tiles = (nnz + BM_CP_TILE - 1) / BM_CP_TILE;
     const bool packed = os->packed != nullptr, keep = os->keep_tf;
@@ -1922,8 +2007,8 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
             HIP_TRY(h, hipMemcpyAsync(ns->indptr_h.data(), indptr_new, (size_t)(V + 1) * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(h, hipStreamSynchronize(st));
         }
-        bm_plan_segment(ns, idf.data(), meta_h);
-        if ((rc = bm_prepare_segment(B, ns, meta_h, {!packed, packed, keep && !packed, keep, keep_indptr_d}))) return rc;
+        bm_plan_segment(ns, idf.empty() ? nullptr : idf.data(), meta_h);
+        if ((rc = bm_prepare_segment(B, ns, meta_h, {!packed && !f32, packed, keep && !packed, keep, keep_indptr_d, f32}))) return rc;
         if (packed) {                        // the code table is shared by every posting that survives: copied as it is
             if ((rc = bm_alloc(h, ns->gtab, os->gtab.size(), what))) return rc;
             ns->n_codes = os->n_codes;
@@ -1940,18 +2025,23 @@ static int bm_remap_segment(rag_ctx* h, const rag_bm25_index* os, rag_bm25_index
         if (keep && own > 0)
             bm_launch_1d(bm25_compact_dl_kernel, own, st, os->dl, (int64_t)os->first, os->n_docs, os->row0, row_map, n_map, ns->row0,
                          ns->n_docs, ns->dl);
-        if (nnz > 0)
-            hipLaunchKernelGGL(packed ? bm25_compact_scatter_kernel<true> : bm25_compact_scatter_kernel<false>, dim3((unsigned)tiles), dim3(256),
-                               0, st, os->doc.get(), os->w.get(), os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(),
-                               ns->doc.get(), ns->w.get(), ns->packed.get(), os->tf16.get(), ns->tf16.get());
+        if (nnz > 0 && f32)
+            hipLaunchKernelGGL((bm25_compact_scatter_kernel<false, float>), dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->wf.get(),
+                               os->packed.get(), row_map, os->row0, ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->wf.get(),
+                               ns->packed.get(), os->tf16.get(), ns->tf16.get());
+        else if (nnz > 0)
+            hipLaunchKernelGGL((packed ? bm25_compact_scatter_kernel<true, double> : bm25_compact_scatter_kernel<false, double>),
+                               dim3((unsigned)tiles), dim3(256), 0, st, os->doc.get(), os->w.get(), os->packed.get(), row_map, os->row0,
+                               ns->row0, mask.get(), tile_off.get(), ns->doc.get(), ns->w.get(), ns->packed.get(), os->tf16.get(),
+                               ns->tf16.get());
         HIP_TRY(h, hipGetLastError());
         return RAG_OK;
     };
     return bm_finish_segment(B, ns, enqueue());
 }
 
-int64_t bm25_base_docs(const rag_ctx* h) { return h->bm25 ? h->bm25->n_docs : 0; }
-int64_t bm25_covered_docs(const rag_ctx* h) { return h->bm25 ? bm_total_docs(h->bm25) : 0; }
+int64_t bm25_base_docs(const rag_bm25_index* ix) { return ix ? ix->n_docs : 0; }
+int64_t bm25_covered_docs(const rag_bm25_index* ix) { return ix ? bm_total_docs(ix) : 0; }
 
 // The postings as they will be after the compaction whose device row map is `row_map` (entries for the covered rows), built
 // BESIDE the resident ones: *out is handed to bm25_compact_commit once the rows have moved, or to bm25_compact_discard.
@@ -1959,10 +2049,11 @@ int64_t bm25_covered_docs(const rag_ctx* h) { return h->bm25 ? bm_total_docs(h->
 // fold: a packed base cannot absorb its tail, and one rule serves both forms); the new tail hangs behind the new base exactly
 // as bm25_append_host would have put it (row0 = the base's last range, first = base documents in that range). A tail without
 // survivors is dropped; a base without survivors is replaced by the remapped tail (always the (doc, impact) form). *out stays
-// null when no covered row survives: there is nothing to keep, the caller falls back to the plain compaction.
-int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t base_live, int64_t covered_live, rag_bm25_index** out) {
+// null when no covered row survives: there is nothing to keep, the caller falls back to the plain compaction. ix: the BM25
+// postings (rag_index_compact_bm25, rag_index_compact_live) or the learned-sparse postings (rag_index_compact_live).
+int bm25_compact_prepare(rag_ctx* h, const rag_bm25_index* ix, const int64_t* row_map, int64_t base_live, int64_t covered_live,
+                         rag_bm25_index** out) {
     *out = nullptr;
-    const rag_bm25_index* ix = h->bm25;
     const rag_bm25_index* tl = ix->tail.get();
     const int64_t n_map = bm_total_docs(ix), tail_live = covered_live - base_live;
     if (covered_live <= 0) return RAG_OK;
@@ -1989,26 +2080,30 @@ int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t base_live, 
 
 void bm25_compact_discard(rag_bm25_index* nb) { delete nb; }
 
-void bm25_compact_commit(rag_ctx* h, rag_bm25_index* nb) {
-    delete h->bm25;                          // the old base, its tail and their workspaces
-    h->bm25 = nb;
+void bm25_compact_commit(rag_bm25_index** slot, rag_bm25_index* nb) {
+    delete *slot;                            // the old base, its tail and their workspaces
+    *slot = nb;
 }
 
-int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) {
-    ARG_CHECK(h, out != nullptr, "bm25_segment_stats: null output");
-    if (!h->bm25) {
-        h->err = "bm25_segment_stats: no postings loaded";
+// HBM bytes of one segment's arrays
+static int64_t bm_segment_bytes(const rag_bm25_index* s) {
+    return (int64_t)(s->doc.size() * 4 + s->w.size() * 8 + s->wf.size() * 4 + s->packed.size() * 4 + s->meta.size() * sizeof(bm_term_meta) +
+                     s->range_tab.size() * 4 + s->indptr_d.size() * 8 + s->tf16.size() * 2 + s->dl.size() * 4);
+}
+
+static int bm_segment_stats(rag_ctx* h, const bm_slot& S, rag_bm25_segments* out) {
+    ARG_CHECK(h, out != nullptr, std::string(S.stats_name) + ": null output");
+    if (!S.ix) {
+        h->err = std::string(S.stats_name) + ": no postings loaded";
         return RAG_ERR_STATE;
     }
-    const rag_bm25_index* ix = h->bm25;
+    const rag_bm25_index* ix = S.ix;
     const rag_bm25_index* tl = ix->tail.get();
-    *out = {ix->n_docs, ix->tail_docs, ix->nnz, tl ? tl->nnz : 0, (int64_t)ix->idf_h.size(),
-            tl ? (int64_t)((tl->doc.size() * 4 + tl->w.size() * 8 + tl->meta.size() * sizeof(bm_term_meta) + tl->range_tab.size() * 4 +
-                            tl->indptr_d.size() * 8 + tl->tf16.size() * 2 + tl->dl.size() * 4))
-               : 0,
-            ix->appends, ix->folds};
+    *out = {ix->n_docs, ix->tail_docs, ix->nnz, tl ? tl->nnz : 0, bm_known_terms(ix), tl ? bm_segment_bytes(tl) : 0, ix->appends, ix->folds};
     return RAG_OK;
 }
+int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) { return bm_segment_stats(h, bm_slot_bm25(h), out); }
+int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out) { return bm_segment_stats(h, bm_slot_sparse(h), out); }
 
 static int bm25_set_attr(rag_ctx* h) {
     return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>, bm25_range_tenants_kernel<true>,
@@ -2022,8 +2117,8 @@ static int bm25_set_attr(rag_ctx* h) {
 static inline bool bm_resident(const rag_ctx* h, const rag_bm25_index* ix) { return ix == h->bm25 || ix == h->sparse; }
 static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
     if (ix == h->sparse && h->sparse_stale) {
-        h->err = "sparse: the postings are stale (rows were inserted or compacted since rag_sparse_load_host): reload postings "
-                 "aligned with the current rows";
+        h->err = "sparse: the postings are stale (rows were inserted or compacted since rag_sparse_load_host): append the inserted "
+                 "rows' postings (rag_sparse_append_host) or reload postings aligned with the current rows";
         return RAG_ERR_STATE;
     }
     if (ix != h->bm25 || !h->bm25_stale) return RAG_OK;
@@ -2553,15 +2648,14 @@ int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     const bm_builder B = {h, "sparse_load", false};
     std::unique_ptr<rag_bm25_index> ix = bm_new_segment(nullptr, 0, n_docs, n_terms);
     ix->nnz = nnz;
+    ix->indptr_h.assign(indptr, indptr + n_terms + 1);   // the fold and the compaction's remap plan from the host offsets
     ix->normalize = 0;                                   // scores are raw
     std::vector<bm_term_meta> meta_h;
     ix->tab_entries = bm_plan_terms(indptr, n_terms, n_docs, nullptr, n_docs, &meta_h);
     hipStream_t st = h->stream;
     auto enqueue = [&]() -> int {
         int rc;
-        if ((rc = bm_prepare_segment(B, ix.get(), meta_h, {false, false, false, false, false}))) return rc;
-        if ((rc = B.alloc(ix->wf, (size_t)nnz + 8))) return rc;                  // the same 8 postings of padding as doc
-        HIP_TRY(h, hipMemsetAsync(ix->wf + nnz, 0, 8 * sizeof(float), st));
+        if ((rc = bm_prepare_segment(B, ix.get(), meta_h, {false, false, false, false, false, true}))) return rc;
         if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->doc, doc, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (nnz) HIP_TRY(h, hipMemcpyAsync(ix->wf, weight, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
         return RAG_OK;
@@ -2570,19 +2664,50 @@ int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, cons
     sparse_free(h);
     h->sparse = ix.release();
     h->sparse_stale = false;
+    h->sparse_compacted = false;
     return RAG_OK;
 }
 
-int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out) {
-    const rag_bm25_index* ix = h->sparse;
-    if (n_docs_out) *n_docs_out = ix ? ix->n_docs : 0;
-    if (n_terms_out) *n_terms_out = ix ? ix->n_terms : 0;
-    if (nnz_out) *nnz_out = ix ? ix->nnz : 0;
-    if (hbm_bytes_out)
-        *hbm_bytes_out = ix ? (int64_t)(ix->doc.size() * 4 + ix->wf.size() * 4 + ix->meta.size() * sizeof(bm_term_meta) + ix->range_tab.size() * 4) : 0;
+// The next n_new rows behind the covered ones (rag_sparse_append_host): bm25_append_host's tail rebuild with the block's float32
+// weights uploaded as they are. Everything is checked on the host before anything is built; a failure changes nothing.
+int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_new, int64_t n_terms_total) {
+    if (!h->sparse) {
+        h->err = "sparse_append: no postings loaded (rag_sparse_load_host first)";
+        return RAG_ERR_STATE;
+    }
+    const bm_slot S = bm_slot_sparse(h);
+    rag_bm25_index* ix = h->sparse;
+    const int64_t V = n_terms_total;
+    if (int rc = bm_check_block(h, S.append_name, ix, indptr, doc, n_new, V, true, weight != nullptr)) return rc;
+    const int64_t nnz_b = indptr[V];
+    for (int64_t p = 0; p < nnz_b; ++p)
+        ARG_CHECK(h, std::isfinite(weight[p]) && weight[p] > 0.0f, "sparse_append: weights must be finite and > 0");
+    const bm_builder B = {h, S.append_name, true};
+    dev_buf<float> b_w;
+    auto fill = [&](const int64_t*, const int32_t*, const float** w_out, const uint16_t** tf16_out) -> int {
+        if (int rc = bm_alloc(h, b_w, (size_t)nnz_b, B.what)) return rc;
+        if (nnz_b) HIP_TRY(h, hipMemcpyAsync(b_w, weight, (size_t)nnz_b * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        *w_out = b_w;
+        *tf16_out = nullptr;
+        return RAG_OK;
+    };
+    std::unique_ptr<rag_bm25_index> nt;
+    if (int rc = bm_build_tail<float>(h, B, ix, indptr, doc, nullptr, n_new, V, nullptr, fill, &nt)) return rc;
+    bm_append_commit(h, S, std::move(nt), n_new);
     return RAG_OK;
 }
-int64_t sparse_n_docs(const rag_ctx* h) { return h->sparse ? h->sparse->n_docs : -1; }
+
+// base and tail together
+int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out) {
+    const rag_bm25_index* ix = h->sparse;
+    const rag_bm25_index* tl = ix ? ix->tail.get() : nullptr;
+    if (n_docs_out) *n_docs_out = ix ? bm_total_docs(ix) : 0;
+    if (n_terms_out) *n_terms_out = ix ? bm_known_terms(ix) : 0;
+    if (nnz_out) *nnz_out = ix ? ix->nnz + (tl ? tl->nnz : 0) : 0;
+    if (hbm_bytes_out) *hbm_bytes_out = ix ? bm_segment_bytes(ix) + (tl ? bm_segment_bytes(tl) : 0) : 0;
+    return RAG_OK;
+}
+int64_t sparse_n_docs(const rag_ctx* h) { return h->sparse ? bm_total_docs(h->sparse) : -1; }
 int sparse_fresh(rag_ctx* h) { return h->sparse ? bm25_check_fresh(h, h->sparse) : RAG_OK; }
 
 // without a dense index of the same rows the ids are row numbers and there is nothing a tenant could be looked up in
@@ -2590,7 +2715,7 @@ static int sparse_args(rag_ctx* h, const void* term_ptr, const void* qweights, i
     ARG_CHECK(h, h->sparse != nullptr, "no sparse index loaded (rag_sparse_load_host)");
     ARG_CHECK(h, term_ptr != nullptr && qweights != nullptr, "sparse: null query arrays");
     if (int rc = bm25_check_fresh(h, h->sparse)) return rc;
-    ARG_CHECK(h, tenant < 0 || (h->index_loaded && h->tenants != nullptr && h->n_rows == h->sparse->n_docs),
+    ARG_CHECK(h, tenant < 0 || (h->index_loaded && h->tenants != nullptr && h->n_rows == bm_total_docs(h->sparse)),
               "sparse: a tenant filter needs a dense index of the same rows with rag_index_set_tenants_host");
     return RAG_OK;
 }

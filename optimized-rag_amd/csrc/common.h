@@ -75,6 +75,8 @@ struct rag_options {
     int bm25_packed = 0;          // (read when postings are LOADED) 4-byte packed postings + shared impact table instead of (doc, impact)
     int bm25_keep_tf = 0;         // (read when postings are LOADED) keep uint16 term frequencies + document lengths (a packed base: its value tables) so that rag_bm25_refresh can recompute every impact on the device: +2 B per posting, +4 B per document
     int bm25_tail_fold = 0;       // appended postings: an append folds the tail into the base once it holds more than this many documents (-1 = never, 0 = the default policy, bm25.hip bm_default_fold_docs)
+    int sparse_tail_fold = 0;     // the same for appended learned-sparse postings (rag_sparse_append_host)
+    int tokvec_compact_rows = 0;  // rag_index_compact_live: token rows per staging chunk of the token-vector move (0 = sized from the staging bound); tests force a small value
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
@@ -196,7 +198,8 @@ struct rag_ctx : rag_device_mem {
 
     rag_bm25_index* bm25 = nullptr;
     rag_bm25_index* sparse = nullptr;        // learned-sparse postings (rag_sparse_load_host): a slot of its own beside the BM25 postings
-    bool sparse_stale = false;               // rows were inserted or compacted since they were loaded: sparse entry points refuse until a reload
+    bool sparse_stale = false;               // rows were inserted or compacted since they were aligned: sparse entry points refuse until rag_sparse_append_host covers the inserted rows, or a reload
+    bool sparse_compacted = false;           // ... and a plain compaction was among them: only a reload helps
     int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
     int tok_L = 0;
     int64_t tv_docs = 0, tv_rows = 0;        // token-vector store: documents / rows appended so far ...
@@ -422,10 +425,12 @@ int bm25_fresh(rag_ctx* h);            // RAG_ERR_STATE while the postings are s
 int live_vis_extend(rag_ctx* h, int64_t first_row, int64_t n);
 // postings through a compaction (rag_index_compact_bm25): built beside the resident ones from the device row map before any
 // row moves, swapped in (or dropped) afterwards
-int64_t bm25_base_docs(const rag_ctx* h);
-int64_t bm25_covered_docs(const rag_ctx* h);
-int bm25_compact_prepare(rag_ctx* h, const int64_t* row_map_dev, int64_t base_live, int64_t covered_live, rag_bm25_index** out);
-void bm25_compact_commit(rag_ctx* h, rag_bm25_index* nb);
+// (ix / slot: the BM25 postings rag_ctx::bm25 or the learned-sparse postings rag_ctx::sparse)
+int64_t bm25_base_docs(const rag_bm25_index* ix);
+int64_t bm25_covered_docs(const rag_bm25_index* ix);
+int bm25_compact_prepare(rag_ctx* h, const rag_bm25_index* ix, const int64_t* row_map_dev, int64_t base_live, int64_t covered_live,
+                         rag_bm25_index** out);
+void bm25_compact_commit(rag_bm25_index** slot, rag_bm25_index* nb);
 void bm25_compact_discard(rag_bm25_index* nb);
 int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists, int64_t list_stride, int Q, int k,
                int64_t* ids_out, double* scores_out, hipStream_t st, int normalize = 0);
@@ -466,6 +471,17 @@ int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t
 int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim);
 int tokvec_info(const rag_ctx* h, int64_t* docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out);
 int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int64_t* n_rows_out);
+// the store through a compaction (rag_index_compact_live): everything allocated by tokvec_compact_prepare before a row of any
+// plane moves; tokvec_compact_commit moves the rows in place through the compaction's staging buffer and swaps the offsets in
+struct tokvec_compact_plan {
+    dev_buf<int64_t> new_off;                // the store's offsets after the move [tv_docs_cap + 1]
+    dev_buf<int64_t> src_start;              // [new documents] first OLD row of each surviving document
+    std::vector<int64_t> new_off_h;          // host copy of new_off[0 .. docs_new]
+    int64_t docs_new = 0, rows_new = 0, first_doc = 0, chunk_rows = 0;
+    bool active = false;
+};
+int tokvec_compact_prepare(rag_ctx* h, const int64_t* row_map_host, int64_t n_map, size_t stage_bytes, tokvec_compact_plan* plan);
+int tokvec_compact_commit(rag_ctx* h, tokvec_compact_plan* plan, char* stage, hipStream_t st);
 int tokvec_usable(rag_ctx* h, const char* who);          // RAG_ERR_STATE without a store or with a stale one
 int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
                   int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st);

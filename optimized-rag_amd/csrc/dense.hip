@@ -1081,6 +1081,7 @@ int dense_free(rag_ctx* h) {
     h->bm25_stale = false;
     h->bm25_compacted = false;
     h->sparse_stale = false;
+    h->sparse_compacted = false;
     h->n_rows = h->n_rows_pad = 0;
     h->n_reserved = 0;
     h->index_loaded = false;

@@ -376,7 +376,10 @@ int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out) {
 // rag_index_compact (keep_postings = false: the postings end stale and compacted) and rag_index_compact_bm25 (true: loaded
 // postings that describe the rows are renumbered through the row map, beside the old ones, BEFORE the first row moves, and
 // swapped in once the rows have moved; bm25_stale is left as it was - current stays current, uncovered rows stay uncovered)
-static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, bool keep_postings) {
+// and rag_index_compact_live (LIVE_KEEP_RESIDENT: the same for the learned-sparse postings as well, and the token-vector store's
+// documents move with their rows - tokvec.hip, "the store through a compaction" - instead of going stale)
+enum { LIVE_KEEP_NONE = 0, LIVE_KEEP_BM25 = 1, LIVE_KEEP_RESIDENT = 2 };
+static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, int keep) {
     int rc = live_begin(h);
     if (rc) return rc;
     const int64_t n0 = h->index_loaded ? h->n_rows : 0;
@@ -400,9 +403,13 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
         HIP_TRY(h, hipGetLastError());
     }
     const int64_t tiles = (n0 + RAG_TILE - 1) / RAG_TILE;
+    // (the token-vector store's own maps are per document - new offsets and first source row, tokvec_compact_prepare - and count
+    // against the same bound)
+    const bool move_tv = keep == LIVE_KEEP_RESIDENT && h->tv_docs_cap > 0 && !h->tv_stale;
+    const size_t tv_bytes = move_tv ? stage_size((size_t)h->tv_docs_cap + 1, 8) + stage_size((size_t)h->tv_docs + 1, 8) : 0;
     const size_t map_bytes = stage_size(tiles, 4) + stage_size(tiles, 8) + stage_size(n0, 8) + stage_size(n0, 4);
-    ARG_CHECK(h, map_bytes + ((size_t)64 << 20) <= LIVE_STAGING_BYTES, "compact: the row map of this index exceeds the 1 GiB staging bound");
-    const size_t data_bytes = std::min<size_t>((size_t)512 << 20, LIVE_STAGING_BYTES - map_bytes);
+    ARG_CHECK(h, map_bytes + tv_bytes + ((size_t)64 << 20) <= LIVE_STAGING_BYTES, "compact: the row map of this index exceeds the 1 GiB staging bound");
+    const size_t data_bytes = std::min<size_t>((size_t)512 << 20, LIVE_STAGING_BYTES - map_bytes - tv_bytes);
     dev_buf<char> ws;
     if (ws.alloc(h, map_bytes + data_bytes)) {
         (void)hipGetLastError();
@@ -441,9 +448,11 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     struct new_postings {
         rag_bm25_index* p = nullptr;
         ~new_postings() { if (p) bm25_compact_discard(p); }
-    } np;
-    const int64_t covered = bm25_covered_docs(h);
-    if (keep_postings && h->bm25 && !h->bm25_compacted && covered <= n0) {
+    } np, np_sparse;
+    // one resident index (the BM25 or the learned-sparse postings) that describes the rows: remapped into `dst`
+    auto prepare = [&](const rag_bm25_index* ix, bool compacted, new_postings& dst) -> int {
+        const int64_t covered = bm25_covered_docs(ix);
+        if (ix == nullptr || compacted || covered > n0) return RAG_OK;
         // live rows below row x: the scanned tile offsets + the live rows of x's own tile before it (at most 255 map entries)
         auto live_below = [&](int64_t x, int64_t* out) -> int {
             *out = n_live;
@@ -457,9 +466,20 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
             return RAG_OK;
         };
         int64_t base_live = 0, covered_live = 0;
-        if ((rc = live_below(bm25_base_docs(h), &base_live))) return rc;
-        if ((rc = live_below(covered, &covered_live))) return rc;
-        if ((rc = bm25_compact_prepare(h, row_map, base_live, covered_live, &np.p))) return rc;
+        int rc2;
+        if ((rc2 = live_below(bm25_base_docs(ix), &base_live))) return rc2;
+        if ((rc2 = live_below(covered, &covered_live))) return rc2;
+        return bm25_compact_prepare(h, ix, row_map, base_live, covered_live, &dst.p);
+    };
+    if (keep >= LIVE_KEEP_BM25 && (rc = prepare(h->bm25, h->bm25_compacted, np))) return rc;
+    if (keep == LIVE_KEEP_RESIDENT && (rc = prepare(h->sparse, h->sparse_compacted, np_sparse))) return rc;
+    // the token-vector store's new offsets and per-document source map, from a host copy of the row map
+    tokvec_compact_plan tvp;
+    if (move_tv) {
+        std::vector<int64_t> map_h((size_t)n0);
+        HIP_TRY(h, hipMemcpyAsync(map_h.data(), row_map, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if ((rc = tokvec_compact_prepare(h, map_h.data(), n0, data_bytes, &tvp))) return rc;
     }
     // every plane, chunk by chunk of destination rows through the staging buffer
     struct plane { void* p; size_t row_bytes; };
@@ -497,7 +517,9 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     if (n0 > n_live) e = hipMemsetAsync(h->emb16 + (size_t)n_live * h->dim_pad, 0, (size_t)(n0 - n_live) * h->dim_pad * 2, st);
     if (e == hipSuccess && row_map_out) e = hipMemcpyAsync(row_map_out, row_map, (size_t)n0 * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e, "finish");
+    if ((rc = tokvec_compact_commit(h, &tvp, data, st))) return rc;      // (the staging buffer is free again: same stream)
+    e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(e, "finish");
     ws.reset();
     h->n_rows = n_live;
@@ -505,10 +527,16 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
     h->vis.reset();
     h->cap_vis = 0;
     h->n_deleted = 0;
-    h->sparse_stale = true;                  // learned-sparse postings are not renumbered: a reload makes them current
-    if (h->tv_docs_cap > 0) h->tv_stale = true;      // nor are the resident token vectors (tokvec.hip)
+    if (np_sparse.p) {                       // rag_index_compact_live: renumbered with the rows, staleness left as it was
+        bm25_compact_commit(&h->sparse, np_sparse.p);
+        np_sparse.p = nullptr;
+    } else {                                 // not renumbered: a reload makes them current
+        h->sparse_stale = true;
+        h->sparse_compacted = true;
+    }
+    if (h->tv_docs_cap > 0 && !move_tv) h->tv_stale = true;      // nor are the resident token vectors, unless they moved (tokvec.hip)
     if (np.p) {
-        bm25_compact_commit(h, np.p);
+        bm25_compact_commit(&h->bm25, np.p);
         np.p = nullptr;
     } else {
         h->bm25_stale = true;
@@ -528,13 +556,19 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, b
 int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    return live_compact(h, row_map_out, n_rows_out, false);
+    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_NONE);
 }
 
 int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
-    return live_compact(h, row_map_out, n_rows_out, true);
+    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_BM25);
+}
+
+int rag_index_compact_live(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_RESIDENT);
 }
 
 }  // extern "C"

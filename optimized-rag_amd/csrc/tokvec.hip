@@ -304,6 +304,100 @@ int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int
     return RAG_OK;
 }
 
+// ---- the store through a compaction (rag_index_compact_live) --------------------------------------------------------------
+// A document is a variable-length group of rows, so the planes' fixed-row gather does not serve. The map is PER DOCUMENT (8 B: the
+// first old row of each surviving document, beside the new offsets), never per token row. One chunk of destination rows
+// [r0, r0 + m) at a time: each lane moves 16 bytes (fp16 bits, never converted) of destination row R into the staging buffer; the
+// row's document is the LAST d in [doc_lo, doc_hi] with new_off[d] <= R (documents without rows share their start with the next
+// one: the last owns the row), a search over the chunk's own documents, and its source row is src_start[d] + (R - new_off[d]).
+// The chunk is then copied to its destination. In place and safe: chunks ascend, every source row lies at or above its
+// destination (rows only move down), so a chunk's sources lie at or above r0 - untouched by the earlier chunks, which wrote
+// below r0 - and are all in the staging buffer before the copy overwrites [r0, r0 + m).
+__global__ __launch_bounds__(256) void tokvec_compact_gather_kernel(const uint4* __restrict__ store, int units_per_row,
+                                                                     const int64_t* __restrict__ new_off, const int64_t* __restrict__ src_start,
+                                                                     int64_t doc_lo, int64_t doc_hi, int64_t r0, int64_t total,
+                                                                     uint4* __restrict__ stage) {
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
+        const int64_t row = u / units_per_row, c = u - row * units_per_row, R = r0 + row;
+        int64_t lo = doc_lo, hi = doc_hi + 1;                  // new_off[doc_lo] <= r0 <= R
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (new_off[mid] <= R) lo = mid; else hi = mid;
+        }
+        const int64_t src = src_start[lo] + (R - new_off[lo]);
+        stage[u] = store[src * units_per_row + c];
+    }
+}
+
+// Plans the move from the compaction's row map (host copy, n_map = index rows before): documents [0, min(tv_docs, n_map)) go
+// through the map, documents the store holds past the index rows keep their order behind the survivors. Allocates the new
+// offsets and the per-document source map (RAG_ERR_NOMEM changes nothing); plan->active stays false when there is no usable
+// store or no document of it is deleted.
+int tokvec_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t n_map, size_t stage_bytes, tokvec_compact_plan* plan) {
+    plan->active = false;
+    if (h->tv_docs_cap <= 0 || h->tv_stale || h->tv_docs == 0) return RAG_OK;
+    hipStream_t st = h->stream;
+    const int64_t nd = h->tv_docs, nd_map = std::min(nd, n_map);
+    std::vector<int64_t> off((size_t)nd + 1);
+    HIP_TRY(h, hipMemcpyAsync(off.data(), h->tv_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::vector<int64_t> src_start;
+    plan->new_off_h.assign(1, 0);
+    plan->first_doc = -1;
+    for (int64_t d = 0; d < nd; ++d) {
+        if (d < nd_map && row_map[d] < 0) {
+            if (plan->first_doc < 0) plan->first_doc = (int64_t)src_start.size();
+            continue;
+        }
+        src_start.push_back(off[(size_t)d]);
+        plan->new_off_h.push_back(plan->new_off_h.back() + (off[(size_t)d + 1] - off[(size_t)d]));
+    }
+    if (plan->first_doc < 0) return RAG_OK;
+    plan->docs_new = (int64_t)src_start.size();
+    plan->rows_new = plan->new_off_h.back();
+    const int64_t row_bytes = (int64_t)h->tv_dim * (int64_t)sizeof(half_t);
+    plan->chunk_rows = h->opt.tokvec_compact_rows > 0 ? h->opt.tokvec_compact_rows : (int64_t)(stage_bytes / (size_t)row_bytes);
+    plan->chunk_rows = std::max<int64_t>(1, std::min(plan->chunk_rows, (int64_t)(stage_bytes / (size_t)row_bytes)));
+    if (plan->new_off.alloc(h, (size_t)h->tv_docs_cap + 1) || plan->src_start.alloc(h, std::max<size_t>(1, src_start.size()))) {
+        (void)hipGetLastError();
+        plan->new_off.reset();
+        plan->src_start.reset();
+        h->err = "compact_live: out of device memory for the token-vector store's new offsets";
+        return RAG_ERR_NOMEM;
+    }
+    HIP_TRY(h, hipMemcpyAsync(plan->new_off, plan->new_off_h.data(), plan->new_off_h.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (!src_start.empty())
+        HIP_TRY(h, hipMemcpyAsync(plan->src_start, src_start.data(), src_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));                        // src_start is a local
+    plan->active = true;
+    return RAG_OK;
+}
+
+// Moves the rows through `stage` (at least chunk_rows rows), waits, then swaps the offsets in and shrinks the counts: the freed
+// rows are headroom of the same reservation again.
+int tokvec_compact_commit(rag_ctx* h, tokvec_compact_plan* plan, char* stage, hipStream_t st) {
+    if (!plan->active) return RAG_OK;
+    const int upr = h->tv_dim / 8;                               // 16-byte units per row (dim is a multiple of 32)
+    const size_t row_bytes = (size_t)h->tv_dim * sizeof(half_t);
+    const std::vector<int64_t>& no = plan->new_off_h;
+    const auto doc_of = [&](int64_t r) { return (int64_t)(std::upper_bound(no.begin(), no.begin() + plan->docs_new + 1, r) - no.begin()) - 1; };
+    for (int64_t r0 = no[(size_t)plan->first_doc]; r0 < plan->rows_new; r0 += plan->chunk_rows) {
+        const int64_t m = std::min(plan->chunk_rows, plan->rows_new - r0), total = m * upr;
+        const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)1 << 20);
+        launch(tokvec_compact_gather_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(h->tv.get()), upr,
+               plan->new_off.get(), plan->src_start.get(), doc_of(r0), doc_of(r0 + m - 1), r0, total, reinterpret_cast<uint4*>(stage));
+        HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->tv.get()) + (size_t)r0 * row_bytes, stage, (size_t)m * row_bytes,
+                                  hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(st));
+    h->tv_off = std::move(plan->new_off);
+    h->tv_docs = plan->docs_new;
+    h->tv_rows = plan->rows_new;
+    plan->active = false;
+    return RAG_OK;
+}
+
 int tokvec_usable(rag_ctx* h, const char* who) {
     if (h->tv_docs_cap <= 0) {
         h->err = std::string(who) + ": no token-vector store (rag_tokvec_reserve / rag_tokvec_load_host)";

@@ -76,6 +76,7 @@ class GpuDocumentIndex:
         self._next_id = 0
         self._doc_chunks: Dict[tuple, List[int]] = {}
         self._shard_without_doc_ids = False
+        self._lexical = None                           # host mirror of the resident lexical postings (load_lexical), kept for live writes
 
     @property
     def engine(self):
@@ -131,13 +132,30 @@ class GpuDocumentIndex:
 
     # ---- live writes (rag_index_insert_host / rag_index_delete_host / rag_index_compact) --------------------------------
     @_locked
-    def add_rows(self, rows: List[Dict[str, Any]], embeddings) -> List[int]:
+    def add_rows(self, rows: List[Dict[str, Any]], embeddings, *, lexical_weights=None, token_vectors=None) -> List[int]:
         """The incremental form of bulk_load: rows[i] {content, agent_id, id?, document_id?, ...} + embeddings [n, dim].
-        A row without `id` gets the next one. Returns the ids; the rows are searchable on return."""
+        A row without `id` gets the next one. Returns the ids; the rows are searchable on return.
+        lexical_weights: one {token id: weight} map per row; when lexical postings are resident (load_lexical) the block is
+        appended to them (rag_sparse_append_host) and search_lexical stays live. token_vectors: (vecs float32 [rows, tok_dim],
+        offsets int64 [n + 1]), host arrays or CUDA tensors; when a token-vector store is resident the documents are appended to
+        it (its reservation must have the headroom). Both happen under the same lock as the insert: a search sees all legs of
+        the new rows or none. Without the arguments the behaviour is unchanged: the resident legs go stale / fall behind."""
         emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
         assert emb.shape[0] == len(rows)
         if not rows:
             return []
+        lex_block = None
+        if lexical_weights is not None and self._lexical is not None:
+            from .sparse import LexicalPostings
+            if len(lexical_weights) != len(rows):
+                raise ValueError(f"add_rows: {len(lexical_weights)} lexical maps for {len(rows)} rows")
+            if self._lexical.n_docs != len(self.rows):
+                raise ValueError("add_rows: the lexical postings do not cover the current rows (load_lexical again)")
+            top = max((int(k) for m in lexical_weights for k in m), default=-1)
+            lex_block = LexicalPostings.from_weights(lexical_weights, max(self._lexical.n_terms, top + 1))     # checked before anything is written
+        store = token_vectors is not None and self.engine.tokvec_info()["dim"] > 0
+        if store and self.engine.tokvec_info()["n_docs"] != len(self.rows):
+            raise ValueError("add_rows: the token-vector store does not cover the current rows")
         ids = np.empty(len(rows), dtype=np.int64)
         ten = np.empty(len(rows), dtype=np.int32)
         for i, r in enumerate(rows):
@@ -145,6 +163,14 @@ class GpuDocumentIndex:
             self._next_id = max(self._next_id, int(ids[i]) + 1)
             ten[i] = self._tenant_id.setdefault(str(r.get("agent_id", "")), len(self._tenant_id))
         self.engine.index_insert(emb, ids=ids, tenants=ten)
+        if lex_block is not None:
+            self._lexical.append_to(self.engine, self._lexical.extend(lex_block))
+        if store:
+            vecs, offsets = token_vectors
+            if hasattr(vecs, "is_cuda"):
+                self.engine.tokvec_append_dev(vecs, offsets, n_docs=len(rows))
+            else:
+                self.engine.tokvec_append(vecs, np.ascontiguousarray(offsets, dtype=np.int64)[:len(rows) + 1])
         if not isinstance(self.rows, (list, _RowView)):
             self.rows = _RowView(self.rows)
         for i, r in enumerate(rows):
@@ -221,9 +247,62 @@ class GpuDocumentIndex:
         return self._delete_ids(agent_id, [int(memory_id)]) > 0
 
     @_locked
-    def compact(self) -> np.ndarray:
-        """Drop deleted rows from HBM (rag_index_compact) and remap the payload rows; returns row_map[old row]."""
-        row_map = self.engine.index_compact()
+    def add_texts(self, agent_id: str, texts: List[str], *, batch: int = 64, document_id: Optional[int] = None,
+                  metadata: Optional[Dict[str, Any]] = None) -> List[int]:
+        """Embed `texts` and add them as rows of `agent_id`: ONE forward per batch gives all three heads of the embedding
+        service - the dense vector, the lexical weights (when lexical postings are resident) and the token vectors (when a
+        token-vector store is resident), which go from the forward's output tensor into the store and never exist on the host, as
+        in build_token_vectors. Each batch goes through add_rows. Returns the ids."""
+        import torch
+        svc = self.embeddings
+        texts = [str(t) for t in texts]
+        want_lex = self._lexical is not None
+        want_tok = self.engine.tokvec_info()["dim"] > 0
+        svc._need_heads(want_lex, want_tok)
+        skip = set(svc.special_ids())
+        ids_out: List[int] = []
+        batch = max(1, int(batch))
+        for b in range(0, len(texts), batch):
+            part = texts[b:b + batch]
+            ids, tt, lens = svc.tokenize(part)
+            n, L = ids.shape
+            dense = torch.empty((n, self.dim), dtype=torch.float32, device="cuda")
+            lex = torch.empty((n, L), dtype=torch.float32, device="cuda") if want_lex else None
+            tok = off = None
+            if want_tok:
+                rows = int((np.clip(lens, 1, L).astype(np.int64) - 1).sum())
+                tok = torch.empty((max(rows, 1), int(svc.engine.embed_tok_dim)), dtype=torch.float32, device="cuda")
+                off = torch.empty((n + 1,), dtype=torch.int64, device="cuda")
+            svc.engine.embed_multi_dev(torch.from_numpy(ids).cuda(), torch.from_numpy(tt).cuda(), torch.from_numpy(lens).cuda(),
+                                       dense=dense, lex=lex, tok=tok, row_off=off)
+            torch.cuda.synchronize()
+            maps = None
+            if want_lex:                                             # the largest weight > 0 of each token id, special tokens left out (encode_multi)
+                lx = lex.cpu().numpy()
+                maps = []
+                for i in range(n):
+                    m: Dict[int, float] = {}
+                    for t in range(int(lens[i])):
+                        k, w = int(ids[i, t]), float(lx[i, t])
+                        if k not in skip and w > 0 and w > m.get(k, 0.0):
+                            m[k] = w
+                    maps.append(m)
+            rows_ = [{"agent_id": agent_id, "content": t, "metadata": dict(metadata or {}),
+                      **({"document_id": int(document_id)} if document_id is not None else {})} for t in part]
+            ids_out += self.add_rows(rows_, dense.cpu().numpy(), lexical_weights=maps, token_vectors=(tok, off) if want_tok else None)
+        return ids_out
+
+    @_locked
+    def compact(self, keep_resident: bool = False) -> np.ndarray:
+        """Drop deleted rows from HBM (rag_index_compact) and remap the payload rows; returns row_map[old row]. keep_resident
+        (rag_index_compact_live): resident lexical postings and token vectors move with the rows and stay searchable, and the
+        held lexical mirror is remapped; by default both end stale until they are loaded again."""
+        row_map = self.engine.index_compact(keep_resident=True) if keep_resident else self.engine.index_compact()
+        if self._lexical is not None:
+            if keep_resident and self._lexical.n_docs == len(row_map):
+                self._lexical.compacted(row_map)
+            elif (row_map < 0).any():
+                self._lexical = None                                 # stale on the device: nothing to mirror until load_lexical
         keep = np.nonzero(row_map >= 0)[0]
         if isinstance(self.rows, list):
             self.rows = [self.rows[int(i)] for i in keep]
@@ -297,6 +376,7 @@ class GpuDocumentIndex:
         if postings.n_docs != len(self.rows):
             raise ValueError(f"load_lexical: postings of {postings.n_docs} documents for an index of {len(self.rows)} rows")
         postings.load(self.engine)
+        self._lexical = postings                       # the mirror grows and shrinks with add_rows(lexical_weights=...) / compact(keep_resident=True)
 
     def search_lexical(self, agent_id: str, query: str, top_k: int = 5, mode: str = "dense+sparse", pool: int = 100,
                        rrf_k: int = 60) -> List[Dict[str, Any]]:
@@ -354,10 +434,12 @@ class GpuDocumentIndex:
         self.engine.tokvec_load(vecs, off)
 
     @_locked
-    def build_token_vectors(self, texts, batch: int = 64) -> None:
+    def build_token_vectors(self, texts, batch: int = 64, *, headroom_docs: int = 0, headroom_rows: int = 0) -> None:
         """Compute the token vectors of the rows' texts (texts[i] belongs to row i) with the embedding service's token-vector head
         and append them to the resident store on the device, `batch` texts per forward: the vectors go from the forward's output
-        tensor into the store and never exist on the host."""
+        tensor into the store and never exist on the host. headroom_docs / headroom_rows reserve room for the documents later
+        add_rows(token_vectors=...) / add_texts calls append (a reservation does not grow; compact(keep_resident=True) returns the
+        rows of deleted documents to it)."""
         import torch
         svc = self.embeddings
         texts = [str(t) for t in texts]
@@ -370,7 +452,7 @@ class GpuDocumentIndex:
         batch = max(1, int(batch))
         batches = [svc.tokenize(texts[b:b + batch]) for b in range(0, len(texts), batch)]
         n_rows = [int((np.clip(lens, 1, ids.shape[1]).astype(np.int64) - 1).sum()) for ids, _, lens in batches]
-        self.engine.tokvec_reserve(len(texts), sum(n_rows), tok_dim)
+        self.engine.tokvec_reserve(len(texts) + max(0, int(headroom_docs)), sum(n_rows) + max(0, int(headroom_rows)), tok_dim)
         for (ids, tt, lens), rows in zip(batches, n_rows):
             tok = torch.empty((max(rows, 1), tok_dim), dtype=torch.float32, device="cuda")
             off = torch.empty((len(lens) + 1,), dtype=torch.int64, device="cuda")

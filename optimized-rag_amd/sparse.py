@@ -101,3 +101,66 @@ class LexicalPostings:
     def load(self, engine):
         engine.sparse_load(self.indptr, self.doc, self.weight, self.n_docs)
         return self
+
+    # ---- live writes: the counterparts of Bm25Postings.extend / append_to / compacted ---------------------------------------
+    def extend(self, maps_or_postings, n_terms=None):
+        """Add documents after the existing ones: a list of {token id: weight} maps, or a LexicalPostings of the new documents
+        alone (document numbers relative to the block). The mirror becomes what `from_weights(old maps + new maps)` builds over
+        the grown vocabulary - every term's old list, then its new postings. n_terms: the vocabulary after the block (default:
+        the larger of the mirror's and the block's); it may not shrink. Returns the relative block `append_to` /
+        `RagEngine.sparse_append` takes."""
+        block = maps_or_postings
+        if not isinstance(block, LexicalPostings):
+            block = LexicalPostings.from_weights(block, n_terms)
+        V_old, nb = self.n_terms, block.n_docs
+        V = max(V_old, block.n_terms) if n_terms is None else int(n_terms)
+        if V < V_old or V < block.n_terms:
+            raise ValueError(f"extend: n_terms may not shrink ({V} < {max(V_old, block.n_terms)})")
+        odf = np.zeros(V, dtype=np.int64)
+        odf[:V_old] = np.diff(self.indptr)
+        bdf = np.zeros(V, dtype=np.int64)
+        bdf[:block.n_terms] = np.diff(block.indptr)
+        bptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(bdf, out=bptr[1:])
+        indptr = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(odf + bdf, out=indptr[1:])
+        nnz_o, nnz_b = self.nnz, block.nnz
+        oterm = np.repeat(np.arange(V, dtype=np.int64), odf)
+        bterm = np.repeat(np.arange(V, dtype=np.int64), bdf)
+        opos = indptr[oterm] + (np.arange(nnz_o, dtype=np.int64) - self.indptr[oterm]) if nnz_o else np.zeros(0, dtype=np.int64)
+        bpos = indptr[bterm] + odf[bterm] + (np.arange(nnz_b, dtype=np.int64) - bptr[bterm])
+        doc = np.empty(nnz_o + nnz_b, dtype=np.int32)
+        weight = np.empty(nnz_o + nnz_b, dtype=np.float32)
+        doc[opos], weight[opos] = self.doc, self.weight
+        doc[bpos], weight[bpos] = block.doc + np.int32(self._n_docs), block.weight
+        self.indptr, self.doc, self.weight = indptr, doc, weight
+        self._n_docs += nb
+        return {"indptr": bptr, "doc": block.doc, "weight": block.weight, "n_docs": nb, "n_terms_total": V}
+
+    def append_to(self, engine, block):
+        """Hand a block `extend` returned to the engine (after the rows themselves were inserted, or on a handle without a
+        dense index)."""
+        engine.sparse_append(block["indptr"], block["doc"], block["weight"], block["n_docs"], block["n_terms_total"])
+        return self
+
+    def compacted(self, row_map):
+        """The host mirror of `RagEngine.index_compact(keep_resident=True)` (rag_index_compact_live), in place: row_map[old
+        document] = its new number, or < 0 for a document that was deleted. Drops the postings of the deleted documents and
+        renumbers the rest; term numbers stay (a term that loses every posting keeps its number, with an empty list). The live
+        entries of the map must be exactly 0 .. n_live-1 ascending; anything else, or a map of another length than `n_docs`,
+        raises ValueError. Returns self."""
+        row_map = np.asarray(row_map, dtype=np.int64)
+        if row_map.shape != (self.n_docs,):
+            raise ValueError(f"compacted: row_map must have one entry per document ({self.n_docs}), got shape {row_map.shape}")
+        live = row_map >= 0
+        n_live = int(live.sum())
+        if not np.array_equal(row_map[live], np.arange(n_live, dtype=np.int64)):
+            raise ValueError("compacted: the live entries of row_map must be 0 .. n_live-1 in ascending order")
+        keep = live[self.doc]
+        before = np.zeros(keep.shape[0] + 1, dtype=np.int64)      # survivors before each posting: the new offsets, read at the old
+        np.cumsum(keep, out=before[1:])
+        self.indptr = before[self.indptr]
+        self.doc = row_map[self.doc[keep]].astype(np.int32)
+        self.weight = np.ascontiguousarray(self.weight[keep])
+        self._n_docs = n_live
+        return self
