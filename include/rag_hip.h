@@ -810,6 +810,69 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
                             int k, int rrf_k, int tenant, int mode, int64_t* ids_out_dev, double* scores_out_dev,
                             int64_t* cand_out_dev /*may be NULL*/, void* stream);
 
+/* ---- the three-way bge-m3 score over resident data: dense + sparse + MaxSim for given rows (no reference counterpart). The
+ *      semantics are restated from FlagEmbedding's BGEM3FlagModel.compute_score, mode "colbert+sparse+dense" with its default
+ *      weights (0.4, 0.2, 0.4) = (dense, sparse, colbert); parity with upstream is NOT pinned by a test here, as for the three heads.
+ * rag_sparse_score_rows_dev / _host: the exact learned-sparse score of GIVEN rows - the point lookup the searches lack
+ *   (rag_sparse_topk_* reports a document only if it made the list). Queries are CSR as in rag_sparse_topk_* (term_ptr [Q + 1],
+ *   terms, qweights); cand_rows [Q][pool] int32; scores_out [Q][pool] float64. scores_out[q][j] is BIT-IDENTICAL to
+ *   rag_sparse_scores_host(...)[q][cand_rows[q][j]] for a row that is not hidden: the float64 sum of (double)qw * (double)w over the
+ *   query's tokens in their order, on the lists that hold the row. Token rules as above: a term < 0 or >= n_terms adds nothing, a
+ *   weight not > 0 (NaN included) adds nothing, a repeated term adds twice. A slot with cand < 0 or cand >= the covered documents
+ *   scores 0.0. Explicit rows: visibility (deletes, tenants) is not looked at, as in rag_tokvec_rerank_dev. 1 <= n_queries <= 65535,
+ *   0 < pool <= 256, else RAG_ERR_ARG; RAG_ERR_STATE when the postings are stale or none are loaded. With appended postings a row
+ *   below the base's documents is looked up in the base, any other row in the tail (its own metadata, tables and vocabulary: a term
+ *   may be known to the tail only); a row lives in one segment, so the bit-identity with a fresh load of the merged CSR is the
+ *   argument made for the searches. One workgroup per query; every (slot, token) lookup is one table read, a few binary steps, two
+ *   16-byte loads and a weight load; only the sum is ordered. A score is a function of its query and row: the same bits at any
+ *   pool, in any neighbourhood, from run to run.
+ * rag_m3_score_rows_dev: for each query and each of its `pool` candidate rows cand_rows [Q][pool] int32, three components widened
+ *   to float64:
+ *     dense   = the float64 cosine of q_emb [Q][dim index] against the fp32 master row - the function the dense search's
+ *               rescoring uses: the bits rag_dense_topk_* reports for that (query, row)
+ *     sparse  = rag_sparse_score_rows_dev
+ *     colbert = the float32 pair score of rag_tokvec_rerank_dev (its pair_scores_out); 0.0 for a document or a query without
+ *               token vectors
+ *   and  score = ((w_colbert * colbert + w_sparse * sparse) + w_dense * dense) / ((w_dense + w_sparse) + w_colbert)  in exactly
+ *   this association, without fused multiply-add (Python's evaluation of the upstream formula). Then the top k by score
+ *   descending, equal scores in candidate order. A slot is empty iff cand < 0 or cand >= the index rows; every other slot is
+ *   ranked, whatever its score. Outputs: ids_out [Q][k] int64 (the index's id mapping), rows_out [Q][k] int32 (may be NULL),
+ *   scores_out [Q][k] float64, components_out [Q][k][3] float64 in the order (dense, sparse, colbert) (may be NULL); padding
+ *   -1 / -1 / 0.0 / 0.0. Weights: finite, each >= 0, sum > 0, else RAG_ERR_ARG. A weight of exactly 0 means its component is not
+ *   computed, is reported as 0.0, and neither its query arrays nor its resident structure are required: w_colbert = 0 is upstream's
+ *   "sparse+dense" with the same bits (0 * c and x + 0 are exact) and needs no token-vector store; w_sparse = 0 needs no sparse
+ *   postings. Limits: 1 <= n_queries <= 65535, 0 < k <= pool <= 256, n_queries * pool < 2^24. A required structure that is
+ *   missing, stale or does not cover exactly the index's rows: RAG_ERR_STATE (sparse postings of another row count: RAG_ERR_ARG,
+ *   as in rag_hybrid_sparse_rrf_dev). q_emb and q_vecs 16-byte aligned. Explicit rows: visibility is not looked at.
+ * rag_retrieve_m3_dev: candidates, then rag_m3_score_rows_dev, in one device-resident call. mode 0: the dense top-`pool`;
+ *   mode 1: the top-`pool` of dense + learned-sparse RRF (both as rag_retrieve_maxsim_dev); mode 2: the UNION of the dense
+ *   top-`pool` and the sparse top-`pool` - what rag_rrf_fuse_dev over the two lists returns at top_k = 2 * pool, in RRF order,
+ *   -1 padded - so 2 * pool candidate slots and pool <= 128. Tenant and deleted rows are filtered by the searches. ids_out /
+ *   scores_out [Q][k], components_out [Q][k][3] (may be NULL), cand_out [Q][slots] int64 (may be NULL) the candidate ids, slots =
+ *   pool or 2 * pool. 0 < k <= pool. Modes 1 and 2 need the query's terms and fresh, row-aligned sparse postings whatever
+ *   w_sparse is. Bit-identical to the search entries (rag_dense_topk_dev; rag_hybrid_sparse_rrf_dev at k = pool; rag_dense_topk_dev
+ *   + rag_sparse_topk_dev + rag_rrf_fuse_dev at top_k = 2 * pool) followed by rag_m3_score_rows_dev on their rows. Workspaces
+ *   are handle-owned and grown as the preamble says. After the candidate stage and the MaxSim launch: three launches (cosines,
+ *   point lookups, combine + select).
+ * Live writes: the rules of the sparse postings and of the token-vector store hold for the components that use them;
+ *   rag_sparse_append_host / rag_tokvec_append_* after inserts and rag_index_compact_live keep all three current.
+ * Ordering: rag_sparse_score_rows_host is a host call; the _dev calls follow the preamble.
+ * Sharding: raw scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev. */
+int rag_sparse_score_rows_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                              const int32_t* cand_rows_dev, int n_queries, int pool, double* scores_out_dev, void* stream);
+int rag_sparse_score_rows_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
+                               const int32_t* cand_rows_host, int n_queries, int pool, double* scores_out_host);
+int rag_m3_score_rows_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                          const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev,
+                          int n_queries, int pool, int k, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
+                          int32_t* rows_out_dev /*may be NULL*/, double* scores_out_dev, double* components_out_dev /*may be NULL*/,
+                          void* stream);
+int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                        const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool, int k,
+                        int rrf_k, int tenant, int mode, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
+                        double* scores_out_dev, double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/,
+                        void* stream);
+
 /* ---- agents mixed in one batch: a tenant PER QUERY. Each entry takes the arguments of its namesake with
  *      `const int32_t* tenants_host` [n_queries] where the namesake has `int tenant`: query i is filtered by tenants_host[i],
  *      a value < 0 leaves that query unfiltered. The result of query i is bit-identical to what the namesake returns for that

@@ -165,6 +165,12 @@ _SIGS = {
     "rag_tokvec_rerank_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "rag_tokvec_rerank_host": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_retrieve_maxsim_dev": ([_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
+    "rag_sparse_score_rows_dev": ([_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
+    "rag_sparse_score_rows_host": ([_P, _P, _P, _P, _P, C.c_int, C.c_int, _P], C.c_int),
+    "rag_m3_score_rows_dev": ([_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                               _P], C.c_int),
+    "rag_retrieve_m3_dev": ([_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                             C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "rag_model_seq_limit": ([_P, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
@@ -1126,6 +1132,67 @@ class RagEngine:
                                                      int(k), int(rrf_k), int(tenant), mode, p(ids), p(sc), p(cand), st),
                     "rag_retrieve_maxsim_dev")
         return ids, sc, cand
+
+    # ---- the three-way bge-m3 score over resident data (rag_sparse_score_rows_*, rag_m3_score_rows_dev, rag_retrieve_m3_dev) ----
+    def sparse_score_rows(self, term_ptr, terms, weights, cand_rows):
+        """The exact learned-sparse score of given rows: weighted queries (CSR as sparse_topk) and int32 rows [Q, pool] -> float64
+        [Q, pool], the bits of sparse_scores(...)[q][row]; 0.0 for a slot < 0 or past the covered documents."""
+        term_ptr, terms, weights = _np(term_ptr, np.int32), _np(terms, np.int32), _np(weights, np.float32)
+        cand = _np(cand_rows, np.int32)
+        if cand.ndim != 2 or term_ptr.shape != (cand.shape[0] + 1,):
+            raise RagError("sparse_score_rows: expected term_ptr [Q + 1] and candidate rows [Q, pool]")
+        Q, pool = cand.shape
+        out = np.empty((Q, pool), dtype=np.float64)
+        self._check(self.lib.rag_sparse_score_rows_host(self.h, _ptr(term_ptr), _ptr(terms), _ptr(weights), _ptr(cand), Q, pool, _ptr(out)),
+                    "rag_sparse_score_rows_host")
+        return out
+
+    def sparse_score_rows_dev(self, term_ptr, terms, weights, cand_rows, scores_out, stream=None):
+        """The same on CUDA tensors (int32 term arrays and rows, float32 weights, float64 scores_out [Q, pool]); asynchronous on `stream`."""
+        import torch
+        Q, pool = cand_rows.shape
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_sparse_score_rows_dev(self.h, p(term_ptr), p(terms), p(weights), p(cand_rows), int(Q), int(pool), p(scores_out),
+                                                       st), "rag_sparse_score_rows_dev")
+
+    def m3_score_rows_dev(self, cand_rows, k, ids_out, scores_out, q_emb=None, term_ptr=None, terms=None, weights=None, q_vecs=None, q_off=None,
+                          w=(0.4, 0.2, 0.4), rows_out=None, components_out=None, stream=None):
+        """bge-m3's "colbert+sparse+dense" score of given rows (int32 [Q, pool], CUDA tensors throughout) and its top k: w = (dense,
+        sparse, colbert); a weight of 0 leaves its component - and its inputs - out. components_out [Q, k, 3] float64 = (dense,
+        sparse, colbert) of every returned row. Asynchronous on `stream`."""
+        import torch
+        Q, pool = cand_rows.shape
+        if q_vecs is not None and float(w[2]) > 0:
+            self._tokvec_rerank_check(tuple(q_vecs.shape), None, "m3_score_rows_dev")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_m3_score_rows_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), p(cand_rows), int(Q),
+                                                   int(pool), int(k), float(w[0]), float(w[1]), float(w[2]), p(ids_out), p(rows_out),
+                                                   p(scores_out), p(components_out), st), "rag_m3_score_rows_dev")
+
+    def retrieve_m3_dev(self, q_emb, pool, k, term_ptr=None, terms=None, weights=None, q_vecs=None, q_off=None, mode=2, w=(0.4, 0.2, 0.4),
+                        rrf_k=60, tenant=-1, stream=None):
+        """Candidates -> three-way score -> top-k in one device-resident call (CUDA tensors). mode 0: dense top-pool; 1: dense +
+        learned-sparse RRF top-pool; 2: the union of the dense and the sparse top-pool (2 * pool slots, pool <= 128). Returns (ids
+        [Q, k] int64, scores [Q, k] float64, components [Q, k, 3] float64 = (dense, sparse, colbert), candidates [Q, slots] int64)."""
+        import torch
+        Q, dev = q_emb.shape[0], q_emb.device
+        slots = 2 * int(pool) if int(mode) == 2 else int(pool)
+        key = ("m3", Q, slots, k)
+        if getattr(self, "_m3_key", None) != key:
+            self._m3 = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float64, device=dev),
+                        torch.empty((Q, k, 3), dtype=torch.float64, device=dev), torch.empty((Q, slots), dtype=torch.int64, device=dev))
+            self._m3_key = key
+        ids, sc, comp, cand = self._m3
+        if q_vecs is not None and float(w[2]) > 0:
+            self._tokvec_rerank_check(tuple(q_vecs.shape), None, "retrieve_m3_dev")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_retrieve_m3_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
+                                                 int(k), int(rrf_k), int(tenant), int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids),
+                                                 p(sc), p(comp), p(cand), st), "rag_retrieve_m3_dev")
+        return ids, sc, comp, cand
 
     def tokens_load(self, tokens, lens, id_bits=16):
         """Passage token store: tokens [N, L] int32 token ids without [CLS]/[SEP], lens [N]; row-aligned with the index.

@@ -1215,4 +1215,42 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
                                ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream);
 }
 
+int rag_sparse_score_rows_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                              const int32_t* cand_rows_dev, int n_queries, int pool, double* scores_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return sparse_score_rows_dev(h, term_ptr_dev, terms_dev, qweights_dev, cand_rows_dev, n_queries, pool, scores_out_dev, (hipStream_t)stream);
+}
+
+int rag_sparse_score_rows_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
+                               const int32_t* cand_rows_host, int n_queries, int pool, double* scores_out_host) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_score_rows_host(h, term_ptr_host, terms_host, qweights_host, cand_rows_host, n_queries, pool, scores_out_host);
+}
+
+int rag_m3_score_rows_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                          const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev,
+                          int n_queries, int pool, int k, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
+                          int32_t* rows_out_dev, double* scores_out_dev, double* components_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return m3_score_rows_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cand_rows_dev, n_queries, pool, k, w_dense,
+                             w_sparse, w_colbert, ids_out_dev, rows_out_dev, scores_out_dev, components_out_dev, (hipStream_t)stream);
+}
+
+int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                        const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool, int k,
+                        int rrf_k, int tenant, int mode, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
+                        double* scores_out_dev, double* components_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return retrieve_m3_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, n_queries, pool, k, rrf_k, tenant, mode,
+                           w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream);
+}
+
 }  // extern "C"

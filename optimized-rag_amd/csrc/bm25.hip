@@ -2739,3 +2739,128 @@ int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* term
     h->sparse->call_qw = qweights_dev;
     return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, {nullptr, nullptr});
 }
+
+// ---- point lookup: the exact learned-sparse score of GIVEN rows (rag_sparse_score_rows_*; the sparse component of rag_m3_score_rows_dev)
+// The range kernel scores whole 2048-document ranges and the top-k reports a document only if it made the list; a weighted sum
+// over candidates another leg found needs s(q, row) for an arbitrary row. One 256-thread workgroup per query. The query's tokens
+// are staged in LDS in chunks of at most 256: the term's bm_term_meta in the base and in the tail (df = 0: the segment does not
+// know the term, or the token adds nothing) and the float32 weight widened to float64. Wave w takes the slots w, w + 4, ...;
+// inside a wave lane = token: bm_bracket at the row, bm_search, one compare of the found doc id, one weight load - every lookup
+// of a slot is independent of the others. Only the sum is ordered: a lane that finds nothing holds +0.0, and the wave adds the
+// lanes' products in lane order = token order into the slot's accumulator (kept in a register of lane `slot / 4` across the 64-token
+// groups and the LDS chunks). Adding +0.0 to a non-negative float64 changes nothing, so the sum is the range kernel's - which adds
+// exactly the postings that exist, in token order - bit for bit. A row lives in one segment (base: row < n_docs, tail: local
+// document row - row0), as its accumulator does in the searches. No atomics, no LDS accumulators, no plan table.
+struct bm_point_seg { const bm_term_meta* meta; const int32_t* doc; const float* wf; const int32_t* range_tab; int64_t n_terms; };
+#define BM_POINT_CHUNK 256
+
+__device__ __forceinline__ double bm_readlane_f64(double v, int i) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, i), hi = (uint32_t)__builtin_amdgcn_readlane((int)(u >> 32), i);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+__global__ __launch_bounds__(256) void sparse_point_kernel(const bm_point_seg sb, const bm_point_seg stl, int64_t base_docs, int64_t total_docs,
+                                                            int64_t tail_row0, const int32_t* __restrict__ term_ptr,
+                                                            const int32_t* __restrict__ terms, const float* __restrict__ qweights,
+                                                            const int32_t* __restrict__ cand, int pool, double* __restrict__ out) {
+    __shared__ bm_term_meta s_meta[2][BM_POINT_CHUNK];
+    __shared__ double s_qw[BM_POINT_CHUNK];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t0 = term_ptr[q], t1 = term_ptr[q + 1];
+    double acc = 0.0;                                          // lane l: the accumulator of slot wv + 4 l
+    for (int tb = t0; tb < t1; tb += BM_POINT_CHUNK) {
+        const int nb = min(BM_POINT_CHUNK, t1 - tb);
+        if (tb != t0) __syncthreads();                         // the previous chunk has been read by every wave
+        if (tid < nb) {
+            const int t = terms[tb + tid];
+            const float qw = qweights[tb + tid];
+            const bool live = qw > 0.0f;                       // a weight that is not > 0 (NaN included) adds nothing
+            const bm_term_meta none = {0, 0, 0.0, 0, BM_NO_TAB};
+            s_meta[0][tid] = live && t >= 0 && t < sb.n_terms ? sb.meta[t] : none;
+            s_meta[1][tid] = live && t >= 0 && t < stl.n_terms ? stl.meta[t] : none;
+            s_qw[tid] = live ? (double)qw : 0.0;
+        }
+        __syncthreads();
+        for (int s = 0; wv + 4 * s < pool; ++s) {
+            const int row = cand[(size_t)q * pool + wv + 4 * s];                                 // (wave-uniform)
+            if (row < 0 || row >= total_docs) continue;
+            const int seg = row >= base_docs ? 1 : 0;
+            const bm_point_seg& S = seg ? stl : sb;
+            const int64_t local = seg ? row - tail_row0 : (int64_t)row;
+            double a = __shfl(acc, s);
+            for (int c = 0; c < nb; c += 64) {
+                double prod = 0.0;
+                if (c + lane < nb) {
+                    const bm_term_meta m = s_meta[seg][c + lane];
+                    if (m.df > 0) {
+                        int lo, hi;
+                        bm_bracket(m, S.range_tab, local, lo, hi);
+                        const int p = bm_search(S.doc + m.post, lo, hi, local);
+                        if (p < m.df && S.doc[m.post + p] == local) prod = s_qw[c + lane] * (double)S.wf[m.post + p];
+                    }
+                }
+                uint64_t found = __ballot(prod != 0.0);
+                while (found) {                                // in lane order = token order
+                    const int i = __builtin_ctzll(found);
+                    a += bm_readlane_f64(prod, i);
+                    found &= found - 1;
+                }
+            }
+            if (lane == s) acc = a;
+        }
+    }
+    const int j = wv + 4 * lane;
+    if (j < pool) out[(size_t)q * pool + j] = acc;
+}
+
+static int sparse_point_usable(rag_ctx* h) {
+    if (!h->sparse) {
+        h->err = "sparse_score_rows: no sparse index loaded (rag_sparse_load_host)";
+        return RAG_ERR_STATE;
+    }
+    return bm25_check_fresh(h, h->sparse);
+}
+
+// scores_dev [Q][pool] float64 <- s(query q, row cand_rows_dev[q][j]); everything on the device, asynchronous on st
+int sparse_score_rows_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                          const int32_t* cand_rows_dev, int Q, int pool, double* scores_dev, hipStream_t st) {
+    if (int rc = sparse_point_usable(h)) return rc;
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K, "sparse_score_rows: 1 <= n_queries <= 65535, 0 < pool <= 256");
+    ARG_CHECK(h, term_ptr_dev && qweights_dev && cand_rows_dev && scores_dev, "sparse_score_rows: null argument");
+    const rag_bm25_index* ix = h->sparse;
+    const rag_bm25_index* tl = ix->tail.get();
+    const bm_point_seg sb = {ix->meta, ix->doc, ix->wf, ix->range_tab, ix->n_terms};
+    const bm_point_seg stl = tl ? bm_point_seg{tl->meta, tl->doc, tl->wf, tl->range_tab, tl->n_terms} : bm_point_seg{nullptr, nullptr, nullptr, nullptr, 0};
+    launch(sparse_point_kernel, dim3((unsigned)Q), dim3(256), 0, st, sb, stl, ix->n_docs, tl ? bm_total_docs(ix) : ix->n_docs, tl ? tl->row0 : (int64_t)0,
+           term_ptr_dev, terms_dev, qweights_dev, cand_rows_dev, pool, scores_dev);
+    return launch_status(h);
+}
+
+int sparse_score_rows_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, const int32_t* cand_rows, int Q,
+                           int pool, double* scores_out) {
+    if (int rc = sparse_point_usable(h)) return rc;
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K, "sparse_score_rows: 1 <= n_queries <= 65535, 0 < pool <= 256");
+    ARG_CHECK(h, term_ptr && cand_rows && scores_out, "sparse_score_rows: null argument");
+    ARG_CHECK(h, term_ptr[0] >= 0, "sparse_score_rows: term_ptr must start at >= 0 and never decrease");
+    for (int q = 0; q < Q; ++q) ARG_CHECK(h, term_ptr[q + 1] >= term_ptr[q], "sparse_score_rows: term_ptr must start at >= 0 and never decrease");
+    const size_t nt = (size_t)term_ptr[Q], P = (size_t)Q * pool;
+    ARG_CHECK(h, nt == 0 || (terms && qweights), "sparse_score_rows: null query arrays");
+    hipStream_t st = h->stream;
+    dev_buf<int32_t> dtp, dtm, dcand;
+    dev_buf<float> dqw;
+    dev_buf<double> dsc;
+    int rc;
+    if ((rc = dtp.alloc(h, (size_t)Q + 1)) || (rc = dtm.alloc(h, std::max<size_t>(nt, 1))) || (rc = dqw.alloc(h, std::max<size_t>(nt, 1))) ||
+        (rc = dcand.alloc(h, P)) || (rc = dsc.alloc(h, P)))
+        return rc;
+    HIP_TRY(h, hipMemcpyAsync(dtp, term_ptr, ((size_t)Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (nt) HIP_TRY(h, hipMemcpyAsync(dtm, terms, nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (nt) HIP_TRY(h, hipMemcpyAsync(dqw, qweights, nt * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dcand, cand_rows, P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    rc = sparse_score_rows_dev(h, dtp, dtm, dqw, dcand, Q, pool, dsc, st);
+    if (!rc) HIP_TRY(h, hipMemcpyAsync(scores_out, dsc, P * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return rc;
+}

@@ -489,3 +489,20 @@ int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, co
                        int32_t* rows_out, double* scores_out, float* pair_scores_out);
 int tokvec_topk(rag_ctx* h, const float* scores_dev, const int32_t* slot_rows_dev, int Q, int pool, int k, int64_t* ids_out, int32_t* rows_out,
                 double* scores_out, hipStream_t st);
+int tokvec_score_slots(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, const float** scores_out,
+                       const int32_t** slots_out, hipStream_t st);
+// the three-way bge-m3 score over resident data (pipeline.hip; rag_m3_score_rows_dev, rag_retrieve_m3_dev) and its components:
+// the float64 cosine of given rows (dense.hip) and the learned-sparse point lookup (bm25.hip)
+int dense_cosine_rows(rag_ctx* h, const float* q_dev, const int32_t* cand_rows_dev, int Q, int pool, double* out_dev, hipStream_t st);
+int sparse_score_rows_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                          const int32_t* cand_rows_dev, int Q, int pool, double* scores_dev, hipStream_t st);
+int sparse_score_rows_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, const int32_t* cand_rows, int Q,
+                           int pool, double* scores_out);
+int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                      const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev, int Q, int pool, int k, double w_dense,
+                      double w_sparse, double w_colbert, int64_t* ids_out, int32_t* rows_out, double* scores_out, double* components_out,
+                      hipStream_t st);
+int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                    const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
+                    double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
+                    hipStream_t st);

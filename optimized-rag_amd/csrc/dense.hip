@@ -1407,6 +1407,30 @@ int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, i
     return launch_status(h);
 }
 
+// float64 cosine of GIVEN rows (rag_m3_score_rows_dev, pipeline.hip): out[q][j] = what rescore_kernel computes for (query q, row
+// cand[q][j]) - exact_norm2_wave + exact_cosine_wave<true>, so the bits are those the dense search reports for that pair. One wave
+// per slot; a slot with cand < 0 or cand >= n_rows gets 0.0. Row visibility is not looked at.
+__global__ __launch_bounds__(256) void cosine_rows_kernel(const float* __restrict__ q32, const float* __restrict__ emb32,
+                                                           const int32_t* __restrict__ cand, int64_t n_rows, int pool, int dim,
+                                                           double* __restrict__ out) {
+    const int q = blockIdx.y, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= pool) return;                                             // (wave-uniform)
+    const int row = cand[(size_t)q * pool + j];
+    double c = 0.0;
+    if (row >= 0 && row < n_rows) {
+        const double nq = exact_norm2_wave(q32 + (size_t)q * dim, dim, lane);
+        c = exact_cosine_wave<true>(q32 + (size_t)q * dim, emb32 + (size_t)row * dim, dim, lane, nq);
+    }
+    if (lane == 0) out[(size_t)q * pool + j] = c;
+}
+
+int dense_cosine_rows(rag_ctx* h, const float* q_dev, const int32_t* cand_rows_dev, int Q, int pool, double* out_dev, hipStream_t st) {
+    launch(cosine_rows_kernel, dim3((unsigned)((pool + 3) / 4), (unsigned)Q), dim3(256), 0, st, q_dev, h->emb32, cand_rows_dev, h->n_rows, pool,
+           h->dim, out_dev);
+    return launch_status(h);
+}
+
 // ------------------------------------------------------------------------------------------------
 // merge of per-shard partial lists (multi-GPU exchange step): [L][Q][k] -> [Q][k], score desc, id asc
 // ------------------------------------------------------------------------------------------------

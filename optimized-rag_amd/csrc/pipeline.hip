@@ -12,6 +12,8 @@
 //   4. rerank_topk_kernel: sigmoid in float64, stable order (score desc, candidate order on ties), top-k
 #include "common.h"
 
+#include <cmath>
+
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
 int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
@@ -468,4 +470,189 @@ int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
         }
     }
     return RAG_OK;
+}
+
+// ---- the three-way bge-m3 score over resident data (rag_m3_score_rows_dev, rag_retrieve_m3_dev): upstream's compute_score mode
+// "colbert+sparse+dense" for [Q][S] candidate rows, every component exact for every candidate:
+//   dense   = the float64 cosine of the query against the fp32 master row   (cosine_rows_kernel, dense.hip: the rescoring's function)
+//   sparse  = the float64 learned-sparse score of that row                  (sparse_point_kernel, bm25.hip)
+//   colbert = the float32 pair score of tokvec_maxsim_kernel, widened       (tokvec.hip)
+//   score   = ((w_colbert * colbert + w_sparse * sparse) + w_dense * dense) / ((w_dense + w_sparse) + w_colbert)
+// in exactly this association (the file is built with -ffp-contract=off: no fused multiply-add), then the stable top-k. A weight of 0
+// leaves its component out: not computed, reported as 0.0, its resident structure not required; 0 * 0.0 and x + 0.0 are exact,
+// so w_colbert = 0 gives the bits of the two-way "sparse+dense" formula.
+// One workgroup per query, S <= 256: rank by (score desc, slot asc) among the slots that hold a row of the index - whatever their
+// score. ids follow the index's mapping; cand_out (may be null) gets every slot's id, -1 for an empty slot.
+__global__ __launch_bounds__(256) void m3_combine_topk_kernel(const int32_t* __restrict__ rows, const double* __restrict__ dense,
+                                                               const double* __restrict__ sparse, const float* __restrict__ colbert, int S, int k,
+                                                               double wd, double ws, double wc, const int64_t* __restrict__ idmap,
+                                                               int64_t n_index, int64_t id_base, int64_t* __restrict__ ids_out,
+                                                               int32_t* __restrict__ rows_out, double* __restrict__ scores_out,
+                                                               double* __restrict__ comp_out, int64_t* __restrict__ cand_out) {
+    __shared__ double s[256];
+    __shared__ int ok[256];
+    const int q = blockIdx.x, j = threadIdx.x;
+    double d = 0.0, sp = 0.0, c = 0.0, mine = 0.0;
+    int valid = 0, row = -1;
+    int64_t id = -1;
+    if (j < S) {
+        const size_t at = (size_t)q * S + j;
+        row = rows[at];
+        valid = row >= 0 && row < n_index;
+        if (valid) {
+            if (dense) d = dense[at];
+            if (sparse) sp = sparse[at];
+            if (colbert) c = (double)colbert[at];
+            mine = ((wc * c + ws * sp) + wd * d) / ((wd + ws) + wc);
+            id = idmap != nullptr ? idmap[row] : id_base + row;
+        }
+        if (cand_out) cand_out[at] = id;
+    }
+    s[j] = mine;
+    ok[j] = valid;
+    for (int i = j; i < k; i += 256) {
+        const size_t o = (size_t)q * k + i;
+        ids_out[o] = -1;
+        scores_out[o] = 0.0;
+        if (rows_out) rows_out[o] = -1;
+        if (comp_out) comp_out[o * 3] = comp_out[o * 3 + 1] = comp_out[o * 3 + 2] = 0.0;
+    }
+    __syncthreads();
+    if (valid) {
+        int rank = 0;
+        for (int i = 0; i < S; ++i) rank += ok[i] && (s[i] > mine || (s[i] == mine && i < j));
+        if (rank < k) {
+            const size_t o = (size_t)q * k + rank;
+            ids_out[o] = id;
+            scores_out[o] = mine;
+            if (rows_out) rows_out[o] = row;
+            if (comp_out) {
+                comp_out[o * 3] = d;
+                comp_out[o * 3 + 1] = sp;
+                comp_out[o * 3 + 2] = c;
+            }
+        }
+    }
+}
+
+struct m3_weights { double dense, sparse, colbert; };
+
+// what both entries check: the weights, and the resident structures the non-zero ones need, aligned with the index's rows
+static int m3_check(rag_ctx* h, const char* who, m3_weights w, const float* q_emb, const int32_t* term_ptr, const float* qweights,
+                    const float* q_vecs, const int64_t* q_off) {
+    const std::string me(who);
+    ARG_CHECK(h, std::isfinite(w.dense) && std::isfinite(w.sparse) && std::isfinite(w.colbert) && w.dense >= 0.0 && w.sparse >= 0.0 &&
+                     w.colbert >= 0.0 && std::isfinite((w.dense + w.sparse) + w.colbert) && (w.dense + w.sparse) + w.colbert > 0.0,
+              (me + ": the weights must be finite, each >= 0, with a sum > 0").c_str());
+    ARG_CHECK(h, h->index_loaded, (me + ": no index loaded").c_str());
+    ARG_CHECK(h, w.dense == 0.0 || (q_emb != nullptr && (reinterpret_cast<uintptr_t>(q_emb) & 15) == 0),
+              (me + ": a dense weight needs the query embeddings, 16-byte aligned").c_str());
+    if (w.sparse > 0.0) {
+        if (sparse_n_docs(h) < 0) {
+            h->err = me + ": no sparse index loaded (rag_sparse_load_host)";
+            return RAG_ERR_STATE;
+        }
+        if (int rc = sparse_fresh(h)) return rc;
+        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, (me + ": the sparse postings must be row-aligned with the index (same number of documents)").c_str());
+        ARG_CHECK(h, term_ptr && qweights, (me + ": a sparse weight needs the query's terms and weights").c_str());
+    }
+    if (w.colbert > 0.0) {
+        if (int rc = tokvec_usable(h, who)) return rc;
+        if (h->tv_docs != h->n_rows) {
+            h->err = me + ": the token-vector store does not hold exactly the index's rows (append the vectors of the inserted rows)";
+            return RAG_ERR_STATE;
+        }
+        ARG_CHECK(h, q_vecs && q_off && (reinterpret_cast<uintptr_t>(q_vecs) & 15) == 0,
+                  (me + ": a colbert weight needs the query's token vectors, 16-byte aligned, and their offsets").c_str());
+    }
+    return RAG_OK;
+}
+
+// the components of [Q][S] slots and the top-k: the MaxSim launch, then three more (cosines, point lookups, combine + select).
+// dn / sp: float64 workspaces [Q][S] of the caller.
+static int m3_score_slots(rag_ctx* h, m3_weights w, const float* q_emb, const int32_t* term_ptr, const int32_t* terms, const float* qweights,
+                          const float* q_vecs, const int64_t* q_off, const int32_t* rows, int Q, int S, int k, double* dn, double* sp,
+                          int64_t* ids_out, int32_t* rows_out, double* scores_out, double* comp_out, int64_t* cand_out, hipStream_t st) {
+    int rc;
+    const float* cb = nullptr;
+    if (w.colbert > 0.0 && (rc = tokvec_score_slots(h, q_vecs, q_off, rows, Q, S, &cb, nullptr, st))) return rc;
+    if (w.dense > 0.0 && (rc = dense_cosine_rows(h, q_emb, rows, Q, S, dn, st))) return rc;
+    if (w.sparse > 0.0 && (rc = sparse_score_rows_dev(h, term_ptr, terms, qweights, rows, Q, S, sp, st))) return rc;
+    launch(m3_combine_topk_kernel, dim3((unsigned)Q), dim3(256), 0, st, rows, w.dense > 0.0 ? dn : nullptr, w.sparse > 0.0 ? sp : nullptr, cb, S, k,
+           w.dense, w.sparse, w.colbert, h->ids.get(), h->n_rows, h->id_base, ids_out, rows_out, scores_out, comp_out, cand_out);
+    return launch_status(h);
+}
+
+int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                      const float* q_vecs_dev, const int64_t* q_off_dev, const int32_t* cand_rows_dev, int Q, int pool, int k, double w_dense,
+                      double w_sparse, double w_colbert, int64_t* ids_out, int32_t* rows_out, double* scores_out, double* components_out,
+                      hipStream_t st) {
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "m3_score_rows: 1 <= n_queries <= 65535, 0 < k <= pool <= 256");
+    ARG_CHECK(h, (int64_t)Q * pool < ((int64_t)1 << 24), "m3_score_rows: n_queries * pool must be below 2^24");
+    ARG_CHECK(h, cand_rows_dev && ids_out && scores_out, "m3_score_rows: null argument");
+    const m3_weights w = {w_dense, w_sparse, w_colbert};
+    if (int rc = m3_check(h, "m3_score_rows", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
+    const size_t P = (size_t)Q * pool;
+    if (int rc = h->pipe_ws.reserve(h, P * 16 + 256)) return rc;       // workspace: dense [Q][pool] f64 | sparse [Q][pool] f64
+    double* dn = reinterpret_cast<double*>(h->pipe_ws.get());
+    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cand_rows_dev, Q, pool, k, dn, dn + P, ids_out,
+                          rows_out, scores_out, components_out, nullptr, st);
+}
+
+// candidates, then the three-way score, in one device-resident call. mode 0 / 1: the candidates of retrieve_maxsim_dev; mode 2: the
+// UNION of the dense top-pool and the sparse top-pool = what rrf_fuse_dev over the two lists returns at top_k = 2 * pool (RRF order,
+// -1 padded): 2 * pool slots. The candidate stage runs in row space as in retrieve_maxsim_dev; the combine kernel maps the ids.
+int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                    const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
+                    double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
+                    hipStream_t st) {
+    ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "retrieve_m3: mode is 0 (dense), 1 (dense + sparse RRF) or 2 (union of dense and sparse)");
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= (mode == 2 ? RAG_MAX_K / 2 : RAG_MAX_K) && k > 0 && k <= pool,
+              "retrieve_m3: 1 <= n_queries <= 65535, 0 < k <= pool <= 256 (mode 2: pool <= 128)");
+    const int S = mode == 2 ? 2 * pool : pool;
+    ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "retrieve_m3: n_queries * candidate slots must be below 2^24");
+    ARG_CHECK(h, q_emb_dev && ids_out && scores_out, "retrieve_m3: null argument");
+    const m3_weights w = {w_dense, w_sparse, w_colbert};
+    if (int rc = m3_check(h, "retrieve_m3", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
+    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_m3: tenant filter requested but no tenants loaded");
+    if (mode != 0) {
+        ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_m3: modes 1 and 2 need the query's terms and weights");
+        if (sparse_n_docs(h) < 0) {
+            h->err = "retrieve_m3: no sparse index loaded (rag_sparse_load_host)";
+            return RAG_ERR_STATE;
+        }
+        if (int rc = sparse_fresh(h)) return rc;
+        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "retrieve_m3: the sparse postings must be row-aligned with the index (same number of documents)");
+    }
+    const size_t P = (size_t)Q * pool, PS = (size_t)Q * S;
+    // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][S] i64 | rrf [Q][S] f64 | ranks [Q][S][2] i32 | dense [Q][S] f64
+    //            | sparse [Q][S] f64 | rows [Q][S] i32
+    const size_t need = P * (16 + 8) + PS * (8 + 8 + 8 + 8 + 8 + 4) + 256;
+    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
+    char* p = h->pipe_ws;
+    int64_t* lists = (int64_t*)p;              p += P * 16;
+    double* sc = (double*)p;                   p += P * 8;
+    int64_t* cand = (int64_t*)p;               p += PS * 8;
+    double* rrf = (double*)p;                  p += PS * 8;
+    int32_t* ranks = (int32_t*)p;              p += PS * 8;
+    double* dn = (double*)p;                   p += PS * 8;
+    double* sp = (double*)p;                   p += PS * 8;
+    int32_t* rows = (int32_t*)p;
+    dev_buf<int64_t> ids_saved = std::move(h->ids);
+    const int64_t id_base_saved = h->id_base;
+    h->id_base = 0;
+    int rc;
+    if (mode == 0) {
+        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st);
+    } else {
+        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, {nullptr, nullptr}, qweights_dev);
+        if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, S, cand, rrf, ranks, st);
+    }
+    h->ids = std::move(ids_saved);
+    h->id_base = id_base_saved;
+    if (rc) return rc;
+    launch(rows_narrow_kernel, dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st, cand, rows, (int64_t)PS);
+    if ((rc = launch_status(h))) return rc;
+    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, rows, Q, S, k, dn, sp, ids_out, nullptr,
+                          scores_out, components_out, cand_out, st);
 }

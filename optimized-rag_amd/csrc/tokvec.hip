@@ -410,6 +410,21 @@ int tokvec_usable(rag_ctx* h, const char* who) {
     return RAG_OK;
 }
 
+// the MaxSim launch alone over [Q][pool] slots (the caller has checked the store and the shape): *scores_out / *slots_out point into
+// the handle's tv_ws - every slot's float32 score, and the row it was scored for or -1
+int tokvec_score_slots(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, const float** scores_out,
+                       const int32_t** slots_out, hipStream_t st) {
+    const size_t P = (size_t)Q * pool;
+    if (int rc = h->tv_ws.reserve(h, stage_size(P, 4) * 2)) return rc;
+    float* sc = reinterpret_cast<float*>(h->tv_ws.get());
+    int32_t* slot = reinterpret_cast<int32_t*>(h->tv_ws.get() + stage_size(P, 4));
+    launch(tokvec_maxsim_kernel, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), h->tv_docs, cand_rows, pool,
+           h->tv_dim, sc, slot);
+    *scores_out = sc;
+    if (slots_out) *slots_out = slot;
+    return launch_status(h);
+}
+
 int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
                   int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st) {
     if (int rc = tokvec_usable(h, "tokvec_rerank")) return rc;
@@ -419,12 +434,9 @@ int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const i
     ARG_CHECK(h, q_vecs && q_off && cand_rows && ids_out && scores_out, "tokvec_rerank: null argument");
     ARG_CHECK(h, (reinterpret_cast<uintptr_t>(q_vecs) & 15) == 0, "tokvec_rerank: query vectors must be 16-byte aligned");
     const size_t P = (size_t)Q * pool;
-    if (int rc = h->tv_ws.reserve(h, stage_size(P, 4) * 2)) return rc;
-    float* sc = reinterpret_cast<float*>(h->tv_ws.get());
-    int32_t* slot = reinterpret_cast<int32_t*>(h->tv_ws.get() + stage_size(P, 4));
-    launch(tokvec_maxsim_kernel, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), h->tv_docs, cand_rows, pool,
-           h->tv_dim, sc, slot);
-    if (int rc = launch_status(h)) return rc;
+    const float* sc;
+    const int32_t* slot;
+    if (int rc = tokvec_score_slots(h, q_vecs, q_off, cand_rows, Q, pool, &sc, &slot, st)) return rc;
     if (pair_scores_out) HIP_TRY(h, hipMemcpyAsync(pair_scores_out, sc, P * sizeof(float), hipMemcpyDeviceToDevice, st));
     return tokvec_topk(h, sc, slot, Q, pool, k, ids_out, rows_out, scores_out, st);
 }

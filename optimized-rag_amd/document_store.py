@@ -506,6 +506,76 @@ class GpuDocumentIndex:
                         "score": float(s), "colbert_score": float(s), "metadata": row.get("metadata") or {}})
         return res
 
+    # ---- bge-m3's three-way score over the resident legs (rag_m3_score_rows_dev) --------------------------------------------
+    def search_m3(self, agent_id: str, query: str, top_k: int = 5, pool: int = 100, weights=(0.4, 0.2, 0.4),
+                  candidates: str = "union") -> List[Dict[str, Any]]:
+        """Rank by bge-m3's "colbert+sparse+dense" score: (w_colbert * colbert + w_sparse * sparse + w_dense * dense) / sum, weights =
+        (dense, sparse, colbert), every component exact for every candidate and computed from resident data - the fp32 rows, the
+        lexical postings (load_lexical), the token vectors (load_token_vectors / build_token_vectors). candidates "union": the dense
+        top-`pool` and the sparse top-`pool` together (pool <= 128); "dense": the dense top-`pool`; "dense+sparse": their reciprocal
+        rank fusion, top-`pool`. A weight of 0 leaves its component and its resident structure out. The query goes through ONE
+        encode_multi forward. Result dicts are `search`'s (without embeddings) plus `dense_score`, `sparse_score`, `colbert_score`
+        and `score`. Never raises: an error (a missing or stale leg, a missing head) is logged and answered with `search`."""
+        try:
+            if candidates not in ("union", "dense", "dense+sparse"):
+                raise ValueError(f"unknown candidates {candidates!r}")
+            w = tuple(float(x) for x in weights)
+            if len(w) != 3:
+                raise ValueError("weights are (dense, sparse, colbert)")
+            need_sparse = w[1] > 0 or candidates != "dense"
+            enc = self.embeddings.encode_multi([query], return_dense=True, return_sparse=need_sparse, return_colbert_vecs=w[2] > 0)
+            with self._lock:
+                return self._search_m3_locked(agent_id, enc, top_k, int(pool), w, candidates)
+        except Exception as e:
+            logger.error("Three-way search failed, answering with search: %s", e)
+            return self.search(agent_id, query, top_k, with_embeddings=False)
+
+    def _search_m3_locked(self, agent_id, enc, top_k, pool, w, candidates, rrf_k=60):
+        import torch
+        from .sparse import LexicalPostings
+        if agent_id is not None and str(agent_id) not in self._tenant_id:
+            return []
+        tenant = -1 if agent_id is None else self._tenant_id[str(agent_id)]
+        pool = max(1, min(128 if candidates == "union" else 256, max(pool, top_k)))
+        q = np.asarray(enc["dense_vecs"], dtype=np.float32).reshape(1, self.dim)
+        _, d_rows, _ = self.engine.dense_topk(q, pool, tenant=tenant)
+        cand = d_rows
+        ptr = terms = qw = None
+        if w[1] > 0 or candidates != "dense":
+            ptr, terms, qw = LexicalPostings.encode_queries(enc["lexical_weights"])
+        if candidates != "dense":
+            _, s_rows, _ = self.engine.sparse_topk(ptr, terms, qw, pool, tenant=tenant)
+            lists = np.stack([d_rows[0], s_rows[0]]).astype(np.int64)[None]                 # rows as keys: [1, 2, pool], -1 padded
+            cand, _, _ = self.engine.rrf_fuse(lists, rrf_k=rrf_k, top_k=2 * pool if candidates == "union" else pool)
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        k = min(int(top_k), cand.shape[1])
+        dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        qv = qo = None
+        if w[2] > 0:
+            v = np.ascontiguousarray(enc["colbert_vecs"][0], dtype=np.float32)
+            qv = torch.from_numpy(v if v.shape[0] else np.zeros((1, max(v.shape[1], 1)), np.float32)).cuda()
+            qo = dev(np.array([0, v.shape[0]], dtype=np.int64))
+        sparse_in = w[1] > 0
+        ids = torch.empty((1, k), dtype=torch.int64, device="cuda")
+        rows = torch.empty((1, k), dtype=torch.int32, device="cuda")
+        sc = torch.empty((1, k), dtype=torch.float64, device="cuda")
+        comp = torch.empty((1, k, 3), dtype=torch.float64, device="cuda")
+        t_ptr, t_terms, t_qw = (dev(ptr), dev(terms) if terms is not None and len(terms) else dev(np.zeros(1, np.int32)),
+                                dev(qw) if qw is not None and len(qw) else dev(np.zeros(1, np.float32))) if sparse_in else (None, None, None)
+        self.engine.m3_score_rows_dev(dev(cand), k, ids, sc, q_emb=dev(q), term_ptr=t_ptr, terms=t_terms, weights=t_qw, q_vecs=qv, q_off=qo,
+                                      w=w, rows_out=rows, components_out=comp)
+        torch.cuda.current_stream().synchronize()
+        rows, sc, comp = rows.cpu().numpy()[0], sc.cpu().numpy()[0], comp.cpu().numpy()[0]
+        res = []
+        for r, s, c in zip(rows, sc, comp):
+            if r < 0:
+                continue
+            row = self.rows[int(r)]
+            res.append({"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                        "score": float(s), "dense_score": float(c[0]), "sparse_score": float(c[1]), "colbert_score": float(c[2]),
+                        "metadata": row.get("metadata") or {}})
+        return res
+
     def search_many(self, agent_id: str, queries: List[str], top_k: int = 5, with_embeddings: bool = True) -> List[List[Dict[str, Any]]]:
         """Batched `search` (the reference agent can only submit one query per call, so nothing in
         its surface reaches the batched throughput): ONE embedding call for all queries when the service offers
