@@ -7,76 +7,6 @@
 #include <cstdlib>
 #include <cstring>
 
-// drivers implemented in other translation units
-int rrf_fuse_host(rag_ctx* h, const int64_t* lists, int Q, int L, int len, int rrf_k, int top_k, int64_t* keys_out,
-                  double* scores_out, int32_t* ranks_out);
-int linear_fuse_topk_host(rag_ctx* h, const double* sem, const double* kw, const double* tmp, int n, double a, double b,
-                          double g, int top_k, int32_t* idx_out, double* hyb_out);
-int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
-                   const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b);
-int bm25_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int tenant, int64_t* ids_out,
-                   int32_t* rows_out, double* scores_out, double* raw_max_out, query_tenants qt);
-int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
-                           const double* idf, int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b,
-                           const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
-int64_t bm25_n_docs(const rag_ctx* h);
-int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len,
-                     const double* idf_new, int64_t n_new, int64_t n_terms_total);
-int bm25_fold(rag_ctx* h);
-int bm25_live_counts_host(rag_ctx* h, int32_t* df_out, int64_t* n_docs_live_out, int64_t* sum_doc_len_out);
-int bm25_set_statistics_host(rag_ctx* h, const double* idf, double avgdl);
-int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_info* info_out);
-int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
-int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
-int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
-int ce_length_class(int d_head, int seq_len);
-int ce_model_seq_limit(const rag_ctx* h, int which);
-int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st,
-                    float* raw32_dev, int64_t ld, unsigned long long* max_key_dev, int tenant, query_tenants qt);
-int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out);
-int bm25_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
-int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
-int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
-                 int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
-void bm25_free(rag_ctx* h);
-void sparse_free(rag_ctx* h);
-int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_docs, int64_t n_terms);
-int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
-int64_t sparse_n_docs(const rag_ctx* h);
-int sparse_fresh(rag_ctx* h);
-int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_new, int64_t n_terms_total);
-int sparse_fold(rag_ctx* h);
-int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out);
-int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant,
-                     int64_t* ids_out, int32_t* rows_out, double* scores_out);
-int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out);
-int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
-                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st);
-int bm25_set_normalize(rag_ctx* h, int on);
-int chunk_chain_host(rag_ctx* h, const float* emb, const int32_t* sent_len, int n, int dim, double threshold, int max_chunk,
-                     int min_chunk, int32_t* group_out);
-int mmr_select_dev(rag_ctx* h, const float* queries_dev, const float* emb_dev, const int32_t* rows_dev, int Q, int n, int dim,
-                   int top_k, double lam, int variant, int32_t* sel_dev, double* score_dev, hipStream_t st);
-int mmr_select_host(rag_ctx* h, const float* query, const float* emb, int n, int dim, int top_k, double lam, int variant,
-                    int32_t* sel_out, double* score_out);
-int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev, int Q, int pool,
-                       int64_t token_id_base, int L_pair, int cls_id, int sep_id, int32_t* ids_out, int32_t* tt_out, int32_t* lens_out,
-                       hipStream_t st);
-int rerank_topk_dev(rag_ctx* h, const float* logits_dev, const int64_t* cand_dev, int Q, int pool, int k, int64_t* ids_out, double* scores_out,
-                    float* logits_out, hipStream_t st);
-int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L, int id_bits);
-int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits);
-int tokens_info(const rag_ctx* h, int64_t* rows_out, int* L_out, int* id_bits_out);
-int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, hipStream_t st);
-int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
-                        const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
-                        int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out, double* scores_out, float* logits_out,
-                        int64_t* cand_out, hipStream_t st, query_tenants qt);
-int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
-                        const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
-                        int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st);
-
 static thread_local std::string g_null_err = "null handle";
 
 // name -> member of rag_options; the environment default of option <name> is RAG_<NAME>
@@ -397,7 +327,7 @@ static int dense_topk_dev_entry(rag_handle_t h, const float* q_dev, int Q, int k
     DEV_ENTRY(h);
     entry_tenants t;
     if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
-    return dense_search(h, q_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream, t.qt);
+    return dense_search(h, q_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream, id_space::of_index(h), t.qt);
 }
 int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
                        double* scores_dev, void* stream) {
@@ -429,7 +359,7 @@ static int dense_topk_host_entry(rag_handle_t h, const float* q_host, int Q, int
     entry_tenants t;
     if ((rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t))) return rc;
     HIP_TRY(h, hipMemcpyAsync(qd, q_host, (size_t)Q * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-    rc = dense_search(h, qd, Q, k, t.tenant, ids_d, rows_d, sc_d, st, t.qt);
+    rc = dense_search(h, qd, Q, k, t.tenant, ids_d, rows_d, sc_d, st, id_space::of_index(h), t.qt);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(ids_out, ids_d, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, rows_d, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -625,7 +555,7 @@ int rag_bm25_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t
     LOCK(h);
     DEV_ENTRY(h);
     return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev,
-                         (hipStream_t)stream, {nullptr, nullptr});
+                         (hipStream_t)stream, id_space::of_index(h), {nullptr, nullptr});
 }
 int rag_bm25_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
                               const int32_t* tenants_host, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev,
@@ -636,7 +566,8 @@ int rag_bm25_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const
     DEV_ENTRY(h);
     entry_tenants t;
     if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
-    return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, (hipStream_t)stream, t.qt);
+    return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, k, t.tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, (hipStream_t)stream, id_space::of_index(h),
+                         t.qt);
 }
 
 int rag_rrf_fuse_dev(rag_handle_t h, const int64_t* lists_dev, int Q, int L, int len, int rrf_k, int top_k, int64_t* keys_dev,
@@ -659,14 +590,14 @@ static int hybrid_rrf_entry(rag_handle_t h, const float* q_dev, const int32_t* t
     ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid: 1 <= n_queries <= 65535");
     ARG_CHECK(h, q_dev && term_ptr_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid: null pointer");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid: 0 < pool <= 256");
-    if (int rc = bm25_fresh(h)) return rc;
-    ARG_CHECK(h, bm25_n_docs(h) == h->n_rows, "hybrid: the BM25 postings must be row-aligned with the index (same number of documents)");
+    if (int rc = keyword_postings_aligned(h, false, "hybrid", RAG_OK)) return rc;
     DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
     entry_tenants t;
     int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t);
     if (rc) return rc;
-    if ((rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, t.tenant, lists_ws_dev, scores_ws_dev, st, t.qt))) return rc;
+    if ((rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, t.tenant, lists_ws_dev, scores_ws_dev, st, id_space::of_index(h), t.qt)))
+        return rc;
     return rrf_fuse_dev(h, lists_ws_dev, Q, 2, pool, (int64_t)Q * pool, pool, rrf_k, k, keys_out_dev, rrf_out_dev, ranks_out_dev, st);
 }
 int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool,
@@ -732,7 +663,8 @@ int rag_sparse_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     DEV_ENTRY(h);
-    return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, n_queries, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream);
+    return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, n_queries, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream,
+                           id_space::of_index(h));
 }
 
 int rag_sparse_scores_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
@@ -753,13 +685,12 @@ int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t*
     ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid_sparse: 1 <= n_queries <= 65535");
     ARG_CHECK(h, q_dev && term_ptr_dev && qweights_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid_sparse: null pointer");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid_sparse: 0 < pool <= 256");
-    ARG_CHECK(h, sparse_n_docs(h) >= 0, "no sparse index loaded (rag_sparse_load_host)");
-    if (int rc = sparse_fresh(h)) return rc;
-    ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "hybrid_sparse: the sparse postings must be row-aligned with the index (same number of documents)");
+    if (int rc = keyword_postings_aligned(h, true, "hybrid_sparse", RAG_ERR_ARG)) return rc;
     DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_sparse: tenant filter requested but no tenants loaded");
-    if (int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st, {nullptr, nullptr}, qweights_dev))
+    if (int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st, id_space::of_index(h),
+                             {nullptr, nullptr}, qweights_dev))
         return rc;
     return rrf_fuse_dev(h, lists_ws_dev, Q, 2, pool, (int64_t)Q * pool, pool, rrf_k, k, keys_out_dev, rrf_out_dev, ranks_out_dev, st);
 }
@@ -842,7 +773,7 @@ static int hybrid_linear_entry(rag_handle_t h, const float* q_dev, const int32_t
             return rc;
         const dense_fused fz = {raw32, ld, qscale, margin, gt, raw, n, mx, h->temporal, alpha, beta, gamma};
         rc = dense_search_fused(h, q_dev + (size_t)q0 * h->dim, qc, k, tenant, ids_out_dev + (size_t)q0 * k, rows_out_dev + (size_t)q0 * k,
-                                hybrid_out_dev + (size_t)q0 * k, st, &fz, t.qt + q0);
+                                hybrid_out_dev + (size_t)q0 * k, st, &fz, id_space::of_index(h), t.qt + q0);
         if (rc) return rc;
         if (semantic_out_dev || keyword_out_dev || temporal_out_dev) {
             rc = linear_components(h, q_dev + (size_t)q0 * h->dim, rows_out_dev + (size_t)q0 * k, qc, k, &fz,

@@ -2130,6 +2130,25 @@ static int bm25_check_fresh(rag_ctx* h, const rag_bm25_index* ix) {
 // the same check for the hybrid entry points, before their row-alignment checks (an insert changes the row count)
 int bm25_fresh(rag_ctx* h) { return h->bm25 ? bm25_check_fresh(h, h->bm25) : RAG_OK; }
 
+// doc ids follow the caller's id space when the postings cover exactly the index's rows (hybrid fusion needs one id space);
+// any other postings - an ad-hoc index, a resident one beside an index of another size - report row numbers
+static id_space bm_id_space(const rag_ctx* h, const rag_bm25_index* ix, id_space ids) {
+    return bm_resident(h, ix) && h->n_rows == bm_total_docs(ix) ? ids : id_space::rows();
+}
+
+// common.h: loaded, fresh, row-aligned - with each entry's own code and text for missing postings
+int keyword_postings_aligned(rag_ctx* h, bool sparse, const char* who, int missing_code, const char* note) {
+    const rag_bm25_index* ix = sparse ? h->sparse : h->bm25;
+    if (ix == nullptr && missing_code != RAG_OK) {          // (the texts are built on the refusing paths only: searches call this)
+        h->err = std::string(missing_code == RAG_ERR_ARG ? "bad argument" : who) + ": no sparse index loaded (rag_sparse_load_host)";
+        return missing_code;
+    }
+    if (int rc = ix ? bm25_check_fresh(h, ix) : RAG_OK) return rc;
+    ARG_CHECK(h, ix != nullptr && bm_total_docs(ix) == h->n_rows,
+              (std::string(who) + ": the " + (sparse ? "sparse" : "BM25") + " postings must be row-aligned with the index" + note).c_str());
+    return RAG_OK;
+}
+
 // visibility argument of the scoring kernels (row_visible): the tenant filter and / or the deleted rows of the resident index
 // (per-query tenants: some query is filtered, so the table is needed as under a scalar filter)
 static int bm25_tenant_args(rag_ctx* h, const rag_bm25_index* ix, int tenant, query_tenants qt, const int32_t** tenants_out) {
@@ -2452,9 +2471,8 @@ static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, con
         ix->call_qw = qw;
     }
     if (mode == 0) {
-        const bool aligned = bm_resident(h, ix) && h->n_rows == bm_total_docs(ix);
-        const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, idd, rwd, scd, mxd,
-                                 ix->normalize};
+        const id_space ids = bm_id_space(h, ix, id_space::of_index(h));       // a *_host search reports the index's ids
+        const bm25_topk_out o = {ids.map, ids.base, idd, rwd, scd, mxd, ix->normalize};
         bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, qt.dev, st);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(ids_out, idd, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -2478,7 +2496,8 @@ static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
 
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
 static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
+                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
+                               query_tenants qt);
 
 // The per-call workspace (partial lists [Q][n_ranges][k] x 12 B + the plan) grows with Q x shard size: on a 12.5M-document shard a
 // query takes ~9 MB at k = 100. Batches are therefore run in sub-batches whose workspace stays under BM_WS_BUDGET (queries are
@@ -2486,7 +2505,8 @@ static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* te
 #define BM_WS_BUDGET ((size_t)6 << 30)
 // ix: the resident BM25 postings (bm25_topk_dev) or the learned-sparse postings (sparse_topk_dev, which sets ix->call_qw first)
 static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                       int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
+                       int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
+                       query_tenants qt) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
     if (int rc = bm25_check_fresh(h, ix)) return rc;
@@ -2497,18 +2517,19 @@ static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_d
         const int nq = std::min(qb, Q - q0);
         const int rc = bm25_topk_dev_batch(h, ix, term_ptr_dev + q0, terms_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
                                            rows_dev ? rows_dev + (size_t)q0 * k : nullptr, scores_dev + (size_t)q0 * k,
-                                           raw_max_dev ? raw_max_dev + q0 : nullptr, st, qt + q0);      // (the tenants go with their queries)
+                                           raw_max_dev ? raw_max_dev + q0 : nullptr, st, ids, qt + q0);      // (the tenants go with their queries)
         if (rc) return rc;
     }
     return RAG_OK;
 }
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
-    return bm_topk_dev(h, h->bm25, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, st, qt);
+                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids, query_tenants qt) {
+    return bm_topk_dev(h, h->bm25, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, st, ids, qt);
 }
 
 static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt) {
+                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
+                               query_tenants qt) {
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && ids_dev && scores_dev, "bm25_topk_dev: bad arguments");
     ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
     const int32_t* tenants = nullptr;
@@ -2524,11 +2545,9 @@ static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* te
     if ((rc = ix->ws_run_key.reserve(h, need_run))) return rc;
     if ((rc = ix->ws_run_row.reserve(h, need_run))) return rc;
     if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
-    // doc ids follow the dense index's mapping when both indexes cover the same rows (hybrid fusion needs one id space)
-    const bool aligned = h->n_rows == bm_total_docs(ix);
+    ids = bm_id_space(h, ix, ids);
     const bm25_topk_ws w = {ix->ws_key, ix->ws_row, ix->ws_cnt, ix->ws_run_key, ix->ws_run_row, ix->ws_tau, {ix->ws_plan_off, ix->ws_plan_meta}};
-    const bm25_topk_out o = {aligned ? h->ids : (const int64_t*)nullptr, aligned ? h->id_base : (int64_t)0, ids_dev, rows_dev, scores_dev,
-                             raw_max_dev, ix->normalize};
+    const bm25_topk_out o = {ids.map, ids.base, ids_dev, rows_dev, scores_dev, raw_max_dev, ix->normalize};
     if ((rc = prof_begin(h, 1, st))) return rc;
     bm25_launch_topk(h, ix, term_ptr_dev, terms_dev, Q, k, w, o, tenants, tenant, qt.dev, st);
     HIP_TRY(h, hipGetLastError());
@@ -2707,8 +2726,6 @@ int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int
     if (hbm_bytes_out) *hbm_bytes_out = ix ? bm_segment_bytes(ix) + (tl ? bm_segment_bytes(tl) : 0) : 0;
     return RAG_OK;
 }
-int64_t sparse_n_docs(const rag_ctx* h) { return h->sparse ? bm_total_docs(h->sparse) : -1; }
-int sparse_fresh(rag_ctx* h) { return h->sparse ? bm25_check_fresh(h, h->sparse) : RAG_OK; }
 
 // without a dense index of the same rows the ids are row numbers and there is nothing a tenant could be looked up in
 static int sparse_args(rag_ctx* h, const void* term_ptr, const void* qweights, int tenant) {
@@ -2734,10 +2751,10 @@ int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms
 }
 
 int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
-                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids) {
     if (int rc = sparse_args(h, term_ptr_dev, qweights_dev, tenant)) return rc;
     h->sparse->call_qw = qweights_dev;
-    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, {nullptr, nullptr});
+    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, ids, {nullptr, nullptr});
 }
 
 // ---- point lookup: the exact learned-sparse score of GIVEN rows (rag_sparse_score_rows_*; the sparse component of rag_m3_score_rows_dev)

@@ -310,6 +310,16 @@ static inline query_tenants operator+(query_tenants t, int q0) {
 __device__ __forceinline__ int tenant_of_query(const int32_t* __restrict__ qten, int q, int tenant) {
     return qten != nullptr ? qten[q] : tenant;
 }
+// ---- id space: what a search leg reports for a row of the index. map[row] where there is a map, else base + row. A leg takes it
+// as an argument and hands it to its kernels; it never reads rag_ctx::ids / id_base itself. The entries pass the index's mapping,
+// the candidate stage of the resident composites (pipeline.hip) row numbers.
+struct id_space {
+    const int64_t* map; int64_t base;
+    static id_space of_index(const rag_ctx* h) { return {h->ids.get(), h->id_base}; }
+    static id_space rows() { return {nullptr, 0}; }
+    bool identity() const { return map == nullptr && base == 0; }
+};
+
 // host words -> device memory as ordinary work of `st`: the words travel as kernel arguments, so the host array is consumed when
 // this returns and nothing waits for the stream (a pageable hipMemcpyAsync would). dense.hip
 int upload_i32(rag_ctx* h, int32_t* dst_dev, const int32_t* src_host, size_t n, hipStream_t st);
@@ -400,16 +410,17 @@ struct dense_fused {
     double alpha, beta, gamma;
 };
 // fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev (dense.hip)
-// qt: per-query tenants (then `tenant` is not read)
+// ids: what ids_dev reports (id_space); qt: per-query tenants (then `tenant` is not read)
 int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                       double* scores_dev, hipStream_t st, const dense_fused* fz, query_tenants qt = {nullptr, nullptr});
+                       double* scores_dev, hipStream_t st, const dense_fused* fz, id_space ids, query_tenants qt = {nullptr, nullptr});
 static inline int dense_search(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                               double* scores_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr}) {
-    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr, qt);
+                               double* scores_dev, hipStream_t st, id_space ids, query_tenants qt = {nullptr, nullptr}) {
+    return dense_search_fused(h, q_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, st, nullptr, ids, qt);
 }
 void comm_free(rag_ctx* h);
+// pipeline.hip: the dense and the keyword leg of a hybrid search into lists_dev [2][Q][pool], both in the id space `ids`
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt = {nullptr, nullptr},
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, id_space ids, query_tenants qt = {nullptr, nullptr},
                 const float* qweights_dev = nullptr);
 // the query terms and what bounds a negative raw BM25 score from them (bm25_negative_bound_args)
 struct linear_neg_bound { const int32_t* term_ptr; double per_token; };
@@ -437,12 +448,90 @@ int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists
 int pairwise_cosine(rag_ctx* h, const float* a_dev, int m, const float* b_dev, int n, int dim, double* out_dev,
                     hipStream_t st);
 int pairwise_cosine_f64(rag_ctx* h, const double* a_dev, int m, const double* b_dev, int n, int dim, double* out_dev, hipStream_t st);
+// fusion.hip
+int rrf_fuse_host(rag_ctx* h, const int64_t* lists, int Q, int L, int len, int rrf_k, int top_k, int64_t* keys_out, double* scores_out,
+                  int32_t* ranks_out);
+int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k, int top_k,
+                 int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
+int linear_fuse_topk_host(rag_ctx* h, const double* sem, const double* kw, const double* tmp, int n, double a, double b, double g, int top_k,
+                          int32_t* idx_out, double* hyb_out);
+// bm25.hip: the BM25 postings (h->bm25) ...
+int bm25_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len, const double* idf,
+                   int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b);
+int bm25_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len, const double* idf_new,
+                     int64_t n_new, int64_t n_terms_total);
+int bm25_fold(rag_ctx* h);
+void bm25_free(rag_ctx* h);
+int64_t bm25_n_docs(const rag_ctx* h);          // -1 without postings
+int bm25_live_counts_host(rag_ctx* h, int32_t* df_out, int64_t* n_docs_live_out, int64_t* sum_doc_len_out);
+int bm25_set_statistics_host(rag_ctx* h, const double* idf, double avgdl);
+int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_info* info_out);
+int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out);
+int bm25_index_bytes(const int64_t* indptr, int64_t n_docs, int64_t n_terms, int64_t* postings_out, int64_t* meta_out, int64_t* table_out);
+int bm25_grid_plan(int n_ranges_in_launch, int n_queries, int linear, int64_t* out5);
+int bm25_set_normalize(rag_ctx* h, int on);
+int bm25_negative_bound_args(const rag_ctx* h, double* per_token_out);
+int bm25_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int tenant, int64_t* ids_out, int32_t* rows_out,
+                   double* scores_out, double* raw_max_out, query_tenants qt);
+// ids: what ids_dev reports for postings that cover exactly the index's rows; any other postings report row numbers
+int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
+                  double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids, query_tenants qt);
+int bm25_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, int Q, double* out);
+int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, double* out_dev, hipStream_t st, float* raw32_dev,
+                    int64_t ld, unsigned long long* max_key_dev, int tenant, query_tenants qt);
+int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const int32_t* tf, const int32_t* doc_len, const double* idf,
+                           int64_t n_docs, int64_t n_terms, double avgdl, double k1, double b, const int32_t* term_ptr, const int32_t* terms, int Q,
+                           double* out);
+// ... and the learned-sparse postings (h->sparse)
+int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_docs, int64_t n_terms);
+int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_new, int64_t n_terms_total);
+int sparse_fold(rag_ctx* h);
+void sparse_free(rag_ctx* h);
+int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
+int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out);
+int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant, int64_t* ids_out,
+                     int32_t* rows_out, double* scores_out);
+int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids);
+int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out);
+// The ONE precondition of a search that fuses keyword postings (sparse: h->sparse, else h->bm25) with the dense index by row: they are
+// loaded, fresh (RAG_ERR_STATE while stale) and hold as many documents as the index has rows (RAG_ERR_ARG, "<who>: the ... postings
+// must be row-aligned with the index" + note). Missing postings return missing_code, which differs by entry and is kept as it was:
+//   RAG_ERR_ARG   "bad argument: no sparse index loaded (rag_sparse_load_host)"   rag_hybrid_sparse_rrf_dev, rag_retrieve_maxsim_dev
+//   RAG_ERR_STATE "<who>: no sparse index loaded (rag_sparse_load_host)"          rag_m3_score_rows_dev, rag_retrieve_m3_dev
+//   RAG_OK        (no message of their own: reported as not row-aligned)          rag_hybrid_rrf*_dev, rag_retrieve_rerank*_dev
+int keyword_postings_aligned(rag_ctx* h, bool sparse, const char* who, int missing_code, const char* note = " (same number of documents)");
+// mmr.hip, chunk_chain.hip
+int mmr_select_dev(rag_ctx* h, const float* queries_dev, const float* emb_dev, const int32_t* rows_dev, int Q, int n, int dim, int top_k, double lam,
+                   int variant, int32_t* sel_dev, double* score_dev, hipStream_t st);
+int mmr_select_host(rag_ctx* h, const float* query, const float* emb, int n, int dim, int top_k, double lam, int variant, int32_t* sel_out,
+                    double* score_out);
+int chunk_chain_host(rag_ctx* h, const float* emb, const int32_t* sent_len, int n, int dim, double threshold, int max_chunk, int min_chunk,
+                     int32_t* group_out);
+// pipeline.hip: the passage token store, the pair builder and the sigmoid top-k on their own, and the resident composites
+int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int64_t n_rows, int L, int id_bits);
+int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits);
+int tokens_info(const rag_ctx* h, int64_t* rows_out, int* L_out, int* id_bits_out);
+int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n_rows, hipStream_t st);
+int ce_build_pairs_dev(rag_ctx* h, const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, const int64_t* cand_dev, int Q, int pool,
+                       int64_t token_id_base, int L_pair, int cls_id, int sep_id, int32_t* ids_out, int32_t* tt_out, int32_t* lens_out,
+                       hipStream_t st);
+int rerank_topk_dev(rag_ctx* h, const float* logits_dev, const int64_t* cand_dev, int Q, int pool, int k, int64_t* ids_out, double* scores_out,
+                    float* logits_out, hipStream_t st);
+int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const int32_t* q_tok_dev,
+                        const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant, int mode, int cls_id, int sep_id, int L_pair,
+                        int64_t* ids_out, double* scores_out, float* logits_out, int64_t* cand_out, hipStream_t st, query_tenants qt);
+int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                        const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, int64_t* ids_out,
+                        double* scores_out, int64_t* cand_out, hipStream_t st);
 // cross_encoder.hip: the cross-encoder (h->ce) and the sentence-embedding encoder (h->emb). ids / tt / lens / out are host
 // arrays (staged, the call waits) or device arrays (queued on st) as host_ptrs says.
 int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n);
 int ce_score(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
              bool host_ptrs);
 void ce_free(rag_ctx* h);
+int ce_length_class(int d_head, int seq_len);
+int ce_model_seq_limit(const rag_ctx* h, int which);
 int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n, int flags);
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
               bool host_ptrs);
@@ -483,6 +572,7 @@ struct tokvec_compact_plan {
 int tokvec_compact_prepare(rag_ctx* h, const int64_t* row_map_host, int64_t n_map, size_t stage_bytes, tokvec_compact_plan* plan);
 int tokvec_compact_commit(rag_ctx* h, tokvec_compact_plan* plan, char* stage, hipStream_t st);
 int tokvec_usable(rag_ctx* h, const char* who);          // RAG_ERR_STATE without a store or with a stale one
+int tokvec_covers_index(rag_ctx* h, const char* who);    // (after tokvec_usable) RAG_ERR_STATE unless the store holds exactly the index's rows
 int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
                   int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st);
 int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,

@@ -1303,13 +1303,13 @@ static int second_pass(rag_ctx* h, emit_args a, int total_tiles, int k, float tw
 }
 
 // ---- float64 scores of the survivors, then the ranking: writes every proven query's top-k and lists the others for the scan
-static int rescore_and_finalize(rag_ctx* h, const float* q_dev, int Q, int k, const dense_fused* fz, int64_t* ids_dev, int32_t* rows_dev,
-                                double* scores_dev, hipStream_t st) {
+static int rescore_and_finalize(rag_ctx* h, const float* q_dev, int Q, int k, const dense_fused* fz, id_space ids, int64_t* ids_dev,
+                                int32_t* rows_dev, double* scores_dev, hipStream_t st) {
     const dense_ws& w = h->ws;
     launch(rescore_kernel, dim3(4, Q), dim3(256), 0, st, q_dev, h->emb32, w.cand, w.n_sorted, h->exact, h->dim);
     if (fz) launch(linear_fuse_kernel, dim3(4, Q), dim3(256), 0, st, w.cand, w.n_sorted, h->exact, fz->raw, fz->n, fz->mx, fz->temporal,
                    fz->alpha, fz->beta, fz->gamma);
-    launch(finalize_kernel, dim3(Q), dim3(256), 0, st, w.cand, w.n_sorted, h->exact, w.bound, h->ids, h->id_base, k, h->opt.force_level, ids_dev,
+    launch(finalize_kernel, dim3(Q), dim3(256), 0, st, w.cand, w.n_sorted, h->exact, w.bound, ids.map, ids.base, k, h->opt.force_level, ids_dev,
            rows_dev, scores_dev, h->flag, h->stats, h->scan_list, h->stats + 7);
     return launch_status(h);
 }
@@ -1317,7 +1317,7 @@ static int rescore_and_finalize(rag_ctx* h, const float* q_dev, int Q, int k, co
 // ---- exact scan for whatever is still unproven (the queries finalize appended to scan_list, count = stats[7]): rounds of
 // SCAN_ROUND flagged queries, device-side early exit when none
 static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const int32_t* vis, int tenant, const int32_t* qten, const dense_fused* fz,
-                             int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
+                             id_space ids, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st) {
     if (h->n_rows == 0) return RAG_OK;
     const int window = SCAN_CHUNK - k;
     const int64_t rows_per_block = std::max<int64_t>(1, (h->n_rows + 1023) / 1024 + window - 1) / window * window;
@@ -1334,7 +1334,7 @@ static int exact_scan_rounds(rag_ctx* h, const float* q_dev, int Q, int k, const
     for (int f0 = 0; f0 < Q; f0 += round_q) {
         launch(scan_chunk_kernel, dim3(n_blocks), dim3(256), 0, st, q_dev, h->emb32, vis, tenant, qten, h->n_rows, rows_per_block, h->dim, k,
                h->scan_list, scan_count, f0, round_q, pk, pr, f.raw, f.n, f.mx, f.temporal, f.alpha, f.beta, f.gamma);
-        launch(scan_merge_kernel, dim3(std::min(Q - f0, round_q)), dim3(256), 0, st, pk, pr, n_blocks, k, h->ids, h->id_base, h->scan_list,
+        launch(scan_merge_kernel, dim3(std::min(Q - f0, round_q)), dim3(256), 0, st, pk, pr, n_blocks, k, ids.map, ids.base, h->scan_list,
                scan_count, f0, h->flag, ids_dev, rows_dev, scores_dev, h->stats);
     }
     return launch_status(h);
@@ -1353,7 +1353,7 @@ static emit_args emit_args_of(const rag_ctx* h, const tile_universe& u, const in
 // fz == nullptr: plain cosine top-k. Otherwise the linear fusion of rag_hybrid_linear_dev: the emitted / keyed / ranked score
 // is alpha * cosine + beta * keyword + gamma * temporal (fz carries the per-(query,row) bias and the float64 inputs).
 int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev,
-                       double* scores_dev, hipStream_t st, const dense_fused* fz, query_tenants qt) {
+                       double* scores_dev, hipStream_t st, const dense_fused* fz, id_space ids, query_tenants qt) {
     ARG_CHECK(h, h->index_loaded, "no index loaded");
     ARG_CHECK(h, Q > 0 && k > 0 && k <= RAG_MAX_K, "need Q>0 and 0<k<=256");
     // any scalar tenant < 0 is "no filter" (include/rag_hip.h) and is -1 from here on: RAG_TENANT_PER_QUERY, which emit_args_of
@@ -1381,8 +1381,8 @@ int dense_search_fused(rag_ctx* h, const float* q_dev, int Q, int k, int tenant,
     if ((rc = prepare_queries(h, q_dev, Q, st))) return rc;
     if ((rc = first_pass(h, a, plan, Q, k, two_eps, fz, with_second_pass, st))) return rc;
     if (u.count > 0 && with_second_pass && (rc = second_pass(h, a, u.count, k, two_eps, fz, col_tenants, st))) return rc;
-    if ((rc = rescore_and_finalize(h, q_dev, Q, k, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
-    if ((rc = exact_scan_rounds(h, q_dev, Q, k, vis, tenant, qt.dev, fz, ids_dev, rows_dev, scores_dev, st))) return rc;
+    if ((rc = rescore_and_finalize(h, q_dev, Q, k, fz, ids, ids_dev, rows_dev, scores_dev, st))) return rc;
+    if ((rc = exact_scan_rounds(h, q_dev, Q, k, vis, tenant, qt.dev, fz, ids, ids_dev, rows_dev, scores_dev, st))) return rc;
     h->last_q = Q;
     h->last_k = k;
     h->last_stages = (int)plan.size();

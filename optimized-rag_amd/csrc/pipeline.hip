@@ -14,14 +14,6 @@
 
 #include <cmath>
 
-int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
-                  int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, query_tenants qt);
-int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
-                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st);
-int64_t bm25_n_docs(const rag_ctx* h);
-int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, int64_t list_stride, int64_t query_stride, int rrf_k,
-                 int top_k, int64_t* keys_dev, double* scores_dev, int32_t* ranks_dev, hipStream_t st);
-
 // The two candidate legs of the hybrid search: dense top-pool into lists[0], BM25 top-pool into lists[1] ([2][Q][pool]).
 // They are independent: the BM25 leg runs on a side stream, forked from and joined back into the caller's stream by events.
 // For a handful of queries both legs are latency-bound (one query: 0.6 ms of HBM-bound scan beside 0.2 ms of BM25 launches that
@@ -32,15 +24,16 @@ int rrf_fuse_dev(rag_ctx* h, const int64_t* lists_dev, int Q, int L, int len, in
 // qweights_dev != null: the second leg is the learned-sparse index (rag_hybrid_sparse_rrf_dev; no per-query tenants there).
 #define RAG_FORK_MAX_Q 4096
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
-                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, query_tenants qt, const float* qweights_dev) {
+                int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, id_space ids, query_tenants qt, const float* qweights_dev) {
     int64_t* const bm_ids = lists_dev + (size_t)Q * pool;
     auto keyword_leg = [&](double* scores, hipStream_t s) -> int {
-        if (qweights_dev != nullptr) return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, Q, pool, tenant, bm_ids, nullptr, scores, s);
-        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores, nullptr, s, qt);
+        if (qweights_dev != nullptr)
+            return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, Q, pool, tenant, bm_ids, nullptr, scores, s, ids);
+        return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores, nullptr, s, ids, qt);
     };
     const int fork_max = h->opt.fork_max_q > 0 ? h->opt.fork_max_q : RAG_FORK_MAX_Q;
     if (Q > fork_max || h->opt.no_fork) {
-        int rc = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);
+        int rc = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, ids, qt);
         if (rc) return rc;
         return keyword_leg(scores_ws_dev, st);
     }
@@ -57,7 +50,7 @@ int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, con
     int rc = keyword_leg(h->side_scores, h->side_stream);
     // the join is recorded and waited for even if a leg failed to launch: the caller's stream must never run ahead of the side stream
     HIP_TRY(h, hipEventRecord(h->ev_join, h->side_stream));
-    const int rc2 = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, qt);
+    const int rc2 = dense_search(h, q_dev, Q, pool, tenant, lists_dev, nullptr, scores_ws_dev, st, ids, qt);
     HIP_TRY(h, hipStreamWaitEvent(st, h->ev_join, 0));
     return rc ? rc : rc2;
 }
@@ -243,6 +236,14 @@ static int launch_build_pairs(rag_ctx* h, const int32_t* q_tok, const int32_t* q
     return launch_status(h);
 }
 
+// the rank of slot j (score `mine`) among the n slots of its query in LDS: how many slots that are ok beat it by (score desc,
+// slot asc). Distinct slots get distinct ranks. The caller has synchronised the writes of s[] and ok[].
+__device__ __forceinline__ int stable_rank(const double* s, const int* ok, int n, int j, double mine) {
+    int rank = 0;
+    for (int i = 0; i < n; ++i) rank += ok[i] && (s[i] > mine || (s[i] == mine && i < j));
+    return rank;
+}
+
 // one workgroup per query, pool <= 256: stable rank by (sigmoid desc, candidate position asc).
 // RAW (rag_tokvec_rerank_*, tokvec.hip): the score is the float32 itself, no sigmoid; slot_rows [Q][pool] int32 holds the row each
 // slot was scored for, -1 = an empty slot, skipped; ids_out gets the row's doc id - idmap[row] or id_base + row for a row of the
@@ -282,8 +283,7 @@ __global__ __launch_bounds__(256) void rerank_topk_kernel(const float* __restric
     }
     __syncthreads();
     if (j < pool && valid) {
-        int rank = 0;
-        for (int i = 0; i < pool; ++i) rank += ok[i] && (s[i] > mine || (s[i] == mine && i < j));
+        const int rank = stable_rank(s, ok, pool, j, mine);
         if (rank < k) {
             score_out[(size_t)q * k + rank] = mine;
             if constexpr (RAW) {
@@ -308,8 +308,9 @@ static void launch_rerank_topk(const float* logits, const int64_t* cand, int Q, 
 int tokvec_topk(rag_ctx* h, const float* scores_dev, const int32_t* slot_rows_dev, int Q, int pool, int k, int64_t* ids_out, int32_t* rows_out,
                 double* scores_out, hipStream_t st) {
     const bool idx = h->index_loaded;
-    launch(rerank_topk_kernel<true>, dim3(Q), dim3(256), 0, st, scores_dev, nullptr, pool, k, ids_out, scores_out, nullptr, slot_rows_dev,
-           idx ? h->ids.get() : nullptr, idx ? h->n_rows : (int64_t)-1, idx ? h->id_base : (int64_t)0, rows_out);
+    const id_space ids = idx ? id_space::of_index(h) : id_space::rows();
+    launch(rerank_topk_kernel<true>, dim3(Q), dim3(256), 0, st, scores_dev, nullptr, pool, k, ids_out, scores_out, nullptr, slot_rows_dev, ids.map,
+           idx ? h->n_rows : (int64_t)-1, ids.base, rows_out);
     return launch_status(h);
 }
 
@@ -339,6 +340,74 @@ __global__ void map_rows_to_ids_kernel(int64_t* __restrict__ v, int64_t n, const
     if (i >= n || v[i] < 0) return;
     v[i] = idmap ? idmap[v[i]] : id_base + v[i];
 }
+// n row numbers at v -> doc ids in place, as work of st (negative entries stay); nothing to launch where a row number is its id
+static int map_rows_to_ids(rag_ctx* h, int64_t* v, size_t n, id_space ids, hipStream_t st) {
+    if (ids.identity()) return RAG_OK;
+    launch(map_rows_to_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, v, (int64_t)n, ids.map, ids.base);
+    return launch_status(h);
+}
+
+__global__ void rows_narrow_kernel(const int64_t* __restrict__ in, int32_t* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i] < 0 ? -1 : (int32_t)in[i];
+}
+
+// ---- the per-call workspace rag_ctx::pipe_ws. `planes` names every plane once, as p = c.take<T>(elements); it runs twice: without
+// memory, which sums the sizes (stage_size: each plane starts on a 256-byte boundary), then over the reserved buffer.
+struct ws_carve {
+    char* base;
+    size_t bytes = 0;
+    template <class T>
+    T* take(size_t n) {
+        T* r = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += stage_size(n, sizeof(T));
+        return r;
+    }
+};
+template <class F>
+static int pipe_ws_carve(rag_ctx* h, F&& planes) {
+    ws_carve sum{nullptr}, c{nullptr};
+    planes(sum);
+    if (int rc = h->pipe_ws.reserve(h, sum.bytes)) return rc;
+    c.base = h->pipe_ws;
+    planes(c);
+    return RAG_OK;
+}
+
+// ---- the candidate stage of the three composites: [Q][S] candidate ROWS of the index into w.cand (-1 = an empty slot)
+//   mode 0  the dense top-pool                                              S = pool
+//   mode 1  dense top-pool + keyword top-pool, RRF -> top-pool              S = pool
+//   mode 2  the same RRF at top_k = 2 * pool: the union of the two lists    S = 2 * pool
+// The keyword leg is BM25 when qweights_dev is null and the learned-sparse index otherwise (hybrid_legs). It runs in ROW space
+// (id_space::rows()): the token store and the token vectors are row-aligned and RRF only needs a consistent key space; each
+// composite maps its outputs to doc ids at its end, so explicit doc ids (e.g. primary keys of a loaded shard) work as well as
+// id_base + row. w.rows (where the composite asked for the plane): the same rows narrowed to int32.
+static inline int cand_slots(int mode, int pool) { return mode == 2 ? 2 * pool : pool; }
+struct cand_ws { int64_t* lists; double* sc; int64_t* cand; double* rrf; int32_t* ranks; int32_t* rows; };
+// lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][S] i64 | rrf [Q][S] f64 | ranks [Q][S][2] i32 | rows [Q][S] i32
+static void cand_ws_planes(ws_carve& c, cand_ws& w, size_t P, size_t PS, bool narrow) {
+    w.lists = c.take<int64_t>(2 * P);
+    w.sc = c.take<double>(P);
+    w.cand = c.take<int64_t>(PS);
+    w.rrf = c.take<double>(PS);
+    w.ranks = c.take<int32_t>(2 * PS);
+    w.rows = narrow ? c.take<int32_t>(PS) : nullptr;
+}
+static int candidate_stage(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                           int Q, int pool, int rrf_k, int tenant, query_tenants qt, int mode, const cand_ws& w, hipStream_t st) {
+    const int S = cand_slots(mode, pool);
+    const size_t P = (size_t)Q * pool, PS = (size_t)Q * S;
+    int rc;
+    if (mode == 0) {
+        rc = dense_search(h, q_emb_dev, Q, pool, tenant, w.cand, nullptr, w.sc, st, id_space::rows(), qt);
+    } else {
+        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, w.lists, w.sc, st, id_space::rows(), qt, qweights_dev);
+        if (!rc) rc = rrf_fuse_dev(h, w.lists, Q, 2, pool, (int64_t)P, pool, rrf_k, S, w.cand, w.rrf, w.ranks, st);
+    }
+    if (rc || w.rows == nullptr) return rc;
+    launch(rows_narrow_kernel, dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st, w.cand, w.rows, (int64_t)PS);
+    return launch_status(h);
+}
 
 int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                         const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int Q, int pool, int k, int rrf_k, int tenant,
@@ -350,71 +419,34 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     ARG_CHECK(h, L_pair >= 8 && L_pair <= 512 && Lq > 0 && q_emb_dev && q_tok_dev && q_len_dev && ids_out && scores_out && logits_out,
               "retrieve_rerank: bad arguments");
     ARG_CHECK(h, mode == 0 || (mode == 1 && term_ptr_dev && h->bm25 != nullptr), "retrieve_rerank: mode 1 needs BM25 postings and query terms");
-    if (mode != 0) {
-        if (int rc = bm25_fresh(h)) return rc;
-    }
-    ARG_CHECK(h, mode == 0 || bm25_n_docs(h) == h->n_rows, "retrieve_rerank: the BM25 postings must be row-aligned with the index");
+    if (int rc = mode != 0 ? keyword_postings_aligned(h, false, "retrieve_rerank", RAG_OK, "") : RAG_OK) return rc;
     const size_t P = (size_t)Q * pool;
-    // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][pool] i64 | rrf [Q][pool] f64 | ranks [Q][pool][2] i32
-    //            | pair ids [P][L] | pair tt [P][L] | lens [P] | logits [P]
-    const size_t need = P * (16 + 8 + 8 + 8 + 8) + P * L_pair * 8 + P * 8 + 256;
-    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
-    char* w = h->pipe_ws;
-    int64_t* lists = (int64_t*)w;              w += P * 16;
-    double* sc = (double*)w;                   w += P * 8;
-    int64_t* cand = (int64_t*)w;               w += P * 8;
-    double* rrf = (double*)w;                  w += P * 8;
-    int32_t* ranks = (int32_t*)w;              w += P * 8;
-    int32_t* pid = (int32_t*)w;                w += P * L_pair * 4;
-    int32_t* ptt = (int32_t*)w;                w += P * L_pair * 4;
-    int32_t* plen = (int32_t*)w;               w += P * 4;
-    float* logit = (float*)w;
-    // The candidate stage runs in ROW space (the token store is row-aligned and RRF only needs a consistent key space):
-    // the id mapping is switched off for these launches (pointers are kernel arguments, captured at launch) and applied to
-    // the outputs at the end, so explicit doc ids (e.g. primary keys of a loaded shard) work as well as id_base + row.
-    dev_buf<int64_t> ids_saved = std::move(h->ids);
-    const int64_t id_base_saved = h->id_base;
-    h->id_base = 0;
-    int rc;
-    if (mode == 0) {
-        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st, qt);
-    } else {
-        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, qt);
-        if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, pool, cand, rrf, ranks, st);
-    }
-    h->ids = std::move(ids_saved);
-    h->id_base = id_base_saved;
+    cand_ws w;
+    int32_t *pid, *ptt, *plen;
+    float* logit;
+    int rc = pipe_ws_carve(h, [&](ws_carve& c) {
+        cand_ws_planes(c, w, P, P, false);
+        pid = c.take<int32_t>(P * L_pair);       // pair ids [P][L]
+        ptt = c.take<int32_t>(P * L_pair);       // pair token types [P][L]
+        plen = c.take<int32_t>(P);               // pair lengths
+        logit = c.take<float>(P);
+    });
     if (rc) return rc;
-    if ((rc = launch_build_pairs(h, q_tok_dev, q_len_dev, Lq, cand, 0, P, pool, L_pair, cls_id, sep_id, pid, ptt, plen, st))) return rc;
-    rc = ce_score(h, pid, ptt, plen, (int)P, L_pair, logit, st, false);
-    if (rc) return rc;
-    launch_rerank_topk(logit, cand, Q, pool, k, ids_out, scores_out, logits_out, st);
+    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, nullptr, Q, pool, rrf_k, tenant, qt, mode, w, st))) return rc;
+    if ((rc = launch_build_pairs(h, q_tok_dev, q_len_dev, Lq, w.cand, 0, P, pool, L_pair, cls_id, sep_id, pid, ptt, plen, st))) return rc;
+    if ((rc = ce_score(h, pid, ptt, plen, (int)P, L_pair, logit, st, false))) return rc;
+    launch_rerank_topk(logit, w.cand, Q, pool, k, ids_out, scores_out, logits_out, st);
     HIP_TRY(h, hipGetLastError());
-    if (cand_out) HIP_TRY(h, hipMemcpyAsync(cand_out, cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    if (h->ids != nullptr || id_base_saved != 0) {
-        hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)(((size_t)Q * k + 255) / 256)), dim3(256), 0, st, ids_out, (int64_t)Q * k,
-                           h->ids, id_base_saved);
-        if (cand_out)
-            hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, h->ids,
-                               id_base_saved);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return RAG_OK;
+    if (cand_out) HIP_TRY(h, hipMemcpyAsync(cand_out, w.cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    const id_space ids = id_space::of_index(h);
+    if ((rc = map_rows_to_ids(h, ids_out, (size_t)Q * k, ids, st))) return rc;
+    return cand_out ? map_rows_to_ids(h, cand_out, P, ids, st) : RAG_OK;
 }
 
 // ---- retrieve + late-interaction rerank as one device-resident call (rag_retrieve_maxsim_dev): what retrieve_rerank_dev does for
 // the cross-encoder, with the resident token vectors (tokvec.hip) in place of the token store and the forward.
 //   1. candidates: dense top-pool (mode 0) or dense + learned-sparse RRF -> top-pool (mode 1), tenant and deleted rows filtered
-//   2. tokvec_maxsim_kernel over the [Q][pool] candidate rows   3. the raw top-k of rerank_topk_kernel
-// The candidate stage runs in row space as in retrieve_rerank_dev; the ids are mapped at the end.
-int64_t sparse_n_docs(const rag_ctx* h);
-int sparse_fresh(rag_ctx* h);
-
-__global__ void rows_narrow_kernel(const int64_t* __restrict__ in, int32_t* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] < 0 ? -1 : (int32_t)in[i];
-}
-
+//   2. tokvec_maxsim_kernel over the [Q][pool] candidate rows   3. the raw top-k of rerank_topk_kernel (which maps the ids)
 int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                         const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
                         int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st) {
@@ -423,53 +455,21 @@ int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     ARG_CHECK(h, q_emb_dev && q_vecs_dev && q_off_dev && ids_out && scores_out, "retrieve_maxsim: null argument");
     ARG_CHECK(h, mode == 0 || mode == 1, "retrieve_maxsim: mode is 0 (dense) or 1 (dense + sparse)");
     ARG_CHECK(h, h->index_loaded, "retrieve_maxsim: no index loaded");
-    if (h->tv_docs != h->n_rows) {
-        h->err = "retrieve_maxsim: the token-vector store does not hold exactly the index's rows (append the vectors of the inserted rows)";
-        return RAG_ERR_STATE;
-    }
+    if (int rc = tokvec_covers_index(h, "retrieve_maxsim")) return rc;
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_maxsim: tenant filter requested but no tenants loaded");
     if (mode == 1) {
         ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_maxsim: mode 1 needs the query's terms and weights");
-        ARG_CHECK(h, sparse_n_docs(h) >= 0, "no sparse index loaded (rag_sparse_load_host)");
-        if (int rc = sparse_fresh(h)) return rc;
-        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "retrieve_maxsim: the sparse postings must be row-aligned with the index (same number of documents)");
+        if (int rc = keyword_postings_aligned(h, true, "retrieve_maxsim", RAG_ERR_ARG)) return rc;
     }
     const size_t P = (size_t)Q * pool;
-    // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][pool] i64 | rrf [Q][pool] f64 | ranks [Q][pool][2] i32 | rows [Q][pool] i32
-    const size_t need = P * (16 + 8 + 8 + 8 + 8 + 4) + 256;
-    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
-    char* w = h->pipe_ws;
-    int64_t* lists = (int64_t*)w;              w += P * 16;
-    double* sc = (double*)w;                   w += P * 8;
-    int64_t* cand = (int64_t*)w;               w += P * 8;
-    double* rrf = (double*)w;                  w += P * 8;
-    int32_t* ranks = (int32_t*)w;              w += P * 8;
-    int32_t* rows = (int32_t*)w;
-    dev_buf<int64_t> ids_saved = std::move(h->ids);
-    const int64_t id_base_saved = h->id_base;
-    h->id_base = 0;
-    int rc;
-    if (mode == 0) {
-        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st);
-    } else {
-        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, {nullptr, nullptr}, qweights_dev);
-        if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, pool, cand, rrf, ranks, st);
-    }
-    h->ids = std::move(ids_saved);
-    h->id_base = id_base_saved;
+    cand_ws w;
+    int rc = pipe_ws_carve(h, [&](ws_carve& c) { cand_ws_planes(c, w, P, P, true); });
     if (rc) return rc;
-    launch(rows_narrow_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand, rows, (int64_t)P);
-    if ((rc = launch_status(h))) return rc;
-    if ((rc = tokvec_rerank(h, q_vecs_dev, q_off_dev, rows, Q, pool, k, ids_out, nullptr, scores_out, nullptr, st))) return rc;
-    if (cand_out) {
-        HIP_TRY(h, hipMemcpyAsync(cand_out, cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        if (h->ids != nullptr || id_base_saved != 0) {
-            hipLaunchKernelGGL(map_rows_to_ids_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, cand_out, (int64_t)P, h->ids,
-                               id_base_saved);
-            HIP_TRY(h, hipGetLastError());
-        }
-    }
-    return RAG_OK;
+    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, {nullptr, nullptr}, mode, w, st))) return rc;
+    if ((rc = tokvec_rerank(h, q_vecs_dev, q_off_dev, w.rows, Q, pool, k, ids_out, nullptr, scores_out, nullptr, st))) return rc;
+    if (!cand_out) return RAG_OK;
+    HIP_TRY(h, hipMemcpyAsync(cand_out, w.cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    return map_rows_to_ids(h, cand_out, P, id_space::of_index(h), st);
 }
 
 // ---- the three-way bge-m3 score over resident data (rag_m3_score_rows_dev, rag_retrieve_m3_dev): upstream's compute_score mode
@@ -519,8 +519,7 @@ __global__ __launch_bounds__(256) void m3_combine_topk_kernel(const int32_t* __r
     }
     __syncthreads();
     if (valid) {
-        int rank = 0;
-        for (int i = 0; i < S; ++i) rank += ok[i] && (s[i] > mine || (s[i] == mine && i < j));
+        const int rank = stable_rank(s, ok, S, j, mine);
         if (rank < k) {
             const size_t o = (size_t)q * k + rank;
             ids_out[o] = id;
@@ -548,20 +547,12 @@ static int m3_check(rag_ctx* h, const char* who, m3_weights w, const float* q_em
     ARG_CHECK(h, w.dense == 0.0 || (q_emb != nullptr && (reinterpret_cast<uintptr_t>(q_emb) & 15) == 0),
               (me + ": a dense weight needs the query embeddings, 16-byte aligned").c_str());
     if (w.sparse > 0.0) {
-        if (sparse_n_docs(h) < 0) {
-            h->err = me + ": no sparse index loaded (rag_sparse_load_host)";
-            return RAG_ERR_STATE;
-        }
-        if (int rc = sparse_fresh(h)) return rc;
-        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, (me + ": the sparse postings must be row-aligned with the index (same number of documents)").c_str());
+        if (int rc = keyword_postings_aligned(h, true, who, RAG_ERR_STATE)) return rc;
         ARG_CHECK(h, term_ptr && qweights, (me + ": a sparse weight needs the query's terms and weights").c_str());
     }
     if (w.colbert > 0.0) {
         if (int rc = tokvec_usable(h, who)) return rc;
-        if (h->tv_docs != h->n_rows) {
-            h->err = me + ": the token-vector store does not hold exactly the index's rows (append the vectors of the inserted rows)";
-            return RAG_ERR_STATE;
-        }
+        if (int rc = tokvec_covers_index(h, who)) return rc;
         ARG_CHECK(h, q_vecs && q_off && (reinterpret_cast<uintptr_t>(q_vecs) & 15) == 0,
                   (me + ": a colbert weight needs the query's token vectors, 16-byte aligned, and their offsets").c_str());
     }
@@ -578,8 +569,9 @@ static int m3_score_slots(rag_ctx* h, m3_weights w, const float* q_emb, const in
     if (w.colbert > 0.0 && (rc = tokvec_score_slots(h, q_vecs, q_off, rows, Q, S, &cb, nullptr, st))) return rc;
     if (w.dense > 0.0 && (rc = dense_cosine_rows(h, q_emb, rows, Q, S, dn, st))) return rc;
     if (w.sparse > 0.0 && (rc = sparse_score_rows_dev(h, term_ptr, terms, qweights, rows, Q, S, sp, st))) return rc;
+    const id_space ids = id_space::of_index(h);
     launch(m3_combine_topk_kernel, dim3((unsigned)Q), dim3(256), 0, st, rows, w.dense > 0.0 ? dn : nullptr, w.sparse > 0.0 ? sp : nullptr, cb, S, k,
-           w.dense, w.sparse, w.colbert, h->ids.get(), h->n_rows, h->id_base, ids_out, rows_out, scores_out, comp_out, cand_out);
+           w.dense, w.sparse, w.colbert, ids.map, h->n_rows, ids.base, ids_out, rows_out, scores_out, comp_out, cand_out);
     return launch_status(h);
 }
 
@@ -593,9 +585,9 @@ int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_pt
     const m3_weights w = {w_dense, w_sparse, w_colbert};
     if (int rc = m3_check(h, "m3_score_rows", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
     const size_t P = (size_t)Q * pool;
-    if (int rc = h->pipe_ws.reserve(h, P * 16 + 256)) return rc;       // workspace: dense [Q][pool] f64 | sparse [Q][pool] f64
-    double* dn = reinterpret_cast<double*>(h->pipe_ws.get());
-    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cand_rows_dev, Q, pool, k, dn, dn + P, ids_out,
+    double *dn, *sp;                                                   // the dense and the sparse component [Q][pool]
+    if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { dn = c.take<double>(P); sp = c.take<double>(P); })) return rc;
+    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cand_rows_dev, Q, pool, k, dn, sp, ids_out,
                           rows_out, scores_out, components_out, nullptr, st);
 }
 
@@ -609,7 +601,7 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
     ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "retrieve_m3: mode is 0 (dense), 1 (dense + sparse RRF) or 2 (union of dense and sparse)");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= (mode == 2 ? RAG_MAX_K / 2 : RAG_MAX_K) && k > 0 && k <= pool,
               "retrieve_m3: 1 <= n_queries <= 65535, 0 < k <= pool <= 256 (mode 2: pool <= 128)");
-    const int S = mode == 2 ? 2 * pool : pool;
+    const int S = cand_slots(mode, pool);
     ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "retrieve_m3: n_queries * candidate slots must be below 2^24");
     ARG_CHECK(h, q_emb_dev && ids_out && scores_out, "retrieve_m3: null argument");
     const m3_weights w = {w_dense, w_sparse, w_colbert};
@@ -617,42 +609,18 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_m3: tenant filter requested but no tenants loaded");
     if (mode != 0) {
         ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_m3: modes 1 and 2 need the query's terms and weights");
-        if (sparse_n_docs(h) < 0) {
-            h->err = "retrieve_m3: no sparse index loaded (rag_sparse_load_host)";
-            return RAG_ERR_STATE;
-        }
-        if (int rc = sparse_fresh(h)) return rc;
-        ARG_CHECK(h, sparse_n_docs(h) == h->n_rows, "retrieve_m3: the sparse postings must be row-aligned with the index (same number of documents)");
+        if (int rc = keyword_postings_aligned(h, true, "retrieve_m3", RAG_ERR_STATE)) return rc;
     }
     const size_t P = (size_t)Q * pool, PS = (size_t)Q * S;
-    // workspace: lists [2][Q][pool] i64 | scores [Q][pool] f64 | cand [Q][S] i64 | rrf [Q][S] f64 | ranks [Q][S][2] i32 | dense [Q][S] f64
-    //            | sparse [Q][S] f64 | rows [Q][S] i32
-    const size_t need = P * (16 + 8) + PS * (8 + 8 + 8 + 8 + 8 + 4) + 256;
-    if (int rc = h->pipe_ws.reserve(h, need)) return rc;
-    char* p = h->pipe_ws;
-    int64_t* lists = (int64_t*)p;              p += P * 16;
-    double* sc = (double*)p;                   p += P * 8;
-    int64_t* cand = (int64_t*)p;               p += PS * 8;
-    double* rrf = (double*)p;                  p += PS * 8;
-    int32_t* ranks = (int32_t*)p;              p += PS * 8;
-    double* dn = (double*)p;                   p += PS * 8;
-    double* sp = (double*)p;                   p += PS * 8;
-    int32_t* rows = (int32_t*)p;
-    dev_buf<int64_t> ids_saved = std::move(h->ids);
-    const int64_t id_base_saved = h->id_base;
-    h->id_base = 0;
-    int rc;
-    if (mode == 0) {
-        rc = dense_search(h, q_emb_dev, Q, pool, tenant, cand, nullptr, sc, st);
-    } else {
-        rc = hybrid_legs(h, q_emb_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists, sc, st, {nullptr, nullptr}, qweights_dev);
-        if (!rc) rc = rrf_fuse_dev(h, lists, Q, 2, pool, (int64_t)P, pool, rrf_k, S, cand, rrf, ranks, st);
-    }
-    h->ids = std::move(ids_saved);
-    h->id_base = id_base_saved;
+    cand_ws cw;
+    double *dn, *sp;                                                   // the dense and the sparse component [Q][S]
+    int rc = pipe_ws_carve(h, [&](ws_carve& c) {
+        cand_ws_planes(c, cw, P, PS, true);
+        dn = c.take<double>(PS);
+        sp = c.take<double>(PS);
+    });
     if (rc) return rc;
-    launch(rows_narrow_kernel, dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st, cand, rows, (int64_t)PS);
-    if ((rc = launch_status(h))) return rc;
-    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, rows, Q, S, k, dn, sp, ids_out, nullptr,
+    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, {nullptr, nullptr}, mode, cw, st))) return rc;
+    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cw.rows, Q, S, k, dn, sp, ids_out, nullptr,
                           scores_out, components_out, cand_out, st);
 }

@@ -409,6 +409,11 @@ int tokvec_usable(rag_ctx* h, const char* who) {
     }
     return RAG_OK;
 }
+int tokvec_covers_index(rag_ctx* h, const char* who) {
+    if (h->tv_docs == h->n_rows) return RAG_OK;
+    h->err = std::string(who) + ": the token-vector store does not hold exactly the index's rows (append the vectors of the inserted rows)";
+    return RAG_ERR_STATE;
+}
 
 // the MaxSim launch alone over [Q][pool] slots (the caller has checked the store and the shape): *scores_out / *slots_out point into
 // the handle's tv_ws - every slot's float32 score, and the row it was scored for or -1

@@ -407,6 +407,38 @@ def test_limits_and_missing_pieces(full):
         e.close()
 
 
+def test_a_refused_composite_leaves_the_handles_id_mapping_alone():
+    """64 rows with explicit ids: each of the three resident composites is refused by a state or an argument check, and the dense
+    search that follows on the same handle still reports the explicit ids (the composites run their candidate stage in row space)"""
+    import torch
+    from optimized_rag_amd import RagEngine, RagError
+    w = F.world()
+    d = T.to_dev(_dev_inputs())
+    q_tok = torch.ones((32, 8), dtype=torch.int32, device="cuda")
+    q_len = torch.full((32,), 8, dtype=torch.int32, device="cuda")
+    e = RagEngine(dim=F.DIM, device=0)
+    try:
+        _load(e, np.arange(64), sparse=False, tokvec=False, tenants=False)
+
+        def refused(code, call):
+            with pytest.raises(RagError, match=code):
+                call()
+            ids, rows, _ = e.dense_topk(np.array(w["q_emb"]), 4)
+            assert (rows >= 0).all() and (rows < 64).all()
+            np.testing.assert_array_equal(ids, w["ids"][rows])
+
+        refused(ERR_ARG, lambda: e.retrieve_rerank_dev(d["q_emb"], q_tok, q_len, 8, 4))              # no cross-encoder
+        refused(ERR_STATE, lambda: e.retrieve_maxsim_dev(d["q_emb"], d["qv"], d["qo"], 8, 4))         # no token-vector store
+        refused(ERR_STATE, lambda: _composite(e, 1, pool=8, k=4))                                     # no sparse index
+        e.tokvec_load(*F.vecs_of_rows(np.arange(10)))                                                 # 10 documents beside 64 rows
+        refused(ERR_STATE, lambda: e.retrieve_maxsim_dev(d["q_emb"], d["qv"], d["qo"], 8, 4))
+        refused(ERR_STATE, lambda: _composite(e, 0, weights=(0.4, 0.0, 0.4), pool=8, k=4))
+        refused(ERR_ARG, lambda: e.retrieve_maxsim_dev(d["q_emb"], d["qv"], d["qo"], 257, 4))
+        refused(ERR_ARG, lambda: _composite(e, 2, weights=(1.0, 0.0, 0.0), pool=129, k=4))
+    finally:
+        e.close()
+
+
 # ---- 5. live writes -----------------------------------------------------------------------------------------------------------------
 def test_live_writes_keep_the_three_way_score_current():
     from optimized_rag_amd import RagEngine
