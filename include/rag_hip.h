@@ -29,7 +29,7 @@
  *     call, nor to any *_dev call). So a *_dev call queued before a host search or a host write (rag_index_set_tenants_host,
  *     rag_index_set_ids_host, rag_index_set_temporal_host, rag_tokens_load_host, rag_tokens_reserve, rag_tokens_load_wide_host,
  *     rag_tokens_reserve_wide, rag_bm25_load_host, rag_sparse_load_host, rag_tokvec_reserve, rag_tokvec_load_host,
- *     rag_tokvec_append_host,
+ *     rag_tokvec_append_host, rag_tokvec_reserve_form, rag_tokvec_load_form_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
  *     rag_sparse_append_host, rag_sparse_fold, rag_index_compact_bm25, rag_index_compact_live, rag_index_load_host, rag_index_reserve,
  *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
@@ -792,8 +792,32 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
  *   Deletes need nothing: the composite's searches hide deleted rows, and the explicit-row entries do not look.
  * Ordering: reserve / load / append_host / fetch / rerank_host are host calls (they wait for queued *_dev work); the _dev calls
  *   follow the preamble, rag_tokvec_append_dev waiting for `stream` as said.
- * Sharding: raw MaxSim scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev. */
+ * Sharding: raw MaxSim scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev.
+ * Storage forms. A store is reserved in one of two forms; RAG_TOKVEC_FP16 (the default, everything above) or RAG_TOKVEC_MXFP8:
+ *   OCP MXFP8, E4M3 codes with one shared power-of-two scale per 32 consecutive components, 33/64 of the fp16 form's passage
+ *   bytes. For a block with amax = max |x|: the scale exponent e is the smallest integer with amax <= 448 * 2^e, clamped to
+ *   [-15, 7] (e = -15 for an all-zero block), stored as one E8M0 byte e + 127. Each component is stored as E4M3(x * 2^-e) in the
+ *   "FN" encoding (max 448, no infinities): round to nearest even, subnormals kept, a magnitude above 448 after scaling (possible
+ *   only at the e = 7 clamp, amax > 57344) saturates to 448, the NaN codes are never stored, the sign of zero is kept. The stored
+ *   value is code * 2^e. The clamps make every stored value an exact fp16 value (smallest step 2^-24, largest magnitude
+ *   448 * 128 = 57344, at most 4 significant bits), and quantising stored values returns them unchanged.
+ *   rag_tokvec_reserve_form: rag_tokvec_reserve with the form (rag_tokvec_reserve is form 0); an unknown form is RAG_ERR_ARG and
+ *   leaves an earlier store as it is. rag_tokvec_load_form_host: reserve_form + append_host. rag_tokvec_form: the form of the
+ *   store, -1 without one; host state only. rag_tokvec_append_* quantise on the device into the reserved form and reject exactly
+ *   the blocks the fp16 form rejects (NaN, inf, |x| >= 65520; 65504 ... 65519 saturate to 57344). rag_tokvec_fetch_host returns
+ *   code * 2^e as float32, exact. rag_tokvec_info's hbm_bytes is what is allocated: a row is dim code bytes, then its dim / 32 scale
+ *   bytes, padded to a multiple of 16 bytes (at most 15 bytes of padding per row). Every rerank and composite entry serves either
+ *   form without a new argument; the stored values are expanded to the fp16 operand exactly, so a pair's score is BIT-IDENTICAL
+ *   to the fp16 form's score over a store loaded with the fetched rows: within 1e-4 of float64 MaxSim over the stored vectors.
+ *   Against the ORIGINAL float32 unit rows: a component at or above the block's smallest normal 2^(e - 6) moves by at most
+ *   2^-4 |x|, a smaller one by at most 2^(e - 10) <= 2^-18 amax, a dot of unit rows by at most 2^-4 + 2^-13 (typical: a few 1e-3,
+ *   DESIGN.md section 4.5). rag_index_compact_live moves the stored bytes, scales with their rows, never requantised. */
+#define RAG_TOKVEC_FP16 0
+#define RAG_TOKVEC_MXFP8 1
 int rag_tokvec_reserve(rag_handle_t h, int64_t n_docs_total, int64_t rows_total, int dim);
+int rag_tokvec_reserve_form(rag_handle_t h, int64_t n_docs_total, int64_t rows_total, int dim, int form);
+int rag_tokvec_load_form_host(rag_handle_t h, const float* vecs_host, const int64_t* off_host, int64_t n_docs, int dim, int form);
+int rag_tokvec_form(rag_handle_t h, int* form_out);
 int rag_tokvec_append_dev(rag_handle_t h, const float* vecs_dev, const int64_t* row_off_dev, int64_t n_docs, void* stream);
 int rag_tokvec_append_host(rag_handle_t h, const float* vecs_host, const int64_t* row_off_host, int64_t n_docs);
 int rag_tokvec_load_host(rag_handle_t h, const float* vecs_host, const int64_t* off_host, int64_t n_docs, int dim);

@@ -157,6 +157,9 @@ _SIGS = {
     "rag_lexical_match_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P], C.c_int),
     "rag_lexical_match_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P], C.c_int),
     "rag_tokvec_reserve": ([_P, C.c_int64, C.c_int64, C.c_int], C.c_int),
+    "rag_tokvec_reserve_form": ([_P, C.c_int64, C.c_int64, C.c_int, C.c_int], C.c_int),
+    "rag_tokvec_load_form_host": ([_P, _P, _P, C.c_int64, C.c_int, C.c_int], C.c_int),
+    "rag_tokvec_form": ([_P, C.POINTER(C.c_int)], C.c_int),
     "rag_tokvec_append_dev": ([_P, _P, _P, C.c_int64, _P], C.c_int),
     "rag_tokvec_append_host": ([_P, _P, _P, C.c_int64], C.c_int),
     "rag_tokvec_load_host": ([_P, _P, _P, C.c_int64, C.c_int], C.c_int),
@@ -1023,10 +1026,28 @@ class RagEngine:
                                                    pair_q.shape[0], _ptr(sk), sk.shape[0], p(out), st), "rag_lexical_match_dev")
 
     # ---- resident token-vector store and late-interaction rerank (rag_tokvec_*, rag_retrieve_maxsim_dev) ---------
-    def tokvec_reserve(self, n_docs_total, rows_total, dim):
-        """Room for n_docs_total documents and rows_total fp16 token-vector rows of `dim`; replaces any earlier store."""
-        self._check(self.lib.rag_tokvec_reserve(self.h, int(n_docs_total), int(rows_total), int(dim)), "rag_tokvec_reserve")
+    TOKVEC_FORMS = {"fp16": 0, "mxfp8": 1}
+
+    def _tokvec_form_code(self, form, what):
+        """"fp16" / "mxfp8" -> RAG_TOKVEC_*; an integer goes to the library as it is (which rejects one it does not know)"""
+        if isinstance(form, str):
+            if form not in self.TOKVEC_FORMS:
+                raise RagError(f"{what}: unknown form {form!r} (one of {sorted(self.TOKVEC_FORMS)})")
+            return self.TOKVEC_FORMS[form]
+        return int(form)
+
+    def tokvec_reserve(self, n_docs_total, rows_total, dim, form="fp16"):
+        """Room for n_docs_total documents and rows_total token-vector rows of `dim`; replaces any earlier store. form "fp16" (2 B
+        per component) or "mxfp8" (E4M3 codes with a power-of-two scale per 32 components: 33/64 of the bytes, for capacity)."""
+        self._check(self.lib.rag_tokvec_reserve_form(self.h, int(n_docs_total), int(rows_total), int(dim),
+                                                     self._tokvec_form_code(form, "tokvec_reserve")), "rag_tokvec_reserve_form")
         self._tv_dim = int(dim)
+
+    def tokvec_form(self):
+        """"fp16" or "mxfp8": the form of the resident token-vector store; None without one."""
+        f = C.c_int()
+        self._check(self.lib.rag_tokvec_form(self.h, C.byref(f)), "rag_tokvec_form")
+        return {v: k for k, v in self.TOKVEC_FORMS.items()}.get(int(f.value))
 
     def _tokvec_dim_check(self, width, what):
         if int(width) != getattr(self, "_tv_dim", int(width)):
@@ -1062,12 +1083,13 @@ class RagEngine:
         self._check(self.lib.rag_tokvec_append_dev(self.h, C.c_void_p(vecs.data_ptr()), C.c_void_p(row_off.data_ptr()), n, st),
                     "rag_tokvec_append_dev")
 
-    def tokvec_load(self, vecs, offsets):
-        """reserve + append of a whole store from host arrays: float32 [rows, dim], int64 offsets [n_docs + 1]."""
+    def tokvec_load(self, vecs, offsets, form="fp16"):
+        """reserve + append of a whole store from host arrays: float32 [rows, dim], int64 offsets [n_docs + 1]; form as tokvec_reserve."""
         v, off = _np(vecs, np.float32), _np(offsets, np.int64)
         if v.ndim != 2 or off.ndim != 1 or off.shape[0] < 2 or int(off[-1]) > v.shape[0]:
             raise RagError("tokvec_load: expected vectors [rows, dim] and offsets [n_docs + 1] that end inside them")
-        self._check(self.lib.rag_tokvec_load_host(self.h, _ptr(v), _ptr(off), off.shape[0] - 1, int(v.shape[1])), "rag_tokvec_load_host")
+        self._check(self.lib.rag_tokvec_load_form_host(self.h, _ptr(v), _ptr(off), off.shape[0] - 1, int(v.shape[1]),
+                                                       self._tokvec_form_code(form, "tokvec_load")), "rag_tokvec_load_form_host")
         self._tv_dim = int(v.shape[1])
 
     def tokvec_info(self):
@@ -1077,7 +1099,7 @@ class RagEngine:
         return {"n_docs": int(docs.value), "rows": int(rows.value), "dim": int(dim.value), "hbm_bytes": int(nb.value)}
 
     def tokvec_fetch(self, doc):
-        """The stored (fp16-rounded) rows of one document as float32 [n, dim]."""
+        """The stored (fp16-rounded, or code * 2^e of the 8-bit form) rows of one document as float32 [n, dim]."""
         dim = self.tokvec_info()["dim"]
         n = C.c_int64()
         rc = self.lib.rag_tokvec_fetch_host(self.h, int(doc), None, 0, C.byref(n))

@@ -1081,7 +1081,14 @@ int rag_tokvec_reserve(rag_handle_t h, int64_t n_docs_total, int64_t rows_total,
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);                      // queued *_dev reranks read the store this call replaces
-    return tokvec_reserve(h, n_docs_total, rows_total, dim);
+    return tokvec_reserve(h, n_docs_total, rows_total, dim, RAG_TOKVEC_FP16);
+}
+
+int rag_tokvec_reserve_form(rag_handle_t h, int64_t n_docs_total, int64_t rows_total, int dim, int form) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_reserve(h, n_docs_total, rows_total, dim, form);
 }
 
 int rag_tokvec_append_dev(rag_handle_t h, const float* vecs_dev, const int64_t* row_off_dev, int64_t n_docs, void* stream) {
@@ -1102,13 +1109,26 @@ int rag_tokvec_load_host(rag_handle_t h, const float* vecs_host, const int64_t* 
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return tokvec_load_host(h, vecs_host, off_host, n_docs, dim);
+    return tokvec_load_host(h, vecs_host, off_host, n_docs, dim, RAG_TOKVEC_FP16);
+}
+
+int rag_tokvec_load_form_host(rag_handle_t h, const float* vecs_host, const int64_t* off_host, int64_t n_docs, int dim, int form) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return tokvec_load_host(h, vecs_host, off_host, n_docs, dim, form);
 }
 
 int rag_tokvec_info(rag_handle_t h, int64_t* n_docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     return tokvec_info(h, n_docs_out, rows_out, dim_out, hbm_bytes_out);
+}
+
+int rag_tokvec_form(rag_handle_t h, int* form_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    return tokvec_form(h, form_out);
 }
 
 int rag_tokvec_fetch_host(rag_handle_t h, int64_t doc, float* out_host, int64_t cap_rows, int64_t* n_rows_out) {

@@ -140,7 +140,8 @@ struct rag_device_mem : rag_index_mem {
     dev_buf<int32_t> qten;           // [>= n_queries]
     dev_buf<int32_t> union_tiles;    // [<= tiles of the index]
     // resident token-vector store (tokvec.hip): packed fp16 rows, document i = rows [tv_off[i], tv_off[i + 1]) = row i of the index
-    dev_buf<half_t> tv;              // [tv_rows_cap][tv_dim]
+    dev_buf<half_t> tv;              // [tv_rows_cap][tv_dim] (form RAG_TOKVEC_FP16)
+    dev_buf<uint8_t> tv8;            // form RAG_TOKVEC_MXFP8: [tv_rows_cap] rows of tokvec_row_bytes: dim E4M3 codes | dim / 32 E8M0 scales | pad to 16 B
     dev_buf<int64_t> tv_off;         // [tv_docs_cap + 1], tv_off[0] = 0
     dev_buf<int> tv_bad;             // [2] device counters of one append: values that are not finite as fp16, decreasing offsets
     dev_buf<char> tv_ws;             // rag_tokvec_rerank_*: pair scores float32 [Q][pool] | scored rows int32 [Q][pool] (-1 = empty slot)
@@ -205,6 +206,7 @@ struct rag_ctx : rag_device_mem {
     int64_t tv_docs = 0, tv_rows = 0;        // token-vector store: documents / rows appended so far ...
     int64_t tv_docs_cap = 0, tv_rows_cap = 0;    // ... and reserved (rag_tokvec_reserve); tv_docs_cap > 0 = a store exists
     int tv_dim = 0;
+    int tv_form = 0;                         // RAG_TOKVEC_FP16 / RAG_TOKVEC_MXFP8, chosen by the reserve
     bool tv_stale = false;                   // a compaction renumbered the rows since the store was filled: its entries refuse until a reload
     int pair_format = RAG_PAIR_BERT;         // rag_ce_set_pair_format: read while a pair-building call enqueues
     // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: remembered per handle, not per process. raise_lds: the
@@ -555,10 +557,11 @@ int lexical_match_dev(rag_ctx* h, const int32_t* q_ids, const float* q_w, const 
                       const int32_t* skip_ids_host, int n_skip, float* out, hipStream_t st);
 // tokvec.hip: the resident token-vector store and MaxSim rerank over it. tokvec_rerank checks the store and its arguments, scores
 // [Q][pool] slots and selects through tokvec_topk (pipeline.hip: the kernel behind rag_rerank_topk_dev, without the sigmoid).
-int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim);
+int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim, int form);
 int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t n_docs, hipStream_t st, bool host_ptrs);
-int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim);
+int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim, int form);
 int tokvec_info(const rag_ctx* h, int64_t* docs_out, int64_t* rows_out, int* dim_out, int64_t* hbm_bytes_out);
+int tokvec_form(const rag_ctx* h, int* form_out);             // RAG_TOKVEC_*, -1 without a store
 int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int64_t* n_rows_out);
 // the store through a compaction (rag_index_compact_live): everything allocated by tokvec_compact_prepare before a row of any
 // plane moves; tokvec_compact_commit moves the rows in place through the compaction's staging buffer and swaps the offsets in

@@ -3,6 +3,7 @@
 // packed fp16 rows [rows][dim] with int64 offsets [docs + 1]; document i is row i of the dense index. A query then costs one
 // embedder forward (its own), and a rerank reads half the bytes rag_maxsim_* reads for the same pairs.
 //   tokvec_convert_kernel     float32 -> fp16, round to nearest even (v_cvt_f16_f32), counting values that are not finite as fp16
+//   tokvec_quant8_kernel      float32 -> block amax, scale exponent, E4M3 codes and the E8M0 scale byte; the same count
 //   tokvec_offsets_kernel     a block's offsets, relative to its first, behind the store's; counting decreasing ones
 //   tokvec_maxsim_kernel      score[q][j] = (1 / nq) * sum_i max_r <vq[i], store[cand[q][j]][r]>
 //
@@ -20,6 +21,11 @@
 // function of the document's own row count, and either gives every accumulator the same MFMA sequence: the same bits.
 // The loads of K-step k + 1 are requested before the MFMAs of step k. Per-wave maxima meet in LDS and one thread sums them in
 // query order in float64: no atomics; a pair's score is a function of its own rows, bit-identical whatever surrounds it.
+// A store is reserved in one of two forms (tokvec_reserve's `form`): the fp16 rows above, or RAG_TOKVEC_MXFP8 - E4M3 codes with one
+// power-of-two scale per 32 components, 33/64 of the bytes ("the 8-bit form" below: tokvec_quant8_kernel beside the convert
+// kernel, tv_doc<FORM> for the scoring kernel's document operand, both instantiations of tokvec_maxsim_kernel<FORM>). Every stored
+// value of the 8-bit form is an fp16 value and is expanded to the same half8, so its scores are the fp16 form's bits over the
+// fetched rows; the fp16 instantiation is the kernel as it was (62 SGPR, 104 VGPR, 40 AGPR, no scratch).
 #include "common.h"
 
 #include <algorithm>
@@ -45,6 +51,98 @@ __global__ __launch_bounds__(256) void tokvec_offsets_kernel(const int64_t* __re
     dst[i] = base + (off[i + 1] - off[0]);
 }
 
+// ---- the 8-bit form (RAG_TOKVEC_MXFP8; the contract is in include/rag_hip.h) --------------------------------------------------
+// A stored row is tokvec_row_bytes bytes: dim E4M3 ("FN": max 448, no infinities) codes, then dim / 32 E8M0 scale bytes (e + 127, one
+// per block of 32 consecutive components), then zero to 15 bytes that nobody reads, so that every row starts on a 16-byte boundary
+// and a row is a whole number of the 16-byte units the compaction moves. value = code * 2^e, e in [-15, 7]: exact in fp16.
+__host__ __device__ __forceinline__ int tokvec_row_bytes(int dim, int form) {
+    return form == RAG_TOKVEC_MXFP8 ? (dim + dim / 32 + 15) & ~15 : dim * (int)sizeof(half_t);
+}
+
+// One thread per 8 consecutive floats, four neighbouring lanes per block of 32 (n is a multiple of 32 and a workgroup starts on a
+// block, so the four are in or out together). `first` is the position of in[0], in floats, behind the first row at `out`.
+// e = the smallest integer with amax <= 448 * 2^e = 1.75 * 2^(8 + e): floor(log2 amax) - 8, one more when the mantissa is above
+// 1.75, clamped to [-15, 7] (zero and float32 subnormals land on -15). x * 2^-e is exact; its magnitude, cut at 448, is rounded to
+// nearest even on the E4M3 grid in integer arithmetic on the float's bits (at or above 2^-6: 3 mantissa bits kept, the carry
+// running into the exponent) or as a multiple of 2^-9 below (rintf; 8 * 2^-9 is the code of 2^-6). The sign bit is x's, zero included.
+__global__ __launch_bounds__(256) void tokvec_quant8_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int64_t first, int64_t n,
+                                                             int dim, int stride, int* __restrict__ bad) {
+    const int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+    if (t >= n) return;
+    float v[8];
+    float amax = 0.f;
+    int nbad = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        v[i] = in[t + i];
+        if (!(fabsf((float)(half_t)v[i]) <= 65504.f)) ++nbad;   // what the fp16 form rejects: NaN, inf, |x| >= 65520
+        amax = fmaxf(amax, fabsf(v[i]));
+    }
+    if (nbad) atomicAdd(bad, nbad);
+    amax = fmaxf(amax, __shfl_xor(amax, 1));
+    amax = fmaxf(amax, __shfl_xor(amax, 2));
+    const unsigned ab = __float_as_uint(amax);
+    int e = (int)(ab >> 23) - 127 - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
+    e = e < -15 ? -15 : e > 7 ? 7 : e;
+    const float inv = __uint_as_float((unsigned)(127 - e) << 23);
+    unsigned w[2] = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float y = v[i] * inv;
+        const float a = fminf(fabsf(y), 448.f);
+        unsigned code;
+        if (a >= 0.015625f) {
+            unsigned b = __float_as_uint(a);
+            b += 0x7ffffu + ((b >> 20) & 1u);
+            code = ((((b >> 23) - 120u) << 3) | ((b >> 20) & 7u)) & 0x7fu;
+        } else {
+            code = (unsigned)rintf(a * 512.f);
+        }
+        code |= (__float_as_uint(y) >> 24) & 0x80u;
+        w[i >> 2] |= code << (8 * (i & 3));
+    }
+    const int64_t g = first + t, row = g / dim;
+    const int col = (int)(g - row * dim);
+    uint8_t* rp = out + row * stride;
+    *reinterpret_cast<uint2*>(rp + col) = make_uint2(w[0], w[1]);
+    if ((col & 31) == 0) rp[dim + (col >> 5)] = (uint8_t)(e + 127);
+}
+
+// The document operand of a lane - 8 consecutive k of one row - per form: where it lies, what a load brings, and the half8 the MFMA
+// reads. fp16: 16 bytes per K-step, as stored. 8-bit: 8 code bytes and the block's scale byte (the four fq lanes of a row read the
+// same one), expanded by v_cvt_scalef32_pk_f16_fp8 with the scale 2^e as a float; every stored value is an fp16 value, so the
+// expansion is exact and the operand is the one the fp16 form holds for the fetched rows. The 8-bit form loads TWO K-steps at a
+// time (tv_query_block_q8): 2 x 8 code bytes and the two scale bytes as one 16-bit load, so that a lane has as many passage bytes
+// in flight as the fp16 form's 16-byte load - with one step in flight the 8-bit kernel was slower than the fp16 one.
+template <int FORM> struct tv_doc;
+template <> struct tv_doc<RAG_TOKVEC_FP16> {
+    typedef half_t elem;
+    typedef half8 raw;
+    static __device__ __forceinline__ int64_t stride(int dim) { return dim; }                   // in elem
+    static __device__ __forceinline__ raw load(const elem* __restrict__ p, int k, int dim, int fq) { return *reinterpret_cast<const half8*>(p + k); }
+    static __device__ __forceinline__ half8 expand(const raw& r) { return r; }
+};
+typedef _Float16 tv_half2 __attribute__((ext_vector_type(2)));
+struct tv_raw_q8 { uint2 c0, c1; unsigned s; };       // the codes of K-steps k and k + 32, their scale bytes in bits 0-7 and 8-15
+template <> struct tv_doc<RAG_TOKVEC_MXFP8> {
+    typedef uint8_t elem;
+    typedef tv_raw_q8 raw;
+    static __device__ __forceinline__ int64_t stride(int dim) { return tokvec_row_bytes(dim, RAG_TOKVEC_MXFP8); }
+    // p = the row + 8 fq; k a multiple of 64, k1 the second step (clamped by the caller to the row). The 16-bit scale load is
+    // aligned (dim and k / 32 are even) and inside the row: when the second scale byte is not one of the row's dim / 32, that
+    // count is odd, dim + dim / 32 is odd, and the byte is the first of the padding to 16
+    static __device__ __forceinline__ raw load(const elem* __restrict__ p, int k, int k1, int dim, int fq) {
+        return {*reinterpret_cast<const uint2*>(p + k), *reinterpret_cast<const uint2*>(p + k1),
+                (unsigned)*reinterpret_cast<const uint16_t*>(p + (dim - fq * 8 + (k >> 5)))};
+    }
+    static __device__ __forceinline__ half8 expand(const uint2& c, unsigned s) {
+        const float sc = __uint_as_float(s << 23);              // E8M0 byte -> 2^(s - 127)
+        const tv_half2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c.x, sc, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c.x, sc, true);
+        const tv_half2 e = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c.y, sc, false), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c.y, sc, true);
+        return (half8){a[0], a[1], b[0], b[1], e[0], e[1], d[0], d[1]};
+    }
+};
+
 struct tv_raw8 { float4 a, b; };             // a lane's 8 consecutive floats of one query row
 __device__ __forceinline__ tv_raw8 tv_load8(const float* __restrict__ p) {
     return {*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4)};
@@ -60,42 +158,45 @@ __device__ __forceinline__ void tv_split8(const tv_raw8& r, half8& hi, half8& lo
 
 // one block of TV_QT * 16 query rows against every document tile group of this wave, DT tiles at a time: best[j] = the maximum over
 // the wave's document rows for query row 16 j + fr (in the lanes of every fq, before the cross-lane steps)
-template <int DT>
-__device__ __forceinline__ void tv_query_block(const half_t* __restrict__ doc, int64_t nd, int64_t nd_tiles, const float* const (&qp)[TV_QT],
+template <int DT, int FORM>
+__device__ __forceinline__ void tv_query_block(const typename tv_doc<FORM>::elem* __restrict__ doc, int64_t nd, int64_t nd_tiles, const float* const (&qp)[TV_QT],
                                                int dim, int wv, int fr, int fq, float (&best)[TV_QT]) {
     for (int64_t dt0 = (int64_t)wv * DT; dt0 < nd_tiles; dt0 += 4 * DT) {
-        const half_t* dp[DT];
+        typedef tv_doc<FORM> D;
+        const typename D::elem* dp[DT];
 #pragma unroll
-        for (int t = 0; t < DT; ++t) dp[t] = doc + min((dt0 + t) * 16 + fr, nd - 1) * dim + fq * 8;
+        for (int t = 0; t < DT; ++t) dp[t] = doc + min((dt0 + t) * 16 + fr, nd - 1) * D::stride(dim) + fq * 8;
         f32x4 acc[DT][TV_QT];
 #pragma unroll
         for (int t = 0; t < DT; ++t)
 #pragma unroll
             for (int j = 0; j < TV_QT; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        half8 dr[DT];
+        typename D::raw dr[DT];
         tv_raw8 qr[TV_QT];
 #pragma unroll
-        for (int t = 0; t < DT; ++t) dr[t] = *reinterpret_cast<const half8*>(dp[t]);
+        for (int t = 0; t < DT; ++t) dr[t] = D::load(dp[t], 0, dim, fq);
 #pragma unroll
         for (int j = 0; j < TV_QT; ++j) qr[j] = tv_load8(qp[j]);
         for (int k = 0; k < dim; k += 32) {
             const int kn = k + 32 < dim ? k + 32 : k;          // the last step re-reads itself: no branch around the loads
-            half8 dn[DT];
+            typename D::raw dn[DT];
             tv_raw8 qn[TV_QT];
 #pragma unroll
-            for (int t = 0; t < DT; ++t) dn[t] = *reinterpret_cast<const half8*>(dp[t] + kn);
+            for (int t = 0; t < DT; ++t) dn[t] = D::load(dp[t], kn, dim, fq);
 #pragma unroll
             for (int j = 0; j < TV_QT; ++j) qn[j] = tv_load8(qp[j] + kn);
             half8 bh[TV_QT], bl[TV_QT];
 #pragma unroll
             for (int j = 0; j < TV_QT; ++j) tv_split8(qr[j], bh[j], bl[j]);
 #pragma unroll
-            for (int t = 0; t < DT; ++t)
+            for (int t = 0; t < DT; ++t) {
+                const half8 da = D::expand(dr[t]);
 #pragma unroll
                 for (int j = 0; j < TV_QT; ++j) {
-                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(dr[t], bl[j], acc[t][j], 0, 0, 0);
-                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(dr[t], bh[j], acc[t][j], 0, 0, 0);
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bl[j], acc[t][j], 0, 0, 0);
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bh[j], acc[t][j], 0, 0, 0);
                 }
+            }
 #pragma unroll
             for (int t = 0; t < DT; ++t) dr[t] = dn[t];
 #pragma unroll
@@ -113,10 +214,93 @@ __device__ __forceinline__ void tv_query_block(const half_t* __restrict__ doc, i
     }
 }
 
+// The same for the 8-bit form, two K-steps per iteration. Every accumulator sees the MFMAs of tv_query_block in the same order -
+// per step lo_q * d then hi_q * d, steps ascending - on the same operands: the same bits. The loads of the NEXT pair of steps (and
+// the query rows of the step after the current one) are requested before the current step's MFMAs. A dim of an odd number of steps
+// (32, 96, ...) ends on a half pair: its second step is skipped (uniform over the grid), its loads re-read the last step.
+// Where the compiler puts the requests: it sinks the second step's query loads into that step's branch and waits there with
+// vmcnt(0), which also waits for the next pair's passage bytes - so the passage loads get about one step to arrive, not two.
+// Forms that pin the order (scheduling barriers; a loop over whole pairs without the branch; single steps with three register
+// stages) were compiled and cost the third wave per SIMD (170 VGPR) or waited at the loop top for the youngest stage; none was
+// measured faster, none is kept. DESIGN 4.5 "8-bit token vectors" has the times.
+template <int DT>
+__device__ __forceinline__ void tv_query_block_q8(const uint8_t* __restrict__ doc, int64_t nd, int64_t nd_tiles, const float* const (&qp)[TV_QT],
+                                                  int dim, int wv, int fr, int fq, float (&best)[TV_QT]) {
+    typedef tv_doc<RAG_TOKVEC_MXFP8> D;
+    const int last = dim - 32;
+    for (int64_t dt0 = (int64_t)wv * DT; dt0 < nd_tiles; dt0 += 4 * DT) {
+        const uint8_t* dp[DT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t) dp[t] = doc + min((dt0 + t) * 16 + fr, nd - 1) * D::stride(dim) + fq * 8;
+        f32x4 acc[DT][TV_QT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        D::raw dr[DT];
+        tv_raw8 qr[TV_QT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t) dr[t] = D::load(dp[t], 0, min(32, last), dim, fq);
+#pragma unroll
+        for (int j = 0; j < TV_QT; ++j) qr[j] = tv_load8(qp[j]);
+        for (int k = 0; k < dim; k += 64) {
+            const int k1 = min(k + 32, last);                  // this pair's second step
+            const int kn = k + 64 < dim ? k + 64 : k;          // the next pair; the last one re-reads itself: no branch around the loads
+            D::raw dn[DT];
+            tv_raw8 q1[TV_QT], qn[TV_QT];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) q1[j] = tv_load8(qp[j] + k1);
+#pragma unroll
+            for (int t = 0; t < DT; ++t) dn[t] = D::load(dp[t], kn, min(kn + 32, last), dim, fq);
+            half8 bh[TV_QT], bl[TV_QT];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) tv_split8(qr[j], bh[j], bl[j]);
+#pragma unroll
+            for (int t = 0; t < DT; ++t) {
+                const half8 da = D::expand(dr[t].c0, dr[t].s & 0xffu);
+#pragma unroll
+                for (int j = 0; j < TV_QT; ++j) {
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bl[j], acc[t][j], 0, 0, 0);
+                    acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bh[j], acc[t][j], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) qn[j] = tv_load8(qp[j] + kn);
+            if (k + 32 < dim) {
+#pragma unroll
+                for (int j = 0; j < TV_QT; ++j) tv_split8(q1[j], bh[j], bl[j]);
+#pragma unroll
+                for (int t = 0; t < DT; ++t) {
+                    const half8 da = D::expand(dr[t].c1, dr[t].s >> 8);
+#pragma unroll
+                    for (int j = 0; j < TV_QT; ++j) {
+                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bl[j], acc[t][j], 0, 0, 0);
+                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, bh[j], acc[t][j], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < DT; ++t) dr[t] = dn[t];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) qr[j] = qn[j];
+        }
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((dt0 + t) * 16 + fq * 4 + r < nd) {
+#pragma unroll
+                    for (int j = 0; j < TV_QT; ++j) best[j] = fmaxf(best[j], acc[t][j][r]);
+                }
+    }
+}
+
 // grid = Q * pool workgroups. slot[q][j] = the row that was scored, or -1 for an empty slot (score 0.0): cand < 0, a row at or past
 // the store's documents, a document without rows, a query without rows.
+template <int FORM>
 __global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restrict__ q, const int64_t* __restrict__ q_off,
-                                                             const half_t* __restrict__ store, const int64_t* __restrict__ d_off, int64_t n_docs,
+                                                             const typename tv_doc<FORM>::elem* __restrict__ store,
+                                                             const int64_t* __restrict__ d_off, int64_t n_docs,
                                                              const int32_t* __restrict__ cand, int pool, int dim, float* __restrict__ out,
                                                              int32_t* __restrict__ slot) {
     __shared__ float wmax[4][TV_QT * 16];
@@ -138,7 +322,7 @@ __global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restr
         return;
     }
     const int64_t nd_tiles = (nd + 15) >> 4;
-    const half_t* doc = store + d0 * dim;
+    const typename tv_doc<FORM>::elem* doc = store + d0 * tv_doc<FORM>::stride(dim);
     double total = 0.0;                                        // thread 0 alone
     for (int64_t qb = 0; qb < nq; qb += TV_QT * 16) {
         const float* qp[TV_QT];
@@ -149,8 +333,13 @@ __global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restr
             qp[j] = q + (q0 + row) * dim + fq * 8;
             best[j] = -INFINITY;
         }
-        if (nd_tiles > 8) tv_query_block<4>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
-        else tv_query_block<2>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+        if constexpr (FORM == RAG_TOKVEC_MXFP8) {
+            if (nd_tiles > 8) tv_query_block_q8<4>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+            else tv_query_block_q8<2>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+        } else {
+            if (nd_tiles > 8) tv_query_block<4, FORM>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+            else tv_query_block<2, FORM>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+        }
 #pragma unroll
         for (int j = 0; j < TV_QT; ++j) {
             best[j] = fmaxf(best[j], __shfl_xor(best[j], 16));
@@ -174,18 +363,23 @@ __global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 static void tokvec_drop(rag_ctx* h) {
     h->tv.reset();
+    h->tv8.reset();
     h->tv_off.reset();
     h->tv_docs = h->tv_rows = h->tv_docs_cap = h->tv_rows_cap = 0;
     h->tv_dim = 0;
+    h->tv_form = RAG_TOKVEC_FP16;
     h->tv_stale = false;
 }
 
-int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim) {
+int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim, int form) {
+    ARG_CHECK(h, form == RAG_TOKVEC_FP16 || form == RAG_TOKVEC_MXFP8, "tokvec_reserve: unknown form (RAG_TOKVEC_FP16, RAG_TOKVEC_MXFP8)");
     ARG_CHECK(h, n_docs_total > 0 && n_docs_total < (int64_t)0x7fffff00 && rows_total >= 0, "tokvec_reserve: need 0 < documents < 2^31 and rows >= 0");
     ARG_CHECK(h, dim >= 32 && dim <= 1024 && dim % 32 == 0, "tokvec_reserve: dim must be a multiple of 32 in [32, 1024]");
     tokvec_drop(h);
     int rc;
-    if ((rc = h->tv.alloc(h, std::max<size_t>((size_t)rows_total * dim, 8))) || (rc = h->tv_off.alloc(h, (size_t)n_docs_total + 1)) ||
+    rc = form == RAG_TOKVEC_MXFP8 ? h->tv8.alloc(h, std::max<size_t>((size_t)rows_total * tokvec_row_bytes(dim, form), 16))
+                                  : h->tv.alloc(h, std::max<size_t>((size_t)rows_total * dim, 8));
+    if (rc || (rc = h->tv_off.alloc(h, (size_t)n_docs_total + 1)) ||
         (rc = h->tv_bad.reserve(h, 2))) {
         tokvec_drop(h);
         return rc;
@@ -198,6 +392,7 @@ int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim
     h->tv_docs_cap = n_docs_total;
     h->tv_rows_cap = rows_total;
     h->tv_dim = dim;
+    h->tv_form = form;
     return RAG_OK;
 }
 
@@ -224,14 +419,21 @@ int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t
     ARG_CHECK(h, ends[0] >= 0 && rows >= 0, "tokvec_append: row offsets must start at >= 0 and never decrease");
     ARG_CHECK(h, h->tv_rows + rows <= h->tv_rows_cap, "tokvec_append: exceeds the reserved rows");
     ARG_CHECK(h, rows == 0 || vecs != nullptr, "tokvec_append: null vectors");
-    half_t* dst = h->tv + (size_t)h->tv_rows * dim;
+    const bool q8 = h->tv_form == RAG_TOKVEC_MXFP8;
+    const int stride = tokvec_row_bytes(dim, h->tv_form);
+    half_t* dst = q8 ? nullptr : h->tv + (size_t)h->tv_rows * dim;
+    uint8_t* dst8 = q8 ? h->tv8 + (size_t)h->tv_rows * stride : nullptr;
     int64_t* dst_off = h->tv_off + h->tv_docs + 1;
     const int64_t total = rows * dim;
     const int64_t piece = (int64_t)64 << 20;                     // floats per launch (a grid stays far below 2^32 threads) and per staged copy
     auto convert = [&](const float* src_dev, int64_t at, int64_t cnt) {
         for (int64_t o = 0; o < cnt; o += piece) {
             const int64_t nn = std::min(piece, cnt - o);
-            launch(tokvec_convert_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, src_dev + o, dst + at + o, nn, h->tv_bad.get());
+            if (q8)       // a piece is a multiple of 32 floats: no block of 32 is cut
+                launch(tokvec_quant8_kernel, dim3((unsigned)((nn / 8 + 255) / 256)), dim3(256), 0, st, src_dev + o, dst8, at + o, nn, dim, stride,
+                       h->tv_bad.get());
+            else
+                launch(tokvec_convert_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, src_dev + o, dst + at + o, nn, h->tv_bad.get());
         }
     };
     if (host_ptrs) {
@@ -271,10 +473,10 @@ int tokvec_append(rag_ctx* h, const float* vecs, const int64_t* row_off, int64_t
     return RAG_OK;
 }
 
-int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim) {
+int tokvec_load_host(rag_ctx* h, const float* vecs, const int64_t* off, int64_t n_docs, int dim, int form) {
     ARG_CHECK(h, off != nullptr && n_docs > 0, "tokvec_load: need offsets and at least one document");
     ARG_CHECK(h, off[n_docs] >= off[0], "tokvec_load: row offsets must never decrease");
-    if (int rc = tokvec_reserve(h, n_docs, off[n_docs] - off[0], dim)) return rc;
+    if (int rc = tokvec_reserve(h, n_docs, off[n_docs] - off[0], dim, form)) return rc;
     return tokvec_append(h, vecs, off, n_docs, h->stream, true);
 }
 
@@ -283,7 +485,12 @@ int tokvec_info(const rag_ctx* h, int64_t* docs_out, int64_t* rows_out, int* dim
     if (docs_out) *docs_out = have ? h->tv_docs : 0;
     if (rows_out) *rows_out = have ? h->tv_rows : 0;
     if (dim_out) *dim_out = have ? h->tv_dim : 0;
-    if (hbm_bytes_out) *hbm_bytes_out = have ? (int64_t)(h->tv.size() * sizeof(half_t) + h->tv_off.size() * sizeof(int64_t)) : 0;
+    if (hbm_bytes_out) *hbm_bytes_out = have ? (int64_t)(h->tv.size() * sizeof(half_t) + h->tv8.size() + h->tv_off.size() * sizeof(int64_t)) : 0;
+    return RAG_OK;
+}
+
+int tokvec_form(const rag_ctx* h, int* form_out) {
+    if (form_out) *form_out = h->tv_docs_cap > 0 ? h->tv_form : -1;
     return RAG_OK;
 }
 
@@ -297,6 +504,21 @@ int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int
     *n_rows_out = n;
     ARG_CHECK(h, n <= cap_rows && (n == 0 || out != nullptr), "tokvec_fetch: the document has more rows than the output holds");
     if (n == 0) return RAG_OK;
+    if (h->tv_form == RAG_TOKVEC_MXFP8) {                        // code * 2^e, decoded here from the stored bytes
+        const int dim = h->tv_dim, stride = tokvec_row_bytes(dim, h->tv_form);
+        std::vector<uint8_t> raw((size_t)n * stride);
+        HIP_TRY(h, hipMemcpyAsync(raw.data(), h->tv8 + (size_t)span[0] * stride, raw.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int64_t r = 0; r < n; ++r) {
+            const uint8_t* rp = raw.data() + (size_t)r * stride;
+            for (int c = 0; c < dim; ++c) {
+                const int code = rp[c], ex = (code >> 3) & 15, man = code & 7, e = (int)rp[dim + c / 32] - 127;
+                const float mag = ex ? std::ldexp((float)(8 + man), ex - 10 + e) : std::ldexp((float)man, e - 9);
+                out[(size_t)r * dim + c] = code & 0x80 ? -mag : mag;
+            }
+        }
+        return RAG_OK;
+    }
     std::vector<half_t> tmp((size_t)n * h->tv_dim);
     HIP_TRY(h, hipMemcpyAsync(tmp.data(), h->tv + (size_t)span[0] * h->tv_dim, tmp.size() * sizeof(half_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -313,6 +535,10 @@ int tokvec_fetch_host(rag_ctx* h, int64_t doc, float* out, int64_t cap_rows, int
 // The chunk is then copied to its destination. In place and safe: chunks ascend, every source row lies at or above its
 // destination (rows only move down), so a chunk's sources lie at or above r0 - untouched by the earlier chunks, which wrote
 // below r0 - and are all in the staging buffer before the copy overwrites [r0, r0 + m).
+// A row is tokvec_row_bytes bytes in either form. The 8-bit form's scale bytes (dim / 32 of them, 1 to 32: not a whole number of
+// units on their own) lie behind their row's codes and the row is padded to a multiple of 16 bytes, so codes and scales move
+// together as stored bits in the same units; the argument above is about rows and holds unchanged, and chunk_rows is derived from
+// the form's row bytes.
 __global__ __launch_bounds__(256) void tokvec_compact_gather_kernel(const uint4* __restrict__ store, int units_per_row,
                                                                      const int64_t* __restrict__ new_off, const int64_t* __restrict__ src_start,
                                                                      int64_t doc_lo, int64_t doc_hi, int64_t r0, int64_t total,
@@ -355,7 +581,7 @@ int tokvec_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t n_map, si
     if (plan->first_doc < 0) return RAG_OK;
     plan->docs_new = (int64_t)src_start.size();
     plan->rows_new = plan->new_off_h.back();
-    const int64_t row_bytes = (int64_t)h->tv_dim * (int64_t)sizeof(half_t);
+    const int64_t row_bytes = tokvec_row_bytes(h->tv_dim, h->tv_form);
     plan->chunk_rows = h->opt.tokvec_compact_rows > 0 ? h->opt.tokvec_compact_rows : (int64_t)(stage_bytes / (size_t)row_bytes);
     plan->chunk_rows = std::max<int64_t>(1, std::min(plan->chunk_rows, (int64_t)(stage_bytes / (size_t)row_bytes)));
     if (plan->new_off.alloc(h, (size_t)h->tv_docs_cap + 1) || plan->src_start.alloc(h, std::max<size_t>(1, src_start.size()))) {
@@ -377,16 +603,19 @@ int tokvec_compact_prepare(rag_ctx* h, const int64_t* row_map, int64_t n_map, si
 // rows are headroom of the same reservation again.
 int tokvec_compact_commit(rag_ctx* h, tokvec_compact_plan* plan, char* stage, hipStream_t st) {
     if (!plan->active) return RAG_OK;
-    const int upr = h->tv_dim / 8;                               // 16-byte units per row (dim is a multiple of 32)
-    const size_t row_bytes = (size_t)h->tv_dim * sizeof(half_t);
+    // 16-byte units per row: dim / 8 of fp16 bits; the 8-bit form's row - codes, its dim / 32 scale bytes and the padding that
+    // makes them a whole number of units - moves as one piece, stored bits, never requantised
+    const size_t row_bytes = (size_t)tokvec_row_bytes(h->tv_dim, h->tv_form);
+    const int upr = (int)(row_bytes / 16);
+    char* base = h->tv_form == RAG_TOKVEC_MXFP8 ? reinterpret_cast<char*>(h->tv8.get()) : reinterpret_cast<char*>(h->tv.get());
     const std::vector<int64_t>& no = plan->new_off_h;
     const auto doc_of = [&](int64_t r) { return (int64_t)(std::upper_bound(no.begin(), no.begin() + plan->docs_new + 1, r) - no.begin()) - 1; };
     for (int64_t r0 = no[(size_t)plan->first_doc]; r0 < plan->rows_new; r0 += plan->chunk_rows) {
         const int64_t m = std::min(plan->chunk_rows, plan->rows_new - r0), total = m * upr;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)1 << 20);
-        launch(tokvec_compact_gather_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(h->tv.get()), upr,
+        launch(tokvec_compact_gather_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(base), upr,
                plan->new_off.get(), plan->src_start.get(), doc_of(r0), doc_of(r0 + m - 1), r0, total, reinterpret_cast<uint4*>(stage));
-        HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->tv.get()) + (size_t)r0 * row_bytes, stage, (size_t)m * row_bytes,
+        HIP_TRY(h, hipMemcpyAsync(base + (size_t)r0 * row_bytes, stage, (size_t)m * row_bytes,
                                   hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(h, hipGetLastError());
@@ -423,8 +652,12 @@ int tokvec_score_slots(rag_ctx* h, const float* q_vecs, const int64_t* q_off, co
     if (int rc = h->tv_ws.reserve(h, stage_size(P, 4) * 2)) return rc;
     float* sc = reinterpret_cast<float*>(h->tv_ws.get());
     int32_t* slot = reinterpret_cast<int32_t*>(h->tv_ws.get() + stage_size(P, 4));
-    launch(tokvec_maxsim_kernel, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), h->tv_docs, cand_rows, pool,
-           h->tv_dim, sc, slot);
+    if (h->tv_form == RAG_TOKVEC_MXFP8)
+        launch(tokvec_maxsim_kernel<RAG_TOKVEC_MXFP8>, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv8.get(), h->tv_off.get(), h->tv_docs,
+               cand_rows, pool, h->tv_dim, sc, slot);
+    else
+        launch(tokvec_maxsim_kernel<RAG_TOKVEC_FP16>, dim3((unsigned)P), dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), h->tv_docs,
+               cand_rows, pool, h->tv_dim, sc, slot);
     *scores_out = sc;
     if (slots_out) *slots_out = slot;
     return launch_status(h);

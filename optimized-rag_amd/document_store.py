@@ -424,22 +424,23 @@ class GpuDocumentIndex:
 
     # ---- late interaction over resident token vectors (rag_tokvec_*) -------------------------------------------------------
     @_locked
-    def load_token_vectors(self, vecs, offsets) -> None:
+    def load_token_vectors(self, vecs, offsets, form: str = "fp16") -> None:
         """Make the rows' token vectors resident: float32 [rows, tok_dim] packed row after row, int64 offsets [len(self.rows) + 1]
-        (e.g. embed_multi's outputs kept from an earlier ingest). They are stored as fp16; a compaction leaves them stale - and
-        search_late_interaction falling back to `search` - until this or build_token_vectors runs again."""
+        (e.g. embed_multi's outputs kept from an earlier ingest). They are stored as fp16, or with form="mxfp8" as block-scaled
+        8-bit codes (33/64 of the bytes; add_rows, add_texts, compact and the searches follow the store's form); a compaction
+        leaves them stale - and search_late_interaction falling back to `search` - until this or build_token_vectors runs again."""
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         if off.shape[0] - 1 != len(self.rows):
             raise ValueError(f"load_token_vectors: offsets of {off.shape[0] - 1} documents for an index of {len(self.rows)} rows")
-        self.engine.tokvec_load(vecs, off)
+        self.engine.tokvec_load(vecs, off, form=form)
 
     @_locked
-    def build_token_vectors(self, texts, batch: int = 64, *, headroom_docs: int = 0, headroom_rows: int = 0) -> None:
+    def build_token_vectors(self, texts, batch: int = 64, *, headroom_docs: int = 0, headroom_rows: int = 0, form: str = "fp16") -> None:
         """Compute the token vectors of the rows' texts (texts[i] belongs to row i) with the embedding service's token-vector head
         and append them to the resident store on the device, `batch` texts per forward: the vectors go from the forward's output
         tensor into the store and never exist on the host. headroom_docs / headroom_rows reserve room for the documents later
         add_rows(token_vectors=...) / add_texts calls append (a reservation does not grow; compact(keep_resident=True) returns the
-        rows of deleted documents to it)."""
+        rows of deleted documents to it). form: "fp16" or "mxfp8", as load_token_vectors."""
         import torch
         svc = self.embeddings
         texts = [str(t) for t in texts]
@@ -452,7 +453,7 @@ class GpuDocumentIndex:
         batch = max(1, int(batch))
         batches = [svc.tokenize(texts[b:b + batch]) for b in range(0, len(texts), batch)]
         n_rows = [int((np.clip(lens, 1, ids.shape[1]).astype(np.int64) - 1).sum()) for ids, _, lens in batches]
-        self.engine.tokvec_reserve(len(texts) + max(0, int(headroom_docs)), sum(n_rows) + max(0, int(headroom_rows)), tok_dim)
+        self.engine.tokvec_reserve(len(texts) + max(0, int(headroom_docs)), sum(n_rows) + max(0, int(headroom_rows)), tok_dim, form=form)
         for (ids, tt, lens), rows in zip(batches, n_rows):
             tok = torch.empty((max(rows, 1), tok_dim), dtype=torch.float32, device="cuda")
             off = torch.empty((len(lens) + 1,), dtype=torch.int64, device="cuda")
