@@ -325,7 +325,8 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
  *   rag_sparse_* search and rag_hybrid_sparse_rrf_dev returns RAG_ERR_STATE until rag_sparse_load_host runs again (the handle
  *   stays usable; a compaction that finds no deleted row moves nothing and marks nothing). rag_index_delete_host does not:
  *   deleted rows are filtered. After inserts, rag_sparse_append_host (below, behind rag_bm25_segments) makes the postings
- *   current again; rag_index_compact_live renumbers them with the rows. There is no per-query tenant array for this index.
+ *   current again; rag_index_compact_live renumbers them with the rows. A tenant per query: rag_sparse_topk_tenants_* and
+ *   rag_hybrid_sparse_rrf_tenants_dev ("a tenant PER QUERY" below).
  * rag_hybrid_sparse_rrf_dev: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list - dense top-`pool` and sparse
  *   top-`pool` (-1 padded at the tail), rag_rrf_fuse_dev semantics with n_lists = 2, dense first, top-k. Workspaces and limits
  *   as rag_hybrid_rrf_dev (pool <= 256; lists_ws_dev [2][Q][pool] int64, scores_ws_dev [Q][pool] float64); the postings must
@@ -936,6 +937,30 @@ int rag_retrieve_rerank_tenants_dev(rag_handle_t h, const float* q_emb_dev, cons
                                     int rrf_k, const int32_t* tenants_host, int mode, int cls_id, int sep_id, int L_pair,
                                     int64_t* ids_out_dev, double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev,
                                     void* stream);
+/* The learned-sparse index and the bge-m3 composites (outputs as their namesakes': ids, rows, float64 scores, RRF scores and
+ * ranks, components_out, cand_out). "Matches nothing" combines with the query's own tenant: a document is listed only if it is
+ * visible to that query and its score is > 0. Only the candidate searches see the tenants: the MaxSim, cosine, point-lookup and
+ * combine steps score the rows they are handed, which arrive filtered. The explicit-row entries (rag_tokvec_rerank_dev,
+ * rag_m3_score_rows_dev, rag_sparse_score_rows_*) never look at visibility and have no such form. */
+int rag_sparse_topk_tenants_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host,
+                                 const float* qweights_host, int n_queries, int k, const int32_t* tenants_host, int64_t* ids_out,
+                                 int32_t* rows_out /*may be NULL*/, double* scores_out);
+int rag_sparse_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                                int n_queries, int k, const int32_t* tenants_host, int64_t* ids_out_dev,
+                                int32_t* rows_out_dev /*may be NULL*/, double* scores_out_dev, void* stream);
+int rag_hybrid_sparse_rrf_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                      const float* qweights_dev, int n_queries, int pool, int k, int rrf_k,
+                                      const int32_t* tenants_host, int64_t* lists_ws_dev, double* scores_ws_dev,
+                                      int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream);
+int rag_retrieve_maxsim_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                    const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries,
+                                    int pool, int k, int rrf_k, const int32_t* tenants_host, int mode, int64_t* ids_out_dev,
+                                    double* scores_out_dev, int64_t* cand_out_dev /*may be NULL*/, void* stream);
+int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool,
+                                int k, int rrf_k, const int32_t* tenants_host, int mode, double w_dense, double w_sparse,
+                                double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
+                                double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/, void* stream);
 
 /* ---- the exchange step of the row-sharded search (the reference is single-process) bound to RCCL
  *      directly, for hosts that do not want torch.distributed in the path: ONE all-gather of each rank's partial top-k lists

@@ -180,7 +180,9 @@ _SIGS = {
 # The per-query-tenant entries: the arguments of their namesakes with `const int32_t* tenants_host` where those have `int tenant`
 # (argument position of the tenant in the namesake's list).
 for _name, _pos in (("rag_dense_topk_host", 4), ("rag_dense_topk_dev", 4), ("rag_bm25_topk_host", 5), ("rag_bm25_topk_dev", 5),
-                    ("rag_hybrid_rrf_dev", 8), ("rag_hybrid_linear_dev", 9), ("rag_retrieve_rerank_dev", 11)):
+                    ("rag_hybrid_rrf_dev", 8), ("rag_hybrid_linear_dev", 9), ("rag_retrieve_rerank_dev", 11),
+                    ("rag_sparse_topk_host", 6), ("rag_sparse_topk_dev", 6), ("rag_hybrid_sparse_rrf_dev", 9),
+                    ("rag_retrieve_maxsim_dev", 11), ("rag_retrieve_m3_dev", 11)):
     _args, _res = _SIGS[_name]
     assert _args[_pos] is C.c_int
     _SIGS[_name.replace("_host", "_tenants_host").replace("_dev", "_tenants_dev")] = (_args[:_pos] + [_P] + _args[_pos + 1:], _res)
@@ -784,8 +786,10 @@ class RagEngine:
         ids = np.empty((Q, k), dtype=np.int64)
         rows = np.empty((Q, k), dtype=np.int32)
         sc = np.empty((Q, k), dtype=np.float64)
-        self._check(self.lib.rag_sparse_topk_host(self.h, _ptr(term_ptr), _ptr(terms), _ptr(weights), Q, int(k), int(tenant), _ptr(ids),
-                                                  _ptr(rows), _ptr(sc)), "rag_sparse_topk_host")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_sparse_topk_tenants_host, "rag_sparse_topk_tenants_host") if per_query else (self.lib.rag_sparse_topk_host, "rag_sparse_topk_host")
+        self._check(fn(self.h, _ptr(term_ptr), _ptr(terms), _ptr(weights), Q, int(k), _ptr(t) if per_query else t, _ptr(ids),
+                       _ptr(rows), _ptr(sc)), name)
         return ids, rows, sc
 
     def sparse_scores(self, term_ptr, terms, weights):
@@ -803,10 +807,12 @@ class RagEngine:
         import torch
         Q = term_ptr.shape[0] - 1
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        self._check(self.lib.rag_sparse_topk_dev(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()),
-                                                 C.c_void_p(weights.data_ptr()), Q, int(k), int(tenant), C.c_void_p(ids_out.data_ptr()),
-                                                 C.c_void_p(rows_out.data_ptr() if rows_out is not None else 0),
-                                                 C.c_void_p(scores_out.data_ptr()), st), "rag_sparse_topk_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_sparse_topk_tenants_dev, "rag_sparse_topk_tenants_dev") if per_query else (self.lib.rag_sparse_topk_dev, "rag_sparse_topk_dev")
+        self._check(fn(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()),
+                       C.c_void_p(weights.data_ptr()), Q, int(k), _ptr(t) if per_query else t, C.c_void_p(ids_out.data_ptr()),
+                       C.c_void_p(rows_out.data_ptr() if rows_out is not None else 0),
+                       C.c_void_p(scores_out.data_ptr()), st), name)
 
     def hybrid_sparse_rrf_dev(self, q, term_ptr, terms, weights, pool, k, rrf_k=60, tenant=-1, stream=None):
         """hybrid_rrf_dev with the learned-sparse list in place of the BM25 list: dense top-pool + sparse top-pool -> RRF ->
@@ -824,11 +830,14 @@ class RagEngine:
             self._hybs_key = key
         lists, sc, keys, rrf, ranks = self._hybs
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        self._check(self.lib.rag_hybrid_sparse_rrf_dev(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()),
-                                                       C.c_void_p(terms.data_ptr()), C.c_void_p(weights.data_ptr()), Q, int(pool), int(k),
-                                                       int(rrf_k), int(tenant), C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
-                                                       C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
-                                                       C.c_void_p(ranks.data_ptr()), st), "rag_hybrid_sparse_rrf_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_hybrid_sparse_rrf_tenants_dev, "rag_hybrid_sparse_rrf_tenants_dev") if per_query
+                    else (self.lib.rag_hybrid_sparse_rrf_dev, "rag_hybrid_sparse_rrf_dev"))
+        self._check(fn(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(term_ptr.data_ptr()),
+                       C.c_void_p(terms.data_ptr()), C.c_void_p(weights.data_ptr()), Q, int(pool), int(k),
+                       int(rrf_k), _ptr(t) if per_query else t, C.c_void_p(lists.data_ptr()), C.c_void_p(sc.data_ptr()),
+                       C.c_void_p(keys.data_ptr()), C.c_void_p(rrf.data_ptr()),
+                       C.c_void_p(ranks.data_ptr()), st), name)
         return keys, rrf, ranks
 
     def set_temporal(self, temporal):
@@ -1150,9 +1159,11 @@ class RagEngine:
         mode = 0 if term_ptr is None else 1
         self._tokvec_rerank_check(tuple(q_vecs.shape), None, "retrieve_maxsim_dev")
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.rag_retrieve_maxsim_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
-                                                     int(k), int(rrf_k), int(tenant), mode, p(ids), p(sc), p(cand), st),
-                    "rag_retrieve_maxsim_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_retrieve_maxsim_tenants_dev, "rag_retrieve_maxsim_tenants_dev") if per_query
+                    else (self.lib.rag_retrieve_maxsim_dev, "rag_retrieve_maxsim_dev"))
+        self._check(fn(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
+                       int(k), int(rrf_k), _ptr(t) if per_query else t, mode, p(ids), p(sc), p(cand), st), name)
         return ids, sc, cand
 
     # ---- the three-way bge-m3 score over resident data (rag_sparse_score_rows_*, rag_m3_score_rows_dev, rag_retrieve_m3_dev) ----
@@ -1211,9 +1222,11 @@ class RagEngine:
             self._tokvec_rerank_check(tuple(q_vecs.shape), None, "retrieve_m3_dev")
         st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.rag_retrieve_m3_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
-                                                 int(k), int(rrf_k), int(tenant), int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids),
-                                                 p(sc), p(comp), p(cand), st), "rag_retrieve_m3_dev")
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_retrieve_m3_tenants_dev, "rag_retrieve_m3_tenants_dev") if per_query else (self.lib.rag_retrieve_m3_dev, "rag_retrieve_m3_dev")
+        self._check(fn(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
+                       int(k), int(rrf_k), _ptr(t) if per_query else t, int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids),
+                       p(sc), p(comp), p(cand), st), name)
         return ids, sc, comp, cand
 
     def tokens_load(self, tokens, lens, id_bits=16):

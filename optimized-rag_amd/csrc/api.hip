@@ -655,7 +655,17 @@ int rag_sparse_topk_host(rag_handle_t h, const int32_t* term_ptr_host, const int
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     HOST_ENTRY(h);
-    return sparse_topk_host(h, term_ptr_host, terms_host, qweights_host, n_queries, k, tenant, ids_out, rows_out, scores_out);
+    return sparse_topk_host(h, term_ptr_host, terms_host, qweights_host, n_queries, k, tenant, ids_out, rows_out, scores_out, {nullptr, nullptr});
+}
+int rag_sparse_topk_tenants_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
+                                 int n_queries, int k, const int32_t* tenants_host, int64_t* ids_out, int32_t* rows_out, double* scores_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && n_queries > 0 && n_queries <= 65535, "sparse: null tenants array or bad n_queries");
+    HOST_ENTRY(h);
+    entry_tenants t;                  // (staged on the stream bm25_run works on)
+    if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, h->stream, &t)) return rc;
+    return sparse_topk_host(h, term_ptr_host, terms_host, qweights_host, n_queries, k, t.tenant, ids_out, rows_out, scores_out, t.qt);
 }
 
 int rag_sparse_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int n_queries,
@@ -664,7 +674,18 @@ int rag_sparse_topk_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32
     LOCK(h);
     DEV_ENTRY(h);
     return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, n_queries, k, tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream,
-                           id_space::of_index(h));
+                           id_space::of_index(h), {nullptr, nullptr});
+}
+int rag_sparse_topk_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int n_queries,
+                                int k, const int32_t* tenants_host, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && n_queries > 0 && n_queries <= 65535, "sparse: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, (hipStream_t)stream, &t)) return rc;
+    return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, n_queries, k, t.tenant, ids_dev, rows_dev, scores_dev, (hipStream_t)stream,
+                           id_space::of_index(h), t.qt);
 }
 
 int rag_sparse_scores_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
@@ -677,9 +698,10 @@ int rag_sparse_scores_host(rag_handle_t h, const int32_t* term_ptr_host, const i
 
 // dense top-pool + learned-sparse top-pool + RRF -> top-k: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list
 // (hybrid_legs: the sparse leg forks onto the side stream exactly as the BM25 leg does).
-int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
-                              const float* qweights_dev, int Q, int pool, int k, int rrf_k, int tenant, int64_t* lists_ws_dev,
-                              double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+static int hybrid_sparse_rrf_entry(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                   const float* qweights_dev, int Q, int pool, int k, int rrf_k, int tenant, const int32_t* tenants_host,
+                                   int64_t* lists_ws_dev, double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev,
+                                   int32_t* ranks_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid_sparse: 1 <= n_queries <= 65535");
@@ -688,11 +710,27 @@ int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t*
     if (int rc = keyword_postings_aligned(h, true, "hybrid_sparse", RAG_ERR_ARG)) return rc;
     DEV_ENTRY(h);
     hipStream_t st = (hipStream_t)stream;
-    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_sparse: tenant filter requested but no tenants loaded");
-    if (int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, tenant, lists_ws_dev, scores_ws_dev, st, id_space::of_index(h),
-                             {nullptr, nullptr}, qweights_dev))
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
+    ARG_CHECK(h, t.tenant < 0 || h->tenants != nullptr, "hybrid_sparse: tenant filter requested but no tenants loaded");
+    if (int rc = hybrid_legs(h, q_dev, term_ptr_dev, terms_dev, Q, pool, t.tenant, lists_ws_dev, scores_ws_dev, st, id_space::of_index(h), t.qt,
+                             qweights_dev))
         return rc;
     return rrf_fuse_dev(h, lists_ws_dev, Q, 2, pool, (int64_t)Q * pool, pool, rrf_k, k, keys_out_dev, rrf_out_dev, ranks_out_dev, st);
+}
+int rag_hybrid_sparse_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                              const float* qweights_dev, int Q, int pool, int k, int rrf_k, int tenant, int64_t* lists_ws_dev,
+                              double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev, int32_t* ranks_out_dev, void* stream) {
+    return hybrid_sparse_rrf_entry(h, q_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, k, rrf_k, tenant, nullptr, lists_ws_dev,
+                                   scores_ws_dev, keys_out_dev, rrf_out_dev, ranks_out_dev, stream);
+}
+int rag_hybrid_sparse_rrf_tenants_dev(rag_handle_t h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                      const float* qweights_dev, int Q, int pool, int k, int rrf_k, const int32_t* tenants_host,
+                                      int64_t* lists_ws_dev, double* scores_ws_dev, int64_t* keys_out_dev, double* rrf_out_dev,
+                                      int32_t* ranks_out_dev, void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return hybrid_sparse_rrf_entry(h, q_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, k, rrf_k, -1, tenants_host, lists_ws_dev,
+                                   scores_ws_dev, keys_out_dev, rrf_out_dev, ranks_out_dev, stream);
 }
 
 // Per-row temporal score of the linear fusion: RECENCY_WEIGHT * 0.5 ** (days_old / half_life) computed by the host from
@@ -1163,7 +1201,20 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
     LOCK(h);
     DEV_ENTRY(h);
     return retrieve_maxsim_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, tenant, mode,
-                               ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream);
+                               ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream, {nullptr, nullptr});
+}
+int rag_retrieve_maxsim_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                    const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k,
+                                    int rrf_k, const int32_t* tenants_host, int mode, int64_t* ids_out_dev, double* scores_out_dev,
+                                    int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "retrieve_maxsim: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
+    return retrieve_maxsim_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, t.tenant, mode,
+                               ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream, t.qt);
 }
 
 int rag_sparse_score_rows_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
@@ -1201,7 +1252,21 @@ int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* t
     LOCK(h);
     DEV_ENTRY(h);
     return retrieve_m3_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, n_queries, pool, k, rrf_k, tenant, mode,
-                           w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream);
+                           w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream,
+                           {nullptr, nullptr});
+}
+int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                                const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool, int k,
+                                int rrf_k, const int32_t* tenants_host, int mode, double w_dense, double w_sparse, double w_colbert,
+                                int64_t* ids_out_dev, double* scores_out_dev, double* components_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && n_queries > 0 && n_queries <= 65535, "retrieve_m3: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, (hipStream_t)stream, &t)) return rc;
+    return retrieve_m3_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, n_queries, pool, k, rrf_k, t.tenant, mode,
+                           w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream, t.qt);
 }
 
 }  // extern "C"

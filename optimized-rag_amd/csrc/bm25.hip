@@ -1215,6 +1215,15 @@ __global__ __launch_bounds__(64 * BMS_WAVES) void bm25_merge_select_kernel(const
     }
 }
 
+// sparse_range_kernel with a tenant per query (rag_sparse_topk_tenants_* and the *_tenants_dev composites over this index): a kernel
+// of its own, as bm25_range_tenants_kernel is, so that sparse_range_kernel's code stays what it was
+__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void sparse_range_tenants_kernel(BM_RANGE_PARAMS,
+                                                                                                              const float* __restrict__ wf,
+                                                                                                              const float* __restrict__ qweights,
+                                                                                                              const int32_t* __restrict__ qten) {
+    bm25_range_body<2>(BM_RANGE_ARGS, qten, wf, qweights);
+}
+
 // per-call device buffers of a top-k search: partial lists [Q][n_ranges][k], counts [Q][n_ranges], running list, threshold
 // + the per-call plan (see bm25_plan_kernel): plan.off [Q][BM_PLAN_T][n_ranges + 1] int32, plan.meta [Q][BM_PLAN_T]
 struct bm25_plan_ws { int32_t* off; bm_plan_meta* meta; };
@@ -1238,7 +1247,11 @@ struct bm25_topk_out {
         bm_grid gm_ = bm_make_grid(NR_L, NQ, (H)->opt.bm25_linear_grid);                                                           \
         gm_.plan_t = (IX)->plan_t;                                                                                                 \
         const bm_seg sg_ = {(IX)->row0, OUT_LD, (IX)->first};                                                                      \
-        if ((IX)->wf != nullptr)                                                                                                   \
+        if ((IX)->wf != nullptr && (QTEN) != nullptr)                                                                              \
+            hipLaunchKernelGGL(sparse_range_tenants_kernel, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
+                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, \
+                               (const float*)(IX)->wf, (IX)->call_qw, QTEN);                                                       \
+        else if ((IX)->wf != nullptr)                                                                                              \
             hipLaunchKernelGGL(sparse_range_kernel, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
                                (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, \
                                (const float*)(IX)->wf, (IX)->call_qw);                                                             \
@@ -2107,7 +2120,7 @@ int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out) { return bm_segment
 
 static int bm25_set_attr(rag_ctx* h) {
     return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>, bm25_range_tenants_kernel<true>,
-                     bm25_range_tenants_kernel<false>, sparse_range_kernel);
+                     bm25_range_tenants_kernel<false>, sparse_range_kernel, sparse_range_tenants_kernel);
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
@@ -2728,20 +2741,22 @@ int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int
 }
 
 // without a dense index of the same rows the ids are row numbers and there is nothing a tenant could be looked up in
-static int sparse_args(rag_ctx* h, const void* term_ptr, const void* qweights, int tenant) {
+// (per-query tenants: some query is filtered, so the check is a filter's - as in bm25_tenant_args)
+static int sparse_args(rag_ctx* h, const void* term_ptr, const void* qweights, int tenant, query_tenants qt = {nullptr, nullptr}) {
     ARG_CHECK(h, h->sparse != nullptr, "no sparse index loaded (rag_sparse_load_host)");
     ARG_CHECK(h, term_ptr != nullptr && qweights != nullptr, "sparse: null query arrays");
     if (int rc = bm25_check_fresh(h, h->sparse)) return rc;
+    if (qt.host != nullptr) tenant = 0;
     ARG_CHECK(h, tenant < 0 || (h->index_loaded && h->tenants != nullptr && h->n_rows == bm_total_docs(h->sparse)),
               "sparse: a tenant filter needs a dense index of the same rows with rag_index_set_tenants_host");
     return RAG_OK;
 }
 
 int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant,
-                     int64_t* ids_out, int32_t* rows_out, double* scores_out) {
+                     int64_t* ids_out, int32_t* rows_out, double* scores_out, query_tenants qt) {
     ARG_CHECK(h, ids_out && scores_out, "sparse_topk: null output");
-    if (int rc = sparse_args(h, term_ptr, qweights, tenant)) return rc;
-    return bm25_run(h, h->sparse, term_ptr, terms, Q, k, 0, tenant, ids_out, rows_out, scores_out, nullptr, nullptr, {nullptr, nullptr}, qweights);
+    if (int rc = sparse_args(h, term_ptr, qweights, tenant, qt)) return rc;
+    return bm25_run(h, h->sparse, term_ptr, terms, Q, k, 0, tenant, ids_out, rows_out, scores_out, nullptr, nullptr, qt, qweights);
 }
 
 int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out) {
@@ -2751,10 +2766,10 @@ int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms
 }
 
 int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
-                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids) {
-    if (int rc = sparse_args(h, term_ptr_dev, qweights_dev, tenant)) return rc;
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids, query_tenants qt) {
+    if (int rc = sparse_args(h, term_ptr_dev, qweights_dev, tenant, qt)) return rc;
     h->sparse->call_qw = qweights_dev;
-    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, ids, {nullptr, nullptr});
+    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, ids, qt);
 }
 
 // ---- point lookup: the exact learned-sparse score of GIVEN rows (rag_sparse_score_rows_*; the sparse component of rag_m3_score_rows_dev)

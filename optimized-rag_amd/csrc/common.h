@@ -492,9 +492,9 @@ void sparse_free(rag_ctx* h);
 int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);
 int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out);
 int sparse_topk_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, int k, int tenant, int64_t* ids_out,
-                     int32_t* rows_out, double* scores_out);
+                     int32_t* rows_out, double* scores_out, query_tenants qt);
 int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
-                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids);
+                    int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids, query_tenants qt);
 int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms, const float* qweights, int Q, double* out);
 // The ONE precondition of a search that fuses keyword postings (sparse: h->sparse, else h->bm25) with the dense index by row: they are
 // loaded, fresh (RAG_ERR_STATE while stale) and hold as many documents as the index has rows (RAG_ERR_ARG, "<who>: the ... postings
@@ -525,7 +525,7 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
                         int64_t* ids_out, double* scores_out, float* logits_out, int64_t* cand_out, hipStream_t st, query_tenants qt);
 int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                         const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, int64_t* ids_out,
-                        double* scores_out, int64_t* cand_out, hipStream_t st);
+                        double* scores_out, int64_t* cand_out, hipStream_t st, query_tenants qt);
 // cross_encoder.hip: the cross-encoder (h->ce) and the sentence-embedding encoder (h->emb). ids / tt / lens / out are host
 // arrays (staged, the call waits) or device arrays (queued on st) as host_ptrs says.
 int ce_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* tensors, int n);
@@ -598,4 +598,4 @@ int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_pt
 int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                     const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
                     double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
-                    hipStream_t st);
+                    hipStream_t st, query_tenants qt);

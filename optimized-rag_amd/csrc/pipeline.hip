@@ -21,14 +21,15 @@
 // workgroups leave room for ONE 20-KiB BM25 workgroup per CU - but the BM25 stages fill the thin opening stages, selects and
 // the rescoring of the dense leg: 1024-query hybrid batches 6.85 -> 6.58 ms on one box (A/B by option fork_max_q).
 // Option no_fork keeps the legs in line always; fork_max_q lowers the largest batch that forks.
-// qweights_dev != null: the second leg is the learned-sparse index (rag_hybrid_sparse_rrf_dev; no per-query tenants there).
+// qweights_dev != null: the second leg is the learned-sparse index (rag_hybrid_sparse_rrf*_dev and the maxsim / m3 composites). Either
+// keyword leg takes the call's per-query tenants, as the dense leg does.
 #define RAG_FORK_MAX_Q 4096
 int hybrid_legs(rag_ctx* h, const float* q_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int pool, int tenant,
                 int64_t* lists_dev, double* scores_ws_dev, hipStream_t st, id_space ids, query_tenants qt, const float* qweights_dev) {
     int64_t* const bm_ids = lists_dev + (size_t)Q * pool;
     auto keyword_leg = [&](double* scores, hipStream_t s) -> int {
         if (qweights_dev != nullptr)
-            return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, Q, pool, tenant, bm_ids, nullptr, scores, s, ids);
+            return sparse_topk_dev(h, term_ptr_dev, terms_dev, qweights_dev, Q, pool, tenant, bm_ids, nullptr, scores, s, ids, qt);
         return bm25_topk_dev(h, term_ptr_dev, terms_dev, Q, pool, tenant, bm_ids, nullptr, scores, nullptr, s, ids, qt);
     };
     const int fork_max = h->opt.fork_max_q > 0 ? h->opt.fork_max_q : RAG_FORK_MAX_Q;
@@ -449,14 +450,14 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
 //   2. tokvec_maxsim_kernel over the [Q][pool] candidate rows   3. the raw top-k of rerank_topk_kernel (which maps the ids)
 int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                         const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
-                        int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st) {
+                        int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st, query_tenants qt) {
     if (int rc = tokvec_usable(h, "retrieve_maxsim")) return rc;
     ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "retrieve_maxsim: 1 <= n_queries <= 65535, 0 < k <= pool <= 256");
     ARG_CHECK(h, q_emb_dev && q_vecs_dev && q_off_dev && ids_out && scores_out, "retrieve_maxsim: null argument");
     ARG_CHECK(h, mode == 0 || mode == 1, "retrieve_maxsim: mode is 0 (dense) or 1 (dense + sparse)");
     ARG_CHECK(h, h->index_loaded, "retrieve_maxsim: no index loaded");
     if (int rc = tokvec_covers_index(h, "retrieve_maxsim")) return rc;
-    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_maxsim: tenant filter requested but no tenants loaded");
+    ARG_CHECK(h, (tenant < 0 && qt.host == nullptr) || h->tenants != nullptr, "retrieve_maxsim: tenant filter requested but no tenants loaded");
     if (mode == 1) {
         ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_maxsim: mode 1 needs the query's terms and weights");
         if (int rc = keyword_postings_aligned(h, true, "retrieve_maxsim", RAG_ERR_ARG)) return rc;
@@ -465,7 +466,7 @@ int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
     cand_ws w;
     int rc = pipe_ws_carve(h, [&](ws_carve& c) { cand_ws_planes(c, w, P, P, true); });
     if (rc) return rc;
-    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, {nullptr, nullptr}, mode, w, st))) return rc;
+    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, qt, mode, w, st))) return rc;
     if ((rc = tokvec_rerank(h, q_vecs_dev, q_off_dev, w.rows, Q, pool, k, ids_out, nullptr, scores_out, nullptr, st))) return rc;
     if (!cand_out) return RAG_OK;
     HIP_TRY(h, hipMemcpyAsync(cand_out, w.cand, P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -597,7 +598,7 @@ int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_pt
 int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                     const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
                     double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
-                    hipStream_t st) {
+                    hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "retrieve_m3: mode is 0 (dense), 1 (dense + sparse RRF) or 2 (union of dense and sparse)");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= (mode == 2 ? RAG_MAX_K / 2 : RAG_MAX_K) && k > 0 && k <= pool,
               "retrieve_m3: 1 <= n_queries <= 65535, 0 < k <= pool <= 256 (mode 2: pool <= 128)");
@@ -606,7 +607,7 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
     ARG_CHECK(h, q_emb_dev && ids_out && scores_out, "retrieve_m3: null argument");
     const m3_weights w = {w_dense, w_sparse, w_colbert};
     if (int rc = m3_check(h, "retrieve_m3", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
-    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "retrieve_m3: tenant filter requested but no tenants loaded");
+    ARG_CHECK(h, (tenant < 0 && qt.host == nullptr) || h->tenants != nullptr, "retrieve_m3: tenant filter requested but no tenants loaded");
     if (mode != 0) {
         ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_m3: modes 1 and 2 need the query's terms and weights");
         if (int rc = keyword_postings_aligned(h, true, "retrieve_m3", RAG_ERR_STATE)) return rc;
@@ -620,7 +621,7 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
         sp = c.take<double>(PS);
     });
     if (rc) return rc;
-    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, {nullptr, nullptr}, mode, cw, st))) return rc;
+    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, qt, mode, cw, st))) return rc;
     return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cw.rows, Q, S, k, dn, sp, ids_out, nullptr,
                           scores_out, components_out, cand_out, st);
 }

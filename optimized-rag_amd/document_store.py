@@ -63,6 +63,11 @@ def _locked(fn):
     return f
 
 
+def _enc_rows(enc, sel):
+    """the texts `sel` of an encode_multi result"""
+    return {k: None if v is None else ([v[i] for i in sel] if isinstance(v, list) else np.asarray(v)[list(sel)]) for k, v in enc.items()}
+
+
 class GpuDocumentIndex:
     def __init__(self, embedding_service, dim: int = 1536, *, engine=None):
         self.embeddings = embedding_service            # same attribute name the reference's DocumentStore uses
@@ -77,6 +82,8 @@ class GpuDocumentIndex:
         self._doc_chunks: Dict[tuple, List[int]] = {}
         self._shard_without_doc_ids = False
         self._lexical = None                           # host mirror of the resident lexical postings (load_lexical), kept for live writes
+        self._row_ids = np.zeros(0, dtype=np.int64)    # engine id of every row (the batched bge-m3 searches map the ids they get back)
+        self._row_ids_sorted = None
 
     @property
     def engine(self):
@@ -104,6 +111,7 @@ class GpuDocumentIndex:
             if r.get("document_id") is not None:
                 self._doc_chunks.setdefault((str(r.get("agent_id", "")), int(r["document_id"])), []).append(ids[-1])
         self._next_id = max(ids, default=-1) + 1
+        self._set_row_ids(np.asarray(ids, dtype=np.int64))
         if any(int(r["id"]) != i for i, r in enumerate(self.rows)):
             self.engine.set_ids(np.asarray(ids, dtype=np.int64))
 
@@ -121,6 +129,7 @@ class GpuDocumentIndex:
         self._tenant_id = dict(sh.tenant_table)
         self.rows = _ShardRows(sh, begin, end)
         self._next_id = int(sh.ids[begin:end].max()) + 1 if end > begin else 0
+        self._set_row_ids(np.array(sh.ids[begin:end], dtype=np.int64))
         self._doc_chunks = {}
         doc = getattr(sh, "document_ids", None)
         self._shard_without_doc_ids = doc is None
@@ -173,6 +182,7 @@ class GpuDocumentIndex:
                 self.engine.tokvec_append(vecs, np.ascontiguousarray(offsets, dtype=np.int64)[:len(rows) + 1])
         if not isinstance(self.rows, (list, _RowView)):
             self.rows = _RowView(self.rows)
+        self._set_row_ids(np.concatenate([self._row_ids, ids]))
         for i, r in enumerate(rows):
             r = dict(r, id=int(ids[i]))
             self.rows.append(r)
@@ -304,6 +314,8 @@ class GpuDocumentIndex:
             elif (row_map < 0).any():
                 self._lexical = None                                 # stale on the device: nothing to mirror until load_lexical
         keep = np.nonzero(row_map >= 0)[0]
+        if self._row_ids.shape[0] == row_map.shape[0]:
+            self._set_row_ids(self._row_ids[keep])
         if isinstance(self.rows, list):
             self.rows = [self.rows[int(i)] for i in keep]
         else:
@@ -576,6 +588,158 @@ class GpuDocumentIndex:
                         "score": float(s), "dense_score": float(c[0]), "sparse_score": float(c[1]), "colbert_score": float(c[2]),
                         "metadata": row.get("metadata") or {}})
         return res
+
+    # ---- the bge-m3 searches for a batch of queries, one agent per query (rag_*_tenants_*) ----------------------------------
+    def _set_row_ids(self, ids):
+        self._row_ids, self._row_ids_sorted = ids, None
+
+    def _rows_of_ids(self, ids):
+        """Engine ids [Q, k] (-1 padded) -> rows of this index (-1 kept). An id that was deleted and inserted again names its
+        latest row: a search never returns a deleted one."""
+        ids = np.asarray(ids, dtype=np.int64)
+        if self._row_ids.shape[0] != len(self.rows):
+            raise RuntimeError("the ids of the index's rows are not known (rows were set without bulk_load / load_shard / add_rows)")
+        if self._row_ids_sorted is None:
+            order = np.argsort(self._row_ids, kind="stable")
+            self._row_ids_sorted = (self._row_ids[order], order)
+        sorted_ids, order = self._row_ids_sorted
+        if not sorted_ids.shape[0]:
+            return np.full(ids.shape, -1, dtype=np.int64)
+        at = np.clip(np.searchsorted(sorted_ids, ids, side="right") - 1, 0, sorted_ids.shape[0] - 1)
+        return np.where((ids >= 0) & (sorted_ids[at] == ids), order[at], -1)
+
+    def _tenants_of(self, agent_id, n_queries):
+        """int32 [n_queries]: the tenant number of every query's agent - one agent for all of them or a list with one per query;
+        None: -1, not filtered; an unknown agent: a number no row carries, so its query comes back all padding
+        (_search_rows_mixed's rule)."""
+        agents = list(agent_id) if isinstance(agent_id, (list, tuple, np.ndarray)) else [agent_id] * n_queries
+        if len(agents) != n_queries:
+            raise ValueError(f"{len(agents)} agent ids for {n_queries} queries")
+        nobody = max(self._tenant_id.values(), default=-1) + 1
+        return np.array([-1 if a is None else self._tenant_id.get(str(a), nobody) for a in agents], dtype=np.int32)
+
+    @staticmethod
+    def _to_device(a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    @staticmethod
+    def _to_host(*tensors):
+        """the outputs of a device call queued on the current stream, as numpy arrays"""
+        import torch
+        torch.cuda.current_stream().synchronize()
+        return [t.cpu().numpy() for t in tensors]
+
+    def _payload(self, r, extra):
+        row = self.rows[int(r)]
+        return {"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                "metadata": row.get("metadata") or {}, **extra}
+
+    def search_lexical_many(self, agent_id, queries: List[str], top_k: int = 5, mode: str = "dense+sparse", pool: int = 100,
+                            rrf_k: int = 60) -> List[List[Dict[str, Any]]]:
+        """Batched `search_lexical`: ONE encode_multi forward for all queries, then ONE search call with a tenant per query -
+        rag_sparse_topk_tenants_host (mode "sparse") or rag_hybrid_sparse_rrf_tenants_dev (mode "dense+sparse"; the fused hits'
+        `sparse_score` is then read back with one point lookup, rag_sparse_score_rows_host, whose bits are the search's).
+        agent_id: one agent, None (not filtered), or a list with one of either per query. Element i equals
+        `search_lexical(agent_id[i], queries[i], top_k, mode, pool, rrf_k)`; an unknown agent gets []. Errors are logged and
+        answered with [] for every query."""
+        try:
+            if mode not in ("dense+sparse", "sparse"):
+                raise ValueError(f"unknown mode {mode!r}")
+            if not queries:
+                return []
+            fused = mode == "dense+sparse"
+            enc = self.embeddings.encode_multi(list(queries), return_dense=fused, return_sparse=True, return_colbert_vecs=False)
+            with self._lock:
+                return self._search_lexical_many_locked(agent_id, enc, len(queries), int(top_k), fused, pool, rrf_k)
+        except Exception as e:
+            logger.error("Batched lexical search failed: %s", e)
+            return [[] for _ in queries]
+
+    def _search_lexical_many_locked(self, agent_id, enc, Q, top_k, fused, pool, rrf_k):
+        from .sparse import LexicalPostings
+        tenants = self._tenants_of(agent_id, Q)
+        if not self._tenant_id and (tenants >= 0).any():                 # no agent known at all: a filtered query finds nothing
+            return [[] for _ in range(Q)] if (tenants >= 0).all() else self._unfiltered_only(
+                tenants, lambda sel: self._search_lexical_many_locked(None, _enc_rows(enc, sel), len(sel), top_k, fused, pool, rrf_k))
+        ptr, terms, weights = LexicalPostings.encode_queries(enc["lexical_weights"])
+        if not fused:
+            _, rows, scores = self.engine.sparse_topk(ptr, terms, weights, top_k, tenant=tenants)
+            return [[self._payload(r, {"score": float(s), "sparse_score": float(s)}) for r, s in zip(rows[i], scores[i]) if r >= 0]
+                    for i in range(Q)]
+        dev = self._to_device
+        q = np.asarray(enc["dense_vecs"], dtype=np.float32).reshape(Q, self.dim)
+        n = max(top_k, pool)
+        keys, rrf, ranks = self.engine.hybrid_sparse_rrf_dev(dev(q), dev(ptr), dev(terms if len(terms) else np.zeros(1, np.int32)),
+                                                             dev(weights if len(weights) else np.zeros(1, np.float32)), n, top_k,
+                                                             rrf_k=rrf_k, tenant=tenants)
+        keys, rrf, ranks = self._to_host(keys, rrf, ranks)
+        rows = self._rows_of_ids(keys)
+        sparse = self.engine.sparse_score_rows(ptr, terms, weights, rows.astype(np.int32))
+        return [[self._payload(r, {"score": float(f), "sparse_score": float(s) if rk[1] > 0 else 0.0, "rrf_score": float(f)})
+                 for r, f, s, rk in zip(rows[i], rrf[i], sparse[i], ranks[i]) if r >= 0] for i in range(Q)]
+
+    def _unfiltered_only(self, tenants, run):
+        """[] for every filtered query, run(sel) for the queries `sel` that are not filtered"""
+        sel = [i for i, t in enumerate(tenants) if t < 0]
+        out = [[] for _ in tenants]
+        for i, res in zip(sel, run(sel)):
+            out[i] = res
+        return out
+
+    def search_m3_many(self, agent_id, queries: List[str], top_k: int = 5, pool: int = 100, weights=(0.4, 0.2, 0.4),
+                       candidates: str = "union") -> List[List[Dict[str, Any]]]:
+        """Batched `search_m3`: ONE encode_multi forward for all queries, then ONE device call with a tenant per query
+        (rag_retrieve_m3_tenants_dev: candidates "dense" / "dense+sparse" / "union" = its modes 0 / 1 / 2) - candidates, the three
+        components and the top-k without a host round trip in between. agent_id: one agent, None (not filtered), or a list with
+        one of either per query. Element i equals `search_m3(agent_id[i], queries[i], top_k, pool, weights, candidates)`: the same
+        rows in the same order, scores and components equal as floats; an unknown agent gets []. weights (0, 0, 1) with candidates
+        "dense" is search_late_interaction's ranking. Never raises: an error is logged and answered with `search_many`."""
+        try:
+            if candidates not in ("union", "dense", "dense+sparse"):
+                raise ValueError(f"unknown candidates {candidates!r}")
+            w = tuple(float(x) for x in weights)
+            if len(w) != 3:
+                raise ValueError("weights are (dense, sparse, colbert)")
+            if not queries:
+                return []
+            need_sparse = w[1] > 0 or candidates != "dense"
+            enc = self.embeddings.encode_multi(list(queries), return_dense=True, return_sparse=need_sparse, return_colbert_vecs=w[2] > 0)
+            with self._lock:
+                return self._search_m3_many_locked(agent_id, enc, len(queries), int(top_k), int(pool), w, candidates)
+        except Exception as e:
+            logger.error("Batched three-way search failed, answering with search_many: %s", e)
+            return self.search_many(agent_id, queries, top_k, with_embeddings=False)
+
+    def _search_m3_many_locked(self, agent_id, enc, Q, top_k, pool, w, candidates, rrf_k=60):
+        from .sparse import LexicalPostings
+        tenants = self._tenants_of(agent_id, Q)
+        if not self._tenant_id and (tenants >= 0).any():
+            return [[] for _ in range(Q)] if (tenants >= 0).all() else self._unfiltered_only(
+                tenants, lambda sel: self._search_m3_many_locked(None, _enc_rows(enc, sel), len(sel), top_k, pool, w, candidates, rrf_k))
+        pool = max(1, min(128 if candidates == "union" else 256, max(pool, top_k)))      # search_m3's clamp
+        k = min(top_k, 2 * pool if candidates == "union" else pool)
+        if k > pool:                                                     # more than a pool of the union: past the one-call form
+            agents = list(agent_id) if isinstance(agent_id, (list, tuple, np.ndarray)) else [agent_id] * Q
+            return [self._search_m3_locked(a, _enc_rows(enc, [i]), top_k, pool, w, candidates, rrf_k) for i, a in enumerate(agents)]
+        dev = self._to_device
+        kw = {}
+        if w[1] > 0 or candidates != "dense":
+            ptr, terms, qw = LexicalPostings.encode_queries(enc["lexical_weights"])
+            kw.update(term_ptr=dev(ptr), terms=dev(terms if len(terms) else np.zeros(1, np.int32)),
+                      weights=dev(qw if len(qw) else np.zeros(1, np.float32)))
+        if w[2] > 0:
+            vecs = [np.ascontiguousarray(v, dtype=np.float32) for v in enc["colbert_vecs"]]
+            off = np.concatenate([[0], np.cumsum([v.shape[0] for v in vecs])]).astype(np.int64)
+            flat = np.concatenate(vecs) if off[-1] else np.zeros((1, max(vecs[0].shape[1], 1)), np.float32)
+            kw.update(q_vecs=dev(flat), q_off=dev(off))
+        q = np.asarray(enc["dense_vecs"], dtype=np.float32).reshape(Q, self.dim)
+        mode = {"dense": 0, "dense+sparse": 1, "union": 2}[candidates]
+        ids, sc, comp, _ = self.engine.retrieve_m3_dev(dev(q), pool, k, mode=mode, w=w, rrf_k=rrf_k, tenant=tenants, **kw)
+        ids, sc, comp = self._to_host(ids, sc, comp)
+        rows = self._rows_of_ids(ids)
+        return [[self._payload(r, {"score": float(s), "dense_score": float(c[0]), "sparse_score": float(c[1]), "colbert_score": float(c[2])})
+                 for r, s, c in zip(rows[i], sc[i], comp[i]) if r >= 0] for i in range(Q)]
 
     def search_many(self, agent_id: str, queries: List[str], top_k: int = 5, with_embeddings: bool = True) -> List[List[Dict[str, Any]]]:
         """Batched `search` (the reference agent can only submit one query per call, so nothing in
