@@ -680,6 +680,33 @@ int rag_lexical_match_dev(rag_handle_t h, const int32_t* q_ids_dev, const float*
                           int q_seq_len, const int32_t* d_ids_dev, const float* d_weights_dev, const int32_t* d_lens_dev, int n_d,
                           int d_seq_len, const int32_t* pair_q_dev, const int32_t* pair_d_dev, int n_pairs,
                           const int32_t* skip_ids_host, int n_skip, float* out_dev, void* stream);
+/* Lexical compaction: a text's per-position lexical weights (lex_out of rag_embed_multi_*) -> its sparse vector, the query or
+ * document form the learned-sparse index takes (term_ptr / terms / qweights of rag_sparse_topk_*; a row of rag_sparse_append_host's
+ * CSR). ids / weights [n_texts][seq_len] int32 / float32, lens [n_texts]. Text i contributes the positions t < clamp(lens[i], 0,
+ * seq_len). A position is dropped if its id is in skip_ids (a HOST array in both forms, n_skip <= 8, as in rag_lexical_match_*), if
+ * its id is < 0, or if its weight is not > 0 (NaN, 0.0, -0.0 and negatives; +inf and float32 subnormals are kept). Of the rest each
+ * distinct id appears ONCE with the largest weight it carries, bit for bit, ids ascending within the text. Every id in
+ * [0, 2^31 - 1] is legal, INT32_MAX included. term_ptr_out [n_texts + 1] int32: term_ptr_out[0] = 0, term_ptr_out[i + 1] -
+ * term_ptr_out[i] = text i's count; terms_out / qweights_out: the texts' slices one after another. Layout, order and bits are those
+ * of the Python path: sparse.LexicalPostings.encode_queries over the {token id: largest weight > 0} maps of
+ * LocalEmbeddingService.encode_multi (tests/test_lexical_compact_cpu.py pins the two to each other).
+ * terms_cap = the entries terms_out / qweights_out hold. The library never writes an entry at or past terms_cap: _host returns
+ * RAG_ERR_ARG before any launch when the cap is too small; _dev drops what does not fit, and term_ptr_out[n_texts] still gives the
+ * true total (the tok_rows_cap rule of rag_embed_multi_dev). n_texts * seq_len always suffices. With terms_cap = 0 the two arrays
+ * may be NULL (counts only).
+ * Limits: 1 <= n_texts <= 65535, 1 <= seq_len <= 8192 (the longest sequence the embedder takes), n_texts * seq_len < 2^31, else
+ * RAG_ERR_ARG; a NULL array: RAG_ERR_ARG.
+ * Deterministic: a text's slice is a function of its own row alone, whatever seq_len, neighbours or batch the call holds.
+ * One workgroup per text sorts 64-bit (id, weight bits) keys in LDS (64 KiB at seq_len 8192), twice: the first pass leaves the
+ * counts in term_ptr_out, one workgroup turns them into offsets in place, the second pass writes the packed output. _host stages
+ * its arrays and waits; _dev is queued on `stream`, ordered as the preamble says, and keeps no workspace. */
+int rag_lexical_compact_host(rag_handle_t h, const int32_t* ids_host /*[n][L]*/, const float* weights_host /*[n][L]*/,
+                             const int32_t* lens_host /*[n]*/, int n_texts, int seq_len, const int32_t* skip_ids_host, int n_skip,
+                             int32_t* term_ptr_out_host /*[n+1]*/, int32_t* terms_out_host, float* qweights_out_host, int64_t terms_cap);
+int rag_lexical_compact_dev(rag_handle_t h, const int32_t* ids_dev /*[n][L]*/, const float* weights_dev /*[n][L]*/,
+                            const int32_t* lens_dev /*[n]*/, int n_texts, int seq_len, const int32_t* skip_ids_host, int n_skip,
+                            int32_t* term_ptr_out_dev /*[n+1]*/, int32_t* terms_out_dev, float* qweights_out_dev, int64_t terms_cap,
+                            void* stream);
 
 /* ---- retrieve + rerank in one device-resident call (BASELINE.json configs[3]): the composition of
  *      HybridRetriever.retrieve (rag/retrieval.py:122-212) and CrossEncoderReranker.rerank (rag/reranker.py:320-384:
@@ -961,6 +988,35 @@ int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const in
                                 int k, int rrf_k, const int32_t* tenants_host, int mode, double w_dense, double w_sparse,
                                 double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
                                 double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/, void* stream);
+
+/* ---- bge-m3 search from query token ids in one device-resident call: the forward, the compaction of its lexical weights and the
+ *      three-way search, with nothing on the host in between (no reference counterpart).
+ * rag_search_m3_tokens_dev is rag_embed_multi_dev on the handle's embedder (input_ids / token_type_ids [n_queries][seq_len],
+ *   lens [n_queries]) into handle-owned buffers - dense [Q][hidden], lexical weights [Q][seq_len], token vectors at a capacity of
+ *   Q * (seq_len - 1) rows (a text never has more: the capacity is known without reading lens) and their row offsets - then
+ *   rag_lexical_compact_dev (skip_ids_host / n_skip: its arguments) at capacity Q * seq_len, then rag_retrieve_m3_dev with q_off =
+ *   the forward's row offsets; pool, k, rrf_k, tenant, mode, the weights and the four outputs are rag_retrieve_m3_dev's. EVERY
+ *   OUTPUT IS BIT-IDENTICAL to those three calls made one after another by the caller, for every mode and weight set: the call runs
+ *   the same three functions with the same arguments on `stream`.
+ *   What is not needed is neither computed nor required: w_colbert == 0 takes no token-vector head, workspace or store; w_sparse == 0
+ *   with mode 0 takes no lexical head, no compaction and no postings.
+ *   RAG_ERR_STATE: no embedder loaded (rag_embed_load_host), or a head the weights or the mode need is missing
+ *   (rag_embed_heads_load_host); RAG_ERR_ARG: an embedder whose output width differs from the index dimension, or whose token
+ *   vectors are not as wide as the resident store's; n_queries / seq_len outside rag_lexical_compact_dev's limits. Every argument
+ *   and state error of the three underlying calls keeps its own code and message; those of the search and of the forward are
+ *   reported before anything is queued.
+ *   The buffers are planes of the handle-owned pipeline workspace, carved once per call beside rag_retrieve_m3_dev's own: nothing
+ *   waits for the device in the steady state; the first call of a larger shape grows the workspace as the preamble says.
+ * rag_search_m3_tokens_tenants_dev: the same with a tenant per query, under the rules of the "a tenant PER QUERY" block above. */
+int rag_search_m3_tokens_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev,
+                             int n_queries, int seq_len, const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k, int tenant,
+                             int mode, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
+                             double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/, void* stream);
+int rag_search_m3_tokens_tenants_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev,
+                                     const int32_t* lens_dev, int n_queries, int seq_len, const int32_t* skip_ids_host, int n_skip,
+                                     int pool, int k, int rrf_k, const int32_t* tenants_host, int mode, double w_dense, double w_sparse,
+                                     double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
+                                     double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/, void* stream);
 
 /* ---- the exchange step of the row-sharded search (the reference is single-process) bound to RCCL
  *      directly, for hosts that do not want torch.distributed in the path: ONE all-gather of each rank's partial top-k lists

@@ -156,6 +156,8 @@ _SIGS = {
     "rag_maxsim_dev": ([_P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
     "rag_lexical_match_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P], C.c_int),
     "rag_lexical_match_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P], C.c_int),
+    "rag_lexical_compact_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int64], C.c_int),
+    "rag_lexical_compact_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int64, _P], C.c_int),
     "rag_tokvec_reserve": ([_P, C.c_int64, C.c_int64, C.c_int], C.c_int),
     "rag_tokvec_reserve_form": ([_P, C.c_int64, C.c_int64, C.c_int, C.c_int], C.c_int),
     "rag_tokvec_load_form_host": ([_P, _P, _P, C.c_int64, C.c_int, C.c_int], C.c_int),
@@ -174,6 +176,8 @@ _SIGS = {
                                _P], C.c_int),
     "rag_retrieve_m3_dev": ([_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                              C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "rag_search_m3_tokens_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  C.c_double, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "rag_model_seq_limit": ([_P, C.c_int, C.POINTER(C.c_int)], C.c_int),
 }
@@ -182,7 +186,7 @@ _SIGS = {
 for _name, _pos in (("rag_dense_topk_host", 4), ("rag_dense_topk_dev", 4), ("rag_bm25_topk_host", 5), ("rag_bm25_topk_dev", 5),
                     ("rag_hybrid_rrf_dev", 8), ("rag_hybrid_linear_dev", 9), ("rag_retrieve_rerank_dev", 11),
                     ("rag_sparse_topk_host", 6), ("rag_sparse_topk_dev", 6), ("rag_hybrid_sparse_rrf_dev", 9),
-                    ("rag_retrieve_maxsim_dev", 11), ("rag_retrieve_m3_dev", 11)):
+                    ("rag_retrieve_maxsim_dev", 11), ("rag_retrieve_m3_dev", 11), ("rag_search_m3_tokens_dev", 11)):
     _args, _res = _SIGS[_name]
     assert _args[_pos] is C.c_int
     _SIGS[_name.replace("_host", "_tenants_host").replace("_dev", "_tenants_dev")] = (_args[:_pos] + [_P] + _args[_pos + 1:], _res)
@@ -1034,6 +1038,33 @@ class RagEngine:
                                                    p(d_weights), p(d_lens), d_ids.shape[0], d_ids.shape[1], p(pair_q), p(pair_d),
                                                    pair_q.shape[0], _ptr(sk), sk.shape[0], p(out), st), "rag_lexical_match_dev")
 
+    def lexical_compact(self, ids, weights, lens, skip_ids=(), terms_cap=None):
+        """Per-position lexical weights -> every text's sparse vector: ids / weights [n, L], lens [n] -> (term_ptr int32 [n + 1],
+        terms int32, weights float32), each text's distinct ids ascending with the largest weight > 0 each carries; the ids in
+        skip_ids (at most 8), ids < 0 and weights that are not > 0 are left out. The arrays LexicalPostings.encode_queries builds
+        from encode_multi's maps. terms_cap (default: n * L, always enough) below the call's total is an error."""
+        ii, ww, ln = _np(ids, np.int32), _np(weights, np.float32), _np(lens, np.int32)
+        n, L = ii.shape
+        sk = _np(list(skip_ids), np.int32)
+        cap = n * L if terms_cap is None else int(terms_cap)
+        ptr = np.zeros((n + 1,), dtype=np.int32)
+        terms, qw = np.empty((max(cap, 1),), dtype=np.int32), np.empty((max(cap, 1),), dtype=np.float32)
+        self._check(self.lib.rag_lexical_compact_host(self.h, _ptr(ii), _ptr(ww), _ptr(ln), n, L, _ptr(sk), sk.shape[0], _ptr(ptr), _ptr(terms),
+                                                      _ptr(qw), cap), "rag_lexical_compact_host")
+        return ptr, terms[:int(ptr[n])].copy(), qw[:int(ptr[n])].copy()
+
+    def lexical_compact_dev(self, ids, weights, lens, term_ptr, terms, qweights, skip_ids=(), stream=None):
+        """The same on CUDA tensors (skip_ids stays a host sequence): int32 term_ptr [n + 1], int32 terms and float32 qweights of
+        one capacity (n * L always suffices); asynchronous on `stream`. Entries past the capacity are dropped and term_ptr[n]
+        still holds the true total."""
+        import torch
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        sk = _np(list(skip_ids), np.int32)
+        cap = 0 if terms is None else int(terms.shape[0])
+        self._check(self.lib.rag_lexical_compact_dev(self.h, p(ids), p(weights), p(lens), ids.shape[0], ids.shape[1], _ptr(sk), sk.shape[0],
+                                                     p(term_ptr), p(terms), p(qweights), cap, st), "rag_lexical_compact_dev")
+
     # ---- resident token-vector store and late-interaction rerank (rag_tokvec_*, rag_retrieve_maxsim_dev) ---------
     TOKVEC_FORMS = {"fp16": 0, "mxfp8": 1}
 
@@ -1227,6 +1258,31 @@ class RagEngine:
         self._check(fn(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), int(Q), int(pool),
                        int(k), int(rrf_k), _ptr(t) if per_query else t, int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids),
                        p(sc), p(comp), p(cand), st), name)
+        return ids, sc, comp, cand
+
+    def search_m3_tokens_dev(self, input_ids, token_type_ids, lens, pool, k, skip_ids=(), mode=2, w=(0.4, 0.2, 0.4), rrf_k=60, tenant=-1,
+                             stream=None):
+        """Query token ids -> the three-way ranking in ONE device-resident call (rag_search_m3_tokens_dev / _tenants_dev): the forward
+        of the handle's embedder, the compaction of its lexical weights and retrieve_m3_dev, with the same bits as those three calls
+        made one after another. int32 CUDA tensors [Q, L], [Q, L], [Q]; the other arguments and the result are retrieve_m3_dev's."""
+        import torch
+        Q, L = input_ids.shape
+        dev = input_ids.device
+        slots = 2 * int(pool) if int(mode) == 2 else int(pool)
+        key = ("m3", Q, slots, k)
+        if getattr(self, "_m3_key", None) != key:
+            self._m3 = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float64, device=dev),
+                        torch.empty((Q, k, 3), dtype=torch.float64, device=dev), torch.empty((Q, slots), dtype=torch.int64, device=dev))
+            self._m3_key = key
+        ids, sc, comp, cand = self._m3
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        sk = _np(list(skip_ids), np.int32)
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = (self.lib.rag_search_m3_tokens_tenants_dev, "rag_search_m3_tokens_tenants_dev") if per_query else \
+            (self.lib.rag_search_m3_tokens_dev, "rag_search_m3_tokens_dev")
+        self._check(fn(self.h, p(input_ids), p(token_type_ids), p(lens), int(Q), int(L), _ptr(sk), sk.shape[0], int(pool), int(k), int(rrf_k),
+                       _ptr(t) if per_query else t, int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids), p(sc), p(comp), p(cand), st), name)
         return ids, sc, comp, cand
 
     def tokens_load(self, tokens, lens, id_bits=16):

@@ -963,6 +963,25 @@ int rag_lexical_match_dev(rag_handle_t h, const int32_t* q_ids, const float* q_w
                              (hipStream_t)stream);
 }
 
+int rag_lexical_compact_host(rag_handle_t h, const int32_t* ids, const float* weights, const int32_t* lens, int n_texts, int L,
+                             const int32_t* skip_ids, int n_skip, int32_t* term_ptr_out, int32_t* terms_out, float* qweights_out,
+                             int64_t terms_cap) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return lexical_compact_host(h, ids, weights, lens, n_texts, L, skip_ids, n_skip, term_ptr_out, terms_out, qweights_out, terms_cap);
+}
+
+int rag_lexical_compact_dev(rag_handle_t h, const int32_t* ids, const float* weights, const int32_t* lens, int n_texts, int L,
+                            const int32_t* skip_ids_host, int n_skip, int32_t* term_ptr_out, int32_t* terms_out, float* qweights_out,
+                            int64_t terms_cap, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return lexical_compact_dev(h, ids, weights, lens, n_texts, L, skip_ids_host, n_skip, term_ptr_out, terms_out, qweights_out, terms_cap,
+                               (hipStream_t)stream);
+}
+
 int rag_ce_length_class(int head_dim, int seq_len, int* class_out) {
     const int c = ce_length_class(head_dim, seq_len);
     if (!class_out || c == 0) return RAG_ERR_ARG;
@@ -1267,6 +1286,33 @@ int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const in
     if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, (hipStream_t)stream, &t)) return rc;
     return retrieve_m3_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, n_queries, pool, k, rrf_k, t.tenant, mode,
                            w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream, t.qt);
+}
+
+int rag_search_m3_tokens_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev,
+                             int n_queries, int seq_len, const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k, int tenant,
+                             int mode, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
+                             double* components_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return search_m3_tokens_dev(h, input_ids_dev, token_type_ids_dev, lens_dev, n_queries, seq_len, skip_ids_host, n_skip, pool, k, rrf_k, tenant,
+                                mode, w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev,
+                                (hipStream_t)stream, {nullptr, nullptr});
+}
+int rag_search_m3_tokens_tenants_dev(rag_handle_t h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev,
+                                     int n_queries, int seq_len, const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k,
+                                     const int32_t* tenants_host, int mode, double w_dense, double w_sparse, double w_colbert,
+                                     int64_t* ids_out_dev, double* scores_out_dev, double* components_out_dev, int64_t* cand_out_dev,
+                                     void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, tenants_host && n_queries > 0 && n_queries <= 65535, "search_m3_tokens: null tenants array or bad n_queries");
+    DEV_ENTRY(h);
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, (hipStream_t)stream, &t)) return rc;
+    return search_m3_tokens_dev(h, input_ids_dev, token_type_ids_dev, lens_dev, n_queries, seq_len, skip_ids_host, n_skip, pool, k, rrf_k, t.tenant,
+                                mode, w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev,
+                                (hipStream_t)stream, t.qt);
 }
 
 }  // extern "C"

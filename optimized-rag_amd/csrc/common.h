@@ -219,6 +219,7 @@ struct rag_ctx : rag_device_mem {
     int attr_ce_attn64_lds = 0;              // the LDS-staged instance of ce_attention64_kernel (64-wide heads)
     int attr_ce_attn64s_lds = 0;             // its streamed instance (the length classes above 512)
     int attr_m3_gemm_lds = 0;                // the split GEMM with the fp32 epilogue (the embedder's token-vector head)
+    int attr_m3_compact_lds = 0;             // the two instances of m3_lexical_compact_kernel (m3_heads.hip): 64 KiB of keys at seq_len 8192
     rag_ce_model* ce = nullptr;
     rag_ce_model* emb = nullptr;             // sentence-embedding encoder (rag_embed_load_host): the K7 kernels behind a mean-pooling head
 };
@@ -538,6 +539,7 @@ int embed_load_host(rag_ctx* h, const rag_ce_config* cfg, const float* const* te
 int embed_run(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* out, hipStream_t st,
               bool host_ptrs);
 int embed_dim(const rag_ctx* h);
+int embed_tok_dim(const rag_ctx* h);     // width of the loaded token-vector head, 0 without one, -1 without an embedder
 // the embedder's optional token-vector and lexical heads, and one forward with up to three outputs (cross_encoder.hip)
 int embed_heads_load_host(rag_ctx* h, const float* tok_w, const float* tok_b, int tok_dim, const float* lex_w, float lex_b);
 int embed_multi_host(rag_ctx* h, const int32_t* ids, const int32_t* tt, const int32_t* lens, int P, int L, float* dense, float* lex, float* tok,
@@ -555,6 +557,11 @@ int lexical_match_host(rag_ctx* h, const int32_t* q_ids, const float* q_w, const
 int lexical_match_dev(rag_ctx* h, const int32_t* q_ids, const float* q_w, const int32_t* q_lens, int n_q, int Lq, const int32_t* d_ids,
                       const float* d_w, const int32_t* d_lens, int n_d, int Ld, const int32_t* pair_q, const int32_t* pair_d, int n_pairs,
                       const int32_t* skip_ids_host, int n_skip, float* out, hipStream_t st);
+// ... and a text's per-position lexical weights reduced to its sorted sparse vector (rag_lexical_compact_*)
+int lexical_compact_host(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids, int n_skip,
+                         int32_t* term_ptr_out, int32_t* terms_out, float* qw_out, int64_t cap);
+int lexical_compact_dev(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids_host, int n_skip,
+                        int32_t* term_ptr_out, int32_t* terms_out, float* qw_out, int64_t cap, hipStream_t st);
 // tokvec.hip: the resident token-vector store and MaxSim rerank over it. tokvec_rerank checks the store and its arguments, scores
 // [Q][pool] slots and selects through tokvec_topk (pipeline.hip: the kernel behind rag_rerank_topk_dev, without the sigmoid).
 int tokvec_reserve(rag_ctx* h, int64_t n_docs_total, int64_t rows_total, int dim, int form);
@@ -599,3 +606,8 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
                     const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
                     double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
                     hipStream_t st, query_tenants qt);
+// token ids -> the forward (h->emb), the compaction of its lexical weights, retrieve_m3_dev: rag_search_m3_tokens(_tenants)_dev
+int search_m3_tokens_dev(rag_ctx* h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev, int Q, int L,
+                         const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k, int tenant, int mode, double w_dense, double w_sparse,
+                         double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out, hipStream_t st,
+                         query_tenants qt);

@@ -1991,3 +1991,4 @@ static int ce_probe_mx(rag_ctx* h, rag_ce_model* m) {
 }
 
 int embed_dim(const rag_ctx* h) { return h->emb ? h->emb->cfg.hidden : -1; }
+int embed_tok_dim(const rag_ctx* h) { return h->emb ? h->emb->heads.tok_dim : -1; }

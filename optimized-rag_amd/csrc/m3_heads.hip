@@ -1,6 +1,9 @@
 // Pair scoring for the embedder's token-vector and lexical heads (rag_embed_multi_*; cross_encoder.hip computes the heads):
 //   m3_maxsim_kernel          late interaction ("ColBERT" MaxSim): (1 / nq) * sum_i max_j <vq[i], vd[j]> over the texts' own rows
 //   m3_lexical_match_kernel   sum over the token ids both texts hold of (max weight in q) * (max weight in d)
+// and the reduction of a text's per-position lexical weights to its sorted sparse vector (rag_lexical_compact_*):
+//   m3_lexical_compact_kernel one workgroup per text: the largest weight > 0 of each distinct id, ids ascending, by a sort in LDS
+//   m3_term_ptr_kernel        the per-text counts -> term_ptr, one workgroup
 // Semantics restated from FlagEmbedding's BGEM3FlagModel (colbert_score / compute_lexical_matching_score); parity with upstream is
 // not pinned.
 //
@@ -20,6 +23,7 @@
 // own rows alone, bit-identical from run to run and whatever else the call holds.
 #include "common.h"
 
+#include <algorithm>
 #include <cmath>
 
 #define MS_QT 2          // 16-row query tiles per block of queries
@@ -187,6 +191,130 @@ __global__ __launch_bounds__(256) void m3_lexical_match_kernel(const int32_t* __
     if (tid == 0) out[pair] = (float)part[0];
 }
 
+// ---- lexical compaction (rag_lexical_compact_*): a text's per-position lexical weights -> its sparse vector, the largest weight > 0
+// of each distinct token id, ids ascending - what LexicalPostings.encode_queries builds from encode_multi's maps. One workgroup per
+// text sorts 64-bit keys (id << 32 | weight bits) in LDS; a dropped position (past the length, a skipped or negative id, a weight
+// that is not > 0) is the key of all ones, whose bit 63 no kept key has (ids end at 2^31 - 1), so it sorts behind every kept key and
+// INT32_MAX stays a legal id. Positive float32 bit patterns order as their values do: after ONE ascending sort the last key of an
+// id's run carries its largest weight, and a run's end is a position whose successor has another high word.
+// Bitonic network over N = the power of two >= max(len, 64) keys. Stages whose partner distance is below 64 run in registers: a
+// wave holds 64 consecutive keys, one per lane, and exchanges by lane shuffles (a distance below 32 keys would put lanes l and l + 16
+// of a 32-lane LDS group on one bank: 2-way on every read); the stages at distance >= 64 read and write 32 consecutive 8-byte keys per
+// 32-lane group, one 256-byte bank row, without conflicts. Each text is sorted twice - COUNT (the per-text counts, which the scan
+// turns into term_ptr in place) and WRITE (the packed output at its offset) - rather than staged through an [n][L] plane: a query
+// is tens of tokens, a passage's sort a few microseconds, and the call keeps no workspace.
+#define LC_DROPPED 0xFFFFFFFFFFFFFFFFull
+
+__device__ __forceinline__ unsigned long long lc_exchange(unsigned long long v, int idx, int j, int k) {
+    const unsigned long long o = __shfl_xor(v, j);
+    const bool keep_min = ((idx & j) == 0) == ((idx & k) == 0);
+    return keep_min ? (v < o ? v : o) : (v < o ? o : v);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void m3_lexical_compact_kernel(const int32_t* __restrict__ ids, const float* __restrict__ weights,
+                                                                  const int32_t* __restrict__ lens, int L, m3_skip skip,
+                                                                  int32_t* __restrict__ term_ptr, int32_t* __restrict__ terms_out,
+                                                                  float* __restrict__ qweights_out, int64_t cap) {
+    extern __shared__ unsigned long long lc_keys[];            // N keys
+    __shared__ int wave_total[4];
+    const int text = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = max(0, min(lens[text], L));
+    int N = 64;
+    while (N < m) N <<= 1;
+    const int32_t* id_row = ids + (size_t)text * L;
+    const float* w_row = weights + (size_t)text * L;
+    // keys in, every phase up to k = 64 in registers
+    for (int c = wv; c < (N >> 6); c += 4) {
+        const int idx = (c << 6) + lane;
+        unsigned long long v = LC_DROPPED;
+        if (idx < m) {
+            const int32_t id = id_row[idx];
+            const float w = w_row[idx];
+            bool use = id >= 0 && w > 0.f;
+            for (int s = 0; s < skip.n; ++s) use = use && id != skip.id[s];
+            if (use) v = ((unsigned long long)(uint32_t)id << 32) | (unsigned long long)__float_as_uint(w);
+        }
+        for (int k = 2; k <= 64; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) v = lc_exchange(v, idx, j, k);
+        lc_keys[idx] = v;
+    }
+    __syncthreads();
+    for (int k = 128; k <= N; k <<= 1) {
+        for (int j = k >> 1; j >= 64; j >>= 1) {
+            for (int p = tid; p < (N >> 1); p += 256) {
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                const unsigned long long a = lc_keys[i], b = lc_keys[i + j];
+                if ((a > b) == ((i & k) == 0)) {
+                    lc_keys[i] = b;
+                    lc_keys[i + j] = a;
+                }
+            }
+            __syncthreads();
+        }
+        for (int c = wv; c < (N >> 6); c += 4) {
+            const int idx = (c << 6) + lane;
+            unsigned long long v = lc_keys[idx];
+            for (int j = 32; j > 0; j >>= 1) v = lc_exchange(v, idx, j, k);
+            lc_keys[idx] = v;
+        }
+        __syncthreads();
+    }
+    // the run ends, counted in key order 256 at a time: a position's output slot is the run ends before it
+    int before = 0;                                            // run ends in the chunks so far (the same in every thread)
+    const int64_t base = WRITE ? (int64_t)term_ptr[text] : 0;
+    for (int c0 = 0; c0 < N; c0 += 256) {
+        const int i = c0 + tid;
+        unsigned long long v = LC_DROPPED;
+        bool end = false;
+        if (i < N) {
+            v = lc_keys[i];
+            end = v != LC_DROPPED && (i == N - 1 || (lc_keys[i + 1] >> 32) != (v >> 32));
+        }
+        const unsigned long long vote = __ballot(end);
+        if (lane == 0) wave_total[wv] = __popcll(vote);
+        __syncthreads();
+        int mine = before + __popcll(vote & ((1ull << lane) - 1ull));
+        for (int x = 0; x < 4; ++x) {
+            if (x < wv) mine += wave_total[x];
+            before += wave_total[x];
+        }
+        if (WRITE && end && base + mine < cap) {
+            terms_out[base + mine] = (int32_t)(v >> 32);
+            qweights_out[base + mine] = __uint_as_float((uint32_t)v);
+        }
+        __syncthreads();
+    }
+    if (!WRITE && tid == 0) term_ptr[text + 1] = before;
+}
+
+// term_ptr[i + 1] holds text i's count on entry; on exit term_ptr is the exclusive prefix (term_ptr[0] = 0, term_ptr[n] = the call's
+// true total). One workgroup, every thread a contiguous span of texts, as m3_row_off_kernel (cross_encoder.hip); in place: a thread
+// reads and writes the entries of its own span only.
+__global__ __launch_bounds__(1024) void m3_term_ptr_kernel(int32_t* __restrict__ term_ptr, int n) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x;
+    const int per = (n + 1023) / 1024;
+    const int b = min(n, tid * per), e = min(n, b + per);
+    int s = 0;
+    for (int p = b; p < e; ++p) s += term_ptr[p + 1];
+    part[tid] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int off = part[tid] - s;
+    for (int p = b; p < e; ++p) {
+        off += term_ptr[p + 1];
+        term_ptr[p + 1] = off;
+    }
+    if (tid == 0) term_ptr[0] = 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
@@ -276,5 +404,78 @@ int lexical_match_host(rag_ctx* h, const int32_t* q_ids, const float* q_w, const
     rc = lexical_match_dev(h, dqi, dqw, dql, n_q, Lq, ddi, ddw, ddl, n_d, Ld, dpq, dpd, n_pairs, skip_ids, n_skip, dout, st);
     if (!rc) HIP_TRY(h, hipMemcpyAsync(out, dout, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
+    return rc;
+}
+
+static int lexical_compact_check(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids,
+                                 int n_skip, const int32_t* term_ptr_out, const int32_t* terms_out, const float* qw_out, int64_t cap) {
+    ARG_CHECK(h, n >= 1 && n <= 65535 && L >= 1 && L <= 8192 && (int64_t)n * L < ((int64_t)1 << 31),
+              "lexical_compact: 1 <= n_texts <= 65535, 1 <= seq_len <= 8192, n_texts * seq_len < 2^31");
+    ARG_CHECK(h, n_skip >= 0 && n_skip <= 8 && (skip_ids || n_skip == 0), "lexical_compact: at most 8 skip ids");
+    ARG_CHECK(h, cap >= 0, "lexical_compact: terms_cap must be >= 0");
+    ARG_CHECK(h, ids && w && lens && term_ptr_out && ((terms_out && qw_out) || cap == 0), "lexical_compact: null argument");
+    return RAG_OK;
+}
+
+static int lexical_compact_run(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids,
+                               int n_skip, int32_t* term_ptr_out, int32_t* terms_out, float* qw_out, int64_t cap, hipStream_t st) {
+    m3_skip skip = {};
+    for (int i = 0; i < n_skip; ++i) skip.id[i] = skip_ids[i];
+    skip.n = n_skip;
+    int N = 64;
+    while (N < L) N <<= 1;
+    const int lds = N * 8;
+    if (int rc = raise_lds(h, h->attr_m3_compact_lds, lds, m3_lexical_compact_kernel<false>, m3_lexical_compact_kernel<true>)) return rc;
+    launch(m3_lexical_compact_kernel<false>, dim3((unsigned)n), dim3(256), (size_t)lds, st, ids, w, lens, L, skip, term_ptr_out, nullptr, nullptr,
+           (int64_t)0);
+    launch(m3_term_ptr_kernel, dim3(1), dim3(1024), 0, st, term_ptr_out, n);
+    if (cap > 0)
+        launch(m3_lexical_compact_kernel<true>, dim3((unsigned)n), dim3(256), (size_t)lds, st, ids, w, lens, L, skip, term_ptr_out, terms_out, qw_out,
+               cap);
+    return launch_status(h);
+}
+
+int lexical_compact_dev(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids_host, int n_skip,
+                        int32_t* term_ptr_out, int32_t* terms_out, float* qw_out, int64_t cap, hipStream_t st) {
+    if (int rc = lexical_compact_check(h, ids, w, lens, n, L, skip_ids_host, n_skip, term_ptr_out, terms_out, qw_out, cap)) return rc;
+    return lexical_compact_run(h, ids, w, lens, n, L, skip_ids_host, n_skip, term_ptr_out, terms_out, qw_out, cap, st);
+}
+
+// Host arrays: the total is counted on the host before anything is queued (the distinct kept ids of each text), so a capacity that is
+// too small is an error here; the device-pointer path then runs on staged copies and the call waits.
+int lexical_compact_host(rag_ctx* h, const int32_t* ids, const float* w, const int32_t* lens, int n, int L, const int32_t* skip_ids, int n_skip,
+                         int32_t* term_ptr_out, int32_t* terms_out, float* qw_out, int64_t cap) {
+    int rc;
+    if ((rc = lexical_compact_check(h, ids, w, lens, n, L, skip_ids, n_skip, term_ptr_out, terms_out, qw_out, cap))) return rc;
+    int64_t total = 0;
+    std::vector<int32_t> kept;
+    for (int i = 0; i < n; ++i) {
+        const int m = std::max(0, std::min(lens[i], L));
+        kept.clear();
+        for (int t = 0; t < m; ++t) {
+            const int32_t id = ids[(size_t)i * L + t];
+            bool use = id >= 0 && w[(size_t)i * L + t] > 0.f;
+            for (int s = 0; s < n_skip; ++s) use = use && id != skip_ids[s];
+            if (use) kept.push_back(id);
+        }
+        std::sort(kept.begin(), kept.end());
+        total += std::unique(kept.begin(), kept.end()) - kept.begin();
+    }
+    ARG_CHECK(h, total <= cap, "lexical_compact: terms_cap is smaller than the call's terms");
+    hipStream_t st = h->stream;
+    const size_t n_tok = (size_t)n * L;
+    dev_buf<int32_t> d_ids, d_lens, d_ptr, d_terms;
+    dev_buf<float> d_w, d_qw;
+    if ((rc = stage_in(h, d_ids, ids, n_tok, st)) || (rc = stage_in(h, d_w, w, n_tok, st)) || (rc = stage_in(h, d_lens, lens, (size_t)n, st))) return rc;
+    if ((rc = d_ptr.alloc(h, (size_t)n + 1)) || (rc = d_terms.alloc(h, (size_t)std::max<int64_t>(total, 1))) ||
+        (rc = d_qw.alloc(h, (size_t)std::max<int64_t>(total, 1))))
+        return rc;
+    rc = lexical_compact_run(h, d_ids, d_w, d_lens, n, L, skip_ids, n_skip, d_ptr, d_terms, d_qw, total, st);
+    if (!rc) HIP_TRY(h, hipMemcpyAsync(term_ptr_out, d_ptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (!rc && total > 0) {
+        HIP_TRY(h, hipMemcpyAsync(terms_out, d_terms, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(qw_out, d_qw, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));                   // also before the staging buffers go
     return rc;
 }

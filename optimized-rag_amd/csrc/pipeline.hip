@@ -595,33 +595,104 @@ int m3_score_rows_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_pt
 // candidates, then the three-way score, in one device-resident call. mode 0 / 1: the candidates of retrieve_maxsim_dev; mode 2: the
 // UNION of the dense top-pool and the sparse top-pool = what rrf_fuse_dev over the two lists returns at top_k = 2 * pool (RRF order,
 // -1 padded): 2 * pool slots. The candidate stage runs in row space as in retrieve_maxsim_dev; the combine kernel maps the ids.
-int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
-                    const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
-                    double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
-                    hipStream_t st, query_tenants qt) {
+struct m3_retrieve_ws { cand_ws cw; double *dn, *sp; };              // the candidate planes, the dense and the sparse component [Q][S]
+static void m3_retrieve_planes(ws_carve& c, m3_retrieve_ws& w, int Q, int pool, int mode) {
+    const size_t P = (size_t)Q * pool, PS = (size_t)Q * cand_slots(mode, pool);
+    cand_ws_planes(c, w.cw, P, PS, true);
+    w.dn = c.take<double>(PS);
+    w.sp = c.take<double>(PS);
+}
+// every check of rag_retrieve_m3_dev: the arguments, then the resident structures the weights and the mode need
+static int retrieve_m3_check(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const float* qweights_dev, const float* q_vecs_dev,
+                             const int64_t* q_off_dev, int Q, int pool, int k, int tenant, int mode, m3_weights w, const int64_t* ids_out,
+                             const double* scores_out, query_tenants qt) {
     ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "retrieve_m3: mode is 0 (dense), 1 (dense + sparse RRF) or 2 (union of dense and sparse)");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= (mode == 2 ? RAG_MAX_K / 2 : RAG_MAX_K) && k > 0 && k <= pool,
               "retrieve_m3: 1 <= n_queries <= 65535, 0 < k <= pool <= 256 (mode 2: pool <= 128)");
-    const int S = cand_slots(mode, pool);
-    ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "retrieve_m3: n_queries * candidate slots must be below 2^24");
+    ARG_CHECK(h, (int64_t)Q * cand_slots(mode, pool) < ((int64_t)1 << 24), "retrieve_m3: n_queries * candidate slots must be below 2^24");
     ARG_CHECK(h, q_emb_dev && ids_out && scores_out, "retrieve_m3: null argument");
-    const m3_weights w = {w_dense, w_sparse, w_colbert};
     if (int rc = m3_check(h, "retrieve_m3", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
     ARG_CHECK(h, (tenant < 0 && qt.host == nullptr) || h->tenants != nullptr, "retrieve_m3: tenant filter requested but no tenants loaded");
     if (mode != 0) {
         ARG_CHECK(h, term_ptr_dev && qweights_dev, "retrieve_m3: modes 1 and 2 need the query's terms and weights");
         if (int rc = keyword_postings_aligned(h, true, "retrieve_m3", RAG_ERR_STATE)) return rc;
     }
-    const size_t P = (size_t)Q * pool, PS = (size_t)Q * S;
-    cand_ws cw;
-    double *dn, *sp;                                                   // the dense and the sparse component [Q][S]
+    return RAG_OK;
+}
+static int retrieve_m3_run(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                           const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, m3_weights w,
+                           const m3_retrieve_ws& ws, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out, hipStream_t st,
+                           query_tenants qt) {
+    if (int rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, qt, mode, ws.cw, st)) return rc;
+    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, ws.cw.rows, Q, cand_slots(mode, pool), k, ws.dn,
+                          ws.sp, ids_out, nullptr, scores_out, components_out, cand_out, st);
+}
+
+int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                    const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
+                    double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
+                    hipStream_t st, query_tenants qt) {
+    const m3_weights w = {w_dense, w_sparse, w_colbert};
+    if (int rc = retrieve_m3_check(h, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, tenant, mode, w, ids_out, scores_out, qt))
+        return rc;
+    m3_retrieve_ws ws;
+    if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { m3_retrieve_planes(c, ws, Q, pool, mode); })) return rc;
+    return retrieve_m3_run(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, tenant, mode, w, ws, ids_out,
+                           scores_out, components_out, cand_out, st, qt);
+}
+
+// ---- token ids in, the three-way ranking out (rag_search_m3_tokens_dev / _tenants_dev): rag_embed_multi_dev on the handle's embedder,
+// rag_lexical_compact_dev on its lexical weights, rag_retrieve_m3_dev on the three results, with every intermediate - dense [Q][hidden],
+// lexical [Q][L], token vectors [Q * (L - 1)][tok_dim] (a text has at most L - 1 rows: the capacity needs no look at lens), row offsets,
+// the query CSR at capacity Q * L - carved from pipe_ws in ONE carve beside retrieve_m3_dev's own planes. The three stages are the
+// functions behind those entries, called with the same arguments a caller would pass, on the same stream: the outputs are the bits
+// of the three calls made one after another. What a zero weight or mode 0 does not need is neither carved nor computed.
+int search_m3_tokens_dev(rag_ctx* h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev, int Q, int L,
+                         const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k, int tenant, int mode, double w_dense, double w_sparse,
+                         double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out, hipStream_t st,
+                         query_tenants qt) {
+    int tok_dim = 0;
+    const int hidden = embed_dim(h);
+    if (hidden < 0) {
+        h->err = "search_m3_tokens: no embedding model loaded (rag_embed_load_host)";
+        return RAG_ERR_STATE;
+    }
+    ARG_CHECK(h, hidden == h->dim, "search_m3_tokens: the embedder's output width differs from the index dimension");
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && L > 0 && L <= 8192 && (int64_t)Q * L < ((int64_t)1 << 31),
+              "search_m3_tokens: 1 <= n_queries <= 65535, 1 <= seq_len <= 8192, n_queries * seq_len < 2^31");
+    const m3_weights w = {w_dense, w_sparse, w_colbert};
+    const bool want_tok = w_colbert > 0.0, want_lex = w_sparse > 0.0 || mode != 0;
+    if (want_tok) {
+        tok_dim = embed_tok_dim(h);
+        if (tok_dim <= 0) {
+            h->err = "search_m3_tokens: the token-vector head is not loaded (rag_embed_heads_load_host)";
+            return RAG_ERR_STATE;
+        }
+    }
+    m3_retrieve_ws ws;
+    float *dense = nullptr, *lex = nullptr, *tok = nullptr, *qw = nullptr;
+    int64_t* row_off = nullptr;
+    int32_t *term_ptr = nullptr, *terms = nullptr;
+    const int64_t tok_cap = (int64_t)Q * (L - 1), terms_cap = (int64_t)Q * L;
     int rc = pipe_ws_carve(h, [&](ws_carve& c) {
-        cand_ws_planes(c, cw, P, PS, true);
-        dn = c.take<double>(PS);
-        sp = c.take<double>(PS);
+        if (mode >= 0 && mode <= 2 && pool > 0 && pool <= RAG_MAX_K) m3_retrieve_planes(c, ws, Q, pool, mode);
+        dense = c.take<float>((size_t)Q * hidden);
+        if (want_lex) {
+            lex = c.take<float>((size_t)Q * L);
+            term_ptr = c.take<int32_t>((size_t)Q + 1);
+            terms = c.take<int32_t>((size_t)terms_cap);
+            qw = c.take<float>((size_t)terms_cap);
+        }
+        if (want_tok) {
+            tok = c.take<float>((size_t)std::max<int64_t>(tok_cap, 1) * tok_dim);
+            row_off = c.take<int64_t>((size_t)Q + 1);
+        }
     });
     if (rc) return rc;
-    if ((rc = candidate_stage(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, Q, pool, rrf_k, tenant, qt, mode, cw, st))) return rc;
-    return m3_score_slots(h, w, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cw.rows, Q, S, k, dn, sp, ids_out, nullptr,
-                          scores_out, components_out, cand_out, st);
+    if ((rc = retrieve_m3_check(h, dense, term_ptr, qw, tok, row_off, Q, pool, k, tenant, mode, w, ids_out, scores_out, qt))) return rc;
+    ARG_CHECK(h, !want_tok || tok_dim == h->tv_dim, "search_m3_tokens: the embedder's token vectors are not as wide as the resident store's");
+    if ((rc = embed_multi_dev(h, input_ids_dev, token_type_ids_dev, lens_dev, Q, L, dense, lex, tok, tok_cap, row_off, st))) return rc;
+    if (want_lex && (rc = lexical_compact_dev(h, input_ids_dev, lex, lens_dev, Q, L, skip_ids_host, n_skip, term_ptr, terms, qw, terms_cap, st))) return rc;
+    return retrieve_m3_run(h, dense, term_ptr, terms, qw, tok, row_off, Q, pool, k, rrf_k, tenant, mode, w, ws, ids_out, scores_out, components_out,
+                           cand_out, st, qt);
 }

@@ -269,7 +269,7 @@ class GpuDocumentIndex:
         want_lex = self._lexical is not None
         want_tok = self.engine.tokvec_info()["dim"] > 0
         svc._need_heads(want_lex, want_tok)
-        skip = set(svc.special_ids())
+        skip = svc.special_ids()
         ids_out: List[int] = []
         batch = max(1, int(batch))
         for b in range(0, len(texts), batch):
@@ -283,20 +283,17 @@ class GpuDocumentIndex:
                 rows = int((np.clip(lens, 1, L).astype(np.int64) - 1).sum())
                 tok = torch.empty((max(rows, 1), int(svc.engine.embed_tok_dim)), dtype=torch.float32, device="cuda")
                 off = torch.empty((n + 1,), dtype=torch.int64, device="cuda")
-            svc.engine.embed_multi_dev(torch.from_numpy(ids).cuda(), torch.from_numpy(tt).cuda(), torch.from_numpy(lens).cuda(),
-                                       dense=dense, lex=lex, tok=tok, row_off=off)
-            torch.cuda.synchronize()
+            d_ids, d_lens = torch.from_numpy(ids).cuda(), torch.from_numpy(lens).cuda()
+            svc.engine.embed_multi_dev(d_ids, torch.from_numpy(tt).cuda(), d_lens, dense=dense, lex=lex, tok=tok, row_off=off)
             maps = None
-            if want_lex:                                             # the largest weight > 0 of each token id, special tokens left out (encode_multi)
-                lx = lex.cpu().numpy()
-                maps = []
-                for i in range(n):
-                    m: Dict[int, float] = {}
-                    for t in range(int(lens[i])):
-                        k, w = int(ids[i, t]), float(lx[i, t])
-                        if k not in skip and w > 0 and w > m.get(k, 0.0):
-                            m[k] = w
-                    maps.append(m)
+            if want_lex:                                             # the largest weight > 0 of each token id, special tokens left out (encode_multi):
+                ptr = torch.empty((n + 1,), dtype=torch.int32, device="cuda")                 # reduced on the device (rag_lexical_compact_dev)
+                terms = torch.empty((n * L,), dtype=torch.int32, device="cuda")
+                qw = torch.empty((n * L,), dtype=torch.float32, device="cuda")
+                svc.engine.lexical_compact_dev(d_ids, lex, d_lens, ptr, terms, qw, skip_ids=skip)
+                ptr, terms, qw = self._to_host(ptr, terms, qw)
+                maps = [dict(zip(terms[a:b].tolist(), qw[a:b].tolist())) for a, b in zip(ptr[:-1], ptr[1:])]
+            torch.cuda.synchronize()
             rows_ = [{"agent_id": agent_id, "content": t, "metadata": dict(metadata or {}),
                       **({"document_id": int(document_id)} if document_id is not None else {})} for t in part]
             ids_out += self.add_rows(rows_, dense.cpu().numpy(), lexical_weights=maps, token_vectors=(tok, off) if want_tok else None)
@@ -521,14 +518,16 @@ class GpuDocumentIndex:
 
     # ---- bge-m3's three-way score over the resident legs (rag_m3_score_rows_dev) --------------------------------------------
     def search_m3(self, agent_id: str, query: str, top_k: int = 5, pool: int = 100, weights=(0.4, 0.2, 0.4),
-                  candidates: str = "union") -> List[Dict[str, Any]]:
+                  candidates: str = "union", device_query: bool = False) -> List[Dict[str, Any]]:
         """Rank by bge-m3's "colbert+sparse+dense" score: (w_colbert * colbert + w_sparse * sparse + w_dense * dense) / sum, weights =
         (dense, sparse, colbert), every component exact for every candidate and computed from resident data - the fp32 rows, the
         lexical postings (load_lexical), the token vectors (load_token_vectors / build_token_vectors). candidates "union": the dense
         top-`pool` and the sparse top-`pool` together (pool <= 128); "dense": the dense top-`pool`; "dense+sparse": their reciprocal
         rank fusion, top-`pool`. A weight of 0 leaves its component and its resident structure out. The query goes through ONE
         encode_multi forward. Result dicts are `search`'s (without embeddings) plus `dense_score`, `sparse_score`, `colbert_score`
-        and `score`. Never raises: an error (a missing or stale leg, a missing head) is logged and answered with `search`."""
+        and `score`. Never raises: an error (a missing or stale leg, a missing head) is logged and answered with `search`.
+        device_query: the query is tokenised on the host and everything else - forward, lexical compaction, candidates, score -
+        runs on the device without a host round trip (search_m3_many's device_query, for one query); the same result."""
         try:
             if candidates not in ("union", "dense", "dense+sparse"):
                 raise ValueError(f"unknown candidates {candidates!r}")
@@ -536,6 +535,10 @@ class GpuDocumentIndex:
             if len(w) != 3:
                 raise ValueError("weights are (dense, sparse, colbert)")
             need_sparse = w[1] > 0 or candidates != "dense"
+            if device_query:
+                res = self._m3_device_query(agent_id, [query], int(top_k), int(pool), w, candidates)
+                if res is not None:
+                    return res[0]
             enc = self.embeddings.encode_multi([query], return_dense=True, return_sparse=need_sparse, return_colbert_vecs=w[2] > 0)
             with self._lock:
                 return self._search_m3_locked(agent_id, enc, top_k, int(pool), w, candidates)
@@ -636,19 +639,28 @@ class GpuDocumentIndex:
                 "metadata": row.get("metadata") or {}, **extra}
 
     def search_lexical_many(self, agent_id, queries: List[str], top_k: int = 5, mode: str = "dense+sparse", pool: int = 100,
-                            rrf_k: int = 60) -> List[List[Dict[str, Any]]]:
+                            rrf_k: int = 60, device_query: bool = False) -> List[List[Dict[str, Any]]]:
         """Batched `search_lexical`: ONE encode_multi forward for all queries, then ONE search call with a tenant per query -
         rag_sparse_topk_tenants_host (mode "sparse") or rag_hybrid_sparse_rrf_tenants_dev (mode "dense+sparse"; the fused hits'
         `sparse_score` is then read back with one point lookup, rag_sparse_score_rows_host, whose bits are the search's).
         agent_id: one agent, None (not filtered), or a list with one of either per query. Element i equals
         `search_lexical(agent_id[i], queries[i], top_k, mode, pool, rrf_k)`; an unknown agent gets []. Errors are logged and
-        answered with [] for every query."""
+        answered with [] for every query. device_query: the queries' CSR is built on the device (the forward, then
+        rag_lexical_compact_dev) and handed to the device forms of the same searches; the same result."""
         try:
             if mode not in ("dense+sparse", "sparse"):
                 raise ValueError(f"unknown mode {mode!r}")
             if not queries:
                 return []
             fused = mode == "dense+sparse"
+            svc = self._device_query_service() if device_query else None
+            if svc is not None:
+                svc._need_heads(True, False)
+                toks = svc.tokenize(list(queries))
+                with self._lock:
+                    res = self._search_lexical_many_device(agent_id, svc, toks, int(top_k), fused, pool, rrf_k)
+                if res is not None:
+                    return res
             enc = self.embeddings.encode_multi(list(queries), return_dense=fused, return_sparse=True, return_colbert_vecs=False)
             with self._lock:
                 return self._search_lexical_many_locked(agent_id, enc, len(queries), int(top_k), fused, pool, rrf_k)
@@ -679,6 +691,96 @@ class GpuDocumentIndex:
         return [[self._payload(r, {"score": float(f), "sparse_score": float(s) if rk[1] > 0 else 0.0, "rrf_score": float(f)})
                  for r, f, s, rk in zip(rows[i], rrf[i], sparse[i], ranks[i]) if r >= 0] for i in range(Q)]
 
+    # ---- the query path on the device (device_query=True): token ids in, nothing on the host until the results are copied out ----
+    def _device_query_service(self):
+        """the embedding service when it can hand over token ids (tokenize, special_ids, an engine), else None and one logged line"""
+        svc = self.embeddings
+        if all(callable(getattr(svc, m, None)) for m in ("tokenize", "special_ids", "_need_heads")) and getattr(svc, "engine", None) is not None:
+            return svc
+        logger.info("device_query: the embedding service offers no tokenize / special_ids; taking the host-assembled query path")
+        return None
+
+    def _query_forward_dev(self, svc, toks, want_dense, want_lex, want_tok):
+        """embed_multi_dev + lexical_compact_dev on the service's engine, on the current stream: dict(q_emb, term_ptr, terms,
+        weights, q_vecs, q_off) of CUDA tensors (None where not asked for), at the capacities rag_search_m3_tokens_dev uses"""
+        import torch
+        ids, tt, lens = (self._to_device(a) for a in toks)
+        Q, L = ids.shape
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device="cuda")
+        out = dict.fromkeys(("q_emb", "term_ptr", "terms", "weights", "q_vecs", "q_off"))
+        lex = new((Q, L), torch.float32) if want_lex else None
+        if want_dense:
+            out["q_emb"] = new((Q, svc.dimensions), torch.float32)
+        tok = None
+        if want_tok:
+            out["q_vecs"] = new((max(Q * (L - 1), 1), int(svc.engine.embed_tok_dim)), torch.float32)
+            out["q_off"] = new((Q + 1,), torch.int64)
+            tok = out["q_vecs"][:Q * (L - 1)]
+        svc.engine.embed_multi_dev(ids, tt, lens, dense=out["q_emb"], lex=lex, tok=tok, row_off=out["q_off"])
+        if want_lex:
+            out.update(term_ptr=new((Q + 1,), torch.int32), terms=new((Q * L,), torch.int32), weights=new((Q * L,), torch.float32))
+            svc.engine.lexical_compact_dev(ids, lex, lens, out["term_ptr"], out["terms"], out["weights"], skip_ids=svc.special_ids())
+        return out
+
+    def _m3_device_query(self, agent_id, queries, top_k, pool, w, candidates, rrf_k=60):
+        """search_m3_many's result through the device query path, or None where that path does not apply (a service without
+        token ids, more than a pool of the union asked for, no agent known at all): the caller goes on as without device_query.
+        One call (rag_search_m3_tokens(_tenants)_dev) when the service runs on the index's engine, else the forward and the
+        compaction on the service's engine and rag_retrieve_m3(_tenants)_dev on the index's, all on the current stream."""
+        svc = self._device_query_service()
+        if svc is None:
+            return None
+        need_sparse = w[1] > 0 or candidates != "dense"
+        svc._need_heads(need_sparse, w[2] > 0)
+        toks = svc.tokenize([str(q) for q in queries])                   # outside the index lock, as the forward of the host path
+        with self._lock:
+            Q = len(queries)
+            tenants = self._tenants_of(agent_id, Q)
+            if not self._tenant_id and (tenants >= 0).any():
+                return None
+            pool = max(1, min(128 if candidates == "union" else 256, max(pool, top_k)))      # search_m3's clamp
+            k = min(top_k, 2 * pool if candidates == "union" else pool)
+            if k > pool:
+                return None
+            mode = {"dense": 0, "dense+sparse": 1, "union": 2}[candidates]
+            if svc.engine is self.engine:
+                ids, tt, lens = (self._to_device(a) for a in toks)
+                ids, sc, comp, _ = self.engine.search_m3_tokens_dev(ids, tt, lens, pool, k, skip_ids=svc.special_ids(), mode=mode, w=w,
+                                                                    rrf_k=rrf_k, tenant=tenants)
+            else:
+                f = self._query_forward_dev(svc, toks, True, need_sparse, w[2] > 0)
+                ids, sc, comp, _ = self.engine.retrieve_m3_dev(f.pop("q_emb"), pool, k, mode=mode, w=w, rrf_k=rrf_k, tenant=tenants, **f)
+            ids, sc, comp = self._to_host(ids, sc, comp)
+            rows = self._rows_of_ids(ids)
+            return [[self._payload(r, {"score": float(s), "dense_score": float(c[0]), "sparse_score": float(c[1]), "colbert_score": float(c[2])})
+                     for r, s, c in zip(rows[i], sc[i], comp[i]) if r >= 0] for i in range(Q)]
+
+    def _search_lexical_many_device(self, agent_id, svc, toks, top_k, fused, pool, rrf_k):
+        """_search_lexical_many_locked with the queries' CSR built on the device; None where it does not apply"""
+        import torch
+        Q = int(toks[0].shape[0])
+        tenants = self._tenants_of(agent_id, Q)
+        if not self._tenant_id and (tenants >= 0).any():
+            return None
+        f = self._query_forward_dev(svc, toks, fused, True, False)
+        ptr, terms, qw = f["term_ptr"], f["terms"], f["weights"]
+        if not fused:
+            ids = torch.empty((Q, top_k), dtype=torch.int64, device="cuda")
+            rows = torch.empty((Q, top_k), dtype=torch.int32, device="cuda")
+            sc = torch.empty((Q, top_k), dtype=torch.float64, device="cuda")
+            self.engine.sparse_topk_dev(ptr, terms, qw, top_k, ids, rows, sc, tenant=tenants)
+            rows, sc = self._to_host(rows, sc)
+            return [[self._payload(r, {"score": float(s), "sparse_score": float(s)}) for r, s in zip(rows[i], sc[i]) if r >= 0]
+                    for i in range(Q)]
+        keys, rrf, ranks = self.engine.hybrid_sparse_rrf_dev(f["q_emb"], ptr, terms, qw, max(top_k, pool), top_k, rrf_k=rrf_k, tenant=tenants)
+        keys, rrf, ranks = self._to_host(keys, rrf, ranks)
+        rows = self._rows_of_ids(keys)
+        sparse = torch.empty((Q, top_k), dtype=torch.float64, device="cuda")
+        self.engine.sparse_score_rows_dev(ptr, terms, qw, self._to_device(rows.astype(np.int32)), sparse)
+        sparse, = self._to_host(sparse)
+        return [[self._payload(r, {"score": float(f_), "sparse_score": float(s) if rk[1] > 0 else 0.0, "rrf_score": float(f_)})
+                 for r, f_, s, rk in zip(rows[i], rrf[i], sparse[i], ranks[i]) if r >= 0] for i in range(Q)]
+
     def _unfiltered_only(self, tenants, run):
         """[] for every filtered query, run(sel) for the queries `sel` that are not filtered"""
         sel = [i for i, t in enumerate(tenants) if t < 0]
@@ -688,13 +790,18 @@ class GpuDocumentIndex:
         return out
 
     def search_m3_many(self, agent_id, queries: List[str], top_k: int = 5, pool: int = 100, weights=(0.4, 0.2, 0.4),
-                       candidates: str = "union") -> List[List[Dict[str, Any]]]:
+                       candidates: str = "union", device_query: bool = False) -> List[List[Dict[str, Any]]]:
         """Batched `search_m3`: ONE encode_multi forward for all queries, then ONE device call with a tenant per query
         (rag_retrieve_m3_tenants_dev: candidates "dense" / "dense+sparse" / "union" = its modes 0 / 1 / 2) - candidates, the three
         components and the top-k without a host round trip in between. agent_id: one agent, None (not filtered), or a list with
         one of either per query. Element i equals `search_m3(agent_id[i], queries[i], top_k, pool, weights, candidates)`: the same
         rows in the same order, scores and components equal as floats; an unknown agent gets []. weights (0, 0, 1) with candidates
-        "dense" is search_late_interaction's ranking. Never raises: an error is logged and answered with `search_many`."""
+        "dense" is search_late_interaction's ranking. Never raises: an error is logged and answered with `search_many`.
+        device_query (needs a local embedding service with `tokenize` and `special_ids`; any other falls back to the path above
+        with one logged line): the queries are tokenised on the host and everything else runs on the device with no host round
+        trip until the ids, scores and components are copied out - rag_search_m3_tokens(_tenants)_dev when the service runs on the
+        index's engine, else embed_multi_dev + lexical_compact_dev on the service's engine and retrieve_m3_dev on the index's.
+        The result is the same: the same rows in the same order, scores and components equal as floats."""
         try:
             if candidates not in ("union", "dense", "dense+sparse"):
                 raise ValueError(f"unknown candidates {candidates!r}")
@@ -704,6 +811,10 @@ class GpuDocumentIndex:
             if not queries:
                 return []
             need_sparse = w[1] > 0 or candidates != "dense"
+            if device_query:
+                res = self._m3_device_query(agent_id, list(queries), int(top_k), int(pool), w, candidates)
+                if res is not None:
+                    return res
             enc = self.embeddings.encode_multi(list(queries), return_dense=True, return_sparse=need_sparse, return_colbert_vecs=w[2] > 0)
             with self._lock:
                 return self._search_m3_many_locked(agent_id, enc, len(queries), int(top_k), int(pool), w, candidates)
