@@ -820,7 +820,9 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
  *   Deletes need nothing: the composite's searches hide deleted rows, and the explicit-row entries do not look.
  * Ordering: reserve / load / append_host / fetch / rerank_host are host calls (they wait for queued *_dev work); the _dev calls
  *   follow the preamble, rag_tokvec_append_dev waiting for `stream` as said.
- * Sharding: raw MaxSim scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev.
+ * Sharding: a candidate's token vectors live on the rank that holds its row, and the candidates come from GLOBAL lists, so a
+ *   merge of per-shard results does not give rag_retrieve_maxsim_dev: the owning rank scores each candidate and the top-k runs
+ *   over the gathered scores (the three rag_m3_*_gathered / _score_ids entries below with weights (0, 0, 1)).
  * Storage forms. A store is reserved in one of two forms; RAG_TOKVEC_FP16 (the default, everything above) or RAG_TOKVEC_MXFP8:
  *   OCP MXFP8, E4M3 codes with one shared power-of-two scale per 32 consecutive components, 33/64 of the fp16 form's passage
  *   bytes. For a block with amax = max |x|: the scale exponent e is the smallest integer with amax <= 448 * 2^e, clamped to
@@ -909,7 +911,8 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
  * Live writes: the rules of the sparse postings and of the token-vector store hold for the components that use them;
  *   rag_sparse_append_host / rag_tokvec_append_* after inserts and rag_index_compact_live keep all three current.
  * Ordering: rag_sparse_score_rows_host is a host call; the _dev calls follow the preamble.
- * Sharding: raw scores need no global statistic, so per-shard lists merge through rag_merge_topk_dev. */
+ * Sharding: the sparse LIST alone merges through rag_merge_topk_dev (raw scores need no global statistic). The composites do
+ *   not: RRF needs global ranks and each candidate is scored by the rank that owns its row - the row-sharded entries below. */
 int rag_sparse_score_rows_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                               const int32_t* cand_rows_dev, int n_queries, int pool, double* scores_out_dev, void* stream);
 int rag_sparse_score_rows_host(rag_handle_t h, const int32_t* term_ptr_host, const int32_t* terms_host, const float* qweights_host,
@@ -924,6 +927,55 @@ int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* t
                         int rrf_k, int tenant, int mode, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
                         double* scores_out_dev, double* components_out_dev /*may be NULL*/, int64_t* cand_out_dev /*may be NULL*/,
                         void* stream);
+
+/* ---- rag_retrieve_m3_dev over ROW SHARDS (one handle per GPU; DESIGN.md section 5, sharded.py ShardedM3Index). Every rank holds
+ *      a contiguous row range loaded with id_base = its first global row: the embeddings, the doc-partitioned sparse postings and
+ *      the token vectors of its own documents (either storage form); the query arrays are replicated. Two small all-gathers per
+ *      batch, and three entries for the work between them:
+ *        local lists (rag_dense_topk_dev and rag_sparse_topk_dev at k = pool, tenants as in those entries)  ->  gather 1  ->
+ *        rag_m3_candidates_gathered_dev  ->  rag_m3_score_ids_dev  ->  gather 2  ->  rag_m3_combine_gathered_dev.
+ *      RRF needs GLOBAL ranks, so the lists are merged before they are fused; a candidate's token vectors live on one rank, so
+ *      the rank that owns a candidate scores it; the combine and the top-k then run over components that came from different ranks.
+ * rag_m3_candidates_gathered_dev: gathered_dev = [world][4][Q][pool] int64 = every rank's dense ids | dense cosines (float64
+ *   bits) | sparse ids | RAW sparse scores (float64 bits), -1 / 0.0 padded anywhere in a list. Merges the dense lists and the
+ *   sparse lists as rag_merge_topk_dev does (score desc, id asc, -1 skipped, nothing normalised) into lists_out_dev [2][Q][pool]
+ *   int64 and scores_out_dev [2][Q][pool] float64, then forms the candidate list of rag_retrieve_m3_dev in id space, cand_out_dev
+ *   [Q][slots] int64: mode 0 the merged dense list (slots = pool); mode 1 the RRF of the two merged lists at rrf_k, top-pool
+ *   (slots = pool); mode 2 the same RRF at top_k = 2 * pool (slots = 2 * pool, pool <= 128), -1 padded. In mode 0 planes 2-3 of
+ *   gathered_dev are not read and the sparse halves of lists_out / scores_out are filled with -1 / 0.0. Limits: 1 <= n_queries <=
+ *   65535, 0 < pool <= 256 (mode 2: 128), n_queries * slots < 2^24, world * pool <= 4092 (the merge kernel's LDS), else
+ *   RAG_ERR_ARG. Needs no index. Bit-identical to the merged lists and the cand_out of rag_retrieve_m3_dev on the unsharded index
+ *   (loaded with id_base): a merged list is the unsharded list because the order (score desc, id asc) is total and the scores are
+ *   functions of (query, row); RRF then sees the same two lists.
+ * rag_m3_score_ids_dev: cand_ids_dev [Q][slots] int64 GLOBAL ids (-1 = empty). A slot is OWNED iff id_base <= id < id_base +
+ *   index rows. partial_out_dev [4][Q][slots] int64 = owned flag (1 / 0) | dense | sparse | colbert, the three components as float64
+ *   bits (colbert: the float32 pair score widened) from the launches rag_m3_score_rows_dev uses, on row = id - id_base; an unowned
+ *   slot carries 0 | 0.0 | 0.0 | 0.0. Weights as rag_m3_score_rows_dev: a weight of 0 computes nothing, writes 0.0 and requires
+ *   neither its query arrays nor its resident structure. Limits: 1 <= n_queries <= 65535, 0 < slots <= 256, n_queries * slots <
+ *   2^24. RAG_ERR_STATE on an index with explicit ids (rag_index_set_ids_host, or ids at the load): ownership is defined through
+ *   id_base alone; the other errors are those of rag_m3_score_rows_dev. Row visibility is not looked at: the candidate searches hid
+ *   what is hidden. With w_dense == 0 and w_sparse == 0 the call is the late-interaction rerank: a slot MaxSim leaves empty (the
+ *   query or the document has no token vectors) is reported UNOWNED, so the combine skips it as the top-k of rag_retrieve_maxsim_dev
+ *   does. This is the one place where the three entries differ from rag_retrieve_m3_dev, which at weights (0, 0, w) ranks such a
+ *   slot with 0.0.
+ * rag_m3_combine_gathered_dev: gathered_dev = [world][4][Q][slots] int64, every rank's partial_out. Each slot takes the components
+ *   of the rank that set its owned flag; a slot with cand < 0 or without an owner is empty (skipped, as cand < 0 is in
+ *   rag_m3_score_rows_dev); with more than one owner - overlapping shards, a caller error - the LOWEST rank wins. Then the score,
+ *   the stable top-k (score desc, slot asc) and the outputs of rag_retrieve_m3_dev: ids_out [Q][k] (the slot's cand id), scores_out
+ *   [Q][k], components_out [Q][k][3] (may be NULL), padded -1 / 0.0. Weights: finite, each >= 0, sum > 0. Limits: world >= 1,
+ *   1 <= n_queries <= 65535, 0 < k <= slots <= 256, n_queries * slots < 2^24. Needs no index. Bit-identical (ids, float64 score and
+ *   component bits) to rag_retrieve_m3_dev on the unsharded index; with weights (0, 0, 1) the score is (1 * c + 0) + 0 over
+ *   (0 + 0) + 1 = c exactly, so ids and scores are those of rag_retrieve_maxsim_dev.
+ * Workspaces are handle-owned, carved once per call; all three follow the preamble's ordering rules. */
+int rag_m3_candidates_gathered_dev(rag_handle_t h, const int64_t* gathered_dev, int world, int n_queries, int pool, int rrf_k, int mode,
+                                   int64_t* lists_out_dev, double* scores_out_dev, int64_t* cand_out_dev, void* stream);
+int rag_m3_score_ids_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                         const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, const int64_t* cand_ids_dev,
+                         int n_queries, int slots, double w_dense, double w_sparse, double w_colbert, int64_t* partial_out_dev,
+                         void* stream);
+int rag_m3_combine_gathered_dev(rag_handle_t h, const int64_t* cand_ids_dev, const int64_t* gathered_dev, int world, int n_queries,
+                                int slots, int k, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
+                                double* scores_out_dev, double* components_out_dev /*may be NULL*/, void* stream);
 
 /* ---- agents mixed in one batch: a tenant PER QUERY. Each entry takes the arguments of its namesake with
  *      `const int32_t* tenants_host` [n_queries] where the namesake has `int tenant`: query i is filtered by tenants_host[i],

@@ -176,6 +176,10 @@ _SIGS = {
                                _P], C.c_int),
     "rag_retrieve_m3_dev": ([_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                              C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "rag_m3_candidates_gathered_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
+    "rag_m3_score_ids_dev": ([_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P], C.c_int),
+    "rag_m3_combine_gathered_dev": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P],
+                                    C.c_int),
     "rag_search_m3_tokens_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                   C.c_double, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "rag_ce_length_class": ([C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
@@ -1259,6 +1263,43 @@ class RagEngine:
                        int(k), int(rrf_k), _ptr(t) if per_query else t, int(mode), float(w[0]), float(w[1]), float(w[2]), p(ids),
                        p(sc), p(comp), p(cand), st), name)
         return ids, sc, comp, cand
+
+    # ---- the row-sharded three-way search: the steps between the two all-gathers (sharded.ShardedM3Index drives them) ----------
+    def m3_candidates_gathered_dev(self, gathered, lists_out, scores_out, cand_out, mode=2, rrf_k=60, stream=None):
+        """gathered [world, 4, Q, pool] int64 (every rank's dense ids | cosine bits | sparse ids | raw sparse score bits) -> merged
+        lists [2, Q, pool] int64, their scores [2, Q, pool] float64 and the candidate ids [Q, slots] int64 of retrieve_m3_dev's
+        mode (slots = 2 * pool in mode 2, else pool). CUDA tensors; needs no index."""
+        import torch
+        world, _, Q, pool = gathered.shape
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_m3_candidates_gathered_dev(self.h, p(gathered), int(world), int(Q), int(pool), int(rrf_k), int(mode),
+                                                            p(lists_out), p(scores_out), p(cand_out), st), "rag_m3_candidates_gathered_dev")
+
+    def m3_score_ids_dev(self, cand_ids, partial_out, q_emb=None, term_ptr=None, terms=None, weights=None, q_vecs=None, q_off=None,
+                         w=(0.4, 0.2, 0.4), stream=None):
+        """The three components of the candidate ids [Q, slots] int64 whose rows this handle holds (id_base <= id < id_base + rows)
+        -> partial_out [4, Q, slots] int64 = owned flag | dense | sparse | colbert (float64 bits; 0 / 0.0 for a slot of another
+        rank). A weight of 0 leaves its component - and its inputs - out."""
+        import torch
+        Q, slots = cand_ids.shape
+        if q_vecs is not None and float(w[2]) > 0:
+            self._tokvec_rerank_check(tuple(q_vecs.shape), None, "m3_score_ids_dev")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_m3_score_ids_dev(self.h, p(q_emb), p(term_ptr), p(terms), p(weights), p(q_vecs), p(q_off), p(cand_ids), int(Q),
+                                                  int(slots), float(w[0]), float(w[1]), float(w[2]), p(partial_out), st), "rag_m3_score_ids_dev")
+
+    def m3_combine_gathered_dev(self, cand_ids, gathered, ids_out, scores_out, components_out=None, w=(0.4, 0.2, 0.4), stream=None):
+        """cand_ids [Q, slots] and every rank's partial block, gathered [world, 4, Q, slots] int64 -> the top k = ids_out.shape[1] of
+        retrieve_m3_dev: ids [Q, k] int64, scores [Q, k] float64, components [Q, k, 3] float64 (may be None). Needs no index."""
+        import torch
+        world, _, Q, slots = gathered.shape
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.rag_m3_combine_gathered_dev(self.h, p(cand_ids), p(gathered), int(world), int(Q), int(slots), int(ids_out.shape[1]),
+                                                         float(w[0]), float(w[1]), float(w[2]), p(ids_out), p(scores_out), p(components_out), st),
+                    "rag_m3_combine_gathered_dev")
 
     def search_m3_tokens_dev(self, input_ids, token_type_ids, lens, pool, k, skip_ids=(), mode=2, w=(0.4, 0.2, 0.4), rrf_k=60, tenant=-1,
                              stream=None):

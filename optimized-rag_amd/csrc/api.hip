@@ -1274,6 +1274,34 @@ int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* t
                            w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream,
                            {nullptr, nullptr});
 }
+// the row-sharded three-way search: the three steps between the two all-gathers (pipeline.hip)
+int rag_m3_candidates_gathered_dev(rag_handle_t h, const int64_t* gathered_dev, int world, int n_queries, int pool, int rrf_k, int mode,
+                                   int64_t* lists_out_dev, double* scores_out_dev, int64_t* cand_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return m3_candidates_gathered_dev(h, gathered_dev, world, n_queries, pool, rrf_k, mode, lists_out_dev, scores_out_dev, cand_out_dev,
+                                      (hipStream_t)stream);
+}
+int rag_m3_score_ids_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
+                         const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, const int64_t* cand_ids_dev,
+                         int n_queries, int slots, double w_dense, double w_sparse, double w_colbert, int64_t* partial_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return m3_score_ids_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, cand_ids_dev, n_queries, slots, w_dense,
+                            w_sparse, w_colbert, partial_out_dev, (hipStream_t)stream);
+}
+int rag_m3_combine_gathered_dev(rag_handle_t h, const int64_t* cand_ids_dev, const int64_t* gathered_dev, int world, int n_queries, int slots,
+                                int k, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev, double* scores_out_dev,
+                                double* components_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    DEV_ENTRY(h);
+    return m3_combine_gathered_dev(h, cand_ids_dev, gathered_dev, world, n_queries, slots, k, w_dense, w_sparse, w_colbert, ids_out_dev,
+                                   scores_out_dev, components_out_dev, (hipStream_t)stream);
+}
+
 int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                                 const float* qweights_dev, const float* q_vecs_dev, const int64_t* q_off_dev, int n_queries, int pool, int k,
                                 int rrf_k, const int32_t* tenants_host, int mode, double w_dense, double w_sparse, double w_colbert,

@@ -606,6 +606,17 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
                     const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode, double w_dense,
                     double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, int64_t* cand_out,
                     hipStream_t st, query_tenants qt);
+// the row-sharded form of retrieve_m3_dev, the halves on each side of its two all-gathers (rag_m3_candidates_gathered_dev,
+// rag_m3_score_ids_dev, rag_m3_combine_gathered_dev): candidates from every rank's lists, the components of the slots this handle's
+// rows own, combine + select over every rank's components. The two gathered ones need no index.
+int m3_candidates_gathered_dev(rag_ctx* h, const int64_t* gathered_dev, int world, int Q, int pool, int rrf_k, int mode, int64_t* lists_out,
+                               double* scores_out, int64_t* cand_out, hipStream_t st);
+int m3_score_ids_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                     const float* q_vecs_dev, const int64_t* q_off_dev, const int64_t* cand_ids_dev, int Q, int slots, double w_dense,
+                     double w_sparse, double w_colbert, int64_t* partial_out, hipStream_t st);
+int m3_combine_gathered_dev(rag_ctx* h, const int64_t* cand_ids_dev, const int64_t* gathered_dev, int world, int Q, int slots, int k,
+                            double w_dense, double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out,
+                            hipStream_t st);
 // token ids -> the forward (h->emb), the compaction of its lexical weights, retrieve_m3_dev: rag_search_m3_tokens(_tenants)_dev
 int search_m3_tokens_dev(rag_ctx* h, const int32_t* input_ids_dev, const int32_t* token_type_ids_dev, const int32_t* lens_dev, int Q, int L,
                          const int32_t* skip_ids_host, int n_skip, int pool, int k, int rrf_k, int tenant, int mode, double w_dense, double w_sparse,

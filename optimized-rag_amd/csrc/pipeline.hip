@@ -537,13 +537,18 @@ __global__ __launch_bounds__(256) void m3_combine_topk_kernel(const int32_t* __r
 
 struct m3_weights { double dense, sparse, colbert; };
 
+static int m3_weights_check(rag_ctx* h, const char* who, m3_weights w) {
+    ARG_CHECK(h, std::isfinite(w.dense) && std::isfinite(w.sparse) && std::isfinite(w.colbert) && w.dense >= 0.0 && w.sparse >= 0.0 &&
+                     w.colbert >= 0.0 && std::isfinite((w.dense + w.sparse) + w.colbert) && (w.dense + w.sparse) + w.colbert > 0.0,
+              (std::string(who) + ": the weights must be finite, each >= 0, with a sum > 0").c_str());
+    return RAG_OK;
+}
+
 // what both entries check: the weights, and the resident structures the non-zero ones need, aligned with the index's rows
 static int m3_check(rag_ctx* h, const char* who, m3_weights w, const float* q_emb, const int32_t* term_ptr, const float* qweights,
                     const float* q_vecs, const int64_t* q_off) {
     const std::string me(who);
-    ARG_CHECK(h, std::isfinite(w.dense) && std::isfinite(w.sparse) && std::isfinite(w.colbert) && w.dense >= 0.0 && w.sparse >= 0.0 &&
-                     w.colbert >= 0.0 && std::isfinite((w.dense + w.sparse) + w.colbert) && (w.dense + w.sparse) + w.colbert > 0.0,
-              (me + ": the weights must be finite, each >= 0, with a sum > 0").c_str());
+    if (int rc = m3_weights_check(h, who, w)) return rc;
     ARG_CHECK(h, h->index_loaded, (me + ": no index loaded").c_str());
     ARG_CHECK(h, w.dense == 0.0 || (q_emb != nullptr && (reinterpret_cast<uintptr_t>(q_emb) & 15) == 0),
               (me + ": a dense weight needs the query embeddings, 16-byte aligned").c_str());
@@ -639,6 +644,166 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
     if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { m3_retrieve_planes(c, ws, Q, pool, mode); })) return rc;
     return retrieve_m3_run(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, tenant, mode, w, ws, ids_out,
                            scores_out, components_out, cand_out, st, qt);
+}
+
+// ---- retrieve_m3_dev over row shards (sharded.py ShardedM3Index): the work between the two all-gathers of a batch.
+//   gather 1  [world][4][Q][pool]  every rank's dense ids | cosine bits | sparse ids | raw sparse score bits
+//   m3_candidates_gathered_dev     two merges (merge_topk_kernel: -1 skipped wherever it stands, nothing normalised), then the candidate
+//                                  list of candidate_stage in ID space: RRF sees the two merged lists, which are the unsharded lists
+//   m3_score_ids_dev               ids -> rows of this handle (m3_own_rows_kernel), the three component launches of m3_score_slots over
+//                                  the owned slots, packed as [4][Q][S] int64 (m3_pack_partial_kernel)
+//   gather 2  [world][4][Q][S]
+//   m3_combine_gathered_dev        m3_combine_topk_kernel with every slot's components taken from the rank that owns it
+// The component kernels are the ones the unsharded call launches and each component is a function of (query, row), so every bit of
+// the result is the unsharded call's.
+int m3_candidates_gathered_dev(rag_ctx* h, const int64_t* gathered_dev, int world, int Q, int pool, int rrf_k, int mode, int64_t* lists_out,
+                               double* scores_out, int64_t* cand_out, hipStream_t st) {
+    ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "m3_candidates_gathered: mode is 0 (dense), 1 (dense + sparse RRF) or 2 (union of dense and sparse)");
+    ARG_CHECK(h, world > 0 && Q > 0 && Q <= 65535 && pool > 0 && pool <= (mode == 2 ? RAG_MAX_K / 2 : RAG_MAX_K),
+              "m3_candidates_gathered: world >= 1, 1 <= n_queries <= 65535, 0 < pool <= 256 (mode 2: pool <= 128)");
+    ARG_CHECK(h, (int64_t)world * pool <= 4092, "m3_candidates_gathered: world * pool must be <= 4092");
+    const int S = cand_slots(mode, pool);
+    ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "m3_candidates_gathered: n_queries * candidate slots must be below 2^24");
+    ARG_CHECK(h, gathered_dev && lists_out && scores_out && cand_out, "m3_candidates_gathered: null argument");
+    const int64_t P = (int64_t)Q * pool, stride = 4 * P;
+    const double* gs = reinterpret_cast<const double*>(gathered_dev);
+    double* rrf = nullptr;                                             // the RRF scores [Q][S]: computed with the keys, not reported
+    if (mode != 0)
+        if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { rrf = c.take<double>((size_t)Q * S); })) return rc;
+    if (int rc = merge_topk(h, gathered_dev, gs + P, world, stride, Q, pool, lists_out, scores_out, st, 0)) return rc;
+    if (mode == 0) {
+        HIP_TRY(h, hipMemsetAsync(lists_out + P, 0xFF, (size_t)P * sizeof(int64_t), st));                  // -1
+        HIP_TRY(h, hipMemsetAsync(scores_out + P, 0, (size_t)P * sizeof(double), st));
+        HIP_TRY(h, hipMemcpyAsync(cand_out, lists_out, (size_t)P * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        return RAG_OK;
+    }
+    if (int rc = merge_topk(h, gathered_dev + 2 * P, gs + 3 * P, world, stride, Q, pool, lists_out + P, scores_out + P, st, 0)) return rc;
+    return rrf_fuse_dev(h, lists_out, Q, 2, pool, P, pool, rrf_k, S, cand_out, rrf, nullptr, st);
+}
+
+// ids -> the rows of this handle: rows[i] = id - id_base where that is a row of the index, else -1 (an empty slot to the component
+// kernels); owned[i] = 1 / 0, plane 0 of the partial block
+__global__ __launch_bounds__(256) void m3_own_rows_kernel(const int64_t* __restrict__ cand, int64_t n, int64_t id_base, int64_t n_rows,
+                                                           int32_t* __restrict__ rows, int64_t* __restrict__ owned) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t id = cand[i];
+    const bool mine = id >= id_base && id - id_base < n_rows;          // (id >= id_base first: id = -1 never wraps)
+    rows[i] = mine ? (int32_t)(id - id_base) : -1;
+    owned[i] = mine ? 1 : 0;
+}
+
+// planes 1-3 of the partial block [4][n]: the float64 bits of the three components, 0.0 for an unowned slot or an absent component.
+// scored != null (the late-interaction form, weights (0, 0, w)): the row MaxSim scored each slot for, -1 where it left the slot empty (a
+// query or a document without token vectors) - such a slot is given up: flag 0, so the combine skips it as the MaxSim rerank's top-k does.
+__global__ __launch_bounds__(256) void m3_pack_partial_kernel(const int32_t* __restrict__ rows, const double* __restrict__ dense,
+                                                               const double* __restrict__ sparse, const float* __restrict__ colbert,
+                                                               const int32_t* __restrict__ scored, int64_t n, int64_t* __restrict__ owned,
+                                                               double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool mine = rows[i] >= 0;
+    if (scored != nullptr && mine && scored[i] < 0) {
+        mine = false;
+        owned[i] = 0;
+    }
+    out[n + i] = mine && dense ? dense[i] : 0.0;
+    out[2 * n + i] = mine && sparse ? sparse[i] : 0.0;
+    out[3 * n + i] = mine && colbert ? (double)colbert[i] : 0.0;
+}
+
+int m3_score_ids_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                     const float* q_vecs_dev, const int64_t* q_off_dev, const int64_t* cand_ids_dev, int Q, int S, double w_dense, double w_sparse,
+                     double w_colbert, int64_t* partial_out, hipStream_t st) {
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && S > 0 && S <= RAG_MAX_K, "m3_score_ids: 1 <= n_queries <= 65535, 0 < slots <= 256");
+    ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "m3_score_ids: n_queries * slots must be below 2^24");
+    ARG_CHECK(h, cand_ids_dev && partial_out, "m3_score_ids: null argument");
+    const m3_weights w = {w_dense, w_sparse, w_colbert};
+    if (int rc = m3_check(h, "m3_score_ids", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
+    if (h->ids != nullptr) {
+        h->err = "m3_score_ids: the index has explicit ids; a row shard is loaded with id_base (ownership is id_base <= id < id_base + rows)";
+        return RAG_ERR_STATE;
+    }
+    const size_t P = (size_t)Q * S;
+    int32_t* rows;
+    double *dn, *sp;
+    if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { rows = c.take<int32_t>(P); dn = c.take<double>(P); sp = c.take<double>(P); })) return rc;
+    const dim3 grid((unsigned)((P + 255) / 256));
+    launch(m3_own_rows_kernel, grid, dim3(256), 0, st, cand_ids_dev, (int64_t)P, h->id_base, h->n_rows, rows, partial_out);
+    int rc;
+    const float* cb = nullptr;
+    const int32_t* scored = nullptr;
+    if (w.colbert > 0.0 && (rc = tokvec_score_slots(h, q_vecs_dev, q_off_dev, rows, Q, S, &cb, &scored, st))) return rc;
+    if (w.dense > 0.0 && (rc = dense_cosine_rows(h, q_emb_dev, rows, Q, S, dn, st))) return rc;
+    if (w.sparse > 0.0 && (rc = sparse_score_rows_dev(h, term_ptr_dev, terms_dev, qweights_dev, rows, Q, S, sp, st))) return rc;
+    const bool late = w.dense == 0.0 && w.sparse == 0.0;               // MaxSim alone: the late-interaction rerank
+    launch(m3_pack_partial_kernel, grid, dim3(256), 0, st, rows, w.dense > 0.0 ? dn : nullptr, w.sparse > 0.0 ? sp : nullptr, cb,
+           late ? scored : nullptr, (int64_t)P, partial_out, reinterpret_cast<double*>(partial_out));
+    return launch_status(h);
+}
+
+// m3_combine_topk_kernel over gathered partial blocks: one workgroup per query, S <= 256. Slot j takes its components from the first
+// rank r whose owned plane holds 1 at the slot (overlapping shards: the lowest rank wins); no owner, or cand < 0: an empty slot.
+// part = [world][4][n] int64, n = Q * S. The score, the stable rank and the writes are m3_combine_topk_kernel's.
+__global__ __launch_bounds__(256) void m3_combine_gathered_kernel(const int64_t* __restrict__ cand, const int64_t* __restrict__ part, int world,
+                                                                   int64_t n, int S, int k, double wd, double ws, double wc,
+                                                                   int64_t* __restrict__ ids_out, double* __restrict__ scores_out,
+                                                                   double* __restrict__ comp_out) {
+    __shared__ double s[256];
+    __shared__ int ok[256];
+    const int q = blockIdx.x, j = threadIdx.x;
+    double d = 0.0, sp = 0.0, c = 0.0, mine = 0.0;
+    int valid = 0;
+    int64_t id = -1;
+    if (j < S) {
+        const size_t at = (size_t)q * S + j;
+        id = cand[at];
+        int owner = -1;
+        for (int r = world - 1; r >= 0; --r)                           // (no early exit: the loads of the flags are independent)
+            if (part[(size_t)r * 4 * n + at] != 0) owner = r;
+        valid = id >= 0 && owner >= 0;
+        if (valid) {
+            const double* p = reinterpret_cast<const double*>(part + (size_t)owner * 4 * n);
+            d = p[n + at];
+            sp = p[2 * n + at];
+            c = p[3 * n + at];
+            mine = ((wc * c + ws * sp) + wd * d) / ((wd + ws) + wc);
+        }
+    }
+    s[j] = mine;
+    ok[j] = valid;
+    for (int i = j; i < k; i += 256) {
+        const size_t o = (size_t)q * k + i;
+        ids_out[o] = -1;
+        scores_out[o] = 0.0;
+        if (comp_out) comp_out[o * 3] = comp_out[o * 3 + 1] = comp_out[o * 3 + 2] = 0.0;
+    }
+    __syncthreads();
+    if (valid) {
+        const int rank = stable_rank(s, ok, S, j, mine);
+        if (rank < k) {
+            const size_t o = (size_t)q * k + rank;
+            ids_out[o] = id;
+            scores_out[o] = mine;
+            if (comp_out) {
+                comp_out[o * 3] = d;
+                comp_out[o * 3 + 1] = sp;
+                comp_out[o * 3 + 2] = c;
+            }
+        }
+    }
+}
+
+int m3_combine_gathered_dev(rag_ctx* h, const int64_t* cand_ids_dev, const int64_t* gathered_dev, int world, int Q, int S, int k, double w_dense,
+                            double w_sparse, double w_colbert, int64_t* ids_out, double* scores_out, double* components_out, hipStream_t st) {
+    ARG_CHECK(h, world > 0 && Q > 0 && Q <= 65535 && S > 0 && S <= RAG_MAX_K && k > 0 && k <= S,
+              "m3_combine_gathered: world >= 1, 1 <= n_queries <= 65535, 0 < k <= slots <= 256");
+    ARG_CHECK(h, (int64_t)Q * S < ((int64_t)1 << 24), "m3_combine_gathered: n_queries * slots must be below 2^24");
+    ARG_CHECK(h, cand_ids_dev && gathered_dev && ids_out && scores_out, "m3_combine_gathered: null argument");
+    if (int rc = m3_weights_check(h, "m3_combine_gathered", {w_dense, w_sparse, w_colbert})) return rc;
+    launch(m3_combine_gathered_kernel, dim3((unsigned)Q), dim3(256), 0, st, cand_ids_dev, gathered_dev, world, (int64_t)Q * S, S, k, w_dense,
+           w_sparse, w_colbert, ids_out, scores_out, components_out);
+    return launch_status(h);
 }
 
 // ---- token ids in, the three-way ranking out (rag_search_m3_tokens_dev / _tenants_dev): rag_embed_multi_dev on the handle's embedder,

@@ -5,6 +5,9 @@ postings, token ids) partitioned contiguously, ONE small collective per stage.
     hybrid:  local dense top-pool + local RAW BM25 top-pool (global idf / avgdl replicated)  ->  ONE all_gather of both
              lists  ->  rag_hybrid_fuse_gathered_dev: two merges, BM25 / global max, RRF on the MERGED lists (RRF needs
              GLOBAL ranks, so the lists are merged before fusing) - all inside the library
+    bge-m3:  local dense + sparse top-pool  ->  all_gather  ->  rag_m3_candidates_gathered_dev (merges, RRF on the merged lists)
+             ->  rag_m3_score_ids_dev (the rank that holds a candidate's rows and token vectors scores it)  ->  all_gather  ->
+             rag_m3_combine_gathered_dev (owner select, three-way combine, stable top-k): ShardedM3Index
     rerank:  the Q x pool pairs are independent: each rank scores a contiguous slice (rag_ce_score_dev), one all_gather
              of the logits
 
@@ -129,6 +132,125 @@ class ShardedHybridIndex(ShardedDenseIndex):
         recv = self._hyb_buffers(queries.shape[0], pool, k, queries.device)["recv"]
         _gather(recv, send, self.group, self.engine)
         return self.fuse_gathered(recv, k, rrf_k)
+
+
+class ShardedM3Index(ShardedDenseIndex):
+    """bge-m3 over row shards: the learned-sparse list, the late-interaction rerank and the three-way score (dense + sparse +
+    MaxSim), each bit-identical on every rank to the one-call entry on the unsharded index.
+
+    Every rank holds a contiguous row range under id_base = its first global row: the embeddings, the doc-partitioned postings
+    (LexicalPostings.shard) and the token vectors of its own documents. The query arrays are replicated. Two small collectives per
+    batch (32 B per slot per rank each):
+
+        local dense top-pool + local sparse top-pool  ->  gather [world, 4, Q, pool]  ->  rag_m3_candidates_gathered_dev (two
+        merges, RRF on the MERGED lists)  ->  rag_m3_score_ids_dev (each rank scores the candidates whose rows it holds: their
+        token vectors live nowhere else)  ->  gather [world, 4, Q, slots]  ->  rag_m3_combine_gathered_dev (owner select, combine,
+        stable top-k)
+
+    The halves on each side of each gather are methods of their own, so one process can stack the sends of several handles."""
+
+    def load_shard(self, emb_shard, first_global_row, lexical_shard=None, token_vecs=None, token_off=None, form="fp16"):
+        """emb_shard: this rank's rows; lexical_shard: LexicalPostings.shard(begin, end); token_vecs [rows, dim] float32 and
+        token_off [n_rows + 1] int64: the token vectors of this rank's documents, stored as `form` ("fp16" / "mxfp8")."""
+        super().load_shard(emb_shard, first_global_row)
+        if lexical_shard is not None:
+            lexical_shard.load(self.engine)
+        if token_vecs is not None:
+            self.engine.tokvec_load(token_vecs, token_off, form=form)
+
+    def _m3_buffers(self, Q, pool, slots, k, device):
+        key = ("m3", Q, pool, slots, k, str(device))
+        if key not in self._bufs:
+            i64, f64 = torch.int64, torch.float64
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+            send = new((4, Q, pool), i64)
+            self._bufs[key] = dict(
+                send=send, send_sc=(send[1].view(f64), send[3].view(f64)),      # dense ids | cosine bits | sparse ids | raw sparse bits
+                recv=new((self.world, 4, Q, pool), i64), lists=new((2, Q, pool), i64), scores=new((2, Q, pool), f64),
+                cand=new((Q, slots), i64), part=new((4, Q, slots), i64), recv2=new((self.world, 4, Q, slots), i64),
+                ids=new((Q, k), i64), sc=new((Q, k), f64), comp=new((Q, k, 3), f64))
+        return self._bufs[key]
+
+    @staticmethod
+    def _slots(pool, mode):
+        return 2 * int(pool) if int(mode) == 2 else int(pool)
+
+    def local_lists(self, q_emb, term_ptr, terms, weights, pool, k, mode=2, tenant=-1):
+        """This rank's half of the first exchange: [4, Q, pool] int64 = dense ids | cosine bits | sparse ids | raw sparse score
+        bits. mode 0 runs no sparse search: its candidates are the dense list and the sparse planes are never read."""
+        b = self._m3_buffers(q_emb.shape[0], pool, self._slots(pool, mode), k, q_emb.device)
+        send = b["send"]
+        self.engine.dense_topk_dev(q_emb, pool, send[0], None, b["send_sc"][0], tenant=tenant)
+        if int(mode) != 0:
+            self.engine.sparse_topk_dev(term_ptr, terms, weights, pool, send[2], None, b["send_sc"][1], tenant=tenant)
+        return send
+
+    def candidates_gathered(self, recv, k, mode=2, rrf_k=60):
+        """recv [world, 4, Q, pool]: every rank's local_lists() -> the global candidate ids [Q, slots] (the same on every rank)."""
+        _, _, Q, pool = recv.shape
+        b = self._m3_buffers(Q, pool, self._slots(pool, mode), k, recv.device)
+        self.engine.m3_candidates_gathered_dev(recv, b["lists"], b["scores"], b["cand"], mode=mode, rrf_k=rrf_k)
+        return b["cand"]
+
+    def score_local(self, cand, q_emb, term_ptr, terms, weights, q_vecs, q_off, pool, k, w=(0.4, 0.2, 0.4)):
+        """This rank's half of the second exchange: [4, Q, slots] int64 = owned flag | dense | sparse | colbert bits."""
+        Q, slots = cand.shape
+        b = self._m3_buffers(Q, pool, slots, k, cand.device)
+        kw = {}
+        if float(w[1]) > 0:
+            kw.update(term_ptr=term_ptr, terms=terms, weights=weights)
+        if float(w[2]) > 0:
+            kw.update(q_vecs=q_vecs, q_off=q_off)
+        self.engine.m3_score_ids_dev(cand, b["part"], q_emb=q_emb, w=w, **kw)
+        return b["part"]
+
+    def combine_gathered(self, cand, recv2, pool, k, w=(0.4, 0.2, 0.4)):
+        """cand [Q, slots] and recv2 [world, 4, Q, slots]: every rank's score_local() -> dict(ids, scores, components, candidates)."""
+        Q, slots = cand.shape
+        b = self._m3_buffers(Q, pool, slots, k, cand.device)
+        self.engine.m3_combine_gathered_dev(cand, recv2, b["ids"], b["sc"], b["comp"], w=w)
+        return dict(ids=b["ids"], scores=b["sc"], components=b["comp"], candidates=cand)
+
+    def search_m3(self, q_emb, term_ptr, terms, weights, q_vecs, q_off, pool, k, mode=2, w=(0.4, 0.2, 0.4), rrf_k=60, tenant=-1):
+        """Replicated CUDA tensors: q_emb [Q, dim] float32, the query CSR term_ptr [Q + 1] / terms int32 / weights float32, q_vecs
+        [rows, tok_dim] float32 / q_off [Q + 1] int64; tenant an int or one number per query. Returns dict(ids [Q, k] int64,
+        scores [Q, k] float64, components [Q, k, 3] float64 = (dense, sparse, colbert), candidates [Q, slots] int64) - the
+        outputs of retrieve_m3_dev on the unsharded index, identical on every rank. world == 1 runs the same path without the
+        gathers."""
+        Q = q_emb.shape[0]
+        b = self._m3_buffers(Q, pool, self._slots(pool, mode), k, q_emb.device)
+        send = self.local_lists(q_emb, term_ptr, terms, weights, pool, k, mode=mode, tenant=tenant)
+        if self.world == 1:
+            recv = send.unsqueeze(0)
+        else:
+            recv = b["recv"]
+            _gather(recv, send, self.group, self.engine)
+        cand = self.candidates_gathered(recv, k, mode=mode, rrf_k=rrf_k)
+        part = self.score_local(cand, q_emb, term_ptr, terms, weights, q_vecs, q_off, pool, k, w=w)
+        if self.world == 1:
+            recv2 = part.unsqueeze(0)
+        else:
+            recv2 = b["recv2"]
+            _gather(recv2, part, self.group, self.engine)
+        return self.combine_gathered(cand, recv2, pool, k, w=w)
+
+    def search_late_interaction(self, q_emb, q_vecs, q_off, pool, k, term_ptr=None, terms=None, weights=None, rrf_k=60, tenant=-1):
+        """The same protocol with weights (0, 0, 1) and mode 0 (term_ptr None) or 1: the score is (1 * c + 0) + 0 over (0 + 0) + 1 =
+        c exactly, so ids and score bits are those of retrieve_maxsim_dev on the unsharded index. Returns search_m3's dict."""
+        return self.search_m3(q_emb, term_ptr, terms, weights, q_vecs, q_off, pool, k, mode=0 if term_ptr is None else 1, w=(0.0, 0.0, 1.0),
+                              rrf_k=rrf_k, tenant=tenant)
+
+    def search_lexical(self, term_ptr, terms, weights, k, tenant=-1):
+        """The learned-sparse top-k alone: local rag_sparse_topk_dev, one gather, rag_merge_topk_dev (raw scores need no global
+        statistic). Returns (ids [Q, k] int64, scores [Q, k] float64), score desc, lower id first on ties."""
+        Q = term_ptr.shape[0] - 1
+        send, recv, out_ids, out_scores, send_ids, send_sc, recv_sc = self._buffers(Q, k, term_ptr.device)
+        self.engine.sparse_topk_dev(term_ptr, terms, weights, k, send_ids, None, send_sc, tenant=tenant)
+        if self.world == 1:
+            return send_ids, send_sc
+        _gather(recv, send, self.group, self.engine)
+        self.engine.merge_topk_dev(recv, recv_sc, out_ids, out_scores, n_lists=self.world, list_stride=2 * Q * k)
+        return out_ids, out_scores
 
 
 class ShardedReranker:
