@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void mx_embed_ln_kernel(const int32_t* __restr
                                                            const float* __restrict__ word, const float* __restrict__ pos,
                                                            const float* __restrict__ type, const float* __restrict__ g,
                                                            const float* __restrict__ b, const int32_t* __restrict__ m_packed,
-                                                           const int32_t* __restrict__ row_pair, const int32_t* __restrict__ pair_off,
+                                                           const int32_t* __restrict__ row_pair, const int32_t* __restrict__ row_off,
                                                            int L, int vocab, float eps, char* __restrict__ x8) {
     constexpr int H = 384, NK = H / 32;
     __shared__ __attribute__((aligned(16))) char tile[NK * 6 * MX_EMB_ROWS * 16];       // [K-step][plane][row][16 B] = 18 KiB
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void mx_embed_ln_kernel(const int32_t* __restr
         const int64_t row = base + rl;
         if (row >= n_rows) break;                            // wave-uniform
         const int pr = row_pair[row];
-        const int p = (int)row - pair_off[pr];
+        const int p = (int)row - row_off[pr];                // position in the pair: rows are the GEMM row space
         const size_t src = (size_t)pr * L + p;
         int id = ids[src];
         id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
@@ -466,16 +466,16 @@ __global__ __launch_bounds__(256) void mx_embed_ln_kernel(const int32_t* __restr
     }
 }
 
-// Row pair_off[p] of one or two (b may be null) image-layout tensors with nk K-steps -> row p of their compact counterparts (one row per pair); also
-// publishes the compact row count. One thread per (pair, 16-B chunk): a row is nk x 6 chunks.
-__global__ void mx_gather_rows_kernel(const char* __restrict__ a, const char* __restrict__ b, const int32_t* __restrict__ pair_off, int P, int nk,
+// Row row_off[p] (a pair's first GEMM row) of one or two (b may be null) image-layout tensors with nk K-steps -> row p of their compact counterparts
+// (one row per pair); also publishes the compact row count. One thread per (pair, 16-B chunk): a row is nk x 6 chunks.
+__global__ void mx_gather_rows_kernel(const char* __restrict__ a, const char* __restrict__ b, const int32_t* __restrict__ row_off, int P, int nk,
                                       char* __restrict__ a_out, char* __restrict__ b_out, int32_t* __restrict__ rows_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) rows_out[0] = P;
     const int per = nk * 6;
     if (i >= (int64_t)P * per) return;
     const int p = (int)(i / per), c = (int)(i % per), s = c / 6, pl = c % 6;
-    const int64_t m = pair_off[p];
+    const int64_t m = row_off[p];
     const size_t src = ((size_t)(m >> 7) * nk + s) * MX_B_STAGE + (size_t)pl * MX_B_PLANE + (size_t)(m & 127) * 16;
     const size_t dst = ((size_t)(p >> 7) * nk + s) * MX_B_STAGE + (size_t)pl * MX_B_PLANE + (size_t)(p & 127) * 16;
     *reinterpret_cast<mx_u4*>(a_out + dst) = *reinterpret_cast<const mx_u4*>(a + src);
@@ -494,13 +494,17 @@ __device__ __forceinline__ float mx_load_elem(const char* __restrict__ x8, int64
 // swapped operands so that a lane holds 4 consecutive KEYS of one dim: the V fragment order)
 // ft_base: the launch's feature tile 0 is tile ft_base of the QKV matrix (the last layer of a classifier projects K and V for every
 // token, ft_base = 1, and Q for the [CLS] rows alone). row_map (Q of compact rows only): token row of compact row p.
+// The GEMM's rows are the GEMM row space (a pair's length rounded up to 4 or 16), the Q / K / V tiles the attention space (rounded up
+// to 16): row_att[m] = attention row of GEMM row m, -1 for the rows past the packed end, which store nothing. Both spaces start a
+// pair on a multiple of 4, so four GEMM rows from a multiple of 4 on are four consecutive slots of one attention tile.
 struct mx_epi_qkv {
     half_t *qf16, *kf16, *vf16;
     size_t kv_plane;
     const float* bias;
-    int m_tiles16;                 // 16-row tiles of the padded row space
+    int m_tiles16;                 // 16-row tiles of the padded attention space
     int ft_base;
-    const int32_t* row_map;
+    const int32_t* row_att;
+    const int32_t* row_map;        // attention rows
     int n_map;
     __device__ __forceinline__ bool swap_for(int ft) const { return ft + ft_base == 2; }
     __device__ __forceinline__ void prepare(char* scratch) const { mx_stage_params(reinterpret_cast<float*>(scratch + MX_PARAM_OFF), bias, 3 * MX_TM); }
@@ -510,17 +514,20 @@ struct mx_epi_qkv {
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wm = wid >> 2, wn = wid & 3;
         const int li = lane & 31, hh = lane >> 5;
         const int m0 = tt * MX_TN + wn * 32;                       // first token row of the wave
+        const int att = row_map == nullptr ? row_att[m0 + li] : -1;        // attention row of token m0 + li: ONE lookup per lane
         if (!swap) {
             half_t* dst = ft == 0 ? qf16 : kf16;
-            int m = m0 + li;
+            int m = att;
             if (row_map != nullptr) {
-                if (m >= n_map) return;
-                m = row_map[m];
-            }
+                if (m0 + li >= n_map) return;
+                m = row_map[m0 + li];
+            } else if (m < 0)
+                return;
+            const unsigned off = (unsigned)((m >> 4) * 512 + (m & 15) * 8 + 4 * hh);     // halfs inside a head's tiles: one lane offset
 #pragma unroll
             for (int b = 0; b < 6; ++b) {
                 const int head = wm * 6 + b;
-                half_t* tile = dst + (((size_t)head * m_tiles16 + (m >> 4)) * 64 + (m & 15)) * 8 + 4 * hh;
+                half_t* tile = dst + (size_t)head * m_tiles16 * 512 + off;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float4 bv = *reinterpret_cast<const float4*>(bias + ft * MX_TM + head * 32 + 8 * q + 4 * hh);
@@ -532,18 +539,27 @@ struct mx_epi_qkv {
                 }
             }
         } else {
-            // lane = dim li of head wm*6 + b; register 4q + e = token m0 + 8q + 4hh + e: 16-row tile (q >> 1), key slots
-            // fq = 2 (q & 1) + hh, e -> vf16[head][tile][d half][fq*16 + d%16][4]
+            // lane = dim li of head wm*6 + b; register 4q + e = token m0 + 8q + 4hh + e = attention row ma[q] + e: 16-row tile ma >> 4,
+            // key slots fq = (ma & 15) >> 2, e -> vf16[head][tile][d half][fq*16 + d%16][4]. Lane 8q + 4hh holds that token's row.
+            // The address is a workgroup-uniform head base plus ONE 32-bit lane offset per group (halfs: tile * 512 + d half * 256 +
+            // fq * 64 + d % 16 * 4; a head's tiles stay far below 2^31 halfs), so the six heads of a group share its arithmetic.
+            float bv[6];
 #pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                const int head = wm * 6 + b;
-                const float bv = bias[2 * MX_TM + head * 32 + li];
+            for (int b = 0; b < 6; ++b) bv[b] = bias[2 * MX_TM + (wm * 6 + b) * 32 + li];
+            int mq[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float v0 = acc[b][q * 4] + bv, v1 = acc[b][q * 4 + 1] + bv, v2 = acc[b][q * 4 + 2] + bv, v3 = acc[b][q * 4 + 3] + bv;
+            for (int q = 0; q < 4; ++q) mq[q] = __shfl(att, 8 * q + 4 * hh);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int ma = mq[q];
+                if (ma < 0) continue;
+                const unsigned off = (unsigned)((ma >> 4) * 512 + (li >> 4) * 256 + ((ma & 15) >> 2) * 64 + (li & 15) * 4);
+#pragma unroll
+                for (int b = 0; b < 6; ++b) {
+                    const float v0 = acc[b][q * 4] + bv[b], v1 = acc[b][q * 4 + 1] + bv[b], v2 = acc[b][q * 4 + 2] + bv[b], v3 = acc[b][q * 4 + 3] + bv[b];
                     const half4 hi = {(half_t)v0, (half_t)v1, (half_t)v2, (half_t)v3};
                     const half4 lo = mx_resid4(hi, v0, v1, v2, v3);
-                    half_t* o = vf16 + ((((size_t)head * m_tiles16 + (m0 >> 4) + (q >> 1)) * 2 + (li >> 4)) * 64 + (2 * (q & 1) + hh) * 16 + (li & 15)) * 4;
+                    half_t* o = vf16 + (size_t)(wm * 6 + b) * m_tiles16 * 512 + off;
                     __builtin_nontemporal_store(hi, reinterpret_cast<half4*>(o));
                     __builtin_nontemporal_store(lo, reinterpret_cast<half4*>(o + kv_plane));
                 }

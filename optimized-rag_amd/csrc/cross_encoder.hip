@@ -8,12 +8,19 @@
 // accumulation (3/16 of the f32-MFMA cost for the same accuracy class). GEMM operands (weights, x, ctx, q, ffn activations)
 // keep the two halves INTERLEAVED per 32-element K group: [hi 32 halfs | lo 32 halfs] = 128 B, so the row piece one K-step
 // (32 elements) stages is one whole 128-B line instead of two 64-B halves of two lines (SPLIT_IDX). Residual stream / LayerNorm / softmax /
-// GELU (erf form, A&S 7.1.26) / pooler are fp32. Layout: tokens are rows, PACKED per pair (pair p owns len_p rounded up
-// to 16 rows, offsets computed on the device), feature contiguous; weights are nn.Linear [out][in] = K-contiguous, so
-// every GEMM is the "both operands K-contiguous" form MFMA wants.
+// GELU (erf form, A&S 7.1.26) / pooler are fp32. Layout: tokens are rows, PACKED per pair (offsets computed on the device),
+// feature contiguous; weights are nn.Linear [out][in] = K-contiguous, so every GEMM is the "both operands K-contiguous" form
+// MFMA wants. The packing has TWO row spaces. Attention space: pair p owns len_p rounded up to 16 rows (pair_off) - the Q / K / V
+// fragment tiles are 16 rows of one pair. GEMM row space: pair p owns len_p rounded up to g rows (row_off) - embeddings, every
+// GEMM operand and result, LayerNorm, GELU and the attention context. g = 4 in the MX forward of a classifier (the GEMMs' 128-row
+// tiles do not care where a pair starts; 4 is what the V epilogue's four-key store needs), which so computes 1.5 pad rows per pair
+// on average instead of 7.5; g = 16 - one row space, row_off = pair_off - in the split-fp16 forward and for embedding models, whose
+// pooling and token heads read rows through pair_off. The QKV epilogue maps a GEMM row to its attention row (row_att), attention
+// writes its context back to GEMM rows, and the slots of a pair's last attention tile past its GEMM rows are written by nobody:
+// K there is masked after the MFMA, V there is zeroed (LDS) or selected to zero (DIRECT) by the attention kernel.
 //
 // Kernels
-//   ce_pack_scan/rows  lens -> pair_off / row_pair / m_packed (the packed row layout of the chunk)
+//   ce_pack_scan/rows  lens -> pair_off / row_off / row_pair / row_att / m_packed (the packed row layout of the chunk)
 //   ce_embed_ln        word+pos+type gather -> LayerNorm -> x16: the residual stream IS the split-fp16 GEMM operand (hi + lo
 //                      = 22 significant bits); there is no separate fp32 copy
 //   ce_gemm<EPI>       persistent, XCD-aware; 128 (out features) x 256 (tokens) tiles, BK = 32, three LDS stages by
@@ -49,9 +56,12 @@
 struct ce_chunk_bufs {
     dev_buf<int32_t> ids, tt, lens;                                    // [Mp] token / type ids padded to L, [pairs] lengths
     dev_buf<int32_t> clen;                                             // [pairs] lengths clamped to [1, L_in]: what every kernel after the scan reads
-    // packed (variable-length) row layout of the current chunk: pair p owns rows [pair_off[p], pair_off[p+1]) where
-    // pair_off[p+1] - pair_off[p] = len rounded up to 16; row_pair[m] = owning pair (-1 past the end); m_packed[0] = rows
-    dev_buf<int32_t> pair_off, row_pair, m_packed;
+    // packed (variable-length) row layout of the current chunk, in two row spaces. ATTENTION space: pair p owns rows
+    // [pair_off[p], pair_off[p+1]), its length rounded up to 16 (whole Q / K / V fragment tiles). GEMM row space (activations, the
+    // residual stream): pair p owns rows [row_off[p], row_off[p+1]), its length rounded up to the forward's granularity g: 4 in the MX
+    // forward of a classifier, else 16, where the two spaces coincide. row_pair[m] = owning pair of GEMM row m (-1 past the end),
+    // row_att[m] = its attention row (-1 past the end); m_packed[0] = row_off[P] = GEMM rows
+    dev_buf<int32_t> pair_off, row_off, row_pair, row_att, m_packed;
     dev_buf<int32_t> sid, stt;                                         // staging of one chunk's [pairs][L_in] token / type ids
     dev_buf<float> logits;                                             // staging of one chunk's outputs, [pairs][out_width]
 };
@@ -472,42 +482,58 @@ __device__ __forceinline__ void wave_layernorm(float (&v)[PER], const float* __r
     }
 }
 
-// ---- packing: pair p owns len_p rounded up to 16 rows; offsets by one block-wide scan, then the row -> pair map.
+// ---- packing: pair p owns len_p rounded up to 16 rows of the attention space and to g rows of the GEMM row space; offsets by one
+// block-wide scan, then the maps of the GEMM rows.
 // The ONE place that reads the caller's lens: a length is clamped to [1, L_in] (L_in = the caller's padded length, not the attention
 // length class it was rounded up to: tokens past L_in do not exist) and written to clen, which attention and the pooling heads read.
-__global__ __launch_bounds__(1024) void ce_pack_scan_kernel(const int32_t* __restrict__ lens, int P, int L_in, int32_t* __restrict__ clen,
-                                                             int32_t* __restrict__ pair_off, int32_t* __restrict__ m_packed) {
-    __shared__ int part[1024];
+// Two prefix sums: pair_off over the lengths rounded up to 16 (attention space), row_off over the lengths rounded up to g = 4 or 16
+// (GEMM row space; g = 16: the same numbers).
+__global__ __launch_bounds__(1024) void ce_pack_scan_kernel(const int32_t* __restrict__ lens, int P, int L_in, int g, int32_t* __restrict__ clen,
+                                                             int32_t* __restrict__ pair_off, int32_t* __restrict__ row_off,
+                                                             int32_t* __restrict__ m_packed) {
+    __shared__ int part[1024], part_g[1024];
     const int tid = threadIdx.x;
     const int per = (P + 1023) / 1024;
     const int b = tid * per, e = min(P, b + per);
-    int s = 0;
-    for (int p = b; p < e; ++p) s += (max(1, min(lens[p], L_in)) + 15) & ~15;
+    int s = 0, sg = 0;
+    for (int p = b; p < e; ++p) {
+        const int len = max(1, min(lens[p], L_in));
+        s += (len + 15) & ~15;
+        sg += (len + g - 1) & ~(g - 1);
+    }
     part[tid] = s;
+    part_g[tid] = sg;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
+        const int v = tid >= o ? part[tid - o] : 0, vg = tid >= o ? part_g[tid - o] : 0;
         __syncthreads();
         part[tid] += v;
+        part_g[tid] += vg;
         __syncthreads();
     }
-    int off = part[tid] - s;
+    int off = part[tid] - s, off_g = part_g[tid] - sg;
     for (int p = b; p < e; ++p) {
         const int len = max(1, min(lens[p], L_in));
         clen[p] = len;
         pair_off[p] = off;
+        row_off[p] = off_g;
         off += (len + 15) & ~15;
+        off_g += (len + g - 1) & ~(g - 1);
     }
-    if (tid == 1023) { pair_off[P] = part[1023]; m_packed[0] = part[1023]; }
+    if (tid == 1023) { pair_off[P] = part[1023]; row_off[P] = part_g[1023]; m_packed[0] = part_g[1023]; }
 }
 
-__global__ void ce_pack_rows_kernel(const int32_t* __restrict__ pair_off, int P, int L, int64_t rows_total,
-                                    int32_t* __restrict__ row_pair) {
+// The maps of the GEMM row space: owning pair and attention row of every row (-1 from row_off[P] up to the allocated rows)
+__global__ void ce_pack_rows_kernel(const int32_t* __restrict__ pair_off, const int32_t* __restrict__ row_off, int P, int L, int64_t rows_total,
+                                    int32_t* __restrict__ row_pair, int32_t* __restrict__ row_att) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < rows_total && i >= pair_off[P]) row_pair[i] = -1;             // tail up to the allocated rows
+    if (i < rows_total && i >= row_off[P]) row_pair[i] = row_att[i] = -1;
     if (i >= (int64_t)P * L) return;
     const int p = (int)(i / L), t = (int)(i % L);
-    if (t < pair_off[p + 1] - pair_off[p]) row_pair[pair_off[p] + t] = p;
+    if (t < row_off[p + 1] - row_off[p]) {
+        row_pair[row_off[p] + t] = p;
+        row_att[row_off[p] + t] = pair_off[p] + t;
+    }
 }
 
 template <int PER>
@@ -581,15 +607,19 @@ template <int QB, bool MX = false, bool DIRECT = false>
 __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __restrict__ q16,
                                                              const half_t* __restrict__ kf16, const half_t* __restrict__ vf16,
                                                              size_t kv_plane, const int32_t* __restrict__ lens,
-                                                             const int32_t* __restrict__ pair_off, int L, int hidden,
-                                                             int heads, int m_pad, half_t* __restrict__ ctx16, int max_qblocks = 1 << 20) {
+                                                             const int32_t* __restrict__ pair_off, const int32_t* __restrict__ row_off,
+                                                             int L, int hidden, int heads, int m_pad, half_t* __restrict__ ctx16,
+                                                             int max_qblocks = 1 << 20) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
     const int head = blockIdx.x, pair = blockIdx.y;
     const int len = max(1, min(lens[pair], L));
     const int fr = lane & 15, fq = lane >> 4;
-    const int po = pair_off[pair], Lp = pair_off[pair + 1] - po;     // this pair's packed rows: len rounded up to 16
+    const int po = pair_off[pair], Lp = pair_off[pair + 1] - po;     // this pair's rows in attention space: len rounded up to 16
+    // its rows in the GEMM row space, where the context goes: len rounded up to 4 or 16. Q, K and V of the slots [Lr, Lp) of the
+    // pair's last tile were written by no GEMM of this forward when Lr < Lp: they hold whatever an earlier call left there.
+    const int ro = row_off[pair], Lr = row_off[pair + 1] - ro;
     const int nt = Lp >> 4;                                           // the pair's 16-row tiles; an odd count leaves the second
     const int nkb = (len + 31) >> 5;                                  // half of the last 32-key block outside the pair (masked)
     const size_t plane_b = (size_t)L * 64;                            // bytes of one K (or V) plane of this (pair, head)
@@ -652,6 +682,14 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
     const float cs = (float)(0.17677669529663687 * 1.4426950408889634);    // 32^-0.5 * log2(e)
     if (!DIRECT) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // The stale V slots of the last tile (keys Lr .. Lp - 1: P = 0 there, V must be finite) are zeroed once, by the wave whose DMA
+        // staged that tile, after its own wait above has landed it. They are the whole slot groups fq >= (Lr & 15) >> 2: one
+        // contiguous run per d half of the tile ([d half][fq * 16 + d % 16][4 slots], 128 B per group); lane -> the tile's 16-B piece.
+        if (MX && Lr < Lp && wv == (nt - 1 < nwaves ? nt - 1 : nt - 1 - nwaves) && ((lane & 31) >> 3) >= ((Lr & 15) >> 2)) {   // nt <= 2 nwaves
+            char* const sv = smem + 2 * plane_b + (nt - 1) * 1024 + lane * 16;
+            *reinterpret_cast<u32x4*>(sv) = (u32x4){0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(sv + plane_b) = (u32x4){0u, 0u, 0u, 0u};
+        }
         __syncthreads();
     }
     if (!has_rows) return;
@@ -670,14 +708,20 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
         // of an odd-count pair lies outside the pair under P = 0: zeros in LDS, and DIRECT selects zeros (that memory belongs to the
         // next pair or is stale slack: a non-finite value there would turn this pair's context into NaN)
         const int vo = kb * 2048 + lane * 8;
-        const half4 a0h = *reinterpret_cast<const half4*>(v_hi + vo), a1h = *reinterpret_cast<const half4*>(v_hi + vo + 512);
-        const half4 a0l = *reinterpret_cast<const half4*>(v_lo + vo), a1l = *reinterpret_cast<const half4*>(v_lo + vo + 512);
+        half4 a0h = *reinterpret_cast<const half4*>(v_hi + vo), a1h = *reinterpret_cast<const half4*>(v_hi + vo + 512);
+        half4 a0l = *reinterpret_cast<const half4*>(v_lo + vo), a1l = *reinterpret_cast<const half4*>(v_lo + vo + 512);
         half4 b0h = {}, b1h = {}, b0l = {}, b1l = {};
         if (!(DIRECT && EDGE && (nt & 1))) {
             b0h = *reinterpret_cast<const half4*>(v_hi + vo + 1024);
             b1h = *reinterpret_cast<const half4*>(v_hi + vo + 1536);
             b0l = *reinterpret_cast<const half4*>(v_lo + vo + 1024);
             b1l = *reinterpret_cast<const half4*>(v_lo + vo + 1536);
+        }
+        // DIRECT has no staged copy to zero: the lane's slot group (4 keys from fq * 4 on in each tile) past the pair's GEMM rows is
+        // stale, and selected to zero here (the LDS form zeroed those groups after staging)
+        if (DIRECT && EDGE && MX) {
+            if (kb * 32 + fq * 4 >= Lr) a0h = a1h = a0l = a1l = (half4){};
+            if (kb * 32 + 16 + fq * 4 >= Lr) b0h = b1h = b0l = b1l = (half4){};
         }
         const half8 v0h = __builtin_shufflevector(a0h, b0h, 0, 1, 2, 3, 4, 5, 6, 7), v1h = __builtin_shufflevector(a1h, b1h, 0, 1, 2, 3, 4, 5, 6, 7);
         const half8 v0l = __builtin_shufflevector(a0l, b0l, 0, 1, 2, 3, 4, 5, 6, 7), v1l = __builtin_shufflevector(a1l, b1l, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -752,8 +796,11 @@ __global__ __launch_bounds__(1024) void ce_attention_kernel(const half_t* __rest
         const float inv = 1.0f / l;
         if ((qb0 + b) * 16 >= Lp || qb0 + b >= max_qblocks) break;
         if (MX) {
+            // the context goes to the pair's GEMM rows; queries past them (stale Q rows of the last tile: a query is one MFMA column,
+            // and the maximum and the sum above stay inside it) have no row there
+            if ((qb0 + b) * 16 + fr >= Lr) continue;
             // K-step = head; c0 = dims 4fq..4fq+3 (MFMA j = 0), c1 = 16 + the same (j = 1); lane half h = fq & 1, position 4 (fq >> 1) + r
-            const int64_t mrow = (int64_t)row0 + (qb0 + b) * 16 + fr;
+            const int64_t mrow = (int64_t)ro + (qb0 + b) * 16 + fr;
             char* img = reinterpret_cast<char*>(ctx16) + mx_img_base(mrow, head * 32, hidden >> 5) + (int)(mrow & 127) * 16 + (fq >> 1) * 8;
             mx_u2 h0, h1;
             unsigned l0, l1;
@@ -1290,7 +1337,9 @@ static int ws_renew(rag_ctx* h, W& w, int P, int L, int out_width, hipStream_t s
     if ((rc = c.lens.alloc(h, (size_t)P))) return rc;
     if ((rc = c.clen.alloc(h, (size_t)P))) return rc;
     if ((rc = c.pair_off.alloc(h, (size_t)P + 1))) return rc;
+    if ((rc = c.row_off.alloc(h, (size_t)P + 1))) return rc;
     if ((rc = c.row_pair.alloc(h, (size_t)Mp))) return rc;
+    if ((rc = c.row_att.alloc(h, (size_t)Mp))) return rc;
     if ((rc = c.m_packed.alloc(h, 1))) return rc;
     if ((rc = c.sid.alloc(h, (size_t)P * L))) return rc;              // L_in <= L
     if ((rc = c.stt.alloc(h, (size_t)P * L))) return rc;
@@ -1465,11 +1514,13 @@ __global__ void ce_pad_tokens_kernel(const int32_t* __restrict__ in_ids, const i
 
 // Start of every chunk: tokens padded to L, then the packed row layout (no host round trip: grids cover the padded worst case,
 // kernels stop at m_packed). Every later kernel reads the clamped lengths the scan writes (io.clen), never c.lens.
-static void chunk_prologue(const ce_ws_base& w, const ce_chunk& c, hipStream_t st) {
+// g = granularity of the GEMM row space (4 or 16; 16: io.row_off = io.pair_off, one row space)
+static void chunk_prologue(const ce_ws_base& w, const ce_chunk& c, int g, hipStream_t st) {
     const ce_chunk_bufs& io = w.io;
     launch(ce_pad_tokens_kernel, dim3((unsigned)(((int64_t)c.P * c.L + 255) / 256)), dim3(256), 0, st, c.ids, c.tt, c.P, c.L_in, c.L, io.ids, io.tt);
-    launch(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, c.lens, c.P, c.L_in, io.clen, io.pair_off, io.m_packed);
-    launch(ce_pack_rows_kernel, dim3((unsigned)((w.tokens + 255) / 256)), dim3(256), 0, st, io.pair_off, c.P, c.L, w.tokens, io.row_pair);
+    launch(ce_pack_scan_kernel, dim3(1), dim3(1024), 0, st, c.lens, c.P, c.L_in, g, io.clen, io.pair_off, io.row_off, io.m_packed);
+    launch(ce_pack_rows_kernel, dim3((unsigned)((w.tokens + 255) / 256)), dim3(256), 0, st, io.pair_off, io.row_off, c.P, c.L, w.tokens, io.row_pair,
+           io.row_att);
 }
 
 // Attention of one layer: one workgroup per (head, pair), QB 16-query blocks per wave, on the forward's Q / K / V planes into
@@ -1483,14 +1534,14 @@ static int launch_attention(rag_ctx* h, const rag_ce_model* m, const ce_ws_base&
     const dim3 grid(heads, c.P);
     if constexpr (MX)
         if (max_qblocks == 1) {
-            launch(ce_attention_kernel<1, true, true>, grid, dim3(64), 0, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, L, H, heads,
-                   (int)w.tokens, ctx, 1);
+            launch(ce_attention_kernel<1, true, true>, grid, dim3(64), 0, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, w.io.row_off, L, H,
+                   heads, (int)w.tokens, ctx, 1);
             return RAG_OK;
         }
     const int lds = L * 256;                                           // K hi | K lo | V hi | V lo fragment planes
     if (int rc = raise_lds(h, h->attr_ce_attn_lds[MX][QB], lds, ce_attention_kernel<QB, MX>)) return rc;
-    launch(ce_attention_kernel<QB, MX>, grid, dim3(64 * (L / (16 * QB))), lds, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, L, H, heads,
-           (int)w.tokens, ctx, max_qblocks);
+    launch(ce_attention_kernel<QB, MX>, grid, dim3(64 * (L / (16 * QB))), lds, st, q, kf, vf, kv_plane, w.io.clen, w.io.pair_off, w.io.row_off, L,
+           H, heads, (int)w.tokens, ctx, max_qblocks);
     return RAG_OK;
 }
 
@@ -1603,7 +1654,7 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     if ((rc = raise_lds(h, h->attr_ce_gemm_lds, CE_GEMM_LDS, ce_gemm_kernel<EPI_QKV>, ce_gemm_kernel<EPI_GELU>, ce_gemm_kernel<EPI_RESID>,
                         ce_gemm_kernel<EPI_QKV64>)))
         return rc;
-    chunk_prologue(w, c, st);
+    chunk_prologue(w, c, 16, st);
     rc = per_lane_dispatch(h, H, [&](auto per) {
         launch(ce_embed_ln_kernel<decltype(per)::value>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, io.ids, io.tt, m->word, m->pos,
                m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, H, m->cfg.vocab_size, m->cfg.max_pos, (float)m->cfg.ln_eps, w.x16);
@@ -1674,7 +1725,8 @@ static void mx_qkv(rag_ctx* h, const rag_ce_model* m, const rag_ce_model::Layer&
     const ce_mx_ws& w = m->mx;
     const int nk = m->cfg.hidden / 32;
     mx_gemm(h, st, ly.wqkv8 + (size_t)ft_base * nk * MX_A_STAGE, X, nk, n_ft, rows,
-            mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, m->cfg.hidden), ly.bqkv, (int)(w.tokens >> 4), ft_base, row_map, n_map});
+            mx_epi_qkv{w.qf16, w.kf16, w.vf16, kv_plane_halfs(w.tokens, m->cfg.hidden), ly.bqkv, (int)(w.tokens >> 4), ft_base, w.io.row_att,
+                       row_map, n_map});
 }
 
 // The layer after its attention, on rows[0] rows: out-projection + bias + residual + LayerNorm (attn -> x, in place), FFN-up +
@@ -1695,9 +1747,13 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     int rc;
     if ((rc = raise_lds(h, h->attr_ce_mx_lds, MX_KERNEL_LDS, mx_gemm_kernel<mx_epi_qkv>, mx_gemm_kernel<mx_epi_gelu>, mx_gemm_kernel<mx_epi_ln>)))
         return rc;
-    chunk_prologue(w, c, st);
+    // A classifier packs its GEMM rows in fours: only attention needs a pair on whole 16-row tiles (its Q / K / V fragments), the GEMMs
+    // work on 128-row image tiles wherever a pair starts, and the V epilogue stores four consecutive keys per lane. Every GEMM,
+    // LayerNorm, GELU and embedding row between a length rounded up to 4 and to 16 is work no result needs. An embedding model keeps
+    // 16: its pooling and token heads read rows through pair_off.
+    chunk_prologue(w, c, m->embed ? 16 : 4, st);
     launch(mx_embed_ln_kernel, dim3((unsigned)(((int64_t)P * L + MX_EMB_ROWS - 1) / MX_EMB_ROWS)), dim3(256), 0, st, io.ids, io.tt, m->word,
-           m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.pair_off, L, m->cfg.vocab_size, (float)m->cfg.ln_eps, w.x8);
+           m->pos, m->type, m->emb_ln_g, m->emb_ln_b, io.m_packed, io.row_pair, io.row_off, L, m->cfg.vocab_size, (float)m->cfg.ln_eps, w.x8);
     half_t* const ctx = reinterpret_cast<half_t*>(w.ctx8.get());       // the attention kernel writes the image tensor as bytes
     const dim3 gather_grid((unsigned)(((int64_t)P * 72 + 255) / 256));
     // The classifier reads the [CLS] row of the last layer alone (pooler: hidden_states[:, 0]), and nothing after the last layer's
@@ -1710,7 +1766,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
         const auto& ly = m->layers[l];
         cls_tail = !m->embed && l == m->cfg.layers - 1;
         if (cls_tail) {                                                // K and V for every token, Q for the [CLS] rows alone
-            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.x8, nullptr, io.pair_off, P, H / 32, w.xc8, nullptr, w.m_cls);
+            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.x8, nullptr, io.row_off, P, H / 32, w.xc8, nullptr, w.m_cls);
             mx_qkv(h, m, ly, st, 1, 2, w.x8, io.m_packed);
             mx_qkv(h, m, ly, st, 0, 1, w.xc8, w.m_cls, io.pair_off, P);
         } else
@@ -1721,12 +1777,13 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
                       : launch_attention<2, true>(h, m, w, w.qf16, w.kf16, w.vf16, ctx, c, st, qblocks);
         if (rc) return rc;
         if (cls_tail) {
-            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.ctx8, nullptr, io.pair_off, P, H / 32, w.cc8, nullptr, w.m_cls);
+            launch(mx_gather_rows_kernel, gather_grid, dim3(256), 0, st, w.ctx8, nullptr, io.row_off, P, H / 32, w.cc8, nullptr, w.m_cls);
             mx_layer_tail(h, m, ly, st, w.cc8, w.xc8, w.hc8, w.m_cls);
         } else
             mx_layer_tail(h, m, ly, st, w.ctx8, w.x8, w.h8, io.m_packed);
     }
-    // head. After a [CLS] tail the classifier's rows are the compact tensor (row p = pair p), else row pair_off[p] of the stream.
+    // head. After a [CLS] tail the classifier's rows are the compact tensor (row p = pair p), else row row_off[p] of the stream. (An
+    // embedding model's row_off is its pair_off: its heads below read the stream through either.)
     const char* const cls = cls_tail ? w.xc8 : w.x8;
     if (m->embed) {
         if (c.out)
@@ -1741,7 +1798,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
         launch(mx_pool_classify_kernel, dim3((unsigned)((P + POOL_PB - 1) / POOL_PB)), dim3(256), 0, st, cls, m->wpT, m->bp, m->wc, m->bc, P, H, c.out);
     else
         launch(ce_pool_classify_kernel<true>, dim3(P), dim3(256), 0, st, reinterpret_cast<const half_t*>(cls), m->wp, m->bp, m->wc, m->bc,
-               cls_tail ? nullptr : io.pair_off.get(), H, c.out);
+               cls_tail ? nullptr : io.row_off.get(), H, c.out);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
