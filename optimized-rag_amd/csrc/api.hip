@@ -30,7 +30,6 @@ static void options_from_env(rag_options* o) {
         if (const char* v = getenv(env.c_str())) o->*(e.field) = atoi(v);
     }
 }
-#define LOCK(h) std::lock_guard<std::mutex> lock_((h)->mu)
 // first statement after the lock and the argument checks of an entry that touches the device (common.h host_after_dev)
 #define DEV_ENTRY(h)                                                                           \
     do {                                                                                      \
@@ -187,10 +186,8 @@ static int index_load_common(rag_ctx* h, const float* emb, const int64_t* ids, i
         if (ids) {
             if (int rc = h->ids.alloc(h, (size_t)n_rows)) return rc;
             HIP_TRY(h, hipMemcpyAsync(h->ids, ids, (size_t)n_rows * sizeof(int64_t), kind, st));
-            h->cap_ids = n_rows;
         }
     }
-    h->cap32 = n_rows;
     int rc = dense_index_build(h, h->emb32, n_rows, st);
     if (rc) return rc;
     h->index_loaded = true;
@@ -220,15 +217,14 @@ int rag_index_reserve(rag_handle_t h, int64_t n_rows_total, int64_t id_base) {
     dense_free(h);
     h->id_base = id_base;
     h->n_reserved = n_rows_total;
-    h->n_rows_pad = round_up(n_rows_total, (int64_t)RAG_TILE * 8);
+    const int64_t pad = round_up(n_rows_total, (int64_t)RAG_TILE * 8);
     int rc;
     if ((rc = h->emb32.alloc(h, (size_t)n_rows_total * h->dim))) return rc;
-    h->cap32 = n_rows_total;
-    if ((rc = h->emb16.alloc(h, (size_t)h->n_rows_pad * h->dim_pad))) return rc;
+    if ((rc = h->emb16.alloc(h, (size_t)pad * h->dim_pad))) return rc;
     if ((rc = h->bad_rows.alloc(h, 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), h->stream));
     // rows not appended yet (and the tile padding) must read as zero vectors
-    HIP_TRY(h, hipMemsetAsync(h->emb16, 0, (size_t)h->n_rows_pad * h->dim_pad * sizeof(half_t), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->emb16, 0, (size_t)pad * h->dim_pad * sizeof(half_t), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->index_loaded = true;
     return RAG_OK;
@@ -269,14 +265,12 @@ int rag_index_set_tenants_host(rag_handle_t h, const int32_t* t, int64_t n_rows)
     ARG_CHECK(h, t == nullptr || n_rows == h->n_rows, "tenant array length must equal the index row count");
     HOST_ENTRY(h);
     h->tenants.reset();
-    h->cap_ten = 0;
     int rc;
     if (t == nullptr || n_rows == 0) {                     // NULL clears the filter table
         if ((rc = dense_build_tenant_tiles(h, nullptr, 0))) return rc;
         return live_vis_rebuild(h);                        // deleted rows stay deleted
     }
     if ((rc = h->tenants.alloc(h, (size_t)n_rows))) return rc;
-    h->cap_ten = n_rows;
     HIP_TRY(h, hipMemcpy(h->tenants, t, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     if ((rc = dense_build_tenant_tiles(h, t, n_rows))) return rc;
     return live_vis_rebuild(h);
@@ -288,10 +282,8 @@ int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
     ARG_CHECK(h, n_rows == h->n_rows, "id array length must equal the index row count");
     HOST_ENTRY(h);
     h->ids.reset();
-    h->cap_ids = 0;
     if (ids == nullptr || n_rows == 0) return RAG_OK;
     if (int rc = h->ids.alloc(h, (size_t)n_rows)) return rc;
-    h->cap_ids = n_rows;
     HIP_TRY(h, hipMemcpy(h->ids, ids, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice));
     return RAG_OK;
 }
@@ -741,13 +733,11 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
     ARG_CHECK(h, temporal == nullptr || n_rows == h->n_rows, "temporal array length must equal the index row count");
     HOST_ENTRY(h);
     h->temporal.reset();
-    h->cap_tmp = 0;
     h->temporal_absmax = 0.0;
     if (temporal == nullptr || n_rows == 0) return RAG_OK;
     for (int64_t i = 0; i < n_rows; ++i) h->temporal_absmax = std::max(h->temporal_absmax, std::fabs(temporal[i]));
     ARG_CHECK(h, std::isfinite(h->temporal_absmax), "temporal scores must be finite");
     if (int rc = h->temporal.alloc(h, (size_t)n_rows)) return rc;
-    h->cap_tmp = n_rows;
     HIP_TRY(h, hipMemcpy(h->temporal, temporal, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice));
     return RAG_OK;
 }
@@ -778,7 +768,7 @@ static int hybrid_linear_entry(rag_handle_t h, const float* q_dev, const int32_t
     entry_tenants t;
     if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
     tenant = t.tenant;
-    const int64_t n = h->n_rows, ld = h->n_rows_pad;
+    const int64_t n = h->n_rows, ld = emb16_rows(h);
     // queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
     // shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
     const int QB = (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)8 << 30) / (n * 12)));

@@ -101,7 +101,7 @@ struct dense_ws {
 // the planes of the dense index (dropped by every index load, dense_free) ...
 struct rag_index_mem {
     dev_buf<float> emb32;            // [n_rows][dim]        fp32 master rows
-    dev_buf<half_t> emb16;           // [n_rows_pad][dim_pad] fp16 (2^7 * unit rows), zero padded
+    dev_buf<half_t> emb16;           // [emb16_rows][dim_pad] fp16 (2^7 * unit rows), zero padded
     dev_buf<int64_t> ids;            // [n_rows] or null
     dev_buf<int32_t> tenants;        // [n_rows] or null
     dev_buf<int> bad_rows;           // device counter: rows with zero / non-finite norm
@@ -162,18 +162,16 @@ struct rag_ctx : rag_device_mem {
     int comm_rank = 0, comm_world = 1;
 
     // dense index
-    int64_t n_rows = 0, n_rows_pad = 0, id_base = 0;
+    int64_t n_rows = 0, id_base = 0;
     bool index_loaded = false;   // rag_index_load_* / rag_index_reserve ran (an EMPTY index is a valid, searchable state)
     int64_t n_reserved = 0;      // rows allocated by rag_index_reserve (chunked bulk load), 0 otherwise
     double temporal_absmax = 0.0;                                      // max |temporal[i]| (sizes the fused emission margin)
     std::unordered_map<int32_t, std::pair<int64_t, int>> tenant_span;  // tenant -> (offset, count) into tenant_tiles
     std::unordered_map<int32_t, std::vector<int32_t>> tenant_lists;    // host copy of those lists (inserts extend them)
     int64_t tenant_rows = 0;                                           // row count the tenant table was built for
-    // live writes (live.hip). Row capacities of the planes inserts grow in place (emb16's is n_rows_pad, the token store's
-    // tok_cap): kept as rows beside the buffers' element counts because a plane may be absent (capacity 0) and live.hip
-    // compares and grows them in rows.
+    // live writes (live.hip). The row capacity of a plane is not kept here: it is its buffer's element count over its row
+    // width (plane_rows and the row-plane list below), 0 for a plane that is absent.
     int64_t n_deleted = 0;
-    int64_t cap32 = 0, cap_ids = 0, cap_ten = 0, cap_tmp = 0, cap_vis = 0;
     bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
     bool bm25_compacted = false; // ... and a compaction was among them: appended postings cannot align the rows again, only a reload
 
@@ -201,7 +199,7 @@ struct rag_ctx : rag_device_mem {
     rag_bm25_index* sparse = nullptr;        // learned-sparse postings (rag_sparse_load_host): a slot of its own beside the BM25 postings
     bool sparse_stale = false;               // rows were inserted or compacted since they were aligned: sparse entry points refuse until rag_sparse_append_host covers the inserted rows, or a reload
     bool sparse_compacted = false;           // ... and a plain compaction was among them: only a reload helps
-    int64_t tok_rows = 0, tok_cap = 0;       // token store: rows loaded / rows reserved (rag_tokens_reserve + rag_tokens_append_dev)
+    int64_t tok_rows = 0;                    // token store: rows filled so far (its reservation: tok_cap_rows below)
     int tok_L = 0;
     int64_t tv_docs = 0, tv_rows = 0;        // token-vector store: documents / rows appended so far ...
     int64_t tv_docs_cap = 0, tv_rows_cap = 0;    // ... and reserved (rag_tokvec_reserve); tv_docs_cap > 0 = a store exists
@@ -253,6 +251,40 @@ inline int dense_ws::alloc(rag_ctx* h, size_t rows, hipStream_t st) {
     HIP_TRY(h, hipMemsetAsync(q16, 0, rows * h->dim_pad * sizeof(half_t), st));
     return RAG_OK;
 }
+
+// one lock per handle (rag_ctx::mu): the first statement of every entry point
+#define LOCK(h) std::lock_guard<std::mutex> lock_((h)->mu)
+
+// ---- row-aligned planes: the buffers that hold one row per index row. THE list, in the order writes visit them, each with its
+// row width in elements. f(plane id, pointer to the member of rag_device_mem, width) is called per plane until one returns
+// non-zero; the member pointer applies to a handle and to any other rag_device_mem (the grown set of an insert) alike. A new
+// plane is one line here plus what live.hip says about who feeds it (insert_feeds) and how it enters the index.
+enum { PLANE_EMB32, PLANE_EMB16, PLANE_IDS, PLANE_TENANTS, PLANE_TEMPORAL, PLANE_VIS, PLANE_TOK, PLANE_TOK_HI, PLANE_TOK_LEN };
+template <class F>
+static int for_each_row_plane(const rag_ctx* h, F&& f) {
+    int rc;
+    if ((rc = f(PLANE_EMB32, &rag_device_mem::emb32, (int64_t)h->dim))) return rc;
+    if ((rc = f(PLANE_EMB16, &rag_device_mem::emb16, (int64_t)h->dim_pad))) return rc;
+    if ((rc = f(PLANE_IDS, &rag_device_mem::ids, (int64_t)1))) return rc;
+    if ((rc = f(PLANE_TENANTS, &rag_device_mem::tenants, (int64_t)1))) return rc;
+    if ((rc = f(PLANE_TEMPORAL, &rag_device_mem::temporal, (int64_t)1))) return rc;
+    if ((rc = f(PLANE_VIS, &rag_device_mem::vis, (int64_t)1))) return rc;
+    if ((rc = f(PLANE_TOK, &rag_device_mem::tok, (int64_t)h->tok_L))) return rc;
+    if ((rc = f(PLANE_TOK_HI, &rag_device_mem::tok_hi, (int64_t)h->tok_L))) return rc;
+    return f(PLANE_TOK_LEN, &rag_device_mem::tok_len, (int64_t)1);
+}
+// rows a plane has room for: 0 for an absent one
+template <class T>
+static inline int64_t plane_rows(const dev_buf<T>& b, int64_t width) { return width > 0 ? (int64_t)(b.size() / (size_t)width) : 0; }
+static inline int64_t emb32_rows(const rag_ctx* h) { return plane_rows(h->emb32, h->dim); }
+// the padded leading dimension of the fp16 operand (a multiple of RAG_TILE * 8) and of everything laid out beside it
+static inline int64_t emb16_rows(const rag_ctx* h) { return plane_rows(h->emb16, h->dim_pad); }
+// the token store's reservation, from the plane whose row is one element: tok and tok_hi are allocated with it
+static inline int64_t tok_cap_rows(const rag_ctx* h) { return (int64_t)h->tok_len.size(); }
+// what the writes and the filtered searches ask of the planes beside the rows
+static inline bool tenants_cover(const rag_ctx* h, int64_t n) { return h->tenant_rows == n && (int64_t)h->tenants.size() >= n; }   // the table and its tile lists are for exactly n rows
+static inline bool ids_cover(const rag_ctx* h, int64_t n) { return !h->ids || (int64_t)h->ids.size() >= n; }                        // implicit ids always do
+static inline bool tokens_aligned(const rag_ctx* h, int64_t n) { return h->tok != nullptr && h->tok_rows == n; }                    // a token store filled to exactly n rows
 
 // ---- kernel launches. Launches kernel k with every argument converted to the kernel's own parameter type: a dev_buf<T> reads as
 // its T* or const T*, nullptr as whatever pointer the kernel takes. The call sites keep only the casts that really reinterpret.

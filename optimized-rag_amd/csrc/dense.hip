@@ -187,7 +187,7 @@ __host__ __device__ static inline int32_t* column_tenants(const float* tau, int 
     return reinterpret_cast<int32_t*>(const_cast<float*>(tau)) + (size_t)n_qtiles * RAG_TILE;
 }
 struct emit_args {
-    const half_t* corpus16;      // [n_rows_pad][Dp] fp16 (2^7 * unit rows)
+    const half_t* corpus16;      // [emb16_rows][Dp] fp16 (2^7 * unit rows)
     const half_t* q16;           // per pass: [n_qtiles * 256][Dp] fp16 query rows, pad rows zero
     int Dp;                      // padded dimension (halfs), a multiple of 128
     int rtile_begin, n_rtiles;   // per stage: the tile POSITIONS [rtile_begin, rtile_begin + n_rtiles)
@@ -1077,12 +1077,11 @@ int dense_free(rag_ctx* h) {
     static_cast<rag_index_mem&>(*h) = rag_index_mem();        // every plane of the index
     h->tenant_span.clear(); h->tenant_lists.clear(); h->tenant_rows = 0;
     h->n_deleted = 0;
-    h->cap32 = h->cap_ids = h->cap_ten = h->cap_vis = 0;
     h->bm25_stale = false;
     h->bm25_compacted = false;
     h->sparse_stale = false;
     h->sparse_compacted = false;
-    h->n_rows = h->n_rows_pad = 0;
+    h->n_rows = 0;
     h->n_reserved = 0;
     h->index_loaded = false;
     return RAG_OK;
@@ -1091,14 +1090,13 @@ int dense_free(rag_ctx* h) {
 // emb32 must already be resident (h->emb32, n_rows rows). Builds the fp16 operand copy.
 int dense_index_build(rag_ctx* h, const float* emb_dev, int64_t n_rows, hipStream_t st) {
     // pad to a multiple of 8 tiles so the XCD-aware block map needs no bounds logic on loads
-    h->n_rows_pad = round_up(n_rows, (int64_t)RAG_TILE * 8);
+    const int64_t pad = round_up(n_rows, (int64_t)RAG_TILE * 8);
     int rc;
-    if ((rc = h->emb16.alloc(h, (size_t)h->n_rows_pad * h->dim_pad))) return rc;
+    if ((rc = h->emb16.alloc(h, (size_t)pad * h->dim_pad))) return rc;
     if ((rc = h->bad_rows.alloc(h, 1))) return rc;
     HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), st));
-    if (h->n_rows_pad > n_rows)
-        HIP_TRY(h, hipMemsetAsync(h->emb16 + (size_t)n_rows * h->dim_pad, 0,
-                                  (size_t)(h->n_rows_pad - n_rows) * h->dim_pad * sizeof(half_t), st));
+    if (pad > n_rows)
+        HIP_TRY(h, hipMemsetAsync(h->emb16 + (size_t)n_rows * h->dim_pad, 0, (size_t)(pad - n_rows) * h->dim_pad * sizeof(half_t), st));
     return launch_normalize(h, emb_dev, h->emb16, n_rows, h->bad_rows, NORMALIZE_INDEX_BLOCKS, st);
 }
 
@@ -1150,7 +1148,7 @@ static int search_tiles(rag_ctx* h, int tenant, query_tenants qt, int Q, hipStre
     u->list = nullptr;
     u->count = (int)(round_up(h->n_rows, RAG_TILE) / RAG_TILE);
     if (qt.host != nullptr) {
-        ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
+        ARG_CHECK(h, tenants_cover(h, h->n_rows), "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
         std::vector<int32_t> distinct(qt.host, qt.host + Q);
         std::sort(distinct.begin(), distinct.end());
         distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
@@ -1175,7 +1173,7 @@ static int search_tiles(rag_ctx* h, int tenant, query_tenants qt, int Q, hipStre
             u->list = tiles.empty() ? nullptr : h->union_tiles.get();
         }
     } else if (tenant >= 0) {
-        ARG_CHECK(h, h->tenant_rows == h->n_rows, "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
+        ARG_CHECK(h, tenants_cover(h, h->n_rows), "tenant table is stale (rows were appended after rag_index_set_tenants_host)");
         const auto it = h->tenant_span.find(tenant);
         u->count = it == h->tenant_span.end() ? 0 : it->second.second;
         u->list = it == h->tenant_span.end() ? nullptr : h->tenant_tiles + it->second.first;

@@ -11,8 +11,6 @@
 #include <cmath>
 #include <cstring>
 
-#define LOCK(h) std::lock_guard<std::mutex> lock_((h)->mu)
-
 // ---- kernels ------------------------------------------------------------------------------------------------------------
 // vis[first, first + n) = tenant of the row (0 without a tenant table); keep_dead leaves deleted rows deleted
 __global__ __launch_bounds__(256) void live_vis_fill_kernel(int32_t* __restrict__ vis, const int32_t* __restrict__ tenants,
@@ -106,19 +104,22 @@ __global__ __launch_bounds__(256) void live_compact_gather_kernel(const W* __res
 // ---- host helpers -----------------------------------------------------------------------------------------------------
 static int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 
+// the tenant table where it covers rows [0, n), else null (vis then reads tenant 0)
+static const int32_t* tenants_covering(const rag_ctx* h, int64_t n) {
+    return (h->tenants != nullptr && (int64_t)h->tenants.size() >= n) ? h->tenants.get() : nullptr;
+}
+
 // vis rows [first, first + n) from the tenant table (0 without one, or where the table does not cover the rows), growing vis
 int live_vis_extend(rag_ctx* h, int64_t first, int64_t n) {
-    if (first + n > h->cap_vis) {
-        const int64_t cap = std::max(first + n, std::max(h->cap32, h->n_rows));
+    if (first + n > (int64_t)h->vis.size()) {
+        const int64_t cap = std::max(first + n, std::max(emb32_rows(h), h->n_rows));
         dev_buf<int32_t> nv;
         if (int rc = nv.alloc(h, (size_t)cap)) return rc;
         if (h->vis && first > 0) HIP_TRY(h, hipMemcpy(nv, h->vis, (size_t)first * sizeof(int32_t), hipMemcpyDeviceToDevice));
         h->vis = std::move(nv);
-        h->cap_vis = cap;
     }
     if (n <= 0) return RAG_OK;
-    const int32_t* ten = (h->tenants != nullptr && h->cap_ten >= first + n) ? h->tenants : nullptr;
-    hipLaunchKernelGGL(live_vis_fill_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, h->vis, ten, first, n, 0);
+    hipLaunchKernelGGL(live_vis_fill_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, h->vis, tenants_covering(h, first + n), first, n, 0);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RAG_OK;
@@ -127,8 +128,8 @@ int live_vis_extend(rag_ctx* h, int64_t first, int64_t n) {
 // the tenant table was replaced (rag_index_set_tenants_host): new tenant numbers, deleted rows stay deleted
 int live_vis_rebuild(rag_ctx* h) {
     if (!h->vis || h->n_rows == 0) return RAG_OK;
-    const int32_t* ten = (h->tenants != nullptr && h->cap_ten >= h->n_rows) ? h->tenants : nullptr;
-    hipLaunchKernelGGL(live_vis_fill_kernel, dim3(grid_for(h->n_rows)), dim3(256), 0, h->stream, h->vis, ten, (int64_t)0, h->n_rows, 1);
+    hipLaunchKernelGGL(live_vis_fill_kernel, dim3(grid_for(h->n_rows)), dim3(256), 0, h->stream, h->vis, tenants_covering(h, h->n_rows),
+                       (int64_t)0, h->n_rows, 1);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RAG_OK;
@@ -181,154 +182,441 @@ static int id_set_apply(rag_ctx* h, const std::vector<int64_t>& set, int tenant,
 
 static int64_t grow_cap(int64_t cap, int64_t need) { return need <= cap ? cap : std::max(need, cap + cap / 8 + 256); }
 
-extern "C" {
+// ---- insert -----------------------------------------------------------------------------------------------------------
+// one rag_index_insert_host call: the block, where it lands, and what the host makes of it before anything changes
+struct insert_job {
+    const rag_row_block* rb;
+    int64_t n0, n, need;                 // rows before, rows of the block, rows after
+    bool has_tok, wide_tok;              // a token store is loaded / a 24-bit one
+    double tmax = 0.0;                   // max |temporal score| of the block
+    std::vector<uint16_t> tok16;         // the block's token ids narrowed: bits 0-15 ...
+    std::vector<uint8_t> tok_hi8;        // ... and bits 16-23, for a 24-bit store
+};
 
-int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* first_row_out) {
-    if (!h) return RAG_ERR_ARG;
-    LOCK(h);
-    ARG_CHECK(h, rb != nullptr, "insert: null row block");
-    const int64_t n = rb->n;
-    ARG_CHECK(h, n >= 0 && (n == 0 || rb->emb != nullptr), "insert: need n >= 0 and emb[n][dim]");
-    int rc = live_begin(h);
-    if (rc) return rc;
-    const int64_t n0 = h->index_loaded ? h->n_rows : 0;
-    ARG_CHECK(h, n0 + n < (int64_t)0x7fffff00, "insert: n_rows must fit int32 per GPU");
+// phase 1: the block brings exactly the planes the index has (an empty index may be started), and those cover its rows
+static int insert_check(rag_ctx* h, const insert_job& in) {
+    const rag_row_block* rb = in.rb;
+    const int64_t n0 = in.n0;
+    ARG_CHECK(h, n0 + in.n < (int64_t)0x7fffff00, "insert: n_rows must fit int32 per GPU");
     const bool empty = n0 == 0;          // planes an empty index does not have yet may be started by this insert
     ARG_CHECK(h, rb->ids != nullptr || h->ids == nullptr, "insert: ids are required (the index stores explicit ids)");
-    const bool has_ten = h->tenants != nullptr, has_tmp = h->temporal != nullptr, has_tok = h->tok != nullptr;
+    const bool has_ten = h->tenants != nullptr, has_tmp = h->temporal != nullptr;
     ARG_CHECK(h, has_ten ? rb->tenants != nullptr : (rb->tenants == nullptr || empty),
               "insert: tenants are required iff the index has a tenant table");
     ARG_CHECK(h, has_tmp ? rb->temporal != nullptr : (rb->temporal == nullptr || empty),
               "insert: temporal scores are required iff the index has them");
-    ARG_CHECK(h, has_tok ? (rb->tokens != nullptr && rb->token_lens != nullptr) : rb->tokens == nullptr,
+    ARG_CHECK(h, in.has_tok ? (rb->tokens != nullptr && rb->token_lens != nullptr) : rb->tokens == nullptr,
               "insert: tokens and token_lens are required iff a token store is loaded");
-    if (has_ten && !(h->tenant_rows == n0 && h->cap_ten >= n0)) {
+    if (has_ten && !tenants_cover(h, n0)) {
         h->err = "insert: the tenant table is stale (rows were appended after rag_index_set_tenants_host)";
         return RAG_ERR_STATE;
     }
-    if ((has_tmp && h->cap_tmp < n0) || (h->ids && h->cap_ids < n0) || (has_tok && h->tok_rows != n0)) {
+    if ((has_tmp && (int64_t)h->temporal.size() < n0) || !ids_cover(h, n0) || (in.has_tok && !tokens_aligned(h, n0))) {
         h->err = "insert: the temporal scores, ids or token store do not cover the index rows";
         return RAG_ERR_STATE;
     }
-    if (first_row_out) *first_row_out = n0;
-    if (n == 0) return RAG_OK;
-    // ---- host-side checks of the block
+    return RAG_OK;
+}
+
+// phase 2, on the host: tenants >= 0, finite temporal scores, token ids narrowed to the store's width, ids unique and not live
+static int insert_convert(rag_ctx* h, insert_job& in) {
+    const rag_row_block* rb = in.rb;
+    const int64_t n = in.n;
     if (rb->tenants)
         for (int64_t i = 0; i < n; ++i) ARG_CHECK(h, rb->tenants[i] >= 0, "insert: tenant numbers must be >= 0");
-    double tmax = 0.0;
     if (rb->temporal) {
-        for (int64_t i = 0; i < n; ++i) tmax = std::max(tmax, std::fabs(rb->temporal[i]));
-        ARG_CHECK(h, std::isfinite(tmax), "insert: temporal scores must be finite");
+        for (int64_t i = 0; i < n; ++i) in.tmax = std::max(in.tmax, std::fabs(rb->temporal[i]));
+        ARG_CHECK(h, std::isfinite(in.tmax), "insert: temporal scores must be finite");
     }
-    std::vector<uint16_t> tok16;
-    std::vector<uint8_t> tok_hi8;        // bits 16-23, for a 24-bit store
-    const bool wide_tok = has_tok && h->tok_hi != nullptr;
-    if (has_tok) {
+    if (in.has_tok) {
         const int L = h->tok_L;
-        tok16.resize((size_t)n * L);
-        if (wide_tok) tok_hi8.resize((size_t)n * L);
+        in.tok16.resize((size_t)n * L);
+        if (in.wide_tok) in.tok_hi8.resize((size_t)n * L);
         for (int64_t i = 0; i < n * L; ++i) {
             const int32_t v = rb->tokens[i];
-            if (wide_tok) {
+            if (in.wide_tok) {
                 ARG_CHECK(h, v >= 0 && v <= 0xFFFFFF, "insert: token ids must be in [0, 16777215]");
-                tok_hi8[(size_t)i] = (uint8_t)(v >> 16);
+                in.tok_hi8[(size_t)i] = (uint8_t)(v >> 16);
             } else {
                 ARG_CHECK(h, v >= 0 && v <= 65535, "insert: token ids must be in [0, 65535]");
             }
-            tok16[(size_t)i] = (uint16_t)v;
+            in.tok16[(size_t)i] = (uint16_t)v;
         }
     }
-    std::vector<int64_t> set;
     if (rb->ids) {
-        set.assign(rb->ids, rb->ids + n);
+        std::vector<int64_t> set(rb->ids, rb->ids + n);
         std::sort(set.begin(), set.end());
         ARG_CHECK(h, std::adjacent_find(set.begin(), set.end()) == set.end(), "insert: an id is repeated inside the block");
         int64_t live = 0;
-        if ((rc = id_set_apply(h, set, -1, 0, &live))) return rc;
+        if (int rc = id_set_apply(h, set, -1, 0, &live)) return rc;
         ARG_CHECK(h, live == 0, "insert: an id is already live in the index (primary key)");
     }
-    // ---- capacity: first what rag_index_reserve left, then growth of every row-aligned plane (all allocated before any change)
-    const int64_t need = n0 + n;
-    const int64_t cap32 = grow_cap(std::max(h->cap32, n0), need);
-    const int64_t pad = round_up(std::max(need, cap32), (int64_t)RAG_TILE * 8);
-    const int64_t cap_ids = h->ids ? grow_cap(h->cap_ids, need) : cap32, cap_ten = h->tenants ? grow_cap(h->cap_ten, need) : cap32;
-    const int64_t cap_tmp = h->temporal ? grow_cap(h->cap_tmp, need) : cap32, cap_vis = grow_cap(h->cap_vis, need);
-    const int64_t cap_tok = grow_cap(h->tok_cap, need);
-    rag_device_mem g;                    // the grown planes under the handle's field names: dropped whole unless committed below
+    return RAG_OK;
+}
+
+// the planes this block writes rows into, or that follow the rows (vis): the others are left as they are
+static bool insert_feeds(const rag_ctx* h, const insert_job& in, int plane) {
+    switch (plane) {
+    case PLANE_IDS: return in.rb->ids != nullptr;
+    case PLANE_TENANTS: return in.rb->tenants != nullptr;
+    case PLANE_TEMPORAL: return in.rb->temporal != nullptr;
+    case PLANE_VIS: return h->vis != nullptr;
+    case PLANE_TOK: case PLANE_TOK_LEN: return in.has_tok;
+    case PLANE_TOK_HI: return in.wide_tok;
+    default: return true;                // emb32, emb16
+    }
+}
+
+// phase 3a: every plane the block feeds and that has no room for `need` rows is allocated anew in g, under the handle's field
+// names; nothing of the handle changes, so a failure leaves the index as it was. The master rows first use what
+// rag_index_reserve left, then grow by grow_cap; emb16 stays padded to 8 tiles beyond them; a plane started here gets the
+// master rows' capacity; the three token planes grow together, by the reservation tok_len shows.
+static int insert_grow(rag_ctx* h, const insert_job& in, rag_device_mem* g) {
+    const int64_t need = in.need, master = grow_cap(std::max(emb32_rows(h), in.n0), need);
     bool ok = true;
-    auto grow = [&](auto& plane, bool wanted, int64_t rows, size_t row_elems) {
-        ok = ok && (!wanted || plane.alloc(h, (size_t)rows * row_elems) == RAG_OK);
-    };
-    grow(g.emb32, cap32 != h->cap32 || !h->emb32, cap32, h->dim);
-    grow(g.emb16, need > h->n_rows_pad || !h->emb16, pad, h->dim_pad);
-    grow(g.ids, rb->ids && (!h->ids || need > h->cap_ids), cap_ids, 1);
-    grow(g.tenants, rb->tenants && (!h->tenants || need > h->cap_ten), cap_ten, 1);
-    grow(g.temporal, rb->temporal && (!h->temporal || need > h->cap_tmp), cap_tmp, 1);
-    grow(g.vis, h->vis && need > h->cap_vis, cap_vis, 1);
-    grow(g.tok, has_tok && need > h->tok_cap, cap_tok, h->tok_L);
-    grow(g.tok_hi, wide_tok && need > h->tok_cap, cap_tok, h->tok_L);
-    grow(g.tok_len, has_tok && need > h->tok_cap, cap_tok, 1);
-    if (!ok) {
-        (void)hipGetLastError();
-        h->err = "insert: out of device memory while growing the index (reserve headroom with rag_index_reserve)";
-        return RAG_ERR_NOMEM;
+    for_each_row_plane(h, [&](int id, auto mp, int64_t width) {
+        const bool token = id == PLANE_TOK || id == PLANE_TOK_HI || id == PLANE_TOK_LEN;
+        const int64_t cap = token ? tok_cap_rows(h) : plane_rows(h->*mp, width);
+        if (!ok || !insert_feeds(h, in, id) || need <= cap) return RAG_OK;
+        const int64_t rows = id == PLANE_EMB32   ? master
+                             : id == PLANE_EMB16 ? round_up(std::max(need, master), (int64_t)RAG_TILE * 8)
+                             : cap > 0           ? grow_cap(cap, need)
+                                                 : master;
+        ok = (g->*mp).alloc(h, (size_t)rows * width) == RAG_OK;
+        return RAG_OK;
+    });
+    if (ok) return RAG_OK;
+    (void)hipGetLastError();
+    h->err = "insert: out of device memory while growing the index (reserve headroom with rag_index_reserve)";
+    return RAG_ERR_NOMEM;
+}
+
+// inserting on a handle with no index creates one
+static int insert_start_index(rag_ctx* h) {
+    if (h->index_loaded) return RAG_OK;
+    if (!h->bad_rows) {
+        if (int rc = h->bad_rows.alloc(h, 1)) return rc;
+        HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), h->stream));
     }
+    h->n_rows = 0;
+    h->id_base = 0;
+    h->index_loaded = true;
+    return RAG_OK;
+}
+
+// phase 3b, per grown plane: copy the used rows over (device to device), then move the new allocation into the handle, which
+// frees the old one
+static int insert_move_in(rag_ctx* h, const insert_job& in, rag_device_mem* g) {
     hipStream_t st = h->stream;
-    if (!h->index_loaded) {              // inserting on a handle with no index creates one
-        if (!h->bad_rows) {
-            if ((rc = h->bad_rows.alloc(h, 1))) return rc;
-            HIP_TRY(h, hipMemsetAsync(h->bad_rows, 0, sizeof(int), st));
-        }
-        h->n_rows = 0;
-        h->id_base = 0;
-        h->index_loaded = true;
-    }
-    // ---- commit, per grown plane: copy the used rows over (device to device), then move the new allocation into the handle,
-    // which frees the old one
-    auto commit = [&](auto& plane, auto& grown, size_t row_elems, int64_t* cap, int64_t new_cap) -> int {
+    const int64_t n0 = in.n0;
+    return for_each_row_plane(h, [&](int id, auto mp, int64_t width) -> int {
+        auto& plane = h->*mp;
+        auto& grown = g->*mp;
         if (!grown) return RAG_OK;
-        if (plane && n0 > 0)
-            HIP_TRY(h, hipMemcpyAsync(grown, plane, (size_t)n0 * row_elems * sizeof(*grown.get()), hipMemcpyDeviceToDevice, st));
+        const size_t row_bytes = (size_t)width * sizeof(*grown.get());
+        if (id == PLANE_EMB16)               // tile padding and not-yet-written rows must read as zero vectors
+            HIP_TRY(h, hipMemsetAsync(grown + (size_t)n0 * width, 0, (size_t)(plane_rows(grown, width) - n0) * row_bytes, st));
+        if (id == PLANE_IDS && !plane && n0 > 0)      // implicit ids become a stored column (same values)
+            hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, g->ids.get(), h->id_base, n0);
+        if (plane && n0 > 0) HIP_TRY(h, hipMemcpyAsync(grown, plane, (size_t)n0 * row_bytes, hipMemcpyDeviceToDevice, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         plane = std::move(grown);
-        if (cap) *cap = new_cap;
         return RAG_OK;
-    };
-    if ((rc = commit(h->emb32, g.emb32, h->dim, &h->cap32, cap32))) return rc;
-    if (g.emb16)                         // tile padding and not-yet-written rows must read as zero vectors
-        HIP_TRY(h, hipMemsetAsync(g.emb16 + (size_t)n0 * h->dim_pad, 0, (size_t)(pad - n0) * h->dim_pad * sizeof(half_t), st));
-    if ((rc = commit(h->emb16, g.emb16, h->dim_pad, &h->n_rows_pad, pad))) return rc;
-    if (g.ids && !h->ids && n0 > 0)      // implicit ids become a stored column (same values)
-        hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, g.ids.get(), h->id_base, n0);
-    if ((rc = commit(h->ids, g.ids, 1, &h->cap_ids, cap_ids))) return rc;
-    if ((rc = commit(h->tenants, g.tenants, 1, &h->cap_ten, cap_ten))) return rc;
-    if ((rc = commit(h->temporal, g.temporal, 1, &h->cap_tmp, cap_tmp))) return rc;
-    if ((rc = commit(h->vis, g.vis, 1, &h->cap_vis, cap_vis))) return rc;
-    if ((rc = commit(h->tok_hi, g.tok_hi, h->tok_L, nullptr, 0))) return rc;
-    if ((rc = commit(h->tok, g.tok, h->tok_L, &h->tok_cap, cap_tok))) return rc;
-    if ((rc = commit(h->tok_len, g.tok_len, 1, nullptr, 0))) return rc;
+    });
+}
+
+// phase 4: the block's rows into every plane it feeds, then the new row count and what depends on it
+static int insert_write(rag_ctx* h, const insert_job& in) {
+    const rag_row_block* rb = in.rb;
+    const int64_t n0 = in.n0, n = in.n;
+    hipStream_t st = h->stream;
+    int rc;
     HIP_TRY(h, hipMemcpyAsync(h->emb32 + (size_t)n0 * h->dim, rb->emb, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
     if ((rc = dense_index_normalize_range(h, n0, n, st))) return rc;
     if (rb->ids) HIP_TRY(h, hipMemcpyAsync(h->ids + n0, rb->ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
     if (rb->tenants) HIP_TRY(h, hipMemcpyAsync(h->tenants + n0, rb->tenants, (size_t)n * 4, hipMemcpyHostToDevice, st));
     if (rb->temporal) {
         HIP_TRY(h, hipMemcpyAsync(h->temporal + n0, rb->temporal, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        h->temporal_absmax = std::max(h->temporal_absmax, tmax);       // sizes the fused-emission error bound
+        h->temporal_absmax = std::max(h->temporal_absmax, in.tmax);       // sizes the fused-emission error bound
     }
-    if (has_tok) {
-        HIP_TRY(h, hipMemcpyAsync(h->tok + (size_t)n0 * h->tok_L, tok16.data(), tok16.size() * 2, hipMemcpyHostToDevice, st));
-        if (wide_tok) HIP_TRY(h, hipMemcpyAsync(h->tok_hi + (size_t)n0 * h->tok_L, tok_hi8.data(), tok_hi8.size(), hipMemcpyHostToDevice, st));
+    if (in.has_tok) {
+        HIP_TRY(h, hipMemcpyAsync(h->tok + (size_t)n0 * h->tok_L, in.tok16.data(), in.tok16.size() * 2, hipMemcpyHostToDevice, st));
+        if (in.wide_tok)
+            HIP_TRY(h, hipMemcpyAsync(h->tok_hi + (size_t)n0 * h->tok_L, in.tok_hi8.data(), in.tok_hi8.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(h->tok_len + n0, rb->token_lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(h, hipStreamSynchronize(st));
     if (h->vis && (rc = live_vis_extend(h, n0, n))) return rc;
     if (rb->tenants && (rc = dense_tenant_tiles_append(h, rb->tenants, n0, n))) return rc;
-    h->n_rows = need;
-    if (has_tok) h->tok_rows = need;
+    h->n_rows = in.need;
+    if (in.has_tok) h->tok_rows = in.need;
     h->bm25_stale = true;
     h->sparse_stale = true;
     live_rows_changed(h);
     return RAG_OK;
+}
+
+// ---- compaction -------------------------------------------------------------------------------------------------------
+#define LIVE_STAGING_BYTES ((size_t)1 << 30)       // bound of the compaction's device memory beyond the planes
+
+// rag_index_compact (keep_postings = false: the postings end stale and compacted) and rag_index_compact_bm25 (true: loaded
+// postings that describe the rows are renumbered through the row map, beside the old ones, BEFORE the first row moves, and
+// swapped in once the rows have moved; bm25_stale is left as it was - current stays current, uncovered rows stay uncovered)
+// and rag_index_compact_live (LIVE_KEEP_RESIDENT: the same for the learned-sparse postings as well, and the token-vector store's
+// documents move with their rows - tokvec.hip, "the store through a compaction" - instead of going stale)
+enum { LIVE_KEEP_NONE = 0, LIVE_KEEP_BM25 = 1, LIVE_KEEP_RESIDENT = 2 };
+
+// postings built beside the resident ones: dropped unless committed
+struct new_postings {
+    rag_bm25_index* p = nullptr;
+    ~new_postings() { if (p) bm25_compact_discard(p); }
+};
+
+// one compaction: the staging buffer and its carve, the row map's host side, and what was prepared beside the rows
+struct compact_job {
+    int keep;
+    int64_t n0, tiles;                   // rows and 256-row tiles before
+    bool move_tv;                        // the token-vector store's documents move with their rows
+    dev_buf<char> ws;                    // tile_cnt [tiles] | tile_off [tiles] (its exclusive scan) | row_map [n0] (old row -> new row or -1) |
+    int* tile_cnt;                       // src_rows [n_live] (new row -> old row) | data: one chunk of gathered rows
+    int64_t *tile_off, *row_map;
+    int32_t* src_rows;
+    char* data;
+    size_t data_bytes;
+    std::vector<int64_t> off;            // host copy of tile_off
+    int64_t n_live = 0, first_move = -1; // rows that stay; the first row of the first tile that loses one (rows before it do not move)
+    new_postings np, np_sparse;
+    tokvec_compact_plan tvp;
+    bool ten = false, tok = false;       // the tenant table / the token store covered the rows and moved with them
+};
+
+static int compact_fail(rag_ctx* h, hipError_t e, const char* what) {
+    h->err = std::string("compact: ") + what + ": " + hipGetErrorString(e);
+    return RAG_ERR_HIP;
+}
+
+// the staging buffer: tile counts | tile offsets | row map | source rows | row data, within LIVE_STAGING_BYTES
+// (the token-vector store's own maps are per document - new offsets and first source row, tokvec_compact_prepare - and count
+// against the same bound)
+static int compact_stage(rag_ctx* h, compact_job& c) {
+    const int64_t n0 = c.n0, tiles = c.tiles;
+    const size_t tv_bytes = c.move_tv ? stage_size((size_t)h->tv_docs_cap + 1, 8) + stage_size((size_t)h->tv_docs + 1, 8) : 0;
+    const size_t map_bytes = stage_size(tiles, 4) + stage_size(tiles, 8) + stage_size(n0, 8) + stage_size(n0, 4);
+    ARG_CHECK(h, map_bytes + tv_bytes + ((size_t)64 << 20) <= LIVE_STAGING_BYTES, "compact: the row map of this index exceeds the 1 GiB staging bound");
+    c.data_bytes = std::min<size_t>((size_t)512 << 20, LIVE_STAGING_BYTES - map_bytes - tv_bytes);
+    if (c.ws.alloc(h, map_bytes + c.data_bytes)) {
+        (void)hipGetLastError();
+        h->err = "compact: out of device memory for the staging buffer";
+        return RAG_ERR_NOMEM;
+    }
+    char* p = c.ws;
+    c.tile_cnt = stage_take<int>(p, tiles);
+    c.tile_off = stage_take<int64_t>(p, tiles);
+    c.row_map = stage_take<int64_t>(p, n0);
+    c.src_rows = stage_take<int32_t>(p, n0);
+    c.data = p;
+    return RAG_OK;
+}
+
+// phase 1, the row map: live rows per tile, their exclusive scan on the host (tiles entries: 49K at 12.5M rows), the first tile
+// that loses a row, then row_map and src_rows on the device
+static int compact_row_map(rag_ctx* h, compact_job& c) {
+    hipStream_t st = h->stream;
+    const int64_t n0 = c.n0, tiles = c.tiles;
+    hipLaunchKernelGGL(live_tile_count_kernel, dim3((unsigned)tiles), dim3(256), 0, st, h->vis, n0, c.tile_cnt);
+    std::vector<int> cnt((size_t)tiles);
+    hipError_t e = hipMemcpyAsync(cnt.data(), c.tile_cnt, (size_t)tiles * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return compact_fail(h, e, "tile counts");
+    c.off.resize((size_t)tiles);
+    for (int64_t t = 0; t < tiles; ++t) {
+        c.off[(size_t)t] = c.n_live;
+        c.n_live += cnt[(size_t)t];
+        if (c.first_move < 0 && cnt[(size_t)t] < std::min<int64_t>(RAG_TILE, n0 - t * RAG_TILE)) c.first_move = t * RAG_TILE;
+    }
+    if (c.first_move < 0) c.first_move = n0;
+    e = hipMemcpyAsync(c.tile_off, c.off.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return compact_fail(h, e, "tile offsets");
+    hipLaunchKernelGGL(live_row_map_kernel, dim3((unsigned)tiles), dim3(256), 0, st, h->vis, n0, c.tile_off, c.row_map, c.src_rows);
+    return RAG_OK;
+}
+
+// live rows below row x: the scanned tile offsets + the live rows of x's own tile before it (at most 255 map entries)
+static int compact_live_below(rag_ctx* h, const compact_job& c, int64_t x, int64_t* out) {
+    *out = c.n_live;
+    if (x >= c.n0) return RAG_OK;
+    const int64_t t0 = x / RAG_TILE * RAG_TILE;
+    int64_t part[RAG_TILE];
+    if (x > t0) HIP_TRY(h, hipMemcpyAsync(part, c.row_map + t0, (size_t)(x - t0) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out = c.off[(size_t)(t0 / RAG_TILE)];
+    for (int64_t i = 0; i < x - t0; ++i) *out += part[i] >= 0;
+    return RAG_OK;
+}
+
+// one resident index (the BM25 or the learned-sparse postings) that describes the rows: remapped into `dst`
+static int compact_remap_postings(rag_ctx* h, const compact_job& c, const rag_bm25_index* ix, bool compacted, new_postings& dst) {
+    const int64_t covered = bm25_covered_docs(ix);
+    if (ix == nullptr || compacted || covered > c.n0) return RAG_OK;
+    int64_t base_live = 0, covered_live = 0;
+    int rc;
+    if ((rc = compact_live_below(h, c, bm25_base_docs(ix), &base_live))) return rc;
+    if ((rc = compact_live_below(h, c, covered, &covered_live))) return rc;
+    return bm25_compact_prepare(h, ix, c.row_map, base_live, covered_live, &dst.p);
+}
+
+// phase 2, what moves beside the rows: the postings of the rows that stay, under their new numbers, and the token-vector
+// store's new offsets and per-document source map (from a host copy of the row map). Everything is allocated and built here,
+// nothing is replaced yet.
+static int compact_prepare(rag_ctx* h, compact_job& c) {
+    int rc;
+    if (c.keep >= LIVE_KEEP_BM25 && (rc = compact_remap_postings(h, c, h->bm25, h->bm25_compacted, c.np))) return rc;
+    if (c.keep == LIVE_KEEP_RESIDENT && (rc = compact_remap_postings(h, c, h->sparse, h->sparse_compacted, c.np_sparse))) return rc;
+    if (c.move_tv) {
+        std::vector<int64_t> map_h((size_t)c.n0);
+        HIP_TRY(h, hipMemcpyAsync(map_h.data(), c.row_map, (size_t)c.n0 * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if ((rc = tokvec_compact_prepare(h, map_h.data(), c.n0, c.data_bytes, &c.tvp))) return rc;
+    }
+    return RAG_OK;
+}
+
+// gathers `bytes` of rows (row_bytes each, sources src_rows) into the staging buffer, in the widest word that divides a row
+template <class W>
+static void gather_words(const void* plane, size_t row_bytes, const int32_t* src_rows, size_t bytes, char* stage, hipStream_t st) {
+    const uint32_t rw = (uint32_t)(row_bytes / sizeof(W)), total = (uint32_t)(bytes / sizeof(W));
+    hipLaunchKernelGGL(live_compact_gather_kernel<W>, dim3(grid_for(total)), dim3(256), 0, st, (const W*)plane, rw, src_rows, total, (W*)stage);
+}
+static void gather_rows(const void* plane, size_t row_bytes, const int32_t* src_rows, size_t bytes, char* stage, hipStream_t st) {
+    if (row_bytes % 16 == 0) gather_words<uint4>(plane, row_bytes, src_rows, bytes, stage, st);
+    else if (row_bytes % 8 == 0) gather_words<uint2>(plane, row_bytes, src_rows, bytes, stage, st);
+    else if (row_bytes % 4 == 0) gather_words<uint32_t>(plane, row_bytes, src_rows, bytes, stage, st);
+    else if (row_bytes % 2 == 0) gather_words<uint16_t>(plane, row_bytes, src_rows, bytes, stage, st);
+    else gather_words<uint8_t>(plane, row_bytes, src_rows, bytes, stage, st);      // a row of L bytes: any alignment
+}
+
+// phase 3: every plane that covers the rows, chunk by chunk of destination rows through the staging buffer; then the fp16
+// padding, the row map for the caller and the token-vector rows, and the one wait for all of it. vis does not move (it is
+// dropped); the token planes move when the store is aligned with the index; any other plane when it has room for the rows.
+static int compact_move_planes(rag_ctx* h, compact_job& c, int64_t* row_map_out) {
+    hipStream_t st = h->stream;
+    const int64_t n0 = c.n0, n_live = c.n_live;
+    c.ten = h->tenants && (int64_t)h->tenants.size() >= n0;
+    c.tok = tokens_aligned(h, n0);
+    struct plane { char* p; size_t row_bytes; };
+    std::vector<plane> planes;
+    for_each_row_plane(h, [&](int id, auto mp, int64_t width) {
+        const auto& b = h->*mp;
+        const bool token = id == PLANE_TOK || id == PLANE_TOK_HI || id == PLANE_TOK_LEN;
+        if (b && id != PLANE_VIS && (token ? c.tok : plane_rows(b, width) >= n0)) planes.push_back({(char*)b.get(), (size_t)width * sizeof(*b.get())});
+        return RAG_OK;
+    });
+    hipError_t e = hipSuccess;
+    for (const plane& pl : planes) {
+        const int64_t chunk = std::max<int64_t>(1, (int64_t)(c.data_bytes / pl.row_bytes));
+        for (int64_t d0 = c.first_move; d0 < n_live; d0 += chunk) {
+            const size_t bytes = (size_t)std::min(chunk, n_live - d0) * pl.row_bytes;
+            gather_rows(pl.p, pl.row_bytes, c.src_rows + d0, bytes, c.data, st);
+            e = hipMemcpyAsync(pl.p + (size_t)d0 * pl.row_bytes, c.data, bytes, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) return compact_fail(h, e, "row copy");
+        }
+    }
+    // the rows past the new end are tile padding of the fp16 operand again: zero
+    if (n0 > n_live) e = hipMemsetAsync(h->emb16 + (size_t)n_live * h->dim_pad, 0, (size_t)(n0 - n_live) * h->dim_pad * 2, st);
+    if (e == hipSuccess && row_map_out) e = hipMemcpyAsync(row_map_out, c.row_map, (size_t)n0 * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return compact_fail(h, e, "finish");
+    if (int rc = tokvec_compact_commit(h, &c.tvp, c.data, st)) return rc;      // (the staging buffer is free again: same stream)
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return compact_fail(h, e, "finish");
+    return RAG_OK;
+}
+
+// phase 4: the new row count, no deleted rows, the prepared postings swapped in (or the resident ones stale), new tenant tiles
+static int compact_publish(rag_ctx* h, compact_job& c) {
+    const int64_t n_live = c.n_live;
+    c.ws.reset();
+    h->n_rows = n_live;
+    if (c.tok) h->tok_rows = n_live;
+    h->vis.reset();
+    h->n_deleted = 0;
+    if (c.np_sparse.p) {                     // rag_index_compact_live: renumbered with the rows, staleness left as it was
+        bm25_compact_commit(&h->sparse, c.np_sparse.p);
+        c.np_sparse.p = nullptr;
+    } else {                                 // not renumbered: a reload makes them current
+        h->sparse_stale = true;
+        h->sparse_compacted = true;
+    }
+    if (h->tv_docs_cap > 0 && !c.move_tv) h->tv_stale = true;    // nor are the resident token vectors, unless they moved (tokvec.hip)
+    if (c.np.p) {
+        bm25_compact_commit(&h->bm25, c.np.p);
+        c.np.p = nullptr;
+    } else {
+        h->bm25_stale = true;
+        h->bm25_compacted = true;
+    }
+    live_rows_changed(h);
+    if (c.ten) {                             // tenant tile lists of the new row numbers
+        std::vector<int32_t> t((size_t)n_live);
+        if (n_live > 0) HIP_TRY(h, hipMemcpy(t.data(), h->tenants, (size_t)n_live * 4, hipMemcpyDeviceToHost));
+        if (int rc = dense_build_tenant_tiles(h, n_live > 0 ? t.data() : nullptr, n_live)) return rc;
+        h->tenant_rows = n_live;
+    }
+    return RAG_OK;
+}
+
+static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, int keep) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    int rc = live_begin(h);
+    if (rc) return rc;
+    const int64_t n0 = h->index_loaded ? h->n_rows : 0;
+    if (h->n_deleted == 0 || h->vis == nullptr) {
+        if (row_map_out)
+            for (int64_t i = 0; i < n0; ++i) row_map_out[i] = i;
+        if (n_rows_out) *n_rows_out = n0;
+        return RAG_OK;
+    }
+    if (!ids_cover(h, n0)) {
+        h->err = "compact: the stored ids do not cover the index rows";
+        return RAG_ERR_STATE;
+    }
+    // doc ids never change: an implicit-id index stores its ids before any row moves
+    if (!h->ids) {
+        if ((rc = h->ids.alloc(h, (size_t)std::max(emb32_rows(h), n0)))) return rc;
+        hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, h->stream, h->ids, h->id_base, n0);
+        HIP_TRY(h, hipGetLastError());
+    }
+    compact_job c{keep, n0, (n0 + RAG_TILE - 1) / RAG_TILE, keep == LIVE_KEEP_RESIDENT && h->tv_docs_cap > 0 && !h->tv_stale};
+    if ((rc = compact_stage(h, c))) return rc;
+    if ((rc = compact_row_map(h, c))) return rc;
+    if ((rc = compact_prepare(h, c))) return rc;
+    if ((rc = compact_move_planes(h, c, row_map_out))) return rc;
+    if ((rc = compact_publish(h, c))) return rc;
+    if (n_rows_out) *n_rows_out = c.n_live;
+    return RAG_OK;
+}
+
+extern "C" {
+
+int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* first_row_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, rb != nullptr, "insert: null row block");
+    ARG_CHECK(h, rb->n >= 0 && (rb->n == 0 || rb->emb != nullptr), "insert: need n >= 0 and emb[n][dim]");
+    int rc = live_begin(h);
+    if (rc) return rc;
+    const int64_t n0 = h->index_loaded ? h->n_rows : 0;
+    insert_job in{rb, n0, rb->n, n0 + rb->n, h->tok != nullptr, h->tok != nullptr && h->tok_hi != nullptr};
+    if ((rc = insert_check(h, in))) return rc;
+    if (first_row_out) *first_row_out = in.n0;
+    if (in.n == 0) return RAG_OK;
+    if ((rc = insert_convert(h, in))) return rc;
+    rag_device_mem g;                    // the grown planes: dropped whole unless moved into the handle
+    if ((rc = insert_grow(h, in, &g))) return rc;
+    if ((rc = insert_start_index(h))) return rc;
+    if ((rc = insert_move_in(h, in, &g))) return rc;
+    return insert_write(h, in);
 }
 
 int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int tenant, int64_t* n_deleted_out) {
@@ -340,11 +628,11 @@ int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int
     if (rc) return rc;
     if (!h->index_loaded || h->n_rows == 0 || n_ids == 0) return RAG_OK;
     ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "delete: tenant predicate given but no tenant table loaded");
-    if (tenant >= 0 && !(h->tenant_rows == h->n_rows && h->cap_ten >= h->n_rows)) {
+    if (tenant >= 0 && !tenants_cover(h, h->n_rows)) {
         h->err = "delete: the tenant table is stale (rows were appended after rag_index_set_tenants_host)";
         return RAG_ERR_STATE;
     }
-    if (h->ids && h->cap_ids < h->n_rows) {
+    if (!ids_cover(h, h->n_rows)) {
         h->err = "delete: the stored ids do not cover the index rows";
         return RAG_ERR_STATE;
     }
@@ -355,10 +643,7 @@ int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int
     if (created && (rc = live_vis_extend(h, 0, h->n_rows))) return rc;
     int64_t n_del = 0;
     if ((rc = id_set_apply(h, set, tenant, 1, &n_del))) return rc;
-    if (created && n_del == 0) {             // nothing deleted: keep the searches on their unfiltered path
-        h->vis.reset();
-        h->cap_vis = 0;
-    }
+    if (created && n_del == 0) h->vis.reset();       // nothing deleted: keep the searches on their unfiltered path
     h->n_deleted += n_del;
     if (n_deleted_out) *n_deleted_out = n_del;
     return RAG_OK;
@@ -371,204 +656,8 @@ int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out) {
     return RAG_OK;
 }
 
-#define LIVE_STAGING_BYTES ((size_t)1 << 30)       // bound of the compaction's device memory beyond the planes
-
-// rag_index_compact (keep_postings = false: the postings end stale and compacted) and rag_index_compact_bm25 (true: loaded
-// postings that describe the rows are renumbered through the row map, beside the old ones, BEFORE the first row moves, and
-// swapped in once the rows have moved; bm25_stale is left as it was - current stays current, uncovered rows stay uncovered)
-// and rag_index_compact_live (LIVE_KEEP_RESIDENT: the same for the learned-sparse postings as well, and the token-vector store's
-// documents move with their rows - tokvec.hip, "the store through a compaction" - instead of going stale)
-enum { LIVE_KEEP_NONE = 0, LIVE_KEEP_BM25 = 1, LIVE_KEEP_RESIDENT = 2 };
-static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, int keep) {
-    int rc = live_begin(h);
-    if (rc) return rc;
-    const int64_t n0 = h->index_loaded ? h->n_rows : 0;
-    if (h->n_deleted == 0 || h->vis == nullptr) {
-        if (row_map_out)
-            for (int64_t i = 0; i < n0; ++i) row_map_out[i] = i;
-        if (n_rows_out) *n_rows_out = n0;
-        return RAG_OK;
-    }
-    if (h->ids && h->cap_ids < n0) {
-        h->err = "compact: the stored ids do not cover the index rows";
-        return RAG_ERR_STATE;
-    }
-    hipStream_t st = h->stream;
-    // doc ids never change: an implicit-id index stores its ids before any row moves
-    if (!h->ids) {
-        const int64_t cap = std::max(h->cap32, n0);
-        if ((rc = h->ids.alloc(h, (size_t)cap))) return rc;
-        h->cap_ids = cap;
-        hipLaunchKernelGGL(live_iota_ids_kernel, dim3(grid_for(n0)), dim3(256), 0, st, h->ids, h->id_base, n0);
-        HIP_TRY(h, hipGetLastError());
-    }
-    const int64_t tiles = (n0 + RAG_TILE - 1) / RAG_TILE;
-    // (the token-vector store's own maps are per document - new offsets and first source row, tokvec_compact_prepare - and count
-    // against the same bound)
-    const bool move_tv = keep == LIVE_KEEP_RESIDENT && h->tv_docs_cap > 0 && !h->tv_stale;
-    const size_t tv_bytes = move_tv ? stage_size((size_t)h->tv_docs_cap + 1, 8) + stage_size((size_t)h->tv_docs + 1, 8) : 0;
-    const size_t map_bytes = stage_size(tiles, 4) + stage_size(tiles, 8) + stage_size(n0, 8) + stage_size(n0, 4);
-    ARG_CHECK(h, map_bytes + tv_bytes + ((size_t)64 << 20) <= LIVE_STAGING_BYTES, "compact: the row map of this index exceeds the 1 GiB staging bound");
-    const size_t data_bytes = std::min<size_t>((size_t)512 << 20, LIVE_STAGING_BYTES - map_bytes - tv_bytes);
-    dev_buf<char> ws;
-    if (ws.alloc(h, map_bytes + data_bytes)) {
-        (void)hipGetLastError();
-        h->err = "compact: out of device memory for the staging buffer";
-        return RAG_ERR_NOMEM;
-    }
-    char* p = ws;
-    int* tile_cnt = stage_take<int>(p, tiles);
-    int64_t* tile_off = stage_take<int64_t>(p, tiles);
-    int64_t* row_map = stage_take<int64_t>(p, n0);
-    int32_t* src_rows = stage_take<int32_t>(p, n0);
-    char* data = p;
-    auto fail = [&](hipError_t e, const char* what) {
-        h->err = std::string("compact: ") + what + ": " + hipGetErrorString(e);
-        return RAG_ERR_HIP;
-    };
-    hipLaunchKernelGGL(live_tile_count_kernel, dim3((unsigned)tiles), dim3(256), 0, st, h->vis, n0, tile_cnt);
-    std::vector<int> cnt((size_t)tiles);
-    hipError_t e = hipMemcpyAsync(cnt.data(), tile_cnt, (size_t)tiles * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e, "tile counts");
-    // exclusive scan of the per-tile live counts (tiles entries: 49K at 12.5M rows), and the first tile that loses a row:
-    // rows before it do not move
-    std::vector<int64_t> off((size_t)tiles);
-    int64_t n_live = 0, first_move = -1;
-    for (int64_t t = 0; t < tiles; ++t) {
-        off[(size_t)t] = n_live;
-        n_live += cnt[(size_t)t];
-        if (first_move < 0 && cnt[(size_t)t] < std::min<int64_t>(RAG_TILE, n0 - t * RAG_TILE)) first_move = t * RAG_TILE;
-    }
-    if (first_move < 0) first_move = n0;
-    e = hipMemcpyAsync(tile_off, off.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(e, "tile offsets");
-    hipLaunchKernelGGL(live_row_map_kernel, dim3((unsigned)tiles), dim3(256), 0, st, h->vis, n0, tile_off, row_map, src_rows);
-    // the postings of the rows that stay, under their new numbers: everything allocated and built here, nothing replaced yet
-    struct new_postings {
-        rag_bm25_index* p = nullptr;
-        ~new_postings() { if (p) bm25_compact_discard(p); }
-    } np, np_sparse;
-    // one resident index (the BM25 or the learned-sparse postings) that describes the rows: remapped into `dst`
-    auto prepare = [&](const rag_bm25_index* ix, bool compacted, new_postings& dst) -> int {
-        const int64_t covered = bm25_covered_docs(ix);
-        if (ix == nullptr || compacted || covered > n0) return RAG_OK;
-        // live rows below row x: the scanned tile offsets + the live rows of x's own tile before it (at most 255 map entries)
-        auto live_below = [&](int64_t x, int64_t* out) -> int {
-            *out = n_live;
-            if (x >= n0) return RAG_OK;
-            const int64_t t0 = x / RAG_TILE * RAG_TILE;
-            int64_t part[RAG_TILE];
-            if (x > t0) HIP_TRY(h, hipMemcpyAsync(part, row_map + t0, (size_t)(x - t0) * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipStreamSynchronize(st));
-            *out = off[(size_t)(t0 / RAG_TILE)];
-            for (int64_t i = 0; i < x - t0; ++i) *out += part[i] >= 0;
-            return RAG_OK;
-        };
-        int64_t base_live = 0, covered_live = 0;
-        int rc2;
-        if ((rc2 = live_below(bm25_base_docs(ix), &base_live))) return rc2;
-        if ((rc2 = live_below(covered, &covered_live))) return rc2;
-        return bm25_compact_prepare(h, ix, row_map, base_live, covered_live, &dst.p);
-    };
-    if (keep >= LIVE_KEEP_BM25 && (rc = prepare(h->bm25, h->bm25_compacted, np))) return rc;
-    if (keep == LIVE_KEEP_RESIDENT && (rc = prepare(h->sparse, h->sparse_compacted, np_sparse))) return rc;
-    // the token-vector store's new offsets and per-document source map, from a host copy of the row map
-    tokvec_compact_plan tvp;
-    if (move_tv) {
-        std::vector<int64_t> map_h((size_t)n0);
-        HIP_TRY(h, hipMemcpyAsync(map_h.data(), row_map, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if ((rc = tokvec_compact_prepare(h, map_h.data(), n0, data_bytes, &tvp))) return rc;
-    }
-    // every plane, chunk by chunk of destination rows through the staging buffer
-    struct plane { void* p; size_t row_bytes; };
-    std::vector<plane> planes = {{h->emb32, (size_t)h->dim * 4}, {h->emb16, (size_t)h->dim_pad * 2}, {h->ids, 8}};
-    const bool ten = h->tenants && h->cap_ten >= n0, tmp = h->temporal && h->cap_tmp >= n0, tok = h->tok && h->tok_rows == n0;
-    if (ten) planes.push_back({h->tenants, 4});
-    if (tmp) planes.push_back({h->temporal, 8});
-    if (tok) {
-        planes.push_back({h->tok, (size_t)h->tok_L * 2});
-        if (h->tok_hi) planes.push_back({h->tok_hi, (size_t)h->tok_L});      // a row of L bytes: any alignment
-        planes.push_back({h->tok_len, 4});
-    }
-    for (const plane& pl : planes) {
-        const int64_t chunk = std::max<int64_t>(1, (int64_t)(data_bytes / pl.row_bytes));
-        for (int64_t d0 = first_move; d0 < n_live; d0 += chunk) {
-            const int64_t m = std::min(chunk, n_live - d0);
-            const size_t bytes = (size_t)m * pl.row_bytes;
-#define LIVE_GATHER(W)                                                                                                       \
-    {                                                                                                                        \
-        const uint32_t rw = (uint32_t)(pl.row_bytes / sizeof(W)), total = (uint32_t)(bytes / sizeof(W));                     \
-        hipLaunchKernelGGL(live_compact_gather_kernel<W>, dim3(grid_for(total)), dim3(256), 0, st, (const W*)pl.p, rw,       \
-                           src_rows + d0, total, (W*)data);                                                                  \
-    }
-            if (pl.row_bytes % 16 == 0) LIVE_GATHER(uint4)
-            else if (pl.row_bytes % 8 == 0) LIVE_GATHER(uint2)
-            else if (pl.row_bytes % 4 == 0) LIVE_GATHER(uint32_t)
-            else if (pl.row_bytes % 2 == 0) LIVE_GATHER(uint16_t)
-            else LIVE_GATHER(uint8_t)
-#undef LIVE_GATHER
-            e = hipMemcpyAsync((char*)pl.p + (size_t)d0 * pl.row_bytes, data, bytes, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return fail(e, "row copy");
-        }
-    }
-    // the rows past the new end are tile padding of the fp16 operand again: zero
-    if (n0 > n_live) e = hipMemsetAsync(h->emb16 + (size_t)n_live * h->dim_pad, 0, (size_t)(n0 - n_live) * h->dim_pad * 2, st);
-    if (e == hipSuccess && row_map_out) e = hipMemcpyAsync(row_map_out, row_map, (size_t)n0 * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fail(e, "finish");
-    if ((rc = tokvec_compact_commit(h, &tvp, data, st))) return rc;      // (the staging buffer is free again: same stream)
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e, "finish");
-    ws.reset();
-    h->n_rows = n_live;
-    if (tok) h->tok_rows = n_live;
-    h->vis.reset();
-    h->cap_vis = 0;
-    h->n_deleted = 0;
-    if (np_sparse.p) {                       // rag_index_compact_live: renumbered with the rows, staleness left as it was
-        bm25_compact_commit(&h->sparse, np_sparse.p);
-        np_sparse.p = nullptr;
-    } else {                                 // not renumbered: a reload makes them current
-        h->sparse_stale = true;
-        h->sparse_compacted = true;
-    }
-    if (h->tv_docs_cap > 0 && !move_tv) h->tv_stale = true;      // nor are the resident token vectors, unless they moved (tokvec.hip)
-    if (np.p) {
-        bm25_compact_commit(&h->bm25, np.p);
-        np.p = nullptr;
-    } else {
-        h->bm25_stale = true;
-        h->bm25_compacted = true;
-    }
-    live_rows_changed(h);
-    if (ten) {                               // tenant tile lists of the new row numbers
-        std::vector<int32_t> t((size_t)n_live);
-        if (n_live > 0) HIP_TRY(h, hipMemcpy(t.data(), h->tenants, (size_t)n_live * 4, hipMemcpyDeviceToHost));
-        if ((rc = dense_build_tenant_tiles(h, n_live > 0 ? t.data() : nullptr, n_live))) return rc;
-        h->tenant_rows = n_live;
-    }
-    if (n_rows_out) *n_rows_out = n_live;
-    return RAG_OK;
-}
-
-int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
-    if (!h) return RAG_ERR_ARG;
-    LOCK(h);
-    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_NONE);
-}
-
-int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
-    if (!h) return RAG_ERR_ARG;
-    LOCK(h);
-    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_BM25);
-}
-
-int rag_index_compact_live(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) {
-    if (!h) return RAG_ERR_ARG;
-    LOCK(h);
-    return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_RESIDENT);
-}
+int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) { return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_NONE); }
+int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) { return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_BM25); }
+int rag_index_compact_live(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out) { return live_compact(h, row_map_out, n_rows_out, LIVE_KEEP_RESIDENT); }
 
 }  // extern "C"

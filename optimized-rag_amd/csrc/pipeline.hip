@@ -92,8 +92,10 @@ static void tokens_drop(rag_ctx* h) {
     h->tok.reset();
     h->tok_hi.reset();
     h->tok_len.reset();
-    h->tok_rows = 0; h->tok_cap = 0;
+    h->tok_rows = 0;
 }
+// a load or a reserve that fails leaves no store behind: a half-built one would read as a reservation (tok_cap_rows)
+struct tokens_pending { rag_ctx* h; bool done = false; ~tokens_pending() { if (!done) tokens_drop(h); } };
 
 // The token store is kept as uint16: 2 B per token (51 GB for 100M x 256-token passages replicated per GPU, the budget of
 // SURVEY.md section 8e; the r1 int32 store would have been 102 GB). The ABI takes int32 ids; they are narrowed on the
@@ -102,6 +104,7 @@ int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int
     ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_load: id_bits must be 16 or 24");
     ARG_CHECK(h, tokens && lens && n_rows > 0 && L > 0 && L <= 512, "tokens_load: bad arguments (passage length <= 512)");
     tokens_drop(h);
+    tokens_pending store{h};
     const int64_t total = n_rows * (int64_t)L, piece = (int64_t)64 << 20;
     int rc;
     if ((rc = h->tok.alloc(h, (size_t)total))) return rc;
@@ -122,17 +125,19 @@ int tokens_load_host(rag_ctx* h, const int32_t* tokens, const int32_t* lens, int
     ARG_CHECK(h, n_bad == 0, tokens_range_msg(h, false));
     HIP_TRY(h, hipMemcpy(h->tok_len, lens, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     h->tok_rows = n_rows;
-    h->tok_cap = n_rows;
     h->tok_L = L;
+    store.done = true;
     return RAG_OK;
 }
 
 // Chunked fill from device memory (a replicated 100M-passage store is 45 GB as uint16 and would be 90 GB as one int32 host
-// array): reserve once, append row blocks in order. tok_rows counts the rows appended so far; tok_cap the reservation.
+// array): reserve once, append row blocks in order. tok_rows counts the rows appended so far; the reservation is
+// what tok_len has room for (tok_cap_rows).
 int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits) {
     ARG_CHECK(h, id_bits == 16 || id_bits == 24, "tokens_reserve: id_bits must be 16 or 24");
     ARG_CHECK(h, n_rows > 0 && L > 0 && L <= 512, "tokens_reserve: bad arguments (passage length <= 512)");
     tokens_drop(h);
+    tokens_pending store{h};
     int rc;
     if ((rc = h->tok.alloc(h, (size_t)n_rows * L))) return rc;
     if (id_bits == 24 && (rc = h->tok_hi.alloc(h, (size_t)n_rows * L))) return rc;
@@ -142,8 +147,8 @@ int tokens_reserve(rag_ctx* h, int64_t n_rows, int L, int id_bits) {
     // first rag_tokens_append_dev counts into it on
     HIP_TRY(h, hipMemsetAsync(h->tok_bad, 0, sizeof(int), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->tok_cap = n_rows;
     h->tok_L = L;
+    store.done = true;
     return RAG_OK;
 }
 
@@ -156,8 +161,8 @@ int tokens_info(const rag_ctx* h, int64_t* rows_out, int* L_out, int* id_bits_ou
 }
 
 int tokens_append_dev(rag_ctx* h, const int32_t* tokens_dev, const int32_t* lens_dev, int64_t n, hipStream_t st) {
-    ARG_CHECK(h, h->tok_cap > 0, "tokens_append: rag_tokens_reserve first");
-    ARG_CHECK(h, n >= 0 && h->tok_rows + n <= h->tok_cap && (n == 0 || (tokens_dev && lens_dev)), "tokens_append: exceeds the reservation");
+    ARG_CHECK(h, tok_cap_rows(h) > 0, "tokens_append: rag_tokens_reserve first");
+    ARG_CHECK(h, n >= 0 && h->tok_rows + n <= tok_cap_rows(h) && (n == 0 || (tokens_dev && lens_dev)), "tokens_append: exceeds the reservation");
     if (n == 0) return RAG_OK;
     const int64_t total = n * (int64_t)h->tok_L;
     tokens_narrow(h, tokens_dev, h->tok_rows * (int64_t)h->tok_L, total, h->tok_bad, st);
@@ -415,7 +420,7 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
                         int mode, int cls_id, int sep_id, int L_pair, int64_t* ids_out, double* scores_out, float* logits_out,
                         int64_t* cand_out, hipStream_t st, query_tenants qt) {
     ARG_CHECK(h, h->ce != nullptr, "retrieve_rerank: no cross-encoder loaded");
-    ARG_CHECK(h, h->tok != nullptr && h->tok_rows == h->n_rows, "retrieve_rerank: token store missing or not row-aligned with the index");
+    ARG_CHECK(h, tokens_aligned(h, h->n_rows), "retrieve_rerank: token store missing or not row-aligned with the index");
     ARG_CHECK(h, Q > 0 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "retrieve_rerank: 0 < k <= pool <= 256");
     ARG_CHECK(h, L_pair >= 8 && L_pair <= 512 && Lq > 0 && q_emb_dev && q_tok_dev && q_len_dev && ids_out && scores_out && logits_out,
               "retrieve_rerank: bad arguments");
