@@ -434,6 +434,36 @@ int rag_sparse_append_host(rag_handle_t h, const int64_t* indptr_host /*n_terms_
                            const float* weight_host, int64_t n_docs_new, int64_t n_terms_total);
 int rag_sparse_fold(rag_handle_t h);
 int rag_sparse_segment_stats(rag_handle_t h, rag_bm25_segments* out);
+/* ---- the same append from a DOC-MAJOR block, on the device: the layout rag_lexical_compact_dev writes (doc_ptr int32
+ * [n_docs_new + 1] from 0, each document's terms strictly ascending, float32 weights finite and > 0; nnz_cap: the capacity of
+ * terms / weights). The library transposes it to the term-major block of rag_sparse_append_host on the device - a check and
+ * count pass, a scan, and a stable counting sort over the term number, 6 bits a pass, so the result is the permutation
+ * np.argsort(term * n + document, kind="stable") whatever the launch order - and only the per-term offsets (n_terms_total + 2
+ * int64) come back to the host, where every segment is planned; no posting crosses PCIe.
+ * rag_sparse_append_dev is a host WRITE that takes device memory: it waits for `stream` (the block's producer), takes the
+ * handle's lock, waits for queued *_dev calls as every *_host write does, and returns once the postings are resident and
+ * checked - the rules of rag_tokvec_append_dev. With postings resident every later result is BIT-IDENTICAL to
+ * rag_sparse_append_host called with the transposed block (and so to a fresh handle loaded with the merged CSR); coverage,
+ * staleness, vocabulary growth, option sparse_tail_fold and the automatic fold are that call's. WITHOUT sparse postings the
+ * block becomes the base: rag_sparse_load_host of its transpose with n_docs = n_docs_new. A block of empty documents is legal.
+ * RAG_ERR_ARG: n_docs_new < 1, a null array, doc_ptr[0] != 0, a decreasing offset, doc_ptr[n_docs_new] > nnz_cap (the producer
+ * cut the block at its capacity), a term outside [0, n_terms_total), terms not strictly ascending inside a document, a weight
+ * that is not finite or not > 0 (the message names the first fault and its position), a shrinking n_terms_total, a block that
+ * would cover more rows than a loaded dense index has, 2^31 rows. RAG_ERR_NOMEM when it cannot allocate. A rejected or failed
+ * call leaves postings, coverage, staleness and segment statistics exactly as they were.
+ * rag_sparse_append_docs_host takes the same block from host arrays, staged and run through the same device path.
+ * rag_sparse_clear drops the resident sparse postings (OK when there are none).
+ * rag_sparse_export_host reads the resident postings back as ONE term-major CSR - per term the base list, then the tail's,
+ * with global document numbers: indptr_out [n_terms + 1], doc_out / weight_out [nnz]. Called with the three arrays NULL it only
+ * reports n_docs, n_terms and nnz (any of them may be NULL). RAG_ERR_STATE when nothing is loaded. It is how an index built on
+ * the device is saved or re-sharded. */
+int rag_sparse_append_dev(rag_handle_t h, const int32_t* doc_ptr_dev /*n_docs_new+1*/, const int32_t* terms_dev, const float* weights_dev,
+                          int64_t n_docs_new, int64_t nnz_cap, int64_t n_terms_total, void* stream);
+int rag_sparse_append_docs_host(rag_handle_t h, const int32_t* doc_ptr_host /*n_docs_new+1*/, const int32_t* terms_host,
+                                const float* weights_host, int64_t n_docs_new, int64_t nnz_cap, int64_t n_terms_total);
+int rag_sparse_clear(rag_handle_t h);
+int rag_sparse_export_host(rag_handle_t h, int64_t* indptr_out, int32_t* doc_out, float* weight_out, int64_t* n_docs_out,
+                           int64_t* n_terms_out, int64_t* nnz_out);
 /* ---- statistics refresh: fresh idf / avgdl computed from, and written into, the RESIDENT postings. The reference builds a new
  * BM25Okapi over the corpus it has on every call (rag/retrieval.py:333-341); appends, deletes and compactions keep the
  * statistics of the last load instead, so an index that has doubled or lost a tenant ranks by numbers no rebuild would give.

@@ -119,6 +119,10 @@ _SIGS = {
     "rag_hybrid_rrf_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "rag_sparse_load_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
     "rag_sparse_append_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64], C.c_int),
+    "rag_sparse_append_dev": ([_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P], C.c_int),
+    "rag_sparse_append_docs_host": ([_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64], C.c_int),
+    "rag_sparse_clear": ([_P], C.c_int),
+    "rag_sparse_export_host": ([_P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "rag_sparse_fold": ([_P], C.c_int),
     "rag_sparse_segment_stats": ([_P, C.POINTER(Bm25Segments)], C.c_int),
     "rag_sparse_info": ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
@@ -769,6 +773,49 @@ class RagEngine:
             raise RagError("sparse_append: indptr must have n_terms_total + 1 entries and end at len(doc) == len(weight)")
         self._check(self.lib.rag_sparse_append_host(self.h, _ptr(indptr), _ptr(doc), _ptr(weight), int(n_docs_new), V),
                     "rag_sparse_append_host")
+
+    # ---- the same from a doc-major block (rag_sparse_append_dev / rag_sparse_append_docs_host), rag_sparse_clear / _export_host --
+    def sparse_append_dev(self, doc_ptr, terms, weights, n_terms_total, n_docs_new=None, stream=None):
+        """The next rows from a doc-major block in CUDA tensors - the term_ptr / terms / qweights outputs of lexical_compact_dev as
+        they are: int32 doc_ptr [n + 1] from 0, int32 terms ascending per document, float32 weights > 0 (terms and weights of one
+        capacity). Transposed and appended on the device; waits for `stream` and returns once the postings are resident and
+        checked. Without resident sparse postings the block becomes the base."""
+        import torch
+        assert doc_ptr.is_cuda and doc_ptr.dtype == torch.int32 and doc_ptr.is_contiguous()
+        assert terms.is_cuda and terms.dtype == torch.int32 and terms.is_contiguous()
+        assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous()
+        if terms.shape[0] != weights.shape[0]:
+            raise RagError("sparse_append_dev: terms and weights must have one capacity")
+        n = doc_ptr.shape[0] - 1 if n_docs_new is None else int(n_docs_new)
+        if n + 1 > doc_ptr.shape[0]:
+            raise RagError("sparse_append_dev: doc_ptr must hold n_docs_new + 1 offsets")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._check(self.lib.rag_sparse_append_dev(self.h, C.c_void_p(doc_ptr.data_ptr()), C.c_void_p(terms.data_ptr()),
+                                                   C.c_void_p(weights.data_ptr()), n, int(terms.shape[0]), int(n_terms_total), st),
+                    "rag_sparse_append_dev")
+
+    def sparse_append_docs(self, doc_ptr, terms, weights, n_terms_total):
+        """The same block from host arrays (LexicalPostings.doc_major builds them), staged and run through the device path."""
+        doc_ptr, terms, weights = _np(doc_ptr, np.int32), _np(terms, np.int32), _np(weights, np.float32)
+        if doc_ptr.ndim != 1 or doc_ptr.shape[0] < 2 or terms.ndim != 1 or terms.shape != weights.shape:
+            raise RagError("sparse_append_docs: expected doc_ptr [n + 1] and terms / weights of one length")
+        self._check(self.lib.rag_sparse_append_docs_host(self.h, _ptr(doc_ptr), _ptr(terms), _ptr(weights), doc_ptr.shape[0] - 1,
+                                                         terms.shape[0], int(n_terms_total)), "rag_sparse_append_docs_host")
+
+    def sparse_clear(self):
+        """Drop the resident sparse postings (nothing happens without any)."""
+        self._check(self.lib.rag_sparse_clear(self.h), "rag_sparse_clear")
+
+    def sparse_export(self):
+        """The resident sparse postings, base and tail merged, as one term-major CSR with global document numbers:
+        {"indptr" int64 [n_terms + 1], "doc" int32, "weight" float32, "n_docs"}."""
+        v = [C.c_int64() for _ in range(3)]
+        self._check(self.lib.rag_sparse_export_host(self.h, None, None, None, *[C.byref(x) for x in v]), "rag_sparse_export_host")
+        n_docs, n_terms, nnz = (int(x.value) for x in v)
+        indptr = np.zeros((n_terms + 1,), dtype=np.int64)
+        doc, weight = np.empty((nnz,), dtype=np.int32), np.empty((nnz,), dtype=np.float32)
+        self._check(self.lib.rag_sparse_export_host(self.h, _ptr(indptr), _ptr(doc), _ptr(weight), None, None, None), "rag_sparse_export_host")
+        return {"indptr": indptr, "doc": doc, "weight": weight, "n_docs": n_docs}
 
     def sparse_fold(self):
         """Merge the appended tail into the base sparse postings on the device (results do not change)."""

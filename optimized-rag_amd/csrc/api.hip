@@ -623,6 +623,42 @@ int rag_sparse_append_host(rag_handle_t h, const int64_t* indptr_host, const int
     return sparse_append_host(h, indptr_host, doc_host, weight_host, n_docs_new, n_terms_total);
 }
 
+// The block is device memory, the call a host write: it waits for `stream` (the block's producer), then for every queued *_dev
+// call as rag_sparse_append_host does, and builds on the handle's own stream.
+int rag_sparse_append_dev(rag_handle_t h, const int32_t* doc_ptr_dev, const int32_t* terms_dev, const float* weights_dev, int64_t n_docs_new,
+                          int64_t nnz_cap, int64_t n_terms_total, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    LOCK(h);
+    HIP_TRY(h, e);
+    HOST_ENTRY(h);
+    return sparse_append_docs_dev(h, doc_ptr_dev, terms_dev, weights_dev, n_docs_new, nnz_cap, n_terms_total);
+}
+
+int rag_sparse_append_docs_host(rag_handle_t h, const int32_t* doc_ptr_host, const int32_t* terms_host, const float* weights_host,
+                                int64_t n_docs_new, int64_t nnz_cap, int64_t n_terms_total) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_append_docs_host(h, doc_ptr_host, terms_host, weights_host, n_docs_new, nnz_cap, n_terms_total);
+}
+
+int rag_sparse_clear(rag_handle_t h) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);                      // queued *_dev searches read the postings this call frees
+    return sparse_clear(h);
+}
+
+int rag_sparse_export_host(rag_handle_t h, int64_t* indptr_out, int32_t* doc_out, float* weight_out, int64_t* n_docs_out,
+                           int64_t* n_terms_out, int64_t* nnz_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    HOST_ENTRY(h);
+    return sparse_export_host(h, indptr_out, doc_out, weight_out, n_docs_out, n_terms_out, nnz_out);
+}
+
 int rag_sparse_fold(rag_handle_t h) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);

@@ -1713,10 +1713,12 @@ static int bm_check_block(rag_ctx* h, const char* who, const rag_bm25_index* ix,
 // The new tail = old tail ++ block, built beside the old one: *out receives it on success only. `fill(b_indptr, b_doc, &b_w,
 // &b_tf16)` enqueues the block's weight plane (and, under keep_tf, its uint16 term frequencies) on the device; the buffers it
 // allocates belong to the caller and outlive this call's synchronise. idf: one value per term of V, or null (every idf 1).
+// The block's offsets and document plane are uploaded from `indptr` / `doc`, unless the caller has them on the device already
+// (indptr_dev / doc_dev, rag_sparse_append_dev): then `doc` is not read and `indptr` is the host copy the plan is made from.
 template <class W, class Fill>
 static int bm_build_tail(rag_ctx* h, const bm_builder& B, const rag_bm25_index* ix, const int64_t* indptr, const int32_t* doc,
                          const int32_t* doc_len, int64_t n_new, int64_t V, const double* idf, Fill&& fill,
-                         std::unique_ptr<rag_bm25_index>* out) {
+                         std::unique_ptr<rag_bm25_index>* out, const int64_t* indptr_dev = nullptr, const int32_t* doc_dev = nullptr) {
     constexpr bool F32 = std::is_same<W, float>::value;
     rag_bm25_index* ot = ix->tail.get();
     const bool keep = ix->keep_tf;
@@ -1736,16 +1738,22 @@ static int bm_build_tail(rag_ctx* h, const bm_builder& B, const rag_bm25_index* 
                 HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first, ot->dl + ot->first, (size_t)ix->tail_docs * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(h, hipMemcpyAsync(nt->dl + nt->first + ix->tail_docs, doc_len, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
         }
-        if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, B.what))) return rc;
-        if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, B.what))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nnz_b) HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
+        const int64_t* bi = indptr_dev;
+        const int32_t* bd = doc_dev;
+        if (bi == nullptr) {                 // a host block: its two planes go up here
+            if ((rc = bm_alloc(h, b_indptr, (size_t)V + 1, B.what))) return rc;
+            if ((rc = bm_alloc(h, b_doc, (size_t)nnz_b, B.what))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(b_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+            if (nnz_b) HIP_TRY(h, hipMemcpyAsync(b_doc, doc, (size_t)nnz_b * 4, hipMemcpyHostToDevice, st));
+            bi = b_indptr.get();
+            bd = b_doc.get();
+        }
         const W* b_w = nullptr;
         const uint16_t* b_tf16 = nullptr;
-        if ((rc = fill(b_indptr.get(), b_doc.get(), &b_w, &b_tf16))) return rc;
+        if ((rc = fill(bi, bd, &b_w, &b_tf16))) return rc;
         if (nt->nnz)
             bm_launch_1d(bm25_concat_kernel<W>, nt->nnz, st, nt->indptr_d, V, nt->nnz, ot ? ot->meta.get() : nullptr, Vo,
-                         ot ? ot->doc.get() : nullptr, ot ? bm_weights<W>(ot).get() : nullptr, b_indptr, b_doc, b_w,
+                         ot ? ot->doc.get() : nullptr, ot ? bm_weights<W>(ot).get() : nullptr, bi, bd, b_w,
                          (int32_t)(nt->first + ix->tail_docs), nt->doc, bm_weights<W>(nt.get()), ot ? ot->tf16.get() : nullptr, b_tf16,
                          nt->tf16);
         HIP_TRY(h, hipGetLastError());
@@ -2726,6 +2734,370 @@ int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, co
     std::unique_ptr<rag_bm25_index> nt;
     if (int rc = bm_build_tail<float>(h, B, ix, indptr, doc, nullptr, n_new, V, nullptr, fill, &nt)) return rc;
     bm_append_commit(h, S, std::move(nt), n_new);
+    return RAG_OK;
+}
+
+// ---- a doc-major block on the device -> the term-major block an append takes (rag_sparse_append_dev) ---------------------------
+// The block as rag_lexical_compact_dev writes it: doc_ptr int32 [n + 1] from 0, every document's terms ascending, float32 weights
+// > 0. Its transpose - per-term lists, documents ascending inside a term - is what bm_build_tail concatenates behind the old tail.
+//   1. sparse_docs_check_kernel: every fault a host append would refuse, and the per-term counts (integer atomics: any order
+//      gives the same counts). The first fault - offsets before postings, then the lowest position - goes into one 64-bit word.
+//   2. bm_scan_kernel: counts -> offsets. Offsets and the fault word come back in ONE copy (V + 2 int64); the host plans the
+//      segment from them as it does from a host block's offsets. Nothing per posting crosses PCIe.
+//   3. sparse_docs_expand_kernel: (term, document, weight) of every posting into private planes (later passes never read the
+//      caller's arrays again), then a STABLE least-significant-digit counting sort over the term number, BM_TR_BITS bits a pass:
+//      per-tile digit counts, one scan over (digit, tile), and a scatter that ranks a posting among the tile's earlier postings
+//      of its digit. The block comes in document order, so stability alone leaves every term's documents ascending: the
+//      permutation is np.argsort(term * n + document, kind="stable"), whatever the launch order. No grid depends on V and a
+//      term in every document is spread over tiles like any other.
+#define BM_TR_BITS 6
+#define BM_TR_BUCKETS (1 << BM_TR_BITS)
+#define BM_TR_TILE 2048
+#define BM_TR_THREADS 256
+#define BM_TR_WAVES (BM_TR_THREADS / 64)
+static_assert(BM_TR_BUCKETS == 64, "the scatter ranks one digit per lane of a wave");
+// digit passes that order term numbers below V
+static inline int bm_tr_passes(int64_t V) {
+    int passes = 0;
+    for (int64_t m = V - 1; m > 0; m >>= BM_TR_BITS) ++passes;
+    return passes;
+}
+
+// the fault word: class (0 an offset, 1 a posting) << 60 | position << 4 | code; the smallest wins, BM_TR_NO_FAULT: none
+#define BM_TR_NO_FAULT (~0ull)
+static const char* const bm_tr_fault_text[] = {
+    "",
+    "doc_ptr must start at 0",
+    "doc_ptr must never decrease",
+    "doc_ptr ends past nnz_cap (the block was cut at its capacity)",
+    "term outside [0, n_terms_total)",
+    "terms must be strictly ascending inside a document",
+    "weights must be finite and > 0",
+};
+
+// owner of posting p: the last document whose offset is <= p (bm_last_le's empty-list rule); in [0, n) for ANY offsets
+__device__ __forceinline__ int64_t bm_tr_doc_of(const int32_t* __restrict__ doc_ptr, int64_t n, int64_t p) {
+    return bm_last_le(n, p, [&](int64_t d) { return (int64_t)doc_ptr[d]; });
+}
+// postings the kernels may touch: doc_ptr[n] clamped to the arrays' capacity, so no read depends on the block being well formed
+__device__ __forceinline__ int64_t bm_tr_nnz(const int32_t* __restrict__ doc_ptr, int64_t n, int64_t nnz_cap) {
+    return std::min<int64_t>(std::max<int64_t>(doc_ptr[n], 0), nnz_cap);
+}
+
+// one thread per offset AND per posting slot (grid over max(n + 1, nnz_cap))
+__global__ __launch_bounds__(256) void sparse_docs_check_kernel(const int32_t* __restrict__ doc_ptr, const int32_t* __restrict__ terms,
+                                                                const float* __restrict__ weights, int64_t n, int64_t nnz_cap, int64_t V,
+                                                                uint32_t* __restrict__ count, unsigned long long* __restrict__ fault) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long bad = BM_TR_NO_FAULT;
+    if (p <= n) {
+        int code = 0;
+        if (p == 0 && doc_ptr[0] != 0) code = 1;
+        else if (p < n && doc_ptr[p + 1] < doc_ptr[p]) code = 2;
+        else if (p == n && doc_ptr[n] > nnz_cap) code = 3;
+        if (code) bad = ((unsigned long long)p << 4) | (unsigned)code;
+    }
+    if (p < bm_tr_nnz(doc_ptr, n, nnz_cap)) {
+        const int64_t d = bm_tr_doc_of(doc_ptr, n, p);
+        const int32_t t = terms[p];
+        const float w = weights[p];
+        int code = 0;
+        if (t < 0 || t >= V) code = 4;
+        else if (p > 0 && p > doc_ptr[d] && terms[p - 1] >= t) code = 5;      // (p > 0: a NEGATIVE offset may not send the look-back before the array)
+        else if (!(__builtin_isfinite(w) && w > 0.0f)) code = 6;
+        if (code) bad = std::min(bad, (1ull << 60) | ((unsigned long long)p << 4) | (unsigned)code);
+        if (code != 4) atomicAdd(&count[t], 1u);
+    }
+    if (bad != BM_TR_NO_FAULT) atomicMin(fault, bad);
+}
+
+// out[i] = count[0] + .. + count[i - 1] for i in [0, n]: ONE workgroup, a contiguous stretch per thread. Sized for what an
+// ingest brings: V counts (250,002 for bge-m3) and nnz / 32 per-(digit, tile) counts - 2,500 for a 1,000-text block, about
+// 250,000 (the size of the V scan) for the 8 M postings of 65,535 texts. Up to there the scans are small beside the passes.
+// They stay correct to the call's limit of 2^31 postings but are not built for it: 67 M counts, 268 MB, would go through one
+// workgroup three times, no longer small beside the passes; a block of that size wants a scan over many workgroups first.
+template <class O>
+__global__ __launch_bounds__(1024) void bm_scan_kernel(const uint32_t* __restrict__ count, int64_t n, O* __restrict__ out) {
+    __shared__ int64_t part[1024];
+    const int tid = threadIdx.x;
+    const int64_t per = (n + 1023) / 1024, lo = std::min<int64_t>(tid * per, n), hi = std::min<int64_t>(lo + per, n);
+    int64_t own = 0;
+    for (int64_t i = lo; i < hi; ++i) own += count[i];
+    part[tid] = own;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t below = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += below;
+        __syncthreads();
+    }
+    int64_t run = part[tid] - own;
+    for (int64_t i = lo; i < hi; ++i) {
+        out[i] = (O)run;
+        run += count[i];
+    }
+    if (tid == 1023) out[n] = (O)part[1023];
+}
+
+__global__ __launch_bounds__(256) void sparse_docs_expand_kernel(const int32_t* __restrict__ doc_ptr, const int32_t* __restrict__ terms,
+                                                                 const float* __restrict__ weights, int64_t n, int64_t nnz,
+                                                                 int32_t* __restrict__ key_out, int32_t* __restrict__ doc_out,
+                                                                 float* __restrict__ w_out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    key_out[p] = terms[p];
+    doc_out[p] = (int32_t)bm_tr_doc_of(doc_ptr, n, p);
+    w_out[p] = weights[p];
+}
+
+// digit counts of one tile of BM_TR_TILE consecutive postings, stored digit-major: tile_count[digit * n_tiles + tile]
+__global__ __launch_bounds__(BM_TR_THREADS) void bm_tr_count_kernel(const int32_t* __restrict__ key, int64_t nnz, int shift, int64_t n_tiles,
+                                                                    uint32_t* __restrict__ tile_count) {
+    __shared__ uint32_t cnt[BM_TR_BUCKETS];
+    const int tid = threadIdx.x;
+    const int64_t tile = blockIdx.x, p0 = tile * BM_TR_TILE;
+    if (tid < BM_TR_BUCKETS) cnt[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < BM_TR_TILE && p0 + i < nnz; i += BM_TR_THREADS) atomicAdd(&cnt[(key[p0 + i] >> shift) & (BM_TR_BUCKETS - 1)], 1u);
+    __syncthreads();
+    if (tid < BM_TR_BUCKETS) tile_count[(int64_t)tid * n_tiles + tile] = cnt[tid];
+}
+
+// The stable scatter of one tile. tile_off = the scan of tile_count: where the tile's first posting of each digit goes. The tile
+// is walked in rounds of one posting per thread; inside a round a posting's rank among the earlier ones of its digit is the
+// round's earlier waves' counts plus the lower lanes of its own wave with the same digit (six ballots).
+__global__ __launch_bounds__(BM_TR_THREADS) void bm_tr_scatter_kernel(const int32_t* __restrict__ key, const int32_t* __restrict__ doc,
+                                                                      const float* __restrict__ w, int64_t nnz, int shift, int64_t n_tiles,
+                                                                      const uint32_t* __restrict__ tile_off, int32_t* __restrict__ key_out,
+                                                                      int32_t* __restrict__ doc_out, float* __restrict__ w_out) {
+    __shared__ uint32_t base[BM_TR_BUCKETS];
+    __shared__ uint32_t wave_cnt[BM_TR_WAVES][BM_TR_BUCKETS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t tile = blockIdx.x, p0 = tile * BM_TR_TILE;
+    if (tid < BM_TR_BUCKETS) base[tid] = tile_off[(int64_t)tid * n_tiles + tile];
+    wave_cnt[wv][lane] = 0;
+    __syncthreads();
+    for (int r = 0; r < BM_TR_TILE / BM_TR_THREADS && p0 + r * BM_TR_THREADS < nnz; ++r) {      // (uniform bounds: every thread meets every barrier)
+        const int64_t p = p0 + r * BM_TR_THREADS + tid;
+        const bool valid = p < nnz;
+        const int32_t k = valid ? key[p] : 0;
+        const int dg = (k >> shift) & (BM_TR_BUCKETS - 1);
+        uint64_t same = __ballot(valid);
+        for (int b = 0; b < BM_TR_BITS; ++b) {
+            const bool bit = (dg >> b) & 1;
+            const uint64_t bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        const int rank = __popcll(same & ((1ull << lane) - 1ull));
+        if (valid && rank == 0) wave_cnt[wv][dg] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (valid) {
+            uint32_t o = base[dg] + (uint32_t)rank;
+            for (int x = 0; x < wv; ++x) o += wave_cnt[x][dg];
+            if ((int64_t)o < nnz) {          // always, when counts and keys agree: kept so that no input can send a store outside
+                key_out[o] = k;
+                doc_out[o] = doc[p];
+                w_out[o] = w[p];
+            }
+        }
+        __syncthreads();
+        if (tid < BM_TR_BUCKETS)
+            for (int x = 0; x < BM_TR_WAVES; ++x) {
+                base[tid] += wave_cnt[x][tid];
+                wave_cnt[x][tid] = 0;
+            }
+        __syncthreads();
+    }
+}
+
+// The transposed block on the device and what the host needs of it. The planes live as long as this object: TWO allocations,
+// the offsets (with the per-term counts behind them) before the one synchronise and the sort's planes after it.
+struct bm_term_block {
+    std::vector<int64_t> indptr_h;           // [V + 2]: the offsets, then the fault word
+    dev_buf<int64_t> indptr;                 // the same on the device, then uint32 count[V]
+    dev_buf<int32_t> planes;                 // key / doc / weight of both sides of the sort, tile_count, tile_off: 4-byte words
+    const int32_t* b_doc = nullptr;
+    const float* b_w = nullptr;
+    int64_t nnz = 0;
+};
+
+// Validates and transposes on the handle's stream; synchronises once for the offsets. RAG_ERR_ARG names the first fault.
+static int sparse_transpose_docs(rag_ctx* h, const char* who, const int32_t* doc_ptr, const int32_t* terms, const float* weights, int64_t n,
+                                 int64_t nnz_cap, int64_t V, bm_term_block& T) {
+    hipStream_t st = h->stream;
+    int rc;
+    if ((rc = bm_alloc(h, T.indptr, (size_t)V + 2 + ((size_t)V + 1) / 2, who))) return rc;
+    uint32_t* count = reinterpret_cast<uint32_t*>(T.indptr + V + 2);
+    try {
+        T.indptr_h.resize((size_t)V + 2);
+    } catch (const std::bad_alloc&) {
+        h->err = std::string(who) + ": out of host memory";
+        return RAG_ERR_NOMEM;
+    }
+    HIP_TRY(h, hipMemsetAsync(count, 0, (size_t)V * sizeof(uint32_t), st));
+    HIP_TRY(h, hipMemsetAsync(T.indptr + V + 1, 0xff, sizeof(int64_t), st));
+    bm_launch_1d(sparse_docs_check_kernel, std::max(n + 1, nnz_cap), st, doc_ptr, terms, weights, n, nnz_cap, V, count,
+                 reinterpret_cast<unsigned long long*>(T.indptr + V + 1));
+    hipLaunchKernelGGL(bm_scan_kernel<int64_t>, dim3(1), dim3(1024), 0, st, count, V, T.indptr.get());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(T.indptr_h.data(), T.indptr, (size_t)(V + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const unsigned long long fault = (unsigned long long)T.indptr_h[(size_t)V + 1];
+    if (fault != BM_TR_NO_FAULT) {
+        const int code = (int)(fault & 15);
+        const long long pos = (long long)((fault >> 4) & 0xffffffffffull);
+        ARG_CHECK(h, false, std::string(who) + ": " + bm_tr_fault_text[code] + " (" + ((fault >> 60) ? "posting " : "document ") + std::to_string(pos) + ")");
+    }
+    const int64_t nnz = T.nnz = T.indptr_h[(size_t)V];
+    const int passes = nnz ? bm_tr_passes(V) : 0;                    // (a block of empty documents sorts nothing)
+    const int64_t n_tiles = (nnz + BM_TR_TILE - 1) / BM_TR_TILE, n_cnt = n_tiles * BM_TR_BUCKETS;
+    // one plane set when no pass runs, two to sort between; the tile tables behind them
+    if ((rc = bm_alloc(h, T.planes, (size_t)(3 * nnz * (passes ? 2 : 1) + (passes ? 2 * n_cnt + 1 : 0)), who))) return rc;
+    int32_t* key[2] = {T.planes.get(), T.planes + 3 * nnz};
+    int32_t* docp[2] = {key[0] + nnz, key[1] + nnz};
+    float* wp[2] = {reinterpret_cast<float*>(key[0] + 2 * nnz), reinterpret_cast<float*>(key[1] + 2 * nnz)};
+    uint32_t* tile_count = reinterpret_cast<uint32_t*>(T.planes + 6 * nnz);
+    uint32_t* tile_off = tile_count + n_cnt;
+    int cur = 0;
+    if (nnz) {
+        bm_launch_1d(sparse_docs_expand_kernel, nnz, st, doc_ptr, terms, weights, n, nnz, key[0], docp[0], wp[0]);
+        for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
+            const int shift = pass * BM_TR_BITS;
+            hipLaunchKernelGGL(bm_tr_count_kernel, dim3((unsigned)n_tiles), dim3(BM_TR_THREADS), 0, st, key[cur], nnz, shift, n_tiles, tile_count);
+            hipLaunchKernelGGL(bm_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, tile_count, n_cnt, tile_off);
+            hipLaunchKernelGGL(bm_tr_scatter_kernel, dim3((unsigned)n_tiles), dim3(BM_TR_THREADS), 0, st, key[cur], docp[cur], wp[cur], nnz, shift,
+                               n_tiles, tile_off, key[cur ^ 1], docp[cur ^ 1], wp[cur ^ 1]);
+        }
+        HIP_TRY(h, hipGetLastError());
+    }
+    T.b_doc = docp[cur];
+    T.b_w = wp[cur];
+    return RAG_OK;
+}
+
+// rag_sparse_append_dev: the next n rows from a doc-major device block. With postings resident it is sparse_append_host of the
+// transposed block (the same bm_build_tail, the block's planes already on the device); without, the block becomes the base as
+// sparse_load_host builds it. Nothing resident is touched before everything has been built.
+int sparse_append_docs_dev(rag_ctx* h, const int32_t* doc_ptr, const int32_t* terms, const float* weights, int64_t n, int64_t nnz_cap,
+                           int64_t n_terms_total) {
+    const bm_slot S = bm_slot_sparse(h);
+    rag_bm25_index* ix = h->sparse;
+    const std::string w = std::string(S.append_name) + ": ";
+    const int64_t V = n_terms_total, known = ix ? bm_known_terms(ix) : 0, covered = ix ? bm_total_docs(ix) : 0;
+    ARG_CHECK(h, n >= 1 && covered + n < 0x7fffffff, w + "n_docs_new must be >= 1 (and the index stay under 2^31 documents)");
+    ARG_CHECK(h, V >= 1 && V >= known && V < 0x7fffffff, w + "n_terms_total may not shrink");
+    ARG_CHECK(h, nnz_cap >= 0 && nnz_cap <= 0x7fffffff, w + "nnz_cap must lie in [0, 2^31)");
+    ARG_CHECK(h, doc_ptr && (nnz_cap == 0 || (terms && weights)), w + "null pointer");
+    ARG_CHECK(h, !h->index_loaded || covered + n <= h->n_rows, w + "the block would cover more rows than the index has");
+    const bm_builder B = {h, S.append_name, true};
+    bm_term_block T;
+    if (int rc = sparse_transpose_docs(h, B.what, doc_ptr, terms, weights, n, nnz_cap, V, T)) {
+        (void)hipStreamSynchronize(h->stream);          // T's planes are freed on return
+        return rc;
+    }
+    if (ix != nullptr) {
+        auto fill = [&](const int64_t*, const int32_t*, const float** w_out, const uint16_t** tf16_out) -> int {
+            *w_out = T.b_w;
+            *tf16_out = nullptr;
+            return RAG_OK;
+        };
+        std::unique_ptr<rag_bm25_index> nt;
+        if (int rc = bm_build_tail<float>(h, B, ix, T.indptr_h.data(), nullptr, nullptr, n, V, nullptr, fill, &nt, T.indptr.get(), T.b_doc)) return rc;
+        bm_append_commit(h, S, std::move(nt), n);
+        return RAG_OK;
+    }
+    std::unique_ptr<rag_bm25_index> nb = bm_new_segment(nullptr, 0, n, V);
+    nb->indptr_h.assign(T.indptr_h.begin(), T.indptr_h.begin() + V + 1);
+    nb->normalize = 0;
+    std::vector<bm_term_meta> meta_h;
+    bm_plan_segment(nb.get(), nullptr, meta_h);
+    hipStream_t st = h->stream;
+    auto enqueue = [&]() -> int {
+        if (int rc = bm_prepare_segment(B, nb.get(), meta_h, {false, false, false, false, false, true})) return rc;
+        if (T.nnz) HIP_TRY(h, hipMemcpyAsync(nb->doc, T.b_doc, (size_t)T.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (T.nnz) HIP_TRY(h, hipMemcpyAsync(nb->wf, T.b_w, (size_t)T.nnz * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return RAG_OK;
+    };
+    if (int rc = bm_finish_segment(B, nb.get(), enqueue())) return rc;
+    h->sparse = nb.release();
+    h->sparse_stale = false;
+    h->sparse_compacted = false;
+    return RAG_OK;
+}
+
+// ... and from host arrays of the same layout (rag_sparse_append_docs_host): staged, then the device path
+int sparse_append_docs_host(rag_ctx* h, const int32_t* doc_ptr, const int32_t* terms, const float* weights, int64_t n, int64_t nnz_cap,
+                            int64_t n_terms_total) {
+    const bm_slot S = bm_slot_sparse(h);
+    const std::string w = std::string(S.append_name) + ": ";
+    ARG_CHECK(h, n >= 1 && n < 0x7fffffff, w + "n_docs_new must be >= 1 (and the index stay under 2^31 documents)");
+    ARG_CHECK(h, nnz_cap >= 0 && nnz_cap <= 0x7fffffff, w + "nnz_cap must lie in [0, 2^31)");
+    ARG_CHECK(h, doc_ptr && (nnz_cap == 0 || (terms && weights)), w + "null pointer");
+    const int64_t used = std::min<int64_t>(std::max<int64_t>(doc_ptr[n], 0), nnz_cap);      // what the kernels may read
+    dev_buf<int32_t> ptr_d, terms_d;
+    dev_buf<float> w_d;
+    int rc;
+    if ((rc = bm_alloc(h, ptr_d, (size_t)n + 1, S.append_name))) return rc;
+    if ((rc = bm_alloc(h, terms_d, (size_t)used, S.append_name))) return rc;
+    if ((rc = bm_alloc(h, w_d, (size_t)used, S.append_name))) return rc;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(ptr_d, doc_ptr, (size_t)(n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (used) HIP_TRY(h, hipMemcpyAsync(terms_d, terms, (size_t)used * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (used) HIP_TRY(h, hipMemcpyAsync(w_d, weights, (size_t)used * sizeof(float), hipMemcpyHostToDevice, st));
+    rc = sparse_append_docs_dev(h, ptr_d, terms_d, w_d, n, nnz_cap, n_terms_total);
+    (void)hipStreamSynchronize(st);                     // the staged copies read the caller's arrays
+    return rc;
+}
+
+// rag_sparse_clear
+int sparse_clear(rag_ctx* h) {
+    sparse_free(h);
+    h->sparse_stale = false;
+    h->sparse_compacted = false;
+    return RAG_OK;
+}
+
+// rag_sparse_export_host: base and tail as ONE term-major CSR with global document numbers - each term's base list, then its
+// tail list (the order of a fold, and of LexicalPostings.extend). Null arrays: the sizes only.
+int sparse_export_host(rag_ctx* h, int64_t* indptr_out, int32_t* doc_out, float* weight_out, int64_t* n_docs_out, int64_t* n_terms_out,
+                       int64_t* nnz_out) {
+    const rag_bm25_index* ix = h->sparse;
+    if (ix == nullptr) {
+        h->err = "sparse_export: no sparse postings loaded";
+        return RAG_ERR_STATE;
+    }
+    const rag_bm25_index* tl = ix->tail.get();
+    const int64_t V = bm_known_terms(ix), nnz = ix->nnz + (tl ? tl->nnz : 0);
+    if (n_docs_out) *n_docs_out = bm_total_docs(ix);
+    if (n_terms_out) *n_terms_out = V;
+    if (nnz_out) *nnz_out = nnz;
+    if (indptr_out == nullptr && doc_out == nullptr && weight_out == nullptr) return RAG_OK;
+    ARG_CHECK(h, indptr_out && (nnz == 0 || (doc_out && weight_out)), "sparse_export: null output");
+    const std::vector<int64_t> merged = bm_merged_offsets(ix->indptr_h.data(), ix->n_terms, tl ? tl->indptr_h.data() : nullptr, tl ? tl->n_terms : 0, V);
+    std::copy(merged.begin(), merged.end(), indptr_out);
+    if (tl == nullptr) {
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(doc_out, ix->doc, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (nnz) HIP_TRY(h, hipMemcpyAsync(weight_out, ix->wf, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return RAG_OK;
+    }
+    std::vector<int32_t> bd((size_t)ix->nnz), td((size_t)tl->nnz);
+    std::vector<float> bw((size_t)ix->nnz), tw((size_t)tl->nnz);
+    if (ix->nnz) HIP_TRY(h, hipMemcpyAsync(bd.data(), ix->doc, bd.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (ix->nnz) HIP_TRY(h, hipMemcpyAsync(bw.data(), ix->wf, bw.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (tl->nnz) HIP_TRY(h, hipMemcpyAsync(td.data(), tl->doc, td.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (tl->nnz) HIP_TRY(h, hipMemcpyAsync(tw.data(), tl->wf, tw.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t t = 0; t < V; ++t) {
+        int64_t o = merged[(size_t)t];
+        if (t < ix->n_terms)
+            for (int64_t p = ix->indptr_h[(size_t)t]; p < ix->indptr_h[(size_t)t + 1]; ++p, ++o) { doc_out[o] = bd[(size_t)p]; weight_out[o] = bw[(size_t)p]; }
+        if (t < tl->n_terms)
+            for (int64_t p = tl->indptr_h[(size_t)t]; p < tl->indptr_h[(size_t)t + 1]; ++p, ++o) {
+                doc_out[o] = td[(size_t)p] + (int32_t)tl->row0;
+                weight_out[o] = tw[(size_t)p];
+            }
+    }
     return RAG_OK;
 }
 

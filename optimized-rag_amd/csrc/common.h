@@ -520,6 +520,13 @@ int bm25_scores_adhoc_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc
 // ... and the learned-sparse postings (h->sparse)
 int sparse_load_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_docs, int64_t n_terms);
 int sparse_append_host(rag_ctx* h, const int64_t* indptr, const int32_t* doc, const float* weight, int64_t n_new, int64_t n_terms_total);
+int sparse_append_docs_dev(rag_ctx* h, const int32_t* doc_ptr, const int32_t* terms, const float* weights, int64_t n, int64_t nnz_cap,
+                           int64_t n_terms_total);
+int sparse_append_docs_host(rag_ctx* h, const int32_t* doc_ptr, const int32_t* terms, const float* weights, int64_t n, int64_t nnz_cap,
+                            int64_t n_terms_total);
+int sparse_clear(rag_ctx* h);
+int sparse_export_host(rag_ctx* h, int64_t* indptr_out, int32_t* doc_out, float* weight_out, int64_t* n_docs_out, int64_t* n_terms_out,
+                       int64_t* nnz_out);
 int sparse_fold(rag_ctx* h);
 void sparse_free(rag_ctx* h);
 int sparse_info(const rag_ctx* h, int64_t* n_docs_out, int64_t* n_terms_out, int64_t* nnz_out, int64_t* hbm_bytes_out);

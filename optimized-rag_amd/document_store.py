@@ -148,12 +148,14 @@ class GpuDocumentIndex:
         appended to them (rag_sparse_append_host) and search_lexical stays live. token_vectors: (vecs float32 [rows, tok_dim],
         offsets int64 [n + 1]), host arrays or CUDA tensors; when a token-vector store is resident the documents are appended to
         it (its reservation must have the headroom). Both happen under the same lock as the insert: a search sees all legs of
-        the new rows or none. Without the arguments the behaviour is unchanged: the resident legs go stale / fall behind."""
+        the new rows or none. Without the arguments the behaviour is unchanged: the resident legs go stale / fall behind.
+        Postings built on the device (build_lexical) have no host mirror: the maps then go as one doc-major block through
+        rag_sparse_append_docs_host (LexicalPostings.doc_major; checked before anything is written, like the mirror's block)."""
         emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.dim)
         assert emb.shape[0] == len(rows)
         if not rows:
             return []
-        lex_block = None
+        lex_append = None
         if lexical_weights is not None and self._lexical is not None:
             from .sparse import LexicalPostings
             if len(lexical_weights) != len(rows):
@@ -161,7 +163,18 @@ class GpuDocumentIndex:
             if self._lexical.n_docs != len(self.rows):
                 raise ValueError("add_rows: the lexical postings do not cover the current rows (load_lexical again)")
             top = max((int(k) for m in lexical_weights for k in m), default=-1)
-            lex_block = LexicalPostings.from_weights(lexical_weights, max(self._lexical.n_terms, top + 1))     # checked before anything is written
+            lex_terms = max(self._lexical.n_terms, top + 1)
+            if self._resident_lexical():                             # either way the block is checked before anything is written
+                lex_block = LexicalPostings.doc_major(lexical_weights, lex_terms)
+                lex_append = lambda: (self.engine.sparse_append_docs(*lex_block, lex_terms), self._lexical.appended(len(rows), lex_terms))
+            else:
+                lex_block = LexicalPostings.from_weights(lexical_weights, lex_terms)
+                lex_append = lambda: self._lexical.append_to(self.engine, self._lexical.extend(lex_block))
+        return self._insert_rows(rows, emb, lex_append, token_vectors)
+
+    def _insert_rows(self, rows, emb, lex_append, token_vectors) -> List[int]:
+        """add_rows behind its checks of the lexical block (the caller holds the lock): the row insert, then the sparse leg
+        (lex_append, or None), then the token vectors, then the payload rows."""
         store = token_vectors is not None and self.engine.tokvec_info()["dim"] > 0
         if store and self.engine.tokvec_info()["n_docs"] != len(self.rows):
             raise ValueError("add_rows: the token-vector store does not cover the current rows")
@@ -172,8 +185,8 @@ class GpuDocumentIndex:
             self._next_id = max(self._next_id, int(ids[i]) + 1)
             ten[i] = self._tenant_id.setdefault(str(r.get("agent_id", "")), len(self._tenant_id))
         self.engine.index_insert(emb, ids=ids, tenants=ten)
-        if lex_block is not None:
-            self._lexical.append_to(self.engine, self._lexical.extend(lex_block))
+        if lex_append is not None:
+            lex_append()
         if store:
             vecs, offsets = token_vectors
             if hasattr(vecs, "is_cuda"):
@@ -189,6 +202,11 @@ class GpuDocumentIndex:
             if r.get("document_id") is not None:
                 self._doc_chunks.setdefault((str(r.get("agent_id", "")), int(r["document_id"])), []).append(int(ids[i]))
         return [int(v) for v in ids]
+
+    def _resident_lexical(self) -> bool:
+        """the lexical postings were built on the device (build_lexical): a ResidentLexical stands in for the host mirror"""
+        from .sparse import ResidentLexical
+        return isinstance(self._lexical, ResidentLexical)
 
     def _delete_ids(self, agent_id, ids) -> int:
         t = self._tenant_id.get(str(agent_id))
@@ -262,7 +280,11 @@ class GpuDocumentIndex:
         """Embed `texts` and add them as rows of `agent_id`: ONE forward per batch gives all three heads of the embedding
         service - the dense vector, the lexical weights (when lexical postings are resident) and the token vectors (when a
         token-vector store is resident), which go from the forward's output tensor into the store and never exist on the host, as
-        in build_token_vectors. Each batch goes through add_rows. Returns the ids."""
+        in build_token_vectors. Each batch goes through add_rows. Returns the ids.
+        Over postings built on the device (build_lexical) the sparse leg stays there too: the outputs of rag_lexical_compact_dev go
+        straight into rag_sparse_append_dev after the row insert, under the same lock, and no weight reaches the host. A block the
+        library rejects (a token id at or past the postings' n_terms) then leaves the rows inserted and the postings stale - as
+        a rejected block of the token-vector leg does - where the mirror route refuses before the insert."""
         import torch
         svc = self.embeddings
         texts = [str(t) for t in texts]
@@ -285,25 +307,37 @@ class GpuDocumentIndex:
                 off = torch.empty((n + 1,), dtype=torch.int64, device="cuda")
             d_ids, d_lens = torch.from_numpy(ids).cuda(), torch.from_numpy(lens).cuda()
             svc.engine.embed_multi_dev(d_ids, torch.from_numpy(tt).cuda(), d_lens, dense=dense, lex=lex, tok=tok, row_off=off)
-            maps = None
+            maps = lex_dev = None
             if want_lex:                                             # the largest weight > 0 of each token id, special tokens left out (encode_multi):
                 ptr = torch.empty((n + 1,), dtype=torch.int32, device="cuda")                 # reduced on the device (rag_lexical_compact_dev)
                 terms = torch.empty((n * L,), dtype=torch.int32, device="cuda")
                 qw = torch.empty((n * L,), dtype=torch.float32, device="cuda")
                 svc.engine.lexical_compact_dev(d_ids, lex, d_lens, ptr, terms, qw, skip_ids=skip)
-                ptr, terms, qw = self._to_host(ptr, terms, qw)
-                maps = [dict(zip(terms[a:b].tolist(), qw[a:b].tolist())) for a, b in zip(ptr[:-1], ptr[1:])]
+                if self._resident_lexical():
+                    lex_dev = (ptr, terms, qw)
+                else:
+                    ptr, terms, qw = self._to_host(ptr, terms, qw)
+                    maps = [dict(zip(terms[a:b].tolist(), qw[a:b].tolist())) for a, b in zip(ptr[:-1], ptr[1:])]
             torch.cuda.synchronize()
             rows_ = [{"agent_id": agent_id, "content": t, "metadata": dict(metadata or {}),
                       **({"document_id": int(document_id)} if document_id is not None else {})} for t in part]
-            ids_out += self.add_rows(rows_, dense.cpu().numpy(), lexical_weights=maps, token_vectors=(tok, off) if want_tok else None)
+            tv = (tok, off) if want_tok else None
+            if lex_dev is None:
+                ids_out += self.add_rows(rows_, dense.cpu().numpy(), lexical_weights=maps, token_vectors=tv)
+            else:                                                    # device-built postings: the compaction's outputs as they are
+                if self._lexical.n_docs != len(self.rows):
+                    raise ValueError("add_texts: the lexical postings do not cover the current rows (build_lexical again)")
+                res = self._lexical
+                dev_append = lambda: (self.engine.sparse_append_dev(*lex_dev, res.n_terms, n_docs_new=n), res.appended(n, res.n_terms))
+                ids_out += self._insert_rows(rows_, dense.cpu().numpy().reshape(-1, self.dim), dev_append, tv)
         return ids_out
 
     @_locked
     def compact(self, keep_resident: bool = False) -> np.ndarray:
         """Drop deleted rows from HBM (rag_index_compact) and remap the payload rows; returns row_map[old row]. keep_resident
         (rag_index_compact_live): resident lexical postings and token vectors move with the rows and stay searchable, and the
-        held lexical mirror is remapped; by default both end stale until they are loaded again."""
+        held lexical mirror (or the stand-in of device-built postings) is remapped; by default both end stale until they are
+        loaded again."""
         row_map = self.engine.index_compact(keep_resident=True) if keep_resident else self.engine.index_compact()
         if self._lexical is not None:
             if keep_resident and self._lexical.n_docs == len(row_map):
@@ -386,6 +420,50 @@ class GpuDocumentIndex:
             raise ValueError(f"load_lexical: postings of {postings.n_docs} documents for an index of {len(self.rows)} rows")
         postings.load(self.engine)
         self._lexical = postings                       # the mirror grows and shrinks with add_rows(lexical_weights=...) / compact(keep_resident=True)
+
+    @_locked
+    def build_lexical(self, texts, batch: int = 64, n_terms: Optional[int] = None) -> None:
+        """The counterpart of build_token_vectors for the lexical leg: compute the lexical weights of the rows' texts (texts[i]
+        belongs to row i) and build the resident postings from them on the device, `batch` texts at a time - one forward with the
+        lexical head, rag_lexical_compact_dev, rag_sparse_append_dev. No weight reaches the host and no host mirror is kept: a
+        sparse.ResidentLexical holds the counts live writes are checked against (its `export` reads the postings back).
+        Replaces any resident postings. n_terms defaults to the model's vocabulary size. Results equal load_lexical of
+        LexicalPostings.from_texts over the same texts."""
+        import torch
+        from .sparse import ResidentLexical
+        svc = self.embeddings
+        texts = [str(t) for t in texts]
+        if len(texts) != len(self.rows):
+            raise ValueError(f"build_lexical: {len(texts)} texts for an index of {len(self.rows)} rows")
+        if not texts:
+            raise ValueError("build_lexical: the index holds no rows")
+        svc._need_heads(True, False)
+        if n_terms is None:
+            n_terms = getattr(svc, "cfg", {}).get("vocab_size")
+        if n_terms is None or int(n_terms) < 1:
+            raise ValueError("build_lexical: n_terms is needed (the service names no vocabulary size)")
+        skip = svc.special_ids()
+        batch = max(1, int(batch))
+        self.engine.sparse_clear()
+        self._lexical = None
+        for b in range(0, len(texts), batch):
+            ids, tt, lens = svc.tokenize(texts[b:b + batch])
+            n, L = ids.shape
+            d_ids, d_lens = torch.from_numpy(ids).cuda(), torch.from_numpy(lens).cuda()
+            lex = torch.empty((n, L), dtype=torch.float32, device="cuda")
+            svc.engine.embed_multi_dev(d_ids, torch.from_numpy(tt).cuda(), d_lens, lex=lex)
+            ptr = torch.empty((n + 1,), dtype=torch.int32, device="cuda")
+            terms = torch.empty((n * L,), dtype=torch.int32, device="cuda")
+            qw = torch.empty((n * L,), dtype=torch.float32, device="cuda")
+            svc.engine.lexical_compact_dev(d_ids, lex, d_lens, ptr, terms, qw, skip_ids=skip)
+            self.engine.sparse_append_dev(ptr, terms, qw, int(n_terms))        # waits for the stream: resident and checked on return
+        self._lexical = ResidentLexical(len(texts), int(n_terms))
+
+    @_locked
+    def export_lexical(self):
+        """The lexical postings of the rows as a sparse.LexicalPostings: the held mirror (load_lexical), or the resident postings
+        read back (build_lexical; rag_sparse_export_host) - to save them or to `shard` them. None when there are none."""
+        return self._lexical.export(self.engine) if self._resident_lexical() else self._lexical
 
     def search_lexical(self, agent_id: str, query: str, top_k: int = 5, mode: str = "dense+sparse", pool: int = 100,
                        rrf_k: int = 60) -> List[Dict[str, Any]]:

@@ -63,6 +63,33 @@ class LexicalPostings:
         np.cumsum(np.bincount(tok, minlength=V), out=indptr[1:])
         return cls(indptr, (key % n).astype(np.int32), np.ascontiguousarray(w[order]), n)
 
+    @staticmethod
+    def doc_major(maps, n_terms=None):
+        """The same maps as a DOC-MAJOR block: (ptr int32 [n + 1] from 0, terms int32 ascending inside a document, weights
+        float32) - the layout rag_lexical_compact_dev writes and `RagEngine.sparse_append_docs` takes. from_weights' rules: an
+        entry whose float32 weight is not > 0 is left out, a weight that is not finite or a token id outside [0, n_terms) raises
+        ValueError, as does a token id that occurs twice in one map. n_terms defaults to the largest token id + 1."""
+        n = len(maps)
+        if n < 1:
+            raise ValueError("doc_major: at least one document")
+        owner, tok, w = _flatten(maps)
+        if not np.isfinite(w).all():
+            raise ValueError("doc_major: non-finite weight")
+        keep = w > 0
+        owner, tok, w = owner[keep], tok[keep], w[keep]
+        V = int(n_terms) if n_terms is not None else (int(tok.max()) + 1 if tok.size else 1)
+        if V < 1 or (tok.size and (int(tok.min()) < 0 or int(tok.max()) >= V)):
+            raise ValueError(f"doc_major: token ids must lie in [0, {V})")
+        order = np.lexsort((tok, owner))                   # document-major, terms ascending
+        key = (owner * V + tok)[order]
+        if key.size > 1 and not (np.diff(key) > 0).all():
+            raise ValueError("doc_major: a token id occurs twice in one document's map")
+        if key.size >= 2**31:
+            raise ValueError("doc_major: the block's offsets must fit int32")
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(owner, minlength=n), out=ptr[1:])
+        return ptr.astype(np.int32), tok[order].astype(np.int32), np.ascontiguousarray(w[order])
+
     @classmethod
     def from_texts(cls, service, texts, batch=256, n_terms=None):
         """Lexical weights of `texts` from the service's lexical head (`encode_multi`, `batch` texts per call), then from_weights.
@@ -164,3 +191,38 @@ class LexicalPostings:
         self.weight = np.ascontiguousarray(self.weight[keep])
         self._n_docs = n_live
         return self
+
+
+class ResidentLexical:
+    """Stand-in for the LexicalPostings mirror of an index whose postings were built on the device
+    (GpuDocumentIndex.build_lexical): it holds the two counts live writes are checked against - documents covered and terms
+    known - and no posting. `export` reads the postings back when a host copy is wanted (to save them, or to `shard` them)."""
+
+    def __init__(self, n_docs, n_terms):
+        self.n_docs, self.n_terms = int(n_docs), int(n_terms)
+
+    def appended(self, n_docs_new, n_terms_total):
+        """Counts after a block of n_docs_new documents over n_terms_total terms was appended on the device. Returns self."""
+        if int(n_terms_total) < self.n_terms:
+            raise ValueError(f"appended: n_terms may not shrink ({int(n_terms_total)} < {self.n_terms})")
+        self.n_docs += int(n_docs_new)
+        self.n_terms = int(n_terms_total)
+        return self
+
+    def compacted(self, row_map):
+        """The counts after `RagEngine.index_compact(keep_resident=True)`: LexicalPostings.compacted's checks of the row map,
+        then n_docs = the live rows; term numbers stay. Returns self."""
+        row_map = np.asarray(row_map, dtype=np.int64)
+        if row_map.shape != (self.n_docs,):
+            raise ValueError(f"compacted: row_map must have one entry per document ({self.n_docs}), got shape {row_map.shape}")
+        live = row_map >= 0
+        n_live = int(live.sum())
+        if not np.array_equal(row_map[live], np.arange(n_live, dtype=np.int64)):
+            raise ValueError("compacted: the live entries of row_map must be 0 .. n_live-1 in ascending order")
+        self.n_docs = n_live
+        return self
+
+    def export(self, engine):
+        """The resident postings as a LexicalPostings (rag_sparse_export_host): base and tail merged per term."""
+        e = engine.sparse_export()
+        return LexicalPostings(e["indptr"], e["doc"], e["weight"], e["n_docs"])
