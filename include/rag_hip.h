@@ -1007,6 +1007,54 @@ int rag_m3_combine_gathered_dev(rag_handle_t h, const int64_t* cand_ids_dev, con
                                 int slots, int k, double w_dense, double w_sparse, double w_colbert, int64_t* ids_out_dev,
                                 double* scores_out_dev, double* components_out_dev /*may be NULL*/, void* stream);
 
+/* ---- rag_hybrid_linear_dev over ROW SHARDS (linear fusion over ROW SHARDS; DESIGN.md section 5, sharded.py
+ *      ShardedHybridIndex.search_linear). Every rank holds a contiguous row range loaded with id_base = its first global row, the
+ *      doc-partitioned postings of its rows (global idf / avgdl) and its slice of the temporal vector; the query arrays are
+ *      replicated. With the maximum of the raw BM25 scores over EVERY rank's rows, a row's hybrid score depends on the query, the
+ *      row and that maximum only, so the one-call entry is cut at the point where the maximum is known:
+ *        rag_hybrid_linear_begin_dev  ->  gather 1: [world][Q] float64 maxima  ->  rag_hybrid_linear_finish_dev  ->
+ *        gather 2: [world][5][Q][k] int64 blocks  ->  rag_hybrid_linear_merge_gathered_dev.
+ * rag_hybrid_linear_batch: *max_queries_out = the query sub-batch rag_hybrid_linear_dev uses for the index as it stands,
+ *   min(256, 8 GiB / (12 * rows)), at least 16. One begin / finish pair takes at most this many queries (the all-document score
+ *   planes of one sub-batch are what the handle keeps between the two calls); ranks with different row counts agree on the
+ *   smallest. Host state only: it waits for nothing.
+ * rag_hybrid_linear_begin_dev: the first half of rag_hybrid_linear_dev for n_queries <= that limit (above it RAG_ERR_ARG, the
+ *   message names the limit): one scoring pass writes every document's raw BM25 score into the handle's workspace and
+ *   local_max_out_dev [n_queries] float64 = the largest raw score over this handle's visible documents of the query's tenant
+ *   (deleted rows and other tenants' rows do not count), -inf when there is no such document. The handle keeps the score planes
+ *   and the queries' token counts, and remembers n_queries, the row count and the tenant argument: it is "begun".
+ * rag_hybrid_linear_finish_dev: gathered_max_dev [world][n_queries] float64, every rank's local maxima. Per query the maximum of
+ *   the FINITE entries is the corpus maximum; with none (no document anywhere) the divisor is 1.0, as it is for a corpus maximum
+ *   <= 0. Then the second half of rag_hybrid_linear_dev with that divisor: partial_out_dev [5][n_queries][k] int64 = ids | hybrid |
+ *   semantic | keyword | temporal, the four score planes float64 bits, padded -1 / 0.0. world = 1 with the handle's own maxima
+ *   gives the bits of rag_hybrid_linear_dev. The call consumes the begun state, whatever it returns. RAG_ERR_STATE: no begin
+ *   before it; n_queries or the tenant argument (scalar against array, or other numbers) differ from the begin's; or the planes
+ *   are gone - any *_host call on the handle in between (every write to the index or the postings is one, the live writes
+ *   included), a device-pointer index load or append, or rag_hybrid_linear_dev / _tenants_dev, which reuse the workspace.
+ *   Other *_dev calls may come in between.
+ * Both: argument checks are rag_hybrid_linear_dev's (alpha > 0, finite weights, 0 < k <= 256, fresh row-aligned postings, a
+ *   loaded tenant table for a tenant >= 0); RAG_ERR_STATE on an index with explicit ids, as rag_m3_score_ids_dev: the order
+ *   across shards is defined through id_base. The handle stays usable after every error.
+ * rag_hybrid_linear_merge_gathered_dev: gathered_dev [world][5][n_queries][k] int64, every rank's partial_out. The global top-k
+ *   by (hybrid desc, id asc), -1 slots skipped wherever they stand, each winner's three components copied with it; outputs
+ *   [n_queries][k], padded -1 / 0.0; semantic / keyword / temporal_out_dev may be NULL. Needs no index. world * k <= 4092 (the
+ *   merge kernel's LDS), else RAG_ERR_ARG.
+ * Bit-identical (ids, hybrid and component bits) to rag_hybrid_linear_dev on the unsharded index loaded with id_base = 0, the
+ *   merged postings and the whole temporal vector: the raw scores are per-document sums over the query's terms under global
+ *   statistics, the maximum of the ranks' maxima is the corpus maximum, every other operand is per row, and the order (hybrid
+ *   desc, id asc) is total, so the merge of the ranks' top-k lists is the top-k of the union.
+ * The _tenants_ forms take tenants_host [n_queries] as the other per-query-tenant entries do. All follow the preamble's ordering
+ *   rules; workspaces are handle-owned. */
+int rag_hybrid_linear_batch(rag_handle_t h, int* max_queries_out);
+int rag_hybrid_linear_begin_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int n_queries, int tenant,
+                                double* local_max_out_dev, void* stream);
+int rag_hybrid_linear_finish_dev(rag_handle_t h, const float* q_dev, const double* gathered_max_dev, int world, int n_queries, int k,
+                                 double alpha, double beta, double gamma, int tenant, int64_t* partial_out_dev, void* stream);
+int rag_hybrid_linear_merge_gathered_dev(rag_handle_t h, const int64_t* gathered_dev, int world, int n_queries, int k,
+                                         int64_t* ids_out_dev, double* hybrid_out_dev, double* semantic_out_dev /*may be NULL*/,
+                                         double* keyword_out_dev /*may be NULL*/, double* temporal_out_dev /*may be NULL*/,
+                                         void* stream);
+
 /* ---- agents mixed in one batch: a tenant PER QUERY. Each entry takes the arguments of its namesake with
  *      `const int32_t* tenants_host` [n_queries] where the namesake has `int tenant`: query i is filtered by tenants_host[i],
  *      a value < 0 leaves that query unfiltered. The result of query i is bit-identical to what the namesake returns for that
@@ -1041,6 +1089,11 @@ int rag_hybrid_linear_tenants_dev(rag_handle_t h, const float* q_dev, const int3
                                   int n_queries, int k, double alpha, double beta, double gamma, const int32_t* tenants_host,
                                   int64_t* ids_out_dev, int32_t* rows_out_dev, double* hybrid_out_dev, double* semantic_out_dev,
                                   double* keyword_out_dev, double* temporal_out_dev, void* stream);
+int rag_hybrid_linear_begin_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int n_queries,
+                                        const int32_t* tenants_host, double* local_max_out_dev, void* stream);
+int rag_hybrid_linear_finish_tenants_dev(rag_handle_t h, const float* q_dev, const double* gathered_max_dev, int world, int n_queries,
+                                         int k, double alpha, double beta, double gamma, const int32_t* tenants_host,
+                                         int64_t* partial_out_dev, void* stream);
 int rag_retrieve_rerank_tenants_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev,
                                     const int32_t* q_tok_dev, const int32_t* q_len_dev, int Lq, int n_queries, int pool, int k,
                                     int rrf_k, const int32_t* tenants_host, int mode, int cls_id, int sep_id, int L_pair,

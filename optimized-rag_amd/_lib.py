@@ -133,6 +133,10 @@ _SIGS = {
     "rag_index_set_temporal_host": ([_P, _P, C.c_int64], C.c_int),
     "rag_hybrid_linear_dev": ([_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P,
                                _P], C.c_int),
+    "rag_hybrid_linear_batch": ([_P, C.POINTER(C.c_int)], C.c_int),
+    "rag_hybrid_linear_begin_dev": ([_P, _P, _P, C.c_int, C.c_int, _P, _P], C.c_int),
+    "rag_hybrid_linear_finish_dev": ([_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P], C.c_int),
+    "rag_hybrid_linear_merge_gathered_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "rag_linear_fuse_topk_host": ([_P, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P], C.c_int),
     "rag_ce_load_host": ([_P, C.POINTER(CeConfig), C.POINTER(_P), C.c_int], C.c_int),
     "rag_ce_score_host": ([_P, _P, _P, _P, C.c_int, C.c_int, _P], C.c_int),
@@ -194,7 +198,8 @@ _SIGS = {
 for _name, _pos in (("rag_dense_topk_host", 4), ("rag_dense_topk_dev", 4), ("rag_bm25_topk_host", 5), ("rag_bm25_topk_dev", 5),
                     ("rag_hybrid_rrf_dev", 8), ("rag_hybrid_linear_dev", 9), ("rag_retrieve_rerank_dev", 11),
                     ("rag_sparse_topk_host", 6), ("rag_sparse_topk_dev", 6), ("rag_hybrid_sparse_rrf_dev", 9),
-                    ("rag_retrieve_maxsim_dev", 11), ("rag_retrieve_m3_dev", 11), ("rag_search_m3_tokens_dev", 11)):
+                    ("rag_retrieve_maxsim_dev", 11), ("rag_retrieve_m3_dev", 11), ("rag_search_m3_tokens_dev", 11),
+                    ("rag_hybrid_linear_begin_dev", 4), ("rag_hybrid_linear_finish_dev", 9)):
     _args, _res = _SIGS[_name]
     assert _args[_pos] is C.c_int
     _SIGS[_name.replace("_host", "_tenants_host").replace("_dev", "_tenants_dev")] = (_args[:_pos] + [_P] + _args[_pos + 1:], _res)
@@ -922,6 +927,63 @@ class RagEngine:
             C.c_void_p(o["hybrid"].data_ptr()), C.c_void_p(o["semantic"].data_ptr()), C.c_void_p(o["keyword"].data_ptr()),
             C.c_void_p(o["temporal"].data_ptr()), st), name)
         return o
+
+    # ---- hybrid_linear_dev over row shards: begin -> gather of the maxima -> finish -> gather of the blocks -> merge -----------
+    def hybrid_linear_batch(self):
+        """Queries one hybrid_linear_begin_dev / _finish_dev pair takes on the index as it stands (the sub-batch of hybrid_linear_dev)."""
+        n = C.c_int(0)
+        self._check(self.lib.rag_hybrid_linear_batch(self.h, C.byref(n)), "rag_hybrid_linear_batch")
+        return int(n.value)
+
+    def hybrid_linear_begin_dev(self, term_ptr, terms, local_max_out, tenant=-1, stream=None):
+        """First half of hybrid_linear_dev: local_max_out [Q] float64 <- this handle's largest raw BM25 score per query (-inf: no
+        visible document of the query's tenant). tenant: an int or one number per query, the same for the finish."""
+        import torch
+        Q = term_ptr.shape[0] - 1
+        if local_max_out.dtype != torch.float64 or local_max_out.numel() < Q or not local_max_out.is_contiguous():
+            raise RagError("hybrid_linear_begin_dev: local_max_out must be a contiguous float64 tensor of n_queries elements")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_hybrid_linear_begin_tenants_dev, "rag_hybrid_linear_begin_tenants_dev") if per_query
+                    else (self.lib.rag_hybrid_linear_begin_dev, "rag_hybrid_linear_begin_dev"))
+        self._check(fn(self.h, C.c_void_p(term_ptr.data_ptr()), C.c_void_p(terms.data_ptr()), int(Q), _ptr(t) if per_query else t,
+                       C.c_void_p(local_max_out.data_ptr()), st), name)
+        return local_max_out
+
+    def hybrid_linear_finish_dev(self, q, gathered_max, k, alpha, beta, gamma, partial_out, tenant=-1, stream=None):
+        """Second half: gathered_max [world, Q] float64 (every rank's local maxima) -> partial_out [5, Q, k] int64 = ids | hybrid |
+        semantic | keyword | temporal (float64 bits), this handle's top-k under the GLOBAL maximum."""
+        import torch
+        Q = q.shape[0]
+        if gathered_max.dtype != torch.float64 or gathered_max.dim() != 2 or gathered_max.shape[1] != Q or not gathered_max.is_contiguous():
+            raise RagError("hybrid_linear_finish_dev: gathered_max must be a contiguous float64 [world, n_queries] tensor")
+        if partial_out.dtype != torch.int64 or tuple(partial_out.shape) != (5, Q, int(k)) or not partial_out.is_contiguous():
+            raise RagError("hybrid_linear_finish_dev: partial_out must be a contiguous int64 [5, n_queries, k] tensor")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_hybrid_linear_finish_tenants_dev, "rag_hybrid_linear_finish_tenants_dev") if per_query
+                    else (self.lib.rag_hybrid_linear_finish_dev, "rag_hybrid_linear_finish_dev"))
+        self._check(fn(self.h, C.c_void_p(q.data_ptr()), C.c_void_p(gathered_max.data_ptr()), int(gathered_max.shape[0]), int(Q), int(k),
+                       float(alpha), float(beta), float(gamma), _ptr(t) if per_query else t, C.c_void_p(partial_out.data_ptr()), st), name)
+        return partial_out
+
+    def hybrid_linear_merge_gathered_dev(self, gathered, ids_out, hybrid_out, semantic_out=None, keyword_out=None, temporal_out=None,
+                                         stream=None):
+        """gathered [world, 5, Q, k] int64 (every rank's partial_out) -> the global top-k by (hybrid desc, id asc): ids_out [Q, k]
+        int64, hybrid_out and the optional component outputs [Q, k] float64. Needs no index."""
+        import torch
+        if gathered.dtype != torch.int64 or gathered.dim() != 4 or gathered.shape[1] != 5 or not gathered.is_contiguous():
+            raise RagError("hybrid_linear_merge_gathered_dev: gathered must be a contiguous int64 [world, 5, n_queries, k] tensor")
+        world, _, Q, k = gathered.shape
+        for name, o, dt in (("ids_out", ids_out, torch.int64), ("hybrid_out", hybrid_out, torch.float64), ("semantic_out", semantic_out, torch.float64),
+                            ("keyword_out", keyword_out, torch.float64), ("temporal_out", temporal_out, torch.float64)):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != (Q, k) or not o.is_contiguous()):
+                raise RagError(f"hybrid_linear_merge_gathered_dev: {name} must be a contiguous {dt} [n_queries, k] tensor")
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._check(self.lib.rag_hybrid_linear_merge_gathered_dev(self.h, p(gathered), int(world), int(Q), int(k), p(ids_out), p(hybrid_out),
+                                                                  p(semantic_out), p(keyword_out), p(temporal_out), st),
+                    "rag_hybrid_linear_merge_gathered_dev")
 
     def bm25_scores(self, term_ptr, terms):
         term_ptr = _np(term_ptr, np.int32)

@@ -176,6 +176,7 @@ static int index_load_common(rag_ctx* h, const float* emb, const int64_t* ids, i
     ARG_CHECK(h, n_rows == 0 || emb != nullptr, "emb is null");
     if (host) HOST_ENTRY(h);
     else DEV_ENTRY(h);
+    h->lin_begun.on = false;            // (the device-pointer load is a write too)
     dense_free(h);
     h->n_rows = n_rows;
     h->id_base = id_base;
@@ -236,6 +237,7 @@ static int index_append(rag_ctx* h, const float* emb, int64_t n, hipStream_t st,
     ARG_CHECK(h, n == 0 || emb != nullptr, "emb is null");
     if (host) HOST_ENTRY(h);
     else DEV_ENTRY(h);
+    h->lin_begun.on = false;
     if (n == 0) return RAG_OK;
     HIP_TRY(h, hipMemcpyAsync(h->emb32 + (size_t)h->n_rows * h->dim, emb, (size_t)n * h->dim * sizeof(float),
                               host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
@@ -778,6 +780,85 @@ int rag_index_set_temporal_host(rag_handle_t h, const double* temporal, int64_t 
     return RAG_OK;
 }
 
+// The two halves of a query sub-batch, shared by the one-call entries and by the begin / finish pair of the fusion over row
+// shards (include/rag_hip.h "linear fusion over ROW SHARDS"). lin_ws, carved in one order by linear_carve:
+struct linear_ws {
+    double* raw; float* raw32;       // [QB][n] float64 BM25 scores of every document, [QB][ld] their float32 copy (the emission operand)
+    double* mx; unsigned long long* max_key; float* qscale; float* margin;      // [QB] each (linear_scale_kernel)
+    float* gt;                       // [ld] float(gamma * temporal)
+    int32_t* term_ptr;               // [QB + 1] the query offsets of a begun sub-batch: finish takes the token counts from them
+    int32_t* rows;                   // [QB][RAG_MAX_K] the rows of finish (its block carries ids)
+    int QB; int64_t n, ld;
+};
+// queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
+// shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
+static int linear_batch(int64_t n) { return (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)8 << 30) / (std::max<int64_t>(n, 1) * 12))); }
+static int linear_carve(rag_ctx* h, hipStream_t st, linear_ws* w) {
+    const int64_t n = h->n_rows, ld = emb16_rows(h);
+    const int QB = linear_batch(n);
+    const size_t need = stage_size((size_t)QB * n, 8) + stage_size((size_t)QB * ld, 4) + 2 * stage_size(QB, 8) + 2 * stage_size(QB, 4) + stage_size(ld, 4) +
+                        stage_size((size_t)QB + 1, 4) + stage_size((size_t)QB * RAG_MAX_K, 4);
+    if (need > h->lin_ws.size()) {
+        h->lin_begun.on = false;
+        if (int rc = h->lin_ws.alloc(h, need)) return rc;
+        HIP_TRY(h, hipMemsetAsync(h->lin_ws, 0, need, st));      // the pad rows [n, ld) of raw32 are read by the last tile: keep them 0
+    }
+    char* p = h->lin_ws;
+    w->raw = stage_take<double>(p, (size_t)QB * n);
+    w->raw32 = stage_take<float>(p, (size_t)QB * ld);
+    w->mx = stage_take<double>(p, QB);
+    w->max_key = stage_take<unsigned long long>(p, QB);
+    w->qscale = stage_take<float>(p, QB);
+    w->margin = stage_take<float>(p, QB);
+    w->gt = stage_take<float>(p, ld);
+    w->term_ptr = stage_take<int32_t>(p, (size_t)QB + 1);
+    w->rows = stage_take<int32_t>(p, (size_t)QB * RAG_MAX_K);
+    w->QB = QB; w->n = n; w->ld = ld;
+    return RAG_OK;
+}
+// what the entries ask of the weights and of the index (the messages are rag_hybrid_linear_dev's)
+static int linear_check_weights(rag_ctx* h, int Q, int k, double alpha, double beta, double gamma) {
+    ARG_CHECK(h, Q > 0 && k > 0 && k <= RAG_MAX_K, "hybrid_linear: need Q > 0 and 0 < k <= 256");
+    ARG_CHECK(h, alpha > 0.0, "hybrid_linear: alpha must be positive (the cosine drives the candidate search)");
+    ARG_CHECK(h, std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma), "hybrid_linear: weights must be finite");
+    return RAG_OK;
+}
+static int linear_check_index(rag_ctx* h, int Q, int tenant, const int32_t* tenants_host) {
+    ARG_CHECK(h, tenants_host == nullptr || Q <= 65535, "hybrid_linear: a tenant array takes n_queries <= 65535");
+    if (tenants_host != nullptr)
+        for (int q = 0; q < Q && tenant < 0; ++q) tenant = std::max(tenants_host[q], -1);      // (for the check below: some filtered query)
+    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_linear: tenant filter requested but no tenants loaded");
+    if (int rc = bm25_fresh(h)) return rc;
+    ARG_CHECK(h, bm25_n_docs(h) == h->n_rows && h->n_rows > 0, "hybrid_linear: needs BM25 postings row-aligned with a non-empty index");
+    return RAG_OK;
+}
+// half (a): ONE pass of the scoring kernel writes the float64 scores (exact fusion of the survivors), their float32 copy (the emission
+// operand) and the per-query maximum; r3 re-read the 2 GB twice more (a one-workgroup-per-query max: 1.8 ms of a 4.5-ms call;
+// a bias pass: 0.6 ms)
+// (per-query tenants go with their sub-batch: the maximum is each query's own tenant's, the search filters by it)
+static int linear_scores(rag_ctx* h, const linear_ws& w, const int32_t* term_ptr_dev, const int32_t* terms_dev, int qc, int tenant,
+                         query_tenants qt, hipStream_t st) {
+    HIP_TRY(h, hipMemsetAsync(w.max_key, 0, (size_t)qc * sizeof(unsigned long long), st));
+    return bm25_scores_dev(h, term_ptr_dev, terms_dev, qc, w.raw, st, w.raw32, w.ld, w.max_key, tenant, qt);
+}
+// half (b): max_key -> divisor, beta / max, margin (token counts from term_ptr_dev), gamma * t when make_gt; the fused search; the
+// components of the returned rows
+static int linear_search(rag_ctx* h, const linear_ws& w, const int32_t* term_ptr_dev, bool make_gt, const float* q_dev, int qc, int k,
+                         double alpha, double beta, double gamma, int tenant, query_tenants qt, int64_t* ids_out_dev, int32_t* rows_out_dev,
+                         double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev, double* temporal_out_dev, hipStream_t st) {
+    double neg_per_token = 0.0;
+    if (int rc = bm25_negative_bound_args(h, &neg_per_token)) return rc;
+    float* gt = (h->temporal != nullptr && gamma != 0.0) ? w.gt : nullptr;
+    const linear_neg_bound nb = {term_ptr_dev, neg_per_token};
+    int rc = linear_prepare(h, w.max_key, nb, qc, w.n, h->temporal, beta, gamma, w.mx, w.qscale, w.margin, make_gt ? gt : nullptr, w.ld, st);
+    if (rc) return rc;
+    const dense_fused fz = {w.raw32, w.ld, w.qscale, w.margin, gt, w.raw, w.n, w.mx, h->temporal, alpha, beta, gamma};
+    if ((rc = dense_search_fused(h, q_dev, qc, k, tenant, ids_out_dev, rows_out_dev, hybrid_out_dev, st, &fz, id_space::of_index(h), qt))) return rc;
+    if (semantic_out_dev || keyword_out_dev || temporal_out_dev)
+        rc = linear_components(h, q_dev, rows_out_dev, qc, k, &fz, semantic_out_dev, keyword_out_dev, temporal_out_dev, st);
+    return rc;
+}
+
 // HybridRetriever.hybrid_search (rag/retrieval.py:214-322) over the WHOLE resident index instead of a host-side corpus list:
 // per query, hybrid = (alpha * cosine + beta * keyword) + gamma * temporal for every row (keyword = BM25Okapi score / max over
 // the corpus, 1.0 when that max is <= 0; temporal from rag_index_set_temporal_host), stable sort descending, first k.
@@ -790,62 +871,24 @@ static int hybrid_linear_entry(rag_handle_t h, const float* q_dev, const int32_t
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_dev && term_ptr_dev && ids_out_dev && rows_out_dev && hybrid_out_dev, "hybrid_linear: null pointer");
-    ARG_CHECK(h, Q > 0 && k > 0 && k <= RAG_MAX_K, "hybrid_linear: need Q > 0 and 0 < k <= 256");
-    ARG_CHECK(h, alpha > 0.0, "hybrid_linear: alpha must be positive (the cosine drives the candidate search)");
-    ARG_CHECK(h, std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma), "hybrid_linear: weights must be finite");
-    ARG_CHECK(h, tenants_host == nullptr || Q <= 65535, "hybrid_linear: a tenant array takes n_queries <= 65535");
-    if (tenants_host != nullptr)
-        for (int q = 0; q < Q && tenant < 0; ++q) tenant = std::max(tenants_host[q], -1);      // (for the check below: some filtered query)
-    ARG_CHECK(h, tenant < 0 || h->tenants != nullptr, "hybrid_linear: tenant filter requested but no tenants loaded");
-    if (int rc = bm25_fresh(h)) return rc;
-    ARG_CHECK(h, bm25_n_docs(h) == h->n_rows && h->n_rows > 0, "hybrid_linear: needs BM25 postings row-aligned with a non-empty index");
+    if (int rc = linear_check_weights(h, Q, k, alpha, beta, gamma)) return rc;
+    if (int rc = linear_check_index(h, Q, tenant, tenants_host)) return rc;
     DEV_ENTRY(h);
+    h->lin_begun.on = false;            // the planes of a begun pair are overwritten
     hipStream_t st = (hipStream_t)stream;
     entry_tenants t;
     if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
-    tenant = t.tenant;
-    const int64_t n = h->n_rows, ld = emb16_rows(h);
-    // queries per sub-batch: one query tile when the all-document scores fit 8 GB (2 GB + 1 GB at 1M rows), fewer on large
-    // shards (12.5M rows: 53 queries, 8 GB instead of 38 GB)
-    const int QB = (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)8 << 30) / (n * 12)));
-    const size_t need = stage_size((size_t)QB * n, 8) + stage_size((size_t)QB * ld, 4) + 2 * stage_size(QB, 8) + 2 * stage_size(QB, 4) + stage_size(ld, 4);
-    if (need > h->lin_ws.size()) {
-        if (int rc = h->lin_ws.alloc(h, need)) return rc;
-        HIP_TRY(h, hipMemsetAsync(h->lin_ws, 0, need, st));      // the pad rows [n, ld) of raw32 are read by the last tile: keep them 0
-    }
-    char* p = h->lin_ws;
-    double* raw = stage_take<double>(p, (size_t)QB * n);
-    float* raw32 = stage_take<float>(p, (size_t)QB * ld);
-    double* mx = stage_take<double>(p, QB);
-    unsigned long long* max_key = stage_take<unsigned long long>(p, QB);
-    float* qscale = stage_take<float>(p, QB);
-    float* margin = stage_take<float>(p, QB);
-    float* gt = (h->temporal != nullptr && gamma != 0.0) ? stage_take<float>(p, ld) : nullptr;
-    double neg_per_token = 0.0;
-    if (int rc = bm25_negative_bound_args(h, &neg_per_token)) return rc;
-    for (int q0 = 0; q0 < Q; q0 += QB) {
-        const int qc = std::min(QB, Q - q0);
-        // ONE pass of the scoring kernel writes the float64 scores (exact fusion of the survivors), their float32 copy (the emission
-        // operand) and the per-query maximum; r3 re-read the 2 GB twice more (a one-workgroup-per-query max: 1.8 ms of a 4.5-ms call;
-        // a bias pass: 0.6 ms)
-        HIP_TRY(h, hipMemsetAsync(max_key, 0, (size_t)qc * sizeof(unsigned long long), st));
-        // (per-query tenants go with their sub-batch: the maximum is each query's own tenant's, the search filters by it)
-        int rc = bm25_scores_dev(h, term_ptr_dev + q0, terms_dev, qc, raw, st, raw32, ld, max_key, tenant, t.qt + q0);
+    linear_ws w;
+    if (int rc = linear_carve(h, st, &w)) return rc;
+    for (int q0 = 0; q0 < Q; q0 += w.QB) {
+        const int qc = std::min(w.QB, Q - q0);
+        const size_t o = (size_t)q0 * k;
+        int rc = linear_scores(h, w, term_ptr_dev + q0, terms_dev, qc, t.tenant, t.qt + q0, st);
         if (rc) return rc;
-        const linear_neg_bound nb = {term_ptr_dev + q0, neg_per_token};
-        if ((rc = linear_prepare(h, max_key, nb, qc, n, h->temporal, beta, gamma, mx, qscale, margin, q0 == 0 ? gt : nullptr, ld, st)))
-            return rc;
-        const dense_fused fz = {raw32, ld, qscale, margin, gt, raw, n, mx, h->temporal, alpha, beta, gamma};
-        rc = dense_search_fused(h, q_dev + (size_t)q0 * h->dim, qc, k, tenant, ids_out_dev + (size_t)q0 * k, rows_out_dev + (size_t)q0 * k,
-                                hybrid_out_dev + (size_t)q0 * k, st, &fz, id_space::of_index(h), t.qt + q0);
+        rc = linear_search(h, w, term_ptr_dev + q0, q0 == 0, q_dev + (size_t)q0 * h->dim, qc, k, alpha, beta, gamma, t.tenant, t.qt + q0,
+                           ids_out_dev + o, rows_out_dev + o, hybrid_out_dev + o, semantic_out_dev ? semantic_out_dev + o : nullptr,
+                           keyword_out_dev ? keyword_out_dev + o : nullptr, temporal_out_dev ? temporal_out_dev + o : nullptr, st);
         if (rc) return rc;
-        if (semantic_out_dev || keyword_out_dev || temporal_out_dev) {
-            rc = linear_components(h, q_dev + (size_t)q0 * h->dim, rows_out_dev + (size_t)q0 * k, qc, k, &fz,
-                                   semantic_out_dev ? semantic_out_dev + (size_t)q0 * k : nullptr,
-                                   keyword_out_dev ? keyword_out_dev + (size_t)q0 * k : nullptr,
-                                   temporal_out_dev ? temporal_out_dev + (size_t)q0 * k : nullptr, st);
-            if (rc) return rc;
-        }
     }
     return RAG_OK;
 }
@@ -863,6 +906,121 @@ int rag_hybrid_linear_tenants_dev(rag_handle_t h, const float* q_dev, const int3
     if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
     return hybrid_linear_entry(h, q_dev, term_ptr_dev, terms_dev, Q, k, alpha, beta, gamma, -1, tenants_host, ids_out_dev, rows_out_dev,
                                hybrid_out_dev, semantic_out_dev, keyword_out_dev, temporal_out_dev, stream);
+}
+
+// ---- the linear fusion over ROW SHARDS: the seam between the two halves, a gather of the ranks' maxima in between -------------
+int rag_hybrid_linear_batch(rag_handle_t h, int* max_queries_out) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, max_queries_out != nullptr, "hybrid_linear_batch: null pointer");
+    *max_queries_out = linear_batch(h->n_rows);
+    return RAG_OK;
+}
+
+// what begin and finish share beyond the one-call entries' checks: one sub-batch, ids through id_base
+static int linear_check_shard(rag_ctx* h, const char* who, int Q) {
+    if (h->ids != nullptr) {
+        h->err = std::string(who) + ": the index has explicit ids; a row shard is loaded with id_base (the order across shards is id_base + row)";
+        return RAG_ERR_STATE;
+    }
+    const int QB = linear_batch(h->n_rows);
+    if (Q > QB) {
+        h->err = "bad argument: " + std::string(who) + ": n_queries " + std::to_string(Q) + " exceeds the sub-batch of this index, " +
+                 std::to_string(QB) + " queries (rag_hybrid_linear_batch)";
+        return RAG_ERR_ARG;
+    }
+    return RAG_OK;
+}
+
+static int hybrid_linear_begin_entry(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int tenant,
+                                     const int32_t* tenants_host, double* local_max_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    h->lin_begun.on = false;            // a begin replaces whatever was begun, and a failed one leaves nothing begun
+    ARG_CHECK(h, term_ptr_dev && local_max_out_dev, "hybrid_linear_begin: null pointer");
+    ARG_CHECK(h, Q > 0, "hybrid_linear_begin: need n_queries > 0");
+    if (int rc = linear_check_index(h, Q, tenant, tenants_host)) return rc;
+    if (int rc = linear_check_shard(h, "hybrid_linear_begin", Q)) return rc;
+    DEV_ENTRY(h);
+    hipStream_t st = (hipStream_t)stream;
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
+    linear_ws w;
+    if (int rc = linear_carve(h, st, &w)) return rc;
+    if (int rc = linear_scores(h, w, term_ptr_dev, terms_dev, Q, t.tenant, t.qt, st)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(w.term_ptr, term_ptr_dev, ((size_t)Q + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (int rc = linear_max_out(h, w.max_key, Q, local_max_out_dev, st)) return rc;
+    h->lin_begun.Q = Q;
+    h->lin_begun.n_rows = h->n_rows;
+    h->lin_begun.tenant = tenants_host ? -1 : std::max(tenant, -1);
+    h->lin_begun.tenants.clear();
+    if (tenants_host) h->lin_begun.tenants.assign(tenants_host, tenants_host + Q);
+    h->lin_begun.on = true;
+    return RAG_OK;
+}
+int rag_hybrid_linear_begin_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int tenant,
+                                double* local_max_out_dev, void* stream) {
+    return hybrid_linear_begin_entry(h, term_ptr_dev, terms_dev, Q, tenant, nullptr, local_max_out_dev, stream);
+}
+int rag_hybrid_linear_begin_tenants_dev(rag_handle_t h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q,
+                                        const int32_t* tenants_host, double* local_max_out_dev, void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return hybrid_linear_begin_entry(h, term_ptr_dev, terms_dev, Q, -1, tenants_host, local_max_out_dev, stream);
+}
+
+static int hybrid_linear_finish_entry(rag_handle_t h, const float* q_dev, const double* gathered_max_dev, int world, int Q, int k,
+                                      double alpha, double beta, double gamma, int tenant, const int32_t* tenants_host,
+                                      int64_t* partial_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    const bool begun = h->lin_begun.on;
+    h->lin_begun.on = false;            // consumed by this call, whatever comes of it
+    ARG_CHECK(h, q_dev && gathered_max_dev && partial_out_dev, "hybrid_linear_finish: null pointer");
+    ARG_CHECK(h, world > 0, "hybrid_linear_finish: need world > 0");
+    if (int rc = linear_check_weights(h, Q, k, alpha, beta, gamma)) return rc;
+    bool same = begun && Q == h->lin_begun.Q && h->n_rows == h->lin_begun.n_rows && h->lin_ws != nullptr;
+    if (same && tenants_host) same = (int)h->lin_begun.tenants.size() == Q && std::equal(tenants_host, tenants_host + Q, h->lin_begun.tenants.begin());
+    else if (same) same = h->lin_begun.tenants.empty() && std::max(tenant, -1) == h->lin_begun.tenant;
+    if (!same) {
+        h->err = begun ? "hybrid_linear_finish: n_queries or the tenant argument differ from the rag_hybrid_linear_begin_dev before it"
+                       : "hybrid_linear_finish: no rag_hybrid_linear_begin_dev before it, or a host call, a write or rag_hybrid_linear_dev "
+                         "came in between (the score planes are gone)";
+        return RAG_ERR_STATE;
+    }
+    if (int rc = linear_check_index(h, Q, tenant, tenants_host)) return rc;
+    if (int rc = linear_check_shard(h, "hybrid_linear_finish", Q)) return rc;
+    DEV_ENTRY(h);
+    hipStream_t st = (hipStream_t)stream;
+    entry_tenants t;
+    if (int rc = entry_tenants_of(h, tenant, tenants_host, Q, st, &t)) return rc;
+    linear_ws w;
+    if (int rc = linear_carve(h, st, &w)) return rc;      // (sized by begin: nothing is allocated here)
+    if (int rc = linear_max_reduce(h, gathered_max_dev, world, Q, w.max_key, st)) return rc;
+    const size_t P = (size_t)Q * k;
+    double* planes = reinterpret_cast<double*>(partial_out_dev + P);
+    return linear_search(h, w, w.term_ptr, true, q_dev, Q, k, alpha, beta, gamma, t.tenant, t.qt, partial_out_dev, w.rows, planes,
+                         planes + P, planes + 2 * P, planes + 3 * P, st);
+}
+int rag_hybrid_linear_finish_dev(rag_handle_t h, const float* q_dev, const double* gathered_max_dev, int world, int Q, int k,
+                                 double alpha, double beta, double gamma, int tenant, int64_t* partial_out_dev, void* stream) {
+    return hybrid_linear_finish_entry(h, q_dev, gathered_max_dev, world, Q, k, alpha, beta, gamma, tenant, nullptr, partial_out_dev, stream);
+}
+int rag_hybrid_linear_finish_tenants_dev(rag_handle_t h, const float* q_dev, const double* gathered_max_dev, int world, int Q, int k,
+                                         double alpha, double beta, double gamma, const int32_t* tenants_host, int64_t* partial_out_dev,
+                                         void* stream) {
+    if (h && !tenants_host) { LOCK(h); ARG_CHECK(h, false, "null tenants array"); }
+    return hybrid_linear_finish_entry(h, q_dev, gathered_max_dev, world, Q, k, alpha, beta, gamma, -1, tenants_host, partial_out_dev, stream);
+}
+
+int rag_hybrid_linear_merge_gathered_dev(rag_handle_t h, const int64_t* gathered_dev, int world, int Q, int k, int64_t* ids_out_dev,
+                                         double* hybrid_out_dev, double* semantic_out_dev, double* keyword_out_dev,
+                                         double* temporal_out_dev, void* stream) {
+    if (!h) return RAG_ERR_ARG;
+    LOCK(h);
+    ARG_CHECK(h, gathered_dev && ids_out_dev && hybrid_out_dev, "hybrid_linear_merge: null pointer");
+    DEV_ENTRY(h);
+    return linear_merge(h, gathered_dev, world, Q, k, ids_out_dev, hybrid_out_dev, semantic_out_dev, keyword_out_dev, temporal_out_dev,
+                        (hipStream_t)stream);
 }
 
 int rag_bm25_set_normalize(rag_handle_t h, int on) {

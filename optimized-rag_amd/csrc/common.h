@@ -115,7 +115,7 @@ struct rag_index_mem {
 struct rag_device_mem : rag_index_mem {
     dev_buf<double> side_scores;     // hybrid_legs: score scratch of the BM25 leg on the side stream
     dev_buf<double> temporal;        // [n_rows] per-row temporal score (linear fusion) or null
-    dev_buf<char> lin_ws;            // rag_hybrid_linear_dev: raw BM25 + bias + max of one sub-batch
+    dev_buf<char> lin_ws;            // rag_hybrid_linear_dev: raw BM25 + bias + max of one sub-batch (api.hip linear_ws); kept between rag_hybrid_linear_begin_dev and its finish
     // dense search workspace (sized for ws_q queries): the batch's candidate state, and what only the whole batch needs
     dense_ws ws;                     // [ws_qpad] rows
     dev_buf<float> q32;              // [ws_q][dim]     staging for host queries
@@ -166,6 +166,10 @@ struct rag_ctx : rag_device_mem {
     bool index_loaded = false;   // rag_index_load_* / rag_index_reserve ran (an EMPTY index is a valid, searchable state)
     int64_t n_reserved = 0;      // rows allocated by rag_index_reserve (chunked bulk load), 0 otherwise
     double temporal_absmax = 0.0;                                      // max |temporal[i]| (sizes the fused emission margin)
+    // rag_hybrid_linear_begin_dev ran and lin_ws still holds its score planes: what rag_hybrid_linear_finish_dev must be called
+    // with. Dropped by finish, by rag_hybrid_linear_dev (it reuses lin_ws) and by every *_host entry (host_after_dev: each write
+    // to the index or the postings is one).
+    struct { bool on = false; int Q = 0; int64_t n_rows = 0; int tenant = -1; std::vector<int32_t> tenants; } lin_begun;
     std::unordered_map<int32_t, std::pair<int64_t, int>> tenant_span;  // tenant -> (offset, count) into tenant_tiles
     std::unordered_map<int32_t, std::vector<int32_t>> tenant_lists;    // host copy of those lists (inserts extend them)
     int64_t tenant_rows = 0;                                           // row count the tenant table was built for
@@ -387,6 +391,7 @@ static inline int prof_end(rag_ctx* h, int stage, hipStream_t st) {
 // enqueue order is device order. So a *_host entry first waits for the device when *_dev work was queued since the last wait.
 // Nothing is added to either path while a caller stays with one kind of call: no HIP call, one flag.
 static inline int host_after_dev(rag_ctx* h) {
+    h->lin_begun.on = false;                 // (a begun linear fusion does not survive a *_host call: rag_ctx::lin_begun)
     if (!h->dev_pending) return RAG_OK;
     HIP_TRY(h, hipDeviceSynchronize());
     h->dev_pending = false;
@@ -463,6 +468,12 @@ int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bou
                    double beta, double gamma, double* mx, float* qscale, float* margin, float* gt, int64_t ld, hipStream_t st);
 int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, int Q, int k, const dense_fused* fz, double* sem_out,
                       double* kw_out, double* tmp_out, hipStream_t st);
+// the fusion over row shards (rag_hybrid_linear_begin_dev / _finish_dev / _merge_gathered_dev): max_key <-> float64 maxima on each
+// side of the gather, and the merge of the ranks' [5][Q][k] blocks that carries the components with their row
+int linear_max_out(rag_ctx* h, const unsigned long long* max_key, int Q, double* out_dev, hipStream_t st);
+int linear_max_reduce(rag_ctx* h, const double* gathered_dev, int world, int Q, unsigned long long* max_key, hipStream_t st);
+int linear_merge(rag_ctx* h, const int64_t* blocks, int world, int Q, int k, int64_t* ids_out, double* hyb_out, double* sem_out,
+                 double* kw_out, double* tmp_out, hipStream_t st);
 int dense_free(rag_ctx* h);
 int dense_build_tenant_tiles(rag_ctx* h, const int32_t* tenants_host, int64_t n_rows);
 int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t first_row, int64_t n);

@@ -895,6 +895,28 @@ __global__ void linear_scale_kernel(const unsigned long long* __restrict__ max_k
     margin[q] = beta == 0.0 ? 0.f : (float)(2.0 * fabs(beta) * fmax(0.0, kw_neg - 1.0) / 2097152.0 * 1.0001);    // (0 * inf is NaN)
 }
 
+// The seam of the fusion over ROW SHARDS (rag_hybrid_linear_begin_dev / _finish_dev): a rank's max_key covers its own rows only,
+// the divisor is the maximum over every rank's. begin reports the local maximum as a float64 (-inf = no visible document of the
+// query's tenant on this handle), finish reduces the gathered [world][Q] maxima back into max_key, which linear_scale_kernel then
+// reads as if one scoring pass had seen every row: the maximum of the finite entries, key 0 (divisor 1.0) when there is none.
+// f64_orderable / f64_from_orderable are inverses, so world = 1 hands linear_scale_kernel the key the scoring kernel wrote.
+__global__ void linear_max_out_kernel(const unsigned long long* __restrict__ max_key, int Q, double* __restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Q) return;
+    const unsigned long long kq = max_key[q];
+    out[q] = kq != 0ull ? f64_from_orderable(kq) : -INFINITY;
+}
+__global__ void linear_max_reduce_kernel(const double* __restrict__ gathered, int world, int Q, unsigned long long* __restrict__ max_key) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Q) return;
+    double m = -INFINITY;
+    for (int r = 0; r < world; ++r) {
+        const double v = gathered[(size_t)r * Q + q];
+        if (v > -INFINITY && v < INFINITY && v > m) m = v;       // (false for NaN)
+    }
+    max_key[q] = m > -INFINITY ? f64_orderable(m) : 0ull;
+}
+
 // float32 recency term of every row for the emission: gamma * temporal (zero past the last row)
 __global__ void linear_gt_kernel(const double* __restrict__ temporal, int64_t n, int64_t ld, double gamma, float* __restrict__ gt) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1398,6 +1420,15 @@ int linear_prepare(rag_ctx* h, const unsigned long long* max_key, linear_neg_bou
     return launch_status(h);
 }
 
+int linear_max_out(rag_ctx* h, const unsigned long long* max_key, int Q, double* out_dev, hipStream_t st) {
+    launch(linear_max_out_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, max_key, Q, out_dev);
+    return launch_status(h);
+}
+int linear_max_reduce(rag_ctx* h, const double* gathered_dev, int world, int Q, unsigned long long* max_key, hipStream_t st) {
+    launch(linear_max_reduce_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, gathered_dev, world, Q, max_key);
+    return launch_status(h);
+}
+
 int linear_components(rag_ctx* h, const float* q_dev, const int32_t* rows_dev, int Q, int k, const dense_fused* fz, double* sem_out,
                       double* kw_out, double* tmp_out, hipStream_t st) {
     launch(linear_components_kernel, dim3((unsigned)(((int64_t)Q * k + 3) / 4)), dim3(256), 0, st, q_dev, h->emb32, rows_dev, Q, k, h->dim,
@@ -1484,6 +1515,63 @@ int merge_topk(rag_ctx* h, const int64_t* ids, const double* scores, int n_lists
     ARG_CHECK(h, lds + 64 <= 64 * 1024, "merge: n_lists*k too large (max 4092 entries)");
     ARG_CHECK(h, list_stride >= (int64_t)Q * k, "merge: list_stride < Q*k");
     launch(merge_topk_kernel, dim3(Q), dim3(256), lds, st, ids, scores, n_lists, list_stride, Q, k, ids_out, scores_out, normalize);
+    return launch_status(h);
+}
+
+// The same merge with a PAYLOAD (rag_hybrid_linear_merge_gathered_dev): blocks[world][5][Q][k] int64 = every rank's ids | hybrid |
+// semantic | keyword | temporal (float64 bits). Ranked by (hybrid desc, id asc) exactly as above; a winner's three components are
+// copied from its source slot as bits, never recomputed. Only ids and hybrid scores go through LDS (16 B per entry, as above).
+__global__ __launch_bounds__(256) void linear_merge_kernel(const int64_t* __restrict__ blocks, int world, int Q, int k,
+                                                            int64_t* __restrict__ ids_out, double* __restrict__ hyb_out,
+                                                            int64_t* __restrict__ sem_out, int64_t* __restrict__ kw_out,
+                                                            int64_t* __restrict__ tmp_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int total = world * k;
+    double* sc = reinterpret_cast<double*>(smem);
+    int64_t* id = reinterpret_cast<int64_t*>(smem + (size_t)total * 8);
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const size_t P = (size_t)Q * k;
+    for (int i = tid; i < total; i += 256) {
+        const size_t src = (size_t)(i / k) * 5 * P + (size_t)q * k + (i % k);
+        id[i] = blocks[src];
+        sc[i] = __builtin_bit_cast(double, blocks[src + P]);
+    }
+    for (int i = tid; i < k; i += 256) {
+        const size_t o = (size_t)q * k + i;
+        ids_out[o] = -1;
+        hyb_out[o] = 0.0;
+        if (sem_out) sem_out[o] = 0;
+        if (kw_out) kw_out[o] = 0;
+        if (tmp_out) tmp_out[o] = 0;
+    }
+    __syncthreads();
+    for (int i = tid; i < total; i += 256) {
+        const int64_t me = id[i];
+        if (me < 0) continue;
+        const double e = sc[i];
+        int rank = 0;
+        for (int u = 0; u < total && rank < k; ++u) {
+            const int64_t o = id[u];
+            rank += (o >= 0) && ((sc[u] > e) || (sc[u] == e && o < me));
+        }
+        if (rank < k) {
+            const size_t src = (size_t)(i / k) * 5 * P + (size_t)q * k + (i % k), o = (size_t)q * k + rank;
+            ids_out[o] = me;
+            hyb_out[o] = e;
+            if (sem_out) sem_out[o] = blocks[src + 2 * P];
+            if (kw_out) kw_out[o] = blocks[src + 3 * P];
+            if (tmp_out) tmp_out[o] = blocks[src + 4 * P];
+        }
+    }
+}
+
+int linear_merge(rag_ctx* h, const int64_t* blocks, int world, int Q, int k, int64_t* ids_out, double* hyb_out, double* sem_out,
+                 double* kw_out, double* tmp_out, hipStream_t st) {
+    ARG_CHECK(h, world > 0 && Q > 0 && k > 0, "hybrid_linear_merge: sizes must be positive");
+    const size_t lds = (size_t)world * k * 16;
+    ARG_CHECK(h, lds + 64 <= 64 * 1024, "hybrid_linear_merge: world * k too large (max 4092 entries)");
+    launch(linear_merge_kernel, dim3(Q), dim3(256), lds, st, blocks, world, Q, k, ids_out, hyb_out, reinterpret_cast<int64_t*>(sem_out),
+           reinterpret_cast<int64_t*>(kw_out), reinterpret_cast<int64_t*>(tmp_out));
     return launch_status(h);
 }
 

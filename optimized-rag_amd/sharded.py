@@ -5,6 +5,9 @@ postings, token ids) partitioned contiguously, ONE small collective per stage.
     hybrid:  local dense top-pool + local RAW BM25 top-pool (global idf / avgdl replicated)  ->  ONE all_gather of both
              lists  ->  rag_hybrid_fuse_gathered_dev: two merges, BM25 / global max, RRF on the MERGED lists (RRF needs
              GLOBAL ranks, so the lists are merged before fusing) - all inside the library
+    linear:  every document's raw BM25 score + the local maximum (rag_hybrid_linear_begin_dev)  ->  all_gather of [Q] float64 maxima
+             ->  the fused search under the GLOBAL maximum (rag_hybrid_linear_finish_dev)  ->  all_gather of [5][Q][k] blocks  ->
+             rag_hybrid_linear_merge_gathered_dev (hybrid desc, id asc, components carried): ShardedHybridIndex.search_linear
     bge-m3:  local dense + sparse top-pool  ->  all_gather  ->  rag_m3_candidates_gathered_dev (merges, RRF on the merged lists)
              ->  rag_m3_score_ids_dev (the rank that holds a candidate's rows and token vectors scores it)  ->  all_gather  ->
              rag_m3_combine_gathered_dev (owner select, three-way combine, stable top-k): ShardedM3Index
@@ -18,6 +21,8 @@ bound RCCL behind the C-ABI); every piece of arithmetic on the gathered lists is
 """
 import torch
 import torch.distributed as dist
+
+from ._lib import _tenant_arg
 
 
 def shard_bounds(n_rows, world):
@@ -85,11 +90,20 @@ class ShardedHybridIndex(ShardedDenseIndex):
     doc-partitioned slice of the postings built by Bm25Postings.shard (global statistics), loaded row-aligned so both
     searches speak the same doc-id space."""
 
-    def load_shard(self, emb_shard, first_global_row, postings_shard=None):
+    # search_linear: queries per begin / finish pair. None = the smallest hybrid_linear_batch() of the ranks, agreed once per
+    # load; a number (the SAME on every rank, not above that) forces smaller pieces.
+    linear_sub_batch = None
+
+    def load_shard(self, emb_shard, first_global_row, postings_shard=None, temporal=None):
+        """temporal: this rank's slice of the per-row temporal vector of search_linear (float64 [rows]; None = zeros)."""
         super().load_shard(emb_shard, first_global_row)
         if postings_shard is not None:
             postings_shard.load(self.engine)
         self.engine.bm25_set_normalize(False)
+        if temporal is not None or getattr(self, "_has_temporal", False):      # (None after a vector clears it: a reload keeps none)
+            self.engine.set_temporal(temporal)
+            self._has_temporal = temporal is not None
+        self._lin_agreed = None
 
     def _hyb_buffers(self, Q, pool, k, device):
         key = ("hyb", Q, pool, k, str(device))
@@ -132,6 +146,66 @@ class ShardedHybridIndex(ShardedDenseIndex):
         recv = self._hyb_buffers(queries.shape[0], pool, k, queries.device)["recv"]
         _gather(recv, send, self.group, self.engine)
         return self.fuse_gathered(recv, k, rrf_k)
+
+    # ---- the reference's own fusion, (alpha * cosine + beta * BM25 / max) + gamma * temporal, over row shards ----------------
+    def _lin_batch(self, device):
+        """Queries per begin / finish pair, the same on every rank: agreed once per load (one gather of one number per rank)."""
+        if self.linear_sub_batch is not None:
+            return int(self.linear_sub_batch)
+        if getattr(self, "_lin_agreed", None) is None:
+            mine = self.engine.hybrid_linear_batch()
+            if self.world > 1:
+                send = torch.full((1,), mine, dtype=torch.int64, device=device)
+                recv = torch.empty((self.world, 1), dtype=torch.int64, device=device)
+                _gather(recv, send, self.group, self.engine)
+                mine = min(int(v) for v in recv.flatten().tolist())
+            self._lin_agreed = mine
+        return self._lin_agreed
+
+    def _lin_buffers(self, Q, k, device):
+        key = ("lin", Q, k, str(device))
+        if key not in self._bufs:
+            i64, f64 = torch.int64, torch.float64
+            self._bufs[key] = dict(mx=torch.empty((Q,), dtype=f64, device=device), mx_all=torch.empty((self.world, Q), dtype=f64, device=device),
+                                   part=torch.empty((5, Q, k), dtype=i64, device=device),
+                                   part_all=torch.empty((self.world, 5, Q, k), dtype=i64, device=device))
+        return self._bufs[key]
+
+    def search_linear(self, queries, term_ptr, terms, k, alpha, beta, gamma, tenant=-1):
+        """HybridRetriever.hybrid_search over the row shards. queries [Q, dim] float32, term_ptr [Q+1] / terms int32 (global term
+        ids), replicated; tenant an int or one number per query. Returns dict(ids [Q,k] int64, hybrid / semantic / keyword /
+        temporal [Q,k] float64): the outputs of hybrid_linear_dev on the unsharded index, identical on every rank.
+
+        Per sub-batch: hybrid_linear_begin_dev (every document's raw BM25 score, this rank's maximum)  ->  gather [world, Q]
+        float64  ->  hybrid_linear_finish_dev (the fused search under the GLOBAL maximum)  ->  gather [world, 5, Q, k] int64  ->
+        hybrid_linear_merge_gathered_dev. world == 1 runs the same calls without the gathers."""
+        Q, dev = queries.shape[0], queries.device
+        per_query, tenant = _tenant_arg(tenant, Q)
+        key = ("lin_out", Q, k, str(dev))
+        if key not in self._bufs:
+            self._bufs[key] = dict(ids=torch.empty((Q, k), dtype=torch.int64, device=dev),
+                                   **{n: torch.empty((Q, k), dtype=torch.float64, device=dev) for n in ("hybrid", "semantic", "keyword", "temporal")})
+        out = self._bufs[key]
+        step = self._lin_batch(dev)
+        for q0 in range(0, Q, step):
+            q1 = min(Q, q0 + step)
+            b = self._lin_buffers(q1 - q0, k, dev)
+            t = tenant[q0:q1] if per_query else tenant
+            self.engine.hybrid_linear_begin_dev(term_ptr[q0:q1 + 1], terms, b["mx"], tenant=t)
+            if self.world == 1:
+                mx_all = b["mx"].unsqueeze(0)
+            else:
+                mx_all = b["mx_all"]
+                _gather(mx_all, b["mx"], self.group, self.engine)
+            self.engine.hybrid_linear_finish_dev(queries[q0:q1], mx_all, k, alpha, beta, gamma, b["part"], tenant=t)
+            if self.world == 1:
+                part_all = b["part"].unsqueeze(0)
+            else:
+                part_all = b["part_all"]
+                _gather(part_all, b["part"], self.group, self.engine)
+            self.engine.hybrid_linear_merge_gathered_dev(part_all, out["ids"][q0:q1], out["hybrid"][q0:q1], out["semantic"][q0:q1],
+                                                         out["keyword"][q0:q1], out["temporal"][q0:q1])
+        return out
 
 
 class ShardedM3Index(ShardedDenseIndex):
