@@ -69,10 +69,11 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, sparse_tail_fold, tokvec_compact_rows, ce_chunk_tokens, ce_mx, ce_attn_stream (DESIGN.md section 6;
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, sparse_tail_fold, tokvec_compact_rows, ce_chunk_tokens, ce_mx, ce_attn_stream, ce_ffn_fused (DESIGN.md section 6;
  * ce_attn_stream: 0 = attention of 64-wide heads above length class 512 by the streamed kernel, -1 = by the global-memory form at
  * every class above 256, 1 = by the streamed kernel at every class above 512 whatever the default there - the same bits in all
- * three). Unknown name: RAG_ERR_ARG. */
+ * three; ce_ffn_fused: the two FFN GEMMs of an MX layer as one launch (0 = where its per-workgroup slots fit
+ * the cache, 1 = always, -1 = two launches) - the same bits in all three). Unknown name: RAG_ERR_ARG. */
 int rag_set_option(rag_handle_t h, const char* name, int value);
 
 /* ---- dense index: replaces the pgvector tables behind

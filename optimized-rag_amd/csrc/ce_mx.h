@@ -157,6 +157,7 @@ struct mx_tile_iter {
 // what the K loop of one tile needs from the persistent loop around it
 struct mx_stream {
     __amdgpu_buffer_rsrc_t w_rs, x_cur, x_nxt;
+    __amdgpu_buffer_rsrc_t w_rs_nxt;                         // the next item's weight tensor, where it can differ (mx_ksteps<.., WSWITCH = true>)
     unsigned w_cur, w_nxt, voff;
     int wid, ring, nk, a_off, b_off;
     bool has_next;
@@ -164,14 +165,14 @@ struct mx_stream {
 };
 
 // piece k (0..5) of this wave in a step: image piece p = wid + 8k; p < 36: weights, else tokens
-#define MX_PIECE(S, k, st_, ws_, xrs_, ks_)                                                                               \
+#define MX_PIECE(S, k, st_, wrs_, ws_, xrs_, ks_)                                                                         \
     {                                                                                                                     \
         const int p_ = (S).wid + 8 * (k);                                                                                 \
-        if (p_ < 36) { MX_ISSUE_W((S).w_rs, (S).voff, (ws_) + (ks_) * MX_A_STAGE + p_ * 1024, (st_) + p_ * 1024); }         \
+        if (p_ < 36) { MX_ISSUE_W(wrs_, (S).voff, (ws_) + (ks_) * MX_A_STAGE + p_ * 1024, (st_) + p_ * 1024); }            \
         else { MX_ISSUE_X(xrs_, (S).voff, (ks_) * MX_B_STAGE + (p_ - 36) * 1024, (st_) + p_ * 1024); }                     \
     }
 
-template <bool SWAP>
+template <bool SWAP, bool WSWITCH = false>
 __device__ __forceinline__ void mx_ksteps(f32x16 (&acc)[6], const mx_stream& S, bool first) {
     const int nk = S.nk;
     for (int t = 0; t < nk; ++t) {
@@ -186,6 +187,7 @@ __device__ __forceinline__ void mx_ksteps(f32x16 (&acc)[6], const mx_stream& S, 
         const unsigned ks_ = (unsigned)(u2 < nk ? u2 : (S.has_next ? u2 - nk : nk - 1));
         char* const dst = S.smem + ((S.ring + u2) % MX_STAGES) * MX_STAGE;
         const unsigned wsrc = nx_ ? S.w_nxt : S.w_cur;
+        const __amdgpu_buffer_rsrc_t wrs = WSWITCH && nx_ ? S.w_rs_nxt : S.w_rs;
         const __amdgpu_buffer_rsrc_t xsrc = nx_ ? S.x_nxt : S.x_cur;
         const half8 xh0 = *reinterpret_cast<const half8*>(st + S.b_off);
         const half8 xh1 = *reinterpret_cast<const half8*>(st + S.b_off + 2 * MX_B_PLANE);
@@ -210,7 +212,7 @@ __device__ __forceinline__ void mx_ksteps(f32x16 (&acc)[6], const mx_stream& S, 
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             if (b + 2 < 6 && MX_READ_A_IF(b + 2)) { MX_READ_A(b + 2, b & 1) }
-            MX_PIECE(S, b, dst, wsrc, xsrc, ks_)
+            MX_PIECE(S, b, dst, wrs, wsrc, xsrc, ks_)
         }
 #undef MX_READ_A
     }
@@ -249,7 +251,7 @@ __device__ __forceinline__ void mx_gemm_loop(const char* __restrict__ W, const c
     for (int u = 0; u < 2; ++u) {                            // prologue: steps 0 and 1 of the first tile
         char* st_ = smem + u * MX_STAGE;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) MX_PIECE(S, k, st_, S.w_cur, S.x_cur, (unsigned)u)
+        for (int k = 0; k < 6; ++k) MX_PIECE(S, k, st_, S.w_rs, S.w_cur, S.x_cur, (unsigned)u)
     }
     // the epilogue's per-feature parameters (bias, LayerNorm weights) go to LDS once per workgroup, under the prologue's DMA latency:
     // a tile's epilogue then reads them with ds_read_b128 instead of 24-72 global float4 loads per thread
@@ -722,3 +724,135 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const char* __restrict__ W
     mx_gemm_loop(W, X, nk, n_ft, n_tt, smem, epi);
 }
 #define MX_KERNEL_LDS (MX_LDS + MX_PARAM_OFF + 6144)      // 155,648 B: ring + exchange space + staged parameters (<= 1536 floats)
+
+// ---- the whole FFN of a token tile in ONE persistent kernel: the intermediate never has a tensor of its own ---------------------
+// The same K loop, ring, tile geometry and epilogues as the two launches it replaces (mx_gemm_kernel<mx_epi_gelu>, then <mx_epi_ln>),
+// so every output element sees the same MFMAs in the same K order, the same GELU and the same LayerNorm grouping: the same bits.
+// What changes is the work list and where the intermediate lives. A workgroup owns token tiles (the r-th one is tile
+// (slot + r * n_slots) * 8 + xcd, as in mx_gemm_loop) and walks, for each of them, n_up + 1 ITEMS:
+//   item i < n_up : FFN-up feature tile i: nk = 12, W = w18 tile i, X = the x8 tile, mx_epi_gelu into the workgroup's SLOT
+//   item n_up     : FFN-down: nk = ffn / 32, W = w28, X = the slot, mx_epi_ln on the x8 tile in place
+// The slot is 128 tokens x ffn x 3 B in the image layout of ONE token tile (mx_store_block and the DMA addressing as they are), at
+// slots + blockIdx.x * slot bytes, overwritten on every token tile: produced, consumed and overwritten by one workgroup, a few
+// hundred KiB that stay in the caches instead of an [all tokens][ffn] tensor written to memory and read back.
+//
+// The DMA stream stays continuous across items (the last two steps of an item issue steps 0 and 1 of the next one), and a slot's
+// bytes go from the GELU epilogue's global stores to the same workgroup's LDS-DMA reads. Why that needs no fence:
+//   * ORDER. On gfx9 stores count in vmcnt with the loads, in issue order. Step 1 of the item after an epilogue waits for
+//     vmcnt(6): all but the six pieces of its step 0 have retired, the epilogue's stores among them, and its barrier follows in
+//     every wave. With n_up >= 2 the first DMA that reads a stored byte is issued at least ten steps later (FFN-down's steps 0 and 1
+//     read features 0..63 = up tile 0, issued in steps 10 and 11 of the LAST up tile; steps 12 k.. of FFN-down, up tile k, are issued
+//     from its step 12 k - 2 >= 10 on). With n_up = 1 there is no item in between: FFN-down is not prefetched, the workgroup drains
+//     its stores (vmcnt(0), barrier) after the epilogue and restarts the stream with a prologue of its own.
+//   * VISIBILITY. Writer and reader are waves of one workgroup on one CU: they share its vector L1, which a retired store has
+//     written through, so a line the previous token tile's reads left there is not served stale (workgroup-scope coherence in the
+//     default, non-split workgroup mode; the DMA reads keep the default cache policy). Nothing crosses workgroups: no flag, no spin.
+//   * WAR. The next token tile's up items read x8 only; its first epilogue overwrites the slot after FFN-down's last read retired
+//     (the vmcnt(0) before every epilogue). x8 rows are rewritten by FFN-down after every up item of the tile has read them, and
+//     no other workgroup reads that tile.
+#define MX_FFN_GELU_OFF (3 * 384 * 4)                   // mx_epi_gelu's exchange base inside the fused kernel: its bias follows the LayerNorm parameters
+#define MX_FFN_LDS (MX_LDS + MX_PARAM_OFF + MX_FFN_GELU_OFF + 6144)     // 160,256 B of the CU's 160 KiB
+__host__ __device__ __forceinline__ size_t mx_ffn_slot_bytes(int ffn) { return (size_t)MX_TN * ffn * 3; }
+
+__device__ __forceinline__ void mx_ffn_loop(const char* W1, const char* W2, int n_up, int n_tt, char* smem, mx_epi_gelu gelu,
+                                            const mx_epi_ln& ln) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wid >> 2, wn = wid & 3;
+    const int xcd = (int)(blockIdx.x & 7), n_slots = (int)(gridDim.x >> 3);
+    int work = (int)(blockIdx.x >> 3);                       // token tile work * 8 + xcd
+    if (work * 8 + xcd >= n_tt) return;
+    constexpr int NK_UP = 384 / 32;
+    const int nk_dn = n_up * (MX_TM / 32);
+    const unsigned up_tile_b = NK_UP * MX_A_STAGE, x_tile_b = NK_UP * MX_B_STAGE, slot_b = (unsigned)mx_ffn_slot_bytes(nk_dn * 32);
+    const char* const X = ln.x8;
+    gelu.h8 += (size_t)blockIdx.x * slot_b;                  // this workgroup's slot: "token tile 0" of the GELU epilogue
+    const __amdgpu_buffer_rsrc_t w1_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(W1), 0, (int)((size_t)n_up * up_tile_b), 0x00020000);
+    const __amdgpu_buffer_rsrc_t w2_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(W2), 0, (int)((size_t)nk_dn * MX_A_STAGE), 0x00020000);
+    const __amdgpu_buffer_rsrc_t slot_rs = __builtin_amdgcn_make_buffer_rsrc(gelu.h8, 0, (int)slot_b, 0x00020000);
+    mx_stream S;
+    S.voff = (unsigned)lane * 16u;
+    S.wid = wid;
+    S.nk = NK_UP;
+    S.smem = smem;
+    S.ring = 0;
+    S.w_rs = S.w_rs_nxt = w1_rs;
+    S.x_cur = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(X + (size_t)(work * 8 + xcd) * x_tile_b), 0, (int)x_tile_b, 0x00020000);
+    S.x_nxt = S.x_cur;
+    S.w_cur = S.w_nxt = 0;
+    S.has_next = false;
+    S.a_off = (lane >> 5) * MX_A_PLANE + (wm * 192 + (lane & 31)) * 16;
+    S.b_off = MX_A_STAGE + (lane >> 5) * MX_B_PLANE + (wn * 32 + (lane & 31)) * 16;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        char* st_ = smem + u * MX_STAGE;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) MX_PIECE(S, k, st_, S.w_rs, S.w_cur, S.x_cur, (unsigned)u)
+    }
+    ln.prepare(smem + MX_LDS);
+    gelu.prepare(smem + MX_LDS + MX_FFN_GELU_OFF);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    MX_BAR
+    int item = 0;
+    for (bool first = true;;) {
+        const bool down = item == n_up;
+        const int tt = work * 8 + xcd;
+        if (!down) {
+            const bool to_down = item + 1 == n_up;
+            S.has_next = !(to_down && n_up == 1);            // one up tile: FFN-down's first steps would be read before they are written
+            S.w_rs_nxt = to_down ? w2_rs : w1_rs;
+            S.w_nxt = to_down ? 0u : (unsigned)(item + 1) * up_tile_b;
+            S.x_nxt = to_down ? slot_rs : S.x_cur;
+        } else {
+            const int tt_n = (work + n_slots) * 8 + xcd;
+            S.has_next = tt_n < n_tt;
+            if (S.has_next) {
+                S.w_rs_nxt = w1_rs;
+                S.w_nxt = 0;
+                S.x_nxt = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(X + (size_t)tt_n * x_tile_b), 0, (int)x_tile_b, 0x00020000);
+            }
+        }
+        f32x16 acc[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+        mx_ksteps<false, true>(acc, S, first);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // as in mx_gemm_loop: the next item's steps 0 and 1 retire before any store
+        MX_BAR
+        if (down) {
+            ln(acc, tt, 0, false, smem + MX_LDS);
+            if (!S.has_next) break;
+            work += n_slots;
+            item = 0;
+        } else {
+            gelu(acc, 0, item, false, smem + MX_LDS + MX_FFN_GELU_OFF);
+            ++item;
+        }
+        S.ring = (S.ring + S.nk) % MX_STAGES;
+        S.nk = item == n_up ? nk_dn : NK_UP;
+        S.w_rs = S.w_rs_nxt;
+        S.w_cur = S.w_nxt;
+        S.x_cur = S.x_nxt;
+        first = !S.has_next;
+        if (first) {                                         // n_up = 1, up -> down: drain the slot's stores, then a prologue for FFN-down
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            MX_BAR
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                char* st_ = smem + ((S.ring + u) % MX_STAGES) * MX_STAGE;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) MX_PIECE(S, k, st_, S.w_rs, S.w_cur, S.x_cur, (unsigned)u)
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// gelu.h8 = the slots (gridDim.x of them), gelu.nk_out = ffn / 32 = 12 n_up; ln.x8 = the residual stream: FFN-up's operand, rewritten in place
+__global__ __launch_bounds__(512) void mx_ffn_kernel(const char* __restrict__ W1, const char* __restrict__ W2, int n_up,
+                                                      const int32_t* __restrict__ m_packed, mx_epi_gelu gelu, mx_epi_ln ln) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n_tt = (m_packed[0] + MX_TN - 1) / MX_TN;
+    mx_ffn_loop(W1, W2, n_up, n_tt, smem, gelu, ln);
+}

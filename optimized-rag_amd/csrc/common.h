@@ -81,6 +81,7 @@ struct rag_options {
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
     int ce_mx = 0;                // cross-encoder forward on hi16 + lo8 operands (ce_mx.h) wherever the shape allows it: 0 = yes if the load-time probe saw it hold (cross_encoder.hip ce_probe_mx), 1 = yes, -1 = never
+    int ce_ffn_fused = 0;         // MX forward: FFN-up and FFN-down of a layer as ONE launch whose intermediate stays in per-workgroup slots (ce_mx.h mx_ffn_kernel): 0 = where the slots fit the cache (cross_encoder.hip mx_ffn_fused), 1 = always, -1 = never (two launches through h8); same bits either way
     int ce_attn_stream = 0;       // 64-wide heads, length classes above 512: 0 = the streamed attention kernel where it is the default (cross_encoder.hip launch_attention64), -1 = DIRECT everywhere above class 256, 1 = streamed at every class above 512
 };
 
@@ -216,7 +217,7 @@ struct rag_ctx : rag_device_mem {
     // persistent ones by [FUSED], the select kernel; bm25.hip: the range kernels. cross_encoder.hip: the two GEMM families, and
     // the attention instantiations by [MX operands][query blocks per wave]: every instantiation is a kernel of its own.
     int attr_dense_emit_lds[2][2][2] = {}, attr_dense_persist_lds[2] = {}, attr_dense_select_lds = 0, attr_bm25_lds = 0;
-    int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0;
+    int attr_ce_gemm_lds = 0, attr_ce_mx_lds = 0, attr_ce_ffn_lds = 0;
     int attr_ce_attn_lds[2][3] = {};
     int attr_ce_attn64_lds = 0;              // the LDS-staged instance of ce_attention64_kernel (64-wide heads)
     int attr_ce_attn64s_lds = 0;             // its streamed instance (the length classes above 512)

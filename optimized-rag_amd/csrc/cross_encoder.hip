@@ -81,6 +81,7 @@ struct ce_split_ws : ce_ws_base {
 struct ce_mx_ws : ce_ws_base {
     dev_buf<char> x8, ctx8, h8;                        // residual stream, attention output, FFN intermediate (image layout)
     dev_buf<char> xc8, cc8, hc8;                       // the same three for ONE row per pair: the [CLS] rows through the last layer's tail
+    dev_buf<char> ffn_slots;                           // fused FFN (mx_ffn_kernel): one token tile of the intermediate per workgroup; h8 / hc8 are then not allocated (mx_ensure_ffn)
     dev_buf<int32_t> m_cls;                            // device scalar: rows of the compact tensors (= pairs of the chunk)
     dev_buf<half_t> qf16, kf16, vf16;                  // Q, K, V in the attention kernel's fragment order (hi | lo planes)
 };
@@ -1689,27 +1690,47 @@ static int ce_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
 }
 
 // ---- the MX forward (ce_mx.h): every GEMM on 384-feature x 128-token tiles with hi16 + lo8 operands ---------------------
+// The FFN of a layer tail as one launch (mx_ffn_kernel) or as two (FFN-up -> h8 -> FFN-down). Option ce_ffn_fused: 1 = one launch,
+// -1 = two, 0 = one wherever every workgroup's slot of the intermediate fits the 256 MiB Infinity Cache together with the operands
+// streaming past it: at most 192 MiB of slots. (256 workgroups at ffn 1536 are 144 MiB, so every shape the MX forward takes today
+// is under the cap; it is there for a wider grid or ffn.) Either way the same bits: the choice is one of speed and workspace.
+#define MX_FFN_SLOT_CAP ((size_t)192 << 20)
+static size_t mx_ffn_slots_bytes(const rag_ctx* h, const rag_ce_model* m) { return (size_t)ce_gemm_grid(h) * mx_ffn_slot_bytes(m->cfg.ffn); }
+static bool mx_ffn_fused(const rag_ctx* h, const rag_ce_model* m) {
+    return h->opt.ce_ffn_fused > 0 || (h->opt.ce_ffn_fused == 0 && mx_ffn_slots_bytes(h, m) <= MX_FFN_SLOT_CAP);
+}
+
+// The intermediate of the FFN form in force (option ce_ffn_fused): the slots, or h8 / hc8. Only that form's buffers are allocated,
+// the other's when the option is first switched on this workspace.
+static int mx_ensure_ffn(rag_ctx* h, rag_ce_model* m, hipStream_t st) {
+    ce_mx_ws& w = m->mx;
+    int rc;
+    if (mx_ffn_fused(h, m)) return w.ffn_slots ? RAG_OK : alloc_zeroed(h, w.ffn_slots, mx_ffn_slots_bytes(h, m), st);
+    if (w.h8) return RAG_OK;
+    const size_t F = m->cfg.ffn;
+    if ((rc = alloc_zeroed(h, w.h8, (size_t)w.tokens * F * 3, st))) return rc;
+    return alloc_zeroed(h, w.hc8, (size_t)round_up((int64_t)w.pairs, MX_TN) * F * 3, st);
+}
+
 static int mx_ensure_ws(rag_ctx* h, rag_ce_model* m, int P, int L, hipStream_t st) {
     ce_mx_ws& w = m->mx;
-    if (w.fits(P, L)) return RAG_OK;
+    if (w.fits(P, L)) return mx_ensure_ffn(h, m, st);
     int rc;
     if ((rc = ws_renew(h, w, P, L, m->out_width, st))) return rc;
-    const size_t H = m->cfg.hidden, F = m->cfg.ffn, rows = (size_t)w.tokens, kv = kv_plane_halfs(w.tokens, H);
+    const size_t H = m->cfg.hidden, rows = (size_t)w.tokens, kv = kv_plane_halfs(w.tokens, H);
     const size_t cls_rows = (size_t)round_up((int64_t)P, MX_TN);
     // rows past a chunk's packed rows are read by the last token tile of every GEMM: keep them finite (zero is a valid image)
     if ((rc = alloc_zeroed(h, w.x8, rows * H * 3, st))) return rc;
     if ((rc = alloc_zeroed(h, w.ctx8, rows * H * 3, st))) return rc;
-    if ((rc = alloc_zeroed(h, w.h8, rows * F * 3, st))) return rc;
     if ((rc = alloc_zeroed(h, w.xc8, cls_rows * H * 3, st))) return rc;
     if ((rc = alloc_zeroed(h, w.cc8, cls_rows * H * 3, st))) return rc;
-    if ((rc = alloc_zeroed(h, w.hc8, cls_rows * F * 3, st))) return rc;
     if ((rc = w.m_cls.alloc(h, 1))) return rc;                         // written by every gather before it is read
     if ((rc = alloc_zeroed(h, w.qf16, 2 * kv, st))) return rc;
     if ((rc = alloc_zeroed(h, w.kf16, 2 * kv, st))) return rc;
     if ((rc = alloc_zeroed(h, w.vf16, 2 * kv, st))) return rc;
     w.pairs = P;
     w.L = L;
-    return RAG_OK;
+    return mx_ensure_ffn(h, m, st);
 }
 
 // one MX GEMM over `rows[0]` token rows of X: nk K-steps, n_ft feature tiles of W, epilogue epi
@@ -1730,12 +1751,18 @@ static void mx_qkv(rag_ctx* h, const rag_ce_model* m, const rag_ce_model::Layer&
 }
 
 // The layer after its attention, on rows[0] rows: out-projection + bias + residual + LayerNorm (attn -> x, in place), FFN-up +
-// bias + GELU (x -> ffn), FFN-down + bias + residual + LayerNorm (ffn -> x, in place)
+// bias + GELU (x -> ffn), FFN-down + bias + residual + LayerNorm (ffn -> x, in place). The two FFN GEMMs are one launch over the
+// workspace's slots (mx_ffn_kernel; `ffn` is then not touched) or two launches through `ffn` (mx_ffn_fused).
 static void mx_layer_tail(rag_ctx* h, const rag_ce_model* m, const rag_ce_model::Layer& ly, hipStream_t st, const char* attn, char* x,
                           char* ffn, const int32_t* rows) {
     const int H = m->cfg.hidden, F = m->cfg.ffn;
     const float eps = (float)m->cfg.ln_eps;
     mx_gemm(h, st, ly.wo8, attn, H / 32, 1, rows, mx_epi_ln{x, ly.bo, ly.ln1_g, ly.ln1_b, eps});
+    if (mx_ffn_fused(h, m)) {
+        launch(mx_ffn_kernel, dim3(ce_gemm_grid(h)), dim3(512), MX_FFN_LDS, st, ly.w18, ly.w28, F / MX_TM, rows,
+               mx_epi_gelu{m->mx.ffn_slots, ly.b1, F / 32}, mx_epi_ln{x, ly.b2, ly.ln2_g, ly.ln2_b, eps});
+        return;
+    }
     mx_gemm(h, st, ly.w18, x, H / 32, F / MX_TM, rows, mx_epi_gelu{ffn, ly.b1, F / 32});
     mx_gemm(h, st, ly.w28, ffn, F / 32, 1, rows, mx_epi_ln{x, ly.b2, ly.ln2_g, ly.ln2_b, eps});
 }
@@ -1747,6 +1774,7 @@ static int mx_forward_chunk(rag_ctx* h, rag_ce_model* m, const ce_chunk& c, hipS
     int rc;
     if ((rc = raise_lds(h, h->attr_ce_mx_lds, MX_KERNEL_LDS, mx_gemm_kernel<mx_epi_qkv>, mx_gemm_kernel<mx_epi_gelu>, mx_gemm_kernel<mx_epi_ln>)))
         return rc;
+    if ((rc = raise_lds(h, h->attr_ce_ffn_lds, MX_FFN_LDS, mx_ffn_kernel))) return rc;
     // A classifier packs its GEMM rows in fours: only attention needs a pair on whole 16-row tiles (its Q / K / V fragments), the GEMMs
     // work on 128-row image tiles wherever a pair starts, and the V epilogue stores four consecutive keys per lane. Every GEMM,
     // LayerNorm, GELU and embedding row between a length rounded up to 4 and to 16 is work no result needs. An embedding model keeps
