@@ -32,7 +32,7 @@
  *     rag_tokvec_append_host, rag_tokvec_reserve_form, rag_tokvec_load_form_host,
  *     rag_bm25_append_host, rag_bm25_fold, rag_bm25_live_counts_host, rag_bm25_set_statistics_host, rag_bm25_refresh,
  *     rag_sparse_append_host, rag_sparse_fold, rag_index_compact_bm25, rag_index_compact_live, rag_index_load_host, rag_index_reserve,
- *     rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
+ *     rag_index_id_map, rag_ce_load_host, rag_embed_load_host, the live writes) returns the result
  *     from before it, and the same call made afterwards the new one. rag_bm25_set_normalize, rag_set_option and
  *     rag_ce_set_pair_format do not
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
@@ -195,6 +195,49 @@ int rag_index_compact(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out)
 int rag_index_compact_bm25(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
 int rag_index_compact_live(rag_handle_t h, int64_t* row_map_out, int64_t* n_rows_out);
 int rag_index_deleted_rows(rag_handle_t h, int64_t* n_deleted_out);
+
+/* ---- id-to-row map: "which of my rows has this id?" on the device, for an index with explicit ids (the primary keys of a row
+ *      shard that takes live writes). No reference counterpart: the reference asks PostgreSQL's primary-key index.
+ * An open-addressing hash table in HBM with linear probing, an int64 key plane and an int32 row plane:
+ *     home(id) = ((uint64_t)id * 0x9E3779B97F4A7C15) >> (64 - log2(slots))
+ * slots is a power of two, at least 128 and at least twice the row capacity of the index, so live keys + tombstones stay at or
+ * below slots / 2. Keys are ids >= 0 (-1 pads every list); an unused slot holds INT64_MIN. Erasing an id leaves a tombstone - the
+ * key stays, its row becomes -1 - so probe chains stay intact, and inserting that id again takes its slot back. Which slot a key
+ * occupies may depend on the order of the device's atomics; no lookup result does.
+ *
+ * rag_index_id_map: a host write (takes the lock, waits for queued *_dev work). enable = 1 builds the map now from the stored ids
+ * of the live rows and keeps it maintained; enable = 0 frees it. On an index with implicit ids the call is legal and builds
+ * nothing: lookups there are arithmetic on id_base. The build also decides ids_ascending: whether the ids of the live rows are
+ * strictly ascending with the rows (implicit ids are). A duplicate live id or a negative id: RAG_ERR_ARG, the message names the
+ * id, the map stays disabled. RAG_ERR_NOMEM changes nothing.
+ * Maintenance, inside the existing writes, whose atomicity is unchanged: rag_index_insert_host adds the block's ids (ids must be
+ * >= 0 while the map is enabled); when live keys + tombstones + n would pass slots / 2, or the grown row capacity asks for more
+ * slots, a new table is allocated BEFORE anything is committed (a failed insert leaves index and map as they were) and built
+ * from the whole id column afterwards - a rebuild, which also drops the tombstones; ids_ascending stays 1 only if the block
+ * ascends and its first id is above the id of the last live row. rag_index_delete_host erases the ids it deleted. Every
+ * rag_index_compact* and rag_index_set_ids_host rebuild the map and decide ids_ascending anew (between rebuilds it only ever goes
+ * from 1 to 0); a duplicate or negative id given to rag_index_set_ids_host while the map is enabled: RAG_ERR_ARG, the ids are
+ * set and the map is disabled. rag_index_load_* and rag_index_reserve replace the index and drop the map.
+ * rag_index_append_host / _dev (rows of a reserved index, which carry no ids) leave the map as it is: the appended rows are unknown
+ * to it, and entries does not count them, until rag_index_set_ids_host gives every row an id and rebuilds it.
+ * With the map disabled every other entry makes exactly the launches it made without this section.
+ *
+ * rag_index_rows_of_ids_dev / _host: rows_out[i] = the row of ids[i], -1 for an unknown id, an id whose row is deleted, or a
+ * negative id. One lane per id; a probe stops at the first unused slot. An index with explicit ids and no map: RAG_ERR_STATE. An
+ * index with implicit ids: id - id_base where that is a live row. The _dev form is asynchronous on `stream` and ordered as the
+ * preamble says.
+ *
+ * rag_index_id_map_info: host state only, waits for nothing. entries = live keys; longest_probe = the longest chain walked by
+ * the last build or insert (1 = every key at home); hbm_bytes = 12 * slots; rebuilds counts the rebuilds since the map was
+ * enabled. Implicit ids: slots = entries = 0, ids_ascending = 1. Disabled: all zero. */
+typedef struct rag_id_map_info {
+    int32_t enabled, ids_ascending;
+    int64_t slots, entries, tombstones, longest_probe, hbm_bytes, rebuilds;
+} rag_id_map_info;
+int rag_index_id_map(rag_handle_t h, int enable);
+int rag_index_rows_of_ids_dev(rag_handle_t h, const int64_t* ids_dev, int64_t n, int32_t* rows_out_dev, void* stream);
+int rag_index_rows_of_ids_host(rag_handle_t h, const int64_t* ids_host, int64_t n, int32_t* rows_out_host);
+int rag_index_id_map_info(rag_handle_t h, rag_id_map_info* out);
 /* copy rows' fp32 embeddings back (kills apply_mmr's per-doc re-embedding, rag/nodes/helpers.py:215-223) */
 int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, float* out_host);
 
@@ -983,8 +1026,12 @@ int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* t
  *   bits (colbert: the float32 pair score widened) from the launches rag_m3_score_rows_dev uses, on row = id - id_base; an unowned
  *   slot carries 0 | 0.0 | 0.0 | 0.0. Weights as rag_m3_score_rows_dev: a weight of 0 computes nothing, writes 0.0 and requires
  *   neither its query arrays nor its resident structure. Limits: 1 <= n_queries <= 65535, 0 < slots <= 256, n_queries * slots <
- *   2^24. RAG_ERR_STATE on an index with explicit ids (rag_index_set_ids_host, or ids at the load): ownership is defined through
- *   id_base alone; the other errors are those of rag_m3_score_rows_dev. Row visibility is not looked at: the candidate searches hid
+ *   2^24. An index with explicit ids (rag_index_set_ids_host, or ids at the load) is accepted when its id map is enabled
+ *   (rag_index_id_map) and ids_ascending holds: a slot is then OWNED iff the map holds the id and its row is live, and row = the
+ *   map's row; one lookup launch takes the place of the id_base arithmetic, every other launch is the same. Without the map:
+ *   RAG_ERR_STATE (ownership is defined through id_base alone); with the map but ids that do not ascend with the rows:
+ *   RAG_ERR_STATE, the message says so (the merges over shards break ties by lower id, the local searches by lower row; the two
+ *   agree exactly when ids ascend with rows on every shard). The other errors are those of rag_m3_score_rows_dev. Row visibility is not looked at: the candidate searches hid
  *   what is hidden. With w_dense == 0 and w_sparse == 0 the call is the late-interaction rerank: a slot MaxSim leaves empty (the
  *   query or the document has no token vectors) is reported UNOWNED, so the combine skips it as the top-k of rag_retrieve_maxsim_dev
  *   does. This is the one place where the three entries differ from rag_retrieve_m3_dev, which at weights (0, 0, w) ranks such a
@@ -1034,8 +1081,8 @@ int rag_m3_combine_gathered_dev(rag_handle_t h, const int64_t* cand_ids_dev, con
  *   included), a device-pointer index load or append, or rag_hybrid_linear_dev / _tenants_dev, which reuse the workspace.
  *   Other *_dev calls may come in between.
  * Both: argument checks are rag_hybrid_linear_dev's (alpha > 0, finite weights, 0 < k <= 256, fresh row-aligned postings, a
- *   loaded tenant table for a tenant >= 0); RAG_ERR_STATE on an index with explicit ids, as rag_m3_score_ids_dev: the order
- *   across shards is defined through id_base. The handle stays usable after every error.
+ *   loaded tenant table for a tenant >= 0); an index with explicit ids under the gate of rag_m3_score_ids_dev: accepted with
+ *   the id map enabled and ids_ascending (no lookup is made, only the order is needed), else RAG_ERR_STATE. The handle stays usable after every error.
  * rag_hybrid_linear_merge_gathered_dev: gathered_dev [world][5][n_queries][k] int64, every rank's partial_out. The global top-k
  *   by (hybrid desc, id asc), -1 slots skipped wherever they stand, each winner's three components copied with it; outputs
  *   [n_queries][k], padded -1 / 0.0; semantic / keyword / temporal_out_dev may be NULL. Needs no index. world * k <= 4092 (the

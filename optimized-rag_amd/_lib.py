@@ -36,6 +36,11 @@ class RowBlock(C.Structure):
                 ("tokens", C.c_void_p), ("token_lens", C.c_void_p)]
 
 
+class IdMapInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("ids_ascending", C.c_int32)] + \
+               [(k, C.c_int64) for k in ("slots", "entries", "tombstones", "longest_probe", "hbm_bytes", "rebuilds")]
+
+
 class Bm25Segments(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("base_docs", "tail_docs", "base_nnz", "tail_nnz", "n_terms", "tail_bytes", "appends", "folds")]
 
@@ -85,6 +90,10 @@ _SIGS = {
     "rag_index_compact_bm25": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_compact_live": ([_P, _P, C.POINTER(C.c_int64)], C.c_int),
     "rag_index_deleted_rows": ([_P, C.POINTER(C.c_int64)], C.c_int),
+    "rag_index_id_map": ([_P, C.c_int], C.c_int),
+    "rag_index_rows_of_ids_dev": ([_P, _P, C.c_int64, _P, _P], C.c_int),
+    "rag_index_rows_of_ids_host": ([_P, _P, C.c_int64, _P], C.c_int),
+    "rag_index_id_map_info": ([_P, C.POINTER(IdMapInfo)], C.c_int),
     "rag_dense_topk_host": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P], C.c_int),
     "rag_dense_topk_dev": ([_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "rag_dense_last_stats": ([_P, C.POINTER(DenseStats)], C.c_int),
@@ -451,6 +460,32 @@ class RagEngine:
         out = C.c_int64()
         self._check(self.lib.rag_index_deleted_rows(self.h, C.byref(out)), "rag_index_deleted_rows")
         return int(out.value)
+
+    # ---- id-to-row map (include/rag_hip.h rag_index_id_map) ----------------------------------------------------------------
+    def index_id_map(self, enable=True):
+        """Build the device id-to-row map of an index with explicit ids and keep it maintained through the writes (False frees it)."""
+        self._check(self.lib.rag_index_id_map(self.h, 1 if enable else 0), "rag_index_id_map")
+
+    def index_id_map_info(self):
+        s = IdMapInfo()
+        self._check(self.lib.rag_index_id_map_info(self.h, C.byref(s)), "rag_index_id_map_info")
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def rows_of_ids(self, ids):
+        """The live row of each doc id (int32, -1 = unknown, deleted or negative id); host arrays."""
+        ids = _np(np.atleast_1d(ids), np.int64)
+        out = np.empty(ids.shape, dtype=np.int32)
+        self._check(self.lib.rag_index_rows_of_ids_host(self.h, _ptr(ids), ids.size, _ptr(out)), "rag_index_rows_of_ids_host")
+        return out
+
+    def rows_of_ids_dev(self, ids, rows_out, stream=None):
+        """torch CUDA tensors (int64 in, int32 out, same number of elements); asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        assert ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous()
+        assert rows_out.is_cuda and rows_out.dtype == torch.int32 and rows_out.is_contiguous() and rows_out.numel() == ids.numel()
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._check(self.lib.rag_index_rows_of_ids_dev(self.h, C.c_void_p(ids.data_ptr()), ids.numel(), C.c_void_p(rows_out.data_ptr()), st),
+                    "rag_index_rows_of_ids_dev")
 
     def dense_topk(self, queries, k, tenant=-1):
         """queries [Q, dim] float32 (numpy). Returns (ids int64 [Q,k], rows int32 [Q,k], scores float64 [Q,k])."""
@@ -1387,7 +1422,7 @@ class RagEngine:
 
     def m3_score_ids_dev(self, cand_ids, partial_out, q_emb=None, term_ptr=None, terms=None, weights=None, q_vecs=None, q_off=None,
                          w=(0.4, 0.2, 0.4), stream=None):
-        """The three components of the candidate ids [Q, slots] int64 whose rows this handle holds (id_base <= id < id_base + rows)
+        """The three components of the candidate ids [Q, slots] int64 whose rows this handle holds (id_base <= id < id_base + rows; explicit ids: the id map's answer, index_id_map)
         -> partial_out [4, Q, slots] int64 = owned flag | dense | sparse | colbert (float64 bits; 0 / 0.0 for a slot of another
         rank). A weight of 0 leaves its component - and its inputs - out."""
         import torch

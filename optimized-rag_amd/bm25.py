@@ -182,14 +182,22 @@ class Bm25Postings:
         V = self.indptr.shape[0] - 1
         term_of = np.repeat(np.arange(V, dtype=np.int64), np.diff(self.indptr))
         df = np.bincount(term_of[live[self.doc]], minlength=V).astype(np.int64)
+        self.idf, self._frozen_mean = self.idf_of_counts(df, n, self.epsilon)
+        self.avgdl = int(self.doc_len[live].sum()) / n
+        return self
+
+    @staticmethod
+    def idf_of_counts(df, n_docs, epsilon=EPSILON):
+        """The idf rule of `refresh` / rag_bm25_refresh from document frequencies alone (row shards sum theirs: sharded.py
+        ShardedHybridIndex.refresh_statistics): df int64 [terms] over n_docs live documents -> (idf float64 [terms], mean)."""
+        df = np.asarray(df, dtype=np.int64)
+        n = int(n_docs)
         occ = df > 0
         udf, inv = np.unique(df, return_inverse=True)
-        idf = np.array([math.log(n - int(d) + 0.5) - math.log(int(d) + 0.5) for d in udf], dtype=np.float64)[inv]
+        idf = np.array([math.log(n - int(d) + 0.5) - math.log(int(d) + 0.5) for d in udf], dtype=np.float64)[inv.reshape(-1)] \
+            if df.size else np.zeros(0, dtype=np.float64)
         mean = float(np.cumsum(idf[occ])[-1]) / int(occ.sum()) if occ.any() else 0.0
-        self.idf = np.where(occ & (idf < 0), self.epsilon * mean, idf)
-        self.avgdl = int(self.doc_len[live].sum()) / n
-        self._frozen_mean = mean
-        return self
+        return np.where(occ & (idf < 0), epsilon * mean, idf), mean
 
     def refresh_on(self, engine, live=None):
         """`RagEngine.bm25_refresh` on the device and `refresh` on this mirror; the two idf tables must agree bit for bit.

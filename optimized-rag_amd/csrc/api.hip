@@ -283,11 +283,24 @@ int rag_index_set_ids_host(rag_handle_t h, const int64_t* ids, int64_t n_rows) {
     LOCK(h);
     ARG_CHECK(h, n_rows == h->n_rows, "id array length must equal the index row count");
     HOST_ENTRY(h);
+    const bool stored = ids != nullptr && n_rows > 0;
+    idmap_table map;                    // an enabled id map is rebuilt from the new column: its table before anything changes
+    if (stored && idmap_must_rebuild(h, 0, std::max(emb32_rows(h), n_rows), true))
+        if (int rc = idmap_prepare(h, std::max(emb32_rows(h), n_rows), &map)) return rc;
     h->ids.reset();
-    if (ids == nullptr || n_rows == 0) return RAG_OK;
-    if (int rc = h->ids.alloc(h, (size_t)n_rows)) return rc;
-    HIP_TRY(h, hipMemcpy(h->ids, ids, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice));
-    return RAG_OK;
+    if (stored) {
+        int rc = h->ids.alloc(h, (size_t)n_rows);
+        if (rc == RAG_OK && hipMemcpy(h->ids, ids, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
+            h->err = "set_ids: the copy of the id column failed";
+            rc = RAG_ERR_HIP;
+        }
+        if (rc) {                       // the id column is gone or undefined: a map of the old one must not outlive it
+            h->ids.reset();
+            idmap_drop(h);
+            return rc;
+        }
+    }
+    return idmap_rebuild(h, &map);
 }
 
 int rag_index_rows(rag_handle_t h, int64_t* n_rows_out) {
@@ -917,12 +930,11 @@ int rag_hybrid_linear_batch(rag_handle_t h, int* max_queries_out) {
     return RAG_OK;
 }
 
-// what begin and finish share beyond the one-call entries' checks: one sub-batch, ids through id_base
+// what begin and finish share beyond the one-call entries' checks: one sub-batch, ids through id_base - or explicit ids that the
+// id map vouches for (idmap.hip: enabled, and the ids ascend with the rows; the order is all that is needed here)
 static int linear_check_shard(rag_ctx* h, const char* who, int Q) {
-    if (h->ids != nullptr) {
-        h->err = std::string(who) + ": the index has explicit ids; a row shard is loaded with id_base (the order across shards is id_base + row)";
-        return RAG_ERR_STATE;
-    }
+    if (int rc = idmap_shard_gate(h, who, ": the index has explicit ids; a row shard is loaded with id_base (the order across shards is id_base + row)"))
+        return rc;
     const int QB = linear_batch(h->n_rows);
     if (Q > QB) {
         h->err = "bad argument: " + std::string(who) + ": n_queries " + std::to_string(Q) + " exceeds the sub-batch of this index, " +

@@ -111,6 +111,10 @@ struct rag_index_mem {
     // live writes (live.hip). vis[row] = the row's tenant (0 without a tenant table) or RAG_DEAD_ROW once deleted; null while
     // nothing is deleted, so the search kernels keep their unfiltered path.
     dev_buf<int32_t> vis;
+    // id-to-row map (idmap.hip, rag_index_id_map): open addressing over [slots] keys and rows, and its device counters
+    dev_buf<int64_t> idmap_keys;     // [slots] id, or IDMAP_EMPTY
+    dev_buf<int32_t> idmap_rows;     // [slots] row of the key, -1 = erased (a tombstone: the key stays)
+    dev_buf<unsigned long long> idmap_stat;      // [IDMAP_STAT_WORDS]
 };
 // ... and everything else (dropped by rag_destroy, with the index planes)
 struct rag_device_mem : rag_index_mem {
@@ -177,6 +181,13 @@ struct rag_ctx : rag_device_mem {
     // live writes (live.hip). The row capacity of a plane is not kept here: it is its buffer's element count over its row
     // width (plane_rows and the row-plane list below), 0 for a plane that is absent.
     int64_t n_deleted = 0;
+    // id-to-row map (idmap.hip): on = rag_index_id_map(h, 1) was called and every write keeps the map current. The table itself
+    // (rag_index_mem::idmap_keys) exists only while the index stores explicit ids; slots == 0 without it.
+    struct idmap_state {
+        bool on = false;
+        bool ascending = true;       // the ids of the live rows ascend strictly with the rows (implicit ids always do)
+        int64_t slots = 0, entries = 0, tombstones = 0, longest_probe = 0, rebuilds = 0;
+    } idmap;
     bool bm25_stale = false;     // rows were inserted or compacted since the postings were loaded: BM25 entry points refuse
     bool bm25_compacted = false; // ... and a compaction was among them: appended postings cannot align the rows again, only a reload
 
@@ -481,6 +492,24 @@ int dense_tenant_tiles_append(rag_ctx* h, const int32_t* tenants_host, int64_t f
 int live_vis_rebuild(rag_ctx* h);
 int bm25_fresh(rag_ctx* h);            // RAG_ERR_STATE while the postings are stale (inserts / compaction since the last load)
 int live_vis_extend(rag_ctx* h, int64_t first_row, int64_t n);
+// idmap.hip: the id-to-row map through the writes. A write that may need a larger (or a first) table allocates it with
+// idmap_prepare BEFORE it commits anything (RAG_ERR_NOMEM: nothing changed) and hands it to idmap_rebuild afterwards; every
+// function is a no-op while the map is disabled.
+#define IDMAP_EMPTY ((int64_t)0x8000000000000000ull)     // an unused slot: no key (ids >= 0) equals it
+#define IDMAP_STAT_WORDS 8
+struct idmap_table { dev_buf<int64_t> keys; dev_buf<int32_t> rows; int64_t slots = 0; };
+int64_t idmap_slots_for(int64_t row_capacity);
+bool idmap_must_rebuild(const rag_ctx* h, int64_t n_new, int64_t row_capacity_after, bool explicit_after);
+int idmap_prepare(rag_ctx* h, int64_t row_capacity, idmap_table* t);
+int idmap_rebuild(rag_ctx* h, idmap_table* t);           // from the id plane and vis; t may be null or empty: in place
+int idmap_insert_rows(rag_ctx* h, int64_t first_row, int64_t n, bool block_ascending);
+int idmap_erase_deleted(rag_ctx* h, const int64_t* set_dev, int n_set);
+void idmap_drop(rag_ctx* h);
+// rows_out[i] = the live row of ids[i] or -1; owned (may be null) = 1 / 0 as int64. Explicit ids go through the map
+// (RAG_ERR_STATE without one), implicit ids through id_base
+int idmap_rows_of_ids(rag_ctx* h, const int64_t* ids_dev, int64_t n, int32_t* rows_out, int64_t* owned, hipStream_t st);
+// what the entries that merge shards by id ask of an index with explicit ids: the map, and ids that ascend with the rows
+int idmap_shard_gate(rag_ctx* h, const char* who, const char* refusal_without_map);
 // postings through a compaction (rag_index_compact_bm25): built beside the resident ones from the device row map before any
 // row moves, swapped in (or dropped) afterwards
 // (ix / slot: the BM25 postings rag_ctx::bm25 or the learned-sparse postings rag_ctx::sparse)

@@ -1099,6 +1099,7 @@ int dense_free(rag_ctx* h) {
     static_cast<rag_index_mem&>(*h) = rag_index_mem();        // every plane of the index
     h->tenant_span.clear(); h->tenant_lists.clear(); h->tenant_rows = 0;
     h->n_deleted = 0;
+    h->idmap = {};                                            // (its table went with the planes)
     h->bm25_stale = false;
     h->bm25_compacted = false;
     h->sparse_stale = false;

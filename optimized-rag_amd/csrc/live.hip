@@ -158,14 +158,16 @@ static int stage_id_set(rag_ctx* h, const std::vector<int64_t>& set, int64_t** s
     return RAG_OK;
 }
 
-// visible rows whose id is in `set` (sorted, unique); mark = 1 deletes them
-static int id_set_apply(rag_ctx* h, const std::vector<int64_t>& set, int tenant, int mark, int64_t* n_out) {
+// visible rows whose id is in `set` (sorted, unique); mark = 1 deletes them. set_dev_out (may be null): where the set was staged
+static int id_set_apply(rag_ctx* h, const std::vector<int64_t>& set, int tenant, int mark, int64_t* n_out, const int64_t** set_dev_out = nullptr) {
     *n_out = 0;
+    if (set_dev_out) *set_dev_out = nullptr;
     if (set.empty() || h->n_rows == 0) return RAG_OK;
     int64_t* sd = nullptr;
     unsigned long long* cd = nullptr;
     int rc = stage_id_set(h, set, &sd, &cd);
     if (rc) return rc;
+    if (set_dev_out) *set_dev_out = sd;
     if (h->ids)
         hipLaunchKernelGGL(live_idset_scan_kernel, dim3(grid_for(h->n_rows)), dim3(256), 0, h->stream, h->ids, h->n_rows, sd, (int)set.size(),
                            h->vis, tenant, mark, cd);
@@ -191,6 +193,7 @@ struct insert_job {
     double tmax = 0.0;                   // max |temporal score| of the block
     std::vector<uint16_t> tok16;         // the block's token ids narrowed: bits 0-15 ...
     std::vector<uint8_t> tok_hi8;        // ... and bits 16-23, for a 24-bit store
+    bool ids_ascend = true;              // the block's ids ascend strictly (what the id map's ids_ascending asks of it)
 };
 
 // phase 1: the block brings exactly the planes the index has (an empty index may be started), and those cover its rows
@@ -244,6 +247,9 @@ static int insert_convert(rag_ctx* h, insert_job& in) {
         }
     }
     if (rb->ids) {
+        for (int64_t i = 1; i < n; ++i) in.ids_ascend = in.ids_ascend && rb->ids[i - 1] < rb->ids[i];
+        if (h->idmap.on)
+            for (int64_t i = 0; i < n; ++i) ARG_CHECK(h, rb->ids[i] >= 0, "insert: ids must be >= 0 while the id map is enabled");
         std::vector<int64_t> set(rb->ids, rb->ids + n);
         std::sort(set.begin(), set.end());
         ARG_CHECK(h, std::adjacent_find(set.begin(), set.end()) == set.end(), "insert: an id is repeated inside the block");
@@ -581,6 +587,9 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, i
         h->err = "compact: the stored ids do not cover the index rows";
         return RAG_ERR_STATE;
     }
+    // an enabled id map is rebuilt from the moved id column; an implicit-id index gets its first table here, before any row moves
+    idmap_table map;
+    if (h->idmap.on && !h->idmap_keys && (rc = idmap_prepare(h, std::max(emb32_rows(h), n0), &map))) return rc;
     // doc ids never change: an implicit-id index stores its ids before any row moves
     if (!h->ids) {
         if ((rc = h->ids.alloc(h, (size_t)std::max(emb32_rows(h), n0)))) return rc;
@@ -593,6 +602,7 @@ static int live_compact(rag_ctx* h, int64_t* row_map_out, int64_t* n_rows_out, i
     if ((rc = compact_prepare(h, c))) return rc;
     if ((rc = compact_move_planes(h, c, row_map_out))) return rc;
     if ((rc = compact_publish(h, c))) return rc;
+    if ((rc = idmap_rebuild(h, &map))) return rc;
     if (n_rows_out) *n_rows_out = c.n_live;
     return RAG_OK;
 }
@@ -614,9 +624,15 @@ int rag_index_insert_host(rag_handle_t h, const rag_row_block* rb, int64_t* firs
     if ((rc = insert_convert(h, in))) return rc;
     rag_device_mem g;                    // the grown planes: dropped whole unless moved into the handle
     if ((rc = insert_grow(h, in, &g))) return rc;
+    // an enabled id map that has no room for the block (or no table yet) gets its new table now, while nothing has changed
+    idmap_table map;
+    const int64_t cap_after = grow_cap(std::max(emb32_rows(h), in.n0), in.need);
+    const bool map_rebuild = idmap_must_rebuild(h, in.n, cap_after, rb->ids != nullptr || h->ids != nullptr);
+    if (map_rebuild && (rc = idmap_prepare(h, cap_after, &map))) return rc;
     if ((rc = insert_start_index(h))) return rc;
     if ((rc = insert_move_in(h, in, &g))) return rc;
-    return insert_write(h, in);
+    if ((rc = insert_write(h, in))) return rc;
+    return map_rebuild ? idmap_rebuild(h, &map) : idmap_insert_rows(h, in.n0, in.n, in.ids_ascend);
 }
 
 int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int tenant, int64_t* n_deleted_out) {
@@ -642,7 +658,9 @@ int rag_index_delete_host(rag_handle_t h, const int64_t* ids, int64_t n_ids, int
     const bool created = h->vis == nullptr;
     if (created && (rc = live_vis_extend(h, 0, h->n_rows))) return rc;
     int64_t n_del = 0;
-    if ((rc = id_set_apply(h, set, tenant, 1, &n_del))) return rc;
+    const int64_t* set_dev = nullptr;
+    if ((rc = id_set_apply(h, set, tenant, 1, &n_del, &set_dev))) return rc;
+    if (n_del > 0 && (rc = idmap_erase_deleted(h, set_dev, (int)set.size()))) return rc;
     if (created && n_del == 0) h->vis.reset();       // nothing deleted: keep the searches on their unfiltered path
     h->n_deleted += n_del;
     if (n_deleted_out) *n_deleted_out = n_del;

@@ -655,7 +655,7 @@ int retrieve_m3_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_
 //   gather 1  [world][4][Q][pool]  every rank's dense ids | cosine bits | sparse ids | raw sparse score bits
 //   m3_candidates_gathered_dev     two merges (merge_topk_kernel: -1 skipped wherever it stands, nothing normalised), then the candidate
 //                                  list of candidate_stage in ID space: RRF sees the two merged lists, which are the unsharded lists
-//   m3_score_ids_dev               ids -> rows of this handle (m3_own_rows_kernel), the three component launches of m3_score_slots over
+//   m3_score_ids_dev               ids -> rows of this handle (m3_own_rows_kernel; explicit ids: the id map, idmap.hip), the three component launches of m3_score_slots over
 //                                  the owned slots, packed as [4][Q][S] int64 (m3_pack_partial_kernel)
 //   gather 2  [world][4][Q][S]
 //   m3_combine_gathered_dev        m3_combine_topk_kernel with every slot's components taken from the rank that owns it
@@ -725,17 +725,20 @@ int m3_score_ids_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr
     ARG_CHECK(h, cand_ids_dev && partial_out, "m3_score_ids: null argument");
     const m3_weights w = {w_dense, w_sparse, w_colbert};
     if (int rc = m3_check(h, "m3_score_ids", w, q_emb_dev, term_ptr_dev, qweights_dev, q_vecs_dev, q_off_dev)) return rc;
-    if (h->ids != nullptr) {
-        h->err = "m3_score_ids: the index has explicit ids; a row shard is loaded with id_base (ownership is id_base <= id < id_base + rows)";
-        return RAG_ERR_STATE;
-    }
+    if (int rc = idmap_shard_gate(h, "m3_score_ids", ": the index has explicit ids; a row shard is loaded with id_base (ownership is id_base <= id < id_base + rows)"))
+        return rc;
     const size_t P = (size_t)Q * S;
     int32_t* rows;
     double *dn, *sp;
     if (int rc = pipe_ws_carve(h, [&](ws_carve& c) { rows = c.take<int32_t>(P); dn = c.take<double>(P); sp = c.take<double>(P); })) return rc;
     const dim3 grid((unsigned)((P + 255) / 256));
-    launch(m3_own_rows_kernel, grid, dim3(256), 0, st, cand_ids_dev, (int64_t)P, h->id_base, h->n_rows, rows, partial_out);
     int rc;
+    // explicit ids (the gate passed: the id map is enabled): owned = the map holds the id and its row is live (idmap.hip)
+    if (h->ids != nullptr) {
+        if ((rc = idmap_rows_of_ids(h, cand_ids_dev, (int64_t)P, rows, partial_out, st))) return rc;
+    } else {
+        launch(m3_own_rows_kernel, grid, dim3(256), 0, st, cand_ids_dev, (int64_t)P, h->id_base, h->n_rows, rows, partial_out);
+    }
     const float* cb = nullptr;
     const int32_t* scored = nullptr;
     if (w.colbert > 0.0 && (rc = tokvec_score_slots(h, q_vecs_dev, q_off_dev, rows, Q, S, &cb, &scored, st))) return rc;

@@ -19,10 +19,12 @@ the GPU box, "gloo" in CPU tests) is plumbing only (buffers, process group, the 
 bound RCCL behind the C-ABI); every piece of arithmetic on the gathered lists is a HIP kernel of the library. The payload is Q*k*16 B per rank
 (327 KB at Q=1024, k=20): latency-bound, so one fused gather of both arrays rather than two collectives.
 """
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from ._lib import _tenant_arg
+from .bm25 import Bm25Postings
 
 
 def shard_bounds(n_rows, world):
@@ -44,9 +46,133 @@ class ShardedDenseIndex:
         self.rank = rank if rank is not None else (dist.get_rank(group) if dist.is_initialized() else 0)
         self._bufs = {}
 
-    def load_shard(self, emb_shard, first_global_row):
-        """emb_shard: this rank's rows; doc ids become first_global_row + local row."""
-        self.engine.index_load(emb_shard, id_base=int(first_global_row))
+    def load_shard(self, emb_shard, first_global_row, ids=None):
+        """emb_shard: this rank's rows; doc ids become first_global_row + local row. With `ids` (int64, one per row, strictly
+        ascending - else ValueError) the shard stores them as explicit ids and enables the device id-to-row map
+        (RagEngine.index_id_map): such a shard takes the writes below, and first_global_row is not used."""
+        if ids is None:
+            self.engine.index_load(emb_shard, id_base=int(first_global_row))
+            self._explicit = False
+            self._local_max_id = int(first_global_row) + int(emb_shard.shape[0]) - 1
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.shape != (emb_shard.shape[0],) or (ids.size and int(ids[0]) < 0) or not (np.diff(ids) > 0).all():
+                raise ValueError("load_shard: ids must be one id >= 0 per row, strictly ascending on the shard")
+            self.engine.index_load(emb_shard, ids=ids)
+            self.engine.index_id_map(True)
+            self._explicit = True
+            self._local_max_id = int(ids[-1]) if ids.size else -1
+        self._layout = None
+
+    # ---- writes on shards. SPMD calls, like the searches: every rank makes the same call with the same arguments. What every
+    # rank knows about the others is one small record, the LAYOUT: each rank's row count, the largest id anywhere and the number
+    # of keyword terms known anywhere. It is agreed by one gather of three int64 per rank at the first write after a load and
+    # after compact(); in between every rank updates its copy by the same rule, with no collective. local_layout / agree_layout
+    # are the halves on each side of that gather, so that one process can stand in for several ranks.
+    def _local_terms(self):
+        return 0
+
+    def _rows_changed(self):
+        """A write changed this rank's or another rank's row count (a hook for what a subclass agreed on from the counts)."""
+
+    def local_layout(self):
+        """This rank's share of the layout: [rows, largest id (-1 without rows), keyword terms known]."""
+        return [int(self.engine.n_rows), int(self._local_max_id), int(self._local_terms())]
+
+    def agree_layout(self, all_layouts):
+        """all_layouts: every rank's local_layout(), in rank order."""
+        if len(all_layouts) != self.world:
+            raise ValueError(f"agree_layout: expected {self.world} layouts, got {len(all_layouts)}")
+        self._layout = dict(rows=[int(l[0]) for l in all_layouts], max_id=max(int(l[1]) for l in all_layouts),
+                            terms=max(int(l[2]) for l in all_layouts))
+        return self._layout
+
+    def _gather_numbers(self, mine):
+        """[world, len(mine)] int64 on the host: one gather of a few numbers per rank."""
+        if self.world == 1:
+            return [list(mine)]
+        dev = torch.device("cuda", self.engine.device)
+        send = torch.tensor(list(mine), dtype=torch.int64, device=dev)
+        recv = torch.empty((self.world, send.shape[0]), dtype=torch.int64, device=dev)
+        _gather(recv, send, self.group, self.engine)
+        return recv.tolist()
+
+    def layout(self):
+        if getattr(self, "_layout", None) is None:
+            self.agree_layout(self._gather_numbers(self.local_layout()))
+        return self._layout
+
+    @staticmethod
+    def owner_of(rows_per_rank):
+        """The owner policy: the rank with the fewest rows, ties to the lowest rank. A function of the layout alone."""
+        rows = [int(r) for r in rows_per_rank]
+        return rows.index(min(rows))
+
+    def _check_block(self, emb, ids, owner):
+        """What must hold before ANY rank changes anything -> (ids int64, owner, the owner's first new row)."""
+        if not getattr(self, "_explicit", False):
+            raise ValueError("insert_rows: the shard was loaded without ids (load_shard(..., ids=...))")
+        lay = self.layout()
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int64)
+        n = int(np.asarray(emb).shape[0]) if np.ndim(emb) == 2 else 1
+        if ids.shape != (n,) or n == 0:
+            raise ValueError(f"insert_rows: need one id per row, got {ids.shape} for {n} rows")
+        if not (np.diff(ids) > 0).all():
+            raise ValueError("insert_rows: ids must be strictly ascending")
+        if int(ids[0]) <= lay["max_id"]:
+            raise ValueError(f"insert_rows: ids must be above the largest id of the index, {lay['max_id']} (got {int(ids[0])})")
+        if owner is None:
+            owner = self.owner_of(lay["rows"])
+        if not 0 <= int(owner) < self.world:
+            raise ValueError(f"insert_rows: owner {owner} is no rank of {self.world}")
+        return ids, int(owner), lay["rows"][int(owner)]
+
+    def _block_done(self, ids, owner, n_terms_total=None):
+        lay = self._layout
+        lay["rows"][owner] += int(ids.shape[0])
+        lay["max_id"] = int(ids[-1])
+        if n_terms_total is not None:
+            lay["terms"] = max(lay["terms"], int(n_terms_total))
+        if owner == self.rank:
+            self._local_max_id = int(ids[-1])
+        self._rows_changed()
+
+    def insert_rows(self, emb, ids, tenants=None, temporal=None, owner=None):
+        """A block of new rows (host arrays, replicated): ids strictly ascending and above every id of the index - a BIGSERIAL
+        key - else ValueError before any rank changes anything; so no id can exist twice across shards, without a lookup. The
+        whole block goes to ONE rank: `owner`, or the rank with the fewest rows (ties: the lowest rank), which every rank
+        computes from its copy of the layout. The owner inserts, the others update the layout. Returns (owner, the block's first
+        row on the owner)."""
+        ids, owner, first = self._check_block(emb, ids, owner)
+        if owner == self.rank:
+            got = self.engine.index_insert(emb, ids=ids, tenants=tenants, temporal=temporal)
+            assert got == first, (got, first)
+        self._block_done(ids, owner)
+        return owner, first
+
+    def delete_local(self, ids, tenant=-1):
+        """This rank's half of delete_ids: the rows it holds of these ids (and of `tenant`, when >= 0) -> their number."""
+        return self.engine.index_delete(ids, tenant=tenant)
+
+    def delete_ids(self, ids, tenant=-1):
+        """Every rank deletes what it holds of these ids; returns the number of rows deleted anywhere (one gather of one number)."""
+        mine = self.delete_local(ids, tenant)
+        return sum(int(r[0]) for r in self._gather_numbers([mine]))
+
+    def compact_local(self):
+        """This rank's half of compact(): the local compaction with postings and resident data kept -> its row map."""
+        row_map = self.engine.index_compact(keep_resident=True)
+        self._layout = None
+        self._rows_changed()
+        return row_map
+
+    def compact(self):
+        """Every rank removes its deleted rows (rag_index_compact_live: BM25 and learned-sparse postings and the token vectors
+        move with the rows), then the layout is agreed again. Ids do not change, so no other rank is affected. Returns this
+        rank's row map."""
+        row_map = self.compact_local()
+        self.layout()
+        return row_map
 
     def _buffers(self, Q, k, device):
         key = (Q, k, str(device))
@@ -94,16 +220,84 @@ class ShardedHybridIndex(ShardedDenseIndex):
     # load; a number (the SAME on every rank, not above that) forces smaller pieces.
     linear_sub_batch = None
 
-    def load_shard(self, emb_shard, first_global_row, postings_shard=None, temporal=None):
-        """temporal: this rank's slice of the per-row temporal vector of search_linear (float64 [rows]; None = zeros)."""
-        super().load_shard(emb_shard, first_global_row)
+    def load_shard(self, emb_shard, first_global_row, postings_shard=None, temporal=None, ids=None):
+        """temporal: this rank's slice of the per-row temporal vector of search_linear (float64 [rows]; None = zeros).
+        ids: ShardedDenseIndex.load_shard."""
+        super().load_shard(emb_shard, first_global_row, ids=ids)
+        self._idf = None
         if postings_shard is not None:
             postings_shard.load(self.engine)
+            # the GLOBAL idf table (replicated at the load, grown by every insert_rows on every rank, replaced by
+            # refresh_statistics): a later block's owner takes from it the idf of terms that other ranks' blocks introduced
+            self._idf = np.array(postings_shard.idf, dtype=np.float64)
+            self._epsilon = float(getattr(postings_shard, "epsilon", 0.25))
         self.engine.bm25_set_normalize(False)
         if temporal is not None or getattr(self, "_has_temporal", False):      # (None after a vector clears it: a reload keeps none)
             self.engine.set_temporal(temporal)
             self._has_temporal = temporal is not None
         self._lin_agreed = None
+
+    def _rows_changed(self):
+        self._lin_agreed = None                 # the sub-batch of search_linear follows the row counts: agreed again at the next search
+
+    def _local_terms(self):
+        return 0 if getattr(self, "_idf", None) is None else int(self.engine.bm25_segment_stats()["n_terms"])
+
+    def insert_rows(self, emb, ids, tenants=None, temporal=None, owner=None, postings=None):
+        """ShardedDenseIndex.insert_rows with the block's BM25 postings: `postings` is what Bm25Postings.extend returned for the
+        block's texts on the mirror of the WHOLE corpus (CSR over the grown global vocabulary, documents relative to the block,
+        idf_new of the terms the block introduced). The owner appends them (rag_bm25_append_host) with the idf of every term ITS
+        handle does not know yet - those of this block and those that blocks of other ranks introduced, from the recorded table.
+        A rank that never sees a term needs nothing: a query term past a handle's vocabulary is out of vocabulary there."""
+        ids, owner, first = self._check_block(emb, ids, owner)
+        V = None
+        if postings is not None:
+            if self._idf is None:
+                raise ValueError("insert_rows: postings given but the shard was loaded without any")
+            V, idf_new = int(postings["n_terms_total"]), np.asarray(postings["idf_new"], dtype=np.float64)
+            if V != self._idf.shape[0] + idf_new.shape[0] or self._idf.shape[0] != self.layout()["terms"]:
+                raise ValueError(f"insert_rows: the block counts {V} terms with {idf_new.shape[0]} new ones, the index knows {self._idf.shape[0]}")
+        elif self._idf is not None:
+            raise ValueError("insert_rows: the shard has BM25 postings: the block's postings are required")
+        if owner == self.rank:
+            got = self.engine.index_insert(emb, ids=ids, tenants=tenants, temporal=temporal)
+            assert got == first, (got, first)
+        if postings is not None:
+            self._idf = np.concatenate([self._idf, idf_new])
+            if owner == self.rank:
+                known = self._local_terms()
+                self.engine.bm25_append(postings["indptr"], postings["doc"], postings["tf"], postings["doc_len"], self._idf[known:V], V)
+        self._block_done(ids, owner, V)
+        return owner, first
+
+    def local_statistics(self):
+        """This rank's half of refresh_statistics: int64 [global terms + 2] = df of every term over its live documents (0 for a
+        term its handle does not know) | live documents | the sum of their lengths."""
+        df, n, total = self.engine.bm25_live_counts()
+        out = np.zeros(self.layout()["terms"] + 2, dtype=np.int64)
+        out[:df.shape[0]] = df
+        out[-2:] = (n, total)
+        return out
+
+    def apply_statistics(self, all_statistics, epsilon=None):
+        """all_statistics: every rank's local_statistics(). Integer sums, so exact; then the idf rule of rag_bm25_refresh on the
+        host (Bm25Postings.idf_of_counts) and rag_bm25_set_statistics_host with this handle's prefix of the table."""
+        tot = np.sum(np.asarray(all_statistics, dtype=np.int64), axis=0)
+        n, length = int(tot[-2]), int(tot[-1])
+        if n == 0:
+            raise ValueError("refresh_statistics: no live document on any rank")
+        eps = self._epsilon if epsilon is None else float(epsilon)
+        self._idf, _ = Bm25Postings.idf_of_counts(tot[:-2], n, eps)
+        avgdl = length / n
+        self.engine.bm25_set_statistics(self._idf[:self._local_terms()], avgdl)
+        return self._idf, avgdl
+
+    def refresh_statistics(self, epsilon=0.25):
+        """idf and avgdl over the live documents of EVERY shard, as rag_bm25_refresh computes them on the unsharded index: one
+        gather of (terms + 2) int64 per rank. Needs option bm25_keep_tf set before the postings were loaded. Returns (idf of
+        every known term, avgdl)."""
+        mine = self.local_statistics()
+        return self.apply_statistics(self._gather_numbers(mine.tolist()), epsilon)
 
     def _hyb_buffers(self, Q, pool, k, device):
         key = ("hyb", Q, pool, k, str(device))
@@ -223,14 +417,46 @@ class ShardedM3Index(ShardedDenseIndex):
 
     The halves on each side of each gather are methods of their own, so one process can stack the sends of several handles."""
 
-    def load_shard(self, emb_shard, first_global_row, lexical_shard=None, token_vecs=None, token_off=None, form="fp16"):
+    def load_shard(self, emb_shard, first_global_row, lexical_shard=None, token_vecs=None, token_off=None, form="fp16", ids=None,
+                   token_reserve=None):
         """emb_shard: this rank's rows; lexical_shard: LexicalPostings.shard(begin, end); token_vecs [rows, dim] float32 and
-        token_off [n_rows + 1] int64: the token vectors of this rank's documents, stored as `form` ("fp16" / "mxfp8")."""
-        super().load_shard(emb_shard, first_global_row)
+        token_off [n_rows + 1] int64: the token vectors of this rank's documents, stored as `form` ("fp16" / "mxfp8").
+        ids: ShardedDenseIndex.load_shard. token_reserve = (documents, token rows): room the store keeps for insert_rows beyond
+        what is loaded (a store without it is full once loaded)."""
+        super().load_shard(emb_shard, first_global_row, ids=ids)
+        self._has_lexical = lexical_shard is not None
+        self._has_tokvec = token_vecs is not None
         if lexical_shard is not None:
             lexical_shard.load(self.engine)
-        if token_vecs is not None:
+        if token_vecs is not None and token_reserve is None:
             self.engine.tokvec_load(token_vecs, token_off, form=form)
+        elif token_vecs is not None:
+            token_off = np.ascontiguousarray(token_off, dtype=np.int64)
+            self.engine.tokvec_reserve(token_off.shape[0] - 1 + int(token_reserve[0]), int(token_off[-1] - token_off[0]) + int(token_reserve[1]),
+                                       int(token_vecs.shape[1]), form=form)
+            self.engine.tokvec_append(token_vecs, token_off)
+
+    def insert_rows(self, emb, ids, tenants=None, temporal=None, owner=None, lexical=None, token_vecs=None, token_off=None):
+        """ShardedDenseIndex.insert_rows with the block's learned-sparse postings and token vectors. lexical: what
+        LexicalPostings.extend returned for the block (host CSR, documents relative to the block), or a (doc_ptr, terms, weights,
+        n_terms_total) tuple of CUDA tensors, the doc-major output of lexical_compact_dev (rag_sparse_append_dev); token_vecs /
+        token_off: float32 [rows, dim] and int64 [n + 1]. The owner appends both; raw sparse scores and MaxSim need no
+        corpus-wide statistic, so the other ranks do nothing."""
+        ids, owner, first = self._check_block(emb, ids, owner)
+        if (lexical is not None) != getattr(self, "_has_lexical", False) or (token_vecs is not None) != getattr(self, "_has_tokvec", False):
+            raise ValueError("insert_rows: the block must bring the lexical postings / token vectors iff the shard holds them")
+        if owner == self.rank:
+            got = self.engine.index_insert(emb, ids=ids, tenants=tenants, temporal=temporal)
+            assert got == first, (got, first)
+            if isinstance(lexical, dict):
+                self.engine.sparse_append(lexical["indptr"], lexical["doc"], lexical["weight"], lexical["n_docs"], lexical["n_terms_total"])
+            elif lexical is not None:
+                doc_ptr, terms, weights, n_terms_total = lexical
+                self.engine.sparse_append_dev(doc_ptr, terms, weights, n_terms_total)
+            if token_vecs is not None:
+                self.engine.tokvec_append(token_vecs, token_off)
+        self._block_done(ids, owner)
+        return owner, first
 
     def _m3_buffers(self, Q, pool, slots, k, device):
         key = ("m3", Q, pool, slots, k, str(device))
