@@ -67,7 +67,6 @@ struct __attribute__((aligned(32))) bm_term_meta {
 #define BM_RANGE_LOG2 (31 - __builtin_clz(BM_RANGE))
 static_assert((BM_RANGE & (BM_RANGE - 1)) == 0, "BM_RANGE must be a power of two");
 
-struct bm_plan_meta;
 struct rag_bm25_index {
     int64_t n_docs = 0, n_terms = 0, nnz = 0;
     dev_buf<int32_t> doc;
@@ -83,23 +82,13 @@ struct rag_bm25_index {
     int64_t n_codes = 0;
     // LEARNED-SPARSE form (rag_sparse_load_host; the index of rag_ctx::sparse): the posting's weight as the caller's float32, 8 B
     // per posting with `doc`; `w` is not built, every term's idf is 1 and the QUERY carries a float32 weight per token
-    // (call_qw: the device array of the current call, as plan_t is the current call's). A tail is of the same form; no refresh, raw scores.
+    // (a device array of the call, bm_range_call::qweights). A tail is of the same form; no refresh, raw scores.
     dev_buf<float> wf;
-    const float* call_qw = nullptr;
     dev_buf<bm_term_meta> meta;        // [n_terms]
     dev_buf<int32_t> range_tab;        // concatenated per-term tables: entry c = first posting (rel. to meta.post) with doc >= c << shift
     int64_t tab_entries = 0;
     int n_ranges = 0;
-    // grow-only workspaces of the device entry points
-    dev_buf<uint64_t> ws_key;          // per-range partial top-k lists
-    dev_buf<uint32_t> ws_row;
-    dev_buf<uint64_t> ws_tau;          // first-stage threshold per query
-    dev_buf<int> ws_cnt;               // valid entries per (query, range) partial list
-    dev_buf<uint64_t> ws_run_key;      // running top-k of every query across the threshold stages
-    dev_buf<uint32_t> ws_run_row;
-    dev_buf<int32_t> ws_plan_off;      // per-call plan (bm25_plan_kernel)
-    dev_buf<bm_plan_meta> ws_plan_meta;
-    int plan_t = 64;                   // planned token slots per query of the CURRENT call (bm25_pick_plan_t), <= BM_PLAN_T
+    dev_buf<char> ws;                  // base: grow-only workspace of the device entry points, carved per call (bm25_ws_planes)
     double avgdl = 0, k1 = 1.5, b = 0.75;
     double neg_idf_absmax = 0;         // largest |idf| among the negative idf values (0: none), for bm25_negative_bound_args
     int normalize = 1;                 // 0: top-k scores stay raw (row-sharded search divides by the GLOBAL max after the merge)
@@ -346,8 +335,8 @@ static bm_grid bm_make_grid(int nr_l, int Q, int linear) {
 // inside its 2048-document range | code of its (tf, doc length) pair) and looks the impact factor g(tf, dl) up in a table shared
 // by all terms. Default: (doc i32, impact f64) = 12 bytes per posting.
 // (SGPRs capped at 96: 256-thread workgroups are admitted 7 per CU up to 96 scalar registers, 6 from 97 on - MI355X_MICROARCH.md)
-// The body of both kernels below. qten: the tenant of every query of the launch (rag_*_tenants_*) or null - a compile-time null in
-// bm25_range_kernel, whose code is therefore what it was before queries had tenants of their own.
+// The body of bm25_range_kernel below. qten: the tenant of every query of the launch (rag_*_tenants_*) or null - a compile-time null
+// in the instantiations without QTEN, whose code is therefore what it was before queries had tenants of their own.
 // FORM 0: (doc i32, impact f64); 1: PACKED; 2: SPARSE, the learned-sparse index - (doc i32, weight f32) postings, a float32 weight per
 // query token (qweights; the planned tokens' weights come in the plan's float64 slot), score += (double)qw * (double)w, and a
 // document whose score is not > 0 - one that matches nothing - is an EMPTY slot for the selection, like a hidden row.
@@ -868,32 +857,22 @@ __device__ __forceinline__ void bm25_range_body(const bm_term_meta* __restrict__
     if (tid == 0) part_cnt[(size_t)q * n_ranges + r] = k;
 }
 
-#define BM_RANGE_PARAMS                                                                                                                  \
-    const bm_term_meta *__restrict__ meta, const int32_t *__restrict__ doc, const double *__restrict__ w, const uint32_t *__restrict__ packed, \
-        const double *__restrict__ gtab, const int32_t *__restrict__ range_tab, int n_ranges, const int32_t *__restrict__ term_ptr,       \
-        const int32_t *__restrict__ terms, int64_t n_docs, int64_t n_terms, int k, int mode, double *__restrict__ dense_out,              \
-        uint64_t *__restrict__ part_key, uint32_t *__restrict__ part_row, int range_begin, const uint64_t *__restrict__ tau_key,          \
-        int *__restrict__ part_cnt, const int32_t *__restrict__ tenants, int tenant, const int32_t *__restrict__ plan_off,                \
-        const bm_plan_meta *__restrict__ plan_meta, const bm_grid gm, const bm_dense_extra dx, const bm_seg sg
-#define BM_RANGE_ARGS                                                                                                                    \
-    meta, doc, w, packed, gtab, range_tab, n_ranges, term_ptr, terms, n_docs, n_terms, k, mode, dense_out, part_key, part_row, range_begin, \
-        tau_key, part_cnt, tenants, tenant, plan_off, plan_meta, gm, dx, sg
-// one tenant (or none) for the whole launch
-template <bool PACKED>
-__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_kernel(BM_RANGE_PARAMS) {
-    bm25_range_body<PACKED ? 1 : 0>(BM_RANGE_ARGS, nullptr, nullptr, nullptr);
-}
-// a tenant per query: the workgroup reads its query's (`tenant` is not read)
-template <bool PACKED>
-__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_tenants_kernel(BM_RANGE_PARAMS,
-                                                                                                            const int32_t* __restrict__ qten) {
-    bm25_range_body<PACKED ? 1 : 0>(BM_RANGE_ARGS, qten, nullptr, nullptr);
-}
-// the learned-sparse index (rag_sparse_*): float32 posting weights wf (`w`, `packed`, `gtab` are null), a float32 weight per query token
-__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void sparse_range_kernel(BM_RANGE_PARAMS,
-                                                                                                      const float* __restrict__ wf,
-                                                                                                      const float* __restrict__ qweights) {
-    bm25_range_body<2>(BM_RANGE_ARGS, nullptr, wf, qweights);
+// FORM: the posting form (bm25_range_body); QTEN: a tenant per query - the workgroup reads its query's, `tenant` is not read - instead
+// of one tenant (or none) for the whole launch. The learned-sparse form (rag_sparse_*) reads float32 posting weights wf (`w`, `packed`,
+// `gtab` are null) and a float32 weight per query token. A trailing parameter an instantiation does not use reaches the body as a
+// compile-time null.
+template <int FORM, bool QTEN>
+__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void bm25_range_kernel(
+    const bm_term_meta* __restrict__ meta, const int32_t* __restrict__ doc, const double* __restrict__ w, const uint32_t* __restrict__ packed,
+    const double* __restrict__ gtab, const int32_t* __restrict__ range_tab, int n_ranges, const int32_t* __restrict__ term_ptr,
+    const int32_t* __restrict__ terms, int64_t n_docs, int64_t n_terms, int k, int mode, double* __restrict__ dense_out,
+    uint64_t* __restrict__ part_key, uint32_t* __restrict__ part_row, int range_begin, const uint64_t* __restrict__ tau_key,
+    int* __restrict__ part_cnt, const int32_t* __restrict__ tenants, int tenant, const int32_t* __restrict__ plan_off,
+    const bm_plan_meta* __restrict__ plan_meta, const bm_grid gm, const bm_dense_extra dx, const bm_seg sg,
+    const int32_t* __restrict__ qten, const float* __restrict__ wf, const float* __restrict__ qweights) {
+    bm25_range_body<FORM>(meta, doc, w, packed, gtab, range_tab, n_ranges, term_ptr, terms, n_docs, n_terms, k, mode, dense_out, part_key,
+                          part_row, range_begin, tau_key, part_cnt, tenants, tenant, plan_off, plan_meta, gm, dx, sg, QTEN ? qten : nullptr,
+                          FORM == 2 ? wf : nullptr, FORM == 2 ? qweights : nullptr);
 }
 
 #define BM_MERGE 2048
@@ -1215,17 +1194,8 @@ __global__ __launch_bounds__(64 * BMS_WAVES) void bm25_merge_select_kernel(const
     }
 }
 
-// sparse_range_kernel with a tenant per query (rag_sparse_topk_tenants_* and the *_tenants_dev composites over this index): a kernel
-// of its own, as bm25_range_tenants_kernel is, so that sparse_range_kernel's code stays what it was
-__global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_num_sgpr(96))) void sparse_range_tenants_kernel(BM_RANGE_PARAMS,
-                                                                                                              const float* __restrict__ wf,
-                                                                                                              const float* __restrict__ qweights,
-                                                                                                              const int32_t* __restrict__ qten) {
-    bm25_range_body<2>(BM_RANGE_ARGS, qten, wf, qweights);
-}
-
 // per-call device buffers of a top-k search: partial lists [Q][n_ranges][k], counts [Q][n_ranges], running list, threshold
-// + the per-call plan (see bm25_plan_kernel): plan.off [Q][BM_PLAN_T][n_ranges + 1] int32, plan.meta [Q][BM_PLAN_T]
+// + the per-call plan (see bm25_plan_kernel): plan.off [Q][plan_t][n_ranges + 1] int32, plan.meta [Q][BM_PLAN_T]
 struct bm25_plan_ws { int32_t* off; bm_plan_meta* meta; };
 struct bm25_topk_ws {
     uint64_t* part_key; uint32_t* part_row; int* part_cnt; uint64_t* run_key; uint32_t* run_row; uint64_t* tau;
@@ -1235,81 +1205,75 @@ struct bm25_topk_out {
     const int64_t* idmap; int64_t id_base; int64_t* ids; int32_t* rows; double* scores; double* raw_max; int normalize;
 };
 
-// STAGED top-k over all doc ranges: ranges [0, first) get the exact per-range top-k; after every stage the running top-k
-// of the query gives tau (k-th best so far), and the next stage - up to BM_STAGE_GROWTH x the ranges seen so far - only
-// compacts keys >= tau. Expected survivors per stage ~ k * growth per query however large the shard is (a single
-// threshold from 32768 docs left ~k/2 per range: 38 k entries per query to merge on a 12.5M-doc shard).
-// the scoring launch: packed 4-byte postings when the index has them, the 12-byte form otherwise
-// OUT_LD: documents of the whole index (both segments), the row length of the all-document score array
-// QTEN: the per-query tenants of the launch's queries (device) or null
-#define BM_RANGE_LAUNCH(H, IX, OUT_LD, NR_L, NQ, ST, DX, NR, TP, TM, K, MODE, QTEN, ...)                                               \
-    {                                                                                                                              \
-        bm_grid gm_ = bm_make_grid(NR_L, NQ, (H)->opt.bm25_linear_grid);                                                           \
-        gm_.plan_t = (IX)->plan_t;                                                                                                 \
-        const bm_seg sg_ = {(IX)->row0, OUT_LD, (IX)->first};                                                                      \
-        if ((IX)->wf != nullptr && (QTEN) != nullptr)                                                                              \
-            hipLaunchKernelGGL(sparse_range_tenants_kernel, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, \
-                               (const float*)(IX)->wf, (IX)->call_qw, QTEN);                                                       \
-        else if ((IX)->wf != nullptr)                                                                                              \
-            hipLaunchKernelGGL(sparse_range_kernel, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, \
-                               (const float*)(IX)->wf, (IX)->call_qw);                                                             \
-        else if ((QTEN) != nullptr && (IX)->packed != nullptr)                                                                     \
-            hipLaunchKernelGGL(bm25_range_tenants_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, QTEN); \
-        else if ((QTEN) != nullptr)                                                                                                \
-            hipLaunchKernelGGL(bm25_range_tenants_kernel<false>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_, QTEN); \
-        else if ((IX)->packed != nullptr)                                                                                          \
-            hipLaunchKernelGGL(bm25_range_kernel<true>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_); \
-        else                                                                                                                       \
-            hipLaunchKernelGGL(bm25_range_kernel<false>, dim3(gm_.blocks), dim3(BM_THREADS), BM_LDS_BYTES, ST, (IX)->meta, (IX)->doc, (IX)->w, \
-                               (IX)->packed, (IX)->gtab, (IX)->range_tab, NR, TP, TM, (IX)->n_docs, (IX)->n_terms, K, MODE, __VA_ARGS__, gm_, DX, sg_); \
-    }
+// Everything ONE scoring launch needs. An entry point fills the first row - what holds for the whole call: the index (seg = its
+// base), the device query arrays with the learned-sparse index's float32 weight per token, k, the mode (0: per-range top-k partials;
+// 1: all-document scores), the planned token slots per query (bm25_pick_plan_t, <= BM_PLAN_T) - and the tenants; the launch
+// functions below fill the rest per segment and stage. An output that a launch does not write stays null.
+struct bm_range_call {
+    const rag_bm25_index* seg; const int32_t* term_ptr; const int32_t* terms; const float* qweights; int k, mode, plan_t;
+    const int32_t* tenants = nullptr; int tenant = -1; const int32_t* qten = nullptr;      // per row (null: no filter) | the launch's | per query
+    double* dense_out = nullptr; bm_dense_extra dx = {nullptr, 0, nullptr};                // mode 1: [Q][out_ld] + the linear fusion's extras
+    int64_t out_ld = 0;                                                                    // documents of the whole index (both segments)
+    uint64_t* part_key = nullptr; uint32_t* part_row = nullptr; int* part_cnt = nullptr;   // mode 0: the segment's partial lists and counts
+    int range_begin = 0; const uint64_t* tau_key = nullptr;                                // first range of the launch; thresholded stage: tau
+    bm25_plan_ws plan = {nullptr, nullptr};                                                // the segment's plan
+};
+
+// the scoring launch of nr_launch ranges from c.range_begin: the instantiation by the segment's posting form and by whether the
+// queries carry tenants of their own
+static void bm_launch_range(const rag_ctx* h, const bm_range_call& c, int nr_launch, int Q, hipStream_t st) {
+    static constexpr decltype(&bm25_range_kernel<0, false>) kernels[3][2] = {{bm25_range_kernel<0, false>, bm25_range_kernel<0, true>},
+                                                                             {bm25_range_kernel<1, false>, bm25_range_kernel<1, true>},
+                                                                             {bm25_range_kernel<2, false>, bm25_range_kernel<2, true>}};
+    const rag_bm25_index* s = c.seg;
+    bm_grid gm = bm_make_grid(nr_launch, Q, h->opt.bm25_linear_grid);
+    gm.plan_t = c.plan_t;
+    const bm_seg sg = {s->row0, c.out_ld, s->first};
+    launch(kernels[s->wf != nullptr ? 2 : s->packed != nullptr ? 1 : 0][c.qten != nullptr], dim3(gm.blocks), dim3(BM_THREADS), BM_LDS_BYTES,
+           st, s->meta, s->doc, s->w, s->packed, s->gtab, s->range_tab, s->n_ranges, c.term_ptr, c.terms, s->n_docs, s->n_terms, c.k, c.mode,
+           c.dense_out, c.part_key, c.part_row, c.range_begin, c.tau_key, c.part_cnt, c.tenants, c.tenant, c.plan.off, c.plan.meta, gm, c.dx,
+           sg, c.qten, s->wf, c.qweights);
+}
+
 static int bm25_pick_plan_t(const rag_ctx* h, const rag_bm25_index* ix, int Q) {
     if (h->opt.bm25_plan_slots > 0) return std::min(BM_PLAN_T, h->opt.bm25_plan_slots);
     const size_t per_slot = (size_t)Q * (ix->n_ranges + 1 + (ix->tail ? ix->tail->n_ranges + 1 : 0)) * sizeof(int32_t);
     return (int)std::min<size_t>(BM_PLAN_T, std::max<size_t>(8, BM_PLAN_BUDGET / std::max<size_t>(1, per_slot)));
 }
-static size_t bm25_plan_off_entries(const rag_bm25_index* ix, int Q) { return (size_t)Q * ix->plan_t * (ix->n_ranges + 1); }
-// the plan of the tail sits behind the base's in the same two buffers (offsets: all of the base's entries; metadata: Q x BM_PLAN_T)
-static size_t bm25_plan_off_total(const rag_bm25_index* ix, int Q) {
-    return bm25_plan_off_entries(ix, Q) + (ix->tail ? (size_t)Q * ix->plan_t * (ix->tail->n_ranges + 1) : 0);
+static size_t bm25_plan_off_total(const rag_bm25_index* ix, int Q, int plan_t) {
+    return (size_t)Q * plan_t * (ix->n_ranges + 1 + (ix->tail ? ix->tail->n_ranges + 1 : 0));
 }
 static size_t bm25_plan_meta_total(const rag_bm25_index* ix, int Q) { return (size_t)Q * BM_PLAN_T * (ix->tail ? 2 : 1); }
-static bm25_plan_ws bm25_tail_plan(const rag_bm25_index* ix, int Q, const bm25_plan_ws& p) {
-    return {p.off + bm25_plan_off_entries(ix, Q), p.meta + (size_t)Q * BM_PLAN_T};
+// The segments of an index are walked base first. `call` as the entry point filled it, narrowed to segment sg of the index call.seg
+// with its SLICE of the call's buffers w: the plan of the tail sits behind the base's in the same two buffers (offsets: all of the
+// base's entries; metadata: Q x BM_PLAN_T), its partial lists [Q][tail ranges][k] and their counts behind the base's.
+static bm_range_call bm_segment_call(const bm_range_call& call, const rag_bm25_index* sg, int Q, const bm25_topk_ws& w) {
+    const size_t before = sg != call.seg ? (size_t)Q : 0, cnt = before * call.seg->n_ranges;      // (0: the base)
+    bm_range_call c = call;
+    c.seg = sg;
+    c.out_ld = bm_total_docs(call.seg);
+    c.plan = {w.plan.off + before * call.plan_t * (call.seg->n_ranges + 1), w.plan.meta + before * BM_PLAN_T};
+    if (call.mode == 0) {
+        c.part_key = w.part_key + cnt * call.k;
+        c.part_row = w.part_row + cnt * call.k;
+        c.part_cnt = w.part_cnt + cnt;
+    }
+    return c;
 }
-static void bm25_launch_plan(const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, const bm25_plan_ws& p,
-                             hipStream_t st) {
-    if (ix->wf != nullptr)
-        launch(bm25_plan_kernel<true>, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab, ix->n_ranges,
-               ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t, ix->call_qw);
-    else
-        launch(bm25_plan_kernel<false>, dim3((ix->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, ix->meta, ix->doc, ix->range_tab, ix->n_ranges,
-               ix->n_terms, term_ptr_dev, terms_dev, p.off, p.meta, ix->plan_t, nullptr);
+static void bm25_launch_plan(const bm_range_call& c, int Q, hipStream_t st) {
+    const rag_bm25_index* s = c.seg;
+    launch(s->wf != nullptr ? bm25_plan_kernel<true> : bm25_plan_kernel<false>, dim3((s->n_ranges + 1 + 255) / 256, Q), dim3(256), 0, st, s->meta,
+           s->doc, s->range_tab, s->n_ranges, s->n_terms, c.term_ptr, c.terms, c.plan.off, c.plan.meta, c.plan_t, s->wf != nullptr ? c.qweights : nullptr);
 }
 
-// mode 1 over every segment: out[Q][documents of the index] (+ the linear fusion's extras); each segment writes its own columns
-static void bm25_launch_scores(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q,
-                               double* out, const bm_dense_extra& dx, const int32_t* tenants, int tenant, const int32_t* qten,
-                               const bm25_plan_ws& pw, hipStream_t st) {
-    const int64_t n_all = bm_total_docs(ix);
-    bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, pw, st);
-    BM_RANGE_LAUNCH(h, ix, n_all, ix->n_ranges, Q, st, dx, ix->n_ranges, term_ptr_dev, terms_dev, 1, 1, qten, out, (uint64_t*)nullptr,
-                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)pw.off,
-                    (const bm_plan_meta*)pw.meta)
-    rag_bm25_index* tl = ix->tail.get();
-    if (tl == nullptr) return;
-    tl->plan_t = ix->plan_t;
-    tl->call_qw = ix->call_qw;                                       // (learned-sparse: the call's query weights, for the tokens past the plan)
-    const bm25_plan_ws tp = bm25_tail_plan(ix, Q, pw);
-    bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
-    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, dx, tl->n_ranges, term_ptr_dev, terms_dev, 1, 1, qten, out, (uint64_t*)nullptr,
-                    (uint32_t*)nullptr, 0, (const uint64_t*)nullptr, (int*)nullptr, tenants, tenant, (const int32_t*)tp.off,
-                    (const bm_plan_meta*)tp.meta)
+// mode 1 over every segment: call.dense_out[Q][documents of the index] (+ the linear fusion's extras); each segment writes its own columns
+static void bm25_launch_scores(const rag_ctx* h, const bm_range_call& call, int Q, const bm25_topk_ws& w, hipStream_t st) {
+    for (const rag_bm25_index* sg : {call.seg, (const rag_bm25_index*)call.seg->tail.get()}) {
+        if (sg == nullptr) continue;
+        const bm_range_call c = bm_segment_call(call, sg, Q, w);
+        bm25_launch_plan(c, Q, st);
+        bm_launch_range(h, c, sg->n_ranges, Q, st);
+    }
 }
 
 // folds the partial lists of the ranges [begin, end) of one segment into the running top-k (selection, or the bitonic sort)
@@ -1325,42 +1289,36 @@ static void bm25_launch_merge(const rag_ctx* h, const bm25_topk_ws& w, const uin
                            o.raw_max, o.normalize);
 }
 
-static void bm25_launch_topk(const rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k,
-                             const bm25_topk_ws& w, const bm25_topk_out& o, const int32_t* tenants, int tenant, const int32_t* qten,
+// mode 0 over every segment, STAGED: ranges [0, first) get the exact per-range top-k; after every stage the running top-k
+// of the query gives tau (k-th best so far), and the next stage - up to BM_STAGE_GROWTH x the ranges seen so far - only
+// compacts keys >= tau. Expected survivors per stage ~ k * growth per query however large the shard is (a single
+// threshold from 32768 docs left ~k/2 per range: 38 k entries per query to merge on a 12.5M-doc shard).
+// The base runs these stages. The tail is ONE more thresholded stage: its rows come after every base row,
+// so the running list's k-th key is the same lower bound for it as for a later base range (0 - everything passes - while the base
+// held fewer than k documents), and its partial lists fold into the same running list. The last fold of the last segment finishes.
+static void bm25_launch_topk(const rag_ctx* h, const bm_range_call& call, int Q, const bm25_topk_ws& w, const bm25_topk_out& o,
                              hipStream_t st) {
-    const int nr = ix->n_ranges;
-    rag_bm25_index* tl = ix->tail.get();
-    bm25_launch_plan(ix, term_ptr_dev, terms_dev, Q, w.plan, st);
-    const int64_t n_all = bm_total_docs(ix);
+    const rag_bm25_index* ix = call.seg;
+    const rag_bm25_index* tl = ix->tail.get();
     const int first_cfg = h->opt.bm25_first_ranges >= 1 && h->opt.bm25_first_ranges <= 16 ? h->opt.bm25_first_ranges : BM_FIRST_RANGES;
-    const bool staged = nr > 2 * first_cfg && !h->opt.bm25_no_staging;
-    int begin = 0, stage = 0;
-    while (begin < nr) {
-        int end = !staged ? nr : (stage == 0 ? first_cfg : (int)std::min<int64_t>(nr, (int64_t)begin * BM_STAGE_GROWTH));
-        if (staged && nr - end < end / 4) end = nr;                   // no tiny trailing stage
-        BM_RANGE_LAUNCH(h, ix, n_all, end - begin, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), nr, term_ptr_dev, terms_dev, k, 0, qten, (double*)nullptr,
-                        w.part_key, w.part_row, begin, stage == 0 ? (const uint64_t*)nullptr : (const uint64_t*)w.tau, w.part_cnt,
-                        tenants, tenant, (const int32_t*)w.plan.off, (const bm_plan_meta*)w.plan.meta)
-        const int last = end == nr && tl == nullptr;
-        bm25_launch_merge(h, w, w.part_key, w.part_row, w.part_cnt, nr, begin, end, Q, k, stage == 0 ? 1 : 0, last, o, st);
-        begin = end;
-        ++stage;
+    int stage = 0;                                                    // stages run so far, over all segments
+    for (const rag_bm25_index* sg : {ix, tl}) {
+        if (sg == nullptr) continue;
+        bm_range_call c = bm_segment_call(call, sg, Q, w);
+        bm25_launch_plan(c, Q, st);
+        const int nr = sg->n_ranges;
+        const bool staged = sg == ix && nr > 2 * first_cfg && !h->opt.bm25_no_staging;
+        for (int begin = 0; begin < nr; ++stage) {
+            int end = !staged ? nr : (stage == 0 ? first_cfg : (int)std::min<int64_t>(nr, (int64_t)begin * BM_STAGE_GROWTH));
+            if (staged && nr - end < end / 4) end = nr;                   // no tiny trailing stage
+            c.range_begin = begin;
+            c.tau_key = stage == 0 ? nullptr : w.tau;
+            bm_launch_range(h, c, end - begin, Q, st);
+            const int last = end == nr && (sg == tl || tl == nullptr);
+            bm25_launch_merge(h, w, c.part_key, c.part_row, c.part_cnt, nr, begin, end, Q, call.k, stage == 0 ? 1 : 0, last, o, st);
+            begin = end;
+        }
     }
-    if (tl == nullptr) return;
-    // The tail: ONE more thresholded stage. Its rows come after every base row, so the running list's k-th key is the same
-    // lower bound for it as for a later base range (0 - everything passes - while the base held fewer than k documents). Its
-    // partial lists sit behind the base's, [Q][tail ranges][k], and fold into the same running list: the last fold.
-    tl->plan_t = ix->plan_t;
-    tl->call_qw = ix->call_qw;                                       // (learned-sparse: the call's query weights, for the tokens past the plan)
-    const bm25_plan_ws tp = bm25_tail_plan(ix, Q, w.plan);
-    bm25_launch_plan(tl, term_ptr_dev, terms_dev, Q, tp, st);
-    uint64_t* t_key = w.part_key + (size_t)Q * nr * k;
-    uint32_t* t_row = w.part_row + (size_t)Q * nr * k;
-    int* t_cnt = w.part_cnt + (size_t)Q * nr;
-    BM_RANGE_LAUNCH(h, tl, n_all, tl->n_ranges, Q, st, (bm_dense_extra{nullptr, 0, nullptr}), tl->n_ranges, term_ptr_dev, terms_dev, k, 0, qten,
-                    (double*)nullptr, t_key, t_row, 0, (const uint64_t*)w.tau, t_cnt, tenants, tenant, (const int32_t*)tp.off,
-                    (const bm_plan_meta*)tp.meta)
-    bm25_launch_merge(h, w, t_key, t_row, t_cnt, tl->n_ranges, 0, tl->n_ranges, Q, k, 0, 1, o, st);
 }
 
 // the kept term-frequency plane (option bm25_keep_tf): the int32 frequencies of a load / an appended block as uint16
@@ -2127,8 +2085,8 @@ int bm25_segment_stats(rag_ctx* h, rag_bm25_segments* out) { return bm_segment_s
 int sparse_segment_stats(rag_ctx* h, rag_bm25_segments* out) { return bm_segment_stats(h, bm_slot_sparse(h), out); }
 
 static int bm25_set_attr(rag_ctx* h) {
-    return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<true>, bm25_range_kernel<false>, bm25_range_tenants_kernel<true>,
-                     bm25_range_tenants_kernel<false>, sparse_range_kernel, sparse_range_tenants_kernel);
+    return raise_lds(h, h->attr_bm25_lds, BM_LDS_BYTES, bm25_range_kernel<0, false>, bm25_range_kernel<0, true>, bm25_range_kernel<1, false>,
+                     bm25_range_kernel<1, true>, bm25_range_kernel<2, false>, bm25_range_kernel<2, true>);
 }
 
 // The resident postings after rag_index_insert_host / rag_index_compact no longer describe the rows (the document count alone
@@ -2438,105 +2396,142 @@ int bm25_refresh(rag_ctx* h, double epsilon, double* idf_out, rag_bm25_refresh_i
     return RAG_OK;
 }
 
+// ---- the per-call workspace of a keyword search: every plane named ONCE, in the order the buffer holds them (ws_carve: one pass
+// sizes, one carves). mode 0: the partial lists [Q][ranges of both segments][k] with their counts, the running list, the threshold;
+// both modes: the plan of both segments (the metadata sized for the largest plan_t). hw - the host entry, which stages everything
+// in the handle's arena: additionally the query arrays (n_tok tokens), the outputs, the all-document plane of mode 1 and, for a
+// call that has them, the query weights.
+struct bm25_host_ws { int32_t* term_ptr; int32_t* terms; int64_t* ids; int32_t* rows; double* raw_max; double* scores; double* dense; float* qweights; };
+static void bm25_ws_planes(ws_carve& c, const rag_bm25_index* ix, int Q, int k, int mode, int plan_t, bm25_topk_ws& w, bm25_host_ws* hw = nullptr,
+                           size_t n_tok = 0, bool qweights = false) {
+    const size_t nq = (size_t)Q, n_cnt = nq * bm_total_ranges(ix), n_part = mode == 0 ? n_cnt * k : 0, n_out = mode == 0 ? nq * k : 0;
+    if (hw) hw->term_ptr = c.take<int32_t>(nq + 1);
+    if (hw) hw->terms = c.take<int32_t>(n_tok);
+    w.part_key = c.take<uint64_t>(n_part);
+    w.part_row = c.take<uint32_t>(n_part);
+    w.part_cnt = c.take<int>(n_cnt);
+    w.run_key = c.take<uint64_t>(n_out);
+    w.run_row = c.take<uint32_t>(n_out);
+    w.tau = c.take<uint64_t>(nq);
+    if (hw) {
+        hw->ids = c.take<int64_t>(n_out);
+        hw->rows = c.take<int32_t>(n_out);
+        hw->raw_max = c.take<double>(nq);
+        hw->scores = c.take<double>(n_out);
+        hw->dense = c.take<double>(mode == 1 ? nq * bm_total_docs(ix) : 0);
+    }
+    w.plan.off = c.take<int32_t>(bm25_plan_off_total(ix, Q, plan_t));
+    w.plan.meta = c.take<bm_plan_meta>(bm25_plan_meta_total(ix, Q));
+    if (hw) hw->qweights = qweights ? c.take<float>(n_tok) : nullptr;
+}
+// What a query is BUDGETED at when a device call is cut into sub-batches (bm_topk_dev): per range its partial list (k x 12 B), the
+// count and 8 plan slots x 4 B, plus the running list. It approximates the planes above - no 256-byte rounding, 8 slots whatever
+// plan_t is, no plan metadata - and stays as it is: the number of sub-batches a budget gives is pinned by tests.
+static size_t bm25_ws_per_query(const rag_bm25_index* ix, int k) {
+    return (size_t)bm_total_ranges(ix) * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
+}
+// the workspace of the device entry points, from the index's grow-only buffer
+static int bm25_dev_ws(rag_ctx* h, rag_bm25_index* ix, int Q, int k, int mode, int plan_t, bm25_topk_ws& w) {
+    ws_carve sum{nullptr};
+    bm25_ws_planes(sum, ix, Q, k, mode, plan_t, w);
+    if (int rc = ix->ws.reserve(h, sum.bytes)) return rc;
+    ws_carve c{ix->ws};
+    bm25_ws_planes(c, ix, Q, k, mode, plan_t, w);
+    return RAG_OK;
+}
+static inline bool bm25_k_ok(int k) { return k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE; }
+
 // host-pointer search against `ix` (the resident index or an ad-hoc one). Device staging comes from the handle's
 // grow-only arena: no device allocation per call.
-static int bm25_run(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int mode, int tenant,
+static int bm25_run(rag_ctx* h, const rag_bm25_index* ix, const int32_t* term_ptr, const int32_t* terms, int Q, int k, int mode, int tenant,
                     int64_t* ids_out, int32_t* rows_out, double* scores_out, double* raw_max_out, double* dense_out,
                     query_tenants qt = {nullptr, nullptr}, const float* qweights = nullptr) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr, "bm25: 1 <= n_queries <= 65535");
     const int n_terms_q = term_ptr[Q];
     ARG_CHECK(h, n_terms_q >= 0 && (n_terms_q == 0 || terms), "bm25: bad term arrays");
-    if (mode == 0) ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
+    if (mode == 0) ARG_CHECK(h, bm25_k_ok(k), "bm25: 0 < k <= 1024");
     const int32_t* tenants = nullptr;
     hipStream_t st = h->stream;
     int rc;
     if ((rc = bm25_tenant_args(h, ix, mode == 0 ? tenant : -1, qt, &tenants))) return rc;
     if ((rc = bm25_set_attr(h))) return rc;
-    const int32_t* dense_vis = mode == 1 ? tenants : nullptr;          // bm25_scores_host: 0.0 for deleted rows
-    const int nr = bm_total_ranges(ix);                               // partial lists: the base's ranges, then the tail's
-    const size_t n_part = mode == 0 ? (size_t)Q * nr * k : 0, n_out = mode == 0 ? (size_t)Q * k : 0;
-    const size_t n_dense = mode == 1 ? (size_t)Q * bm_total_docs(ix) : 0;
-    {   // plan slots: the batch's longest query (term_ptr is on the host here), within the per-call budget
-        int max_nt = 1;
-        for (int q = 0; q < Q; ++q) max_nt = std::max(max_nt, term_ptr[q + 1] - term_ptr[q]);
-        ix->plan_t = std::min(bm25_pick_plan_t(h, ix, Q), std::min(BM_PLAN_T, max_nt));
-    }
-    size_t total = stage_size(Q + 1, 4) + stage_size(std::max(1, n_terms_q), 4) + stage_size(n_part, 8) + stage_size(n_part, 4) +
-                   stage_size((size_t)Q * nr, 4) + 2 * stage_size(n_out, 8) + 2 * stage_size(n_out, 4) + 2 * stage_size(Q, 8) +
-                   stage_size(n_out, 8) + stage_size(n_dense, 8) + stage_size(bm25_plan_off_total(ix, Q), 4) +
-                   stage_size(bm25_plan_meta_total(ix, Q), sizeof(bm_plan_meta)) + (qweights ? stage_size(std::max(1, n_terms_q), 4) : 0);
-    if ((rc = stage_reserve(h, total))) return rc;
-    char* p = h->stage;
-    int32_t* tp = stage_take<int32_t>(p, Q + 1);
-    int32_t* tm = stage_take<int32_t>(p, std::max(1, n_terms_q));
+    int max_nt = 1;             // plan slots: the batch's longest query (term_ptr is on the host here), within the per-call budget
+    for (int q = 0; q < Q; ++q) max_nt = std::max(max_nt, term_ptr[q + 1] - term_ptr[q]);
+    const int plan_t = std::min(bm25_pick_plan_t(h, ix, Q), std::min(BM_PLAN_T, max_nt));
     bm25_topk_ws w;
-    w.part_key = stage_take<uint64_t>(p, n_part);
-    w.part_row = stage_take<uint32_t>(p, n_part);
-    w.part_cnt = stage_take<int>(p, (size_t)Q * nr);
-    w.run_key = stage_take<uint64_t>(p, n_out);
-    w.run_row = stage_take<uint32_t>(p, n_out);
-    w.tau = stage_take<uint64_t>(p, Q);
-    int64_t* idd = stage_take<int64_t>(p, n_out);
-    int32_t* rwd = stage_take<int32_t>(p, n_out);
-    double* mxd = stage_take<double>(p, Q);
-    double* scd = stage_take<double>(p, n_out);
-    double* dd = stage_take<double>(p, n_dense);
-    w.plan.off = stage_take<int32_t>(p, bm25_plan_off_total(ix, Q));
-    w.plan.meta = stage_take<bm_plan_meta>(p, bm25_plan_meta_total(ix, Q));  // (sized for the largest plan_t)
-    HIP_TRY(h, hipMemcpyAsync(tp, term_ptr, (size_t)(Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(tm, terms, (size_t)n_terms_q * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (qweights) {                                                    // the learned-sparse index: a weight per query token
-        float* qw = stage_take<float>(p, std::max(1, n_terms_q));
-        if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(qw, qweights, (size_t)n_terms_q * sizeof(float), hipMemcpyHostToDevice, st));
-        ix->call_qw = qw;
-    }
+    bm25_host_ws hw;
+    ws_carve sum{nullptr};
+    bm25_ws_planes(sum, ix, Q, k, mode, plan_t, w, &hw, std::max(1, n_terms_q), qweights != nullptr);
+    if ((rc = stage_reserve(h, sum.bytes))) return rc;
+    ws_carve c{h->stage};
+    bm25_ws_planes(c, ix, Q, k, mode, plan_t, w, &hw, std::max(1, n_terms_q), qweights != nullptr);
+    bm_range_call call = {ix, hw.term_ptr, hw.terms, hw.qweights, mode == 0 ? k : 1, mode, plan_t};
+    call.tenants = tenants;                                            // (mode 1, bm25_scores_host: 0.0 for deleted rows)
+    HIP_TRY(h, hipMemcpyAsync(hw.term_ptr, term_ptr, (size_t)(Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (n_terms_q) HIP_TRY(h, hipMemcpyAsync(hw.terms, terms, (size_t)n_terms_q * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (qweights && n_terms_q)                                         // the learned-sparse index: a weight per query token
+        HIP_TRY(h, hipMemcpyAsync(hw.qweights, qweights, (size_t)n_terms_q * sizeof(float), hipMemcpyHostToDevice, st));
     if (mode == 0) {
+        const size_t n_out = (size_t)Q * k;
         const id_space ids = bm_id_space(h, ix, id_space::of_index(h));       // a *_host search reports the index's ids
-        const bm25_topk_out o = {ids.map, ids.base, idd, rwd, scd, mxd, ix->normalize};
-        bm25_launch_topk(h, ix, tp, tm, Q, k, w, o, tenants, tenant, qt.dev, st);
+        const bm25_topk_out o = {ids.map, ids.base, hw.ids, hw.rows, hw.scores, hw.raw_max, ix->normalize};
+        call.tenant = tenant;
+        call.qten = qt.dev;
+        bm25_launch_topk(h, call, Q, w, o, st);
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(ids_out, idd, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, rwd, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(scores_out, scd, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (raw_max_out) HIP_TRY(h, hipMemcpyAsync(raw_max_out, mxd, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(ids_out, hw.ids, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, hw.rows, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(scores_out, hw.scores, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (raw_max_out) HIP_TRY(h, hipMemcpyAsync(raw_max_out, hw.raw_max, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
     } else {
-        bm25_launch_scores(h, ix, tp, tm, Q, dd, bm_dense_extra{nullptr, 0, nullptr}, dense_vis, -1, nullptr, w.plan, st);
+        call.dense_out = hw.dense;
+        bm25_launch_scores(h, call, Q, w, st);
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(dense_out, dd, n_dense * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(dense_out, hw.dense, (size_t)Q * bm_total_docs(ix) * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(h, hipStreamSynchronize(st));
     return RAG_OK;
 }
 
-static int bm25_ensure_plan(rag_ctx* h, rag_bm25_index* ix, int Q) {
-    ix->plan_t = bm25_pick_plan_t(h, ix, Q);
-    if (int rc = ix->ws_plan_off.reserve(h, bm25_plan_off_total(ix, Q))) return rc;
-    return ix->ws_plan_meta.reserve(h, bm25_plan_meta_total(ix, Q));
-}
-
 // device-pointer entry: everything stays in HBM, asynchronous on `st` (workspace grows on first use / larger Q)
-static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
-                               query_tenants qt);
+static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
+                               int Q, int k, int tenant, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev,
+                               hipStream_t st, id_space ids, query_tenants qt) {
+    ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && ids_dev && scores_dev, "bm25_topk_dev: bad arguments");
+    ARG_CHECK(h, bm25_k_ok(k), "bm25: 0 < k <= 1024");
+    bm_range_call call = {ix, term_ptr_dev, terms_dev, qweights_dev, k, 0, bm25_pick_plan_t(h, ix, Q)};
+    call.tenant = tenant;
+    call.qten = qt.dev;
+    int rc = bm25_tenant_args(h, ix, tenant, qt, &call.tenants);
+    if (rc) return rc;
+    if ((rc = bm25_set_attr(h))) return rc;
+    bm25_topk_ws w;
+    if ((rc = bm25_dev_ws(h, ix, Q, k, 0, call.plan_t, w))) return rc;
+    ids = bm_id_space(h, ix, ids);
+    const bm25_topk_out o = {ids.map, ids.base, ids_dev, rows_dev, scores_dev, raw_max_dev, ix->normalize};
+    if ((rc = prof_begin(h, 1, st))) return rc;
+    bm25_launch_topk(h, call, Q, w, o, st);
+    HIP_TRY(h, hipGetLastError());
+    return prof_end(h, 1, st);
+}
 
 // The per-call workspace (partial lists [Q][n_ranges][k] x 12 B + the plan) grows with Q x shard size: on a 12.5M-document shard a
 // query takes ~9 MB at k = 100. Batches are therefore run in sub-batches whose workspace stays under BM_WS_BUDGET (queries are
 // independent: same results; the 1M-document bench index runs 1,024 queries in one piece, the 12.5M-document shard 256).
 #define BM_WS_BUDGET ((size_t)6 << 30)
-// ix: the resident BM25 postings (bm25_topk_dev) or the learned-sparse postings (sparse_topk_dev, which sets ix->call_qw first)
-static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                       int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
-                       query_tenants qt) {
+// ix: the resident BM25 postings (bm25_topk_dev) or the learned-sparse postings (sparse_topk_dev, with the queries' weights)
+static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q,
+                       int k, int tenant, int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st,
+                       id_space ids, query_tenants qt) {
     ARG_CHECK(h, ix != nullptr, "no BM25 index loaded");
     ARG_CHECK(h, Q > 0 && Q <= 65535 && k > 0, "bm25_topk_dev: bad arguments");
     if (int rc = bm25_check_fresh(h, ix)) return rc;
-    const size_t per_query = (size_t)bm_total_ranges(ix) * ((size_t)k * 12 + 4 + 8 * 4) + (size_t)k * 12;
     const size_t budget = h->opt.bm25_ws_mb > 0 ? (size_t)h->opt.bm25_ws_mb << 20 : BM_WS_BUDGET;
-    const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, budget / std::max<size_t>(1, per_query)));
+    const int qb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, budget / std::max<size_t>(1, bm25_ws_per_query(ix, k))));
     for (int q0 = 0; q0 < Q; q0 += qb) {
         const int nq = std::min(qb, Q - q0);
-        const int rc = bm25_topk_dev_batch(h, ix, term_ptr_dev + q0, terms_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
+        const int rc = bm25_topk_dev_batch(h, ix, term_ptr_dev + q0, terms_dev, qweights_dev, nq, k, tenant, ids_dev + (size_t)q0 * k,
                                            rows_dev ? rows_dev + (size_t)q0 * k : nullptr, scores_dev + (size_t)q0 * k,
                                            raw_max_dev ? raw_max_dev + q0 : nullptr, st, ids, qt + q0);      // (the tenants go with their queries)
         if (rc) return rc;
@@ -2545,34 +2540,7 @@ static int bm_topk_dev(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_d
 }
 int bm25_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant, int64_t* ids_dev,
                   int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids, query_tenants qt) {
-    return bm_topk_dev(h, h->bm25, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, st, ids, qt);
-}
-
-static int bm25_topk_dev_batch(rag_ctx* h, rag_bm25_index* ix, const int32_t* term_ptr_dev, const int32_t* terms_dev, int Q, int k, int tenant,
-                               int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, double* raw_max_dev, hipStream_t st, id_space ids,
-                               query_tenants qt) {
-    ARG_CHECK(h, Q > 0 && Q <= 65535 && term_ptr_dev && ids_dev && scores_dev, "bm25_topk_dev: bad arguments");
-    ARG_CHECK(h, k > 0 && k <= BM_MERGE / 2 && k <= BM_RANGE, "bm25: 0 < k <= 1024");
-    const int32_t* tenants = nullptr;
-    int rc = bm25_tenant_args(h, ix, tenant, qt, &tenants);
-    if (rc) return rc;
-    if ((rc = bm25_set_attr(h))) return rc;
-    const int nr_all = bm_total_ranges(ix);
-    const size_t need = (size_t)Q * nr_all * k, need_run = (size_t)Q * k;
-    if ((rc = ix->ws_key.reserve(h, need))) return rc;
-    if ((rc = ix->ws_row.reserve(h, need))) return rc;
-    if ((rc = ix->ws_tau.reserve(h, (size_t)Q))) return rc;
-    if ((rc = ix->ws_cnt.reserve(h, (size_t)Q * nr_all))) return rc;
-    if ((rc = ix->ws_run_key.reserve(h, need_run))) return rc;
-    if ((rc = ix->ws_run_row.reserve(h, need_run))) return rc;
-    if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
-    ids = bm_id_space(h, ix, ids);
-    const bm25_topk_ws w = {ix->ws_key, ix->ws_row, ix->ws_cnt, ix->ws_run_key, ix->ws_run_row, ix->ws_tau, {ix->ws_plan_off, ix->ws_plan_meta}};
-    const bm25_topk_out o = {ids.map, ids.base, ids_dev, rows_dev, scores_dev, raw_max_dev, ix->normalize};
-    if ((rc = prof_begin(h, 1, st))) return rc;
-    bm25_launch_topk(h, ix, term_ptr_dev, terms_dev, Q, k, w, o, tenants, tenant, qt.dev, st);
-    HIP_TRY(h, hipGetLastError());
-    return prof_end(h, 1, st);
+    return bm_topk_dev(h, h->bm25, term_ptr_dev, terms_dev, nullptr, Q, k, tenant, ids_dev, rows_dev, scores_dev, raw_max_dev, st, ids, qt);
 }
 
 // raw float64 scores of EVERY document for Q queries, device pointers, asynchronous: out_dev[Q][n_docs]
@@ -2585,13 +2553,16 @@ int bm25_scores_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* term
     rag_bm25_index* ix = h->bm25;
     int rc = bm25_set_attr(h);
     if (rc) return rc;
-    const int32_t* tenants = nullptr;
+    bm_range_call call = {ix, term_ptr_dev, terms_dev, nullptr, 1, 1, bm25_pick_plan_t(h, ix, Q)};
+    call.tenant = tenant;
+    call.qten = qt.dev;
+    call.dense_out = out_dev;
+    call.dx = {raw32_dev, ld, max_key_dev};
     if ((rc = bm25_check_fresh(h, ix))) return rc;
-    if (max_key_dev != nullptr && (rc = bm25_tenant_args(h, ix, tenant, qt, &tenants))) return rc;
-    const bm_dense_extra dx = {raw32_dev, ld, max_key_dev};
-    if ((rc = bm25_ensure_plan(h, ix, Q))) return rc;
-    const bm25_plan_ws pw = {ix->ws_plan_off, ix->ws_plan_meta};
-    bm25_launch_scores(h, ix, term_ptr_dev, terms_dev, Q, out_dev, dx, tenants, tenant, qt.dev, pw, st);
+    if (max_key_dev != nullptr && (rc = bm25_tenant_args(h, ix, tenant, qt, &call.tenants))) return rc;
+    bm25_topk_ws w;
+    if ((rc = bm25_dev_ws(h, ix, Q, 1, 1, call.plan_t, w))) return rc;
+    bm25_launch_scores(h, call, Q, w, st);
     HIP_TRY(h, hipGetLastError());
     return RAG_OK;
 }
@@ -3140,8 +3111,7 @@ int sparse_scores_host(rag_ctx* h, const int32_t* term_ptr, const int32_t* terms
 int sparse_topk_dev(rag_ctx* h, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev, int Q, int k, int tenant,
                     int64_t* ids_dev, int32_t* rows_dev, double* scores_dev, hipStream_t st, id_space ids, query_tenants qt) {
     if (int rc = sparse_args(h, term_ptr_dev, qweights_dev, tenant, qt)) return rc;
-    h->sparse->call_qw = qweights_dev;
-    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, ids, qt);
+    return bm_topk_dev(h, h->sparse, term_ptr_dev, terms_dev, qweights_dev, Q, k, tenant, ids_dev, rows_dev, scores_dev, nullptr, st, ids, qt);
 }
 
 // ---- point lookup: the exact learned-sparse score of GIVEN rows (rag_sparse_score_rows_*; the sparse component of rag_m3_score_rows_dev)

@@ -423,6 +423,18 @@ static inline T* stage_take(char*& p, size_t n) {
     p += stage_size(n, sizeof(T));
     return r;
 }
+// ---- a per-call workspace carved from one buffer. A `planes` function names every plane once, as p = c.take<T>(elements); it runs
+// twice: without memory, which sums the sizes (stage_size: each plane starts on a 256-byte boundary), then over the reserved buffer.
+struct ws_carve {
+    char* base;
+    size_t bytes = 0;
+    template <class T>
+    T* take(size_t n) {
+        T* r = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += stage_size(n, sizeof(T));
+        return r;
+    }
+};
 
 // ---- sortable keys: larger key = higher score, then lower row ---------------------------------
 __host__ __device__ static inline uint32_t f32_orderable(float s) {

@@ -358,18 +358,7 @@ __global__ void rows_narrow_kernel(const int64_t* __restrict__ in, int32_t* __re
     if (i < n) out[i] = in[i] < 0 ? -1 : (int32_t)in[i];
 }
 
-// ---- the per-call workspace rag_ctx::pipe_ws. `planes` names every plane once, as p = c.take<T>(elements); it runs twice: without
-// memory, which sums the sizes (stage_size: each plane starts on a 256-byte boundary), then over the reserved buffer.
-struct ws_carve {
-    char* base;
-    size_t bytes = 0;
-    template <class T>
-    T* take(size_t n) {
-        T* r = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
-        bytes += stage_size(n, sizeof(T));
-        return r;
-    }
-};
+// ---- the per-call workspace rag_ctx::pipe_ws: `planes` names every plane once (common.h ws_carve) and runs twice, to size and to carve
 template <class F>
 static int pipe_ws_carve(rag_ctx* h, F&& planes) {
     ws_carve sum{nullptr}, c{nullptr};
