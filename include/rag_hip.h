@@ -18,10 +18,11 @@
  *     *_host calls may be issued from several threads at once (the reference graph is single-threaded,
  *     agent/rag_graph.py:506, but its DB pool allows 10 concurrent searches, database/connection.py:38-42); they
  *     run one after another. *_dev calls share the handle's device workspaces: issue them on ONE stream.
- *   - Ordering (pinned by tests/test_stream_order_gpu.py). A *_dev call returns once its work is queued on `stream`; all it
+ *   - Ordering (pinned by tests/test_stream_order_gpu.py and, for the entries added since, tests/test_stream_order_resident_gpu.py;
+ *     tests/test_stream_order_table_cpu.py fails for a *_dev entry declared here that neither file exercises). A *_dev call returns once its work is queued on `stream`; all it
  *     reads and writes is ordered on that stream as if it had run there alone: inputs produced earlier on the stream are
  *     seen, outputs may be consumed by later work on it, no other stream and no device-wide wait is needed. The calls that
- *     do wait for `stream` say so below (rag_tokens_append_dev, rag_tokvec_append_dev; any call that has to grow a workspace it used before frees
+ *     do wait for `stream` say so below (rag_tokens_append_dev, rag_tokvec_append_dev, rag_sparse_append_dev; any call that has to grow a workspace it used before frees
  *     the old one first, which waits for the device - the first call of a larger shape, not the steady state).
  *     A *_host call may be made while *_dev work of the handle is pending, from any thread, and behaves as if it ran after
  *     that work: it first waits for the device when a *_dev call was made on the handle since the last such wait (a
