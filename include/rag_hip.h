@@ -39,6 +39,12 @@
  *     wait: they change host state that a *_dev call reads while it enqueues, so a call queued earlier keeps the old value.
  *     rag_tokens_info reads host state only and waits for nothing.
  *     *_dev calls of one handle on SEVERAL streams stay unordered among themselves: that is the caller's to order.
+ *     A result does not depend on the calls the handle served before: the per-handle workspaces are grow-only and carved anew by
+ *     every call, so a call of another shape, another entry over the same workspace, or an index that shrank, grew or was
+ *     replaced in between (live writes, compactions, rag_index_load_*, rag_index_reserve, an option flipped by rag_set_option)
+ *     leaves nothing a later call can see - each call returns the bits it returns on a fresh handle in the same state
+ *     (tests/test_call_history_gpu.py, tests/test_state_history_gpu.py; tests/test_workspace_table_cpu.py fails for a grow-only
+ *     buffer that neither exercises).
  *   - doc ids are int64 (SQL BIGSERIAL ids, database/migrations/001_initial_schema.sql); scores are
  *     float64 because the reference computes every score as a Python float.
  */
