@@ -256,7 +256,19 @@ int rag_index_fetch_rows_host(rag_handle_t h, const int64_t* rows_host, int n, f
  * the fp16 error), survivors are rescored in float64; a float64 scan of every row is the overflow fallback.
  * eps (rag_dense_stats.eps) is pinned by tests on worst-case rows whose fp16 products all err the same way: they reach
  * max |fp16 score - cosine| = 0.85 eps at dim 64, 0.76 at dim 100, 0.78 at dim 384, 0.68 at dim 1536, and put a row of
- * the exact top-k 1.29 to 1.49 eps below the k-th best fp16 score (tests/fp16_adversary.py). */
+ * the exact top-k 1.29 to 1.49 eps below the k-th best fp16 score (tests/fp16_adversary.py).
+ * Alignment, ONE rule for every *_dev entry: a caller array that a kernel reads or writes through a type wider than its element
+ * is marked "16-byte aligned" where it is declared, and the entry refuses any other address with RAG_ERR_ARG and a message
+ * naming the array before it enqueues anything (tests/test_output_bounds_gpu.py). That is the float32 query matrix of every
+ * dense-backed search - q_dev [Q][dim] of rag_dense_topk_dev, rag_hybrid_rrf_dev, rag_hybrid_sparse_rrf_dev, rag_hybrid_linear_dev,
+ * rag_hybrid_linear_finish_dev, q_emb_dev of rag_retrieve_rerank_dev, rag_retrieve_maxsim_dev, rag_retrieve_m3_dev and of
+ * rag_m3_score_rows_dev / rag_m3_score_ids_dev under a dense weight, and their _tenants forms: rows are read as float4; dim is a
+ * multiple of 4, so every row of an aligned matrix is aligned - and the token-vector arrays (q_vecs, d_vecs of rag_maxsim_dev, the
+ * q_vecs of the rag_tokvec_rerank / rag_retrieve_maxsim / m3 entries). Every other array, inputs and outputs alike, is read and
+ * written element by element and needs its element's alignment only: emb_dev of rag_index_load_dev / rag_index_append_dev (copied
+ * by the runtime before any kernel reads it), q_dev of rag_mmr_select_dev, vecs_dev of rag_tokvec_append_dev, every token-id,
+ * length, term, weight and candidate array, and EVERY output array. Host pointers have no rule beyond the element's.
+ * q_dev: float32 [Q][dim], 16-byte aligned. */
 int rag_dense_topk_host(rag_handle_t h, const float* q_host, int n_queries, int k, int tenant,
                         int64_t* ids_out_host, int32_t* rows_out_host, double* scores_out_host);
 int rag_dense_topk_dev(rag_handle_t h, const float* q_dev, int n_queries, int k, int tenant,
@@ -329,7 +341,8 @@ int rag_rrf_fuse_host(rag_handle_t h, const int64_t* lists_host, int n_queries, 
 
 /* Device-pointer forms of the fusion / BM25 entry points (asynchronous on `stream`), and the whole hybrid path of
  * BASELINE.json configs[2] in one call: dense top-`pool` + BM25 top-`pool` -> RRF(rrf_k) -> top-k, nothing leaves HBM.
- * rag_rrf_fuse_dev: lists_dev is [Q][n_lists][list_len]. rag_hybrid_rrf_dev: lists_ws_dev is caller scratch
+ * rag_rrf_fuse_dev: lists_dev is [Q][n_lists][list_len]. rag_hybrid_rrf_dev: q_dev float32 [Q][dim], 16-byte aligned (else
+ * RAG_ERR_ARG, as in rag_dense_topk_dev); lists_ws_dev is caller scratch
  * [2][Q][pool] int64, scores_ws_dev [Q][pool] float64; keys are doc ids (BM25 rows use the dense index's id mapping,
  * the two indexes must be row-aligned). For batches of up to 4096 queries the BM25 leg of rag_hybrid_rrf_dev / rag_retrieve_rerank_dev
  * runs on an internal side stream that is forked from and joined back into `stream` by events: everything the call
@@ -380,9 +393,9 @@ int rag_hybrid_rrf_dev(rag_handle_t h, const float* q_dev, const int32_t* term_p
  *   rag_hybrid_sparse_rrf_tenants_dev ("a tenant PER QUERY" below).
  * rag_hybrid_sparse_rrf_dev: rag_hybrid_rrf_dev with the sparse list in place of the BM25 list - dense top-`pool` and sparse
  *   top-`pool` (-1 padded at the tail), rag_rrf_fuse_dev semantics with n_lists = 2, dense first, top-k. Workspaces and limits
- *   as rag_hybrid_rrf_dev (pool <= 256; lists_ws_dev [2][Q][pool] int64, scores_ws_dev [Q][pool] float64); the postings must
- *   be row-aligned with the index. Bit-identical to rag_dense_topk_dev + rag_sparse_topk_dev + rag_rrf_fuse_dev called one
- *   after another. The sparse leg forks onto the internal side stream as the BM25 leg of rag_hybrid_rrf_dev does (batches
+ *   as rag_hybrid_rrf_dev (q_dev 16-byte aligned; pool <= 256; lists_ws_dev [2][Q][pool] int64, scores_ws_dev [Q][pool]
+ *   float64); the postings must be row-aligned with the index. Bit-identical to rag_dense_topk_dev + rag_sparse_topk_dev +
+ *   rag_rrf_fuse_dev called one after another. The sparse leg forks onto the internal side stream as the BM25 leg of rag_hybrid_rrf_dev does (batches
  *   of up to 4096 queries; options no_fork / fork_max_q), joined back by events: everything is ordered on `stream`.
  * The _dev calls follow the ordering rules of the preamble.
  * Sharding: raw scores need no global statistic, so rag_merge_topk_dev over the per-shard lists (global ids through id_base
@@ -611,7 +624,8 @@ int rag_linear_fuse_topk_host(rag_handle_t h, const double* semantic_host, const
  * of rag_index_set_temporal_host (RECENCY_WEIGHT * 0.5 ** (days_old / half_life), computed by the host as :266-292 does;
  * NULL = zeros). Result: stable sort descending (lower row first on ties), first k; rows_out are index rows, ids_out doc
  * ids, hybrid_out the float64 hybrid scores; semantic / keyword / temporal_out (each [Q*k], may be NULL) are the
- * components the reference returns next to them. alpha must be > 0; tenant as in rag_dense_topk_dev. The postings must be
+ * components the reference returns next to them. alpha must be > 0; tenant as in rag_dense_topk_dev, and q_dev 16-byte aligned
+ * as there. The postings must be
  * row-aligned with the index. Exact by the same construction as the dense search: the fp16 MFMA pass only discards rows
  * whose FUSED score is provably below the k-th best, survivors are rescored in float64. The bound on the fused fp16-pass
  * score is |alpha| * eps + 2^-21 * (|alpha| + |beta| * max|keyword| + |gamma| * max|temporal|): beta and gamma may have
@@ -797,7 +811,8 @@ int rag_lexical_compact_dev(rag_handle_t h, const int32_t* ids_dev /*[n][L]*/, c
  *      pairs are [CLS] query [SEP] passage [SEP] truncated 'longest_first' to max_length L_pair (what CrossEncoder.predict's
  *      tokenizer call does; the reference's max_length is 512, rag/reranker.py:290-294) and padded to it; outputs per query:
  *      ids_out[k] doc ids (-1 padded), scores_out[k] = sigmoid(logit) as float64, logits_out[k] raw logits,
- *      cand_out[pool] (may be NULL) the candidate list that was reranked. 0 < k <= pool <= 256.
+ *      cand_out[pool] (may be NULL) the candidate list that was reranked. 0 < k <= pool <= 256. q_emb_dev float32 [Q][dim],
+ *      16-byte aligned (else RAG_ERR_ARG; the token arrays are read element by element).
  *      Token store: 1 <= L <= 512, ids in [0, 65535] (the resident store is 16 bits wide); anything else is RAG_ERR_ARG. L_pair
  *      is at most 512 as well, whatever the loaded model's own limit (rag_model_seq_limit): the resident pipeline stays at 512
  *      tokens per pair. */
@@ -887,7 +902,8 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
  *   float32 unit vectors (fp16 rounding moves a dot of unit vectors by at most 2^-11). A pair's score is a function of its own
  *   rows only: bit-identical from run to run, whatever pool, neighbours or batch surround it.
  * rag_retrieve_maxsim_dev: candidates, MaxSim rerank and top-k in one device-resident call, as rag_retrieve_rerank_dev does for the
- *   cross-encoder. mode 0: the dense top-`pool` of q_emb [Q][dim index]; mode 1: the top-`pool` of dense + learned-sparse RRF
+ *   cross-encoder. q_emb and q_vecs 16-byte aligned (else RAG_ERR_ARG, before anything is queued). mode 0: the dense
+ *   top-`pool` of q_emb [Q][dim index]; mode 1: the top-`pool` of dense + learned-sparse RRF
  *   (term_ptr / terms / qweights as rag_hybrid_sparse_rrf_dev, rrf_k), with tenant and deleted-row filtering as in those searches;
  *   then rag_tokvec_rerank_dev over those rows. ids_out / scores_out [Q][k], cand_out [Q][pool] int64 (may be NULL) the candidate
  *   ids. 1 <= n_queries <= 65535, 0 < k <= pool <= 256. Bit-identical to rag_dense_topk_dev (mode 0) or rag_hybrid_sparse_rrf_dev
@@ -984,7 +1000,8 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
  *   top-`pool` and the sparse top-`pool` - what rag_rrf_fuse_dev over the two lists returns at top_k = 2 * pool, in RRF order,
  *   -1 padded - so 2 * pool candidate slots and pool <= 128. Tenant and deleted rows are filtered by the searches. ids_out /
  *   scores_out [Q][k], components_out [Q][k][3] (may be NULL), cand_out [Q][slots] int64 (may be NULL) the candidate ids, slots =
- *   pool or 2 * pool. 0 < k <= pool. Modes 1 and 2 need the query's terms and fresh, row-aligned sparse postings whatever
+ *   pool or 2 * pool. 0 < k <= pool. q_emb 16-byte aligned whatever w_dense is (the candidate search reads it). Modes 1 and 2
+ *   need the query's terms and fresh, row-aligned sparse postings whatever
  *   w_sparse is. Bit-identical to the search entries (rag_dense_topk_dev; rag_hybrid_sparse_rrf_dev at k = pool; rag_dense_topk_dev
  *   + rag_sparse_topk_dev + rag_rrf_fuse_dev at top_k = 2 * pool) followed by rag_m3_score_rows_dev on their rows. Workspaces
  *   are handle-owned and grown as the preamble says. After the candidate stage and the MaxSim launch: three launches (cosines,
@@ -1082,7 +1099,8 @@ int rag_m3_combine_gathered_dev(rag_handle_t h, const int64_t* cand_ids_dev, con
  *   the FINITE entries is the corpus maximum; with none (no document anywhere) the divisor is 1.0, as it is for a corpus maximum
  *   <= 0. Then the second half of rag_hybrid_linear_dev with that divisor: partial_out_dev [5][n_queries][k] int64 = ids | hybrid |
  *   semantic | keyword | temporal, the four score planes float64 bits, padded -1 / 0.0. world = 1 with the handle's own maxima
- *   gives the bits of rag_hybrid_linear_dev. The call consumes the begun state, whatever it returns. RAG_ERR_STATE: no begin
+ *   gives the bits of rag_hybrid_linear_dev. q_dev 16-byte aligned (else RAG_ERR_ARG). The call consumes the begun state,
+ *   whatever it returns. RAG_ERR_STATE: no begin
  *   before it; n_queries or the tenant argument (scalar against array, or other numbers) differ from the begin's; or the planes
  *   are gone - any *_host call on the handle in between (every write to the index or the postings is one, the live writes
  *   included), a device-pointer index load or append, or rag_hybrid_linear_dev / _tenants_dev, which reuse the workspace.

@@ -330,6 +330,7 @@ static int dense_topk_dev_entry(rag_handle_t h, const float* q_dev, int Q, int k
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_dev && ids_dev && scores_dev, "null pointer");
+    ARG_CHECK(h, aligned16(q_dev), "dense_topk: the queries (q_dev) must be 16-byte aligned");
     ARG_CHECK(h, Q > 0 && Q <= 65535, "1 <= n_queries <= 65535");
     DEV_ENTRY(h);
     entry_tenants t;
@@ -596,6 +597,7 @@ static int hybrid_rrf_entry(rag_handle_t h, const float* q_dev, const int32_t* t
     LOCK(h);
     ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid: 1 <= n_queries <= 65535");
     ARG_CHECK(h, q_dev && term_ptr_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid: null pointer");
+    ARG_CHECK(h, aligned16(q_dev), "hybrid: the queries (q_dev) must be 16-byte aligned");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid: 0 < pool <= 256");
     if (int rc = keyword_postings_aligned(h, false, "hybrid", RAG_OK)) return rc;
     DEV_ENTRY(h);
@@ -749,6 +751,7 @@ static int hybrid_sparse_rrf_entry(rag_handle_t h, const float* q_dev, const int
     LOCK(h);
     ARG_CHECK(h, Q > 0 && Q <= 65535, "hybrid_sparse: 1 <= n_queries <= 65535");
     ARG_CHECK(h, q_dev && term_ptr_dev && qweights_dev && lists_ws_dev && scores_ws_dev && keys_out_dev && rrf_out_dev, "hybrid_sparse: null pointer");
+    ARG_CHECK(h, aligned16(q_dev), "hybrid_sparse: the queries (q_dev) must be 16-byte aligned");
     ARG_CHECK(h, pool > 0 && pool <= RAG_MAX_K && k > 0, "hybrid_sparse: 0 < pool <= 256");
     if (int rc = keyword_postings_aligned(h, true, "hybrid_sparse", RAG_ERR_ARG)) return rc;
     DEV_ENTRY(h);
@@ -884,6 +887,7 @@ static int hybrid_linear_entry(rag_handle_t h, const float* q_dev, const int32_t
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, q_dev && term_ptr_dev && ids_out_dev && rows_out_dev && hybrid_out_dev, "hybrid_linear: null pointer");
+    ARG_CHECK(h, aligned16(q_dev), "hybrid_linear: the queries (q_dev) must be 16-byte aligned");
     if (int rc = linear_check_weights(h, Q, k, alpha, beta, gamma)) return rc;
     if (int rc = linear_check_index(h, Q, tenant, tenants_host)) return rc;
     DEV_ENTRY(h);
@@ -988,6 +992,7 @@ static int hybrid_linear_finish_entry(rag_handle_t h, const float* q_dev, const 
     const bool begun = h->lin_begun.on;
     h->lin_begun.on = false;            // consumed by this call, whatever comes of it
     ARG_CHECK(h, q_dev && gathered_max_dev && partial_out_dev, "hybrid_linear_finish: null pointer");
+    ARG_CHECK(h, aligned16(q_dev), "hybrid_linear_finish: the queries (q_dev) must be 16-byte aligned");
     ARG_CHECK(h, world > 0, "hybrid_linear_finish: need world > 0");
     if (int rc = linear_check_weights(h, Q, k, alpha, beta, gamma)) return rc;
     bool same = begun && Q == h->lin_begun.Q && h->n_rows == h->lin_begun.n_rows && h->lin_ws != nullptr;
@@ -1291,6 +1296,7 @@ int rag_retrieve_rerank_dev(rag_handle_t h, const float* q_emb_dev, const int32_
                             double* scores_out_dev, float* logits_out_dev, int64_t* cand_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_rerank: the query embeddings (q_emb_dev) must be 16-byte aligned");
     DEV_ENTRY(h);
     return retrieve_rerank_dev(h, q_emb_dev, term_ptr_dev, terms_dev, q_tok_dev, q_len_dev, Lq, Q, pool, k, rrf_k, tenant, mode,
                                cls_id, sep_id, L_pair, ids_out_dev, scores_out_dev, logits_out_dev, cand_out_dev,
@@ -1303,6 +1309,7 @@ int rag_retrieve_rerank_tenants_dev(rag_handle_t h, const float* q_emb_dev, cons
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "retrieve_rerank: null tenants array or bad n_queries");
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_rerank: the query embeddings (q_emb_dev) must be 16-byte aligned");
     DEV_ENTRY(h);
     entry_tenants t;
     if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
@@ -1414,6 +1421,8 @@ int rag_retrieve_maxsim_dev(rag_handle_t h, const float* q_emb_dev, const int32_
                             int tenant, int mode, int64_t* ids_out_dev, double* scores_out_dev, int64_t* cand_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_maxsim: the query embeddings (q_emb_dev) must be 16-byte aligned");
+    ARG_CHECK(h, aligned16(q_vecs_dev), "retrieve_maxsim: the query's token vectors (q_vecs_dev) must be 16-byte aligned");
     DEV_ENTRY(h);
     return retrieve_maxsim_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, Q, pool, k, rrf_k, tenant, mode,
                                ids_out_dev, scores_out_dev, cand_out_dev, (hipStream_t)stream, {nullptr, nullptr});
@@ -1425,6 +1434,8 @@ int rag_retrieve_maxsim_tenants_dev(rag_handle_t h, const float* q_emb_dev, cons
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, tenants_host && Q > 0 && Q <= 65535, "retrieve_maxsim: null tenants array or bad n_queries");
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_maxsim: the query embeddings (q_emb_dev) must be 16-byte aligned");
+    ARG_CHECK(h, aligned16(q_vecs_dev), "retrieve_maxsim: the query's token vectors (q_vecs_dev) must be 16-byte aligned");
     DEV_ENTRY(h);
     entry_tenants t;
     if (int rc = entry_tenants_of(h, -1, tenants_host, Q, (hipStream_t)stream, &t)) return rc;
@@ -1465,6 +1476,7 @@ int rag_retrieve_m3_dev(rag_handle_t h, const float* q_emb_dev, const int32_t* t
                         double* scores_out_dev, double* components_out_dev, int64_t* cand_out_dev, void* stream) {
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_m3: the query embeddings (q_emb_dev) must be 16-byte aligned (the candidate search reads them whatever the dense weight)");
     DEV_ENTRY(h);
     return retrieve_m3_dev(h, q_emb_dev, term_ptr_dev, terms_dev, qweights_dev, q_vecs_dev, q_off_dev, n_queries, pool, k, rrf_k, tenant, mode,
                            w_dense, w_sparse, w_colbert, ids_out_dev, scores_out_dev, components_out_dev, cand_out_dev, (hipStream_t)stream,
@@ -1505,6 +1517,7 @@ int rag_retrieve_m3_tenants_dev(rag_handle_t h, const float* q_emb_dev, const in
     if (!h) return RAG_ERR_ARG;
     LOCK(h);
     ARG_CHECK(h, tenants_host && n_queries > 0 && n_queries <= 65535, "retrieve_m3: null tenants array or bad n_queries");
+    ARG_CHECK(h, aligned16(q_emb_dev), "retrieve_m3: the query embeddings (q_emb_dev) must be 16-byte aligned (the candidate search reads them whatever the dense weight)");
     DEV_ENTRY(h);
     entry_tenants t;
     if (int rc = entry_tenants_of(h, -1, tenants_host, n_queries, (hipStream_t)stream, &t)) return rc;

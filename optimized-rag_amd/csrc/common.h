@@ -334,6 +334,10 @@ static int raise_lds(rag_ctx* h, int& have, int need, K... kernels) {
         }                                                                                     \
     } while (0)
 
+// a caller array that a kernel reads 16 bytes at a time (float4: exact_norm2_wave, exact_cosine_wave, normalize_rows_kernel, the
+// MaxSim row loads): the entry refuses any other address before it enqueues anything (include/rag_hip.h says "16-byte aligned")
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---- row visibility: the one predicate every search kernel applies to an index row. vis = rag_ctx::vis when rows are

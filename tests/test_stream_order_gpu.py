@@ -155,10 +155,9 @@ def case_dense(Q=QBIG, k=10):
     return Case(("index",), {}, dict(q=np.zeros((Q, D), np.float32)), dict(q=w["q"][np.arange(Q) % QBIG]), bind)
 
 
-def case_merge():
+def case_merge(L=3, Q=40, k=10):
     import torch
     rng = np.random.default_rng(1)
-    L, Q, k = 3, 40, 10
     ids = np.stack([rng.permutation(100000)[:Q * k].reshape(Q, k) + l * 100000 for l in range(L)]).astype(np.int64)
     sc = -np.sort(-rng.random((L, Q, k)), axis=2)
 
@@ -171,10 +170,9 @@ def case_merge():
     return Case((), {}, dict(ids=np.full_like(ids, -1), sc=np.zeros_like(sc)), dict(ids=ids, sc=sc), bind)
 
 
-def case_fuse_gathered():
+def case_fuse_gathered(W=2, Q=40, pool=20, k=10):
     import torch
     rng = np.random.default_rng(2)
-    W, Q, pool, k = 2, 40, 20, 10
     g = np.empty((W, 4, Q, pool), np.int64)
     for r in range(W):
         g[r, 0] = rng.permutation(50000)[:Q * pool].reshape(Q, pool) + r * 50000
@@ -199,9 +197,8 @@ def rrf_lists(rng, Q, n_lists, ln):
     return np.stack([np.stack([rng.permutation(3 * ln)[:ln] for _ in range(n_lists)]) for _ in range(Q)]).astype(np.int64)
 
 
-def case_rrf():
+def case_rrf(Q=40, n_lists=2, ln=20, k=10):
     import torch
-    Q, n_lists, ln, k = 40, 2, 20, 10
     lists = rrf_lists(np.random.default_rng(3), Q, n_lists, ln)
 
     def bind(eng):
@@ -260,13 +257,12 @@ def case_hybrid_linear(Q=QBIG, k=10, big=False):
     return Case((("big", "temporal") if big else ("index", "bm25", "temporal")), dict(bm25_plan_slots=8), wrong, real, bind)
 
 
-def case_mmr(variant=0):
+def case_mmr(variant=0, Q=24, pool=40, k=8):
     import torch
     w = world()
     rng = np.random.default_rng(4)
-    Q, pool, k = 24, 40, 8
     rows = np.stack([rng.choice(N, pool, replace=False) for _ in range(Q)]).astype(np.int32)
-    rows[1, 30:] = -1
+    rows[min(1, Q - 1), 3 * pool // 4:] = -1
 
     def bind(eng):
         def call(d, s):
@@ -304,13 +300,12 @@ def case_embed(P=100, L=64):
     return Case(("embed",), dict(ce_chunk_tokens=4096), wrong_pairs(P, L), real, bind)
 
 
-def case_build_pairs():
+def case_build_pairs(Q=12, pool=16, Lq=6, L=32):
     import torch
     w = world()
     rng = np.random.default_rng(7)
-    Q, pool, Lq, L = 12, 16, 6, 32
     cand = rng.integers(0, N, (Q, pool)).astype(np.int64)
-    cand[0, 10:] = -1
+    cand[0, 5 * pool // 8:] = -1
     real = dict(q_tok=rng.integers(200, 2000, (Q, Lq)).astype(np.int32), q_len=rng.integers(1, Lq + 1, Q).astype(np.int32), cand=cand)
     wrong = dict(q_tok=np.zeros((Q, Lq), np.int32), q_len=np.ones(Q, np.int32), cand=np.full_like(cand, -1))
 
@@ -323,12 +318,11 @@ def case_build_pairs():
     return Case(("tokens",), {}, wrong, real, bind)
 
 
-def case_rerank_topk():
+def case_rerank_topk(Q=12, pool=16, k=5):
     import torch
     rng = np.random.default_rng(8)
-    Q, pool, k = 12, 16, 5
     cand = rng.permutation(1000)[:Q * pool].reshape(Q, pool).astype(np.int64)
-    cand[2, ::3] = -1
+    cand[min(2, Q - 1), ::3] = -1
     real = dict(logits=rng.standard_normal(Q * pool).astype(np.float32), cand=cand)
     wrong = dict(logits=np.zeros(Q * pool, np.float32), cand=np.full_like(cand, -1))
 

@@ -445,11 +445,10 @@ def case_retrieve_m3(mode, per_query=False, n=QBIG):
     return Case(("index", "tenants", "sparse", "tokvec"), {}, blank(real, terms=-1), real, bind)
 
 
-def case_maxsim(n=Q):
+def case_maxsim(n=Q, n_docs=60, n_pairs=200):
     import torch
     w = world()
     rng = np.random.default_rng(24)
-    n_docs, n_pairs = 60, 200
     d, do = w["d_vecs"][:w["d_off"][n_docs]], w["d_off"][:n_docs + 1]
     pq, pd = rng.integers(-1, n + 1, n_pairs).astype(np.int32), rng.integers(-1, n_docs + 1, n_pairs).astype(np.int32)
     v = vecs(n)
@@ -473,10 +472,9 @@ def texts(n=Q):
     return dict(ids=np.array(w["tid"][:n]), w=wt, lens=np.array(w["tlen"][:n]))
 
 
-def case_lexical_match(n=Q):
+def case_lexical_match(n=Q, n_pairs=120):
     import torch
     rng = np.random.default_rng(26)
-    n_pairs = 120
     real = dict(**texts(n), pq=rng.integers(-1, n + 1, n_pairs).astype(np.int32), pd=rng.integers(-1, n + 1, n_pairs).astype(np.int32))
 
     def bind(eng):
