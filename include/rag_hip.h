@@ -76,7 +76,7 @@ int rag_synchronize(rag_handle_t h);
 /* Diagnostic / tuning switch of one handle (no reference counterpart). Every switch <name> takes its default from the
  * environment variable RAG_<NAME> ONCE, when rag_create runs; afterwards only this call changes it. Names: force_level,
  * stage_growth, no_smallq, no_second_pass, dense_linear_order, bm25_first_ranges, bm25_no_staging, bm25_packed, bm25_linear_grid, bm25_sort_merge, no_fork,
- * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, sparse_tail_fold, tokvec_compact_rows, ce_chunk_tokens, ce_mx, ce_attn_stream, ce_ffn_fused (DESIGN.md section 6;
+ * fork_max_q, bm25_plan_slots, bm25_ws_mb, bm25_tail_fold, bm25_keep_tf, sparse_tail_fold, tokvec_compact_rows, tokvec_scan_ws_mb, tokvec_scan_queries, ce_chunk_tokens, ce_mx, ce_attn_stream, ce_ffn_fused (DESIGN.md section 6;
  * ce_attn_stream: 0 = attention of 64-wide heads above length class 512 by the streamed kernel, -1 = by the global-memory form at
  * every class above 256, 1 = by the streamed kernel at every class above 512 whatever the default there - the same bits in all
  * three; ce_ffn_fused: the two FFN GEMMs of an MX layer as one launch (0 = where its per-workgroup slots fit
@@ -909,6 +909,23 @@ int rag_rerank_topk_dev(rag_handle_t h, const float* logits_dev, const int64_t* 
  *   ids. 1 <= n_queries <= 65535, 0 < k <= pool <= 256. Bit-identical to rag_dense_topk_dev (mode 0) or rag_hybrid_sparse_rrf_dev
  *   with k = pool (mode 1) followed by rag_tokvec_rerank_dev on the rows. Needs store documents == index rows, else RAG_ERR_STATE.
  *   Workspaces are handle-owned and grown as the preamble says (the first call of a larger shape frees the old one, which waits).
+ *   mode 2, the exhaustive MaxSim search: no candidate stage. For each query the result is the top-`pool` of
+ *     score[q][d] = (1 / nq) * sum_i max_r <vq[i], store[d][r]>
+ *   over EVERY document d of the store that the query may see - not deleted, and of the query's tenant when one is given (the
+ *   predicate of the other searches) - score descending, the lower row first on equal scores. ids_out / scores_out [Q][k] are the
+ *   first k of that list (ids by the index's id mapping, scores the float32 pair score widened); cand_out [Q][pool] (may be NULL)
+ *   holds the ids of the whole top-`pool` in that order; padding -1 / 0.0. A document without rows and a query without rows score
+ *   0.0 and are never listed, as in rag_tokvec_rerank_dev. q_emb, term_ptr, terms, qweights and rrf_k are not read, and q_emb may
+ *   be NULL in this mode only. Every other check of the entry holds: a usable store that is not stale and holds exactly the
+ *   index's rows (else RAG_ERR_STATE), the tenant table when a tenant is asked for, q_vecs 16-byte aligned,
+ *   1 <= n_queries <= 65535, 0 < k <= pool <= 256, n_queries * pool < 2^24. BIT-IDENTITY: for every listed (query, row),
+ *   scores_out has the bits rag_tokvec_rerank_dev reports for that pair, in both storage forms - the scan scores a pair by the
+ *   rerank kernel's own MFMA sequence, row maxima and float64 sum, and the call's last step is that rerank over the scan's
+ *   top-`pool` rows. Cost: 2 * nq * nd * dim FLOP per pair and twice that issued (hi + lo query halves), over every visible
+ *   document: a search for per-tenant corpora and mid-sized stores, an exact baseline on larger ones.
+ *   The scan writes one 4-byte key per (query, document) of a sub-batch of Qb queries into a plane of the call's handle-owned workspace; option
+ *   tokvec_scan_ws_mb (default 2048) bounds the plane, Qb = max(1, min(Q, bound / (4 * documents))), option tokvec_scan_queries
+ *   (default 0 = derived) sets Qb itself. The same bits for every Qb. Modes 0 and 1 are unchanged by mode 2, workspace included.
  * Live writes, as the BM25 postings: rag_index_compact / rag_index_compact_bm25 mark the store STALE when deleted rows are removed
  * (rag_index_compact_live moves the store's documents with their rows instead and does not);
  *   every rag_tokvec_rerank_* and rag_retrieve_maxsim_dev then returns RAG_ERR_STATE until rag_tokvec_reserve / rag_tokvec_load_host

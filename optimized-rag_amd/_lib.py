@@ -1345,6 +1345,32 @@ class RagEngine:
                        int(k), int(rrf_k), _ptr(t) if per_query else t, mode, p(ids), p(sc), p(cand), st), name)
         return ids, sc, cand
 
+    def tokvec_search_dev(self, q_vecs, q_off, k, pool=None, tenant=-1, stream=None):
+        """Exhaustive MaxSim search (mode 2 of rag_retrieve_maxsim_dev): every document of the resident token-vector store that
+        the query may see is scored against the query's token vectors (CUDA tensors: q_vecs float32 [rows, dim], q_off int64
+        [Q + 1]); no candidate stage, no query embedding. tenant: an int, or one number per query. pool (default k, at most 256)
+        is how many of the best are ranked. Returns (ids [Q, k] int64, scores [Q, k] float64, candidates [Q, pool] int64 = the
+        ids of the whole top-pool): score descending, the lower row first on equal scores, -1 / 0.0 padded; a score has the bits
+        tokvec_rerank_dev reports for the pair. Asynchronous on `stream`."""
+        import torch
+        Q, dev = int(q_off.shape[0]) - 1, q_vecs.device
+        pool = int(k) if pool is None else int(pool)
+        key = ("ts", Q, pool, int(k), str(dev))
+        if getattr(self, "_ts_key", None) != key:
+            self._ts = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float64, device=dev),
+                        torch.empty((Q, pool), dtype=torch.int64, device=dev))
+            self._ts_key = key
+        ids, sc, cand = self._ts
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        self._tokvec_rerank_check(tuple(q_vecs.shape), None, "tokvec_search_dev")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        per_query, t = _tenant_arg(tenant, Q)
+        fn, name = ((self.lib.rag_retrieve_maxsim_tenants_dev, "rag_retrieve_maxsim_tenants_dev") if per_query
+                    else (self.lib.rag_retrieve_maxsim_dev, "rag_retrieve_maxsim_dev"))
+        self._check(fn(self.h, None, None, None, None, p(q_vecs), p(q_off), int(Q), int(pool), int(k), 60,
+                       _ptr(t) if per_query else t, 2, p(ids), p(sc), p(cand), st), name + " (mode 2)")
+        return ids, sc, cand
+
     # ---- the three-way bge-m3 score over resident data (rag_sparse_score_rows_*, rag_m3_score_rows_dev, rag_retrieve_m3_dev) ----
     def sparse_score_rows(self, term_ptr, terms, weights, cand_rows):
         """The exact learned-sparse score of given rows: weighted queries (CSR as sparse_topk) and int32 rows [Q, pool] -> float64

@@ -18,6 +18,7 @@ static const struct { const char* name; int rag_options::*field; } g_options[] =
     {"bm25_packed", &rag_options::bm25_packed},         {"bm25_plan_slots", &rag_options::bm25_plan_slots},       {"bm25_ws_mb", &rag_options::bm25_ws_mb},
     {"bm25_tail_fold", &rag_options::bm25_tail_fold},     {"bm25_keep_tf", &rag_options::bm25_keep_tf},
     {"sparse_tail_fold", &rag_options::sparse_tail_fold}, {"tokvec_compact_rows", &rag_options::tokvec_compact_rows},
+    {"tokvec_scan_ws_mb", &rag_options::tokvec_scan_ws_mb}, {"tokvec_scan_queries", &rag_options::tokvec_scan_queries},
     {"bm25_linear_grid", &rag_options::bm25_linear_grid},            {"bm25_sort_merge", &rag_options::bm25_sort_merge},
     {"no_fork", &rag_options::no_fork},                 {"fork_max_q", &rag_options::fork_max_q},
     {"ce_chunk_tokens", &rag_options::ce_chunk_tokens}, {"ce_mx", &rag_options::ce_mx},

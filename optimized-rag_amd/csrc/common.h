@@ -77,6 +77,8 @@ struct rag_options {
     int bm25_tail_fold = 0;       // appended postings: an append folds the tail into the base once it holds more than this many documents (-1 = never, 0 = the default policy, bm25.hip bm_default_fold_docs)
     int sparse_tail_fold = 0;     // the same for appended learned-sparse postings (rag_sparse_append_host)
     int tokvec_compact_rows = 0;  // rag_index_compact_live: token rows per staging chunk of the token-vector move (0 = sized from the staging bound); tests force a small value
+    int tokvec_scan_ws_mb = 0;    // exhaustive MaxSim search (rag_retrieve_maxsim_dev mode 2): bound of the key plane [Qb][documents] in MiB (0 = 2048): batches beyond it run in sub-batches of Qb queries
+    int tokvec_scan_queries = 0;  // ... or Qb itself (0 = derived from the bound); tests force small values
     int no_fork = 0;              // keep the BM25 leg of a small hybrid batch in line on the caller's stream
     int fork_max_q = 0;           // largest batch whose BM25 leg runs on the side stream beside the dense leg (0 = RAG_FORK_MAX_Q)
     int ce_chunk_tokens = 0;      // activation chunk size in tokens (0 = sized from the model)
@@ -683,6 +685,12 @@ int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const i
                   int32_t* rows_out, double* scores_out, float* pair_scores_out, hipStream_t st);
 int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,
                        int32_t* rows_out, double* scores_out, float* pair_scores_out);
+// every visible document of the store against every query: rows_out [Q][pool] int32 = each query's top-pool rows in rank order
+// (score desc, row asc), -1 padded. plane = [tokvec_scan_batch(h, Q)][tv_docs] uint32 of the caller's workspace: the keys of one
+// sub-batch of queries. The caller has checked the store, the index and the shape (retrieve_maxsim_dev, mode 2).
+int tokvec_scan_batch(const rag_ctx* h, int Q);
+int tokvec_scan(rag_ctx* h, const float* q_vecs, const int64_t* q_off, int Q, int pool, int tenant, query_tenants qt, uint32_t* plane,
+                int32_t* rows_out, hipStream_t st);
 int tokvec_topk(rag_ctx* h, const float* scores_dev, const int32_t* slot_rows_dev, int Q, int pool, int k, int64_t* ids_out, int32_t* rows_out,
                 double* scores_out, hipStream_t st);
 int tokvec_score_slots(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, const float** scores_out,

@@ -442,13 +442,16 @@ int retrieve_rerank_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
 // the cross-encoder, with the resident token vectors (tokvec.hip) in place of the token store and the forward.
 //   1. candidates: dense top-pool (mode 0) or dense + learned-sparse RRF -> top-pool (mode 1), tenant and deleted rows filtered
 //   2. tokvec_maxsim_kernel over the [Q][pool] candidate rows   3. the raw top-k of rerank_topk_kernel (which maps the ids)
+// mode 2 has no candidate stage: tokvec_scan (tokvec.hip) scores every visible document of the store and hands over each query's
+// top-pool rows in rank order; steps 2 and 3 then run over those rows as they are, so a listed pair's score is the rerank kernel's
+// own. cand_out is the same ranking at k = pool. q_emb, the query's terms and rrf_k are not read; its planes are carved in mode 2 only.
 int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_ptr_dev, const int32_t* terms_dev, const float* qweights_dev,
                         const float* q_vecs_dev, const int64_t* q_off_dev, int Q, int pool, int k, int rrf_k, int tenant, int mode,
                         int64_t* ids_out, double* scores_out, int64_t* cand_out, hipStream_t st, query_tenants qt) {
     if (int rc = tokvec_usable(h, "retrieve_maxsim")) return rc;
     ARG_CHECK(h, Q > 0 && Q <= 65535 && pool > 0 && pool <= RAG_MAX_K && k > 0 && k <= pool, "retrieve_maxsim: 1 <= n_queries <= 65535, 0 < k <= pool <= 256");
-    ARG_CHECK(h, q_emb_dev && q_vecs_dev && q_off_dev && ids_out && scores_out, "retrieve_maxsim: null argument");
-    ARG_CHECK(h, mode == 0 || mode == 1, "retrieve_maxsim: mode is 0 (dense) or 1 (dense + sparse)");
+    ARG_CHECK(h, (q_emb_dev || mode == 2) && q_vecs_dev && q_off_dev && ids_out && scores_out, "retrieve_maxsim: null argument");
+    ARG_CHECK(h, mode == 0 || mode == 1 || mode == 2, "retrieve_maxsim: mode is 0 (dense), 1 (dense + sparse) or 2 (every document)");
     ARG_CHECK(h, h->index_loaded, "retrieve_maxsim: no index loaded");
     if (int rc = tokvec_covers_index(h, "retrieve_maxsim")) return rc;
     ARG_CHECK(h, (tenant < 0 && qt.host == nullptr) || h->tenants != nullptr, "retrieve_maxsim: tenant filter requested but no tenants loaded");
@@ -457,6 +460,25 @@ int retrieve_maxsim_dev(rag_ctx* h, const float* q_emb_dev, const int32_t* term_
         if (int rc = keyword_postings_aligned(h, true, "retrieve_maxsim", RAG_ERR_ARG)) return rc;
     }
     const size_t P = (size_t)Q * pool;
+    if (mode == 2) {
+        ARG_CHECK(h, (int64_t)Q * pool < ((int64_t)1 << 24), "retrieve_maxsim: n_queries * pool must be below 2^24");
+        ARG_CHECK(h, (tenant < 0 && qt.host == nullptr) || tenants_cover(h, h->n_rows), "retrieve_maxsim: the tenant table does not cover the index's rows");
+        int32_t* rows;
+        double* cand_sc;
+        uint32_t* plane;
+        int rc = pipe_ws_carve(h, [&](ws_carve& c) {
+            rows = c.take<int32_t>(P);                           // each query's top-pool rows, rank order
+            cand_sc = c.take<double>(cand_out ? P : 0);          // the scores beside cand_out: nobody reads them
+            plane = c.take<uint32_t>((size_t)tokvec_scan_batch(h, Q) * (size_t)h->tv_docs);      // the scan's keys of one sub-batch
+        });
+        if (rc) return rc;
+        if ((rc = tokvec_scan(h, q_vecs_dev, q_off_dev, Q, pool, tenant, qt, plane, rows, st))) return rc;
+        const float* sc;
+        const int32_t* slot;
+        if ((rc = tokvec_score_slots(h, q_vecs_dev, q_off_dev, rows, Q, pool, &sc, &slot, st))) return rc;
+        if ((rc = tokvec_topk(h, sc, slot, Q, pool, k, ids_out, nullptr, scores_out, st))) return rc;
+        return cand_out ? tokvec_topk(h, sc, slot, Q, pool, pool, cand_out, nullptr, cand_sc, st) : RAG_OK;
+    }
     cand_ws w;
     int rc = pipe_ws_carve(h, [&](ws_carve& c) { cand_ws_planes(c, w, P, P, true); });
     if (rc) return rc;

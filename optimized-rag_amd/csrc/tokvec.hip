@@ -6,6 +6,8 @@
 //   tokvec_quant8_kernel      float32 -> block amax, scale exponent, E4M3 codes and the E8M0 scale byte; the same count
 //   tokvec_offsets_kernel     a block's offsets, relative to its first, behind the store's; counting decreasing ones
 //   tokvec_maxsim_kernel      score[q][j] = (1 / nq) * sum_i max_r <vq[i], store[cand[q][j]][r]>
+//   tokvec_scan_kernel        the same score of EVERY visible document for every query, document-stationary (mode 2 of
+//   tokvec_scan_select_kernel rag_retrieve_maxsim_dev: the exhaustive search), and the exact top-pool of a query's scores
 //
 // tokvec_maxsim_kernel carries over m3_maxsim_kernel's fragment map and masking (m3_heads.hip): lane (fr = lane & 15, fq = lane >> 4)
 // holds A[row fr][k = 8 fq ..+8] and B[col fr][the same k], acc[r] = C[row 4 fq + r][col fr]; A = 16 document rows, B = 16 query
@@ -358,6 +360,174 @@ __global__ __launch_bounds__(256) void tokvec_maxsim_kernel(const float* __restr
     }
 }
 
+// ---- exhaustive MaxSim search (rag_retrieve_maxsim_dev, mode 2): every visible document against every query of the batch ------
+// tokvec_scan_kernel is document-stationary: workgroup (d, g) owns document d and loops over the G queries of group g, so a stored
+// row comes from HBM once per query group and from L1 / L2 for the group's other queries - not once per pair, as the rerank grid
+// reads it. The host picks G so that a few hundred documents still give every CU several workgroups (tokvec_scan).
+// The bits are the rerank kernel's, by three things that are the same here and there, whatever iterates around them:
+//   1. a pair's float32 dot products come from tv_query_block / tv_query_block_q8, unchanged: document-relative 16-row tiles,
+//      clamped row loads, one accumulator per (tile, query tile), K-steps ascending, per step lo_q * d then hi_q * d on
+//      mfma_f32_16x16x32_f16 with the passage as the exact fp16 A operand; which of the two instantiations (2 or 4 tiles per
+//      wave) runs is the same function of the document's own row count;
+//   2. the maximum of a query row over the document's rows (lanes, then waves through LDS) is order-free;
+//   3. one thread sums the maxima in query-row order in float64 and stores (float)(total / nq).
+// What the kernel writes is the score's orderable key (f32_orderable: larger key = higher score), 0 = "not ranked": a pair whose
+// document the query may not see (row_visible with the query's own tenant), a document without rows, a query without rows.
+// Those tests are made once per workgroup, 256 pairs at a time, and leave the group's ranked queries as an ascending list in LDS:
+// the loop below runs over that list alone, and a document nobody in the group may see ends there - a tenant's search pays the
+// MFMA work of the tenant's documents only. Every workgroup walks the queries in the same order, so neighbours share them in L2. A real score never
+// has key 0 (that is the NaN of all ones). Plane [Qb][n_docs], written whole by every launch: nothing of an earlier call is read.
+#define TV_SCAN_G 1024     // most queries one workgroup of the scan loops over
+template <int FORM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void tokvec_scan_kernel(const float* __restrict__ q, const int64_t* __restrict__ q_off,
+                                                           const typename tv_doc<FORM>::elem* __restrict__ store,
+                                                           const int64_t* __restrict__ d_off, int64_t n_docs, const int32_t* __restrict__ vis,
+                                                           const int32_t* __restrict__ qten, int tenant, int q_first, int n_q, int G, int dim,
+                                                           uint32_t* __restrict__ plane) {
+    __shared__ float wmax[4][TV_QT * 16];
+    __shared__ unsigned short qlist[TV_SCAN_G];                  // the group's ranked queries, ascending, relative to g0
+    __shared__ int wcnt[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int64_t di = blockIdx.x;
+    const int g0 = blockIdx.y * G, g1 = min(g0 + G, n_q);         // this workgroup's queries, relative to q_first; G <= TV_SCAN_G
+    const int64_t d0 = d_off[di], nd = d_off[di + 1] - d0;
+    int n_list = 0;
+    for (int c0 = g0; c0 < g1; c0 += 256) {                      // 256 pairs at a time: unranked ones are written, ranked ones listed in order
+        const int ql = c0 + tid;
+        bool is_ranked = false;
+        if (ql < g1) {
+            const int qi = q_first + ql;
+            is_ranked = nd > 0 && q_off[qi + 1] > q_off[qi] && row_visible(vis, di, tenant_of_query(qten, qi, tenant));
+            if (!is_ranked) plane[(size_t)ql * n_docs + di] = 0u;
+        }
+        const unsigned long long m = __ballot(is_ranked);
+        if (lane == 0) wcnt[wv] = __popcll(m);
+        __syncthreads();
+        int at = n_list;
+        for (int w = 0; w < wv; ++w) at += wcnt[w];
+        if (is_ranked) qlist[at + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)(ql - g0);
+        n_list += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (n_list == 0) return;                                     // a document no query of the group may see costs this much
+    const int64_t nd_tiles = (nd + 15) >> 4;
+    const typename tv_doc<FORM>::elem* doc = store + d0 * tv_doc<FORM>::stride(dim);
+    for (int i = 0; i < n_list; ++i) {
+        const int ql = g0 + qlist[i], qi = q_first + ql;
+        const int64_t q0 = q_off[qi], nq = q_off[qi + 1] - q0;
+        double total = 0.0;                                    // thread 0 alone
+        for (int64_t qb = 0; qb < nq; qb += TV_QT * 16) {
+            const float* qp[TV_QT];
+            float best[TV_QT];
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) {
+                const int64_t row = min(qb + j * 16 + fr, nq - 1);
+                qp[j] = q + (q0 + row) * dim + fq * 8;
+                best[j] = -INFINITY;
+            }
+            if constexpr (FORM == RAG_TOKVEC_MXFP8) {
+                if (nd_tiles > 8) tv_query_block_q8<4>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+                else tv_query_block_q8<2>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+            } else {
+                if (nd_tiles > 8) tv_query_block<4, FORM>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+                else tv_query_block<2, FORM>(doc, nd, nd_tiles, qp, dim, wv, fr, fq, best);
+            }
+#pragma unroll
+            for (int j = 0; j < TV_QT; ++j) {
+                best[j] = fmaxf(best[j], __shfl_xor(best[j], 16));
+                best[j] = fmaxf(best[j], __shfl_xor(best[j], 32));
+                if (lane < 16) wmax[wv][j * 16 + lane] = best[j];
+            }
+            __syncthreads();
+            if (tid == 0)
+                for (int i = 0; i < TV_QT * 16 && qb + i < nq; ++i)
+                    total += (double)fmaxf(fmaxf(wmax[0][i], wmax[1][i]), fmaxf(wmax[2][i], wmax[3][i]));
+            __syncthreads();
+        }
+        if (tid == 0) plane[(size_t)ql * n_docs + di] = f32_orderable((float)(total / (double)nq));
+    }
+}
+
+// The exact select: one workgroup per query of the sub-batch over its plane row -> the query's top-pool rows in rank order (score
+// desc, row asc), -1 padded. A ranked pair's sort key is make_key's (score key << 32 | ~row): distinct for distinct rows, so the
+// pool-th largest key T is one pair and "key >= T" is exactly the top-pool. T comes from a radix select, 8 bits per pass from the
+// top, over the keys that still match the chosen prefix; it stops as soon as the pairs that match are exactly the ones still
+// wanted (with distinct scores: after the 4 score passes at the latest). Unranked pairs have key 0, are never counted and never
+// taken; with fewer ranked pairs than `pool` the first pass says so and all of them are taken. The at
+// most 256 survivors are gathered in any order and placed by counting the keys above each: the order of the atomics shows nowhere.
+__global__ __launch_bounds__(256) void tokvec_scan_select_kernel(const uint32_t* __restrict__ plane, int64_t n_docs, int pool,
+                                                                  int32_t* __restrict__ rows_out) {
+    __shared__ unsigned hist[256];
+    __shared__ uint64_t top[RAG_MAX_K];
+    __shared__ unsigned s_sel, s_need, s_cnt, n_top;
+    const int tid = threadIdx.x;
+    const uint32_t* row = plane + (size_t)blockIdx.x * n_docs;
+    auto key_of = [&](int64_t d) -> uint64_t {
+        const uint32_t s = row[d];
+        return s ? ((uint64_t)s << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)d) : 0ull;
+    };
+    uint64_t prefix = 0, mask = 0;
+    unsigned need = (unsigned)min((int64_t)pool, n_docs);        // after the first pass at least `need` ranked keys match the prefix
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hist[tid] = 0u;
+        __syncthreads();
+        // scores of one batch share their leading bits: a thread adds a run of equal digits once, or every lane of every wave
+        // would queue for the same counter
+        unsigned run = 0u, run_bin = 0u;
+        for (int64_t d = tid; d < n_docs; d += 256) {
+            const uint64_t key = key_of(d);
+            if (key == 0ull || (key & mask) != prefix) continue;
+            const unsigned bin = (unsigned)(key >> shift) & 255u;
+            if (bin == run_bin) { ++run; continue; }
+            if (run) atomicAdd(&hist[run_bin], run);
+            run_bin = bin;
+            run = 1u;
+        }
+        if (run) atomicAdd(&hist[run_bin], run);
+        __syncthreads();
+        if (tid == 0) {
+            unsigned left = need;
+            int b = 255;
+            for (; b >= 0 && hist[b] < left; --b) left -= hist[b];
+            s_sel = (unsigned)(b < 0 ? 256 : b);                 // 256: fewer ranked keys than wanted (the first pass alone can find that)
+            s_need = left;
+            s_cnt = b < 0 ? 0u : hist[b];
+            n_top = 0u;
+        }
+        __syncthreads();
+        const unsigned sel = s_sel;
+        const bool all = sel == 256u || s_cnt == s_need;         // every ranked key under this prefix is wanted: T = the prefix, zeros below
+        if (sel != 256u) prefix |= (uint64_t)sel << shift;
+        mask |= (uint64_t)0xff << shift;
+        need = s_need;
+        __syncthreads();
+        if (all) break;
+    }
+    const uint64_t thr = prefix > 1ull ? prefix : 1ull;
+    for (int64_t d = tid; d < n_docs; d += 256) {
+        const uint64_t key = key_of(d);
+        if (key >= thr) {
+            const unsigned at = atomicAdd(&n_top, 1u);
+            if (at < (unsigned)pool) top[at] = key;              // never more than pool: the keys are distinct
+        }
+    }
+    __syncthreads();
+    const int n = (int)min(n_top, (unsigned)pool);
+    if (tid < pool) {
+        int32_t* out = rows_out + (size_t)blockIdx.x * pool;
+        if (tid < n) {
+            const uint64_t mine = top[tid];
+            int rank = 0;
+            for (int i = 0; i < n; ++i) rank += top[i] > mine;
+            out[rank] = (int32_t)key_row(mine);
+        } else {
+            out[tid] = -1;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
@@ -677,6 +847,44 @@ int tokvec_rerank(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const i
     if (int rc = tokvec_score_slots(h, q_vecs, q_off, cand_rows, Q, pool, &sc, &slot, st)) return rc;
     if (pair_scores_out) HIP_TRY(h, hipMemcpyAsync(pair_scores_out, sc, P * sizeof(float), hipMemcpyDeviceToDevice, st));
     return tokvec_topk(h, sc, slot, Q, pool, k, ids_out, rows_out, scores_out, st);
+}
+
+// The exhaustive search's candidate stage: scan + select per sub-batch of Qb queries, Qb from the plane's bound (options
+// tokvec_scan_ws_mb / tokvec_scan_queries). The plane is carved from the call's workspace by the caller; a sub-batch's select has
+// read it before the next scan of the same stream writes it.
+// Query groups: a workgroup loops over G queries of one document. With many documents G = Qb (a stored row leaves HBM once per
+// sub-batch); with few, the queries are split so that documents x groups stays near 8 workgroups per CU.
+int tokvec_scan_batch(const rag_ctx* h, int Q) {
+    if (h->opt.tokvec_scan_queries > 0) return std::min(Q, h->opt.tokvec_scan_queries);
+    const size_t cap = (size_t)(h->opt.tokvec_scan_ws_mb > 0 ? h->opt.tokvec_scan_ws_mb : 2048) << 20;
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)Q, cap / (4 * (size_t)std::max<int64_t>(h->tv_docs, 1))));
+}
+
+int tokvec_scan(rag_ctx* h, const float* q_vecs, const int64_t* q_off, int Q, int pool, int tenant, query_tenants qt, uint32_t* plane,
+                int32_t* rows_out, hipStream_t st) {
+    const int64_t n_docs = h->tv_docs;
+    if (n_docs == 0) {                                           // an empty index: nothing to rank
+        HIP_TRY(h, hipMemsetAsync(rows_out, 0xff, (size_t)Q * pool * sizeof(int32_t), st));
+        return RAG_OK;
+    }
+    const int Qb = tokvec_scan_batch(h, Q);
+    // per-query tenants: some query is filtered, so the table is needed as under a scalar filter
+    const int32_t* vis = h->vis ? h->vis.get() : (tenant >= 0 || qt.dev != nullptr) ? h->tenants.get() : nullptr;
+    const int64_t want = 8 * (int64_t)std::max(h->n_cu, 1);
+    for (int q0 = 0; q0 < Q; q0 += Qb) {
+        const int nb = std::min(Qb, Q - q0);
+        const int groups = (int)std::min<int64_t>(nb, std::max<int64_t>(1, (want + n_docs - 1) / n_docs));
+        const int G = std::min((nb + groups - 1) / groups, TV_SCAN_G);
+        const dim3 grid((unsigned)n_docs, (unsigned)((nb + G - 1) / G));
+        if (h->tv_form == RAG_TOKVEC_MXFP8)
+            launch(tokvec_scan_kernel<RAG_TOKVEC_MXFP8>, grid, dim3(256), 0, st, q_vecs, q_off, h->tv8.get(), h->tv_off.get(), n_docs, vis, qt.dev,
+                   tenant, q0, nb, G, h->tv_dim, plane);
+        else
+            launch(tokvec_scan_kernel<RAG_TOKVEC_FP16>, grid, dim3(256), 0, st, q_vecs, q_off, h->tv.get(), h->tv_off.get(), n_docs, vis, qt.dev,
+                   tenant, q0, nb, G, h->tv_dim, plane);
+        launch(tokvec_scan_select_kernel, dim3((unsigned)nb), dim3(256), 0, st, plane, n_docs, pool, rows_out + (size_t)q0 * pool);
+    }
+    return launch_status(h);
 }
 
 int tokvec_rerank_host(rag_ctx* h, const float* q_vecs, const int64_t* q_off, const int32_t* cand_rows, int Q, int pool, int k, int64_t* ids_out,

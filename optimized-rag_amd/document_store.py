@@ -551,9 +551,15 @@ class GpuDocumentIndex:
         """Retrieve `pool` candidates - mode "dense": what `search` ranks by; "dense+sparse": reciprocal rank fusion with the
         learned-sparse list, as search_lexical - and rerank them by MaxSim of the query's token vectors against the rows' resident
         ones (rag_tokvec_rerank_*). The query goes through ONE encode_multi forward. Result dicts are `search`'s (without
-        embeddings) plus `colbert_score`, which `score` equals. Never raises: an error (no store, a stale one, a missing head) is
+        embeddings) plus `colbert_score`, which `score` equals. mode "maxsim" has no candidate stage: every row the agent may see
+        is scored by MaxSim on the device (RagEngine.tokvec_search_dev) and the best `top_k` are returned - retrieval by MaxSim, for
+        a passage that neither the pooled vector nor the lexical weights would bring into the pool. Never raises: an error (no store, a stale one, a missing head) is
         logged and answered with `search`."""
         try:
+            if mode == "maxsim":
+                enc = self.embeddings.encode_multi([query], return_dense=False, return_sparse=False, return_colbert_vecs=True)
+                with self._lock:
+                    return self._search_maxsim_locked(agent_id, enc, top_k, int(pool))
             if mode not in ("dense", "dense+sparse"):
                 raise ValueError(f"unknown mode {mode!r}")
             fused = mode == "dense+sparse"
@@ -587,6 +593,25 @@ class GpuDocumentIndex:
         _, rows, scores, _ = self.engine.tokvec_rerank(qv, np.array([0, qv.shape[0]], dtype=np.int64), np.asarray(cand, dtype=np.int32), k)
         res = []
         for r, s in zip(rows[0], scores[0]):
+            if r < 0:
+                continue
+            row = self.rows[int(r)]
+            res.append({"content": row.get("content", ""), "filename": row.get("filename"), "file_type": row.get("file_type"),
+                        "score": float(s), "colbert_score": float(s), "metadata": row.get("metadata") or {}})
+        return res
+
+    def _search_maxsim_locked(self, agent_id, enc, top_k, pool):
+        if agent_id is not None and str(agent_id) not in self._tenant_id:
+            return []
+        tenant = -1 if agent_id is None else self._tenant_id[str(agent_id)]
+        pool = max(1, min(256, max(pool, top_k)))
+        k = min(int(top_k), pool)
+        qv = np.ascontiguousarray(enc["colbert_vecs"][0], dtype=np.float32)
+        ids, scores, _ = self.engine.tokvec_search_dev(self._to_device(qv), self._to_device(np.array([0, qv.shape[0]], dtype=np.int64)), k,
+                                                       pool=pool, tenant=tenant)
+        ids, scores = self._to_host(ids, scores)
+        res = []
+        for r, s in zip(self._rows_of_ids(ids)[0], scores[0]):
             if r < 0:
                 continue
             row = self.rows[int(r)]

@@ -540,6 +540,37 @@ class ShardedM3Index(ShardedDenseIndex):
         return self.search_m3(q_emb, term_ptr, terms, weights, q_vecs, q_off, pool, k, mode=0 if term_ptr is None else 1, w=(0.0, 0.0, 1.0),
                               rrf_k=rrf_k, tenant=tenant)
 
+    def local_maxsim(self, q_vecs, q_off, k, tenant=-1):
+        """This rank's half of search_maxsim: [2, Q, k] int64 = the ids | float64 score bits of the local exhaustive MaxSim search
+        (RagEngine.tokvec_search_dev at pool = k)."""
+        if not hasattr(self, "_explicit"):
+            raise ValueError("search_maxsim: load_shard first (ids must be one id >= 0 per row, strictly ascending on the shard)")
+        send, _, _, _, send_ids, send_sc, _ = self._buffers(q_off.shape[0] - 1, k, q_vecs.device)
+        ids, sc, _ = self.engine.tokvec_search_dev(q_vecs, q_off, k, pool=k, tenant=tenant)
+        send_ids.copy_(ids)
+        send_sc.copy_(sc)
+        return send
+
+    def merge_maxsim(self, recv):
+        """recv [world, 2, Q, k]: every rank's local_maxsim() -> (ids [Q, k] int64, scores [Q, k] float64)."""
+        _, _, Q, k = recv.shape
+        _, _, out_ids, out_scores, _, _, _ = self._buffers(Q, k, recv.device)
+        self.engine.merge_topk_dev(recv, recv.view(torch.float64)[:, 1], out_ids, out_scores, n_lists=self.world, list_stride=2 * Q * k)
+        return out_ids, out_scores
+
+    def search_maxsim(self, q_vecs, q_off, k, tenant=-1):
+        """The exhaustive MaxSim search over row shards: the local search at k, one gather, rag_merge_topk_dev. A pair's score is a
+        function of its own rows and needs no global statistic, so the merged list is the unsharded one - score desc, lower id
+        first on ties - wherever id order is row order: implicit ids, or explicit ids ascending with the rows, which is all that
+        load_shard and insert_rows accept (ValueError otherwise). Returns (ids [Q, k] int64, scores [Q, k] float64), identical
+        on every rank."""
+        send = self.local_maxsim(q_vecs, q_off, k, tenant=tenant)
+        if self.world == 1:
+            return send[0], send[1].view(torch.float64)
+        recv = self._buffers(q_off.shape[0] - 1, k, q_vecs.device)[1]
+        _gather(recv, send, self.group, self.engine)
+        return self.merge_maxsim(recv)
+
     def search_lexical(self, term_ptr, terms, weights, k, tenant=-1):
         """The learned-sparse top-k alone: local rag_sparse_topk_dev, one gather, rag_merge_topk_dev (raw scores need no global
         statistic). Returns (ids [Q, k] int64, scores [Q, k] float64), score desc, lower id first on ties."""
